@@ -7,10 +7,18 @@ update) on a 4096 x 4096 single level with 64^2 boxes, SHMIP-A synthetic inputs
 (SURVEY.md 8d "K-bench").  N > 1: weak scaling, every rank holds a 4096 x 4096 strip of
 a 4096 x (4096 N) level, strips coupled by halo exchange over RCCL.
 
-Prints ONE JSON line (rank 0).  `value` = V-cycles/s of the whole job; the GSRB
-cell-update rate and the roofline of the dominant kernel (the GSRB sweep at depth 0,
-72 algorithmic bytes per cell per sweep) ride along, plus the CPU baseline (the oracle's
-un-fused box-by-box restatement of the reference path, timed on this host's cores).
+Prints ONE JSON line (rank 0).  `value` = V-cycles/s of the whole job, `ms_per_step` = the
+milliseconds of one timed V-cycle.  A plain run sets up, warms up, times --steps V-cycles
+and prints the line.  --full adds everything else: the residual before and after, the
+roofline of the dominant kernel (the GSRB sweep at depth 0, 72 algorithmic bytes per cell
+per sweep, from a profiled pass of its own after the timed steps), the side configurations
+with their regression guard, the converged solve, and the CPU baseline (the oracle's
+un-fused box-by-box restatement of the reference path, timed on this host's cores) with
+the parity check at the bench size.
+
+--dump-outputs DIR writes the head the last timed V-cycle left (what a caller of the
+V-cycle reads back) as DIR/phi.npy, float64; a level larger than DUMP_SAMPLE cells is
+written as a fixed seeded sample of its cells (N > 1: DIR/phi_rank<r>.npy per rank).
 """
 import argparse
 import json
@@ -28,6 +36,8 @@ PMC_FILE = "r04_pmc_traffic_gsrb.json"   # HBM bytes per launch of the depth-0 k
 PMC_VCYCLE_FILE = "r04_pmc_traffic_vcycle.json"   # HBM bytes of ONE whole V-cycle, every kernel (tools/pmc_vcycle.sh + tools/make_traffic_json.py --vcycle)
 FLOOR_FILE = "r04_other_configs_floor.json"       # ms of the smaller configurations this build is held to (regression guard)
 LX = 1.0e5                     # width of the synthetic domain in metres (SHMIP-A: 100 km)
+DUMP_SAMPLE = 1 << 22          # --dump-outputs: at most this many cells of the head (float64: 32 MB), over all ranks
+DUMP_SEED = 4096               # --dump-outputs: seed of the sampled cell indices (the same cells on every run)
 
 
 def main():
@@ -36,13 +46,22 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--cells", dest="n", type=int, default=4096, help="cells per side of one rank strip")
-    ap.add_argument("--no-cpu", action="store_true", help="skip the CPU baseline leg")
-    ap.add_argument("--sweeps-only", type=int, default=0, help="also time this many bare GSRB sweeps")
-    ap.add_argument("--no-side", action="store_true", help="skip the side figures of the smaller BASELINE configurations")
-    ap.add_argument("--no-guard", action="store_true", help="report a configuration slower than its committed floor without failing")
+    ap.add_argument("--full", action="store_true",
+                    help="also every figure besides the headline: residuals, roofline (a profiled pass of its own), side configurations "
+                         "and their regression guard, converged solve, CPU baseline and parity at the bench size")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the head the last timed V-cycle left to DIR/phi.npy (float64; a fixed seeded sample on large levels)")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip the CPU baseline leg")
+    ap.add_argument("--sweeps-only", type=int, default=0, help="with --full: also time this many bare GSRB sweeps")
+    ap.add_argument("--no-side", action="store_true", help="with --full: skip the side figures of the smaller BASELINE configurations")
+    ap.add_argument("--no-guard", action="store_true", help="with --full: report a configuration slower than its committed floor without failing")
     ap.add_argument("--scaling", choices=("weak", "strong"), default="weak",
                     help="weak: every rank holds cells x cells; strong: the level of cells x cells is cut into --gpus row strips")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.sweeps_only and not args.full:
+        ap.error("--sweeps-only is one of the --full figures")
 
     if "RANK" not in os.environ and args.gpus > 1:
         sys.exit(spawn_ranks(args))                     # plain `python bench.py --gpus N`: this process starts the N ranks itself
@@ -52,7 +71,6 @@ def main():
     if world != args.gpus:
         sys.exit("bench.py: WORLD_SIZE = %d but --gpus %d" % (world, args.gpus))
 
-    import numpy as np
     from suhmo_amd import capi, level, synthetic as sy
 
     n = args.n
@@ -91,11 +109,12 @@ def main():
             torch.cuda.synchronize()
             dist.barrier()
 
-    G.residual(); res_before = G.norm(level.F_RES, 0)     # max norm over all ranks (outside the timed region)
+    res_before = None
+    if args.full:
+        G.residual(); res_before = G.norm(level.F_RES, 0)     # max norm over all ranks (outside the timed region)
     for _ in range(args.warmup):
         G.vcycle(sp)
     sync()
-    G.profile(True)
     msgs0 = G.rccl_exchanges() if world > 1 else 0
     agg0 = G.get_option("agg_gathers") if world > 1 else 0
     t0 = time.perf_counter()
@@ -104,16 +123,15 @@ def main():
     sync()
     t1 = time.perf_counter()
     msgs = (G.rccl_exchanges() - msgs0) / args.steps if world > 1 else 0.0
+    aggs = (G.get_option("agg_gathers") - agg0) / args.steps if world > 1 else None
     elapsed = t1 - t0
     if dist is not None:
         import torch
         t = torch.tensor([elapsed], device="cuda")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
-    G.residual(); res_after = G.norm(level.F_RES, 0)
-    gsrb_ms, gsrb_launches, gsrb_cells = G.profile_read()
-    rst_ms, rst_launches, rst_cells = G.profile_read(restricting=True)
-    G.profile(False)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, G, level, rank, world)
 
     sweeps_depth0 = 2 * sp["num_smooth"]
     cells = n * rows                                    # cells of this rank's strip
@@ -123,8 +141,74 @@ def main():
     ndepth = G.ndepth
     updates_per_vcycle = sum((cells >> (2 * d)) * (sp["num_bottom"] if d == ndepth - 1 else sweeps_depth0)
                              for d in range(ndepth))
-    # profile_read: device time over all depth-0 relax launches in the timed region and the
-    # cell-updates they performed (a K-sweep fused launch counts K sweeps)
+    extra, guard = {}, None
+    if args.full:
+        extra, guard = full_figures(args, sy, level, G, f, sp, sync, n, rows, cells, ms_per_step, world, rank, res_before)
+
+    if rank == 0:
+        out = {
+            "metric": "multigrid V-cycles/s (FAS head solve) + GSRB cell-updates/s; achieved HBM GB/s vs peak",
+            # whole-job aggregate: a unit is one V-cycle over one GPU's batch of n x n cells; a step runs one on every GPU
+            # (weak scaling: the level is world x as large), so value = world x steps / time
+            "value": vps * (1 if strong else world), "unit": "V-cycles/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+            "ms_per_step": ms_per_step, "higher_is_better": True, "scaling": args.scaling, "vs_baseline": None,
+            "dtype": "f64", "data": "synthetic", "full": args.full,
+            "config": {"workload": "SHMIP-A head solve, %dx%d cells per GPU (square cells of %.1f m), single AMR level, 64x64 boxes, "
+                                   "%d MG depths, 4+4 GSRB sweeps per depth, %d bottom (BASELINE north_star: 4096^2 single-level)"
+                                   % (n, rows, LX / n, ndepth, sp["num_bottom"]),
+                       "global_cells": [n, ny_global], "partition": "row strips, 1 per GPU" if world > 1 else "none",
+                       # N > 1: the halo transport in use and the number of ranks its communicator reports (ncclCommCount), so that N can be verified
+                       "transport": transport_name(G) if world > 1 else None,
+                       "transport_probe": getattr(G, "_ipc_probe", None) if world > 1 else None,
+                       "ranks_in_communicator": int(capi.lib().suhmo_level_rccl_comm_count(G.h)) if world > 1 else None,
+                       "unit_of_value": "V-cycles over %dx%d cells (%s; the level of %dx%d cells completes %.4g V-cycles/s)"
+                                        % (n, n, "the whole level, cut into strips" if strong else "one per GPU per step", n, ny_global, vps),
+                       "halo_message_groups_per_vcycle_per_rank": msgs if world > 1 else None,
+                       # rank strips: multigrid depths from this one on run agglomerated on a whole-level copy (0 = none; suhmo_agg.hip),
+                       # fed by all-gathers that are counted among the message groups above
+                       "agglomerated_from_depth": int(capi.lib().suhmo_level_agglomerated_depth(G.h)) if world > 1 else None,
+                       "allgathers_per_vcycle_per_rank": aggs},
+            "gsrb_cell_updates_per_s": updates_per_vcycle * vps * world,   # per-rank strip updates x ranks (strong and weak alike)
+        }
+        out.update(extra)
+        print(json.dumps(out))
+    if dist is not None:
+        dist.destroy_process_group()
+    if guard is not None and not guard["ok"] and not args.no_guard:
+        sys.exit("bench.py: regression guard: %s" % "; ".join(guard["slower_than_floor"]))
+
+
+def dump_outputs(path, G, level, rank, world):
+    """--dump-outputs: the head the last timed V-cycle left, as a caller of the V-cycle reads it back (float64).  A strip of more cells than
+    its share of DUMP_SAMPLE is written as that many of its cells, drawn without replacement by a generator seeded with DUMP_SEED and the
+    rank, in ascending row-major order: the same cells on every run with the same arguments."""
+    import numpy as np
+    phi = G.get(level.F_PHI)
+    k = DUMP_SAMPLE // world
+    if phi.size > k:
+        idx = np.sort(np.random.default_rng([DUMP_SEED, rank]).choice(phi.size, k, replace=False))
+        phi = phi.reshape(-1)[idx]
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "phi.npy" if world == 1 else "phi_rank%d.npy" % rank), phi)
+
+
+def full_figures(args, sy, level, G, f, sp, sync, n, rows, cells, ms_per_step, world, rank, res_before):
+    """--full: every figure of the line besides the headline, all measured after the timed steps.  Returns (figures, regression guard)."""
+    import numpy as np
+    extra = {}
+    G.residual(); res_after = G.norm(level.F_RES, 0)
+    extra["residual_max_norm"] = {"before_warmup": res_before, "after_timed_cycles": res_after, "cycles": args.warmup + args.steps}
+
+    # the depth-0 relaxation launches timed by HIP events, in a pass of its own of as many V-cycles as the timed steps (the events stay out of
+    # those): device time over all depth-0 relax launches and the cell-updates they performed (a K-sweep fused launch counts K sweeps)
+    sync()
+    G.profile(True)
+    for _ in range(args.steps):
+        G.vcycle(sp)
+    sync()
+    gsrb_ms, gsrb_launches, gsrb_cells = G.profile_read()
+    rst_ms, rst_launches, rst_cells = G.profile_read(restricting=True)
+    G.profile(False)
     sweeps_timed = gsrb_cells / cells
     sweep_ms = gsrb_ms / max(sweeps_timed, 1)
     achieved = BYTES_PER_CELL_SWEEP * cells / (sweep_ms * 1e-3) / 1e9 if gsrb_launches else 0.0
@@ -146,7 +230,6 @@ def main():
     launch_ms = gsrb_ms / max(gsrb_launches, 1)
     alg_bytes_launch = BYTES_PER_CELL_SWEEP * cells * sweeps_timed / max(gsrb_launches, 1)
 
-    extra = {}
     if rst_launches:
         # the launch that ends the pre-smoothing also restricts: 2 sweeps (144 B/cell) + RESTRICTRESVCNL2D/RESTRICTVCNL (76 B/cell)
         rl = rst_ms / rst_launches
@@ -209,33 +292,8 @@ def main():
                 sys.exit("bench.py: the HIP V-cycles differ from the CPU restatement at %dx%d: max |d| = %g" % (n, n, float(np.max(np.abs(phi_gpu - phi_cpu)))))
             del phi_gpu, phi_cpu
 
-    if rank == 0:
-        out = {
-            "metric": "multigrid V-cycles/s (FAS head solve) + GSRB cell-updates/s; achieved HBM GB/s vs peak",
-            # whole-job aggregate: a unit is one V-cycle over one GPU's batch of n x n cells; a step runs one on every GPU
-            # (weak scaling: the level is world x as large), so value = world x steps / time
-            "value": vps * (1 if strong else world), "unit": "V-cycles/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": ms_per_step, "higher_is_better": True, "scaling": args.scaling, "vs_baseline": None,
-            "dtype": "f64", "data": "synthetic",
-            "config": {"workload": "SHMIP-A head solve, %dx%d cells per GPU (square cells of %.1f m), single AMR level, 64x64 boxes, "
-                                   "%d MG depths, 4+4 GSRB sweeps per depth, %d bottom (BASELINE north_star: 4096^2 single-level)"
-                                   % (n, rows, LX / n, ndepth, sp["num_bottom"]),
-                       "global_cells": [n, ny_global], "partition": "row strips, 1 per GPU" if world > 1 else "none",
-                       # N > 1: the halo transport in use and the number of ranks its communicator reports (ncclCommCount), so that N can be verified
-                       "transport": transport_name(G) if world > 1 else None,
-                       "transport_probe": getattr(G, "_ipc_probe", None) if world > 1 else None,
-                       "ranks_in_communicator": int(capi.lib().suhmo_level_rccl_comm_count(G.h)) if world > 1 else None,
-                       "unit_of_value": "V-cycles over %dx%d cells (%s; the level of %dx%d cells completes %.4g V-cycles/s)"
-                                        % (n, n, "the whole level, cut into strips" if strong else "one per GPU per step", n, ny_global, vps),
-                       "halo_message_groups_per_vcycle_per_rank": msgs if world > 1 else None,
-                       # rank strips: multigrid depths from this one on run agglomerated on a whole-level copy (0 = none; suhmo_agg.hip),
-                       # fed by all-gathers that are counted among the message groups above
-                       "agglomerated_from_depth": int(capi.lib().suhmo_level_agglomerated_depth(G.h)) if world > 1 else None,
-                       "allgathers_per_vcycle_per_rank": (G.get_option("agg_gathers") - agg0) / args.steps if world > 1 else None},
-            "residual_max_norm": {"before_warmup": res_before, "after_timed_cycles": res_after, "cycles": args.warmup + args.steps},
-            "gsrb_cell_updates_per_s": updates_per_vcycle * vps * world,   # per-rank strip updates x ranks (strong and weak alike)
-            "gsrb_depth0_cell_updates_per_s_kernel": cells / (sweep_ms * 1e-3) * world if gsrb_launches else None,
-            "roofline": {"bound": "hbm", "kernel": "GSRB sweep (red+black) at depth 0", "achieved": achieved,
+    extra["gsrb_depth0_cell_updates_per_s_kernel"] = cells / (sweep_ms * 1e-3) * world if gsrb_launches else None
+    extra["roofline"] = {"bound": "hbm", "kernel": "GSRB sweep (red+black) at depth 0", "achieved": achieved,
                          "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
                          "frac_is": "effective (temporal blocking: K = 2 sweeps per pass over HBM); HBM utilisation = physical_frac",
                          "frac_note": "algorithmic bytes (72 B per cell per sweep) / time / peak, SURVEY 8(d); the kernel does K = 2 sweeps per "
@@ -250,17 +308,12 @@ def main():
                          "vcycle_physical_frac": (vtraffic / (ms_per_step * 1e-3) / 1e9 / HBM_PEAK_GBS) if vtraffic else None,
                          "algorithmic_bytes_per_launch": alg_bytes_launch, "avg_launch_ms": launch_ms,
                          "algorithmic_bytes_per_cell_sweep": BYTES_PER_CELL_SWEEP,
-                         "avg_sweep_ms": sweep_ms, "sweeps_timed": sweeps_timed, "launches_timed": gsrb_launches},
-            "cpu_baseline": cpu,
-            # head after the cpu_baseline's V-cycles: HIP level == CPU restatement, np.array_equal, at this very size (None: no CPU leg)
-            "parity_at_bench_size": parity,
-        }
-        out.update(extra)
-        print(json.dumps(out))
-    if dist is not None:
-        dist.destroy_process_group()
-    if guard is not None and not guard["ok"] and not args.no_guard:
-        sys.exit("bench.py: regression guard: %s" % "; ".join(guard["slower_than_floor"]))
+                         "avg_sweep_ms": sweep_ms, "sweeps_timed": sweeps_timed, "launches_timed": gsrb_launches,
+                         "launches_timed_in": "a profiled pass of as many V-cycles as the timed steps, after them"}
+    extra["cpu_baseline"] = cpu
+    # head after the cpu_baseline's V-cycles: HIP level == CPU restatement, np.array_equal, at this very size (None: no CPU leg)
+    extra["parity_at_bench_size"] = parity
+    return extra, guard
 
 
 def transport_name(G):

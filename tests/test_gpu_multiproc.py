@@ -19,7 +19,7 @@ def test_bench_starts_its_own_ranks(scaling):
     env = dict(os.environ, SUHMO_DIST_BACKEND="gloo", OMP_NUM_THREADS="1", GLOO_SOCKET_IFNAME="lo")   # (the box's hostname may not resolve)
     env.pop("RANK", None); env.pop("WORLD_SIZE", None); env.pop("LOCAL_RANK", None)
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--cells", "512", "--steps", "3", "--warmup", "1",
-                        "--no-cpu", "--no-side", "--scaling", scaling], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
+                        "--full", "--no-cpu", "--no-side", "--scaling", scaling], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
     assert p.returncode == 0, p.stderr.decode()[-3000:]
     line = [l for l in p.stdout.decode().splitlines() if l.startswith("{")][-1]
     out = json.loads(line)
