@@ -112,6 +112,13 @@ int suhmo_level_num_depths(const suhmo_level_t *L);
  * agg_min_cells, fas_rhs_fused, resid_in_relax (1: the residual the solve loops evaluate after every V-cycle is left behind by the cycle's
  * last launch where the streaming kernel runs depth 0; 0: always a pass of its own).  Read-only counters: overlapped_launches, agg_gathers,
  * rhs_in_streaming_launches, rhs_in_tile_launches, residual_in_relax_launches.
+ * Not a kernel-selection knob (it changes the bits): bottom_solver (default 0: the cycle's bottom is its numBottom relaxes; 1: followed by
+ * Chombo's RelaxSolver as the reference configures it, src/AmrHydro.cpp:623,628,726,733-735 -- up to 40 rounds of relax(2), ended by an l2
+ * residual below 1e-6 x its first value or reduced by less than 10 %).  It reaches the level's agglomerated copy and its gap-height operator;
+ * suhmo_hier_set_option forwards it to level 0 of a hierarchy and to its gap-height hierarchy.  bottom_one_launch_max_cells (default 16384,
+ * env SUHMO_BOTTOM_ONE_LAUNCH_MAX_CELLS; 0 = never): whole-level bottoms of up to this many cells (at most 128 x 128) run the loop in one
+ * launch, larger ones, rank strips and AMR patches as a host loop of launches with an 8-byte read-back per iteration (their V-cycles are
+ * then not replayed as graphs).  Read-only counters: bottom_solver_iterations, bottom_solves_one_launch, bottom_solves_host_loop.
  * On rank strips every rank must make the same choices (suhmo_level_attach_rccl checks). */
 int suhmo_level_set_option(suhmo_level_t *L, const char *key, long value);
 int suhmo_level_get_option(const suhmo_level_t *L, const char *key, long *value);

@@ -209,6 +209,11 @@ struct suhmo_level {
     int tile_restrict;          // the tile kernel's last pre-smoothing launch also restricts: 0 never (a separate kernel restricts: faster on one GPU and
                                 // on a rank strip alike, profiles/r02_h_tile_restrict_ab.txt), 1 always, 2 on rank strips only (env SUHMO_TILE_RESTRICT, default 0)
     int tile_order;             // workgroup -> tile map of the tile kernel: 0 as launched, 1 a contiguous run of tiles per XCD, 2 the same in panels of 8 tile rows (env SUHMO_TILE_ORDER)
+    // bottom solver (suhmo_bottom.hip): 1 = Chombo's RelaxSolver after the bottom relaxes of every cycle (option bottom_solver, default 0);
+    // bottoms of up to bottom_one_launch_max_cells cells that fit the LDS run it in one launch (option / env SUHMO_BOTTOM_ONE_LAUNCH_MAX_CELLS,
+    // 0 = always the host loop); bottom_ctr: device counters (iterations, one-launch solves); the host loop counts on the host
+    int bottom_solver; long bottom_one_launch_max_cells;
+    unsigned long long *bottom_ctr; long bottom_host_iters, bottom_host_solves;
     int gsrb_tile, tile_t, tile_s;      // cache-resident depths: S sweeps per launch on LDS tiles (env SUHMO_GSRB_TILE, default 1); tile edge 16 / 32
                                 // (env SUHMO_TILE_T, 0 = by size)
 };
@@ -277,4 +282,9 @@ int suhmo_agg_gather_faces(suhmo_level *L, int nd, hipStream_t st);
 int suhmo_agg_gather_state(suhmo_level *L, hipStream_t st);
 int suhmo_agg_scatter(suhmo_level *L, hipStream_t st);
 int suhmo_exchange_list(suhmo_level *L, int depth, const int *fields, int n, hipStream_t st);   // LevelData::exchange across rank boundaries
+// suhmo_bottom.hip: the bottom solver of the FAS cycle
+bool suhmo_bottom_one_launch(const suhmo_level *L, int dep);
+int suhmo_bottom_configure(suhmo_level *L, int solver, long one_launch_max_cells);
+long suhmo_bottom_counter(const suhmo_level *L, int which);
+int suhmo_bottom_solve(suhmo_level *L, int dep, int tail, hipStream_t st);
 static inline int suhmo_halo_rows(const DV &v) { return v.gy < v.ny ? v.gy : v.ny; }

@@ -53,7 +53,14 @@ static int fas_cycle(suhmo_level *L, int dep, const suhmo_solver_params_t *sp, i
     int rc;
     const int S = sp->num_smooth;
     const int tail_post = dep == 0 ? 2 : (rows_after_prolong(dep - 1, S) + 1) / 2;
-    if (dep == nd - 1) return relax(L, dep, sp->num_bottom, tail_post, s, dep == 0);   // bottom relaxes
+    if (dep == nd - 1) {
+        if (!L->bottom_solver) return relax(L, dep, sp->num_bottom, tail_post, s, dep == 0);   // bottom relaxes
+        // bottom relaxes, then RelaxSolver (suhmo_bottom.hip); the oracle's loop ends on a residual evaluation, whose ghost fill is
+        // the inhomogeneous one: that is what a depth-0 bottom leaves in the ghost ring
+        if ((rc = relax(L, dep, sp->num_bottom, tail_post, s))) return rc;
+        if ((rc = suhmo_bottom_solve(L, dep, tail_post, (hipStream_t)s))) return rc;
+        return dep == 0 ? suhmo_level_fill_ghosts(L, dep, SUHMO_F_PHI, 0, s) : 0;
+    }
     Depth &C = L->d[dep + 1];
     int restricted = 0;
     if ((rc = relax(L, dep, S, rows_after_prolong(dep, S), s, false, &restricted))) return rc;   // pre-smooth (the restriction reads 1 halo
@@ -205,7 +212,9 @@ extern "C" int suhmo_level_vcycle(suhmo_level_t *L, const suhmo_solver_params_t 
     int nd = eff_depths(L, sp);
     const Depth &D = L->d[0];
     const bool ext = D.v.ext[0] || D.v.ext[1];
-    if (L->graph_max_cells > 0 && !L->ex && !ext && !L->prof_on && (long)D.v.nx * D.v.ny <= L->graph_max_cells) {
+    // (a bottom solved by the host loop decides on the host after every iteration: not capturable)
+    const bool host_bottom = L->bottom_solver && !suhmo_bottom_one_launch(L, nd - 1);
+    if (L->graph_max_cells > 0 && !L->ex && !ext && !L->prof_on && !host_bottom && (long)D.v.nx * D.v.ny <= L->graph_max_cells) {
         bool done = false;
         int rc = vcycle_graph(L, sp, nd, s, done);
         if (rc || done) return rc;

@@ -2041,6 +2041,13 @@ int suhmo_hier_gap_(suhmo_hier *H, const suhmo_model_params_t *mp, double dt, su
         for (int l = 0; l < H->nlev; l++)
             for (suhmo_level *L : H->gap->lev[l].box) if (!L->stub && (rc = suhmo_level_set_value(L, 0, SUHMO_F_ACOEF, 1.0, nullptr))) return rc;   // aCoeff_GH :1820-1828
     }
+    {   // the bottom solver of the head solve's hierarchy
+        const suhmo_level *B = base_of(H);
+        suhmo_level *G0 = H->gap->lev[0].box[0];
+        if (G0->bottom_solver != B->bottom_solver || G0->bottom_one_launch_max_cells != B->bottom_one_launch_max_cells) {
+            int rc = suhmo_bottom_configure(G0, B->bottom_solver, B->bottom_one_launch_max_cells); if (rc) return rc;
+        }
+    }
     *gap = H->gap;
     return 0;
 }
@@ -2048,6 +2055,11 @@ int suhmo_hier_gap_(suhmo_hier *H, const suhmo_model_params_t *mp, double dt, su
 extern "C" int suhmo_hier_set_option(suhmo_hier_t *H, const char *key, long value)
 {
     ARG(H && key);
+    if (!strcmp(key, "bottom_solver") || !strcmp(key, "bottom_one_launch_max_cells")) {   // the bottom of every V-cycle is level 0's
+        int rc = suhmo_level_set_option(base_of(H), key, value);
+        if (rc == 0 && H->gap) rc = suhmo_hier_set_option(H->gap, key, value);
+        return rc;
+    }
     if (!strcmp(key, "incremental_residual")) {      // 0: every composite residual / coarse gradient over the whole of level 0 (A/B runs, tests)
         H->incremental = value != 0;
         H->base_res_seen = 0;
@@ -2071,6 +2083,13 @@ extern "C" int suhmo_hier_get_option(const suhmo_hier_t *H, const char *key, lon
 {
     ARG(H && key && value);
     if (!strcmp(key, "push_ghosts")) { *value = H->push_ghosts; return 0; }
+    if (!strncmp(key, "bottom_", 7)) {                    // bottom_solver, bottom_one_launch_max_cells, the bottom counters (with the gap solve's)
+        int rc = suhmo_level_get_option(base_of(const_cast<suhmo_hier *>(H)), key, value);
+        long g = 0;
+        if (rc == 0 && H->gap && (!strcmp(key, "bottom_solver_iterations") || !strncmp(key, "bottom_solves_", 14))
+            && (rc = suhmo_hier_get_option(H->gap, key, &g)) == 0) *value += g;
+        return rc;
+    }
     if (!strcmp(key, "fused_prolong")) { *value = H->fused_prolong; return 0; }
     if (!strcmp(key, "merged_launches")) { *value = H->merged_launches; return 0; }
     if (!strcmp(key, "box_sweeps")) { *value = H->box_sweeps; return 0; }

@@ -179,6 +179,8 @@ int suhmo_level_create_(suhmo_level_t **out, const suhmo_level_desc_t *desc, boo
     L->graph_max_cells = 1500000; L->gstream = nullptr; memset(L->vgraph_seen, 0, sizeof(L->vgraph_seen));
     L->fused_min_cells = 1000000;
     L->skip_mask = 1; L->poll_readback = 1;
+    L->bottom_solver = 0; L->bottom_one_launch_max_cells = 16384;    // (every bottom the one-launch kernel's LDS holds: up to 128 x 128)
+    L->bottom_ctr = nullptr; L->bottom_host_iters = L->bottom_host_solves = 0;
     // ... and ONE place where the environment may override them, read when a level is created: the A/B runs DESIGN.md quotes and the tests that
     // force a kernel onto a small level.  Nothing else of a level is taken from the environment.
     {
@@ -194,7 +196,8 @@ int suhmo_level_create_(suhmo_level_t **out, const suhmo_level_desc_t *desc, boo
             {"SUHMO_FUSED_RESTRICT", &suhmo_level::fused_restrict}, {"SUHMO_SKIP_MASK", &suhmo_level::skip_mask}, {"SUHMO_POLL_READBACK", &suhmo_level::poll_readback}};
         static const LongKnob longs[] = {
             {"SUHMO_AGG_MIN_CELLS", &suhmo_level::agg_min_cells}, {"SUHMO_TILE_MAX_CELLS", &suhmo_level::tile_max_cells},
-            {"SUHMO_GRAPH_MAX_CELLS", &suhmo_level::graph_max_cells}, {"SUHMO_FUSED_MIN_CELLS", &suhmo_level::fused_min_cells}};
+            {"SUHMO_GRAPH_MAX_CELLS", &suhmo_level::graph_max_cells}, {"SUHMO_FUSED_MIN_CELLS", &suhmo_level::fused_min_cells},
+            {"SUHMO_BOTTOM_ONE_LAUNCH_MAX_CELLS", &suhmo_level::bottom_one_launch_max_cells}};
         for (const IntKnob &k : ints) if (const char *e = getenv(k.env)) L->*(k.field) = atoi(e);
         for (const LongKnob &k : longs) if (const char *e = getenv(k.env)) L->*(k.field) = atol(e);
         L->fas_rhs_fused = L->fas_rhs_fused != 0;
@@ -290,6 +293,7 @@ extern "C" int suhmo_level_destroy(suhmo_level_t *L)
     for (auto &pe : L->prof) { (void)hipEventDestroy(pe.a); (void)hipEventDestroy(pe.b); }
     if (L->xstream) { (void)hipStreamDestroy(L->xstream); (void)hipEventDestroy(L->xev[0]); (void)hipEventDestroy(L->xev[1]); }
     if (L->scratch) (void)hipFree(L->scratch);
+    if (L->bottom_ctr) (void)hipFree(L->bottom_ctr);
     if (L->hscratch) (void)hipHostFree(L->hscratch);
     delete L;
     return 0;
@@ -348,6 +352,15 @@ static int *option_slot_int(suhmo_level *L, const char *key)
 extern "C" int suhmo_level_set_option(suhmo_level_t *L, const char *key, long value)
 {
     ARG(L && key);
+    // the bottom solver changes the bits (not a kernel-selection knob); it reaches the sub-levels that run this level's cycles
+    if (!strcmp(key, "bottom_solver")) {
+        if (value != 0 && value != 1) { suhmo_set_error("bottom_solver: 0 (bottom relaxes only) or 1 (RelaxSolver)"); return -1; }
+        return suhmo_bottom_configure(L, (int)value, L->bottom_one_launch_max_cells);
+    }
+    if (!strcmp(key, "bottom_one_launch_max_cells")) {
+        if (value < 0) { suhmo_set_error("bottom_one_launch_max_cells: >= 0"); return -1; }
+        return suhmo_bottom_configure(L, L->bottom_solver, value);
+    }
     if (long *p = option_slot_long(L, key)) {
         *p = value; suhmo_level_drop_graphs(L);
         if (!strcmp(key, "agg_min_cells")) return suhmo_agg_setup(L);     // (every rank of the partition must set the same value)
@@ -372,6 +385,11 @@ extern "C" int suhmo_level_get_option(const suhmo_level_t *L, const char *key, l
     if (!strcmp(key, "rhs_in_streaming_launches")) { *value = L->frhs_stream; return 0; }   // read-only counters (fas_rhs_in_relax)
     if (!strcmp(key, "rhs_in_tile_launches")) { *value = L->frhs_tile; return 0; }
     if (!strcmp(key, "residual_in_relax_launches")) { *value = L->resout_count; return 0; }
+    if (!strcmp(key, "bottom_solver")) { *value = L->bottom_solver; return 0; }
+    if (!strcmp(key, "bottom_one_launch_max_cells")) { *value = L->bottom_one_launch_max_cells; return 0; }
+    if (!strcmp(key, "bottom_solver_iterations")) { *value = suhmo_bottom_counter(L, 0); return 0; }    // read-only counters (bottom_solver)
+    if (!strcmp(key, "bottom_solves_one_launch")) { *value = suhmo_bottom_counter(L, 1); return 0; }
+    if (!strcmp(key, "bottom_solves_host_loop")) { *value = suhmo_bottom_counter(L, 2); return 0; }
     suhmo_set_error("unknown option '%s'", key);
     return -1;
 }

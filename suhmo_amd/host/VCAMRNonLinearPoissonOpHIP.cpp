@@ -436,6 +436,10 @@ void VCAMRNonLinearPoissonOpHIP::setAlphaAndBeta(const Real &a_alpha, const Real
     if (m_amrLevel == 0) { m_factory->m_desc.alpha = a_alpha; m_factory->m_desc.beta = a_beta; }
 }
 void VCAMRNonLinearPoissonOpHIP::setBC(const suhmo_bc_t &a_bc) { chk(suhmo_level_set_bc(h(), &a_bc), "setBC"); }
+void VCAMRNonLinearPoissonOpHIP::setBottomSolver(bool a_relaxSolver)
+{
+    chk(suhmo_level_set_option(h(), "bottom_solver", a_relaxSolver ? 1 : 0), "setBottomSolver");
+}
 void VCAMRNonLinearPoissonOpHIP::getFlux(FArrayBox &a_flux, const FArrayBox &a_data, const FluxBox &a_bCoef, const Box &a_facebox,
                                          int a_dir, int a_ref) const
 {
