@@ -436,7 +436,8 @@ int suhmo_hier_create(suhmo_hier_t **out, const suhmo_level_desc_t *base, int nl
  * launches (default: one workgroup per box); merged_launches = 0: a launch for either kind of ghost cell, for the gradient and its ghosts, for Re
  * and bCoef, per level for ghosts / operator / reflux / norm, a read-back per level's norm, the closing ghost fill and the leaving of a FAS problem on
  * their own (default 1: one launch each, several levels per launch where nothing orders them -- the same bits).  These can also be changed later
- * (suhmo_hier_set_option).
+ * (suhmo_hier_set_option; the gap-height hierarchy of suhmo_hier_timestep is created with the current values and follows every change).
+ * An unknown key is refused; shadow and partition_min_cells are fixed at creation.
  * partition_min_cells = n (rank strips; default 350000): when the largest level >= 1 holds at least n cells PER RANK the levels >= 1 are dealt to the ranks, the boxes
  * of a level in the order given cut into runs of about equal cell counts (the reference: LoadBalance(procIDs, grids),
  * src/AmrHydro.cpp:4283, 4929).  OWNER COMPUTES: every pass over such a level runs on the owner's boxes only and only they (plus mirrors

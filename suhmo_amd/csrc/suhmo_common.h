@@ -139,7 +139,7 @@ struct ProfEv { hipEvent_t a, b; long cells; int restricts; };   // restricts: t
 
 struct suhmo_level {
     int ndepth;
-    int stub;                   // geometry only: no canvas, no scratch (a box of a partitioned AMR level held by other ranks; suhmo_hier.hip)
+    int stub;                   // geometry only: no canvas, no scratch (a box of a partitioned AMR level held by other ranks; suhmo_hier_plan.hip)
     Depth d[SUHMO_MAXDEPTH];
     suhmo_level_desc_t desc;
     std::vector<int> boxes;     // nbox x 4, global indices, depth 0
@@ -230,12 +230,14 @@ struct SuhmoTimer { const char *name; double t0; int mode; explicit SuhmoTimer(c
 
 double *suhmo_field(suhmo_level *L, int depth, int field);   // lazily allocates
 int suhmo_level_create_(suhmo_level_t **out, const suhmo_level_desc_t *desc, bool stub);   // suhmo_level.hip
+// dst uses src's transport hooks (exchange, reductions, peer-direct arena): a gap-height handle and the level it solves for
+void suhmo_level_share_transport(suhmo_level *dst, const suhmo_level *src);   // suhmo_level.hip
 int suhmo_level_materialize_(suhmo_level *L);
 // Two canvases of a level trade places while its FAS problem runs (the level's own right-hand side is set aside): whatever way the
 // scope is left -- an exchange or all-gather hook failing in between included -- they trade back, so a caller that catches the
 // error still holds the problem it posed
 // every change of a field POINTER of any level (a field allocated on first use, phi canvases trading places) advances this count: tables of
-// pointers kept elsewhere (suhmo_hier.hip: the boxes of a level as one launch target) are compared again only after it moved
+// pointers kept elsewhere (suhmo_hier_fill.hip: the boxes of a level as one launch target) are compared again only after it moved
 void suhmo_fp_changed();
 unsigned long suhmo_fp_epoch();
 struct SwapGuard {

@@ -1,18 +1,7 @@
-// suhmo_hier.h -- what suhmo_step.hip needs from a hierarchy of box unions (suhmo_hier.hip)
+// suhmo_hier.h -- every box of a level of a hierarchy of box unions as one launch target, and the kernels of suhmo_gsrb.hip / suhmo_ops.hip
+// that launch over them (the hierarchy itself: suhmo_hier_int.h)
 #pragma once
 #include "suhmo_common.h"
-struct suhmo_hier;
-int suhmo_hier_nlev_(const suhmo_hier *H);
-const std::vector<suhmo_level *> &suhmo_hier_boxes_(suhmo_hier *H, int l);
-int suhmo_hier_device_(const suhmo_hier *H);
-int suhmo_hier_ff_(suhmo_hier *H, int l, int f0, int f1, bool corners, hipStream_t st);      // Copier::exchange between the boxes of a level
-int suhmo_hier_cf_(suhmo_hier *H, int l, int ff, int fc, hipStream_t st);                    // QuadCFInterp from level l-1
-int suhmo_hier_cf2_(suhmo_hier *H, int l, int ff0, int fc0, int ff1, int fc1, hipStream_t st);   // two fields over the same stencils, one launch
-int suhmo_hier_pwl_(suhmo_hier *H, int l, int ff, int fc, hipStream_t st);                   // PiecewiseLinearFillPatch from level l-1
-int suhmo_hier_avg_(suhmo_hier *H, int l, int ff, int fc, hipStream_t st);                   // CoarseAverage into level l-1
-// the hierarchy of SolveForGap_nl: the same boxes, alpha = 1, beta = dt diffFactor, Neumann-0 sides, no nonlinear term
-int suhmo_hier_gap_(suhmo_hier *H, const suhmo_model_params_t *mp, double dt, suhmo_hier **gap);
-
 // every box of a level in ONE launch (blockIdx.z = box): device tables of the boxes' views and field pointers
 constexpr int SUHMO_BOX_HALO = 8;    // cells around a box the plan `halo` of a level covers (k_gsrb_box_m advances through up to that many: 4 sweeps per launch)
 struct suhmo_multi { const DV *dv; const FP *fp; int nbox, maxnx, maxny; double *red; /* reduction scratch, 64 nbox + 16 doubles */
@@ -49,14 +38,3 @@ int suhmo_levels_apply(const suhmo_lvboxes &lv, const suhmo_phys_t &ph, bool has
 int suhmo_levels_norm_max_cover_partials(const suhmo_lvboxes &lv, int field, double *partial, int *np, hipStream_t st);
 int suhmo_level_norm_max_cover_partials(suhmo_level *L, int field, const double **partials, int *np, hipStream_t st);
 int suhmo_levels_grad_cc(const suhmo_lvboxes &lv, int hasMask, hipStream_t st);                              // suhmo_multi_grad_cc (merged form) of several levels
-int suhmo_hier_multi_(suhmo_hier *H, int l, hipStream_t st, suhmo_multi *m);       // l >= 1
-int suhmo_hier_ensure_(suhmo_hier *H, int l, int field);                            // allocate a field on every box of a level
-void suhmo_hier_invalidate_(suhmo_hier *H);                                         // an entry point outside suhmo_hier.hip: the caller may have loaded new data
-const double *suhmo_hier_base_cover_(suhmo_hier *H, DV *whole);
-// owner computes (levels >= 1 dealt to the ranks): is it on; the boxes of level l this rank owns (everything suhmo_hier_multi_ launches on);
-// MAX over the ranks of a value each computed on its own boxes; the all-gather of the hierarchy (device buffers, `count` doubles per rank)
-bool suhmo_hier_partitioned_(const suhmo_hier *H);
-void suhmo_hier_owned_(const suhmo_hier *H, int l, int *first, int *n);
-int suhmo_hier_allreduce_max_(suhmo_hier *H, double *v);
-int suhmo_hier_allgather_(suhmo_hier *H, const double *send, long count, double *recv, hipStream_t st);
-int suhmo_hier_world_(const suhmo_hier *H);                     // level 0 cut into rank strips: COVER of the WHOLE level and its view; else NULL

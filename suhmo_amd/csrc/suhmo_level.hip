@@ -407,6 +407,11 @@ extern "C" int suhmo_level_set_hooks(suhmo_level_t *L, suhmo_exchange_fn ex, suh
     L->ex = ex; L->ar = ar; L->ar2 = nullptr; L->ard = nullptr; L->user = user; L->ex_begin = nullptr; L->ex_end = nullptr;
     return 0;
 }
+void suhmo_level_share_transport(suhmo_level *dst, const suhmo_level *src)
+{
+    dst->ex = src->ex; dst->ar = src->ar; dst->ar2 = src->ar2; dst->ard = src->ard; dst->user = src->user;
+    dst->ex_begin = src->ex_begin; dst->ex_end = src->ex_end; dst->ipc = src->ipc;
+}
 extern "C" int suhmo_level_set_allgather(suhmo_level_t *L, suhmo_allgather_fn fn, void *user)
 {
     ARG(L);

@@ -216,7 +216,7 @@ int reduce_dev_hook(void *user, double *dev_values, int n, int op, suhmo_stream_
 }
 }  // namespace
 
-// all-gather of the coarse cells a hierarchy's level 1 reads of a level 0 cut into strips (suhmo_hier.hip), on the kernels' stream
+// all-gather of the coarse cells a hierarchy's level 1 reads of a level 0 cut into strips (suhmo_hier_fill.hip), on the kernels' stream
 int suhmo_rccl_allgather_hook(void *user, const double *send, long count, double *recv, suhmo_stream_t s)
 {
     Strip *S = (Strip *)user;

@@ -14,8 +14,10 @@
 // a field (b, mR, grad h, RHS halos for the redundant halo-row relaxation) the strip's exchange hook is called, the
 // Picard test is MAX all-reduced; the moulin integrals are evaluated redundantly over the whole domain (analytic
 // integrand, no data), so the result does not depend on the partition bit for bit.
-#include "suhmo_hier.h"
+#include "suhmo_hier_int.h"
 #include <cmath>
+
+using namespace hier;
 
 // Qw on x- and y-faces: B_ec, Re_ec by CellToEdge (half*(cell + lower cell)), grad h by NEWMACGRAD
 // with the physical BC applied on the fly, COMPUTEQW (src/AmrHydroF.ChF:137-150)
@@ -363,7 +365,7 @@ static int gap_level_prepare(suhmo_level *L, const suhmo_model_params_t *mp, dou
     if (G->bottom_solver != L->bottom_solver || G->bottom_one_launch_max_cells != L->bottom_one_launch_max_cells) {   // the same bottom solver
         int rc = suhmo_bottom_configure(G, L->bottom_solver, L->bottom_one_launch_max_cells); if (rc) return rc;
     }
-    G->ex = L->ex; G->ar = L->ar; G->ar2 = L->ar2; G->ard = L->ard; G->user = L->user; G->ex_begin = L->ex_begin; G->ex_end = L->ex_end; G->ipc = L->ipc;
+    suhmo_level_share_transport(G, L);
     if (G->ag != L->ag || G->ag_user != L->ag_user || G->agg_min_cells != L->agg_min_cells) {                // ... and the same agglomeration
         G->ag = L->ag; G->ag_user = L->ag_user; G->agg_min_cells = L->agg_min_cells;
         int rca = suhmo_agg_setup(G); if (rca) return rca;
@@ -651,25 +653,25 @@ struct LevT { suhmo_level *base; suhmo_multi m; };
 int lev_target(suhmo_hier *H, int l, hipStream_t st, LevT &t)
 {
     t.base = nullptr;
-    if (l == 0) { t.base = suhmo_hier_boxes_(H, 0)[0]; return 0; }
-    return suhmo_hier_multi_(H, l, st, &t.m);
+    if (l == 0) { t.base = H->lev[0].box[0]; return 0; }
+    return multi_of(H, l, st, t.m);
 }
 int hier_chain(suhmo_hier *H, int l, hipStream_t st)
 {
     int rc;
     LevT t;
     if ((rc = lev_target(H, l, st, t))) return rc;
-    const suhmo_phys_t &ph = suhmo_hier_boxes_(H, l)[0]->ph;
-    if ((rc = suhmo_hier_cf_(H, l, SUHMO_F_PHI, SUHMO_F_PHI, st))) return rc;                  // inside compGradientMAC
-    if ((rc = suhmo_hier_ff_(H, l, SUHMO_F_PHI, -1, false, st))) return rc;
+    const suhmo_phys_t &ph = H->lev[l].box[0]->ph;
+    if ((rc = hier_cf(H, l, SUHMO_F_PHI, SUHMO_F_PHI, st))) return rc;                  // inside compGradientMAC
+    if ((rc = hier_ff(H, l, SUHMO_F_PHI, -1, false, st))) return rc;
     if (t.base) rc = suhmo_grad_cc(t.base, 0, st); else rc = suhmo_multi_grad_cc(t.m, ph.use_mask_gradients, st);
     if (rc) return rc;
-    if ((rc = suhmo_hier_cf2_(H, l, SUHMO_F_GRADX, SUHMO_F_GRADX, SUHMO_F_GRADY, SUHMO_F_GRADY, st))) return rc;   // :1650-1659
-    if ((rc = suhmo_hier_ff_(H, l, SUHMO_F_GRADX, SUHMO_F_GRADY, true, st))) return rc;
+    if ((rc = hier_cf(H, l, SUHMO_F_GRADX, SUHMO_F_GRADX, st, SUHMO_F_GRADY, SUHMO_F_GRADY))) return rc;   // :1650-1659
+    if ((rc = hier_ff(H, l, SUHMO_F_GRADX, SUHMO_F_GRADY, true, st))) return rc;
     if (t.base) rc = suhmo_re_cells(t.base, 0, st); else rc = suhmo_multi_re(t.m, ph, st);
     if (rc) return rc;
-    if ((rc = suhmo_hier_pwl_(H, l, SUHMO_F_RE, SUHMO_F_RE, st))) return rc;                   // :2711-2721
-    if ((rc = suhmo_hier_ff_(H, l, SUHMO_F_RE, -1, true, st))) return rc;
+    if ((rc = hier_pwl(H, l, SUHMO_F_RE, SUHMO_F_RE, st))) return rc;                   // :2711-2721
+    if ((rc = hier_ff(H, l, SUHMO_F_RE, -1, true, st))) return rc;
     if (t.base) { Depth &D = t.base->d[0];
         hipLaunchKernelGGL(k_qw_faces, dim3((D.v.nx + 1 + 63) / 64, (D.v.ny + 1 + 3) / 4), dim3(64, 4), 0, st, D.v, D.fp, ph); }
     else if (t.m.nbox > 0) hipLaunchKernelGGL(k_qw_faces_m, grid_m(t.m, 1, 1), dim3(64, 4), 0, st, t.m.dv, t.m.fp, ph);
@@ -682,8 +684,8 @@ int hier_gap_ghosts(suhmo_hier *H, int l, hipStream_t st)
     int rc;
     LevT t;
     if ((rc = lev_target(H, l, st, t))) return rc;
-    if ((rc = suhmo_hier_pwl_(H, l, SUHMO_F_B, SUHMO_F_B, st))) return rc;
-    if ((rc = suhmo_hier_ff_(H, l, SUHMO_F_B, -1, true, st))) return rc;
+    if ((rc = hier_pwl(H, l, SUHMO_F_B, SUHMO_F_B, st))) return rc;
+    if ((rc = hier_ff(H, l, SUHMO_F_B, -1, true, st))) return rc;
     if (t.base) { if ((rc = suhmo_copy_ghosts(t.base, 0, SUHMO_F_B, st))) return rc; return exchange1(t.base, SUHMO_F_B, st); }   // rank strips: halo rows
     return suhmo_multi_coef_ghosts(t.m, SUHMO_F_B, st);
 }
@@ -693,7 +695,7 @@ int hier_melt(suhmo_hier *H, int l, const suhmo_model_params_t *mp, double dt, i
     int rc;
     LevT t;
     if ((rc = lev_target(H, l, st, t))) return rc;
-    const suhmo_phys_t &ph = suhmo_hier_boxes_(H, l)[0]->ph;
+    const suhmo_phys_t &ph = H->lev[l].box[0]->ph;
     if (t.base) {
         suhmo_level *L = t.base;
         Depth &D = L->d[0];
@@ -702,7 +704,7 @@ int hier_melt(suhmo_hier *H, int l, const suhmo_model_params_t *mp, double dt, i
         else hipLaunchKernelGGL(k_melt<0>, dim3((D.v.nx + 63) / 64, (D.v.ny + 3) / 4), dim3(64, 4), 0, st, D.v, D.fp, ph, *mp, dt);
     } else {
         const suhmo_multi &m = t.m;
-        if (diffusion) for (int f : {SUHMO_F_DCX, SUHMO_F_DCY, SUHMO_F_DTERM}) if ((rc = suhmo_hier_ensure_(H, l, f))) return rc;
+        if (diffusion) for (int f : {SUHMO_F_DCX, SUHMO_F_DCY, SUHMO_F_DTERM}) if ((rc = ensure_field(H, l, f))) return rc;
         if (m.nbox <= 0) return 0;                                               // owner computes: none of this level's boxes is this rank's
         if (diffusion) {
             if ((rc = lev_target(H, l, st, t))) return rc;                       // the tables after the allocation
@@ -723,7 +725,7 @@ int hier_picard_maxima(suhmo_hier *H, int l, bool covered, double *maxh, double 
     int rc;
     LevT t;
     if ((rc = lev_target(H, l, st, t))) return rc;
-    suhmo_level *slot = suhmo_hier_boxes_(H, 0)[0];
+    suhmo_level *slot = H->lev[0].box[0];
     if (t.base) {
         suhmo_level *L = t.base;
         if ((rc = picard_maxima(L, L->d[0].fp.f[SUHMO_F_PHI], L->d[0].fp.f[SUHMO_F_HLAG], maxh, maxd, st, Excl{0, 0, 0, 0}, covered ? L->d[0].fp.f[SUHMO_F_COVER] : nullptr))) return rc;
@@ -742,7 +744,7 @@ int hier_picard_maxima(suhmo_hier *H, int l, bool covered, double *maxh, double 
         HIPCHK(hipGetLastError());
         if ((rc = suhmo_readback(slot, st, maxh, maxd))) return rc;
     }
-    if (suhmo_hier_partitioned_(H)) {                                            // owner computes: computeMax over the ranks
+    if (H->part) {                                            // owner computes: computeMax over the ranks
         if ((rc = suhmo_hier_allreduce_max_(H, maxh)) || (rc = suhmo_hier_allreduce_max_(H, maxd))) return rc;
     }
     return 0;
@@ -755,22 +757,21 @@ extern "C" int suhmo_hier_timestep(suhmo_hier_t *H, const suhmo_model_params_t *
     SUHMO_TIME("AmrHydro::timeStepFAS");
     ARG(H && mp); ARG(dt > 0 && cur_step >= 1);
     if (mp->use_impl_diff && mp->diffFactor == 0.0) { suhmo_set_error("use_ImplDiff with diffFactor = 0"); return -1; }
-    const int nlev = suhmo_hier_nlev_(H);
-    HIPCHK(hipSetDevice(suhmo_hier_device_(H)));
+    const int nlev = H->nlev;
+    HIPCHK(hipSetDevice(H->device));
     suhmo_hier_invalidate_(H);
     hipStream_t st = (hipStream_t)s;
     int rc;
     static const int need[] = {SUHMO_F_MR, SUHMO_F_PW, SUHMO_F_QWX, SUHMO_F_QWY, SUHMO_F_HLAG, SUHMO_F_CD, SUHMO_F_GRADX, SUHMO_F_GRADY, SUHMO_F_RE};
     for (int l = 0; l < nlev; l++) {
-        for (int f : need) if ((rc = suhmo_hier_ensure_(H, l, f))) return rc;
+        for (int f : need) if ((rc = ensure_field(H, l, f))) return rc;
         if (mp->use_moulin_source) {
-            int k0, nk;
-            suhmo_hier_owned_(H, l, &k0, &nk);
+            const int k0 = H->lev[l].first_owned(), nk = H->lev[l].n_owned();
             for (int k = k0; k < k0 + nk; k++)
-                if (!suhmo_hier_boxes_(H, l)[k]->d[0].fp.f[SUHMO_F_MSRC]) { suhmo_set_error("use_moulin_source without a moulin source term (suhmo_hier_moulin_source)"); return -1; }
+                if (!H->lev[l].box[k]->d[0].fp.f[SUHMO_F_MSRC]) { suhmo_set_error("use_moulin_source without a moulin source term (suhmo_hier_moulin_source)"); return -1; }
         }
     }
-    suhmo_level *base = suhmo_hier_boxes_(H, 0)[0];
+    suhmo_level *base = H->lev[0].box[0];
     if ((base->d[0].v.rk[0] || base->d[0].v.rk[1]) && !(base->ex && base->ar)) { suhmo_set_error("time step on rank strips needs the exchange hooks on level 0"); return -1; }
     // [I]
     for (int l = 0; l < nlev; l++) if ((rc = hier_gap_ghosts(H, l, st))) return rc;
@@ -785,17 +786,17 @@ extern "C" int suhmo_hier_timestep(suhmo_hier_t *H, const suhmo_model_params_t *
         for (int l = 0; l < nlev; l++) {
             if ((rc = hier_gap_ghosts(H, l, st))) return rc;
             if (l == 0 && (rc = exchange1(base, SUHMO_F_MR, st))) return rc;                    // rank strips: levelmR.exchange() :2513
-            if ((rc = suhmo_hier_pwl_(H, l, SUHMO_F_MR, SUHMO_F_MR, st))) return rc;
-            if ((rc = suhmo_hier_ff_(H, l, SUHMO_F_MR, -1, true, st))) return rc;               // levelmR.exchange() :2513
+            if ((rc = hier_pwl(H, l, SUHMO_F_MR, SUHMO_F_MR, st))) return rc;
+            if ((rc = hier_ff(H, l, SUHMO_F_MR, -1, true, st))) return rc;               // levelmR.exchange() :2513
             if (l == 0) { Depth &D = base->d[0];
                 HIPCHK(hipMemcpyAsync(D.fp.f[SUHMO_F_HLAG], D.fp.f[SUHMO_F_PHI], D.elems * sizeof(double), hipMemcpyDeviceToDevice, st)); }
-            else { suhmo_multi m; if ((rc = suhmo_hier_multi_(H, l, st, &m)) || (rc = suhmo_multi_copy(m, SUHMO_F_HLAG, SUHMO_F_PHI, st))) return rc; }
+            else { suhmo_multi m; if ((rc = multi_of(H, l, st, m)) || (rc = suhmo_multi_copy(m, SUHMO_F_HLAG, SUHMO_F_PHI, st))) return rc; }
         }
         for (int l = 0; l < nlev; l++) if ((rc = hier_chain(H, l, st))) return rc;
         for (int l = 0; l < nlev; l++) {                                                        // aCoeff_bCoeff :3087-3102
             LevT t;
             if ((rc = lev_target(H, l, st, t))) return rc;
-            if (t.base) rc = suhmo_bcoef_faces(t.base, 0, st); else rc = suhmo_multi_bcoef_faces(t.m, suhmo_hier_boxes_(H, l)[0]->ph, st);
+            if (t.base) rc = suhmo_bcoef_faces(t.base, 0, st); else rc = suhmo_multi_bcoef_faces(t.m, H->lev[l].box[0]->ph, st);
             if (rc) return rc;
         }
         for (int l = 0; l < nlev; l++) if ((rc = hier_melt(H, l, mp, dt, 0, mp->diffFactor != 0.0, st))) return rc;
@@ -803,7 +804,7 @@ extern "C" int suhmo_hier_timestep(suhmo_hier_t *H, const suhmo_model_params_t *
         int it = 0;
         if ((rc = suhmo_hier_solve(H, &sp, &it, nullptr, s))) return rc;
         nv += it;
-        for (int l = nlev - 1; l > 0; l--) if ((rc = suhmo_hier_avg_(H, l, SUHMO_F_PHI, SUHMO_F_PHI, st))) return rc;   // CoarseAverage :3138-3141
+        for (int l = nlev - 1; l > 0; l--) if ((rc = hier_avg(H, l, SUHMO_F_PHI, SUHMO_F_PHI, 0, 0.0, st))) return rc;   // CoarseAverage :3138-3141
         double maxHead = -1.0e300, maxd = 0.0, res = 0.0;
         for (int l = 0; l < nlev; l++) {
             double m = 0.0, d = 0.0;
@@ -828,13 +829,13 @@ extern "C" int suhmo_hier_timestep(suhmo_hier_t *H, const suhmo_model_params_t *
         suhmo_hier *G = nullptr;
         if ((rc = suhmo_hier_gap_(H, mp, dt, &G))) return rc;
         for (int l = 0; l < nlev; l++) {
-            const auto &hb = suhmo_hier_boxes_(H, l), &gb = suhmo_hier_boxes_(G, l);
+            const auto &hb = H->lev[l].box, &gb = G->lev[l].box;
             if (l > 0) {                                               // all boxes of a level: one launch
                 static const int fd[4] = {SUHMO_F_PHI, SUHMO_F_RHS, SUHMO_F_BX, SUHMO_F_BY}, fs[4] = {SUHMO_F_B, SUHMO_F_RES, SUHMO_F_DCX, SUHMO_F_DCY};
-                for (int f : fs) if ((rc = suhmo_hier_ensure_(H, l, f))) return rc;
-                for (int f : fd) if ((rc = suhmo_hier_ensure_(G, l, f))) return rc;
+                for (int f : fs) if ((rc = ensure_field(H, l, f))) return rc;
+                for (int f : fd) if ((rc = ensure_field(G, l, f))) return rc;
                 suhmo_multi mh, mg;
-                if ((rc = suhmo_hier_multi_(H, l, st, &mh)) || (rc = suhmo_hier_multi_(G, l, st, &mg))) return rc;
+                if ((rc = multi_of(H, l, st, mh)) || (rc = multi_of(G, l, st, mg))) return rc;
                 if ((rc = suhmo_multi_copy_between(mg, mh, fd, fs, 4, st))) return rc;                                     // initial guess = b :3382-3385
                 for (suhmo_level *L : gb) L->d[0].phi_fresh = 0;
                 continue;
@@ -851,17 +852,17 @@ extern "C" int suhmo_hier_timestep(suhmo_hier_t *H, const suhmo_model_params_t *
             }
         }
         {   static const int halo_fields[] = {SUHMO_F_RHS, SUHMO_F_ACOEF, SUHMO_F_BX, SUHMO_F_BY};          // rank strips
-            if ((rc = suhmo_exchange_list(suhmo_hier_boxes_(G, 0)[0], 0, halo_fields, 4, st))) return rc; }
-        if ((rc = suhmo_level_build_mg_coefficients(suhmo_hier_boxes_(G, 0)[0], s))) return rc;
+            if ((rc = suhmo_exchange_list(G->lev[0].box[0], 0, halo_fields, 4, st))) return rc; }
+        if ((rc = suhmo_level_build_mg_coefficients(G->lev[0].box[0], s))) return rc;
         suhmo_solver_params_t spg;
         gap_solver_params(spg, cur_step);
         if ((rc = suhmo_hier_solve(G, &spg, nullptr, nullptr, s))) return rc;
         for (int l = 0; l < nlev; l++) {
-            const auto &hb = suhmo_hier_boxes_(H, l), &gb = suhmo_hier_boxes_(G, l);
+            const auto &hb = H->lev[l].box, &gb = G->lev[l].box;
             if (l > 0) {
                 static const int fd[1] = {SUHMO_F_B}, fs[1] = {SUHMO_F_PHI};
                 suhmo_multi mh, mg;
-                if ((rc = suhmo_hier_multi_(H, l, st, &mh)) || (rc = suhmo_hier_multi_(G, l, st, &mg))) return rc;
+                if ((rc = multi_of(H, l, st, mh)) || (rc = multi_of(G, l, st, mg))) return rc;
                 if (mp->freeze_icefree_gap && mh.nbox > 0) {
                     hipLaunchKernelGGL(k_keep_icefree_m, grid_m(mh), dim3(64, 4), 0, st, mh.dv, mh.fp, mg.fp);
                     HIPCHK(hipGetLastError());
@@ -1074,8 +1075,8 @@ extern "C" int suhmo_hier_moulin_source(suhmo_hier_t *H, int n, const double *po
                                         double time_factor, double *integrals, suhmo_stream_t s)
 {
     ARG(H && n >= 1 && positions && sigma && flux);
-    const int nlev = suhmo_hier_nlev_(H);
-    HIPCHK(hipSetDevice(suhmo_hier_device_(H)));
+    const int nlev = H->nlev;
+    HIPCHK(hipSetDevice(H->device));
     hipStream_t st = (hipStream_t)s;
     int rc;
     std::vector<double> h(4 * (size_t)n), total((size_t)n, 0.0), part((size_t)n);
@@ -1085,14 +1086,13 @@ extern "C" int suhmo_hier_moulin_source(suhmo_hier_t *H, int n, const double *po
     }
     // owner computes (levels >= 1 dealt to the ranks): a rank integrates and fills the boxes it owns; the per-box integrals of all ranks are
     // gathered and added up in the single-process order (finest level first, box after box), so every rank gets the same bits
-    const bool parted = suhmo_hier_partitioned_(H);
+    const bool parted = H->part;
     size_t maxblk = 0, nbt = 0;
     std::vector<size_t> first(nlev + 1, 0);
     for (int l = 0; l < nlev; l++) {
-        const auto &bx = suhmo_hier_boxes_(H, l);
+        const auto &bx = H->lev[l].box;
         first[l] = nbt; nbt += bx.size();
-        int k0, nk;
-        suhmo_hier_owned_(H, l, &k0, &nk);
+        const int k0 = H->lev[l].first_owned(), nk = H->lev[l].n_owned();
         for (int k = 0; k < (int)bx.size(); k++) {
             suhmo_level *L = bx[k];
             if (k >= k0 && k < k0 + nk && !suhmo_field(L, 0, SUHMO_F_MSRC)) { suhmo_set_error("field allocation failed"); return -2; }
@@ -1104,13 +1104,11 @@ extern "C" int suhmo_hier_moulin_source(suhmo_hier_t *H, int n, const double *po
     HIPCHK(hipMalloc(&dev, (5 * (size_t)n + maxblk * n) * sizeof(double)));
     double *mo = dev, *fl = dev + 3 * (size_t)n, *integ = dev + 4 * (size_t)n, *partial = dev + 5 * (size_t)n;
     hipError_t e = hipMemcpyAsync(dev, h.data(), 4 * (size_t)n * sizeof(double), hipMemcpyHostToDevice, st);
-    DV whole;
-    const double *whole_cover = suhmo_hier_base_cover_(H, &whole);     // level 0 cut into rank strips: every rank integrates all of it (geometry only)
+    const double *whole_cover = dist_base(H) ? H->cover_whole : nullptr;   // level 0 cut into rank strips: every rank integrates all of it (geometry only)
     std::vector<double> perbox(nbt * (size_t)n, 0.0);                  // the integrals over every box (this rank's; the others' after the gather)
     for (int l = nlev - 1; l >= 0 && e == hipSuccess; l--) {
-        const auto &bx = suhmo_hier_boxes_(H, l);
-        int k0, nk;
-        suhmo_hier_owned_(H, l, &k0, &nk);
+        const auto &bx = H->lev[l].box;
+        const int k0 = H->lev[l].first_owned(), nk = H->lev[l].n_owned();
         for (int k = k0; k < k0 + nk; k++) {
             suhmo_level *L = bx[k];
             const bool cutbase = l == 0 && (L->d[0].v.rk[0] || L->d[0].v.rk[1]);
@@ -1128,7 +1126,7 @@ extern "C" int suhmo_hier_moulin_source(suhmo_hier_t *H, int n, const double *po
         }
     }
     if (e == hipSuccess && parted) {                                   // every rank's integrals over its boxes -> every rank
-        const int world = suhmo_hier_world_(H);
+        const int world = H->world;
         const size_t cnt = nbt * (size_t)n;
         double *gs = nullptr, *gr = nullptr;
         std::vector<double> all(cnt * world);
@@ -1152,9 +1150,8 @@ extern "C" int suhmo_hier_moulin_source(suhmo_hier_t *H, int n, const double *po
             for (int m = 0; m < n; m++) total[m] += perbox[k * (size_t)n + m];
     if (e == hipSuccess) e = hipMemcpyAsync(integ, total.data(), (size_t)n * sizeof(double), hipMemcpyHostToDevice, st);
     for (int l = 0; l < nlev && e == hipSuccess; l++) {
-        const auto &bx = suhmo_hier_boxes_(H, l);
-        int k0, nk;
-        suhmo_hier_owned_(H, l, &k0, &nk);
+        const auto &bx = H->lev[l].box;
+        const int k0 = H->lev[l].first_owned(), nk = H->lev[l].n_owned();
         for (int k = k0; k < k0 + nk; k++) {
             suhmo_level *L = bx[k];
             const DV &v = L->d[0].v;
@@ -1168,7 +1165,7 @@ extern "C" int suhmo_hier_moulin_source(suhmo_hier_t *H, int n, const double *po
     if (e == hipSuccess) e = hipStreamSynchronize(st);
     (void)hipFree(dev);
     if (e != hipSuccess) { suhmo_set_error("moulin source: %s", hipGetErrorString(e)); return -2; }
-    for (int l = nlev - 1; l > 0; l--) if ((rc = suhmo_hier_avg_(H, l, SUHMO_F_MSRC, SUHMO_F_MSRC, st))) return rc;
+    for (int l = nlev - 1; l > 0; l--) if ((rc = hier_avg(H, l, SUHMO_F_MSRC, SUHMO_F_MSRC, 0, 0.0, st))) return rc;
     if (integrals) for (int m = 0; m < n; m++) integrals[m] = total[m];
     return 0;
 }

@@ -293,11 +293,12 @@ class _BoxView(HipLevel):
 
 class HipHier:
     """Base level + levels that are unions of boxes (boxes[l-1] = list of (lo0, lo1, hi0, hi1) in the index space of
-    level l), the reference's DisjointBoxLayout per AMR level: suhmo_hier_* (suhmo_amd/csrc/suhmo_hier.hip)."""
+    level l), the reference's DisjointBoxLayout per AMR level: suhmo_hier_* (suhmo_amd/csrc/suhmo_hier*.hip)."""
 
     def __init__(self, nx0, ny0, dx0, dy0, bc, phys, boxes, alpha=0.0, beta=-1.0, max_box=64, device=0, j0=0, ny_global=None, halo_rows=1, options=None):
         """ny0 rows of level 0 starting at row j0 of ny_global: this rank's strip (one process per GPU; the boxes of the finer
-        levels are given whole on every rank); default: the whole level.  options: "key=value,..." of suhmo_hier_create_opts (shadow, push_ghosts)"""
+        levels are given whole on every rank); default: the whole level.  options: "key=value,..." of suhmo_hier_create_opts (the
+        table hier_opts in suhmo_hier.hip; an unknown key is refused)"""
         self.boxes = [[tuple(int(v) for v in b) for b in bl] for bl in boxes]
         self.nlev = 1 + len(self.boxes)
         d = capi.LevelDesc()

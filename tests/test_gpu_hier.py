@@ -204,3 +204,73 @@ def test_hier_refuses_layouts_the_reference_could_not_have():
         H.cf_interp(1)
     assert "all-gather" in str(e.value)
     H.close()
+
+
+# the hierarchy's options (one table in suhmo_hier.hip): value given at creation / by suhmo_hier_set_option -> what get_option reports
+OPTION_DEFAULTS = dict(push_ghosts=1, incremental_residual=1, fused_prolong=1, merged_launches=1, box_sweeps=4, fused_relax=1, shadow=0,
+                       partition_min_cells=350000)
+OPTION_OTHERS = dict(push_ghosts=0, incremental_residual=0, fused_prolong=0, merged_launches=0, box_sweeps=2, fused_relax=0, shadow=1,
+                     partition_min_cells=1234)
+CREATION_ONLY = ("shadow", "partition_min_cells")
+
+
+def hier(options=None):
+    from suhmo_amd import level
+    fs = sy.amrm_fields(64, 16, UNION)
+    return level.HipHier(64, 16, fs[0]["dx"], fs[0]["dy"], BC_NP, sy.CFG3_PHYS, UNION, max_box=32, options=options)
+
+
+def test_hier_options_round_trip():
+    G = hier()
+    assert {k: G.get_option(k) for k in OPTION_DEFAULTS} == OPTION_DEFAULTS
+    for k, v in OPTION_OTHERS.items():
+        if k in CREATION_ONLY:
+            continue
+        G.set_option(k, v)
+        assert G.get_option(k) == v, k
+        G.set_option(k, OPTION_DEFAULTS[k])
+        assert G.get_option(k) == OPTION_DEFAULTS[k], k
+    G.set_option("box_sweeps", 3)                         # sweeps per launch: 4 or 2
+    assert G.get_option("box_sweeps") == 2
+    G.close()
+    G = hier(",".join("%s=%d" % kv for kv in OPTION_OTHERS.items()))
+    assert {k: G.get_option(k) for k in OPTION_OTHERS} == OPTION_OTHERS
+    G.close()
+
+
+def test_hier_options_refused():
+    from suhmo_amd.capi import SuhmoError
+    with pytest.raises(SuhmoError, match="fused_relaxx"):
+        hier("fused_relaxx=0")
+    with pytest.raises(SuhmoError, match="no_such_option"):
+        hier("push_ghosts=0,no_such_option=1")
+    G = hier()
+    for k in CREATION_ONLY:
+        with pytest.raises(SuhmoError, match=k):
+            G.set_option(k, OPTION_OTHERS[k])
+        assert G.get_option(k) == OPTION_DEFAULTS[k]
+    with pytest.raises(SuhmoError, match="no_such_option"):
+        G.set_option("no_such_option", 1)
+    G.close()
+
+
+def test_hier_option_set_before_the_first_step_reaches_the_gap_solve():
+    """fused_relax = 0 set before the first implicit time step reaches the gap-height hierarchy (created then, with the parent's current
+    values): no launch of two sweeps or more anywhere, and the same bits as a hierarchy created with fused_relax=0"""
+    from suhmo_amd import model
+    m = dict(sy.A3_MODEL, diffFactor=1.0, use_impl_diff=1)
+    sts = sy.shmip_amrm_states(64, 32, UNION, rough=0.5)
+    runs = []
+    for options in ("fused_relax=0", None):
+        G = model.HipHierModel(64, 32, sts[0][0]["dx"], sts[0][0]["dy"], sy.A3_BC, sy.A3_PHYS, m, UNION, max_box=16, options=options)
+        G.set_states(sts)
+        if options is None:
+            G.hier.set_option("fused_relax", 0)
+        counts = [G.timestep(m["dt"]) for _ in range(2)]
+        assert G.hier.get_option("fused_relax_launches") == 0, options
+        runs.append((counts, [[G.get(l, k, nm) for k in range(len(G.level[l])) for nm in ("head", "B")] for l in range(G.hier.nlev)]))
+        G.close()
+    assert runs[0][0] == runs[1][0]
+    for a, b in zip(runs[0][1], runs[1][1]):
+        for x, y in zip(a, b):
+            assert np.array_equal(x, y, equal_nan=True)
