@@ -451,6 +451,8 @@ extern "C" int suhmo_amr2_solve(suhmo_level_t *C, suhmo_level_t *F, const suhmo_
         goNorm = rnorm > sp->norm_thresh; goRedu = rnorm > sp->eps * initial_rnorm; goIter = iter < sp->max_iter;
         goHang = iter < sp->imin || rnorm < (1.0 - sp->hang) * norm_last; goMin = iter < sp->iter_min;
     }
+    // the domain sides of the rings as the solve's last residual evaluation leaves them in the oracle (as suhmo_level_solve)
+    if ((rc = suhmo_level_fill_ghosts(C, 0, SUHMO_F_PHI, 0, s)) || (rc = suhmo_level_fill_ghosts(F, 0, SUHMO_F_PHI, 0, s))) return rc;
     if (iters) *iters = iter;
     return 0;
 }
@@ -606,6 +608,10 @@ extern "C" int suhmo_amr_solve(suhmo_level_t **lv, int nlev, const suhmo_solver_
         goNorm = rnorm > sp->norm_thresh; goRedu = rnorm > sp->eps * initial_rnorm; goIter = iter < sp->max_iter;
         goHang = iter < sp->imin || rnorm < (1.0 - sp->hang) * norm_last; goMin = iter < sp->iter_min;
     }
+    // the domain sides of the rings as the solve's last residual evaluation leaves them in the oracle (as suhmo_level_solve);
+    // patch sides inside the domain keep their coarse-fine data
+    for (int l = 0; l < nlev; l++)
+        if (lv[l] && (rc = suhmo_level_fill_ghosts(lv[l], 0, SUHMO_F_PHI, 0, s))) return rc;
     if (iters) *iters = iter;
     return 0;
 }

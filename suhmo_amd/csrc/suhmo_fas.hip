@@ -259,6 +259,10 @@ extern "C" int suhmo_level_solve(suhmo_level_t *L, const suhmo_solver_params_t *
         goHang = iter < sp->imin || rnorm < (1.0 - sp->hang) * norm_last;
         goMin = iter < sp->iter_min;
     }
+    // the solve ends on the residual evaluation of the final phi, whose ghost fill is the inhomogeneous one (the oracle's residual
+    // leaves it in the ring); the device's residual passes evaluate the boundary values on the fly and leave the relaxation's
+    // homogeneous ring behind: one fill of the ring, as the caller reads it
+    if ((rc = suhmo_level_fill_ghosts(L, 0, SUHMO_F_PHI, 0, s))) return rc;
     if (iters) *iters = iter;
     return 0;
 }

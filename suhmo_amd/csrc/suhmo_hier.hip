@@ -39,8 +39,10 @@ int hier_gsrb(suhmo_hier *H, int l, int sweeps, suhmo_stream_t s, bool may_swap 
             H->phi_ver[l]++; H->n_fused_relax++;
         }
         if (src != SUHMO_F_PHI) {                          // an odd number of launches: the result is on the second canvas
-            if (may_swap && Vf.d_fp_alt) swap_head(H, l);  // (inside a V-cycle: that canvas becomes the head; vcycle_amr puts things back)
-            else if ((rc = suhmo_multi_copy(m, SUHMO_F_PHI, SUHMO_F_PHI2, HST(s)))) return rc;
+            if (may_swap && Vf.d_fp_alt) {                 // (inside a V-cycle: that canvas becomes the head; vcycle_amr puts things back)
+                swap_head(H, l);
+                if (!bcg && (rc = multi_of(H, l, HST(s), m))) return rc;   // the closing fill below writes the ring of the new head
+            } else if ((rc = suhmo_multi_copy(m, SUHMO_F_PHI, SUHMO_F_PHI2, HST(s)))) return rc;
         }
         return bcg ? 0 : suhmo_multi_fill_ghosts(m, SUHMO_F_PHI, 1, HST(s));                                  // :757-759
     }
@@ -776,6 +778,13 @@ extern "C" int suhmo_hier_solve(suhmo_hier_t *H, const suhmo_solver_params_t *sp
         if (hist) hist[iter] = rnorm;
         goNorm = rnorm > sp->norm_thresh; goRedu = rnorm > sp->eps * initial_rnorm; goIter = iter < sp->max_iter;
         goHang = iter < sp->imin || rnorm < (1.0 - sp->hang) * norm_last; goMin = iter < sp->iter_min;
+    }
+    // the domain sides of every ring as the solve's last residual evaluation leaves them in the oracle: the inhomogeneous boundary
+    // condition (as suhmo_level_solve); the residual kernels evaluate it on the fly over the relaxation's homogeneous fill
+    if ((rc = suhmo_level_fill_ghosts(base_of(H), 0, SUHMO_F_PHI, 0, s))) return rc;
+    for (int l = 1; l < H->nlev; l++) {
+        suhmo_multi m;
+        if ((rc = multi_of(H, l, HST(s), m)) || (rc = suhmo_multi_fill_ghosts(m, SUHMO_F_PHI, 0, HST(s)))) return rc;
     }
     if (iters) *iters = iter;
     return 0;

@@ -564,6 +564,8 @@ extern "C" int suhmo_amr_timestep(suhmo_level_t **lv, int nlev, const suhmo_mode
             if (lv[l]) { if ((rc = suhmo_amr2_average(lv[l - 1], lv[l], SUHMO_F_PHI, SUHMO_F_PHI, s))) return rc; }
             else if (lv[l - 1]) lv[l - 1]->d[0].phi_fresh = 0;                          // changed on the ranks that hold level l
         }
+        for (int l = 0; l + 1 < nlev; l++)      // the rings of the averaged heads, as the oracle refills them (exchange + BC, every level)
+            if (lv[l] && (rc = suhmo_level_fill_ghosts(lv[l], 0, SUHMO_F_PHI, 0, s))) return rc;
         double maxHead = -1.0e300, maxd = 0.0, res = 0.0;
         for (int l = 0; l < nlev; l++) {
             if (!lv[l]) continue;
@@ -805,6 +807,11 @@ extern "C" int suhmo_hier_timestep(suhmo_hier_t *H, const suhmo_model_params_t *
         if ((rc = suhmo_hier_solve(H, &sp, &it, nullptr, s))) return rc;
         nv += it;
         for (int l = nlev - 1; l > 0; l--) if ((rc = hier_avg(H, l, SUHMO_F_PHI, SUHMO_F_PHI, 0, 0.0, st))) return rc;   // CoarseAverage :3138-3141
+        for (int l = 0; l + 1 < nlev; l++) {    // the averaged heads' rings as the oracle refills them: BC of every box, level 0's periodic sides
+            if (l == 0) { if ((rc = suhmo_level_fill_ghosts(base, 0, SUHMO_F_PHI, 0, s))) return rc; continue; }
+            suhmo_multi m;
+            if ((rc = multi_of(H, l, st, m)) || (rc = suhmo_multi_fill_ghosts(m, SUHMO_F_PHI, 0, st))) return rc;
+        }
         double maxHead = -1.0e300, maxd = 0.0, res = 0.0;
         for (int l = 0; l < nlev; l++) {
             double m = 0.0, d = 0.0;

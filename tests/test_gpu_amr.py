@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 
 from suhmo_amd import synthetic as sy
+from tests import ghostring as gr
 
 pytestmark = pytest.mark.gpu
 BC = dict(type=[[0, 0], [1, 0]], value=[[0.0, 0.0], [0.0, 0.0]], periodic=[0, 1])     # 2lev_base/input.hydro:8-13,76
@@ -33,6 +34,16 @@ def eq(a, b, what):
     assert np.array_equal(a, b), (what, float(np.max(np.abs(a - b))))
 
 
+def patch_ring(a, b, patch, nxc, nyc, bc, what, dx=None, dy=None):
+    """ghost ring of a nested patch (refinement 2 of `patch`, given in the cells of the level below), every side, bitwise the oracle's;
+    with dx, dy (after a relaxation) the domain sides also hold the homogeneous boundary condition of the device's own valid cells"""
+    ci0, cj0, ci1, cj1 = patch
+    box, dom = (2 * ci0, 2 * cj0, 2 * ci1 + 1, 2 * cj1 + 1), (2 * nxc, 2 * nyc)
+    gr.ring_equal(a, b, box, dom, bc["periodic"], what=what)
+    if dx is not None:
+        gr.domain_bc_holds(b, bc, dx, dy, box, dom, what)
+
+
 @pytest.mark.parametrize("case", CASES, ids=[c[0] for c in CASES])
 def test_amr2_pieces_bitwise(oracle, case):
     from suhmo_amd.level import F_PHI, F_RES, F_BX, F_BY
@@ -55,6 +66,8 @@ def test_amr2_pieces_bitwise(oracle, case):
     # fine relaxation with stored coarse-fine ghosts
     O.fine_gsrb(2); G.fine.gsrb(2)
     eq(O.fine_get(oracle.F_PHI), G.fine.get(F_PHI), "fine gsrb")
+    fdx, fdy = G.fine.dx, G.fine.dy
+    patch_ring(O.fine_get(oracle.F_PHI, ghosted=True), G.fine.get(F_PHI, ghosted=True), patch, case[1], case[2], case[4], "fine gsrb", fdx, fdy)
     O.close(); G.close()
 
 
@@ -79,12 +92,15 @@ def test_amr2_vcycle_and_solve_bitwise(oracle, case):
     sp = dict(sy.SOLVER_DEFAULT, eps=1e-9, norm_thresh=1e-14, max_iter=6, imin=30)
     O.vcycle(sp); G.vcycle(sp)
     eq(O.fine_get(oracle.F_PHI), G.fine.get(F_PHI), "fine head after one AMR V-cycle")
+    patch_ring(O.fine_get(oracle.F_PHI, ghosted=True), G.fine.get(F_PHI, ghosted=True), patch, case[1], case[2], case[4], "fine vcycle",
+               G.fine.dx, G.fine.dy)
     eq(O.coarse.get(oracle.F_PHI), G.coarse.get(F_PHI), "coarse head after one AMR V-cycle")
     eq(O.coarse.get(oracle.F_RHS), G.coarse.get(1), "coarse rhs restored")
     no, ho = O.solve(sp)
     ng, hg = G.solve(sp)
     assert no == ng and np.array_equal(ho, hg), (ho, hg)
     eq(O.fine_get(oracle.F_PHI), G.fine.get(F_PHI), "fine head after the solve")
+    patch_ring(O.fine_get(oracle.F_PHI, ghosted=True), G.fine.get(F_PHI, ghosted=True), patch, case[1], case[2], case[4], "fine solve")
     eq(O.coarse.get(oracle.F_PHI), G.coarse.get(F_PHI), "coarse head after the solve")
     O.close(); G.close()
 
@@ -116,11 +132,15 @@ def test_amr_n_levels_bitwise(oracle, case):
     O.vcycle(sp); G.vcycle(sp)
     for l in range(1, len(fs)):
         eq(O.patch_get(l, oracle.F_PHI), G.levels[l].get(F_PHI), "level %d head after one AMR V-cycle" % l)
+        patch_ring(O.patch_get(l, oracle.F_PHI, ghosted=True), G.levels[l].get(F_PHI, ghosted=True), patches[l - 1], nx0 << (l - 1),
+                   ny0 << (l - 1), bc, ("vcycle", l), fs[l]["dx"], fs[l]["dy"])
     eq(O.coarse.get(oracle.F_PHI), G.levels[0].get(F_PHI), "base head after one AMR V-cycle")
     no, ho = O.solve(sp)
     ng, hg = G.solve(sp)
     assert no == ng and np.array_equal(ho, hg), (ho, hg)
     for l in range(1, len(fs)):
         eq(O.patch_get(l, oracle.F_PHI), G.levels[l].get(F_PHI), "level %d head after the solve" % l)
+        patch_ring(O.patch_get(l, oracle.F_PHI, ghosted=True), G.levels[l].get(F_PHI, ghosted=True), patches[l - 1], nx0 << (l - 1),
+                   ny0 << (l - 1), bc, ("solve", l))
     eq(O.coarse.get(oracle.F_PHI), G.levels[0].get(F_PHI), "base head after the solve")
     O.close(); G.close()

@@ -5,6 +5,7 @@ import numpy as np
 import pytest
 
 from suhmo_amd import synthetic as sy
+from tests import ghostring as gr
 
 pytestmark = pytest.mark.gpu
 
@@ -40,6 +41,10 @@ def test_amr_timestep_bitwise(oracle, name, nx0, ny0, patches, mpo, nsteps):
             for nm, fid in (("qwx", oracle.OM_QWX), ("qwy", oracle.OM_QWY)):
                 a, b = np.array(O.field(l, fid)), G.get(l, nm)
                 assert np.array_equal(a, b, equal_nan=True), (name, k, l, nm, float(np.nanmax(np.abs(a - b))))
+            # the head's ghost ring after the step, every side (domain, coarse-fine)
+            box = (0, 0, nx0 - 1, ny0 - 1) if l == 0 else tuple(2 * v + (i > 1) for i, v in enumerate(patches[l - 1]))
+            gr.ring_equal(np.array(O.field(l, oracle.OM_H)), G.get(l, "head", ghosted=True), box, (nx0 << l, ny0 << l), sy.A3_BC["periodic"],
+                          what=(name, k, l, "head"))
             # ghost cells of the gap height after the step: PiecewiseLinearFillPatch on coarse-fine sides, copies on domain sides
             a, b = np.array(O.field(l, oracle.OM_B)), G.get(l, "B", ghosted=True)
             assert np.array_equal(a[1:-1, :], b[1:-1, :]) and np.array_equal(a[:, 1:-1], b[:, 1:-1]), (name, k, l, "B ghosts")

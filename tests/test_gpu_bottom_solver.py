@@ -9,6 +9,8 @@ import numpy as np
 import pytest
 
 from suhmo_amd import synthetic as sy
+from tests import ghostring as gr
+from test_gpu_parity import same_ring
 
 pytestmark = pytest.mark.gpu
 
@@ -71,6 +73,8 @@ def test_vcycle_and_solve_bitwise(oracle, hip, case, monkeypatch):
     O.vcycle(sp); G.vcycle(sp); G0.vcycle(sp)
     a, b = G.get(hip.F_PHI), O.get(oracle.F_PHI)
     assert np.array_equal(a, b), float(np.max(np.abs(a - b)))
+    # (a level of one depth ends its cycle on RelaxSolver's residual evaluation, not on a relaxation)
+    same_ring(O, G, oracle, hip, f, case[2], (case[0], "vcycle"), relaxed_last=G.ndepth > 1)
     assert not np.array_equal(a, G0.get(hip.F_PHI))
     assert G.get_option("bottom_solver_iterations") > 0
     assert G.get_option("bottom_solves_one_launch") == 1 and G.get_option("bottom_solves_host_loop") == 0
@@ -78,6 +82,7 @@ def test_vcycle_and_solve_bitwise(oracle, hip, case, monkeypatch):
     ng, hg = G.solve(sp)
     assert no == ng and np.array_equal(ho, hg), (ho, hg)
     assert np.array_equal(G.get(hip.F_PHI), O.get(oracle.F_PHI))
+    same_ring(O, G, oracle, hip, f, case[2], (case[0], "solve"))
     O.residual(); G.residual()
     assert np.array_equal(G.get(hip.F_RES), O.get(oracle.F_RES))
     O.close(); G.close(); G0.close()
@@ -94,14 +99,14 @@ def solve_1024(oracle, hip, max_box, host_loop=False, with_oracle=True):
     G.set_inputs(f); G.build_mg_coefficients()
     sp = dict(sy.SOLVER_DEFAULT)
     ng, hg = G.solve(sp)
-    out = dict(n=ng, hist=hg, phi=G.get(hip.F_PHI), iters=G.get_option("bottom_solver_iterations"),
+    out = dict(n=ng, hist=hg, phi=G.get(hip.F_PHI), ghosted=G.get(hip.F_PHI, ghosted=True), iters=G.get_option("bottom_solver_iterations"),
                one=G.get_option("bottom_solves_one_launch"), host=G.get_option("bottom_solves_host_loop"), ndepth=G.ndepth)
     G.close()
     if with_oracle:
         O = oracle.OracleLevel(n, n, f["dx"], f["dy"], sy.A3_BC, sy.A3_PHYS, max_box=max_box, nthreads=min(16, os.cpu_count() or 1))
         O.set_inputs(f); O.build_mg_coefficients()
         no, ho = O.solve(sp)
-        out["oracle"] = (no, ho, O.get(oracle.F_PHI))
+        out["oracle"] = (no, ho, O.get(oracle.F_PHI), O.get(oracle.F_PHI, ghosted=True))
         O.close()
     return out
 
@@ -113,15 +118,17 @@ def test_both_paths_at_1024(oracle, hip, max_box, bottom_cells, one_launch, monk
     monkeypatch.setenv("SUHMO_ORACLE_BOTTOM", "1")
     r = solve_1024(oracle, hip, max_box)
     assert (1024 >> (r["ndepth"] - 1)) ** 2 == bottom_cells
-    no, ho, po = r["oracle"]
+    no, ho, po, pgo = r["oracle"]
     assert no == r["n"] and np.array_equal(ho, r["hist"]), (no, r["n"], ho[-3:], r["hist"][-3:])
     assert np.array_equal(r["phi"], po)
+    gr.level_ring_equal(pgo, r["ghosted"], (1024, 1024), sy.A3_BC["periodic"], what=("solve", max_box))
     assert r["iters"] > 0
     if one_launch:
         assert r["one"] == r["n"] and r["host"] == 0
         h = solve_1024(oracle, hip, max_box, host_loop=True, with_oracle=False)
         assert h["host"] == h["n"] and h["one"] == 0
         assert h["n"] == r["n"] and np.array_equal(h["hist"], r["hist"]) and np.array_equal(h["phi"], r["phi"])
+        gr.level_ring_equal(pgo, h["ghosted"], (1024, 1024), sy.A3_BC["periodic"], what=("solve, host loop", max_box))
         assert h["iters"] == r["iters"]
     else:
         assert r["host"] == r["n"] and r["one"] == 0
@@ -169,11 +176,12 @@ def test_graph_replay(hip):
         for _ in range(3):
             n_, h = G.solve(sp)
             hs.append(h.copy())
-        res.append((hs, G.get(hip.F_PHI), G.get_option("bottom_solver_iterations"), G.get_option("bottom_solves_one_launch")))
+        res.append((hs, G.get(hip.F_PHI, ghosted=True), G.get_option("bottom_solver_iterations"), G.get_option("bottom_solves_one_launch")))
         G.close()
     (ha, pa, ia, oa), (hb, pb, ib, ob) = res
     assert all(np.array_equal(x, y) for x, y in zip(ha, hb))
-    assert np.array_equal(pa, pb)
+    assert np.array_equal(pa[1:-1, 1:-1], pb[1:-1, 1:-1])
+    gr.level_ring_equal(pb, pa, (n, n), sy.A3_BC["periodic"], what="graph replay against eager")
     assert ia == ib > 0 and oa == ob > 0
 
 
@@ -251,7 +259,7 @@ def test_tutorial_run_first_steps(oracle, monkeypatch):
 def test_hier_vcycle_and_solve_bitwise(oracle, monkeypatch):
     """a hierarchy of box unions: the option set through HipHier.set_option reaches level 0's cycle (the bottom of every AMR V-cycle)"""
     from suhmo_amd.level import F_PHI
-    from test_gpu_hier import pair as hpair, same_levels, UNION, BC_NP
+    from test_gpu_hier import pair as hpair, same_levels, same_rings, UNION, BC_NP
     monkeypatch.setenv("SUHMO_ORACLE_BOTTOM", "1")
     sp = dict(sy.SOLVER_DEFAULT, eps=1e-9, norm_thresh=1e-14, max_iter=6, imin=30)
     O, G, fs = hpair(oracle, UNION, BC_NP, sy.CFG3_PHYS)
@@ -259,11 +267,13 @@ def test_hier_vcycle_and_solve_bitwise(oracle, monkeypatch):
     assert G.get_option("bottom_solver") == 1
     O.vcycle(sp); G.vcycle(sp)
     same_levels(O, G, oracle, ((oracle.F_PHI, F_PHI),), "vcycle")
+    same_rings(O, G, oracle, BC_NP, fs, "vcycle", relaxed_last=True)
     no, ho = O.solve(sp)
     ng, hg = G.solve(sp)
     assert no == ng and np.array_equal(ho, hg), (ho, hg)
     same_levels(O, G, oracle, ((oracle.F_PHI, F_PHI),), "solve")
     assert G.get_option("bottom_solver_iterations") > 0
+    same_rings(O, G, oracle, BC_NP, fs, "solve", exchange=True)
     O.close(); G.close()
 
 

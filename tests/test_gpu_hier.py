@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 from suhmo_amd import synthetic as sy
+from tests import ghostring as gr
 
 pytestmark = pytest.mark.gpu
 BC = dict(type=[[0, 0], [1, 0]], value=[[0.0, 0.0], [0.0, 0.0]], periodic=[0, 1])     # 2lev_base/input.hydro:8-13,76
@@ -17,6 +18,8 @@ CUT = ([(16, 8, 31, 23), (32, 8, 47, 15), (32, 16, 47, 23)], [(44, 22, 59, 41), 
 # periodic in y: two boxes that are neighbours THROUGH the wrap (rows 0-7 and 24-31 of a level of 32 rows), one that spans the period and is its own
 # neighbour, and a finer box on the wrap inside it
 WRAP = ([(16, 0, 31, 7), (16, 24, 31, 31), (40, 0, 55, 31)], [(84, 0, 99, 11), (84, 52, 99, 63)])
+# periodic in y: on both levels a box that spans the period (its own periodic neighbour) lies against the x-lo domain side
+WRAP_SIDE = ([(0, 0, 15, 31), (32, 0, 47, 7), (32, 24, 47, 31)], [(0, 0, 11, 63)])
 UNION = ([(16, 8, 31, 23), (32, 8, 47, 15), (0, 2, 11, 13)],
          [(36, 20, 59, 27), (36, 28, 51, 43), (4, 8, 15, 19)],
          [(80, 44, 103, 51), (12, 20, 23, 31)])
@@ -62,6 +65,31 @@ def same_levels(O, G, oracle, fields, what, skip_covered=False):
     eq(O.coarse.get(oracle.F_PHI), G.coarse.get(level.F_PHI), (what, "base phi"))
 
 
+def same_rings(O, G, oracle, bc, fs, what, relaxed_last=False, exchange=False):
+    """the head's ghost ring of every box of every level and of level 0, bitwise the oracle's: domain and coarse-fine sides as the call left
+    them; with `exchange`, fine-fine and periodic sides (a box across the wrap, or the box itself) after an exchange on both sides, which is
+    where the design refreshes them (suhmo_gsrb.hip:259-260) -- the exchange changes the state, so only after the last call a test judges.
+    After a call whose last step is a relaxation the domain sides also hold the homogeneous boundary condition of the device's own valid
+    cells (npref)."""
+    from suhmo_amd.level import F_PHI
+    nx0, ny0 = O.coarse.nx, O.coarse.ny
+    gr.level_ring_equal(O.coarse.get(oracle.F_PHI, ghosted=True), G.coarse.get(F_PHI, ghosted=True), (nx0, ny0), bc["periodic"],
+                        what=(what, "base"))
+    for l in range(1, O.nlev):
+        dom, lb = (nx0 << l, ny0 << l), O.boxes[l - 1]
+        for k, b in enumerate(lb):
+            gg = G.level[l][k].get(F_PHI, ghosted=True)
+            gr.ring_equal(O.box_get(l, k, oracle.F_PHI, ghosted=True), gg, b, dom, bc["periodic"], lb, ("domain", "coarse-fine"), (what, l, k))
+            if relaxed_last:
+                gr.domain_bc_holds(gg, bc, fs[l][k]["dx"], fs[l][k]["dy"], b, dom, (what, l, k))
+        if not exchange:
+            continue
+        O.exchange(l, oracle.F_PHI); G.exchange(l, F_PHI)
+        for k, b in enumerate(lb):
+            gr.ring_equal(O.box_get(l, k, oracle.F_PHI, ghosted=True), G.level[l][k].get(F_PHI, ghosted=True), b, dom, bc["periodic"], lb,
+                          ("fine-fine", "periodic"), (what, "after exchange", l, k))
+
+
 @pytest.mark.parametrize("bc,ph", [(BC_NP, sy.CFG3_PHYS), (BC_V, MASKPH)], ids=["cfg5-bc", "values-mask"])
 def test_hier_pieces_bitwise(oracle, bc, ph):
     from suhmo_amd.level import F_PHI, F_RES, F_BX, F_BY
@@ -103,7 +131,9 @@ def test_hier_pieces_bitwise(oracle, bc, ph):
                                               ("union-4lev-a-launch-per-ghost-kind", UNION, BC_NP, sy.CFG3_PHYS),
                                               ("union-4lev-base-on-the-streaming-kernel", UNION, BC_NP, sy.CFG3_PHYS),
                                               ("union-4lev-values-mask-base-on-the-streaming-kernel", UNION, BC_V, MASKPH),
-                                              ("union-4lev-base-on-the-streaming-kernel-own-residual-pass", UNION, BC_NP, sy.CFG3_PHYS)],
+                                              ("union-4lev-base-on-the-streaming-kernel-own-residual-pass", UNION, BC_NP, sy.CFG3_PHYS),
+                                              ("union-4lev-merged-launches-off", UNION, BC_V, MASKPH),
+                                              ("wrap-side-self-neighbour", WRAP_SIDE, BC, sy.CFG3_PHYS)],
                          ids=lambda v: v if isinstance(v, str) else "")
 def test_hier_vcycle_and_solve_bitwise(oracle, name, boxes, bc, ph, monkeypatch):
     from suhmo_amd.level import F_PHI, F_RES, F_BX
@@ -126,12 +156,16 @@ def test_hier_vcycle_and_solve_bitwise(oracle, name, boxes, bc, ph, monkeypatch)
     # default: two sweeps per launch on the box levels (suhmo_gsrb.hip:k_gsrb_box_m) and AMRProlongS_2 of a box in one workgroup;
     # a-launch-per-colour-pass: the paths they replace (a launch per colour pass that pushes its side cells; gather, BC and prolongation as three launches;
     # merged_launches=0: a launch for either kind of ghost cell, a norm and a read-back per level, the closing ghost fill on its own)
+    # merged-launches-off and wrap-side-self-neighbour (a box that is its own periodic neighbour, against a domain side): the closing ghost
+    # fill on its own after one launch of four sweeps, which inside a V-cycle hands the second canvas over as the head -- the fill must
+    # write the ring of that canvas (the domain sides of the ring are what catches it)
     opts = {"exchange-per-pass": "push_ghosts=0,fused_relax=0", "whole-level-residuals": "incremental_residual=0", "a-launch-per-colour-pass": "fused_relax=0,fused_prolong=0,merged_launches=0",
-            "a-launch-per-ghost-kind": "merged_launches=0,box_sweeps=2"}
+            "a-launch-per-ghost-kind": "merged_launches=0,box_sweeps=2", "merged-launches-off": "merged_launches=0"}
     options = next((v for k, v in opts.items() if name.endswith(k)), None)
     O, G, fs = pair(oracle, boxes, bc, ph, options=options)
     O.vcycle(sp); G.vcycle(sp)
     same_levels(O, G, oracle, ((oracle.F_PHI, F_PHI), (oracle.F_BX, F_BX)), "vcycle")
+    same_rings(O, G, oracle, bc, fs, (name, "vcycle"), relaxed_last=True)
     no, ho = O.solve(sp)
     ng, hg = G.solve(sp)
     assert no == ng and np.array_equal(ho, hg), (ho, hg)
@@ -140,6 +174,7 @@ def test_hier_vcycle_and_solve_bitwise(oracle, name, boxes, bc, ph, monkeypatch)
     if streams:
         assert (G.coarse.get_option("residual_in_relax_launches") > 0) == (not name.endswith("own-residual-pass"))
     assert (G.get_option("fused_relax_launches") > 0) == (options is None or "fused_relax=0" not in options)
+    same_rings(O, G, oracle, bc, fs, (name, "solve"), exchange=True)
     O.close(); G.close()
 
 

@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 
 from suhmo_amd import synthetic as sy
+from tests import ghostring as gr
 
 pytestmark = pytest.mark.gpu
 ONE = ([(32, 16, 95, 47)], [(80, 44, 159, 83)])
@@ -39,7 +40,8 @@ def make(oracle, boxes, m, nx0=64, ny0=32, bc=sy.A3_BC):
 def test_hier_timestep_bitwise(oracle, name, boxes, mpo, nsteps):
     from suhmo_amd import level as lv
     m = dict(sy.A3_MODEL, **mpo)
-    O, G, sts = make(oracle, boxes, m, bc=sy.CONV_BC if name.startswith("periodic-") else sy.A3_BC)
+    bc = sy.CONV_BC if name.startswith("periodic-") else sy.A3_BC
+    O, G, sts = make(oracle, boxes, m, bc=bc)
     if m.get("use_moulin_source"):
         io, ig = O.moulin_source(**MOULINS), G.moulin_source(**MOULINS)
         assert np.max(np.abs(io - ig)) <= 1e-13 * np.max(io)
@@ -62,6 +64,9 @@ def test_hier_timestep_bitwise(oracle, name, boxes, mpo, nsteps):
                 for nm, fid in (("qwx", oracle.OM_QWX), ("qwy", oracle.OM_QWY)):
                     a, b = np.array(O.field(l, k, fid)), G.get(l, k, nm)
                     assert np.array_equal(a, b, equal_nan=True), (name, step, l, k, nm)
+                # the head's ghost ring after the step, every side (domain, periodic, fine-fine, coarse-fine)
+                gr.ring_equal(np.array(O.field(l, k, oracle.OM_H)), G.get(l, k, "head", ghosted=True), O.boxes[l][k], (64 << l, 32 << l),
+                              bc["periodic"], O.boxes[l], what=(name, step, l, k, "head"))
                 a, b = np.array(O.field(l, k, oracle.OM_B)), G.get(l, k, "B", ghosted=True)
                 assert np.array_equal(a[1:-1, :], b[1:-1, :]) and np.array_equal(a[:, 1:-1], b[:, 1:-1]), (name, step, l, k, "B ghosts")
     O.close(); G.close()

@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 from suhmo_amd import synthetic as sy
+from tests import ghostring as gr
 
 pytestmark = pytest.mark.gpu
 
@@ -26,6 +27,16 @@ def pair(oracle, hip, f, bc, ph, alpha=0.0, beta=-1.0, max_box=16):
     O.set_inputs(f)
     G.set_inputs(f)
     return O, G
+
+
+def same_ring(O, G, oracle, hip, f, bc, what, relaxed_last=False):
+    """the head's ghost ring, every side (domain and periodic), against the oracle's ghosted read-back, bitwise; after a call whose
+    last step is a relaxation the domain sides also hold the homogeneous boundary condition of the device's own valid cells (npref)"""
+    go, gg = O.get(oracle.F_PHI, ghosted=True), G.get(hip.F_PHI, ghosted=True)
+    nx, ny = f["nx"], f["ny"]
+    gr.level_ring_equal(go, gg, (nx, ny), bc["periodic"], what=what)
+    if relaxed_last:
+        gr.domain_bc_holds(gg, bc, f["dx"], f["dy"], (0, 0, nx - 1, ny - 1), (nx, ny), what)
 
 
 CASES = [
@@ -109,6 +120,7 @@ def test_gsrb_fused_variants(oracle, hip, case, variant, hc, sweeps, monkeypatch
     O.gsrb(sweeps); G.gsrb(sweeps)
     a, b = G.get(hip.F_PHI), O.get(oracle.F_PHI)
     assert np.array_equal(a, b), "mismatch at %s" % (np.argwhere(a != b)[:5],)
+    same_ring(O, G, oracle, hip, f, case[2], (case[0], variant, hc, sweeps), relaxed_last=True)
 
 
 @pytest.mark.parametrize("case", CASES, ids=IDS)
@@ -208,11 +220,13 @@ def test_vcycle_and_solve(oracle, hip, case):
     sp = dict(sy.SOLVER_DEFAULT, eps=1e-10, norm_thresh=1e-13, max_iter=6, imin=6)
     O.vcycle(sp); G.vcycle(sp)
     assert np.array_equal(G.get(hip.F_PHI), O.get(oracle.F_PHI))      # one V-cycle: bitwise
+    same_ring(O, G, oracle, hip, f, bc, (case[0], "vcycle"), relaxed_last=True)
     no, ho = O.solve(sp)
     ng, hg = G.solve(sp)
     assert ng == no
     assert np.array_equal(hg, ho)
     assert np.array_equal(G.get(hip.F_PHI), O.get(oracle.F_PHI))      # converged head: bitwise
+    same_ring(O, G, oracle, hip, f, bc, (case[0], "solve"))
 
 
 FUSED_VCYCLE_CASES = [
@@ -247,6 +261,7 @@ def test_vcycle_on_fused_kernels(oracle, hip, case, fused_restrict, rhs_in_relax
     for k in range(2):
         O.vcycle(sp); G.vcycle(sp)
         assert np.array_equal(G.get(hip.F_PHI), O.get(oracle.F_PHI)), (k, float(np.max(np.abs(G.get(hip.F_PHI) - O.get(oracle.F_PHI)))))
+        same_ring(O, G, oracle, hip, f, bc, (case[0], "vcycle", k), relaxed_last=True)
     for d in range(1, G.ndepth):
         assert np.array_equal(G.get(hip.F_RES, depth=d), O.get(oracle.F_RES, depth=d)), ("coarse residual", d)
         assert np.array_equal(G.get(hip.F_RHS, depth=d), O.get(oracle.F_RHS, depth=d)), ("coarse right-hand side", d)
@@ -255,6 +270,7 @@ def test_vcycle_on_fused_kernels(oracle, hip, case, fused_restrict, rhs_in_relax
     no, ho = O.solve(sp)
     ng, hg = G.solve(sp)
     assert ng == no and np.array_equal(hg, ho)
+    same_ring(O, G, oracle, hip, f, bc, (case[0], "solve"))
     if case[0] in ("wide-3strips", "allperiodic", "shmip-512"):          # (depth 1 is wide enough for the streaming kernel there, alpha = 0)
         assert (G.get_option("rhs_in_streaming_launches") > 0) == (rhs_in_relax == 3), G.get_option("rhs_in_streaming_launches")
     # the solve loop's residual evaluation: left behind by the launch that ends each V-cycle (alpha = 0, two-sweep launches), its own pass otherwise
@@ -313,6 +329,7 @@ def test_vcycle_on_tile_kernels(oracle, hip, case, tile, fused_restrict, tile_t,
     for k in range(5):                                                   # from the second on: captured / replayed HIP graphs (two ping-pong states)
         O.vcycle(sp); G.vcycle(sp)
         assert np.array_equal(G.get(hip.F_PHI), O.get(oracle.F_PHI)), (k, float(np.max(np.abs(G.get(hip.F_PHI) - O.get(oracle.F_PHI)))))
+        same_ring(O, G, oracle, hip, f, bc, (case[0], "vcycle", k), relaxed_last=True)
     for d in range(1, G.ndepth):
         assert np.array_equal(G.get(hip.F_RES, depth=d), O.get(oracle.F_RES, depth=d)), ("coarse residual", d)
         assert np.array_equal(G.get(hip.F_RHS, depth=d), O.get(oracle.F_RHS, depth=d)), ("coarse right-hand side", d)
@@ -321,6 +338,7 @@ def test_vcycle_on_tile_kernels(oracle, hip, case, tile, fused_restrict, tile_t,
     ng, hg = G.solve(sp)
     assert ng == no and np.array_equal(hg, ho)
     assert np.array_equal(G.get(hip.F_PHI), O.get(oracle.F_PHI))
+    same_ring(O, G, oracle, hip, f, bc, (case[0], "solve"))
 
 
 def _random_tile_case(seed):
@@ -389,12 +407,14 @@ def test_streaming_cycle_random_shapes(oracle, hip, seed, monkeypatch):
     for k in range(2):
         O.vcycle(sp); G.vcycle(sp)
         assert np.array_equal(G.get(hip.F_PHI), O.get(oracle.F_PHI)), (seed, nx, ny, bc, hc, k)
+        same_ring(O, G, oracle, hip, f, bc, (seed, nx, ny, bc, hc, "vcycle", k), relaxed_last=True)
     for d in range(1, G.ndepth):
         assert np.array_equal(G.get(hip.F_RHS, depth=d), O.get(oracle.F_RHS, depth=d)), (seed, "coarse right-hand side", d)
     no, ho = O.solve(sp)
     ng, hg = G.solve(sp)
     assert ng == no and np.array_equal(hg, ho), (seed, nx, ny, bc, hc, hg, ho)
     assert np.array_equal(G.get(hip.F_PHI), O.get(oracle.F_PHI)) and np.array_equal(G.get(hip.F_RES), O.get(oracle.F_RES)), (seed, nx, ny, bc, hc)
+    same_ring(O, G, oracle, hip, f, bc, (seed, nx, ny, bc, hc, "solve"))
     assert G.get_option("residual_in_relax_launches") > 0 and (G.ndepth < 2 or G.get_option("rhs_in_streaming_launches") > 0)
 
 
@@ -442,6 +462,7 @@ def test_bench_size_vcycle_bitwise(oracle, hip):
         O.vcycle(sp); G.vcycle(sp)
         a, b = G.get(hip.F_PHI), O.get(oracle.F_PHI)
         assert np.array_equal(a, b), (k, float(np.max(np.abs(a - b))))
+        same_ring(O, G, oracle, hip, f, sy.A3_BC, ("4096^2 vcycle", k), relaxed_last=True)
     for d in range(1, G.ndepth):
         assert np.array_equal(G.get(hip.F_RES, depth=d), O.get(oracle.F_RES, depth=d)), ("coarse residual", d)
     O.residual(); G.residual()

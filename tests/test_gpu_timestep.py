@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 from suhmo_amd import synthetic as sy
+from tests import ghostring as gr
 
 pytestmark = pytest.mark.gpu
 GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
@@ -64,6 +65,8 @@ def test_timestep_bitwise(oracle, hipmodel, name, nx, ny, bc, ph, mpo, holes, ns
         for nm, fid in (("qwx", oracle.OM_QWX), ("qwy", oracle.OM_QWY)):
             a, b = np.array(O.field(fid)), G.get(nm)
             assert np.array_equal(a, b, equal_nan=True), (name, k, nm, float(np.nanmax(np.abs(a - b))))   # cd = 0/0 where nothing opens the gap
+        # the head's ghost ring after the step, every side (domain and periodic)
+        gr.level_ring_equal(np.array(O.field(oracle.OM_H)), G.get("head", ghosted=True), (nx, ny), bc["periodic"], what=(name, k, "head"))
         # ghosts of the gap height after the step (CopyGhostCells): edges, corners are never read
         a, b = np.array(O.field(oracle.OM_B)), G.get("B", ghosted=True)
         assert np.array_equal(a[1:-1, :], b[1:-1, :]) and np.array_equal(a[:, 1:-1], b[:, 1:-1])
