@@ -1,5 +1,7 @@
-// suhmo_amr.hip -- two AMR levels: a base level (with its multigrid depths) and ONE rectangular fine patch
-// refined by 2 (cfg3 of BASELINE.json: exec/0_convergence_channelized/2lev_base, fixed refined box).
+// suhmo_amr.hip -- nested AMR levels: a base level (with its multigrid depths) and rectangular patches refined by 2, each
+// properly nested in the one below (cfg3 of BASELINE.json: exec/0_convergence_channelized/2lev_base, fixed refined box; the
+// time loop's hierarchies).  The per-pair operators (suhmo_amr2_*) act on one coarse level and its patch; the residual, V-cycle
+// and solve run on N levels, a pair being the nlev = 2 case.
 //
 // From the reference's own source:
 //   relaxNF / AMRResidualNF / AMROperator / AMRRestrictS / AMRProlongS_2 / AMRNorm
@@ -8,9 +10,9 @@
 //   UpdateOperator / WFlx_level with a coarser level   src/VCAMRNonLinearPoissonOp.cpp:34-64, src/AmrHydro.cpp:1455-1488
 // Restated from upstream Chombo's documented semantics because the fork is not vendored (UNPINNED, SURVEY.md
 // Appendix E): QuadCFInterp, LevelFluxRegister, FORT_AVERAGE, the ghosted coarse copy of AMRProlongS_2 and the AMR
-// FAS cycle order.  The oracle's amr2.c states the same arithmetic; parity is bitwise.
+// FAS cycle order.  The oracle's amr2.c and amrn.c state the same arithmetic; parity is bitwise.
 //
-// The fine level is an ordinary suhmo_level created with desc.i0/nx_global/j0/ny_global: sides of its rectangle
+// A fine level is an ordinary suhmo_level created with desc.i0/nx_global/j0/ny_global: sides of its rectangle
 // inside the domain are coarse-fine sides whose ghost cells are STORED (DV::cfx / DV::ext) and filled here.
 #include "suhmo_common.h"
 
@@ -270,35 +272,6 @@ extern "C" int suhmo_amr2_fine_update_operator(suhmo_level_t *C, suhmo_level_t *
     return suhmo_re_bcoef_unfused(F, 0, st);
 }
 
-// composite residual: fine RES = rhs1 - L1(phi1) after coarseFineInterp (AMRResidualNF :922-939); coarse RES =
-// rhs0 - [applyOpI(phi0) + reflux] (AMRResidual :889-903, AMROperator :942-967); covered coarse cells are zeroed
-// and the max norm over both levels is returned (AMRNorm :1222-1264)
-extern "C" int suhmo_amr2_residual(suhmo_level_t *C, suhmo_level_t *F, double *norm, suhmo_stream_t s)
-{
-    int rc = check_pair(C, F); if (rc) return rc;
-    HIPCHK(hipSetDevice(F->device));
-    hipStream_t st = (hipStream_t)s;
-    const DV &vf = F->d[0].v, &vc = C->d[0].v;
-    if ((rc = suhmo_amr2_cf_interp(C, F, SUHMO_F_PHI, SUHMO_F_PHI, s))) return rc;
-    if ((rc = suhmo_level_residual(F, 0, s))) return rc;
-    if ((rc = suhmo_level_apply_op(C, 0, 0, s))) return rc;                       // LPHI = L0(phi0), kept
-    double *res = suhmo_field(C, 0, SUHMO_F_RES), *lphi = suhmo_field(C, 0, SUHMO_F_LPHI);
-    HIPCHK(hipMemcpyAsync(res, lphi, C->d[0].elems * sizeof(double), hipMemcpyDeviceToDevice, st));
-    int n = vf.ny + vf.nx;                                                        // 2 * (ncy + ncx) coarse faces
-    hipLaunchKernelGGL(k_amr_reflux, dim3((n + 255) / 256), dim3(256), 0, st, vf, F->d[0].fp, vc, C->d[0].fp, res);
-    HIPCHK(hipGetLastError());
-    if ((rc = suhmo_level_axby(C, 0, SUHMO_F_RES, SUHMO_F_RES, SUHMO_F_RHS, -1.0, 1.0, s))) return rc;
-    hipLaunchKernelGGL(k_amr_set_covered, dim3((vf.nx / 2 + 63) / 64, (vf.ny / 2 + 3) / 4), dim3(64, 4), 0, st, vf, vc, res, 0.0);
-    HIPCHK(hipGetLastError());
-    if (norm) {
-        double a = 0.0, b = 0.0;
-        if ((rc = suhmo_level_norm(C, 0, SUHMO_F_RES, 0, &a, s))) return rc;
-        if ((rc = suhmo_level_norm(F, 0, SUHMO_F_RES, 0, &b, s))) return rc;
-        *norm = a > b ? a : b;
-    }
-    return 0;
-}
-
 // reflux (src/VCAMRNonLinearPoissonOp.cpp:555-652): coarse field_c (= L(phi) of the coarse level, e.g. LPHI after
 // applyOpI) += the flux mismatch on the coarse-fine faces; the fine coarse-fine ghosts are interpolated first (:602)
 extern "C" int suhmo_amr2_reflux(suhmo_level_t *C, suhmo_level_t *F, int field_c, suhmo_stream_t s)
@@ -396,71 +369,9 @@ extern "C" int suhmo_amr2_set_covered(suhmo_level_t *C, suhmo_level_t *F, int fi
     return 0;
 }
 
-// one AMR FAS V-cycle (VCycleAMR; same order as oracle/amr2.c:or_amr2_vcycle)
-extern "C" int suhmo_amr2_vcycle(suhmo_level_t *C, suhmo_level_t *F, const suhmo_solver_params_t *sp, suhmo_stream_t s)
-{
-    int rc = check_pair(C, F); if (rc) return rc;
-    ARG(sp);
-    HIPCHK(hipSetDevice(F->device));
-    hipStream_t st = (hipStream_t)s;
-    Depth &DC = C->d[0];
-    const size_t cbytes = DC.elems * sizeof(double);
-    double *rhs0 = suhmo_field(C, 0, SUHMO_F_RHS0), *phiold = suhmo_field(C, 0, SUHMO_F_PHIOLD), *corr = suhmo_field(C, 0, SUHMO_F_CORR);
-    if (!rhs0 || !phiold || !corr) { suhmo_set_error("field allocation failed"); return -2; }
-    // operator of the fine level from the current head
-    if ((rc = suhmo_amr2_cf_interp(C, F, SUHMO_F_PHI, SUHMO_F_PHI, s))) return rc;
-    if (sp->bcoeff_otf && (rc = suhmo_amr2_fine_update_operator(C, F, s))) return rc;
-    // relaxNF(phi1, phi0, rhs1, pre)
-    if ((rc = suhmo_level_gsrb(F, 0, sp->num_smooth, s))) return rc;
-    // AMRRestrictS(skip_res): phi0 under the patch <- average(phi1)
-    if ((rc = suhmo_amr2_average(C, F, SUHMO_F_PHI, SUHMO_F_PHI, s))) return rc;
-    // residuals; covered coarse cells <- average(res1); FAS rhs of the base level = res0' + L0(phi0)
-    if ((rc = suhmo_amr2_residual(C, F, nullptr, s))) return rc;
-    if ((rc = suhmo_amr2_average(C, F, SUHMO_F_RES, SUHMO_F_RES, s))) return rc;
-    HIPCHK(hipMemcpyAsync(rhs0, DC.fp.f[SUHMO_F_RHS], cbytes, hipMemcpyDeviceToDevice, st));
-    if ((rc = suhmo_level_axby(C, 0, SUHMO_F_RHS, SUHMO_F_RES, SUHMO_F_LPHI, 1.0, 1.0, s))) return rc;
-    HIPCHK(hipMemcpyAsync(phiold, DC.fp.f[SUHMO_F_PHI], cbytes, hipMemcpyDeviceToDevice, st));
-    if ((rc = suhmo_level_vcycle(C, sp, s))) return rc;                          // MGCycle of the base level
-    HIPCHK(hipMemcpyAsync(DC.fp.f[SUHMO_F_RHS], rhs0, cbytes, hipMemcpyDeviceToDevice, st));
-    // AMRProlongS_2: phi1 += PROLONG_2_NL(phi0 - phi0_old), coarse correction with inhomogeneous-BC ghosts
-    if ((rc = suhmo_level_axby(C, 0, SUHMO_F_CORR, SUHMO_F_PHI, SUHMO_F_PHIOLD, 1.0, -1.0, s))) return rc;
-    if ((rc = suhmo_amr2_prolong2(C, F, SUHMO_F_CORR, s))) return rc;
-    // relaxNF(phi1, phi0, rhs1, post)
-    if ((rc = suhmo_amr2_cf_interp(C, F, SUHMO_F_PHI, SUHMO_F_PHI, s))) return rc;
-    return suhmo_level_gsrb(F, 0, sp->num_smooth, s);
-}
-
-// AMRMultiGrid::solveNoInit stopping rule on the composite residual norm
-extern "C" int suhmo_amr2_solve(suhmo_level_t *C, suhmo_level_t *F, const suhmo_solver_params_t *sp, int *iters, double *hist, suhmo_stream_t s)
-{
-    ARG(sp);
-    int rc;
-    double rnorm = 0.0;
-    if ((rc = suhmo_amr2_residual(C, F, &rnorm, s))) return rc;
-    double initial_rnorm = rnorm, norm_last = 2.0 * initial_rnorm;
-    int iter = 0;
-    if (hist) hist[0] = rnorm;
-    bool goNorm = rnorm > sp->norm_thresh, goRedu = rnorm > sp->eps * initial_rnorm, goIter = iter < sp->max_iter;
-    bool goHang = iter < sp->imin || rnorm < (1.0 - sp->hang) * norm_last, goMin = iter < sp->iter_min;
-    while (goMin || (goIter && goRedu && goHang && goNorm)) {
-        norm_last = rnorm;
-        if ((rc = suhmo_amr2_vcycle(C, F, sp, s))) return rc;
-        if ((rc = suhmo_amr2_residual(C, F, &rnorm, s))) return rc;
-        iter++;
-        if (hist) hist[iter] = rnorm;
-        goNorm = rnorm > sp->norm_thresh; goRedu = rnorm > sp->eps * initial_rnorm; goIter = iter < sp->max_iter;
-        goHang = iter < sp->imin || rnorm < (1.0 - sp->hang) * norm_last; goMin = iter < sp->iter_min;
-    }
-    // the domain sides of the rings as the solve's last residual evaluation leaves them in the oracle (as suhmo_level_solve)
-    if ((rc = suhmo_level_fill_ghosts(C, 0, SUHMO_F_PHI, 0, s)) || (rc = suhmo_level_fill_ghosts(F, 0, SUHMO_F_PHI, 0, s))) return rc;
-    if (iters) *iters = iter;
-    return 0;
-}
-
-
 // ================================================================ N nested levels
 // levels[0] = base level, levels[l] = patch of level l (properly nested in level l-1): oracle/amrn.c states the same
-// cycle.  The two-level entry points above are the nlev = 2 case.
+// cycle.  The residual, V-cycle and solve of a pair (suhmo_amr2_*) are the nlev = 2 case.
 // Rank strips: a rank holds of every level the rows of its own physical slab, so levels[l] may be NULL on a rank the
 // patch of level l does not reach.  Such a rank still runs the coarse half of every pair it has a coarse strip of (the
 // FAS right-hand side res' + L(phi) replaces rhs on the WHOLE coarse level) and every base-level collective.
@@ -505,13 +416,9 @@ int vcycle_amr(suhmo_level_t **lv, int l, const suhmo_solver_params_t *sp, suhmo
     if ((rc = cf_phi(lv, l, s))) return rc;
     if (sp->bcoeff_otf) {                                          // UpdateOperator of level l with its coarser level
         if ((rc = cf_phi(lv, l - 1, s))) return rc;                // the coarser level's own coarse-fine ghosts (its gradient reads them)
-        if (F && (rc = suhmo_grad_cc(F, 0, st))) return rc;
-        if (C && (rc = suhmo_grad_cc(C, 0, st))) return rc;        // every rank of the coarser level's communicator (gradient halo exchange)
-        if (F) {
-            if ((rc = suhmo_amr2_cf_interp(C, F, SUHMO_F_GRADX, SUHMO_F_GRADX, s))) return rc;
-            if ((rc = suhmo_amr2_cf_interp(C, F, SUHMO_F_GRADY, SUHMO_F_GRADY, s))) return rc;
-            if ((rc = suhmo_re_bcoef_unfused(F, 0, st))) return rc;
-        }
+        if (F) rc = suhmo_amr2_fine_update_operator(C, F, s);
+        else if (C) rc = suhmo_grad_cc(C, 0, st);                  // every rank of the coarser level's communicator (gradient halo exchange)
+        if (rc) return rc;
     }
     if (F) {
         if ((rc = suhmo_level_gsrb(F, 0, sp->num_smooth, s))) return rc;                       // relaxNF
@@ -559,13 +466,12 @@ int check_hierarchy(suhmo_level_t **lv, int nlev)
     }
     return 0;
 }
-}  // namespace
-int suhmo_amr_check_hierarchy(suhmo_level_t **lv, int nlev) { return check_hierarchy(lv, nlev); }   // for suhmo_step.hip
-
-extern "C" int suhmo_amr_residual(suhmo_level_t **lv, int nlev, double *norm, suhmo_stream_t s)
+// composite residual: RES of the finest level = rhs - L(phi) after coarseFineInterp (AMRResidualNF :922-939); of every coarser level
+// rhs - [applyOpI(phi) + reflux] (AMRResidual :889-903, AMROperator :942-967); covered coarse cells are zeroed and the max norm over
+// all levels is returned (AMRNorm :1222-1264)
+int amr_residual(suhmo_level_t **lv, int nlev, double *norm, suhmo_stream_t s)
 {
-    int rc = check_hierarchy(lv, nlev); if (rc) return rc;
-    HIPCHK(hipSetDevice(lv[0]->device));
+    int rc;
     int top = nlev - 1;
     if ((rc = cf_phi(lv, top, s))) return rc;
     if (lv[top] && (rc = suhmo_level_residual(lv[top], 0, s))) return rc;                  // AMRResidualNF on the finest level
@@ -581,6 +487,26 @@ extern "C" int suhmo_amr_residual(suhmo_level_t **lv, int nlev, double *norm, su
     }
     return 0;
 }
+int amr_solve(suhmo_level_t **lv, int nlev, const suhmo_solver_params_t *sp, int *iters, double *hist, suhmo_stream_t s)
+{
+    int rc = suhmo_solve_no_init(sp, iters, hist, [&](double *rnorm) { return amr_residual(lv, nlev, rnorm, s); },
+                                 [&] { return vcycle_amr(lv, nlev - 1, sp, s); });
+    if (rc) return rc;
+    // the domain sides of the rings as the solve's last residual evaluation leaves them in the oracle (as suhmo_level_solve);
+    // patch sides inside the domain keep their coarse-fine data
+    for (int l = 0; l < nlev; l++)
+        if (lv[l] && (rc = suhmo_level_fill_ghosts(lv[l], 0, SUHMO_F_PHI, 0, s))) return rc;
+    return 0;
+}
+}  // namespace
+int suhmo_amr_check_hierarchy(suhmo_level_t **lv, int nlev) { return check_hierarchy(lv, nlev); }   // for suhmo_step.hip
+
+extern "C" int suhmo_amr_residual(suhmo_level_t **lv, int nlev, double *norm, suhmo_stream_t s)
+{
+    int rc = check_hierarchy(lv, nlev); if (rc) return rc;
+    HIPCHK(hipSetDevice(lv[0]->device));
+    return amr_residual(lv, nlev, norm, s);
+}
 extern "C" int suhmo_amr_vcycle(suhmo_level_t **lv, int nlev, const suhmo_solver_params_t *sp, suhmo_stream_t s)
 {
     int rc = check_hierarchy(lv, nlev); if (rc) return rc;
@@ -591,27 +517,32 @@ extern "C" int suhmo_amr_vcycle(suhmo_level_t **lv, int nlev, const suhmo_solver
 extern "C" int suhmo_amr_solve(suhmo_level_t **lv, int nlev, const suhmo_solver_params_t *sp, int *iters, double *hist, suhmo_stream_t s)
 {
     ARG(sp);
-    int rc;
-    double rnorm = 0.0;
-    if ((rc = suhmo_amr_residual(lv, nlev, &rnorm, s))) return rc;
-    double initial_rnorm = rnorm, norm_last = 2.0 * initial_rnorm;
-    int iter = 0;
-    if (hist) hist[0] = rnorm;
-    bool goNorm = rnorm > sp->norm_thresh, goRedu = rnorm > sp->eps * initial_rnorm, goIter = iter < sp->max_iter;
-    bool goHang = iter < sp->imin || rnorm < (1.0 - sp->hang) * norm_last, goMin = iter < sp->iter_min;
-    while (goMin || (goIter && goRedu && goHang && goNorm)) {
-        norm_last = rnorm;
-        if ((rc = suhmo_amr_vcycle(lv, nlev, sp, s))) return rc;
-        if ((rc = suhmo_amr_residual(lv, nlev, &rnorm, s))) return rc;
-        iter++;
-        if (hist) hist[iter] = rnorm;
-        goNorm = rnorm > sp->norm_thresh; goRedu = rnorm > sp->eps * initial_rnorm; goIter = iter < sp->max_iter;
-        goHang = iter < sp->imin || rnorm < (1.0 - sp->hang) * norm_last; goMin = iter < sp->iter_min;
-    }
-    // the domain sides of the rings as the solve's last residual evaluation leaves them in the oracle (as suhmo_level_solve);
-    // patch sides inside the domain keep their coarse-fine data
-    for (int l = 0; l < nlev; l++)
-        if (lv[l] && (rc = suhmo_level_fill_ghosts(lv[l], 0, SUHMO_F_PHI, 0, s))) return rc;
-    if (iters) *iters = iter;
-    return 0;
+    int rc = check_hierarchy(lv, nlev); if (rc) return rc;
+    HIPCHK(hipSetDevice(lv[0]->device));
+    return amr_solve(lv, nlev, sp, iters, hist, s);
+}
+
+// the two-level entry points: any pair check_pair accepts, as the nlev = 2 case (oracle/amr2.c states the same arithmetic as amrn.c)
+extern "C" int suhmo_amr2_residual(suhmo_level_t *C, suhmo_level_t *F, double *norm, suhmo_stream_t s)
+{
+    int rc = check_pair(C, F); if (rc) return rc;
+    HIPCHK(hipSetDevice(F->device));
+    suhmo_level_t *lv[2] = {C, F};
+    return amr_residual(lv, 2, norm, s);
+}
+extern "C" int suhmo_amr2_vcycle(suhmo_level_t *C, suhmo_level_t *F, const suhmo_solver_params_t *sp, suhmo_stream_t s)
+{
+    int rc = check_pair(C, F); if (rc) return rc;
+    ARG(sp);
+    HIPCHK(hipSetDevice(F->device));
+    suhmo_level_t *lv[2] = {C, F};
+    return vcycle_amr(lv, 1, sp, s);
+}
+extern "C" int suhmo_amr2_solve(suhmo_level_t *C, suhmo_level_t *F, const suhmo_solver_params_t *sp, int *iters, double *hist, suhmo_stream_t s)
+{
+    ARG(sp);
+    int rc = check_pair(C, F); if (rc) return rc;
+    HIPCHK(hipSetDevice(F->device));
+    suhmo_level_t *lv[2] = {C, F};
+    return amr_solve(lv, 2, sp, iters, hist, s);
 }

@@ -290,3 +290,28 @@ int suhmo_bottom_configure(suhmo_level *L, int solver, long one_launch_max_cells
 long suhmo_bottom_counter(const suhmo_level *L, int which);
 int suhmo_bottom_solve(suhmo_level *L, int dep, int tail, hipStream_t st);
 static inline int suhmo_halo_rows(const DV &v) { return v.gy < v.ny ? v.gy : v.ny; }
+// AMRMultiGrid::solveNoInit's stopping rule, for every level layout: `residual(&norm)` evaluates the residual and its norm, `cycle()`
+// runs one V-cycle; hist[0..*iters] receive the norms.  What differs between layouts (a cycle that leaves its residual behind, the
+// closing fill of the rings) stays with the callables and the caller.
+template <class Residual, class Cycle>
+int suhmo_solve_no_init(const suhmo_solver_params_t *sp, int *iters, double *hist, Residual residual, Cycle cycle)
+{
+    int rc;
+    double rnorm = 0.0;
+    if ((rc = residual(&rnorm))) return rc;
+    const double initial_rnorm = rnorm;
+    double norm_last = 2.0 * initial_rnorm;
+    int iter = 0;
+    if (hist) hist[0] = rnorm;
+    for (;;) {
+        const bool goNorm = rnorm > sp->norm_thresh, goRedu = rnorm > sp->eps * initial_rnorm, goIter = iter < sp->max_iter;
+        const bool goHang = iter < sp->imin || rnorm < (1.0 - sp->hang) * norm_last, goMin = iter < sp->iter_min;
+        if (!(goMin || (goIter && goRedu && goHang && goNorm))) break;
+        norm_last = rnorm;
+        if ((rc = cycle()) || (rc = residual(&rnorm))) return rc;
+        iter++;
+        if (hist) hist[iter] = rnorm;
+    }
+    if (iters) *iters = iter;
+    return 0;
+}

@@ -227,42 +227,26 @@ extern "C" int suhmo_level_solve(suhmo_level_t *L, const suhmo_solver_params_t *
     SUHMO_TIME("AMRFASMultiGrid::solve");
     ARG(L && sp);
     HIPCHK(hipSetDevice(L->device));
-    int rc;
-    double rnorm = 0.0;
-    if ((rc = suhmo_level_residual_and_norm(L, &rnorm, (hipStream_t)s))) return rc;
-    double initial_rnorm = rnorm, norm_last = 2.0 * initial_rnorm;
-    int iter = 0;
-    if (hist) hist[0] = rnorm;
-    bool goNorm = rnorm > sp->norm_thresh;
-    bool goRedu = rnorm > sp->eps * initial_rnorm;
-    bool goIter = iter < sp->max_iter;
-    bool goHang = iter < sp->imin || rnorm < (1.0 - sp->hang) * norm_last;
-    bool goMin = iter < sp->iter_min;
-    while (goMin || (goIter && goRedu && goHang && goNorm)) {
-        norm_last = rnorm;
-        // (the launch that ends the cycle leaves rhs - L(phi) of the final phi in RES when it can: the pass below is then not needed)
+    // (the launch that ends the cycle leaves rhs - L(phi) of the final phi in RES when it can: the pass below is then not needed)
+    bool have_res = false;
+    int np = 0;
+    auto residual = [&](double *rnorm) {
+        if (!have_res) return suhmo_level_residual_and_norm(L, rnorm, (hipStream_t)s);      // (two launches: the pass leaves the partial maxima too)
+        if (np > 0) return suhmo_level_norm_from_partials(L, np, rnorm, (hipStream_t)s);
+        return suhmo_level_norm(L, 0, SUHMO_F_RES, 0, rnorm, s);
+    };
+    auto cycle = [&] {
         L->resout_req = 1 | 4; L->resout_rhs = nullptr; L->resout_done = 0; L->resout_np = 0;      // (4: and the partial maxima of its max norm)
-        rc = suhmo_level_vcycle(L, sp, s);
-        const bool have_res = L->resout_done != 0;
-        const int np = have_res ? L->resout_np : 0;
+        int rc = suhmo_level_vcycle(L, sp, s);
+        have_res = L->resout_done != 0;
+        np = have_res ? L->resout_np : 0;
         L->resout_req = 0; L->resout_done = 0; L->resout_np = 0;
-        if (rc) return rc;
-        if (!have_res) rc = suhmo_level_residual_and_norm(L, &rnorm, (hipStream_t)s);        // (two launches: the pass leaves the partial maxima too)
-        else if (np > 0) rc = suhmo_level_norm_from_partials(L, np, &rnorm, (hipStream_t)s);
-        else rc = suhmo_level_norm(L, 0, SUHMO_F_RES, 0, &rnorm, s);
-        if (rc) return rc;
-        iter++;
-        if (hist) hist[iter] = rnorm;
-        goNorm = rnorm > sp->norm_thresh;
-        goRedu = rnorm > sp->eps * initial_rnorm;
-        goIter = iter < sp->max_iter;
-        goHang = iter < sp->imin || rnorm < (1.0 - sp->hang) * norm_last;
-        goMin = iter < sp->iter_min;
-    }
+        return rc;
+    };
+    int rc = suhmo_solve_no_init(sp, iters, hist, residual, cycle);
+    if (rc) return rc;
     // the solve ends on the residual evaluation of the final phi, whose ghost fill is the inhomogeneous one (the oracle's residual
     // leaves it in the ring); the device's residual passes evaluate the boundary values on the fly and leave the relaxation's
     // homogeneous ring behind: one fill of the ring, as the caller reads it
-    if ((rc = suhmo_level_fill_ghosts(L, 0, SUHMO_F_PHI, 0, s))) return rc;
-    if (iters) *iters = iter;
-    return 0;
+    return suhmo_level_fill_ghosts(L, 0, SUHMO_F_PHI, 0, s);
 }

@@ -762,23 +762,9 @@ extern "C" int suhmo_hier_solve(suhmo_hier_t *H, const suhmo_solver_params_t *sp
     // average from level 1 changed its head
     if ((rc = check_hier(H))) return rc;
     HIPCHK(hipSetDevice(H->device));
-    double rnorm = 0.0;
-    if ((rc = hier_residual_(H, &rnorm, s))) return rc;
-    double initial_rnorm = rnorm, norm_last = 2.0 * initial_rnorm;
-    int iter = 0;
-    if (hist) hist[0] = rnorm;
-    bool goNorm = rnorm > sp->norm_thresh, goRedu = rnorm > sp->eps * initial_rnorm, goIter = iter < sp->max_iter;
-    bool goHang = iter < sp->imin || rnorm < (1.0 - sp->hang) * norm_last, goMin = iter < sp->iter_min;
-    while (goMin || (goIter && goRedu && goHang && goNorm)) {
-        norm_last = rnorm;
-        { SUHMO_TIME("AMRFASMultiGrid::VCycle(AMR)"); rc = vcycle_amr(H, H->nlev - 1, sp, s); }
-        if (rc) return rc;
-        if ((rc = hier_residual_(H, &rnorm, s))) return rc;
-        iter++;
-        if (hist) hist[iter] = rnorm;
-        goNorm = rnorm > sp->norm_thresh; goRedu = rnorm > sp->eps * initial_rnorm; goIter = iter < sp->max_iter;
-        goHang = iter < sp->imin || rnorm < (1.0 - sp->hang) * norm_last; goMin = iter < sp->iter_min;
-    }
+    rc = suhmo_solve_no_init(sp, iters, hist, [&](double *rnorm) { return hier_residual_(H, rnorm, s); },
+                             [&] { SUHMO_TIME("AMRFASMultiGrid::VCycle(AMR)"); return vcycle_amr(H, H->nlev - 1, sp, s); });
+    if (rc) return rc;
     // the domain sides of every ring as the solve's last residual evaluation leaves them in the oracle: the inhomogeneous boundary
     // condition (as suhmo_level_solve); the residual kernels evaluate it on the fly over the relaxation's homogeneous fill
     if ((rc = suhmo_level_fill_ghosts(base_of(H), 0, SUHMO_F_PHI, 0, s))) return rc;
@@ -786,6 +772,5 @@ extern "C" int suhmo_hier_solve(suhmo_hier_t *H, const suhmo_solver_params_t *sp
         suhmo_multi m;
         if ((rc = multi_of(H, l, HST(s), m)) || (rc = suhmo_multi_fill_ghosts(m, SUHMO_F_PHI, 0, HST(s)))) return rc;
     }
-    if (iters) *iters = iter;
     return 0;
 }

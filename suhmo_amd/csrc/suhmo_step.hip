@@ -340,6 +340,17 @@ static int diffusion_terms(suhmo_level *L, const suhmo_model_params_t *mp, hipSt
     HIPCHK(hipGetLastError());
     return 0;
 }
+// the lagged diffusion terms (diffusion), then the melt rate with RHS_h (final_ = 0) or with the gap-height update (1) of one level
+static int level_melt(suhmo_level *L, const suhmo_model_params_t *mp, double dt, int final_, bool diffusion, hipStream_t st)
+{
+    Depth &D = L->d[0];
+    int rc;
+    if (diffusion && (rc = diffusion_terms(L, mp, st))) return rc;
+    if (!final_) hipLaunchKernelGGL(k_melt<0>, dim3((D.v.nx + 63) / 64, (D.v.ny + 3) / 4), dim3(64, 4), 0, st, D.v, D.fp, L->ph, *mp, dt);
+    else hipLaunchKernelGGL(k_melt<1>, dim3((D.v.nx + 63) / 64, (D.v.ny + 3) / 4), dim3(64, 4), 0, st, D.v, D.fp, L->ph, *mp, dt);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
 // SolveForGap_nl (src/AmrHydro.cpp:593-662): (1 - dt diffFactor div(D grad)) b = RES on a second level handle with the
 // linear operator (alpha = 1, aCoef = 1, beta = dt diffFactor, bCoef = D, no nonlinear term), FixedNeumBCFill = Neumann 0.
 // [Chombo] VCAMRPoissonOp2 / AMRMultiGrid are not in the reference's tree: the cycle is the FAS cycle of suhmo_fas.hip,
@@ -386,6 +397,13 @@ static void gap_solver_params(suhmo_solver_params_t &sp, int cur_step)
     sp.num_smooth = 2; sp.num_bottom = 4; sp.max_iter = 100; sp.iter_min = 2; sp.imin = cur_step < 50 ? 10 : 5;
     sp.eps = 1.0e-7; sp.hang = 1.0e-6; sp.norm_thresh = 1.0e-7; sp.bcoeff_otf = 0; sp.max_depth = -1;
 }
+// SolveForHead_nl, :737-762
+static void head_solver_params(suhmo_solver_params_t &sp, int cur_step)
+{
+    sp.num_smooth = 4; sp.num_bottom = 16; sp.max_iter = 100; sp.iter_min = 2; sp.imin = 5;
+    sp.eps = 1.0e-7; sp.hang = 0.01; sp.norm_thresh = 1.0e-7; sp.bcoeff_otf = 1; sp.max_depth = -1;
+    if (cur_step < 50) { sp.num_bottom = 10; sp.eps = 1.0e-10; sp.hang = 0.0001; sp.imin = 20; }
+}
 static int solve_gap_implicit(suhmo_level *L, const suhmo_model_params_t *mp, double dt, int cur_step, hipStream_t st)
 {
     int rc = gap_level_prepare(L, mp, dt, st); if (rc) return rc;
@@ -399,64 +417,108 @@ static int solve_gap_implicit(suhmo_level *L, const suhmo_model_params_t *mp, do
     return 0;
 }
 
+// ------------------------------------------------------------------ AmrHydro::timeStepFAS, once for every level layout
+// the checks every time step starts with, and the fields of every level its phases write
+static const int step_fields[] = {SUHMO_F_MR, SUHMO_F_PW, SUHMO_F_QWX, SUHMO_F_QWY, SUHMO_F_HLAG, SUHMO_F_CD, SUHMO_F_GRADX, SUHMO_F_GRADY, SUHMO_F_RE};
+static int check_step_args(const suhmo_model_params_t *mp, double dt, int cur_step)
+{
+    ARG(mp); ARG(dt > 0 && cur_step >= 1);
+    if (mp->use_impl_diff && mp->diffFactor == 0.0) { suhmo_set_error("use_ImplDiff with diffFactor = 0"); return -1; }
+    return 0;
+}
+// the Picard test after iteration ite_idx (:3169-3195), given max h and max |h_lagged - h| over the cells no finer level covers
+static int picard_test(double maxHead, double maxd, int ite_idx, int cur_step, const suhmo_model_params_t *mp, bool &converged)
+{
+    const double res = picard_quotient(maxd, maxHead);
+    if (ite_idx > 100) { suhmo_set_error("does not converge (Picard iterations > 100)"); return -6; }   // :3190-3195
+    if (cur_step < 2) converged = res < 0.05 && ite_idx > 2;
+    else if (cur_step < 50) converged = res < 0.05;
+    else converged = res < mp->eps_picard;
+    return 0;
+}
+// The skeleton over a level layout Y (OneLevel, Nested, BoxUnions below).  Y has `nlev`, `base` (level 0's handle, the one the head
+// solve's multigrid depths hang off) and `st`; its hooks gap_ghosts(l), chain(l) and melt_final(l) act on level l, the others on every
+// level in the layout's own launch order.
+template <class Y>
+static int timestep_fas(Y &y, const suhmo_model_params_t *mp, double dt, int cur_step, int *picard_iters, int *vcycles)
+{
+    int rc;
+    // [I] ghosts of b (exchange + CopyGhostCells, :2385,:2429); ghosts of h are evaluated on the fly.  MGnewOp coarsening of B
+    // (+ static Pi, zb, mask, aCoef): once per step, b does not change in [II]
+    for (int l = 0; l < y.nlev; l++) if ((rc = y.gap_ghosts(l))) return rc;
+    if ((rc = suhmo_build_mg_coefficients(y.base, false, y.st))) return rc;      // bCoef: re-averaged by every V-cycle (bcoeff_otf)
+    suhmo_solver_params_t sp;
+    head_solver_params(sp, cur_step);
+    int ite_idx = 0, nv = 0;
+    for (bool converged = false; !converged; ite_idx++) {                         // [II]
+        if ((rc = y.lag_head())) return rc;                                       // h_lagged = h, coarse-fine ghosts of b and mR
+        for (int l = 0; l < y.nlev; l++) if ((rc = y.chain(l))) return rc;       // grad h, Re, Qw
+        if ((rc = y.head_rhs(mp, dt))) return rc;                                 // bCoef, melt rate, RHS_h
+        int it = 0;
+        if ((rc = y.solve_head(sp, &it))) return rc;                              // SolveForHead_nl, CoarseAverage of h
+        nv += it;
+        double maxHead = 0.0, maxd = 0.0;
+        if ((rc = y.picard_maxima(&maxHead, &maxd)) || (rc = picard_test(maxHead, maxd, ite_idx, cur_step, mp, converged))) return rc;
+    }
+    // [III] level by level: the coarse gap height is already updated when the fine ghost cells are filled
+    for (int l = 0; l < y.nlev; l++) {
+        if ((rc = y.chain(l)) || (rc = y.melt_final(l, mp, dt))) return rc;
+        if (!mp->use_impl_diff && (rc = y.gap_ghosts(l))) return rc;             // (implicit: b stays, RES = b + dt RHS)
+    }
+    if (mp->use_impl_diff && (rc = y.solve_gap(mp, dt, cur_step))) return rc;    // SolveForGap_nl :3425-3455, then the ghosts of b
+    if (picard_iters) *picard_iters = ite_idx;
+    if (vcycles) *vcycles = nv;
+    return 0;
+}
+
+// ------------------------------------------------------------------ the time step on one level
+struct OneLevel {
+    suhmo_level *base;
+    hipStream_t st;
+    int nlev = 1;
+    int gap_ghosts(int) { int rc = suhmo_copy_ghosts(base, 0, SUHMO_F_B, st); return rc ? rc : exchange1(base, SUHMO_F_B, st); }   // :3419-3420 / :3451-3452
+    int lag_head()
+    {
+        Depth &D = base->d[0];
+        HIPCHK(hipMemcpyAsync(D.fp.f[SUHMO_F_HLAG], D.fp.f[SUHMO_F_PHI], D.elems * sizeof(double), hipMemcpyDeviceToDevice, st));
+        return 0;
+    }
+    int chain(int) { return lagged_chain(base, st); }
+    int head_rhs(const suhmo_model_params_t *mp, double dt)
+    {
+        int rc;
+        if ((rc = suhmo_bcoef_faces(base, 0, st))) return rc;                          // aCoeff_bCoeff :3087-3102
+        if ((rc = level_melt(base, mp, dt, 0, mp->diffFactor != 0.0, st))) return rc;   // lagged melt rate :2548-2551, :2982-2992
+        return exchange1(base, SUHMO_F_RHS, st);                                        // rank strips relax their halo rows redundantly
+    }
+    int solve_head(const suhmo_solver_params_t &sp, int *it) { return suhmo_level_solve(base, &sp, it, nullptr, st); }
+    int picard_maxima(double *maxh, double *maxd)                                       // computeMax over all ranks
+    {
+        Depth &D = base->d[0];
+        return ::picard_maxima(base, D.fp.f[SUHMO_F_PHI], D.fp.f[SUHMO_F_HLAG], maxh, maxd, st, Excl{0, 0, 0, 0}, nullptr, true);
+    }
+    int melt_final(int, const suhmo_model_params_t *mp, double dt) { return level_melt(base, mp, dt, 1, false, st); }
+    int solve_gap(const suhmo_model_params_t *mp, double dt, int cur_step)
+    {
+        int rc = solve_gap_implicit(base, mp, dt, cur_step, st);
+        return rc ? rc : gap_ghosts(0);
+    }
+};
+
 extern "C" int suhmo_level_timestep(suhmo_level_t *L, const suhmo_model_params_t *mp, double dt, int cur_step,
                                     int *picard_iters, int *vcycles, suhmo_stream_t s)
 {
     SUHMO_TIME("AmrHydro::timeStepFAS");
-    ARG(L && mp); ARG(dt > 0 && cur_step >= 1);
-    if (mp->use_impl_diff && mp->diffFactor == 0.0) { suhmo_set_error("use_ImplDiff with diffFactor = 0"); return -1; }
+    ARG(L);
+    int rc = check_step_args(mp, dt, cur_step); if (rc) return rc;
     Depth &D = L->d[0];
     if (L->desc.nx_global > 0 || (D.v.ext[0] && !D.v.rk[0]) || (D.v.ext[1] && !D.v.rk[1])) { suhmo_set_error("timestep on an AMR patch is not built yet"); return -5; }
     if ((D.v.ext[0] || D.v.ext[1]) && !(L->ex && L->ar)) { suhmo_set_error("timestep on a rank strip needs the exchange hooks (suhmo_level_attach_rccl / suhmo_level_set_hooks)"); return -1; }
     HIPCHK(hipSetDevice(L->device));
-    hipStream_t st = (hipStream_t)s;
     if (mp->use_moulin_source && !L->d[0].fp.f[SUHMO_F_MSRC]) { suhmo_set_error("use_moulin_source without suhmo_level_moulin_source"); return -1; }
-    static const int need[] = {SUHMO_F_MR, SUHMO_F_PW, SUHMO_F_QWX, SUHMO_F_QWY, SUHMO_F_HLAG, SUHMO_F_CD,
-                               SUHMO_F_GRADX, SUHMO_F_GRADY, SUHMO_F_RE};
-    for (int f : need) if (!suhmo_field(L, 0, f)) { suhmo_set_error("field allocation failed"); return -2; }
-    int rc;
-    // [I] ghosts of b (exchange + CopyGhostCells, :2385,:2429); ghosts of h are evaluated on the fly
-    if ((rc = suhmo_copy_ghosts(L, 0, SUHMO_F_B, st))) return rc;
-    if ((rc = exchange1(L, SUHMO_F_B, st))) return rc;
-    // MGnewOp coarsening of B (+ static Pi, zb, mask, aCoef): once per step, b does not change in [II]
-    if ((rc = suhmo_build_mg_coefficients(L, false, (hipStream_t)s))) return rc;    // bCoef: re-averaged by every V-cycle (bcoeff_otf)
-    suhmo_solver_params_t sp;                                      // SolveForHead_nl, :737-762
-    sp.num_smooth = 4; sp.num_bottom = 16; sp.max_iter = 100; sp.iter_min = 2; sp.imin = 5;
-    sp.eps = 1.0e-7; sp.hang = 0.01; sp.norm_thresh = 1.0e-7; sp.bcoeff_otf = 1; sp.max_depth = -1;
-    if (cur_step < 50) { sp.num_bottom = 10; sp.eps = 1.0e-10; sp.hang = 0.0001; sp.imin = 20; }
-    const dim3 blk(64, 4), grd((D.v.nx + 63) / 64, (D.v.ny + 3) / 4);
-    bool converged = false;
-    int ite_idx = 0, cur_picard = 0, nv = 0;
-    while (!converged) {                                           // [II]
-        HIPCHK(hipMemcpyAsync(D.fp.f[SUHMO_F_HLAG], D.fp.f[SUHMO_F_PHI], D.elems * sizeof(double), hipMemcpyDeviceToDevice, st));
-        if ((rc = lagged_chain(L, st))) return rc;
-        if ((rc = suhmo_bcoef_faces(L, 0, st))) return rc;                          // aCoeff_bCoeff :3087-3102
-        if (mp->diffFactor != 0.0 && (rc = diffusion_terms(L, mp, st))) return rc;   // lagged melt rate :2548-2551, :2982-2992
-        hipLaunchKernelGGL(k_melt<0>, grd, blk, 0, st, D.v, D.fp, L->ph, *mp, dt);
-        HIPCHK(hipGetLastError());
-        if ((rc = exchange1(L, SUHMO_F_RHS, st))) return rc;        // rank strips relax their halo rows redundantly
-        int it = 0;
-        if ((rc = suhmo_level_solve(L, &sp, &it, nullptr, s))) return rc;
-        nv += it;
-        double maxHead = 0.0, maxd = 0.0, res = 0.0;
-        if ((rc = picard_maxima(L, D.fp.f[SUHMO_F_PHI], D.fp.f[SUHMO_F_HLAG], &maxHead, &maxd, st, Excl{0, 0, 0, 0}, nullptr, true))) return rc;   // computeMax over all ranks
-        res = picard_quotient(maxd, maxHead);
-        if (ite_idx > 100) { suhmo_set_error("does not converge (Picard iterations > 100)"); return -6; }   // :3190-3195
-        if (cur_step < 2) { if (res < 0.05 && cur_picard > 2) converged = true; }
-        else if (cur_step < 50) { if (res < 0.05) converged = true; }
-        else { if (res < mp->eps_picard) converged = true; }
-        ite_idx++; cur_picard++;
-    }
-    // [III]
-    if ((rc = lagged_chain(L, st))) return rc;
-    hipLaunchKernelGGL(k_melt<1>, grd, blk, 0, st, D.v, D.fp, L->ph, *mp, dt);
-    HIPCHK(hipGetLastError());
-    if (mp->use_impl_diff && (rc = solve_gap_implicit(L, mp, dt, cur_step, st))) return rc;   // :3425-3439
-    if ((rc = suhmo_copy_ghosts(L, 0, SUHMO_F_B, st))) return rc;  // :3419-3420 / :3451-3452
-    if ((rc = exchange1(L, SUHMO_F_B, st))) return rc;
-    if (picard_iters) *picard_iters = ite_idx;
-    if (vcycles) *vcycles = nv;
-    return 0;
+    for (int f : step_fields) if (!suhmo_field(L, 0, f)) { suhmo_set_error("field allocation failed"); return -2; }
+    OneLevel y{L, (hipStream_t)s};
+    return timestep_fas(y, mp, dt, cur_step, picard_iters, vcycles);
 }
 
 
@@ -506,95 +568,72 @@ static int amr_gap_ghosts(suhmo_level_t **lv, int nlev, int l, hipStream_t st)
 }
 int suhmo_amr_check_hierarchy(suhmo_level_t **lv, int nlev);      // suhmo_amr.hip
 
-extern "C" int suhmo_amr_timestep(suhmo_level_t **lv, int nlev, const suhmo_model_params_t *mp, double dt, int cur_step,
-                                  int *picard_iters, int *vcycles, suhmo_stream_t s)
-{
-    SUHMO_TIME("AmrHydro::timeStepFAS");
-    ARG(lv && mp && nlev >= 1 && nlev <= 8 && lv[0]); ARG(dt > 0 && cur_step >= 1);
-    if (mp->use_impl_diff && mp->diffFactor == 0.0) { suhmo_set_error("use_ImplDiff with diffFactor = 0"); return -1; }
-    int rc = suhmo_amr_check_hierarchy(lv, nlev); if (rc) return rc;
-    bool strips = false;
-    for (int l = 0; l < nlev; l++) {
-        if (!lv[l]) { strips = true; continue; }
-        const DV &v = lv[l]->d[0].v;
-        if (v.rk[0] || v.rk[1]) {
-            strips = true;
-            if (!(lv[l]->ex && lv[l]->ar)) { suhmo_set_error("time step on rank strips needs the exchange hooks on every level"); return -1; }
-        }
-        if (mp->use_moulin_source && !lv[l]->d[0].fp.f[SUHMO_F_MSRC]) { suhmo_set_error("use_moulin_source without a moulin source term (SUHMO_F_MSRC)"); return -1; }
-    }
-    HIPCHK(hipSetDevice(lv[0]->device));
-    hipStream_t st = (hipStream_t)s;
-    static const int need[] = {SUHMO_F_MR, SUHMO_F_PW, SUHMO_F_QWX, SUHMO_F_QWY, SUHMO_F_HLAG, SUHMO_F_CD, SUHMO_F_GRADX, SUHMO_F_GRADY, SUHMO_F_RE};
-    for (int l = 0; l < nlev; l++) if (lv[l]) for (int f : need) if (!suhmo_field(lv[l], 0, f)) { suhmo_set_error("field allocation failed"); return -2; }
-    // [I]
-    for (int l = 0; l < nlev; l++) if ((rc = amr_gap_ghosts(lv, nlev, l, st))) return rc;
-    if ((rc = suhmo_build_mg_coefficients(lv[0], false, (hipStream_t)s))) return rc;    // bCoef: re-averaged by every V-cycle (bcoeff_otf)
-    suhmo_solver_params_t sp;
-    sp.num_smooth = 4; sp.num_bottom = 16; sp.max_iter = 100; sp.iter_min = 2; sp.imin = 5;
-    sp.eps = 1.0e-7; sp.hang = 0.01; sp.norm_thresh = 1.0e-7; sp.bcoeff_otf = 1; sp.max_depth = -1;
-    if (cur_step < 50) { sp.num_bottom = 10; sp.eps = 1.0e-10; sp.hang = 0.0001; sp.imin = 20; }
-    bool converged = false;
-    int ite_idx = 0, cur_picard = 0, nv = 0;
-    while (!converged) {
+struct Nested {
+    suhmo_level_t **lv;
+    int nlev;
+    bool strips;
+    suhmo_level *base;
+    hipStream_t st;
+    int gap_ghosts(int l) { return amr_gap_ghosts(lv, nlev, l, st); }
+    int lag_head()
+    {
+        int rc;
         for (int l = 0; l < nlev; l++) {
             if (!lv[l]) continue;
             Depth &D = lv[l]->d[0];
             if ((rc = exchange1(lv[l], SUHMO_F_MR, st))) return rc;                    // levelmR.exchange() :2513 (and the stencil of the fill below)
-            if (l > 0 && (rc = suhmo_amr2_pwl_fill(lv[l - 1], lv[l], SUHMO_F_MR, SUHMO_F_MR, s))) return rc;
+            if (l > 0 && (rc = suhmo_amr2_pwl_fill(lv[l - 1], lv[l], SUHMO_F_MR, SUHMO_F_MR, (suhmo_stream_t)st))) return rc;
             if ((rc = amr_gap_ghosts(lv, nlev, l, st))) return rc;
             HIPCHK(hipMemcpyAsync(D.fp.f[SUHMO_F_HLAG], D.fp.f[SUHMO_F_PHI], D.elems * sizeof(double), hipMemcpyDeviceToDevice, st));
         }
-        for (int l = 0; l < nlev; l++) if ((rc = amr_chain(lv, l, st))) return rc;
+        return 0;
+    }
+    int chain(int l) { return amr_chain(lv, l, st); }
+    int head_rhs(const suhmo_model_params_t *mp, double dt)
+    {
+        int rc;
         for (int l = 0; l < nlev; l++) {
             if (!lv[l]) continue;
-            Depth &D = lv[l]->d[0];
             if ((rc = suhmo_bcoef_faces(lv[l], 0, st))) return rc;                      // aCoeff_bCoeff :3087-3102
-            if (mp->diffFactor != 0.0 && (rc = diffusion_terms(lv[l], mp, st))) return rc;
-            hipLaunchKernelGGL(k_melt<0>, dim3((D.v.nx + 63) / 64, (D.v.ny + 3) / 4), dim3(64, 4), 0, st, D.v, D.fp, lv[l]->ph, *mp, dt);
-            HIPCHK(hipGetLastError());
+            if ((rc = level_melt(lv[l], mp, dt, 0, mp->diffFactor != 0.0, st))) return rc;
             if ((rc = exchange1(lv[l], SUHMO_F_RHS, st))) return rc;                   // halo rows relaxed redundantly
         }
-        int it = 0;
-        if (nlev == 1) rc = suhmo_level_solve(lv[0], &sp, &it, nullptr, s);
-        else rc = suhmo_amr_solve(lv, nlev, &sp, &it, nullptr, s);
+        return 0;
+    }
+    int solve_head(const suhmo_solver_params_t &sp, int *it)
+    {
+        suhmo_stream_t s = (suhmo_stream_t)st;
+        int rc = nlev == 1 ? suhmo_level_solve(lv[0], &sp, it, nullptr, s) : suhmo_amr_solve(lv, nlev, &sp, it, nullptr, s);
         if (rc) return rc;
-        nv += it;
         for (int l = nlev - 1; l > 0; l--) {                                            // CoarseAverage :3138-3141
             if (lv[l]) { if ((rc = suhmo_amr2_average(lv[l - 1], lv[l], SUHMO_F_PHI, SUHMO_F_PHI, s))) return rc; }
             else if (lv[l - 1]) lv[l - 1]->d[0].phi_fresh = 0;                          // changed on the ranks that hold level l
         }
         for (int l = 0; l + 1 < nlev; l++)      // the rings of the averaged heads, as the oracle refills them (exchange + BC, every level)
             if (lv[l] && (rc = suhmo_level_fill_ghosts(lv[l], 0, SUHMO_F_PHI, 0, s))) return rc;
-        double maxHead = -1.0e300, maxd = 0.0, res = 0.0;
+        return 0;
+    }
+    int picard_maxima(double *maxHead, double *maxd)
+    {
+        int rc;
+        *maxHead = -1.0e300; *maxd = 0.0;
         for (int l = 0; l < nlev; l++) {
             if (!lv[l]) continue;
             double m = 0.0, d = 0.0;
-            if ((rc = picard_maxima(lv[l], lv[l]->d[0].fp.f[SUHMO_F_PHI], lv[l]->d[0].fp.f[SUHMO_F_HLAG], &m, &d, st, covered_by(lv, nlev, l)))) return rc;
-            maxHead = std::max(maxHead, m); maxd = std::max(maxd, d);
+            if ((rc = ::picard_maxima(lv[l], lv[l]->d[0].fp.f[SUHMO_F_PHI], lv[l]->d[0].fp.f[SUHMO_F_HLAG], &m, &d, st, covered_by(lv, nlev, l)))) return rc;
+            *maxHead = std::max(*maxHead, m); *maxd = std::max(*maxd, d);
         }
         if (strips && lv[0]->ar) {                                  // computeMax over all ranks (level 0 reaches every rank)
-            if ((rc = lv[0]->ar(lv[0]->user, &maxHead))) return rc;
-            if ((rc = lv[0]->ar(lv[0]->user, &maxd))) return rc;
+            if ((rc = lv[0]->ar(lv[0]->user, maxHead))) return rc;
+            if ((rc = lv[0]->ar(lv[0]->user, maxd))) return rc;
         }
-        res = picard_quotient(maxd, maxHead);
-        if (ite_idx > 100) { suhmo_set_error("does not converge (Picard iterations > 100)"); return -6; }
-        if (cur_step < 2) { if (res < 0.05 && cur_picard > 2) converged = true; }
-        else if (cur_step < 50) { if (res < 0.05) converged = true; }
-        else { if (res < mp->eps_picard) converged = true; }
-        ite_idx++; cur_picard++;
+        return 0;
     }
-    // [III] level by level: the coarse gap height is already updated when the fine ghost cells are filled
-    for (int l = 0; l < nlev; l++) {
-        if ((rc = amr_chain(lv, l, st))) return rc;
-        if (!lv[l]) continue;
-        Depth &D = lv[l]->d[0];
-        hipLaunchKernelGGL(k_melt<1>, dim3((D.v.nx + 63) / 64, (D.v.ny + 3) / 4), dim3(64, 4), 0, st, D.v, D.fp, lv[l]->ph, *mp, dt);
-        HIPCHK(hipGetLastError());
-        if (mp->use_impl_diff) continue;                               // b stays, RES = b + dt RHS
-        if ((rc = amr_gap_ghosts(lv, nlev, l, st))) return rc;
-    }
-    if (mp->use_impl_diff) {                                           // SolveForGap_nl over the hierarchy :3425-3455
+    int melt_final(int l, const suhmo_model_params_t *mp, double dt) { return lv[l] ? level_melt(lv[l], mp, dt, 1, false, st) : 0; }
+    int solve_gap(const suhmo_model_params_t *mp, double dt, int cur_step)     // over a second hierarchy of handles
+    {
+        int rc;
+        suhmo_stream_t s = (suhmo_stream_t)st;
         suhmo_level_t *gaps[8];
         for (int l = 0; l < nlev; l++) {
             gaps[l] = nullptr;
@@ -615,10 +654,31 @@ extern "C" int suhmo_amr_timestep(suhmo_level_t **lv, int nlev, const suhmo_mode
             HIPCHK(hipMemcpyAsync(D.fp.f[SUHMO_F_B], gaps[l]->d[0].fp.f[SUHMO_F_PHI], D.elems * sizeof(double), hipMemcpyDeviceToDevice, st));
             if ((rc = amr_gap_ghosts(lv, nlev, l, st))) return rc;
         }
+        return 0;
     }
-    if (picard_iters) *picard_iters = ite_idx;
-    if (vcycles) *vcycles = nv;
-    return 0;
+};
+
+extern "C" int suhmo_amr_timestep(suhmo_level_t **lv, int nlev, const suhmo_model_params_t *mp, double dt, int cur_step,
+                                  int *picard_iters, int *vcycles, suhmo_stream_t s)
+{
+    SUHMO_TIME("AmrHydro::timeStepFAS");
+    ARG(lv && nlev >= 1 && nlev <= 8 && lv[0]);
+    int rc = check_step_args(mp, dt, cur_step); if (rc) return rc;
+    if ((rc = suhmo_amr_check_hierarchy(lv, nlev))) return rc;
+    bool strips = false;
+    for (int l = 0; l < nlev; l++) {
+        if (!lv[l]) { strips = true; continue; }
+        const DV &v = lv[l]->d[0].v;
+        if (v.rk[0] || v.rk[1]) {
+            strips = true;
+            if (!(lv[l]->ex && lv[l]->ar)) { suhmo_set_error("time step on rank strips needs the exchange hooks on every level"); return -1; }
+        }
+        if (mp->use_moulin_source && !lv[l]->d[0].fp.f[SUHMO_F_MSRC]) { suhmo_set_error("use_moulin_source without a moulin source term (SUHMO_F_MSRC)"); return -1; }
+    }
+    HIPCHK(hipSetDevice(lv[0]->device));
+    for (int l = 0; l < nlev; l++) if (lv[l]) for (int f : step_fields) if (!suhmo_field(lv[l], 0, f)) { suhmo_set_error("field allocation failed"); return -2; }
+    Nested y{lv, nlev, strips, lv[0], (hipStream_t)s};
+    return timestep_fas(y, mp, dt, cur_step, picard_iters, vcycles);
 }
 
 // ------------------------------------------------------------------ the time step on a hierarchy of box unions
@@ -698,26 +758,19 @@ int hier_melt(suhmo_hier *H, int l, const suhmo_model_params_t *mp, double dt, i
     LevT t;
     if ((rc = lev_target(H, l, st, t))) return rc;
     const suhmo_phys_t &ph = H->lev[l].box[0]->ph;
-    if (t.base) {
-        suhmo_level *L = t.base;
-        Depth &D = L->d[0];
-        if (diffusion && (rc = diffusion_terms(L, mp, st))) return rc;
-        if (final_) hipLaunchKernelGGL(k_melt<1>, dim3((D.v.nx + 63) / 64, (D.v.ny + 3) / 4), dim3(64, 4), 0, st, D.v, D.fp, ph, *mp, dt);
-        else hipLaunchKernelGGL(k_melt<0>, dim3((D.v.nx + 63) / 64, (D.v.ny + 3) / 4), dim3(64, 4), 0, st, D.v, D.fp, ph, *mp, dt);
-    } else {
-        const suhmo_multi &m = t.m;
-        if (diffusion) for (int f : {SUHMO_F_DCX, SUHMO_F_DCY, SUHMO_F_DTERM}) if ((rc = ensure_field(H, l, f))) return rc;
-        if (m.nbox <= 0) return 0;                                               // owner computes: none of this level's boxes is this rank's
-        if (diffusion) {
-            if ((rc = lev_target(H, l, st, t))) return rc;                       // the tables after the allocation
-            int n = 2 * m.maxny + 2 * m.maxnx;
-            hipLaunchKernelGGL(k_extrap_ghosts_m, dim3((n + 255) / 256, 1, m.nbox), dim3(256), 0, st, m.dv, m.fp, (int)SUHMO_F_MR);
-            hipLaunchKernelGGL(k_dcoef_faces_m, grid_m(m, 1, 1), dim3(64, 4), 0, st, m.dv, m.fp, ph, mp->rho_i);
-            hipLaunchKernelGGL(k_difterm_m, grid_m(m), dim3(64, 4), 0, st, m.dv, m.fp);
-        }
-        if (final_) hipLaunchKernelGGL(k_melt_m<1>, grid_m(m), dim3(64, 4), 0, st, m.dv, m.fp, ph, *mp, dt);
-        else hipLaunchKernelGGL(k_melt_m<0>, grid_m(m), dim3(64, 4), 0, st, m.dv, m.fp, ph, *mp, dt);
+    if (t.base) return level_melt(t.base, mp, dt, final_, diffusion, st);
+    const suhmo_multi &m = t.m;
+    if (diffusion) for (int f : {SUHMO_F_DCX, SUHMO_F_DCY, SUHMO_F_DTERM}) if ((rc = ensure_field(H, l, f))) return rc;
+    if (m.nbox <= 0) return 0;                                               // owner computes: none of this level's boxes is this rank's
+    if (diffusion) {
+        if ((rc = lev_target(H, l, st, t))) return rc;                       // the tables after the allocation
+        int n = 2 * m.maxny + 2 * m.maxnx;
+        hipLaunchKernelGGL(k_extrap_ghosts_m, dim3((n + 255) / 256, 1, m.nbox), dim3(256), 0, st, m.dv, m.fp, (int)SUHMO_F_MR);
+        hipLaunchKernelGGL(k_dcoef_faces_m, grid_m(m, 1, 1), dim3(64, 4), 0, st, m.dv, m.fp, ph, mp->rho_i);
+        hipLaunchKernelGGL(k_difterm_m, grid_m(m), dim3(64, 4), 0, st, m.dv, m.fp);
     }
+    if (final_) hipLaunchKernelGGL(k_melt_m<1>, grid_m(m), dim3(64, 4), 0, st, m.dv, m.fp, ph, *mp, dt);
+    else hipLaunchKernelGGL(k_melt_m<0>, grid_m(m), dim3(64, 4), 0, st, m.dv, m.fp, ph, *mp, dt);
     HIPCHK(hipGetLastError());
     return 0;
 }
@@ -751,40 +804,15 @@ int hier_picard_maxima(suhmo_hier *H, int l, bool covered, double *maxh, double 
     }
     return 0;
 }
-}  // namespace
-
-extern "C" int suhmo_hier_timestep(suhmo_hier_t *H, const suhmo_model_params_t *mp, double dt, int cur_step,
-                                   int *picard_iters, int *vcycles, suhmo_stream_t s)
-{
-    SUHMO_TIME("AmrHydro::timeStepFAS");
-    ARG(H && mp); ARG(dt > 0 && cur_step >= 1);
-    if (mp->use_impl_diff && mp->diffFactor == 0.0) { suhmo_set_error("use_ImplDiff with diffFactor = 0"); return -1; }
-    const int nlev = H->nlev;
-    HIPCHK(hipSetDevice(H->device));
-    suhmo_hier_invalidate_(H);
-    hipStream_t st = (hipStream_t)s;
-    int rc;
-    static const int need[] = {SUHMO_F_MR, SUHMO_F_PW, SUHMO_F_QWX, SUHMO_F_QWY, SUHMO_F_HLAG, SUHMO_F_CD, SUHMO_F_GRADX, SUHMO_F_GRADY, SUHMO_F_RE};
-    for (int l = 0; l < nlev; l++) {
-        for (int f : need) if ((rc = ensure_field(H, l, f))) return rc;
-        if (mp->use_moulin_source) {
-            const int k0 = H->lev[l].first_owned(), nk = H->lev[l].n_owned();
-            for (int k = k0; k < k0 + nk; k++)
-                if (!H->lev[l].box[k]->d[0].fp.f[SUHMO_F_MSRC]) { suhmo_set_error("use_moulin_source without a moulin source term (suhmo_hier_moulin_source)"); return -1; }
-        }
-    }
-    suhmo_level *base = H->lev[0].box[0];
-    if ((base->d[0].v.rk[0] || base->d[0].v.rk[1]) && !(base->ex && base->ar)) { suhmo_set_error("time step on rank strips needs the exchange hooks on level 0"); return -1; }
-    // [I]
-    for (int l = 0; l < nlev; l++) if ((rc = hier_gap_ghosts(H, l, st))) return rc;
-    if ((rc = suhmo_build_mg_coefficients(base, false, st))) return rc;         // bCoef: re-averaged by every V-cycle (bcoeff_otf)
-    suhmo_solver_params_t sp;
-    sp.num_smooth = 4; sp.num_bottom = 16; sp.max_iter = 100; sp.iter_min = 2; sp.imin = 5;
-    sp.eps = 1.0e-7; sp.hang = 0.01; sp.norm_thresh = 1.0e-7; sp.bcoeff_otf = 1; sp.max_depth = -1;
-    if (cur_step < 50) { sp.num_bottom = 10; sp.eps = 1.0e-10; sp.hang = 0.0001; sp.imin = 20; }
-    bool converged = false;
-    int ite_idx = 0, cur_picard = 0, nv = 0;
-    while (!converged) {
+struct BoxUnions {
+    suhmo_hier *H;
+    int nlev;
+    suhmo_level *base;
+    hipStream_t st;
+    int gap_ghosts(int l) { return hier_gap_ghosts(H, l, st); }
+    int lag_head()
+    {
+        int rc;
         for (int l = 0; l < nlev; l++) {
             if ((rc = hier_gap_ghosts(H, l, st))) return rc;
             if (l == 0 && (rc = exchange1(base, SUHMO_F_MR, st))) return rc;                    // rank strips: levelmR.exchange() :2513
@@ -794,7 +822,12 @@ extern "C" int suhmo_hier_timestep(suhmo_hier_t *H, const suhmo_model_params_t *
                 HIPCHK(hipMemcpyAsync(D.fp.f[SUHMO_F_HLAG], D.fp.f[SUHMO_F_PHI], D.elems * sizeof(double), hipMemcpyDeviceToDevice, st)); }
             else { suhmo_multi m; if ((rc = multi_of(H, l, st, m)) || (rc = suhmo_multi_copy(m, SUHMO_F_HLAG, SUHMO_F_PHI, st))) return rc; }
         }
-        for (int l = 0; l < nlev; l++) if ((rc = hier_chain(H, l, st))) return rc;
+        return 0;
+    }
+    int chain(int l) { return hier_chain(H, l, st); }
+    int head_rhs(const suhmo_model_params_t *mp, double dt)
+    {
+        int rc;
         for (int l = 0; l < nlev; l++) {                                                        // aCoeff_bCoeff :3087-3102
             LevT t;
             if ((rc = lev_target(H, l, st, t))) return rc;
@@ -802,37 +835,35 @@ extern "C" int suhmo_hier_timestep(suhmo_hier_t *H, const suhmo_model_params_t *
             if (rc) return rc;
         }
         for (int l = 0; l < nlev; l++) if ((rc = hier_melt(H, l, mp, dt, 0, mp->diffFactor != 0.0, st))) return rc;
-        if ((rc = exchange1(base, SUHMO_F_RHS, st))) return rc;                                 // rank strips: halo rows relaxed redundantly
-        int it = 0;
-        if ((rc = suhmo_hier_solve(H, &sp, &it, nullptr, s))) return rc;
-        nv += it;
+        return exchange1(base, SUHMO_F_RHS, st);                                                // rank strips: halo rows relaxed redundantly
+    }
+    int solve_head(const suhmo_solver_params_t &sp, int *it)
+    {
+        int rc;
+        if ((rc = suhmo_hier_solve(H, &sp, it, nullptr, (suhmo_stream_t)st))) return rc;
         for (int l = nlev - 1; l > 0; l--) if ((rc = hier_avg(H, l, SUHMO_F_PHI, SUHMO_F_PHI, 0, 0.0, st))) return rc;   // CoarseAverage :3138-3141
         for (int l = 0; l + 1 < nlev; l++) {    // the averaged heads' rings as the oracle refills them: BC of every box, level 0's periodic sides
-            if (l == 0) { if ((rc = suhmo_level_fill_ghosts(base, 0, SUHMO_F_PHI, 0, s))) return rc; continue; }
+            if (l == 0) { if ((rc = suhmo_level_fill_ghosts(base, 0, SUHMO_F_PHI, 0, (suhmo_stream_t)st))) return rc; continue; }
             suhmo_multi m;
             if ((rc = multi_of(H, l, st, m)) || (rc = suhmo_multi_fill_ghosts(m, SUHMO_F_PHI, 0, st))) return rc;
         }
-        double maxHead = -1.0e300, maxd = 0.0, res = 0.0;
+        return 0;
+    }
+    int picard_maxima(double *maxHead, double *maxd)
+    {
+        int rc;
+        *maxHead = -1.0e300; *maxd = 0.0;
         for (int l = 0; l < nlev; l++) {
             double m = 0.0, d = 0.0;
             if ((rc = hier_picard_maxima(H, l, l < nlev - 1, &m, &d, st))) return rc;
-            maxHead = std::max(maxHead, m); maxd = std::max(maxd, d);
+            *maxHead = std::max(*maxHead, m); *maxd = std::max(*maxd, d);
         }
-        res = picard_quotient(maxd, maxHead);
-        if (ite_idx > 100) { suhmo_set_error("does not converge (Picard iterations > 100)"); return -6; }
-        if (cur_step < 2) { if (res < 0.05 && cur_picard > 2) converged = true; }
-        else if (cur_step < 50) { if (res < 0.05) converged = true; }
-        else { if (res < mp->eps_picard) converged = true; }
-        ite_idx++; cur_picard++;
+        return 0;
     }
-    // [III] level by level: the coarse gap height is already updated when the fine ghost cells are filled
-    for (int l = 0; l < nlev; l++) {
-        if ((rc = hier_chain(H, l, st))) return rc;
-        if ((rc = hier_melt(H, l, mp, dt, 1, false, st))) return rc;
-        if (mp->use_impl_diff) continue;                               // b stays, RES = b + dt RHS
-        if ((rc = hier_gap_ghosts(H, l, st))) return rc;
-    }
-    if (mp->use_impl_diff) {                                           // SolveForGap_nl over the hierarchy :3425-3455
+    int melt_final(int l, const suhmo_model_params_t *mp, double dt) { return hier_melt(H, l, mp, dt, 1, false, st); }
+    int solve_gap(const suhmo_model_params_t *mp, double dt, int cur_step)     // over the gap-height hierarchy
+    {
+        int rc;
         suhmo_hier *G = nullptr;
         if ((rc = suhmo_hier_gap_(H, mp, dt, &G))) return rc;
         for (int l = 0; l < nlev; l++) {
@@ -860,10 +891,10 @@ extern "C" int suhmo_hier_timestep(suhmo_hier_t *H, const suhmo_model_params_t *
         }
         {   static const int halo_fields[] = {SUHMO_F_RHS, SUHMO_F_ACOEF, SUHMO_F_BX, SUHMO_F_BY};          // rank strips
             if ((rc = suhmo_exchange_list(G->lev[0].box[0], 0, halo_fields, 4, st))) return rc; }
-        if ((rc = suhmo_level_build_mg_coefficients(G->lev[0].box[0], s))) return rc;
+        if ((rc = suhmo_level_build_mg_coefficients(G->lev[0].box[0], (suhmo_stream_t)st))) return rc;
         suhmo_solver_params_t spg;
         gap_solver_params(spg, cur_step);
-        if ((rc = suhmo_hier_solve(G, &spg, nullptr, nullptr, s))) return rc;
+        if ((rc = suhmo_hier_solve(G, &spg, nullptr, nullptr, (suhmo_stream_t)st))) return rc;
         for (int l = 0; l < nlev; l++) {
             const auto &hb = H->lev[l].box, &gb = G->lev[l].box;
             if (l > 0) {
@@ -882,10 +913,32 @@ extern "C" int suhmo_hier_timestep(suhmo_hier_t *H, const suhmo_model_params_t *
                 }
             if ((rc = hier_gap_ghosts(H, l, st))) return rc;
         }
+        return 0;
     }
-    if (picard_iters) *picard_iters = ite_idx;
-    if (vcycles) *vcycles = nv;
-    return 0;
+};
+}  // namespace
+
+extern "C" int suhmo_hier_timestep(suhmo_hier_t *H, const suhmo_model_params_t *mp, double dt, int cur_step,
+                                   int *picard_iters, int *vcycles, suhmo_stream_t s)
+{
+    SUHMO_TIME("AmrHydro::timeStepFAS");
+    ARG(H);
+    int rc = check_step_args(mp, dt, cur_step); if (rc) return rc;
+    const int nlev = H->nlev;
+    HIPCHK(hipSetDevice(H->device));
+    suhmo_hier_invalidate_(H);
+    for (int l = 0; l < nlev; l++) {
+        for (int f : step_fields) if ((rc = ensure_field(H, l, f))) return rc;
+        if (mp->use_moulin_source) {
+            const int k0 = H->lev[l].first_owned(), nk = H->lev[l].n_owned();
+            for (int k = k0; k < k0 + nk; k++)
+                if (!H->lev[l].box[k]->d[0].fp.f[SUHMO_F_MSRC]) { suhmo_set_error("use_moulin_source without a moulin source term (suhmo_hier_moulin_source)"); return -1; }
+        }
+    }
+    suhmo_level *base = H->lev[0].box[0];
+    if ((base->d[0].v.rk[0] || base->d[0].v.rk[1]) && !(base->ex && base->ar)) { suhmo_set_error("time step on rank strips needs the exchange hooks on level 0"); return -1; }
+    BoxUnions y{H, nlev, base, (hipStream_t)s};
+    return timestep_fas(y, mp, dt, cur_step, picard_iters, vcycles);
 }
 
 // ------------------------------------------------------------------ moulin source term
