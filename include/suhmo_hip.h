@@ -485,6 +485,45 @@ int suhmo_hier_timestep(suhmo_hier_t *H, const suhmo_model_params_t *mp, double 
 int suhmo_hier_moulin_source(suhmo_hier_t *H, int n_moulins, const double *positions, const double *sigma, const double *flux,
                              double time_factor, double *integrals, suhmo_stream_t s);
 
+/* ---- an ENSEMBLE of N independent models on the same grid, stepped together (suhmo_amd/csrc/suhmo_batch.hip): the
+ * reference's SHMIP suites are parameter sweeps on one 320 x 64 level (exec/A_SHMIP ... exec/F_SHMIP), far too small to occupy the device.  Every
+ * kernel launch of a batch call serves all members that still have work and ONE read-back per V-cycle carries all their residual norms; each
+ * member's results are bit for bit those of running it alone.
+ *   suhmo_batch_create    n_members (1 .. 64) whole levels from one descriptor: nx, ny, dx, dy, max_box (hence the depth count), alpha / beta, BC types
+ *                         and periodicity are shared (a batch call on members that differ in them fails with rc -1); a descriptor of a rank strip or an AMR patch is refused (rc -5), n_members out of range rc -1,
+ *                         no device rc -3
+ *   suhmo_batch_member    member k as an ordinary level handle, owned by the batch (suhmo_level_destroy on it fails with rc -1): its fields, BC
+ *                         VALUES (suhmo_level_set_bc with the shared types) and physics constants are per member, loaded and read through
+ *                         suhmo_level_put_box / get_box / set_field / get_field / set_bc / norm / ...
+ *   suhmo_batch_set_phys  the physics constants of member k (a level has them from its descriptor only; members are created from one)
+ *   suhmo_batch_vcycle    one FAS V-cycle (suhmo_level_vcycle) of the members whose flag in active[n] is not 0 (NULL = all; none: a no-op, rc 0)
+ *   suhmo_batch_solve     the AMRMultiGrid::solve loop (suhmo_level_solve) with the stopping rule applied per member: a member that stops leaves
+ *                         the launches that follow.  iters[n], residual[n] (may be NULL): cycles and final residual max norm of every member.
+ *                         Read-backs: one for the initial norms + one per cycle of the member that runs longest.
+ *   suhmo_batch_timestep  suhmo_level_timestep of every member, in lock-step by phase: [I] gap-height ghosts and MG coefficients of all members, [II] Picard
+ *                         iterations of the members still iterating (lagged chain, RHS_h, the solve above over exactly those members, ONE read-back
+ *                         of all their Picard maxima, the test per member), [III] chain, melt rate, forward-Euler gap update and ghosts of all.
+ *                         mp[n]: the model parameters of every member (use_moulin_source, distributed_input, ramp, diffFactor, head_melt_off, eps_picard, ...);
+ *                         dt and cur_step are shared.  picard_iters[n], vcycles[n] (may be NULL).  use_impl_diff = 1 on any member: rc -5 (the implicit
+ *                         gap solve is a second batch of linear operators: not built).  Moulin sources / recharge: suhmo_level_moulin_source /
+ *                         suhmo_level_time_varying_recharge on the member handle.
+ *   suhmo_batch_set_option / get_option   tile_order (0 .. 2, as the level's); bottom_solver: only 0 (1 is refused with rc -5: the bottom of a
+ *                         batched cycle is its numBottom relaxes).  Read-only counters: batch_launches, batch_readbacks, batch_member_cycles
+ *                         (V-cycles summed over the members that ran them).  An unknown key: rc -1.
+ * A batch relaxes every depth with the tile kernel (colour passes where the grid rules it out); eager launches only, no graph capture.
+ * Not built: the implicit gap solve of a batch, rank strips, AMR patches and hierarchies as members, graph capture, bottom_solver = 1. */
+typedef struct suhmo_batch suhmo_batch_t;
+int suhmo_batch_create(suhmo_batch_t **out, const suhmo_level_desc_t *desc, int n_members);
+int suhmo_batch_destroy(suhmo_batch_t *B);
+int suhmo_batch_size(const suhmo_batch_t *B);
+suhmo_level_t *suhmo_batch_member(suhmo_batch_t *B, int k);
+int suhmo_batch_set_phys(suhmo_batch_t *B, int k, const suhmo_phys_t *phys);
+int suhmo_batch_vcycle(suhmo_batch_t *B, const suhmo_solver_params_t *sp, const int *active, suhmo_stream_t s);
+int suhmo_batch_solve(suhmo_batch_t *B, const suhmo_solver_params_t *sp, int *iters, double *residual, suhmo_stream_t s);
+int suhmo_batch_timestep(suhmo_batch_t *B, const suhmo_model_params_t *mp, double dt, int cur_step, int *picard_iters, int *vcycles, suhmo_stream_t s);
+int suhmo_batch_set_option(suhmo_batch_t *B, const char *key, long value);
+int suhmo_batch_get_option(const suhmo_batch_t *B, const char *key, long *value);
+
 /* Named timers with the reference's CH_TIME labels (src/VCAMRNonLinearPoissonOp.cpp:40,69,103,277,390,660; CH_TIMER_REPORT at
  * exec/A_SHMIP/Suhmo.cpp:136).  mode 0 off (default; env SUHMO_TIMERS), 1 host wall time per scope, 2 with the device synchronised at
  * both ends of a scope (the time of the kernels it launched; serialises, for profiling only).  suhmo_timers_report writes

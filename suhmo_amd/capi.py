@@ -81,6 +81,8 @@ SYMBOLS = [
     "suhmo_hier_set_allgather", "suhmo_hier_attach_rccl", "suhmo_hier_gathers", "suhmo_level_set_option", "suhmo_level_get_option", "suhmo_timers_enable", "suhmo_timers_reset", "suhmo_timers_report",
     "suhmo_level_set_reduce_hook", "suhmo_level_dot", "suhmo_level_set_allgather", "suhmo_level_agglomerated_depth",
     "suhmo_hier_create_opts", "suhmo_hier_set_option", "suhmo_hier_get_option",
+    "suhmo_batch_create", "suhmo_batch_destroy", "suhmo_batch_size", "suhmo_batch_member", "suhmo_batch_set_phys", "suhmo_batch_vcycle", "suhmo_batch_solve", "suhmo_batch_timestep",
+    "suhmo_batch_set_option", "suhmo_batch_get_option",
 ]
 
 
@@ -209,6 +211,17 @@ def lib():
     L.suhmo_timers_report.restype = C.c_long
     L.suhmo_level_set_option.argtypes = [vp, C.c_char_p, C.c_long]
     L.suhmo_level_get_option.argtypes = [vp, C.c_char_p, C.POINTER(C.c_long)]
+    L.suhmo_batch_create.argtypes = [C.POINTER(vp), C.POINTER(LevelDesc), ci]
+    L.suhmo_batch_destroy.argtypes = [vp]
+    L.suhmo_batch_size.argtypes = [vp]
+    L.suhmo_batch_member.argtypes = [vp, ci]
+    L.suhmo_batch_member.restype = vp
+    L.suhmo_batch_set_phys.argtypes = [vp, ci, C.POINTER(Phys)]
+    L.suhmo_batch_vcycle.argtypes = [vp, C.POINTER(SolverParams), ip, vp]
+    L.suhmo_batch_solve.argtypes = [vp, C.POINTER(SolverParams), ip, dp, vp]
+    L.suhmo_batch_timestep.argtypes = [vp, C.POINTER(ModelParams), C.c_double, ci, ip, ip, vp]
+    L.suhmo_batch_set_option.argtypes = [vp, C.c_char_p, C.c_long]
+    L.suhmo_batch_get_option.argtypes = [vp, C.c_char_p, C.POINTER(C.c_long)]
     L.suhmo_level_profile_reset.argtypes = [vp]
     L.suhmo_level_profile_enable.argtypes = [vp, ci]
     L.suhmo_level_profile_read.argtypes = [vp, vp, dp, C.POINTER(C.c_long), C.POINTER(C.c_long)]

@@ -1,0 +1,418 @@
+// suhmo_batch.hip -- an ensemble of N independent whole levels on ONE grid, stepped through one launch sequence.
+//
+// The reference's SHMIP suites are parameter sweeps on a 320 x 64 level (exec/A_SHMIP ... exec/F_SHMIP): 80 waves of tile work per
+// member, on a part with 1024 SIMDs, and every launch costs its fixed few microseconds whatever its size.  A batch runs the FAS V-cycle of
+// suhmo_fas.hip (operator methods src/VCAMRNonLinearPoissonOp.cpp:32-460, src/AMRNonLinearPoissonOp.cpp:707-886) and
+// the solveNoInit loop with every kernel launched ONCE for all members that still have work (gridDim.z = active members, suhmo_batch.h),
+// and one read-back per cycle that carries all their residual norms.  Each member sees exactly the sequence of operations it would see
+// alone: the device bodies are the solo kernels', the stopping rule is SolveNoInit (suhmo_common.h) per member, and a member that has
+// stopped is simply no longer in the active list of the launches that follow.
+//
+// Members are ordinary level handles owned by the batch (suhmo_batch_member): fields, BC values and physics constants are loaded and read
+// through the suhmo_level_* entry points.  Tables are compared with the handles at the start of every batch call and written again only
+// when a pointer, a view or a constant has changed.
+#include "suhmo_batch.h"
+#include <new>
+
+struct suhmo_batch {
+    int n, ndepth, device;
+    bool has_alpha;
+    std::vector<suhmo_level *> mem;
+    DV *d_dv[SUHMO_MAXDEPTH];
+    FP *d_fp[SUHMO_MAXDEPTH];
+    suhmo_phys_t *d_ph;
+    std::vector<DV> h_dv[SUHMO_MAXDEPTH];                   // what the device tables hold
+    std::vector<FP> h_fp[SUHMO_MAXDEPTH];
+    std::vector<suhmo_phys_t> h_ph;
+    unsigned long long alt[SUHMO_MAXDEPTH];                 // bit k: the head canvases of member k have traded places since the table was written
+    bool written;
+    double *partial; size_t np;                             // partial maxima of the reductions: np workgroups per member, up to two values each
+    double *hslot, *hslot_dev;                              // pinned: n values + the sequence number at [SUHMO_BATCH_MAX]
+    unsigned long long hseq;
+    int tile_order;
+    long launches, readbacks, member_cycles;
+    void *d_avg;                                            // the members' coefficient / face canvases of all depths (suhmo_bcoef.hip)
+    suhmo_model_params_t *d_mp; std::vector<suhmo_model_params_t> h_mp;   // the time step: mp[n] on the device, rewritten when it changed
+    BatchSel phase;                                         // the time step: the members the current phase serves
+};
+constexpr int SLOT_FLAG = 2 * SUHMO_BATCH_MAX;             // pinned slot: two values per member, then the sequence number
+
+static const DV &view(const suhmo_batch *B, int dep) { return B->mem[0]->d[dep].v; }
+static BatchTab tab(const suhmo_batch *B, int dep) { return BatchTab{B->d_dv[dep], B->d_fp[dep], B->d_ph, B->alt[dep]}; }
+
+// the device tables against the member handles: rows are rewritten when something other than the trade of the two head canvases changed
+static int batch_sync(suhmo_batch *B, hipStream_t st)
+{
+    bool dirty = !B->written;
+    for (int dep = 0; dep < B->ndepth; dep++) {
+        unsigned long long alt = 0;
+        for (int k = 0; k < B->n; k++) {
+            Depth &D = B->mem[k]->d[dep];
+            FP row = D.fp;
+            row.f[SUHMO_F_PHI2] = D.phi_alt;
+            FP &m = B->h_fp[dep][k];
+            FP traded = m;
+            std::swap(traded.f[SUHMO_F_PHI], traded.f[SUHMO_F_PHI2]);
+            if (!memcmp(&row, &m, sizeof(FP))) { }
+            else if (!memcmp(&row, &traded, sizeof(FP))) alt |= 1ull << k;
+            else { m = row; dirty = true; }
+            if (memcmp(&D.v, &B->h_dv[dep][k], sizeof(DV))) { B->h_dv[dep][k] = D.v; dirty = true; }
+            // launch geometry and kernel variant are decided once for all members: what decides them must be shared (the BC VALUES are not)
+            const DV &v0 = B->mem[0]->d[dep].v;
+            if (memcmp(D.v.bct, v0.bct, sizeof(v0.bct)) || memcmp(D.v.per, v0.per, sizeof(v0.per)) || D.v.alpha != v0.alpha || D.v.beta != v0.beta) {
+                suhmo_set_error("batch: member %d differs from member 0 in BC types, periodicity or alpha / beta: these are shared by all members", k);
+                B->written = false;                          // (rows compared so far may be ahead of the device: the next call writes all)
+                return -1;
+            }
+        }
+        B->alt[dep] = alt;
+    }
+    for (int k = 0; k < B->n; k++)
+        if (memcmp(&B->mem[k]->ph, &B->h_ph[k], sizeof(suhmo_phys_t))) { B->h_ph[k] = B->mem[k]->ph; dirty = true; }
+    if (!dirty) return 0;
+    HIPCHK(hipStreamSynchronize(st));                        // (no launch in flight reads the rows about to change)
+    for (int dep = 0; dep < B->ndepth; dep++) {
+        HIPCHK(hipMemcpy(B->d_dv[dep], B->h_dv[dep].data(), B->n * sizeof(DV), hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(B->d_fp[dep], B->h_fp[dep].data(), B->n * sizeof(FP), hipMemcpyHostToDevice));
+    }
+    HIPCHK(hipMemcpy(B->d_ph, B->h_ph.data(), B->n * sizeof(suhmo_phys_t), hipMemcpyHostToDevice));
+    B->written = true;
+    return 0;
+}
+// the active members' head canvases of a depth have traded places (an out-of-place relaxation launch)
+static void traded(suhmo_batch *B, int dep, const BatchSel &sel)
+{
+    for (int z = 0; z < sel.n; z++) {
+        Depth &D = B->mem[sel.m[z]]->d[dep];
+        std::swap(D.fp.f[SUHMO_F_PHI], D.phi_alt);
+        B->alt[dep] ^= 1ull << sel.m[z];
+    }
+    suhmo_fp_changed();
+}
+static int batch_readback(suhmo_batch *B, hipStream_t st)
+{
+    B->readbacks++;
+    volatile unsigned long long *flag = (volatile unsigned long long *)(B->hslot + SLOT_FLAG);
+    for (long spin = 0; spin < 400000000L; spin++) {
+        if (__atomic_load_n((unsigned long long *)flag, __ATOMIC_ACQUIRE) == B->hseq) return 0;
+        if ((spin & 0xfff) == 0xfff && hipStreamQuery(st) != hipErrorNotReady) break;        // finished, or failed: the synchronisation below reports it
+    }
+    HIPCHK(hipStreamSynchronize(st));
+    if (__atomic_load_n((unsigned long long *)flag, __ATOMIC_ACQUIRE) == B->hseq) return 0;
+    suhmo_set_error("batch: the reduction's values did not arrive in the pinned slot");
+    return -2;
+}
+// (suhmo_readback's mechanism -- a sequence number behind the values in pinned memory, polled -- with a slot per member: that one is tied to a
+// level's two-value slot and its strip reductions)
+// residualI of depth 0 of the active members and their max norms: hslot[k]
+static int batch_residual_norms(suhmo_batch *B, const BatchSel &sel, hipStream_t st)
+{
+    int rc = suhmo_batch_residual_norm(tab(B, 0), sel, view(B, 0), B->has_alpha, B->partial, B->hslot_dev,
+                                       (unsigned long long *)(B->hslot_dev + SLOT_FLAG), ++B->hseq, st);
+    if (rc) return rc;
+    B->launches += 2;
+    return batch_readback(B, st);
+}
+
+// relax() of the cycle (suhmo_fas.hip): tile launches of 4 / 2 / 1 sweeps where the grid allows (a depth that is one tile: all its sweeps in
+// one launch), colour passes elsewhere; the relax that ends the cycle fills the ring with the homogeneous boundary condition
+static int batch_relax(suhmo_batch *B, int dep, int sweeps, const BatchSel &sel, hipStream_t st, bool observable, bool frhs, bool prolong)
+{
+    const DV &v = view(B, dep);
+    int rc;
+    if (suhmo_batch_tile_ok(v)) {
+        for (int it = 0; it < sweeps;) {
+            const int TS = sweeps - it >= 4 ? 4 : sweeps - it >= 2 ? 2 : 1, one = suhmo_batch_single_tile(v);
+            const int chunks = (TS == 4 && one) ? (sweeps - it) / TS : 1;
+            const BatchTab c = prolong ? tab(B, dep + 1) : tab(B, dep);
+            if ((rc = suhmo_batch_gsrb_tile(tab(B, dep), prolong ? &c : nullptr, prolong ? &view(B, dep + 1) : nullptr, sel, v, TS, chunks > 1 ? one : 16, chunks,
+                                            frhs, prolong, B->has_alpha, B->tile_order, st))) return rc;
+            traded(B, dep, sel);
+            B->launches++;
+            frhs = prolong = false;
+            it += TS * chunks;
+        }
+    } else {
+        if (frhs || prolong) { suhmo_set_error("internal: batch: a fused right-hand side / prolongation on a depth of colour passes"); return -4; }
+        for (int p = 0; p < 2 * sweeps; p++) {
+            if ((rc = suhmo_batch_colour_pass(tab(B, dep), sel, v, p & 1, B->has_alpha, st))) return rc;
+            B->launches++;
+        }
+    }
+    if (sweeps > 0 && observable) {
+        if ((rc = suhmo_batch_fill_ghosts(tab(B, dep), sel, v, SUHMO_F_PHI, 1, st))) return rc;
+        B->launches++;
+    }
+    return 0;
+}
+// fas_cycle of suhmo_fas.hip for whole levels (no rank strips, bottom = its numBottom relaxes), `frhs`: this depth's first relaxation
+// forms its FAS right-hand side
+static int batch_fas_cycle(suhmo_batch *B, int dep, const suhmo_solver_params_t *sp, int nd, const BatchSel &sel, hipStream_t st, bool frhs)
+{
+    int rc;
+    const int S = sp->num_smooth;
+    if (dep == nd - 1) return batch_relax(B, dep, sp->num_bottom, sel, st, dep == 0, frhs, false);
+    if ((rc = batch_relax(B, dep, S, sel, st, false, frhs, false))) return rc;                        // pre-smooth
+    if ((rc = suhmo_batch_restrict_both(tab(B, dep), tab(B, dep + 1), sel, view(B, dep + 1), B->has_alpha, st))) return rc;   // RES, PHI of dep + 1
+    B->launches++;
+    const int next_sweeps = dep + 1 == nd - 1 ? sp->num_bottom : S;
+    const bool rhs_in_relax = next_sweeps >= 1 && suhmo_batch_tile_ok(view(B, dep + 1));
+    if (!rhs_in_relax) {                                                                                // PHIOLD = R phi, rhs_c = res_c + L_c(R phi)
+        if ((rc = suhmo_batch_fas_coarse_rhs(tab(B, dep + 1), sel, view(B, dep + 1), B->has_alpha, st))) return rc;
+        B->launches++;
+    }
+    if ((rc = batch_fas_cycle(B, dep + 1, sp, nd, sel, st, rhs_in_relax))) return rc;
+    const bool prolong_in_relax = S >= 1 && suhmo_batch_tile_ok(view(B, dep));
+    if (!prolong_in_relax) {                                                                            // corr = phi_c - phi_c,old; phi += P(corr)
+        if ((rc = suhmo_batch_prolong(tab(B, dep), tab(B, dep + 1), sel, view(B, dep), view(B, dep + 1), st))) return rc;
+        B->launches += 2;
+    }
+    return batch_relax(B, dep, S, sel, st, dep == 0, false, prolong_in_relax);                          // post-smooth
+}
+static int batch_vcycle(suhmo_batch *B, const suhmo_solver_params_t *sp, const BatchSel &sel, hipStream_t st)
+{
+    int rc, nd = B->ndepth;
+    if (sel.n <= 0) return 0;
+    if (sp->max_depth >= 0 && sp->max_depth + 1 < nd) nd = sp->max_depth + 1;
+    if (sp->bcoeff_otf) {                                                                               // UpdateOperator, AverageOperator on every depth > 0
+        if ((rc = suhmo_batch_update_operator(tab(B, 0), sel, view(B, 0), st))) return rc;
+        B->launches++;
+        BatchTab tabs[SUHMO_MAXDEPTH];
+        for (int dep = 0; dep < nd; dep++) tabs[dep] = tab(B, dep);
+        int nl = 0;
+        if ((rc = suhmo_batch_average_operator_all(tabs, B->d_avg, sel, B->mem[0], nd, st, &nl))) return rc;
+        B->launches += nl;
+    }
+    if ((rc = batch_fas_cycle(B, 0, sp, nd, sel, st, false))) return rc;
+    B->member_cycles += sel.n;
+    return 0;
+}
+static BatchSel all_members(const suhmo_batch *B)
+{
+    BatchSel sel; memset(&sel, 0, sizeof(sel));
+    sel.n = B->n;
+    for (int k = 0; k < B->n; k++) sel.m[k] = (unsigned char)k;
+    return sel;
+}
+static int batch_enter(suhmo_batch *B, hipStream_t st)
+{
+    HIPCHK(hipSetDevice(B->device));
+    for (suhmo_level *L : B->mem)
+        if (L->bottom_solver) { suhmo_set_error("batch: bottom_solver = 1 on a member is not built (the bottom of a batched cycle is its numBottom relaxes)"); return -5; }
+    return batch_sync(B, st);
+}
+
+extern "C" int suhmo_batch_destroy(suhmo_batch_t *B)
+{
+    if (!B) return 0;
+    (void)hipSetDevice(B->device);
+    (void)hipDeviceSynchronize();
+    for (suhmo_level *L : B->mem) if (L) { L->batch_owned = 0; (void)suhmo_level_destroy(L); }
+    for (int dep = 0; dep < SUHMO_MAXDEPTH; dep++) { if (B->d_dv[dep]) (void)hipFree(B->d_dv[dep]); if (B->d_fp[dep]) (void)hipFree(B->d_fp[dep]); }
+    if (B->d_ph) (void)hipFree(B->d_ph);
+    if (B->partial) (void)hipFree(B->partial);
+    if (B->d_avg) (void)hipFree(B->d_avg);
+    if (B->d_mp) (void)hipFree(B->d_mp);
+    if (B->hslot) (void)hipHostFree(B->hslot);
+    delete B;
+    return 0;
+}
+extern "C" int suhmo_batch_create(suhmo_batch_t **out, const suhmo_level_desc_t *desc, int n_members)
+{
+    ARG(out && desc);
+    *out = nullptr;
+    if (n_members < 1 || n_members > SUHMO_BATCH_MAX) { suhmo_set_error("batch: n_members = %d, must be 1 .. %d", n_members, SUHMO_BATCH_MAX); return -1; }
+    if (desc->j0 != 0 || desc->ny_global != desc->ny || desc->i0 != 0 || desc->nx_global != 0 || desc->patch_ny != 0 || desc->patch_j0 != 0) {
+        suhmo_set_error("batch: members are whole levels (a rank strip or an AMR patch descriptor is refused: j0 / ny_global / i0 / nx_global / patch_*)");
+        return -5;
+    }
+    if (desc->nx < 4 || desc->ny < 4) { suhmo_set_error("batch: members of at least 4 x 4 cells (the fused UpdateOperator kernel)"); return -5; }
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { (void)hipGetLastError(); suhmo_set_error("no HIP device: the product path has no CPU fallback"); return -3; }
+    suhmo_batch *B = new (std::nothrow) suhmo_batch();
+    if (!B) { suhmo_set_error("out of memory"); return -2; }
+    B->n = n_members; B->device = desc->device; B->has_alpha = desc->alpha != 0.0; B->tile_order = 0;
+    auto fail = [&](int rc) { (void)suhmo_batch_destroy(B); return rc; };
+    for (int k = 0; k < n_members; k++) {
+        suhmo_level *L = nullptr;
+        int rc = suhmo_level_create(&L, desc);
+        if (rc) return fail(rc);                              // (no device: rc -3 with suhmo_level_create's message)
+        L->batch_owned = 1;
+        B->mem.push_back(L);
+    }
+    B->ndepth = B->mem[0]->ndepth;
+    if (hipSetDevice(B->device) != hipSuccess) { suhmo_set_error("batch: hipSetDevice failed"); return fail(-2); }
+    for (suhmo_level *L : B->mem)
+        for (int dep = 0; dep < B->ndepth; dep++) {
+            Depth &D = L->d[dep];
+            for (int f : {SUHMO_F_LPHI, SUHMO_F_PHIOLD, SUHMO_F_CORR, SUHMO_F_RES})
+                if (!suhmo_field(L, dep, f)) { suhmo_set_error("batch: field allocation failed"); return fail(-2); }
+            if (!D.phi_alt) {
+                if (hipMalloc(&D.phi_alt, D.elems * sizeof(double)) != hipSuccess || hipMemset(D.phi_alt, 0, D.elems * sizeof(double)) != hipSuccess) {
+                    suhmo_set_error("batch: hipMalloc failed"); return fail(-2);
+                }
+            }
+        }
+    for (int dep = 0; dep < B->ndepth; dep++) {
+        B->h_dv[dep].resize(n_members); B->h_fp[dep].resize(n_members);
+        memset(B->h_dv[dep].data(), 0, n_members * sizeof(DV)); memset(B->h_fp[dep].data(), 0, n_members * sizeof(FP));
+        if (hipMalloc(&B->d_dv[dep], n_members * sizeof(DV)) != hipSuccess || hipMalloc(&B->d_fp[dep], n_members * sizeof(FP)) != hipSuccess) {
+            suhmo_set_error("batch: hipMalloc failed"); return fail(-2);
+        }
+    }
+    B->h_ph.resize(n_members);
+    memset(B->h_ph.data(), 0, n_members * sizeof(suhmo_phys_t));
+    B->np = suhmo_batch_residual_partials(view(B, 0));
+    if (hipMalloc(&B->d_ph, n_members * sizeof(suhmo_phys_t)) != hipSuccess || hipMalloc(&B->partial, 2 * n_members * B->np * sizeof(double)) != hipSuccess
+        || hipHostMalloc(&B->hslot, (SLOT_FLAG + 8) * sizeof(double), hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess
+        || hipHostGetDevicePointer((void **)&B->hslot_dev, B->hslot, 0) != hipSuccess) {
+        suhmo_set_error("batch: allocation of the tables / the pinned slot failed"); return fail(-2);
+    }
+    memset(B->hslot, 0, (SLOT_FLAG + 8) * sizeof(double));
+    B->h_mp.resize(n_members);
+    memset(B->h_mp.data(), 0xff, n_members * sizeof(suhmo_model_params_t));
+    if (hipMalloc(&B->d_mp, n_members * sizeof(suhmo_model_params_t)) != hipSuccess) { suhmo_set_error("batch: hipMalloc failed"); return fail(-2); }
+    { int rc = suhmo_batch_avg_table(B->mem.data(), n_members, &B->d_avg); if (rc) return fail(rc); }
+    B->phase = all_members(B);
+    *out = B;
+    return 0;
+}
+extern "C" int suhmo_batch_size(const suhmo_batch_t *B) { return B ? B->n : 0; }
+extern "C" suhmo_level_t *suhmo_batch_member(suhmo_batch_t *B, int k)
+{
+    if (!B || k < 0 || k >= B->n) { suhmo_set_error("batch: no member %d", k); return nullptr; }
+    return B->mem[k];
+}
+
+extern "C" int suhmo_batch_set_phys(suhmo_batch_t *B, int k, const suhmo_phys_t *phys)
+{
+    ARG(B && phys && k >= 0 && k < B->n);
+    suhmo_level *L = B->mem[k];
+    L->ph = *phys; L->desc.phys = *phys;
+    suhmo_level_drop_graphs(L);                               // (captured launches of the member's own V-cycles carry the constants by value)
+    return 0;
+}
+
+extern "C" int suhmo_batch_vcycle(suhmo_batch_t *B, const suhmo_solver_params_t *sp, const int *active, suhmo_stream_t s)
+{
+    SUHMO_TIME("AMRFASMultiGrid::VCycle");
+    ARG(B && sp);
+    int rc = batch_enter(B, (hipStream_t)s); if (rc) return rc;
+    BatchSel sel = all_members(B);
+    if (active) { sel.n = 0; for (int k = 0; k < B->n; k++) if (active[k]) sel.m[sel.n++] = (unsigned char)k; }
+    return batch_vcycle(B, sp, sel, (hipStream_t)s);          // (no member selected: nothing to do)
+}
+// the AMRMultiGrid::solve loop of the members in `first`, each with its own stopping rule; iters / residual: arrays over ALL members
+static int batch_solve(suhmo_batch *B, const suhmo_solver_params_t *sp, const BatchSel &first, int *iters, double *residual, hipStream_t st)
+{
+    int rc;
+    if (first.n <= 0) return 0;
+    std::vector<SolveNoInit> state(B->n);
+    std::vector<char> in(B->n, 0);
+    if ((rc = batch_residual_norms(B, first, st))) return rc;
+    for (int z = 0; z < first.n; z++) { in[first.m[z]] = 1; state[first.m[z]].start(B->hslot[first.m[z]]); }
+    for (;;) {
+        BatchSel sel; memset(&sel, 0, sizeof(sel));
+        for (int k = 0; k < B->n; k++) if (in[k] && state[k].go(sp)) sel.m[sel.n++] = (unsigned char)k;
+        if (!sel.n) break;
+        if ((rc = batch_vcycle(B, sp, sel, st)) || (rc = batch_residual_norms(B, sel, st))) return rc;
+        for (int z = 0; z < sel.n; z++) state[sel.m[z]].cycled(B->hslot[sel.m[z]]);
+    }
+    for (int k = 0; k < B->n; k++) if (in[k]) { if (iters) iters[k] = state[k].iter; if (residual) residual[k] = state[k].rnorm; }
+    // the ring as the solve of a level leaves it (suhmo_level_solve): the inhomogeneous fill of the final residual evaluation
+    if ((rc = suhmo_batch_fill_ghosts(tab(B, 0), first, view(B, 0), SUHMO_F_PHI, 0, st))) return rc;
+    B->launches++;
+    return 0;
+}
+extern "C" int suhmo_batch_solve(suhmo_batch_t *B, const suhmo_solver_params_t *sp, int *iters, double *residual, suhmo_stream_t s)
+{
+    SUHMO_TIME("AMRFASMultiGrid::solve");
+    ARG(B && sp);
+    int rc = batch_enter(B, (hipStream_t)s); if (rc) return rc;
+    return batch_solve(B, sp, all_members(B), iters, residual, (hipStream_t)s);
+}
+
+// ---- the time step: timestep_fas over the layout Batch (suhmo_step.hip), whose hooks reach the batch through these
+int suhmo_batch_size_(const suhmo_batch *B) { return B->n; }
+void suhmo_batch_count(suhmo_batch *B, int launches) { B->launches += launches; }
+bool suhmo_batch_step_select(suhmo_batch *B, const char *still)
+{
+    BatchSel sel; memset(&sel, 0, sizeof(sel));
+    for (int k = 0; k < B->n; k++) if (still[k]) sel.m[sel.n++] = (unsigned char)k;
+    B->phase = sel.n ? sel : all_members(B);
+    return sel.n > 0;
+}
+BatchStep suhmo_batch_step(suhmo_batch *B, bool reduction)
+{
+    if (reduction) ++B->hseq;
+    return BatchStep{tab(B, 0), B->phase, &view(B, 0), B->mem[0]->d[0].elems, B->d_mp, B->partial, B->hslot_dev,
+                     (unsigned long long *)(B->hslot_dev + SLOT_FLAG), B->hseq};
+}
+BatchSel suhmo_batch_step_subset(const suhmo_batch *B, const suhmo_model_params_t *mp_host, bool (*pick)(const suhmo_model_params_t &))
+{
+    BatchSel sel; memset(&sel, 0, sizeof(sel));
+    for (int z = 0; z < B->phase.n; z++) if (pick(mp_host[B->phase.m[z]])) sel.m[sel.n++] = B->phase.m[z];
+    return sel;
+}
+int suhmo_batch_step_mg_coefficients(suhmo_batch *B, hipStream_t st)
+{
+    int nl = 0;
+    int rc = suhmo_batch_build_mg_coefficients(tab(B, 0), B->d_avg, B->phase, B->mem[0], st, &nl);
+    B->launches += nl;
+    for (suhmo_level *L : B->mem) L->coarse_mask_ok = 1;
+    return rc;
+}
+int suhmo_batch_step_solve(suhmo_batch *B, const suhmo_solver_params_t *sp, int *iters, hipStream_t st) { return batch_solve(B, sp, B->phase, iters, nullptr, st); }
+int suhmo_batch_step_read(suhmo_batch *B, hipStream_t st, double *a, double *b)
+{
+    int rc = batch_readback(B, st); if (rc) return rc;
+    for (int z = 0; z < B->phase.n; z++) { const int k = B->phase.m[z]; a[k] = B->hslot[2 * k]; b[k] = B->hslot[2 * k + 1]; }
+    return 0;
+}
+// the step's entry: tables against the handles (the step's fields have just been allocated), mp[n] on the device, everybody in the first phase
+int suhmo_batch_step_begin(suhmo_batch *B, const suhmo_model_params_t *mp, hipStream_t st)
+{
+    int rc = batch_enter(B, st); if (rc) return rc;
+    if (memcmp(B->h_mp.data(), mp, B->n * sizeof(suhmo_model_params_t))) {
+        HIPCHK(hipStreamSynchronize(st));                    // (no launch in flight reads the rows about to change)
+        memcpy(B->h_mp.data(), mp, B->n * sizeof(suhmo_model_params_t));
+        HIPCHK(hipMemcpy(B->d_mp, B->h_mp.data(), B->n * sizeof(suhmo_model_params_t), hipMemcpyHostToDevice));
+    }
+    B->phase = all_members(B);
+    return 0;
+}
+extern "C" int suhmo_batch_timestep(suhmo_batch_t *B, const suhmo_model_params_t *mp, double dt, int cur_step, int *picard_iters, int *vcycles,
+                                    suhmo_stream_t s)
+{
+    SUHMO_TIME("AmrHydro::timeStepFAS");
+    ARG(B && mp);
+    for (int k = 0; k < B->n; k++)
+        if (mp[k].use_impl_diff) { suhmo_set_error("batch: use_impl_diff = 1 (member %d): the implicit gap-height solve of a batch is not built", k); return -5; }
+    HIPCHK(hipSetDevice(B->device));
+    return suhmo_batch_timestep_run(B, mp, dt, cur_step, picard_iters, vcycles, (hipStream_t)s);
+}
+
+extern "C" int suhmo_batch_set_option(suhmo_batch_t *B, const char *key, long value)
+{
+    ARG(B && key);
+    if (!strcmp(key, "tile_order")) { ARG(value >= 0 && value <= 2); B->tile_order = (int)value; return 0; }
+    if (!strcmp(key, "bottom_solver")) {
+        if (value == 0) return 0;
+        suhmo_set_error("batch: bottom_solver = %ld is not built (the one-launch RelaxSolver keeps its loop state per level; the bottom of a batched cycle is its numBottom relaxes)", value);
+        return -5;
+    }
+    if (!strcmp(key, "batch_launches") || !strcmp(key, "batch_readbacks") || !strcmp(key, "batch_member_cycles")) { suhmo_set_error("batch: option %s is read-only", key); return -1; }
+    suhmo_set_error("batch: unknown option %s", key);
+    return -1;
+}
+extern "C" int suhmo_batch_get_option(const suhmo_batch_t *B, const char *key, long *value)
+{
+    ARG(B && key && value);
+    if (!strcmp(key, "tile_order")) *value = B->tile_order;
+    else if (!strcmp(key, "bottom_solver")) *value = 0;
+    else if (!strcmp(key, "batch_launches")) *value = B->launches;
+    else if (!strcmp(key, "batch_readbacks")) *value = B->readbacks;
+    else if (!strcmp(key, "batch_member_cycles")) *value = B->member_cycles;
+    else { suhmo_set_error("batch: unknown option %s", key); return -1; }
+    return 0;
+}

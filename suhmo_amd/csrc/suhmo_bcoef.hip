@@ -2,6 +2,7 @@
 // coefficient coarsening.  (Split off suhmo_level.hip in round 4; reference citations: file:line in the SUHMO checkout.)
 #include "suhmo_hier.h"
 #include "suhmo_level_int.h"
+#include "suhmo_batch.h"
 #include <algorithm>
 #include <cmath>
 #include <initializer_list>
@@ -384,13 +385,27 @@ __global__ __launch_bounds__(256) void k_mask_halo_report(MaskHalo h, unsigned *
     if (neg) *negflag = epoch;
 }
 template <int BT_X, int BT_Y>
-__global__ __launch_bounds__(256) void k_bcoef_fused(DV v, FP fp, suhmo_phys_t ph, int hasMask, unsigned *negflag, unsigned epoch)
+__device__ __forceinline__ void d_bcoef_fused(const DV &v, const FP &fp, const suhmo_phys_t &ph, int hasMask, unsigned *negflag, unsigned epoch)
 {
     __shared__ double sphi[(BT_X + 4) * (BT_Y + 4)], sB[(BT_X + 2) * (BT_Y + 2)], sM[(BT_X + 2) * (BT_Y + 2)];
     const int i0 = blockIdx.x * BT_X, j0 = blockIdx.y * BT_Y;
     const bool interior = i0 - 2 >= 0 && i0 + BT_X + 1 <= v.nx - 1 && j0 - 2 >= 0 && j0 + BT_Y + 1 <= v.ny - 1;
     if (interior) bcoef_tile<true, BT_X, BT_Y>(v, fp, ph, hasMask, sphi, sB, sM, negflag, epoch);
     else bcoef_tile<false, BT_X, BT_Y>(v, fp, ph, hasMask, sphi, sB, sM, negflag, epoch);
+}
+template <int BT_X, int BT_Y>
+__global__ __launch_bounds__(256) void k_bcoef_fused(DV v, FP fp, suhmo_phys_t ph, int hasMask, unsigned *negflag, unsigned epoch)
+{
+    d_bcoef_fused<BT_X, BT_Y>(v, fp, ph, hasMask, negflag, epoch);
+}
+// every active member of a batch (suhmo_batch.h); no report on the ice mask: the batched relaxation always reads it.  The tile is the
+// level's default (bcoef_tile_x = 62: 62 x 14 cells on 64 x 4 threads); the wide tile is an A/B option of large levels
+constexpr int BCOEF_B_TX = 62, BCOEF_B_TY = 14;
+__global__ __launch_bounds__(256) void k_bcoef_fused_b(BatchTab t, BatchSel sel)
+{
+    const int k = batch_member(sel);
+    const suhmo_phys_t ph = t.ph[k];
+    d_bcoef_fused<BCOEF_B_TX, BCOEF_B_TY>(t.dv[k], batch_fp(t, k), ph, ph.use_mask_gradients, nullptr, 0u);
 }
 
 extern "C" int suhmo_level_update_operator(suhmo_level_t *L, int depth, suhmo_stream_t s)
@@ -513,8 +528,8 @@ int suhmo_grad_re(suhmo_level *L, int depth, hipStream_t st)
 
 // AverageOperator: CoarseAverageFace(bCoef[0] -> bCoef[depth], ratio r = 2^depth), sequential
 // sum of the r collinear fine faces divided by r  (src/VCAMRNonLinearPoissonOp.cpp:66-95)
-__global__ void k_average_faces(DV vf, const double *__restrict__ bxf, const double *__restrict__ byf,
-                                DV vc, double *__restrict__ bxc, double *__restrict__ byc, int r)
+__device__ __forceinline__ void d_average_faces(const DV &vf, const double *__restrict__ bxf, const double *__restrict__ byf,
+                                                const DV &vc, double *__restrict__ bxc, double *__restrict__ byc, int r)
 {
     int ic = blockIdx.x * blockDim.x + threadIdx.x, jc = blockIdx.y * blockDim.y + threadIdx.y;
     if (ic > vc.nx || jc > vc.ny) return;
@@ -530,6 +545,17 @@ __global__ void k_average_faces(DV vf, const double *__restrict__ bxf, const dou
         for (int k = 0; k < r; k++) sm = sm + byf[base + k];
         byc[cidx(vc, ic, jc)] = sm / (double)r;
     }
+}
+__global__ void k_average_faces(DV vf, const double *__restrict__ bxf, const double *__restrict__ byf,
+                                DV vc, double *__restrict__ bxc, double *__restrict__ byc, int r)
+{
+    d_average_faces(vf, bxf, byf, vc, bxc, byc, r);
+}
+__global__ void k_average_faces_b(BatchTab f, BatchTab c, BatchSel sel, int r)      // every active member of a batch (suhmo_batch.h)
+{
+    const int k = batch_member(sel);
+    const FP &ff = f.fp[k], &fc = c.fp[k];                   // (faces: no second canvas)
+    d_average_faces(f.dv[k], ff.f[SUHMO_F_BX], ff.f[SUHMO_F_BY], c.dv[k], fc.f[SUHMO_F_BX], fc.f[SUHMO_F_BY], r);
 }
 // All depths of AverageOperator in ONE pass over the depth-0 faces (the V-cycle refreshes every
 // depth right after UpdateOperator).  The reference's arithmetic is a sequential sum of the
@@ -604,11 +630,15 @@ __device__ __forceinline__ void d_average_faces_y_all(const DV &vf, const double
 
 // both directions in ONE launch of 256-thread workgroups: the first gxx * gxy of them are the x-face walkers (64 x 4 threads), the rest the
 // y-face walkers (four waves): nothing of one reads what the other writes
-__global__ __launch_bounds__(256) void k_average_faces_all(DV vf, const double *__restrict__ bxf, const double *__restrict__ byf, AvgOut o, int nd, int gxx, int gxy, int gyx)
+__device__ __forceinline__ void d_average_faces_all(const DV &vf, const double *__restrict__ bxf, const double *__restrict__ byf, const AvgOut &o, int nd, int gxx, int gxy, int gyx)
 {
     const int b = blockIdx.x, nbx = gxx * gxy;
     if (b < nbx) d_average_faces_x_all(vf, bxf, o, nd, b % gxx, b / gxx, threadIdx.x & 63, threadIdx.x >> 6);
     else d_average_faces_y_all(vf, byf, o, nd, (b - nbx) % gyx, (b - nbx) / gyx, threadIdx.x);
+}
+__global__ __launch_bounds__(256) void k_average_faces_all(DV vf, const double *__restrict__ bxf, const double *__restrict__ byf, AvgOut o, int nd, int gxx, int gxy, int gyx)
+{
+    d_average_faces_all(vf, bxf, byf, o, nd, gxx, gxy, gyx);
 }
 
 extern "C" int suhmo_level_average_operator(suhmo_level_t *L, int depth, suhmo_stream_t s)
@@ -625,22 +655,32 @@ extern "C" int suhmo_level_average_operator(suhmo_level_t *L, int depth, suhmo_s
     return 0;
 }
 
+static void fill_avg_out(const suhmo_level *L, int nd, AvgOut &o)
+{
+    for (int d = 0; d < nd; d++) { o.bx[d] = L->d[d].fp.f[SUHMO_F_BX]; o.by[d] = L->d[d].fp.f[SUHMO_F_BY]; o.P[d] = L->d[d].v.P; o.gy[d] = L->d[d].v.gy; }
+}
+static void avg_faces_grids(const DV &v, int nd, dim3 &gx, dim3 &gy)      // workgroups of the x-face and of the y-face walkers
+{
+    const int R = 1 << (nd - 1);
+    gx = dim3((v.nx / 2 + 1 + 63) / 64, (v.ny / R + 3) / 4);
+    gy = dim3((v.nx + 63) / 64, ((v.ny / 2 + 1 + AVG_YR - 1) / AVG_YR + 3) / 4);
+}
+static bool avg_faces_one_pass(const DV &v, int nd) { return !(nd > 7 || v.nx % (1 << (nd - 1)) || v.ny % (1 << (nd - 1))); }
 int suhmo_average_operator_all(suhmo_level *L, int nd, hipStream_t st)
 {
     Depth &F = L->d[0];
     const bool d0 = L->faces_deferred != 0;          // the halo rows of the depth-0 faces are still to travel
     L->faces_deferred = 0;
     if (nd < 2) return d0 ? suhmo_exchange_fields(L, 0, {SUHMO_F_BX, SUHMO_F_BY}, st) : 0;
-    if (nd > 7 || F.v.nx % (1 << (nd - 1)) || F.v.ny % (1 << (nd - 1))) {     // generic fallback
+    if (!avg_faces_one_pass(F.v, nd)) {     // generic fallback
         if (d0) { int rc = suhmo_exchange_fields(L, 0, {SUHMO_F_BX, SUHMO_F_BY}, st); if (rc) return rc; }
         for (int k = 1; k < nd; k++) { int rc = suhmo_level_average_operator(L, k, (suhmo_stream_t)st); if (rc) return rc; }
         return suhmo_agg_gather_faces(L, nd, st);
     }
     AvgOut o;
-    for (int d = 0; d < nd; d++) { o.bx[d] = L->d[d].fp.f[SUHMO_F_BX]; o.by[d] = L->d[d].fp.f[SUHMO_F_BY]; o.P[d] = L->d[d].v.P; o.gy[d] = L->d[d].v.gy; }
-    const int R = 1 << (nd - 1);
-    dim3 gx((F.v.nx / 2 + 1 + 63) / 64, (F.v.ny / R + 3) / 4);
-    dim3 gy((F.v.nx + 63) / 64, ((F.v.ny / 2 + 1 + AVG_YR - 1) / AVG_YR + 3) / 4);
+    fill_avg_out(L, nd, o);
+    dim3 gx, gy;
+    avg_faces_grids(F.v, nd, gx, gy);
     hipLaunchKernelGGL(k_average_faces_all, dim3(gx.x * gx.y + gy.x * gy.y), dim3(256), 0, st, F.v, F.fp.f[SUHMO_F_BX], F.fp.f[SUHMO_F_BY], o, nd, (int)gx.x, (int)gx.y, (int)gy.x);
     HIPCHK(hipGetLastError());
     // strips: the coarse face coefficients of all depths travel as one message group when the transport can batch
@@ -681,7 +721,7 @@ __device__ __forceinline__ double average_block(const double *__restrict__ f, in
     }
     return sm * (1.0 / (double)(r * r));
 }
-__global__ __launch_bounds__(256) void k_average_cells_all(DV vf, AvgAll a, int nd)
+__device__ __forceinline__ void d_average_cells_all(const DV &vf, const AvgAll &a, int nd)
 {
     // workgroups are numbered depth by depth (a grid sized for the largest depth would dispatch mostly empty ones)
     int dep = 1;
@@ -702,6 +742,10 @@ __global__ __launch_bounds__(256) void k_average_cells_all(DV vf, AvgAll a, int 
     default: m = average_block<0>(f, base, vf.P, r); break;
     }
     C.c[q][(jc + C.gy) * C.P + SUHMO_XOFF + ic] = m;
+}
+__global__ __launch_bounds__(256) void k_average_cells_all(DV vf, AvgAll a, int nd)
+{
+    d_average_cells_all(vf, a, nd);
 }
 // ghosts of coarse B / Pi / zb / mask: periodic wrap or Neumann copy (NeumBCForB :1309-1341)
 __device__ __forceinline__ void d_coef_ghosts(const DV &v, double *__restrict__ p)
@@ -731,7 +775,7 @@ __global__ void k_coef_ghosts_m(const DV *__restrict__ vt, const FP *__restrict_
 {
     d_coef_ghosts(vt[blockIdx.z], ft[blockIdx.z].f[field]);
 }
-__global__ void k_coef_ghosts_all(DV v0, AvgAll a)        // B, Pi, zb, mask of every coarse depth (blockIdx.y = (depth - 1) * 4 + field - 1)
+__device__ __forceinline__ void d_coef_ghosts_all(const DV &v0, const AvgAll &a)        // B, Pi, zb, mask of every coarse depth (blockIdx.y = (depth - 1) * 4 + field - 1)
 {
     const AvgDepth &C = a.d[blockIdx.y / 4];
     double *__restrict__ p = C.c[1 + blockIdx.y % 4];
@@ -752,6 +796,53 @@ __global__ void k_coef_ghosts_all(DV v0, AvgAll a)        // B, Pi, zb, mask of 
         else { int idx = (ny - 1 + C.gy) * P + SUHMO_XOFF + i; p[idx + P] = v0.per[1] ? p[idx - (ny - 1) * P] : p[idx]; }
     }
 }
+__global__ void k_coef_ghosts_all(DV v0, AvgAll a)
+{
+    d_coef_ghosts_all(v0, a);
+}
+// every active member of a batch (suhmo_batch.h): the member's pointers of all depths are a row of a device table written once
+struct BatchAvg { AvgAll a; AvgOut o; };
+__global__ __launch_bounds__(256) void k_average_cells_all_b(BatchTab t, const BatchAvg *__restrict__ at, BatchSel sel, int nd)
+{
+    const int k = batch_member(sel);
+    d_average_cells_all(t.dv[k], at[k].a, nd);
+}
+__global__ void k_coef_ghosts_all_b(BatchTab t, const BatchAvg *__restrict__ at, BatchSel sel)
+{
+    const int k = batch_member(sel);
+    d_coef_ghosts_all(t.dv[k], at[k].a);
+}
+__global__ __launch_bounds__(256) void k_average_faces_all_b(BatchTab t, const BatchAvg *__restrict__ at, BatchSel sel, int nd, int gxx, int gxy, int gyx)
+{
+    const int k = batch_member(sel);
+    const FP &fp = t.fp[k];
+    d_average_faces_all(t.dv[k], fp.f[SUHMO_F_BX], fp.f[SUHMO_F_BY], at[k].o, nd, gxx, gxy, gyx);
+}
+__global__ void k_coef_ghosts_b(BatchTab t, BatchSel sel, int field)
+{
+    const int k = batch_member(sel);
+    d_coef_ghosts(t.dv[k], t.fp[k].f[field]);
+}
+__global__ __launch_bounds__(256) void k_gradcc_b(BatchTab t, BatchSel sel)
+{
+    const int k = batch_member(sel);
+    d_gradcc(t.dv[k], batch_fp(t, k), t.ph[k].use_mask_gradients);
+}
+__global__ void k_grad_ghosts_b(BatchTab t, BatchSel sel)
+{
+    const int k = batch_member(sel);
+    d_grad_ghosts(t.dv[k], t.fp[k].f[SUHMO_F_GRADX], t.fp[k].f[SUHMO_F_GRADY]);
+}
+__global__ __launch_bounds__(256) void k_re_b(BatchTab t, BatchSel sel)
+{
+    const int k = batch_member(sel);
+    d_re(t.dv[k], t.fp[k], t.ph[k]);
+}
+__global__ __launch_bounds__(256) void k_bcoef_faces_b(BatchTab t, BatchSel sel)
+{
+    const int k = batch_member(sel);
+    d_bcoef_faces(t.dv[k], t.fp[k], t.ph[k]);
+}
 // exchange + CopyGhostCells of a cell field (util/ExtrapGhostCells.cpp:182-269)
 int suhmo_copy_ghosts(suhmo_level *L, int depth, int field, hipStream_t st)
 {
@@ -763,24 +854,29 @@ int suhmo_copy_ghosts(suhmo_level *L, int depth, int field, hipStream_t st)
     HIPCHK(hipGetLastError());
     return 0;
 }
+static int fill_avg_all(const suhmo_level *L, AvgAll &a)      // returns the workgroups of k_average_cells_all
+{
+    static const int fields[5] = {SUHMO_F_ACOEF, SUHMO_F_B, SUHMO_F_PI, SUHMO_F_ZB, SUHMO_F_MASK};
+    int nblocks = 0;
+    for (int q = 0; q < 5; q++) a.f[q] = L->d[0].fp.f[fields[q]];
+    for (int dep = 1; dep < L->ndepth; dep++) {
+        const Depth &C = L->d[dep];
+        AvgDepth &o = a.d[dep - 1];
+        o.nx = C.v.nx; o.ny = C.v.ny; o.P = C.v.P; o.gy = C.v.gy;
+        for (int q = 0; q < 5; q++) o.c[q] = C.fp.f[fields[q]];
+        o.boff = nblocks; o.nbx = (C.v.nx + 63) / 64;
+        nblocks += 5 * o.nbx * ((C.v.ny + 3) / 4);
+    }
+    return nblocks;
+}
 // with_faces = false: the caller's cycle re-averages bCoef itself (bcoeff_otf: UpdateOperator + AverageOperator every V-cycle)
 int suhmo_build_mg_coefficients(suhmo_level *L, bool with_faces, hipStream_t st)
 {
-    static const int fields[5] = {SUHMO_F_ACOEF, SUHMO_F_B, SUHMO_F_PI, SUHMO_F_ZB, SUHMO_F_MASK};
     Depth &F = L->d[0];
     const int nd = L->ndepth;
     if (nd > 1) {
         AvgAll a;
-        int nblocks = 0;
-        for (int q = 0; q < 5; q++) a.f[q] = F.fp.f[fields[q]];
-        for (int dep = 1; dep < nd; dep++) {
-            const Depth &C = L->d[dep];
-            AvgDepth &o = a.d[dep - 1];
-            o.nx = C.v.nx; o.ny = C.v.ny; o.P = C.v.P; o.gy = C.v.gy;
-            for (int q = 0; q < 5; q++) o.c[q] = C.fp.f[fields[q]];
-            o.boff = nblocks; o.nbx = (C.v.nx + 63) / 64;
-            nblocks += 5 * o.nbx * ((C.v.ny + 3) / 4);
-        }
+        const int nblocks = fill_avg_all(L, a);
         const Depth &C1 = L->d[1];
         hipLaunchKernelGGL(k_average_cells_all, dim3(nblocks), dim3(64, 4), 0, st, F.v, a, nd);
         const int n = 2 * C1.v.ny + 2 * C1.v.nx;
@@ -863,3 +959,93 @@ int suhmo_multi_coef_ghosts(const suhmo_multi &m, int field, hipStream_t st)
     return 0;
 }
 
+
+// ------------------------------------------------------------------ every active member of a batch of whole levels in one launch (suhmo_batch.hip)
+int suhmo_batch_update_operator(const BatchTab &t, const BatchSel &sel, const DV &v, hipStream_t st)
+{
+    if (sel.n <= 0) return 0;
+    hipLaunchKernelGGL(k_bcoef_fused_b, dim3((v.nx + BCOEF_B_TX - 1) / BCOEF_B_TX, (v.ny + BCOEF_B_TY - 1) / BCOEF_B_TY, sel.n), dim3(BCOEF_B_TX + 2, 256 / (BCOEF_B_TX + 2)), 0, st, t, sel);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+int suhmo_batch_average_operator(const BatchTab &f, const BatchTab &c, const BatchSel &sel, const DV &vc, int r, hipStream_t st)
+{
+    if (sel.n <= 0) return 0;
+    dim3 grd = grid2d(vc.nx + 1, vc.ny + 1); grd.z = sel.n;
+    hipLaunchKernelGGL(k_average_faces_b, grd, BLK2D, 0, st, f, c, sel, r);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+// the members' pointers of all depths (coefficient and face canvases: they never trade places): n rows, written once
+int suhmo_batch_avg_table(suhmo_level *const *mem, int n, void **dev)
+{
+    std::vector<BatchAvg> h(n);
+    for (int k = 0; k < n; k++) { memset(&h[k], 0, sizeof(BatchAvg)); fill_avg_all(mem[k], h[k].a); fill_avg_out(mem[k], mem[k]->ndepth, h[k].o); }
+    if (!*dev) HIPCHK(hipMalloc(dev, n * sizeof(BatchAvg)));
+    HIPCHK(hipMemcpy(*dev, h.data(), n * sizeof(BatchAvg), hipMemcpyHostToDevice));
+    return 0;
+}
+// AverageOperator of every depth > 0 in one pass over the depth-0 faces where the grid allows (*launches: how many it took)
+int suhmo_batch_average_operator_all(const BatchTab *tabs, const void *avg, const BatchSel &sel, const suhmo_level *L0, int nd, hipStream_t st, int *launches)
+{
+    *launches = 0;
+    if (sel.n <= 0 || nd < 2) return 0;
+    const DV &v = L0->d[0].v;
+    if (!avg_faces_one_pass(v, nd)) {
+        for (int dep = 1; dep < nd; dep++) {
+            int rc = suhmo_batch_average_operator(tabs[0], tabs[dep], sel, L0->d[dep].v, 1 << dep, st); if (rc) return rc;
+            ++*launches;
+        }
+        return 0;
+    }
+    dim3 gx, gy;
+    avg_faces_grids(v, nd, gx, gy);
+    hipLaunchKernelGGL(k_average_faces_all_b, dim3(gx.x * gx.y + gy.x * gy.y, 1, sel.n), dim3(256), 0, st, tabs[0], (const BatchAvg *)avg, sel, nd, (int)gx.x, (int)gx.y, (int)gy.x);
+    HIPCHK(hipGetLastError());
+    *launches = 1;
+    return 0;
+}
+// MGnewOp's coefficient averages of every depth > 0 and their ghosts (suhmo_build_mg_coefficients without the faces): two launches
+int suhmo_batch_build_mg_coefficients(const BatchTab &t0, const void *avg, const BatchSel &sel, const suhmo_level *L0, hipStream_t st, int *launches)
+{
+    *launches = 0;
+    const int nd = L0->ndepth;
+    if (sel.n <= 0 || nd < 2) return 0;
+    AvgAll a;
+    const int nblocks = fill_avg_all(L0, a);                 // (the geometry: the members share it)
+    const DV &v1 = L0->d[1].v;
+    hipLaunchKernelGGL(k_average_cells_all_b, dim3(nblocks, 1, sel.n), dim3(64, 4), 0, st, t0, (const BatchAvg *)avg, sel, nd);
+    const int n = 2 * v1.ny + 2 * v1.nx;
+    hipLaunchKernelGGL(k_coef_ghosts_all_b, dim3((n + 255) / 256, 4 * (nd - 1), sel.n), dim3(256), 0, st, t0, (const BatchAvg *)avg, sel);
+    HIPCHK(hipGetLastError());
+    *launches = 2;
+    return 0;
+}
+int suhmo_batch_copy_ghosts(const BatchTab &t, const BatchSel &sel, const DV &v, int field, hipStream_t st)
+{
+    if (sel.n <= 0) return 0;
+    const int n = 2 * v.ny + 2 * v.nx;
+    hipLaunchKernelGGL(k_coef_ghosts_b, dim3((n + 255) / 256, 1, sel.n), dim3(256), 0, st, t, sel, field);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+// suhmo_grad_re of every active member: cell-centred gradient, its ghosts, Re on the ghosted level (three launches)
+int suhmo_batch_grad_re(const BatchTab &t, const BatchSel &sel, const DV &v, hipStream_t st)
+{
+    if (sel.n <= 0) return 0;
+    dim3 g = grid2d(v.nx, v.ny), gr = grid2d(v.nx + 2, v.ny + 2); g.z = gr.z = sel.n;
+    const int n = 2 * v.ny + 2 * v.nx;
+    hipLaunchKernelGGL(k_gradcc_b, g, BLK2D, 0, st, t, sel);
+    hipLaunchKernelGGL(k_grad_ghosts_b, dim3((n + 255) / 256, 1, sel.n), dim3(256), 0, st, t, sel);
+    hipLaunchKernelGGL(k_re_b, gr, BLK2D, 0, st, t, sel);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+int suhmo_batch_bcoef_faces(const BatchTab &t, const BatchSel &sel, const DV &v, hipStream_t st)
+{
+    if (sel.n <= 0) return 0;
+    dim3 g = grid2d(v.nx + 1, v.ny + 1); g.z = sel.n;
+    hipLaunchKernelGGL(k_bcoef_faces_b, g, BLK2D, 0, st, t, sel);
+    HIPCHK(hipGetLastError());
+    return 0;
+}

@@ -139,6 +139,7 @@ struct ProfEv { hipEvent_t a, b; long cells; int restricts; };   // restricts: t
 
 struct suhmo_level {
     int ndepth;
+    int batch_owned;            // a member of a batch (suhmo_batch.hip): suhmo_level_destroy refuses it
     int stub;                   // geometry only: no canvas, no scratch (a box of a partitioned AMR level held by other ranks; suhmo_hier_plan.hip)
     Depth d[SUHMO_MAXDEPTH];
     suhmo_level_desc_t desc;
@@ -290,28 +291,37 @@ int suhmo_bottom_configure(suhmo_level *L, int solver, long one_launch_max_cells
 long suhmo_bottom_counter(const suhmo_level *L, int which);
 int suhmo_bottom_solve(suhmo_level *L, int dep, int tail, hipStream_t st);
 static inline int suhmo_halo_rows(const DV &v) { return v.gy < v.ny ? v.gy : v.ny; }
-// AMRMultiGrid::solveNoInit's stopping rule, for every level layout: `residual(&norm)` evaluates the residual and its norm, `cycle()`
-// runs one V-cycle; hist[0..*iters] receive the norms.  What differs between layouts (a cycle that leaves its residual behind, the
-// closing fill of the rings) stays with the callables and the caller.
+// AMRMultiGrid::solveNoInit's stopping rule as the state of ONE solve: the solve loop of a level layout below keeps one, a batch of levels
+// (suhmo_batch.hip) one per member, so that members stop at their own cycle.
+struct SolveNoInit {
+    double rnorm, initial_rnorm, norm_last;
+    int iter;
+    void start(double r) { rnorm = r; initial_rnorm = r; norm_last = 2.0 * r; iter = 0; }
+    bool go(const suhmo_solver_params_t *sp) const
+    {
+        const bool goNorm = rnorm > sp->norm_thresh, goRedu = rnorm > sp->eps * initial_rnorm, goIter = iter < sp->max_iter;
+        const bool goHang = iter < sp->imin || rnorm < (1.0 - sp->hang) * norm_last, goMin = iter < sp->iter_min;
+        return goMin || (goIter && goRedu && goHang && goNorm);
+    }
+    void cycled(double r) { norm_last = rnorm; rnorm = r; iter++; }       // one V-cycle later the residual norm is r
+};
+// The loop for every level layout: `residual(&norm)` evaluates the residual and its norm, `cycle()` runs one V-cycle; hist[0..*iters]
+// receive the norms.  What differs between layouts (a cycle that leaves its residual behind, the closing fill of the rings) stays with
+// the callables and the caller.
 template <class Residual, class Cycle>
 int suhmo_solve_no_init(const suhmo_solver_params_t *sp, int *iters, double *hist, Residual residual, Cycle cycle)
 {
     int rc;
     double rnorm = 0.0;
     if ((rc = residual(&rnorm))) return rc;
-    const double initial_rnorm = rnorm;
-    double norm_last = 2.0 * initial_rnorm;
-    int iter = 0;
+    SolveNoInit s;
+    s.start(rnorm);
     if (hist) hist[0] = rnorm;
-    for (;;) {
-        const bool goNorm = rnorm > sp->norm_thresh, goRedu = rnorm > sp->eps * initial_rnorm, goIter = iter < sp->max_iter;
-        const bool goHang = iter < sp->imin || rnorm < (1.0 - sp->hang) * norm_last, goMin = iter < sp->iter_min;
-        if (!(goMin || (goIter && goRedu && goHang && goNorm))) break;
-        norm_last = rnorm;
+    while (s.go(sp)) {
         if ((rc = cycle()) || (rc = residual(&rnorm))) return rc;
-        iter++;
-        if (hist) hist[iter] = rnorm;
+        s.cycled(rnorm);
+        if (hist) hist[s.iter] = rnorm;
     }
-    if (iters) *iters = iter;
+    if (iters) *iters = s.iter;
     return 0;
 }

@@ -21,6 +21,7 @@
 //                        recomputed redundantly, output goes to a second phi buffer (ping-
 //                        pong) so no workgroup ever reads a neighbour's updated cell.
 #include "suhmo_hier.h"
+#include "suhmo_batch.h"
 #include <type_traits>
 
 // ---- variant 0: one thread per active-colour cell ----
@@ -765,10 +766,10 @@ template <int T, bool RST> struct TileShape { static constexpr int TX = T, TY = 
 // 384 threads (3 pairs per thread, 161-168 VGPRs, 3 waves per SIMD on paper) -- the six waves of a workgroup land 2 + 2 + 1 + 1 on the
 // four SIMDs, a second workgroup no longer fits beside the first, and the 2048^2 launch takes 266 us instead of 203.
 template <int S, int T, bool RST> struct TileThreads { static constexpr int NT = 256; };
+// (the body, shared by the solo kernel and the batched one below: blockIdx.x = tile)
 template <int S, int T, bool HAS_ALPHA, bool RST = false, bool CHUNKED = false>
-__global__ __launch_bounds__((TileThreads<S, T, RST>::NT)) __attribute__((amdgpu_waves_per_eu((TileThreads<S, T, RST>::NT == 384 ? 3 : 2)))) void k_gsrb_tile(DV v,
-    FP fp, const double *__restrict__ pin, double *__restrict__ pout,
-                                                   suhmo_phys_t ph, TileGeom g)
+__device__ __forceinline__ void d_gsrb_tile(const DV &v, const FP &fp, const double *__restrict__ pin, double *__restrict__ pout,
+                                            const suhmo_phys_t &ph, const TileGeom &g)
 {
     constexpr int TX = TileShape<T, RST>::TX, TY = TileShape<T, RST>::TY;
     constexpr int HX = 2 * S + (RST ? 2 : 0), HY = 2 * S + (RST ? 1 : 0);
@@ -1127,13 +1128,44 @@ __global__ __launch_bounds__((TileThreads<S, T, RST>::NT)) __attribute__((amdgpu
         }
     }
 }
+#define TILE_KERNEL_ATTRS(S, T, RST) __launch_bounds__((TileThreads<S, T, RST>::NT)) __attribute__((amdgpu_waves_per_eu((TileThreads<S, T, RST>::NT == 384 ? 3 : 2))))
+template <int S, int T, bool HAS_ALPHA, bool RST = false, bool CHUNKED = false>
+__global__ TILE_KERNEL_ATTRS(S, T, RST) void k_gsrb_tile(DV v, FP fp, const double *__restrict__ pin, double *__restrict__ pout, suhmo_phys_t ph, TileGeom g)
+{
+    d_gsrb_tile<S, T, HAS_ALPHA, RST, CHUNKED>(v, fp, pin, pout, ph, g);
+}
+// every active member of a batch in one launch (blockIdx.z, through the active list: suhmo_batch.h): the member's row of the tables, its
+// head canvases as `alt` says they lie, the coarse canvases of the fused prolongation from the coarse depth's row
+template <int S, int T, bool HAS_ALPHA, bool CHUNKED>
+__global__ TILE_KERNEL_ATTRS(S, T, false) void k_gsrb_tile_b(BatchTab t, BatchTab c, BatchSel sel, TileGeom g, int prolong)
+{
+    const int k = batch_member(sel);
+    const DV v = t.dv[k];
+    const FP fp = batch_fp(t, k);
+    const suhmo_phys_t ph = t.ph[k];
+    if (prolong) { const FP fc = batch_fp(c, k); g.pc = fc.f[SUHMO_F_PHI]; g.pco = fc.f[SUHMO_F_PHIOLD]; }
+    d_gsrb_tile<S, T, HAS_ALPHA, false, CHUNKED>(v, fp, fp.f[SUHMO_F_PHI], fp.f[SUHMO_F_PHI2], ph, g);
+}
+template <bool HAS_ALPHA>
+__global__ __launch_bounds__(256) void k_gsrb_pass_simple_b(BatchTab t, BatchSel sel, int pass)
+{
+    const int k = batch_member(sel);
+    const DV v = t.dv[k];
+    d_gsrb_pass_simple<HAS_ALPHA>(v, batch_fp(t, k), t.ph[k], pass, 0, v.ny - 1);
+}
 
 static bool tile_ok(const suhmo_level *L, const Depth &D)
 {
     const DV &v = D.v;
-    if (!L->gsrb_tile || (v.nx & 1)) return false;
+    if (!L->gsrb_tile || !suhmo_batch_tile_ok(v)) return false;
     if ((v.rk[0] || v.rk[1]) && (!L->ex || !L->tile_strips || L->desc.nx_global > 0 || v.gy < 10 || v.ny < 10)) return false;   // rank strips: 2S + 1
                                                               // valid halo rows per launch (AMR patch strips: colour passes)
+    return true;
+}
+// what the tile kernel asks of the grid itself (a batch, whole levels only, asks nothing else)
+bool suhmo_batch_tile_ok(const DV &v)
+{
+    if (v.nx & 1) return false;                               // column pairs
     if (v.per[1] && (v.ny & 1)) return false;                 // colour of a periodic image = colour of the cell
     if ((v.per[0] && v.cfx[0] != v.cfx[1]) || (v.per[1] && v.ext[0] != v.ext[1])) return false;   // patch on one side of a periodic domain
     return true;
@@ -1199,12 +1231,14 @@ static int tile_edge(const suhmo_level *L, const DV &v)
 }
 // a level that is ONE tile (16-wide, or 32-wide when there are sweeps enough to pay for the larger region) can take all its
 // sweeps in one launch; returns the tile edge to use or 0
-static int single_tile(const suhmo_level *L, const DV &v)
+static int single_tile_of(int tile_t, const DV &v)
 {
-    if (L->tile_t != 32 && v.nx <= 16 && v.ny <= 16) return 16;
-    if (L->tile_t != 16 && v.nx <= 32 && v.ny <= 28) return 32;   // (the restricting variant of the 32-wide tile is 28 rows high)
+    if (tile_t != 32 && v.nx <= 16 && v.ny <= 16) return 16;
+    if (tile_t != 16 && v.nx <= 32 && v.ny <= 28) return 32;   // (the restricting variant of the 32-wide tile is 28 rows high)
     return 0;
 }
+static int single_tile(const suhmo_level *L, const DV &v) { return single_tile_of(L->tile_t, v); }
+int suhmo_batch_single_tile(const DV &v) { return single_tile_of(0, v); }
 static int launch_tile_any(suhmo_level *L, int depth, int S, int chunks, bool rst, int ext_rows, hipStream_t st)
 {
     const int T = chunks > 1 ? single_tile(L, L->d[depth].v) : tile_edge(L, L->d[depth].v);
@@ -1415,6 +1449,55 @@ int suhmo_launch_gsrb(suhmo_level *L, int depth, int sweeps, int tail, hipStream
         }
         it += done;
     }
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+// ------------------------------------------------------------------ a batch of whole levels (suhmo_batch.hip): every active member in one launch
+// T = 16 for depths of several tiles (the small levels a batch is for), 16 or 32 for a depth that is one tile (chunks > 1: S = 4)
+template <int S, int T, bool CHUNKED>
+static void launch_tile_b(const BatchTab &t, const BatchTab &c, const BatchSel &sel, const TileGeom &g, bool has_alpha, int prolong, hipStream_t st)
+{
+    const dim3 grd(g.ntx * g.nty, 1, sel.n), blk(TileThreads<S, T, false>::NT);
+    if (has_alpha) hipLaunchKernelGGL((k_gsrb_tile_b<S, T, true, CHUNKED>), grd, blk, 0, st, t, c, sel, g, prolong);
+    else hipLaunchKernelGGL((k_gsrb_tile_b<S, T, false, CHUNKED>), grd, blk, 0, st, t, c, sel, g, prolong);
+}
+int suhmo_batch_gsrb_tile(const BatchTab &t, const BatchTab *coarse, const DV *vc, const BatchSel &sel, const DV &v, int S, int T, int chunks, bool frhs, bool prolong,
+                          bool has_alpha, int order, hipStream_t st)
+{
+    if (sel.n <= 0) return 0;
+    TileGeom g;
+    g.jbeg = 0; g.jend = v.ny;
+    g.ntx = (v.nx + T - 1) / T; g.nty = (v.ny + T - 1) / T;
+    g.pc = g.pco = nullptr; g.Pc = g.gyc = 0;
+    g.rres = g.rphi = nullptr; g.rP = g.rgy = 0;
+    if (prolong) {
+        if (!coarse || !vc) { suhmo_set_error("internal: fused prolongation without the coarse tables"); return -4; }
+        g.Pc = vc->P; g.gyc = vc->gy;                         // (the canvases themselves: the member's coarse row, in the kernel)
+    }
+    g.chunks = chunks; g.order = order; g.frhs = frhs ? 1 : 0;
+    BatchTab c = coarse ? *coarse : t;
+    if (chunks > 1) {
+        if (S != 4 || g.ntx * g.nty != 1) { suhmo_set_error("internal: chunked tile launch of a batch"); return -4; }
+        if (T == 32) launch_tile_b<4, 32, true>(t, c, sel, g, has_alpha, prolong, st); else launch_tile_b<4, 16, true>(t, c, sel, g, has_alpha, prolong, st);
+    } else if (T == 32) {
+        if (S == 4) launch_tile_b<4, 32, false>(t, c, sel, g, has_alpha, prolong, st);
+        else if (S == 2) launch_tile_b<2, 32, false>(t, c, sel, g, has_alpha, prolong, st);
+        else launch_tile_b<1, 32, false>(t, c, sel, g, has_alpha, prolong, st);
+    } else {
+        if (S == 4) launch_tile_b<4, 16, false>(t, c, sel, g, has_alpha, prolong, st);
+        else if (S == 2) launch_tile_b<2, 16, false>(t, c, sel, g, has_alpha, prolong, st);
+        else launch_tile_b<1, 16, false>(t, c, sel, g, has_alpha, prolong, st);
+    }
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+int suhmo_batch_colour_pass(const BatchTab &t, const BatchSel &sel, const DV &v, int pass, bool has_alpha, hipStream_t st)
+{
+    if (sel.n <= 0) return 0;
+    const dim3 blk(64, 4), grd(((v.nx + 1) / 2 + 63) / 64, (v.ny + 3) / 4, sel.n);
+    if (has_alpha) hipLaunchKernelGGL(k_gsrb_pass_simple_b<true>, grd, blk, 0, st, t, sel, pass);
+    else hipLaunchKernelGGL(k_gsrb_pass_simple_b<false>, grd, blk, 0, st, t, sel, pass);
     HIPCHK(hipGetLastError());
     return 0;
 }

@@ -154,7 +154,7 @@ int suhmo_level_create_(suhmo_level_t **out, const suhmo_level_desc_t *desc, boo
     ARG(desc->device >= 0 && desc->device < ndev);
     HIPCHK(hipSetDevice(desc->device));
     suhmo_level *L = new suhmo_level();
-    L->desc = *desc; L->ph = desc->phys; L->device = desc->device;
+    L->desc = *desc; L->ph = desc->phys; L->device = desc->device; L->batch_owned = 0;
     L->ex = nullptr; L->ar = nullptr; L->ar2 = nullptr; L->ard = nullptr; L->user = nullptr; L->ex_begin = nullptr; L->ex_end = nullptr; L->rccl = nullptr;
         L->ipc = nullptr; L->ipc_owner = 0; L->faces_deferred = 0; L->gap = nullptr; L->gap_dt = 0.0; L->prof_on = 0; L->gsrb_variant = -1; L->fused_hc = 0;
     // defaults of the kernel-selection knobs (each with the measurement it comes from where it is declared, suhmo_common.h) ...
@@ -278,6 +278,7 @@ static int level_storage(suhmo_level *L)
 extern "C" int suhmo_level_destroy(suhmo_level_t *L)
 {
     if (!L) return 0;
+    if (L->batch_owned) { suhmo_set_error("this level is a member of a batch: suhmo_batch_destroy frees it"); return -1; }
     (void)hipSetDevice(L->device);
     (void)hipDeviceSynchronize();
     if (L->rccl) (void)suhmo_level_detach_rccl(L);

@@ -2,6 +2,7 @@
 // same for every box of a multi-box AMR level in one launch.  (Split off suhmo_level.hip in round 4; reference citations: file:line in the SUHMO checkout.)
 #include "suhmo_hier.h"
 #include "suhmo_level_int.h"
+#include "suhmo_batch.h"
 #include <algorithm>
 #include <cmath>
 #include <initializer_list>
@@ -104,7 +105,7 @@ __global__ __launch_bounds__(256) void k_apply(DV v, FP fp, suhmo_phys_t ph, int
 // RES = rhs - L(phi) and, in the same pass, the first stage of its max norm (one partial per workgroup, as k_norm_partial leaves them for
 // k_norm_final): the solve loop's residual evaluation on levels whose cycle's last launch cannot leave it behind (the tile-kernel sizes)
 template <bool HAS_ALPHA>
-__global__ __launch_bounds__(256) void k_residual_norm(DV v, FP fp, suhmo_phys_t ph, double *__restrict__ partial)
+__device__ __forceinline__ void d_residual_norm(const DV &v, const FP &fp, const suhmo_phys_t &ph, double *__restrict__ partial)
 {
     __shared__ double sm[4];
     const int i = blockIdx.x * blockDim.x + threadIdx.x, j = blockIdx.y * blockDim.y + threadIdx.y;
@@ -114,6 +115,29 @@ __global__ __launch_bounds__(256) void k_residual_norm(DV v, FP fp, suhmo_phys_t
     if (threadIdx.x == 0) sm[threadIdx.y] = r;
     __syncthreads();
     if (threadIdx.x == 0 && threadIdx.y == 0) partial[blockIdx.y * gridDim.x + blockIdx.x] = fmax(fmax(sm[0], sm[1]), fmax(sm[2], sm[3]));
+}
+template <bool HAS_ALPHA>
+__global__ __launch_bounds__(256) void k_residual_norm(DV v, FP fp, suhmo_phys_t ph, double *__restrict__ partial)
+{
+    d_residual_norm<HAS_ALPHA>(v, fp, ph, partial);
+}
+// every active member of a batch (suhmo_batch.h): member k's partial maxima at partial + k * workgroups, in the solo kernel's order
+template <bool HAS_ALPHA>
+__global__ __launch_bounds__(256) void k_residual_norm_b(BatchTab t, BatchSel sel, double *__restrict__ partial)
+{
+    const int k = batch_member(sel);
+    d_residual_norm<HAS_ALPHA>(t.dv[k], batch_fp(t, k), t.ph[k], partial + (size_t)k * gridDim.x * gridDim.y);
+}
+template <bool HAS_ALPHA, int MODE>
+__global__ __launch_bounds__(256) void k_apply_b(BatchTab t, BatchSel sel, int homog)
+{
+    const int k = batch_member(sel);
+    d_apply<HAS_ALPHA, MODE>(t.dv[k], batch_fp(t, k), t.ph[k], homog, 0, 0);
+}
+__global__ void k_fill_ghosts_b(BatchTab t, BatchSel sel, int field, int homog)
+{
+    const int k = batch_member(sel);
+    d_fill_ghosts(t.dv[k], batch_fp(t, k).f[field], homog);
 }
 // LPHI and RES = rhs - LPHI on a list of rectangles (x = first column, y = first row, z = columns, w = rows) of the level: the part of
 // a composite residual that has changed since the whole level was evaluated (suhmo_hier.hip); overlapping rectangles write the same values
@@ -318,7 +342,7 @@ extern "C" int suhmo_level_gsrb(suhmo_level_t *L, int depth, int sweeps, suhmo_s
 // per coarse cell; the four fine contributions are accumulated in the reference's loop order
 // (2I,2J), (2I+1,2J), (2I,2J+1), (2I+1,2J+1) onto a zero-initialised coarse value.
 template <bool HAS_ALPHA>
-__global__ __launch_bounds__(256) void k_restrict_residual(DV v, FP fp, DV vc, double *__restrict__ resC, double *__restrict__ phiC, suhmo_phys_t ph)
+__device__ __forceinline__ void d_restrict_residual(const DV &v, const FP &fp, const DV &vc, double *__restrict__ resC, double *__restrict__ phiC, const suhmo_phys_t &ph)
 {
     int I = blockIdx.x * blockDim.x + threadIdx.x, J = blockIdx.y * blockDim.y + threadIdx.y;
     if (I >= vc.nx || J >= vc.ny) return;
@@ -365,6 +389,18 @@ __global__ __launch_bounds__(256) void k_restrict_residual(DV v, FP fp, DV vc, d
     }
     resC[cidx(vc, I, J)] = acc;
     if (phiC) phiC[cidx(vc, I, J)] = accp;
+}
+template <bool HAS_ALPHA>
+__global__ __launch_bounds__(256) void k_restrict_residual(DV v, FP fp, DV vc, double *__restrict__ resC, double *__restrict__ phiC, suhmo_phys_t ph)
+{
+    d_restrict_residual<HAS_ALPHA>(v, fp, vc, resC, phiC, ph);
+}
+template <bool HAS_ALPHA>
+__global__ __launch_bounds__(256) void k_restrict_residual_b(BatchTab f, BatchTab c, BatchSel sel)      // RES and PHI of the coarse depth
+{
+    const int k = batch_member(sel);
+    const FP fc = batch_fp(c, k);
+    d_restrict_residual<HAS_ALPHA>(f.dv[k], batch_fp(f, k), c.dv[k], fc.f[SUHMO_F_RES], fc.f[SUHMO_F_PHI], f.ph[k]);
 }
 
 static int restrict_residual_impl(suhmo_level *L, int depth, bool also_phi, hipStream_t st)
@@ -435,19 +471,41 @@ extern "C" int suhmo_level_prolong_increment(suhmo_level_t *L, int depth, suhmo_
 // FAS correction of the cycle: CORR_c = 1*phi_c + (-1)*phi_c,old (LevelDataOps::axby), phi += P(CORR_c) (PROLONGNL).
 // On rank strips both kernels also cover the halo rows that are valid on BOTH depths (fine: phi_fresh rows, coarse:
 // phi_fresh rows of phi_c; PHIOLD was copied after the exchange), so the post-smoothing can start without an exchange.
-__global__ void k_axby_rows(DV v, double *__restrict__ dst, const double *__restrict__ x, const double *__restrict__ y, double a, double b, int jlo, int jhi)
+__device__ __forceinline__ void d_axby_rows(const DV &v, double *__restrict__ dst, const double *__restrict__ x, const double *__restrict__ y, double a, double b, int jlo, int jhi)
 {
     int i = blockIdx.x * blockDim.x + threadIdx.x, j = jlo + (int)(blockIdx.y * blockDim.y + threadIdx.y);
     if (i >= v.nx || j > jhi) return;
     int idx = cidx(v, i, j);
     dst[idx] = a * x[idx] + b * y[idx];
 }
-__global__ void k_prolong_rows(DV v, double *__restrict__ phi, DV vc, const double *__restrict__ c, int jlo, int jhi)
+__device__ __forceinline__ void d_prolong_rows(const DV &v, double *__restrict__ phi, const DV &vc, const double *__restrict__ c, int jlo, int jhi)
 {
     int i = blockIdx.x * blockDim.x + threadIdx.x, j = jlo + (int)(blockIdx.y * blockDim.y + threadIdx.y);
     if (i >= v.nx || j > jhi) return;
     int idx = cidx(v, i, j);
     phi[idx] = phi[idx] + c[cidx(vc, i / 2, j >> 1)];          // j >> 1: floor, halo rows have j < 0
+}
+__global__ void k_axby_rows(DV v, double *__restrict__ dst, const double *__restrict__ x, const double *__restrict__ y, double a, double b, int jlo, int jhi)
+{
+    d_axby_rows(v, dst, x, y, a, b, jlo, jhi);
+}
+__global__ void k_prolong_rows(DV v, double *__restrict__ phi, DV vc, const double *__restrict__ c, int jlo, int jhi)
+{
+    d_prolong_rows(v, phi, vc, c, jlo, jhi);
+}
+// every active member of a batch (suhmo_batch.h)
+__global__ void k_axby_rows_b(BatchTab t, BatchSel sel, int fd, int fx, int fy, double a, double b)
+{
+    const int k = batch_member(sel);
+    const DV v = t.dv[k];
+    const FP fp = batch_fp(t, k);
+    d_axby_rows(v, fp.f[fd], fp.f[fx], fp.f[fy], a, b, 0, v.ny - 1);
+}
+__global__ void k_prolong_rows_b(BatchTab f, BatchTab c, BatchSel sel)
+{
+    const int k = batch_member(sel);
+    const DV v = f.dv[k];
+    d_prolong_rows(v, batch_fp(f, k).f[SUHMO_F_PHI], c.dv[k], batch_fp(c, k).f[SUHMO_F_CORR], 0, v.ny - 1);
 }
 int suhmo_prolong_with_halo(suhmo_level *L, int depth, hipStream_t st)
 {
@@ -987,3 +1045,88 @@ int suhmo_multi_norm_max(const suhmo_multi &m, suhmo_level *slot, int field, dou
     return suhmo_readback(slot, st, out);
 }
 
+
+// ------------------------------------------------------------------ every active member of a batch of whole levels in one launch (suhmo_batch.hip)
+int suhmo_batch_fill_ghosts(const BatchTab &t, const BatchSel &sel, const DV &v, int field, int homog, hipStream_t st)
+{
+    if (sel.n <= 0) return 0;
+    const int n = 2 * v.ny + 2 * v.nx;
+    hipLaunchKernelGGL(k_fill_ghosts_b, dim3((n + 255) / 256, 1, sel.n), dim3(256), 0, st, t, sel, field, homog);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+int suhmo_batch_restrict_both(const BatchTab &f, const BatchTab &c, const BatchSel &sel, const DV &vc, bool has_alpha, hipStream_t st)
+{
+    if (sel.n <= 0) return 0;
+    dim3 grd = grid2d(vc.nx, vc.ny); grd.z = sel.n;
+    if (has_alpha) hipLaunchKernelGGL(k_restrict_residual_b<true>, grd, BLK2D, 0, st, f, c, sel);
+    else hipLaunchKernelGGL(k_restrict_residual_b<false>, grd, BLK2D, 0, st, f, c, sel);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+int suhmo_batch_fas_coarse_rhs(const BatchTab &t, const BatchSel &sel, const DV &v, bool has_alpha, hipStream_t st)
+{
+    if (sel.n <= 0) return 0;
+    dim3 grd = grid2d(v.nx, v.ny); grd.z = sel.n;
+    if (has_alpha) hipLaunchKernelGGL((k_apply_b<true, 2>), grd, BLK2D, 0, st, t, sel, 0);
+    else hipLaunchKernelGGL((k_apply_b<false, 2>), grd, BLK2D, 0, st, t, sel, 0);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+int suhmo_batch_prolong(const BatchTab &f, const BatchTab &c, const BatchSel &sel, const DV &vf, const DV &vc, hipStream_t st)
+{
+    if (sel.n <= 0) return 0;
+    dim3 gc = grid2d(vc.nx, vc.ny), gf = grid2d(vf.nx, vf.ny); gc.z = gf.z = sel.n;
+    hipLaunchKernelGGL(k_axby_rows_b, gc, BLK2D, 0, st, c, sel, (int)SUHMO_F_CORR, (int)SUHMO_F_PHI, (int)SUHMO_F_PHIOLD, 1.0, -1.0);
+    hipLaunchKernelGGL(k_prolong_rows_b, gf, BLK2D, 0, st, f, c, sel);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+// second stage of the members' max norms: a wave per member (the maximum is exact whatever the order), every value stored into the pinned
+// slot of its member, then ONE sequence number for all of them
+__global__ __launch_bounds__(256) void k_norm_final_b(BatchSel sel, const double *__restrict__ partial, int np, double *__restrict__ slot,
+                                                      unsigned long long *flag, unsigned long long seq)
+{
+    const int lane = threadIdx.x & 63;
+    for (int z = threadIdx.x >> 6; z < sel.n; z += 4) {
+        const int k = sel.m[z];
+        double acc = 0.0;
+        for (int q = lane; q < np; q += 64) acc = fmax(acc, partial[(size_t)k * np + q]);
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) acc = fmax(acc, __shfl_xor(acc, o));
+        if (lane == 0) slot[k] = acc;
+    }
+    __threadfence_system();
+    __syncthreads();
+    if (threadIdx.x == 0) __hip_atomic_store(flag, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+}
+size_t suhmo_batch_residual_partials(const DV &v) { const dim3 g = grid2d(v.nx, v.ny); return (size_t)g.x * g.y; }
+int suhmo_batch_residual_norm(const BatchTab &t, const BatchSel &sel, const DV &v, bool has_alpha, double *partial, double *slot,
+                              unsigned long long *flag, unsigned long long seq, hipStream_t st)
+{
+    if (sel.n <= 0) return 0;
+    dim3 grd = grid2d(v.nx, v.ny);
+    const int np = (int)(grd.x * grd.y);
+    grd.z = sel.n;
+    if (has_alpha) hipLaunchKernelGGL(k_residual_norm_b<true>, grd, BLK2D, 0, st, t, sel, partial);
+    else hipLaunchKernelGGL(k_residual_norm_b<false>, grd, BLK2D, 0, st, t, sel, partial);
+    hipLaunchKernelGGL(k_norm_final_b, dim3(1), dim3(256), 0, st, sel, partial, np, slot, flag, seq);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+__global__ void k_copy_canvas_b(BatchTab t, BatchSel sel, int fd, int fs, size_t elems)
+{
+    const int k = batch_member(sel);
+    const FP fp = batch_fp(t, k);
+    const double *__restrict__ src = fp.f[fs];
+    double *__restrict__ dst = fp.f[fd];
+    for (size_t q = (size_t)blockIdx.x * blockDim.x + threadIdx.x; q < elems; q += (size_t)gridDim.x * blockDim.x) dst[q] = src[q];
+}
+int suhmo_batch_copy_canvas(const BatchTab &t, const BatchSel &sel, int fd, int fs, size_t elems, hipStream_t st)
+{
+    if (sel.n <= 0) return 0;
+    const unsigned nb = (unsigned)std::min<size_t>((elems + 255) / 256, 256);
+    hipLaunchKernelGGL(k_copy_canvas_b, dim3(nb, 1, sel.n), dim3(256), 0, st, t, sel, fd, fs, elems);
+    HIPCHK(hipGetLastError());
+    return 0;
+}

@@ -15,6 +15,7 @@
 // Picard test is MAX all-reduced; the moulin integrals are evaluated redundantly over the whole domain (analytic
 // integrand, no data), so the result does not depend on the partition bit for bit.
 #include "suhmo_hier_int.h"
+#include "suhmo_batch.h"
 #include <cmath>
 
 using namespace hier;
@@ -80,6 +81,12 @@ __global__ __launch_bounds__(256) void k_qw_faces(DV v, FP fp, suhmo_phys_t ph)
 __global__ __launch_bounds__(256) void k_qw_faces_m(const DV *__restrict__ vt, const FP *__restrict__ ft, suhmo_phys_t ph)
 {
     d_qw_faces(vt[blockIdx.z], ft[blockIdx.z], ph);
+}
+// every active member of a batch (suhmo_batch.h): its own physics constants
+__global__ __launch_bounds__(256) void k_qw_faces_b(BatchTab t, BatchSel sel)
+{
+    const int k = batch_member(sel);
+    d_qw_faces(t.dv[k], batch_fp(t, k), t.ph[k]);
 }
 
 // MODE 0: melt rate + RHS_h (Picard iteration).  MODE 1: melt rate + gap-height RHS + forward Euler.
@@ -150,6 +157,13 @@ __global__ __launch_bounds__(256) void k_melt_m(const DV *__restrict__ vt, const
 {
     d_melt<MODE>(vt[blockIdx.z], ft[blockIdx.z], ph, mp, dt);
 }
+// every active member of a batch (suhmo_batch.h): its own physics constants and model parameters (mpt: device rows of mp[n])
+template <int MODE>
+__global__ __launch_bounds__(256) void k_melt_b(BatchTab t, BatchSel sel, const suhmo_model_params_t *__restrict__ mpt, double dt)
+{
+    const int k = batch_member(sel);
+    d_melt<MODE>(t.dv[k], batch_fp(t, k), t.ph[k], mpt[k], dt);
+}
 
 // run-state setting freeze_icefree_gap (suhmo_hip.h): cells without ice keep their gap height through SolveForGap_nl -- the solved
 // value of such a cell is replaced by the old one before the solution is copied back (valid cells; the ghosts are refilled afterwards)
@@ -183,8 +197,8 @@ static int exchange1(suhmo_level *L, int f, hipStream_t st) { return suhmo_excha
 // Both numbers of the Picard test in one pass and one read-back: max h and max |h_lagged - h|.  The reference's
 // max |(h_lagged - h) / maxHead| is the second divided by |maxHead| afterwards: a correctly rounded division by a fixed
 // divisor is monotone and sign-symmetric, so the maximum of the quotients is the quotient of the maximum, bit for bit.
-__global__ __launch_bounds__(256) void k_picard2_partial(DV v, const double *__restrict__ h, const double *__restrict__ hl,
-                                                         double *__restrict__ partial, Excl ex, const double *__restrict__ cover = nullptr)
+__device__ __forceinline__ void d_picard2_partial(const DV &v, const double *__restrict__ h, const double *__restrict__ hl,
+                                                  double *__restrict__ partial, const Excl &ex, const double *__restrict__ cover)
 {
     __shared__ double sm0[256], sm1[256];
     int tid = threadIdx.y * blockDim.x + threadIdx.x;
@@ -204,6 +218,35 @@ __global__ __launch_bounds__(256) void k_picard2_partial(DV v, const double *__r
         __syncthreads();
     }
     if (tid == 0) { int b = blockIdx.y * gridDim.x + blockIdx.x; partial[2 * b] = sm0[0]; partial[2 * b + 1] = sm1[0]; }
+}
+__global__ __launch_bounds__(256) void k_picard2_partial(DV v, const double *__restrict__ h, const double *__restrict__ hl,
+                                                         double *__restrict__ partial, Excl ex, const double *__restrict__ cover = nullptr)
+{
+    d_picard2_partial(v, h, hl, partial, ex, cover);
+}
+// every active member of a batch (suhmo_batch.h): the solo kernel's workgroups per member, its partial maxima at partial + 2 k workgroups
+__global__ __launch_bounds__(256) void k_picard2_partial_b(BatchTab t, BatchSel sel, double *__restrict__ partial)
+{
+    const int k = batch_member(sel);
+    const FP fp = batch_fp(t, k);
+    d_picard2_partial(t.dv[k], fp.f[SUHMO_F_PHI], fp.f[SUHMO_F_HLAG], partial + (size_t)k * 2 * gridDim.x * gridDim.y, Excl{0, 0, 0, 0}, nullptr);
+}
+// second stage for all of them: a wave per member (maxima: exact in any order), both values into the member's pinned slots, then ONE sequence number
+__global__ __launch_bounds__(256) void k_max2_final_b(BatchSel sel, const double *__restrict__ partial, int np, double *__restrict__ slot,
+                                                      unsigned long long *flag, unsigned long long seq)
+{
+    const int lane = threadIdx.x & 63;
+    for (int z = threadIdx.x >> 6; z < sel.n; z += 4) {
+        const int k = sel.m[z];
+        double a0 = -1.0e300, a1 = 0.0;
+        for (int q = lane; q < np; q += 64) { a0 = fmax(a0, partial[((size_t)k * np + q) * 2]); a1 = fmax(a1, partial[((size_t)k * np + q) * 2 + 1]); }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) { a0 = fmax(a0, __shfl_xor(a0, o)); a1 = fmax(a1, __shfl_xor(a1, o)); }
+        if (lane == 0) { slot[2 * k] = a0; slot[2 * k + 1] = a1; }
+    }
+    __threadfence_system();
+    __syncthreads();
+    if (threadIdx.x == 0) __hip_atomic_store(flag, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 __global__ void k_max2_final(const double *__restrict__ partial, int n, double *__restrict__ out, HostSlot hs)
 {
@@ -279,6 +322,11 @@ __global__ void k_extrap_ghosts_m(const DV *__restrict__ vt, const FP *__restric
 {
     d_extrap_ghosts(vt[blockIdx.z], ft[blockIdx.z].f[field]);
 }
+__global__ void k_extrap_ghosts_b(BatchTab t, BatchSel sel, int field)
+{
+    const int k = batch_member(sel);
+    d_extrap_ghosts(t.dv[k], t.fp[k].f[field]);
+}
 // dCoeff: CellToEdge(mR), CellToEdge(b), setup_iceMask_EC, COMPUTEDCOEFF (src/AmrHydro.cpp:1831-1862, ...F.ChF:241-265)
 __device__ __forceinline__ void d_dcoef_faces(const DV &v, const FP &fp, suhmo_phys_t ph, double rho_i)
 {
@@ -307,6 +355,11 @@ __global__ __launch_bounds__(256) void k_dcoef_faces_m(const DV *__restrict__ vt
 {
     d_dcoef_faces(vt[blockIdx.z], ft[blockIdx.z], ph, rho_i);
 }
+__global__ __launch_bounds__(256) void k_dcoef_faces_b(BatchTab t, BatchSel sel, const suhmo_model_params_t *__restrict__ mpt)
+{
+    const int k = batch_member(sel);
+    d_dcoef_faces(t.dv[k], t.fp[k], t.ph[k], mpt[k].rho_i);
+}
 // COMPUTEDIFTERM2D (src/AmrHydroF.ChF:289-343) of the gap height with its copied ghosts
 __device__ __forceinline__ void d_difterm(const DV &v, FP fp)
 {
@@ -327,6 +380,11 @@ __global__ __launch_bounds__(256) void k_difterm(DV v, FP fp)
 __global__ __launch_bounds__(256) void k_difterm_m(const DV *__restrict__ vt, const FP *__restrict__ ft)
 {
     d_difterm(vt[blockIdx.z], ft[blockIdx.z]);
+}
+__global__ __launch_bounds__(256) void k_difterm_b(BatchTab t, BatchSel sel)
+{
+    const int k = batch_member(sel);
+    d_difterm(t.dv[k], t.fp[k]);
 }
 static int diffusion_terms(suhmo_level *L, const suhmo_model_params_t *mp, hipStream_t st)
 {
@@ -439,6 +497,11 @@ static int picard_test(double maxHead, double maxd, int ite_idx, int cur_step, c
 // The skeleton over a level layout Y (OneLevel, Nested, BoxUnions below).  Y has `nlev`, `base` (level 0's handle, the one the head
 // solve's multigrid depths hang off) and `st`; its hooks gap_ghosts(l), chain(l) and melt_final(l) act on level l, the others on every
 // level in the layout's own launch order.
+// A layout may hold several independent MEMBERS on one grid (`nmem`; the three layouts of one model have 1; a batch: suhmo_batch.hip): the
+// hooks then act on the members of the current phase, mp, the solve's cycle counts and the Picard maxima are arrays over the members, and
+// `select(still)` tells the layout which members the next Picard iteration serves (returns false when none is left: the phases after
+// the loop serve everybody again).  Every member sees the sequence of one model.
+template <class Y> static int mg_coefficients(Y &y) { return suhmo_build_mg_coefficients(y.base, false, y.st); }
 template <class Y>
 static int timestep_fas(Y &y, const suhmo_model_params_t *mp, double dt, int cur_step, int *picard_iters, int *vcycles)
 {
@@ -446,19 +509,29 @@ static int timestep_fas(Y &y, const suhmo_model_params_t *mp, double dt, int cur
     // [I] ghosts of b (exchange + CopyGhostCells, :2385,:2429); ghosts of h are evaluated on the fly.  MGnewOp coarsening of B
     // (+ static Pi, zb, mask, aCoef): once per step, b does not change in [II]
     for (int l = 0; l < y.nlev; l++) if ((rc = y.gap_ghosts(l))) return rc;
-    if ((rc = suhmo_build_mg_coefficients(y.base, false, y.st))) return rc;      // bCoef: re-averaged by every V-cycle (bcoeff_otf)
+    if ((rc = mg_coefficients(y))) return rc;                                     // bCoef: re-averaged by every V-cycle (bcoeff_otf)
     suhmo_solver_params_t sp;
     head_solver_params(sp, cur_step);
-    int ite_idx = 0, nv = 0;
-    for (bool converged = false; !converged; ite_idx++) {                         // [II]
+    const int n = y.nmem;
+    int ite[SUHMO_BATCH_MAX], nv[SUHMO_BATCH_MAX], it[SUHMO_BATCH_MAX];
+    char still[SUHMO_BATCH_MAX];
+    double maxHead[SUHMO_BATCH_MAX], maxd[SUHMO_BATCH_MAX];
+    for (int k = 0; k < n; k++) { ite[k] = nv[k] = 0; still[k] = 1; }
+    for (int ite_idx = 0; y.select(still); ite_idx++) {                           // [II]
         if ((rc = y.lag_head())) return rc;                                       // h_lagged = h, coarse-fine ghosts of b and mR
         for (int l = 0; l < y.nlev; l++) if ((rc = y.chain(l))) return rc;       // grad h, Re, Qw
         if ((rc = y.head_rhs(mp, dt))) return rc;                                 // bCoef, melt rate, RHS_h
-        int it = 0;
-        if ((rc = y.solve_head(sp, &it))) return rc;                              // SolveForHead_nl, CoarseAverage of h
-        nv += it;
-        double maxHead = 0.0, maxd = 0.0;
-        if ((rc = y.picard_maxima(&maxHead, &maxd)) || (rc = picard_test(maxHead, maxd, ite_idx, cur_step, mp, converged))) return rc;
+        for (int k = 0; k < n; k++) { it[k] = 0; maxHead[k] = maxd[k] = 0.0; }
+        if ((rc = y.solve_head(sp, it))) return rc;                               // SolveForHead_nl, CoarseAverage of h
+        if ((rc = y.picard_maxima(maxHead, maxd))) return rc;
+        for (int k = 0; k < n; k++) {
+            if (!still[k]) continue;
+            bool converged = false;
+            nv[k] += it[k];
+            if ((rc = picard_test(maxHead[k], maxd[k], ite_idx, cur_step, &mp[k], converged))) return rc;
+            ite[k] = ite_idx + 1;
+            if (converged) still[k] = 0;
+        }
     }
     // [III] level by level: the coarse gap height is already updated when the fine ghost cells are filled
     for (int l = 0; l < y.nlev; l++) {
@@ -466,8 +539,7 @@ static int timestep_fas(Y &y, const suhmo_model_params_t *mp, double dt, int cur
         if (!mp->use_impl_diff && (rc = y.gap_ghosts(l))) return rc;             // (implicit: b stays, RES = b + dt RHS)
     }
     if (mp->use_impl_diff && (rc = y.solve_gap(mp, dt, cur_step))) return rc;    // SolveForGap_nl :3425-3455, then the ghosts of b
-    if (picard_iters) *picard_iters = ite_idx;
-    if (vcycles) *vcycles = nv;
+    for (int k = 0; k < n; k++) { if (picard_iters) picard_iters[k] = ite[k]; if (vcycles) vcycles[k] = nv[k]; }
     return 0;
 }
 
@@ -476,6 +548,8 @@ struct OneLevel {
     suhmo_level *base;
     hipStream_t st;
     int nlev = 1;
+    int nmem = 1;
+    bool select(const char *still) { return still[0] != 0; }
     int gap_ghosts(int) { int rc = suhmo_copy_ghosts(base, 0, SUHMO_F_B, st); return rc ? rc : exchange1(base, SUHMO_F_B, st); }   // :3419-3420 / :3451-3452
     int lag_head()
     {
@@ -518,6 +592,99 @@ extern "C" int suhmo_level_timestep(suhmo_level_t *L, const suhmo_model_params_t
     if (mp->use_moulin_source && !L->d[0].fp.f[SUHMO_F_MSRC]) { suhmo_set_error("use_moulin_source without suhmo_level_moulin_source"); return -1; }
     for (int f : step_fields) if (!suhmo_field(L, 0, f)) { suhmo_set_error("field allocation failed"); return -2; }
     OneLevel y{L, (hipStream_t)s};
+    return timestep_fas(y, mp, dt, cur_step, picard_iters, vcycles);
+}
+
+// ------------------------------------------------------------------ the time step on a batch of levels on one grid (suhmo_batch.hip)
+// OneLevel's hooks with every launch serving the members of the current phase (BatchStep): a whole level has no exchange, the chain is
+// suhmo_grad_re + Qw, the Picard maxima of all members come back in one read-back.  The diffusion terms run over the members whose
+// diffFactor is not 0, as level_melt decides for one model.
+static bool has_diffusion(const suhmo_model_params_t &m) { return m.diffFactor != 0.0; }
+struct Batch {
+    suhmo_batch *B;
+    hipStream_t st;
+    int nlev = 1;
+    int nmem;
+    bool select(const char *still) { return suhmo_batch_step_select(B, still); }
+    int gap_ghosts(int)
+    {
+        const BatchStep p = suhmo_batch_step(B);
+        suhmo_batch_count(B, 1);
+        return suhmo_batch_copy_ghosts(p.t, p.sel, *p.v, SUHMO_F_B, st);
+    }
+    int lag_head()
+    {
+        const BatchStep p = suhmo_batch_step(B);
+        suhmo_batch_count(B, 1);
+        return suhmo_batch_copy_canvas(p.t, p.sel, SUHMO_F_HLAG, SUHMO_F_PHI, p.elems, st);
+    }
+    int chain(int)
+    {
+        const BatchStep p = suhmo_batch_step(B);
+        int rc = suhmo_batch_grad_re(p.t, p.sel, *p.v, st); if (rc) return rc;
+        dim3 g((p.v->nx + 1 + 63) / 64, (p.v->ny + 1 + 3) / 4, p.sel.n);
+        hipLaunchKernelGGL(k_qw_faces_b, g, dim3(64, 4), 0, st, p.t, p.sel);
+        HIPCHK(hipGetLastError());
+        suhmo_batch_count(B, 4);
+        return 0;
+    }
+    int melt(const suhmo_model_params_t *mp, double dt, int final_, bool diffusion)
+    {
+        const BatchStep p = suhmo_batch_step(B);
+        const DV &v = *p.v;
+        if (diffusion) {
+            const BatchSel d = suhmo_batch_step_subset(B, mp, has_diffusion);
+            if (d.n > 0) {
+                const int n = 2 * v.ny + 2 * v.nx;
+                hipLaunchKernelGGL(k_extrap_ghosts_b, dim3((n + 255) / 256, 1, d.n), dim3(256), 0, st, p.t, d, (int)SUHMO_F_MR);
+                hipLaunchKernelGGL(k_dcoef_faces_b, dim3((v.nx + 1 + 63) / 64, (v.ny + 1 + 3) / 4, d.n), dim3(64, 4), 0, st, p.t, d, p.mp);
+                hipLaunchKernelGGL(k_difterm_b, dim3((v.nx + 63) / 64, (v.ny + 3) / 4, d.n), dim3(64, 4), 0, st, p.t, d);
+                suhmo_batch_count(B, 3);
+            }
+        }
+        const dim3 g((v.nx + 63) / 64, (v.ny + 3) / 4, p.sel.n);
+        if (!final_) hipLaunchKernelGGL(k_melt_b<0>, g, dim3(64, 4), 0, st, p.t, p.sel, p.mp, dt);
+        else hipLaunchKernelGGL(k_melt_b<1>, g, dim3(64, 4), 0, st, p.t, p.sel, p.mp, dt);
+        HIPCHK(hipGetLastError());
+        suhmo_batch_count(B, 1);
+        return 0;
+    }
+    int head_rhs(const suhmo_model_params_t *mp, double dt)
+    {
+        const BatchStep p = suhmo_batch_step(B);
+        int rc = suhmo_batch_bcoef_faces(p.t, p.sel, *p.v, st); if (rc) return rc;      // aCoeff_bCoeff :3087-3102
+        suhmo_batch_count(B, 1);
+        return melt(mp, dt, 0, true);                                                    // lagged melt rate :2548-2551, :2982-2992
+    }
+    int solve_head(const suhmo_solver_params_t &sp, int *it) { return suhmo_batch_step_solve(B, &sp, it, st); }
+    int picard_maxima(double *maxh, double *maxd)
+    {
+        const BatchStep p = suhmo_batch_step(B, true);
+        const DV &v = *p.v;
+        dim3 grd(std::min((v.nx + 63) / 64, 32), std::min((v.ny + 3) / 4, 128), p.sel.n);      // (the workgroups of picard_maxima, per member)
+        hipLaunchKernelGGL(k_picard2_partial_b, grd, dim3(64, 4), 0, st, p.t, p.sel, p.partial);
+        hipLaunchKernelGGL(k_max2_final_b, dim3(1), dim3(256), 0, st, p.sel, p.partial, (int)(grd.x * grd.y), p.slot, p.flag, p.seq);
+        HIPCHK(hipGetLastError());
+        suhmo_batch_count(B, 2);
+        return suhmo_batch_step_read(B, st, maxh, maxd);
+    }
+    int melt_final(int, const suhmo_model_params_t *mp, double dt) { return melt(mp, dt, 1, false); }
+    int solve_gap(const suhmo_model_params_t *, double, int) { suhmo_set_error("batch: the implicit gap-height solve (use_impl_diff) is not built"); return -5; }
+};
+static int mg_coefficients(Batch &y) { return suhmo_batch_step_mg_coefficients(y.B, y.st); }
+int suhmo_batch_timestep_run(suhmo_batch *B, const suhmo_model_params_t *mp, double dt, int cur_step, int *picard_iters, int *vcycles, hipStream_t st)
+{
+    int rc = 0;
+    for (int k = 0; k < suhmo_batch_size_(B) && !rc; k++) rc = check_step_args(&mp[k], dt, cur_step);
+    if (rc) return rc;
+    for (int k = 0; k < suhmo_batch_size_(B); k++) {
+        suhmo_level *L = suhmo_batch_member(B, k);
+        if (mp[k].use_moulin_source && !L->d[0].fp.f[SUHMO_F_MSRC]) { suhmo_set_error("use_moulin_source without suhmo_level_moulin_source (member %d)", k); return -1; }
+        for (int f : step_fields) if (!suhmo_field(L, 0, f)) { suhmo_set_error("field allocation failed"); return -2; }
+        if (mp[k].diffFactor != 0.0) for (int f : {SUHMO_F_DCX, SUHMO_F_DCY, SUHMO_F_DTERM}) if (!suhmo_field(L, 0, f)) { suhmo_set_error("field allocation failed"); return -2; }
+    }
+    if ((rc = suhmo_batch_step_begin(B, mp, st))) return rc;
+    Batch y{B, st, 1, suhmo_batch_size_(B)};
     return timestep_fas(y, mp, dt, cur_step, picard_iters, vcycles);
 }
 
@@ -574,6 +741,8 @@ struct Nested {
     bool strips;
     suhmo_level *base;
     hipStream_t st;
+    int nmem = 1;
+    bool select(const char *still) { return still[0] != 0; }
     int gap_ghosts(int l) { return amr_gap_ghosts(lv, nlev, l, st); }
     int lag_head()
     {
@@ -809,6 +978,8 @@ struct BoxUnions {
     int nlev;
     suhmo_level *base;
     hipStream_t st;
+    int nmem = 1;
+    bool select(const char *still) { return still[0] != 0; }
     int gap_ghosts(int l) { return hier_gap_ghosts(H, l, st); }
     int lag_head()
     {

@@ -291,6 +291,73 @@ class _BoxView(HipLevel):
         self.h = None
 
 
+class HipBatch:
+    """An ensemble of n whole levels on one grid (suhmo_batch_*, suhmo_amd/csrc/suhmo_batch.hip): V-cycles and solves of all members
+    through one launch sequence, every member bit for bit what it is alone.  bc gives the shared BC types and periodicity (and the
+    values every member starts with), phys the constants every member starts with; member(k) is an ordinary level."""
+
+    def __init__(self, n, nx, ny, dx, dy, bc, phys, alpha=0.0, beta=-1.0, max_box=64, device=0, stream=None):
+        self.n, self.nx, self.ny, self.dx, self.dy = n, nx, ny, dx, dy
+        self.stream = C.c_void_p(stream) if stream else C.c_void_p(0)
+        d = capi.LevelDesc()
+        d.nx, d.ny, d.j0, d.ny_global, d.dx, d.dy = nx, ny, 0, ny, dx, dy
+        d.nbox, d.boxes, d.max_box, d.alpha, d.beta = 0, None, max_box, alpha, beta
+        d.bc, d.phys, d.device, d.halo_rows = _bc(bc), _phys(phys), device, 1
+        h = C.c_void_p()
+        check(capi.lib().suhmo_batch_create(C.byref(h), C.byref(d), n))
+        self.h = h
+        self._members = [_BoxView(capi.lib().suhmo_batch_member(h, k), nx, ny, dx, dy, self.stream) for k in range(n)]
+        self.ndepth = self._members[0].ndepth
+
+    def close(self):
+        if getattr(self, "h", None):
+            for m in self._members:
+                m.close()
+            capi.lib().suhmo_batch_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __len__(self):
+        return self.n
+
+    def member(self, k):
+        return self._members[k]
+
+    def set_phys(self, k, phys):
+        p = _phys(phys)
+        check(capi.lib().suhmo_batch_set_phys(self.h, k, C.byref(p)))
+
+    def set_bc(self, k, bc):
+        """BC values of member k (the types and the periodicity are the batch's)"""
+        b = _bc(bc)
+        check(capi.lib().suhmo_level_set_bc(self._members[k].h, C.byref(b)))
+
+    def vcycle(self, sp, active=None):
+        s = solver_params(sp)
+        a = None if active is None else (C.c_int * self.n)(*[int(bool(x)) for x in active])
+        check(capi.lib().suhmo_batch_vcycle(self.h, C.byref(s), a, self.stream))
+
+    def solve(self, sp):
+        """(cycles, final residual max norm) of every member"""
+        s = solver_params(sp)
+        it, res = (C.c_int * self.n)(), np.zeros(self.n)
+        check(capi.lib().suhmo_batch_solve(self.h, C.byref(s), it, res.ctypes.data_as(C.POINTER(C.c_double)), self.stream))
+        return list(it), res
+
+    def set_option(self, key, value):
+        check(capi.lib().suhmo_batch_set_option(self.h, key.encode(), int(value)))
+
+    def get_option(self, key):
+        v = C.c_long()
+        check(capi.lib().suhmo_batch_get_option(self.h, key.encode(), C.byref(v)))
+        return v.value
+
+
 class HipHier:
     """Base level + levels that are unions of boxes (boxes[l-1] = list of (lo0, lo1, hi0, hi1) in the index space of
     level l), the reference's DisjointBoxLayout per AMR level: suhmo_hier_* (suhmo_amd/csrc/suhmo_hier*.hip)."""

@@ -103,6 +103,85 @@ class HipModel:
         self.level.close()
 
 
+class _MemberModel(HipModel):
+    """Member k of a HipBatchModel as a HipModel: state, moulin source, recharge and post-processing through the member's level handle
+    (stepping belongs to the batch)"""
+
+    def __init__(self, level, model):
+        self.level, self.nx, self.ny, self.dx, self.dy = level, level.nx, level.ny, level.dx, level.dy
+        self.model = dict(model)
+        self._mp = model_params(model)
+        self.cur_step = 0
+
+    def timestep(self, dt):
+        raise capi.SuhmoError("a member of a batch is stepped by HipBatchModel.timestep")
+
+    def close(self):
+        pass
+
+
+class HipBatchModel:
+    """An ensemble of n models on one grid stepped together (suhmo_batch_timestep, suhmo_amd/csrc/suhmo_batch.hip): shared grid, BC types,
+    dt and step number; per member every field, the BC values, the physics constants and the model parameters.  models: one dict per member
+    (as HipModel's); phys / bc: one for all or a list per member.  Every member's results are those of a HipModel run alone, bit for bit."""
+
+    FIELDS = HipModel.FIELDS
+
+    def __init__(self, nx, ny, dx, dy, bc, phys, models, max_box=64, device=0):
+        n = len(models)
+        bcs = list(bc) if isinstance(bc, (list, tuple)) else [bc] * n
+        phs = list(phys) if isinstance(phys, (list, tuple)) else [phys] * n
+        self.batch = lv.HipBatch(n, nx, ny, dx, dy, bcs[0], phs[0], alpha=0.0, beta=-1.0, max_box=max_box, device=device)
+        self.n, self.nx, self.ny, self.dx, self.dy = n, nx, ny, dx, dy
+        for k in range(n):
+            self.batch.set_bc(k, bcs[k])
+            self.batch.set_phys(k, phs[k])
+        self.members = [_MemberModel(self.batch.member(k), models[k]) for k in range(n)]
+        self._mp = (capi.ModelParams * n)(*[m._mp for m in self.members])
+        self.cur_step = 0
+
+    def member(self, k):
+        """member k with HipModel's methods: set_state, moulin_source, time_varying_recharge, get, postproc_*"""
+        return self.members[k]
+
+    def set_state(self, k, f):
+        self.members[k].set_state(f)
+
+    def set_model(self, k, **changes):
+        """change model parameters of member k between steps (e.g. ramp)"""
+        m = self.members[k]
+        m.model.update(changes)
+        m._mp = model_params(m.model)
+        self._mp[k] = m._mp
+
+    def timestep(self, dt):
+        """one step of every member; returns ([picard iterations], [V-cycles]) per member"""
+        self.cur_step += 1
+        pi, nv = (C.c_int * self.n)(), (C.c_int * self.n)()
+        check(capi.lib().suhmo_batch_timestep(self.batch.h, self._mp, float(dt), self.cur_step, pi, nv, self.batch.stream))
+        for m in self.members:
+            m.cur_step = self.cur_step
+        return list(pi), list(nv)
+
+    def get(self, k, name, ghosted=False):
+        return self.members[k].get(name, ghosted=ghosted)
+
+    def postproc_table(self, k):
+        return self.members[k].postproc_table()
+
+    def postproc_table_device(self, k):
+        return self.members[k].postproc_table_device()
+
+    def postproc_temporal(self, k):
+        return self.members[k].postproc_temporal()
+
+    def get_option(self, key):
+        return self.batch.get_option(key)
+
+    def close(self):
+        self.batch.close()
+
+
 class HipAmrModel:
     """The time loop on a hierarchy (base level + nested patches, patches[k] = box of level k+1 in the cells of level k):
     suhmo_amr_timestep over the array of level handles; head and gap height of every level stay in HBM."""

@@ -4,6 +4,8 @@ post-processing steps of input.hydro_pp; the six cases differ in suhmo.distribut
 loop and compares the cross-section table with the reference's committed result
 tests/golden/shmip_A<k>_postproc_reference.dat (a DATA fixture copied from exec/A_SHMIP/A<k>/results/postproc.dat).
 usage: run_shmip_a.py oracle|hip A<k> [nsteps] [out.json] [--head-melt-coef X] [--mask-gradients 0|1] [--freeze-icefree]
+       run_shmip_a.py --batch [nsteps] [--head-melt-coef 0] [--mask-gradients 0|1]    A1 ... A6 as ONE ensemble on the device
+                                                                                      (HipBatchModel); the same result per case
 --mask-gradients 0|1 overrides solver.use_mask_for_gradients of the case.
 --head-melt-coef X scales the melt term of RHS_h (src/AmrHydro.cpp:3046); X = 0 reproduces the code state the reference's
 committed results were evidently produced with ("end-to-end pin").  The oracle takes any X (environment knob); the
@@ -32,6 +34,42 @@ def compare(table, ref):
     return out
 
 
+def run_batch(nsteps, coef, mask_grad):
+    """A1 ... A6 stepped together (suhmo_batch_timestep): one launch sequence for the six runs, the single run's table per case"""
+    from suhmo_amd import model
+    from suhmo_amd import level as lv
+    cases = ["A1", "A2", "A3", "A4", "A5", "A6"]
+    ms = [sy.shmip_a_model(c) for c in cases]
+    if coef is not None:
+        assert float(coef) == 0.0, "the device path has the model option head_melt_off only"
+        ms = [dict(m, head_melt_off=1) for m in ms]
+    m0 = ms[0]
+    phys = sy.A3_PHYS if mask_grad is None else dict(sy.A3_PHYS, use_mask_gradients=mask_grad)
+    st = sy.shmip_initial_state(m0["nx"], m0["ny"], m0["lx"], m0["ly"])
+    nsteps = nsteps if nsteps is not None else m0["max_step"] + 2
+    t0 = time.time()
+    M = model.HipBatchModel(m0["nx"], m0["ny"], st["dx"], st["dy"], sy.A3_BC, phys, ms, max_box=64)
+    for k, m in enumerate(ms):
+        M.set_state(k, st)
+        M.member(k).level.set(lv.F_MR, np.full((m["ny"], m["nx"]), m["G"] / m["L"]))
+    tot_p, tot_v = [0] * len(ms), [0] * len(ms)
+    for k in range(nsteps):
+        p, v = M.timestep(m0["dt"])
+        tot_p = [a + b for a, b in zip(tot_p, p)]; tot_v = [a + b for a, b in zip(tot_v, v)]
+        if (k + 1) % 1000 == 0:
+            print("step %d  picard %s  vcycles %s  %.0f s" % (k + 1, tot_p, tot_v, time.time() - t0), flush=True)
+    secs = time.time() - t0
+    for k, case in enumerate(cases):
+        table, head, gap = M.postproc_table(k), M.get(k, "head"), M.get(k, "B")
+        ref = np.loadtxt(os.path.join(ROOT, "tests", "golden", "shmip_%s_postproc_reference.dat" % case))
+        print(json.dumps({"which": "hip-batch", "case": case, "head_melt_coef": coef, "mask_gradients": mask_grad, "steps": nsteps,
+                          "picard_total": tot_p[k], "vcycles_total": tot_v[k], "seconds_all_cases": secs,
+                          "head_min_max": [float(head.min()), float(head.max())], "gap_min_max": [float(gap.min()), float(gap.max())],
+                          "vs_reference": compare(table, ref)}, indent=1))
+    print("launches %d, read-backs %d for %d steps of %d runs" % (M.get_option("batch_launches"), M.get_option("batch_readbacks"), nsteps, len(ms)))
+    M.close()
+
+
 def main():
     coef = None
     if "--head-melt-coef" in sys.argv:
@@ -53,6 +91,9 @@ def main():
     if "--freeze-icefree" in sys.argv:
         sys.argv.remove("--freeze-icefree")
         freeze = True
+    if "--batch" in sys.argv:
+        sys.argv.remove("--batch")
+        return run_batch(int(sys.argv[1]) if len(sys.argv) > 1 else None, coef, mask_grad)
     which = sys.argv[1] if len(sys.argv) > 1 else "oracle"
     case = sys.argv[2] if len(sys.argv) > 2 else "A3"
     binp = None
