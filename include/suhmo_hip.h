@@ -504,14 +504,20 @@ int suhmo_hier_moulin_source(suhmo_hier_t *H, int n_moulins, const double *posit
  *                         iterations of the members still iterating (lagged chain, RHS_h, the solve above over exactly those members, ONE read-back
  *                         of all their Picard maxima, the test per member), [III] chain, melt rate, forward-Euler gap update and ghosts of all.
  *                         mp[n]: the model parameters of every member (use_moulin_source, distributed_input, ramp, diffFactor, head_melt_off, eps_picard, ...);
- *                         dt and cur_step are shared.  picard_iters[n], vcycles[n] (may be NULL).  use_impl_diff = 1 on any member: rc -5 (the implicit
- *                         gap solve is a second batch of linear operators: not built).  Moulin sources / recharge: suhmo_level_moulin_source /
- *                         suhmo_level_time_varying_recharge on the member handle.
+ *                         dt and cur_step are shared.  picard_iters[n], vcycles[n] (may be NULL).  use_impl_diff = 1 on any member: rc -5 unless
+ *                         option implicit_gap is 1.  With it, [III] is per member: forward-Euler members as above, the others through
+ *                         SolveForGap_nl on a second batch of linear operators the batch owns (created by the first step that needs it; alpha = 1,
+ *                         beta = dt x diffFactor of the member, Neumann-0 sides): one launch loads b, the right-hand side and D of all of them, one
+ *                         averages D to the coarse depths, the solve above runs with the gap solve's parameters, one launch stores the solution
+ *                         (freeze_icefree_gap per member), one fills the ghosts of b.  A batch may mix both kinds; use_impl_diff with diffFactor = 0
+ *                         on a member: rc -1.  Moulin sources / recharge: suhmo_level_moulin_source / suhmo_level_time_varying_recharge on the
+ *                         member handle.
  *   suhmo_batch_set_option / get_option   tile_order (0 .. 2, as the level's); bottom_solver: only 0 (1 is refused with rc -5: the bottom of a
- *                         batched cycle is its numBottom relaxes).  Read-only counters: batch_launches, batch_readbacks, batch_member_cycles
- *                         (V-cycles summed over the members that ran them).  An unknown key: rc -1.
+ *                         batched cycle is its numBottom relaxes); implicit_gap (0 / 1, default 0: see suhmo_batch_timestep).  Read-only counters:
+ *                         batch_launches, batch_readbacks (both include the gap solves), batch_member_cycles (V-cycles of head solves summed over
+ *                         the members that ran them), batch_gap_member_cycles (the same for the gap solves).  An unknown key: rc -1.
  * A batch relaxes every depth with the tile kernel (colour passes where the grid rules it out); eager launches only, no graph capture.
- * Not built: the implicit gap solve of a batch, rank strips, AMR patches and hierarchies as members, graph capture, bottom_solver = 1. */
+ * Not built: rank strips, AMR patches and hierarchies as members, graph capture, bottom_solver = 1. */
 typedef struct suhmo_batch suhmo_batch_t;
 int suhmo_batch_create(suhmo_batch_t **out, const suhmo_level_desc_t *desc, int n_members);
 int suhmo_batch_destroy(suhmo_batch_t *B);

@@ -67,4 +67,10 @@ int suhmo_batch_step_mg_coefficients(suhmo_batch *B, hipStream_t st);
 int suhmo_batch_step_solve(suhmo_batch *B, const suhmo_solver_params_t *sp, int *iters, hipStream_t st);   // SolveForHead_nl of the phase's members; iters[n]
 int suhmo_batch_step_read(suhmo_batch *B, hipStream_t st, double *a, double *b);                          // the pinned slots of the phase's members -> a[k], b[k]
 int suhmo_batch_step_begin(suhmo_batch *B, const suhmo_model_params_t *mp, hipStream_t st);   // tables against the handles, mp[n] on the device
+// SolveForGap_nl of the members `sel` (all with use_impl_diff) on the gap batch, sp = gap_solver_params; mp: host rows of ALL members
+int suhmo_batch_step_solve_gap(suhmo_batch *B, const BatchSel &sel, const suhmo_model_params_t *mp, double dt, const suhmo_solver_params_t *sp, hipStream_t st);
+// suhmo_step.hip: b, RES, DCX, DCY of the members -> PHI, RHS, BX, BY of their gap handles (whole canvases) in one launch; and PHI of the gap
+// handles -> b in one, cells without ice keeping their b where the member's freeze_icefree_gap is set (mpt: device rows of mp[n])
+int suhmo_batch_gap_load(const BatchTab &h, const BatchTab &g, const BatchSel &sel, size_t elems, hipStream_t st);
+int suhmo_batch_gap_store(const BatchTab &h, const BatchTab &g, const BatchSel &sel, const suhmo_model_params_t *mpt, size_t elems, hipStream_t st);
 int suhmo_batch_timestep_run(suhmo_batch *B, const suhmo_model_params_t *mp, double dt, int cur_step, int *picard_iters, int *vcycles, hipStream_t st);

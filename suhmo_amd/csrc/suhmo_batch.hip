@@ -11,6 +11,10 @@
 // Members are ordinary level handles owned by the batch (suhmo_batch_member): fields, BC values and physics constants are loaded and read
 // through the suhmo_level_* entry points.  Tables are compared with the handles at the start of every batch call and written again only
 // when a pointer, a view or a constant has changed.
+//
+// The implicit gap-height solve of the time step (option implicit_gap; SolveForGap_nl, src/AmrHydro.cpp:593-662, :3376-3455) runs on a second
+// batch the first one owns: N handles with the linear operator of gap_level_prepare (suhmo_step.hip), their own tables, the same cycle and
+// solve loop.  Its beta = dt x diffFactor is the member's own (the kernels read it from the member's row).
 #include "suhmo_batch.h"
 #include <new>
 
@@ -34,6 +38,10 @@ struct suhmo_batch {
     void *d_avg;                                            // the members' coefficient / face canvases of all depths (suhmo_bcoef.hip)
     suhmo_model_params_t *d_mp; std::vector<suhmo_model_params_t> h_mp;   // the time step: mp[n] on the device, rewritten when it changed
     BatchSel phase;                                         // the time step: the members the current phase serves
+    bool beta_per_member;                                   // a gap batch: beta belongs to the member (alpha and everything that shapes a launch stay shared)
+    int implicit_gap;                                       // option: members with use_impl_diff are stepped (default 0: refused)
+    suhmo_batch *gap;                                       // the gap batch, created by the first step that needs it; its counters add to this one's
+    std::vector<double> gap_beta;                           // beta its handle of member k holds
 };
 constexpr int SLOT_FLAG = 2 * SUHMO_BATCH_MAX;             // pinned slot: two values per member, then the sequence number
 
@@ -59,7 +67,7 @@ static int batch_sync(suhmo_batch *B, hipStream_t st)
             if (memcmp(&D.v, &B->h_dv[dep][k], sizeof(DV))) { B->h_dv[dep][k] = D.v; dirty = true; }
             // launch geometry and kernel variant are decided once for all members: what decides them must be shared (the BC VALUES are not)
             const DV &v0 = B->mem[0]->d[dep].v;
-            if (memcmp(D.v.bct, v0.bct, sizeof(v0.bct)) || memcmp(D.v.per, v0.per, sizeof(v0.per)) || D.v.alpha != v0.alpha || D.v.beta != v0.beta) {
+            if (memcmp(D.v.bct, v0.bct, sizeof(v0.bct)) || memcmp(D.v.per, v0.per, sizeof(v0.per)) || D.v.alpha != v0.alpha || (D.v.beta != v0.beta && !B->beta_per_member)) {
                 suhmo_set_error("batch: member %d differs from member 0 in BC types, periodicity or alpha / beta: these are shared by all members", k);
                 B->written = false;                          // (rows compared so far may be ahead of the device: the next call writes all)
                 return -1;
@@ -214,12 +222,12 @@ extern "C" int suhmo_batch_destroy(suhmo_batch_t *B)
     if (B->d_avg) (void)hipFree(B->d_avg);
     if (B->d_mp) (void)hipFree(B->d_mp);
     if (B->hslot) (void)hipHostFree(B->hslot);
+    if (B->gap) (void)suhmo_batch_destroy(B->gap);
     delete B;
     return 0;
 }
-extern "C" int suhmo_batch_create(suhmo_batch_t **out, const suhmo_level_desc_t *desc, int n_members)
+static int batch_create(suhmo_batch **out, const suhmo_level_desc_t *desc, int n_members, bool beta_per_member)
 {
-    ARG(out && desc);
     *out = nullptr;
     if (n_members < 1 || n_members > SUHMO_BATCH_MAX) { suhmo_set_error("batch: n_members = %d, must be 1 .. %d", n_members, SUHMO_BATCH_MAX); return -1; }
     if (desc->j0 != 0 || desc->ny_global != desc->ny || desc->i0 != 0 || desc->nx_global != 0 || desc->patch_ny != 0 || desc->patch_j0 != 0) {
@@ -232,6 +240,7 @@ extern "C" int suhmo_batch_create(suhmo_batch_t **out, const suhmo_level_desc_t 
     suhmo_batch *B = new (std::nothrow) suhmo_batch();
     if (!B) { suhmo_set_error("out of memory"); return -2; }
     B->n = n_members; B->device = desc->device; B->has_alpha = desc->alpha != 0.0; B->tile_order = 0;
+    B->beta_per_member = beta_per_member; B->implicit_gap = 0; B->gap = nullptr;
     auto fail = [&](int rc) { (void)suhmo_batch_destroy(B); return rc; };
     for (int k = 0; k < n_members; k++) {
         suhmo_level *L = nullptr;
@@ -276,6 +285,11 @@ extern "C" int suhmo_batch_create(suhmo_batch_t **out, const suhmo_level_desc_t 
     B->phase = all_members(B);
     *out = B;
     return 0;
+}
+extern "C" int suhmo_batch_create(suhmo_batch_t **out, const suhmo_level_desc_t *desc, int n_members)
+{
+    ARG(out && desc);
+    return batch_create(out, desc, n_members, false);
 }
 extern "C" int suhmo_batch_size(const suhmo_batch_t *B) { return B ? B->n : 0; }
 extern "C" suhmo_level_t *suhmo_batch_member(suhmo_batch_t *B, int k)
@@ -369,6 +383,60 @@ int suhmo_batch_step_read(suhmo_batch *B, hipStream_t st, double *a, double *b)
     for (int z = 0; z < B->phase.n; z++) { const int k = B->phase.m[z]; a[k] = B->hslot[2 * k]; b[k] = B->hslot[2 * k + 1]; }
     return 0;
 }
+// ---- SolveForGap_nl of a batch: solve_gap_implicit (suhmo_step.hip) of every member in `sel`, one launch sequence
+// the gap batch with beta = dt diffFactor of every member in its handles.  Created once: the descriptor of gap_level_prepare, aCoef = 1 on
+// depth 0 and MGnewOp's cell averages of every coarse depth (aCoef = 1 there too; they never change, so they are not built again per step)
+static int gap_batch_prepare(suhmo_batch *B, const suhmo_model_params_t *mp, double dt, hipStream_t st)
+{
+    int rc;
+    const bool fresh = !B->gap;
+    if (fresh) {
+        suhmo_level *L0 = B->mem[0];
+        suhmo_level_desc_t d = L0->desc;
+        d.boxes = L0->boxes.data(); d.nbox = (int)(L0->boxes.size() / 4);
+        for (int a = 0; a < 2; a++) for (int b = 0; b < 2; b++) { d.bc.type[a][b] = 1; d.bc.value[a][b] = 0.0; }
+        d.phys.use_NL = 0; d.alpha = 1.0; d.beta = dt * mp[0].diffFactor;
+        suhmo_batch *G = nullptr;
+        if ((rc = batch_create(&G, &d, B->n, true))) return rc;
+        B->gap = G;
+        B->gap_beta.assign(B->n, d.beta);
+        for (suhmo_level *L : G->mem)
+            if ((rc = suhmo_level_set_value(L, 0, SUHMO_F_ACOEF, 1.0, (suhmo_stream_t)st))) return rc;      // aCoeff_GH :1820-1828
+    }
+    suhmo_batch *G = B->gap;
+    for (int k = 0; k < B->n; k++) {                        // a new dt or diffFactor: only beta changes (the tables follow in batch_sync)
+        const double beta = dt * mp[k].diffFactor;
+        if (beta == B->gap_beta[k]) continue;
+        if ((rc = suhmo_level_set_alpha_beta(G->mem[k], 1.0, beta))) return rc;
+        B->gap_beta[k] = beta;
+    }
+    G->tile_order = B->tile_order;
+    if ((rc = batch_enter(G, st)) || !fresh) return rc;
+    int nl = 0;
+    rc = suhmo_batch_build_mg_coefficients(tab(G, 0), G->d_avg, all_members(G), G->mem[0], st, &nl);
+    G->launches += nl;
+    return rc;
+}
+int suhmo_batch_step_solve_gap(suhmo_batch *B, const BatchSel &sel, const suhmo_model_params_t *mp, double dt, const suhmo_solver_params_t *sp, hipStream_t st)
+{
+    int rc, nl = 0;
+    if (sel.n <= 0) return 0;
+    if (sp->bcoeff_otf) { suhmo_set_error("internal: batch: the gap-height solve keeps its coefficients (bcoeff_otf = 0)"); return -4; }
+    if ((rc = gap_batch_prepare(B, mp, dt, st))) return rc;
+    suhmo_batch *G = B->gap;
+    const size_t elems = B->mem[0]->d[0].elems;
+    if (G->mem[0]->d[0].elems != elems) { suhmo_set_error("internal: batch: gap level geometry"); return -4; }
+    if ((rc = suhmo_batch_gap_load(tab(B, 0), tab(G, 0), sel, elems, st))) return rc;                   // initial guess = b :3382-3385, RHS, D on the faces
+    G->launches++;
+    BatchTab tabs[SUHMO_MAXDEPTH];
+    for (int dep = 0; dep < G->ndepth; dep++) tabs[dep] = tab(G, dep);
+    if ((rc = suhmo_batch_average_operator_all(tabs, G->d_avg, sel, G->mem[0], G->ndepth, st, &nl))) return rc;     // coarse D = average of the fine faces
+    G->launches += nl;
+    if ((rc = batch_solve(G, sp, sel, nullptr, nullptr, st))) return rc;
+    if ((rc = suhmo_batch_gap_store(tab(B, 0), tab(G, 0), sel, B->d_mp, elems, st))) return rc;         // (tab(G, 0) after the solve: the canvases have traded)
+    G->launches++;
+    return 0;
+}
 // the step's entry: tables against the handles (the step's fields have just been allocated), mp[n] on the device, everybody in the first phase
 int suhmo_batch_step_begin(suhmo_batch *B, const suhmo_model_params_t *mp, hipStream_t st)
 {
@@ -386,8 +454,11 @@ extern "C" int suhmo_batch_timestep(suhmo_batch_t *B, const suhmo_model_params_t
 {
     SUHMO_TIME("AmrHydro::timeStepFAS");
     ARG(B && mp);
-    for (int k = 0; k < B->n; k++)
-        if (mp[k].use_impl_diff) { suhmo_set_error("batch: use_impl_diff = 1 (member %d): the implicit gap-height solve of a batch is not built", k); return -5; }
+    for (int k = 0; k < B->n && !B->implicit_gap; k++)
+        if (mp[k].use_impl_diff) {
+            suhmo_set_error("batch: use_impl_diff = 1 (member %d): the implicit gap-height solve of a batch is not built (into a step, unless batch option implicit_gap is set to 1)", k);
+            return -5;
+        }
     HIPCHK(hipSetDevice(B->device));
     return suhmo_batch_timestep_run(B, mp, dt, cur_step, picard_iters, vcycles, (hipStream_t)s);
 }
@@ -401,7 +472,8 @@ extern "C" int suhmo_batch_set_option(suhmo_batch_t *B, const char *key, long va
         suhmo_set_error("batch: bottom_solver = %ld is not built (the one-launch RelaxSolver keeps its loop state per level; the bottom of a batched cycle is its numBottom relaxes)", value);
         return -5;
     }
-    if (!strcmp(key, "batch_launches") || !strcmp(key, "batch_readbacks") || !strcmp(key, "batch_member_cycles")) { suhmo_set_error("batch: option %s is read-only", key); return -1; }
+    if (!strcmp(key, "implicit_gap")) { ARG(value == 0 || value == 1); B->implicit_gap = (int)value; return 0; }
+    if (!strcmp(key, "batch_launches") || !strcmp(key, "batch_readbacks") || !strcmp(key, "batch_member_cycles") || !strcmp(key, "batch_gap_member_cycles")) { suhmo_set_error("batch: option %s is read-only", key); return -1; }
     suhmo_set_error("batch: unknown option %s", key);
     return -1;
 }
@@ -410,9 +482,11 @@ extern "C" int suhmo_batch_get_option(const suhmo_batch_t *B, const char *key, l
     ARG(B && key && value);
     if (!strcmp(key, "tile_order")) *value = B->tile_order;
     else if (!strcmp(key, "bottom_solver")) *value = 0;
-    else if (!strcmp(key, "batch_launches")) *value = B->launches;
-    else if (!strcmp(key, "batch_readbacks")) *value = B->readbacks;
+    else if (!strcmp(key, "implicit_gap")) *value = B->implicit_gap;
+    else if (!strcmp(key, "batch_launches")) *value = B->launches + (B->gap ? B->gap->launches : 0);
+    else if (!strcmp(key, "batch_readbacks")) *value = B->readbacks + (B->gap ? B->gap->readbacks : 0);
     else if (!strcmp(key, "batch_member_cycles")) *value = B->member_cycles;
+    else if (!strcmp(key, "batch_gap_member_cycles")) *value = B->gap ? B->gap->member_cycles : 0;
     else { suhmo_set_error("batch: unknown option %s", key); return -1; }
     return 0;
 }

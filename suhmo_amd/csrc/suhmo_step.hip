@@ -167,12 +167,15 @@ __global__ __launch_bounds__(256) void k_melt_b(BatchTab t, BatchSel sel, const 
 
 // run-state setting freeze_icefree_gap (suhmo_hip.h): cells without ice keep their gap height through SolveForGap_nl -- the solved
 // value of such a cell is replaced by the old one before the solution is copied back (valid cells; the ghosts are refilled afterwards)
+__device__ __forceinline__ void d_keep_icefree_cell(const double *mk, const double *bold, double *sol, size_t idx)
+{
+    if (mk[idx] < 0.0) sol[idx] = bold[idx];
+}
 __device__ __forceinline__ void d_keep_icefree(const DV &v, const double *__restrict__ mk, const double *__restrict__ bold, double *__restrict__ sol)
 {
     int i = blockIdx.x * blockDim.x + threadIdx.x, j = blockIdx.y * blockDim.y + threadIdx.y;
     if (i >= v.nx || j >= v.ny) return;
-    int idx = cidx(v, i, j);
-    if (mk[idx] < 0.0) sol[idx] = bold[idx];
+    d_keep_icefree_cell(mk, bold, sol, cidx(v, i, j));
 }
 __global__ __launch_bounds__(256) void k_keep_icefree(DV v, const double *__restrict__ mk, const double *__restrict__ bold, double *__restrict__ sol)
 {
@@ -181,6 +184,56 @@ __global__ __launch_bounds__(256) void k_keep_icefree(DV v, const double *__rest
 __global__ __launch_bounds__(256) void k_keep_icefree_m(const DV *__restrict__ vt, const FP *__restrict__ fh, const FP *__restrict__ fg)
 {
     d_keep_icefree(vt[blockIdx.z], fh[blockIdx.z].f[SUHMO_F_MASK], fh[blockIdx.z].f[SUHMO_F_B], fg[blockIdx.z].f[SUHMO_F_PHI]);
+}
+// SolveForGap_nl of a batch (suhmo_batch.hip): h = the members' tables of depth 0, g = those of their gap handles.  What
+// gap_level_prepare copies canvas by canvas (b -> PHI the initial guess, RES -> RHS, DCX -> BX, DCY -> BY; ghosts included), for every
+// implicit member in one launch; a canvas is an even number of doubles (the pitch is a multiple of 16)
+__global__ __launch_bounds__(256) void k_gap_load_b(BatchTab h, BatchTab g, BatchSel sel, size_t elems2)
+{
+    const int k = batch_member(sel);
+    const FP &s = h.fp[k];
+    const FP d = batch_fp(g, k);
+    const double2 *__restrict__ b = (const double2 *)s.f[SUHMO_F_B], *__restrict__ res = (const double2 *)s.f[SUHMO_F_RES];
+    const double2 *__restrict__ dcx = (const double2 *)s.f[SUHMO_F_DCX], *__restrict__ dcy = (const double2 *)s.f[SUHMO_F_DCY];
+    double2 *__restrict__ phi = (double2 *)d.f[SUHMO_F_PHI], *__restrict__ rhs = (double2 *)d.f[SUHMO_F_RHS];
+    double2 *__restrict__ bx = (double2 *)d.f[SUHMO_F_BX], *__restrict__ by = (double2 *)d.f[SUHMO_F_BY];
+    for (size_t q = (size_t)blockIdx.x * blockDim.x + threadIdx.x; q < elems2; q += (size_t)gridDim.x * blockDim.x) {
+        const double2 v0 = b[q], v1 = res[q], v2 = dcx[q], v3 = dcy[q];
+        phi[q] = v0; rhs[q] = v1; bx[q] = v2; by[q] = v3;
+    }
+}
+// ... and the way back: keep_icefree where the member's freeze_icefree_gap asks for it (valid cells), then the whole canvas into b
+__global__ __launch_bounds__(256) void k_gap_store_b(BatchTab h, BatchTab g, BatchSel sel, const suhmo_model_params_t *__restrict__ mpt, size_t elems)
+{
+    const int k = batch_member(sel);
+    const DV &v = h.dv[k];
+    const double *mk = h.fp[k].f[SUHMO_F_MASK];
+    double *b = h.fp[k].f[SUHMO_F_B], *sol = batch_fp(g, k).f[SUHMO_F_PHI];
+    const bool freeze = mpt[k].freeze_icefree_gap != 0;
+    for (size_t q = (size_t)blockIdx.x * blockDim.x + threadIdx.x; q < elems; q += (size_t)gridDim.x * blockDim.x) {
+        if (freeze) {
+            const int i = (int)(q % v.P) - SUHMO_XOFF, j = (int)(q / v.P) - v.gy;
+            if (i >= 0 && i < v.nx && j >= 0 && j < v.ny) d_keep_icefree_cell(mk, b, sol, q);
+        }
+        b[q] = sol[q];
+    }
+}
+int suhmo_batch_gap_load(const BatchTab &h, const BatchTab &g, const BatchSel &sel, size_t elems, hipStream_t st)
+{
+    if (sel.n <= 0) return 0;
+    if (elems & 1) { suhmo_set_error("internal: batch: a canvas of an odd number of doubles"); return -4; }
+    const unsigned nb = (unsigned)std::min<size_t>((elems / 2 + 255) / 256, 256);
+    hipLaunchKernelGGL(k_gap_load_b, dim3(nb, 1, sel.n), dim3(256), 0, st, h, g, sel, elems / 2);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+int suhmo_batch_gap_store(const BatchTab &h, const BatchTab &g, const BatchSel &sel, const suhmo_model_params_t *mpt, size_t elems, hipStream_t st)
+{
+    if (sel.n <= 0) return 0;
+    const unsigned nb = (unsigned)std::min<size_t>((elems + 255) / 256, 256);
+    hipLaunchKernelGGL(k_gap_store_b, dim3(nb, 1, sel.n), dim3(256), 0, st, h, g, sel, mpt, elems);
+    HIPCHK(hipGetLastError());
+    return 0;
 }
 static int keep_icefree(suhmo_level *L, suhmo_level *G, hipStream_t st)
 {
@@ -496,12 +549,15 @@ static int picard_test(double maxHead, double maxd, int ite_idx, int cur_step, c
 }
 // The skeleton over a level layout Y (OneLevel, Nested, BoxUnions below).  Y has `nlev`, `base` (level 0's handle, the one the head
 // solve's multigrid depths hang off) and `st`; its hooks gap_ghosts(l), chain(l) and melt_final(l) act on level l, the others on every
-// level in the layout's own launch order.
+// level in the layout's own launch order.  What [III] does with the gap height depends on use_impl_diff: explicit_gap_ghosts and
+// implicit_gap_solve decide it from mp of the one model, or per member (the overloads for Batch below).
 // A layout may hold several independent MEMBERS on one grid (`nmem`; the three layouts of one model have 1; a batch: suhmo_batch.hip): the
 // hooks then act on the members of the current phase, mp, the solve's cycle counts and the Picard maxima are arrays over the members, and
 // `select(still)` tells the layout which members the next Picard iteration serves (returns false when none is left: the phases after
 // the loop serve everybody again).  Every member sees the sequence of one model.
 template <class Y> static int mg_coefficients(Y &y) { return suhmo_build_mg_coefficients(y.base, false, y.st); }
+template <class Y> static int explicit_gap_ghosts(Y &y, int l, const suhmo_model_params_t *mp) { return mp->use_impl_diff ? 0 : y.gap_ghosts(l); }
+template <class Y> static int implicit_gap_solve(Y &y, const suhmo_model_params_t *mp, double dt, int cur_step) { return mp->use_impl_diff ? y.solve_gap(mp, dt, cur_step) : 0; }
 template <class Y>
 static int timestep_fas(Y &y, const suhmo_model_params_t *mp, double dt, int cur_step, int *picard_iters, int *vcycles)
 {
@@ -536,9 +592,9 @@ static int timestep_fas(Y &y, const suhmo_model_params_t *mp, double dt, int cur
     // [III] level by level: the coarse gap height is already updated when the fine ghost cells are filled
     for (int l = 0; l < y.nlev; l++) {
         if ((rc = y.chain(l)) || (rc = y.melt_final(l, mp, dt))) return rc;
-        if (!mp->use_impl_diff && (rc = y.gap_ghosts(l))) return rc;             // (implicit: b stays, RES = b + dt RHS)
+        if ((rc = explicit_gap_ghosts(y, l, mp))) return rc;                      // (implicit: b stays, RES = b + dt RHS)
     }
-    if (mp->use_impl_diff && (rc = y.solve_gap(mp, dt, cur_step))) return rc;    // SolveForGap_nl :3425-3455, then the ghosts of b
+    if ((rc = implicit_gap_solve(y, mp, dt, cur_step))) return rc;                // SolveForGap_nl :3425-3455, then the ghosts of b
     for (int k = 0; k < n; k++) { if (picard_iters) picard_iters[k] = ite[k]; if (vcycles) vcycles[k] = nv[k]; }
     return 0;
 }
@@ -600,18 +656,22 @@ extern "C" int suhmo_level_timestep(suhmo_level_t *L, const suhmo_model_params_t
 // suhmo_grad_re + Qw, the Picard maxima of all members come back in one read-back.  The diffusion terms run over the members whose
 // diffFactor is not 0, as level_melt decides for one model.
 static bool has_diffusion(const suhmo_model_params_t &m) { return m.diffFactor != 0.0; }
+static bool is_implicit(const suhmo_model_params_t &m) { return m.use_impl_diff != 0; }
+static bool is_explicit(const suhmo_model_params_t &m) { return m.use_impl_diff == 0; }
 struct Batch {
     suhmo_batch *B;
     hipStream_t st;
     int nlev = 1;
     int nmem;
     bool select(const char *still) { return suhmo_batch_step_select(B, still); }
-    int gap_ghosts(int)
+    int gap_ghosts(const BatchSel &sel)
     {
+        if (sel.n <= 0) return 0;
         const BatchStep p = suhmo_batch_step(B);
         suhmo_batch_count(B, 1);
-        return suhmo_batch_copy_ghosts(p.t, p.sel, *p.v, SUHMO_F_B, st);
+        return suhmo_batch_copy_ghosts(p.t, sel, *p.v, SUHMO_F_B, st);
     }
+    int gap_ghosts(int) { return gap_ghosts(suhmo_batch_step(B).sel); }
     int lag_head()
     {
         const BatchStep p = suhmo_batch_step(B);
@@ -669,9 +729,23 @@ struct Batch {
         return suhmo_batch_step_read(B, st, maxh, maxd);
     }
     int melt_final(int, const suhmo_model_params_t *mp, double dt) { return melt(mp, dt, 1, false); }
-    int solve_gap(const suhmo_model_params_t *, double, int) { suhmo_set_error("batch: the implicit gap-height solve (use_impl_diff) is not built"); return -5; }
+    // SolveForGap_nl of the members `sel` (solve_gap_implicit of each, one launch sequence), then the ghosts of their b
+    int solve_gap(const BatchSel &sel, const suhmo_model_params_t *mp, double dt, int cur_step)
+    {
+        suhmo_solver_params_t sp;
+        gap_solver_params(sp, cur_step);
+        int rc = suhmo_batch_step_solve_gap(B, sel, mp, dt, &sp, st);
+        return rc ? rc : gap_ghosts(sel);
+    }
 };
 static int mg_coefficients(Batch &y) { return suhmo_batch_step_mg_coefficients(y.B, y.st); }
+// [III] per member: forward Euler members get the ghosts of their new b, the others go through the gap batch
+static int explicit_gap_ghosts(Batch &y, int, const suhmo_model_params_t *mp) { return y.gap_ghosts(suhmo_batch_step_subset(y.B, mp, is_explicit)); }
+static int implicit_gap_solve(Batch &y, const suhmo_model_params_t *mp, double dt, int cur_step)
+{
+    const BatchSel sel = suhmo_batch_step_subset(y.B, mp, is_implicit);
+    return sel.n > 0 ? y.solve_gap(sel, mp, dt, cur_step) : 0;
+}
 int suhmo_batch_timestep_run(suhmo_batch *B, const suhmo_model_params_t *mp, double dt, int cur_step, int *picard_iters, int *vcycles, hipStream_t st)
 {
     int rc = 0;

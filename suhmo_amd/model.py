@@ -123,16 +123,20 @@ class _MemberModel(HipModel):
 class HipBatchModel:
     """An ensemble of n models on one grid stepped together (suhmo_batch_timestep, suhmo_amd/csrc/suhmo_batch.hip): shared grid, BC types,
     dt and step number; per member every field, the BC values, the physics constants and the model parameters.  models: one dict per member
-    (as HipModel's); phys / bc: one for all or a list per member.  Every member's results are those of a HipModel run alone, bit for bit."""
+    (as HipModel's); phys / bc: one for all or a list per member.  Every member's results are those of a HipModel run alone, bit for bit.
+    implicit_gap=True (batch option implicit_gap): members with use_impl_diff=1 are stepped too, their gap-height solves as one launch
+    sequence; explicit and implicit members may share a batch.  Off, such a member is refused."""
 
     FIELDS = HipModel.FIELDS
 
-    def __init__(self, nx, ny, dx, dy, bc, phys, models, max_box=64, device=0):
+    def __init__(self, nx, ny, dx, dy, bc, phys, models, max_box=64, device=0, implicit_gap=False):
         n = len(models)
         bcs = list(bc) if isinstance(bc, (list, tuple)) else [bc] * n
         phs = list(phys) if isinstance(phys, (list, tuple)) else [phys] * n
         self.batch = lv.HipBatch(n, nx, ny, dx, dy, bcs[0], phs[0], alpha=0.0, beta=-1.0, max_box=max_box, device=device)
         self.n, self.nx, self.ny, self.dx, self.dy = n, nx, ny, dx, dy
+        if implicit_gap:
+            self.batch.set_option("implicit_gap", 1)
         for k in range(n):
             self.batch.set_bc(k, bcs[k])
             self.batch.set_phys(k, phs[k])
@@ -177,6 +181,9 @@ class HipBatchModel:
 
     def get_option(self, key):
         return self.batch.get_option(key)
+
+    def set_option(self, key, value):
+        self.batch.set_option(key, value)
 
     def close(self):
         self.batch.close()
