@@ -111,7 +111,8 @@ int suhmo_level_num_depths(const suhmo_level_t *L);
  * fused_nt (64, 256), fused_restrict, fas_rhs_in_relax, strips_rhs_local, bcoef_fused, graph_max_cells, poll_readback, overlap_halo,
  * agg_min_cells, fas_rhs_fused, resid_in_relax (1: the residual the solve loops evaluate after every V-cycle is left behind by the cycle's
  * last launch where the streaming kernel runs depth 0; 0: always a pass of its own).  Read-only counters: overlapped_launches, agg_gathers,
- * rhs_in_streaming_launches, rhs_in_tile_launches, residual_in_relax_launches.
+ * rhs_in_streaming_launches, rhs_in_tile_launches, residual_in_relax_launches, vcycle_graph_replays (V-cycles that ran
+ * as a launch of a captured graph).
  * Not a kernel-selection knob (it changes the bits): bottom_solver (default 0: the cycle's bottom is its numBottom relaxes; 1: followed by
  * Chombo's RelaxSolver as the reference configures it, src/AmrHydro.cpp:623,628,726,733-735 -- up to 40 rounds of relax(2), ended by an l2
  * residual below 1e-6 x its first value or reduced by less than 10 %).  It reaches the level's agglomerated copy and its gap-height operator;

@@ -64,9 +64,15 @@ bool stage(std::vector<HF> fabs, DF *out)
     }
     return true;
 }
-void unstage(const DF &d, double *h) { (void)hipMemcpy(h, d.d, (size_t)d.n0 * d.n1 * d.nc * 8, hipMemcpyDeviceToHost); }
+// the copy back is the call's synchronisation point: a kernel that faulted reports there, and the caller's fab stays as it was
+#define UNSTAGE(df, h) B2CHK(hipMemcpy(h, (df).d, (size_t)(df).n0 * (df).n1 * (df).nc * 8, hipMemcpyDeviceToHost))
 inline dim3 grid(const BX &b) { return dim3((b.n0 + 63) / 64, (b.n1 + 3) / 4); }
+// Chombo passes empty boxes (hi < lo) for boundary boxes that do not exist: a Fortran loop over one runs zero times, a grid
+// with a zero dimension is refused by the runtime -- every symbol returns before it stages anything
+inline bool empty(const BX &b) { return b.n0 <= 0 || b.n1 <= 0; }
 #define BLK dim3(64, 4)
+// a launch the runtime refuses reaches the caller through the handler (and is not left pending for somebody else's hipGetLastError)
+#define LAUNCH(k, b, ...) do { hipLaunchKernelGGL(k, grid(b), BLK, 0, 0, __VA_ARGS__); B2CHK(hipGetLastError()); } while (0)
 #define CELL(b) int i = b.lo0 + blockIdx.x * blockDim.x + threadIdx.x, j = b.lo1 + blockIdx.y * blockDim.y + threadIdx.y; \
                 if (i >= b.lo0 + b.n0 || j >= b.lo1 + b.n1) return
 
@@ -256,12 +262,13 @@ void gsrbhelmholtzvcnl2d_(SUHMO_CHF_FRA(phi), SUHMO_CHF_CONST_FRA(rhs), SUHMO_CH
                           SUHMO_CHF_CONST_FRA(nlDfunc), SUHMO_CHF_CONST_FRA(lambda), SUHMO_CHF_CONST_INT(redBlack))
 {
     if (!ncomp_ok(*nphicomp, *nrhscomp) || !ncomp_ok(*nphicomp, *nbCoef0comp) || !ncomp_ok(*nphicomp, *nbCoef1comp)) return;  // :87-106
+    BX r = HBOX(region);
+    if (empty(r)) return;
     DF d[8];
     if (!stage({HFAB(phi), HFAB(rhs), HFAB(aCoef), HFAB(bCoef0), HFAB(bCoef1), HFAB(nlfunc), HFAB(nlDfunc), HFAB(lambda)}, d)) return;
-    BX r = HBOX(region);
-    hipLaunchKernelGGL(kb_gsrb, grid(r), BLK, 0, 0, d[0], d[1], r, 1.0 / (dx[0] * dx[0]), 1.0 / (dx[1] * dx[1]), *alpha, d[2], *beta,
+    LAUNCH(kb_gsrb, r, d[0], d[1], r, 1.0 / (dx[0] * dx[0]), 1.0 / (dx[1] * dx[1]), *alpha, d[2], *beta,
                        d[3], d[4], d[5], d[6], d[7], *redBlack);
-    unstage(d[0], phi);
+    UNSTAGE(d[0], phi);
 }
 
 void vcnlcomputeop2d_(SUHMO_CHF_FRA(lofphi), SUHMO_CHF_CONST_FRA(phi), SUHMO_CHF_CONST_REAL(alpha), SUHMO_CHF_CONST_FRA(aCoef),
@@ -269,12 +276,13 @@ void vcnlcomputeop2d_(SUHMO_CHF_FRA(lofphi), SUHMO_CHF_CONST_FRA(phi), SUHMO_CHF
                       SUHMO_CHF_CONST_FRA(nlfunc), SUHMO_CHF_BOX(region), SUHMO_CHF_CONST_REALVECT(dx))
 {
     if (!ncomp_ok(*nphicomp, *nlofphicomp)) return;
+    BX r = HBOX(region);
+    if (empty(r)) return;
     DF d[6];
     if (!stage({HFAB(lofphi), HFAB(phi), HFAB(aCoef), HFAB(bCoef0), HFAB(bCoef1), HFAB(nlfunc)}, d)) return;
-    BX r = HBOX(region);
-    hipLaunchKernelGGL(kb_op, grid(r), BLK, 0, 0, d[0], d[1], d[1], 0, *alpha, d[2], *beta, d[3], d[4], d[5], r,
+    LAUNCH(kb_op, r, d[0], d[1], d[1], 0, *alpha, d[2], *beta, d[3], d[4], d[5], r,
                        1.0 / (dx[0] * dx[0]), 1.0 / (dx[1] * dx[1]));
-    unstage(d[0], lofphi);
+    UNSTAGE(d[0], lofphi);
 }
 
 void vcnlcomputeres2d_(SUHMO_CHF_FRA(res), SUHMO_CHF_CONST_FRA(phi), SUHMO_CHF_CONST_FRA(rhs), SUHMO_CHF_CONST_REAL(alpha),
@@ -282,24 +290,26 @@ void vcnlcomputeres2d_(SUHMO_CHF_FRA(res), SUHMO_CHF_CONST_FRA(phi), SUHMO_CHF_C
                        SUHMO_CHF_CONST_FRA(bCoef1), SUHMO_CHF_CONST_FRA(nlfunc), SUHMO_CHF_BOX(region), SUHMO_CHF_CONST_REALVECT(dx))
 {
     if (!ncomp_ok(*nphicomp, *nrescomp)) return;
+    BX r = HBOX(region);
+    if (empty(r)) return;
     DF d[7];
     if (!stage({HFAB(res), HFAB(phi), HFAB(rhs), HFAB(aCoef), HFAB(bCoef0), HFAB(bCoef1), HFAB(nlfunc)}, d)) return;
-    BX r = HBOX(region);
-    hipLaunchKernelGGL(kb_op, grid(r), BLK, 0, 0, d[0], d[1], d[2], 1, *alpha, d[3], *beta, d[4], d[5], d[6], r,
+    LAUNCH(kb_op, r, d[0], d[1], d[2], 1, *alpha, d[3], *beta, d[4], d[5], d[6], r,
                        1.0 / (dx[0] * dx[0]), 1.0 / (dx[1] * dx[1]));
-    unstage(d[0], res);
+    UNSTAGE(d[0], res);
 }
 
 static void restrict_impl(double *phiCoarse, const int *l0, const int *l1, const int *h0, const int *h1, const int *nc,
                           const double *phiFine, const int *fl0, const int *fl1, const int *fh0, const int *fh1, const int *fnc,
                           const int *r0, const int *r1, const int *r2, const int *r3)
 {
+    BX rf{*r0, *r1, *r2 - *r0 + 1, *r3 - *r1 + 1};
+    if (empty(rf)) return;
     DF d[2];
     if (!stage({HF{phiCoarse, *l0, *l1, *h0, *h1, *nc}, HF{phiFine, *fl0, *fl1, *fh0, *fh1, *fnc}}, d)) return;
-    BX rf{*r0, *r1, *r2 - *r0 + 1, *r3 - *r1 + 1};
     BX rc{*r0 / 2, *r1 / 2, *r2 / 2 - *r0 / 2 + 1, *r3 / 2 - *r1 / 2 + 1};
-    hipLaunchKernelGGL(kb_restrict, grid(rc), BLK, 0, 0, d[0], d[1], rc, rf);
-    unstage(d[0], phiCoarse);
+    LAUNCH(kb_restrict, rc, d[0], d[1], rc, rf);
+    UNSTAGE(d[0], phiCoarse);
 }
 void restrictvcnl_(SUHMO_CHF_FRA(phiCoarse), SUHMO_CHF_CONST_FRA(phiFine), SUHMO_CHF_BOX(region), SUHMO_CHF_CONST_REAL(dx))
 {
@@ -318,142 +328,157 @@ void restrictresvcnl2d_(SUHMO_CHF_FRA(res), SUHMO_CHF_CONST_FRA(phi), SUHMO_CHF_
                         SUHMO_CHF_CONST_FRA(aCoef), SUHMO_CHF_CONST_REAL(beta), SUHMO_CHF_CONST_FRA(bCoef0),
                         SUHMO_CHF_CONST_FRA(bCoef1), SUHMO_CHF_CONST_FRA(nlfunc), SUHMO_CHF_BOX(region), SUHMO_CHF_CONST_REALVECT(dx))
 {
+    BX rf = HBOX(region);
+    if (empty(rf)) return;
     DF d[7];
     if (!stage({HFAB(res), HFAB(phi), HFAB(rhs), HFAB(aCoef), HFAB(bCoef0), HFAB(bCoef1), HFAB(nlfunc)}, d)) return;
-    BX rf = HBOX(region);
     BX rc{rf.lo0 / 2, rf.lo1 / 2, (rf.lo0 + rf.n0 - 1) / 2 - rf.lo0 / 2 + 1, (rf.lo1 + rf.n1 - 1) / 2 - rf.lo1 / 2 + 1};
-    hipLaunchKernelGGL(kb_restrictres, grid(rc), BLK, 0, 0, d[0], d[1], d[2], *alpha, d[3], *beta, d[4], d[5], d[6], rc, rf,
+    LAUNCH(kb_restrictres, rc, d[0], d[1], d[2], *alpha, d[3], *beta, d[4], d[5], d[6], rc, rf,
                        1.0 / (dx[0] * dx[0]), 1.0 / (dx[1] * dx[1]));
-    unstage(d[0], res);
+    UNSTAGE(d[0], res);
 }
 
 void sumfacesnl_(SUHMO_CHF_FRA(lhs), SUHMO_CHF_CONST_REAL(beta), SUHMO_CHF_CONST_FRA(bCoefs), SUHMO_CHF_BOX(box),
                  SUHMO_CHF_CONST_INT(dir), SUHMO_CHF_CONST_REAL(scale))
 {
+    BX r = HBOX(box);
+    if (empty(r)) return;
     DF d[2];
     if (!stage({HFAB(lhs), HFAB(bCoefs)}, d)) return;
-    BX r = HBOX(box);
-    hipLaunchKernelGGL(kb_sumfaces, grid(r), BLK, 0, 0, d[0], *beta, d[1], r, *dir, *scale);
-    unstage(d[0], lhs);
+    LAUNCH(kb_sumfaces, r, d[0], *beta, d[1], r, *dir, *scale);
+    UNSTAGE(d[0], lhs);
 }
 
 void prolongnl_(SUHMO_CHF_FRA(phi), SUHMO_CHF_CONST_FRA(coarse), SUHMO_CHF_BOX(region), SUHMO_CHF_CONST_INT(m))
 {
+    BX r = HBOX(region);
+    if (empty(r)) return;
     DF d[2];
     if (!stage({HFAB(phi), HFAB(coarse)}, d)) return;
-    BX r = HBOX(region);
-    hipLaunchKernelGGL(kb_prolong, grid(r), BLK, 0, 0, d[0], d[1], r, *m);
-    unstage(d[0], phi);
+    LAUNCH(kb_prolong, r, d[0], d[1], r, *m);
+    UNSTAGE(d[0], phi);
 }
 void prolong_2_nl_(SUHMO_CHF_FRA(phi), SUHMO_CHF_CONST_FRA(coarse), SUHMO_CHF_BOX(region), SUHMO_CHF_CONST_INT(m))
 {
+    BX r = HBOX(region);
+    if (empty(r)) return;
     DF d[2];
     if (!stage({HFAB(phi), HFAB(coarse)}, d)) return;
-    BX r = HBOX(region);
-    hipLaunchKernelGGL(kb_prolong2, grid(r), BLK, 0, 0, d[0], d[1], r, *m);
-    unstage(d[0], phi);
+    LAUNCH(kb_prolong2, r, d[0], d[1], r, *m);
+    UNSTAGE(d[0], phi);
 }
 void newgetfluxnl_(SUHMO_CHF_FRA(flux), SUHMO_CHF_CONST_FRA(phi), SUHMO_CHF_BOX(box), SUHMO_CHF_CONST_REAL(beta_dx), SUHMO_CHF_CONST_INT(a_idir))
 {
+    BX r = HBOX(box);
+    if (empty(r)) return;
     DF d[2];
     if (!stage({HFAB(flux), HFAB(phi)}, d)) return;
-    BX r = HBOX(box);
-    hipLaunchKernelGGL(kb_getflux, grid(r), BLK, 0, 0, d[0], d[1], r, *beta_dx, *a_idir);
-    unstage(d[0], flux);
+    LAUNCH(kb_getflux, r, d[0], d[1], r, *beta_dx, *a_idir);
+    UNSTAGE(d[0], flux);
 }
 
 void computenonlinearterms_(SUHMO_CHF_CONST_FRA(phi), SUHMO_CHF_CONST_FRA(aB), SUHMO_CHF_CONST_FRA(IM), SUHMO_CHF_CONST_FRA(aPi),
                             SUHMO_CHF_CONST_FRA(aZb), SUHMO_CHF_BOX(region), SUHMO_CHF_FRA(nlfunc), SUHMO_CHF_FRA(dnlfunc),
                             SUHMO_CHF_CONST_REAL(Aparam), SUHMO_CHF_CONST_REAL(brparam), SUHMO_CHF_CONST_REAL(brparamMax))
 {
+    BX r = HBOX(region);
+    if (empty(r)) return;
     DF d[7];
     if (!stage({HFAB(phi), HFAB(aB), HFAB(IM), HFAB(aPi), HFAB(aZb), HFAB(nlfunc), HFAB(dnlfunc)}, d)) return;
-    BX r = HBOX(region);
-    hipLaunchKernelGGL(kb_nl, grid(r), BLK, 0, 0, d[0], d[1], d[2], d[3], d[4], r, d[5], d[6], *Aparam, *brparam, *brparamMax);
-    unstage(d[5], nlfunc); unstage(d[6], dnlfunc);
+    LAUNCH(kb_nl, r, d[0], d[1], d[2], d[3], d[4], r, d[5], d[6], *Aparam, *brparam, *brparamMax);
+    UNSTAGE(d[5], nlfunc); UNSTAGE(d[6], dnlfunc);
 }
 void computeqw_(SUHMO_CHF_CONST_FRA(aB), SUHMO_CHF_CONST_FRA(aRe), SUHMO_CHF_CONST_FRA(agradH), SUHMO_CHF_BOX(region),
                 SUHMO_CHF_FRA(Qw), SUHMO_CHF_CONST_REAL(omegaparam), SUHMO_CHF_CONST_REAL(nuparam))
 {
+    BX r = HBOX(region);
+    if (empty(r)) return;
     DF d[4];
     if (!stage({HFAB(aB), HFAB(aRe), HFAB(agradH), HFAB(Qw)}, d)) return;
-    BX r = HBOX(region);
-    hipLaunchKernelGGL(kb_qw, grid(r), BLK, 0, 0, d[0], d[1], d[2], r, d[3], *omegaparam, *nuparam);
-    unstage(d[3], Qw);
+    LAUNCH(kb_qw, r, d[0], d[1], d[2], r, d[3], *omegaparam, *nuparam);
+    UNSTAGE(d[3], Qw);
 }
 void computescaprod_(SUHMO_CHF_CONST_FRA(vara), SUHMO_CHF_CONST_FRA(var1b), SUHMO_CHF_CONST_FRA(var2b), SUHMO_CHF_BOX(region),
                      SUHMO_CHF_FRA(prod1), SUHMO_CHF_FRA(prod2))
 {
+    BX r = HBOX(region);
+    if (empty(r)) return;
     DF d[5];
     if (!stage({HFAB(vara), HFAB(var1b), HFAB(var2b), HFAB(prod1), HFAB(prod2)}, d)) return;
-    BX r = HBOX(region);
-    hipLaunchKernelGGL(kb_scaprod, grid(r), BLK, 0, 0, d[0], d[1], d[2], r, d[3], d[4]);
-    unstage(d[3], prod1); unstage(d[4], prod2);
+    LAUNCH(kb_scaprod, r, d[0], d[1], d[2], r, d[3], d[4]);
+    UNSTAGE(d[3], prod1); UNSTAGE(d[4], prod2);
 }
 void computedcoeff_(SUHMO_CHF_BOX(region), SUHMO_CHF_FRA(Dcoeff), SUHMO_CHF_CONST_REALVECT(dx), SUHMO_CHF_CONST_REAL(rho),
                     SUHMO_CHF_FRA(MRec), SUHMO_CHF_FRA(Bec), SUHMO_CHF_FRA(IMec), SUHMO_CHF_INT(cutOffB))
 {
     (void)dx;
+    BX r = HBOX(region);
+    if (empty(r)) return;
     DF d[4];
     if (!stage({HFAB(Dcoeff), HFAB(MRec), HFAB(Bec), HFAB(IMec)}, d)) return;
-    BX r = HBOX(region);
-    hipLaunchKernelGGL(kb_dcoeff, grid(r), BLK, 0, 0, r, d[0], *rho, d[1], d[2], d[3], *cutOffB);
-    unstage(d[0], Dcoeff);
+    LAUNCH(kb_dcoeff, r, r, d[0], *rho, d[1], d[2], d[3], *cutOffB);
+    UNSTAGE(d[0], Dcoeff);
 }
 void computedifterm2d_(SUHMO_CHF_FRA(phi), SUHMO_CHF_BOX(region), SUHMO_CHF_CONST_REALVECT(dx), SUHMO_CHF_FRA(Dterm),
                        SUHMO_CHF_CONST_FRA(Dcoef0), SUHMO_CHF_CONST_FRA(Dcoef1))
 {
+    BX r = HBOX(region);
+    if (empty(r)) return;
     DF d[4];
     if (!stage({HFAB(phi), HFAB(Dterm), HFAB(Dcoef0), HFAB(Dcoef1)}, d)) return;
-    BX r = HBOX(region);
-    hipLaunchKernelGGL(kb_difterm, grid(r), BLK, 0, 0, d[0], r, 1.0 / (dx[0] * dx[0]), 1.0 / (dx[1] * dx[1]), d[1], d[2], d[3]);
-    unstage(d[1], Dterm);
+    LAUNCH(kb_difterm, r, d[0], r, 1.0 / (dx[0] * dx[0]), 1.0 / (dx[1] * dx[1]), d[1], d[2], d[3]);
+    UNSTAGE(d[1], Dterm);
 }
 void compute_timevaryingrecharge_(SUHMO_CHF_CONST_FRA(aZs), SUHMO_CHF_BOX(region), SUHMO_CHF_FRA(Recharge),
                                   SUHMO_CHF_CONST_REAL(TK), SUHMO_CHF_CONST_REAL(BackgroundInput))
 {
+    BX r = HBOX(region);
+    if (empty(r)) return;
     DF d[2];
     if (!stage({HFAB(aZs), HFAB(Recharge)}, d)) return;
-    BX r = HBOX(region);
-    hipLaunchKernelGGL(kb_tvrecharge, grid(r), BLK, 0, 0, d[0], r, d[1], *TK, *BackgroundInput);
-    unstage(d[1], Recharge);
+    LAUNCH(kb_tvrecharge, r, d[0], r, d[1], *TK, *BackgroundInput);
+    UNSTAGE(d[1], Recharge);
 }
 void computere_(SUHMO_CHF_CONST_FRA(aB), SUHMO_CHF_CONST_FRA(agradH), SUHMO_CHF_BOX(region), SUHMO_CHF_FRA(Re),
                 SUHMO_CHF_CONST_REAL(omegaparam), SUHMO_CHF_CONST_REAL(nuparam))
 {
+    BX r = HBOX(region);
+    if (empty(r)) return;
     DF d[3];
     if (!stage({HFAB(aB), HFAB(agradH), HFAB(Re)}, d)) return;
-    BX r = HBOX(region);
-    hipLaunchKernelGGL(kb_re, grid(r), BLK, 0, 0, d[0], d[1], r, d[2], *omegaparam, *nuparam);
-    unstage(d[2], Re);
+    LAUNCH(kb_re, r, d[0], d[1], r, d[2], *omegaparam, *nuparam);
+    UNSTAGE(d[2], Re);
 }
 void computebcoeff_(SUHMO_CHF_CONST_FRA(aB), SUHMO_CHF_CONST_FRA(aRe), SUHMO_CHF_BOX(region), SUHMO_CHF_FRA(Bcoeff),
                     SUHMO_CHF_CONST_FRA(IMec), SUHMO_CHF_CONST_REAL(omegaparam), SUHMO_CHF_CONST_REAL(nuparam), SUHMO_CHF_INT(cutOffB))
 {
+    BX r = HBOX(region);
+    if (empty(r)) return;
     DF d[4];
     if (!stage({HFAB(aB), HFAB(aRe), HFAB(Bcoeff), HFAB(IMec)}, d)) return;
-    BX r = HBOX(region);
-    hipLaunchKernelGGL(kb_bcoeff, grid(r), BLK, 0, 0, d[0], d[1], r, d[2], d[3], *omegaparam, *nuparam, *cutOffB);
-    unstage(d[2], Bcoeff);
+    LAUNCH(kb_bcoeff, r, d[0], d[1], r, d[2], d[3], *omegaparam, *nuparam, *cutOffB);
+    UNSTAGE(d[2], Bcoeff);
 }
 void newmacgrad_(SUHMO_CHF_FRA1(edgeGrad), SUHMO_CHF_FRA1(mask), SUHMO_CHF_FRA1(phi), SUHMO_CHF_BOX(edgeGrid),
                  SUHMO_CHF_CONST_REALVECT(dx), SUHMO_CHF_INT(dir), SUHMO_CHF_INT(hasMask), SUHMO_CHF_INT(edgeDir))
 {
     if (*dir != *edgeDir) { g_handler("newmacgrad_: only the normal-derivative branch (dir == edgeDir) is on the hot path"); return; }
+    BX r = HBOX(edgeGrid);
+    if (empty(r)) return;
     DF d[3];
     if (!stage({HFAB1(edgeGrad), HFAB1(mask), HFAB1(phi)}, d)) return;
-    BX r = HBOX(edgeGrid);
-    hipLaunchKernelGGL(kb_macgrad, grid(r), BLK, 0, 0, d[0], d[1], d[2], r, 1.0 / dx[*dir], *dir, *hasMask);
-    unstage(d[0], edgeGrad);
+    LAUNCH(kb_macgrad, r, d[0], d[1], d[2], r, 1.0 / dx[*dir], *dir, *hasMask);
+    UNSTAGE(d[0], edgeGrad);
 }
 static void bc_impl(double *phi, const int *l0, const int *l1, const int *h0, const int *h1, const int *nc, const int *b0,
                     const int *b1, const int *b2, const int *b3, int dir, int hiLo, int mode)
 {
+    BX r{*b0, *b1, *b2 - *b0 + 1, *b3 - *b1 + 1};
+    if (empty(r)) return;
     DF d[1];
     if (!stage({HF{phi, *l0, *l1, *h0, *h1, *nc}}, d)) return;
-    BX r{*b0, *b1, *b2 - *b0 + 1, *b3 - *b1 + 1};
-    hipLaunchKernelGGL(kb_bcfill, grid(r), BLK, 0, 0, d[0], r, dir, hiLo, mode);
-    unstage(d[0], phi);
+    LAUNCH(kb_bcfill, r, d[0], r, dir, hiLo, mode);
+    UNSTAGE(d[0], phi);
 }
 void simpleextrapbc_(SUHMO_CHF_FRA(phi), SUHMO_CHF_BOX(bcbox), SUHMO_CHF_INT(dir), SUHMO_CHF_INT(hiLo))
 { bc_impl(phi, iphilo0, iphilo1, iphihi0, iphihi1, nphicomp, ibcboxlo0, ibcboxlo1, ibcboxhi0, ibcboxhi1, *dir, *hiLo, 0); }
@@ -463,11 +488,12 @@ void nullbc_(SUHMO_CHF_FRA(phi), SUHMO_CHF_BOX(bcbox), SUHMO_CHF_INT(dir), SUHMO
 { bc_impl(phi, iphilo0, iphilo1, iphihi0, iphihi1, nphicomp, ibcboxlo0, ibcboxlo1, ibcboxhi0, ibcboxhi1, *dir, *hiLo, 2); }
 void divergence_(SUHMO_CHF_CONST_FRA(uEdge), SUHMO_CHF_FRA(div), SUHMO_CHF_BOX(gridInt), SUHMO_CHF_CONST_REAL(dx), SUHMO_CHF_INT(idir))
 {
+    BX r = HBOX(gridInt);
+    if (empty(r)) return;
     DF d[2];
     if (!stage({HFAB(uEdge), HFAB(div)}, d)) return;
-    BX r = HBOX(gridInt);
-    hipLaunchKernelGGL(kb_div, grid(r), BLK, 0, 0, d[0], d[1], r, 1.0 / *dx, *idir);
-    unstage(d[1], div);
+    LAUNCH(kb_div, r, d[0], d[1], r, 1.0 / *dx, *idir);
+    UNSTAGE(d[1], div);
 }
 
 } // extern "C"

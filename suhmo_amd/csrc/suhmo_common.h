@@ -161,6 +161,7 @@ struct suhmo_level {
     int (*ex_end)(void *user, suhmo_level *L, suhmo_stream_t s);   // travel as ONE message group (native transport)
     long graph_max_cells;        // V-cycles of levels up to this size are replayed as HIP graphs (env SUHMO_GRAPH_MAX_CELLS, 0 = off)
     std::vector<VGraph> vgraphs; int vgraph_seen[4]; hipStream_t gstream;
+    long vgraph_replays;         // V-cycles that ran as a launch of a captured graph (read-only option vcycle_graph_replays)
     suhmo_level *gap; double gap_dt;   // implicit gap-height operator of the time step (suhmo_step.hip), owned
     void *rccl;                 // native transport state (suhmo_rccl.hip), owned by the level
     int faces_deferred;         // rank strips: UpdateOperator left the halo rows of the depth-0 faces to the message that carries the coarse depths' (suhmo_average_operator_all)

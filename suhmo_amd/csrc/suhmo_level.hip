@@ -176,7 +176,7 @@ int suhmo_level_create_(suhmo_level_t **out, const suhmo_level_desc_t *desc, boo
     L->frhs_stream = L->frhs_tile = 0;
     L->resout_np = 0;
     L->resout_req = L->resout_armed = L->resout_done = 0; L->resout_rhs = nullptr; L->resout_count = 0; L->resid_in_relax = 1;
-    L->graph_max_cells = 1500000; L->gstream = nullptr; memset(L->vgraph_seen, 0, sizeof(L->vgraph_seen));
+    L->graph_max_cells = 1500000; L->gstream = nullptr; L->vgraph_replays = 0; memset(L->vgraph_seen, 0, sizeof(L->vgraph_seen));
     L->fused_min_cells = 1000000;
     L->skip_mask = 1; L->poll_readback = 1;
     L->bottom_solver = 0; L->bottom_one_launch_max_cells = 16384;    // (every bottom the one-launch kernel's LDS holds: up to 128 x 128)
@@ -386,6 +386,7 @@ extern "C" int suhmo_level_get_option(const suhmo_level_t *L, const char *key, l
     if (!strcmp(key, "rhs_in_streaming_launches")) { *value = L->frhs_stream; return 0; }   // read-only counters (fas_rhs_in_relax)
     if (!strcmp(key, "rhs_in_tile_launches")) { *value = L->frhs_tile; return 0; }
     if (!strcmp(key, "residual_in_relax_launches")) { *value = L->resout_count; return 0; }
+    if (!strcmp(key, "vcycle_graph_replays")) { *value = L->vgraph_replays; return 0; }   // read-only counter (graph_max_cells)
     if (!strcmp(key, "bottom_solver")) { *value = L->bottom_solver; return 0; }
     if (!strcmp(key, "bottom_one_launch_max_cells")) { *value = L->bottom_one_launch_max_cells; return 0; }
     if (!strcmp(key, "bottom_solver_iterations")) { *value = suhmo_bottom_counter(L, 0); return 0; }    // read-only counters (bottom_solver)

@@ -181,6 +181,15 @@ class HipLevel:
         check(capi.lib().suhmo_level_get_option(self.h, key.encode(), C.byref(v)))
         return v.value
 
+    def set_alpha_beta(self, alpha, beta):
+        """setAlphaAndBeta of the operator: every multigrid depth takes the new values"""
+        check(capi.lib().suhmo_level_set_alpha_beta(self.h, float(alpha), float(beta)))
+
+    def set_bc(self, bc):
+        """setBC of the operator: other types and values on every depth (the periodicity of the domain cannot change)"""
+        b = _bc(bc)
+        check(capi.lib().suhmo_level_set_bc(self.h, C.byref(b)))
+
     def rccl_exchanges(self):
         """halo message groups this strip has sent so far (native transport), or the calls of the Python exchanger"""
         n = capi.lib().suhmo_level_rccl_exchanges(self.h)
