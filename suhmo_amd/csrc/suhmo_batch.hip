@@ -47,6 +47,7 @@ constexpr int SLOT_FLAG = 2 * SUHMO_BATCH_MAX;             // pinned slot: two v
 
 static const DV &view(const suhmo_batch *B, int dep) { return B->mem[0]->d[dep].v; }
 static BatchTab tab(const suhmo_batch *B, int dep) { return BatchTab{B->d_dv[dep], B->d_fp[dep], B->d_ph, B->alt[dep]}; }
+static OnMembers on(const suhmo_batch *B, int dep, const BatchSel &sel) { return on_members(tab(B, dep), sel, view(B, dep)); }   // the members `sel` at a depth, as a launch target
 
 // the device tables against the member handles: rows are rewritten when something other than the trade of the two head canvases changed
 static int batch_sync(suhmo_batch *B, hipStream_t st)
@@ -115,8 +116,8 @@ static int batch_readback(suhmo_batch *B, hipStream_t st)
 // residualI of depth 0 of the active members and their max norms: hslot[k]
 static int batch_residual_norms(suhmo_batch *B, const BatchSel &sel, hipStream_t st)
 {
-    int rc = suhmo_batch_residual_norm(tab(B, 0), sel, view(B, 0), B->has_alpha, B->partial, B->hslot_dev,
-                                       (unsigned long long *)(B->hslot_dev + SLOT_FLAG), ++B->hseq, st);
+    int rc = launch_residual_norm_members(on(B, 0, sel), B->has_alpha, B->partial, B->hslot_dev,
+                                          (unsigned long long *)(B->hslot_dev + SLOT_FLAG), ++B->hseq, st);
     if (rc) return rc;
     B->launches += 2;
     return batch_readback(B, st);
@@ -143,12 +144,12 @@ static int batch_relax(suhmo_batch *B, int dep, int sweeps, const BatchSel &sel,
     } else {
         if (frhs || prolong) { suhmo_set_error("internal: batch: a fused right-hand side / prolongation on a depth of colour passes"); return -4; }
         for (int p = 0; p < 2 * sweeps; p++) {
-            if ((rc = suhmo_batch_colour_pass(tab(B, dep), sel, v, p & 1, B->has_alpha, st))) return rc;
+            if ((rc = launch_colour_pass(on(B, dep, sel), B->has_alpha, p & 1, 0, 0, nullptr, nullptr, st))) return rc;
             B->launches++;
         }
     }
     if (sweeps > 0 && observable) {
-        if ((rc = suhmo_batch_fill_ghosts(tab(B, dep), sel, v, SUHMO_F_PHI, 1, st))) return rc;
+        if ((rc = launch_fill_ghosts(on(B, dep, sel), SUHMO_F_PHI, 1, st))) return rc;
         B->launches++;
     }
     return 0;
@@ -161,18 +162,18 @@ static int batch_fas_cycle(suhmo_batch *B, int dep, const suhmo_solver_params_t 
     const int S = sp->num_smooth;
     if (dep == nd - 1) return batch_relax(B, dep, sp->num_bottom, sel, st, dep == 0, frhs, false);
     if ((rc = batch_relax(B, dep, S, sel, st, false, frhs, false))) return rc;                        // pre-smooth
-    if ((rc = suhmo_batch_restrict_both(tab(B, dep), tab(B, dep + 1), sel, view(B, dep + 1), B->has_alpha, st))) return rc;   // RES, PHI of dep + 1
+    if ((rc = launch_restrict(on(B, dep, sel), on(B, dep + 1, sel), true, B->has_alpha, st))) return rc;   // RES, PHI of dep + 1
     B->launches++;
     const int next_sweeps = dep + 1 == nd - 1 ? sp->num_bottom : S;
     const bool rhs_in_relax = next_sweeps >= 1 && suhmo_batch_tile_ok(view(B, dep + 1));
     if (!rhs_in_relax) {                                                                                // PHIOLD = R phi, rhs_c = res_c + L_c(R phi)
-        if ((rc = suhmo_batch_fas_coarse_rhs(tab(B, dep + 1), sel, view(B, dep + 1), B->has_alpha, st))) return rc;
+        if ((rc = launch_fas_coarse_rhs(on(B, dep + 1, sel), B->has_alpha, st))) return rc;
         B->launches++;
     }
     if ((rc = batch_fas_cycle(B, dep + 1, sp, nd, sel, st, rhs_in_relax))) return rc;
     const bool prolong_in_relax = S >= 1 && suhmo_batch_tile_ok(view(B, dep));
     if (!prolong_in_relax) {                                                                            // corr = phi_c - phi_c,old; phi += P(corr)
-        if ((rc = suhmo_batch_prolong(tab(B, dep), tab(B, dep + 1), sel, view(B, dep), view(B, dep + 1), st))) return rc;
+        if ((rc = launch_prolong(on(B, dep, sel), on(B, dep + 1, sel), 0, 0, 0, 0, st))) return rc;
         B->launches += 2;
     }
     return batch_relax(B, dep, S, sel, st, dep == 0, false, prolong_in_relax);                          // post-smooth
@@ -183,12 +184,12 @@ static int batch_vcycle(suhmo_batch *B, const suhmo_solver_params_t *sp, const B
     if (sel.n <= 0) return 0;
     if (sp->max_depth >= 0 && sp->max_depth + 1 < nd) nd = sp->max_depth + 1;
     if (sp->bcoeff_otf) {                                                                               // UpdateOperator, AverageOperator on every depth > 0
-        if ((rc = suhmo_batch_update_operator(tab(B, 0), sel, view(B, 0), st))) return rc;
+        if ((rc = launch_bcoef_fused(on(B, 0, sel), false, nullptr, 0u, st))) return rc;
         B->launches++;
-        BatchTab tabs[SUHMO_MAXDEPTH];
-        for (int dep = 0; dep < nd; dep++) tabs[dep] = tab(B, dep);
+        OnMembers tabs[SUHMO_MAXDEPTH];
+        for (int dep = 0; dep < nd; dep++) tabs[dep] = on(B, dep, sel);
         int nl = 0;
-        if ((rc = suhmo_batch_average_operator_all(tabs, B->d_avg, sel, B->mem[0], nd, st, &nl))) return rc;
+        if ((rc = suhmo_batch_average_operator_all(tabs, B->d_avg, nd, st, &nl))) return rc;
         B->launches += nl;
     }
     if ((rc = batch_fas_cycle(B, 0, sp, nd, sel, st, false))) return rc;
@@ -271,7 +272,7 @@ static int batch_create(suhmo_batch **out, const suhmo_level_desc_t *desc, int n
     }
     B->h_ph.resize(n_members);
     memset(B->h_ph.data(), 0, n_members * sizeof(suhmo_phys_t));
-    B->np = suhmo_batch_residual_partials(view(B, 0));
+    B->np = suhmo_batch_residual_partials(on_members(BatchTab{}, BatchSel{}, view(B, 0)));
     if (hipMalloc(&B->d_ph, n_members * sizeof(suhmo_phys_t)) != hipSuccess || hipMalloc(&B->partial, 2 * n_members * B->np * sizeof(double)) != hipSuccess
         || hipHostMalloc(&B->hslot, (SLOT_FLAG + 8) * sizeof(double), hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess
         || hipHostGetDevicePointer((void **)&B->hslot_dev, B->hslot, 0) != hipSuccess) {
@@ -334,7 +335,7 @@ static int batch_solve(suhmo_batch *B, const suhmo_solver_params_t *sp, const Ba
     }
     for (int k = 0; k < B->n; k++) if (in[k]) { if (iters) iters[k] = state[k].iter; if (residual) residual[k] = state[k].rnorm; }
     // the ring as the solve of a level leaves it (suhmo_level_solve): the inhomogeneous fill of the final residual evaluation
-    if ((rc = suhmo_batch_fill_ghosts(tab(B, 0), first, view(B, 0), SUHMO_F_PHI, 0, st))) return rc;
+    if ((rc = launch_fill_ghosts(on(B, 0, first), SUHMO_F_PHI, 0, st))) return rc;
     B->launches++;
     return 0;
 }
@@ -371,7 +372,7 @@ BatchSel suhmo_batch_step_subset(const suhmo_batch *B, const suhmo_model_params_
 int suhmo_batch_step_mg_coefficients(suhmo_batch *B, hipStream_t st)
 {
     int nl = 0;
-    int rc = suhmo_batch_build_mg_coefficients(tab(B, 0), B->d_avg, B->phase, B->mem[0], st, &nl);
+    int rc = suhmo_batch_build_mg_coefficients(on(B, 0, B->phase), B->d_avg, B->mem[0], st, &nl);
     B->launches += nl;
     for (suhmo_level *L : B->mem) L->coarse_mask_ok = 1;
     return rc;
@@ -413,7 +414,7 @@ static int gap_batch_prepare(suhmo_batch *B, const suhmo_model_params_t *mp, dou
     G->tile_order = B->tile_order;
     if ((rc = batch_enter(G, st)) || !fresh) return rc;
     int nl = 0;
-    rc = suhmo_batch_build_mg_coefficients(tab(G, 0), G->d_avg, all_members(G), G->mem[0], st, &nl);
+    rc = suhmo_batch_build_mg_coefficients(on(G, 0, all_members(G)), G->d_avg, G->mem[0], st, &nl);
     G->launches += nl;
     return rc;
 }
@@ -426,14 +427,14 @@ int suhmo_batch_step_solve_gap(suhmo_batch *B, const BatchSel &sel, const suhmo_
     suhmo_batch *G = B->gap;
     const size_t elems = B->mem[0]->d[0].elems;
     if (G->mem[0]->d[0].elems != elems) { suhmo_set_error("internal: batch: gap level geometry"); return -4; }
-    if ((rc = suhmo_batch_gap_load(tab(B, 0), tab(G, 0), sel, elems, st))) return rc;                   // initial guess = b :3382-3385, RHS, D on the faces
+    if ((rc = suhmo_batch_gap_load(on(B, 0, sel), on(G, 0, sel), elems, st))) return rc;                   // initial guess = b :3382-3385, RHS, D on the faces
     G->launches++;
-    BatchTab tabs[SUHMO_MAXDEPTH];
-    for (int dep = 0; dep < G->ndepth; dep++) tabs[dep] = tab(G, dep);
-    if ((rc = suhmo_batch_average_operator_all(tabs, G->d_avg, sel, G->mem[0], G->ndepth, st, &nl))) return rc;     // coarse D = average of the fine faces
+    OnMembers tabs[SUHMO_MAXDEPTH];
+    for (int dep = 0; dep < G->ndepth; dep++) tabs[dep] = on(G, dep, sel);
+    if ((rc = suhmo_batch_average_operator_all(tabs, G->d_avg, G->ndepth, st, &nl))) return rc;     // coarse D = average of the fine faces
     G->launches += nl;
     if ((rc = batch_solve(G, sp, sel, nullptr, nullptr, st))) return rc;
-    if ((rc = suhmo_batch_gap_store(tab(B, 0), tab(G, 0), sel, B->d_mp, elems, st))) return rc;         // (tab(G, 0) after the solve: the canvases have traded)
+    if ((rc = suhmo_batch_gap_store(on_members(tab(B, 0), sel, view(B, 0), B->d_mp), on(G, 0, sel), elems, st))) return rc;         // (tab(G, 0) after the solve: the canvases have traded)
     G->launches++;
     return 0;
 }

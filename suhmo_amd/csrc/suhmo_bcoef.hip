@@ -6,6 +6,7 @@
 #include <algorithm>
 #include <cmath>
 #include <initializer_list>
+#include <type_traits>
 // ------------------------------------------------------------------ bCoef update (WFlx_level)
 // step 1: cell-centred gradient = EdgeToCell(NEWMACGRAD) (util/Gradient.cpp:96-127, :623;
 // util/GradientF.ChF:57-70)
@@ -41,21 +42,13 @@ __device__ __forceinline__ void d_gradcc(const DV &v, const FP &fp, int hasMask)
 {
     d_gradcc_at(v, fp, hasMask, blockIdx.x * blockDim.x + threadIdx.x, blockIdx.y * blockDim.y + threadIdx.y);
 }
-__global__ __launch_bounds__(256) void k_gradcc(DV v, FP fp, int hasMask)
-{
-    d_gradcc(v, fp, hasMask);
-}
+template <class T> __global__ __launch_bounds__(256) void k_gradcc(T t) { d_gradcc(t.view(), t.fields(), t.phys().use_mask_gradients); }
 // the same at a list of cells (x = i, y = j): the coarse cells a finer level's coarse-fine interpolation of the gradient reads
 __global__ __launch_bounds__(256) void k_gradcc_list(DV v, FP fp, int hasMask, const int2 *__restrict__ cells, int n)
 {
     const int t = blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= n) return;
     d_gradcc_at(v, fp, hasMask, cells[t].x, cells[t].y);
-}
-// every box of a multi-box AMR level in one launch (blockIdx.z = box; suhmo_hier.hip)
-__global__ __launch_bounds__(256) void k_gradcc_m(const DV *__restrict__ vt, const FP *__restrict__ ft, int hasMask)
-{
-    d_gradcc(vt[blockIdx.z], ft[blockIdx.z], hasMask);
 }
 // step 2: ghosts of the gradient: exchange (periodic wrap) + ExtrapGhostCells
 // (src/AmrHydro.cpp:1490-1491, util/ExtrapGhostCells.cpp:94-180, util/ExtrapBCF.ChF:21-29)
@@ -84,14 +77,10 @@ __device__ __forceinline__ void d_grad_ghosts(const DV &v, double *__restrict__ 
         }
     }
 }
-__global__ void k_grad_ghosts(DV v, double *__restrict__ gx, double *__restrict__ gy)
+template <class T> __global__ void k_grad_ghosts(T t)
 {
-    d_grad_ghosts(v, gx, gy);
-}
-// every box of a multi-box AMR level in one launch (blockIdx.z = box; suhmo_hier.hip)
-__global__ void k_grad_ghosts_m(const DV *__restrict__ vt, const FP *__restrict__ ft)
-{
-    d_grad_ghosts(vt[blockIdx.z], ft[blockIdx.z].f[SUHMO_F_GRADX], ft[blockIdx.z].f[SUHMO_F_GRADY]);
+    const FP &fp = t.fields();
+    d_grad_ghosts(t.view(), fp.f[SUHMO_F_GRADX], fp.f[SUHMO_F_GRADY]);
 }
 // steps 1 + 2 of every box of a level in ONE launch: the thread of a cell on a physical side of its box also writes the ghost cell beyond it,
 // from the gradient of the neighbour the extrapolation (or the periodic wrap) reads, evaluated a second time: d_grad_ghosts' expressions on the
@@ -122,10 +111,7 @@ __device__ __forceinline__ void d_gradcc_ghosts(const DV &v, const FP &fp, int h
         GX[idx + v.P] = v.per[1] ? ox : 2.0 * gx - ox; GY[idx + v.P] = v.per[1] ? oy : 2.0 * gy - oy;
     }
 }
-__global__ __launch_bounds__(256) void k_gradcc_ghosts_m(const DV *__restrict__ vt, const FP *__restrict__ ft, int hasMask)
-{
-    d_gradcc_ghosts(vt[blockIdx.z], ft[blockIdx.z], hasMask);
-}
+__global__ __launch_bounds__(256) void k_gradcc_ghosts(OnBoxes t) { d_gradcc_ghosts(t.view(), t.fields(), t.phys().use_mask_gradients); }
 // ... of SEVERAL levels (UpdateOperator of an AMR level evaluates the gradient of its own and of the coarser level)
 __global__ __launch_bounds__(256) void k_gradcc_ghosts_lv(suhmo_lvboxes lv, int hasMask)
 {
@@ -156,15 +142,7 @@ __device__ __forceinline__ void d_re(const DV &v, const FP &fp, suhmo_phys_t ph)
     int idx = cidx(v, i, j);
     fp.f[SUHMO_F_RE][idx] = d_re_val(fp, ph, idx);
 }
-__global__ __launch_bounds__(256) void k_re(DV v, FP fp, suhmo_phys_t ph)
-{
-    d_re(v, fp, ph);
-}
-// every box of a multi-box AMR level in one launch (blockIdx.z = box; suhmo_hier.hip)
-__global__ __launch_bounds__(256) void k_re_m(const DV *__restrict__ vt, const FP *__restrict__ ft, suhmo_phys_t ph)
-{
-    d_re(vt[blockIdx.z], ft[blockIdx.z], ph);
-}
+template <class T> __global__ __launch_bounds__(256) void k_re(T t) { d_re(t.view(), t.fields(), t.phys()); }
 // step 4: CellToEdge(Re), CellToEdge(B), setup_iceMask_EC, COMPUTEBCOEFF
 // (src/AmrHydro.cpp:1512-1537, src/HydroIBC.cpp:139-184, src/AmrHydroF.ChF:212-228)
 __device__ __forceinline__ double bcoef_face(const suhmo_phys_t &ph, double Rc, double Rm, double Bc, double Bm,
@@ -192,21 +170,14 @@ __device__ __forceinline__ void d_bcoef_faces(const DV &v, const FP &fp, suhmo_p
         fp.f[SUHMO_F_BY][idx] = bcoef_face(ph, Re[idx], Re[idx - v.P], B[idx], B[idx - v.P], m[idx], m[idx - v.P], jg == 0 || jg == v.nyg);
     }
 }
-__global__ __launch_bounds__(256) void k_bcoef_faces(DV v, FP fp, suhmo_phys_t ph)
-{
-    d_bcoef_faces(v, fp, ph);
-}
-// every box of a multi-box AMR level in one launch (blockIdx.z = box; suhmo_hier.hip)
-__global__ __launch_bounds__(256) void k_bcoef_faces_m(const DV *__restrict__ vt, const FP *__restrict__ ft, suhmo_phys_t ph)
-{
-    d_bcoef_faces(vt[blockIdx.z], ft[blockIdx.z], ph);
-}
+template <class T> __global__ __launch_bounds__(256) void k_bcoef_faces(T t) { d_bcoef_faces(t.view(), t.fields(), t.phys()); }
 // steps 3 + 4 of every box of a level in ONE launch: the thread of a position of the ghosted box stores Re there (d_re) and the two faces on
 // its low sides (d_bcoef_faces), with the Re of the two cells across those faces evaluated a second time from the same gradient and gap height
-__global__ __launch_bounds__(256) void k_re_bcoef_m(const DV *__restrict__ vt, const FP *__restrict__ ft, suhmo_phys_t ph)
+__global__ __launch_bounds__(256) void k_re_bcoef(OnBoxes t)
 {
-    const DV &v = vt[blockIdx.z];
-    const FP &fp = ft[blockIdx.z];
+    const DV &v = t.view();
+    const FP &fp = t.fields();
+    const suhmo_phys_t &ph = t.phys();
     const int i = (int)(blockIdx.x * blockDim.x + threadIdx.x) - 1, j = (int)(blockIdx.y * blockDim.y + threadIdx.y) - 1;
     if (i > v.nx || j > v.ny) return;
     const bool xo = (i < 0 || i >= v.nx), yo = (j < 0 || j >= v.ny);
@@ -393,20 +364,36 @@ __device__ __forceinline__ void d_bcoef_fused(const DV &v, const FP &fp, const s
     if (interior) bcoef_tile<true, BT_X, BT_Y>(v, fp, ph, hasMask, sphi, sB, sM, negflag, epoch);
     else bcoef_tile<false, BT_X, BT_Y>(v, fp, ph, hasMask, sphi, sB, sM, negflag, epoch);
 }
-template <int BT_X, int BT_Y>
-__global__ __launch_bounds__(256) void k_bcoef_fused(DV v, FP fp, suhmo_phys_t ph, int hasMask, unsigned *negflag, unsigned epoch)
+template <class T, int BT_X, int BT_Y>
+__global__ __launch_bounds__(256) void k_bcoef_fused(T t, unsigned *negflag, unsigned epoch)
 {
-    d_bcoef_fused<BT_X, BT_Y>(v, fp, ph, hasMask, negflag, epoch);
+    const suhmo_phys_t ph = t.phys();
+    if (std::is_same<T, OnMembers>::value) { negflag = nullptr; epoch = 0u; }      // an ensemble's relaxation always reads the ice mask: nobody takes a report
+    d_bcoef_fused<BT_X, BT_Y>(t.view(), t.fields(), ph, ph.use_mask_gradients, negflag, epoch);
 }
-// every active member of a batch (suhmo_batch.h); no report on the ice mask: the batched relaxation always reads it.  The tile is the
-// level's default (bcoef_tile_x = 62: 62 x 14 cells on 64 x 4 threads); the wide tile is an A/B option of large levels
-constexpr int BCOEF_B_TX = 62, BCOEF_B_TY = 14;
-__global__ __launch_bounds__(256) void k_bcoef_fused_b(BatchTab t, BatchSel sel)
+// tiles of 62 x 14 cells on 64 x 4 threads; wide (an A/B option of large single levels): 126 x 14 on 128 x 2.  flag: the report on the ice
+// mask, or NULL (an ensemble: its relaxation always reads the mask).  The last tile column / row also owns the E / N faces
+template <class T> int launch_bcoef_fused(const T &t, bool wide, unsigned *flag, unsigned epoch, hipStream_t st)
 {
-    const int k = batch_member(sel);
-    const suhmo_phys_t ph = t.ph[k];
-    d_bcoef_fused<BCOEF_B_TX, BCOEF_B_TY>(t.dv[k], batch_fp(t, k), ph, ph.use_mask_gradients, nullptr, 0u);
+    if constexpr (std::is_same<T, OnLevel>::value)
+        if (wide) return launch_grid(k_bcoef_fused<T, 126, 14>, t, dim3((t.nx() + 125) / 126, (t.ny() + 13) / 14), dim3(128, 2), st, flag, epoch);
+    return launch_grid(k_bcoef_fused<T, 62, 14>, t, dim3((t.nx() + 61) / 62, (t.ny() + 13) / 14), dim3(64, 4), st, flag, epoch);
 }
+template int launch_bcoef_fused(const OnMembers &, bool, unsigned *, unsigned, hipStream_t);
+template <class T> int launch_re(const T &t, hipStream_t st) { return launch_over(k_re<T>, t, GHOSTED, st); }      // COMPUTERE on the ghosted box
+template <class T> int launch_bcoef_faces(const T &t, hipStream_t st) { return launch_over(k_bcoef_faces<T>, t, FACES, st); }
+template <class T> int launch_grad_cc(const T &t, hipStream_t st)      // the gradient and its ghosts (a level exchanges in between: suhmo_grad_cc)
+{
+    int rc = launch_over(k_gradcc<T>, t, CELLS, st);
+    return rc ? rc : launch_over(k_grad_ghosts<T>, t, PERIMETER, st);
+}
+template int launch_re(const OnLevel &, hipStream_t);
+template int launch_re(const OnBoxes &, hipStream_t);
+template int launch_re(const OnMembers &, hipStream_t);
+template int launch_bcoef_faces(const OnLevel &, hipStream_t);
+template int launch_bcoef_faces(const OnBoxes &, hipStream_t);
+template int launch_bcoef_faces(const OnMembers &, hipStream_t);
+template int launch_grad_cc(const OnMembers &, hipStream_t);
 
 extern "C" int suhmo_level_update_operator(suhmo_level_t *L, int depth, suhmo_stream_t s)
 {
@@ -421,9 +408,7 @@ extern "C" int suhmo_level_update_operator(suhmo_level_t *L, int depth, suhmo_st
                  && L->desc.nx_global == 0;      // AMR patches: un-fused kernels (coarse-fine ghosts are stored data)
     int rc = suhmo_ensure_phi_halo(L, depth, fused ? 2 : 1, st); if (rc) return rc;
     if (fused) {
-        const bool wide = L->bcoef_tile_x == 126 && D.v.nx >= 256;          // tiles of 126 x 14 cells on 128 x 2 threads (else 62 x 14 on 64 x 4)
-        const int BX = wide ? 126 : 62, BY = 14;
-        dim3 grd((D.v.nx + BX - 1) / BX, (D.v.ny + BY - 1) / BY);   // the last tile column / row also owns the E / N faces
+        const bool wide = L->bcoef_tile_x == 126 && D.v.nx >= 256;
         // depth 0 of a whole level: the kernel also reports (device word = this call's number) whether the ice mask has a negative cell
         // (the V-cycle that called takes the report up, suhmo_fas.hip: it holds until that cycle ends, not across calls of this entry point)
         unsigned *flag = nullptr;
@@ -433,8 +418,7 @@ extern "C" int suhmo_level_update_operator(suhmo_level_t *L, int depth, suhmo_st
             if (++L->mask_epoch == 0) L->mask_epoch = 1;
             L->mask_reported = 1;
         }
-        if (wide) hipLaunchKernelGGL((k_bcoef_fused<126, 14>), grd, dim3(128, 2), 0, st, D.v, D.fp, L->ph, L->ph.use_mask_gradients, flag, L->mask_epoch);
-        else hipLaunchKernelGGL((k_bcoef_fused<62, 14>), grd, dim3(64, 4), 0, st, D.v, D.fp, L->ph, L->ph.use_mask_gradients, flag, L->mask_epoch);
+        if ((rc = launch_bcoef_fused(on_level(L, depth), wide, flag, L->mask_epoch, st))) return rc;
         if (flag && (D.v.ext[0] || D.v.ext[1])) {
             MaskHalo h;
             h.nd = 0; h.lo = D.v.ext[0]; h.hi = D.v.ext[1];
@@ -451,12 +435,10 @@ extern "C" int suhmo_level_update_operator(suhmo_level_t *L, int depth, suhmo_st
     } else {
         if (depth == 0) { L->maskflag_epoch = 0; L->mask_reported = 0; }
         if (!suhmo_field(L, depth, SUHMO_F_GRADX) || !suhmo_field(L, depth, SUHMO_F_GRADY) || !suhmo_field(L, depth, SUHMO_F_RE)) return -2;
-        hipLaunchKernelGGL(k_gradcc, grid2d(D.v.nx, D.v.ny), BLK2D, 0, st, D.v, D.fp, L->ph.use_mask_gradients);
+        const OnLevel t = on_level(L, depth);
+        if ((rc = launch_over(k_gradcc<OnLevel>, t, CELLS, st))) return rc;
         rc = suhmo_exchange_fields(L, depth, {SUHMO_F_GRADX, SUHMO_F_GRADY}, st); if (rc) return rc;
-        int n = 2 * D.v.ny + 2 * D.v.nx;
-        hipLaunchKernelGGL(k_grad_ghosts, dim3((n + 255) / 256), dim3(256), 0, st, D.v, D.fp.f[SUHMO_F_GRADX], D.fp.f[SUHMO_F_GRADY]);
-        hipLaunchKernelGGL(k_re, grid2d(D.v.nx + 2, D.v.ny + 2), BLK2D, 0, st, D.v, D.fp, L->ph);
-        hipLaunchKernelGGL(k_bcoef_faces, grid2d(D.v.nx + 1, D.v.ny + 1), BLK2D, 0, st, D.v, D.fp, L->ph);
+        if ((rc = launch_over(k_grad_ghosts<OnLevel>, t, PERIMETER, st)) || (rc = launch_re(t, st)) || (rc = launch_bcoef_faces(t, st))) return rc;
     }
     HIPCHK(hipGetLastError());
     // strips: the fused relaxation recomputes halo rows, so it needs the coefficients there too (faces_deferred: the V-cycle sends them
@@ -470,15 +452,11 @@ extern "C" int suhmo_level_update_operator(suhmo_level_t *L, int depth, suhmo_st
 // domain-side ghosts; then (after the coarse-fine ghosts were interpolated) Re and bCoef
 int suhmo_grad_cc(suhmo_level *L, int depth, hipStream_t st)
 {
-    Depth &D = L->d[depth];
     if (!suhmo_field(L, depth, SUHMO_F_GRADX) || !suhmo_field(L, depth, SUHMO_F_GRADY) || !suhmo_field(L, depth, SUHMO_F_RE)) return -2;
     int rc = suhmo_ensure_phi_halo(L, depth, 1, st); if (rc) return rc;
-    hipLaunchKernelGGL(k_gradcc, grid2d(D.v.nx, D.v.ny), BLK2D, 0, st, D.v, D.fp, L->ph.use_mask_gradients);
+    if ((rc = launch_over(k_gradcc<OnLevel>, on_level(L, depth), CELLS, st))) return rc;
     rc = suhmo_exchange_fields(L, depth, {SUHMO_F_GRADX, SUHMO_F_GRADY}, st); if (rc) return rc;    // lvlgradH.exchange() :1490
-    int n = 2 * D.v.ny + 2 * D.v.nx;
-    hipLaunchKernelGGL(k_grad_ghosts, dim3((n + 255) / 256), dim3(256), 0, st, D.v, D.fp.f[SUHMO_F_GRADX], D.fp.f[SUHMO_F_GRADY]);
-    HIPCHK(hipGetLastError());
-    return 0;
+    return launch_over(k_grad_ghosts<OnLevel>, on_level(L, depth), PERIMETER, st);
 }
 // GRADX / GRADY at the listed cells only (device list of (i, j)); nothing else of the two fields is touched
 int suhmo_grad_cc_list(suhmo_level *L, int depth, const int2 *d_cells, int n, hipStream_t st)
@@ -492,38 +470,15 @@ int suhmo_grad_cc_list(suhmo_level *L, int depth, const int2 *d_cells, int n, hi
 }
 int suhmo_re_bcoef_unfused(suhmo_level *L, int depth, hipStream_t st)
 {
-    Depth &D = L->d[depth];
-    hipLaunchKernelGGL(k_re, grid2d(D.v.nx + 2, D.v.ny + 2), BLK2D, 0, st, D.v, D.fp, L->ph);
-    hipLaunchKernelGGL(k_bcoef_faces, grid2d(D.v.nx + 1, D.v.ny + 1), BLK2D, 0, st, D.v, D.fp, L->ph);
-    HIPCHK(hipGetLastError());
-    return 0;
-}
-
-// aCoeff_bCoeff (src/AmrHydro.cpp:1781-1817, called at :3087-3102): the bCoef the solver's operators are defined with, from the
-// lagged Re and gap height of the time step (RE, B with their ghosts) -- the first residual of a solve sees it
-int suhmo_bcoef_faces(suhmo_level *L, int depth, hipStream_t st)
-{
-    Depth &D = L->d[depth];
-    hipLaunchKernelGGL(k_bcoef_faces, grid2d(D.v.nx + 1, D.v.ny + 1), BLK2D, 0, st, D.v, D.fp, L->ph);
-    HIPCHK(hipGetLastError());
-    return 0;
-}
-int suhmo_re_cells(suhmo_level *L, int depth, hipStream_t st)      // COMPUTERE on the ghosted box (time step on a hierarchy)
-{
-    Depth &D = L->d[depth];
-    hipLaunchKernelGGL(k_re, grid2d(D.v.nx + 2, D.v.ny + 2), BLK2D, 0, st, D.v, D.fp, L->ph);
-    HIPCHK(hipGetLastError());
-    return 0;
+    int rc = launch_re(on_level(L, depth), st);
+    return rc ? rc : launch_bcoef_faces(on_level(L, depth), st);
 }
 // grad h (cell centred, extrapolated ghosts) and Re on the ghosted level, for the time step
 // (suhmo_step.hip): the un-fused steps 1-3 above
 int suhmo_grad_re(suhmo_level *L, int depth, hipStream_t st)
 {
-    Depth &D = L->d[depth];
-    int rc = suhmo_grad_cc(L, depth, st); if (rc) return rc;       // rank strips: phi halo row + exchange of the gradient
-    hipLaunchKernelGGL(k_re, grid2d(D.v.nx + 2, D.v.ny + 2), BLK2D, 0, st, D.v, D.fp, L->ph);
-    HIPCHK(hipGetLastError());
-    return 0;
+    int rc = suhmo_grad_cc(L, depth, st);                           // rank strips: phi halo row + exchange of the gradient
+    return rc ? rc : launch_re(on_level(L, depth), st);
 }
 
 // AverageOperator: CoarseAverageFace(bCoef[0] -> bCoef[depth], ratio r = 2^depth), sequential
@@ -546,16 +501,10 @@ __device__ __forceinline__ void d_average_faces(const DV &vf, const double *__re
         byc[cidx(vc, ic, jc)] = sm / (double)r;
     }
 }
-__global__ void k_average_faces(DV vf, const double *__restrict__ bxf, const double *__restrict__ byf,
-                                DV vc, double *__restrict__ bxc, double *__restrict__ byc, int r)
+template <class T> __global__ void k_average_faces(T c, T f, int r)      // (faces: no second canvas)
 {
-    d_average_faces(vf, bxf, byf, vc, bxc, byc, r);
-}
-__global__ void k_average_faces_b(BatchTab f, BatchTab c, BatchSel sel, int r)      // every active member of a batch (suhmo_batch.h)
-{
-    const int k = batch_member(sel);
-    const FP &ff = f.fp[k], &fc = c.fp[k];                   // (faces: no second canvas)
-    d_average_faces(f.dv[k], ff.f[SUHMO_F_BX], ff.f[SUHMO_F_BY], c.dv[k], fc.f[SUHMO_F_BX], fc.f[SUHMO_F_BY], r);
+    const FP &ff = f.fields(), &fc = c.fields();
+    d_average_faces(f.view(), ff.f[SUHMO_F_BX], ff.f[SUHMO_F_BY], c.view(), fc.f[SUHMO_F_BX], fc.f[SUHMO_F_BY], r);
 }
 // All depths of AverageOperator in ONE pass over the depth-0 faces (the V-cycle refreshes every
 // depth right after UpdateOperator).  The reference's arithmetic is a sequential sum of the
@@ -636,23 +585,29 @@ __device__ __forceinline__ void d_average_faces_all(const DV &vf, const double *
     if (b < nbx) d_average_faces_x_all(vf, bxf, o, nd, b % gxx, b / gxx, threadIdx.x & 63, threadIdx.x >> 6);
     else d_average_faces_y_all(vf, byf, o, nd, (b - nbx) % gyx, (b - nbx) / gyx, threadIdx.x);
 }
-__global__ __launch_bounds__(256) void k_average_faces_all(DV vf, const double *__restrict__ bxf, const double *__restrict__ byf, AvgOut o, int nd, int gxx, int gxy, int gyx)
+// the pointers of all depths beside the target (`A`): by value for a level, a device row per member of an ensemble (row_of)
+struct AvgAll;
+struct BatchAvg;
+__device__ __forceinline__ const AvgOut &avg_out(const AvgOut &o) { return o; }
+__device__ __forceinline__ const AvgOut &avg_out(const BatchAvg &b);
+__device__ __forceinline__ const AvgAll &avg_all(const AvgAll &a) { return a; }
+__device__ __forceinline__ const AvgAll &avg_all(const BatchAvg &b);
+template <class T, class A>
+__global__ __launch_bounds__(256) void k_average_faces_all(T t, A av, int nd, int gxx, int gxy, int gyx)
 {
-    d_average_faces_all(vf, bxf, byf, o, nd, gxx, gxy, gyx);
+    const FP &fp = t.fields();
+    d_average_faces_all(t.view(), fp.f[SUHMO_F_BX], fp.f[SUHMO_F_BY], avg_out(row_of(t, av)), nd, gxx, gxy, gyx);
 }
 
+template <class T> int launch_average_faces(const T &f, const T &c, int r, hipStream_t st) { return launch_over(k_average_faces<T>, c, FACES, st, f, r); }
 extern "C" int suhmo_level_average_operator(suhmo_level_t *L, int depth, suhmo_stream_t s)
 {
     SUHMO_TIME("VCAMRNonLinearPoissonOp::AverageOperator");
     ARG(L); ARG(depth >= 0 && depth < L->ndepth);
     if (depth == 0) return 0;
     HIPCHK(hipSetDevice(L->device));
-    Depth &F = L->d[0], &C = L->d[depth];
-    hipLaunchKernelGGL(k_average_faces, grid2d(C.v.nx + 1, C.v.ny + 1), BLK2D, 0, (hipStream_t)s, F.v, F.fp.f[SUHMO_F_BX], F.fp.f[SUHMO_F_BY],
-                       C.v, C.fp.f[SUHMO_F_BX], C.fp.f[SUHMO_F_BY], 1 << depth);
-    HIPCHK(hipGetLastError());
-    int rc = suhmo_exchange_fields(L, depth, {SUHMO_F_BX, SUHMO_F_BY}, (hipStream_t)s); if (rc) return rc;
-    return 0;
+    int rc = launch_average_faces(on_level(L, 0), on_level(L, depth), 1 << depth, (hipStream_t)s);
+    return rc ? rc : suhmo_exchange_fields(L, depth, {SUHMO_F_BX, SUHMO_F_BY}, (hipStream_t)s);
 }
 
 static void fill_avg_out(const suhmo_level *L, int nd, AvgOut &o)
@@ -681,8 +636,7 @@ int suhmo_average_operator_all(suhmo_level *L, int nd, hipStream_t st)
     fill_avg_out(L, nd, o);
     dim3 gx, gy;
     avg_faces_grids(F.v, nd, gx, gy);
-    hipLaunchKernelGGL(k_average_faces_all, dim3(gx.x * gx.y + gy.x * gy.y), dim3(256), 0, st, F.v, F.fp.f[SUHMO_F_BX], F.fp.f[SUHMO_F_BY], o, nd, (int)gx.x, (int)gx.y, (int)gy.x);
-    HIPCHK(hipGetLastError());
+    { int rc = launch_grid(k_average_faces_all<OnLevel, AvgOut>, on_level(L, 0), dim3(gx.x * gx.y + gy.x * gy.y), dim3(256), st, o, nd, (int)gx.x, (int)gx.y, (int)gy.x); if (rc) return rc; }
     // strips: the coarse face coefficients of all depths travel as one message group when the transport can batch
     if (L->ipc) { int rc = suhmo_ipc_batch(L, 1, st); if (rc) return rc; }
     else if (L->ex_begin && L->ex) { int rc = L->ex_begin(L->user); if (rc) return rc; }
@@ -743,10 +697,7 @@ __device__ __forceinline__ void d_average_cells_all(const DV &vf, const AvgAll &
     }
     C.c[q][(jc + C.gy) * C.P + SUHMO_XOFF + ic] = m;
 }
-__global__ __launch_bounds__(256) void k_average_cells_all(DV vf, AvgAll a, int nd)
-{
-    d_average_cells_all(vf, a, nd);
-}
+template <class T, class A> __global__ __launch_bounds__(256) void k_average_cells_all(T t, A av, int nd) { d_average_cells_all(t.view(), avg_all(row_of(t, av)), nd); }
 // ghosts of coarse B / Pi / zb / mask: periodic wrap or Neumann copy (NeumBCForB :1309-1341)
 __device__ __forceinline__ void d_coef_ghosts(const DV &v, double *__restrict__ p)
 {
@@ -766,15 +717,7 @@ __device__ __forceinline__ void d_coef_ghosts(const DV &v, double *__restrict__ 
         else { int idx = cidx(v, i, v.ny - 1); p[idx + v.P] = v.per[1] ? p[idx - (v.ny - 1) * v.P] : p[idx]; }
     }
 }
-__global__ void k_coef_ghosts(DV v, double *__restrict__ p)
-{
-    d_coef_ghosts(v, p);
-}
-// every box of a multi-box AMR level in one launch (blockIdx.z = box; suhmo_hier.hip)
-__global__ void k_coef_ghosts_m(const DV *__restrict__ vt, const FP *__restrict__ ft, int field)
-{
-    d_coef_ghosts(vt[blockIdx.z], ft[blockIdx.z].f[field]);
-}
+template <class T> __global__ void k_coef_ghosts(T t, int field) { d_coef_ghosts(t.view(), t.field(field)); }
 __device__ __forceinline__ void d_coef_ghosts_all(const DV &v0, const AvgAll &a)        // B, Pi, zb, mask of every coarse depth (blockIdx.y = (depth - 1) * 4 + field - 1)
 {
     const AvgDepth &C = a.d[blockIdx.y / 4];
@@ -796,63 +739,20 @@ __device__ __forceinline__ void d_coef_ghosts_all(const DV &v0, const AvgAll &a)
         else { int idx = (ny - 1 + C.gy) * P + SUHMO_XOFF + i; p[idx + P] = v0.per[1] ? p[idx - (ny - 1) * P] : p[idx]; }
     }
 }
-__global__ void k_coef_ghosts_all(DV v0, AvgAll a)
-{
-    d_coef_ghosts_all(v0, a);
-}
-// every active member of a batch (suhmo_batch.h): the member's pointers of all depths are a row of a device table written once
+template <class T, class A> __global__ void k_coef_ghosts_all(T t, A av) { d_coef_ghosts_all(t.view(), avg_all(row_of(t, av))); }
+// an ensemble: the member's pointers of all depths are a row of a device table written once
 struct BatchAvg { AvgAll a; AvgOut o; };
-__global__ __launch_bounds__(256) void k_average_cells_all_b(BatchTab t, const BatchAvg *__restrict__ at, BatchSel sel, int nd)
-{
-    const int k = batch_member(sel);
-    d_average_cells_all(t.dv[k], at[k].a, nd);
-}
-__global__ void k_coef_ghosts_all_b(BatchTab t, const BatchAvg *__restrict__ at, BatchSel sel)
-{
-    const int k = batch_member(sel);
-    d_coef_ghosts_all(t.dv[k], at[k].a);
-}
-__global__ __launch_bounds__(256) void k_average_faces_all_b(BatchTab t, const BatchAvg *__restrict__ at, BatchSel sel, int nd, int gxx, int gxy, int gyx)
-{
-    const int k = batch_member(sel);
-    const FP &fp = t.fp[k];
-    d_average_faces_all(t.dv[k], fp.f[SUHMO_F_BX], fp.f[SUHMO_F_BY], at[k].o, nd, gxx, gxy, gyx);
-}
-__global__ void k_coef_ghosts_b(BatchTab t, BatchSel sel, int field)
-{
-    const int k = batch_member(sel);
-    d_coef_ghosts(t.dv[k], t.fp[k].f[field]);
-}
-__global__ __launch_bounds__(256) void k_gradcc_b(BatchTab t, BatchSel sel)
-{
-    const int k = batch_member(sel);
-    d_gradcc(t.dv[k], batch_fp(t, k), t.ph[k].use_mask_gradients);
-}
-__global__ void k_grad_ghosts_b(BatchTab t, BatchSel sel)
-{
-    const int k = batch_member(sel);
-    d_grad_ghosts(t.dv[k], t.fp[k].f[SUHMO_F_GRADX], t.fp[k].f[SUHMO_F_GRADY]);
-}
-__global__ __launch_bounds__(256) void k_re_b(BatchTab t, BatchSel sel)
-{
-    const int k = batch_member(sel);
-    d_re(t.dv[k], t.fp[k], t.ph[k]);
-}
-__global__ __launch_bounds__(256) void k_bcoef_faces_b(BatchTab t, BatchSel sel)
-{
-    const int k = batch_member(sel);
-    d_bcoef_faces(t.dv[k], t.fp[k], t.ph[k]);
-}
+__device__ __forceinline__ const AvgOut &avg_out(const BatchAvg &b) { return b.o; }
+__device__ __forceinline__ const AvgAll &avg_all(const BatchAvg &b) { return b.a; }
+typedef const BatchAvg *__restrict__ BatchAvgRows;      // (written once: a kernel's stores never change them)
+template <class T> int launch_coef_ghosts(const T &t, int field, hipStream_t st) { return launch_over(k_coef_ghosts<T>, t, PERIMETER, st, field); }
+template int launch_coef_ghosts(const OnBoxes &, int, hipStream_t);
+template int launch_coef_ghosts(const OnMembers &, int, hipStream_t);
 // exchange + CopyGhostCells of a cell field (util/ExtrapGhostCells.cpp:182-269)
 int suhmo_copy_ghosts(suhmo_level *L, int depth, int field, hipStream_t st)
 {
-    Depth &D = L->d[depth];
-    double *p = suhmo_field(L, depth, field);
-    if (!p) return -2;
-    int n = 2 * D.v.ny + 2 * D.v.nx;
-    hipLaunchKernelGGL(k_coef_ghosts, dim3((n + 255) / 256), dim3(256), 0, st, D.v, p);
-    HIPCHK(hipGetLastError());
-    return 0;
+    if (!suhmo_field(L, depth, field)) return -2;
+    return launch_coef_ghosts(on_level(L, depth), field, st);
 }
 static int fill_avg_all(const suhmo_level *L, AvgAll &a)      // returns the workgroups of k_average_cells_all
 {
@@ -869,19 +769,20 @@ static int fill_avg_all(const suhmo_level *L, AvgAll &a)      // returns the wor
     }
     return nblocks;
 }
+// MGnewOp's coefficient averages of every depth > 0 and their ghosts: two launches (v1: the view of depth 1, the largest ring)
+template <class T, class A> static int launch_average_cells_all(const T &t, A av, int nblocks, const DV &v1, int nd, hipStream_t st)
+{
+    int rc = launch_grid(k_average_cells_all<T, A>, t, dim3(nblocks), BLK2D, st, av, nd);
+    return rc ? rc : launch_grid(k_coef_ghosts_all<T, A>, t, dim3((2 * v1.ny + 2 * v1.nx + 255) / 256, 4 * (nd - 1)), dim3(256), st, av);
+}
 // with_faces = false: the caller's cycle re-averages bCoef itself (bcoeff_otf: UpdateOperator + AverageOperator every V-cycle)
 int suhmo_build_mg_coefficients(suhmo_level *L, bool with_faces, hipStream_t st)
 {
-    Depth &F = L->d[0];
     const int nd = L->ndepth;
     if (nd > 1) {
         AvgAll a;
         const int nblocks = fill_avg_all(L, a);
-        const Depth &C1 = L->d[1];
-        hipLaunchKernelGGL(k_average_cells_all, dim3(nblocks), dim3(64, 4), 0, st, F.v, a, nd);
-        const int n = 2 * C1.v.ny + 2 * C1.v.nx;
-        hipLaunchKernelGGL(k_coef_ghosts_all, dim3((n + 255) / 256, 4 * (nd - 1)), dim3(256), 0, st, F.v, a);
-        HIPCHK(hipGetLastError());
+        int rc = launch_average_cells_all(on_level(L, 0), a, nblocks, L->d[1].v, nd, st); if (rc) return rc;
     }
     for (int dep = 1; dep < nd; dep++) {
         int rc;
@@ -900,19 +801,9 @@ extern "C" int suhmo_level_build_mg_coefficients(suhmo_level_t *L, suhmo_stream_
 }
 
 // ---- every box of a multi-box AMR level in one launch
-int suhmo_multi_grad_cc(const suhmo_multi &m, int hasMask, hipStream_t st)
+int suhmo_multi_grad_cc(const suhmo_multi &m, hipStream_t st)
 {
-    if (m.nbox <= 0) return 0;                       // a rank that owns no box of the level
-    if (m.merged) {
-        hipLaunchKernelGGL(k_gradcc_ghosts_m, grid_m(m), BLK2D, 0, st, m.dv, m.fp, hasMask);
-        HIPCHK(hipGetLastError());
-        return 0;
-    }
-    hipLaunchKernelGGL(k_gradcc_m, grid_m(m), BLK2D, 0, st, m.dv, m.fp, hasMask);
-    int n = 2 * m.maxny + 2 * m.maxnx;
-    hipLaunchKernelGGL(k_grad_ghosts_m, dim3((n + 255) / 256, 1, m.nbox), dim3(256), 0, st, m.dv, m.fp);
-    HIPCHK(hipGetLastError());
-    return 0;
+    return m.merged ? launch_over(k_gradcc_ghosts, m.on(), CELLS, st) : launch_grad_cc(m.on(), st);
 }
 
 int suhmo_levels_grad_cc(const suhmo_lvboxes &lv, int hasMask, hipStream_t st)
@@ -925,57 +816,15 @@ int suhmo_levels_grad_cc(const suhmo_lvboxes &lv, int hasMask, hipStream_t st)
     return 0;
 }
 
-int suhmo_multi_re(const suhmo_multi &m, const suhmo_phys_t &ph, hipStream_t st)
+int suhmo_multi_re_bcoef(const suhmo_multi &m, hipStream_t st)
 {
-    if (m.nbox <= 0) return 0;                       // a rank that owns no box of the level
-    hipLaunchKernelGGL(k_re_m, grid_m(m, 2, 2), BLK2D, 0, st, m.dv, m.fp, ph);
-    HIPCHK(hipGetLastError());
-    return 0;
+    const OnBoxes t = m.on();
+    if (m.merged) return launch_over(k_re_bcoef, t, GHOSTED, st);
+    int rc = launch_re(t, st);
+    return rc ? rc : launch_bcoef_faces(t, st);
 }
 
-int suhmo_multi_bcoef_faces(const suhmo_multi &m, const suhmo_phys_t &ph, hipStream_t st)
-{
-    if (m.nbox <= 0) return 0;                       // a rank that owns no box of the level
-    hipLaunchKernelGGL(k_bcoef_faces_m, grid_m(m, 1, 1), BLK2D, 0, st, m.dv, m.fp, ph);
-    HIPCHK(hipGetLastError());
-    return 0;
-}
-
-int suhmo_multi_re_bcoef(const suhmo_multi &m, const suhmo_phys_t &ph, hipStream_t st)
-{
-    if (m.nbox <= 0) return 0;
-    if (!m.merged) { int rc = suhmo_multi_re(m, ph, st); return rc ? rc : suhmo_multi_bcoef_faces(m, ph, st); }
-    hipLaunchKernelGGL(k_re_bcoef_m, grid_m(m, 2, 2), BLK2D, 0, st, m.dv, m.fp, ph);
-    HIPCHK(hipGetLastError());
-    return 0;
-}
-
-int suhmo_multi_coef_ghosts(const suhmo_multi &m, int field, hipStream_t st)
-{
-    if (m.nbox <= 0) return 0;                       // a rank that owns no box of the level
-    int n = 2 * m.maxny + 2 * m.maxnx;
-    hipLaunchKernelGGL(k_coef_ghosts_m, dim3((n + 255) / 256, 1, m.nbox), dim3(256), 0, st, m.dv, m.fp, field);
-    HIPCHK(hipGetLastError());
-    return 0;
-}
-
-
-// ------------------------------------------------------------------ every active member of a batch of whole levels in one launch (suhmo_batch.hip)
-int suhmo_batch_update_operator(const BatchTab &t, const BatchSel &sel, const DV &v, hipStream_t st)
-{
-    if (sel.n <= 0) return 0;
-    hipLaunchKernelGGL(k_bcoef_fused_b, dim3((v.nx + BCOEF_B_TX - 1) / BCOEF_B_TX, (v.ny + BCOEF_B_TY - 1) / BCOEF_B_TY, sel.n), dim3(BCOEF_B_TX + 2, 256 / (BCOEF_B_TX + 2)), 0, st, t, sel);
-    HIPCHK(hipGetLastError());
-    return 0;
-}
-int suhmo_batch_average_operator(const BatchTab &f, const BatchTab &c, const BatchSel &sel, const DV &vc, int r, hipStream_t st)
-{
-    if (sel.n <= 0) return 0;
-    dim3 grd = grid2d(vc.nx + 1, vc.ny + 1); grd.z = sel.n;
-    hipLaunchKernelGGL(k_average_faces_b, grd, BLK2D, 0, st, f, c, sel, r);
-    HIPCHK(hipGetLastError());
-    return 0;
-}
+// ------------------------------------------------------------------ an ensemble (suhmo_batch.hip)
 // the members' pointers of all depths (coefficient and face canvases: they never trade places): n rows, written once
 int suhmo_batch_avg_table(suhmo_level *const *mem, int n, void **dev)
 {
@@ -985,67 +834,34 @@ int suhmo_batch_avg_table(suhmo_level *const *mem, int n, void **dev)
     HIPCHK(hipMemcpy(*dev, h.data(), n * sizeof(BatchAvg), hipMemcpyHostToDevice));
     return 0;
 }
-// AverageOperator of every depth > 0 in one pass over the depth-0 faces where the grid allows (*launches: how many it took)
-int suhmo_batch_average_operator_all(const BatchTab *tabs, const void *avg, const BatchSel &sel, const suhmo_level *L0, int nd, hipStream_t st, int *launches)
+// AverageOperator of every depth > 0 in one pass over the depth-0 faces where the grid allows (*launches: how many it took); t[dep]: the
+// members at every depth
+int suhmo_batch_average_operator_all(const OnMembers *t, const void *avg, int nd, hipStream_t st, int *launches)
 {
     *launches = 0;
-    if (sel.n <= 0 || nd < 2) return 0;
-    const DV &v = L0->d[0].v;
+    if (t[0].count() <= 0 || nd < 2) return 0;
+    DV v{};
+    v.nx = t[0].nx(); v.ny = t[0].ny();
     if (!avg_faces_one_pass(v, nd)) {
         for (int dep = 1; dep < nd; dep++) {
-            int rc = suhmo_batch_average_operator(tabs[0], tabs[dep], sel, L0->d[dep].v, 1 << dep, st); if (rc) return rc;
+            int rc = launch_average_faces(t[0], t[dep], 1 << dep, st); if (rc) return rc;
             ++*launches;
         }
         return 0;
     }
     dim3 gx, gy;
     avg_faces_grids(v, nd, gx, gy);
-    hipLaunchKernelGGL(k_average_faces_all_b, dim3(gx.x * gx.y + gy.x * gy.y, 1, sel.n), dim3(256), 0, st, tabs[0], (const BatchAvg *)avg, sel, nd, (int)gx.x, (int)gx.y, (int)gy.x);
-    HIPCHK(hipGetLastError());
     *launches = 1;
-    return 0;
+    return launch_grid(k_average_faces_all<OnMembers, BatchAvgRows>, t[0], dim3(gx.x * gx.y + gy.x * gy.y), dim3(256), st, (const BatchAvg *)avg, nd, (int)gx.x, (int)gx.y, (int)gy.x);
 }
 // MGnewOp's coefficient averages of every depth > 0 and their ghosts (suhmo_build_mg_coefficients without the faces): two launches
-int suhmo_batch_build_mg_coefficients(const BatchTab &t0, const void *avg, const BatchSel &sel, const suhmo_level *L0, hipStream_t st, int *launches)
+int suhmo_batch_build_mg_coefficients(const OnMembers &t0, const void *avg, const suhmo_level *L0, hipStream_t st, int *launches)
 {
     *launches = 0;
     const int nd = L0->ndepth;
-    if (sel.n <= 0 || nd < 2) return 0;
+    if (t0.count() <= 0 || nd < 2) return 0;
     AvgAll a;
     const int nblocks = fill_avg_all(L0, a);                 // (the geometry: the members share it)
-    const DV &v1 = L0->d[1].v;
-    hipLaunchKernelGGL(k_average_cells_all_b, dim3(nblocks, 1, sel.n), dim3(64, 4), 0, st, t0, (const BatchAvg *)avg, sel, nd);
-    const int n = 2 * v1.ny + 2 * v1.nx;
-    hipLaunchKernelGGL(k_coef_ghosts_all_b, dim3((n + 255) / 256, 4 * (nd - 1), sel.n), dim3(256), 0, st, t0, (const BatchAvg *)avg, sel);
-    HIPCHK(hipGetLastError());
     *launches = 2;
-    return 0;
-}
-int suhmo_batch_copy_ghosts(const BatchTab &t, const BatchSel &sel, const DV &v, int field, hipStream_t st)
-{
-    if (sel.n <= 0) return 0;
-    const int n = 2 * v.ny + 2 * v.nx;
-    hipLaunchKernelGGL(k_coef_ghosts_b, dim3((n + 255) / 256, 1, sel.n), dim3(256), 0, st, t, sel, field);
-    HIPCHK(hipGetLastError());
-    return 0;
-}
-// suhmo_grad_re of every active member: cell-centred gradient, its ghosts, Re on the ghosted level (three launches)
-int suhmo_batch_grad_re(const BatchTab &t, const BatchSel &sel, const DV &v, hipStream_t st)
-{
-    if (sel.n <= 0) return 0;
-    dim3 g = grid2d(v.nx, v.ny), gr = grid2d(v.nx + 2, v.ny + 2); g.z = gr.z = sel.n;
-    const int n = 2 * v.ny + 2 * v.nx;
-    hipLaunchKernelGGL(k_gradcc_b, g, BLK2D, 0, st, t, sel);
-    hipLaunchKernelGGL(k_grad_ghosts_b, dim3((n + 255) / 256, 1, sel.n), dim3(256), 0, st, t, sel);
-    hipLaunchKernelGGL(k_re_b, gr, BLK2D, 0, st, t, sel);
-    HIPCHK(hipGetLastError());
-    return 0;
-}
-int suhmo_batch_bcoef_faces(const BatchTab &t, const BatchSel &sel, const DV &v, hipStream_t st)
-{
-    if (sel.n <= 0) return 0;
-    dim3 g = grid2d(v.nx + 1, v.ny + 1); g.z = sel.n;
-    hipLaunchKernelGGL(k_bcoef_faces_b, g, BLK2D, 0, st, t, sel);
-    HIPCHK(hipGetLastError());
-    return 0;
+    return launch_average_cells_all(t0, (BatchAvgRows)avg, nblocks, L0->d[1].v, nd, st);
 }

@@ -62,48 +62,35 @@ __device__ __forceinline__ void d_gsrb_pass_simple(const DV &v, const FP &fp, su
         if (j == v.ny - 1) { int2 q = push[2 * v.ny + v.nx + i]; if (q.x >= 0) ft[q.x].f[SUHMO_F_PHI][q.y] = pnew; }
     }
 }
-template <bool HAS_ALPHA>
-__global__ __launch_bounds__(256) void k_gsrb_pass_simple(DV v, FP fp, suhmo_phys_t ph, int pass, int jlo, int jhi)
+// rows [-lo, ny - 1 + hi] of a target.  push / pbase: the boxes' push tables (a target without a pointer table pushes nowhere)
+template <class T, bool HAS_ALPHA>
+__global__ __launch_bounds__(256) void k_gsrb_pass_simple(T t, int pass, int lo, int hi, const int2 *__restrict__ push, const int *__restrict__ pbase)
 {
-    d_gsrb_pass_simple<HAS_ALPHA>(v, fp, ph, pass, jlo, jhi);
+    const DV &v = t.view();
+    const FP *ft = t.table();
+    d_gsrb_pass_simple<HAS_ALPHA>(v, t.fields(), t.phys(), pass, -lo, v.ny - 1 + hi, ft, ft && push ? push + pbase[blockIdx.z] : nullptr);
 }
-// every box of a multi-box AMR level in one launch (blockIdx.z = box; suhmo_hier.hip)
-template <bool HAS_ALPHA>
-__global__ __launch_bounds__(256) void k_gsrb_pass_simple_m(const DV *__restrict__ vt, const FP *__restrict__ ft, suhmo_phys_t ph, int pass,
-                                                            const int2 *__restrict__ push, const int *__restrict__ pbase)
+template <class T> int launch_colour_pass(const T &t, bool has_alpha, int pass, int lo, int hi, const void *push, const int *pbase, hipStream_t st)
 {
-    d_gsrb_pass_simple<HAS_ALPHA>(vt[blockIdx.z], ft[blockIdx.z], ph, pass, 0, vt[blockIdx.z].ny - 1, ft, push ? push + pbase[blockIdx.z] : nullptr);
+    const dim3 grd = grid2d((t.nx() + 1) / 2, t.ny() + lo + hi);
+    if (has_alpha) return launch_grid(k_gsrb_pass_simple<T, true>, t, grd, BLK2D, st, pass, lo, hi, (const int2 *)push, pbase);
+    return launch_grid(k_gsrb_pass_simple<T, false>, t, grd, BLK2D, st, pass, lo, hi, (const int2 *)push, pbase);
 }
+template int launch_colour_pass(const OnBoxes &, bool, int, int, int, const void *, const int *, hipStream_t);
+template int launch_colour_pass(const OnMembers &, bool, int, int, int, const void *, const int *, hipStream_t);
 
-static void launch_simple(suhmo_level *L, int depth, int pass, int ext_rows, hipStream_t st)
+static int launch_simple(suhmo_level *L, int depth, int pass, int ext_rows, hipStream_t st)
 {
-    Depth &D = L->d[depth];
-    int jlo = D.v.rk[0] ? -ext_rows : 0, jhi = D.v.ny - 1 + (D.v.rk[1] ? ext_rows : 0);
-    dim3 blk(64, 4), grd(((D.v.nx + 1) / 2 + 63) / 64, (jhi - jlo + 1 + 3) / 4);
-    if (D.v.alpha != 0.0)
-        hipLaunchKernelGGL(k_gsrb_pass_simple<true>, grd, blk, 0, st, D.v, D.fp, L->ph, pass, jlo, jhi);
-    else
-        hipLaunchKernelGGL(k_gsrb_pass_simple<false>, grd, blk, 0, st, D.v, D.fp, L->ph, pass, jlo, jhi);
+    const DV &v = L->d[depth].v;
+    return launch_colour_pass(on_level(L, depth), v.alpha != 0.0, pass, v.rk[0] ? ext_rows : 0, v.rk[1] ? ext_rows : 0, nullptr, nullptr, st);
 }
 
 // one colour pass of one box of a multi-box AMR level (suhmo_hier.hip): in place, the ghost ring holds exchanged /
 // interpolated data
 int suhmo_gsrb_colour_pass(suhmo_level *L, int depth, int pass, hipStream_t st)
 {
-    launch_simple(L, depth, pass, 0, st);
-    HIPCHK(hipGetLastError());
+    int rc = launch_simple(L, depth, pass, 0, st); if (rc) return rc;
     L->d[depth].phi_fresh = 0;
-    return 0;
-}
-
-int suhmo_multi_colour_pass(const suhmo_multi &m, const suhmo_phys_t &ph, bool has_alpha, int pass, hipStream_t st, bool push)
-{
-    if (m.nbox <= 0) return 0;                       // a rank that owns no box of the level
-    dim3 blk(64, 4), grd(((m.maxnx + 1) / 2 + 63) / 64, (m.maxny + 3) / 4, m.nbox);
-    const int2 *pp = push ? (const int2 *)m.push : nullptr;
-    if (has_alpha) hipLaunchKernelGGL(k_gsrb_pass_simple_m<true>, grd, blk, 0, st, m.dv, m.fp, ph, pass, pp, m.pbase);
-    else hipLaunchKernelGGL(k_gsrb_pass_simple_m<false>, grd, blk, 0, st, m.dv, m.fp, ph, pass, pp, m.pbase);
-    HIPCHK(hipGetLastError());
     return 0;
 }
 
@@ -1146,14 +1133,6 @@ __global__ TILE_KERNEL_ATTRS(S, T, false) void k_gsrb_tile_b(BatchTab t, BatchTa
     if (prolong) { const FP fc = batch_fp(c, k); g.pc = fc.f[SUHMO_F_PHI]; g.pco = fc.f[SUHMO_F_PHIOLD]; }
     d_gsrb_tile<S, T, HAS_ALPHA, false, CHUNKED>(v, fp, fp.f[SUHMO_F_PHI], fp.f[SUHMO_F_PHI2], ph, g);
 }
-template <bool HAS_ALPHA>
-__global__ __launch_bounds__(256) void k_gsrb_pass_simple_b(BatchTab t, BatchSel sel, int pass)
-{
-    const int k = batch_member(sel);
-    const DV v = t.dv[k];
-    d_gsrb_pass_simple<HAS_ALPHA>(v, batch_fp(t, k), t.ph[k], pass, 0, v.ny - 1);
-}
-
 static bool tile_ok(const suhmo_level *L, const Depth &D)
 {
     const DV &v = D.v;
@@ -1383,7 +1362,7 @@ int suhmo_launch_gsrb(suhmo_level *L, int depth, int sweeps, int tail, hipStream
                 int E = ext ? (F - 1 < want ? F - 1 : want) : 0;
                 if (L->desc.nx_global > 0) E = 0;                          // AMR patch strips: the coarse-fine ghost columns of halo
                                                                            // rows are not exchanged -> no redundant advance
-                launch_simple(L, depth, pass, E, st);
+                { int rc2 = launch_simple(L, depth, pass, E, st); if (rc2) return rc2; }
                 if (ext) { F = E; D.phi_fresh = F; }
             }
         } else {
@@ -1489,15 +1468,6 @@ int suhmo_batch_gsrb_tile(const BatchTab &t, const BatchTab *coarse, const DV *v
         else if (S == 2) launch_tile_b<2, 16, false>(t, c, sel, g, has_alpha, prolong, st);
         else launch_tile_b<1, 16, false>(t, c, sel, g, has_alpha, prolong, st);
     }
-    HIPCHK(hipGetLastError());
-    return 0;
-}
-int suhmo_batch_colour_pass(const BatchTab &t, const BatchSel &sel, const DV &v, int pass, bool has_alpha, hipStream_t st)
-{
-    if (sel.n <= 0) return 0;
-    const dim3 blk(64, 4), grd(((v.nx + 1) / 2 + 63) / 64, (v.ny + 3) / 4, sel.n);
-    if (has_alpha) hipLaunchKernelGGL(k_gsrb_pass_simple_b<true>, grd, blk, 0, st, t, sel, pass);
-    else hipLaunchKernelGGL(k_gsrb_pass_simple_b<false>, grd, blk, 0, st, t, sel, pass);
     HIPCHK(hipGetLastError());
     return 0;
 }

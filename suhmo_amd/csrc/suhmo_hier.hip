@@ -42,9 +42,9 @@ int hier_gsrb(suhmo_hier *H, int l, int sweeps, suhmo_stream_t s, bool may_swap 
             if (may_swap && Vf.d_fp_alt) {                 // (inside a V-cycle: that canvas becomes the head; vcycle_amr puts things back)
                 swap_head(H, l);
                 if (!bcg && (rc = multi_of(H, l, HST(s), m))) return rc;   // the closing fill below writes the ring of the new head
-            } else if ((rc = suhmo_multi_copy(m, SUHMO_F_PHI, SUHMO_F_PHI2, HST(s)))) return rc;
+            } else if ((rc = launch_copy(m.on(), SUHMO_F_PHI, SUHMO_F_PHI2, HST(s)))) return rc;
         }
-        return bcg ? 0 : suhmo_multi_fill_ghosts(m, SUHMO_F_PHI, 1, HST(s));                                  // :757-759
+        return bcg ? 0 : launch_fill_ghosts(m.on(), SUHMO_F_PHI, 1, HST(s));                                  // :757-759
     }
     // exchange() before every colour pass (:692, :751): once here (unless the side ghosts are current), then every pass pushes
     // its new side cells into the ghost cells they feed
@@ -55,11 +55,11 @@ int hier_gsrb(suhmo_hier *H, int l, int sweeps, suhmo_stream_t s, bool may_swap 
     const bool push = H->push_ghosts && !V.part;
     for (int it = 0; it < sweeps; it++)
         for (int pass = 0; pass < 2; pass++) {
-            if ((rc = suhmo_multi_colour_pass(m, phys_of(H, l), has_alpha(H, l), pass, HST(s), push))) return rc;
+            if ((rc = launch_colour_pass(m.on(), has_alpha(H, l), pass, 0, 0, push ? m.push : nullptr, m.pbase, HST(s)))) return rc;
             H->phi_ver[l]++;
             if (!push && (rc = hier_ff(H, l, SUHMO_F_PHI, -1, false, HST(s), V.part ? pass : -1))) return rc;
         }
-    if (sweeps > 0 && (rc = suhmo_multi_fill_ghosts(m, SUHMO_F_PHI, 1, HST(s)))) return rc;                        // :757-759
+    if (sweeps > 0 && (rc = launch_fill_ghosts(m.on(), SUHMO_F_PHI, 1, HST(s)))) return rc;                        // :757-759
     if (sweeps > 0 && push) H->ff_seen[l] = H->phi_ver[l];          // every pass pushed its side cells: the ghosts are current
     return 0;
 }
@@ -69,7 +69,7 @@ int hier_level_residual(suhmo_hier *H, int l, suhmo_stream_t s)   // residualI: 
     int rc;
     suhmo_multi m;
     if ((rc = hier_ff(H, l, SUHMO_F_PHI, -1, false, HST(s))) || (rc = multi_of(H, l, HST(s), m))) return rc;
-    return suhmo_multi_apply(m, phys_of(H, l), has_alpha(H, l), 1, HST(s));            // (owner computes: m = this rank's boxes)
+    return launch_apply_boxes(m.on(), has_alpha(H, l), 1, HST(s));            // (owner computes: m = this rank's boxes)
 }
 int hier_axby(suhmo_hier *H, int l, int dst, int x, int y, double a, double b, suhmo_stream_t s)
 {
@@ -77,7 +77,7 @@ int hier_axby(suhmo_hier *H, int l, int dst, int x, int y, double a, double b, s
     int rc;
     suhmo_multi m;
     if ((rc = ensure_field(H, l, dst)) || (rc = ensure_field(H, l, x)) || (rc = ensure_field(H, l, y)) || (rc = multi_of(H, l, HST(s), m))) return rc;
-    return suhmo_multi_axby(m, dst, x, y, a, b, HST(s));
+    return launch_axby(m.on(), dst, x, y, a, b, HST(s));
 }
 int hier_copy(suhmo_hier *H, int l, int dst, int src, suhmo_stream_t s)
 {
@@ -93,7 +93,7 @@ int hier_copy(suhmo_hier *H, int l, int dst, int src, suhmo_stream_t s)
     }
     suhmo_multi m;
     if ((rc = multi_of(H, l, HST(s), m))) return rc;
-    return suhmo_multi_copy(m, dst, src, HST(s));
+    return launch_copy(m.on(), dst, src, HST(s));
 }
 // head of level l: its coarse-fine ghosts from level l-1
 int cf_phi(suhmo_hier *H, int l, suhmo_stream_t s)
@@ -164,7 +164,7 @@ int hier_grad_cc(suhmo_hier *H, int l, suhmo_stream_t s)
     suhmo_multi m;
     if ((rc = hier_ff(H, l, SUHMO_F_PHI, -1, false, HST(s)))) return rc;              // UpdateOperator :47
     if ((rc = ensure_field(H, l, SUHMO_F_GRADX)) || (rc = ensure_field(H, l, SUHMO_F_GRADY)) || (rc = ensure_field(H, l, SUHMO_F_RE)) || (rc = multi_of(H, l, HST(s), m))) return rc;
-    return suhmo_multi_grad_cc(m, phys_of(H, l).use_mask_gradients, HST(s));
+    return suhmo_multi_grad_cc(m, HST(s));
 }
 // UpdateOperator of level l >= 1 with its coarser level (src/VCAMRNonLinearPoissonOp.cpp:34-64, src/AmrHydro.cpp:1415-1539)
 int hier_update_operator(suhmo_hier *H, int l, suhmo_stream_t s)
@@ -180,7 +180,7 @@ int hier_update_operator(suhmo_hier *H, int l, suhmo_stream_t s)
         if ((rc = hier_cf_ff(H, l, SUHMO_F_GRADX, SUHMO_F_GRADX, SUHMO_F_GRADY, SUHMO_F_GRADY, true, HST(s)))) return rc;
         suhmo_multi m;
         if ((rc = multi_of(H, l, HST(s), m))) return rc;
-        return suhmo_multi_re_bcoef(m, phys_of(H, l), HST(s));
+        return suhmo_multi_re_bcoef(m, HST(s));
     }
     if ((rc = cf_phi(H, l - 1, s))) return rc;                    // the coarser level's own coarse-fine ghosts (its gradient reads them)
     if ((rc = hier_grad_cc(H, l, s))) return rc;
@@ -197,7 +197,7 @@ int hier_update_operator(suhmo_hier *H, int l, suhmo_stream_t s)
     }
     suhmo_multi m;
     if ((rc = multi_of(H, l, HST(s), m))) return rc;
-    return suhmo_multi_re_bcoef(m, phys_of(H, l), HST(s));
+    return suhmo_multi_re_bcoef(m, HST(s));
 }
 // RES of level l-1 = rhs - [applyOpI(phi) + reflux from level l]; LPHI of level l-1 keeps the plain L(phi)
 // whole_level_follows: called from inside a V-cycle (what follows turns RES of level l-1 into a FAS right-hand side); false: the
@@ -212,7 +212,7 @@ int composite_residual(suhmo_hier *H, int l, suhmo_stream_t s, bool whole_level_
     else {
         suhmo_multi m;
         if ((rc = hier_ff(H, l - 1, SUHMO_F_PHI, -1, false, HST(s))) || (rc = ensure_field(H, l - 1, SUHMO_F_LPHI)) || (rc = multi_of(H, l - 1, HST(s), m))) return rc;
-        rc = suhmo_multi_apply(m, phys_of(H, l - 1), has_alpha(H, l - 1), 3, HST(s));
+        rc = launch_apply_boxes(m.on(), has_alpha(H, l - 1), 3, HST(s));
     }
     if (rc) return rc;
     if ((rc = cf_phi(H, l, s))) return rc;
@@ -248,7 +248,7 @@ int vcycle_amr(suhmo_hier *H, int l, const suhmo_solver_params_t *sp, suhmo_stre
         // (copy RHS0 <- RHS, axby RHS <- RES + LPHI, copy PHIOLD <- PHI: the same expressions on the same operands)
         suhmo_multi mc;
         for (int f : {SUHMO_F_RHS0, SUHMO_F_PHIOLD, SUHMO_F_LPHI}) if ((rc = ensure_field(H, l - 1, f))) return rc;
-        if ((rc = multi_of(H, l - 1, HST(s), mc)) || (rc = suhmo_multi_fas_enter(mc, HST(s)))) return rc;
+        if ((rc = multi_of(H, l - 1, HST(s), mc)) || (rc = launch_fas_enter(mc.on(), HST(s)))) return rc;
     }
     if (l - 1 == 0) {
         // level 0's own V-cycle runs against the FAS right-hand side; its last launch is asked to leave L(phi) and TRUE rhs - L(phi) behind
@@ -266,7 +266,7 @@ int vcycle_amr(suhmo_hier *H, int l, const suhmo_solver_params_t *sp, suhmo_stre
         if (H->merged_launches) rc = hier_prolong2(H, l, SUHMO_F_PHI, HST(s), false, true);      // leaving and prolongation in one launch
         else {
             suhmo_multi mc;
-            if ((rc = multi_of(H, l - 1, HST(s), mc)) || (rc = suhmo_multi_fas_leave(mc, HST(s)))) return rc;
+            if ((rc = multi_of(H, l - 1, HST(s), mc)) || (rc = launch_fas_leave(mc.on(), HST(s)))) return rc;
             rc = hier_prolong2(H, l, SUHMO_F_CORR, HST(s));
         }
     }
@@ -275,7 +275,7 @@ int vcycle_amr(suhmo_hier *H, int l, const suhmo_solver_params_t *sp, suhmo_stre
     if ((rc = hier_gsrb(H, l, sp->num_smooth, s, true))) return rc;
     if (H->lev[l].swapped) {                               // (an odd number of odd relaxations: the head goes back to its own canvas by a copy after all)
         suhmo_multi m;
-        if ((rc = multi_of(H, l, HST(s), m)) || (rc = suhmo_multi_copy(m, SUHMO_F_PHI2, SUHMO_F_PHI, HST(s)))) return rc;
+        if ((rc = multi_of(H, l, HST(s), m)) || (rc = launch_copy(m.on(), SUHMO_F_PHI2, SUHMO_F_PHI, HST(s)))) return rc;
         swap_head(H, l);
     }
     return 0;
@@ -292,7 +292,7 @@ int check_hier(suhmo_hier *H)
             int rc;
             HIPCHK(hipSetDevice(H->device));
             HIPCHK(hipDeviceSynchronize());
-            if ((rc = multi_of(H, l, nullptr, m)) || (rc = suhmo_multi_copy(m, SUHMO_F_PHI2, SUHMO_F_PHI, nullptr))) return rc;
+            if ((rc = multi_of(H, l, nullptr, m)) || (rc = launch_copy(m.on(), SUHMO_F_PHI2, SUHMO_F_PHI, nullptr))) return rc;
             HIPCHK(hipDeviceSynchronize());
             swap_head(H, l);
         }
@@ -770,7 +770,7 @@ extern "C" int suhmo_hier_solve(suhmo_hier_t *H, const suhmo_solver_params_t *sp
     if ((rc = suhmo_level_fill_ghosts(base_of(H), 0, SUHMO_F_PHI, 0, s))) return rc;
     for (int l = 1; l < H->nlev; l++) {
         suhmo_multi m;
-        if ((rc = multi_of(H, l, HST(s), m)) || (rc = suhmo_multi_fill_ghosts(m, SUHMO_F_PHI, 0, HST(s)))) return rc;
+        if ((rc = multi_of(H, l, HST(s), m)) || (rc = launch_fill_ghosts(m.on(), SUHMO_F_PHI, 0, HST(s)))) return rc;
     }
     return 0;
 }

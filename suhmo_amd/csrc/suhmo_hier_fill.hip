@@ -224,7 +224,7 @@ __global__ void k_prolong2_win(const Win *__restrict__ wins, const double *__res
 // window, PROLONG_2_NL) with the window in LDS instead of three launches over a buffer in HBM; the same expressions on the same operands.
 // wstart[k] .. wstart[k + 1]: the gather pieces of box k.  old != NULL: the window gets c - old (see k_win_gather)
 // fc_minus >= 0: the coarse field is 1 fc + (-1) fc_minus formed on the fly (the correction PHI - PHIOLD of a level of boxes leaving its FAS problem),
-// and the workgroups from nk on ARE that leaving (k_fas_leave_m's RHS <- RHS0, CORR <- PHI - PHIOLD on the coarse level's boxes: they write
+// and the workgroups from nk on ARE that leaving (k_fas_leave's RHS <- RHS0, CORR <- PHI - PHIOLD on the coarse level's boxes: they write
 // neither PHI nor PHIOLD): one launch instead of two
 __global__ __launch_bounds__(256) void k_prolong2_fused(const WinEnt *__restrict__ e, const int *__restrict__ wstart, const Win *__restrict__ wins, int k0,
                                                         const FP *__restrict__ ctab, const DV *__restrict__ cdv, FP cbase, DV cbdv, int use_base, int fc,
@@ -687,7 +687,7 @@ int hier_prolong2(suhmo_hier *H, int l, int field_c, hipStream_t st, bool minus_
     CoarseArgs ca;
     if (leave_below && !(H->fused_prolong && V.win_max <= 6144 && !V.part && !H->lev[l - 1].part && l - 1 >= 1)) {     // two launches after all
         suhmo_multi mc;
-        if ((rc = multi_of(H, l - 1, st, mc)) || (rc = suhmo_multi_fas_leave(mc, st))) return rc;
+        if ((rc = multi_of(H, l - 1, st, mc)) || (rc = launch_fas_leave(mc.on(), st))) return rc;
         return hier_prolong2(H, l, SUHMO_F_CORR, st);
     }
     if ((rc = ensure_field(H, l - 1, field_c)) || (rc = refresh_tables(H, l, st))) return rc;

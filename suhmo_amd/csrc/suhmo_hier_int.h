@@ -249,7 +249,7 @@ inline int multi_of(suhmo_hier *H, int l, hipStream_t st, suhmo_multi &m)
     int rc = refresh_tables(H, l, st); if (rc) return rc;
     HLev &V = H->lev[l];
     m.dv = V.d_dv; m.fp = V.d_fp; m.nbox = (int)V.box.size(); m.maxnx = V.maxnx; m.maxny = V.maxny; m.red = V.d_red;
-    m.push = V.push.d; m.pbase = V.pbase.d; m.merged = H->merged_launches;
+    m.push = V.push.d; m.pbase = V.pbase.d; m.merged = H->merged_launches; m.ph = V.box[0]->ph;
     if (V.part) { m.dv += V.b0; m.fp += V.b0; m.nbox = V.nown; m.push = nullptr; m.pbase = nullptr; }   // owner computes: the tables from this rank's first box
     return 0;
 }

@@ -32,26 +32,17 @@ __device__ __forceinline__ void d_fill_ghosts(const DV &v, double *__restrict__ 
         if (side) p[idx + v.P] = phiN(v, p, idx, j, c, homog); else p[idx - v.P] = phiS(v, p, idx, j, c, homog);
     }
 }
-__global__ void k_fill_ghosts(DV v, double *__restrict__ p, int homog)
-{
-    d_fill_ghosts(v, p, homog);
-}
-// every box of a multi-box AMR level in one launch (blockIdx.z = box; suhmo_hier.hip)
-__global__ void k_fill_ghosts_m(const DV *__restrict__ vt, const FP *__restrict__ ft, int field, int homog)
-{
-    d_fill_ghosts(vt[blockIdx.z], ft[blockIdx.z].f[field], homog);
-}
+template <class T> __global__ void k_fill_ghosts(T t, int field, int homog) { d_fill_ghosts(t.view(), t.field(field), homog); }
+template <class T> int launch_fill_ghosts(const T &t, int field, int homog, hipStream_t st) { return launch_over(k_fill_ghosts<T>, t, PERIMETER, st, field, homog); }
+template int launch_fill_ghosts(const OnBoxes &, int, int, hipStream_t);
+template int launch_fill_ghosts(const OnMembers &, int, int, hipStream_t);
 
 extern "C" int suhmo_level_fill_ghosts(suhmo_level_t *L, int depth, int field, int homogeneous, suhmo_stream_t s)
 {
     CHECK_DF(L, depth, field); ARG(!is_face(field));
     HIPCHK(hipSetDevice(L->device));
-    const DV &v = L->d[depth].v;
-    double *p = suhmo_field(L, depth, field);
-    int n = 2 * v.ny + 2 * v.nx;
-    hipLaunchKernelGGL(k_fill_ghosts, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)s, v, p, homogeneous);
-    HIPCHK(hipGetLastError());
-    return 0;
+    if (!suhmo_field(L, depth, field)) return -2;
+    return launch_fill_ghosts(on_level(L, depth), field, homogeneous, (hipStream_t)s);
 }
 
 // VCNLCOMPUTEOP2D / VCNLCOMPUTERES2D with BC, NL fused.  MODE 0: LPHI = L(phi); 1: RES = rhs - L(phi);
@@ -97,10 +88,17 @@ __device__ __forceinline__ void d_apply(const DV &v, const FP &fp, suhmo_phys_t 
     const int j = (int)(blockIdx.y * blockDim.y + threadIdx.y) - halo;     // MODE 2 on a rank strip: the halo rows only copy phi
     d_apply_at<HAS_ALPHA, MODE>(v, fp, ph, homog, halo, hcomp, i, j);
 }
-template <bool HAS_ALPHA, int MODE>
-__global__ __launch_bounds__(256) void k_apply(DV v, FP fp, suhmo_phys_t ph, int homog, int halo = 0, int hcomp = 0)
+template <class T, bool HAS_ALPHA, int MODE>
+__global__ __launch_bounds__(256) void k_apply(T t, int homog, int halo, int hcomp)
 {
-    d_apply<HAS_ALPHA, MODE>(v, fp, ph, homog, halo, hcomp);
+    d_apply<HAS_ALPHA, MODE>(t.view(), t.fields(), t.phys(), homog, halo, hcomp);
+}
+// the operator over the cells of a target and `halo` rows beyond both y sides (MODE 2 on a rank strip)
+template <int MODE, class T> static int launch_apply(const T &t, bool has_alpha, int homog, hipStream_t st, int halo = 0, int hcomp = 0)
+{
+    const dim3 grd = grid2d(t.nx(), t.ny() + 2 * halo);
+    if (has_alpha) return launch_grid(k_apply<T, true, MODE>, t, grd, BLK2D, st, homog, halo, hcomp);
+    return launch_grid(k_apply<T, false, MODE>, t, grd, BLK2D, st, homog, halo, hcomp);
 }
 // RES = rhs - L(phi) and, in the same pass, the first stage of its max norm (one partial per workgroup, as k_norm_partial leaves them for
 // k_norm_final): the solve loop's residual evaluation on levels whose cycle's last launch cannot leave it behind (the tile-kernel sizes)
@@ -116,28 +114,16 @@ __device__ __forceinline__ void d_residual_norm(const DV &v, const FP &fp, const
     __syncthreads();
     if (threadIdx.x == 0 && threadIdx.y == 0) partial[blockIdx.y * gridDim.x + blockIdx.x] = fmax(fmax(sm[0], sm[1]), fmax(sm[2], sm[3]));
 }
-template <bool HAS_ALPHA>
-__global__ __launch_bounds__(256) void k_residual_norm(DV v, FP fp, suhmo_phys_t ph, double *__restrict__ partial)
+// (a member of an ensemble: its partial maxima at partial + member * workgroups, in the order of a level's own launch)
+template <class T, bool HAS_ALPHA>
+__global__ __launch_bounds__(256) void k_residual_norm(T t, double *__restrict__ partial)
 {
-    d_residual_norm<HAS_ALPHA>(v, fp, ph, partial);
+    d_residual_norm<HAS_ALPHA>(t.view(), t.fields(), t.phys(), partial + t.slot((size_t)gridDim.x * gridDim.y));
 }
-// every active member of a batch (suhmo_batch.h): member k's partial maxima at partial + k * workgroups, in the solo kernel's order
-template <bool HAS_ALPHA>
-__global__ __launch_bounds__(256) void k_residual_norm_b(BatchTab t, BatchSel sel, double *__restrict__ partial)
+template <class T> static int launch_residual_norm(const T &t, bool has_alpha, double *partial, hipStream_t st)
 {
-    const int k = batch_member(sel);
-    d_residual_norm<HAS_ALPHA>(t.dv[k], batch_fp(t, k), t.ph[k], partial + (size_t)k * gridDim.x * gridDim.y);
-}
-template <bool HAS_ALPHA, int MODE>
-__global__ __launch_bounds__(256) void k_apply_b(BatchTab t, BatchSel sel, int homog)
-{
-    const int k = batch_member(sel);
-    d_apply<HAS_ALPHA, MODE>(t.dv[k], batch_fp(t, k), t.ph[k], homog, 0, 0);
-}
-__global__ void k_fill_ghosts_b(BatchTab t, BatchSel sel, int field, int homog)
-{
-    const int k = batch_member(sel);
-    d_fill_ghosts(t.dv[k], batch_fp(t, k).f[field], homog);
+    if (has_alpha) return launch_over(k_residual_norm<T, true>, t, CELLS, st, partial);
+    return launch_over(k_residual_norm<T, false>, t, CELLS, st, partial);
 }
 // LPHI and RES = rhs - LPHI on a list of rectangles (x = first column, y = first row, z = columns, w = rows) of the level: the part of
 // a composite residual that has changed since the whole level was evaluated (suhmo_hier.hip); overlapping rectangles write the same values
@@ -148,12 +134,6 @@ __global__ __launch_bounds__(256) void k_apply_rects(DV v, FP fp, suhmo_phys_t p
     const int a = blockIdx.x * blockDim.x + threadIdx.x, b = blockIdx.y * blockDim.y + threadIdx.y;
     if (a >= r.z || b >= r.w) return;
     d_apply_at<HAS_ALPHA, 3>(v, fp, ph, 0, 0, 0, r.x + a, r.y + b);
-}
-// every box of a multi-box AMR level in one launch (blockIdx.z = box; suhmo_hier.hip)
-template <bool HAS_ALPHA, int MODE>
-__global__ __launch_bounds__(256) void k_apply_m(const DV *__restrict__ vt, const FP *__restrict__ ft, suhmo_phys_t ph, int homog)
-{
-    d_apply<HAS_ALPHA, MODE>(vt[blockIdx.z], ft[blockIdx.z], ph, homog, 0, 0);
 }
 
 // the box of blockIdx.z among the boxes of several levels: its level's slot q (unrolled: constant indices only), its index in that level
@@ -227,10 +207,7 @@ extern "C" int suhmo_level_apply_op(suhmo_level_t *L, int depth, int homogeneous
     Depth &D = L->d[depth];
     if (!suhmo_field(L, depth, SUHMO_F_LPHI)) return -2;
     int rc = suhmo_ensure_phi_halo(L, depth, 1, (hipStream_t)s); if (rc) return rc;
-    if (D.v.alpha != 0.0) hipLaunchKernelGGL((k_apply<true, 0>), grid2d(D.v.nx, D.v.ny), BLK2D, 0, (hipStream_t)s, D.v, D.fp, L->ph, homogeneous);
-    else hipLaunchKernelGGL((k_apply<false, 0>), grid2d(D.v.nx, D.v.ny), BLK2D, 0, (hipStream_t)s, D.v, D.fp, L->ph, homogeneous);
-    HIPCHK(hipGetLastError());
-    return 0;
+    return launch_apply<0>(on_level(L, depth), D.v.alpha != 0.0, homogeneous, (hipStream_t)s);
 }
 
 // applyOpI (inhomogeneous) and the residual of it in one pass: LPHI = L(phi), RES = rhs - L(phi)
@@ -240,10 +217,7 @@ int suhmo_apply_and_residual(suhmo_level *L, int depth, hipStream_t st)
     Depth &D = L->d[depth];
     if (!suhmo_field(L, depth, SUHMO_F_LPHI) || !suhmo_field(L, depth, SUHMO_F_RES)) return -2;
     int rc = suhmo_ensure_phi_halo(L, depth, 1, st); if (rc) return rc;
-    if (D.v.alpha != 0.0) hipLaunchKernelGGL((k_apply<true, 3>), grid2d(D.v.nx, D.v.ny), BLK2D, 0, st, D.v, D.fp, L->ph, 0);
-    else hipLaunchKernelGGL((k_apply<false, 3>), grid2d(D.v.nx, D.v.ny), BLK2D, 0, st, D.v, D.fp, L->ph, 0);
-    HIPCHK(hipGetLastError());
-    return 0;
+    return launch_apply<3>(on_level(L, depth), D.v.alpha != 0.0, 0, st);
 }
 
 int suhmo_apply_and_residual_rects(suhmo_level *L, int depth, const int4 *d_rects, int n, int maxw, int maxh, hipStream_t st)
@@ -267,10 +241,7 @@ int suhmo_fas_coarse_rhs(suhmo_level *L, int depth, hipStream_t st, int hcomp)
     Depth &D = L->d[depth];
     if (!suhmo_field(L, depth, SUHMO_F_LPHI) || !suhmo_field(L, depth, SUHMO_F_PHIOLD)) return -2;
     const int halo = (D.v.ext[0] || D.v.ext[1]) ? D.v.gy : 0;
-    if (D.v.alpha != 0.0) hipLaunchKernelGGL((k_apply<true, 2>), grid2d(D.v.nx, D.v.ny + 2 * halo), BLK2D, 0, st, D.v, D.fp, L->ph, 0, halo, hcomp);
-    else hipLaunchKernelGGL((k_apply<false, 2>), grid2d(D.v.nx, D.v.ny + 2 * halo), BLK2D, 0, st, D.v, D.fp, L->ph, 0, halo, hcomp);
-    HIPCHK(hipGetLastError());
-    return 0;
+    return launch_apply<2>(on_level(L, depth), D.v.alpha != 0.0, 0, st, halo, hcomp);
 }
 
 extern "C" int suhmo_level_residual(suhmo_level_t *L, int depth, suhmo_stream_t s)
@@ -280,10 +251,7 @@ extern "C" int suhmo_level_residual(suhmo_level_t *L, int depth, suhmo_stream_t 
     HIPCHK(hipSetDevice(L->device));
     Depth &D = L->d[depth];
     int rc = suhmo_ensure_phi_halo(L, depth, 1, (hipStream_t)s); if (rc) return rc;
-    if (D.v.alpha != 0.0) hipLaunchKernelGGL((k_apply<true, 1>), grid2d(D.v.nx, D.v.ny), BLK2D, 0, (hipStream_t)s, D.v, D.fp, L->ph, 0);
-    else hipLaunchKernelGGL((k_apply<false, 1>), grid2d(D.v.nx, D.v.ny), BLK2D, 0, (hipStream_t)s, D.v, D.fp, L->ph, 0);
-    HIPCHK(hipGetLastError());
-    return 0;
+    return launch_apply<1>(on_level(L, depth), D.v.alpha != 0.0, 0, (hipStream_t)s);
 }
 
 // COMPUTENONLINEARTERMS / lambda as stand-alone kernels (parity of a2, a9)
@@ -390,29 +358,24 @@ __device__ __forceinline__ void d_restrict_residual(const DV &v, const FP &fp, c
     resC[cidx(vc, I, J)] = acc;
     if (phiC) phiC[cidx(vc, I, J)] = accp;
 }
-template <bool HAS_ALPHA>
-__global__ __launch_bounds__(256) void k_restrict_residual(DV v, FP fp, DV vc, double *__restrict__ resC, double *__restrict__ phiC, suhmo_phys_t ph)
+template <class T, bool HAS_ALPHA>
+__global__ __launch_bounds__(256) void k_restrict_residual(T c, T f, int also_phi)      // RES (and PHI) of the coarse depth c
 {
-    d_restrict_residual<HAS_ALPHA>(v, fp, vc, resC, phiC, ph);
+    const FP &fc = c.fields();
+    d_restrict_residual<HAS_ALPHA>(f.view(), f.fields(), c.view(), fc.f[SUHMO_F_RES], also_phi ? fc.f[SUHMO_F_PHI] : nullptr, f.phys());
 }
-template <bool HAS_ALPHA>
-__global__ __launch_bounds__(256) void k_restrict_residual_b(BatchTab f, BatchTab c, BatchSel sel)      // RES and PHI of the coarse depth
+template <class T> int launch_restrict(const T &f, const T &c, bool also_phi, bool has_alpha, hipStream_t st)
 {
-    const int k = batch_member(sel);
-    const FP fc = batch_fp(c, k);
-    d_restrict_residual<HAS_ALPHA>(f.dv[k], batch_fp(f, k), c.dv[k], fc.f[SUHMO_F_RES], fc.f[SUHMO_F_PHI], f.ph[k]);
+    if (has_alpha) return launch_over(k_restrict_residual<T, true>, c, CELLS, st, f, (int)also_phi);
+    return launch_over(k_restrict_residual<T, false>, c, CELLS, st, f, (int)also_phi);
 }
+template int launch_restrict(const OnMembers &, const OnMembers &, bool, bool, hipStream_t);
 
 static int restrict_residual_impl(suhmo_level *L, int depth, bool also_phi, hipStream_t st)
 {
-    Depth &D = L->d[depth], &C = L->d[depth + 1];
     int rc = suhmo_ensure_phi_halo(L, depth, 1, st); if (rc) return rc;
     if (also_phi) phi_changed(L, depth + 1);
-    double *phiC = also_phi ? C.fp.f[SUHMO_F_PHI] : nullptr;
-    if (D.v.alpha != 0.0) hipLaunchKernelGGL(k_restrict_residual<true>, grid2d(C.v.nx, C.v.ny), BLK2D, 0, st, D.v, D.fp, C.v, C.fp.f[SUHMO_F_RES], phiC, L->ph);
-    else hipLaunchKernelGGL(k_restrict_residual<false>, grid2d(C.v.nx, C.v.ny), BLK2D, 0, st, D.v, D.fp, C.v, C.fp.f[SUHMO_F_RES], phiC, L->ph);
-    HIPCHK(hipGetLastError());
-    return 0;
+    return launch_restrict(on_level(L, depth), on_level(L, depth + 1), also_phi, L->d[depth].v.alpha != 0.0, st);
 }
 extern "C" int suhmo_level_restrict_residual(suhmo_level_t *L, int depth, suhmo_stream_t s)
 {
@@ -485,28 +448,24 @@ __device__ __forceinline__ void d_prolong_rows(const DV &v, double *__restrict__
     int idx = cidx(v, i, j);
     phi[idx] = phi[idx] + c[cidx(vc, i / 2, j >> 1)];          // j >> 1: floor, halo rows have j < 0
 }
-__global__ void k_axby_rows(DV v, double *__restrict__ dst, const double *__restrict__ x, const double *__restrict__ y, double a, double b, int jlo, int jhi)
+// rows [-lo, ny - 1 + hi] of the target (lo, hi: halo rows below / above)
+template <class T> __global__ void k_axby_rows(T t, int fd, int fx, int fy, double a, double b, int lo, int hi)
 {
-    d_axby_rows(v, dst, x, y, a, b, jlo, jhi);
+    const DV v = t.view();
+    d_axby_rows(v, t.field(fd), t.field(fx), t.field(fy), a, b, -lo, v.ny - 1 + hi);
 }
-__global__ void k_prolong_rows(DV v, double *__restrict__ phi, DV vc, const double *__restrict__ c, int jlo, int jhi)
+template <class T> __global__ void k_prolong_rows(T f, T c, int lo, int hi)
 {
-    d_prolong_rows(v, phi, vc, c, jlo, jhi);
+    const DV v = f.view();
+    d_prolong_rows(v, f.fields().f[SUHMO_F_PHI], c.view(), c.fields().f[SUHMO_F_CORR], -lo, v.ny - 1 + hi);
 }
-// every active member of a batch (suhmo_batch.h)
-__global__ void k_axby_rows_b(BatchTab t, BatchSel sel, int fd, int fx, int fy, double a, double b)
+// CORR_c = phi_c - phi_c,old over lo_c / hi_c halo rows, phi += P(CORR_c) over lo / hi
+template <class T> int launch_prolong(const T &f, const T &c, int lo, int hi, int lo_c, int hi_c, hipStream_t st)
 {
-    const int k = batch_member(sel);
-    const DV v = t.dv[k];
-    const FP fp = batch_fp(t, k);
-    d_axby_rows(v, fp.f[fd], fp.f[fx], fp.f[fy], a, b, 0, v.ny - 1);
+    int rc = launch_grid(k_axby_rows<T>, c, grid2d(c.nx(), c.ny() + lo_c + hi_c), BLK2D, st, (int)SUHMO_F_CORR, (int)SUHMO_F_PHI, (int)SUHMO_F_PHIOLD, 1.0, -1.0, lo_c, hi_c);
+    return rc ? rc : launch_grid(k_prolong_rows<T>, f, grid2d(f.nx(), f.ny() + lo + hi), BLK2D, st, c, lo, hi);
 }
-__global__ void k_prolong_rows_b(BatchTab f, BatchTab c, BatchSel sel)
-{
-    const int k = batch_member(sel);
-    const DV v = f.dv[k];
-    d_prolong_rows(v, batch_fp(f, k).f[SUHMO_F_PHI], c.dv[k], batch_fp(c, k).f[SUHMO_F_CORR], 0, v.ny - 1);
-}
+template int launch_prolong(const OnMembers &, const OnMembers &, int, int, int, int, hipStream_t);
 int suhmo_prolong_with_halo(suhmo_level *L, int depth, hipStream_t st)
 {
     Depth &D = L->d[depth], &C = L->d[depth + 1];
@@ -516,11 +475,9 @@ int suhmo_prolong_with_halo(suhmo_level *L, int depth, hipStream_t st)
     const int Rc = R / 2;
     const int jlo = D.v.ext[0] ? -R : 0, jhi = D.v.ny - 1 + (D.v.ext[1] ? R : 0);
     const int cjlo = C.v.ext[0] ? -Rc : 0, cjhi = C.v.ny - 1 + (C.v.ext[1] ? Rc : 0);
-    double *corr = suhmo_field(L, depth + 1, SUHMO_F_CORR);
-    if (!corr) return -2;
-    hipLaunchKernelGGL(k_axby_rows, grid2d(C.v.nx, cjhi - cjlo + 1), BLK2D, 0, st, C.v, corr, C.fp.f[SUHMO_F_PHI], C.fp.f[SUHMO_F_PHIOLD], 1.0, -1.0, cjlo, cjhi);
-    hipLaunchKernelGGL(k_prolong_rows, grid2d(D.v.nx, jhi - jlo + 1), BLK2D, 0, st, D.v, D.fp.f[SUHMO_F_PHI], C.v, corr, jlo, jhi);
-    HIPCHK(hipGetLastError());
+    if (!suhmo_field(L, depth + 1, SUHMO_F_CORR)) return -2;
+    int rc = launch_prolong(on_level(L, depth), on_level(L, depth + 1), -jlo, jhi - (D.v.ny - 1), -cjlo, cjhi - (C.v.ny - 1), st);
+    if (rc) return rc;
     D.phi_fresh = R;
     return 0;
 }
@@ -610,15 +567,12 @@ __device__ __forceinline__ void d_axby(const DV &v, double *__restrict__ dst, co
     int idx = cidx(v, i, j);
     dst[idx] = a * x[idx] + b * y[idx];
 }
-__global__ void k_axby(DV v, double *__restrict__ dst, const double *__restrict__ x, const double *__restrict__ y, double a, double b)
+template <class T> __global__ void k_axby(T t, int fd, int fx, int fy, double a, double b)
 {
-    d_axby(v, dst, x, y, a, b);
+    d_axby(t.view(), t.field(fd), t.field(fx), t.field(fy), a, b);
 }
-// every box of a multi-box AMR level in one launch (blockIdx.z = box; suhmo_hier.hip)
-__global__ void k_axby_m(const DV *__restrict__ vt, const FP *__restrict__ ft, int fd, int fx, int fy, double a, double b)
-{
-    d_axby(vt[blockIdx.z], ft[blockIdx.z].f[fd], ft[blockIdx.z].f[fx], ft[blockIdx.z].f[fy], a, b);
-}
+template <class T> int launch_axby(const T &t, int fd, int fx, int fy, double a, double b, hipStream_t st) { return launch_over(k_axby<T>, t, CELLS, st, fd, fx, fy, a, b); }
+template int launch_axby(const OnBoxes &, int, int, int, double, double, hipStream_t);
 __global__ void k_setval(DV v, double *__restrict__ dst, double val)
 {
     int i = blockIdx.x * blockDim.x + threadIdx.x, j = blockIdx.y * blockDim.y + threadIdx.y;
@@ -629,13 +583,10 @@ extern "C" int suhmo_level_axby(suhmo_level_t *L, int depth, int dst, int x, int
 {
     CHECK_DF(L, depth, dst); CHECK_DF(L, depth, x); CHECK_DF(L, depth, y);
     HIPCHK(hipSetDevice(L->device));
-    Depth &D = L->d[depth];
-    double *pd = suhmo_field(L, depth, dst), *px = suhmo_field(L, depth, x), *py = suhmo_field(L, depth, y);
+    if (!suhmo_field(L, depth, dst) || !suhmo_field(L, depth, x) || !suhmo_field(L, depth, y)) return -2;
     if (dst == SUHMO_F_PHI) phi_changed(L, depth);
     if (dst == SUHMO_F_MASK) { L->coarse_mask_ok = 0; L->maskflag_epoch = 0; }      // (the reports about the ice mask end with any write to it)
-    hipLaunchKernelGGL(k_axby, grid2d(D.v.nx, D.v.ny), BLK2D, 0, (hipStream_t)s, D.v, pd, px, py, a, b);
-    HIPCHK(hipGetLastError());
-    return 0;
+    return launch_axby(on_level(L, depth), dst, x, y, a, b, (hipStream_t)s);
 }
 extern "C" int suhmo_level_set_value(suhmo_level_t *L, int depth, int field, double val, suhmo_stream_t s)
 {
@@ -804,9 +755,7 @@ int suhmo_level_residual_and_norm(suhmo_level *L, double *out, hipStream_t st)
         return suhmo_level_norm(L, 0, SUHMO_F_RES, 0, out, (suhmo_stream_t)st);
     }
     if ((rc = suhmo_ensure_phi_halo(L, 0, 1, st))) return rc;
-    if (D.v.alpha != 0.0) hipLaunchKernelGGL(k_residual_norm<true>, grd, BLK2D, 0, st, D.v, D.fp, L->ph, L->scratch + 2);
-    else hipLaunchKernelGGL(k_residual_norm<false>, grd, BLK2D, 0, st, D.v, D.fp, L->ph, L->scratch + 2);
-    HIPCHK(hipGetLastError());
+    if ((rc = launch_residual_norm(on_level(L, 0), D.v.alpha != 0.0, L->scratch + 2, st))) return rc;
     return suhmo_level_norm_from_partials(L, (int)np, out, st);
 }
 // max norm of RES at depth 0 from the partial maxima the cycle's last launch left behind (suhmo_gsrb.hip, residual output): the second
@@ -821,21 +770,22 @@ int suhmo_level_norm_from_partials(suhmo_level *L, int np, double *out, hipStrea
 }
 
 // ------------------------------------------------------------------ every box of a multi-box AMR level in one launch
-__global__ void k_copy_m(const DV *__restrict__ vt, const FP *__restrict__ ft, int fd, int fs)
+__global__ void k_copy(OnBoxes t, int fd, int fs)
 {
-    const DV &v = vt[blockIdx.z];
+    const DV &v = t.view();
+    const FP &f = t.fields();
     int i = (int)(blockIdx.x * blockDim.x + threadIdx.x) - 1, j = (int)(blockIdx.y * blockDim.y + threadIdx.y) - 1;
     if (i > v.nx || j > v.ny) return;
     int idx = cidx(v, i, j);
-    ft[blockIdx.z].f[fd][idx] = ft[blockIdx.z].f[fs][idx];
+    f.f[fd][idx] = f.f[fs][idx];
 }
 // A level of boxes entering / leaving its FAS problem in an AMR V-cycle (suhmo_hier.hip:vcycle_amr), one launch each instead of three / two:
 //   enter: RHS0 <- RHS (copy, ghost ring included), RHS <- 1 RES + 1 LPHI (axby, valid cells), PHIOLD <- PHI (copy)
-//   leave: RHS <- RHS0 (copy), CORR <- 1 PHI + (-1) PHIOLD (axby)               -- the expressions of k_copy_m / k_axby_m on the same operands
-__global__ void k_fas_enter_m(const DV *__restrict__ vt, const FP *__restrict__ ft)
+//   leave: RHS <- RHS0 (copy), CORR <- 1 PHI + (-1) PHIOLD (axby)               -- the expressions of k_copy / k_axby on the same operands
+__global__ void k_fas_enter(OnBoxes t)
 {
-    const DV &v = vt[blockIdx.z];
-    const FP &f = ft[blockIdx.z];
+    const DV &v = t.view();
+    const FP &f = t.fields();
     int i = (int)(blockIdx.x * blockDim.x + threadIdx.x) - 1, j = (int)(blockIdx.y * blockDim.y + threadIdx.y) - 1;
     if (i > v.nx || j > v.ny) return;
     int idx = cidx(v, i, j);
@@ -843,10 +793,10 @@ __global__ void k_fas_enter_m(const DV *__restrict__ vt, const FP *__restrict__ 
     f.f[SUHMO_F_PHIOLD][idx] = f.f[SUHMO_F_PHI][idx];
     if (i >= 0 && i < v.nx && j >= 0 && j < v.ny) f.f[SUHMO_F_RHS][idx] = 1.0 * f.f[SUHMO_F_RES][idx] + 1.0 * f.f[SUHMO_F_LPHI][idx];
 }
-__global__ void k_fas_leave_m(const DV *__restrict__ vt, const FP *__restrict__ ft)
+__global__ void k_fas_leave(OnBoxes t)
 {
-    const DV &v = vt[blockIdx.z];
-    const FP &f = ft[blockIdx.z];
+    const DV &v = t.view();
+    const FP &f = t.fields();
     int i = (int)(blockIdx.x * blockDim.x + threadIdx.x) - 1, j = (int)(blockIdx.y * blockDim.y + threadIdx.y) - 1;
     if (i > v.nx || j > v.ny) return;
     int idx = cidx(v, i, j);
@@ -855,19 +805,20 @@ __global__ void k_fas_leave_m(const DV *__restrict__ vt, const FP *__restrict__ 
 }
 // fields of the boxes of one hierarchy <- fields of the same boxes of another (the implicit gap-height operator's copy of a level)
 struct CopyPairs { int n, fd[4], fs[4]; };
-__global__ void k_copy_between_m(const DV *__restrict__ vt, const FP *__restrict__ fdst, const FP *__restrict__ fsrc, CopyPairs cp)
+__global__ void k_copy_between(OnBoxes src, OnBoxes dst, CopyPairs cp)
 {
-    const DV &v = vt[blockIdx.z];
+    const DV &v = src.view();
+    const FP &fs = src.fields(), &fd = dst.fields();
     int i = (int)(blockIdx.x * blockDim.x + threadIdx.x) - 1, j = (int)(blockIdx.y * blockDim.y + threadIdx.y) - 1;
     if (i > v.nx || j > v.ny) return;
     int idx = cidx(v, i, j);
-    for (int q = 0; q < cp.n; q++) fdst[blockIdx.z].f[cp.fd[q]][idx] = fsrc[blockIdx.z].f[cp.fs[q]][idx];
+    for (int q = 0; q < cp.n; q++) fd.f[cp.fd[q]][idx] = fs.f[cp.fs[q]][idx];
 }
-__global__ __launch_bounds__(256) void k_norm_max_partial_m(const DV *__restrict__ vt, const FP *__restrict__ ft, int field, double *__restrict__ partial)
+__global__ __launch_bounds__(256) void k_norm_max_partial(OnBoxes t, int field, double *__restrict__ partial)
 {
     __shared__ double sm[256];
-    const DV &v = vt[blockIdx.z];
-    const double *__restrict__ x = ft[blockIdx.z].f[field];
+    const DV &v = t.view();
+    const double *__restrict__ x = t.fields().f[field];
     int tid = threadIdx.y * blockDim.x + threadIdx.x;
     double acc = 0.0;
     for (int j = blockIdx.y * blockDim.y + threadIdx.y; j < v.ny; j += gridDim.y * blockDim.y)
@@ -875,66 +826,23 @@ __global__ __launch_bounds__(256) void k_norm_max_partial_m(const DV *__restrict
     sm[tid] = acc;
     __syncthreads();
     for (int s = 128; s > 0; s >>= 1) { if (tid < s) sm[tid] = fmax(sm[tid], sm[tid + s]); __syncthreads(); }
-    if (tid == 0) partial[(blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x] = sm[0];
+    if (tid == 0) partial[t.slot((size_t)gridDim.x * gridDim.y) + blockIdx.y * gridDim.x + blockIdx.x] = sm[0];
 }
-int suhmo_multi_fill_ghosts(const suhmo_multi &m, int field, int homog, hipStream_t st)
+// mode 0: LPHI, 1: RES, 3: both
+int launch_apply_boxes(const OnBoxes &t, bool has_alpha, int mode, hipStream_t st)
 {
-    if (m.nbox <= 0) return 0;                       // a rank that owns no box of the level
-    int n = 2 * m.maxny + 2 * m.maxnx;
-    hipLaunchKernelGGL(k_fill_ghosts_m, dim3((n + 255) / 256, 1, m.nbox), dim3(256), 0, st, m.dv, m.fp, field, homog);
-    HIPCHK(hipGetLastError());
-    return 0;
+    return mode == 0 ? launch_apply<0>(t, has_alpha, 0, st) : mode == 1 ? launch_apply<1>(t, has_alpha, 0, st) : launch_apply<3>(t, has_alpha, 0, st);
 }
-int suhmo_multi_apply(const suhmo_multi &m, const suhmo_phys_t &ph, bool has_alpha, int mode, hipStream_t st)
-{
-    if (m.nbox <= 0) return 0;                       // a rank that owns no box of the level
-    if (has_alpha) { if (mode == 0) hipLaunchKernelGGL((k_apply_m<true, 0>), grid_m(m), BLK2D, 0, st, m.dv, m.fp, ph, 0);
-                     else if (mode == 1) hipLaunchKernelGGL((k_apply_m<true, 1>), grid_m(m), BLK2D, 0, st, m.dv, m.fp, ph, 0);
-                     else hipLaunchKernelGGL((k_apply_m<true, 3>), grid_m(m), BLK2D, 0, st, m.dv, m.fp, ph, 0); }
-    else { if (mode == 0) hipLaunchKernelGGL((k_apply_m<false, 0>), grid_m(m), BLK2D, 0, st, m.dv, m.fp, ph, 0);
-           else if (mode == 1) hipLaunchKernelGGL((k_apply_m<false, 1>), grid_m(m), BLK2D, 0, st, m.dv, m.fp, ph, 0);
-           else hipLaunchKernelGGL((k_apply_m<false, 3>), grid_m(m), BLK2D, 0, st, m.dv, m.fp, ph, 0); }
-    HIPCHK(hipGetLastError());
-    return 0;
-}
-int suhmo_multi_axby(const suhmo_multi &m, int fd, int fx, int fy, double a, double b, hipStream_t st)
-{
-    if (m.nbox <= 0) return 0;                       // a rank that owns no box of the level
-    hipLaunchKernelGGL(k_axby_m, grid_m(m), BLK2D, 0, st, m.dv, m.fp, fd, fx, fy, a, b);
-    HIPCHK(hipGetLastError());
-    return 0;
-}
-int suhmo_multi_copy(const suhmo_multi &m, int fd, int fs, hipStream_t st)
-{
-    if (m.nbox <= 0) return 0;                       // a rank that owns no box of the level
-    hipLaunchKernelGGL(k_copy_m, grid_m(m, 2, 2), BLK2D, 0, st, m.dv, m.fp, fd, fs);
-    HIPCHK(hipGetLastError());
-    return 0;
-}
-int suhmo_multi_fas_enter(const suhmo_multi &m, hipStream_t st)
-{
-    if (m.nbox <= 0) return 0;
-    hipLaunchKernelGGL(k_fas_enter_m, grid_m(m, 2, 2), BLK2D, 0, st, m.dv, m.fp);
-    HIPCHK(hipGetLastError());
-    return 0;
-}
-int suhmo_multi_fas_leave(const suhmo_multi &m, hipStream_t st)
-{
-    if (m.nbox <= 0) return 0;
-    hipLaunchKernelGGL(k_fas_leave_m, grid_m(m, 2, 2), BLK2D, 0, st, m.dv, m.fp);
-    HIPCHK(hipGetLastError());
-    return 0;
-}
-int suhmo_multi_copy_between(const suhmo_multi &dst, const suhmo_multi &src, const int *fd, const int *fs, int n, hipStream_t st)
+int launch_copy(const OnBoxes &t, int fd, int fs, hipStream_t st) { return launch_over(k_copy, t, GHOSTED, st, fd, fs); }
+int launch_fas_enter(const OnBoxes &t, hipStream_t st) { return launch_over(k_fas_enter, t, GHOSTED, st); }
+int launch_fas_leave(const OnBoxes &t, hipStream_t st) { return launch_over(k_fas_leave, t, GHOSTED, st); }
+int launch_copy_between(const OnBoxes &dst, const OnBoxes &src, const int *fd, const int *fs, int n, hipStream_t st)
 {
     if (n < 1 || n > 4 || dst.nbox != src.nbox) { suhmo_set_error("internal: copy between hierarchies"); return -4; }
-    if (src.nbox <= 0) return 0;
     CopyPairs cp;
     cp.n = n;
     for (int q = 0; q < n; q++) { cp.fd[q] = fd[q]; cp.fs[q] = fs[q]; }
-    hipLaunchKernelGGL(k_copy_between_m, grid_m(src, 2, 2), BLK2D, 0, st, src.dv, dst.fp, src.fp, cp);
-    HIPCHK(hipGetLastError());
-    return 0;
+    return launch_over(k_copy_between, src, GHOSTED, st, dst, cp);
 }
 // AMRNorm over a hierarchy in ONE read-back: the first stages of level 0 (suhmo_level_norm_partials) and of every level of boxes
 // (suhmo_multi_norm_max_partials) leave their partial maxima where they always do; one launch takes the maximum of all the lists
@@ -965,12 +873,9 @@ int suhmo_level_norm_max_partials(suhmo_level *L, int field, const double **part
 int suhmo_multi_norm_max_partials(const suhmo_multi &m, int field, const double **partials, int *np, hipStream_t st)
 {
     *partials = m.red; *np = 0;
-    if (m.nbox <= 0) return 0;
-    dim3 grd(std::min((m.maxnx + 63) / 64, 4), std::min((m.maxny + 3) / 4, 16), m.nbox);
-    hipLaunchKernelGGL(k_norm_max_partial_m, grd, BLK2D, 0, st, m.dv, m.fp, field, m.red);
-    HIPCHK(hipGetLastError());
-    *np = (int)(grd.x * grd.y * grd.z);
-    return 0;
+    const dim3 grd(std::min((m.maxnx + 63) / 64, 4), std::min((m.maxny + 3) / 4, 16));
+    *np = (int)(grd.x * grd.y) * std::max(m.nbox, 0);
+    return launch_grid(k_norm_max_partial, m.on(), grd, BLK2D, st, field, m.red);
 }
 int suhmo_norm_max_of_lists(suhmo_level *slot, const double *const *partials, const int *np, int cnt, double *out, hipStream_t st)
 {
@@ -1037,54 +942,20 @@ int suhmo_level_norm_max_cover_partials(suhmo_level *L, int field, const double 
 }
 int suhmo_multi_norm_max(const suhmo_multi &m, suhmo_level *slot, int field, double *out, hipStream_t st)
 {
+    const double *partials; int np;
     if (m.nbox <= 0) { *out = 0.0; return 0; }
-    dim3 grd(std::min((m.maxnx + 63) / 64, 4), std::min((m.maxny + 3) / 4, 16), m.nbox);
-    hipLaunchKernelGGL(k_norm_max_partial_m, grd, BLK2D, 0, st, m.dv, m.fp, field, m.red);
-    hipLaunchKernelGGL(k_norm_final, dim3(1), dim3(256), 0, st, m.red, (int)(grd.x * grd.y * grd.z), 0, slot->scratch, suhmo_host_slot(slot));
+    int rc = suhmo_multi_norm_max_partials(m, field, &partials, &np, st); if (rc) return rc;
+    hipLaunchKernelGGL(k_norm_final, dim3(1), dim3(256), 0, st, partials, np, 0, slot->scratch, suhmo_host_slot(slot));
     HIPCHK(hipGetLastError());
     return suhmo_readback(slot, st, out);
 }
 
 
 // ------------------------------------------------------------------ every active member of a batch of whole levels in one launch (suhmo_batch.hip)
-int suhmo_batch_fill_ghosts(const BatchTab &t, const BatchSel &sel, const DV &v, int field, int homog, hipStream_t st)
-{
-    if (sel.n <= 0) return 0;
-    const int n = 2 * v.ny + 2 * v.nx;
-    hipLaunchKernelGGL(k_fill_ghosts_b, dim3((n + 255) / 256, 1, sel.n), dim3(256), 0, st, t, sel, field, homog);
-    HIPCHK(hipGetLastError());
-    return 0;
-}
-int suhmo_batch_restrict_both(const BatchTab &f, const BatchTab &c, const BatchSel &sel, const DV &vc, bool has_alpha, hipStream_t st)
-{
-    if (sel.n <= 0) return 0;
-    dim3 grd = grid2d(vc.nx, vc.ny); grd.z = sel.n;
-    if (has_alpha) hipLaunchKernelGGL(k_restrict_residual_b<true>, grd, BLK2D, 0, st, f, c, sel);
-    else hipLaunchKernelGGL(k_restrict_residual_b<false>, grd, BLK2D, 0, st, f, c, sel);
-    HIPCHK(hipGetLastError());
-    return 0;
-}
-int suhmo_batch_fas_coarse_rhs(const BatchTab &t, const BatchSel &sel, const DV &v, bool has_alpha, hipStream_t st)
-{
-    if (sel.n <= 0) return 0;
-    dim3 grd = grid2d(v.nx, v.ny); grd.z = sel.n;
-    if (has_alpha) hipLaunchKernelGGL((k_apply_b<true, 2>), grd, BLK2D, 0, st, t, sel, 0);
-    else hipLaunchKernelGGL((k_apply_b<false, 2>), grd, BLK2D, 0, st, t, sel, 0);
-    HIPCHK(hipGetLastError());
-    return 0;
-}
-int suhmo_batch_prolong(const BatchTab &f, const BatchTab &c, const BatchSel &sel, const DV &vf, const DV &vc, hipStream_t st)
-{
-    if (sel.n <= 0) return 0;
-    dim3 gc = grid2d(vc.nx, vc.ny), gf = grid2d(vf.nx, vf.ny); gc.z = gf.z = sel.n;
-    hipLaunchKernelGGL(k_axby_rows_b, gc, BLK2D, 0, st, c, sel, (int)SUHMO_F_CORR, (int)SUHMO_F_PHI, (int)SUHMO_F_PHIOLD, 1.0, -1.0);
-    hipLaunchKernelGGL(k_prolong_rows_b, gf, BLK2D, 0, st, f, c, sel);
-    HIPCHK(hipGetLastError());
-    return 0;
-}
+int launch_fas_coarse_rhs(const OnMembers &t, bool has_alpha, hipStream_t st) { return launch_apply<2>(t, has_alpha, 0, st); }
 // second stage of the members' max norms: a wave per member (the maximum is exact whatever the order), every value stored into the pinned
 // slot of its member, then ONE sequence number for all of them
-__global__ __launch_bounds__(256) void k_norm_final_b(BatchSel sel, const double *__restrict__ partial, int np, double *__restrict__ slot,
+__global__ __launch_bounds__(256) void k_norm_final_members(BatchSel sel, const double *__restrict__ partial, int np, double *__restrict__ slot,
                                                       unsigned long long *flag, unsigned long long seq)
 {
     const int lane = threadIdx.x & 63;
@@ -1100,33 +971,22 @@ __global__ __launch_bounds__(256) void k_norm_final_b(BatchSel sel, const double
     __syncthreads();
     if (threadIdx.x == 0) __hip_atomic_store(flag, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
 }
-size_t suhmo_batch_residual_partials(const DV &v) { const dim3 g = grid2d(v.nx, v.ny); return (size_t)g.x * g.y; }
-int suhmo_batch_residual_norm(const BatchTab &t, const BatchSel &sel, const DV &v, bool has_alpha, double *partial, double *slot,
-                              unsigned long long *flag, unsigned long long seq, hipStream_t st)
+size_t suhmo_batch_residual_partials(const OnMembers &t) { const dim3 g = grid2d(t.nx(), t.ny()); return (size_t)g.x * g.y; }
+int launch_residual_norm_members(const OnMembers &t, bool has_alpha, double *partial, double *slot, unsigned long long *flag, unsigned long long seq, hipStream_t st)
 {
-    if (sel.n <= 0) return 0;
-    dim3 grd = grid2d(v.nx, v.ny);
-    const int np = (int)(grd.x * grd.y);
-    grd.z = sel.n;
-    if (has_alpha) hipLaunchKernelGGL(k_residual_norm_b<true>, grd, BLK2D, 0, st, t, sel, partial);
-    else hipLaunchKernelGGL(k_residual_norm_b<false>, grd, BLK2D, 0, st, t, sel, partial);
-    hipLaunchKernelGGL(k_norm_final_b, dim3(1), dim3(256), 0, st, sel, partial, np, slot, flag, seq);
+    if (t.count() <= 0) return 0;
+    int rc = launch_residual_norm(t, has_alpha, partial, st); if (rc) return rc;
+    hipLaunchKernelGGL(k_norm_final_members, dim3(1), dim3(256), 0, st, t.sel, partial, (int)suhmo_batch_residual_partials(t), slot, flag, seq);
     HIPCHK(hipGetLastError());
     return 0;
 }
-__global__ void k_copy_canvas_b(BatchTab t, BatchSel sel, int fd, int fs, size_t elems)
+__global__ void k_copy_canvas(OnMembers t, int fd, int fs, size_t elems)
 {
-    const int k = batch_member(sel);
-    const FP fp = batch_fp(t, k);
-    const double *__restrict__ src = fp.f[fs];
-    double *__restrict__ dst = fp.f[fd];
+    const double *__restrict__ src = t.field(fs);
+    double *__restrict__ dst = t.field(fd);
     for (size_t q = (size_t)blockIdx.x * blockDim.x + threadIdx.x; q < elems; q += (size_t)gridDim.x * blockDim.x) dst[q] = src[q];
 }
-int suhmo_batch_copy_canvas(const BatchTab &t, const BatchSel &sel, int fd, int fs, size_t elems, hipStream_t st)
+int launch_copy_canvas(const OnMembers &t, int fd, int fs, size_t elems, hipStream_t st)
 {
-    if (sel.n <= 0) return 0;
-    const unsigned nb = (unsigned)std::min<size_t>((elems + 255) / 256, 256);
-    hipLaunchKernelGGL(k_copy_canvas_b, dim3(nb, 1, sel.n), dim3(256), 0, st, t, sel, fd, fs, elems);
-    HIPCHK(hipGetLastError());
-    return 0;
+    return launch_grid(k_copy_canvas, t, dim3((unsigned)std::min<size_t>((elems + 255) / 256, 256)), dim3(256), st, fd, fs, elems);
 }

@@ -73,21 +73,8 @@ __device__ __forceinline__ void d_qw_faces(const DV &v, const FP &fp, suhmo_phys
         fp.f[SUHMO_F_QWY][idx] = num_q / denom_q;
     }
 }
-__global__ __launch_bounds__(256) void k_qw_faces(DV v, FP fp, suhmo_phys_t ph)
-{
-    d_qw_faces(v, fp, ph);
-}
-// every box of a multi-box AMR level in one launch (blockIdx.z = box; suhmo_hier.hip)
-__global__ __launch_bounds__(256) void k_qw_faces_m(const DV *__restrict__ vt, const FP *__restrict__ ft, suhmo_phys_t ph)
-{
-    d_qw_faces(vt[blockIdx.z], ft[blockIdx.z], ph);
-}
-// every active member of a batch (suhmo_batch.h): its own physics constants
-__global__ __launch_bounds__(256) void k_qw_faces_b(BatchTab t, BatchSel sel)
-{
-    const int k = batch_member(sel);
-    d_qw_faces(t.dv[k], batch_fp(t, k), t.ph[k]);
-}
+template <class T> __global__ __launch_bounds__(256) void k_qw_faces(T t) { d_qw_faces(t.view(), t.fields(), t.phys()); }
+template <class T> static int launch_qw_faces(const T &t, hipStream_t st) { return launch_over(k_qw_faces<T>, t, FACES, st); }
 
 // MODE 0: melt rate + RHS_h (Picard iteration).  MODE 1: melt rate + gap-height RHS + forward Euler.
 template <int MODE>
@@ -146,23 +133,11 @@ __device__ __forceinline__ void d_melt(const DV &v, const FP &fp, suhmo_phys_t p
         else fp.f[SUHMO_F_B][idx] = RHS * dt + b;              // old b == b: the gap height is untouched during [II]
     }
 }
-template <int MODE>
-__global__ __launch_bounds__(256) void k_melt(DV v, FP fp, suhmo_phys_t ph, suhmo_model_params_t mp, double dt)
+// (an ensemble: every member's own physics constants and model parameters)
+template <class T, int MODE> __global__ __launch_bounds__(256) void k_melt(T t, double dt) { d_melt<MODE>(t.view(), t.fields(), t.phys(), t.model(), dt); }
+template <class T> static int launch_melt(const T &t, int final_, double dt, hipStream_t st)
 {
-    d_melt<MODE>(v, fp, ph, mp, dt);
-}
-// every box of a multi-box AMR level in one launch (blockIdx.z = box; suhmo_hier.hip)
-template <int MODE>
-__global__ __launch_bounds__(256) void k_melt_m(const DV *__restrict__ vt, const FP *__restrict__ ft, suhmo_phys_t ph, suhmo_model_params_t mp, double dt)
-{
-    d_melt<MODE>(vt[blockIdx.z], ft[blockIdx.z], ph, mp, dt);
-}
-// every active member of a batch (suhmo_batch.h): its own physics constants and model parameters (mpt: device rows of mp[n])
-template <int MODE>
-__global__ __launch_bounds__(256) void k_melt_b(BatchTab t, BatchSel sel, const suhmo_model_params_t *__restrict__ mpt, double dt)
-{
-    const int k = batch_member(sel);
-    d_melt<MODE>(t.dv[k], batch_fp(t, k), t.ph[k], mpt[k], dt);
+    return final_ ? launch_over(k_melt<T, 1>, t, CELLS, st, dt) : launch_over(k_melt<T, 0>, t, CELLS, st, dt);
 }
 
 // run-state setting freeze_icefree_gap (suhmo_hip.h): cells without ice keep their gap height through SolveForGap_nl -- the solved
@@ -177,22 +152,18 @@ __device__ __forceinline__ void d_keep_icefree(const DV &v, const double *__rest
     if (i >= v.nx || j >= v.ny) return;
     d_keep_icefree_cell(mk, bold, sol, cidx(v, i, j));
 }
-__global__ __launch_bounds__(256) void k_keep_icefree(DV v, const double *__restrict__ mk, const double *__restrict__ bold, double *__restrict__ sol)
+template <class T> __global__ __launch_bounds__(256) void k_keep_icefree(T h, T g)     // h: the level, g: its gap handle
 {
-    d_keep_icefree(v, mk, bold, sol);
+    const FP &fh = h.fields();
+    d_keep_icefree(h.view(), fh.f[SUHMO_F_MASK], fh.f[SUHMO_F_B], g.fields().f[SUHMO_F_PHI]);
 }
-__global__ __launch_bounds__(256) void k_keep_icefree_m(const DV *__restrict__ vt, const FP *__restrict__ fh, const FP *__restrict__ fg)
-{
-    d_keep_icefree(vt[blockIdx.z], fh[blockIdx.z].f[SUHMO_F_MASK], fh[blockIdx.z].f[SUHMO_F_B], fg[blockIdx.z].f[SUHMO_F_PHI]);
-}
+template <class T> static int launch_keep_icefree(const T &h, const T &g, hipStream_t st) { return launch_over(k_keep_icefree<T>, h, CELLS, st, g); }
 // SolveForGap_nl of a batch (suhmo_batch.hip): h = the members' tables of depth 0, g = those of their gap handles.  What
 // gap_level_prepare copies canvas by canvas (b -> PHI the initial guess, RES -> RHS, DCX -> BX, DCY -> BY; ghosts included), for every
 // implicit member in one launch; a canvas is an even number of doubles (the pitch is a multiple of 16)
-__global__ __launch_bounds__(256) void k_gap_load_b(BatchTab h, BatchTab g, BatchSel sel, size_t elems2)
+__global__ __launch_bounds__(256) void k_gap_load(OnMembers h, OnMembers g, size_t elems2)
 {
-    const int k = batch_member(sel);
-    const FP &s = h.fp[k];
-    const FP d = batch_fp(g, k);
+    const FP s = h.fields(), d = g.fields();
     const double2 *__restrict__ b = (const double2 *)s.f[SUHMO_F_B], *__restrict__ res = (const double2 *)s.f[SUHMO_F_RES];
     const double2 *__restrict__ dcx = (const double2 *)s.f[SUHMO_F_DCX], *__restrict__ dcy = (const double2 *)s.f[SUHMO_F_DCY];
     double2 *__restrict__ phi = (double2 *)d.f[SUHMO_F_PHI], *__restrict__ rhs = (double2 *)d.f[SUHMO_F_RHS];
@@ -203,13 +174,13 @@ __global__ __launch_bounds__(256) void k_gap_load_b(BatchTab h, BatchTab g, Batc
     }
 }
 // ... and the way back: keep_icefree where the member's freeze_icefree_gap asks for it (valid cells), then the whole canvas into b
-__global__ __launch_bounds__(256) void k_gap_store_b(BatchTab h, BatchTab g, BatchSel sel, const suhmo_model_params_t *__restrict__ mpt, size_t elems)
+__global__ __launch_bounds__(256) void k_gap_store(OnMembers h, OnMembers g, size_t elems)
 {
-    const int k = batch_member(sel);
-    const DV &v = h.dv[k];
-    const double *mk = h.fp[k].f[SUHMO_F_MASK];
-    double *b = h.fp[k].f[SUHMO_F_B], *sol = batch_fp(g, k).f[SUHMO_F_PHI];
-    const bool freeze = mpt[k].freeze_icefree_gap != 0;
+    const DV &v = h.view();
+    const FP fh = h.fields();
+    const double *mk = fh.f[SUHMO_F_MASK];
+    double *b = fh.f[SUHMO_F_B], *sol = g.fields().f[SUHMO_F_PHI];
+    const bool freeze = h.model().freeze_icefree_gap != 0;
     for (size_t q = (size_t)blockIdx.x * blockDim.x + threadIdx.x; q < elems; q += (size_t)gridDim.x * blockDim.x) {
         if (freeze) {
             const int i = (int)(q % v.P) - SUHMO_XOFF, j = (int)(q / v.P) - v.gy;
@@ -218,31 +189,16 @@ __global__ __launch_bounds__(256) void k_gap_store_b(BatchTab h, BatchTab g, Bat
         b[q] = sol[q];
     }
 }
-int suhmo_batch_gap_load(const BatchTab &h, const BatchTab &g, const BatchSel &sel, size_t elems, hipStream_t st)
+int suhmo_batch_gap_load(const OnMembers &h, const OnMembers &g, size_t elems, hipStream_t st)
 {
-    if (sel.n <= 0) return 0;
     if (elems & 1) { suhmo_set_error("internal: batch: a canvas of an odd number of doubles"); return -4; }
-    const unsigned nb = (unsigned)std::min<size_t>((elems / 2 + 255) / 256, 256);
-    hipLaunchKernelGGL(k_gap_load_b, dim3(nb, 1, sel.n), dim3(256), 0, st, h, g, sel, elems / 2);
-    HIPCHK(hipGetLastError());
-    return 0;
+    return launch_grid(k_gap_load, h, dim3((unsigned)std::min<size_t>((elems / 2 + 255) / 256, 256)), dim3(256), st, g, elems / 2);
 }
-int suhmo_batch_gap_store(const BatchTab &h, const BatchTab &g, const BatchSel &sel, const suhmo_model_params_t *mpt, size_t elems, hipStream_t st)
+int suhmo_batch_gap_store(const OnMembers &h, const OnMembers &g, size_t elems, hipStream_t st)
 {
-    if (sel.n <= 0) return 0;
-    const unsigned nb = (unsigned)std::min<size_t>((elems + 255) / 256, 256);
-    hipLaunchKernelGGL(k_gap_store_b, dim3(nb, 1, sel.n), dim3(256), 0, st, h, g, sel, mpt, elems);
-    HIPCHK(hipGetLastError());
-    return 0;
+    return launch_grid(k_gap_store, h, dim3((unsigned)std::min<size_t>((elems + 255) / 256, 256)), dim3(256), st, g, elems);
 }
-static int keep_icefree(suhmo_level *L, suhmo_level *G, hipStream_t st)
-{
-    Depth &D = L->d[0];
-    hipLaunchKernelGGL(k_keep_icefree, dim3((D.v.nx + 63) / 64, (D.v.ny + 3) / 4), dim3(64, 4), 0, st, D.v, D.fp.f[SUHMO_F_MASK], D.fp.f[SUHMO_F_B],
-                       G->d[0].fp.f[SUHMO_F_PHI]);
-    HIPCHK(hipGetLastError());
-    return 0;
-}
+static int keep_icefree(suhmo_level *L, suhmo_level *G, hipStream_t st) { return launch_keep_icefree(on_level(L, 0), on_level(G, 0), st); }
 
 // Picard convergence test, :3169-3185
 struct Excl { int i0, j0, i1, j1; };       // local cells [i0, i1) x [j0, j1) do not count (covered by a finer level)
@@ -272,20 +228,21 @@ __device__ __forceinline__ void d_picard2_partial(const DV &v, const double *__r
     }
     if (tid == 0) { int b = blockIdx.y * gridDim.x + blockIdx.x; partial[2 * b] = sm0[0]; partial[2 * b + 1] = sm1[0]; }
 }
-__global__ __launch_bounds__(256) void k_picard2_partial(DV v, const double *__restrict__ h, const double *__restrict__ hl,
-                                                         double *__restrict__ partial, Excl ex, const double *__restrict__ cover = nullptr)
+// (the boxes of a level, the members of an ensemble: a level's own workgroups per box / member, its partial maxima one after the other)
+template <class T> __global__ __launch_bounds__(256) void k_picard2_partial(T t, double *__restrict__ partial, Excl ex, int use_cover)
 {
-    d_picard2_partial(v, h, hl, partial, ex, cover);
+    const FP &fp = t.fields();
+    d_picard2_partial(t.view(), fp.f[SUHMO_F_PHI], fp.f[SUHMO_F_HLAG], partial + 2 * t.slot((size_t)gridDim.x * gridDim.y), ex, use_cover ? fp.f[SUHMO_F_COVER] : nullptr);
 }
-// every active member of a batch (suhmo_batch.h): the solo kernel's workgroups per member, its partial maxima at partial + 2 k workgroups
-__global__ __launch_bounds__(256) void k_picard2_partial_b(BatchTab t, BatchSel sel, double *__restrict__ partial)
+// first stage over the cells of a target with at most gx x gy workgroups each; *np: the pairs of partial maxima it leaves
+template <class T> static int launch_picard2_partial(const T &t, int gx, int gy, double *partial, Excl ex, bool covered, int *np, hipStream_t st)
 {
-    const int k = batch_member(sel);
-    const FP fp = batch_fp(t, k);
-    d_picard2_partial(t.dv[k], fp.f[SUHMO_F_PHI], fp.f[SUHMO_F_HLAG], partial + (size_t)k * 2 * gridDim.x * gridDim.y, Excl{0, 0, 0, 0}, nullptr);
+    const dim3 grd(std::min((t.nx() + 63) / 64, gx), std::min((t.ny() + 3) / 4, gy));
+    *np = (int)(grd.x * grd.y);
+    return launch_grid(k_picard2_partial<T>, t, grd, BLK2D, st, partial, ex, (int)covered);
 }
 // second stage for all of them: a wave per member (maxima: exact in any order), both values into the member's pinned slots, then ONE sequence number
-__global__ __launch_bounds__(256) void k_max2_final_b(BatchSel sel, const double *__restrict__ partial, int np, double *__restrict__ slot,
+__global__ __launch_bounds__(256) void k_max2_final_members(BatchSel sel, const double *__restrict__ partial, int np, double *__restrict__ slot,
                                                       unsigned long long *flag, unsigned long long seq)
 {
     const int lane = threadIdx.x & 63;
@@ -317,13 +274,11 @@ __global__ void k_max2_final(const double *__restrict__ partial, int n, double *
 }
 // max h and max |hl - h| over the level's cells (local to the rank)
 // over_ranks: the maxima over all ranks of the level's strip partition (computeMax; one MAX all-reduce of both values)
-static int picard_maxima(suhmo_level *L, const double *h, const double *hl, double *maxh, double *maxd, hipStream_t st,
-                         Excl ex = Excl{0, 0, 0, 0}, const double *cover = nullptr, bool over_ranks = false)
+static int picard_maxima(suhmo_level *L, double *maxh, double *maxd, hipStream_t st, Excl ex = Excl{0, 0, 0, 0}, bool covered = false, bool over_ranks = false)
 {
-    Depth &D = L->d[0];
-    dim3 grd(std::min((D.v.nx + 63) / 64, 32), std::min((D.v.ny + 3) / 4, 128));
-    hipLaunchKernelGGL(k_picard2_partial, grd, dim3(64, 4), 0, st, D.v, h, hl, L->scratch + 2, ex, cover);
-    hipLaunchKernelGGL(k_max2_final, dim3(1), dim3(256), 0, st, L->scratch + 2, (int)(grd.x * grd.y), L->scratch, over_ranks ? suhmo_reduce_slot(L) : suhmo_host_slot(L));
+    int np, rc = launch_picard2_partial(on_level(L, 0), 32, 128, L->scratch + 2, ex, covered, &np, st);
+    if (rc) return rc;
+    hipLaunchKernelGGL(k_max2_final, dim3(1), dim3(256), 0, st, L->scratch + 2, np, L->scratch, over_ranks ? suhmo_reduce_slot(L) : suhmo_host_slot(L));
     if (over_ranks) return suhmo_reduce_finish(L, st, 2, 0, maxh, maxd);
     return suhmo_readback(L, st, maxh, maxd);
 }
@@ -333,17 +288,12 @@ static inline double picard_quotient(double maxd, double maxHead) { return maxd 
 // suhmo_bcoef.hip (identical arithmetic: NEWMACGRAD + EdgeToCell + ExtrapGhostCells + COMPUTERE)
 int suhmo_grad_re(suhmo_level *L, int depth, hipStream_t st);      // suhmo_bcoef.hip
 int suhmo_grad_cc(suhmo_level *L, int depth, hipStream_t st);
-int suhmo_re_cells(suhmo_level *L, int depth, hipStream_t st);
-int suhmo_bcoef_faces(suhmo_level *L, int depth, hipStream_t st);
 int suhmo_copy_ghosts(suhmo_level *L, int depth, int field, hipStream_t st);
 
 static int lagged_chain(suhmo_level *L, hipStream_t st)
 {
-    Depth &D = L->d[0];
     int rc = suhmo_grad_re(L, 0, st); if (rc) return rc;
-    hipLaunchKernelGGL(k_qw_faces, dim3((D.v.nx + 1 + 63) / 64, (D.v.ny + 1 + 3) / 4), dim3(64, 4), 0, st, D.v, D.fp, L->ph);
-    HIPCHK(hipGetLastError());
-    return 0;
+    return launch_qw_faces(on_level(L, 0), st);
 }
 
 // ---- diffusion of the gap height (suhmo.diffFactor != 0)
@@ -366,20 +316,7 @@ __device__ __forceinline__ void d_extrap_ghosts(const DV &v, double *__restrict_
         else { int idx = cidx(v, i, v.ny - 1); g[idx + v.P] = v.per[1] ? g[idx - (v.ny - 1) * v.P] : 2.0 * g[idx] - g[idx - v.P]; }
     }
 }
-__global__ void k_extrap_ghosts(DV v, double *__restrict__ g)
-{
-    d_extrap_ghosts(v, g);
-}
-// every box of a multi-box AMR level in one launch (blockIdx.z = box; suhmo_hier.hip)
-__global__ void k_extrap_ghosts_m(const DV *__restrict__ vt, const FP *__restrict__ ft, int field)
-{
-    d_extrap_ghosts(vt[blockIdx.z], ft[blockIdx.z].f[field]);
-}
-__global__ void k_extrap_ghosts_b(BatchTab t, BatchSel sel, int field)
-{
-    const int k = batch_member(sel);
-    d_extrap_ghosts(t.dv[k], t.fp[k].f[field]);
-}
+template <class T> __global__ void k_extrap_ghosts(T t, int field) { d_extrap_ghosts(t.view(), t.field(field)); }
 // dCoeff: CellToEdge(mR), CellToEdge(b), setup_iceMask_EC, COMPUTEDCOEFF (src/AmrHydro.cpp:1831-1862, ...F.ChF:241-265)
 __device__ __forceinline__ void d_dcoef_faces(const DV &v, const FP &fp, suhmo_phys_t ph, double rho_i)
 {
@@ -399,20 +336,7 @@ __device__ __forceinline__ void d_dcoef_faces(const DV &v, const FP &fp, suhmo_p
         fp.f[dir == 0 ? SUHMO_F_DCX : SUHMO_F_DCY][idx] = d;
     }
 }
-__global__ __launch_bounds__(256) void k_dcoef_faces(DV v, FP fp, suhmo_phys_t ph, double rho_i)
-{
-    d_dcoef_faces(v, fp, ph, rho_i);
-}
-// every box of a multi-box AMR level in one launch (blockIdx.z = box; suhmo_hier.hip)
-__global__ __launch_bounds__(256) void k_dcoef_faces_m(const DV *__restrict__ vt, const FP *__restrict__ ft, suhmo_phys_t ph, double rho_i)
-{
-    d_dcoef_faces(vt[blockIdx.z], ft[blockIdx.z], ph, rho_i);
-}
-__global__ __launch_bounds__(256) void k_dcoef_faces_b(BatchTab t, BatchSel sel, const suhmo_model_params_t *__restrict__ mpt)
-{
-    const int k = batch_member(sel);
-    d_dcoef_faces(t.dv[k], t.fp[k], t.ph[k], mpt[k].rho_i);
-}
+template <class T> __global__ __launch_bounds__(256) void k_dcoef_faces(T t) { d_dcoef_faces(t.view(), t.fields(), t.phys(), t.model().rho_i); }
 // COMPUTEDIFTERM2D (src/AmrHydroF.ChF:289-343) of the gap height with its copied ghosts
 __device__ __forceinline__ void d_difterm(const DV &v, FP fp)
 {
@@ -425,42 +349,26 @@ __device__ __forceinline__ void d_difterm(const DV &v, FP fp)
         (dx_[idx + 1] * (B[idx + 1] - B[idx]) * dxinv0 - dx_[idx] * (B[idx] - B[idx - 1]) * dxinv0
          + dy_[idx + v.P] * (B[idx + v.P] - B[idx]) * dxinv1 - dy_[idx] * (B[idx] - B[idx - v.P]) * dxinv1);
 }
-__global__ __launch_bounds__(256) void k_difterm(DV v, FP fp)
+template <class T> __global__ __launch_bounds__(256) void k_difterm(T t) { d_difterm(t.view(), t.fields()); }
+// the lagged diffusion terms of a target: ghosts of the melt rate, dCoeff on the faces, the term itself (the fields exist)
+template <class T> static int launch_diffusion_terms(const T &t, hipStream_t st)
 {
-    d_difterm(v, fp);
-}
-// every box of a multi-box AMR level in one launch (blockIdx.z = box; suhmo_hier.hip)
-__global__ __launch_bounds__(256) void k_difterm_m(const DV *__restrict__ vt, const FP *__restrict__ ft)
-{
-    d_difterm(vt[blockIdx.z], ft[blockIdx.z]);
-}
-__global__ __launch_bounds__(256) void k_difterm_b(BatchTab t, BatchSel sel)
-{
-    const int k = batch_member(sel);
-    d_difterm(t.dv[k], t.fp[k]);
+    int rc;
+    if ((rc = launch_over(k_extrap_ghosts<T>, t, PERIMETER, st, (int)SUHMO_F_MR)) || (rc = launch_over(k_dcoef_faces<T>, t, FACES, st))) return rc;
+    return launch_over(k_difterm<T>, t, CELLS, st);
 }
 static int diffusion_terms(suhmo_level *L, const suhmo_model_params_t *mp, hipStream_t st)
 {
-    Depth &D = L->d[0];
     for (int f : {SUHMO_F_DCX, SUHMO_F_DCY, SUHMO_F_DTERM}) if (!suhmo_field(L, 0, f)) { suhmo_set_error("field allocation failed"); return -2; }
-    int n = 2 * D.v.ny + 2 * D.v.nx;
     int rc = exchange1(L, SUHMO_F_MR, st); if (rc) return rc;          // levelmR.exchange() :2513
-    hipLaunchKernelGGL(k_extrap_ghosts, dim3((n + 255) / 256), dim3(256), 0, st, D.v, D.fp.f[SUHMO_F_MR]);
-    hipLaunchKernelGGL(k_dcoef_faces, dim3((D.v.nx + 1 + 63) / 64, (D.v.ny + 1 + 3) / 4), dim3(64, 4), 0, st, D.v, D.fp, L->ph, mp->rho_i);
-    hipLaunchKernelGGL(k_difterm, dim3((D.v.nx + 63) / 64, (D.v.ny + 3) / 4), dim3(64, 4), 0, st, D.v, D.fp);
-    HIPCHK(hipGetLastError());
-    return 0;
+    return launch_diffusion_terms(stepping(on_level(L, 0), *mp), st);
 }
 // the lagged diffusion terms (diffusion), then the melt rate with RHS_h (final_ = 0) or with the gap-height update (1) of one level
 static int level_melt(suhmo_level *L, const suhmo_model_params_t *mp, double dt, int final_, bool diffusion, hipStream_t st)
 {
-    Depth &D = L->d[0];
     int rc;
     if (diffusion && (rc = diffusion_terms(L, mp, st))) return rc;
-    if (!final_) hipLaunchKernelGGL(k_melt<0>, dim3((D.v.nx + 63) / 64, (D.v.ny + 3) / 4), dim3(64, 4), 0, st, D.v, D.fp, L->ph, *mp, dt);
-    else hipLaunchKernelGGL(k_melt<1>, dim3((D.v.nx + 63) / 64, (D.v.ny + 3) / 4), dim3(64, 4), 0, st, D.v, D.fp, L->ph, *mp, dt);
-    HIPCHK(hipGetLastError());
-    return 0;
+    return launch_melt(stepping(on_level(L, 0), *mp), final_, dt, st);
 }
 // SolveForGap_nl (src/AmrHydro.cpp:593-662): (1 - dt diffFactor div(D grad)) b = RES on a second level handle with the
 // linear operator (alpha = 1, aCoef = 1, beta = dt diffFactor, bCoef = D, no nonlinear term), FixedNeumBCFill = Neumann 0.
@@ -617,15 +525,14 @@ struct OneLevel {
     int head_rhs(const suhmo_model_params_t *mp, double dt)
     {
         int rc;
-        if ((rc = suhmo_bcoef_faces(base, 0, st))) return rc;                          // aCoeff_bCoeff :3087-3102
+        if ((rc = launch_bcoef_faces(on_level(base, 0), st))) return rc;                          // aCoeff_bCoeff :3087-3102
         if ((rc = level_melt(base, mp, dt, 0, mp->diffFactor != 0.0, st))) return rc;   // lagged melt rate :2548-2551, :2982-2992
         return exchange1(base, SUHMO_F_RHS, st);                                        // rank strips relax their halo rows redundantly
     }
     int solve_head(const suhmo_solver_params_t &sp, int *it) { return suhmo_level_solve(base, &sp, it, nullptr, st); }
     int picard_maxima(double *maxh, double *maxd)                                       // computeMax over all ranks
     {
-        Depth &D = base->d[0];
-        return ::picard_maxima(base, D.fp.f[SUHMO_F_PHI], D.fp.f[SUHMO_F_HLAG], maxh, maxd, st, Excl{0, 0, 0, 0}, nullptr, true);
+        return ::picard_maxima(base, maxh, maxd, st, Excl{0, 0, 0, 0}, false, true);
     }
     int melt_final(int, const suhmo_model_params_t *mp, double dt) { return level_melt(base, mp, dt, 1, false, st); }
     int solve_gap(const suhmo_model_params_t *mp, double dt, int cur_step)
@@ -669,50 +576,42 @@ struct Batch {
         if (sel.n <= 0) return 0;
         const BatchStep p = suhmo_batch_step(B);
         suhmo_batch_count(B, 1);
-        return suhmo_batch_copy_ghosts(p.t, sel, *p.v, SUHMO_F_B, st);
+        return launch_coef_ghosts(on_members(p.t, sel, *p.v), SUHMO_F_B, st);
     }
     int gap_ghosts(int) { return gap_ghosts(suhmo_batch_step(B).sel); }
     int lag_head()
     {
         const BatchStep p = suhmo_batch_step(B);
         suhmo_batch_count(B, 1);
-        return suhmo_batch_copy_canvas(p.t, p.sel, SUHMO_F_HLAG, SUHMO_F_PHI, p.elems, st);
+        return launch_copy_canvas(on_members(p.t, p.sel, *p.v), SUHMO_F_HLAG, SUHMO_F_PHI, p.elems, st);
     }
     int chain(int)
     {
         const BatchStep p = suhmo_batch_step(B);
-        int rc = suhmo_batch_grad_re(p.t, p.sel, *p.v, st); if (rc) return rc;
-        dim3 g((p.v->nx + 1 + 63) / 64, (p.v->ny + 1 + 3) / 4, p.sel.n);
-        hipLaunchKernelGGL(k_qw_faces_b, g, dim3(64, 4), 0, st, p.t, p.sel);
-        HIPCHK(hipGetLastError());
+        const OnMembers t = on_members(p.t, p.sel, *p.v);
+        int rc;
+        if ((rc = launch_grad_cc(t, st)) || (rc = launch_re(t, st))) return rc;
         suhmo_batch_count(B, 4);
-        return 0;
+        return launch_qw_faces(t, st);
     }
     int melt(const suhmo_model_params_t *mp, double dt, int final_, bool diffusion)
     {
         const BatchStep p = suhmo_batch_step(B);
-        const DV &v = *p.v;
+        int rc;
         if (diffusion) {
             const BatchSel d = suhmo_batch_step_subset(B, mp, has_diffusion);
             if (d.n > 0) {
-                const int n = 2 * v.ny + 2 * v.nx;
-                hipLaunchKernelGGL(k_extrap_ghosts_b, dim3((n + 255) / 256, 1, d.n), dim3(256), 0, st, p.t, d, (int)SUHMO_F_MR);
-                hipLaunchKernelGGL(k_dcoef_faces_b, dim3((v.nx + 1 + 63) / 64, (v.ny + 1 + 3) / 4, d.n), dim3(64, 4), 0, st, p.t, d, p.mp);
-                hipLaunchKernelGGL(k_difterm_b, dim3((v.nx + 63) / 64, (v.ny + 3) / 4, d.n), dim3(64, 4), 0, st, p.t, d);
+                if ((rc = launch_diffusion_terms(on_members(p.t, d, *p.v, p.mp), st))) return rc;
                 suhmo_batch_count(B, 3);
             }
         }
-        const dim3 g((v.nx + 63) / 64, (v.ny + 3) / 4, p.sel.n);
-        if (!final_) hipLaunchKernelGGL(k_melt_b<0>, g, dim3(64, 4), 0, st, p.t, p.sel, p.mp, dt);
-        else hipLaunchKernelGGL(k_melt_b<1>, g, dim3(64, 4), 0, st, p.t, p.sel, p.mp, dt);
-        HIPCHK(hipGetLastError());
         suhmo_batch_count(B, 1);
-        return 0;
+        return launch_melt(on_members(p.t, p.sel, *p.v, p.mp), final_, dt, st);
     }
     int head_rhs(const suhmo_model_params_t *mp, double dt)
     {
         const BatchStep p = suhmo_batch_step(B);
-        int rc = suhmo_batch_bcoef_faces(p.t, p.sel, *p.v, st); if (rc) return rc;      // aCoeff_bCoeff :3087-3102
+        int rc = launch_bcoef_faces(on_members(p.t, p.sel, *p.v), st); if (rc) return rc;      // aCoeff_bCoeff :3087-3102
         suhmo_batch_count(B, 1);
         return melt(mp, dt, 0, true);                                                    // lagged melt rate :2548-2551, :2982-2992
     }
@@ -720,10 +619,9 @@ struct Batch {
     int picard_maxima(double *maxh, double *maxd)
     {
         const BatchStep p = suhmo_batch_step(B, true);
-        const DV &v = *p.v;
-        dim3 grd(std::min((v.nx + 63) / 64, 32), std::min((v.ny + 3) / 4, 128), p.sel.n);      // (the workgroups of picard_maxima, per member)
-        hipLaunchKernelGGL(k_picard2_partial_b, grd, dim3(64, 4), 0, st, p.t, p.sel, p.partial);
-        hipLaunchKernelGGL(k_max2_final_b, dim3(1), dim3(256), 0, st, p.sel, p.partial, (int)(grd.x * grd.y), p.slot, p.flag, p.seq);
+        int np, rc = launch_picard2_partial(on_members(p.t, p.sel, *p.v), 32, 128, p.partial, Excl{0, 0, 0, 0}, false, &np, st);   // (the workgroups of picard_maxima, per member)
+        if (rc) return rc;
+        hipLaunchKernelGGL(k_max2_final_members, dim3(1), dim3(256), 0, st, p.sel, p.partial, np, p.slot, p.flag, p.seq);
         HIPCHK(hipGetLastError());
         suhmo_batch_count(B, 2);
         return suhmo_batch_step_read(B, st, maxh, maxd);
@@ -778,18 +676,15 @@ static int amr_chain(suhmo_level_t **lv, int l, hipStream_t st)
     suhmo_stream_t s = (suhmo_stream_t)st;
     int rc;
     if (!L) return C ? suhmo_ensure_phi_halo(C, 0, 1, st) : 0;
-    Depth &D = L->d[0];
     if (C && (rc = suhmo_amr2_cf_interp(C, L, SUHMO_F_PHI, SUHMO_F_PHI, s))) return rc;
     if ((rc = suhmo_grad_cc(L, 0, st))) return rc;
     if (C) {
         if ((rc = suhmo_amr2_cf_interp(C, L, SUHMO_F_GRADX, SUHMO_F_GRADX, s))) return rc;
         if ((rc = suhmo_amr2_cf_interp(C, L, SUHMO_F_GRADY, SUHMO_F_GRADY, s))) return rc;
     }
-    if ((rc = suhmo_re_cells(L, 0, st))) return rc;
+    if ((rc = launch_re(on_level(L, 0), st))) return rc;
     if (C && (rc = suhmo_amr2_pwl_fill(C, L, SUHMO_F_RE, SUHMO_F_RE, s))) return rc;
-    hipLaunchKernelGGL(k_qw_faces, dim3((D.v.nx + 1 + 63) / 64, (D.v.ny + 1 + 3) / 4), dim3(64, 4), 0, st, D.v, D.fp, L->ph);
-    HIPCHK(hipGetLastError());
-    return 0;
+    return launch_qw_faces(on_level(L, 0), st);
 }
 static Excl covered_by(suhmo_level_t **lv, int nlev, int l)
 {
@@ -837,7 +732,7 @@ struct Nested {
         int rc;
         for (int l = 0; l < nlev; l++) {
             if (!lv[l]) continue;
-            if ((rc = suhmo_bcoef_faces(lv[l], 0, st))) return rc;                      // aCoeff_bCoeff :3087-3102
+            if ((rc = launch_bcoef_faces(on_level(lv[l], 0), st))) return rc;                      // aCoeff_bCoeff :3087-3102
             if ((rc = level_melt(lv[l], mp, dt, 0, mp->diffFactor != 0.0, st))) return rc;
             if ((rc = exchange1(lv[l], SUHMO_F_RHS, st))) return rc;                   // halo rows relaxed redundantly
         }
@@ -863,7 +758,7 @@ struct Nested {
         for (int l = 0; l < nlev; l++) {
             if (!lv[l]) continue;
             double m = 0.0, d = 0.0;
-            if ((rc = ::picard_maxima(lv[l], lv[l]->d[0].fp.f[SUHMO_F_PHI], lv[l]->d[0].fp.f[SUHMO_F_HLAG], &m, &d, st, covered_by(lv, nlev, l)))) return rc;
+            if ((rc = ::picard_maxima(lv[l], &m, &d, st, covered_by(lv, nlev, l)))) return rc;
             *maxHead = std::max(*maxHead, m); *maxd = std::max(*maxd, d);
         }
         if (strips && lv[0]->ar) {                                  // computeMax over all ranks (level 0 reaches every rank)
@@ -929,30 +824,6 @@ extern "C" int suhmo_amr_timestep(suhmo_level_t **lv, int nlev, const suhmo_mode
 // the reference's exchange() is the fine-fine copy between the boxes of the level (suhmo_hier.hip).  Every phase of a level
 // >= 1 is ONE launch over all its boxes (blockIdx.z = box, device tables of views and field pointers).
 namespace {
-__global__ __launch_bounds__(256) void k_picard2_partial_m(const DV *__restrict__ vt, const FP *__restrict__ ft, int use_cover, double *__restrict__ partial)
-{
-    __shared__ double sm0[256], sm1[256];
-    const DV &v = vt[blockIdx.z];
-    const double *__restrict__ h = ft[blockIdx.z].f[SUHMO_F_PHI], *__restrict__ hl = ft[blockIdx.z].f[SUHMO_F_HLAG];
-    const double *__restrict__ cover = use_cover ? ft[blockIdx.z].f[SUHMO_F_COVER] : nullptr;
-    int tid = threadIdx.y * blockDim.x + threadIdx.x;
-    double a0 = -1.0e300, a1 = 0.0;
-    for (int j = blockIdx.y * blockDim.y + threadIdx.y; j < v.ny; j += gridDim.y * blockDim.y)
-        for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < v.nx; i += gridDim.x * blockDim.x) {
-            int idx = cidx(v, i, j);
-            if (cover && cover[idx] != 0.0) continue;
-            a0 = fmax(a0, h[idx]);
-            a1 = fmax(a1, fabs(hl[idx] - h[idx]));
-        }
-    sm0[tid] = a0; sm1[tid] = a1;
-    __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) {
-        if (tid < s) { sm0[tid] = fmax(sm0[tid], sm0[tid + s]); sm1[tid] = fmax(sm1[tid], sm1[tid + s]); }
-        __syncthreads();
-    }
-    if (tid == 0) { int b = (blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x; partial[2 * b] = sm0[0]; partial[2 * b + 1] = sm1[0]; }
-}
-inline dim3 grid_m(const suhmo_multi &m, int ex = 0, int ey = 0) { return dim3((m.maxnx + ex + 63) / 64, (m.maxny + ey + 3) / 4, m.nbox); }
 // a level of the hierarchy as a launch target: level 0 = the base handle, level l >= 1 = all its boxes at once
 struct LevT { suhmo_level *base; suhmo_multi m; };
 int lev_target(suhmo_hier *H, int l, hipStream_t st, LevT &t)
@@ -966,22 +837,17 @@ int hier_chain(suhmo_hier *H, int l, hipStream_t st)
     int rc;
     LevT t;
     if ((rc = lev_target(H, l, st, t))) return rc;
-    const suhmo_phys_t &ph = H->lev[l].box[0]->ph;
     if ((rc = hier_cf(H, l, SUHMO_F_PHI, SUHMO_F_PHI, st))) return rc;                  // inside compGradientMAC
     if ((rc = hier_ff(H, l, SUHMO_F_PHI, -1, false, st))) return rc;
-    if (t.base) rc = suhmo_grad_cc(t.base, 0, st); else rc = suhmo_multi_grad_cc(t.m, ph.use_mask_gradients, st);
+    if (t.base) rc = suhmo_grad_cc(t.base, 0, st); else rc = suhmo_multi_grad_cc(t.m, st);
     if (rc) return rc;
     if ((rc = hier_cf(H, l, SUHMO_F_GRADX, SUHMO_F_GRADX, st, SUHMO_F_GRADY, SUHMO_F_GRADY))) return rc;   // :1650-1659
     if ((rc = hier_ff(H, l, SUHMO_F_GRADX, SUHMO_F_GRADY, true, st))) return rc;
-    if (t.base) rc = suhmo_re_cells(t.base, 0, st); else rc = suhmo_multi_re(t.m, ph, st);
+    rc = t.base ? launch_re(on_level(t.base, 0), st) : launch_re(t.m.on(), st);
     if (rc) return rc;
     if ((rc = hier_pwl(H, l, SUHMO_F_RE, SUHMO_F_RE, st))) return rc;                   // :2711-2721
     if ((rc = hier_ff(H, l, SUHMO_F_RE, -1, true, st))) return rc;
-    if (t.base) { Depth &D = t.base->d[0];
-        hipLaunchKernelGGL(k_qw_faces, dim3((D.v.nx + 1 + 63) / 64, (D.v.ny + 1 + 3) / 4), dim3(64, 4), 0, st, D.v, D.fp, ph); }
-    else if (t.m.nbox > 0) hipLaunchKernelGGL(k_qw_faces_m, grid_m(t.m, 1, 1), dim3(64, 4), 0, st, t.m.dv, t.m.fp, ph);
-    HIPCHK(hipGetLastError());
-    return 0;
+    return t.base ? launch_qw_faces(on_level(t.base, 0), st) : launch_qw_faces(t.m.on(), st);
 }
 // ghosts of b of level l: PiecewiseLinearFillPatch on coarse-fine cells, exchange between the boxes, copies on domain sides
 int hier_gap_ghosts(suhmo_hier *H, int l, hipStream_t st)
@@ -992,7 +858,7 @@ int hier_gap_ghosts(suhmo_hier *H, int l, hipStream_t st)
     if ((rc = hier_pwl(H, l, SUHMO_F_B, SUHMO_F_B, st))) return rc;
     if ((rc = hier_ff(H, l, SUHMO_F_B, -1, true, st))) return rc;
     if (t.base) { if ((rc = suhmo_copy_ghosts(t.base, 0, SUHMO_F_B, st))) return rc; return exchange1(t.base, SUHMO_F_B, st); }   // rank strips: halo rows
-    return suhmo_multi_coef_ghosts(t.m, SUHMO_F_B, st);
+    return launch_coef_ghosts(t.m.on(), SUHMO_F_B, st);
 }
 // lagged diffusion terms (diffusion_terms of one level) and RHS_h / the gap-height right-hand side of a whole level
 int hier_melt(suhmo_hier *H, int l, const suhmo_model_params_t *mp, double dt, int final_, bool diffusion, hipStream_t st)
@@ -1000,22 +866,15 @@ int hier_melt(suhmo_hier *H, int l, const suhmo_model_params_t *mp, double dt, i
     int rc;
     LevT t;
     if ((rc = lev_target(H, l, st, t))) return rc;
-    const suhmo_phys_t &ph = H->lev[l].box[0]->ph;
     if (t.base) return level_melt(t.base, mp, dt, final_, diffusion, st);
     const suhmo_multi &m = t.m;
     if (diffusion) for (int f : {SUHMO_F_DCX, SUHMO_F_DCY, SUHMO_F_DTERM}) if ((rc = ensure_field(H, l, f))) return rc;
     if (m.nbox <= 0) return 0;                                               // owner computes: none of this level's boxes is this rank's
     if (diffusion) {
         if ((rc = lev_target(H, l, st, t))) return rc;                       // the tables after the allocation
-        int n = 2 * m.maxny + 2 * m.maxnx;
-        hipLaunchKernelGGL(k_extrap_ghosts_m, dim3((n + 255) / 256, 1, m.nbox), dim3(256), 0, st, m.dv, m.fp, (int)SUHMO_F_MR);
-        hipLaunchKernelGGL(k_dcoef_faces_m, grid_m(m, 1, 1), dim3(64, 4), 0, st, m.dv, m.fp, ph, mp->rho_i);
-        hipLaunchKernelGGL(k_difterm_m, grid_m(m), dim3(64, 4), 0, st, m.dv, m.fp);
+        if ((rc = launch_diffusion_terms(stepping(m.on(), *mp), st))) return rc;
     }
-    if (final_) hipLaunchKernelGGL(k_melt_m<1>, grid_m(m), dim3(64, 4), 0, st, m.dv, m.fp, ph, *mp, dt);
-    else hipLaunchKernelGGL(k_melt_m<0>, grid_m(m), dim3(64, 4), 0, st, m.dv, m.fp, ph, *mp, dt);
-    HIPCHK(hipGetLastError());
-    return 0;
+    return launch_melt(stepping(m.on(), *mp), final_, dt, st);
 }
 // max h and max |h_lagged - h| over the cells of level l no finer level covers
 int hier_picard_maxima(suhmo_hier *H, int l, bool covered, double *maxh, double *maxd, hipStream_t st)
@@ -1026,7 +885,7 @@ int hier_picard_maxima(suhmo_hier *H, int l, bool covered, double *maxh, double 
     suhmo_level *slot = H->lev[0].box[0];
     if (t.base) {
         suhmo_level *L = t.base;
-        if ((rc = picard_maxima(L, L->d[0].fp.f[SUHMO_F_PHI], L->d[0].fp.f[SUHMO_F_HLAG], maxh, maxd, st, Excl{0, 0, 0, 0}, covered ? L->d[0].fp.f[SUHMO_F_COVER] : nullptr))) return rc;
+        if ((rc = picard_maxima(L, maxh, maxd, st, Excl{0, 0, 0, 0}, covered))) return rc;
         if (L->ar && (L->d[0].v.rk[0] || L->d[0].v.rk[1])) {                     // computeMax over the ranks of level 0
             if ((rc = L->ar(L->user, maxh))) return rc;
             if ((rc = L->ar(L->user, maxd))) return rc;
@@ -1036,9 +895,9 @@ int hier_picard_maxima(suhmo_hier *H, int l, bool covered, double *maxh, double 
     const suhmo_multi &m = t.m;
     *maxh = -1.0e300; *maxd = 0.0;
     if (m.nbox > 0) {
-        dim3 grd(std::min((m.maxnx + 63) / 64, 4), std::min((m.maxny + 3) / 4, 8), m.nbox);       // 2 values per block: 64 nbox doubles
-        hipLaunchKernelGGL(k_picard2_partial_m, grd, dim3(64, 4), 0, st, m.dv, m.fp, covered ? 1 : 0, m.red);
-        hipLaunchKernelGGL(k_max2_final, dim3(1), dim3(256), 0, st, m.red, (int)(grd.x * grd.y * grd.z), slot->scratch, suhmo_host_slot(slot));
+        int np;
+        if ((rc = launch_picard2_partial(m.on(), 4, 8, m.red, Excl{0, 0, 0, 0}, covered, &np, st))) return rc;     // 2 values per block: 64 nbox doubles
+        hipLaunchKernelGGL(k_max2_final, dim3(1), dim3(256), 0, st, m.red, np * m.nbox, slot->scratch, suhmo_host_slot(slot));
         HIPCHK(hipGetLastError());
         if ((rc = suhmo_readback(slot, st, maxh, maxd))) return rc;
     }
@@ -1065,7 +924,7 @@ struct BoxUnions {
             if ((rc = hier_ff(H, l, SUHMO_F_MR, -1, true, st))) return rc;               // levelmR.exchange() :2513
             if (l == 0) { Depth &D = base->d[0];
                 HIPCHK(hipMemcpyAsync(D.fp.f[SUHMO_F_HLAG], D.fp.f[SUHMO_F_PHI], D.elems * sizeof(double), hipMemcpyDeviceToDevice, st)); }
-            else { suhmo_multi m; if ((rc = multi_of(H, l, st, m)) || (rc = suhmo_multi_copy(m, SUHMO_F_HLAG, SUHMO_F_PHI, st))) return rc; }
+            else { suhmo_multi m; if ((rc = multi_of(H, l, st, m)) || (rc = launch_copy(m.on(), SUHMO_F_HLAG, SUHMO_F_PHI, st))) return rc; }
         }
         return 0;
     }
@@ -1076,7 +935,7 @@ struct BoxUnions {
         for (int l = 0; l < nlev; l++) {                                                        // aCoeff_bCoeff :3087-3102
             LevT t;
             if ((rc = lev_target(H, l, st, t))) return rc;
-            if (t.base) rc = suhmo_bcoef_faces(t.base, 0, st); else rc = suhmo_multi_bcoef_faces(t.m, H->lev[l].box[0]->ph, st);
+            rc = t.base ? launch_bcoef_faces(on_level(t.base, 0), st) : launch_bcoef_faces(t.m.on(), st);
             if (rc) return rc;
         }
         for (int l = 0; l < nlev; l++) if ((rc = hier_melt(H, l, mp, dt, 0, mp->diffFactor != 0.0, st))) return rc;
@@ -1090,7 +949,7 @@ struct BoxUnions {
         for (int l = 0; l + 1 < nlev; l++) {    // the averaged heads' rings as the oracle refills them: BC of every box, level 0's periodic sides
             if (l == 0) { if ((rc = suhmo_level_fill_ghosts(base, 0, SUHMO_F_PHI, 0, (suhmo_stream_t)st))) return rc; continue; }
             suhmo_multi m;
-            if ((rc = multi_of(H, l, st, m)) || (rc = suhmo_multi_fill_ghosts(m, SUHMO_F_PHI, 0, st))) return rc;
+            if ((rc = multi_of(H, l, st, m)) || (rc = launch_fill_ghosts(m.on(), SUHMO_F_PHI, 0, st))) return rc;
         }
         return 0;
     }
@@ -1119,7 +978,7 @@ struct BoxUnions {
                 for (int f : fd) if ((rc = ensure_field(G, l, f))) return rc;
                 suhmo_multi mh, mg;
                 if ((rc = multi_of(H, l, st, mh)) || (rc = multi_of(G, l, st, mg))) return rc;
-                if ((rc = suhmo_multi_copy_between(mg, mh, fd, fs, 4, st))) return rc;                                     // initial guess = b :3382-3385
+                if ((rc = launch_copy_between(mg.on(), mh.on(), fd, fs, 4, st))) return rc;                                     // initial guess = b :3382-3385
                 for (suhmo_level *L : gb) L->d[0].phi_fresh = 0;
                 continue;
             }
@@ -1146,11 +1005,8 @@ struct BoxUnions {
                 static const int fd[1] = {SUHMO_F_B}, fs[1] = {SUHMO_F_PHI};
                 suhmo_multi mh, mg;
                 if ((rc = multi_of(H, l, st, mh)) || (rc = multi_of(G, l, st, mg))) return rc;
-                if (mp->freeze_icefree_gap && mh.nbox > 0) {
-                    hipLaunchKernelGGL(k_keep_icefree_m, grid_m(mh), dim3(64, 4), 0, st, mh.dv, mh.fp, mg.fp);
-                    HIPCHK(hipGetLastError());
-                }
-                if ((rc = suhmo_multi_copy_between(mh, mg, fd, fs, 1, st))) return rc;
+                if (mp->freeze_icefree_gap && (rc = launch_keep_icefree(mh.on(), mg.on(), st))) return rc;
+                if ((rc = launch_copy_between(mh.on(), mg.on(), fd, fs, 1, st))) return rc;
             } else
                 for (size_t k = 0; k < hb.size(); k++) {
                     if (mp->freeze_icefree_gap && (rc = keep_icefree(hb[k], gb[k], st))) return rc;
