@@ -113,6 +113,16 @@ int suhmo_level_num_depths(const suhmo_level_t *L);
  * last launch where the streaming kernel runs depth 0; 0: always a pass of its own).  Read-only counters: overlapped_launches, agg_gathers,
  * rhs_in_streaming_launches, rhs_in_tile_launches, residual_in_relax_launches, vcycle_graph_replays (V-cycles that ran
  * as a launch of a captured graph).
+ * mask_known (default 1): what UpdateOperator finds out about the ice mask is kept until the mask is written again.  Contract: the mask
+ * of a level changes only through this library -- every entry point that writes a field the caller names (set_field, put_box, axby,
+ * set_value, divergence, fill_ghosts, unpack_rows, the exchanges (suhmo_hier_exchange included), suhmo_amr2_average / _set_covered / _reflux / _finer_operator_changed, suhmo_hier_average
+ * and the hierarchy's copies) notices when that field is SUHMO_F_MASK.  suhmo_level_field_view of SUHMO_F_MASK hands out a writable pointer the
+ * library cannot watch: from then on that level keeps nothing about its mask (as with mask_known = 0).  The first fused UpdateOperator of depth 0
+ * after a write scans for values below 1e-6 among everything it loads (cells, ghost ring, a strip's halo rows); the answer comes back
+ * through an asynchronous 4-byte copy and an event that later calls only query.  While it says "none", whole levels run the instantiations of
+ * the fused WFlx_level kernel and of the streaming relaxation that leave the mask out (no load, no register, no test); the results are the
+ * same bits.  0: the per-cycle report of skip_mask only.  Ensembles and box unions always read the mask.  Read-only: mask_scans,
+ * bcoef_unmasked_launches, relax_unmasked_launches (launches of graph replays included), mask_state (0 unknown, 1 clean, 2 dirty).
  * Not a kernel-selection knob (it changes the bits): bottom_solver (default 0: the cycle's bottom is its numBottom relaxes; 1: followed by
  * Chombo's RelaxSolver as the reference configures it, src/AmrHydro.cpp:623,628,726,733-735 -- up to 40 rounds of relax(2), ended by an l2
  * residual below 1e-6 x its first value or reduced by less than 10 %).  It reaches the level's agglomerated copy and its gap-height operator;

@@ -209,10 +209,14 @@ __global__ __launch_bounds__(256) void k_re_bcoef(OnBoxes t)
 // rows are 1040 instead of 528 bytes, so the 128-byte lines its unaligned ends drag in weigh half as much.
 // INTERIOR: the tile and its two-cell halo lie inside the level -- no boundary condition, no wrap, no missing cell: the
 // same expressions without the case distinctions (most tiles; uniform per workgroup)
-template <bool INTERIOR, int BT_X, int BT_Y>
-__device__ __forceinline__ void bcoef_tile(const DV &v, const FP &fp, const suhmo_phys_t &ph, int hasMask, double *sphi, double *sB, double *sM,
-                                           unsigned *negflag, unsigned epoch)
+// MASKED = false (the host knows the level's mask clean, suhmo_common.h: every value this kernel could read is >= 1e-6): no mask load, no
+// mask tile (18 instead of 26 KB of LDS), no mask test in the gradient, no report; bcoef_face sees two equal positive cells, so its early
+// return folds away.  The same expressions in the same order otherwise.
+template <bool INTERIOR, int BT_X, int BT_Y, bool MASKED>
+__device__ __forceinline__ void bcoef_tile(const DV &v, const FP &fp, const suhmo_phys_t &ph, int hasMask_, double *sphi, double *sB, double *sM,
+                                           unsigned *negflag, unsigned epoch, unsigned *smallflag)
 {
+    const int hasMask = MASKED ? hasMask_ : 0;
     constexpr int PW = BT_X + 4, PH = BT_Y + 4;     // phi tile: cells [i0-2, i0+BT_X+1] x [j0-2, j0+BT_Y+1]
     constexpr int RW = BT_X + 2, RH = BT_Y + 2;     // Re tile:  cells [i0-1, i0+BT_X]   x [j0-1, j0+BT_Y]
     constexpr int TX = BT_X + 2, TY = 256 / TX;     // threads of the workgroup: TX lanes along a row, TY rows at a time
@@ -257,20 +261,27 @@ __device__ __forceinline__ void bcoef_tile(const DV &v, const FP &fp, const suhm
     const bool xi = xin(i);
     double Br[NK];
     bool hasB[NK];
-    bool neg = false;
+    bool neg = false, small = false;
 #pragma unroll
     for (int k = 0; k < NK; k++) {
         const int lj = ty + TY * k, j = j0 - 1 + lj;
         hasB[k] = INTERIOR || (i >= -1 && i <= v.nx && j >= -v.gy && j <= v.ny + v.gy - 1 && !((i < 0 || i >= v.nx) && (j < 0 || j >= v.ny)));
         double b = 0.0, m = 0.0;
-        if (hasB[k]) { int idx = cidx(v, i, j); b = Bf[idx]; m = mk[idx]; }
-        neg = neg || (m < 0.0 && i >= 0 && i < v.nx && j >= 0 && j < v.ny);      // (no branch here: the loads of the unrolled rows stay batched)
+        if (hasB[k]) { int idx = cidx(v, i, j); b = Bf[idx]; if (MASKED) m = mk[idx]; }
+        if (MASKED) {
+            neg = neg || (m < 0.0 && i >= 0 && i < v.nx && j >= 0 && j < v.ny);      // (no branch here: the loads of the unrolled rows stay batched)
+            small = small || (hasB[k] && m < 1e-6 && j >= -1 && j <= v.ny);      // (rows beyond a physical side's ghost row are loaded, never used)
+        }
         Br[k] = b;
-        sB[lj * RW + tx] = b; sM[lj * RW + tx] = m;
+        sB[lj * RW + tx] = b;
+        if (MASKED) sM[lj * RW + tx] = m;
     }
     // this pass sees the ice mask of every cell of the level anyway: it leaves word whether any is negative, so that the relaxation
-    // launches of the same V-cycle may skip reading the array (suhmo_gsrb.hip; COMPUTENONLINEARTERMS only asks mask < 0)
-    if (negflag && neg) *negflag = epoch;
+    // launches of the same V-cycle may skip reading the array (suhmo_gsrb.hip; COMPUTENONLINEARTERMS only asks mask < 0) ...
+    if (MASKED && negflag && neg) *negflag = epoch;
+    // ... and, when the host asks (the first launch after a write to the mask), whether anything it loaded -- ghost ring included: the
+    // gradient's mask tests read no other cells -- is below the 1e-6 of those tests: if not, later launches leave the mask out
+    if (MASKED && smallflag && small) *smallflag = 1u;
     __syncthreads();
     // cell-centred gradient of the cell at phi-tile position p (k_gradcc); (gi, gj) = its indices
     auto gradcc = [&](int p, int gi, int gj, double &gx, double &gy) {
@@ -330,10 +341,10 @@ __device__ __forceinline__ void bcoef_tile(const DV &v, const FP &fp, const suhm
         for (int fy = ty; fy < nyt; fy += TY) {
             const int j = j0 + fy, idx = cidx(v, i, j), r = (fy + 1) * RW + tx;
             if (INTERIOR || j < v.ny)
-                bxo[idx] = bcoef_face(ph, sre[r], sre[r - 1], sB[r], sB[r - 1], sM[r], sM[r - 1], !INTERIOR && (i == 0 || i == v.nx));
+                bxo[idx] = bcoef_face(ph, sre[r], sre[r - 1], sB[r], sB[r - 1], MASKED ? sM[r] : 1.0, MASKED ? sM[r - 1] : 1.0, !INTERIOR && (i == 0 || i == v.nx));
             if (INTERIOR || i < v.nx) {
                 int jg = j + v.j0;
-                byo[idx] = bcoef_face(ph, sre[r], sre[r - RW], sB[r], sB[r - RW], sM[r], sM[r - RW], !INTERIOR && (jg == 0 || jg == v.nyg));
+                byo[idx] = bcoef_face(ph, sre[r], sre[r - RW], sB[r], sB[r - RW], MASKED ? sM[r] : 1.0, MASKED ? sM[r - RW] : 1.0, !INTERIOR && (jg == 0 || jg == v.nyg));
             }
         }
     }
@@ -341,45 +352,85 @@ __device__ __forceinline__ void bcoef_tile(const DV &v, const FP &fp, const suhm
 // rank strip: the relaxation also reads the ice mask of its halo rows (the neighbours' cells, on every depth that streams); k_bcoef_fused
 // reports on the strip's own cells, this one on the stored halo rows of the depths [0, nd)
 struct MaskHalo { const double *m[SUHMO_MAXDEPTH]; int nx[SUHMO_MAXDEPTH], ny[SUHMO_MAXDEPTH], P[SUHMO_MAXDEPTH], gy[SUHMO_MAXDEPTH]; int nd, lo, hi; };
-__global__ __launch_bounds__(256) void k_mask_halo_report(MaskHalo h, unsigned *negflag, unsigned epoch)
+// (smallflag: the scan, bcoef_tile.  At depth 0 it asks what k_bcoef_fused's gradient asks, `< 1e-6`, of the two halo rows that reads and of the two
+// ghost columns of the FIRST halo row of either side -- the only halo row whose Re enters a face, so the only one whose end cells' gradient
+// tests them; they are caller data, set with the ghosted field.  The deeper halo rows and the coarse depths only the relaxation reads: `< 0`)
+__global__ __launch_bounds__(256) void k_mask_halo_report(MaskHalo h, unsigned *negflag, unsigned epoch, unsigned *smallflag)
 {
     const int d = blockIdx.z, i = blockIdx.x * blockDim.x + threadIdx.x;
     if (d >= h.nd || i >= h.nx[d]) return;
     const int g = h.gy[d];
-    bool neg = false;
+    bool neg = false, small = false;
     for (int r = blockIdx.y; r < 2 * g; r += gridDim.y) {
         const bool top = r >= g;
         if (top ? !h.hi : !h.lo) continue;
         const int j = top ? h.ny[d] + (r - g) : -1 - r;
-        neg = neg || h.m[d][(long)(j + g) * h.P[d] + SUHMO_XOFF + i] < 0.0;
+        const double *__restrict__ row = h.m[d] + (long)(j + g) * h.P[d] + SUHMO_XOFF;
+        const double m = row[i];
+        neg = neg || m < 0.0;
+        const int dist = top ? r - g : r;      // 0: the halo row next to the strip
+        small = small || ((d == 0 && dist < 2) ? m < 1e-6 : m < 0.0);
+        if (smallflag && d == 0 && i == 0 && (j == -1 || j == h.ny[d])) small = small || row[-1] < 1e-6 || row[h.nx[d]] < 1e-6;
     }
-    if (neg) *negflag = epoch;
+    if (negflag && neg) *negflag = epoch;
+    if (smallflag && small) *smallflag = 1u;
 }
-template <int BT_X, int BT_Y>
-__device__ __forceinline__ void d_bcoef_fused(const DV &v, const FP &fp, const suhmo_phys_t &ph, int hasMask, unsigned *negflag, unsigned epoch)
+template <int BT_X, int BT_Y, bool MASKED>
+__device__ __forceinline__ void d_bcoef_fused(const DV &v, const FP &fp, const suhmo_phys_t &ph, int hasMask, unsigned *negflag, unsigned epoch, unsigned *smallflag)
 {
-    __shared__ double sphi[(BT_X + 4) * (BT_Y + 4)], sB[(BT_X + 2) * (BT_Y + 2)], sM[(BT_X + 2) * (BT_Y + 2)];
+    __shared__ double sphi[(BT_X + 4) * (BT_Y + 4)], sB[(BT_X + 2) * (BT_Y + 2)], sM[MASKED ? (BT_X + 2) * (BT_Y + 2) : 1];
     const int i0 = blockIdx.x * BT_X, j0 = blockIdx.y * BT_Y;
     const bool interior = i0 - 2 >= 0 && i0 + BT_X + 1 <= v.nx - 1 && j0 - 2 >= 0 && j0 + BT_Y + 1 <= v.ny - 1;
-    if (interior) bcoef_tile<true, BT_X, BT_Y>(v, fp, ph, hasMask, sphi, sB, sM, negflag, epoch);
-    else bcoef_tile<false, BT_X, BT_Y>(v, fp, ph, hasMask, sphi, sB, sM, negflag, epoch);
+    if (interior) bcoef_tile<true, BT_X, BT_Y, MASKED>(v, fp, ph, hasMask, sphi, sB, sM, negflag, epoch, smallflag);
+    else bcoef_tile<false, BT_X, BT_Y, MASKED>(v, fp, ph, hasMask, sphi, sB, sM, negflag, epoch, smallflag);
 }
-template <class T, int BT_X, int BT_Y>
-__global__ __launch_bounds__(256) void k_bcoef_fused(T t, unsigned *negflag, unsigned epoch)
+template <class T, int BT_X, int BT_Y, bool MASKED = true>
+__global__ __launch_bounds__(256) void k_bcoef_fused(T t, unsigned *negflag, unsigned epoch, unsigned *smallflag)
 {
     const suhmo_phys_t ph = t.phys();
-    if (std::is_same<T, OnMembers>::value) { negflag = nullptr; epoch = 0u; }      // an ensemble's relaxation always reads the ice mask: nobody takes a report
-    d_bcoef_fused<BT_X, BT_Y>(t.view(), t.fields(), ph, ph.use_mask_gradients, negflag, epoch);
+    if (std::is_same<T, OnMembers>::value) { negflag = nullptr; epoch = 0u; smallflag = nullptr; }      // an ensemble's relaxation always reads the ice mask: nobody takes a report
+    d_bcoef_fused<BT_X, BT_Y, MASKED>(t.view(), t.fields(), ph, ph.use_mask_gradients, negflag, epoch, smallflag);
 }
 // tiles of 62 x 14 cells on 64 x 4 threads; wide (an A/B option of large single levels): 126 x 14 on 128 x 2.  flag: the report on the ice
 // mask, or NULL (an ensemble: its relaxation always reads the mask).  The last tile column / row also owns the E / N faces
-template <class T> int launch_bcoef_fused(const T &t, bool wide, unsigned *flag, unsigned epoch, hipStream_t st)
+// small: the word of the scan for values below 1e-6, or NULL; unmasked (whole levels whose mask is known clean): the instantiation without the mask
+template <class T> int launch_bcoef_fused(const T &t, bool wide, unsigned *flag, unsigned epoch, hipStream_t st, unsigned *small, bool unmasked)
 {
-    if constexpr (std::is_same<T, OnLevel>::value)
-        if (wide) return launch_grid(k_bcoef_fused<T, 126, 14>, t, dim3((t.nx() + 125) / 126, (t.ny() + 13) / 14), dim3(128, 2), st, flag, epoch);
-    return launch_grid(k_bcoef_fused<T, 62, 14>, t, dim3((t.nx() + 61) / 62, (t.ny() + 13) / 14), dim3(64, 4), st, flag, epoch);
+    if constexpr (std::is_same<T, OnLevel>::value) {
+        const dim3 gw((t.nx() + 125) / 126, (t.ny() + 13) / 14), gn((t.nx() + 61) / 62, (t.ny() + 13) / 14);
+        unsigned *const none = nullptr;
+        if (unmasked && wide) return launch_grid(k_bcoef_fused<T, 126, 14, false>, t, gw, dim3(128, 2), st, none, 0u, none);
+        if (unmasked) return launch_grid(k_bcoef_fused<T, 62, 14, false>, t, gn, dim3(64, 4), st, none, 0u, none);
+        if (wide) return launch_grid(k_bcoef_fused<T, 126, 14>, t, gw, dim3(128, 2), st, flag, epoch, small);
+    }
+    return launch_grid(k_bcoef_fused<T, 62, 14>, t, dim3((t.nx() + 61) / 62, (t.ny() + 13) / 14), dim3(64, 4), st, flag, epoch, small);
 }
-template int launch_bcoef_fused(const OnMembers &, bool, unsigned *, unsigned, hipStream_t);
+template int launch_bcoef_fused(const OnMembers &, bool, unsigned *, unsigned, hipStream_t, unsigned *, bool);
+// the answer of a scan, if it has arrived (an event query: never a wait); a scan of a mask that has been written since is forgotten
+void suhmo_mask_poll(suhmo_level *L)
+{
+    if (!L->mask_scan_pending) return;
+    const hipError_t e = hipEventQuery(L->mask_ev);
+    if (e == hipErrorNotReady) { (void)hipGetLastError(); return; }
+    L->mask_scan_pending = 0;
+    // a query that fails for good (the event was recorded into a stream some caller is capturing, say): that scan has no answer; the state
+    // stays unknown and a later cycle scans again, three times at the most
+    if (e != hipSuccess) { (void)hipGetLastError(); L->mask_scan_errors++; return; }
+    if (L->mask_scan_version == L->mask_version) L->mask_state = *(volatile unsigned *)L->mask_host ? SUHMO_MASK_DIRTY : SUHMO_MASK_CLEAN;
+}
+int suhmo_mask_scan_begin(suhmo_level *L, hipStream_t st)
+{
+    if (!L->mask_ev) HIPCHK(hipEventCreateWithFlags(&L->mask_ev, hipEventDisableTiming));
+    HIPCHK(hipMemsetAsync(suhmo_mask_scan_word(L), 0, sizeof(unsigned), st));
+    return 0;
+}
+int suhmo_mask_scan_end(suhmo_level *L, hipStream_t st)
+{
+    HIPCHK(hipMemcpyAsync(L->mask_host, suhmo_mask_scan_word(L), sizeof(unsigned), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipEventRecord(L->mask_ev, st));
+    L->mask_scan_pending = 1; L->mask_scan_version = L->mask_version; L->mask_scans++;
+    return 0;
+}
 template <class T> int launch_re(const T &t, hipStream_t st) { return launch_over(k_re<T>, t, GHOSTED, st); }      // COMPUTERE on the ghosted box
 template <class T> int launch_bcoef_faces(const T &t, hipStream_t st) { return launch_over(k_bcoef_faces<T>, t, FACES, st); }
 template <class T> int launch_grad_cc(const T &t, hipStream_t st)      // the gradient and its ghosts (a level exchanges in between: suhmo_grad_cc)
@@ -395,6 +446,20 @@ template int launch_bcoef_faces(const OnBoxes &, hipStream_t);
 template int launch_bcoef_faces(const OnMembers &, hipStream_t);
 template int launch_grad_cc(const OnMembers &, hipStream_t);
 
+// fused single-kernel path: needs >= 3 cells per direction (extrapolation sources inside every
+// edge tile) and, on rank boundaries, 2 exchanged phi rows for the halo-row gradient
+static bool bcoef_is_fused(const suhmo_level *L, int depth)
+{
+    const Depth &D = L->d[depth];
+    return L->bcoef_fused && D.v.nx >= 4 && D.v.ny >= 4 && (!(D.v.ext[0] || D.v.ext[1]) || (D.v.gy >= 2 && D.v.ny >= 2))
+           && L->desc.nx_global == 0;      // AMR patches: un-fused kernels (coarse-fine ghosts are stored data)
+}
+// the next UpdateOperator of depth 0 would scan the ice mask (suhmo_common.h)
+bool suhmo_mask_would_scan(const suhmo_level *L)
+{
+    return L->mask_known && !L->mask_view && L->mask_scan_errors < 3 && L->mask_state == SUHMO_MASK_UNKNOWN && !L->mask_scan_pending && L->mask_host
+           && !L->mask_capturing && bcoef_is_fused(L, 0);
+}
 extern "C" int suhmo_level_update_operator(suhmo_level_t *L, int depth, suhmo_stream_t s)
 {
     SUHMO_TIME("VCAMRNonLinearPoissonOp::UpdateOperator");
@@ -402,10 +467,7 @@ extern "C" int suhmo_level_update_operator(suhmo_level_t *L, int depth, suhmo_st
     HIPCHK(hipSetDevice(L->device));
     hipStream_t st = (hipStream_t)s;
     Depth &D = L->d[depth];
-    // fused single-kernel path: needs >= 3 cells per direction (extrapolation sources inside every
-    // edge tile) and, on rank boundaries, 2 exchanged phi rows for the halo-row gradient
-    bool fused = L->bcoef_fused && D.v.nx >= 4 && D.v.ny >= 4 && (!(D.v.ext[0] || D.v.ext[1]) || (D.v.gy >= 2 && D.v.ny >= 2))
-                 && L->desc.nx_global == 0;      // AMR patches: un-fused kernels (coarse-fine ghosts are stored data)
+    const bool fused = bcoef_is_fused(L, depth);
     int rc = suhmo_ensure_phi_halo(L, depth, fused ? 2 : 1, st); if (rc) return rc;
     if (fused) {
         const bool wide = L->bcoef_tile_x == 126 && D.v.nx >= 256;
@@ -413,13 +475,25 @@ extern "C" int suhmo_level_update_operator(suhmo_level_t *L, int depth, suhmo_st
         // (the V-cycle that called takes the report up, suhmo_fas.hip: it holds until that cycle ends, not across calls of this entry point)
         unsigned *flag = nullptr;
         if (depth == 0) { L->maskflag_epoch = 0; L->mask_reported = 0; }
-        if (depth == 0 && L->skip_mask) {
-            flag = (unsigned *)(L->scratch + L->scratch_elems - 1);
+        // what is known about the mask across calls (suhmo_common.h): clean -> the kernel without it; unknown, nothing in flight, not inside a
+        // graph capture -> this launch scans: a second word (the other half of the report's double) is cleared, set by any workgroup that
+        // loads a value below 1e-6, copied to pinned memory behind the launch; an event marks the copy
+        if (depth == 0 && !L->mask_capturing) suhmo_mask_poll(L);
+        const bool unmasked = depth == 0 && suhmo_mask_clean(L, 0);
+        unsigned *small = nullptr;
+        const bool scan = depth == 0 && suhmo_mask_would_scan(L);
+        if (scan) { small = suhmo_mask_scan_word(L); if ((rc = suhmo_mask_scan_begin(L, st))) return rc; }
+        // inside a graph capture the masked kernels get the word too: the launch of the graph can then carry a scan, with the clear, the
+        // copy and the event around it (suhmo_fas.hip)
+        if (depth == 0 && L->mask_capturing && L->mask_known && !L->mask_view && !unmasked && L->mask_host) { small = suhmo_mask_scan_word(L); L->mask_scan_captured = 1; }
+        if (depth == 0 && L->skip_mask && !unmasked) {
+            flag = suhmo_mask_report_word(L);
             if (++L->mask_epoch == 0) L->mask_epoch = 1;
             L->mask_reported = 1;
         }
-        if ((rc = launch_bcoef_fused(on_level(L, depth), wide, flag, L->mask_epoch, st))) return rc;
-        if (flag && (D.v.ext[0] || D.v.ext[1])) {
+        if ((rc = launch_bcoef_fused(on_level(L, depth), wide, flag, L->mask_epoch, st, small, unmasked))) return rc;
+        if (unmasked) L->bcoef_unmasked++;
+        if ((flag || small) && (D.v.ext[0] || D.v.ext[1])) {
             MaskHalo h;
             h.nd = 0; h.lo = D.v.ext[0]; h.hi = D.v.ext[1];
             const int last = L->coarse_mask_ok ? (L->agg ? L->agg_depth : L->ndepth) : 1;      // (agglomerated depths keep no halo rows)
@@ -430,8 +504,9 @@ extern "C" int suhmo_level_update_operator(suhmo_level_t *L, int depth, suhmo_st
                 if (Dk.v.gy > gmax) gmax = Dk.v.gy;
                 h.nd = k + 1;
             }
-            hipLaunchKernelGGL(k_mask_halo_report, dim3((D.v.nx + 255) / 256, 2 * gmax, h.nd), dim3(256), 0, st, h, flag, L->mask_epoch);
+            hipLaunchKernelGGL(k_mask_halo_report, dim3((D.v.nx + 255) / 256, 2 * gmax, h.nd), dim3(256), 0, st, h, flag, L->mask_epoch, small);
         }
+        if (scan && (rc = suhmo_mask_scan_end(L, st))) return rc;
     } else {
         if (depth == 0) { L->maskflag_epoch = 0; L->mask_reported = 0; }
         if (!suhmo_field(L, depth, SUHMO_F_GRADX) || !suhmo_field(L, depth, SUHMO_F_GRADY) || !suhmo_field(L, depth, SUHMO_F_RE)) return -2;
@@ -790,6 +865,9 @@ int suhmo_build_mg_coefficients(suhmo_level *L, bool with_faces, hipStream_t st)
         if (L->agg && dep >= L->agg_depth) continue;                  // agglomerated depths: no halo rows, the whole rows travel below
         rc = suhmo_exchange_fields(L, dep, {SUHMO_F_ACOEF, SUHMO_F_B, SUHMO_F_PI, SUHMO_F_ZB, SUHMO_F_MASK}, st); if (rc) return rc;
     }
+    // a rank strip's scan looked at the halo rows of the depths whose masks were depth 0's averages at the time: if the coarse ones only
+    // become so now, it looks again
+    if (!L->coarse_mask_ok && (L->d[0].v.ext[0] || L->d[0].v.ext[1])) suhmo_mask_halo_written(L);
     L->coarse_mask_ok = 1;
     return suhmo_agg_gather_static(L, with_faces, st);
 }

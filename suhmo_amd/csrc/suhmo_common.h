@@ -134,6 +134,8 @@ struct VGraph {                 // a V-cycle captured for one set of solver para
     double *p1[SUHMO_MAXDEPTH], *a1[SUHMO_MAXDEPTH];     // ... and when it ends (an odd number of out-of-place launches on a depth swaps them)
     double *rhs;                                         // right-hand-side canvas of depth 0 the cycle was captured with
     int rout_req, rout_done, rout_np; const double *rout_rhs;     // the residual its last launch was asked to leave behind (resout_req, resout_rhs) and did
+    int mask_clean; long n_bcoef_unmasked, n_relax_unmasked;      // captured with the ice mask known clean (part of the key); its launches that leave the mask out
+    int has_scan;                                                 // its (masked) k_bcoef_fused also writes the scan word: a launch of it can carry a scan of the mask
 };
 struct ProfEv { hipEvent_t a, b; long cells; int restricts; };   // restricts: the launch also did the restriction (RST)
 
@@ -199,6 +201,22 @@ struct suhmo_level {
     int coarse_mask_ok;         // the ice masks of the depths > 0 are MGnewOp's averages of depth 0's current one (suhmo_build_mg_coefficients; any
                                 // write to the field clears it): the report about depth 0 then covers them (an average of non-negative cells)
     unsigned mask_epoch, maskflag_epoch;   // number of the last k_bcoef_fused call on depth 0; the call whose report is current (0: none)
+    // what is known about the ice mask ACROSS cycles (option mask_known, default 1; 0: only the per-cycle report above).  The mask is caller
+    // data: it changes through the entry points that write SUHMO_F_MASK (suhmo_mask_written) and, on a rank strip, through the halo rows an
+    // exchange brings (suhmo_mask_halo_written); between two writes what one scan found stays true.  CLEAN: every value k_bcoef_fused can
+    // read at depth 0 -- the level's cells, the stored ghost ring on the Re range, a strip's halo rows with their ghost columns -- is >= 1e-6,
+    // so `mask < 0`, `mask < 1e-6` and bcoef_face's early return are all constant there (and on the coarse depths while coarse_mask_ok
+    // holds: averages of such values, Neumann / periodic ghosts); DIRTY: the scan met a smaller value.  The first k_bcoef_fused after a write
+    // scans (widened report into a second device word), a 4-byte copy into pinned memory and an event follow it on the stream, and later
+    // launches ask the event (hipEventQuery: never a wait); until the answer is there everything runs as without the option.
+    int mask_known, mask_state;            // SUHMO_MASK_UNKNOWN / _CLEAN / _DIRTY
+    unsigned mask_version, mask_scan_version;   // writes so far; the one the scan in flight (mask_scan_pending) looked at
+    int mask_scan_pending, mask_capturing;      // (mask_capturing: inside a graph capture -- the masked kernels get the scan word, the host-side clear / copy / event stay outside)
+    int mask_scan_captured;                     // ... and such a kernel was captured (VGraph::has_scan)
+    int mask_view;                              // the caller holds a writable device pointer to the mask (suhmo_level_field_view): nothing about it is ever known
+    int mask_scan_errors;                       // event queries that failed for good (not "not ready"): after three the level stops scanning
+    unsigned *mask_host; hipEvent_t mask_ev;    // pinned word the scan's answer arrives in (0: nothing below 1e-6), the event behind the copy
+    long mask_scans, bcoef_unmasked, relax_unmasked;   // read-only options mask_scans, bcoef_unmasked_launches, relax_unmasked_launches
     int overlap_halo;           // rank strips, streaming kernel: the halo exchange travels on a second stream while the chunks that do not
                                 // read halo rows relax; the two end chunks follow (env SUHMO_OVERLAP_HALO; 1 = default: with the native, stream-ordered
                                 // RCCL transport only; 2 = with any hook, the caller vouches that it orders against the stream it is given; 0 = off)
@@ -220,6 +238,31 @@ struct suhmo_level {
                                 // (env SUHMO_TILE_T, 0 = by size)
 };
 
+enum { SUHMO_MASK_UNKNOWN = 0, SUHMO_MASK_CLEAN = 1, SUHMO_MASK_DIRTY = 2 };
+// a write to the ice mask of the level's cells or ghost ring: the coarse masks are no longer its averages, no report about it holds
+static inline void suhmo_mask_written(suhmo_level *L)
+{
+    L->coarse_mask_ok = 0; L->maskflag_epoch = 0;
+    L->mask_version++; L->mask_state = SUHMO_MASK_UNKNOWN;
+}
+// a write to the halo rows of a rank strip's mask only (the neighbours' cells): the strip's own averages stand, what a scan found does not
+static inline void suhmo_mask_halo_written(suhmo_level *L) { L->mask_version++; L->mask_state = SUHMO_MASK_UNKNOWN; }
+bool suhmo_mask_would_scan(const suhmo_level *L);   // suhmo_bcoef.hip: the next UpdateOperator of depth 0 scans the mask
+// the two device words behind the reductions' scratch (its last double): [0] the per-cycle report "a negative cell" (= the epoch), [1] the scan
+// "a value below 1e-6"; the scan's answer arrives in the pinned scratch at double SUHMO_HSCRATCH_MASK (the reductions use [0, 16))
+#define SUHMO_HSCRATCH_DOUBLES 64
+#define SUHMO_HSCRATCH_MASK 60
+static inline unsigned *suhmo_mask_report_word(const suhmo_level *L) { return (unsigned *)(L->scratch + L->scratch_elems - 1); }
+static inline unsigned *suhmo_mask_scan_word(const suhmo_level *L) { return suhmo_mask_report_word(L) + 1; }
+int suhmo_mask_scan_begin(suhmo_level *L, hipStream_t st);   // suhmo_bcoef.hip: clears the scan word on st ...
+int suhmo_mask_scan_end(suhmo_level *L, hipStream_t st);     // ... and, behind the kernels that set it, the copy to pinned memory and the event
+void suhmo_mask_poll(suhmo_level *L);      // suhmo_bcoef.hip: takes the answer of a scan up if it has arrived
+// the relaxation of `depth` may leave the mask out altogether (levels and rank strips, not AMR patches; the coarse depths while their masks
+// are depth 0's averages)
+static inline bool suhmo_mask_clean(const suhmo_level *L, int depth)
+{
+    return L->mask_known && !L->mask_view && L->mask_state == SUHMO_MASK_CLEAN && (depth == 0 || L->coarse_mask_ok) && L->desc.nx_global == 0;
+}
 void suhmo_set_error(const char *fmt, ...);
 // Named scoped timers with the reference's CH_TIME labels (src/VCAMRNonLinearPoissonOp.cpp:40,69,103,277,390,660; report =
 // CH_TIMER_REPORT, exec/A_SHMIP/Suhmo.cpp:136).  Off by default (one relaxed load per scope); suhmo_timers_enable(1): host wall

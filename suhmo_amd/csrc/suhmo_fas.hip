@@ -148,18 +148,36 @@ static int vcycle_graph(suhmo_level *L, const suhmo_solver_params_t *sp, int nd,
 {
     done = false;
     const int key[4] = {sp->num_smooth, sp->num_bottom, sp->bcoeff_otf, nd};
+    // what is known about the ice mask selects kernels (suhmo_common.h), so it is part of a graph's identity.  A cycle that scans the mask
+    // (unknown, no scan in flight) still runs as a graph where one exists: the masked kernels of a captured cycle write the scan word, and
+    // the clear before, the 4-byte copy and the event behind it go around the graph launch (a level whose mask is rewritten before every
+    // step keeps its replays and pays three small stream operations per write)
+    // (the launchers' own predicate, per depth: depth 0's answer in bit 0, the coarse depths' -- which also need coarse_mask_ok -- in bit 1)
+    const int mask_clean = (suhmo_mask_clean(L, 0) ? 1 : 0) | (L->ndepth > 1 && suhmo_mask_clean(L, 1) ? 2 : 0);
+    const bool scanning = sp->bcoeff_otf && suhmo_mask_would_scan(L);
+    auto launch = [&](const VGraph &g) {
+        int rc = 0;
+        if (scanning && (rc = suhmo_mask_scan_begin(L, (hipStream_t)s))) return rc;
+        HIPCHK(hipGraphLaunch(g.exec, (hipStream_t)s)); L->vgraph_replays++;
+        if (scanning && (rc = suhmo_mask_scan_end(L, (hipStream_t)s))) return rc;
+        return 0;
+    };
+    auto replayed = [&](const VGraph &g) {
+        L->bcoef_unmasked += g.n_bcoef_unmasked; L->relax_unmasked += g.n_relax_unmasked;
+        if (g.rout_done) { L->resout_done = 1; L->resout_count++; L->resout_np = g.rout_np; }
+    };
     auto at_start = [&](const VGraph &g) {
-        if (memcmp(g.key, key, sizeof(key))) return false;
+        if (memcmp(g.key, key, sizeof(key)) || g.mask_clean != mask_clean) return false;
         for (int d = 0; d < L->ndepth; d++) if (L->d[d].fp.f[SUHMO_F_PHI] != g.p0[d] || L->d[d].phi_alt != g.a0[d]) return false;
         if (g.rout_req != (L->resid_in_relax ? L->resout_req : 0) || g.rout_rhs != L->resout_rhs) return false;   // (what the last launch leaves behind)
         return L->d[0].fp.f[SUHMO_F_RHS] == g.rhs;                       // an AMR cycle runs level 0 on a second right-hand-side canvas (suhmo_hier.hip)
     };
     for (const VGraph &g : L->vgraphs)
         if (at_start(g)) {
-            if (!g.exec) return 0;                                       // known not to be capturable
-            HIPCHK(hipGraphLaunch(g.exec, (hipStream_t)s)); L->vgraph_replays++;
+            if (!g.exec || (scanning && !g.has_scan)) return 0;          // known not to be capturable (or no scan in it): eagerly
+            { int rc = launch(g); if (rc) return rc; }
             for (int d = 0; d < L->ndepth; d++) { L->d[d].fp.f[SUHMO_F_PHI] = g.p1[d]; L->d[d].phi_alt = g.a1[d]; } suhmo_fp_changed();
-            if (g.rout_done) { L->resout_done = 1; L->resout_count++; L->resout_np = g.rout_np; }
+            replayed(g);
             done = true;
             return 0;
         }
@@ -167,20 +185,25 @@ static int vcycle_graph(suhmo_level *L, const suhmo_solver_params_t *sp, int nd,
     for (int k = 0; k < 4; k++) if (L->vgraph_seen[k] != key[k]) { memcpy(L->vgraph_seen, key, sizeof(key)); return 0; }
     if (L->vgraphs.size() >= 16) return 0;                               // (pointer states keep changing: give up capturing)
     if (!L->gstream) HIPCHK(hipStreamCreateWithFlags(&L->gstream, hipStreamNonBlocking));
-    VGraph g; memcpy(g.key, key, sizeof(key)); g.exec = nullptr;
+    VGraph g; memcpy(g.key, key, sizeof(key)); g.exec = nullptr; g.mask_clean = mask_clean; g.has_scan = 0;
     for (int d = 0; d < SUHMO_MAXDEPTH; d++) { g.p0[d] = g.a0[d] = g.p1[d] = g.a1[d] = nullptr; }
     for (int d = 0; d < L->ndepth; d++) { g.p0[d] = L->d[d].fp.f[SUHMO_F_PHI]; g.a0[d] = L->d[d].phi_alt; }
     g.rhs = L->d[0].fp.f[SUHMO_F_RHS];
     g.rout_req = L->resid_in_relax ? L->resout_req : 0; g.rout_rhs = L->resout_rhs; g.rout_done = 0;
     const int rout_before = L->resout_done; const long rout_count = L->resout_count;
+    const long bcoef_unmasked = L->bcoef_unmasked, relax_unmasked = L->relax_unmasked;
     HIPCHK(hipStreamSynchronize((hipStream_t)s));                        // the private stream starts from a quiescent state
     hipGraph_t graph = nullptr;
     hipError_t e = hipStreamBeginCapture(L->gstream, hipStreamCaptureModeThreadLocal);
     int rc = 0;
     if (e == hipSuccess) {
+        L->mask_capturing = 1; L->mask_scan_captured = 0;
         rc = vcycle_body(L, sp, nd, (suhmo_stream_t)L->gstream);
+        L->mask_capturing = 0; g.has_scan = L->mask_scan_captured;
         e = hipStreamEndCapture(L->gstream, &graph);
     }
+    g.n_bcoef_unmasked = L->bcoef_unmasked - bcoef_unmasked; g.n_relax_unmasked = L->relax_unmasked - relax_unmasked;
+    L->bcoef_unmasked = bcoef_unmasked; L->relax_unmasked = relax_unmasked;
     g.rout_done = L->resout_count != rout_count;                         // (nothing was executed during capture: the flags go back)
     g.rout_np = L->resout_np;
     L->resout_done = rout_before; L->resout_count = rout_count;
@@ -196,10 +219,10 @@ static int vcycle_graph(suhmo_level *L, const suhmo_solver_params_t *sp, int nd,
     if (graph) (void)hipGraphDestroy(graph);
     (void)hipGetLastError();
     L->vgraphs.push_back(g);
-    if (!g.exec) return 0;                                               // run eagerly
-    HIPCHK(hipGraphLaunch(g.exec, (hipStream_t)s)); L->vgraph_replays++;
+    if (!g.exec || (scanning && !g.has_scan)) return 0;                  // run eagerly
+    if ((rc = launch(g))) return rc;
     for (int d = 0; d < L->ndepth; d++) { L->d[d].fp.f[SUHMO_F_PHI] = g.p1[d]; L->d[d].phi_alt = g.a1[d]; } suhmo_fp_changed();
-    if (g.rout_done) { L->resout_done = 1; L->resout_count++; L->resout_np = g.rout_np; }
+    replayed(g);
     done = true;
     return 0;
 }
@@ -214,6 +237,7 @@ extern "C" int suhmo_level_vcycle(suhmo_level_t *L, const suhmo_solver_params_t 
     const bool ext = D.v.ext[0] || D.v.ext[1];
     // (a bottom solved by the host loop decides on the host after every iteration: not capturable)
     const bool host_bottom = L->bottom_solver && !suhmo_bottom_one_launch(L, nd - 1);
+    suhmo_mask_poll(L);                     // (before a graph is chosen: the answer of a scan of the ice mask, if it is there)
     if (L->graph_max_cells > 0 && !L->ex && !ext && !L->prof_on && !host_bottom && (long)D.v.nx * D.v.ny <= L->graph_max_cells) {
         bool done = false;
         int rc = vcycle_graph(L, sp, nd, s, done);

@@ -321,15 +321,24 @@ struct FusedGeom {
     double *onorm;      // ... and the chunk's max |RES| (one partial per strip x chunk: k_norm_partial's job, for k_norm_final); NULL: not asked for
 };
 
-struct RowCoef {          // per-thread coefficients of its column pair in one row
-    double rhs[2], B[2], Pi[2], zb[2], mask[2], a[2], byS[2], byN[2];
+// MASKED = false: the level's ice mask is known clean (suhmo_common.h): the ring carries no mask, nothing loads, moves or tests it
+template <bool MASKED> struct RowMask { double mask[2]; };
+template <> struct RowMask<false> {};
+template <bool MASKED>
+struct RowCoef : RowMask<MASKED> {          // per-thread coefficients of its column pair in one row
+    double rhs[2], B[2], Pi[2], zb[2], a[2], byS[2], byN[2];
     double bx0, bx1, bx2;
 };
-#define CP2(d, s, f) d.f[0] = s.f[0]; d.f[1] = s.f[1]
-template <bool HAS_ALPHA>
-__device__ __forceinline__ void copy_coef(RowCoef &d, const RowCoef &s)
+template <bool MASKED> __device__ __forceinline__ double row_mask(const RowCoef<MASKED> &q, int a)
 {
-    CP2(d, s, rhs); CP2(d, s, B); CP2(d, s, Pi); CP2(d, s, zb); CP2(d, s, mask);
+    if constexpr (MASKED) return q.mask[a]; else return 1.0;
+}
+#define CP2(d, s, f) d.f[0] = s.f[0]; d.f[1] = s.f[1]
+template <bool HAS_ALPHA, bool MASKED>
+__device__ __forceinline__ void copy_coef(RowCoef<MASKED> &d, const RowCoef<MASKED> &s)
+{
+    CP2(d, s, rhs); CP2(d, s, B); CP2(d, s, Pi); CP2(d, s, zb);
+    if constexpr (MASKED) { CP2(d, s, mask); }
     if (HAS_ALPHA) { CP2(d, s, a); }
     CP2(d, s, byS); CP2(d, s, byN);
     d.bx0 = s.bx0; d.bx1 = s.bx1; d.bx2 = s.bx2;
@@ -340,7 +349,7 @@ __device__ __forceinline__ void copy_coef(RowCoef &d, const RowCoef &s)
 // visiting order, into the coarse cell of the thread's column pair (RESTRICTRESVCNL2D + RESTRICTVCNL, VCAMR...OpF.ChF:480-561,
 // 419-449): the separate pass over phi and the 8 coefficient arrays (75 B/cell) disappears.  Costs: one more ring row, one
 // more coefficient row, one more final row above and below the chunk and two more halo columns per side.
-template <int K, bool HAS_ALPHA, int NT, int RM = 0, bool FRHS = false>
+template <int K, bool HAS_ALPHA, int NT, int RM = 0, bool FRHS = false, bool MASKED = true>
 __global__ __launch_bounds__(NT) void k_gsrb_fused(DV v, FP fp, const double *__restrict__ pin,
                                                    double *__restrict__ pout, suhmo_phys_t ph, FusedGeom g)
 {
@@ -384,7 +393,7 @@ __global__ __launch_bounds__(NT) void k_gsrb_fused(DV v, FP fp, const double *__
 
     // coefficient ring as NAMED variables (an indexed array ends up in scratch memory):
     // cf0 = row r (being prefetched), cfM = row r-M
-    RowCoef cf0, cf1, cf2, cf3, cf4, cf5;
+    RowCoef<MASKED> cf0, cf1, cf2, cf3, cf4, cf5;
     double racc = 0.0, raccp = 0.0;        // RST: the coarse cell's sums after its first fine row
     double nmax = 0.0;                     // ROUT: max |RES| over this thread's cells of the chunk
     // physical-BC sides this tile can touch (uniform): skip the per-lane boundary tests elsewhere
@@ -393,8 +402,9 @@ __global__ __launch_bounds__(NT) void k_gsrb_fused(DV v, FP fp, const double *__
     double2 pnext = make_double2(0.0, 0.0);
     double2 pprev = make_double2(0.0, 0.0);    // FRHS: this thread's pair of the row below the one whose L(phi) is formed, as loaded
     // the mask array is 8 of the 80 bytes a cell costs per launch and only its sign is used: when this V-cycle's UpdateOperator saw
-    // no negative cell the loads are skipped (uniform)
-    const bool usemask = !g.negflag || *g.negflag == g.mask_epoch;
+    // no negative cell the loads are skipped (uniform); MASKED = false: the host knows already, the word is not read either
+    bool usemask = false;
+    if constexpr (MASKED) usemask = !g.negflag || *g.negflag == g.mask_epoch;
 
     int sr = 0;                            // LDS ring slot of row r
     // slot of an earlier row: sr - m, m <= R -- a compare instead of a division by 7 (the kernel issues nearly as many scalar as vector
@@ -419,7 +429,7 @@ __global__ __launch_bounds__(NT) void k_gsrb_fused(DV v, FP fp, const double *__
 #define LD2(dst, p, ix) { double2 t_ = ld2(p, ix); dst[0] = t_.x; dst[1] = t_.y; }
             LD2(cf0.rhs, (FRHS ? g.fres : f_rhs), idx); LD2(cf0.B, f_B, idx); LD2(cf0.Pi, f_Pi, idx);
             LD2(cf0.zb, f_zb, idx);
-            if (usemask) { LD2(cf0.mask, f_mask, idx); } else { cf0.mask[0] = 1.0; cf0.mask[1] = 1.0; }
+            if constexpr (MASKED) { if (usemask) { LD2(cf0.mask, f_mask, idx); } else { cf0.mask[0] = 1.0; cf0.mask[1] = 1.0; } }
             if (HAS_ALPHA) LD2(cf0.a, f_a, idx);
             LD2(cf0.byS, f_by, idx); LD2(cf0.byN, f_by, idx + v.P);
             double2 bxp = ld2(f_bx, idx);
@@ -450,7 +460,7 @@ __global__ __launch_bounds__(NT) void k_gsrb_fused(DV v, FP fp, const double *__
                         if (jf == v.ny - 1 && !v.ext[1]) n = (v.bct[1][1] == 0) ? v.two_v[1][1] - c : c + v.neu[1][1];
                     }
                     double nl, dnl;
-                    nl_terms(ph, c, cf1.B[a], cf1.Pi[a], cf1.zb[a], cf1.mask[a], nl, dnl);
+                    nl_terms(ph, c, cf1.B[a], cf1.Pi[a], cf1.zb[a], row_mask(cf1, a), nl, dnl);
                     const double bxW = a ? cf1.bx1 : cf1.bx0, bxE = a ? cf1.bx2 : cf1.bx1;
                     lo[a] = lofphi_cell(v, v.alpha, c, e, w, n, s, bxE, bxW, cf1.byN[a], cf1.byS[a], nl);
                     cc[a] = c;
@@ -479,7 +489,7 @@ __global__ __launch_bounds__(NT) void k_gsrb_fused(DV v, FP fp, const double *__
         // One half-sweep of row r-m.  The colour offset `a` (which cell of the pair is updated)
         // depends only on the row, so it is WAVE-UNIFORM: branch on it once (scalar branch) and
         // address the pair's coefficients statically instead of selecting per lane.
-        auto advance_a = [&](const int m, const RowCoef &q, auto a_tag) {
+        auto advance_a = [&](const int m, const RowCoef<MASKED> &q, auto a_tag) {
             constexpr int a = decltype(a_tag)::value;
             const int j = r - m;
             const int x = xl + a, i = im + a;
@@ -497,7 +507,7 @@ __global__ __launch_bounds__(NT) void k_gsrb_fused(DV v, FP fp, const double *__
                 if (j == v.ny - 1 && !v.ext[1]) n = (v.bct[1][1] == 0) ? v.two_v[1][1] - c : c + v.neu[1][1];
             }
             double nl, dnl;
-            nl_terms(ph, c, q.B[a], q.Pi[a], q.zb[a], q.mask[a], nl, dnl);
+            nl_terms(ph, c, q.B[a], q.Pi[a], q.zb[a], row_mask(q, a), nl, dnl);
             const double bxW = a ? q.bx1 : q.bx0, bxE = a ? q.bx2 : q.bx1;
             double aterm = HAS_ALPHA ? v.alpha * q.a[a] : v.alpha;
             double lofphi = lofphi_cell(v, aterm, c, e, w, n, s, bxE, bxW, q.byN[a], q.byS[a], nl);
@@ -505,7 +515,7 @@ __global__ __launch_bounds__(NT) void k_gsrb_fused(DV v, FP fp, const double *__
             double denom = 1.0e-16 + lam + dnl;
             lds[s0 * LW + x] = c + (q.rhs[a] - lofphi) / denom;
         };
-        auto advance = [&](const int m, const RowCoef &q) {
+        auto advance = [&](const int m, const RowCoef<MASKED> &q) {
             const int j = r - m;
             if (j >= jmin && j <= jmax) {                      // uniform
                 const int a = (j + v.j0 + ((m - 1) & 1)) & 1;  // uniform: colour offset of this row
@@ -527,7 +537,7 @@ __global__ __launch_bounds__(NT) void k_gsrb_fused(DV v, FP fp, const double *__
         if constexpr (RR) {
             const int jr = r - 2 * K - 1;
             if (own && jr >= jA && jr < jB && jr >= 0 && jr < v.ny) {    // (rank strips: halo rows are advanced, not restricted)
-                const RowCoef &q = (K >= 2) ? cf5 : cf3;
+                const RowCoef<MASKED> &q = (K >= 2) ? cf5 : cf3;
                 const int s0 = ring(sr - (2 * K + 1)), sN = ring(sr - 2 * K), sS = ring(sr - (2 * K + 2));
                 const double *row = lds + s0 * LW;
                 double acc = (jr & 1) ? racc : 0.0, accp = (jr & 1) ? raccp : 0.0;
@@ -546,7 +556,7 @@ __global__ __launch_bounds__(NT) void k_gsrb_fused(DV v, FP fp, const double *__
                         if (jr == v.ny - 1 && !v.ext[1]) n = (v.bct[1][1] == 0) ? v.two_v[1][1] - c : c + v.neu[1][1];
                     }
                     double nl, dnl;
-                    nl_terms(ph, c, q.B[a], q.Pi[a], q.zb[a], q.mask[a], nl, dnl);
+                    nl_terms(ph, c, q.B[a], q.Pi[a], q.zb[a], row_mask(q, a), nl, dnl);
                     const double bxW = a ? q.bx1 : q.bx0, bxE = a ? q.bx2 : q.bx1;
                     double aterm = HAS_ALPHA ? v.alpha * q.a[a] : v.alpha;
                     double lofphi = lofphi_cell(v, aterm, c, e, w, n, s, bxE, bxW, q.byN[a], q.byS[a], nl);
@@ -581,11 +591,11 @@ __global__ __launch_bounds__(NT) void k_gsrb_fused(DV v, FP fp, const double *__
         // ---- 4. row r+1 enters the ring (its slot held row r-2K-2: no longer read), rotate
         sr = sr + 1 == R ? 0 : sr + 1;
         if (in_row) { lds[sr * LW + xl] = pnext.x; lds[sr * LW + xl + 1] = pnext.y; }
-        if constexpr (RR && K >= 2) copy_coef<HAS_ALPHA>(cf5, cf4);
-        if constexpr (K >= 2) { copy_coef<HAS_ALPHA>(cf4, cf3); copy_coef<HAS_ALPHA>(cf3, cf2); }
-        else if constexpr (RR) copy_coef<HAS_ALPHA>(cf3, cf2);
-        copy_coef<HAS_ALPHA>(cf2, cf1);
-        copy_coef<HAS_ALPHA>(cf1, cf0);
+        if constexpr (RR && K >= 2) copy_coef<HAS_ALPHA, MASKED>(cf5, cf4);
+        if constexpr (K >= 2) { copy_coef<HAS_ALPHA, MASKED>(cf4, cf3); copy_coef<HAS_ALPHA, MASKED>(cf3, cf2); }
+        else if constexpr (RR) copy_coef<HAS_ALPHA, MASKED>(cf3, cf2);
+        copy_coef<HAS_ALPHA, MASKED>(cf2, cf1);
+        copy_coef<HAS_ALPHA, MASKED>(cf1, cf0);
     }
     if constexpr (ROUT) {
         if (g.onorm) {                         // (uniform) the chunk's max norm: a maximum, so the order of the lanes does not matter
@@ -628,19 +638,22 @@ static int launch_fused(suhmo_level *L, int depth, int ext_rows, hipStream_t st,
     // rows per chunk: all tiles resident in ONE round (tiles <= workgroup slots of the chip;
     // a partial second round costs a full one), but never shorter than 16K rows so that the
     // 4K-row pipeline fill stays small; measured on MI355X: profiles/r01_b_hc_sweep.log
+    // the ice mask is known clean (suhmo_common.h): the instantiation without it (alpha = 0 operators: the head solve)
+    const bool unmasked = suhmo_mask_clean(L, depth) && v.alpha == 0.0;
     {
-        static int slots_k[3] = {0, 0, 0};     // per (K, NT, RST) instantiation
-        if (!slots_k[K]) {
+        static int slots_k[3][2] = {{0, 0}, {0, 0}, {0, 0}};     // per (K, NT, RST) instantiation, with / without the mask: its own occupancy
+        if (!slots_k[K][unmasked]) {
             int nb = 0, ncu = 0, dev = 0;
             HIPCHK(hipGetDevice(&dev));
             HIPCHK(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev));
-            HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (k_gsrb_fused<K, false, NT, RM>), NT, 0));
-            slots_k[K] = (nb > 0 ? nb : 1) * (ncu > 0 ? ncu : 256);
+            if (unmasked) HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (k_gsrb_fused<K, false, NT, RM, false, false>), NT, 0));
+            else HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (k_gsrb_fused<K, false, NT, RM>), NT, 0));
+            slots_k[K][unmasked] = (nb > 0 ? nb : 1) * (ncu > 0 ? ncu : 256);
         }
         g.jbeg = v.ext[0] ? -ext_rows : 0;
         g.jend = v.ny + (v.ext[1] ? ext_rows : 0);
         const int nrows = g.jend - g.jbeg;
-        int nch = slots_k[K] / g.nstrips;
+        int nch = slots_k[K][unmasked] / g.nstrips;
         if (nch < 1) nch = 1;
         g.Hc = (nrows + nch - 1) / nch;
         // (not shorter than 8K rows: the 4K-row pipeline fill.  The one-round height itself is the optimum where it is allowed: 2048^2,
@@ -681,9 +694,9 @@ static int launch_fused(suhmo_level *L, int depth, int ext_rows, hipStream_t st,
     g.negflag = nullptr; g.mask_epoch = 0;
     // (the report is about depth 0's mask and, on a rank strip, the stored halo rows of every depth; the coarse masks are averages of
     //  depth 0's, MGnewOp: none of them is negative either -- as long as nobody has written one since, coarse_mask_ok)
-    if (L->skip_mask && L->maskflag_epoch && L->maskflag_epoch == L->mask_epoch && (depth == 0 || L->coarse_mask_ok)
+    if (!unmasked && L->skip_mask && L->maskflag_epoch && L->maskflag_epoch == L->mask_epoch && (depth == 0 || L->coarse_mask_ok)
         && (L->desc.nx_global == 0)) {
-        g.negflag = (const unsigned *)(L->scratch + L->scratch_elems - 1); g.mask_epoch = L->mask_epoch;
+        g.negflag = suhmo_mask_report_word(L); g.mask_epoch = L->mask_epoch;
     }
     g.rres = g.rphi = nullptr; g.rP = g.rgy = 0;
     if (RST) {
@@ -709,14 +722,18 @@ static int launch_fused(suhmo_level *L, int depth, int ext_rows, hipStream_t st,
             g.fres = D.fp.f[SUHMO_F_RES]; g.frhs = D.fp.f[SUHMO_F_RHS]; g.flphi = suhmo_field(L, depth, SUHMO_F_LPHI); g.fphiold = suhmo_field(L, depth, SUHMO_F_PHIOLD);
             if (!g.flphi || !g.fphiold) return -2;
             D.rhs_pending = 0; L->frhs_stream++;
-            hipLaunchKernelGGL((k_gsrb_fused<2, false, 64, false, true>), dim3(g.ntiles), dim3(NT), 0, st, v, D.fp, pin, D.phi_alt, L->ph, g);
+            if (unmasked) { hipLaunchKernelGGL((k_gsrb_fused<2, false, 64, 0, true, false>), dim3(g.ntiles), dim3(NT), 0, st, v, D.fp, pin, D.phi_alt, L->ph, g); L->relax_unmasked++; }
+            else hipLaunchKernelGGL((k_gsrb_fused<2, false, 64, 0, true>), dim3(g.ntiles), dim3(NT), 0, st, v, D.fp, pin, D.phi_alt, L->ph, g);
             { std::swap(D.fp.f[SUHMO_F_PHI], D.phi_alt); suhmo_fp_changed(); }
             return 0;
         } else { suhmo_set_error("internal: rhs_pending on a launch that cannot form it"); return -4; }
     }
     if (v.alpha != 0.0)
-        hipLaunchKernelGGL((k_gsrb_fused<K, true, NT, false>), dim3(g.ntiles), dim3(NT), 0, st, v, D.fp, pin, D.phi_alt, L->ph, g);
-    else
+        hipLaunchKernelGGL((k_gsrb_fused<K, true, NT, 0>), dim3(g.ntiles), dim3(NT), 0, st, v, D.fp, pin, D.phi_alt, L->ph, g);
+    else if (unmasked) {
+        hipLaunchKernelGGL((k_gsrb_fused<K, false, NT, RM, false, false>), dim3(g.ntiles), dim3(NT), 0, st, v, D.fp, pin, D.phi_alt, L->ph, g);
+        L->relax_unmasked++;
+    } else
         hipLaunchKernelGGL((k_gsrb_fused<K, false, NT, RM>), dim3(g.ntiles), dim3(NT), 0, st, v, D.fp, pin, D.phi_alt, L->ph, g);
     if (part != 1) { std::swap(D.fp.f[SUHMO_F_PHI], D.phi_alt); suhmo_fp_changed(); }
     return 0;
@@ -754,6 +771,8 @@ template <int T, bool RST> struct TileShape { static constexpr int TX = T, TY = 
 // four SIMDs, a second workgroup no longer fits beside the first, and the 2048^2 launch takes 266 us instead of 203.
 template <int S, int T, bool RST> struct TileThreads { static constexpr int NT = 256; };
 // (the body, shared by the solo kernel and the batched one below: blockIdx.x = tile)
+// (no MASKED parameter here, unlike k_gsrb_fused: tried on the plain alpha = 0 launches -- the mask is one load per pair kept as two sign
+// bits, the registers stay at the cap and the launches take what they took)
 template <int S, int T, bool HAS_ALPHA, bool RST = false, bool CHUNKED = false>
 __device__ __forceinline__ void d_gsrb_tile(const DV &v, const FP &fp, const double *__restrict__ pin, double *__restrict__ pout,
                                             const suhmo_phys_t &ph, const TileGeom &g)

@@ -30,7 +30,7 @@ template <class T> int launch_grad_cc(const T &t, hipStream_t st);         // ce
 template <class T> int launch_re(const T &t, hipStream_t st);              // COMPUTERE on the ghosted box
 template <class T> int launch_bcoef_faces(const T &t, hipStream_t st);
 template <class T> int launch_coef_ghosts(const T &t, int field, hipStream_t st);      // CopyGhostCells
-template <class T> int launch_bcoef_fused(const T &t, bool wide, unsigned *flag, unsigned epoch, hipStream_t st);   // UpdateOperator, the fused WFlx_level kernel
+template <class T> int launch_bcoef_fused(const T &t, bool wide, unsigned *flag, unsigned epoch, hipStream_t st, unsigned *small = nullptr, bool unmasked = false);   // UpdateOperator, the fused WFlx_level kernel
 int suhmo_multi_grad_cc(const suhmo_multi &m, hipStream_t st);      // launch_grad_cc, or one launch when m.merged
 int suhmo_multi_re_bcoef(const suhmo_multi &m, hipStream_t st);     // launch_re + launch_bcoef_faces, or one launch when m.merged
 int suhmo_multi_norm_max(const suhmo_multi &m, suhmo_level *slot, int field, double *out, hipStream_t st);                // max |x| over the valid cells of all boxes

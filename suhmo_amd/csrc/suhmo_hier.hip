@@ -85,6 +85,7 @@ int hier_copy(suhmo_hier *H, int l, int dst, int src, suhmo_stream_t s)
     if ((rc = ensure_field(H, l, dst)) || (rc = ensure_field(H, l, src))) return rc;
     if (dst == SUHMO_F_PHI) { for (suhmo_level *L : H->lev[l].box) L->d[0].phi_fresh = 0; H->phi_ver[l]++; }
     if (dst == SUHMO_F_PHI && l == 0) H->phi_shadow_fresh = false;
+    if (dst == SUHMO_F_MASK) for (suhmo_level *L : H->lev[l].box) suhmo_mask_written(L);
     if (l == 0) H->base_full_ver++;
     if (l == 0) {
         suhmo_level *L = base_of(H);
@@ -639,6 +640,7 @@ extern "C" int suhmo_hier_exchange(suhmo_hier_t *H, int l, int field, int corner
     int rc = check_hier(H); if (rc) return rc;
     ARG(l >= 0 && l < H->nlev && field >= 0 && field < SUHMO_F_COUNT);
     HIPCHK(hipSetDevice(H->device));
+    if (field == SUHMO_F_MASK) for (suhmo_level *L : H->lev[l].box) suhmo_mask_written(L);      // (ghost cells of the mask are rewritten)
     return hier_ff(H, l, field, -1, corners != 0, HST(s));
 }
 extern "C" int suhmo_hier_cf_interp(suhmo_hier_t *H, int l, int field_f, int field_c, suhmo_stream_t s)

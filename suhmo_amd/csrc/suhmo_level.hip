@@ -178,7 +178,7 @@ int suhmo_level_create_(suhmo_level_t **out, const suhmo_level_desc_t *desc, boo
     L->resout_req = L->resout_armed = L->resout_done = 0; L->resout_rhs = nullptr; L->resout_count = 0; L->resid_in_relax = 1;
     L->graph_max_cells = 1500000; L->gstream = nullptr; L->vgraph_replays = 0; memset(L->vgraph_seen, 0, sizeof(L->vgraph_seen));
     L->fused_min_cells = 1000000;
-    L->skip_mask = 1; L->poll_readback = 1;
+    L->skip_mask = 1; L->mask_known = 1; L->poll_readback = 1;
     L->bottom_solver = 0; L->bottom_one_launch_max_cells = 16384;    // (every bottom the one-launch kernel's LDS holds: up to 128 x 128)
     L->bottom_ctr = nullptr; L->bottom_host_iters = L->bottom_host_solves = 0;
     // ... and ONE place where the environment may override them, read when a level is created: the A/B runs DESIGN.md quotes and the tests that
@@ -193,7 +193,8 @@ int suhmo_level_create_(suhmo_level_t **out, const suhmo_level_desc_t *desc, boo
             {"SUHMO_RESID_IN_RELAX", &suhmo_level::resid_in_relax}, {"SUHMO_TILE_STRIPS", &suhmo_level::tile_strips}, {"SUHMO_TILE_CHUNKS", &suhmo_level::tile_chunks},
             {"SUHMO_TILE_RESTRICT", &suhmo_level::tile_restrict}, {"SUHMO_TILE_ORDER", &suhmo_level::tile_order}, {"SUHMO_FAS_RHS_IN_RELAX", &suhmo_level::fas_rhs_in_relax},
             {"SUHMO_TILE_S", &suhmo_level::tile_s}, {"SUHMO_GSRB_TILE", &suhmo_level::gsrb_tile}, {"SUHMO_TILE_T", &suhmo_level::tile_t},
-            {"SUHMO_FUSED_RESTRICT", &suhmo_level::fused_restrict}, {"SUHMO_SKIP_MASK", &suhmo_level::skip_mask}, {"SUHMO_POLL_READBACK", &suhmo_level::poll_readback}};
+            {"SUHMO_FUSED_RESTRICT", &suhmo_level::fused_restrict}, {"SUHMO_SKIP_MASK", &suhmo_level::skip_mask}, {"SUHMO_MASK_KNOWN", &suhmo_level::mask_known},
+            {"SUHMO_POLL_READBACK", &suhmo_level::poll_readback}};
         static const LongKnob longs[] = {
             {"SUHMO_AGG_MIN_CELLS", &suhmo_level::agg_min_cells}, {"SUHMO_TILE_MAX_CELLS", &suhmo_level::tile_max_cells},
             {"SUHMO_GRAPH_MAX_CELLS", &suhmo_level::graph_max_cells}, {"SUHMO_FUSED_MIN_CELLS", &suhmo_level::fused_min_cells},
@@ -248,6 +249,9 @@ int suhmo_level_create_(suhmo_level_t **out, const suhmo_level_desc_t *desc, boo
     }
     L->scratch = nullptr; L->scratch_elems = 0; L->hscratch = nullptr; L->hscratch_dev = nullptr; L->hseq = 0;
     L->mask_epoch = 0; L->maskflag_epoch = 0; L->mask_reported = 0; L->coarse_mask_ok = 0;
+    L->mask_state = SUHMO_MASK_UNKNOWN; L->mask_version = 1; L->mask_scan_version = 0; L->mask_scan_pending = 0; L->mask_capturing = 0;
+    L->mask_scan_captured = 0; L->mask_view = 0; L->mask_scan_errors = 0;
+    L->mask_host = nullptr; L->mask_ev = nullptr; L->mask_scans = L->bcoef_unmasked = L->relax_unmasked = 0;
     L->stub = 1;
     if (!stub) { int rc = level_storage(L); if (rc) { suhmo_level_destroy(L); return rc; } }
     *out = L;
@@ -269,8 +273,9 @@ static int level_storage(suhmo_level *L)
     L->scratch_elems = 16384;
     HIPCHK(hipMalloc(&L->scratch, L->scratch_elems * sizeof(double)));
     HIPCHK(hipMemset(L->scratch, 0, L->scratch_elems * sizeof(double)));                   // (its last word: the negative-mask report of k_bcoef_fused)
-    HIPCHK(hipHostMalloc(&L->hscratch, 64 * sizeof(double), hipHostMallocMapped | hipHostMallocCoherent));
-    memset(L->hscratch, 0, 64 * sizeof(double));
+    HIPCHK(hipHostMalloc(&L->hscratch, SUHMO_HSCRATCH_DOUBLES * sizeof(double), hipHostMallocMapped | hipHostMallocCoherent));
+    memset(L->hscratch, 0, SUHMO_HSCRATCH_DOUBLES * sizeof(double));
+    L->mask_host = (unsigned *)(L->hscratch + SUHMO_HSCRATCH_MASK);
     if (L->poll_readback && hipHostGetDevicePointer((void **)&L->hscratch_dev, L->hscratch, 0) != hipSuccess) { L->hscratch_dev = nullptr; L->poll_readback = 0; (void)hipGetLastError(); }
     return 0;
 }
@@ -295,6 +300,7 @@ extern "C" int suhmo_level_destroy(suhmo_level_t *L)
     if (L->xstream) { (void)hipStreamDestroy(L->xstream); (void)hipEventDestroy(L->xev[0]); (void)hipEventDestroy(L->xev[1]); }
     if (L->scratch) (void)hipFree(L->scratch);
     if (L->bottom_ctr) (void)hipFree(L->bottom_ctr);
+    if (L->mask_ev) (void)hipEventDestroy(L->mask_ev);
     if (L->hscratch) (void)hipHostFree(L->hscratch);
     delete L;
     return 0;
@@ -343,7 +349,7 @@ static int *option_slot_int(suhmo_level *L, const char *key)
     static const struct { const char *k; int suhmo_level::*m; } tab[] = {
         {"gsrb_variant", &suhmo_level::gsrb_variant}, {"fused_hc", &suhmo_level::fused_hc}, {"bcoef_fused", &suhmo_level::bcoef_fused}, {"bcoef_tile_x", &suhmo_level::bcoef_tile_x},
         {"fused_nt", &suhmo_level::fused_nt}, {"fused_restrict", &suhmo_level::fused_restrict}, {"strips_rhs_local", &suhmo_level::strips_rhs_local},
-        {"tile_strips", &suhmo_level::tile_strips}, {"overlap_halo", &suhmo_level::overlap_halo}, {"skip_mask", &suhmo_level::skip_mask}, {"tile_chunks",
+        {"tile_strips", &suhmo_level::tile_strips}, {"overlap_halo", &suhmo_level::overlap_halo}, {"skip_mask", &suhmo_level::skip_mask}, {"mask_known", &suhmo_level::mask_known}, {"tile_chunks",
             &suhmo_level::tile_chunks}, {"tile_order", &suhmo_level::tile_order}, {"tile_restrict", &suhmo_level::tile_restrict}, {"fas_rhs_in_relax",
             &suhmo_level::fas_rhs_in_relax}, {"resid_in_relax", &suhmo_level::resid_in_relax}, {"fas_rhs_fused", &suhmo_level::fas_rhs_fused},
         {"tile_s", &suhmo_level::tile_s}, {"gsrb_tile", &suhmo_level::gsrb_tile}, {"tile_t", &suhmo_level::tile_t}, {"poll_readback", &suhmo_level::poll_readback}};
@@ -386,6 +392,10 @@ extern "C" int suhmo_level_get_option(const suhmo_level_t *L, const char *key, l
     if (!strcmp(key, "rhs_in_streaming_launches")) { *value = L->frhs_stream; return 0; }   // read-only counters (fas_rhs_in_relax)
     if (!strcmp(key, "rhs_in_tile_launches")) { *value = L->frhs_tile; return 0; }
     if (!strcmp(key, "residual_in_relax_launches")) { *value = L->resout_count; return 0; }
+    if (!strcmp(key, "mask_scans")) { *value = L->mask_scans; return 0; }                 // read-only counters (mask_known)
+    if (!strcmp(key, "mask_state")) { *value = L->mask_state; return 0; }                 // 0 unknown, 1 clean, 2 dirty, as of the last V-cycle
+    if (!strcmp(key, "bcoef_unmasked_launches")) { *value = L->bcoef_unmasked; return 0; }
+    if (!strcmp(key, "relax_unmasked_launches")) { *value = L->relax_unmasked; return 0; }
     if (!strcmp(key, "vcycle_graph_replays")) { *value = L->vgraph_replays; return 0; }   // read-only counter (graph_max_cells)
     if (!strcmp(key, "bottom_solver")) { *value = L->bottom_solver; return 0; }
     if (!strcmp(key, "bottom_one_launch_max_cells")) { *value = L->bottom_one_launch_max_cells; return 0; }
@@ -437,6 +447,7 @@ extern "C" int suhmo_level_exchange(suhmo_level_t *L, int depth, int field, suhm
         if (!suhmo_field(L, depth, field)) return -2;
         int rc = L->ex(L->user, L, depth, &field, 1, s);
         if (!rc && field == SUHMO_F_PHI) L->d[depth].phi_fresh = suhmo_halo_rows(v);
+        if (field == SUHMO_F_MASK) suhmo_mask_halo_written(L);
         return rc;
     }
     return 0;
@@ -460,6 +471,8 @@ extern "C" int suhmo_level_field_view(suhmo_level_t *L, int depth, int field, do
     CHECK_DF(L, depth, field);
     double *p = suhmo_field(L, depth, field);
     if (!p) { suhmo_set_error("field allocation failed"); return -2; }
+    // a writable pointer to the ice mask: the library no longer sees the writes, so it stops keeping anything about the mask for good
+    if (field == SUHMO_F_MASK) { L->mask_view = 1; suhmo_mask_written(L); suhmo_level_drop_graphs(L); }
     if (base) *base = p;
     if (pitch) *pitch = L->d[depth].v.P;
     if (origin) *origin = cidx(L->d[depth].v, 0, 0);
@@ -502,7 +515,7 @@ extern "C" int suhmo_level_set_field(suhmo_level_t *L, int depth, int field, con
     CHECK_DF(L, depth, field); ARG(src);
     HIPCHK(hipSetDevice(L->device));
     if (field == SUHMO_F_PHI) phi_changed(L, depth);
-    if (field == SUHMO_F_MASK) { L->coarse_mask_ok = 0; L->maskflag_epoch = 0; }
+    if (field == SUHMO_F_MASK) suhmo_mask_written(L);
     return field_io(L, depth, field, (double *)src, ghosted, on_device, true, (hipStream_t)s);
 }
 extern "C" int suhmo_level_get_field(suhmo_level_t *L, int depth, int field, double *dst, int ghosted,
@@ -532,7 +545,7 @@ extern "C" int suhmo_level_put_box(suhmo_level_t *L, int depth, int field, int i
     hipStream_t st = (hipStream_t)s;
     const DV &v = L->d[depth].v;
     if (field == SUHMO_F_PHI) phi_changed(L, depth);
-    if (field == SUHMO_F_MASK) { L->coarse_mask_ok = 0; L->maskflag_epoch = 0; }
+    if (field == SUHMO_F_MASK) suhmo_mask_written(L);
     int r[4]; box_region(L, depth, field, ibox, r);
     int j0 = v.j0;                         // fab indices are global: local j = global j - j0
     flo0 -= v.i0; fhi0 -= v.i0;            // ... and local i = global i - i0 (AMR patch)
@@ -617,6 +630,7 @@ extern "C" int suhmo_level_unpack_rows(suhmo_level_t *L, int depth, int field, i
     const DV &v = L->d[depth].v;
     ARG(rows >= 1 && rows <= v.gy);
     HIPCHK(hipSetDevice(L->device));
+    if (field == SUHMO_F_MASK) suhmo_mask_halo_written(L);
     int jstart = side == 0 ? -rows : v.ny;        // ghost rows of that side, ascending j
     if (field == SUHMO_F_BY && side == 1) jstart = v.ny + 1;   // face row ny is owned (see pack)
     hipLaunchKernelGGL(k_unpack_rows, grid2d(v.nx + 1, rows), BLK2D, 0, (hipStream_t)s, v, suhmo_field(L, depth, field), jstart, rows, dev_buf);
