@@ -503,6 +503,13 @@ int suhmo_hier_moulin_source(suhmo_hier_t *H, int n_moulins, const double *posit
  *   suhmo_batch_create    n_members (1 .. 64) whole levels from one descriptor: nx, ny, dx, dy, max_box (hence the depth count), alpha / beta, BC types
  *                         and periodicity are shared (a batch call on members that differ in them fails with rc -1); a descriptor of a rank strip or an AMR patch is refused (rc -5), n_members out of range rc -1,
  *                         no device rc -3
+ *   suhmo_batch_create_opts   the same with creation options "key=value,...": bottom_solver=1 -- every V-cycle of the batch (and of the gap batch of
+ *                         implicit_gap) ends with Chombo's RelaxSolver after its numBottom relaxes, as level option bottom_solver = 1 does on a member run
+ *                         alone, bit for bit: ONE more launch per cycle whatever n_members, one workgroup per active member, each with its own loop
+ *                         and break test.  The option changes the results and needs allocations, so it is fixed for the life of the batch.  Only the
+ *                         one-launch path exists: a bottom depth of more than 16384 cells (or bottom_one_launch_max_cells) is refused with rc -5 and a
+ *                         message naming its size, here and by a call whose max_depth makes such a depth the bottom.  NULL or "": suhmo_batch_create.
+ *                         An unknown key or a value other than 0 / 1: rc -1.
  *   suhmo_batch_member    member k as an ordinary level handle, owned by the batch (suhmo_level_destroy on it fails with rc -1): its fields, BC
  *                         VALUES (suhmo_level_set_bc with the shared types) and physics constants are per member, loaded and read through
  *                         suhmo_level_put_box / get_box / set_field / get_field / set_bc / norm / ...
@@ -523,14 +530,19 @@ int suhmo_hier_moulin_source(suhmo_hier_t *H, int n_moulins, const double *posit
  *                         (freeze_icefree_gap per member), one fills the ghosts of b.  A batch may mix both kinds; use_impl_diff with diffFactor = 0
  *                         on a member: rc -1.  Moulin sources / recharge: suhmo_level_moulin_source / suhmo_level_time_varying_recharge on the
  *                         member handle.
- *   suhmo_batch_set_option / get_option   tile_order (0 .. 2, as the level's); bottom_solver: only 0 (1 is refused with rc -5: the bottom of a
- *                         batched cycle is its numBottom relaxes); implicit_gap (0 / 1, default 0: see suhmo_batch_timestep).  Read-only counters:
- *                         batch_launches, batch_readbacks (both include the gap solves), batch_member_cycles (V-cycles of head solves summed over
- *                         the members that ran them), batch_gap_member_cycles (the same for the gap solves).  An unknown key: rc -1.
+ *   suhmo_batch_set_option / get_option   tile_order (0 .. 2, as the level's); bottom_solver: get reports the creation value, set returns 0 for
+ *                         that value and rc -5 for the other one (fixed at creation: suhmo_batch_create_opts); implicit_gap (0 / 1, default 0: see
+ *                         suhmo_batch_timestep).  Read-only counters: batch_launches, batch_readbacks (both include the gap solves),
+ *                         batch_member_cycles (V-cycles of head solves summed over the members that ran them), batch_gap_member_cycles (the same for
+ *                         the gap solves), bottom_solver_iterations and bottom_solves_one_launch (RelaxSolver's iterations and solves summed over
+ *                         the members, the gap solves included; the same keys on a member handle: that member alone).  An unknown key: rc -1.
+ *                         Every batch call first checks that bottom_solver of every member handle is the batch's: a member set to the other value
+ *                         through suhmo_level_set_option makes the call fail with rc -5 before anything is launched.
  * A batch relaxes every depth with the tile kernel (colour passes where the grid rules it out); eager launches only, no graph capture.
- * Not built: rank strips, AMR patches and hierarchies as members, graph capture, bottom_solver = 1. */
+ * Not built: rank strips, AMR patches and hierarchies as members, graph capture, a host-loop RelaxSolver for bottoms the one launch cannot take. */
 typedef struct suhmo_batch suhmo_batch_t;
 int suhmo_batch_create(suhmo_batch_t **out, const suhmo_level_desc_t *desc, int n_members);
+int suhmo_batch_create_opts(suhmo_batch_t **out, const suhmo_level_desc_t *desc, int n_members, const char *options);
 int suhmo_batch_destroy(suhmo_batch_t *B);
 int suhmo_batch_size(const suhmo_batch_t *B);
 suhmo_level_t *suhmo_batch_member(suhmo_batch_t *B, int k);

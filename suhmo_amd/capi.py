@@ -82,7 +82,7 @@ SYMBOLS = [
     "suhmo_level_set_reduce_hook", "suhmo_level_dot", "suhmo_level_set_allgather", "suhmo_level_agglomerated_depth",
     "suhmo_hier_create_opts", "suhmo_hier_set_option", "suhmo_hier_get_option",
     "suhmo_batch_create", "suhmo_batch_destroy", "suhmo_batch_size", "suhmo_batch_member", "suhmo_batch_set_phys", "suhmo_batch_vcycle", "suhmo_batch_solve", "suhmo_batch_timestep",
-    "suhmo_batch_set_option", "suhmo_batch_get_option",
+    "suhmo_batch_set_option", "suhmo_batch_get_option", "suhmo_batch_create_opts",
 ]
 
 
@@ -212,6 +212,7 @@ def lib():
     L.suhmo_level_set_option.argtypes = [vp, C.c_char_p, C.c_long]
     L.suhmo_level_get_option.argtypes = [vp, C.c_char_p, C.POINTER(C.c_long)]
     L.suhmo_batch_create.argtypes = [C.POINTER(vp), C.POINTER(LevelDesc), ci]
+    L.suhmo_batch_create_opts.argtypes = [C.POINTER(vp), C.POINTER(LevelDesc), ci, C.c_char_p]
     L.suhmo_batch_destroy.argtypes = [vp]
     L.suhmo_batch_size.argtypes = [vp]
     L.suhmo_batch_member.argtypes = [vp, ci]

@@ -10,6 +10,9 @@ int suhmo_batch_gsrb_tile(const BatchTab &t, const BatchTab *coarse, const DV *v
                           bool has_alpha, int order, hipStream_t st);
 bool suhmo_batch_tile_ok(const DV &v);                    // the tile kernel can relax this depth (else colour passes)
 int suhmo_batch_single_tile(const DV &v);                 // the depth is ONE tile of this edge (all its sweeps in one launch), or 0
+// suhmo_bottom.hip: RelaxSolver::solve of the members' bottom depth, one workgroup per active member in ONE launch; ctr[k]: the device
+// counters of member k (iterations, solves).  The depth must fit the LDS (suhmo_bottom_fits)
+int suhmo_batch_relax_solve(const OnMembers &t, bool has_alpha, unsigned long long *const *ctr, hipStream_t st);
 // suhmo_ops.hip
 int launch_fas_coarse_rhs(const OnMembers &t, bool has_alpha, hipStream_t st);
 // RES = rhs - L(phi) of depth 0 and max |RES| of every active member: two launches, slot[k] <- the norm of member k, then the sequence number

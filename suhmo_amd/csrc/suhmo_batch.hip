@@ -16,6 +16,7 @@
 // batch the first one owns: N handles with the linear operator of gap_level_prepare (suhmo_step.hip), their own tables, the same cycle and
 // solve loop.  Its beta = dt x diffFactor is the member's own (the kernels read it from the member's row).
 #include "suhmo_batch.h"
+#include <algorithm>
 #include <new>
 
 struct suhmo_batch {
@@ -42,6 +43,10 @@ struct suhmo_batch {
     int implicit_gap;                                       // option: members with use_impl_diff are stepped (default 0: refused)
     suhmo_batch *gap;                                       // the gap batch, created by the first step that needs it; its counters add to this one's
     std::vector<double> gap_beta;                           // beta its handle of member k holds
+    // creation option bottom_solver (suhmo_batch_create_opts): RelaxSolver after the bottom relaxes of every cycle, one workgroup per member in one
+    // launch (suhmo_bottom.hip).  Every member handle holds the same value; d_ctr[k]: the device counters of member k (its bottom_ctr)
+    int bottom_solver; long bottom_max_cells;
+    unsigned long long **d_ctr;
 };
 constexpr int SLOT_FLAG = 2 * SUHMO_BATCH_MAX;             // pinned slot: two values per member, then the sequence number
 
@@ -154,13 +159,33 @@ static int batch_relax(suhmo_batch *B, int dep, int sweeps, const BatchSel &sel,
     }
     return 0;
 }
-// fas_cycle of suhmo_fas.hip for whole levels (no rank strips, bottom = its numBottom relaxes), `frhs`: this depth's first relaxation
-// forms its FAS right-hand side
+// the bottom depth `dep` of a batch with bottom_solver = 1 runs in the one launch (the only path a batch has): 0, or -5 and a message
+static int batch_bottom_fits(const suhmo_batch *B, int dep)
+{
+    const DV &v = view(B, dep);
+    const long cells = (long)v.nx * v.ny;
+    if (cells <= 16384 && cells <= B->bottom_max_cells) return 0;
+    suhmo_set_error("batch: bottom_solver = 1 with a bottom depth of %d x %d = %ld cells: a batch runs RelaxSolver in one launch only, on at most %ld cells "
+                    "(16384, and bottom_one_launch_max_cells)", v.nx, v.ny, cells, std::min(16384L, B->bottom_max_cells));
+    return -5;
+}
+// fas_cycle of suhmo_fas.hip for whole levels (no rank strips), `frhs`: this depth's first relaxation forms its FAS right-hand side
 static int batch_fas_cycle(suhmo_batch *B, int dep, const suhmo_solver_params_t *sp, int nd, const BatchSel &sel, hipStream_t st, bool frhs)
 {
     int rc;
     const int S = sp->num_smooth;
-    if (dep == nd - 1) return batch_relax(B, dep, sp->num_bottom, sel, st, dep == 0, frhs, false);
+    if (dep == nd - 1) {
+        if (!B->bottom_solver) return batch_relax(B, dep, sp->num_bottom, sel, st, dep == 0, frhs, false);   // bottom relaxes
+        // bottom relaxes, then RelaxSolver of every active member in one launch; its loop ends on a residual evaluation, whose ghost fill is
+        // the inhomogeneous one: that is what a depth-0 bottom leaves in the ghost ring
+        if ((rc = batch_relax(B, dep, sp->num_bottom, sel, st, false, frhs, false))) return rc;
+        if ((rc = suhmo_batch_relax_solve(on(B, dep, sel), B->has_alpha, B->d_ctr, st))) return rc;
+        B->launches++;
+        if (dep != 0) return 0;
+        if ((rc = launch_fill_ghosts(on(B, 0, sel), SUHMO_F_PHI, 0, st))) return rc;
+        B->launches++;
+        return 0;
+    }
     if ((rc = batch_relax(B, dep, S, sel, st, false, frhs, false))) return rc;                        // pre-smooth
     if ((rc = launch_restrict(on(B, dep, sel), on(B, dep + 1, sel), true, B->has_alpha, st))) return rc;   // RES, PHI of dep + 1
     B->launches++;
@@ -183,6 +208,7 @@ static int batch_vcycle(suhmo_batch *B, const suhmo_solver_params_t *sp, const B
     int rc, nd = B->ndepth;
     if (sel.n <= 0) return 0;
     if (sp->max_depth >= 0 && sp->max_depth + 1 < nd) nd = sp->max_depth + 1;
+    if (B->bottom_solver && (rc = batch_bottom_fits(B, nd - 1))) return rc;                             // (max_depth moves the bottom)
     if (sp->bcoeff_otf) {                                                                               // UpdateOperator, AverageOperator on every depth > 0
         if ((rc = launch_bcoef_fused(on(B, 0, sel), false, nullptr, 0u, st))) return rc;
         B->launches++;
@@ -206,8 +232,12 @@ static BatchSel all_members(const suhmo_batch *B)
 static int batch_enter(suhmo_batch *B, hipStream_t st)
 {
     HIPCHK(hipSetDevice(B->device));
-    for (suhmo_level *L : B->mem)
-        if (L->bottom_solver) { suhmo_set_error("batch: bottom_solver = 1 on a member is not built (the bottom of a batched cycle is its numBottom relaxes)"); return -5; }
+    for (int k = 0; k < B->n; k++)
+        if (B->mem[k]->bottom_solver != B->bottom_solver) {
+            suhmo_set_error("batch: bottom_solver = %d on member %d, %d on the batch: the option is fixed when the batch is created (suhmo_batch_create_opts) and "
+                            "shared by all members", B->mem[k]->bottom_solver, k, B->bottom_solver);
+            return -5;
+        }
     return batch_sync(B, st);
 }
 
@@ -222,12 +252,13 @@ extern "C" int suhmo_batch_destroy(suhmo_batch_t *B)
     if (B->partial) (void)hipFree(B->partial);
     if (B->d_avg) (void)hipFree(B->d_avg);
     if (B->d_mp) (void)hipFree(B->d_mp);
+    if (B->d_ctr) (void)hipFree(B->d_ctr);
     if (B->hslot) (void)hipHostFree(B->hslot);
     if (B->gap) (void)suhmo_batch_destroy(B->gap);
     delete B;
     return 0;
 }
-static int batch_create(suhmo_batch **out, const suhmo_level_desc_t *desc, int n_members, bool beta_per_member)
+static int batch_create(suhmo_batch **out, const suhmo_level_desc_t *desc, int n_members, bool beta_per_member, int bottom_solver)
 {
     *out = nullptr;
     if (n_members < 1 || n_members > SUHMO_BATCH_MAX) { suhmo_set_error("batch: n_members = %d, must be 1 .. %d", n_members, SUHMO_BATCH_MAX); return -1; }
@@ -242,6 +273,7 @@ static int batch_create(suhmo_batch **out, const suhmo_level_desc_t *desc, int n
     if (!B) { suhmo_set_error("out of memory"); return -2; }
     B->n = n_members; B->device = desc->device; B->has_alpha = desc->alpha != 0.0; B->tile_order = 0;
     B->beta_per_member = beta_per_member; B->implicit_gap = 0; B->gap = nullptr;
+    B->bottom_solver = bottom_solver; B->bottom_max_cells = 0; B->d_ctr = nullptr;
     auto fail = [&](int rc) { (void)suhmo_batch_destroy(B); return rc; };
     for (int k = 0; k < n_members; k++) {
         suhmo_level *L = nullptr;
@@ -249,9 +281,23 @@ static int batch_create(suhmo_batch **out, const suhmo_level_desc_t *desc, int n
         if (rc) return fail(rc);                              // (no device: rc -3 with suhmo_level_create's message)
         L->batch_owned = 1;
         B->mem.push_back(L);
+        if (k == 0) {                                         // (a bottom the one launch cannot take: refused before the other members are allocated)
+            B->ndepth = L->ndepth; B->bottom_max_cells = L->bottom_one_launch_max_cells;
+            if (bottom_solver && batch_bottom_fits(B, B->ndepth - 1)) return fail(-5);
+        }
     }
-    B->ndepth = B->mem[0]->ndepth;
     if (hipSetDevice(B->device) != hipSuccess) { suhmo_set_error("batch: hipSetDevice failed"); return fail(-2); }
+    if (bottom_solver) {                                      // the members take the option (and their counters) as a level does; the rows of d_ctr never change
+        std::vector<unsigned long long *> ctr;
+        for (suhmo_level *L : B->mem) {
+            int rc = suhmo_bottom_configure(L, 1, B->bottom_max_cells); if (rc) return fail(rc);
+            ctr.push_back(L->bottom_ctr);
+        }
+        if (hipMalloc(&B->d_ctr, n_members * sizeof(unsigned long long *)) != hipSuccess
+            || hipMemcpy(B->d_ctr, ctr.data(), n_members * sizeof(unsigned long long *), hipMemcpyHostToDevice) != hipSuccess) {
+            suhmo_set_error("batch: hipMalloc failed"); return fail(-2);
+        }
+    }
     for (suhmo_level *L : B->mem)
         for (int dep = 0; dep < B->ndepth; dep++) {
             Depth &D = L->d[dep];
@@ -287,11 +333,24 @@ static int batch_create(suhmo_batch **out, const suhmo_level_desc_t *desc, int n
     *out = B;
     return 0;
 }
-extern "C" int suhmo_batch_create(suhmo_batch_t **out, const suhmo_level_desc_t *desc, int n_members)
+// "key=value,key=value": the creation options (bottom_solver), the defaults for the keys it does not name
+extern "C" int suhmo_batch_create_opts(suhmo_batch_t **out, const suhmo_level_desc_t *desc, int n_members, const char *options)
 {
     ARG(out && desc);
-    return batch_create(out, desc, n_members, false);
+    int bottom_solver = 0;
+    for (const char *p = options ? options : ""; *p;) {
+        while (*p == ',' || *p == ' ') p++;
+        if (!*p) break;
+        const char *e = p + strcspn(p, ",=");
+        if (*e != '=' || e - p != 13 || strncmp(p, "bottom_solver", 13)) { suhmo_set_error("unknown batch option '%.*s' in \"%s\"", (int)(e - p), p, options); return -1; }
+        const long v = atol(e + 1);
+        if (v != 0 && v != 1) { suhmo_set_error("batch: bottom_solver: 0 (bottom relaxes only) or 1 (RelaxSolver)"); return -1; }
+        bottom_solver = (int)v;
+        p = e + strcspn(e, ",");
+    }
+    return batch_create(out, desc, n_members, false, bottom_solver);
 }
+extern "C" int suhmo_batch_create(suhmo_batch_t **out, const suhmo_level_desc_t *desc, int n_members) { return suhmo_batch_create_opts(out, desc, n_members, nullptr); }
 extern "C" int suhmo_batch_size(const suhmo_batch_t *B) { return B ? B->n : 0; }
 extern "C" suhmo_level_t *suhmo_batch_member(suhmo_batch_t *B, int k)
 {
@@ -398,7 +457,7 @@ static int gap_batch_prepare(suhmo_batch *B, const suhmo_model_params_t *mp, dou
         for (int a = 0; a < 2; a++) for (int b = 0; b < 2; b++) { d.bc.type[a][b] = 1; d.bc.value[a][b] = 0.0; }
         d.phys.use_NL = 0; d.alpha = 1.0; d.beta = dt * mp[0].diffFactor;
         suhmo_batch *G = nullptr;
-        if ((rc = batch_create(&G, &d, B->n, true))) return rc;
+        if ((rc = batch_create(&G, &d, B->n, true, B->bottom_solver))) return rc;                      // (the same bottom solver: gap_level_prepare)
         B->gap = G;
         B->gap_beta.assign(B->n, d.beta);
         for (suhmo_level *L : G->mem)
@@ -469,12 +528,13 @@ extern "C" int suhmo_batch_set_option(suhmo_batch_t *B, const char *key, long va
     ARG(B && key);
     if (!strcmp(key, "tile_order")) { ARG(value >= 0 && value <= 2); B->tile_order = (int)value; return 0; }
     if (!strcmp(key, "bottom_solver")) {
-        if (value == 0) return 0;
-        suhmo_set_error("batch: bottom_solver = %ld is not built (the one-launch RelaxSolver keeps its loop state per level; the bottom of a batched cycle is its numBottom relaxes)", value);
+        if (value == B->bottom_solver) return 0;
+        suhmo_set_error("batch: bottom_solver = %ld on a batch created with %d: the option is fixed at creation (suhmo_batch_create_opts)", value, B->bottom_solver);
         return -5;
     }
     if (!strcmp(key, "implicit_gap")) { ARG(value == 0 || value == 1); B->implicit_gap = (int)value; return 0; }
-    if (!strcmp(key, "batch_launches") || !strcmp(key, "batch_readbacks") || !strcmp(key, "batch_member_cycles") || !strcmp(key, "batch_gap_member_cycles")) { suhmo_set_error("batch: option %s is read-only", key); return -1; }
+    if (!strcmp(key, "batch_launches") || !strcmp(key, "batch_readbacks") || !strcmp(key, "batch_member_cycles") || !strcmp(key, "batch_gap_member_cycles")
+        || !strcmp(key, "bottom_solver_iterations") || !strcmp(key, "bottom_solves_one_launch")) { suhmo_set_error("batch: option %s is read-only", key); return -1; }
     suhmo_set_error("batch: unknown option %s", key);
     return -1;
 }
@@ -482,7 +542,13 @@ extern "C" int suhmo_batch_get_option(const suhmo_batch_t *B, const char *key, l
 {
     ARG(B && key && value);
     if (!strcmp(key, "tile_order")) *value = B->tile_order;
-    else if (!strcmp(key, "bottom_solver")) *value = 0;
+    else if (!strcmp(key, "bottom_solver")) *value = B->bottom_solver;
+    else if (!strcmp(key, "bottom_solver_iterations") || !strcmp(key, "bottom_solves_one_launch")) {      // summed over the members, the gap batch's included
+        const int which = strcmp(key, "bottom_solver_iterations") ? 1 : 0;
+        *value = 0;
+        for (const suhmo_batch *b : {B, (const suhmo_batch *)B->gap})
+            if (b) for (const suhmo_level *L : b->mem) *value += suhmo_bottom_counter(L, which);
+    }
     else if (!strcmp(key, "implicit_gap")) *value = B->implicit_gap;
     else if (!strcmp(key, "batch_launches")) *value = B->launches + (B->gap ? B->gap->launches : 0);
     else if (!strcmp(key, "batch_readbacks")) *value = B->readbacks + (B->gap ? B->gap->readbacks : 0);

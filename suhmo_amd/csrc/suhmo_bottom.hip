@@ -11,14 +11,19 @@
 //   k_relax_solve   the whole loop in ONE launch of one workgroup: phi of the bottom depth lives in LDS for the whole solve, the
 //                   coefficients are read through L2, the l2 norm is a fixed-order reduction in LDS, the break test runs on the device.
 //                   Whole-level depths of up to 128 x 128 cells (and up to bottom_one_launch_max_cells).  A fixed launch: the V-cycle
-//                   stays capturable as a graph.
-//   host loop       everything else (larger bottoms, rank strips whose bottom is not agglomerated, AMR patches): the same loop from
+//                   stays capturable as a graph.  One __global__ template over the launch target (suhmo_target.h): OnLevel is that one
+//                   workgroup; OnMembers (an ensemble created with bottom_solver=1, suhmo_batch.hip) is one workgroup per ACTIVE member in
+//                   one launch, each with its own loop, break test and counters -- a member's iteration count and bits are those of the
+//                   same level run alone, and no workgroup waits for another.  The LDS stays the static 128 KiB: a workgroup then has a CU
+//                   to itself, and an ensemble has at most 64 members for the part's 256 CUs, so sizing it to the depth would buy no
+//                   concurrency the launch lacks (nothing measured).
+//   host loop      everything else (larger bottoms, rank strips whose bottom is not agglomerated, AMR patches): the same loop from
 //                   the existing launches (suhmo_launch_gsrb, suhmo_level_residual, suhmo_level_norm) and one 8-byte read-back per
 //                   iteration.  A level whose bottom takes it is not replayed as a graph (suhmo_fas.hip).
 // Every update and every residual is the expression of k_gsrb_pass_simple / k_apply<., 1> on the same operands: the same bits.  Only
 // the order of the l2 sum differs from the oracle's serial one (the tests' tolerance for l2 norms; only a near-tie at a break test
 // could show it).
-#include "suhmo_common.h"
+#include "suhmo_batch.h"
 #include <cmath>
 
 #define SUHMO_BOTTOM_NT 1024
@@ -98,8 +103,10 @@ __device__ double lds_residual_l2(const DV &v, const FP &fp, const suhmo_phys_t 
     return sqrt(r);
 }
 
+// RelaxSolver::solve of ONE whole depth by the workgroup that runs it: the loop state (norm, first, it) lives in that workgroup's registers,
+// phi and the wave sums in its LDS, and nothing is synchronised beyond the workgroup.  ctr: iterations, solves of that depth's level
 template <bool HAS_ALPHA>
-__global__ __launch_bounds__(SUHMO_BOTTOM_NT) void k_relax_solve(DV v, FP fp, suhmo_phys_t ph, unsigned long long *__restrict__ counters)
+__device__ __forceinline__ void d_relax_solve(const DV &v, const FP &fp, const suhmo_phys_t &ph, unsigned long long *__restrict__ ctr)
 {
     __shared__ double p[SUHMO_BOTTOM_LDS_CELLS];
     __shared__ double wsum[SUHMO_BOTTOM_NT / 64];
@@ -130,8 +137,28 @@ __global__ __launch_bounds__(SUHMO_BOTTOM_NT) void k_relax_solve(DV v, FP fp, su
         if (norm < 1.0e-6 * first || norm > old * (1.0 - 0.1)) break;
     }
     for (int k = threadIdx.x; k < ncell; k += SUHMO_BOTTOM_NT) { const int j = k / v.nx, i = k - j * v.nx; phi[cidx(v, i, j)] = p[k]; }
-    if (threadIdx.x == 0) { atomicAdd(counters, (unsigned long long)it); atomicAdd(counters + 1, 1ull); }
+    if (threadIdx.x == 0) { atomicAdd(ctr, (unsigned long long)it); atomicAdd(ctr + 1, 1ull); }
 }
+// one workgroup per launch target: the depth of a level (OnLevel), or the bottom depth of every ACTIVE member of an ensemble (OnMembers:
+// blockIdx.z -> member; its view, constants and counters are copied from the member's rows once, fields() hands out the head canvas the
+// relaxation before has left current).  Members stop after their own iteration counts; none waits for another.
+// C: the counters of the level (unsigned long long *), or a device row of them per member
+template <class T, bool HAS_ALPHA, class C>
+__global__ __launch_bounds__(SUHMO_BOTTOM_NT) void k_relax_solve(T t, C counters)
+{
+    const DV v = t.view();
+    const FP fp = t.fields();
+    const suhmo_phys_t ph = t.phys();
+    d_relax_solve<HAS_ALPHA>(v, fp, ph, row_of(t, counters));
+}
+template <class T, class C> static int launch_relax_solve(const T &t, bool has_alpha, C counters, hipStream_t st)
+{
+    if ((long)t.nx() * t.ny() > SUHMO_BOTTOM_LDS_CELLS) { suhmo_set_error("internal: RelaxSolver in one launch on %d x %d cells: more than the LDS holds", t.nx(), t.ny()); return -4; }
+    if (has_alpha) return launch_grid(k_relax_solve<T, true, C>, t, dim3(1), dim3(SUHMO_BOTTOM_NT), st, counters);
+    return launch_grid(k_relax_solve<T, false, C>, t, dim3(1), dim3(SUHMO_BOTTOM_NT), st, counters);
+}
+// an ensemble: one launch for the members `t` at their bottom depth; ctr[k]: the device counters of member k (iterations, solves)
+int suhmo_batch_relax_solve(const OnMembers &t, bool has_alpha, unsigned long long *const *ctr, hipStream_t st) { return launch_relax_solve(t, has_alpha, ctr, st); }
 
 // the bottom depth `dep` of L takes the one-launch path
 bool suhmo_bottom_one_launch(const suhmo_level *L, int dep)
@@ -180,9 +207,7 @@ int suhmo_bottom_solve(suhmo_level *L, int dep, int tail, hipStream_t st)
     SUHMO_TIME("RelaxSolver::solve");
     Depth &D = L->d[dep];
     if (suhmo_bottom_one_launch(L, dep)) {
-        if (D.v.alpha != 0.0) hipLaunchKernelGGL(k_relax_solve<true>, dim3(1), dim3(SUHMO_BOTTOM_NT), 0, st, D.v, D.fp, L->ph, L->bottom_ctr);
-        else hipLaunchKernelGGL(k_relax_solve<false>, dim3(1), dim3(SUHMO_BOTTOM_NT), 0, st, D.v, D.fp, L->ph, L->bottom_ctr);
-        HIPCHK(hipGetLastError());
+        int rc1 = launch_relax_solve(on_level(L, dep), D.v.alpha != 0.0, L->bottom_ctr, st); if (rc1) return rc1;
         D.phi_fresh = 0;
         return 0;
     }

@@ -303,9 +303,11 @@ class _BoxView(HipLevel):
 class HipBatch:
     """An ensemble of n whole levels on one grid (suhmo_batch_*, suhmo_amd/csrc/suhmo_batch.hip): V-cycles and solves of all members
     through one launch sequence, every member bit for bit what it is alone.  bc gives the shared BC types and periodicity (and the
-    values every member starts with), phys the constants every member starts with; member(k) is an ordinary level."""
+    values every member starts with), phys the constants every member starts with; member(k) is an ordinary level.
+    bottom_solver=True (creation option bottom_solver=1 of suhmo_batch_create_opts): RelaxSolver after the bottom relaxes of every cycle, as
+    level option bottom_solver = 1 on every member run alone; fixed for the life of the batch."""
 
-    def __init__(self, n, nx, ny, dx, dy, bc, phys, alpha=0.0, beta=-1.0, max_box=64, device=0, stream=None):
+    def __init__(self, n, nx, ny, dx, dy, bc, phys, alpha=0.0, beta=-1.0, max_box=64, device=0, stream=None, bottom_solver=False):
         self.n, self.nx, self.ny, self.dx, self.dy = n, nx, ny, dx, dy
         self.stream = C.c_void_p(stream) if stream else C.c_void_p(0)
         d = capi.LevelDesc()
@@ -313,7 +315,7 @@ class HipBatch:
         d.nbox, d.boxes, d.max_box, d.alpha, d.beta = 0, None, max_box, alpha, beta
         d.bc, d.phys, d.device, d.halo_rows = _bc(bc), _phys(phys), device, 1
         h = C.c_void_p()
-        check(capi.lib().suhmo_batch_create(C.byref(h), C.byref(d), n))
+        check(capi.lib().suhmo_batch_create_opts(C.byref(h), C.byref(d), n, b"bottom_solver=1" if bottom_solver else None))
         self.h = h
         self._members = [_BoxView(capi.lib().suhmo_batch_member(h, k), nx, ny, dx, dy, self.stream) for k in range(n)]
         self.ndepth = self._members[0].ndepth

@@ -125,15 +125,16 @@ class HipBatchModel:
     dt and step number; per member every field, the BC values, the physics constants and the model parameters.  models: one dict per member
     (as HipModel's); phys / bc: one for all or a list per member.  Every member's results are those of a HipModel run alone, bit for bit.
     implicit_gap=True (batch option implicit_gap): members with use_impl_diff=1 are stepped too, their gap-height solves as one launch
-    sequence; explicit and implicit members may share a batch.  Off, such a member is refused."""
+    sequence; explicit and implicit members may share a batch.  Off, such a member is refused.
+    bottom_solver=True: the head solves and the implicit gap-height solves end every V-cycle with RelaxSolver (HipBatch), as the reference does."""
 
     FIELDS = HipModel.FIELDS
 
-    def __init__(self, nx, ny, dx, dy, bc, phys, models, max_box=64, device=0, implicit_gap=False):
+    def __init__(self, nx, ny, dx, dy, bc, phys, models, max_box=64, device=0, implicit_gap=False, bottom_solver=False):
         n = len(models)
         bcs = list(bc) if isinstance(bc, (list, tuple)) else [bc] * n
         phs = list(phys) if isinstance(phys, (list, tuple)) else [phys] * n
-        self.batch = lv.HipBatch(n, nx, ny, dx, dy, bcs[0], phs[0], alpha=0.0, beta=-1.0, max_box=max_box, device=device)
+        self.batch = lv.HipBatch(n, nx, ny, dx, dy, bcs[0], phs[0], alpha=0.0, beta=-1.0, max_box=max_box, device=device, bottom_solver=bottom_solver)
         self.n, self.nx, self.ny, self.dx, self.dy = n, nx, ny, dx, dy
         if implicit_gap:
             self.batch.set_option("implicit_gap", 1)

@@ -9,6 +9,12 @@ Both sides start from the SHMIP initial state and take `--warmup` steps (past th
 Prints for every n
     (a) wall time per batched step, (b) wall time of n solo steps, (b)/(a), launches and read-backs per batched step, V-cycles per step.
     python tools/batch_bench.py [--suite A|B] [--only both|batch|solo] [--n 1,2,4,6,8,16,32] [--steps 200] [--warmup 60] [--repeat 5]
+
+--bottom-solver: the batched step without and with the creation option bottom_solver (RelaxSolver after the bottom relaxes of every V-cycle,
+one workgroup per member in one launch) against n solo steps with level option bottom_solver = 1, for two workloads at 320 x 64: SHMIP A3 and the
+tutorial run's model (exec/0_convergence_channelized: moulin, ramp, diffusion, implicit gap-height solve; tools/convergence_channelized.py).  The
+two batches do not compute the same bits (the option changes every cycle): V-cycles per step and member are printed next to the milliseconds.
+    python tools/batch_bench.py --bottom-solver [--n 1,6,16,32] [--steps 50] [--warmup 60] [--repeat 3]
 """
 import argparse
 import json
@@ -53,15 +59,86 @@ def runs(step, sync, steps, repeat):
     return statistics.median(out), min(out), max(out)
 
 
+def bottom_solver_table(a):
+    """--bottom-solver: per workload and n, the batched step with the option off and on, and n solo steps with bottom_solver = 1"""
+    sys.path.insert(0, os.path.join(ROOT, "tools"))
+    import convergence_channelized as cc
+    print("# batched time step at %d x %d with and without RelaxSolver at the bottom of every V-cycle; %d timed steps after %d, median of %d runs [min .. max], ms per step"
+          % (NX, NY, a.steps, a.warmup, a.repeat))
+    print("# workload   n   (a) batch, bottom_solver=0    (b) batch, bottom_solver=1    (c) n solo steps, bottom_solver=1   (a)/(b)  (c)/(b)  "
+          "V-cycles/step/member (a) (b)   gap V-cycles/step/member (a) (b)   launches/step (a) (b)   RelaxSolver iterations/solve (b)")
+    for name in ("a3", "tutorial"):
+        if name == "a3":
+            m, bc, ph = sy.shmip_a_model("A3"), sy.A3_BC, sy.A3_PHYS
+            st, src, ramp = sy.shmip_initial_state(NX, NY, m["lx"], m["ly"]), None, None
+        else:
+            m, bc, ph, ramp = dict(cc.MODEL), cc.BC, cc.PHYS, cc.ramp
+            st = cc.basic_state(NX, NY)
+            L = model.HipModel(NX, NY, st["dx"], st["dy"], bc, ph, m, max_box=64)
+            L.moulin_source(cc.MOULIN[0], cc.MOULIN[1], cc.MOULIN[2], 1.0)
+            src = L.get("msrc")
+            L.close()
+        implicit = bool(m.get("use_impl_diff", 0))
+        for n in [int(x) for x in a.n.split(",")]:
+            Bs = [model.HipBatchModel(NX, NY, st["dx"], st["dy"], bc, ph, [m] * n, max_box=64, implicit_gap=implicit, bottom_solver=on) for on in (False, True)]
+            Ls = [model.HipModel(NX, NY, st["dx"], st["dy"], bc, ph, m, max_box=64) for _ in range(n)]
+            for L in Ls:
+                L.level.set_option("bottom_solver", 1)
+            for k in range(n):
+                for M in [B.member(k) for B in Bs] + [Ls[k]]:
+                    M.set_state(st)
+                    if src is not None:                      # (the tutorial run: its moulin, and the melt rate it starts from)
+                        M.level.set(lv.F_MSRC, src)
+                        M.level.set(lv.F_MR, np.full((NY, NX), m["G"] / m["L"]))
+            res = []
+            for B in Bs + [None]:
+                cyc, stepno = [0], [0]
+
+                def step():
+                    r = float(ramp(stepno[0] * m["dt"])) if ramp else None
+                    stepno[0] += 1
+                    if B:
+                        if r is not None:
+                            for k in range(n):
+                                B.set_model(k, ramp=r)
+                        cyc[0] += sum(B.timestep(m["dt"])[1])
+                    else:
+                        for L in Ls:
+                            if r is not None:
+                                L._mp.ramp = r
+                            cyc[0] += L.timestep(m["dt"])[1]
+
+                for _ in range(a.warmup):
+                    step()
+                keys = ("batch_launches", "batch_gap_member_cycles", "bottom_solver_iterations", "bottom_solves_one_launch")
+                o0, c0 = [B.get_option(k) for k in keys] if B else [0] * 4, cyc[0]
+                t = runs(step, (B.member(0) if B else Ls[0]).level.synchronize, a.steps, a.repeat)
+                o1 = [B.get_option(k) for k in keys] if B else [0] * 4
+                nst = a.steps * a.repeat
+                res.append((t, (cyc[0] - c0) / nst / n, (o1[1] - o0[1]) / nst / n, (o1[0] - o0[0]) / nst, (o1[2] - o0[2]) / max(o1[3] - o0[3], 1)))
+            (ta, va, ga, la, _), (tb, vb, gb, lb, ib), (tc, vc, _, _, _) = res
+            print("%-9s %3d   %8.3f [%7.3f .. %7.3f]   %8.3f [%7.3f .. %7.3f]   %8.3f [%7.3f .. %7.3f]   %6.2f   %6.2f   %6.2f %6.2f   %6.2f %6.2f   %7.1f %7.1f   %6.2f   (solo V-cycles/step/member %.2f)"
+                  % (name, n, ta[0], ta[1], ta[2], tb[0], tb[1], tb[2], tc[0], tc[1], tc[2], ta[0] / tb[0], tc[0] / tb[0], va, vb, ga, gb, la, lb, ib, vc), flush=True)
+            for B in Bs:
+                B.close()
+            for L in Ls:
+                L.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--n", default="1,2,4,6,8,16,32")
-    ap.add_argument("--steps", type=int, default=200)
+    ap.add_argument("--n", default=None)
+    ap.add_argument("--steps", type=int, default=None)
     ap.add_argument("--warmup", type=int, default=60)
-    ap.add_argument("--repeat", type=int, default=5)
+    ap.add_argument("--repeat", type=int, default=None)
+    ap.add_argument("--bottom-solver", action="store_true")
     ap.add_argument("--suite", choices=("A", "B"), default="A")
     ap.add_argument("--only", choices=("both", "batch", "solo"), default="both")
     a = ap.parse_args()
+    a.n = a.n or ("1,6,16,32" if a.bottom_solver else "1,2,4,6,8,16,32")
+    a.steps, a.repeat = a.steps or (50 if a.bottom_solver else 200), a.repeat or (3 if a.bottom_solver else 5)
+    if a.bottom_solver:
+        return bottom_solver_table(a)
     m = sy.shmip_a_model("A3")
     st = sy.shmip_initial_state(NX, NY, m["lx"], m["ly"])
     what = "A3" if a.suite == "A" else "suite B (implicit gap-height solve)"
