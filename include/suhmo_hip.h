@@ -529,10 +529,23 @@ int suhmo_hier_moulin_source(suhmo_hier_t *H, int n_moulins, const double *posit
  *                         averages D to the coarse depths, the solve above runs with the gap solve's parameters, one launch stores the solution
  *                         (freeze_icefree_gap per member), one fills the ghosts of b.  A batch may mix both kinds; use_impl_diff with diffFactor = 0
  *                         on a member: rc -1.  Moulin sources / recharge: suhmo_level_moulin_source / suhmo_level_time_varying_recharge on the
- *                         member handle.
+ *                         member handle, one member at a time, or the calls below for all members at once.
+ *   Forcing and diagnostics of all members whose flag in active[n] is not 0 (NULL = all; none: a no-op, rc 0), each with the launches of ONE
+ *   member and bit for bit what the per-level call on the member handle gives; a member without a flag keeps its source term and its rows of
+ *   the output.  Every flagged member is checked before anything is launched (rc -1 and a message naming the member); a NULL array other than
+ *   active (and integrals): rc -1.
+ *   suhmo_batch_time_varying_recharge   suhmo_level_time_varying_recharge with T_K[n] and background[n]: SUHMO_F_MSRC of every member from its
+ *                         SUHMO_F_ZS, which stays on the device (load it once through the member handle; a member without it: rc -1).  One launch.
+ *   suhmo_batch_moulin_source   suhmo_level_moulin_source with a list per member: n_moulins[n], and positions (2 per moulin), sigma, flux and
+ *                         integrals (may be NULL) concatenated, member 0 first -- member k's entries follow those of the members before it (a
+ *                         member without a flag may give 0, or entries that are skipped); time_factor[n].  n_moulins < 1 or a sigma <= 0 on a
+ *                         flagged member: rc -1.  Three launches and one synchronisation; the scratch belongs to the batch.
+ *   suhmo_batch_postproc_partial / _temporal / _table   suhmo_level_postproc_partial / _temporal / _table of every member with mp[n]: sums
+ *                         [n][8][nx], out [n][6], table [n][nx][8].  One launch and one read-back for all members.  No time step run yet on a
+ *                         member, or use_moulin_source without a source term: rc -1.
  *   suhmo_batch_set_option / get_option   tile_order (0 .. 2, as the level's); bottom_solver: get reports the creation value, set returns 0 for
  *                         that value and rc -5 for the other one (fixed at creation: suhmo_batch_create_opts); implicit_gap (0 / 1, default 0: see
- *                         suhmo_batch_timestep).  Read-only counters: batch_launches, batch_readbacks (both include the gap solves),
+ *                         suhmo_batch_timestep).  Read-only counters: batch_launches, batch_readbacks (both include the gap solves and the calls above),
  *                         batch_member_cycles (V-cycles of head solves summed over the members that ran them), batch_gap_member_cycles (the same for
  *                         the gap solves), bottom_solver_iterations and bottom_solves_one_launch (RelaxSolver's iterations and solves summed over
  *                         the members, the gap solves included; the same keys on a member handle: that member alone).  An unknown key: rc -1.
@@ -550,6 +563,12 @@ int suhmo_batch_set_phys(suhmo_batch_t *B, int k, const suhmo_phys_t *phys);
 int suhmo_batch_vcycle(suhmo_batch_t *B, const suhmo_solver_params_t *sp, const int *active, suhmo_stream_t s);
 int suhmo_batch_solve(suhmo_batch_t *B, const suhmo_solver_params_t *sp, int *iters, double *residual, suhmo_stream_t s);
 int suhmo_batch_timestep(suhmo_batch_t *B, const suhmo_model_params_t *mp, double dt, int cur_step, int *picard_iters, int *vcycles, suhmo_stream_t s);
+int suhmo_batch_time_varying_recharge(suhmo_batch_t *B, const double *T_K, const double *background, const int *active, suhmo_stream_t s);
+int suhmo_batch_moulin_source(suhmo_batch_t *B, const int *n_moulins, const double *positions, const double *sigma, const double *flux,
+                              const double *time_factor, double *integrals, const int *active, suhmo_stream_t s);
+int suhmo_batch_postproc_partial(suhmo_batch_t *B, const suhmo_model_params_t *mp, double *sums, const int *active, suhmo_stream_t s);
+int suhmo_batch_postproc_temporal(suhmo_batch_t *B, const suhmo_model_params_t *mp, double *out, const int *active, suhmo_stream_t s);
+int suhmo_batch_postproc_table(suhmo_batch_t *B, const suhmo_model_params_t *mp, double *table, const int *active, suhmo_stream_t s);
 int suhmo_batch_set_option(suhmo_batch_t *B, const char *key, long value);
 int suhmo_batch_get_option(const suhmo_batch_t *B, const char *key, long *value);
 

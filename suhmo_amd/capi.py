@@ -83,6 +83,7 @@ SYMBOLS = [
     "suhmo_hier_create_opts", "suhmo_hier_set_option", "suhmo_hier_get_option",
     "suhmo_batch_create", "suhmo_batch_destroy", "suhmo_batch_size", "suhmo_batch_member", "suhmo_batch_set_phys", "suhmo_batch_vcycle", "suhmo_batch_solve", "suhmo_batch_timestep",
     "suhmo_batch_set_option", "suhmo_batch_get_option", "suhmo_batch_create_opts",
+    "suhmo_batch_time_varying_recharge", "suhmo_batch_moulin_source", "suhmo_batch_postproc_partial", "suhmo_batch_postproc_temporal", "suhmo_batch_postproc_table",
 ]
 
 
@@ -221,6 +222,10 @@ def lib():
     L.suhmo_batch_vcycle.argtypes = [vp, C.POINTER(SolverParams), ip, vp]
     L.suhmo_batch_solve.argtypes = [vp, C.POINTER(SolverParams), ip, dp, vp]
     L.suhmo_batch_timestep.argtypes = [vp, C.POINTER(ModelParams), C.c_double, ci, ip, ip, vp]
+    L.suhmo_batch_time_varying_recharge.argtypes = [vp, dp, dp, ip, vp]
+    L.suhmo_batch_moulin_source.argtypes = [vp, ip, dp, dp, dp, dp, dp, ip, vp]
+    for fn in (L.suhmo_batch_postproc_partial, L.suhmo_batch_postproc_temporal, L.suhmo_batch_postproc_table):
+        fn.argtypes = [vp, C.POINTER(ModelParams), dp, ip, vp]
     L.suhmo_batch_set_option.argtypes = [vp, C.c_char_p, C.c_long]
     L.suhmo_batch_get_option.argtypes = [vp, C.c_char_p, C.POINTER(C.c_long)]
     L.suhmo_level_profile_reset.argtypes = [vp]

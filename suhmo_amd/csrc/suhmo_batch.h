@@ -48,3 +48,18 @@ int suhmo_batch_step_solve_gap(suhmo_batch *B, const BatchSel &sel, const suhmo_
 int suhmo_batch_gap_load(const OnMembers &h, const OnMembers &g, size_t elems, hipStream_t st);
 int suhmo_batch_gap_store(const OnMembers &h, const OnMembers &g, size_t elems, hipStream_t st);      // h.mp: the members' device rows
 int suhmo_batch_timestep_run(suhmo_batch *B, const suhmo_model_params_t *mp, double dt, int cur_step, int *picard_iters, int *vcycles, hipStream_t st);
+
+// ---- forcing and diagnostics of the members in one launch each (suhmo_step.hip: the device bodies of the per-level calls over OnMembers)
+// COMPUTE_TIMEVARYINGRECHARGE of the members `t` serves: SUHMO_F_MSRC from the resident SUHMO_F_ZS, temperature and background input per member
+int launch_time_varying_recharge(const OnMembers &t, const PerMember &TK, const PerMember &background, hipStream_t st);
+// one moulin list on one view, what the three moulin kernels work on: a level, box or patch passes it by value, an ensemble keeps a device row per member
+struct MoulinJob {
+    DV v; int n, nblk;                 // the cells the Gaussians are sampled on; moulins; 16 x 16 tiles of v (= partial sums per moulin)
+    const double *mo, *flux;           // {x, y, sigma} and the flux of every moulin
+    double *integ, *partial;           // n integrals; nblk x n tile sums
+    double tf; double *out;            // time factor; the source term (a canvas of v)
+};
+// the lists of the members in `sel` (rows[k]: member k's, on the device; nmax: the longest of them): three launches
+int suhmo_batch_moulin_launch(const MoulinJob *rows, const BatchSel &sel, int nx, int ny, int nmax, hipStream_t st);
+// column sums of the SHMIP tables (suhmo_level_postproc_partial), out[k][8][nx] for every member k `t` serves; t.mp: the members' device rows
+int launch_postproc_columns(const OnMembers &t, double *out, hipStream_t st);

@@ -47,6 +47,10 @@ struct suhmo_batch {
     // launch (suhmo_bottom.hip).  Every member handle holds the same value; d_ctr[k]: the device counters of member k (its bottom_ctr)
     int bottom_solver; long bottom_max_cells;
     unsigned long long **d_ctr;
+    // forcing and diagnostics of all members (suhmo_batch_moulin_source, suhmo_batch_postproc_*): scratch that grows on demand and goes with the batch
+    double *d_moulin; size_t moulin_cap;                    // the members' rows (MoulinJob), their moulin tables, integrals and tile sums
+    std::vector<double> h_moulin, h_integ;                  // what is sent to / read from it
+    double *d_cols, *h_cols; size_t cols_cap;               // column sums [n][8][nx] on the device and in pinned host memory
 };
 constexpr int SLOT_FLAG = 2 * SUHMO_BATCH_MAX;             // pinned slot: two values per member, then the sequence number
 
@@ -229,6 +233,13 @@ static BatchSel all_members(const suhmo_batch *B)
     for (int k = 0; k < B->n; k++) sel.m[k] = (unsigned char)k;
     return sel;
 }
+// the members whose flag in active[n] is not 0 (NULL: all)
+static BatchSel flagged_members(const suhmo_batch *B, const int *active)
+{
+    BatchSel sel = all_members(B);
+    if (active) { sel.n = 0; for (int k = 0; k < B->n; k++) if (active[k]) sel.m[sel.n++] = (unsigned char)k; }
+    return sel;
+}
 static int batch_enter(suhmo_batch *B, hipStream_t st)
 {
     HIPCHK(hipSetDevice(B->device));
@@ -253,6 +264,9 @@ extern "C" int suhmo_batch_destroy(suhmo_batch_t *B)
     if (B->d_avg) (void)hipFree(B->d_avg);
     if (B->d_mp) (void)hipFree(B->d_mp);
     if (B->d_ctr) (void)hipFree(B->d_ctr);
+    if (B->d_moulin) (void)hipFree(B->d_moulin);
+    if (B->d_cols) (void)hipFree(B->d_cols);
+    if (B->h_cols) (void)hipHostFree(B->h_cols);
     if (B->hslot) (void)hipHostFree(B->hslot);
     if (B->gap) (void)suhmo_batch_destroy(B->gap);
     delete B;
@@ -372,8 +386,7 @@ extern "C" int suhmo_batch_vcycle(suhmo_batch_t *B, const suhmo_solver_params_t 
     SUHMO_TIME("AMRFASMultiGrid::VCycle");
     ARG(B && sp);
     int rc = batch_enter(B, (hipStream_t)s); if (rc) return rc;
-    BatchSel sel = all_members(B);
-    if (active) { sel.n = 0; for (int k = 0; k < B->n; k++) if (active[k]) sel.m[sel.n++] = (unsigned char)k; }
+    const BatchSel sel = flagged_members(B, active);
     return batch_vcycle(B, sp, sel, (hipStream_t)s);          // (no member selected: nothing to do)
 }
 // the AMRMultiGrid::solve loop of the members in `first`, each with its own stopping rule; iters / residual: arrays over ALL members
@@ -497,15 +510,20 @@ int suhmo_batch_step_solve_gap(suhmo_batch *B, const BatchSel &sel, const suhmo_
     G->launches++;
     return 0;
 }
+// mp[n] on the device: rewritten when a row changed
+static int batch_mp_sync(suhmo_batch *B, const suhmo_model_params_t *mp, hipStream_t st)
+{
+    if (!memcmp(B->h_mp.data(), mp, B->n * sizeof(suhmo_model_params_t))) return 0;
+    HIPCHK(hipStreamSynchronize(st));                        // (no launch in flight reads the rows about to change)
+    memcpy(B->h_mp.data(), mp, B->n * sizeof(suhmo_model_params_t));
+    HIPCHK(hipMemcpy(B->d_mp, B->h_mp.data(), B->n * sizeof(suhmo_model_params_t), hipMemcpyHostToDevice));
+    return 0;
+}
 // the step's entry: tables against the handles (the step's fields have just been allocated), mp[n] on the device, everybody in the first phase
 int suhmo_batch_step_begin(suhmo_batch *B, const suhmo_model_params_t *mp, hipStream_t st)
 {
     int rc = batch_enter(B, st); if (rc) return rc;
-    if (memcmp(B->h_mp.data(), mp, B->n * sizeof(suhmo_model_params_t))) {
-        HIPCHK(hipStreamSynchronize(st));                    // (no launch in flight reads the rows about to change)
-        memcpy(B->h_mp.data(), mp, B->n * sizeof(suhmo_model_params_t));
-        HIPCHK(hipMemcpy(B->d_mp, B->h_mp.data(), B->n * sizeof(suhmo_model_params_t), hipMemcpyHostToDevice));
-    }
+    if ((rc = batch_mp_sync(B, mp, st))) return rc;
     B->phase = all_members(B);
     return 0;
 }
@@ -521,6 +539,158 @@ extern "C" int suhmo_batch_timestep(suhmo_batch_t *B, const suhmo_model_params_t
         }
     HIPCHK(hipSetDevice(B->device));
     return suhmo_batch_timestep_run(B, mp, dt, cur_step, picard_iters, vcycles, (hipStream_t)s);
+}
+
+// ---- forcing and diagnostics of all members: what suhmo_level_time_varying_recharge, suhmo_level_moulin_source and suhmo_level_postproc_* do on
+// a member handle, for the members whose flag in active[n] is not 0, in the launches of ONE member.  Everything is checked on every such member
+// before anything is launched; the source field is allocated like a member's first per-level call does, and the tables follow (batch_enter)
+static int batch_source_fields(suhmo_batch *B, const BatchSel &sel, hipStream_t st)
+{
+    HIPCHK(hipSetDevice(B->device));
+    for (int z = 0; z < sel.n; z++)
+        if (!suhmo_field(B->mem[sel.m[z]], 0, SUHMO_F_MSRC)) { suhmo_set_error("batch: field allocation failed (member %d)", sel.m[z]); return -2; }
+    return batch_enter(B, st);
+}
+extern "C" int suhmo_batch_time_varying_recharge(suhmo_batch_t *B, const double *T_K, const double *background, const int *active, suhmo_stream_t s)
+{
+    ARG(B && T_K && background);
+    hipStream_t st = (hipStream_t)s;
+    const BatchSel sel = flagged_members(B, active);
+    if (!sel.n) return 0;
+    for (int z = 0; z < sel.n; z++)
+        if (!B->mem[sel.m[z]]->d[0].fp.f[SUHMO_F_ZS]) {
+            suhmo_set_error("batch: time-varying recharge: load the ice surface height (SUHMO_F_ZS) of member %d first", sel.m[z]);
+            return -1;
+        }
+    int rc = batch_source_fields(B, sel, st); if (rc) return rc;
+    PerMember tk, bg;
+    memset(&tk, 0, sizeof(tk)); memset(&bg, 0, sizeof(bg));
+    for (int k = 0; k < B->n; k++) { tk.x[k] = T_K[k]; bg.x[k] = background[k]; }
+    if ((rc = launch_time_varying_recharge(on(B, 0, sel), tk, bg, st))) return rc;
+    B->launches++;
+    return 0;
+}
+// member k's moulins are entries off[k] .. off[k] + n_moulins[k] - 1 of the concatenated arrays, off[k] = the entries of the members before it
+// (a member without a flag may give 0, or a list that is skipped)
+extern "C" int suhmo_batch_moulin_source(suhmo_batch_t *B, const int *n_moulins, const double *positions, const double *sigma, const double *flux,
+                                         const double *time_factor, double *integrals, const int *active, suhmo_stream_t s)
+{
+    SUHMO_TIME("AmrHydro::Calc_moulin_source_term_distributed");
+    ARG(B && n_moulins && positions && sigma && flux && time_factor);
+    hipStream_t st = (hipStream_t)s;
+    const BatchSel sel = flagged_members(B, active);
+    if (!sel.n) return 0;
+    size_t off[SUHMO_BATCH_MAX + 1];
+    off[0] = 0;
+    for (int k = 0; k < B->n; k++) off[k + 1] = off[k] + (n_moulins[k] > 0 ? (size_t)n_moulins[k] : 0);
+    const size_t N = off[B->n];
+    int nmax = 0;
+    for (int z = 0; z < sel.n; z++) {
+        const int k = sel.m[z];
+        if (n_moulins[k] < 1) { suhmo_set_error("batch: moulin source: n_moulins = %d on member %d (at least 1)", n_moulins[k], k); return -1; }
+        for (int m = 0; m < n_moulins[k]; m++)
+            if (!(sigma[off[k] + m] > 0.0)) { suhmo_set_error("batch: moulin source: sigma <= 0 (member %d, its moulin %d)", k, m); return -1; }
+        nmax = std::max(nmax, n_moulins[k]);
+    }
+    int rc = batch_source_fields(B, sel, st); if (rc) return rc;
+    const DV &v = view(B, 0);
+    const size_t nblk = (size_t)((v.nx + 15) / 16) * ((v.ny + 15) / 16);
+    // the device scratch: rows[n] | {x, y, sigma} x n_k, flux x n_k of every member (4 N) | integrals (N) | tile sums (nblk x N)
+    static_assert(sizeof(MoulinJob) % sizeof(double) == 0, "rows and tables share one array of doubles");
+    const size_t rowd = sizeof(MoulinJob) / sizeof(double), head = B->n * rowd, need = head + (5 + nblk) * N;
+    if (need > B->moulin_cap) {
+        HIPCHK(hipStreamSynchronize(st));
+        if (B->d_moulin) (void)hipFree(B->d_moulin);
+        B->d_moulin = nullptr; B->moulin_cap = 0;
+        HIPCHK(hipMalloc(&B->d_moulin, need * sizeof(double)));
+        B->moulin_cap = need;
+    }
+    double *tab_d = B->d_moulin + head, *integ_d = tab_d + 4 * N, *partial_d = integ_d + N;
+    B->h_moulin.assign(head + 4 * N, 0.0);
+    double *tab_h = B->h_moulin.data() + head;
+    for (int z = 0; z < sel.n; z++) {
+        const int k = sel.m[z], n = n_moulins[k];
+        const size_t o = off[k];
+        for (int m = 0; m < n; m++) {
+            tab_h[4 * o + 3 * m] = positions[2 * (o + m)]; tab_h[4 * o + 3 * m + 1] = positions[2 * (o + m) + 1]; tab_h[4 * o + 3 * m + 2] = sigma[o + m];
+            tab_h[4 * o + 3 * (size_t)n + m] = flux[o + m];
+        }
+        const Depth &D = B->mem[k]->d[0];
+        const MoulinJob job{D.v, n, (int)nblk, tab_d + 4 * o, tab_d + 4 * o + 3 * (size_t)n, integ_d + o, partial_d + nblk * o, time_factor[k], D.fp.f[SUHMO_F_MSRC]};
+        memcpy(B->h_moulin.data() + k * rowd, &job, sizeof(job));
+    }
+    hipError_t e = hipMemcpyAsync(B->d_moulin, B->h_moulin.data(), B->h_moulin.size() * sizeof(double), hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) {
+        if ((rc = suhmo_batch_moulin_launch((const MoulinJob *)B->d_moulin, sel, v.nx, v.ny, nmax, st))) return rc;
+        B->launches += 3;
+        if (integrals) { B->h_integ.resize(N); e = hipMemcpyAsync(B->h_integ.data(), integ_d, N * sizeof(double), hipMemcpyDeviceToHost, st); }
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(st);       // (the one synchronisation: the integrals have arrived, the host table may be written again)
+    if (e != hipSuccess) { suhmo_set_error("batch: moulin source: %s", hipGetErrorString(e)); return -2; }
+    if (integrals)
+        for (int z = 0; z < sel.n; z++) { const int k = sel.m[z]; memcpy(integrals + off[k], B->h_integ.data() + off[k], n_moulins[k] * sizeof(double)); }
+    return 0;
+}
+// column sums of the flagged members in B->h_cols[k][8][nx]: one launch, one copy, one synchronisation
+static int batch_column_sums(suhmo_batch *B, const suhmo_model_params_t *mp, const BatchSel &sel, hipStream_t st)
+{
+    for (int z = 0; z < sel.n; z++) {
+        const int k = sel.m[z];
+        const Depth &D = B->mem[k]->d[0];
+        for (int f : {SUHMO_F_QWX, SUHMO_F_CD, SUHMO_F_MR, SUHMO_F_PW}) if (!D.fp.f[f]) { suhmo_set_error("batch: no time step has run on member %d", k); return -1; }
+        if (mp[k].use_moulin_source && !D.fp.f[SUHMO_F_MSRC]) { suhmo_set_error("batch: use_moulin_source without a moulin source term (SUHMO_F_MSRC) on member %d", k); return -1; }
+    }
+    int rc = batch_enter(B, st); if (rc) return rc;
+    if ((rc = batch_mp_sync(B, mp, st))) return rc;
+    const DV &v = view(B, 0);
+    const size_t per = 8 * (size_t)v.nx, need = B->n * per;
+    if (need > B->cols_cap) {
+        HIPCHK(hipStreamSynchronize(st));
+        if (B->d_cols) (void)hipFree(B->d_cols);
+        if (B->h_cols) (void)hipHostFree(B->h_cols);
+        B->d_cols = B->h_cols = nullptr; B->cols_cap = 0;
+        HIPCHK(hipMalloc(&B->d_cols, need * sizeof(double)));
+        HIPCHK(hipHostMalloc(&B->h_cols, need * sizeof(double), hipHostMallocDefault));
+        B->cols_cap = need;
+    }
+    if ((rc = launch_postproc_columns(on_members(tab(B, 0), sel, v, B->d_mp), B->d_cols, st))) return rc;
+    B->launches++;
+    const int k0 = sel.m[0], k1 = sel.m[sel.n - 1];           // (the list ascends: the rows from the first to the last flagged member)
+    HIPCHK(hipMemcpyAsync(B->h_cols + k0 * per, B->d_cols + k0 * per, (k1 - k0 + 1) * per * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    B->readbacks++;
+    return 0;
+}
+// what: 0 the sums [n][8][nx], 1 suhmo_postproc_temporal of them [n][6], 2 suhmo_postproc_finish [n][nx][8]; rows of members without a flag stay
+static int batch_postproc(suhmo_batch *B, const suhmo_model_params_t *mp, double *out, const int *active, suhmo_stream_t s, int what)
+{
+    const BatchSel sel = flagged_members(B, active);
+    if (!sel.n) return 0;
+    int rc = batch_column_sums(B, mp, sel, (hipStream_t)s); if (rc) return rc;
+    const DV &v = view(B, 0);
+    const size_t per = 8 * (size_t)v.nx;
+    for (int z = 0; z < sel.n; z++) {
+        const int k = sel.m[z];
+        const double *sums = B->h_cols + k * per;
+        if (what == 0) memcpy(out + k * per, sums, per * sizeof(double));
+        else if ((rc = what == 1 ? suhmo_postproc_temporal(sums, v.nx, v.dx, out + 6 * (size_t)k) : suhmo_postproc_finish(sums, v.nx, v.dx, out + k * per))) return rc;
+    }
+    return 0;
+}
+extern "C" int suhmo_batch_postproc_partial(suhmo_batch_t *B, const suhmo_model_params_t *mp, double *sums, const int *active, suhmo_stream_t s)
+{
+    ARG(B && mp && sums);
+    return batch_postproc(B, mp, sums, active, s, 0);
+}
+extern "C" int suhmo_batch_postproc_temporal(suhmo_batch_t *B, const suhmo_model_params_t *mp, double *out, const int *active, suhmo_stream_t s)
+{
+    ARG(B && mp && out);
+    return batch_postproc(B, mp, out, active, s, 1);
+}
+extern "C" int suhmo_batch_postproc_table(suhmo_batch_t *B, const suhmo_model_params_t *mp, double *table, const int *active, suhmo_stream_t s)
+{
+    ARG(B && mp && table);
+    return batch_postproc(B, mp, table, active, s, 2);
 }
 
 extern "C" int suhmo_batch_set_option(suhmo_batch_t *B, const char *key, long value)

@@ -1067,8 +1067,18 @@ __device__ __forceinline__ double moulin_cell(double xc, double yc, double dx, d
          + v[0] * v[1] * MS[3] + v[1] * v[1] * MS[4] + v[2] * v[1] * MS[5]
          + v[0] * v[2] * MS[6] + v[1] * v[2] * MS[7] + v[2] * v[2] * MS[8];
 }
-__global__ __launch_bounds__(256) void k_moulin_partial(DV v, int n, const double *__restrict__ mo, double *__restrict__ partial, Excl ex,
-                                                        const double *__restrict__ cover = nullptr)
+// the three device bodies work on one MoulinJob (suhmo_batch.h): one moulin list on one view.  They are launched over a level, a box or a patch
+// (OneMoulinList: the job by value) or over the members of an ensemble (MemberMoulinLists: a device row per member, blockIdx.z -> member)
+struct OneMoulinList {
+    MoulinJob j;
+    __device__ __forceinline__ const MoulinJob &job() const { return j; }
+};
+struct MemberMoulinLists {
+    const MoulinJob *rows; BatchSel sel;
+    __device__ __forceinline__ const MoulinJob &job() const { return rows[batch_member(sel)]; }
+};
+__device__ __forceinline__ void d_moulin_partial(const DV &v, int n, const double *__restrict__ mo, double *__restrict__ partial, const Excl &ex,
+                                                 const double *__restrict__ cover)
 {
     __shared__ double sm[256];
     const int tid = threadIdx.y * 16 + threadIdx.x;
@@ -1091,10 +1101,12 @@ __global__ __launch_bounds__(256) void k_moulin_partial(DV v, int n, const doubl
         __syncthreads();
     }
 }
-__global__ void k_moulin_final(const double *__restrict__ partial, int nblk, int n, double *__restrict__ integ)
+// one workgroup per moulin (blockIdx.x; the lists of an ensemble differ in length: a workgroup past the end of its member's list has nothing to do)
+__device__ __forceinline__ void d_moulin_final(const double *__restrict__ partial, int nblk, int n, double *__restrict__ integ)
 {
     __shared__ double sm[256];
     const int m = blockIdx.x, tid = threadIdx.x;
+    if (m >= n) return;                                                                                  // uniform
     double acc = 0.0;
     for (int b = tid; b < nblk; b += 256) acc = acc + partial[(size_t)b * n + m];
     sm[tid] = acc;
@@ -1102,9 +1114,9 @@ __global__ void k_moulin_final(const double *__restrict__ partial, int nblk, int
     for (int s = 128; s > 0; s >>= 1) { if (tid < s) sm[tid] = sm[tid] + sm[tid + s]; __syncthreads(); }
     if (tid == 0) integ[m] = sm[0];
 }
-__global__ __launch_bounds__(256) void k_moulin_src(DV v, int n, const double *__restrict__ mo, const double *__restrict__ flux,
-                                                    const double *__restrict__ integ, double tf, double *__restrict__ out, Excl ex,
-                                                    const double *__restrict__ cover = nullptr)
+__device__ __forceinline__ void d_moulin_src(const DV &v, int n, const double *__restrict__ mo, const double *__restrict__ flux,
+                                             const double *__restrict__ integ, double tf, double *__restrict__ out, const Excl &ex,
+                                             const double *__restrict__ cover)
 {
     const int i = blockIdx.x * 16 + threadIdx.x, j = blockIdx.y * 16 + threadIdx.y;
     if (i >= v.nx || j >= v.ny) return;
@@ -1117,7 +1129,53 @@ __global__ __launch_bounds__(256) void k_moulin_src(DV v, int n, const double *_
     }
     out[cidx(v, i, j)] = sum;
 }
+template <class J> __global__ __launch_bounds__(256) void k_moulin_partial(J t, Excl ex, const double *__restrict__ cover)
+{
+    const MoulinJob &j = t.job();
+    d_moulin_partial(j.v, j.n, j.mo, j.partial, ex, cover);
+}
+template <class J> __global__ void k_moulin_final(J t)
+{
+    const MoulinJob &j = t.job();
+    d_moulin_final(j.partial, j.nblk, j.n, j.integ);
+}
+template <class J> __global__ __launch_bounds__(256) void k_moulin_src(J t, Excl ex, const double *__restrict__ cover)
+{
+    const MoulinJob &j = t.job();
+    d_moulin_src(j.v, j.n, j.mo, j.flux, j.integ, j.tf, j.out, ex, cover);
+}
+// the launchers: 16 x 16 tiles of the job's view (grd), one workgroup per moulin for the integrals; gz = 1, or the active members
+template <class J> void launch_moulin_partial(const J &t, dim3 grd, hipStream_t st, Excl ex, const double *cover = nullptr)
+{
+    hipLaunchKernelGGL(k_moulin_partial<J>, grd, dim3(16, 16), 0, st, t, ex, cover);
+}
+template <class J> void launch_moulin_final(const J &t, int nmax, int gz, hipStream_t st) { hipLaunchKernelGGL(k_moulin_final<J>, dim3(nmax, 1, gz), dim3(256), 0, st, t); }
+template <class J> void launch_moulin_src(const J &t, dim3 grd, hipStream_t st, Excl ex, const double *cover = nullptr)
+{
+    hipLaunchKernelGGL(k_moulin_src<J>, grd, dim3(16, 16), 0, st, t, ex, cover);
+}
+// one list on one view: the integration passes read v, n, mo, partial (nblk tiles), integ; the source pass v, n, mo, flux, integ, tf, out
+OneMoulinList moulin_integrals_on(const DV &v, int n, const double *mo, double *partial, size_t nblk, double *integ)
+{
+    return OneMoulinList{MoulinJob{v, n, (int)nblk, mo, nullptr, integ, partial, 0.0, nullptr}};
+}
+OneMoulinList moulin_source_on(const DV &v, int n, const double *mo, const double *flux, double *integ, double tf, double *out)
+{
+    return OneMoulinList{MoulinJob{v, n, 0, mo, flux, integ, nullptr, tf, out}};
+}
 }  // namespace
+// the lists of the active members of an ensemble (rows[k]: member k's, on the device; nmax: the longest list): three launches whatever their number
+int suhmo_batch_moulin_launch(const MoulinJob *rows, const BatchSel &sel, int nx, int ny, int nmax, hipStream_t st)
+{
+    if (sel.n <= 0) return 0;
+    const MemberMoulinLists t{rows, sel};
+    const dim3 grd((nx + 15) / 16, (ny + 15) / 16, sel.n);
+    launch_moulin_partial(t, grd, st, Excl{0, 0, 0, 0});
+    launch_moulin_final(t, nmax, sel.n, st);
+    launch_moulin_src(t, grd, st, Excl{0, 0, 0, 0});
+    HIPCHK(hipGetLastError());
+    return 0;
+}
 
 extern "C" int suhmo_level_moulin_source(suhmo_level_t *L, int n, const double *positions, const double *sigma,
                                          const double *flux, double time_factor, double *integrals, suhmo_stream_t s)
@@ -1138,16 +1196,17 @@ extern "C" int suhmo_level_moulin_source(suhmo_level_t *L, int n, const double *
     // rank strip: the integrals run over the whole level on every rank (geometry only), in the single-level order
     DV vg = D.v;
     vg.ny = D.v.nyg; vg.j0 = 0;
-    dim3 blk(16, 16), grd((D.v.nx + 15) / 16, (D.v.ny + 15) / 16), grdg((vg.nx + 15) / 16, (vg.ny + 15) / 16);
+    dim3 grd((D.v.nx + 15) / 16, (D.v.ny + 15) / 16), grdg((vg.nx + 15) / 16, (vg.ny + 15) / 16);
     const size_t nblk = (size_t)grdg.x * grdg.y;
     double *dev = nullptr;
     HIPCHK(hipMalloc(&dev, (5 * (size_t)n + nblk * n) * sizeof(double)));
     double *mo = dev, *fl = dev + 3 * (size_t)n, *integ = dev + 4 * (size_t)n, *partial = dev + 5 * (size_t)n;
     hipError_t e = hipMemcpyAsync(dev, h.data(), 4 * (size_t)n * sizeof(double), hipMemcpyHostToDevice, st);
     if (e == hipSuccess) {
-        hipLaunchKernelGGL(k_moulin_partial, grdg, blk, 0, st, vg, n, mo, partial, Excl{0, 0, 0, 0});
-        hipLaunchKernelGGL(k_moulin_final, dim3(n), dim3(256), 0, st, partial, (int)nblk, n, integ);
-        hipLaunchKernelGGL(k_moulin_src, grd, blk, 0, st, D.v, n, mo, fl, integ, time_factor, out, Excl{0, 0, 0, 0});
+        const OneMoulinList whole = moulin_integrals_on(vg, n, mo, partial, nblk, integ);
+        launch_moulin_partial(whole, grdg, st, Excl{0, 0, 0, 0});
+        launch_moulin_final(whole, n, 1, st);
+        launch_moulin_src(moulin_source_on(D.v, n, mo, fl, integ, time_factor, out), grd, st, Excl{0, 0, 0, 0});
         e = hipGetLastError();
     }
     if (e == hipSuccess && integrals) e = hipMemcpyAsync(integrals, integ, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, st);
@@ -1205,9 +1264,10 @@ extern "C" int suhmo_amr_moulin_source(suhmo_level_t **lv, int nlev, const int *
     for (int l = nlev - 1; l >= 0 && e == hipSuccess; l--) {          // finest first (:1891)
         DV vg = b;                                                     // only the geometry below is read by the kernel
         vg.nx = geo[l].nx; vg.ny = geo[l].ny; vg.i0 = geo[l].i0; vg.j0 = geo[l].j0; vg.dx = geo[l].dx; vg.dy = geo[l].dy;
-        dim3 blk(16, 16), grd((vg.nx + 15) / 16, (vg.ny + 15) / 16);
-        hipLaunchKernelGGL(k_moulin_partial, grd, blk, 0, st, vg, n, mo, partial, excl_of(l, vg.i0, vg.j0));
-        hipLaunchKernelGGL(k_moulin_final, dim3(n), dim3(256), 0, st, partial, (int)(grd.x * grd.y), n, integ);
+        dim3 grd((vg.nx + 15) / 16, (vg.ny + 15) / 16);
+        const OneMoulinList lev = moulin_integrals_on(vg, n, mo, partial, (size_t)grd.x * grd.y, integ);
+        launch_moulin_partial(lev, grd, st, excl_of(l, vg.i0, vg.j0));
+        launch_moulin_final(lev, n, 1, st);
         e = hipGetLastError();
         if (e == hipSuccess) e = hipMemcpyAsync(part.data(), integ, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, st);
         if (e == hipSuccess) e = hipStreamSynchronize(st);
@@ -1217,8 +1277,8 @@ extern "C" int suhmo_amr_moulin_source(suhmo_level_t **lv, int nlev, const int *
     for (int l = 0; l < nlev && e == hipSuccess; l++) {
         if (!lv[l]) continue;
         const DV &v = lv[l]->d[0].v;
-        dim3 blk(16, 16), grd((v.nx + 15) / 16, (v.ny + 15) / 16);
-        hipLaunchKernelGGL(k_moulin_src, grd, blk, 0, st, v, n, mo, fl, integ, time_factor, lv[l]->d[0].fp.f[SUHMO_F_MSRC], excl_of(l, v.i0, v.j0));
+        dim3 grd((v.nx + 15) / 16, (v.ny + 15) / 16);
+        launch_moulin_src(moulin_source_on(v, n, mo, fl, integ, time_factor, lv[l]->d[0].fp.f[SUHMO_F_MSRC]), grd, st, excl_of(l, v.i0, v.j0));
         e = hipGetLastError();
     }
     if (e == hipSuccess) e = hipStreamSynchronize(st);
@@ -1275,10 +1335,11 @@ extern "C" int suhmo_hier_moulin_source(suhmo_hier_t *H, int n, const double *po
             const bool cutbase = l == 0 && (L->d[0].v.rk[0] || L->d[0].v.rk[1]);
             DV v = L->d[0].v;
             if (cutbase) { v.ny = v.nyg; v.j0 = 0; }
-            dim3 blk(16, 16), grd((v.nx + 15) / 16, (v.ny + 15) / 16);
+            dim3 grd((v.nx + 15) / 16, (v.ny + 15) / 16);
             const double *cover = l < nlev - 1 ? (cutbase ? whole_cover : L->d[0].fp.f[SUHMO_F_COVER]) : nullptr;
-            hipLaunchKernelGGL(k_moulin_partial, grd, blk, 0, st, v, n, mo, partial, Excl{0, 0, 0, 0}, cover);
-            hipLaunchKernelGGL(k_moulin_final, dim3(n), dim3(256), 0, st, partial, (int)(grd.x * grd.y), n, integ);
+            const OneMoulinList box = moulin_integrals_on(v, n, mo, partial, (size_t)grd.x * grd.y, integ);
+            launch_moulin_partial(box, grd, st, Excl{0, 0, 0, 0}, cover);
+            launch_moulin_final(box, n, 1, st);
             e = hipGetLastError();
             if (e == hipSuccess) e = hipMemcpyAsync(part.data(), integ, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, st);
             if (e == hipSuccess) e = hipStreamSynchronize(st);
@@ -1316,9 +1377,9 @@ extern "C" int suhmo_hier_moulin_source(suhmo_hier_t *H, int n, const double *po
         for (int k = k0; k < k0 + nk; k++) {
             suhmo_level *L = bx[k];
             const DV &v = L->d[0].v;
-            dim3 blk(16, 16), grd((v.nx + 15) / 16, (v.ny + 15) / 16);
+            dim3 grd((v.nx + 15) / 16, (v.ny + 15) / 16);
             const double *cover = l < nlev - 1 ? L->d[0].fp.f[SUHMO_F_COVER] : nullptr;
-            hipLaunchKernelGGL(k_moulin_src, grd, blk, 0, st, v, n, mo, fl, integ, time_factor, L->d[0].fp.f[SUHMO_F_MSRC], Excl{0, 0, 0, 0}, cover);
+            launch_moulin_src(moulin_source_on(v, n, mo, fl, integ, time_factor, L->d[0].fp.f[SUHMO_F_MSRC]), grd, st, Excl{0, 0, 0, 0}, cover);
             e = hipGetLastError();
             if (e != hipSuccess) break;
         }
@@ -1332,13 +1393,26 @@ extern "C" int suhmo_hier_moulin_source(suhmo_hier_t *H, int n, const double *po
 }
 
 // COMPUTE_TIMEVARYINGRECHARGE (src/AmrHydroF.ChF:346-373) on the ghosted box of the source term
-__global__ void k_time_varying_recharge(DV v, const double *__restrict__ zs, double *__restrict__ out, double TK, double background)
+__device__ __forceinline__ void d_time_varying_recharge(const DV &v, const double *__restrict__ zs, double *__restrict__ out, double TK, double background)
 {
     int i = blockIdx.x * blockDim.x + threadIdx.x - 1, j = blockIdx.y * blockDim.y + threadIdx.y - 1;
     if (i > v.nx || j > v.ny) return;
     const double ddf = 0.01 / 86400., dT_dZ = -0.0075;
     int idx = cidx(v, i, j);
     out[idx] = fmax(ddf * (TK + zs[idx] * dT_dZ), 0.0) + background;
+}
+// V: the temperature and the background input -- a double each for a level, PerMember for an ensemble
+template <class T, class V> __global__ void k_time_varying_recharge(T t, V TK, V background)
+{
+    d_time_varying_recharge(t.view(), t.field(SUHMO_F_ZS), t.field(SUHMO_F_MSRC), value_of(t, TK), value_of(t, background));
+}
+template <class T, class V> static int launch_time_varying_recharge_(const T &t, const V &TK, const V &background, hipStream_t st)
+{
+    return launch_over(k_time_varying_recharge<T, V>, t, GHOSTED, st, TK, background);
+}
+int launch_time_varying_recharge(const OnMembers &t, const PerMember &TK, const PerMember &background, hipStream_t st)
+{
+    return launch_time_varying_recharge_(t, TK, background, st);
 }
 extern "C" int suhmo_level_time_varying_recharge(suhmo_level_t *L, double T_K, double background_input, suhmo_stream_t s)
 {
@@ -1348,14 +1422,12 @@ extern "C" int suhmo_level_time_varying_recharge(suhmo_level_t *L, double T_K, d
     if (!D.fp.f[SUHMO_F_ZS]) { suhmo_set_error("time-varying recharge: load the ice surface height (SUHMO_F_ZS) first"); return -1; }
     double *out = suhmo_field(L, 0, SUHMO_F_MSRC);
     if (!out) { suhmo_set_error("field allocation failed"); return -2; }
-    hipLaunchKernelGGL(k_time_varying_recharge, dim3((D.v.nx + 2 + 63) / 64, (D.v.ny + 2 + 3) / 4), dim3(64, 4), 0, (hipStream_t)s, D.v, D.fp.f[SUHMO_F_ZS], out, T_K, background_input);
-    HIPCHK(hipGetLastError());
-    return 0;
+    return launch_time_varying_recharge_(on_level(L, 0), T_K, background_input, (hipStream_t)s);
 }
 
 // ------------------------------------------------------------------ SHMIP cross-section table
 // one thread per cell column, rows summed in ascending j (the order of the reference's BoxIterator per column)
-__global__ void k_postproc_columns(DV v, FP fp, suhmo_model_params_t mp, double *__restrict__ out /* 8 x nx */)
+__device__ __forceinline__ void d_postproc_columns(const DV &v, const FP &fp, const suhmo_model_params_t &mp, double *__restrict__ out /* 8 x nx */)
 {
     int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= v.nx) return;
@@ -1376,6 +1448,16 @@ __global__ void k_postproc_columns(DV v, FP fp, suhmo_model_params_t mp, double 
     out[0 * v.nx + i] = yl; out[1 * v.nx + i] = qt; out[2 * v.nx + i] = qc; out[3 * v.nx + i] = qd;
     out[4 * v.nx + i] = ext; out[5 * v.nx + i] = mr; out[6 * v.nx + i] = avp; out[7 * v.nx + i] = cnt;
 }
+// out: 8 x nx of a level; of an ensemble [n][8][nx], the rows of the members the launch serves
+template <class T> __global__ void k_postproc_columns(T t, double *__restrict__ out)
+{
+    d_postproc_columns(t.view(), t.fields(), t.model(), out + t.slot(8 * (size_t)t.view().nx));
+}
+template <class T> static int launch_postproc_columns_(const T &t, double *out, hipStream_t st)
+{
+    return launch_grid(k_postproc_columns<T>, t, dim3((t.nx() + 63) / 64), dim3(64), st, out);
+}
+int launch_postproc_columns(const OnMembers &t, double *out, hipStream_t st) { return launch_postproc_columns_(t, out, st); }
 // column sums over the rows of this level / strip: 8 x nx = width, Q, Q channelised, Q distributed, external recharge,
 // melt recharge, sum of (Pi - Pw), count of its terms
 extern "C" int suhmo_level_postproc_partial(suhmo_level_t *L, const suhmo_model_params_t *mp, double *sums, suhmo_stream_t s)
@@ -1390,11 +1472,11 @@ extern "C" int suhmo_level_postproc_partial(suhmo_level_t *L, const suhmo_model_
     const int nx = D.v.nx;
     double *dev = nullptr;
     HIPCHK(hipMalloc(&dev, 8 * (size_t)nx * sizeof(double)));
-    hipLaunchKernelGGL(k_postproc_columns, dim3((nx + 63) / 64), dim3(64), 0, st, D.v, D.fp, *mp, dev);
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess) e = hipMemcpyAsync(sums, dev, 8 * (size_t)nx * sizeof(double), hipMemcpyDeviceToHost, st);
+    const int rc = launch_postproc_columns_(stepping(on_level(L, 0), *mp), dev, st);
+    hipError_t e = rc ? hipSuccess : hipMemcpyAsync(sums, dev, 8 * (size_t)nx * sizeof(double), hipMemcpyDeviceToHost, st);
     if (e == hipSuccess) e = hipStreamSynchronize(st);
     (void)hipFree(dev);
+    if (rc) return rc;
     if (e != hipSuccess) { suhmo_set_error("postproc table: %s", hipGetErrorString(e)); return -2; }
     return 0;
 }

@@ -92,6 +92,11 @@ template <class T> static inline Stepping<T> stepping(const T &t, const suhmo_mo
 // a table a kernel needs beside the target's own: by value for a level, a device row per member of an ensemble
 template <class M> __device__ __forceinline__ const M &row_of(const OnLevel &, const M &m) { return m; }
 template <class M> __device__ __forceinline__ const M &row_of(const OnMembers &t, const M *m) { return m[t.member()]; }
+// a number a kernel needs per launch: itself for a level, one per member of an ensemble -- like BatchSel a kernel argument by value (512 B: no
+// copy and no synchronisation maintains it)
+struct PerMember { double x[SUHMO_BATCH_MAX]; };
+__device__ __forceinline__ double value_of(const OnLevel &, double x) { return x; }
+__device__ __forceinline__ double value_of(const OnMembers &t, const PerMember &p) { return p.x[t.member()]; }
 
 // ---- the grid of a launch: what the threads of a target's x-y plane stand for
 enum Extent { CELLS, FACES /* cells + 1 */, GHOSTED /* the box with its ghost ring: cells + 2 */, PERIMETER /* 2 nx + 2 ny, 256 threads */ };

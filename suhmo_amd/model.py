@@ -92,6 +92,13 @@ class HipModel:
                                                t.ctypes.data_as(C.POINTER(C.c_double))))
         return t
 
+    def postproc_temporal_host(self, sums):
+        """the daily row from column sums already on the host (suhmo_postproc_temporal; the sums of rank strips added up, or one member's rows
+        of HipBatchModel.postproc_partial_all)"""
+        out, a = np.zeros(6), np.ascontiguousarray(sums, dtype=np.float64)
+        check(capi.lib().suhmo_postproc_temporal(a.ctypes.data_as(C.POINTER(C.c_double)), self.nx, self.dx, out.ctypes.data_as(C.POINTER(C.c_double))))
+        return out
+
     def postproc_table(self):
         """SHMIP cross-section table (src/AmrHydro.cpp:3647-4102) from the device-resident state, reduced on the host"""
         mask = self.get("mask")
@@ -179,6 +186,65 @@ class HipBatchModel:
 
     def postproc_temporal(self, k):
         return self.members[k].postproc_temporal()
+
+    # ---- forcing and diagnostics of all members at once (suhmo_batch_time_varying_recharge / _moulin_source / _postproc_*): the launches of
+    # one member whatever n, every member bit for bit what the per-k methods give
+    def _active(self, active):
+        return None if active is None else (C.c_int * self.n)(*[int(bool(x)) for x in active])
+
+    def _per_member(self, x):
+        return np.ascontiguousarray(np.broadcast_to(np.asarray(x, dtype=np.float64), (self.n,)))
+
+    def set_surface(self, k, zs):
+        """the ghosted ice surface height of member k (F_ZS): loaded once, it stays on the device for time_varying_recharge"""
+        self.members[k].level.set(lv.F_ZS, zs, ghosted=True)
+
+    def time_varying_recharge(self, T_K, background, active=None):
+        """F_MSRC of every member from its surface height (set_surface); T_K, background: one for all or one per member"""
+        tk, bg = self._per_member(T_K), self._per_member(background)
+        dp = lambda a: a.ctypes.data_as(C.POINTER(C.c_double))
+        check(capi.lib().suhmo_batch_time_varying_recharge(self.batch.h, dp(tk), dp(bg), self._active(active), self.batch.stream))
+
+    def moulin_source(self, lists, time_factor=1.0, active=None):
+        """lists[k] = (positions, sigma, flux) of member k (None for a member that is not active); time_factor: one for all or one per member.
+        Returns the integrals of every member's moulins (None for a member that is not active)"""
+        on = [True] * self.n if active is None else [bool(x) for x in active]
+        pos, sg, fl, cnt = [], [], [], []
+        for k in range(self.n):
+            if lists[k] is None:
+                assert not on[k], "member %d is active and has no moulin list" % k
+                cnt.append(0)
+                continue
+            s = np.asarray(lists[k][1], dtype=np.float64).reshape(-1)
+            pos.append(np.asarray(lists[k][0], dtype=np.float64).reshape(-1)); sg.append(s); fl.append(np.asarray(lists[k][2], dtype=np.float64).reshape(-1))
+            assert pos[-1].size == 2 * s.size and fl[-1].size == s.size
+            cnt.append(s.size)
+        cat = lambda a: np.ascontiguousarray(np.concatenate(a)) if a else np.zeros(1)
+        pos, sg, fl = cat(pos), cat(sg), cat(fl)
+        integ, tf = np.zeros(max(sum(cnt), 1)), self._per_member(time_factor)
+        dp = lambda a: a.ctypes.data_as(C.POINTER(C.c_double))
+        check(capi.lib().suhmo_batch_moulin_source(self.batch.h, (C.c_int * self.n)(*cnt), dp(pos), dp(sg), dp(fl), dp(tf), dp(integ), self._active(active),
+                                                   self.batch.stream))
+        off = np.concatenate([[0], np.cumsum(cnt)])
+        return [integ[off[k]:off[k + 1]].copy() if on[k] else None for k in range(self.n)]
+
+    def _postproc_all(self, fn, shape, active, out):
+        t = np.zeros((self.n,) + shape) if out is None else out
+        assert t.shape == (self.n,) + shape and t.dtype == np.float64 and t.flags.c_contiguous
+        check(fn(self.batch.h, self._mp, t.ctypes.data_as(C.POINTER(C.c_double)), self._active(active), self.batch.stream))
+        return t
+
+    def postproc_partial_all(self, active=None, out=None):
+        """column sums of every member, (n, 8, nx); out: an array whose rows of the members that are not active are kept"""
+        return self._postproc_all(capi.lib().suhmo_batch_postproc_partial, (8, self.nx), active, out)
+
+    def postproc_temporal_all(self, active=None, out=None):
+        """the daily row of every member, (n, 6)"""
+        return self._postproc_all(capi.lib().suhmo_batch_postproc_temporal, (6,), active, out)
+
+    def postproc_table_device_all(self, active=None, out=None):
+        """the SHMIP cross-section table of every member, (n, nx, 8)"""
+        return self._postproc_all(capi.lib().suhmo_batch_postproc_table, (self.nx, 8), active, out)
 
     def get_option(self, key):
         return self.batch.get_option(key)

@@ -15,6 +15,14 @@ one workgroup per member in one launch) against n solo steps with level option b
 tutorial run's model (exec/0_convergence_channelized: moulin, ramp, diffusion, implicit gap-height solve; tools/convergence_channelized.py).  The
 two batches do not compute the same bits (the option changes every cycle): V-cycles per step and member are printed next to the milliseconds.
     python tools/batch_bench.py --bottom-solver [--n 1,6,16,32] [--steps 50] [--warmup 60] [--repeat 3]
+
+--forcing: a run is more than the step -- the water input changes every step and a diagnostic row is written.  Two ensembles, each stepped with its
+forcing before and the daily row (post_proc_shmip_temporal) after EVERY step: suite F's style (the valley glacier at 256 x 64 under the seasonal
+recharge, a temperature offset per member) and suite C's style (suite B's moulins at 320 x 64 under a diurnal time factor per member).  Timed
+(a) through the member handles, one member at a time (suhmo_level_time_varying_recharge with the surface uploaded every call /
+suhmo_level_moulin_source, suhmo_level_postproc_temporal: nothing else existed before the ensemble calls, so --only handles runs on older
+trees too) and (b) through suhmo_batch_time_varying_recharge / suhmo_batch_moulin_source and suhmo_batch_postproc_temporal.
+    python tools/batch_bench.py --forcing [--only both|handles|batch] [--n 1,5,16,32] [--steps 200] [--warmup 60] [--repeat 5]
 """
 import argparse
 import json
@@ -125,6 +133,83 @@ def bottom_solver_table(a):
                 L.close()
 
 
+def forcing_table(a):
+    """--forcing: per ensemble and n, the forced and diagnosed step through the member handles and through the ensemble calls"""
+    sys.path.insert(0, os.path.join(ROOT, "tools"))
+    import run_shmip_f as rf
+    print("# forced and diagnosed time step (forcing before, daily row after every step); %d timed steps after %d, median of %d runs [min .. max], ms per step"
+          % (a.steps, a.warmup, a.repeat))
+    print("# ensemble   n   (a) member handles       (b) ensemble calls       (a)/(b)   launches/step (a) (b)   read-backs/step (a) (b)   [counters: the batch's own; "
+          "the per-level calls of (a) are not in them]")
+    binp = json.load(open(os.path.join(ROOT, "tests", "golden", "shmip_B_inputs.json")))
+    nan = (float("nan"),) * 3
+    for name in ("suite-F", "suite-C"):
+        for n in [int(x) for x in a.n.split(",")]:
+            if name == "suite-F":
+                m, nx, ny, dt = dict(rf.F_MODEL), rf.F_MODEL["nx"], rf.F_MODEL["ny"], 7200.0
+                st = sy.valley_initial_state(nx, ny, 0.05, m["lx"], m["ly"])
+                phys = dict(sy.A3_PHYS, A=2.5e-25)
+                X = (np.arange(-1, nx + 1) + 0.5)[None, :] * st["dx"] + np.zeros((ny + 2, 1))
+                zs = 100.0 * np.power(X + 200.0, 0.25) + X / 60.0 - np.power(2.0e10, 0.25) + 1.0
+                delta = np.linspace(-6.0, 6.0, n) if n > 1 else np.zeros(1)
+                models = [m] * n
+            else:
+                nx, ny, dt, phys = NX, NY, 3600.0, sy.A3_PHYS
+                st = sy.shmip_initial_state(nx, ny)
+                cases = [("B1", "B2", "B3", "B4", "B5")[k % 5] for k in range(n)]
+                models = [sy.shmip_b_model(c, binp[c]) for c in cases]
+                lists = [(np.array(binp[c]["positions"]).reshape(-1, 2), np.array(binp[c]["sigma"], dtype=float), np.array(binp[c]["flux"], dtype=float)) for c in cases]
+                shift = np.arange(n) * 3600.0
+            res = {}
+            for way in ("handles", "batch"):
+                if a.only not in ("both", way):
+                    res[way] = (nan, float("nan"), float("nan"))
+                    continue
+                B = model.HipBatchModel(nx, ny, st["dx"], st["dy"], sy.A3_BC, phys, models, max_box=64, implicit_gap=True)
+                for k in range(n):
+                    B.set_state(k, st)
+                    if name == "suite-F":
+                        B.member(k).level.set(lv.F_MR, np.full((ny, nx), m["G"] / m["L"]))
+                        if way == "batch":
+                            B.set_surface(k, zs)
+                tm = [180.0 * 86400.0]
+
+                def step():
+                    t = tm[0]
+                    tm[0] += dt
+                    if name == "suite-F":
+                        T_K = -16.0 * np.cos(2.0 * np.pi * t / (365.0 * 24 * 60 * 60.0)) - 5.0 + delta
+                        if way == "batch":
+                            B.time_varying_recharge(T_K, rf.BACKGROUND)
+                        else:
+                            for k in range(n):
+                                B.member(k).time_varying_recharge(zs, T_K[k], rf.BACKGROUND)
+                    else:
+                        tf = np.maximum(0.0, 1.0 - np.sin(2.0 * np.pi * (t + shift) / 86400.0))      # a diurnal cycle, an hour's shift per member
+                        if way == "batch":
+                            B.moulin_source(lists, tf)
+                        else:
+                            for k in range(n):
+                                B.member(k).moulin_source(lists[k][0], lists[k][1], lists[k][2], tf[k])
+                    B.timestep(dt)
+                    if way == "batch":
+                        B.postproc_temporal_all()
+                    else:
+                        for k in range(n):
+                            B.postproc_temporal(k)
+
+                for _ in range(a.warmup):
+                    step()
+                l0, r0 = B.get_option("batch_launches"), B.get_option("batch_readbacks")
+                t = runs(step, B.member(0).level.synchronize, a.steps, a.repeat)
+                nst = a.steps * a.repeat
+                res[way] = (t, (B.get_option("batch_launches") - l0) / nst, (B.get_option("batch_readbacks") - r0) / nst)
+                B.close()
+            (ta, la, ra), (tb, lb, rb) = res["handles"], res["batch"]
+            print("%-9s %3d   %8.3f [%7.3f .. %7.3f]   %8.3f [%7.3f .. %7.3f]   %6.2f   %7.1f %7.1f   %6.2f %6.2f"
+                  % (name, n, ta[0], ta[1], ta[2], tb[0], tb[1], tb[2], ta[0] / tb[0], la, lb, ra, rb), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--n", default=None)
@@ -133,12 +218,15 @@ def main():
     ap.add_argument("--repeat", type=int, default=None)
     ap.add_argument("--bottom-solver", action="store_true")
     ap.add_argument("--suite", choices=("A", "B"), default="A")
-    ap.add_argument("--only", choices=("both", "batch", "solo"), default="both")
+    ap.add_argument("--forcing", action="store_true")
+    ap.add_argument("--only", choices=("both", "batch", "solo", "handles"), default="both")
     a = ap.parse_args()
-    a.n = a.n or ("1,6,16,32" if a.bottom_solver else "1,2,4,6,8,16,32")
+    a.n = a.n or ("1,6,16,32" if a.bottom_solver else "1,5,16,32" if a.forcing else "1,2,4,6,8,16,32")
     a.steps, a.repeat = a.steps or (50 if a.bottom_solver else 200), a.repeat or (3 if a.bottom_solver else 5)
     if a.bottom_solver:
         return bottom_solver_table(a)
+    if a.forcing:
+        return forcing_table(a)
     m = sy.shmip_a_model("A3")
     st = sy.shmip_initial_state(NX, NY, m["lx"], m["ly"])
     what = "A3" if a.suite == "A" else "suite B (implicit gap-height solve)"

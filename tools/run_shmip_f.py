@@ -7,7 +7,9 @@ The reference restarts F<k> from the checkpoint of exec/F_SHMIP/SS_initial_run (
 7.93e-11, no time variation) with m_time = 0 (amr.restart_time), then takes 21960 steps of 2 h (5 years); the checkpoint is not
 shipped, so the spin-up is run here too.
 usage: run_shmip_f.py oracle|hip F<k> [years] [out.json] [--head-melt-coef X] [--mask-gradients 0|1] [--freeze-icefree]
-                      [--mask-rhs-b 0|1] [--cutoffb 0|1] [--zs surface|thickness]      (run-state knobs of the oracle)"""
+                      [--mask-rhs-b 0|1] [--cutoffb 0|1] [--zs surface|thickness]      (run-state knobs of the oracle)
+       run_shmip_f.py hip all [years] [out.json] [the same options]: F1-F5 as ONE ensemble (HipBatchModel): the surface height stays on the device,
+                      one recharge call per step and one diagnostic call per day serve all five; each member against its own reference table"""
 import json, os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -48,6 +50,64 @@ def daily_row(t_end, dx, dy, qwx, src, mR, Pw, Pi, mask, rho_w=1000.0):
             rech, -dis, ext[1:].sum(), mr[1:].sum()]
 
 
+def compare(table, case):
+    """the series against the reference's table of the case: per column the largest deviation relative to the column's scale"""
+    ref = np.loadtxt(os.path.join(ROOT, "tests", "golden", "shmip_%s_postproc_reference.dat" % case))[: len(table)]
+    names = ["T_hrs", "T_days", "avgN", "N_LB", "N_MB", "N_HB", "rech", "dis"]
+    cmp_ = {}
+    for c in range(2, 8):
+        scale = np.max(np.abs(ref[:, c]))
+        d = np.abs(table[:, c] - ref[:, c])
+        cmp_[names[c]] = {"max_rel_to_scale": float(d.max() / scale), "at_day": float(table[int(d.argmax()), 1]), "first_row_rel": float(d[0] / scale)}
+    return cmp_
+
+
+def run_all(m, phys, st, zs, mask, nspin, nsteps, years, out_json, knobs, t0):
+    """F1 ... F5 as one ensemble: the spin-up of all five (identical members: the reference spins up once and restarts five times), then the
+    seasonal cycle with one suhmo_batch_time_varying_recharge per step and one suhmo_batch_postproc_partial per day"""
+    from suhmo_amd import model
+    cases = sorted(DELTA_T)
+    n, nx, ny = len(cases), m["nx"], m["ny"]
+    lv = model.lv
+    M = model.HipBatchModel(nx, ny, st["dx"], st["dy"], sy.A3_BC, phys, [dict(m) for _ in cases], max_box=64, implicit_gap=bool(m.get("use_impl_diff", 0)))
+    for k in range(n):
+        M.set_state(k, st)
+        M.member(k).level.set(lv.F_MR, np.full((ny, nx), m["G"] / m["L"]))
+        M.member(k).level.set(lv.F_MSRC, np.where(mask > 0.0, BACKGROUND, 0.0), ghosted=True)
+        M.set_surface(k, zs)
+    tot_p, tot_v = np.zeros(n, dtype=int), np.zeros(n, dtype=int)
+    for k in range(nspin):
+        p, v_ = M.timestep(3600.0); tot_p += p; tot_v += v_
+        if (k + 1) % 2000 == 0:
+            print("spin-up step %d  picard %s  vcycles %s  %.0f s" % (k + 1, tot_p.tolist(), tot_v.tolist(), time.time() - t0), flush=True)
+    rows = [[] for _ in cases]
+    delta = np.array([DELTA_T[c] for c in cases])
+    tm, dt = 0.0, 7200.0
+    for k in range(nsteps):
+        T_K = -16.0 * np.cos(2.0 * np.pi * tm / (365.0 * 24 * 60 * 60.0)) - 5.0 + delta        # :2855, m_restart_time = 0
+        M.time_varying_recharge(T_K, BACKGROUND)
+        p, v_ = M.timestep(dt); tot_p += p; tot_v += v_
+        if int(tm + dt) % 86400 == 0:
+            sums = M.postproc_partial_all()
+            for q in range(n):
+                row = M.members[q].postproc_temporal_host(sums[q])
+                rows[q].append([(tm + dt) / 3600.0, (tm + dt) / 86400.0] + list(row) + [sums[q, 4, 1:].sum(), sums[q, 5, 1:].sum()])
+        tm += dt
+        if (k + 1) % 2000 == 0:
+            print("step %d  picard %s  vcycles %s  %.0f s" % (k + 1, tot_p.tolist(), tot_v.tolist(), time.time() - t0), flush=True)
+    res = dict({"which": "hip", "case": "all", "years": years, "spinup_steps": nspin}, **knobs)
+    res.update({"seconds": time.time() - t0, "launches": M.get_option("batch_launches"), "readbacks": M.get_option("batch_readbacks"), "members": {}})
+    for q, c in enumerate(cases):
+        table = np.array(rows[q])
+        res["members"][c] = {"picard_total": int(tot_p[q]), "vcycles_total": int(tot_v[q]), "rows": len(rows[q]), "vs_reference": compare(table, c) if len(table) else {}}
+        if out_json:
+            np.savetxt(out_json.replace(".json", "_%s_table.dat" % c), table, fmt="%.10g")
+    print(json.dumps(res, indent=1))
+    if out_json:
+        json.dump(res, open(out_json, "w"), indent=1)
+    M.close()
+
+
 def main():
     coef = opt("--head-melt-coef")
     mask_grad = opt("--mask-gradients", int)
@@ -84,6 +144,10 @@ def main():
     nspin = 8000 if spin is None else spin
     nsteps = int(round(years * 366 * 12))                                # 21960 steps of 2 h in 5 "years" of 366 days (input.hydro:5)
     t0 = time.time()
+    if case == "all":
+        assert which == "hip", "the ensemble is the device path's"
+        knobs = {"head_melt_coef": coef, "mask_gradients": mask_grad, "mask_rhs_b": mask_rhs_b, "cutoffb": cutoffb, "zs": zs_kind, "freeze_icefree": bool(freeze)}
+        return run_all(m, phys, st, zs, mask, nspin, nsteps, years, out_json, knobs, t0)
     if which == "oracle":
         from oracle import pyoracle as po
         M = po.OracleModel(nx, ny, st["dx"], st["dy"], sy.A3_BC, phys, m, max_box=64, nthreads=int(os.environ.get("OMP_NUM_THREADS", min(8, os.cpu_count() or 1))))
@@ -129,13 +193,7 @@ def main():
         if (k + 1) % 2000 == 0:
             print("step %d  picard %d  vcycles %d  %.0f s" % (k + 1, tot_p, tot_v, time.time() - t0), flush=True)
     table = np.array(rows)
-    ref = np.loadtxt(os.path.join(ROOT, "tests", "golden", "shmip_%s_postproc_reference.dat" % case))[: len(rows)]
-    names = ["T_hrs", "T_days", "avgN", "N_LB", "N_MB", "N_HB", "rech", "dis"]
-    cmp_ = {}
-    for c in range(2, 8):
-        scale = np.max(np.abs(ref[:, c]))
-        d = np.abs(table[:, c] - ref[:, c])
-        cmp_[names[c]] = {"max_rel_to_scale": float(d.max() / scale), "at_day": float(table[int(d.argmax()), 1]), "first_row_rel": float(d[0] / scale)}
+    cmp_ = compare(table, case)
     res = {"which": which, "case": case, "years": years, "spinup_steps": nspin, "head_melt_coef": coef, "mask_gradients": mask_grad, "mask_rhs_b": mask_rhs_b,
            "cutoffb": cutoffb, "zs": zs_kind, "freeze_icefree": bool(os.environ.get("SUHMO_ORACLE_GAP_FREEZE_ICEFREE")), "picard_total": tot_p, "vcycles_total": tot_v,
            "seconds": time.time() - t0, "rows": len(rows), "vs_reference": cmp_}
