@@ -287,6 +287,9 @@ int suhmo_postproc_finish(const double *sums, int nx, double dx, double *table);
  * upstream of column 1 (external + melt) and the discharge through x-face 1.  suhmo_level_postproc_temporal: a whole level. */
 int suhmo_postproc_temporal(const double *sums, int nx, double dx, double *out);
 int suhmo_level_postproc_temporal(suhmo_level_t *L, const suhmo_model_params_t *mp, double *out, suhmo_stream_t s);
+/* the same six values finished on the device (the body a run of an ensemble writes its rows with, suhmo_batch_run): the column sums stay there,
+ * 48 bytes come back.  The bits of suhmo_level_postproc_temporal: one thread per value, the host function's operations in its column order. */
+int suhmo_level_postproc_temporal_device(suhmo_level_t *L, const suhmo_model_params_t *mp, double *out, suhmo_stream_t s);
 
 /* setAlphaAndBeta (src/VCAMRNonLinearPoissonOp.cpp:462-469) and setBC (src/AMRNonLinearPoissonOp.cpp:1275-1278) of the
  * operator, for every multigrid depth of the level; setBC keeps the periodicity the level was created with */
@@ -543,6 +546,23 @@ int suhmo_hier_moulin_source(suhmo_hier_t *H, int n_moulins, const double *posit
  *   suhmo_batch_postproc_partial / _temporal / _table   suhmo_level_postproc_partial / _temporal / _table of every member with mp[n]: sums
  *                         [n][8][nx], out [n][6], table [n][nx][8].  One launch and one read-back for all members.  No time step run yet on a
  *                         member, or use_moulin_source without a source term: rc -1.
+ *   suhmo_batch_run       the time loop (AmrHydro::run, src/AmrHydro.cpp:1283-1365) of the members whose flag in active[n] is not 0 (NULL = all; none: a
+ *                         no-op, rc 0) in ONE call: per step k = 0 .. n_steps - 1 the forcing launches the schedule asks for, the step
+ *                         suhmo_batch_timestep runs (mp[n] with the schedule's ramp; cur_step = first_cur_step + k; members without a flag are in none
+ *                         of its launches) and, when (k + 1) % diag_every == 0, the column sums and one more launch that finishes the row of
+ *                         suhmo_batch_postproc_temporal ON THE DEVICE into a series [rows][n][6] -- no copy and no synchronisation per row.  After the
+ *                         last step the series comes back in one copy: the diagnostics of a run are ONE read-back in batch_readbacks whatever the
+ *                         number of rows.  Every member's fields, counts and rows are bit for bit what the per-call loop gives (recharge or moulin
+ *                         call, suhmo_batch_timestep, suhmo_batch_postproc_temporal).  The schedule carries VALUES, all host arrays (the caller
+ *                         evaluates the cos / sin of the temperature and the time factor, so they are its bits): see suhmo_batch_schedule_t.
+ *                         res: steps_done; picard_iters / vcycles [n_steps][n] (may be NULL; 0 for a member without a flag); rows [n_rows][n][6]
+ *                         (n_rows = n_steps / diag_every; the entries of members without a flag keep what the caller put there; may be NULL when
+ *                         diag_every = 0).  A step that fails ends the run: its rc, steps_done = the steps completed, the rows written so far
+ *                         copied out.  Checked on every flagged member before anything is launched, rc -1 / -5 and a message naming the member:
+ *                         SUHMO_F_ZS where a temperature schedule is given, sigma > 0 and non-empty moulin lists, use_moulin_source without a
+ *                         source, use_impl_diff against option implicit_gap, bottom_solver of the handles; n_steps < 1, dt <= 0, first_cur_step < 1,
+ *                         diag_every < 0, n_members other than the batch's, T_K without background (or the reverse), an incomplete set of moulin
+ *                         arrays, both kinds of forcing at once (they write the same source term): rc -1.
  *   suhmo_batch_set_option / get_option   tile_order (0 .. 2, as the level's); bottom_solver: get reports the creation value, set returns 0 for
  *                         that value and rc -5 for the other one (fixed at creation: suhmo_batch_create_opts); implicit_gap (0 / 1, default 0: see
  *                         suhmo_batch_timestep).  Read-only counters: batch_launches, batch_readbacks (both include the gap solves and the calls above),
@@ -552,7 +572,7 @@ int suhmo_hier_moulin_source(suhmo_hier_t *H, int n_moulins, const double *posit
  *                         Every batch call first checks that bottom_solver of every member handle is the batch's: a member set to the other value
  *                         through suhmo_level_set_option makes the call fail with rc -5 before anything is launched.
  * A batch relaxes every depth with the tile kernel (colour passes where the grid rules it out); eager launches only, no graph capture.
- * Not built: rank strips, AMR patches and hierarchies as members, graph capture, a host-loop RelaxSolver for bottoms the one launch cannot take. */
+ * Not built: rank strips, AMR patches and hierarchies as members, graph capture of a step or a run, a host-loop RelaxSolver for bottoms the one launch cannot take. */
 typedef struct suhmo_batch suhmo_batch_t;
 int suhmo_batch_create(suhmo_batch_t **out, const suhmo_level_desc_t *desc, int n_members);
 int suhmo_batch_create_opts(suhmo_batch_t **out, const suhmo_level_desc_t *desc, int n_members, const char *options);
@@ -569,6 +589,25 @@ int suhmo_batch_moulin_source(suhmo_batch_t *B, const int *n_moulins, const doub
 int suhmo_batch_postproc_partial(suhmo_batch_t *B, const suhmo_model_params_t *mp, double *sums, const int *active, suhmo_stream_t s);
 int suhmo_batch_postproc_temporal(suhmo_batch_t *B, const suhmo_model_params_t *mp, double *out, const int *active, suhmo_stream_t s);
 int suhmo_batch_postproc_table(suhmo_batch_t *B, const suhmo_model_params_t *mp, double *table, const int *active, suhmo_stream_t s);
+typedef struct suhmo_batch_schedule {
+    int n_steps;
+    double dt;
+    int first_cur_step;             /* cur_step of the first step (1 for a fresh batch; a second run continues with the first's + its n_steps) */
+    int n_members;                  /* the member count the arrays below are laid out for: must be the batch's */
+    const double *T_K, *background; /* [n_steps][n] each, or both NULL: one suhmo_batch_time_varying_recharge launch per step */
+    const int *n_moulins;           /* [n]; positions, sigma, flux: the members' lists concatenated, as suhmo_batch_moulin_source takes them, given */
+    const double *positions, *sigma, *flux;   /* once for the run; or all NULL */
+    const double *moulin_factor;    /* [n_steps][n]: the time factor of every step (three launches per step) */
+    const double *ramp;             /* [n_steps], or NULL: written into every member's mp.ramp for that step */
+    int diag_every;                 /* 0: no rows; else a row after step k when (k + 1) % diag_every == 0 */
+} suhmo_batch_schedule_t;
+typedef struct suhmo_batch_run_result {
+    int steps_done, n_rows;
+    int *picard_iters, *vcycles;    /* [n_steps][n], may be NULL */
+    double *rows;                   /* [n_steps / diag_every][n][6] */
+} suhmo_batch_run_result_t;
+int suhmo_batch_run(suhmo_batch_t *B, const suhmo_model_params_t *mp, const suhmo_batch_schedule_t *sch, const int *active,
+                    suhmo_batch_run_result_t *res, suhmo_stream_t s);
 int suhmo_batch_set_option(suhmo_batch_t *B, const char *key, long value);
 int suhmo_batch_get_option(const suhmo_batch_t *B, const char *key, long *value);
 

@@ -51,6 +51,20 @@ class LevelDesc(C.Structure):
                 ("i0", C.c_int), ("nx_global", C.c_int), ("patch_j0", C.c_int), ("patch_ny", C.c_int)]
 
 
+class BatchSchedule(C.Structure):
+    """suhmo_batch_schedule_t: the values a run of an ensemble is driven by (suhmo_batch_run), all host arrays"""
+    _fields_ = [("n_steps", C.c_int), ("dt", C.c_double), ("first_cur_step", C.c_int), ("n_members", C.c_int),
+                ("T_K", C.POINTER(C.c_double)), ("background", C.POINTER(C.c_double)),
+                ("n_moulins", C.POINTER(C.c_int)), ("positions", C.POINTER(C.c_double)), ("sigma", C.POINTER(C.c_double)),
+                ("flux", C.POINTER(C.c_double)), ("moulin_factor", C.POINTER(C.c_double)), ("ramp", C.POINTER(C.c_double)),
+                ("diag_every", C.c_int)]
+
+
+class BatchRunResult(C.Structure):
+    _fields_ = [("steps_done", C.c_int), ("n_rows", C.c_int), ("picard_iters", C.POINTER(C.c_int)), ("vcycles", C.POINTER(C.c_int)),
+                ("rows", C.POINTER(C.c_double))]
+
+
 EXCHANGE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int), C.c_int, C.c_void_p)
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(C.c_double))
 REDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(C.c_double), C.c_int, C.c_int)      # values, n, op (0 MAX, 1 SUM)
@@ -84,6 +98,7 @@ SYMBOLS = [
     "suhmo_batch_create", "suhmo_batch_destroy", "suhmo_batch_size", "suhmo_batch_member", "suhmo_batch_set_phys", "suhmo_batch_vcycle", "suhmo_batch_solve", "suhmo_batch_timestep",
     "suhmo_batch_set_option", "suhmo_batch_get_option", "suhmo_batch_create_opts",
     "suhmo_batch_time_varying_recharge", "suhmo_batch_moulin_source", "suhmo_batch_postproc_partial", "suhmo_batch_postproc_temporal", "suhmo_batch_postproc_table",
+    "suhmo_batch_run", "suhmo_level_postproc_temporal_device",
 ]
 
 
@@ -226,6 +241,8 @@ def lib():
     L.suhmo_batch_moulin_source.argtypes = [vp, ip, dp, dp, dp, dp, dp, ip, vp]
     for fn in (L.suhmo_batch_postproc_partial, L.suhmo_batch_postproc_temporal, L.suhmo_batch_postproc_table):
         fn.argtypes = [vp, C.POINTER(ModelParams), dp, ip, vp]
+    L.suhmo_batch_run.argtypes = [vp, C.POINTER(ModelParams), C.POINTER(BatchSchedule), ip, C.POINTER(BatchRunResult), vp]
+    L.suhmo_level_postproc_temporal_device.argtypes = [vp, C.POINTER(ModelParams), dp, vp]
     L.suhmo_batch_set_option.argtypes = [vp, C.c_char_p, C.c_long]
     L.suhmo_batch_get_option.argtypes = [vp, C.c_char_p, C.POINTER(C.c_long)]
     L.suhmo_level_profile_reset.argtypes = [vp]

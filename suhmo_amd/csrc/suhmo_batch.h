@@ -40,14 +40,17 @@ void suhmo_batch_count(suhmo_batch *B, int launches);
 int suhmo_batch_step_mg_coefficients(suhmo_batch *B, hipStream_t st);
 int suhmo_batch_step_solve(suhmo_batch *B, const suhmo_solver_params_t *sp, int *iters, hipStream_t st);   // SolveForHead_nl of the phase's members; iters[n]
 int suhmo_batch_step_read(suhmo_batch *B, hipStream_t st, double *a, double *b);                          // the pinned slots of the phase's members -> a[k], b[k]
-int suhmo_batch_step_begin(suhmo_batch *B, const suhmo_model_params_t *mp, hipStream_t st);   // tables against the handles, mp[n] on the device
+// tables against the handles, mp[n] on the device; serve[n] (NULL: everybody): the members this step is for
+int suhmo_batch_step_begin(suhmo_batch *B, const suhmo_model_params_t *mp, hipStream_t st, const char *serve = nullptr);
 // SolveForGap_nl of the members `sel` (all with use_impl_diff) on the gap batch, sp = gap_solver_params; mp: host rows of ALL members
 int suhmo_batch_step_solve_gap(suhmo_batch *B, const BatchSel &sel, const suhmo_model_params_t *mp, double dt, const suhmo_solver_params_t *sp, hipStream_t st);
 // suhmo_step.hip: b, RES, DCX, DCY of the members -> PHI, RHS, BX, BY of their gap handles (whole canvases) in one launch; and PHI of the gap
 // handles -> b in one, cells without ice keeping their b where the member's freeze_icefree_gap is set (mpt: device rows of mp[n])
 int suhmo_batch_gap_load(const OnMembers &h, const OnMembers &g, size_t elems, hipStream_t st);
 int suhmo_batch_gap_store(const OnMembers &h, const OnMembers &g, size_t elems, hipStream_t st);      // h.mp: the members' device rows
-int suhmo_batch_timestep_run(suhmo_batch *B, const suhmo_model_params_t *mp, double dt, int cur_step, int *picard_iters, int *vcycles, hipStream_t st);
+// active[n] (NULL: everybody): the members the step is for (suhmo_batch_run; the others are in none of its launches, 0 iterations)
+int suhmo_batch_timestep_run(suhmo_batch *B, const suhmo_model_params_t *mp, double dt, int cur_step, int *picard_iters, int *vcycles, hipStream_t st,
+                             const int *active = nullptr);
 
 // ---- forcing and diagnostics of the members in one launch each (suhmo_step.hip: the device bodies of the per-level calls over OnMembers)
 // COMPUTE_TIMEVARYINGRECHARGE of the members `t` serves: SUHMO_F_MSRC from the resident SUHMO_F_ZS, temperature and background input per member
@@ -59,7 +62,10 @@ struct MoulinJob {
     double *integ, *partial;           // n integrals; nblk x n tile sums
     double tf; double *out;            // time factor; the source term (a canvas of v)
 };
-// the lists of the members in `sel` (rows[k]: member k's, on the device; nmax: the longest of them): three launches
-int suhmo_batch_moulin_launch(const MoulinJob *rows, const BatchSel &sel, int nx, int ny, int nmax, hipStream_t st);
+// the lists of the members in `sel` (rows[k]: member k's, on the device; nmax: the longest of them): three launches.  tf != NULL: the time
+// factors of this launch, by value, instead of the rows' (a run writes the rows once and changes the factor every step)
+int suhmo_batch_moulin_launch(const MoulinJob *rows, const BatchSel &sel, int nx, int ny, int nmax, hipStream_t st, const PerMember *tf = nullptr);
 // column sums of the SHMIP tables (suhmo_level_postproc_partial), out[k][8][nx] for every member k `t` serves; t.mp: the members' device rows
 int launch_postproc_columns(const OnMembers &t, double *out, hipStream_t st);
+// suhmo_postproc_temporal of those column sums on the device: out[k][6] for every member k `t` serves (one row of a run's series)
+int launch_postproc_temporal_row(const OnMembers &t, const double *cols, double *out, hipStream_t st);

@@ -39,6 +39,7 @@ struct suhmo_batch {
     void *d_avg;                                            // the members' coefficient / face canvases of all depths (suhmo_bcoef.hip)
     suhmo_model_params_t *d_mp; std::vector<suhmo_model_params_t> h_mp;   // the time step: mp[n] on the device, rewritten when it changed
     BatchSel phase;                                         // the time step: the members the current phase serves
+    BatchSel everyone;                                      // ... and the members the step is for (all of them, or the active ones of a run)
     bool beta_per_member;                                   // a gap batch: beta belongs to the member (alpha and everything that shapes a launch stay shared)
     int implicit_gap;                                       // option: members with use_impl_diff are stepped (default 0: refused)
     suhmo_batch *gap;                                       // the gap batch, created by the first step that needs it; its counters add to this one's
@@ -51,6 +52,7 @@ struct suhmo_batch {
     double *d_moulin; size_t moulin_cap;                    // the members' rows (MoulinJob), their moulin tables, integrals and tile sums
     std::vector<double> h_moulin, h_integ;                  // what is sent to / read from it
     double *d_cols, *h_cols; size_t cols_cap;               // column sums [n][8][nx] on the device and in pinned host memory
+    double *d_series, *h_series; size_t series_cap;         // the finished rows of a run [rows][n][6] (suhmo_batch_run), the same way
 };
 constexpr int SLOT_FLAG = 2 * SUHMO_BATCH_MAX;             // pinned slot: two values per member, then the sequence number
 
@@ -267,6 +269,8 @@ extern "C" int suhmo_batch_destroy(suhmo_batch_t *B)
     if (B->d_moulin) (void)hipFree(B->d_moulin);
     if (B->d_cols) (void)hipFree(B->d_cols);
     if (B->h_cols) (void)hipHostFree(B->h_cols);
+    if (B->d_series) (void)hipFree(B->d_series);
+    if (B->h_series) (void)hipHostFree(B->h_series);
     if (B->hslot) (void)hipHostFree(B->hslot);
     if (B->gap) (void)suhmo_batch_destroy(B->gap);
     delete B;
@@ -343,7 +347,7 @@ static int batch_create(suhmo_batch **out, const suhmo_level_desc_t *desc, int n
     memset(B->h_mp.data(), 0xff, n_members * sizeof(suhmo_model_params_t));
     if (hipMalloc(&B->d_mp, n_members * sizeof(suhmo_model_params_t)) != hipSuccess) { suhmo_set_error("batch: hipMalloc failed"); return fail(-2); }
     { int rc = suhmo_batch_avg_table(B->mem.data(), n_members, &B->d_avg); if (rc) return fail(rc); }
-    B->phase = all_members(B);
+    B->phase = B->everyone = all_members(B);
     *out = B;
     return 0;
 }
@@ -426,7 +430,7 @@ bool suhmo_batch_step_select(suhmo_batch *B, const char *still)
 {
     BatchSel sel; memset(&sel, 0, sizeof(sel));
     for (int k = 0; k < B->n; k++) if (still[k]) sel.m[sel.n++] = (unsigned char)k;
-    B->phase = sel.n ? sel : all_members(B);
+    B->phase = sel.n ? sel : B->everyone;
     return sel.n > 0;
 }
 BatchStep suhmo_batch_step(suhmo_batch *B, bool reduction)
@@ -520,11 +524,13 @@ static int batch_mp_sync(suhmo_batch *B, const suhmo_model_params_t *mp, hipStre
     return 0;
 }
 // the step's entry: tables against the handles (the step's fields have just been allocated), mp[n] on the device, everybody in the first phase
-int suhmo_batch_step_begin(suhmo_batch *B, const suhmo_model_params_t *mp, hipStream_t st)
+int suhmo_batch_step_begin(suhmo_batch *B, const suhmo_model_params_t *mp, hipStream_t st, const char *serve)
 {
     int rc = batch_enter(B, st); if (rc) return rc;
     if ((rc = batch_mp_sync(B, mp, st))) return rc;
-    B->phase = all_members(B);
+    B->everyone = all_members(B);
+    if (serve) { B->everyone.n = 0; for (int k = 0; k < B->n; k++) if (serve[k]) B->everyone.m[B->everyone.n++] = (unsigned char)k; }
+    B->phase = B->everyone;
     return 0;
 }
 extern "C" int suhmo_batch_timestep(suhmo_batch_t *B, const suhmo_model_params_t *mp, double dt, int cur_step, int *picard_iters, int *vcycles,
@@ -571,28 +577,27 @@ extern "C" int suhmo_batch_time_varying_recharge(suhmo_batch_t *B, const double 
     return 0;
 }
 // member k's moulins are entries off[k] .. off[k] + n_moulins[k] - 1 of the concatenated arrays, off[k] = the entries of the members before it
-// (a member without a flag may give 0, or a list that is skipped)
-extern "C" int suhmo_batch_moulin_source(suhmo_batch_t *B, const int *n_moulins, const double *positions, const double *sigma, const double *flux,
-                                         const double *time_factor, double *integrals, const int *active, suhmo_stream_t s)
+// (a member without a flag may give 0, or a list that is skipped).  The checks of every flagged member; *nmax: the longest list
+static int batch_moulin_check(const suhmo_batch *B, const BatchSel &sel, const int *n_moulins, const double *sigma, size_t *off, int *nmax)
 {
-    SUHMO_TIME("AmrHydro::Calc_moulin_source_term_distributed");
-    ARG(B && n_moulins && positions && sigma && flux && time_factor);
-    hipStream_t st = (hipStream_t)s;
-    const BatchSel sel = flagged_members(B, active);
-    if (!sel.n) return 0;
-    size_t off[SUHMO_BATCH_MAX + 1];
     off[0] = 0;
     for (int k = 0; k < B->n; k++) off[k + 1] = off[k] + (n_moulins[k] > 0 ? (size_t)n_moulins[k] : 0);
-    const size_t N = off[B->n];
-    int nmax = 0;
+    *nmax = 0;
     for (int z = 0; z < sel.n; z++) {
         const int k = sel.m[z];
         if (n_moulins[k] < 1) { suhmo_set_error("batch: moulin source: n_moulins = %d on member %d (at least 1)", n_moulins[k], k); return -1; }
         for (int m = 0; m < n_moulins[k]; m++)
             if (!(sigma[off[k] + m] > 0.0)) { suhmo_set_error("batch: moulin source: sigma <= 0 (member %d, its moulin %d)", k, m); return -1; }
-        nmax = std::max(nmax, n_moulins[k]);
+        *nmax = std::max(*nmax, n_moulins[k]);
     }
-    int rc = batch_source_fields(B, sel, st); if (rc) return rc;
+    return 0;
+}
+// the lists and a row (MoulinJob) per flagged member into the batch's scratch, enqueued on st; time_factor NULL: 0 in the rows (a run passes the
+// factor with every launch).  *integ_d: where the integrals of all lists will be
+static int batch_moulin_upload(suhmo_batch *B, const BatchSel &sel, const int *n_moulins, const double *positions, const double *sigma, const double *flux,
+                               const double *time_factor, const size_t *off, hipStream_t st, double **integ_out)
+{
+    const size_t N = off[B->n];
     const DV &v = view(B, 0);
     const size_t nblk = (size_t)((v.nx + 15) / 16) * ((v.ny + 15) / 16);
     // the device scratch: rows[n] | {x, y, sigma} x n_k, flux x n_k of every member (4 N) | integrals (N) | tile sums (nblk x N)
@@ -616,23 +621,43 @@ extern "C" int suhmo_batch_moulin_source(suhmo_batch_t *B, const int *n_moulins,
             tab_h[4 * o + 3 * (size_t)n + m] = flux[o + m];
         }
         const Depth &D = B->mem[k]->d[0];
-        const MoulinJob job{D.v, n, (int)nblk, tab_d + 4 * o, tab_d + 4 * o + 3 * (size_t)n, integ_d + o, partial_d + nblk * o, time_factor[k], D.fp.f[SUHMO_F_MSRC]};
+        const MoulinJob job{D.v, n, (int)nblk, tab_d + 4 * o, tab_d + 4 * o + 3 * (size_t)n, integ_d + o, partial_d + nblk * o, time_factor ? time_factor[k] : 0.0,
+                            D.fp.f[SUHMO_F_MSRC]};
         memcpy(B->h_moulin.data() + k * rowd, &job, sizeof(job));
     }
-    hipError_t e = hipMemcpyAsync(B->d_moulin, B->h_moulin.data(), B->h_moulin.size() * sizeof(double), hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) {
-        if ((rc = suhmo_batch_moulin_launch((const MoulinJob *)B->d_moulin, sel, v.nx, v.ny, nmax, st))) return rc;
-        B->launches += 3;
-        if (integrals) { B->h_integ.resize(N); e = hipMemcpyAsync(B->h_integ.data(), integ_d, N * sizeof(double), hipMemcpyDeviceToHost, st); }
-    }
+    *integ_out = integ_d;
+    const hipError_t e = hipMemcpyAsync(B->d_moulin, B->h_moulin.data(), B->h_moulin.size() * sizeof(double), hipMemcpyHostToDevice, st);
+    if (e != hipSuccess) { suhmo_set_error("batch: moulin source: %s", hipGetErrorString(e)); return -2; }
+    return 0;
+}
+extern "C" int suhmo_batch_moulin_source(suhmo_batch_t *B, const int *n_moulins, const double *positions, const double *sigma, const double *flux,
+                                         const double *time_factor, double *integrals, const int *active, suhmo_stream_t s)
+{
+    SUHMO_TIME("AmrHydro::Calc_moulin_source_term_distributed");
+    ARG(B && n_moulins && positions && sigma && flux && time_factor);
+    hipStream_t st = (hipStream_t)s;
+    const BatchSel sel = flagged_members(B, active);
+    if (!sel.n) return 0;
+    size_t off[SUHMO_BATCH_MAX + 1];
+    int nmax = 0;
+    int rc = batch_moulin_check(B, sel, n_moulins, sigma, off, &nmax); if (rc) return rc;
+    const size_t N = off[B->n];
+    if ((rc = batch_source_fields(B, sel, st))) return rc;
+    const DV &v = view(B, 0);
+    double *integ_d = nullptr;
+    if ((rc = batch_moulin_upload(B, sel, n_moulins, positions, sigma, flux, time_factor, off, st, &integ_d))) return rc;
+    if ((rc = suhmo_batch_moulin_launch((const MoulinJob *)B->d_moulin, sel, v.nx, v.ny, nmax, st))) return rc;
+    B->launches += 3;
+    hipError_t e = hipSuccess;
+    if (integrals) { B->h_integ.resize(N); e = hipMemcpyAsync(B->h_integ.data(), integ_d, N * sizeof(double), hipMemcpyDeviceToHost, st); }
     if (e == hipSuccess) e = hipStreamSynchronize(st);       // (the one synchronisation: the integrals have arrived, the host table may be written again)
     if (e != hipSuccess) { suhmo_set_error("batch: moulin source: %s", hipGetErrorString(e)); return -2; }
     if (integrals)
         for (int z = 0; z < sel.n; z++) { const int k = sel.m[z]; memcpy(integrals + off[k], B->h_integ.data() + off[k], n_moulins[k] * sizeof(double)); }
     return 0;
 }
-// column sums of the flagged members in B->h_cols[k][8][nx]: one launch, one copy, one synchronisation
-static int batch_column_sums(suhmo_batch *B, const suhmo_model_params_t *mp, const BatchSel &sel, hipStream_t st)
+// column sums of the flagged members in B->d_cols[k][8][nx]: the checks, then one launch
+static int batch_column_launch(suhmo_batch *B, const suhmo_model_params_t *mp, const BatchSel &sel, hipStream_t st)
 {
     for (int z = 0; z < sel.n; z++) {
         const int k = sel.m[z];
@@ -655,6 +680,13 @@ static int batch_column_sums(suhmo_batch *B, const suhmo_model_params_t *mp, con
     }
     if ((rc = launch_postproc_columns(on_members(tab(B, 0), sel, v, B->d_mp), B->d_cols, st))) return rc;
     B->launches++;
+    return 0;
+}
+// ... and in B->h_cols[k][8][nx]: one copy, one synchronisation
+static int batch_column_sums(suhmo_batch *B, const suhmo_model_params_t *mp, const BatchSel &sel, hipStream_t st)
+{
+    int rc = batch_column_launch(B, mp, sel, st); if (rc) return rc;
+    const size_t per = 8 * (size_t)view(B, 0).nx;
     const int k0 = sel.m[0], k1 = sel.m[sel.n - 1];           // (the list ascends: the rows from the first to the last flagged member)
     HIPCHK(hipMemcpyAsync(B->h_cols + k0 * per, B->d_cols + k0 * per, (k1 - k0 + 1) * per * sizeof(double), hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
@@ -691,6 +723,106 @@ extern "C" int suhmo_batch_postproc_table(suhmo_batch_t *B, const suhmo_model_pa
 {
     ARG(B && mp && table);
     return batch_postproc(B, mp, table, active, s, 2);
+}
+
+// ---- the run: AmrHydro::run (src/AmrHydro.cpp:1283-1365) of the flagged members in one call.  Per step the forcing launches from the
+// schedule's values, suhmo_batch_timestep_run, and on a diagnostic step the column sums and the row finished on the device
+// (d_postproc_temporal_row) into B->d_series[row][n][6]; one copy and one synchronisation after the last step
+static int batch_run_series_out(suhmo_batch *B, const BatchSel &sel, int rows, double *out, hipStream_t st)
+{
+    if (rows <= 0) return 0;
+    const size_t per = 6 * (size_t)B->n;
+    HIPCHK(hipMemcpyAsync(B->h_series, B->d_series, rows * per * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    B->readbacks++;
+    for (int r = 0; r < rows; r++)                           // (the entries of members without a flag stay the caller's)
+        for (int z = 0; z < sel.n; z++) memcpy(out + r * per + 6 * (size_t)sel.m[z], B->h_series + r * per + 6 * (size_t)sel.m[z], 6 * sizeof(double));
+    return 0;
+}
+extern "C" int suhmo_batch_run(suhmo_batch_t *B, const suhmo_model_params_t *mp, const suhmo_batch_schedule_t *sch, const int *active,
+                               suhmo_batch_run_result_t *res, suhmo_stream_t s)
+{
+    SUHMO_TIME("AmrHydro::run");
+    ARG(B && mp && sch && res);
+    hipStream_t st = (hipStream_t)s;
+    res->steps_done = 0; res->n_rows = 0;
+    if (sch->n_steps < 1) { suhmo_set_error("batch: run: n_steps = %d (at least 1)", sch->n_steps); return -1; }
+    if (!(sch->dt > 0.0) || sch->first_cur_step < 1 || sch->diag_every < 0) { suhmo_set_error("batch: run: dt > 0, first_cur_step >= 1 and diag_every >= 0"); return -1; }
+    if (sch->n_members != B->n) { suhmo_set_error("batch: run: the schedule is laid out for %d members, the batch has %d", sch->n_members, B->n); return -1; }
+    const bool recharge = sch->T_K || sch->background, moulins = sch->n_moulins || sch->positions || sch->sigma || sch->flux || sch->moulin_factor;
+    if (recharge && !(sch->T_K && sch->background)) { suhmo_set_error("batch: run: a temperature schedule needs T_K and background"); return -1; }
+    if (moulins && !(sch->n_moulins && sch->positions && sch->sigma && sch->flux && sch->moulin_factor)) {
+        suhmo_set_error("batch: run: a moulin schedule needs n_moulins, positions, sigma, flux and moulin_factor"); return -1;
+    }
+    if (recharge && moulins) { suhmo_set_error("batch: run: a temperature schedule and a moulin schedule write the same source term (SUHMO_F_MSRC): give one"); return -1; }
+    const int n = B->n, total_rows = sch->diag_every ? sch->n_steps / sch->diag_every : 0;
+    if (total_rows > 0 && !res->rows) { suhmo_set_error("batch: run: %d rows and no array for them", total_rows); return -1; }
+    const BatchSel sel = flagged_members(B, active);
+    if (!sel.n) return 0;
+    // ---- every flagged member, before anything is launched
+    size_t off[SUHMO_BATCH_MAX + 1];
+    int nmax = 0, rc;
+    for (int z = 0; z < sel.n; z++) {
+        const int k = sel.m[z];
+        const Depth &D = B->mem[k]->d[0];
+        if (recharge && !D.fp.f[SUHMO_F_ZS]) { suhmo_set_error("batch: run: time-varying recharge: load the ice surface height (SUHMO_F_ZS) of member %d first", k); return -1; }
+        if (mp[k].use_impl_diff && !B->implicit_gap) { suhmo_set_error("batch: run: use_impl_diff = 1 (member %d) without batch option implicit_gap", k); return -5; }
+        if (mp[k].use_impl_diff && mp[k].diffFactor == 0.0) { suhmo_set_error("batch: run: use_ImplDiff with diffFactor = 0 (member %d)", k); return -1; }
+        if (mp[k].use_moulin_source && !recharge && !moulins && !D.fp.f[SUHMO_F_MSRC]) {
+            suhmo_set_error("batch: run: use_moulin_source without a source term or a schedule that writes one (member %d)", k); return -1;
+        }
+    }
+    if (moulins && (rc = batch_moulin_check(B, sel, sch->n_moulins, sch->sigma, off, &nmax))) return rc;
+    HIPCHK(hipSetDevice(B->device));
+    if ((rc = (recharge || moulins) ? batch_source_fields(B, sel, st) : batch_enter(B, st))) return rc;      // (bottom_solver of the handles: rc -5)
+    // ---- what the run needs on the device: the lists once, the series
+    const DV &v = view(B, 0);
+    if (moulins) {
+        double *integ_d = nullptr;
+        if ((rc = batch_moulin_upload(B, sel, sch->n_moulins, sch->positions, sch->sigma, sch->flux, nullptr, off, st, &integ_d))) return rc;
+        HIPCHK(hipStreamSynchronize(st));                    // (the host table may be written again)
+    }
+    const size_t per = 6 * (size_t)n;
+    if (total_rows * per > B->series_cap) {
+        HIPCHK(hipStreamSynchronize(st));
+        if (B->d_series) (void)hipFree(B->d_series);
+        if (B->h_series) (void)hipHostFree(B->h_series);
+        B->d_series = B->h_series = nullptr; B->series_cap = 0;
+        HIPCHK(hipMalloc(&B->d_series, total_rows * per * sizeof(double)));
+        HIPCHK(hipHostMalloc(&B->h_series, total_rows * per * sizeof(double), hipHostMallocDefault));
+        B->series_cap = total_rows * per;
+    }
+    std::vector<suhmo_model_params_t> mps(mp, mp + n);
+    int rows = 0;
+    rc = 0;
+    for (int k = 0; k < sch->n_steps && !rc; k++) {
+        PerMember a, b;
+        if (recharge) {
+            memset(&a, 0, sizeof(a)); memset(&b, 0, sizeof(b));
+            for (int m = 0; m < n; m++) { a.x[m] = sch->T_K[(size_t)k * n + m]; b.x[m] = sch->background[(size_t)k * n + m]; }
+            if ((rc = launch_time_varying_recharge(on(B, 0, sel), a, b, st))) break;
+            B->launches++;
+        }
+        if (moulins) {
+            memset(&a, 0, sizeof(a));
+            for (int m = 0; m < n; m++) a.x[m] = sch->moulin_factor[(size_t)k * n + m];
+            if ((rc = suhmo_batch_moulin_launch((const MoulinJob *)B->d_moulin, sel, v.nx, v.ny, nmax, st, &a))) break;
+            B->launches += 3;
+        }
+        if (sch->ramp) for (int m = 0; m < n; m++) mps[m].ramp = sch->ramp[k];
+        if ((rc = suhmo_batch_timestep_run(B, mps.data(), sch->dt, sch->first_cur_step + k, res->picard_iters ? res->picard_iters + (size_t)k * n : nullptr,
+                                           res->vcycles ? res->vcycles + (size_t)k * n : nullptr, st, active))) break;
+        res->steps_done = k + 1;
+        if (sch->diag_every && (k + 1) % sch->diag_every == 0) {
+            if ((rc = batch_column_launch(B, mps.data(), sel, st))) break;
+            if ((rc = launch_postproc_temporal_row(on(B, 0, sel), B->d_cols, B->d_series + rows * per, st))) break;
+            B->launches++;
+            rows++;
+        }
+    }
+    res->n_rows = rows;
+    const int rc2 = batch_run_series_out(B, sel, rows, res->rows, st);
+    return rc ? rc : rc2;
 }
 
 extern "C" int suhmo_batch_set_option(suhmo_batch_t *B, const char *key, long value)

@@ -467,7 +467,7 @@ template <class Y> static int mg_coefficients(Y &y) { return suhmo_build_mg_coef
 template <class Y> static int explicit_gap_ghosts(Y &y, int l, const suhmo_model_params_t *mp) { return mp->use_impl_diff ? 0 : y.gap_ghosts(l); }
 template <class Y> static int implicit_gap_solve(Y &y, const suhmo_model_params_t *mp, double dt, int cur_step) { return mp->use_impl_diff ? y.solve_gap(mp, dt, cur_step) : 0; }
 template <class Y>
-static int timestep_fas(Y &y, const suhmo_model_params_t *mp, double dt, int cur_step, int *picard_iters, int *vcycles)
+static int timestep_fas(Y &y, const suhmo_model_params_t *mp, double dt, int cur_step, int *picard_iters, int *vcycles, const char *serve = nullptr)
 {
     int rc;
     // [I] ghosts of b (exchange + CopyGhostCells, :2385,:2429); ghosts of h are evaluated on the fly.  MGnewOp coarsening of B
@@ -480,7 +480,7 @@ static int timestep_fas(Y &y, const suhmo_model_params_t *mp, double dt, int cur
     int ite[SUHMO_BATCH_MAX], nv[SUHMO_BATCH_MAX], it[SUHMO_BATCH_MAX];
     char still[SUHMO_BATCH_MAX];
     double maxHead[SUHMO_BATCH_MAX], maxd[SUHMO_BATCH_MAX];
-    for (int k = 0; k < n; k++) { ite[k] = nv[k] = 0; still[k] = 1; }
+    for (int k = 0; k < n; k++) { ite[k] = nv[k] = 0; still[k] = serve ? serve[k] : 1; }    // (serve: the members of a layout the step is for)
     for (int ite_idx = 0; y.select(still); ite_idx++) {                           // [II]
         if ((rc = y.lag_head())) return rc;                                       // h_lagged = h, coarse-fine ghosts of b and mR
         for (int l = 0; l < y.nlev; l++) if ((rc = y.chain(l))) return rc;       // grad h, Re, Qw
@@ -644,20 +644,25 @@ static int implicit_gap_solve(Batch &y, const suhmo_model_params_t *mp, double d
     const BatchSel sel = suhmo_batch_step_subset(y.B, mp, is_implicit);
     return sel.n > 0 ? y.solve_gap(sel, mp, dt, cur_step) : 0;
 }
-int suhmo_batch_timestep_run(suhmo_batch *B, const suhmo_model_params_t *mp, double dt, int cur_step, int *picard_iters, int *vcycles, hipStream_t st)
+// active (NULL: everybody): the members the step is for; the others are in none of its launches and report 0 iterations
+int suhmo_batch_timestep_run(suhmo_batch *B, const suhmo_model_params_t *mp, double dt, int cur_step, int *picard_iters, int *vcycles, hipStream_t st,
+                             const int *active)
 {
     int rc = 0;
+    char serve[SUHMO_BATCH_MAX];
+    for (int k = 0; k < suhmo_batch_size_(B); k++) serve[k] = !active || active[k];
     for (int k = 0; k < suhmo_batch_size_(B) && !rc; k++) rc = check_step_args(&mp[k], dt, cur_step);
     if (rc) return rc;
     for (int k = 0; k < suhmo_batch_size_(B); k++) {
+        if (!serve[k]) continue;
         suhmo_level *L = suhmo_batch_member(B, k);
         if (mp[k].use_moulin_source && !L->d[0].fp.f[SUHMO_F_MSRC]) { suhmo_set_error("use_moulin_source without suhmo_level_moulin_source (member %d)", k); return -1; }
         for (int f : step_fields) if (!suhmo_field(L, 0, f)) { suhmo_set_error("field allocation failed"); return -2; }
         if (mp[k].diffFactor != 0.0) for (int f : {SUHMO_F_DCX, SUHMO_F_DCY, SUHMO_F_DTERM}) if (!suhmo_field(L, 0, f)) { suhmo_set_error("field allocation failed"); return -2; }
     }
-    if ((rc = suhmo_batch_step_begin(B, mp, st))) return rc;
+    if ((rc = suhmo_batch_step_begin(B, mp, st, active ? serve : nullptr))) return rc;
     Batch y{B, st, 1, suhmo_batch_size_(B)};
-    return timestep_fas(y, mp, dt, cur_step, picard_iters, vcycles);
+    return timestep_fas(y, mp, dt, cur_step, picard_iters, vcycles, active ? serve : nullptr);
 }
 
 
@@ -1072,10 +1077,17 @@ __device__ __forceinline__ double moulin_cell(double xc, double yc, double dx, d
 struct OneMoulinList {
     MoulinJob j;
     __device__ __forceinline__ const MoulinJob &job() const { return j; }
+    __device__ __forceinline__ double time_factor() const { return j.tf; }
 };
 struct MemberMoulinLists {
     const MoulinJob *rows; BatchSel sel;
     __device__ __forceinline__ const MoulinJob &job() const { return rows[batch_member(sel)]; }
+    __device__ __forceinline__ double time_factor() const { return job().tf; }
+};
+// the same rows under the time factors of one step of a run (suhmo_batch_run): by value with the launch, the rows are written once
+struct StepMoulinLists : MemberMoulinLists {
+    PerMember tf;
+    __device__ __forceinline__ double time_factor() const { return tf.x[batch_member(sel)]; }
 };
 __device__ __forceinline__ void d_moulin_partial(const DV &v, int n, const double *__restrict__ mo, double *__restrict__ partial, const Excl &ex,
                                                  const double *__restrict__ cover)
@@ -1142,7 +1154,7 @@ template <class J> __global__ void k_moulin_final(J t)
 template <class J> __global__ __launch_bounds__(256) void k_moulin_src(J t, Excl ex, const double *__restrict__ cover)
 {
     const MoulinJob &j = t.job();
-    d_moulin_src(j.v, j.n, j.mo, j.flux, j.integ, j.tf, j.out, ex, cover);
+    d_moulin_src(j.v, j.n, j.mo, j.flux, j.integ, t.time_factor(), j.out, ex, cover);
 }
 // the launchers: 16 x 16 tiles of the job's view (grd), one workgroup per moulin for the integrals; gz = 1, or the active members
 template <class J> void launch_moulin_partial(const J &t, dim3 grd, hipStream_t st, Excl ex, const double *cover = nullptr)
@@ -1165,14 +1177,16 @@ OneMoulinList moulin_source_on(const DV &v, int n, const double *mo, const doubl
 }
 }  // namespace
 // the lists of the active members of an ensemble (rows[k]: member k's, on the device; nmax: the longest list): three launches whatever their number
-int suhmo_batch_moulin_launch(const MoulinJob *rows, const BatchSel &sel, int nx, int ny, int nmax, hipStream_t st)
+// (tf != NULL: the time factors of this launch instead of the rows')
+int suhmo_batch_moulin_launch(const MoulinJob *rows, const BatchSel &sel, int nx, int ny, int nmax, hipStream_t st, const PerMember *tf)
 {
     if (sel.n <= 0) return 0;
     const MemberMoulinLists t{rows, sel};
     const dim3 grd((nx + 15) / 16, (ny + 15) / 16, sel.n);
     launch_moulin_partial(t, grd, st, Excl{0, 0, 0, 0});
     launch_moulin_final(t, nmax, sel.n, st);
-    launch_moulin_src(t, grd, st, Excl{0, 0, 0, 0});
+    if (tf) launch_moulin_src(StepMoulinLists{{rows, sel}, *tf}, grd, st, Excl{0, 0, 0, 0});
+    else launch_moulin_src(t, grd, st, Excl{0, 0, 0, 0});
     HIPCHK(hipGetLastError());
     return 0;
 }
@@ -1522,6 +1536,65 @@ extern "C" int suhmo_level_postproc_temporal(suhmo_level_t *L, const suhmo_model
     std::vector<double> h(8 * (size_t)D.v.nx);
     int rc = suhmo_level_postproc_partial(L, mp, h.data(), s); if (rc) return rc;
     return suhmo_postproc_temporal(h.data(), D.v.nx, D.v.dx, out);
+}
+// suhmo_postproc_temporal on the device: the six values from column sums that never leave it (a run keeps finished rows, 6 doubles per member,
+// instead of 8 nx).  One thread per value, each the host function's loop over the columns in ascending order with its operations -- no tree, so
+// the bits are the host's (0 / 0 of an empty band: NaN on both sides)
+__device__ __forceinline__ void d_postproc_temporal_row(const DV &v, const double *__restrict__ h /* 8 x nx */, double *__restrict__ out /* 6 */)
+{
+    const int q = threadIdx.x;
+    if (q >= 6) return;
+    const size_t nx = v.nx;
+    if (q == 0) {
+        double tot = 0.0, cnt = 0.0;
+        for (size_t i = 0; i < nx; i++) { tot += h[6 * nx + i]; cnt += h[7 * nx + i]; }
+        out[0] = tot / cnt;
+    } else if (q <= 3) {
+        const double lo = q == 1 ? 600.0 : q == 2 ? 3000.0 : 5100.0, hi = q == 1 ? 900.0 : q == 2 ? 3300.0 : 5400.0;
+        double bs = 0.0, bc = 0.0;
+        for (size_t i = 0; i < nx; i++) {
+            const double x = ((int)i + 0.5) * v.dx;
+            if (x > lo && x < hi) { bs += h[6 * nx + i]; bc += h[7 * nx + i]; }
+        }
+        out[q] = bs / bc;
+    } else if (q == 4) {
+        double rech = 0.0;
+        for (size_t i = 1; i < nx; i++) rech += h[4 * nx + i] + h[5 * nx + i];
+        out[4] = rech;
+    } else out[5] = -h[1 * nx + 1];
+}
+// cols: 8 x nx of a level, [n][8][nx] of an ensemble; out: 6 values, of an ensemble [n][6] (one row of a series): the entries of the members served
+template <class T> __global__ void k_postproc_temporal_row(T t, const double *__restrict__ cols, double *__restrict__ out)
+{
+    d_postproc_temporal_row(t.view(), cols + t.slot(8 * (size_t)t.view().nx), out + t.slot(6));
+}
+template <class T> static int launch_postproc_temporal_row_(const T &t, const double *cols, double *out, hipStream_t st)
+{
+    return launch_grid(k_postproc_temporal_row<T>, t, dim3(1), dim3(64), st, cols, out);
+}
+int launch_postproc_temporal_row(const OnMembers &t, const double *cols, double *out, hipStream_t st) { return launch_postproc_temporal_row_(t, cols, out, st); }
+extern "C" int suhmo_level_postproc_temporal_device(suhmo_level_t *L, const suhmo_model_params_t *mp, double *out, suhmo_stream_t s)
+{
+    ARG(L && mp && out);
+    HIPCHK(hipSetDevice(L->device));
+    hipStream_t st = (hipStream_t)s;
+    Depth &D = L->d[0];
+    if (L->desc.nx_global > 0) { suhmo_set_error("post-processing table on an AMR patch is not built"); return -5; }
+    if (D.v.ext[0] || D.v.ext[1]) { suhmo_set_error("rank strip: add the strips' suhmo_level_postproc_partial sums, then suhmo_postproc_temporal"); return -5; }
+    if (D.v.nx < 2) { suhmo_set_error("temporal post-processing needs at least two columns"); return -1; }
+    for (int f : {SUHMO_F_QWX, SUHMO_F_CD, SUHMO_F_MR, SUHMO_F_PW}) if (!D.fp.f[f]) { suhmo_set_error("no time step has run on this level"); return -1; }
+    if (mp->use_moulin_source && !D.fp.f[SUHMO_F_MSRC]) { suhmo_set_error("use_moulin_source without suhmo_level_moulin_source"); return -1; }
+    const size_t ncol = 8 * (size_t)D.v.nx;
+    double *dev = nullptr;
+    HIPCHK(hipMalloc(&dev, (ncol + 6) * sizeof(double)));
+    int rc = launch_postproc_columns_(stepping(on_level(L, 0), *mp), dev, st);
+    if (!rc) rc = launch_postproc_temporal_row_(on_level(L, 0), dev, dev + ncol, st);
+    hipError_t e = rc ? hipSuccess : hipMemcpyAsync(out, dev + ncol, 6 * sizeof(double), hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    (void)hipFree(dev);
+    if (rc) return rc;
+    if (e != hipSuccess) { suhmo_set_error("postproc temporal: %s", hipGetErrorString(e)); return -2; }
+    return 0;
 }
 extern "C" int suhmo_level_postproc_table(suhmo_level_t *L, const suhmo_model_params_t *mp, double *table, suhmo_stream_t s)
 {

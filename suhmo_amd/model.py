@@ -72,6 +72,12 @@ class HipModel:
         check(capi.lib().suhmo_level_postproc_temporal(self.level.h, C.byref(self._mp), out.ctypes.data_as(C.POINTER(C.c_double)), self.level.stream))
         return out
 
+    def postproc_temporal_device(self):
+        """the same row finished on the device (suhmo_level_postproc_temporal_device): the column sums stay there"""
+        out = np.zeros(6)
+        check(capi.lib().suhmo_level_postproc_temporal_device(self.level.h, C.byref(self._mp), out.ctypes.data_as(C.POINTER(C.c_double)), self.level.stream))
+        return out
+
     def postproc_table_device(self):
         """SHMIP cross-section table reduced on the device (suhmo_level_postproc_table)"""
         t = np.zeros((self.nx, 8))
@@ -245,6 +251,75 @@ class HipBatchModel:
     def postproc_table_device_all(self, active=None, out=None):
         """the SHMIP cross-section table of every member, (n, nx, 8)"""
         return self._postproc_all(capi.lib().suhmo_batch_postproc_table, (self.nx, 8), active, out)
+
+    def run(self, n_steps, dt, T_K=None, background=None, moulins=None, moulin_factor=None, ramp=None, diag_every=0, active=None, rows=None):
+        """the time loop of the active members in ONE call (suhmo_batch_run): per step the forcing of the schedule, the time step and, after
+        every diag_every-th step, the daily row finished on the device; the rows of the whole run come back in one copy.  Bit for bit what
+        time_varying_recharge / moulin_source, timestep and postproc_temporal_all give step by step.
+        T_K, background: (n_steps, n), or anything that broadcasts to it (a column per step, a scalar): the seasonal recharge, VALUES -- the
+        caller evaluates the temperature.  moulins: lists[k] = (positions, sigma, flux) as moulin_source takes them, given once, with
+        moulin_factor (n_steps, n).  ramp: (n_steps,), written into every member's ramp for that step.  rows: an (n_rows, n, 6) array whose
+        entries of the members that are not active are kept.
+        Returns (picard iterations (n_steps, n), V-cycles (n_steps, n), rows (n_steps // diag_every, n, 6))."""
+        n = self.n
+        n_steps, diag_every = int(n_steps), int(diag_every)
+        dp = lambda a: a.ctypes.data_as(C.POINTER(C.c_double))
+        keep = []                                              # the arrays the schedule points into
+
+        def table(x, what):
+            a = np.asarray(x, dtype=np.float64)
+            if a.ndim == 2 and a.shape != (max(n_steps, 0), n):
+                raise ValueError("%s has shape %s, the run needs (n_steps, n) = (%d, %d)" % (what, a.shape, n_steps, n))
+            a = np.ascontiguousarray(np.broadcast_to(a, (max(n_steps, 0), n)))
+            keep.append(a)
+            return dp(a)
+
+        sch = capi.BatchSchedule(n_steps=n_steps, dt=float(dt), first_cur_step=self.cur_step + 1, n_members=n, diag_every=diag_every)
+        if (T_K is None) != (background is None):
+            raise ValueError("the seasonal recharge needs T_K and background")
+        if T_K is not None:
+            sch.T_K, sch.background = table(T_K, "T_K"), table(background, "background")
+        if (moulins is None) != (moulin_factor is None):
+            raise ValueError("a moulin schedule needs moulins and moulin_factor")
+        if moulins is not None:
+            on = [True] * n if active is None else [bool(x) for x in active]
+            if len(moulins) != n:
+                raise ValueError("moulins has %d lists, the batch %d members" % (len(moulins), n))
+            pos, sg, fl, cnt = [], [], [], []
+            for k in range(n):
+                if moulins[k] is None:
+                    assert not on[k], "member %d is active and has no moulin list" % k
+                    cnt.append(0)
+                    continue
+                sgk = np.asarray(moulins[k][1], dtype=np.float64).reshape(-1)
+                pos.append(np.asarray(moulins[k][0], dtype=np.float64).reshape(-1)); sg.append(sgk); fl.append(np.asarray(moulins[k][2], dtype=np.float64).reshape(-1))
+                assert pos[-1].size == 2 * sgk.size and fl[-1].size == sgk.size
+                cnt.append(sgk.size)
+            cat = lambda a: np.ascontiguousarray(np.concatenate(a)) if a and sum(x.size for x in a) else np.zeros(1)
+            pos, sg, fl, cnt = cat(pos), cat(sg), cat(fl), (C.c_int * n)(*cnt)
+            keep += [pos, sg, fl, cnt]
+            sch.n_moulins, sch.positions, sch.sigma, sch.flux, sch.moulin_factor = cnt, dp(pos), dp(sg), dp(fl), table(moulin_factor, "moulin_factor")
+        if ramp is not None:
+            r = np.ascontiguousarray(ramp, dtype=np.float64)
+            if r.shape != (max(n_steps, 0),):
+                raise ValueError("ramp has shape %s, the run needs (n_steps,) = (%d,)" % (r.shape, n_steps))
+            keep.append(r)
+            sch.ramp = dp(r)
+        n_rows = n_steps // diag_every if diag_every > 0 and n_steps > 0 else 0
+        out = np.zeros((n_rows, n, 6)) if rows is None else rows
+        assert out.shape == (n_rows, n, 6) and out.dtype == np.float64 and out.flags.c_contiguous
+        pi, nv = np.zeros((max(n_steps, 0), n), dtype=np.intc), np.zeros((max(n_steps, 0), n), dtype=np.intc)
+        ip = lambda a: a.ctypes.data_as(C.POINTER(C.c_int))
+        res = capi.BatchRunResult(picard_iters=ip(pi), vcycles=ip(nv), rows=dp(out))
+        rc = capi.lib().suhmo_batch_run(self.batch.h, self._mp, C.byref(sch), self._active(active), C.byref(res), self.batch.stream)
+        self.cur_step += res.steps_done
+        for m in self.members:
+            m.cur_step = self.cur_step
+        if ramp is not None and res.steps_done > 0:            # the members' ramp is the last step's, as a loop of set_model leaves it
+            for k in range(n):
+                self.set_model(k, ramp=float(r[res.steps_done - 1]))
+        check(rc)
+        return pi, nv, out
 
     def get_option(self, key):
         return self.batch.get_option(key)

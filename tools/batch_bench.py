@@ -23,6 +23,12 @@ recharge, a temperature offset per member) and suite C's style (suite B's moulin
 suhmo_level_moulin_source, suhmo_level_postproc_temporal: nothing else existed before the ensemble calls, so --only handles runs on older
 trees too) and (b) through suhmo_batch_time_varying_recharge / suhmo_batch_moulin_source and suhmo_batch_postproc_temporal.
     python tools/batch_bench.py --forcing [--only both|handles|batch] [--n 1,5,16,32] [--steps 200] [--warmup 60] [--repeat 5]
+
+--run: the time loop itself.  A suite-F-style run (the valley glacier at 320 x 64 under the seasonal recharge, a temperature offset per member,
+steps of 2 h, a daily row) of `--steps` steps after `--warmup`, timed (a) as the per-call loop (time_varying_recharge + timestep per step,
+postproc_partial_all + the host function per day) and (b) as ONE call of HipBatchModel.run (suhmo_batch_run), the two in alternating runs on the
+same ensemble; wall time per step, median of `--repeat` runs each [min .. max].  A gain smaller than the spread is no gain.
+    python tools/batch_bench.py --run [--only both|loop|run] [--n 1,5,16,32] [--steps 2000] [--warmup 200] [--repeat 3]
 """
 import argparse
 import json
@@ -210,19 +216,86 @@ def forcing_table(a):
                   % (name, n, ta[0], ta[1], ta[2], tb[0], tb[1], tb[2], ta[0] / tb[0], la, lb, ra, rb), flush=True)
 
 
+def run_table(a):
+    """--run: per n, a run of a.steps steps through the per-call loop and through one call, alternating"""
+    sys.path.insert(0, os.path.join(ROOT, "tools"))
+    import run_shmip_f as rf
+    m, nx, ny, dt, per_day = dict(rf.F_MODEL), NX, NY, 7200.0, 12
+    st = sy.valley_initial_state(nx, ny, 0.05, m["lx"], m["ly"])
+    phys = dict(sy.A3_PHYS, A=2.5e-25)
+    X = (np.arange(-1, nx + 1) + 0.5)[None, :] * st["dx"] + np.zeros((ny + 2, 1))
+    zs = 100.0 * np.power(X + 200.0, 0.25) + X / 60.0 - np.power(2.0e10, 0.25) + 1.0
+    print("# suite-F-style run at %d x %d: %d steps of 2 h after %d, a daily row; (a) the per-call loop, (b) one call (HipBatchModel.run), alternating runs on one "
+          "ensemble; median of %d runs [min .. max], ms per step" % (nx, ny, a.steps, a.warmup, a.repeat))
+    print("#   n   (a) per-call loop          (b) one call               (a)/(b)   (a) - (b) [ms/step]   spread (a), (b) [ms/step]   verdict   "
+          "launches/step (a) (b)   read-backs/step (a) (b)")
+    for n in [int(x) for x in a.n.split(",")]:
+        delta = np.linspace(-6.0, 6.0, n) if n > 1 else np.zeros(1)
+        B = model.HipBatchModel(nx, ny, st["dx"], st["dy"], sy.A3_BC, phys, [m] * n, max_box=64, implicit_gap=True)
+        for k in range(n):
+            B.set_state(k, st)
+            B.member(k).level.set(lv.F_MR, np.full((ny, nx), m["G"] / m["L"]))
+            B.set_surface(k, zs)
+        tm = [180.0 * 86400.0]
+
+        def temperatures(steps):
+            t = tm[0] + dt * np.arange(steps)
+            tm[0] += dt * steps
+            return -16.0 * np.cos(2.0 * np.pi * t[:, None] / (365.0 * 24 * 60 * 60.0)) - 5.0 + delta[None, :]
+
+        def loop(steps):
+            T_K = temperatures(steps)
+            for k in range(steps):
+                B.time_varying_recharge(T_K[k], rf.BACKGROUND)
+                B.timestep(dt)
+                if (k + 1) % per_day == 0:
+                    sums = B.postproc_partial_all()
+                    for q in range(n):
+                        B.members[q].postproc_temporal_host(sums[q])
+
+        def one_call(steps):
+            B.run(steps, dt, T_K=temperatures(steps), background=rf.BACKGROUND, diag_every=per_day)
+
+        ways = [w for w in (("loop", loop), ("run", one_call)) if a.only in ("both", w[0])]
+        ways[0][1](a.warmup)
+        times, counts = {w: [] for w, _ in ways}, {}
+        for _ in range(a.repeat):
+            for w, fn in ways:
+                l0, r0 = B.get_option("batch_launches"), B.get_option("batch_readbacks")
+                B.member(0).level.synchronize()
+                t0 = time.perf_counter()
+                fn(a.steps)
+                B.member(0).level.synchronize()
+                times[w].append((time.perf_counter() - t0) / a.steps * 1e3)
+                counts[w] = ((B.get_option("batch_launches") - l0) / a.steps, (B.get_option("batch_readbacks") - r0) / a.steps)
+        B.close()
+        nan = [float("nan")]
+        ta, tb = times.get("loop", nan), times.get("run", nan)
+        ma, mb = statistics.median(ta), statistics.median(tb)
+        sa, sb = max(ta) - min(ta), max(tb) - min(tb)
+        verdict = "n/a" if ma != ma or mb != mb else "no gain" if abs(ma - mb) <= max(sa, sb) else "one call faster" if mb < ma else "one call slower"
+        ca, cb = counts.get("loop", (float("nan"),) * 2), counts.get("run", (float("nan"),) * 2)
+        print("%5d   %8.3f [%7.3f .. %7.3f]   %8.3f [%7.3f .. %7.3f]   %6.2f   %8.3f   %7.3f %7.3f   %-15s   %7.1f %7.1f   %6.2f %6.2f"
+              % (n, ma, min(ta), max(ta), mb, min(tb), max(tb), ma / mb, ma - mb, sa, sb, verdict, ca[0], cb[0], ca[1], cb[1]), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--n", default=None)
     ap.add_argument("--steps", type=int, default=None)
-    ap.add_argument("--warmup", type=int, default=60)
+    ap.add_argument("--warmup", type=int, default=None)
     ap.add_argument("--repeat", type=int, default=None)
     ap.add_argument("--bottom-solver", action="store_true")
     ap.add_argument("--suite", choices=("A", "B"), default="A")
     ap.add_argument("--forcing", action="store_true")
-    ap.add_argument("--only", choices=("both", "batch", "solo", "handles"), default="both")
+    ap.add_argument("--run", action="store_true")
+    ap.add_argument("--only", choices=("both", "batch", "solo", "handles", "loop", "run"), default="both")
     a = ap.parse_args()
-    a.n = a.n or ("1,6,16,32" if a.bottom_solver else "1,5,16,32" if a.forcing else "1,2,4,6,8,16,32")
-    a.steps, a.repeat = a.steps or (50 if a.bottom_solver else 200), a.repeat or (3 if a.bottom_solver else 5)
+    a.n = a.n or ("1,6,16,32" if a.bottom_solver else "1,5,16,32" if a.forcing or a.run else "1,2,4,6,8,16,32")
+    a.steps, a.repeat = a.steps or (50 if a.bottom_solver else 2000 if a.run else 200), a.repeat or (3 if a.bottom_solver or a.run else 5)
+    a.warmup = (200 if a.run else 60) if a.warmup is None else a.warmup
+    if a.run:
+        return run_table(a)
     if a.bottom_solver:
         return bottom_solver_table(a)
     if a.forcing:

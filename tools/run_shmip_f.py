@@ -9,7 +9,11 @@ shipped, so the spin-up is run here too.
 usage: run_shmip_f.py oracle|hip F<k> [years] [out.json] [--head-melt-coef X] [--mask-gradients 0|1] [--freeze-icefree]
                       [--mask-rhs-b 0|1] [--cutoffb 0|1] [--zs surface|thickness]      (run-state knobs of the oracle)
        run_shmip_f.py hip all [years] [out.json] [the same options]: F1-F5 as ONE ensemble (HipBatchModel): the surface height stays on the device,
-                      one recharge call per step and one diagnostic call per day serve all five; each member against its own reference table"""
+                      one recharge call per step and one diagnostic call per day serve all five; each member against its own reference table
+       run_shmip_f.py hip all ... --one-call [--recharge-columns]: the spin-up and the five years as two calls of HipBatchModel.run
+                      (suhmo_batch_run): the daily rows are finished on the device and come back once.  The tables then hold the six values of
+                      the row; --recharge-columns adds the two recharge columns (external, melt) of the per-call loop, which costs the run one
+                      call per printed day, with a postproc_partial_all at its end"""
 import json, os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -62,7 +66,37 @@ def compare(table, case):
     return cmp_
 
 
-def run_all(m, phys, st, zs, mask, nspin, nsteps, years, out_json, knobs, t0):
+def run_all_one_call(M, cases, nspin, nsteps, recharge_columns, t0):
+    """the same run through HipBatchModel.run: the spin-up in one call (the background input stays in the source field), then the seasonal
+    cycle -- in one call, or day by day where the two recharge columns are asked for.  The temperatures are evaluated here: the schedule
+    carries values"""
+    n = len(cases)
+    tot_p, tot_v = np.zeros(n, dtype=int), np.zeros(n, dtype=int)
+    if nspin:
+        p, v_, _ = M.run(nspin, 3600.0)
+        tot_p += p.sum(axis=0); tot_v += v_.sum(axis=0)
+        print("spin-up %d steps  picard %s  vcycles %s  %.0f s" % (nspin, tot_p.tolist(), tot_v.tolist(), time.time() - t0), flush=True)
+    delta = np.array([DELTA_T[c] for c in cases])
+    dt, per_day = 7200.0, 12
+    tm = dt * np.arange(nsteps)
+    T_K = -16.0 * np.cos(2.0 * np.pi * tm[:, None] / (365.0 * 24 * 60 * 60.0)) - 5.0 + delta[None, :]        # :2855, m_restart_time = 0
+    rows = [[] for _ in cases]
+    chunk = per_day if recharge_columns else nsteps
+    for k0 in range(0, nsteps, chunk):
+        k1 = min(k0 + chunk, nsteps)
+        p, v_, series = M.run(k1 - k0, dt, T_K=T_K[k0:k1], background=BACKGROUND, diag_every=per_day)
+        tot_p += p.sum(axis=0); tot_v += v_.sum(axis=0)
+        sums = M.postproc_partial_all() if recharge_columns and len(series) else None
+        for r in range(len(series)):
+            t_end = (k0 + (r + 1) * per_day) * dt
+            for q in range(n):
+                extra = [sums[q, 4, 1:].sum(), sums[q, 5, 1:].sum()] if sums is not None else []
+                rows[q].append([t_end / 3600.0, t_end / 86400.0] + list(series[r, q]) + extra)
+    print("%d steps  picard %s  vcycles %s  %.0f s" % (nsteps, tot_p.tolist(), tot_v.tolist(), time.time() - t0), flush=True)
+    return tot_p, tot_v, rows
+
+
+def run_all(m, phys, st, zs, mask, nspin, nsteps, years, out_json, knobs, t0, one_call=False, recharge_columns=False):
     """F1 ... F5 as one ensemble: the spin-up of all five (identical members: the reference spins up once and restarts five times), then the
     seasonal cycle with one suhmo_batch_time_varying_recharge per step and one suhmo_batch_postproc_partial per day"""
     from suhmo_amd import model
@@ -76,14 +110,16 @@ def run_all(m, phys, st, zs, mask, nspin, nsteps, years, out_json, knobs, t0):
         M.member(k).level.set(lv.F_MSRC, np.where(mask > 0.0, BACKGROUND, 0.0), ghosted=True)
         M.set_surface(k, zs)
     tot_p, tot_v = np.zeros(n, dtype=int), np.zeros(n, dtype=int)
-    for k in range(nspin):
+    for k in range(0 if one_call else nspin):
         p, v_ = M.timestep(3600.0); tot_p += p; tot_v += v_
         if (k + 1) % 2000 == 0:
             print("spin-up step %d  picard %s  vcycles %s  %.0f s" % (k + 1, tot_p.tolist(), tot_v.tolist(), time.time() - t0), flush=True)
     rows = [[] for _ in cases]
     delta = np.array([DELTA_T[c] for c in cases])
     tm, dt = 0.0, 7200.0
-    for k in range(nsteps):
+    if one_call:
+        tot_p, tot_v, rows = run_all_one_call(M, cases, nspin, nsteps, recharge_columns, t0)
+    for k in range(0 if one_call else nsteps):
         T_K = -16.0 * np.cos(2.0 * np.pi * tm / (365.0 * 24 * 60 * 60.0)) - 5.0 + delta        # :2855, m_restart_time = 0
         M.time_varying_recharge(T_K, BACKGROUND)
         p, v_ = M.timestep(dt); tot_p += p; tot_v += v_
@@ -95,7 +131,7 @@ def run_all(m, phys, st, zs, mask, nspin, nsteps, years, out_json, knobs, t0):
         tm += dt
         if (k + 1) % 2000 == 0:
             print("step %d  picard %s  vcycles %s  %.0f s" % (k + 1, tot_p.tolist(), tot_v.tolist(), time.time() - t0), flush=True)
-    res = dict({"which": "hip", "case": "all", "years": years, "spinup_steps": nspin}, **knobs)
+    res = dict({"which": "hip", "case": "all", "years": years, "spinup_steps": nspin, "one_call": bool(one_call)}, **knobs)
     res.update({"seconds": time.time() - t0, "launches": M.get_option("batch_launches"), "readbacks": M.get_option("batch_readbacks"), "members": {}})
     for q, c in enumerate(cases):
         table = np.array(rows[q])
@@ -116,6 +152,8 @@ def main():
     spin = opt("--spinup-steps", int)
     zs_kind = opt("--zs") or "thickness"
     freeze = opt("--freeze-icefree", flag=True)
+    one_call = opt("--one-call", flag=True)
+    recharge_columns = opt("--recharge-columns", flag=True)
     if freeze:
         os.environ["SUHMO_ORACLE_GAP_FREEZE_ICEFREE"] = "1"
     if coef is not None:
@@ -147,7 +185,8 @@ def main():
     if case == "all":
         assert which == "hip", "the ensemble is the device path's"
         knobs = {"head_melt_coef": coef, "mask_gradients": mask_grad, "mask_rhs_b": mask_rhs_b, "cutoffb": cutoffb, "zs": zs_kind, "freeze_icefree": bool(freeze)}
-        return run_all(m, phys, st, zs, mask, nspin, nsteps, years, out_json, knobs, t0)
+        return run_all(m, phys, st, zs, mask, nspin, nsteps, years, out_json, knobs, t0, one_call=one_call, recharge_columns=recharge_columns)
+    assert not one_call, "--one-call is the ensemble's (hip all)"
     if which == "oracle":
         from oracle import pyoracle as po
         M = po.OracleModel(nx, ny, st["dx"], st["dy"], sy.A3_BC, phys, m, max_box=64, nthreads=int(os.environ.get("OMP_NUM_THREADS", min(8, os.cpu_count() or 1))))
