@@ -142,7 +142,12 @@ int suhmo_level_synchronize(suhmo_level_t *L, suhmo_stream_t s);
  * box `ibox` and, if with_domain_ghosts != 0, those ghost cells of the fab that lie outside
  * the problem domain (caller-owned data for B / iceMask); interior ghost cells are never
  * copied (they duplicate a neighbour's valid cells).  get fills valid cells plus all ghost
- * cells of the fab from the canvas (= what exchange + BC would have produced). */
+ * cells of the fab from the canvas (= what exchange + BC would have produced).
+ * Caller-owned ghost data across a PERIODIC side (B, Pi, zb, iceMask, however they are set: put_box, set_field, a box of a
+ * hierarchy) must be the periodic image of the valid cells, bit for bit, as the reference's exchange leaves it.  A periodic
+ * level has one face on the wrap: the library keeps the coefficient of face 0 == face nx (ny) once, computed from the ghost
+ * on one side, and a reflux or a flux across the wrap reads it.  Ghost data that is periodic only up to rounding gives two
+ * values for that face, and results that differ from the reference's in the last bits. */
 int suhmo_level_put_box(suhmo_level_t *L, int depth, int field, int ibox, const double *fab,
                         int flo0, int flo1, int fhi0, int fhi1, int with_domain_ghosts,
                         suhmo_stream_t s);

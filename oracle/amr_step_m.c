@@ -161,6 +161,8 @@ static void mm_pwl(OrAmrMModel *S, int l, int fid)
     free(c);
     mm_ff(S, l, fid, 1);
 }
+/* the same for tests of the device's suhmo_hier_pwl_fill on its own (tests/test_gpu_hier_layouts.py) */
+void or_amrm_model_pwl_fill(OrAmrMModel *S, int l, int fid) { mm_pwl(S, l, fid); }
 /* [Chombo] CoarseAverage: covered cells of level l-1 <- average of the 4 fine cells */
 static void mm_average_down(OrAmrMModel *S, int l, int fid)
 {

@@ -145,6 +145,7 @@ def lib():
         L.or_amrm_model_gap_solver_layout.argtypes = [C.c_void_p, C.c_int, C.c_int]
         L.or_amrm_model_field.restype = dp
         L.or_amrm_model_field.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int]
+        L.or_amrm_model_pwl_fill.argtypes = [C.c_void_p, C.c_int, C.c_int]
         L.or_amrm_model_timestep.argtypes = [C.c_void_p, C.c_double, C.POINTER(C.c_int), C.POINTER(C.c_int)]
         L.or_amrm_model_moulin_source.argtypes = [C.c_void_p, C.c_int, dp, dp, dp, C.c_double, dp]
         ip = C.POINTER(C.c_int)
@@ -665,6 +666,10 @@ class OracleAmrMModel:
         for l, bl in enumerate(sts):
             for k, st in enumerate(bl):
                 self.set_state(l, k, st)
+
+    def pwl_fill(self, l, fid):
+        """ghost cells of field fid of every box of level l <- PiecewiseLinearFillPatch from level l-1, then the exchange between the boxes"""
+        lib().or_amrm_model_pwl_fill(self.h, l, fid)
 
     def moulin_source(self, positions, sigma, flux, time_factor=1.0):
         pos = np.ascontiguousarray(positions, dtype=np.float64).reshape(-1)
