@@ -123,6 +123,11 @@ int suhmo_level_num_depths(const suhmo_level_t *L);
  * the fused WFlx_level kernel and of the streaming relaxation that leave the mask out (no load, no register, no test); the results are the
  * same bits.  0: the per-cycle report of skip_mask only.  Ensembles and box unions always read the mask.  Read-only: mask_scans,
  * bcoef_unmasked_launches, relax_unmasked_launches (launches of graph replays included), mask_state (0 unknown, 1 clean, 2 dirty).
+ * bcoef_in_relax (default 1): while the mask of a whole level (no rank strip, no AMR patch) is known clean, alpha = 0, depth 0 relaxes on the
+ * streaming kernel and the pre-smoothing has at least three sweeps, the V-cycle's UpdateOperator is not a pass of its own: the first
+ * pre-smoothing launch of depth 0 forms the face coefficients from the head as it loads it and stores them (same bits), AverageOperator
+ * follows that launch.  0, or any of the conditions not met: the fused WFlx_level kernel as before.  Read-only: bcoef_in_relax_launches
+ * (graph replays included; such a launch also counts as a bcoef_unmasked_launch and a relax_unmasked_launch).
  * Not a kernel-selection knob (it changes the bits): bottom_solver (default 0: the cycle's bottom is its numBottom relaxes; 1: followed by
  * Chombo's RelaxSolver as the reference configures it, src/AmrHydro.cpp:623,628,726,733-735 -- up to 40 rounds of relax(2), ended by an l2
  * residual below 1e-6 x its first value or reduced by less than 10 %).  It reaches the level's agglomerated copy and its gap-height operator;

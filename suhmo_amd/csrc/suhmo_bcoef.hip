@@ -17,17 +17,16 @@ __device__ __forceinline__ void d_gradcc_val(const DV &v, const FP &fp, int hasM
     double c = phi[idx];
     double e = phiE(v, phi, idx, i, c, false), w = phiW(v, phi, idx, i, c, false);
     double n = phiN(v, phi, idx, j, c, false), s = phiS(v, phi, idx, j, c, false);
-    double gW = v.fdx * (c - w), gE = v.fdx * (e - c), gS = v.fdy * (c - s), gN = v.fdy * (n - c);
+    bool zW = false, zE = false, zS = false, zN = false;
     if (hasMask) {
         const double *__restrict__ m = fp.f[SUHMO_F_MASK];
         bool mc = m[idx] < 1e-6;
-        if (mc || m[idx - 1] < 1e-6) gW = 0.0;
-        if (mc || m[idx + 1] < 1e-6) gE = 0.0;
-        if (mc || m[idx - v.P] < 1e-6) gS = 0.0;
-        if (mc || m[idx + v.P] < 1e-6) gN = 0.0;
+        zW = mc || m[idx - 1] < 1e-6;
+        zE = mc || m[idx + 1] < 1e-6;
+        zS = mc || m[idx - v.P] < 1e-6;
+        zN = mc || m[idx + v.P] < 1e-6;
     }
-    gx = 0.5 * (gW + gE);
-    gy = 0.5 * (gS + gN);
+    gradcc_from(v, c, w, e, s, n, zW, zE, zS, zN, gx, gy);
 }
 __device__ __forceinline__ void d_gradcc_at(const DV &v, const FP &fp, int hasMask, int i, int j)
 {
@@ -129,9 +128,7 @@ __global__ __launch_bounds__(256) void k_gradcc_ghosts_lv(suhmo_lvboxes lv, int 
 __device__ __forceinline__ double d_re_val(const FP &fp, const suhmo_phys_t &ph, int idx)
 {
     double gx = fp.f[SUHMO_F_GRADX][idx], gy = fp.f[SUHMO_F_GRADY][idx], B = fp.f[SUHMO_F_B][idx];
-    double sg = sqrt(gx * gx + gy * gy);
-    double discr = 1.0 + 4.0 * ph.omega * (B * B * B * ph.grav * sg) / (12.0 * ph.nu * ph.nu);
-    return (-1.0 + sqrt(discr)) / (2.0 * ph.omega);
+    return re_from(ph, grad_norm(gx, gy), B);
 }
 __device__ __forceinline__ void d_re(const DV &v, const FP &fp, suhmo_phys_t ph)
 {
@@ -143,20 +140,7 @@ __device__ __forceinline__ void d_re(const DV &v, const FP &fp, suhmo_phys_t ph)
     fp.f[SUHMO_F_RE][idx] = d_re_val(fp, ph, idx);
 }
 template <class T> __global__ __launch_bounds__(256) void k_re(T t) { d_re(t.view(), t.fields(), t.phys()); }
-// step 4: CellToEdge(Re), CellToEdge(B), setup_iceMask_EC, COMPUTEBCOEFF
-// (src/AmrHydro.cpp:1512-1537, src/HydroIBC.cpp:139-184, src/AmrHydroF.ChF:212-228)
-__device__ __forceinline__ double bcoef_face(const suhmo_phys_t &ph, double Rc, double Rm, double Bc, double Bm,
-                                             double mc, double mm, bool dom_edge)
-{
-    double Ref = 0.5 * (Rc + Rm), Bf = 0.5 * (Bc + Bm);
-    double mec;
-    if (fabs(mc - mm) < 1e-10) mec = (mc > 0.0) ? 1.0 : -1.0; else mec = 0.0;
-    if (dom_edge) mec = 0.0;
-    double num_q = -(Bf * Bf * Bf * ph.grav);
-    double denom_q = 12.0 * ph.nu * (1.0 + ph.omega * Ref);
-    if (mec < 0.0 && ph.cutOffB > 0) return 0.0;
-    return num_q / denom_q;
-}
+// step 4: CellToEdge(Re), CellToEdge(B), setup_iceMask_EC, COMPUTEBCOEFF: bcoef_face (suhmo_common.h)
 __device__ __forceinline__ void d_bcoef_faces(const DV &v, const FP &fp, suhmo_phys_t ph)
 {
     int i = blockIdx.x * blockDim.x + threadIdx.x, j = blockIdx.y * blockDim.y + threadIdx.y;
@@ -286,16 +270,16 @@ __device__ __forceinline__ void bcoef_tile(const DV &v, const FP &fp, const suhm
     // cell-centred gradient of the cell at phi-tile position p (k_gradcc); (gi, gj) = its indices
     auto gradcc = [&](int p, int gi, int gj, double &gx, double &gy) {
         double c = sphi[p], w = sphi[p - 1], e = sphi[p + 1], s = sphi[p - PW], n = sphi[p + PW];
-        double gW = v.fdx * (c - w), gE = v.fdx * (e - c), gS = v.fdy * (c - s), gN = v.fdy * (n - c);
+        bool zW = false, zE = false, zS = false, zN = false;
         if (hasMask) {
             int idx = cidx(v, wrapx(gi), wrapy(gj));
             bool mc = mk[idx] < 1e-6;
-            if (mc || mk[idx - 1] < 1e-6) gW = 0.0;
-            if (mc || mk[idx + 1] < 1e-6) gE = 0.0;
-            if (mc || mk[idx - v.P] < 1e-6) gS = 0.0;
-            if (mc || mk[idx + v.P] < 1e-6) gN = 0.0;
+            zW = mc || mk[idx - 1] < 1e-6;
+            zE = mc || mk[idx + 1] < 1e-6;
+            zS = mc || mk[idx - v.P] < 1e-6;
+            zN = mc || mk[idx + v.P] < 1e-6;
         }
-        gx = 0.5 * (gW + gE); gy = 0.5 * (gS + gN);
+        gradcc_from(v, c, w, e, s, n, zW, zE, zS, zN, gx, gy);
     };
     double rer[NK];
 #pragma unroll
@@ -322,10 +306,7 @@ __device__ __forceinline__ void bcoef_tile(const DV &v, const FP &fp, const suhm
         // Re on the (ghosted) range (k_re)
         double re = 0.0;
         if (hasB[k]) {
-            double B = Br[k];
-            double sg = sqrt(gx * gx + gy * gy);
-            double discr = 1.0 + 4.0 * ph.omega * (B * B * B * ph.grav * sg) / (12.0 * ph.nu * ph.nu);
-            re = (-1.0 + sqrt(discr)) / (2.0 * ph.omega);
+            re = re_from(ph, grad_norm(gx, gy), Br[k]);
         }
         rer[k] = re;
     }

@@ -117,6 +117,42 @@ __device__ __forceinline__ double lambda_cell(const DV &v, double aterm, double 
     return lam;
 }
 
+// WFlx_level's arithmetic on values, shared by every kernel that forms face coefficients (suhmo_bcoef.hip: the four-kernel path and
+// k_bcoef_fused; suhmo_gsrb.hip: the relaxation launch that forms depth 0's faces itself).
+// Cell-centred gradient = EdgeToCell(NEWMACGRAD) (util/GradientF.ChF:57-70); z*: the face gradient is masked out (use_mask_gradients)
+__device__ __forceinline__ void gradcc_from(const DV &v, double c, double w, double e, double s, double n, bool zW, bool zE, bool zS,
+                                            bool zN, double &gx, double &gy)
+{
+    double gW = v.fdx * (c - w), gE = v.fdx * (e - c), gS = v.fdy * (c - s), gN = v.fdy * (n - c);
+    if (zW) gW = 0.0;
+    if (zE) gE = 0.0;
+    if (zS) gS = 0.0;
+    if (zN) gN = 0.0;
+    gx = 0.5 * (gW + gE);
+    gy = 0.5 * (gS + gN);
+}
+// COMPUTERE (src/AmrHydroF.ChF:92-109) in two steps: the norm of the gradient, then Re from it and the gap height
+__device__ __forceinline__ double grad_norm(double gx, double gy) { return sqrt(gx * gx + gy * gy); }
+__device__ __forceinline__ double re_from(const suhmo_phys_t &ph, double sg, double B)
+{
+    double discr = 1.0 + 4.0 * ph.omega * (B * B * B * ph.grav * sg) / (12.0 * ph.nu * ph.nu);
+    return (-1.0 + sqrt(discr)) / (2.0 * ph.omega);
+}
+// CellToEdge(Re), CellToEdge(B), setup_iceMask_EC, COMPUTEBCOEFF (src/AmrHydro.cpp:1512-1537, src/HydroIBC.cpp:139-184,
+// src/AmrHydroF.ChF:212-228): the face between cell c and the cell m below / left of it
+__device__ __forceinline__ double bcoef_face(const suhmo_phys_t &ph, double Rc, double Rm, double Bc, double Bm,
+                                             double mc, double mm, bool dom_edge)
+{
+    double Ref = 0.5 * (Rc + Rm), Bf = 0.5 * (Bc + Bm);
+    double mec;
+    if (fabs(mc - mm) < 1e-10) mec = (mc > 0.0) ? 1.0 : -1.0; else mec = 0.0;
+    if (dom_edge) mec = 0.0;
+    double num_q = -(Bf * Bf * Bf * ph.grav);
+    double denom_q = 12.0 * ph.nu * (1.0 + ph.omega * Ref);
+    if (mec < 0.0 && ph.cutOffB > 0) return 0.0;
+    return num_q / denom_q;
+}
+
 struct Depth {
     DV v;
     FP fp;
@@ -124,6 +160,7 @@ struct Depth {
     int nbox;
     int prolong_pending; // the next fused relax adds P(phi_c - phi_c,old) while loading phi (FAS prolongIncrement)
     int rhs_pending;     // the next tile relax forms the FAS right-hand side rhs = res + L(phi) while loading (and PHIOLD, LPHI)
+    int bcoef_pending;   // depth 0: the next streaming relax forms the face coefficients from phi as loaded (UpdateOperator) and stores them
     double *phi_alt;   // second phi canvas: the fused GSRB kernel writes out of place (ping-pong)
     int phi_fresh;     // strips: halo rows of phi (each rank-boundary side) that hold the neighbour's CURRENT values
 };
@@ -134,10 +171,11 @@ struct VGraph {                 // a V-cycle captured for one set of solver para
     double *p1[SUHMO_MAXDEPTH], *a1[SUHMO_MAXDEPTH];     // ... and when it ends (an odd number of out-of-place launches on a depth swaps them)
     double *rhs;                                         // right-hand-side canvas of depth 0 the cycle was captured with
     int rout_req, rout_done, rout_np; const double *rout_rhs;     // the residual its last launch was asked to leave behind (resout_req, resout_rhs) and did
+    int bcoef_in_relax; long n_bcoef_in_relax;                    // captured with the option (part of the key); its launches that form depth 0's faces
     int mask_clean; long n_bcoef_unmasked, n_relax_unmasked;      // captured with the ice mask known clean (part of the key); its launches that leave the mask out
     int has_scan;                                                 // its (masked) k_bcoef_fused also writes the scan word: a launch of it can carry a scan of the mask
 };
-struct ProfEv { hipEvent_t a, b; long cells; int restricts; };   // restricts: the launch also did the restriction (RST)
+struct ProfEv { hipEvent_t a, b; long cells; int restricts; };   // restricts: 1 the launch also did the restriction (RST), 2 it also formed the face coefficients (BCF: neither read counts it)
 
 struct suhmo_level {
     int ndepth;
@@ -181,6 +219,9 @@ struct suhmo_level {
     // resout_done: the launch did it (else the caller runs its own pass); read-only option residual_in_relax_launches counts them
     int resout_req, resout_armed, resout_done; const double *resout_rhs; long resout_count;
     int resout_np;              // resout_req bit 2: the launch also left that many partial maxima of |RES| in scratch + 2 (k_norm_final's input)
+    // UpdateOperator of the V-cycle inside the first pre-smoothing launch of depth 0 (suhmo_gsrb.hip, BCF; option bcoef_in_relax, default 1);
+    // bcoef_nd: the depths AverageOperator refreshes right behind that launch; read-only option bcoef_in_relax_launches counts them
+    int bcoef_in_relax, bcoef_nd; long bcoef_in_relax_count;
     long frhs_stream, frhs_tile;   // launches that formed a coarse depth's FAS right-hand side themselves (streaming / tile kernel); read-only options
     int prof_on;
     std::vector<ProfEv> prof;
@@ -298,6 +339,7 @@ bool suhmo_gsrb_can_fuse_prolong(suhmo_level *L, int depth, int sweeps);        
 int suhmo_level_residual_and_norm(suhmo_level *L, double *out, hipStream_t st);                   // suhmo_ops.hip
 int suhmo_level_norm_from_partials(suhmo_level *L, int np, double *out, hipStream_t st);   // suhmo_ops.hip
 bool suhmo_gsrb_can_fuse_rhs(suhmo_level *L, int depth, int sweeps, bool rhs_local = false);               // suhmo_gsrb.hip
+bool suhmo_gsrb_can_fuse_bcoef(suhmo_level *L, int sweeps);   // suhmo_gsrb.hip: the first of `sweeps` pre-smoothing sweeps of depth 0 can form the faces
 int suhmo_launch_gsrb(suhmo_level *L, int depth, int sweeps, int tail, hipStream_t st, int *restricted = nullptr);   // suhmo_gsrb.hip; tail = halo
                                                     // rows worth keeping valid at exit; restricted: see there
 void suhmo_level_drop_graphs(suhmo_level *L);                                     // suhmo_fas.hip

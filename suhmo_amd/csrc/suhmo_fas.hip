@@ -118,7 +118,12 @@ static int fas_cycle(suhmo_level *L, int dep, const suhmo_solver_params_t *sp, i
 static int vcycle_body(suhmo_level *L, const suhmo_solver_params_t *sp, int nd, suhmo_stream_t s)
 {
     int rc;
-    if (sp->bcoeff_otf) {
+    if (sp->bcoeff_otf && nd > 1 && suhmo_gsrb_can_fuse_bcoef(L, sp->num_smooth)) {
+        // UpdateOperator rides on the first pre-smoothing launch of depth 0 (suhmo_gsrb.hip, BCF), AverageOperator follows that launch.  The
+        // mask is known clean here: no report, no scan (what suhmo_level_update_operator leaves behind in that state)
+        L->d[0].bcoef_pending = 1; L->bcoef_nd = nd;
+        L->maskflag_epoch = 0; L->mask_reported = 0;
+    } else if (sp->bcoeff_otf) {
         L->faces_deferred = 1;              // rank strips: the halo rows of the depth-0 faces travel with those of the coarse depths, one message
         rc = suhmo_level_update_operator(L, 0, s);
         if (rc) { L->faces_deferred = 0; return rc; }
@@ -126,6 +131,10 @@ static int vcycle_body(suhmo_level *L, const suhmo_solver_params_t *sp, int nd, 
         if ((rc = suhmo_average_operator_all(L, nd, (hipStream_t)s))) return rc;   // AverageOperator on every depth > 0
     } else L->maskflag_epoch = 0;
     rc = fas_cycle(L, 0, sp, nd, s);
+    if (L->d[0].bcoef_pending) {            // (no launch took it up: the predicate and the launcher disagree)
+        L->d[0].bcoef_pending = 0;
+        if (!rc) { suhmo_set_error("internal: no relaxation launch formed the face coefficients"); rc = -4; }
+    }
     L->maskflag_epoch = 0;                  // the report on the ice mask (k_bcoef_fused) holds for this cycle only: the caller may load another mask
     return rc;
 }
@@ -155,6 +164,7 @@ static int vcycle_graph(suhmo_level *L, const suhmo_solver_params_t *sp, int nd,
     // (the launchers' own predicate, per depth: depth 0's answer in bit 0, the coarse depths' -- which also need coarse_mask_ok -- in bit 1)
     const int mask_clean = (suhmo_mask_clean(L, 0) ? 1 : 0) | (L->ndepth > 1 && suhmo_mask_clean(L, 1) ? 2 : 0);
     const bool scanning = sp->bcoeff_otf && suhmo_mask_would_scan(L);
+    const int bcoef_in_relax = L->bcoef_in_relax != 0;                   // selects depth 0's first pre-smoothing kernel: part of the identity too
     auto launch = [&](const VGraph &g) {
         int rc = 0;
         if (scanning && (rc = suhmo_mask_scan_begin(L, (hipStream_t)s))) return rc;
@@ -163,11 +173,11 @@ static int vcycle_graph(suhmo_level *L, const suhmo_solver_params_t *sp, int nd,
         return 0;
     };
     auto replayed = [&](const VGraph &g) {
-        L->bcoef_unmasked += g.n_bcoef_unmasked; L->relax_unmasked += g.n_relax_unmasked;
+        L->bcoef_unmasked += g.n_bcoef_unmasked; L->relax_unmasked += g.n_relax_unmasked; L->bcoef_in_relax_count += g.n_bcoef_in_relax;
         if (g.rout_done) { L->resout_done = 1; L->resout_count++; L->resout_np = g.rout_np; }
     };
     auto at_start = [&](const VGraph &g) {
-        if (memcmp(g.key, key, sizeof(key)) || g.mask_clean != mask_clean) return false;
+        if (memcmp(g.key, key, sizeof(key)) || g.mask_clean != mask_clean || g.bcoef_in_relax != bcoef_in_relax) return false;
         for (int d = 0; d < L->ndepth; d++) if (L->d[d].fp.f[SUHMO_F_PHI] != g.p0[d] || L->d[d].phi_alt != g.a0[d]) return false;
         if (g.rout_req != (L->resid_in_relax ? L->resout_req : 0) || g.rout_rhs != L->resout_rhs) return false;   // (what the last launch leaves behind)
         return L->d[0].fp.f[SUHMO_F_RHS] == g.rhs;                       // an AMR cycle runs level 0 on a second right-hand-side canvas (suhmo_hier.hip)
@@ -185,13 +195,13 @@ static int vcycle_graph(suhmo_level *L, const suhmo_solver_params_t *sp, int nd,
     for (int k = 0; k < 4; k++) if (L->vgraph_seen[k] != key[k]) { memcpy(L->vgraph_seen, key, sizeof(key)); return 0; }
     if (L->vgraphs.size() >= 16) return 0;                               // (pointer states keep changing: give up capturing)
     if (!L->gstream) HIPCHK(hipStreamCreateWithFlags(&L->gstream, hipStreamNonBlocking));
-    VGraph g; memcpy(g.key, key, sizeof(key)); g.exec = nullptr; g.mask_clean = mask_clean; g.has_scan = 0;
+    VGraph g; memcpy(g.key, key, sizeof(key)); g.exec = nullptr; g.mask_clean = mask_clean; g.has_scan = 0; g.bcoef_in_relax = bcoef_in_relax;
     for (int d = 0; d < SUHMO_MAXDEPTH; d++) { g.p0[d] = g.a0[d] = g.p1[d] = g.a1[d] = nullptr; }
     for (int d = 0; d < L->ndepth; d++) { g.p0[d] = L->d[d].fp.f[SUHMO_F_PHI]; g.a0[d] = L->d[d].phi_alt; }
     g.rhs = L->d[0].fp.f[SUHMO_F_RHS];
     g.rout_req = L->resid_in_relax ? L->resout_req : 0; g.rout_rhs = L->resout_rhs; g.rout_done = 0;
     const int rout_before = L->resout_done; const long rout_count = L->resout_count;
-    const long bcoef_unmasked = L->bcoef_unmasked, relax_unmasked = L->relax_unmasked;
+    const long bcoef_unmasked = L->bcoef_unmasked, relax_unmasked = L->relax_unmasked, bcoef_in_relax_count = L->bcoef_in_relax_count;
     HIPCHK(hipStreamSynchronize((hipStream_t)s));                        // the private stream starts from a quiescent state
     hipGraph_t graph = nullptr;
     hipError_t e = hipStreamBeginCapture(L->gstream, hipStreamCaptureModeThreadLocal);
@@ -203,15 +213,16 @@ static int vcycle_graph(suhmo_level *L, const suhmo_solver_params_t *sp, int nd,
         e = hipStreamEndCapture(L->gstream, &graph);
     }
     g.n_bcoef_unmasked = L->bcoef_unmasked - bcoef_unmasked; g.n_relax_unmasked = L->relax_unmasked - relax_unmasked;
+    g.n_bcoef_in_relax = L->bcoef_in_relax_count - bcoef_in_relax_count; L->bcoef_in_relax_count = bcoef_in_relax_count;
     L->bcoef_unmasked = bcoef_unmasked; L->relax_unmasked = relax_unmasked;
     g.rout_done = L->resout_count != rout_count;                         // (nothing was executed during capture: the flags go back)
     g.rout_np = L->resout_np;
     L->resout_done = rout_before; L->resout_count = rout_count;
     bool clean = true;                                                   // host-side state the cycle must leave behind: none pending
     for (int d = 0; d < L->ndepth; d++) {
-        clean = clean && !L->d[d].prolong_pending && !L->d[d].rhs_pending;
+        clean = clean && !L->d[d].prolong_pending && !L->d[d].rhs_pending && !L->d[d].bcoef_pending;
         g.p1[d] = L->d[d].fp.f[SUHMO_F_PHI]; g.a1[d] = L->d[d].phi_alt;
-        L->d[d].prolong_pending = 0; L->d[d].rhs_pending = 0;
+        L->d[d].prolong_pending = 0; L->d[d].rhs_pending = 0; L->d[d].bcoef_pending = 0;
         L->d[d].fp.f[SUHMO_F_PHI] = g.p0[d]; L->d[d].phi_alt = g.a0[d];  // nothing was executed during capture
     }
     if (e == hipSuccess && rc == 0 && clean && graph && hipGraphInstantiate(&g.exec, graph, nullptr, nullptr, 0) != hipSuccess) g.exec = nullptr;

@@ -349,16 +349,33 @@ __device__ __forceinline__ void copy_coef(RowCoef<MASKED> &d, const RowCoef<MASK
 // visiting order, into the coarse cell of the thread's column pair (RESTRICTRESVCNL2D + RESTRICTVCNL, VCAMR...OpF.ChF:480-561,
 // 419-449): the separate pass over phi and the 8 coefficient arrays (75 B/cell) disappears.  Costs: one more ring row, one
 // more coefficient row, one more final row above and below the chunk and two more halo columns per side.
-template <int K, bool HAS_ALPHA, int NT, int RM = 0, bool FRHS = false, bool MASKED = true>
+// BCF = true: the launch is also the V-cycle's UpdateOperator of depth 0 (WFlx_level, suhmo_bcoef.hip): it loads no bx and no by but forms
+// them from phi AS LOADED and stores them.  The half-sweeps run one step later, so that rows r, r-1, r-2 of the ring are still as loaded in
+// step r: step r forms the cell-centred gradient of row r-1 (gx from the LDS row, gy from the lane's own column in rows r and r-2), its Re,
+// the y-faces between rows r-2 and r-1 (byN of the row whose first half-sweep follows in the same step, byS of the next: computed once) and,
+// after the step's first barrier -- Re goes through an LDS row so that a lane can read Re of the cells left and right of its pair, whose B it
+// loaded with the row -- the row's x-faces.  Every value is gradcc_from / grad_norm / re_from / bcoef_face of k_bcoef_fused<.., MASKED = false>
+// on the same operands: the ghost cells beyond a physical side get the gradient 2 g1 - g2 (k_grad_ghosts; in x both belong to the boundary
+// lane's pair, in y the previous row's gradient waits in LDS) and the stored ghost B, the ghost cells of a periodic side the gradient
+// of their image and the stored ghost B.  Costs: the geometry of the restricting launch (one more ring row and coefficient row, two more
+// halo columns per side) and one more row of phi above and below a chunk; rhs, Pi and zb, which only the half-sweeps read, are loaded one
+// step later than B (registers: 247, two waves per SIMD).  Every workgroup forms the faces of its halo cells itself, so no
+// workgroup reads bx or by during the launch; owners store, the domain's last face column / row goes with the last strip / chunk.
+template <int K, bool HAS_ALPHA, int NT, int RM = 0, bool FRHS = false, bool MASKED = true, bool BCF = false>
 __global__ __launch_bounds__(NT) void k_gsrb_fused(DV v, FP fp, const double *__restrict__ pin,
                                                    double *__restrict__ pout, suhmo_phys_t ph, FusedGeom g)
 {
     // RM: what the launch does with the final rows besides storing them: 0 nothing, 1 restricts (RST), 2 stores their residual (ROUT)
     constexpr bool ROUT = RM == 2, RR = RM != 0;
     static_assert(!(FRHS && (RR || HAS_ALPHA)), "the right-hand side is formed in the plain launch of an alpha = 0 operator");
-    constexpr int LW = 2 * NT, R = 2 * K + 3 + (RR ? 1 : 0);
-    constexpr int HX = 2 * K + (RR ? 2 : 0), EY = RR ? 1 : 0;
+    static_assert(!BCF || (K == 2 && NT == 64 && RM == 0 && !FRHS && !HAS_ALPHA && !MASKED), "the faces are formed in the plain two-sweep launch of a clean-mask alpha = 0 operator");
+    constexpr bool WIDE = RR || BCF;           // one more ring row and coefficient row, two more halo columns per side
+    constexpr int DL = BCF ? 1 : 0;            // steps the half-sweeps (and the output) lag behind
+    constexpr int LW = 2 * NT, R = 2 * K + 3 + (WIDE ? 1 : 0);
+    constexpr int HX = 2 * K + (WIDE ? 2 : 0), EY = RR ? 1 : 0;
     __shared__ double lds[R * LW];
+    __shared__ double rre[BCF ? LW : 1], rsg[BCF ? LW : 1];      // BCF: Re and |grad| of the row whose faces are being formed
+    __shared__ double2 gpv[BCF ? 2 * NT : 1];                    // BCF: every lane's gradient of the row below (read at the level's y sides only: not worth registers)
 
     // XCD-aware tile order: blocks are dealt round-robin over the 8 XCDs; give every XCD a
     // contiguous range of tiles (adjacent chunks of one strip share 2K halo rows in its L2).
@@ -387,6 +404,9 @@ __global__ __launch_bounds__(NT) void k_gsrb_fused(DV v, FP fp, const double *__
     const double *__restrict__ f_Pi = fp.f[SUHMO_F_PI], *__restrict__ f_zb = fp.f[SUHMO_F_ZB];
     const double *__restrict__ f_mask = fp.f[SUHMO_F_MASK], *__restrict__ f_a = fp.f[SUHMO_F_ACOEF];
     const double *__restrict__ f_bx = fp.f[SUHMO_F_BX], *__restrict__ f_by = fp.f[SUHMO_F_BY];
+    // BCF (a whole level: no stored halo rows): phi is loaded one row further than the rows that are advanced, where the level has one
+    const int jminP = BCF ? ((g.wrap_y || jmin > 0) ? jmin - 1 : jmin) : jmin;
+    const int jmaxP = BCF ? ((g.wrap_y || jmax < v.ny - 1) ? jmax + 1 : jmax) : jmax;
 
     auto wrapj = [&](int j) { if (g.wrap_y) { if (j < 0) j += v.ny; else if (j >= v.ny) j -= v.ny; } return j; };
     auto ld2 = [&](const double *__restrict__ p, int idx) { return *reinterpret_cast<const double2 *>(p + idx); };
@@ -401,6 +421,10 @@ __global__ __launch_bounds__(NT) void k_gsrb_fused(DV v, FP fp, const double *__
     const bool ybc = !v.per[1] && (jmin <= 0 || jmax >= v.ny - 1);
     double2 pnext = make_double2(0.0, 0.0);
     double2 pprev = make_double2(0.0, 0.0);    // FRHS: this thread's pair of the row below the one whose L(phi) is formed, as loaded
+    // BCF: B of the cells left and right of the pair in rows r and r-1 (the stored ghost cell at a side of the level); Re of row r-1 and of
+    // the row below it, that row's gradient; |grad| of the ghost cell beyond a physical x side
+    double bw0 = 0.0, be0 = 0.0, bw1 = 0.0, be1 = 0.0, rn0 = 0.0, rn1 = 0.0, rep0 = 0.0, rep1 = 0.0, sgG = 0.0;
+    const bool xedge = c0 - HX <= 0 || c0 + g.W + HX >= v.nx;      // (uniform) the strip holds a lane next to a side of the level, or its image
     // the mask array is 8 of the 80 bytes a cell costs per launch and only its sign is used: when this V-cycle's UpdateOperator saw
     // no negative cell the loads are skipped (uniform); MASKED = false: the host knows already, the word is not read either
     bool usemask = false;
@@ -411,9 +435,9 @@ __global__ __launch_bounds__(NT) void k_gsrb_fused(DV v, FP fp, const double *__
     // instructions: 290.7 against 294.7 us per launch, profiles/r03_i_ring_index_ab.txt; keeping the seven offsets in rotating scalars
     // instead: fewer instructions, more spilled scalars, the same time)
     auto ring = [](int x) { return x < 0 ? x + R : x; };
-    for (int r = jmin - 1; r <= jB - 1 + 2 * K + EY; r++) {
+    for (int r = jminP - 1; r <= jB - 1 + 2 * K + EY + DL; r++) {
         // ---- 1. prefetch: phi of row r+1, coefficients of row r (both first used in step r+1)
-        bool lphi = cval && (r + 1 >= jmin) && (r + 1 <= jmax);
+        bool lphi = cval && (r + 1 >= jminP) && (r + 1 <= jmaxP);
         if (lphi) {
             const int jr = wrapj(r + 1);
             pnext = ld2(pin, cidx(v, im, jr));
@@ -427,13 +451,23 @@ __global__ __launch_bounds__(NT) void k_gsrb_fused(DV v, FP fp, const double *__
         if (lcf) {
             int idx = cidx(v, im, wrapj(r));
 #define LD2(dst, p, ix) { double2 t_ = ld2(p, ix); dst[0] = t_.x; dst[1] = t_.y; }
-            LD2(cf0.rhs, (FRHS ? g.fres : f_rhs), idx); LD2(cf0.B, f_B, idx); LD2(cf0.Pi, f_Pi, idx);
-            LD2(cf0.zb, f_zb, idx);
+            if constexpr (!BCF) { LD2(cf0.rhs, (FRHS ? g.fres : f_rhs), idx); LD2(cf0.Pi, f_Pi, idx); LD2(cf0.zb, f_zb, idx); }
+            LD2(cf0.B, f_B, idx);
             if constexpr (MASKED) { if (usemask) { LD2(cf0.mask, f_mask, idx); } else { cf0.mask[0] = 1.0; cf0.mask[1] = 1.0; } }
             if (HAS_ALPHA) LD2(cf0.a, f_a, idx);
-            LD2(cf0.byS, f_by, idx); LD2(cf0.byN, f_by, idx + v.P);
-            double2 bxp = ld2(f_bx, idx);
-            cf0.bx0 = bxp.x; cf0.bx1 = bxp.y; cf0.bx2 = f_bx[idx + 2];
+            if constexpr (BCF) { bw0 = f_B[idx - 1]; be0 = f_B[idx + 2]; }      // (the stored ghost cell at a side of the level)
+            else {
+                LD2(cf0.byS, f_by, idx); LD2(cf0.byN, f_by, idx + v.P);
+                double2 bxp = ld2(f_bx, idx);
+                cf0.bx0 = bxp.x; cf0.bx1 = bxp.y; cf0.bx2 = f_bx[idx + 2];
+            }
+        }
+        if constexpr (BCF) {
+            // what only the half-sweeps read comes a step later, with the row that is one step from its first half-sweep (registers)
+            if (cval && (r - 1 >= jmin) && (r - 1 <= jmax)) {
+                const int idx = cidx(v, im, wrapj(r - 1));
+                LD2(cf1.rhs, f_rhs, idx); LD2(cf1.Pi, f_Pi, idx); LD2(cf1.zb, f_zb, idx);
+            }
         }
         __syncthreads();                   // row r (written at the end of step r-1) is visible
 
@@ -491,9 +525,9 @@ __global__ __launch_bounds__(NT) void k_gsrb_fused(DV v, FP fp, const double *__
         // address the pair's coefficients statically instead of selecting per lane.
         auto advance_a = [&](const int m, const RowCoef<MASKED> &q, auto a_tag) {
             constexpr int a = decltype(a_tag)::value;
-            const int j = r - m;
+            const int j = r - m - DL;
             const int x = xl + a, i = im + a;
-            const int s0 = ring(sr - m), sN = ring(sr - m + 1), sS = ring(sr - m - 1);
+            const int s0 = ring(sr - m - DL), sN = ring(sr - m - DL + 1), sS = ring(sr - m - DL - 1);
             const double *row = lds + s0 * LW;
             double c = row[x];
             double w = row[(a == 0 && xl == 0) ? 0 : x - 1], e = row[(a == 1 && xl == LW - 2) ? LW - 1 : x + 1];
@@ -516,13 +550,111 @@ __global__ __launch_bounds__(NT) void k_gsrb_fused(DV v, FP fp, const double *__
             lds[s0 * LW + x] = c + (q.rhs[a] - lofphi) / denom;
         };
         auto advance = [&](const int m, const RowCoef<MASKED> &q) {
-            const int j = r - m;
+            const int j = r - m - DL;
             if (j >= jmin && j <= jmax) {                      // uniform
                 const int a = (j + v.j0 + ((m - 1) & 1)) & 1;  // uniform: colour offset of this row
                 if (a) { if (cval) advance_a(m, q, std::integral_constant<int, 1>()); }
                 else   { if (cval) advance_a(m, q, std::integral_constant<int, 0>()); }
             }
         };
+        if constexpr (BCF) {
+            // ---- 1c / 2. the faces of row r-1 (cf1), around the half-sweeps of rows r-2 .. r-5 (cf2 .. cf5)
+            const int j1 = r - 1;
+            const bool faces = j1 >= jmin && j1 <= jmax;       // uniform
+            double *__restrict__ o_bx = fp.f[SUHMO_F_BX], *__restrict__ o_by = fp.f[SUHMO_F_BY];
+            if (faces && cval) {
+                const double *row = lds + ring(sr - 1) * LW, *rowN = lds + sr * LW, *rowS = lds + ring(sr - 2) * LW;
+                const double ca = row[xl], cb = row[xl + 1];
+                double w = row[xl == 0 ? 0 : xl - 1], e = row[xl == LW - 2 ? LW - 1 : xl + 2];
+                double na = rowN[xl], nb = rowN[xl + 1], sa = rowS[xl], sb = rowS[xl + 1];      // (the lane's own cells: row r-2 is advanced below)
+                if (xbc) {                                     // phiW / phiE (.., false)
+                    if (im == 0) w = (v.bct[0][0] == 0) ? v.two_v[0][0] - ca : ca + v.neu[0][0];
+                    if (im + 1 == v.nx - 1) e = (v.bct[0][1] == 0) ? v.two_v[0][1] - cb : cb + v.neu[0][1];
+                }
+                if (ybc) {                                     // phiS / phiN (.., false)
+                    if (j1 == 0) { sa = (v.bct[1][0] == 0) ? v.two_v[1][0] - ca : ca + v.neu[1][0]; sb = (v.bct[1][0] == 0) ? v.two_v[1][0] - cb : cb + v.neu[1][0]; }
+                    if (j1 == v.ny - 1) { na = (v.bct[1][1] == 0) ? v.two_v[1][1] - ca : ca + v.neu[1][1]; nb = (v.bct[1][1] == 0) ? v.two_v[1][1] - cb : cb + v.neu[1][1]; }
+                }
+                double gx0, gy0, gx1, gy1;
+                gradcc_from(v, ca, w, cb, sa, na, false, false, false, false, gx0, gy0);
+                gradcc_from(v, cb, ca, e, sb, nb, false, false, false, false, gx1, gy1);
+                const double sg0 = grad_norm(gx0, gy0), sg1 = grad_norm(gx1, gy1);
+                rn0 = re_from(ph, sg0, cf1.B[0]); rn1 = re_from(ph, sg1, cf1.B[1]);
+                *reinterpret_cast<double2 *>(rre + xl) = make_double2(rn0, rn1);
+                if (xedge) {
+                    // the cell beyond a side of the level in x: periodic -- the gradient of its image, read from the neighbour lane below;
+                    // physical -- 2 g1 - g2 of the two cells next to the side, both this lane's
+                    if (v.per[0]) *reinterpret_cast<double2 *>(rsg + xl) = make_double2(sg0, sg1);
+                    else if (im == 0) sgG = grad_norm(2.0 * gx0 - gx1, 2.0 * gy0 - gy1);
+                    else if (im == v.nx - 2) sgG = grad_norm(2.0 * gx1 - gx0, 2.0 * gy1 - gy0);
+                }
+                cf1.byN[0] = 0.0; cf1.byN[1] = 0.0;            // (set in the next step, or below at the level's top row)
+                if (j1 > jmin) {                               // Re of the row below was formed in the previous step
+                    cf1.byS[0] = bcoef_face(ph, rn0, rep0, cf1.B[0], cf2.B[0], 1.0, 1.0, false);
+                    cf1.byS[1] = bcoef_face(ph, rn1, rep1, cf1.B[1], cf2.B[1], 1.0, 1.0, false);
+                    cf2.byN[0] = cf1.byS[0]; cf2.byN[1] = cf1.byS[1];
+                    double gxp0 = 0.0, gxp1 = 0.0, gyp0 = 0.0, gyp1 = 0.0;
+                    if ((g.wrap_y && (j1 == 0 || j1 == v.ny)) || (ybc && (j1 == 1 || j1 == v.ny - 1))) {
+                        const double2 px = gpv[t], py = gpv[NT + t];
+                        gxp0 = px.x; gxp1 = px.y; gyp0 = py.x; gyp1 = py.y;
+                    }
+                    if (g.wrap_y && (j1 == 0 || j1 == v.ny)) {
+                        // periodic seam: face 0 has the stored ghost row -1 below it, face ny the stored ghost row ny above it, each with the
+                        // gradient of its image
+                        const double2 bS = ld2(f_B, cidx(v, im, -1)), bN = ld2(f_B, cidx(v, im, v.ny));
+                        const double sp0 = grad_norm(gxp0, gyp0), sp1 = grad_norm(gxp1, gyp1);
+                        cf1.byS[0] = bcoef_face(ph, rn0, re_from(ph, sp0, bS.x), cf1.B[0], bS.x, 1.0, 1.0, false);
+                        cf1.byS[1] = bcoef_face(ph, rn1, re_from(ph, sp1, bS.y), cf1.B[1], bS.y, 1.0, 1.0, false);
+                        cf2.byN[0] = bcoef_face(ph, re_from(ph, sg0, bN.x), rep0, bN.x, cf2.B[0], 1.0, 1.0, false);
+                        cf2.byN[1] = bcoef_face(ph, re_from(ph, sg1, bN.y), rep1, bN.y, cf2.B[1], 1.0, 1.0, false);
+                        if (own && j1 == v.ny && jB == g.jend) *reinterpret_cast<double2 *>(o_by + cidx(v, i0, v.ny)) = make_double2(cf2.byN[0], cf2.byN[1]);
+                    }
+                    if (ybc && j1 == 1) {
+                        // physical bottom: face 0 of row 0 (cf2), the ghost row's gradient 2 g(0) - g(1) and its stored B
+                        const double2 bS = ld2(f_B, cidx(v, im, -1));
+                        const double rg0 = re_from(ph, grad_norm(2.0 * gxp0 - gx0, 2.0 * gyp0 - gy0), bS.x);
+                        const double rg1 = re_from(ph, grad_norm(2.0 * gxp1 - gx1, 2.0 * gyp1 - gy1), bS.y);
+                        cf2.byS[0] = bcoef_face(ph, rep0, rg0, cf2.B[0], bS.x, 1.0, 1.0, false);
+                        cf2.byS[1] = bcoef_face(ph, rep1, rg1, cf2.B[1], bS.y, 1.0, 1.0, false);
+                        if (own && jA <= 0) *reinterpret_cast<double2 *>(o_by + cidx(v, i0, 0)) = make_double2(cf2.byS[0], cf2.byS[1]);
+                    }
+                    if (ybc && j1 == v.ny - 1) {
+                        // physical top: face ny, the ghost row's gradient 2 g(ny-1) - g(ny-2) and its stored B
+                        const double2 bN = ld2(f_B, cidx(v, im, v.ny));
+                        const double rg0 = re_from(ph, grad_norm(2.0 * gx0 - gxp0, 2.0 * gy0 - gyp0), bN.x);
+                        const double rg1 = re_from(ph, grad_norm(2.0 * gx1 - gxp1, 2.0 * gy1 - gyp1), bN.y);
+                        cf1.byN[0] = bcoef_face(ph, rg0, rn0, bN.x, cf1.B[0], 1.0, 1.0, false);
+                        cf1.byN[1] = bcoef_face(ph, rg1, rn1, bN.y, cf1.B[1], 1.0, 1.0, false);
+                        if (own && jB == g.jend) *reinterpret_cast<double2 *>(o_by + cidx(v, i0, v.ny)) = make_double2(cf1.byN[0], cf1.byN[1]);
+                    }
+                    if (own && j1 >= jA && j1 < jB) *reinterpret_cast<double2 *>(o_by + cidx(v, i0, j1)) = make_double2(cf1.byS[0], cf1.byS[1]);
+                } else { cf1.byS[0] = 0.0; cf1.byS[1] = 0.0; }      // (the chunk's first loaded row: at the level's bottom set one step later, else never valid)
+                gpv[t] = make_double2(gx0, gx1); gpv[NT + t] = make_double2(gy0, gy1);
+            }
+            advance(1, cf2);
+            __syncthreads();                   // (also: Re of row r-1 is visible)
+            if (faces && cval) {
+                double reW = rre[xl == 0 ? 0 : xl - 1], reE = rre[xl == LW - 2 ? LW - 1 : xl + 2];
+                if (xedge) {
+                    if (im == 0) reW = re_from(ph, v.per[0] ? rsg[xl == 0 ? 0 : xl - 1] : sgG, bw1);
+                    if (im == v.nx - 2) reE = re_from(ph, v.per[0] ? rsg[xl == LW - 2 ? LW - 1 : xl + 2] : sgG, be1);
+                }
+                cf1.bx0 = bcoef_face(ph, rn0, reW, cf1.B[0], bw1, 1.0, 1.0, false);
+                cf1.bx1 = bcoef_face(ph, rn1, rn0, cf1.B[1], cf1.B[0], 1.0, 1.0, false);
+                cf1.bx2 = bcoef_face(ph, reE, rn1, be1, cf1.B[1], 1.0, 1.0, false);
+                if (own && j1 >= jA && j1 < jB) {
+                    const int idx = cidx(v, i0, j1);
+                    *reinterpret_cast<double2 *>(o_bx + idx) = make_double2(cf1.bx0, cf1.bx1);
+                    if (i0 == v.nx - 2) o_bx[idx + 2] = cf1.bx2;      // the level's last face column
+                }
+                rep0 = rn0; rep1 = rn1;
+            }
+            advance(2, cf3);
+            __syncthreads();
+            advance(3, cf4);
+            __syncthreads();
+            advance(4, cf5);
+        } else {
         advance(1, cf1);
         __syncthreads();
         advance(2, cf2);
@@ -531,6 +663,7 @@ __global__ __launch_bounds__(NT) void k_gsrb_fused(DV v, FP fp, const double *__
             advance(3, cf3);
             __syncthreads();
             advance(4, cf4);
+        }
         }
 
         // ---- 2b. RST: rows r-2K-2 .. r-2K are final: residual of row r-2K-1, restricted
@@ -581,9 +714,9 @@ __global__ __launch_bounds__(NT) void k_gsrb_fused(DV v, FP fp, const double *__
         }
         // ---- 3. row r-2K has all 2K half-sweeps: stream it out (own pair, written by this thread)
         {
-            const int jo = r - 2 * K;
+            const int jo = r - 2 * K - DL;
             if (own && jo >= jA && jo < jB) {
-                const int so = ring(sr - 2 * K);
+                const int so = ring(sr - 2 * K - DL);
                 double2 o = make_double2(lds[so * LW + xl], lds[so * LW + xl + 1]);
                 *reinterpret_cast<double2 *>(pout + cidx(v, i0, jo)) = o;
             }
@@ -591,11 +724,12 @@ __global__ __launch_bounds__(NT) void k_gsrb_fused(DV v, FP fp, const double *__
         // ---- 4. row r+1 enters the ring (its slot held row r-2K-2: no longer read), rotate
         sr = sr + 1 == R ? 0 : sr + 1;
         if (in_row) { lds[sr * LW + xl] = pnext.x; lds[sr * LW + xl + 1] = pnext.y; }
-        if constexpr (RR && K >= 2) copy_coef<HAS_ALPHA, MASKED>(cf5, cf4);
+        if constexpr (WIDE && K >= 2) copy_coef<HAS_ALPHA, MASKED>(cf5, cf4);
         if constexpr (K >= 2) { copy_coef<HAS_ALPHA, MASKED>(cf4, cf3); copy_coef<HAS_ALPHA, MASKED>(cf3, cf2); }
         else if constexpr (RR) copy_coef<HAS_ALPHA, MASKED>(cf3, cf2);
         copy_coef<HAS_ALPHA, MASKED>(cf2, cf1);
-        copy_coef<HAS_ALPHA, MASKED>(cf1, cf0);
+        if constexpr (BCF) { CP2(cf1, cf0, B); bw1 = bw0; be1 = be0; }      // (its faces are formed in the next step, the rest is loaded then)
+        else copy_coef<HAS_ALPHA, MASKED>(cf1, cf0);
     }
     if constexpr (ROUT) {
         if (g.onorm) {                         // (uniform) the chunk's max norm: a maximum, so the order of the lanes does not matter
@@ -630,7 +764,10 @@ static int launch_fused(suhmo_level *L, int depth, int ext_rows, hipStream_t st,
         HIPCHK(hipMemsetAsync(D.phi_alt, 0, D.elems * sizeof(double), st));
     }
     FusedGeom g;
-    constexpr int HX = 2 * K + (RR ? 2 : 0), EY = RR ? 1 : 0;
+    // (a launch that also forms depth 0's faces has the restricting launch's strips: two more halo columns per side)
+    const bool bcf = D.bcoef_pending != 0;
+    const int HX = 2 * K + ((RR || bcf) ? 2 : 0);
+    constexpr int EY = RR ? 1 : 0;
     const int maxW = 2 * NT - 2 * HX;
     g.nstrips = (v.nx + maxW - 1) / maxW;
     g.W = 2 * ((v.nx + 2 * g.nstrips - 1) / (2 * g.nstrips));
@@ -714,6 +851,18 @@ static int launch_fused(suhmo_level *L, int depth, int ext_rows, hipStream_t st,
         g.onorm = nullptr;
         if ((L->resout_req & 4) && (size_t)g.nstrips * g.nchunks + 4 < L->scratch_elems) { g.onorm = L->scratch + 2; L->resout_np = g.nstrips * g.nchunks; }
         else L->resout_np = 0;
+    }
+    if (bcf) {
+        // (suhmo_gsrb_can_fuse_bcoef said yes for exactly this launch: depth 0 of a whole level, clean mask, alpha = 0, two sweeps on one-wave
+        //  workgroups, more sweeps to follow)
+        if constexpr (K == 2 && NT == 64 && !RR) {
+            if (part || depth != 0 || !unmasked || D.rhs_pending || g.pc || v.ext[0] || v.ext[1]) { suhmo_set_error("internal: bcoef_pending on a launch that cannot form the faces"); return -4; }
+            D.bcoef_pending = 0; L->bcoef_in_relax_count++;
+            hipLaunchKernelGGL((k_gsrb_fused<2, false, 64, 0, false, false, true>), dim3(g.ntiles), dim3(NT), 0, st, v, D.fp, pin, D.phi_alt, L->ph, g);
+            L->relax_unmasked++; L->bcoef_unmasked++;         // (it is the cycle's unmasked UpdateOperator too)
+            { std::swap(D.fp.f[SUHMO_F_PHI], D.phi_alt); suhmo_fp_changed(); }
+            return 0;
+        } else { suhmo_set_error("internal: bcoef_pending on a launch that cannot form the faces"); return -4; }
     }
     if (D.rhs_pending) {
         // (suhmo_gsrb_can_fuse_rhs said yes for exactly this launch: whole level, two sweeps, one-wave workgroups, alpha = 0)
@@ -1296,6 +1445,17 @@ bool suhmo_gsrb_can_fuse_rhs(suhmo_level *L, int depth, int sweeps, bool rhs_loc
     // rank strip: R phi and RES have just arrived in all halo rows (the caller's rhs_local exchange); the launch then loads all of them
     return strip && L->ex && rhs_local && L->desc.nx_global == 0 && D.phi_fresh >= D.v.gy && D.v.gy >= 2 * K + 1 && D.v.ny >= D.v.gy;
 }
+// the first pre-smoothing launch of depth 0 can be the cycle's UpdateOperator as well (k_gsrb_fused<.., BCF>): a whole level -- no rank
+// strip, no AMR patch -- with a mask known clean and alpha = 0, whose pre-smoothing starts with the plain two-sweep launch of one-wave
+// workgroups and goes on after it (the launch that ends a smoothing restricts or leaves the residual behind)
+bool suhmo_gsrb_can_fuse_bcoef(suhmo_level *L, int sweeps)
+{
+    Depth &D = L->d[0];
+    if (!L->bcoef_in_relax || !suhmo_mask_clean(L, 0) || D.v.alpha != 0.0 || L->ex) return false;
+    if (D.v.ext[0] || D.v.ext[1] || D.v.cfx[0] || D.v.cfx[1] || D.prolong_pending || D.rhs_pending) return false;
+    const int nt = L->fused_nt ? L->fused_nt : ((long)D.v.nx * D.v.ny >= 8000000L ? 256 : 64);
+    return sweeps >= 3 && nt == 64 && pick_K(L, D, pick_variant(L, D), sweeps) == 2;
+}
 bool suhmo_gsrb_can_fuse_prolong(suhmo_level *L, int depth, int sweeps)
 {
     Depth &D = L->d[depth];
@@ -1365,6 +1525,7 @@ int suhmo_launch_gsrb(suhmo_level *L, int depth, int sweeps, int tail, hipStream
             HIPCHK(hipEventRecord(pe.a, st));
         }
         int tchunks = 1;
+        bool bcf = false;                                          // the launch also formed depth 0's face coefficients
         if (TS) {
             if (L->tile_chunks && !ext && TS == 4 && single_tile(L, D.v)) tchunks = (sweeps - it) / TS;       // e.g. the 16 bottom sweeps in one launch (1: as before)
             const bool rst = trst && it + TS * tchunks == sweeps;
@@ -1432,7 +1593,11 @@ int suhmo_launch_gsrb(suhmo_level *L, int depth, int sweeps, int tail, hipStream
                 if (rc < 0) return rc;
                 HIPCHK(hipStreamWaitEvent(st, L->xev[1], 0));              // the halo rows have arrived
                 if (rc == 1) rc = launch(0); else { rc = launch(2); L->overlapped++; }
-            } else rc = launch(0);
+            } else {
+                bcf = D.bcoef_pending != 0;
+                rc = launch(0);
+                if (!rc && bcf && D.bcoef_pending) rc = -4;
+            }
             if (rc) return rc;
             if (rst) *restricted = 1;
             if (rout) { L->resout_done = 1; L->resout_count++; }
@@ -1442,9 +1607,11 @@ int suhmo_launch_gsrb(suhmo_level *L, int depth, int sweeps, int tail, hipStream
         if (prof) {
             HIPCHK(hipEventRecord(pe.b, st));
             pe.cells = (long)D.v.nx * D.v.ny * done;
-            pe.restricts = (restricted && *restricted && it + done == sweeps) ? 1 : 0;
+            pe.restricts = bcf ? 2 : (restricted && *restricted && it + done == sweeps) ? 1 : 0;
             L->prof.push_back(pe);
         }
+        // AverageOperator reads the faces that launch has just stored: right behind it
+        if (bcf) { int rc = suhmo_average_operator_all(L, L->bcoef_nd, st); if (rc) return rc; }
         it += done;
     }
     HIPCHK(hipGetLastError());

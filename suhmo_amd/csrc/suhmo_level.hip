@@ -174,6 +174,7 @@ int suhmo_level_create_(suhmo_level_t **out, const suhmo_level_desc_t *desc, boo
     L->agg_min_cells = 100000; L->agg_depth = 0; L->agg_world = 1; L->agg_rank = 0; L->agg = nullptr; L->ag = nullptr; L->ag_user = nullptr;
     L->agg_send = L->agg_recv = nullptr; L->agg_cap = 0; L->agg_gathers = 0; L->agg_static_stale = 0;
     L->frhs_stream = L->frhs_tile = 0;
+    L->bcoef_in_relax = 1; L->bcoef_nd = 0; L->bcoef_in_relax_count = 0;
     L->resout_np = 0;
     L->resout_req = L->resout_armed = L->resout_done = 0; L->resout_rhs = nullptr; L->resout_count = 0; L->resid_in_relax = 1;
     L->graph_max_cells = 1500000; L->gstream = nullptr; L->vgraph_replays = 0; memset(L->vgraph_seen, 0, sizeof(L->vgraph_seen));
@@ -190,7 +191,7 @@ int suhmo_level_create_(suhmo_level_t **out, const suhmo_level_desc_t *desc, boo
             {"SUHMO_GSRB_VARIANT", &suhmo_level::gsrb_variant}, {"SUHMO_FUSED_HC", &suhmo_level::fused_hc}, {"SUHMO_BCOEF_FUSED", &suhmo_level::bcoef_fused},
             {"SUHMO_BCOEF_TILE_X", &suhmo_level::bcoef_tile_x}, {"SUHMO_FUSED_NT", &suhmo_level::fused_nt}, {"SUHMO_OVERLAP_HALO", &suhmo_level::overlap_halo},
             {"SUHMO_STRIPS_RHS_LOCAL", &suhmo_level::strips_rhs_local}, {"SUHMO_FAS_RHS_FUSED", &suhmo_level::fas_rhs_fused},
-            {"SUHMO_RESID_IN_RELAX", &suhmo_level::resid_in_relax}, {"SUHMO_TILE_STRIPS", &suhmo_level::tile_strips}, {"SUHMO_TILE_CHUNKS", &suhmo_level::tile_chunks},
+            {"SUHMO_RESID_IN_RELAX", &suhmo_level::resid_in_relax}, {"SUHMO_BCOEF_IN_RELAX", &suhmo_level::bcoef_in_relax}, {"SUHMO_TILE_STRIPS", &suhmo_level::tile_strips}, {"SUHMO_TILE_CHUNKS", &suhmo_level::tile_chunks},
             {"SUHMO_TILE_RESTRICT", &suhmo_level::tile_restrict}, {"SUHMO_TILE_ORDER", &suhmo_level::tile_order}, {"SUHMO_FAS_RHS_IN_RELAX", &suhmo_level::fas_rhs_in_relax},
             {"SUHMO_TILE_S", &suhmo_level::tile_s}, {"SUHMO_GSRB_TILE", &suhmo_level::gsrb_tile}, {"SUHMO_TILE_T", &suhmo_level::tile_t},
             {"SUHMO_FUSED_RESTRICT", &suhmo_level::fused_restrict}, {"SUHMO_SKIP_MASK", &suhmo_level::skip_mask}, {"SUHMO_MASK_KNOWN", &suhmo_level::mask_known},
@@ -245,7 +246,7 @@ int suhmo_level_create_(suhmo_level_t **out, const suhmo_level_desc_t *desc, boo
         D.elems = (size_t)D.v.P * (size_t)(D.v.rows + 1);
         D.nbox = L->desc.nbox;
         memset(&D.fp, 0, sizeof(D.fp));
-        D.phi_alt = nullptr; D.prolong_pending = 0; D.rhs_pending = 0; D.phi_fresh = 0;
+        D.phi_alt = nullptr; D.prolong_pending = 0; D.rhs_pending = 0; D.bcoef_pending = 0; D.phi_fresh = 0;
     }
     L->scratch = nullptr; L->scratch_elems = 0; L->hscratch = nullptr; L->hscratch_dev = nullptr; L->hseq = 0;
     L->mask_epoch = 0; L->maskflag_epoch = 0; L->mask_reported = 0; L->coarse_mask_ok = 0;
@@ -351,7 +352,7 @@ static int *option_slot_int(suhmo_level *L, const char *key)
         {"fused_nt", &suhmo_level::fused_nt}, {"fused_restrict", &suhmo_level::fused_restrict}, {"strips_rhs_local", &suhmo_level::strips_rhs_local},
         {"tile_strips", &suhmo_level::tile_strips}, {"overlap_halo", &suhmo_level::overlap_halo}, {"skip_mask", &suhmo_level::skip_mask}, {"mask_known", &suhmo_level::mask_known}, {"tile_chunks",
             &suhmo_level::tile_chunks}, {"tile_order", &suhmo_level::tile_order}, {"tile_restrict", &suhmo_level::tile_restrict}, {"fas_rhs_in_relax",
-            &suhmo_level::fas_rhs_in_relax}, {"resid_in_relax", &suhmo_level::resid_in_relax}, {"fas_rhs_fused", &suhmo_level::fas_rhs_fused},
+            &suhmo_level::fas_rhs_in_relax}, {"resid_in_relax", &suhmo_level::resid_in_relax}, {"bcoef_in_relax", &suhmo_level::bcoef_in_relax}, {"fas_rhs_fused", &suhmo_level::fas_rhs_fused},
         {"tile_s", &suhmo_level::tile_s}, {"gsrb_tile", &suhmo_level::gsrb_tile}, {"tile_t", &suhmo_level::tile_t}, {"poll_readback", &suhmo_level::poll_readback}};
     for (const auto &e : tab) if (!strcmp(key, e.k)) return &(L->*(e.m));
     return nullptr;
@@ -392,6 +393,7 @@ extern "C" int suhmo_level_get_option(const suhmo_level_t *L, const char *key, l
     if (!strcmp(key, "rhs_in_streaming_launches")) { *value = L->frhs_stream; return 0; }   // read-only counters (fas_rhs_in_relax)
     if (!strcmp(key, "rhs_in_tile_launches")) { *value = L->frhs_tile; return 0; }
     if (!strcmp(key, "residual_in_relax_launches")) { *value = L->resout_count; return 0; }
+    if (!strcmp(key, "bcoef_in_relax_launches")) { *value = L->bcoef_in_relax_count; return 0; }   // read-only counter (bcoef_in_relax)
     if (!strcmp(key, "mask_scans")) { *value = L->mask_scans; return 0; }                 // read-only counters (mask_known)
     if (!strcmp(key, "mask_state")) { *value = L->mask_state; return 0; }                 // 0 unknown, 1 clean, 2 dirty, as of the last V-cycle
     if (!strcmp(key, "bcoef_unmasked_launches")) { *value = L->bcoef_unmasked; return 0; }
