@@ -321,6 +321,32 @@ struct FusedGeom {
     double *onorm;      // ... and the chunk's max |RES| (one partial per strip x chunk: k_norm_partial's job, for k_norm_final); NULL: not asked for
 };
 
+// Cold uniform data of k_gsrb_fused<.., BCF>: what only a workgroup at a side of the level reads (the boundary types and values, the level's
+// last row).  Carried through the row loop as kernel arguments by value it costs scalar registers the loop does not have: the launch that
+// forms the faces is bound by its waves' instruction streams, and 62 spilled scalars were read back from vector lanes in every step.  So that
+// instantiation reads them from the kernel-argument segment where they are used, inside the rare branch.  FusedArgs is the argument list as it
+// lies there (every member is 8-byte aligned, as every argument is); the empty asm keeps the compiler from knowing the pointer, so the loads
+// stay in the branch instead of moving in front of the loop.  The other instantiations gain nothing from it (measured) and
+// keep the arguments by value.
+struct FusedArgs { DV v; FP fp; const double *pin; double *pout; suhmo_phys_t ph; FusedGeom g; };
+typedef const __attribute__((address_space(4))) FusedArgs *ColdArgs;
+__device__ __forceinline__ ColdArgs cold_args()
+{
+    ColdArgs k = (ColdArgs)__builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("" : "+s"(k));
+    return k;
+}
+// mixBCValues on the fly for one side (phiW / phiE / phiS / phiN, suhmo_common.h): the same expression on the same operands
+struct SideBC { int t; double two_v, neu; };
+template <bool COLD> __device__ __forceinline__ SideBC side_bc(const DV &v, const int d, const int s)
+{
+    SideBC b;
+    if constexpr (COLD) { const ColdArgs k = cold_args(); b.t = k->v.bct[d][s]; b.two_v = k->v.two_v[d][s]; b.neu = k->v.neu[d][s]; }
+    else { b.t = v.bct[d][s]; b.two_v = v.two_v[d][s]; b.neu = v.neu[d][s]; }
+    return b;
+}
+__device__ __forceinline__ double bc_ghost(const SideBC &b, double c) { return (b.t == 0) ? b.two_v - c : c + b.neu; }
+
 // MASKED = false: the level's ice mask is known clean (suhmo_common.h): the ring carries no mask, nothing loads, moves or tests it
 template <bool MASKED> struct RowMask { double mask[2]; };
 template <> struct RowMask<false> {};
@@ -441,7 +467,7 @@ __global__ __launch_bounds__(NT) void k_gsrb_fused(DV v, FP fp, const double *__
         if (lphi) {
             const int jr = wrapj(r + 1);
             pnext = ld2(pin, cidx(v, im, jr));
-            if (g.pc) {
+            if (!BCF && g.pc) {            // (never on the launch that forms the faces: launch_fused refuses it)
                 const int ic = ((jr >> 1) + g.gyc) * g.Pc + SUHMO_XOFF + (im >> 1);
                 const double corr = 1.0 * g.pc[ic] + (-1.0) * g.pco[ic];      // axby(1, -1), then PROLONGNL
                 pnext.x = pnext.x + corr; pnext.y = pnext.y + corr;
@@ -533,12 +559,13 @@ __global__ __launch_bounds__(NT) void k_gsrb_fused(DV v, FP fp, const double *__
             double w = row[(a == 0 && xl == 0) ? 0 : x - 1], e = row[(a == 1 && xl == LW - 2) ? LW - 1 : x + 1];
             double n = lds[sN * LW + x], s = lds[sS * LW + x];
             if (xbc) {                                         // mixBCValues on the fly (strip touches a BC side)
-                if (i == 0) w = (v.bct[0][0] == 0) ? v.two_v[0][0] - c : c + v.neu[0][0];
-                if (i == v.nx - 1) e = (v.bct[0][1] == 0) ? v.two_v[0][1] - c : c + v.neu[0][1];
+                const SideBC bW = side_bc<BCF>(v, 0, 0), bE = side_bc<BCF>(v, 0, 1);
+                if (i == 0) w = bc_ghost(bW, c);
+                if (i == v.nx - 1) e = bc_ghost(bE, c);
             }
-            if (ybc) {
-                if (j == 0 && !v.ext[0]) s = (v.bct[1][0] == 0) ? v.two_v[1][0] - c : c + v.neu[1][0];
-                if (j == v.ny - 1 && !v.ext[1]) n = (v.bct[1][1] == 0) ? v.two_v[1][1] - c : c + v.neu[1][1];
+            if (ybc) {                                         // (BCF: a whole level, no stored halo rows)
+                if (j == 0 && (BCF || !v.ext[0])) s = bc_ghost(side_bc<BCF>(v, 1, 0), c);
+                if (j == v.ny - 1 && (BCF || !v.ext[1])) n = bc_ghost(side_bc<BCF>(v, 1, 1), c);
             }
             double nl, dnl;
             nl_terms(ph, c, q.B[a], q.Pi[a], q.zb[a], row_mask(q, a), nl, dnl);
@@ -568,12 +595,13 @@ __global__ __launch_bounds__(NT) void k_gsrb_fused(DV v, FP fp, const double *__
                 double w = row[xl == 0 ? 0 : xl - 1], e = row[xl == LW - 2 ? LW - 1 : xl + 2];
                 double na = rowN[xl], nb = rowN[xl + 1], sa = rowS[xl], sb = rowS[xl + 1];      // (the lane's own cells: row r-2 is advanced below)
                 if (xbc) {                                     // phiW / phiE (.., false)
-                    if (im == 0) w = (v.bct[0][0] == 0) ? v.two_v[0][0] - ca : ca + v.neu[0][0];
-                    if (im + 1 == v.nx - 1) e = (v.bct[0][1] == 0) ? v.two_v[0][1] - cb : cb + v.neu[0][1];
+                    const SideBC bW = side_bc<true>(v, 0, 0), bE = side_bc<true>(v, 0, 1);
+                    if (im == 0) w = bc_ghost(bW, ca);
+                    if (im + 1 == v.nx - 1) e = bc_ghost(bE, cb);
                 }
                 if (ybc) {                                     // phiS / phiN (.., false)
-                    if (j1 == 0) { sa = (v.bct[1][0] == 0) ? v.two_v[1][0] - ca : ca + v.neu[1][0]; sb = (v.bct[1][0] == 0) ? v.two_v[1][0] - cb : cb + v.neu[1][0]; }
-                    if (j1 == v.ny - 1) { na = (v.bct[1][1] == 0) ? v.two_v[1][1] - ca : ca + v.neu[1][1]; nb = (v.bct[1][1] == 0) ? v.two_v[1][1] - cb : cb + v.neu[1][1]; }
+                    if (j1 == 0) { const SideBC bS = side_bc<true>(v, 1, 0); sa = bc_ghost(bS, ca); sb = bc_ghost(bS, cb); }
+                    if (j1 == v.ny - 1) { const SideBC bN = side_bc<true>(v, 1, 1); na = bc_ghost(bN, ca); nb = bc_ghost(bN, cb); }
                 }
                 double gx0, gy0, gx1, gy1;
                 gradcc_from(v, ca, w, cb, sa, na, false, false, false, false, gx0, gy0);
@@ -607,7 +635,7 @@ __global__ __launch_bounds__(NT) void k_gsrb_fused(DV v, FP fp, const double *__
                         cf1.byS[1] = bcoef_face(ph, rn1, re_from(ph, sp1, bS.y), cf1.B[1], bS.y, 1.0, 1.0, false);
                         cf2.byN[0] = bcoef_face(ph, re_from(ph, sg0, bN.x), rep0, bN.x, cf2.B[0], 1.0, 1.0, false);
                         cf2.byN[1] = bcoef_face(ph, re_from(ph, sg1, bN.y), rep1, bN.y, cf2.B[1], 1.0, 1.0, false);
-                        if (own && j1 == v.ny && jB == g.jend) *reinterpret_cast<double2 *>(o_by + cidx(v, i0, v.ny)) = make_double2(cf2.byN[0], cf2.byN[1]);
+                        if (own && j1 == v.ny && jB == cold_args()->g.jend) *reinterpret_cast<double2 *>(o_by + cidx(v, i0, v.ny)) = make_double2(cf2.byN[0], cf2.byN[1]);
                     }
                     if (ybc && j1 == 1) {
                         // physical bottom: face 0 of row 0 (cf2), the ghost row's gradient 2 g(0) - g(1) and its stored B
@@ -625,7 +653,7 @@ __global__ __launch_bounds__(NT) void k_gsrb_fused(DV v, FP fp, const double *__
                         const double rg1 = re_from(ph, grad_norm(2.0 * gx1 - gxp1, 2.0 * gy1 - gyp1), bN.y);
                         cf1.byN[0] = bcoef_face(ph, rg0, rn0, bN.x, cf1.B[0], 1.0, 1.0, false);
                         cf1.byN[1] = bcoef_face(ph, rg1, rn1, bN.y, cf1.B[1], 1.0, 1.0, false);
-                        if (own && jB == g.jend) *reinterpret_cast<double2 *>(o_by + cidx(v, i0, v.ny)) = make_double2(cf1.byN[0], cf1.byN[1]);
+                        if (own && jB == cold_args()->g.jend) *reinterpret_cast<double2 *>(o_by + cidx(v, i0, v.ny)) = make_double2(cf1.byN[0], cf1.byN[1]);
                     }
                     if (own && j1 >= jA && j1 < jB) *reinterpret_cast<double2 *>(o_by + cidx(v, i0, j1)) = make_double2(cf1.byS[0], cf1.byS[1]);
                 } else { cf1.byS[0] = 0.0; cf1.byS[1] = 0.0; }      // (the chunk's first loaded row: at the level's bottom set one step later, else never valid)
