@@ -509,6 +509,70 @@ int suhmo_hier_timestep(suhmo_hier_t *H, const suhmo_model_params_t *mp, double 
 int suhmo_hier_moulin_source(suhmo_hier_t *H, int n_moulins, const double *positions, const double *sigma, const double *flux,
                              double time_factor, double *integrals, suhmo_stream_t s);
 
+/* ---- GRID GENERATION: from tagged cells to the box lists suhmo_hier_create takes (suhmo_amd/csrc/suhmo_tags.hip).  The
+ * reference grids every AMR run this way: AmrHydro::initGrids (src/AmrHydro.cpp:4835-4955) and regrid (:4227-4511) tag cells by a threshold on a
+ * field (tagCellsLevel, :4539-4604) and hand the tags to BRMeshRefine with fill_ratio, block_factor, nestingRadius and max_box_size.
+ *
+ * TAGGING (device).  suhmo_hier_tag_cells accumulates into the tag map of level `level` (0 .. nlev - 1) of a hierarchy, suhmo_level_tag_cells
+ * into that of a single level handle (level 0, the first pass of initGrids).  A VALID cell of any box of the level is tagged when
+ * vmin < value && value < vmax -- both strict, so a NaN tags nothing; ghost cells are never read; cells under a finer level are tagged like
+ * the others.  field: any SUHMO_F_* the level holds (the reference's tag variables: meltingRate = SUHMO_F_MR, GapHeight = SUHMO_F_B,
+ * Pi = SUHMO_F_PI, Qx = SUHMO_F_QWX; a face field is read at the low face of the cell; a field the level does not hold yet is allocated, zero, as on any first use).  A tag grows
+ * to the square of `grow` cells around it (Chebyshev, IntVectSet::grow, tags_grow), then further by grow_x - grow / grow_y - grow in a
+ * direction whose value exceeds grow (tags_grow_dir), and is clipped to the level's domain box in BOTH directions.  DEVIATION from the
+ * reference's `&= ProblemDomain`: no periodic wrap -- a grown tag that leaves a periodic side is dropped, not carried to the other side (the
+ * nesting margins of suhmo_grids_generate do wrap).  Several calls form the union (a_tags |= local_tags); suhmo_hier_clear_tags /
+ * suhmo_level_clear_tags empty the map (level < 0: every level's).
+ * The map is kept at `granularity` g >= 1 cells of the level per entry, row-major [nby][nbx] with nbx = ceil(nx / g), nby = ceil(ny / g): an entry is
+ * 1 when any grown tag lies in it, whichever box (or none) holds its cells.  g = block_factor / 2 is the size, in this level's cells, of one
+ * block of the level to be generated.  A map in use keeps its granularity: another g before a clear is rc -1.
+ * MEMORY: ONE BYTE PER ENTRY on the device, allocated on first use, owned by the handle and freed with it: 2 x 2^l x nx0 x ny0 / g^2 bytes
+ * for level l.  The reference's run_C_3lev (256 x 256 base, block_factor 2, so g = 1) costs 64 KiB + 256 KiB (+ 1 MiB with a third refined
+ * level); cfg5 at the 4096 x 4096 north-star base with three refined levels costs 256 MiB for its finest tag level (level 2: 16384 x 16384
+ * entries at g = 1), 64 MiB and 16 MiB for the two below.  The kernels store the byte 1 with plain vector stores (every writer of an entry stores
+ * the same value).  suhmo_*_get_tags copies a map out: host may be NULL (sizes only); a level without a map reports 0 x 0.
+ * Rank strips: rc -5 (a strip's map would be a part of the level's; not built).
+ *
+ * BOX GENERATION (host; needs no device).  suhmo_grids_generate turns tag maps into box lists by Berger-Rigoutsos clustering.  Chombo's
+ * BRMeshRefine is in the un-vendored fork: the algorithm below is restated from Berger & Rigoutsos (1991), UNPINNED against the reference
+ * (SURVEY.md Appendix E).  tags[l], l = 0 .. ntag - 1: the map of level l at granularity block_factor / 2, of
+ * (nx0 << l) / g x (ny0 << l) / g entries (g must divide nx0 and ny0).  block_factor: a power of two >= 2; max_box_size: a positive
+ * multiple of block_factor; fill_ratio in (0, 1]; nesting_radius below 2 is RAISED TO 2, the margin suhmo_hier_create demands.
+ * Top-down, as BRMeshRefine::regrid with base level 0: for l = ntag - 1 down to 0, tags[l] first receives every entry touched by
+ * coarsen(grow(coarsen(box), nesting_radius)) of each box already generated on level l + 2 (inner coarsen: to cells of level l + 1, outer: to
+ * level l; a cell that leaves a periodic side wraps, one that leaves a non-periodic side is dropped), then level l + 1 is generated from it --
+ * every tagged entry is covered by a box, so the proper-nesting rule of suhmo_hier_create holds by construction.  Levels above the first
+ * level without tags are dropped.  Per level, in block units on the bounding rectangle of the tags, make(R): shrink R to the bounding box of
+ * its tags (none: return); emit R when tagged / area >= fill_ratio and both sides <= max_box_size / block_factor; else split by the first
+ * rule that applies to the signatures Sx (column sums), Sy (row sums) -- (a) a hole S = 0, per direction the one nearest the centre (tie: lower
+ * index), the longer side's first (tie: x), else the other's: [lo, i-1] + [i+1, hi]; (b) an inflection, D[i] = S[i-1] - 2 S[i] + S[i+1] for
+ * lo < i < hi, between i and i+1 where D[i] D[i+1] < 0 with strength |D[i] - D[i+1]|, per direction the strongest (ties: nearest the centre, then
+ * lower index), of the two the stronger (ties: longer side, then x): [lo, i] + [i+1, hi]; (c) bisect the longer side (tie: x) into floor(len/2)
+ * and the rest -- and recurse on the lower part first.  Boxes come in emission order: deterministic.  A box (I0, J0, I1, J1) in blocks is
+ * (I0 b, J0 b, (I1+1) b - 1, (J1+1) b - 1) in cells of level l + 1.
+ * Output as suhmo_hier_create takes it: *nlev_out = levels including level 0, nbox[0 .. *nlev_out - 1] (nbox[0] = 0; the array must hold ntag + 1
+ * ints), boxes = (lo0, lo1, hi0, hi1) one after the other, level 1 first.  rc -1: a bad parameter, ntag < 1 or > 7; rc -4: boxes_cap (in
+ * boxes) too small -- nbox[] and *nlev_out are still set and the message names the needed count, so a second call can succeed.
+ * tagSubset boxes (AmrHydro.tagSubsetBoxesFile) are not built.
+ *
+ * BOTH.  suhmo_hier_generate_grids copies out the tag maps of the levels 0, 1, ... of H that have one (up to the first without; their
+ * granularity must be block_factor / 2: rc -1; no map on level 0: rc -1) and calls the generator with the hierarchy's base size and
+ * periodicity.  *same (may be NULL) = 1 when the generated hierarchy has H's number of levels and every level holds the same SET of boxes, in
+ * any order (gridsSame, :4278-4296).  A hierarchy on rank strips: rc -5.  No fields move: carrying a state to the new grids is the caller's
+ * (initGrids loads the initial state; the regrid's interpolation is not built). */
+typedef struct suhmo_grid_params { double fill_ratio; int block_factor, max_box_size, nesting_radius; } suhmo_grid_params_t;
+int suhmo_hier_tag_cells(suhmo_hier_t *H, int level, int field, double vmin, double vmax, int grow, int grow_x, int grow_y, int granularity,
+                         suhmo_stream_t s);
+int suhmo_hier_clear_tags(suhmo_hier_t *H, int level);
+int suhmo_hier_get_tags(suhmo_hier_t *H, int level, unsigned char *host, int *nbx, int *nby);
+int suhmo_level_tag_cells(suhmo_level_t *L, int field, double vmin, double vmax, int grow, int grow_x, int grow_y, int granularity,
+                          suhmo_stream_t s);
+int suhmo_level_clear_tags(suhmo_level_t *L);
+int suhmo_level_get_tags(suhmo_level_t *L, unsigned char *host, int *nbx, int *nby);
+int suhmo_grids_generate(int nx0, int ny0, const int periodic[2], const suhmo_grid_params_t *p, int ntag, const unsigned char *const *tags,
+                         int *nlev_out, int *nbox, int *boxes, int boxes_cap);
+int suhmo_hier_generate_grids(suhmo_hier_t *H, const suhmo_grid_params_t *p, int *nlev_out, int *nbox, int *boxes, int boxes_cap, int *same);
+
 /* ---- an ENSEMBLE of N independent models on the same grid, stepped together (suhmo_amd/csrc/suhmo_batch.hip): the
  * reference's SHMIP suites are parameter sweeps on one 320 x 64 level (exec/A_SHMIP ... exec/F_SHMIP), far too small to occupy the device.  Every
  * kernel launch of a batch call serves all members that still have work and ONE read-back per V-cycle carries all their residual norms; each

@@ -65,6 +65,11 @@ class BatchRunResult(C.Structure):
                 ("rows", C.POINTER(C.c_double))]
 
 
+class GridParams(C.Structure):
+    """suhmo_grid_params_t: what the reference hands to BRMeshRefine"""
+    _fields_ = [("fill_ratio", C.c_double), ("block_factor", C.c_int), ("max_box_size", C.c_int), ("nesting_radius", C.c_int)]
+
+
 EXCHANGE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int), C.c_int, C.c_void_p)
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(C.c_double))
 REDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(C.c_double), C.c_int, C.c_int)      # values, n, op (0 MAX, 1 SUM)
@@ -99,6 +104,8 @@ SYMBOLS = [
     "suhmo_batch_set_option", "suhmo_batch_get_option", "suhmo_batch_create_opts",
     "suhmo_batch_time_varying_recharge", "suhmo_batch_moulin_source", "suhmo_batch_postproc_partial", "suhmo_batch_postproc_temporal", "suhmo_batch_postproc_table",
     "suhmo_batch_run", "suhmo_level_postproc_temporal_device",
+    "suhmo_hier_tag_cells", "suhmo_hier_clear_tags", "suhmo_hier_get_tags", "suhmo_level_tag_cells", "suhmo_level_clear_tags", "suhmo_level_get_tags",
+    "suhmo_grids_generate", "suhmo_hier_generate_grids",
 ]
 
 
@@ -249,6 +256,15 @@ def lib():
     L.suhmo_level_profile_enable.argtypes = [vp, ci]
     L.suhmo_level_profile_read.argtypes = [vp, vp, dp, C.POINTER(C.c_long), C.POINTER(C.c_long)]
     L.suhmo_level_profile_read_restricting.argtypes = [vp, vp, dp, C.POINTER(C.c_long), C.POINTER(C.c_long)]
+    ucp = C.POINTER(C.c_ubyte)
+    L.suhmo_hier_tag_cells.argtypes = [vp, ci, ci, C.c_double, C.c_double, ci, ci, ci, ci, vp]
+    L.suhmo_hier_clear_tags.argtypes = [vp, ci]
+    L.suhmo_hier_get_tags.argtypes = [vp, ci, ucp, ip, ip]
+    L.suhmo_level_tag_cells.argtypes = [vp, ci, C.c_double, C.c_double, ci, ci, ci, ci, vp]
+    L.suhmo_level_clear_tags.argtypes = [vp]
+    L.suhmo_level_get_tags.argtypes = [vp, ucp, ip, ip]
+    L.suhmo_grids_generate.argtypes = [ci, ci, ip, C.POINTER(GridParams), ci, C.POINTER(ucp), ip, ip, ip, ci]
+    L.suhmo_hier_generate_grids.argtypes = [vp, C.POINTER(GridParams), ip, ip, ip, ci, ip]
     _LIB = L
     return L
 

@@ -277,6 +277,7 @@ struct suhmo_level {
     unsigned long long *bottom_ctr; long bottom_host_iters, bottom_host_solves;
     int gsrb_tile, tile_t, tile_s;      // cache-resident depths: S sweeps per launch on LDS tiles (env SUHMO_GSRB_TILE, default 1); tile edge 16 / 32
                                 // (env SUHMO_TILE_T, 0 = by size)
+    struct suhmo_tagmap *tags;  // tag map of suhmo_level_tag_cells (suhmo_tags.hip), owned; NULL until the first call
 };
 
 enum { SUHMO_MASK_UNKNOWN = 0, SUHMO_MASK_CLEAN = 1, SUHMO_MASK_DIRTY = 2 };
@@ -305,6 +306,7 @@ static inline bool suhmo_mask_clean(const suhmo_level *L, int depth)
     return L->mask_known && !L->mask_view && L->mask_state == SUHMO_MASK_CLEAN && (depth == 0 || L->coarse_mask_ok) && L->desc.nx_global == 0;
 }
 void suhmo_set_error(const char *fmt, ...);
+void suhmo_tagmap_release(struct suhmo_tagmap *m);   // suhmo_tags.hip (NULL: nothing)
 // Named scoped timers with the reference's CH_TIME labels (src/VCAMRNonLinearPoissonOp.cpp:40,69,103,277,390,660; report =
 // CH_TIMER_REPORT, exec/A_SHMIP/Suhmo.cpp:136).  Off by default (one relaxed load per scope); suhmo_timers_enable(1): host wall
 // time per scope, (2): the device is synchronised at both ends, so the time includes the kernels the scope launched.

@@ -332,6 +332,7 @@ extern "C" int suhmo_hier_destroy(suhmo_hier_t *H)
         for (Sync *S : {&V.sy_side[0], &V.sy_side[1], &V.sy_sides, &V.sy_all, &V.sy_cread, &V.sy_win, &V.sy_fface}) S->release();
         V.avg_cov.release(); V.avg_put.release(); V.avg_get.release();
     }
+    for (suhmo_tagmap *&m : H->tags) { suhmo_tagmap_release(m); m = nullptr; }
     if (H->ps) (void)hipFree(H->ps);
     if (H->pr) (void)hipFree(H->pr);
     delete H;

@@ -183,6 +183,7 @@ struct suhmo_hier {
     // behind by the launch that ended level 0's V-cycle), coarse gradients evaluated on the cell list only
     long n_incr_residual = 0, n_fused_residual = 0, n_sparse_grad = 0;
     double *red_all = nullptr;                             // partial maxima of a norm over all levels of boxes (64 per box + 16)
+    struct suhmo_tagmap *tags[8] = {};                     // tag maps of suhmo_hier_tag_cells, one per level (suhmo_tags.hip), owned
     hier::DevVec<hier::RectEnt> cover_full;                            // coarsen(boxes of level 1) in the shadow: COVER of the whole level 0
 };
 

@@ -301,6 +301,7 @@ extern "C" int suhmo_level_destroy(suhmo_level_t *L)
     if (L->xstream) { (void)hipStreamDestroy(L->xstream); (void)hipEventDestroy(L->xev[0]); (void)hipEventDestroy(L->xev[1]); }
     if (L->scratch) (void)hipFree(L->scratch);
     if (L->bottom_ctr) (void)hipFree(L->bottom_ctr);
+    suhmo_tagmap_release(L->tags);
     if (L->mask_ev) (void)hipEventDestroy(L->mask_ev);
     if (L->hscratch) (void)hipHostFree(L->hscratch);
     delete L;

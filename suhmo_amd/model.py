@@ -19,6 +19,97 @@ def model_params(m):
                             int(m.get("head_melt_off", 0)), int(m.get("freeze_icefree_gap", 0)))
 
 
+# the reference's tag variables (AmrHydro.tag_variables, src/AmrHydro.cpp:4539-4604) under the names of HipModel.FIELDS
+TAG_VARIABLES = dict(meltingRate="mR", GapHeight="B", Pi="Pi", Qx="qwx")
+
+
+def _tag_field(fields, name):
+    if isinstance(name, int):
+        return name
+    return fields[TAG_VARIABLES.get(name, name)]
+
+
+def _tag_reach(grow, grow_dir):
+    return int(grow), int(grow_dir[0]), int(grow_dir[1])
+
+
+def _tags_out(get, *handle):
+    """the tag map behind get(*handle, host, nbx, nby) as a (nby, nbx) uint8 array; None when there is none"""
+    nbx, nby = C.c_int(), C.c_int()
+    check(get(*handle, None, C.byref(nbx), C.byref(nby)))
+    if nbx.value == 0:
+        return None
+    out = np.zeros((nby.value, nbx.value), dtype=np.uint8)
+    check(get(*handle, out.ctypes.data_as(C.POINTER(C.c_ubyte)), C.byref(nbx), C.byref(nby)))
+    return out
+
+
+def _boxes_out(nlev, nbox, flat):
+    boxes, q = [], 0
+    for l in range(1, nlev):
+        boxes.append([tuple(int(v) for v in flat[q + 4 * k:q + 4 * k + 4]) for k in range(nbox[l])])
+        q += 4 * nbox[l]
+    return boxes
+
+
+def _generate(call, ntag):
+    """run call(nlev, nbox, boxes, cap) -> rc with a box buffer that grows to the count the library reports"""
+    nlev, nbox, cap = C.c_int(), (C.c_int * (ntag + 1))(), 256
+    while True:
+        flat = (C.c_int * (4 * cap))()
+        rc = call(C.byref(nlev), nbox, flat, cap)
+        if rc == -4 and sum(nbox) > cap:
+            cap = sum(nbox)
+            continue
+        check(rc)
+        return _boxes_out(nlev.value, list(nbox), list(flat))
+
+
+def generate_grids(nx0, ny0, periodic, tags, fill_ratio, block_factor, max_box_size, nesting_radius=2):
+    """suhmo_grids_generate, the host part alone (no device): tags[l] = the (ny0 << l) / g x (nx0 << l) / g map of level l at granularity
+    g = block_factor / 2 -> boxes[l - 1] = list of (lo0, lo1, hi0, hi1) in the index space of level l, as HipHierModel takes them"""
+    g = int(block_factor) // 2
+    maps = []
+    for l, t in enumerate(tags):
+        a = np.ascontiguousarray(t, dtype=np.uint8)
+        if g < 1 or a.shape != ((ny0 << l) // g, (nx0 << l) // g):
+            raise ValueError("tags[%d] has shape %s, level %d at block_factor %d needs %s" % (l, a.shape, l, block_factor, ((ny0 << l) // max(g, 1), (nx0 << l) // max(g, 1))))
+        maps.append(a)
+    ucp = C.POINTER(C.c_ubyte)
+    ptr = (ucp * max(len(maps), 1))(*[a.ctypes.data_as(ucp) for a in maps])
+    per = (C.c_int * 2)(int(periodic[0]), int(periodic[1]))
+    gp = capi.GridParams(float(fill_ratio), int(block_factor), int(max_box_size), int(nesting_radius))
+    return _generate(lambda nlev, nbox, flat, cap: capi.lib().suhmo_grids_generate(int(nx0), int(ny0), per, C.byref(gp), len(maps), ptr, nlev, nbox, flat, cap),
+                     len(maps))
+
+
+def initial_grids(make_model, tag_specs, params, max_level):
+    """The loop of AmrHydro::initGrids (src/AmrHydro.cpp:4835-4955): make_model(boxes) creates a model on the boxes so far and loads its
+    initial state -- boxes = [] first: level 0 alone, a HipModel or a HipHierModel without boxes -- every level is tagged with tag_specs
+    (dicts of tag_cells' arguments: name, vmin, vmax, grow, grow_dir), grids are generated with params (generate_grids' keywords), and the
+    loop repeats while a new level appeared and max_level is not reached.  Returns (boxes, the model on them); the models in between are closed."""
+    g = int(params["block_factor"]) // 2
+    boxes = []
+    m = make_model(boxes)
+    while len(boxes) < max_level:
+        if isinstance(m, HipModel):
+            for sp in tag_specs:
+                m.tag_cells(granularity=g, **sp)
+            new = generate_grids(m.nx, m.ny, m.level._desc.bc.periodic, [m.tags()], **params)
+        else:
+            for l in range(len(boxes) + 1):
+                for sp in tag_specs:
+                    m.tag_cells(l, granularity=g, **sp)
+            new, _ = m.generate_grids(**params)
+        new = new[:max_level]
+        if len(new) <= len(boxes):
+            break
+        m.close()
+        boxes = new
+        m = make_model(boxes)
+    return boxes, m
+
+
 class HipModel:
     FIELDS = dict(head=lv.F_PHI, B=lv.F_B, Pi=lv.F_PI, zb=lv.F_ZB, mask=lv.F_MASK, mR=lv.F_MR, Pw=lv.F_PW,
                   qwx=lv.F_QWX, qwy=lv.F_QWY, cd=lv.F_CD, rhs_h=lv.F_RHS, Re=lv.F_RE, msrc=lv.F_MSRC)
@@ -55,6 +146,19 @@ class HipModel:
         """suhmo.time_varying_input (src/AmrHydro.cpp:2849-2861): F_MSRC from the ghosted ice surface height zs"""
         self.level.set(lv.F_ZS, zs, ghosted=True)
         check(capi.lib().suhmo_level_time_varying_recharge(self.level.h, float(T_K), float(background), self.level.stream))
+
+    def tag_cells(self, name, vmin, vmax, grow=0, grow_dir=(0, 0), granularity=1):
+        """tagCellsLevel on this level (suhmo_level_tag_cells): cells with vmin < name < vmax, grown by `grow` cells (and to grow_dir in a
+        direction where that is more), join the level's tag map, kept at `granularity` cells per entry"""
+        check(capi.lib().suhmo_level_tag_cells(self.level.h, _tag_field(self.FIELDS, name), float(vmin), float(vmax), *_tag_reach(grow, grow_dir),
+                                               int(granularity), self.level.stream))
+
+    def clear_tags(self):
+        check(capi.lib().suhmo_level_clear_tags(self.level.h))
+
+    def tags(self):
+        """the tag map, (nby, nbx) uint8; None before the first tag_cells and after clear_tags"""
+        return _tags_out(capi.lib().suhmo_level_get_tags, self.level.h)
 
     def timestep(self, dt):
         self.cur_step += 1                                         # src/AmrHydro.cpp:2259
@@ -420,6 +524,29 @@ class HipHierModel:
         dp = lambda a: a.ctypes.data_as(C.POINTER(C.c_double))
         check(capi.lib().suhmo_hier_moulin_source(self.hier.h, sg.size, dp(pos), dp(sg), dp(fl), float(time_factor), dp(integ), self.hier.stream))
         return integ
+
+    def tag_cells(self, level, name, vmin, vmax, grow=0, grow_dir=(0, 0), granularity=1):
+        """tagCellsLevel on every box of `level` (suhmo_hier_tag_cells) into the level's tag map; granularity = block_factor / 2 of the
+        generate_grids call that is to read it"""
+        check(capi.lib().suhmo_hier_tag_cells(self.hier.h, int(level), _tag_field(self.FIELDS, name), float(vmin), float(vmax),
+                                              *_tag_reach(grow, grow_dir), int(granularity), self.hier.stream))
+
+    def clear_tags(self, level=-1):
+        """empty the tag map of `level` (default: of every level)"""
+        check(capi.lib().suhmo_hier_clear_tags(self.hier.h, int(level)))
+
+    def tags(self, level):
+        """the tag map of `level`, (nby, nbx) uint8; None where there is none"""
+        return _tags_out(capi.lib().suhmo_hier_get_tags, self.hier.h, int(level))
+
+    def generate_grids(self, fill_ratio, block_factor, max_box_size, nesting_radius=2):
+        """suhmo_hier_generate_grids: box lists from the tag maps of the levels 0, 1, ... that have one -> (boxes, same); boxes in the form the
+        constructor takes, same: they are this hierarchy's own, level by level, in any order (the reference's gridsSame)"""
+        gp = capi.GridParams(float(fill_ratio), int(block_factor), int(max_box_size), int(nesting_radius))
+        same = C.c_int()
+        boxes = _generate(lambda nlev, nbox, flat, cap: capi.lib().suhmo_hier_generate_grids(self.hier.h, C.byref(gp), nlev, nbox, flat, cap, C.byref(same)),
+                          self.hier.nlev)
+        return boxes, bool(same.value)
 
     def get(self, l, k, name, ghosted=False):
         """a field of box k of level l; None where another rank owns the box (levels dealt to the ranks: hier.owns(l, k))"""

@@ -5,7 +5,9 @@ run goes its main.maxStep steps with the ramp, then the post-processing restart 
 files compared are plot003200 for 1lev-5lev, plot001600 for 6lev, plot001100 for 7lev, CONV_ANA/scripts/launch_comparaison.py).
 L2 self-convergence errors between successive resolutions as ChomboCompare computes them; the reference's table is
 exec/0_convergence_channelized/CONV_ANA/results/convergence_data_singleLevel.dat.
-usage: convergence_channelized.py [max_level 2..7]"""
+usage: convergence_channelized.py [max_level 2..7]
+       convergence_channelized.py --generated-grids [--oracle] [--steps n] [base cells ...]: the grids of the {k}lev_base / {k}lev_base2levs runs made by
+       tagging the melt rate with the run's own settings (suhmo_grids_generate), next to the rectangles inferred from the reference's tables"""
 import os
 import sys
 import time
@@ -166,6 +168,87 @@ def amr_moulin_error(nx0, rects, which="oracle"):
     return float(np.sqrt(tot))
 
 
+def grid_inputs():
+    """what each {k}lev_base / {k}lev_base2levs run gives tagCellsLevel and BRMeshRefine (copied from its input.hydro)"""
+    import json
+    return json.load(open(os.path.join(ROOT, "tests", "golden", "convergence_channelized_grid_inputs.json")))
+
+
+def host_tags(v, vmin, vmax, grow, g):
+    """tagCellsLevel on a host array (the oracle's melt rate): suhmo_level_tag_cells' rule -- strict bounds, a square of `grow` cells, clipped"""
+    ny, nx = v.shape
+    t = np.zeros((-(-ny // g), -(-nx // g)), dtype=np.uint8)
+    for j, i in zip(*np.nonzero((vmin < v) & (v < vmax))):
+        t[max(j - grow, 0) // g:min(j + grow, ny - 1) // g + 1, max(i - grow, 0) // g:min(i + grow, nx - 1) // g + 1] = 1
+    return t
+
+
+def generated_grids(klev, amr_levels, which="hip", steps=None):
+    """The grids of {klev}lev_base (amr_levels = 1) / {klev}lev_base2levs (2) made the reference's way: the model runs through the ramp
+    (`steps`, default the run's main steps: the AMR runs restart from that checkpoint), the melt rate is tagged with the run's own
+    tagging_values / tags_grow and suhmo_grids_generate gets its fill_ratio, block_factor, max_box_size and nestingRadius.  Device: the loop of
+    initGrids (model.initial_grids), a level per pass, every pass a run from the basic state on the grids so far.  Oracle: the single
+    level on the CPU, tagged on the host -- the first refined level only.  Returns boxes[l - 1] in the index space of level l."""
+    inp = grid_inputs()["%dlev_base%s" % (klev, "2levs" if amr_levels == 2 else "")]
+    nx0, ny0 = inp["num_cells"]
+    assert nx0 == 32 << (klev - 1) and inp["max_level"] == amr_levels
+    steps = STEPS[klev][0] if steps is None else steps
+    params = dict(fill_ratio=inp["fill_ratio"], block_factor=inp["block_factor"], max_box_size=inp["max_box_size"], nesting_radius=inp["nestingRadius"])
+    specs = [dict(name=nm, vmin=lo, vmax=hi, grow=inp["tags_grow"]) for nm, lo, hi in zip(inp["tag_variables"], inp["tagging_values_min"], inp["tagging_values_max"])]
+    from suhmo_amd import model
+    m = dict(MODEL)
+    if which == "oracle":
+        from oracle import pyoracle as po
+        import ctypes as C
+        st = basic_state(nx0, ny0)
+        M = po.OracleModel(nx0, ny0, st["dx"], st["dy"], BC, PHYS, m, max_box=min(64, ny0), nthreads=min(8, os.cpu_count() or 1))
+        M.set_state(st)
+        M.field(po.OM_MR)[:] = m["G"] / m["L"]
+        src, _ = po.moulin_source(nx0, ny0, st["dx"], st["dy"], MOULIN[0], MOULIN[1], MOULIN[2], 1.0)
+        M.field(po.OM_MSRC)[1:-1, 1:-1] = src
+        for k in range(steps):
+            M._mp.ramp = float(ramp(k * m["dt"]))
+            po.lib().or_model_set_ramp(M.h, C.c_double(M._mp.ramp))
+            M.timestep(m["dt"])
+        mr = np.array(M.field(po.OM_MR))[1:-1, 1:-1]
+        M.close()
+        assert specs[0]["name"] == "meltingRate" and len(specs) == 1
+        t = host_tags(mr, specs[0]["vmin"], specs[0]["vmax"], specs[0]["grow"], params["block_factor"] // 2)
+        return model.generate_grids(nx0, ny0, BC["periodic"], [t], **params), float(mr.max())
+
+    def make_model(boxes):
+        if not boxes:
+            H = model.HipModel(nx0, ny0, LX / nx0, LY / ny0, BC, PHYS, m, max_box=min(64, ny0))
+            H.set_state(basic_state(nx0, ny0))
+            H.level.set(model.lv.F_MR, np.full((ny0, nx0), m["G"] / m["L"]))
+        else:
+            H = model.HipHierModel(nx0, ny0, LX / nx0, LY / ny0, BC, PHYS, m, boxes, max_box=min(64, ny0))
+            for l, bl in enumerate([[(0, 0, nx0 - 1, ny0 - 1)]] + boxes):
+                full = basic_state(nx0 << l, ny0 << l)
+                for k, (lo0, lo1, hi0, hi1) in enumerate(bl):
+                    H.set_state(l, k, {key: (np.ascontiguousarray(v[lo1:hi1 + 3, lo0:hi0 + 3]) if isinstance(v, np.ndarray) else v) for key, v in full.items()})
+                    H.level[l][k].set(model.lv.F_MR, np.full((hi1 - lo1 + 1, hi0 - lo0 + 1), m["G"] / m["L"]))
+        H.moulin_source(*MOULIN, 1.0)
+        for k in range(steps):
+            H._mp.ramp = float(ramp(k * m["dt"]))
+            H.timestep(m["dt"])
+        return H
+
+    boxes, H = model.initial_grids(make_model, specs, params, max_level=amr_levels)
+    mx = float(max(H.get("mR").max(), 0.0)) if isinstance(H, model.HipModel) else float(H.get(0, 0, "mR").max())
+    H.close()
+    return boxes, mx
+
+
+def union_metres(nx0, boxes):
+    """per refined level the bounding rectangle of its boxes in metres, (x0, x1, y0, y1) as the golden table has it, and the box count"""
+    out = []
+    for l, bl in enumerate(boxes, start=1):
+        dx = LX / (nx0 << l)
+        out.append(([min(b[0] for b in bl) * dx, (max(b[2] for b in bl) + 1) * dx, min(b[1] for b in bl) * dx, (max(b[3] for b in bl) + 1) * dx], len(bl)))
+    return out
+
+
 def amr_run(nx0, rects, main_steps=3000, total_steps=7200):
     """{k}lev_base / {k}lev_base2levs on the device with the inferred (fixed) grids: the reference restarts the AMR run from the
     single-level checkpoint after the ramp (3000 steps) and regrids every 250 steps; here the hierarchy exists from the start --
@@ -239,6 +322,28 @@ def table(max_level=7, log=None, which="hip", phys=None):
 
 if __name__ == "__main__":
     args = sys.argv[1:]
+    if "--generated-grids" in args:                     # convergence_channelized.py --generated-grids [--oracle] [--steps n] [base cells ...]
+        args.remove("--generated-grids")
+        which = "hip"
+        if "--oracle" in args:
+            which = "oracle"; args.remove("--oracle")
+        steps = None
+        if "--steps" in args:
+            k = args.index("--steps"); steps = int(args[k + 1]); del args[k:k + 2]
+        golden = amr_grids()
+        for case in (args or ["32"]):
+            klev = int(np.log2(int(case) // 32)) + 1
+            for amr_levels, name in ((1, "2Levels"), (2, "3Levels")):
+                if which == "oracle" and amr_levels == 2:
+                    continue
+                t0 = time.time()
+                boxes, mx = generated_grids(klev, amr_levels, which, steps)
+                print("%s base %s (%s, max melt rate %.4g): generated %s   [%.0f s]" % (name, case, which, mx, boxes, time.time() - t0))
+                for l, (rect, n) in enumerate(union_metres(int(case), boxes), start=1):
+                    ref = golden.get(name, {}).get(case)
+                    print("   level %d: union %s m in %d boxes; inferred from the reference's table: %s" % (l, [round(v, 4) for v in rect], n,
+                          ref[l - 1] if ref and l <= len(ref) else "none"), flush=True)
+        sys.exit(0)
     if args and args[0] == "amr":                       # convergence_channelized.py amr [2Levels|3Levels] [case ...]
         name = args[1] if len(args) > 1 else "2Levels"
         grids = amr_grids()[name]

@@ -1,13 +1,51 @@
 #!/usr/bin/env python3
 """cfg5 (exec/AMR_multiMoulins physics) time step on base + 3 AMR levels of box unions: ms per step.
-    python tools/hier_bench.py [base cells per side] [steps]"""
+    python tools/hier_bench.py [--generated-grids] [base cells per side] [steps]
+--generated-grids: the hierarchy is made the reference's way instead of synthetic.boxes_around -- a level per pass of the initGrids loop, by tagging
+the moulin source term on the device (suhmo_hier_tag_cells) and clustering the tags (suhmo_grids_generate) with run_C_3lev's fill_ratio,
+block_factor, max_box_size, nestingRadius and tags_grow; the time of tagging, copy-out and generation is reported per level."""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from suhmo_amd import model, synthetic as sy
-nb = int(sys.argv[1]) if len(sys.argv) > 1 else 256
-nstep = int(sys.argv[2]) if len(sys.argv) > 2 else 10
+generated = "--generated-grids" in sys.argv
+argv = [a for a in sys.argv[1:] if a != "--generated-grids"]
+nb = int(argv[0]) if len(argv) > 0 else 256
+nstep = int(argv[1]) if len(argv) > 1 else 10
 bc, ph, mm, mo = sy.multimoulins_setup()
-boxes = sy.boxes_around(mo["positions"], nb, nb, 4, 1.0e5, 1.0e5)
+
+
+def generated_boxes():
+    """three passes of the initGrids loop.  Tagged: the moulin source term above a fraction of its peak on level 0 that rises with the level
+    (0.01, 0.1, 0.5: the refined region narrows level by level, as boxes_around's radii do), buffered by tags_grow = 4; exec/AMR_multiMoulins/
+    run_C_3lev/input.hydro:67-76 for the rest"""
+    params = dict(fill_ratio=0.5, block_factor=2, max_box_size=64, nesting_radius=4)
+    boxes = []
+    for _ in range(3):
+        M = model.HipHierModel(nb, nb, 1.0e5 / nb, 1.0e5 / nb, bc, ph, mm, boxes, max_box=64)
+        M.moulin_source(**mo)
+        peak = float(M.get(0, 0, "msrc").max())
+        maps = []
+        for l in range(len(boxes) + 1):
+            M.level[0][0].synchronize()
+            t0 = time.perf_counter()
+            M.tag_cells(l, "msrc", (0.01, 0.1, 0.5)[l] * peak, 1.0e300, grow=4, granularity=params["block_factor"] // 2)
+            M.level[0][0].synchronize()
+            t1 = time.perf_counter()
+            maps.append(M.tags(l))
+            t2 = time.perf_counter()
+            print("  pass %d level %d: tagging %.3f ms, copy-out of %d x %d entries %.3f ms, %d entries set" % (len(boxes) + 1, l, 1e3 * (t1 - t0),
+                  maps[-1].shape[1], maps[-1].shape[0], 1e3 * (t2 - t1), int(maps[-1].sum())), flush=True)
+        t0 = time.perf_counter()
+        new = model.generate_grids(nb, nb, bc["periodic"], maps, **params)
+        print("  pass %d: generation of %d levels %.3f ms, boxes per level %s" % (len(boxes) + 1, len(new), 1e3 * (time.perf_counter() - t0), [len(b) for b in new]), flush=True)
+        M.close()
+        if len(new) <= len(boxes):
+            break
+        boxes = new
+    return boxes
+
+
+boxes = generated_boxes() if generated else sy.boxes_around(mo["positions"], nb, nb, 4, 1.0e5, 1.0e5)
 sts = sy.mountain_amrm_states(nb, nb, boxes)
 t0 = time.perf_counter()
 H = model.HipHierModel(nb, nb, sts[0][0]["dx"], sts[0][0]["dy"], bc, ph, mm, boxes, max_box=64)
