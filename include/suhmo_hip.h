@@ -558,8 +558,8 @@ int suhmo_hier_moulin_source(suhmo_hier_t *H, int n_moulins, const double *posit
  * BOTH.  suhmo_hier_generate_grids copies out the tag maps of the levels 0, 1, ... of H that have one (up to the first without; their
  * granularity must be block_factor / 2: rc -1; no map on level 0: rc -1) and calls the generator with the hierarchy's base size and
  * periodicity.  *same (may be NULL) = 1 when the generated hierarchy has H's number of levels and every level holds the same SET of boxes, in
- * any order (gridsSame, :4278-4296).  A hierarchy on rank strips: rc -5.  No fields move: carrying a state to the new grids is the caller's
- * (initGrids loads the initial state; the regrid's interpolation is not built). */
+ * any order (gridsSame, :4278-4296).  A hierarchy on rank strips: rc -5.  No fields move here: suhmo_hier_regrid (below) carries a state to
+ * the new grids; initGrids loads the initial state instead. */
 typedef struct suhmo_grid_params { double fill_ratio; int block_factor, max_box_size, nesting_radius; } suhmo_grid_params_t;
 int suhmo_hier_tag_cells(suhmo_hier_t *H, int level, int field, double vmin, double vmax, int grow, int grow_x, int grow_y, int granularity,
                          suhmo_stream_t s);
@@ -572,6 +572,59 @@ int suhmo_level_get_tags(suhmo_level_t *L, unsigned char *host, int *nbx, int *n
 int suhmo_grids_generate(int nx0, int ny0, const int periodic[2], const suhmo_grid_params_t *p, int ntag, const unsigned char *const *tags,
                          int *nlev_out, int *nbox, int *boxes, int boxes_cap);
 int suhmo_hier_generate_grids(suhmo_hier_t *H, const suhmo_grid_params_t *p, int *nlev_out, int *nbox, int *boxes, int boxes_cap, int *same);
+
+/* ---- REGRID: FIELD TRANSFER (suhmo_amd/csrc/suhmo_regrid.hip; tests/regrid_ref.py is the numpy twin of this text).
+ * The third step of AmrHydro::regrid (src/AmrHydro.cpp:4227-4511) after tagging and clustering: destructiveRegrid (:4176-4223) for refinement
+ * ratio 2.  Level 0 is the domain and never changes (m_regrid_lbase = 0, the only value the reference ships): its fields are carried over
+ * unchanged.  Per level l = 1 .. new finest, ASCENDING, so that level l reads the NEW level l - 1 with all its steps done, and per field:
+ *  a. INTERPOLATE every valid cell of every new box of level l from level l - 1 -- FineInterp::interpToFine with m_boundary_limit_type = 3,
+ *     limitTangentialOnly.  For the coarse cell (I, J) under the fine cells (2I + p, 2J + q), p, q in {0, 1}, c(a, b) the coarse value at
+ *     (I + a, J + b), c0 = c(0, 0):
+ *       neighbours  (I + a, J + b) EXISTS if it lies in the coarse domain after the wrap through a periodic side; proper nesting makes every
+ *                   existing neighbour a valid cell of level l - 1.
+ *       slopes      s[d] as oracle/amr_step.c:or_pwl_fill and k_pwl compute them: central 0.5 * (c(+1) - c(-1)) when both neighbours in
+ *                   direction d exist, c(+1) - c0 when the low one does not, c0 - c(-1) when the high one does not (neither: 0).
+ *       limiter     FORT_INTERPLIMIT, or_pwl_fill's arithmetic: smax, smin over the existing cells of the 3 x 3 block (c0 included);
+ *                   deltasum = 0.5 * (|s0| + |s1|); where deltasum > 0: etamax = (smax - c0) / deltasum, etamin = (c0 - smin) / deltasum,
+ *                   eta = max(min(min(etamin, etamax), 1), 0).
+ *       where       a cell with all eight neighbours: both slopes times eta.  A cell that lacks a neighbour in the directions N != {} (next to
+ *                   a non-periodic domain side): eta on the slopes of the directions NOT in N only; the one-sided normal slopes stay as
+ *                   computed (at a domain corner, N = both: nothing is limited).  eta itself is the value above, normal slope included in
+ *                   deltasum: a tangential slope larger than half the normal range is still cut.
+ *       value       v = c0; v = v + s0 * (p ? 0.25 : -0.25); v = v + s1 * (q ? 0.25 : -0.25) -- this order, separate statements, no
+ *                   contraction, as k_pwl is written.
+ *     [Chombo] FineInterp.cpp is in the un-vendored fork.  Away from the domain sides the arithmetic is exactly or_pwl_fill's, which the test
+ *     oracle pins; the BOUNDARY CLAUSE ("where", and one-sided slopes that escape the limiter) is restated from the documented meaning of
+ *     limitTangentialOnly and is UNPINNED against the reference, as BRMeshRefine is.
+ *  b. COARSE-FINE GHOST CELLS of the new boxes: PiecewiseLinearFillPatch from the new level l - 1 (suhmo_hier_pwl_fill: corners included, no
+ *     periodic images in its stencil, both slopes limited).
+ *  c. COPY: every valid cell of a new box that is a valid cell of some old box of level l gets the old value, bit for bit
+ *     (a_oldData->copyTo(*newData)); the copy wins over (a).  Only old VALID cells are read, never an old ghost cell.  A level the old
+ *     hierarchy does not have contributes nothing; a level the new one does not have is dropped (:4462-4467).
+ *  d. EXCHANGE between the new boxes, corners included (suhmo_hier_exchange).
+ *  e. DOMAIN GHOST CELLS across a non-periodic side, side cells only, by the rule the reference's regrid applies to the field and with the
+ *     launches of the time step: CopyGhostCells (ghost = the cell next to it) for SUHMO_F_ZB and SUHMO_F_MASK (:4419, :4436) and for
+ *     SUHMO_F_B (the time step's own ghost fill of b); ExtrapGhostCells (ghost = 2 x the cell next to it - the one behind) for SUHMO_F_PI,
+ *     SUHMO_F_ZS, SUHMO_F_MR, SUHMO_F_PW (:4379-4383, :4420-4421); the head's are the solver's business and every other field's are left as
+ *     created (0).  Ghost cells diagonal to a domain corner are written by nobody.
+ *
+ * suhmo_hier_regrid(H, nlev, nbox, boxes, nfields, fields, out, s): nlev / nbox / boxes exactly as suhmo_hier_create takes them, so the output of
+ * suhmo_hier_generate_grids passes straight in.  fields: nfields (<= 16) ids of cell-centred fields (a face field, SUHMO_F_COVER or
+ * SUHMO_F_PHI2: rc -1); NULL = the reference's list (:4363-4376) restricted to what is held as arrays here: PHI, B, PI, ZB, MASK, MR, PW, ZS.
+ * A field a level does not hold yet is allocated, zero, as on any first use.  Every other field of the levels >= 1 starts as in a freshly
+ * created hierarchy (the reference allocates m_old_head, m_Re, m_qw, the moulin source term and the gradients anew); the next
+ * suhmo_hier_moulin_source / suhmo_hier_timestep recomputes them.  The new hierarchy gets the base descriptor, the options and the all-gather
+ * callback of the old one.
+ * OWNERSHIP: *out ADOPTS the base level handle of H -- level 0 with its multigrid depths is neither copied nor re-created, and
+ * suhmo_hier_box(*out, 0, 0) is the handle suhmo_hier_box(H, 0, 0) was -- and H IS CONSUMED: destroyed on success (its boxes, plans, tag
+ * maps and the gap-height hierarchy of its time step go with it; the base level forgets what it knew about its ice mask and drops its
+ * captured V-cycles).  When the call fails *out = NULL and H is untouched and usable; lists suhmo_hier_create refuses (bad nesting,
+ * misaligned or overlapping boxes, ...) give suhmo_hier_create's return code and message.  A hierarchy on rank strips, with levels dealt
+ * to the ranks or created with shadow = 1: rc -5.  The call synchronises the device.
+ * MEMORY of the plans, per level and only for the duration of the call: 32 B per pair (new box, box of level l - 1) that intersect + 24 B
+ * per pair (old box, new box) that intersect.  Not built: tagSubset boxes, m_regrid_lbase > 0, refinement ratios other than 2, rank strips. */
+int suhmo_hier_regrid(suhmo_hier_t *H, int nlev, const int *nbox, const int *boxes, int nfields, const int *fields, suhmo_hier_t **out,
+                      suhmo_stream_t s);
 
 /* ---- an ENSEMBLE of N independent models on the same grid, stepped together (suhmo_amd/csrc/suhmo_batch.hip): the
  * reference's SHMIP suites are parameter sweeps on one 320 x 64 level (exec/A_SHMIP ... exec/F_SHMIP), far too small to occupy the device.  Every

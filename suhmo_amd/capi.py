@@ -105,7 +105,7 @@ SYMBOLS = [
     "suhmo_batch_time_varying_recharge", "suhmo_batch_moulin_source", "suhmo_batch_postproc_partial", "suhmo_batch_postproc_temporal", "suhmo_batch_postproc_table",
     "suhmo_batch_run", "suhmo_level_postproc_temporal_device",
     "suhmo_hier_tag_cells", "suhmo_hier_clear_tags", "suhmo_hier_get_tags", "suhmo_level_tag_cells", "suhmo_level_clear_tags", "suhmo_level_get_tags",
-    "suhmo_grids_generate", "suhmo_hier_generate_grids",
+    "suhmo_grids_generate", "suhmo_hier_generate_grids", "suhmo_hier_regrid",
 ]
 
 
@@ -265,6 +265,7 @@ def lib():
     L.suhmo_level_get_tags.argtypes = [vp, ucp, ip, ip]
     L.suhmo_grids_generate.argtypes = [ci, ci, ip, C.POINTER(GridParams), ci, C.POINTER(ucp), ip, ip, ip, ci]
     L.suhmo_hier_generate_grids.argtypes = [vp, C.POINTER(GridParams), ip, ip, ip, ci, ip]
+    L.suhmo_hier_regrid.argtypes = [vp, ci, ip, ip, ci, ip, C.POINTER(vp), vp]
     _LIB = L
     return L
 

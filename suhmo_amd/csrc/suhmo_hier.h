@@ -25,6 +25,7 @@ int launch_fas_enter(const OnBoxes &t, hipStream_t st);   // RHS0 <- RHS, RHS <-
 int launch_fas_leave(const OnBoxes &t, hipStream_t st);   // RHS <- RHS0, CORR <- PHI - PHIOLD in one launch
 int launch_copy(const OnBoxes &t, int fd, int fs, hipStream_t st);                                                        // valid cells + ghost ring
 int launch_copy_between(const OnBoxes &dst, const OnBoxes &src, const int *fd, const int *fs, int n, hipStream_t st);   // same boxes, two hierarchies
+int launch_extrap_ghosts(const OnBoxes &t, int field, hipStream_t st);                 // suhmo_step.hip: ExtrapGhostCells of a cell field
 // suhmo_bcoef.hip
 template <class T> int launch_grad_cc(const T &t, hipStream_t st);         // cell-centred gradient and its ghosts
 template <class T> int launch_re(const T &t, hipStream_t st);              // COMPUTERE on the ghosted box

@@ -317,7 +317,7 @@ extern "C" int suhmo_hier_destroy(suhmo_hier_t *H)
     if (H->xr) (void)hipFree(H->xr);
     for (int l = 0; l < 8; l++) {
         HLev &V = H->lev[l];
-        for (suhmo_level *L : V.box) (void)suhmo_level_destroy(L);
+        for (suhmo_level *L : V.box) if (!(l == 0 && H->base_borrowed)) (void)suhmo_level_destroy(L);
         V.ff_side.release(); V.ff_all.release(); V.push.release(); V.pbase.release(); V.cf.release(); V.pwl.release(); V.avg.release(); V.wing.release();
             V.wstart.release(); V.halo.release(); V.hbase.release();
         V.targets.release(); V.faces.release(); V.dirty0.release(); V.gcells.release();
@@ -386,6 +386,17 @@ static int parse_opts(suhmo_hier *H, const char *opts)
 }
 extern "C" int suhmo_hier_create_opts(suhmo_hier_t **out, const suhmo_level_desc_t *base, int nlev, const int *nbox, const int *boxes, const char *options)
 {
+    return suhmo_hier_create_on_(out, base, nullptr, nlev, nbox, boxes, options);
+}
+std::string suhmo_hier_options_(const suhmo_hier *H)
+{
+    std::string opts;
+    for (const HierOpt &o : hier_opts) opts += std::string(o.key) + "=" + std::to_string(H->*o.m) + ",";
+    return opts;
+}
+int suhmo_hier_check_(suhmo_hier *H) { return check_hier(H); }
+int suhmo_hier_create_on_(suhmo_hier **out, const suhmo_level_desc_t *base, suhmo_level *adopt, int nlev, const int *nbox, const int *boxes, const char *options)
+{
     ARG(out && base && nlev >= 1 && nlev <= 8);
     ARG(nlev == 1 || (nbox && boxes));
     ARG(base->i0 == 0 && (base->nx_global == 0 || base->nx_global == base->nx));
@@ -395,8 +406,9 @@ extern "C" int suhmo_hier_create_opts(suhmo_hier_t **out, const suhmo_level_desc
     if (parse_opts(H, options)) { delete H; return -1; }
     if (cut) { H->world = base->ny_global / base->ny; H->rank = base->j0 / base->ny; H->shadowed = 1; }
     H->nlev = nlev; H->device = base->device; H->bc = base->bc; H->base_desc = *base; H->base_desc.boxes = nullptr; H->base_desc.nbox = 0;
-    suhmo_level *B = nullptr;
-    int rc = suhmo_level_create(&B, base);
+    suhmo_level *B = adopt;
+    H->base_borrowed = adopt != nullptr;
+    int rc = adopt ? 0 : suhmo_level_create(&B, base);
     if (rc) { delete H; return rc; }
     H->lev[0].l = 0; H->lev[0].nxd = base->nx; H->lev[0].nyd = base->ny_global; H->lev[0].box.push_back(B);
     H->vglob = B->d[0].v;
@@ -521,8 +533,7 @@ int suhmo_hier_gap_(suhmo_hier *H, const suhmo_model_params_t *mp, double dt, su
         d.phys.use_NL = 0; d.alpha = 1.0; d.beta = dt * mp->diffFactor;
         std::vector<int> nbox(H->nlev, 0), flat;
         for (int l = 1; l < H->nlev; l++) { nbox[l] = (int)H->lev[l].box.size(); flat.insert(flat.end(), H->lev[l].b4.begin(), H->lev[l].b4.end()); }
-        std::string opts;                                  // the parent's options as they are now
-        for (const HierOpt &o : hier_opts) opts += std::string(o.key) + "=" + std::to_string(H->*o.m) + ",";
+        const std::string opts = suhmo_hier_options_(H);   // the parent's options as they are now
         int rc = suhmo_hier_create_opts(&H->gap, &d, H->nlev, nbox.data(), flat.data(), opts.c_str()); if (rc) return rc;
         H->gap_dt = dt;
         H->gap->ag = H->ag; H->gap->ag_user = H->ag_user;                                  // same strips, same ranks

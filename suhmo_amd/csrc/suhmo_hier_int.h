@@ -136,6 +136,8 @@ struct suhmo_hier {
     suhmo_bc_t bc;
     suhmo_level_desc_t base_desc;
     suhmo_hier *gap = nullptr; double gap_dt = 0.0;        // implicit gap-height operator of the time step, owned
+    bool base_borrowed = false;                            // level 0's handle belongs to another hierarchy (suhmo_hier_regrid, while the new one is built /
+                                                           // once the old one has handed its base level over): suhmo_hier_destroy leaves it alone
     // ---- level 0 cut into rank strips (one process per GPU): a rank holds its own rows of level 0 and ALL boxes of the finer
     // levels.  What level 1 reads of level 0 (coarse-fine stencils, linear fill, correction windows, reflux) comes from a
     // SHADOW: canvases with the geometry of the whole level 0, kept current only at the cells the plans read (`need`, sorted
@@ -275,3 +277,8 @@ int suhmo_hier_allreduce_max_(suhmo_hier *H, double *v);
 int suhmo_hier_allgather_(suhmo_hier *H, const double *send, long count, double *recv, hipStream_t st);
 // the hierarchy of SolveForGap_nl: the same boxes, alpha = 1, beta = dt diffFactor, Neumann-0 sides, no nonlinear term
 int suhmo_hier_gap_(suhmo_hier *H, const suhmo_model_params_t *mp, double dt, suhmo_hier **gap);
+// ---- suhmo_hier.hip: what the regrid (suhmo_regrid.hip) needs of the creation path
+// suhmo_hier_create_opts around an EXISTING base level handle (adopt != NULL: borrowed until the caller settles who owns it, base_borrowed)
+int suhmo_hier_create_on_(suhmo_hier **out, const suhmo_level_desc_t *base, suhmo_level *adopt, int nlev, const int *nbox, const int *boxes, const char *options);
+std::string suhmo_hier_options_(const suhmo_hier *H);                               // the options as they are now, "key=value,..."
+int suhmo_hier_check_(suhmo_hier *H);                                               // what every C-ABI entry of a hierarchy does first

@@ -317,6 +317,8 @@ __device__ __forceinline__ void d_extrap_ghosts(const DV &v, double *__restrict_
     }
 }
 template <class T> __global__ void k_extrap_ghosts(T t, int field) { d_extrap_ghosts(t.view(), t.field(field)); }
+// ... of any cell field of every box of a level (the regrid's field transfer, suhmo_regrid.hip)
+int launch_extrap_ghosts(const OnBoxes &t, int field, hipStream_t st) { return launch_over(k_extrap_ghosts<OnBoxes>, t, PERIMETER, st, field); }
 // dCoeff: CellToEdge(mR), CellToEdge(b), setup_iceMask_EC, COMPUTEDCOEFF (src/AmrHydro.cpp:1831-1862, ...F.ChF:241-265)
 __device__ __forceinline__ void d_dcoef_faces(const DV &v, const FP &fp, suhmo_phys_t ph, double rho_i)
 {

@@ -388,11 +388,18 @@ class HipHier:
         arr = (C.c_int * max(len(flat), 1))(*flat)
         h = C.c_void_p()
         check(capi.lib().suhmo_hier_create_opts(C.byref(h), C.byref(d), self.nlev, nbox, arr, options.encode() if options else None))
-        self.h = h
         self.j0, self.ny_global = j0, int(d.ny_global)
+        self.rank = (j0 // ny0) if ny_global is not None and ny_global != ny0 else 0
+        self._base = (nx0, ny0, dx0, dy0)
+        self._bind(h)
+
+    def _bind(self, h):
+        """wrap the handle h of a hierarchy on self.boxes: the box views and the owner / held tables"""
+        nx0, ny0, dx0, dy0 = self._base
+        self.h = h
         self.stream = C.c_void_p(0)
         self.level = [[_BoxView(capi.lib().suhmo_hier_box(h, 0, 0), nx0, ny0, dx0, dy0, self.stream)]]
-        self.level[0][0].j0, self.level[0][0].ny_global = j0, self.ny_global          # (this rank's strip of level 0)
+        self.level[0][0].j0, self.level[0][0].ny_global = self.j0, self.ny_global          # (this rank's strip of level 0)
         for l, bl in enumerate(self.boxes, start=1):
             self.level.append([_BoxView(capi.lib().suhmo_hier_box(h, l, k), b[2] - b[0] + 1, b[3] - b[1] + 1, dx0 / 2 ** l, dy0 / 2 ** l,
                                         self.stream) for k, b in enumerate(bl)])
@@ -407,7 +414,28 @@ class HipHier:
                 ow.append(int(capi.lib().suhmo_hier_box_owner(h, l, k, C.byref(hf))))
                 he.append(bool(hf.value))
             self.owner.append(ow); self.held.append(he)
-        self.rank = (j0 // ny0) if ny_global is not None and ny_global != ny0 else 0
+
+    def regrid(self, boxes, fields=None):
+        """suhmo_hier_regrid: the hierarchy moves onto `boxes` (as the constructor takes them; [] = the base level alone), the listed fields
+        (ids; None: head, B, Pi, zb, mask, mR, Pw, zs) transferred on the device.  The old handle is consumed: on success this object wraps
+        the new one -- new box views in self.level, new owner / held tables, the same base level -- and views taken before are dead.  When the
+        call fails (SuhmoError) nothing has changed and the old hierarchy goes on."""
+        boxes = [[tuple(int(v) for v in b) for b in bl] for bl in boxes]
+        nlev = 1 + len(boxes)
+        nbox = (C.c_int * nlev)(0, *[len(bl) for bl in boxes])
+        flat = [v for bl in boxes for b in bl for v in b]
+        arr = (C.c_int * max(len(flat), 1))(*flat)
+        fl, nf = None, 0
+        if fields is not None:
+            nf = len(fields)
+            fl = (C.c_int * max(nf, 1))(*[int(f) for f in fields])
+        h = C.c_void_p()
+        check(capi.lib().suhmo_hier_regrid(self.h, nlev, nbox, arr, nf, fl, C.byref(h), self.stream))
+        for bl in self.level:
+            for v in bl:
+                v.close()
+        self.boxes, self.nlev = boxes, nlev
+        self._bind(h)
 
     def owns(self, l, k):
         """this rank computes box k of level l (every box of a replicated level; on a level dealt to the ranks: its own boxes)"""

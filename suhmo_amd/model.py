@@ -548,6 +548,53 @@ class HipHierModel:
                           self.hier.nlev)
         return boxes, bool(same.value)
 
+    def regrid(self, boxes, reload=None, fields=None):
+        """AmrHydro::regrid's third step (destructiveRegrid, src/AmrHydro.cpp:4176-4223, 4363-4437) on the device, suhmo_hier_regrid: the
+        hierarchy moves onto `boxes` (the form the constructor and generate_grids use; [] = level 0 alone) between two time steps.  Per new
+        level, ascending: every cell interpolated from the new level below (FineInterp, limited slopes), then overwritten bit for bit where an
+        old box of the level held it; ghost cells refilled.  fields: names of FIELDS (or ids); None = head, B, Pi, zb, mask, mR, Pw, zs.
+        Every other field of the levels >= 1 starts as in a new hierarchy (the next moulin_source / timestep recomputes them); level 0, the
+        model parameters and cur_step stay.  self.hier wraps the new handle afterwards and self.level holds the new boxes' views.
+        reload(l, k, box) -> dict as set_state takes it, possibly partial (head, B, Pi, zb, mask: ghosted arrays of the box), or None: called
+        for every new box after the transfer and loaded over the transferred values -- the place of initializeBed / initializePi /
+        setup_iceMask (:4387-4437); the IBCs stay the caller's.
+        THE MASK: a transferred ice mask is INTERPOLATED and therefore not +-1 along an ice margin.  The reference does not keep it either:
+        it recomputes the mask from Pi after every regrid (setup_iceMask, :4436).  A caller whose domain has a margin must do the same in
+        `reload` (return "mask" for every box); where the mask is +1 everywhere the transferred one is exact.
+        A list that suhmo_hier_create would refuse (nesting, alignment) raises SuhmoError with its return code and leaves the model as it was."""
+        ids = None if fields is None else [f if isinstance(f, int) else (lv.F_ZS if f == "zs" else self.FIELDS[f]) for f in fields]
+        self.hier.regrid(boxes, ids)
+        self.level = self.hier.level
+        if reload is not None:
+            for l, bl in enumerate(self.hier.boxes, start=1):
+                for k, b in enumerate(bl):
+                    f = reload(l, k, b)
+                    if f:
+                        self._load(l, k, f)
+
+    def _load(self, l, k, f):
+        L = self.level[l][k]
+        if "head" in f:
+            L.set(lv.F_PHI, f["head"][1:-1, 1:-1])
+        for key, fid in (("B", lv.F_B), ("Pi", lv.F_PI), ("zb", lv.F_ZB), ("mask", lv.F_MASK)):
+            if key in f:
+                L.set(fid, f[key], ghosted=True)
+
+    def tag_and_regrid(self, tag_specs, params, reload=None):
+        """The body of AmrHydro::regrid (src/AmrHydro.cpp:4227-4511): the tag maps are emptied, every level is tagged with tag_specs (dicts of
+        tag_cells' arguments without the level: name, vmin, vmax, grow, grow_dir), grids are generated with params (generate_grids' keywords)
+        and, when they are not the hierarchy's own (gridsSame), the fields move onto them (regrid).  Returns (boxes, same); with same = True
+        the handle is not touched."""
+        g = int(params["block_factor"]) // 2
+        self.clear_tags()
+        for l in range(self.hier.nlev):
+            for sp in tag_specs:
+                self.tag_cells(l, granularity=g, **sp)
+        boxes, same = self.generate_grids(**params)
+        if not same:
+            self.regrid(boxes, reload=reload)
+        return boxes, same
+
     def get(self, l, k, name, ghosted=False):
         """a field of box k of level l; None where another rank owns the box (levels dealt to the ranks: hier.owns(l, k))"""
         if not self.hier.owns(l, k):

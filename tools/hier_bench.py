@@ -1,6 +1,11 @@
 #!/usr/bin/env python3
 """cfg5 (exec/AMR_multiMoulins physics) time step on base + 3 AMR levels of box unions: ms per step.
-    python tools/hier_bench.py [--generated-grids] [base cells per side] [steps]
+    python tools/hier_bench.py [--generated-grids] [--regrid-interval N] [base cells per side] [steps]
+--regrid-interval N: the time loop regrids every N steps as AmrHydro::regrid does (HipHierModel.tag_and_regrid's body, with the per-level tag
+thresholds of --generated-grids; the thresholds alternate between two sets, so that every regrid moves boxes) and prints, per regrid, the times of
+tagging, clustering, hierarchy creation, the transfer's plans and launches, the moulin source term on the new boxes and the steps around it --
+and, for the first regrid, what the same move costs through the host (all fields read back, the interpolation in numpy, a new model created and
+loaded: what a caller can do without suhmo_hier_regrid), its valid cells compared with the device's bit for bit.
 --generated-grids: the hierarchy is made the reference's way instead of synthetic.boxes_around -- a level per pass of the initGrids loop, by tagging
 the moulin source term on the device (suhmo_hier_tag_cells) and clustering the tags (suhmo_grids_generate) with run_C_3lev's fill_ratio,
 block_factor, max_box_size, nestingRadius and tags_grow; the time of tagging, copy-out and generation is reported per level."""
@@ -9,6 +14,11 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from suhmo_amd import model, synthetic as sy
 generated = "--generated-grids" in sys.argv
 argv = [a for a in sys.argv[1:] if a != "--generated-grids"]
+regrid_interval = 0
+if "--regrid-interval" in argv:
+    q = argv.index("--regrid-interval")
+    regrid_interval = int(argv[q + 1])
+    del argv[q:q + 2]
 nb = int(argv[0]) if len(argv) > 0 else 256
 nstep = int(argv[1]) if len(argv) > 1 else 10
 bc, ph, mm, mo = sy.multimoulins_setup()
@@ -45,6 +55,134 @@ def generated_boxes():
     return boxes
 
 
+GRID_PARAMS = dict(fill_ratio=0.5, block_factor=2, max_box_size=64, nesting_radius=4)
+REGRID_FIELDS = ("head", "B", "Pi", "zb", "mask", "mR", "Pw", "zs")
+
+
+def host_interp(c, periodic):
+    """rule (a) of "REGRID: FIELD TRANSFER" (include/suhmo_hip.h) for every cell of the full-domain array c of a level (NaN where the level has no
+    cell), vectorised: the four children as one array of twice the size.  The statements of tests/regrid_ref.py, array by array"""
+    import numpy as np
+    ny, nx = c.shape
+    p = np.pad(c, 1, constant_values=np.nan)
+    if periodic[0]:
+        p[1:-1, 0], p[1:-1, -1] = c[:, -1], c[:, 0]
+    if periodic[1]:
+        p[0, :], p[-1, :] = p[-2, :].copy(), p[1, :].copy()
+    nb = lambda a, b: p[1 + b:1 + b + ny, 1 + a:1 + a + nx]
+    W, E, S, N = nb(-1, 0), nb(1, 0), nb(0, -1), nb(0, 1)
+    xl, xh, yl, yh = ~np.isnan(W), ~np.isnan(E), ~np.isnan(S), ~np.isnan(N)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        s0 = np.where(xl & xh, 0.5 * (E - W), np.where(xh, E - c, np.where(xl, c - W, 0.0)))
+        s1 = np.where(yl & yh, 0.5 * (N - S), np.where(yh, N - c, np.where(yl, c - S, 0.0)))
+        smax, smin = c.copy(), c.copy()
+        for b in (-1, 0, 1):
+            for a in (-1, 0, 1):
+                smax, smin = np.fmax(smax, nb(a, b)), np.fmin(smin, nb(a, b))
+        ds = 0.5 * (np.abs(s0) + np.abs(s1))
+        eta = np.maximum(np.minimum(np.minimum((c - smin) / ds, (smax - c) / ds), 1.0), 0.0)
+        cut = ds > 0.0
+        s0 = np.where(cut & xl & xh, eta * s0, s0)
+        s1 = np.where(cut & yl & yh, eta * s1, s1)
+    out = np.empty((2 * ny, 2 * nx))
+    for q in (0, 1):
+        for pp in (0, 1):
+            v = c + s0 * (0.25 if pp else -0.25)
+            out[q::2, pp::2] = v + s1 * (0.25 if q else -0.25)
+    return out
+
+
+def host_round_trip(H, new_boxes):
+    """the same regrid without suhmo_hier_regrid: read back, interpolate and copy in numpy (valid cells only: the ghost fills are left out, in the
+    host's favour), create a model on the new boxes and load it.  -> (times, the new model)"""
+    import numpy as np
+    from suhmo_amd import level as lv
+    ids = dict(H.FIELDS, zs=lv.F_ZS)
+    t = {}
+    t0 = time.perf_counter()
+    old = {nm: [[L.get(ids[nm], ghosted=True) for L in bl] for bl in H.level] for nm in REGRID_FIELDS}
+    t["read back"] = time.perf_counter() - t0
+    t0 = time.perf_counter()
+    new = {}
+    for nm in REGRID_FIELDS:
+        coarse, per_level = old[nm][0][0][1:-1, 1:-1], []
+        for l, bl in enumerate(new_boxes, start=1):
+            full = host_interp(coarse, bc["periodic"])
+            keep = np.zeros(full.shape, dtype=bool)
+            for b in bl:
+                keep[b[1]:b[3] + 1, b[0]:b[2] + 1] = True
+            full[~keep] = np.nan
+            if l < len(H.level):
+                for b, a in zip(H.hier.boxes[l - 1], old[nm][l]):
+                    m = keep[b[1]:b[3] + 1, b[0]:b[2] + 1]
+                    full[b[1]:b[3] + 1, b[0]:b[2] + 1][m] = a[1:-1, 1:-1][m]
+            per_level.append([np.ascontiguousarray(full[b[1]:b[3] + 1, b[0]:b[2] + 1]) for b in bl])
+            coarse = full
+        new[nm] = per_level
+    t["numpy"] = time.perf_counter() - t0
+    t0 = time.perf_counter()
+    M = model.HipHierModel(nb, nb, 1.0e5 / nb, 1.0e5 / nb, bc, ph, mm, new_boxes, max_box=64)
+    t["create"] = time.perf_counter() - t0
+    t0 = time.perf_counter()
+    for nm in REGRID_FIELDS:
+        M.level[0][0].set(ids[nm], old[nm][0][0], ghosted=True)
+        for l, bl in enumerate(new_boxes, start=1):
+            for k in range(len(bl)):
+                M.level[l][k].set(ids[nm], new[nm][l - 1][k])
+    M.level[0][0].synchronize()
+    t["load"] = time.perf_counter() - t0
+    return t, M, new
+
+
+def timed_regrid(H, n, first):
+    """the body of HipHierModel.tag_and_regrid with a clock around every part"""
+    from suhmo_amd import capi, level as lv
+    sync = lambda: H.level[0][0].synchronize()          # (the views change hands with the regrid)
+    peak = float(H.get(0, 0, "msrc").max())
+    scale = (1.0, 0.6)[n % 2]
+    sync(); t0 = time.perf_counter()
+    H.clear_tags()
+    for l in range(min(H.hier.nlev, 3)):
+        H.tag_cells(l, "msrc", scale * (0.01, 0.1, 0.5)[l] * peak, 1.0e300, grow=4, granularity=GRID_PARAMS["block_factor"] // 2)
+    sync(); t1 = time.perf_counter()
+    new, same = H.generate_grids(**GRID_PARAMS)
+    t2 = time.perf_counter()
+    host = None
+    if first and not same:
+        host = host_round_trip(H, new)
+    t_host = time.perf_counter() - t2
+    # (mode 1: host wall time per scope; both scopes end with a synchronisation of their own)
+    capi.lib().suhmo_timers_enable(1); capi.lib().suhmo_timers_reset()
+    t3 = time.perf_counter()
+    if not same:
+        H.regrid(new)
+    sync(); t4 = time.perf_counter()
+    rep = capi.timers_report(); capi.lib().suhmo_timers_enable(0)
+    scope = {}
+    for line in rep.splitlines():
+        q = line.rsplit(None, 3)
+        if len(q) == 4 and q[0].startswith("regrid:"):
+            scope[q[0]] = 1e3 * float(q[2])
+    H.moulin_source(**mo)
+    sync(); t5 = time.perf_counter()
+    print("regrid %d: same %s, boxes per level %s | tagging %.3f ms, clustering (copy-out + generation) %.3f ms, regrid call %.3f ms "
+          "(hierarchy creation %.3f ms, transfer plans + launches %.3f ms, old hierarchy destroyed %.3f ms), moulin source on the new boxes %.3f ms"
+          % (n, same, [len(b) for b in new], 1e3 * (t1 - t0), 1e3 * (t2 - t1), 1e3 * (t4 - t3),
+             scope.get("regrid: hierarchy creation (boxes, plans, tables)", 0.0), scope.get("regrid: transfer plans and launches", 0.0),
+             scope.get("regrid: old hierarchy destroyed", 0.0), 1e3 * (t5 - t4)), flush=True)
+    if host:
+        import numpy as np
+        t, M, ref = host
+        ids = dict(H.FIELDS, zs=lv.F_ZS)
+        eq = all(np.array_equal(H.level[l][k].get(ids[nm]), ref[nm][l - 1][k], equal_nan=True)
+                 for nm in REGRID_FIELDS for l, bl in enumerate(new, start=1) for k in range(len(bl)))
+        print("  the same move through the host: read back %.3f ms, interpolation and copy in numpy %.3f ms, new model created %.3f ms, loaded %.3f ms: "
+              "%.3f ms in all; valid cells bitwise equal to the device's: %s" % (1e3 * t["read back"], 1e3 * t["numpy"], 1e3 * t["create"], 1e3 * t["load"],
+              1e3 * sum(t.values()), eq), flush=True)
+        M.close()
+    return t5 - t0 - t_host, t_host
+
+
 boxes = generated_boxes() if generated else sy.boxes_around(mo["positions"], nb, nb, 4, 1.0e5, 1.0e5)
 sts = sy.mountain_amrm_states(nb, nb, boxes)
 t0 = time.perf_counter()
@@ -60,9 +198,23 @@ if os.environ.get("SUHMO_TIMERS"):
     from suhmo_amd import capi
     capi.lib().suhmo_timers_reset()
 t0 = time.perf_counter()
-c = [H.timestep(mm["dt"]) for _ in range(nstep)]
-H.level[0][0].synchronize()
-dt = (time.perf_counter() - t0) / nstep
+if regrid_interval:
+    c, t_regrid, t_other, t_last = [], 0.0, 0.0, time.perf_counter()
+    for n in range(nstep):
+        c.append(H.timestep(mm["dt"]))
+        if (n + 1) % regrid_interval == 0:
+            H.level[0][0].synchronize()
+            print("steps %d..%d: %.2f ms per step" % (n + 2 - regrid_interval, n + 1, 1e3 * (time.perf_counter() - t_last) / regrid_interval), flush=True)
+            tr, th = timed_regrid(H, (n + 1) // regrid_interval, (n + 1) == regrid_interval)
+            t_regrid += tr; t_other += th
+            t_last = time.perf_counter()
+    H.level[0][0].synchronize()
+    dt = (time.perf_counter() - t0 - t_regrid - t_other) / nstep
+    print("regrids: %.2f ms per interval of %d steps" % (1e3 * t_regrid / max(1, nstep // regrid_interval), regrid_interval))
+else:
+    c = [H.timestep(mm["dt"]) for _ in range(nstep)]
+    H.level[0][0].synchronize()
+    dt = (time.perf_counter() - t0) / nstep
 print("base %d^2: %.2f ms per step, Picard %.1f, V-cycles %.1f per step" % (nb, 1e3 * dt, sum(a for a, _ in c) / nstep, sum(b for _, b in c) / nstep))
 if os.environ.get("SUHMO_TIMERS"):            # named scopes (mode 2: device time per scope; serialises)
     from suhmo_amd import capi
