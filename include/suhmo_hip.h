@@ -473,6 +473,8 @@ int suhmo_hier_create(suhmo_hier_t **out, const suhmo_level_desc_t *base, int nl
  * rectangles.  Below the threshold a pass over the levels is shorter than the messages, so every rank relaxes all boxes.  The same
  * bits either way.  Read-only through suhmo_hier_get_option: partitioned_level_<l> (0 / 1), own_boxes_level_<l>, held_boxes_level_<l>
  * (own + mirrors), owned_cells_level_<l>, canvas_bytes_level_<l> (bytes of the level's canvases on this rank),
+ * gap_num_boxes (boxes of the levels >= 1 of the gap-height hierarchy of the implicit time step, which is made on the hierarchy's own boxes by the
+ * first implicit step; -1 while there is none),
  * ghost_exchange_bytes_level_<l> (what this rank sends per colour-pass exchange) and ghost_exchange_bound_bytes_level_<l> (4 sides x 8 B
  * of its boxes), partition_gathers, partition_bytes (collectives of the partition so far / bytes this rank put into them). */
 int suhmo_hier_create_opts(suhmo_hier_t **out, const suhmo_level_desc_t *base, int nlev, const int *nbox, const int *boxes, const char *options);
@@ -487,6 +489,9 @@ int suhmo_hier_destroy(suhmo_hier_t *H);
 int suhmo_hier_num_levels(const suhmo_hier_t *H);
 int suhmo_hier_num_boxes(const suhmo_hier_t *H, int level);
 suhmo_level_t *suhmo_hier_box(suhmo_hier_t *H, int level, int box);   /* level 0, box 0 = the base level */
+/* the boxes of level `level` >= 1 as the hierarchy was created with them: 4 x suhmo_hier_num_boxes(H, level) ints (lo0, lo1, hi0, hi1) -- what a
+ * caller needs of a handle it did not create itself (the one a regrid inside suhmo_hier_run leaves) */
+int suhmo_hier_get_boxes(const suhmo_hier_t *H, int level, int *boxes);
 /* the rank that owns box `box` of a level dealt to the ranks (partition_min_cells), -1: every rank holds it (a replicated level, level 0's
  * strip), -2: no such box; *held (may be NULL): this rank keeps storage for it -- its own box or a mirror; load and read a box where it is
  * owned (a mirror's cells are overwritten by its owner's; a box that is not held refuses field access with rc -7) */
@@ -553,7 +558,22 @@ int suhmo_hier_moulin_source(suhmo_hier_t *H, int n_moulins, const double *posit
  * Output as suhmo_hier_create takes it: *nlev_out = levels including level 0, nbox[0 .. *nlev_out - 1] (nbox[0] = 0; the array must hold ntag + 1
  * ints), boxes = (lo0, lo1, hi0, hi1) one after the other, level 1 first.  rc -1: a bad parameter, ntag < 1 or > 7; rc -4: boxes_cap (in
  * boxes) too small -- nbox[] and *nlev_out are still set and the message names the needed count, so a second call can succeed.
- * tagSubset boxes (AmrHydro.tagSubsetBoxesFile) are not built.
+ *
+ * THE REST OF tagCells (src/AmrHydro.cpp:4514-4536): subset boxes and per-variable level ranges.
+ * suhmo_hier_restrict_tags(H, level, nboxes, boxes, s) is `levelTags &= tagSubset` (:4530-4533, AmrHydro.tagSubsetBoxesFile): every entry of the
+ * level's tag map that lies in none of the boxes (lo0, lo1, hi0, hi1 in cells of that level, HOST array; they may overlap and may reach beyond
+ * the domain) is cleared -- entry (a, b) of a map at granularity g lies in a box when lo0 <= a g <= hi0 and lo1 <= b g <= hi1.  One launch: one
+ * thread per entry, the box list in device memory (owned by the map), plain byte stores of 0.  nboxes == 0: a no-op, rc 0 (the reference skips
+ * an empty subset); a level without a map: rc 0, nothing to do; a box with lo > hi, or whose lo or hi + 1 is not a multiple of g (an entry must
+ * lie wholly inside or wholly outside): rc -1 and nothing is cleared; rank strips: rc -5.  Tagging after a restrict accumulates again.
+ * suhmo_tag_subsets_nest (host; no device) builds the per-level subsets the way the reference does when it reads the file (:1097-1108): input
+ * nbox[l] boxes per level l = 0 .. nlev - 1, one after the other in `boxes`; for l = 1, 2, ... in this order, with C = the NESTED subset of level
+ * l - 1, every box (lo0, lo1, hi0, hi1) -> (2 lo0, 2 lo1, 2 hi0 + 1, 2 hi1 + 1): C empty: level l keeps its own; else level l's own empty: it becomes C;
+ * else it becomes the non-empty pairwise intersections own[a] x C[c], a outer, c inner (none: the subset is empty and constrains nothing).
+ * Output like the input; rc -4 when boxes_cap (in boxes) is too small, nbox_out set and the needed count in the message.
+ * A tag variable m has a level range (AmrHydro.tagging_mins / tagging_caps): it tags the levels max(min_level, 0) .. min(cap_level, max_level - 1,
+ * finest level) (:4521-4527), and the subset of a level is applied after each variable's tagging of it, on the accumulated map (suhmo_tag_spec_t
+ * and suhmo_hier_run below; HipHierModel.tag_and_regrid is the same loop over these calls).
  *
  * BOTH.  suhmo_hier_generate_grids copies out the tag maps of the levels 0, 1, ... of H that have one (up to the first without; their
  * granularity must be block_factor / 2: rc -1; no map on level 0: rc -1) and calls the generator with the hierarchy's base size and
@@ -572,6 +592,8 @@ int suhmo_level_get_tags(suhmo_level_t *L, unsigned char *host, int *nbx, int *n
 int suhmo_grids_generate(int nx0, int ny0, const int periodic[2], const suhmo_grid_params_t *p, int ntag, const unsigned char *const *tags,
                          int *nlev_out, int *nbox, int *boxes, int boxes_cap);
 int suhmo_hier_generate_grids(suhmo_hier_t *H, const suhmo_grid_params_t *p, int *nlev_out, int *nbox, int *boxes, int boxes_cap, int *same);
+int suhmo_hier_restrict_tags(suhmo_hier_t *H, int level, int nboxes, const int *boxes, suhmo_stream_t s);
+int suhmo_tag_subsets_nest(int nlev, const int *nbox, const int *boxes, int *nbox_out, int *boxes_out, int boxes_cap);
 
 /* ---- REGRID: FIELD TRANSFER (suhmo_amd/csrc/suhmo_regrid.hip; tests/regrid_ref.py is the numpy twin of this text).
  * The third step of AmrHydro::regrid (src/AmrHydro.cpp:4227-4511) after tagging and clustering: destructiveRegrid (:4176-4223) for refinement
@@ -622,9 +644,84 @@ int suhmo_hier_generate_grids(suhmo_hier_t *H, const suhmo_grid_params_t *p, int
  * misaligned or overlapping boxes, ...) give suhmo_hier_create's return code and message.  A hierarchy on rank strips, with levels dealt
  * to the ranks or created with shadow = 1: rc -5.  The call synchronises the device.
  * MEMORY of the plans, per level and only for the duration of the call: 32 B per pair (new box, box of level l - 1) that intersect + 24 B
- * per pair (old box, new box) that intersect.  Not built: tagSubset boxes, m_regrid_lbase > 0, refinement ratios other than 2, rank strips. */
+ * per pair (old box, new box) that intersect.  Not built: m_regrid_lbase > 0, refinement ratios other than 2, rank strips. */
 int suhmo_hier_regrid(suhmo_hier_t *H, int nlev, const int *nbox, const int *boxes, int nfields, const int *fields, suhmo_hier_t **out,
                       suhmo_stream_t s);
+
+/* ---- THE RUN OF A HIERARCHY (suhmo_amd/csrc/suhmo_run.hip, suhmo_step.hip): what AmrHydro::run (src/AmrHydro.cpp:1283-1365)
+ * does around timeStepFAS, for a hierarchy of box unions.
+ * suhmo_hier_time_varying_recharge   suhmo_level_time_varying_recharge on every box (timeStepFAS evaluates COMPUTE_TIMEVARYINGRECHARGE level by
+ *     level, :2846-2863): SUHMO_F_MSRC of every box, ghost ring included, bit for bit what the level call on that box's handle writes.  ONE launch
+ *     for level 0 and ONE per refined level (read-only option recharge_launches counts them), never one per box.  No averaging down and no
+ *     coarse-fine fill: the reference does neither for this source (:2854-2863, unlike the moulins', :2818-2839).  Checked before anything is
+ *     launched: a box that does not hold SUHMO_F_ZS: rc -1, the message names level and box; a hierarchy on rank strips or with levels dealt to
+ *     the ranks: rc -5.
+ * suhmo_hier_postproc_temporal   the daily row: the reference evaluates it on level 0 ("POST PROC -- 1 LEVEL", :3643-3700) --
+ *     suhmo_level_postproc_temporal_device on suhmo_hier_box(H, 0, 0), its bits and its refusals; rank strips: rc -5.
+ * suhmo_hier_run   the time loop in one call.  For step k = 0 .. n_steps - 1 with c = first_cur_step + k (cur_step of suhmo_hier_timestep):
+ *   1. REGRID when regrid_interval > 0, c - 1 != 0 and (c - 1) % regrid_interval == 0 (:1317; c - 1 is m_cur_step before its increment), except at
+ *      k = 0 when skip_first_regrid is set (the reference's m_cur_step != m_restart_step).  suhmo_hier_clear_tags(-1); for every tag variable m, in
+ *      order, for l = max(min_level, 0) .. min(cap_level, max_level - 1, finest level): suhmo_hier_tag_cells(l, field, vmin, vmax, grow, grow_x,
+ *      grow_y, grid.block_factor / 2), then, when subset_nbox[l] > 0, suhmo_hier_restrict_tags(l) with the boxes of that level (subset_boxes: level
+ *      0's first; the caller has nested them, suhmo_tag_subsets_nest); suhmo_hier_generate_grids; when *same is 0, suhmo_hier_regrid with
+ *      n_fields / fields (NULL: its default list).  After such a grid-changing regrid *H is the new handle and reload(user, *H, index of the regrid
+ *      in the log, c) is called -- the place of initializeBed / initializePi / setup_iceMask (:4387-4437): it loads through the ordinary per-box
+ *      calls.  When *same is 1 the handle and every view stay.
+ *   2. FORCING.  With T_K: the recharge launches above with T_K[k], background[k], every step.  With moulins: suhmo_hier_moulin_source with the
+ *      factor f[k] = moulin_factor[k] (NULL: 1.0), but only when k = 0, or a grid-changing regrid happened in this step's (1), or the bits of f[k]
+ *      differ from those of f[k - 1] -- the reference's m_regrid rule (:2802) plus a factor that can change.  Both kinds at once: rc -1.
+ *   3. suhmo_hier_timestep with *mp, ramp = ramp[k] when ramp is given, dt, cur_step = c.
+ *   4. When diag_every > 0 and (k + 1) % diag_every == 0: the column sums of level 0 and the row of suhmo_hier_postproc_temporal finished ON THE
+ *      DEVICE into a series [rows][6]: no copy and no synchronisation per row.
+ * After the last step the series comes back in ONE copy (read-only option run_readbacks counts it; moulin_source_calls counts (2)'s calls; a run
+ * carries the three counters of this section over its regrids).  Every field of every box, every count and every row is bit for bit what the
+ * same sequence of the public calls gives.  The schedule carries VALUES, all HOST arrays.
+ * res: steps_done, n_rows; picard_iters / vcycles [n_steps] (may be NULL); rows [n_steps / diag_every][6] (may be NULL when there are none);
+ * moulin_steps [n_steps] (may be NULL): 1 where (2) formed the moulin source; n_regrids = regrids done, the first regrids_cap of them logged in
+ * regrids (may be NULL): cur_step = c, same, nlev and nbox[l] of the generated lists (nbox[0] = 0); n_moved = those of them with same = 0, i.e. how
+ * often *H became a new handle.  A regrid whose lists suhmo_hier_create refuses is neither logged nor counted: the hierarchy is the old one.
+ * THE SURFACE HEIGHT ACROSS A REGRID: with T_K the new boxes must hold SUHMO_F_ZS before the next recharge launch.  They do when `fields` is NULL
+ * or lists SUHMO_F_ZS (the transfer brings it), or when `reload` loads it on EVERY new box; after a grid-changing regrid and its `reload` every
+ * box is checked again, and a box without it ends the run there with rc -1 (the message names level and box), nothing launched on the new
+ * hierarchy, steps_done = the steps completed and *H the new handle.
+ * A failing step, a list suhmo_hier_create refuses, or a reload that returns non-zero ends the run with that call's rc (reload: rc -1, its value
+ * in the message): steps_done = the steps completed, the rows so far copied out, and *H a usable hierarchy -- the old one when the regrid
+ * failed, the new one otherwise.  Checked before anything is launched, rc -1 (rank strips, levels dealt to the ranks: -5) and a message:
+ * n_steps < 1, dt <= 0, first_cur_step < 1, diag_every < 0; T_K without background or the reverse; an incomplete set of moulin arrays (n_moulins
+ * >= 1 with positions, sigma > 0, flux; or none of them), both kinds of forcing; regrid_interval < 0, regrid_interval > 0 without tags, with
+ * max_level outside 1 .. 8, with grid parameters suhmo_grids_generate refuses (its rc), with a bad tag field or reach, with a subset box not
+ * aligned to block_factor / 2; SUHMO_F_ZS missing where T_K is given; use_moulin_source without any forcing and without a source term on
+ * some box; use_impl_diff with diffFactor = 0; rows without an array for them, or a level 0 suhmo_hier_postproc_temporal refuses.
+ * Eager launches as in suhmo_batch_run; no graph capture.  Not built: rank strips. */
+typedef struct suhmo_tag_spec { int field; double vmin, vmax; int grow, grow_x, grow_y; int min_level, cap_level; } suhmo_tag_spec_t;
+typedef int (*suhmo_hier_reload_fn)(void *user, suhmo_hier_t *Hnew, int regrid_index, int cur_step);
+typedef struct suhmo_hier_schedule {
+    int n_steps; double dt; int first_cur_step;
+    const double *T_K, *background;            /* [n_steps] each, or both NULL */
+    int n_moulins; const double *positions, *sigma, *flux;   /* once for the run, or n_moulins = 0 and all NULL */
+    const double *moulin_factor;               /* [n_steps] or NULL (= 1.0) */
+    const double *ramp;                        /* [n_steps] or NULL */
+    int diag_every;                            /* 0: no rows */
+    int regrid_interval, skip_first_regrid, max_level;       /* regrid_interval 0: never regrid; max_level: AmrHydro.max_level, levels above 0 at most */
+    int n_tags; const suhmo_tag_spec_t *tags; suhmo_grid_params_t grid;
+    const int *subset_nbox, *subset_boxes;     /* per level 0 .. max_level - 1, or both NULL */
+    int n_fields; const int *fields;           /* as suhmo_hier_regrid */
+    suhmo_hier_reload_fn reload; void *user;   /* or NULL */
+} suhmo_hier_schedule_t;
+typedef struct suhmo_hier_regrid_log { int cur_step, same, nlev; int nbox[8]; } suhmo_hier_regrid_log_t;
+typedef struct suhmo_hier_run_result {
+    int steps_done, n_rows;
+    int *picard_iters, *vcycles;               /* [n_steps], may be NULL */
+    double *rows;                              /* [n_steps / diag_every][6] */
+    int *moulin_steps;                         /* [n_steps], may be NULL */
+    int n_regrids, regrids_cap;
+    suhmo_hier_regrid_log_t *regrids;          /* [regrids_cap], may be NULL */
+    int n_moved;                               /* regrids that moved the hierarchy onto other boxes (*H changed n_moved times) */
+} suhmo_hier_run_result_t;
+int suhmo_hier_time_varying_recharge(suhmo_hier_t *H, double T_K, double background_input, suhmo_stream_t s);
+int suhmo_hier_postproc_temporal(suhmo_hier_t *H, const suhmo_model_params_t *mp, double *out, suhmo_stream_t s);
+int suhmo_hier_run(suhmo_hier_t **H, const suhmo_model_params_t *mp, const suhmo_hier_schedule_t *sch, suhmo_hier_run_result_t *res,
+                   suhmo_stream_t s);
 
 /* ---- an ENSEMBLE of N independent models on the same grid, stepped together (suhmo_amd/csrc/suhmo_batch.hip): the
  * reference's SHMIP suites are parameter sweeps on one 320 x 64 level (exec/A_SHMIP ... exec/F_SHMIP), far too small to occupy the device.  Every

@@ -70,6 +70,37 @@ class GridParams(C.Structure):
     _fields_ = [("fill_ratio", C.c_double), ("block_factor", C.c_int), ("max_box_size", C.c_int), ("nesting_radius", C.c_int)]
 
 
+class TagSpec(C.Structure):
+    """suhmo_tag_spec_t: a tag variable of a run's regrids, with the levels it tags"""
+    _fields_ = [("field", C.c_int), ("vmin", C.c_double), ("vmax", C.c_double), ("grow", C.c_int), ("grow_x", C.c_int), ("grow_y", C.c_int),
+                ("min_level", C.c_int), ("cap_level", C.c_int)]
+
+
+RELOAD_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int)      # user, the new hierarchy, index of the regrid, cur_step
+
+
+class HierSchedule(C.Structure):
+    """suhmo_hier_schedule_t: the values a run of a hierarchy is driven by (suhmo_hier_run), all host arrays"""
+    _fields_ = [("n_steps", C.c_int), ("dt", C.c_double), ("first_cur_step", C.c_int),
+                ("T_K", C.POINTER(C.c_double)), ("background", C.POINTER(C.c_double)),
+                ("n_moulins", C.c_int), ("positions", C.POINTER(C.c_double)), ("sigma", C.POINTER(C.c_double)), ("flux", C.POINTER(C.c_double)),
+                ("moulin_factor", C.POINTER(C.c_double)), ("ramp", C.POINTER(C.c_double)), ("diag_every", C.c_int),
+                ("regrid_interval", C.c_int), ("skip_first_regrid", C.c_int), ("max_level", C.c_int),
+                ("n_tags", C.c_int), ("tags", C.POINTER(TagSpec)), ("grid", GridParams),
+                ("subset_nbox", C.POINTER(C.c_int)), ("subset_boxes", C.POINTER(C.c_int)),
+                ("n_fields", C.c_int), ("fields", C.POINTER(C.c_int)), ("reload", RELOAD_FN), ("user", C.c_void_p)]
+
+
+class HierRegridLog(C.Structure):
+    _fields_ = [("cur_step", C.c_int), ("same", C.c_int), ("nlev", C.c_int), ("nbox", C.c_int * 8)]
+
+
+class HierRunResult(C.Structure):
+    _fields_ = [("steps_done", C.c_int), ("n_rows", C.c_int), ("picard_iters", C.POINTER(C.c_int)), ("vcycles", C.POINTER(C.c_int)),
+                ("rows", C.POINTER(C.c_double)), ("moulin_steps", C.POINTER(C.c_int)), ("n_regrids", C.c_int), ("regrids_cap", C.c_int),
+                ("regrids", C.POINTER(HierRegridLog)), ("n_moved", C.c_int)]
+
+
 EXCHANGE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int), C.c_int, C.c_void_p)
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(C.c_double))
 REDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(C.c_double), C.c_int, C.c_int)      # values, n, op (0 MAX, 1 SUM)
@@ -106,6 +137,8 @@ SYMBOLS = [
     "suhmo_batch_run", "suhmo_level_postproc_temporal_device",
     "suhmo_hier_tag_cells", "suhmo_hier_clear_tags", "suhmo_hier_get_tags", "suhmo_level_tag_cells", "suhmo_level_clear_tags", "suhmo_level_get_tags",
     "suhmo_grids_generate", "suhmo_hier_generate_grids", "suhmo_hier_regrid",
+    "suhmo_hier_restrict_tags", "suhmo_tag_subsets_nest", "suhmo_hier_get_boxes",
+    "suhmo_hier_time_varying_recharge", "suhmo_hier_postproc_temporal", "suhmo_hier_run",
 ]
 
 
@@ -266,6 +299,12 @@ def lib():
     L.suhmo_grids_generate.argtypes = [ci, ci, ip, C.POINTER(GridParams), ci, C.POINTER(ucp), ip, ip, ip, ci]
     L.suhmo_hier_generate_grids.argtypes = [vp, C.POINTER(GridParams), ip, ip, ip, ci, ip]
     L.suhmo_hier_regrid.argtypes = [vp, ci, ip, ip, ci, ip, C.POINTER(vp), vp]
+    L.suhmo_hier_restrict_tags.argtypes = [vp, ci, ci, ip, vp]
+    L.suhmo_tag_subsets_nest.argtypes = [ci, ip, ip, ip, ip, ci]
+    L.suhmo_hier_get_boxes.argtypes = [vp, ci, ip]
+    L.suhmo_hier_time_varying_recharge.argtypes = [vp, C.c_double, C.c_double, vp]
+    L.suhmo_hier_postproc_temporal.argtypes = [vp, C.POINTER(ModelParams), dp, vp]
+    L.suhmo_hier_run.argtypes = [C.POINTER(vp), C.POINTER(ModelParams), C.POINTER(HierSchedule), C.POINTER(HierRunResult), vp]
     _LIB = L
     return L
 

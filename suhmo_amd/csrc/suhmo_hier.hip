@@ -580,6 +580,14 @@ extern "C" int suhmo_hier_get_option(const suhmo_hier_t *H, const char *key, lon
         return rc;
     }
     if (!strcmp(key, "fused_relax_launches")) { *value = H->n_fused_relax + (H->gap ? H->gap->n_fused_relax : 0); return 0; }
+    if (!strcmp(key, "gap_num_boxes")) {                  // boxes of the levels >= 1 of the gap-height hierarchy of the implicit step; -1: there is none (yet)
+        *value = -1;
+        if (H->gap) { *value = 0; for (int l = 1; l < H->gap->nlev; l++) *value += (long)H->gap->lev[l].box.size(); }
+        return 0;
+    }
+    if (!strcmp(key, "recharge_launches")) { *value = H->n_recharge_launches; return 0; }
+    if (!strcmp(key, "moulin_source_calls")) { *value = H->n_moulin_calls; return 0; }
+    if (!strcmp(key, "run_readbacks")) { *value = H->n_run_readbacks; return 0; }
     if (!strcmp(key, "incremental_residual_passes")) { *value = H->n_incr_residual; return 0; }
     if (!strcmp(key, "residuals_left_by_relax")) { *value = H->n_fused_residual; return 0; }
     if (!strcmp(key, "sparse_gradient_passes")) { *value = H->n_sparse_grad; return 0; }
@@ -633,6 +641,12 @@ extern "C" int suhmo_hier_attach_rccl(suhmo_hier_t *H)
 extern "C" long suhmo_hier_gathers(const suhmo_hier_t *H) { return H ? H->gathers + (H->gap ? H->gap->gathers : 0) : -1; }
 extern "C" int suhmo_hier_num_levels(const suhmo_hier_t *H) { return H ? H->nlev : -1; }
 extern "C" int suhmo_hier_num_boxes(const suhmo_hier_t *H, int l) { return (H && l >= 0 && l < H->nlev) ? (int)H->lev[l].box.size() : -1; }
+extern "C" int suhmo_hier_get_boxes(const suhmo_hier_t *H, int l, int *boxes)
+{
+    ARG(H && l >= 1 && l < H->nlev && boxes);
+    std::copy(H->lev[l].b4.begin(), H->lev[l].b4.end(), boxes);
+    return 0;
+}
 extern "C" suhmo_level_t *suhmo_hier_box(suhmo_hier_t *H, int l, int k)
 {
     if (!H || l < 0 || l >= H->nlev || k < 0 || k >= (int)H->lev[l].box.size()) return nullptr;

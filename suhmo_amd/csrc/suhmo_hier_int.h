@@ -184,6 +184,9 @@ struct suhmo_hier {
     // read-only counters (suhmo_hier_get_option): composite residuals of level 0 evaluated on the dirty rectangles only / not at all (left
     // behind by the launch that ended level 0's V-cycle), coarse gradients evaluated on the cell list only
     long n_incr_residual = 0, n_fused_residual = 0, n_sparse_grad = 0;
+    // launches of suhmo_hier_time_varying_recharge (one per level), calls of suhmo_hier_moulin_source, copies of a run's series to the host
+    // (read-only options recharge_launches, moulin_source_calls, run_readbacks; a run carries them across its regrids)
+    long n_recharge_launches = 0, n_moulin_calls = 0, n_run_readbacks = 0;
     double *red_all = nullptr;                             // partial maxima of a norm over all levels of boxes (64 per box + 16)
     struct suhmo_tagmap *tags[8] = {};                     // tag maps of suhmo_hier_tag_cells, one per level (suhmo_tags.hip), owned
     hier::DevVec<hier::RectEnt> cover_full;                            // coarsen(boxes of level 1) in the shadow: COVER of the whole level 0
@@ -282,3 +285,9 @@ int suhmo_hier_gap_(suhmo_hier *H, const suhmo_model_params_t *mp, double dt, su
 int suhmo_hier_create_on_(suhmo_hier **out, const suhmo_level_desc_t *base, suhmo_level *adopt, int nlev, const int *nbox, const int *boxes, const char *options);
 std::string suhmo_hier_options_(const suhmo_hier *H);                               // the options as they are now, "key=value,..."
 int suhmo_hier_check_(suhmo_hier *H);                                               // what every C-ABI entry of a hierarchy does first
+// ---- suhmo_step.hip: what the run of a hierarchy (suhmo_run.hip) needs of the forcing and the diagnostics
+int suhmo_hier_recharge_check_(suhmo_hier *H, const char *who);                      // rank strips: -5; a box without SUHMO_F_ZS: -1, naming it
+int suhmo_hier_recharge_launch_(suhmo_hier *H, double T_K, double background_input, hipStream_t st);      // one launch per level
+int suhmo_level_postproc_row_check_(suhmo_level *L, const suhmo_model_params_t *mp, bool forcing_writes_source);
+int suhmo_level_postproc_row_launch_(suhmo_level *L, const suhmo_model_params_t *mp, double *cols, double *out6, hipStream_t st);
+int suhmo_step_check_args_(const suhmo_model_params_t *mp, double dt, int cur_step);

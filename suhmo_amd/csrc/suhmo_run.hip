@@ -1,0 +1,197 @@
+// suhmo_run.hip -- AmrHydro::run (src/AmrHydro.cpp:1283-1365) for a hierarchy of box unions in one call: per step the regrid the reference
+// does before it (:1317; tagCells :4514-4536, suhmo_hier_generate_grids, suhmo_hier_regrid), the forcing timeStepFAS evaluates first (seasonal
+// recharge :2846-2863, or the moulin source when m_regrid asks for it, :2802), suhmo_hier_timestep, and the daily row of level 0 finished on the
+// device into a series that comes back in one copy.  The C-ABI and the order: include/suhmo_hip.h, "THE RUN OF A HIERARCHY".  Nothing here
+// computes: every step is one of the public calls (or the launches of one), so the results are the per-call loop's bit for bit.  Eager
+// launches, no graph capture, as suhmo_batch_run.
+#include "suhmo_hier_int.h"
+#include <cstring>
+#include <vector>
+
+using namespace hier;
+
+namespace {
+bool same_bits(double a, double b) { return memcmp(&a, &b, sizeof(double)) == 0; }
+// (c - 1) is the reference's m_cur_step before its increment
+bool regrid_due(const suhmo_hier_schedule_t *sch, int k)
+{
+    const int before = sch->first_cur_step + k - 1;
+    if (sch->regrid_interval <= 0 || before == 0 || before % sch->regrid_interval) return false;
+    return !(k == 0 && sch->skip_first_regrid);
+}
+// the subset of level l: its boxes follow those of the levels below in subset_boxes
+const int *subset_of(const suhmo_hier_schedule_t *sch, int l)
+{
+    const int *q = sch->subset_boxes;
+    for (int m = 0; m < l; m++) q += 4 * (size_t)sch->subset_nbox[m];
+    return q;
+}
+// the body of AmrHydro::regrid on *Hp before the step with cur_step c.  *changed: the hierarchy moved onto other boxes (*Hp is the new handle)
+int run_regrid(suhmo_hier **Hp, const suhmo_hier_schedule_t *sch, int c, suhmo_hier_run_result_t *res, bool *changed, suhmo_stream_t s)
+{
+    suhmo_hier *H = *Hp;
+    const int g = sch->grid.block_factor / 2;
+    int rc;
+    *changed = false;
+    if ((rc = suhmo_hier_clear_tags(H, -1))) return rc;
+    for (int m = 0; m < sch->n_tags; m++) {
+        const suhmo_tag_spec_t &t = sch->tags[m];
+        const int top = std::min(t.cap_level, std::min(sch->max_level - 1, H->nlev - 1)), lo = std::max(t.min_level, 0);
+        for (int l = lo; l <= top; l++) {
+            if ((rc = suhmo_hier_tag_cells(H, l, t.field, t.vmin, t.vmax, t.grow, t.grow_x, t.grow_y, g, s))) return rc;
+            if (sch->subset_nbox && sch->subset_nbox[l] > 0 && (rc = suhmo_hier_restrict_tags(H, l, sch->subset_nbox[l], subset_of(sch, l), s))) return rc;
+        }
+    }
+    int nlev = 0, nbox[9] = {}, same = 0;
+    std::vector<int> boxes(4 * 256);
+    rc = suhmo_hier_generate_grids(H, &sch->grid, &nlev, nbox, boxes.data(), (int)(boxes.size() / 4), &same);
+    if (rc == -4) {
+        long total = 0;
+        for (int l = 1; l < nlev; l++) total += nbox[l];
+        boxes.assign(4 * (size_t)total, 0);
+        rc = suhmo_hier_generate_grids(H, &sch->grid, &nlev, nbox, boxes.data(), (int)total, &same);
+    }
+    if (rc) return rc;
+    // a regrid is logged and counted once it is done: for lists suhmo_hier_create refuses there is no entry, and the hierarchy is the old one
+    const int idx = res->n_regrids;
+    auto log = [&]() {
+        if (res->regrids && idx < res->regrids_cap) {
+            suhmo_hier_regrid_log_t &e = res->regrids[idx];
+            e.cur_step = c; e.same = same; e.nlev = nlev;
+            for (int l = 0; l < 8; l++) e.nbox[l] = l < nlev ? nbox[l] : 0;
+        }
+        res->n_regrids = idx + 1;
+    };
+    if (same) { log(); return 0; }
+    const long carried[3] = {H->n_recharge_launches, H->n_moulin_calls, H->n_run_readbacks};
+    suhmo_hier *N = nullptr;
+    if ((rc = suhmo_hier_regrid(H, nlev, nbox, boxes.data(), sch->n_fields, sch->fields, &N, s))) return rc;      // (H is untouched and usable)
+    N->n_recharge_launches = carried[0]; N->n_moulin_calls = carried[1]; N->n_run_readbacks = carried[2];
+    *Hp = N;
+    *changed = true;
+    log();
+    res->n_moved++;
+    if (sch->reload) {
+        const int r = sch->reload(sch->user, N, idx, c);
+        if (r) { suhmo_set_error("suhmo_hier_run: reload returned %d after regrid %d (before the step with cur_step %d)", r, idx, c); return -1; }
+    }
+    // the seasonal recharge reads SUHMO_F_ZS of every box: the new boxes hold it only when the transfer's field list or `reload` brought it
+    if ((sch->T_K || sch->background) && (rc = suhmo_hier_recharge_check_(N, "suhmo_hier_run: after a regrid"))) return rc;
+    return 0;
+}
+}  // namespace
+
+extern "C" int suhmo_hier_run(suhmo_hier_t **Hp, const suhmo_model_params_t *mp, const suhmo_hier_schedule_t *sch, suhmo_hier_run_result_t *res,
+                              suhmo_stream_t s)
+{
+    SUHMO_TIME("AmrHydro::run");
+    ARG(Hp && *Hp && mp && sch && res);
+    suhmo_hier *H = *Hp;
+    hipStream_t st = HST(s);
+    res->steps_done = 0; res->n_rows = 0; res->n_regrids = 0; res->n_moved = 0;
+    int rc;
+    // ---- everything that can be refused, before anything is launched
+    if (sch->n_steps < 1) { suhmo_set_error("suhmo_hier_run: n_steps = %d (at least 1)", sch->n_steps); return -1; }
+    if (!(sch->dt > 0.0) || sch->first_cur_step < 1 || sch->diag_every < 0) { suhmo_set_error("suhmo_hier_run: dt > 0, first_cur_step >= 1 and diag_every >= 0"); return -1; }
+    if (H->world > 1 || H->part) { suhmo_set_error("suhmo_hier_run: a hierarchy on rank strips (or with levels dealt to the ranks) is not built"); return -5; }
+    const bool recharge = sch->T_K || sch->background;
+    const bool moulins = sch->n_moulins != 0 || sch->positions || sch->sigma || sch->flux || sch->moulin_factor;
+    if (recharge && !(sch->T_K && sch->background)) { suhmo_set_error("suhmo_hier_run: a temperature schedule needs T_K and background"); return -1; }
+    if (moulins && !(sch->n_moulins > 0 && sch->positions && sch->sigma && sch->flux)) {
+        suhmo_set_error("suhmo_hier_run: a moulin schedule needs n_moulins >= 1, positions, sigma and flux"); return -1;
+    }
+    if (recharge && moulins) { suhmo_set_error("suhmo_hier_run: a temperature schedule and a moulin schedule write the same source term (SUHMO_F_MSRC): give one"); return -1; }
+    if (moulins) for (int m = 0; m < sch->n_moulins; m++) if (!(sch->sigma[m] > 0.0)) { suhmo_set_error("suhmo_hier_run: sigma of moulin %d is not positive", m); return -1; }
+    if (sch->regrid_interval < 0) { suhmo_set_error("suhmo_hier_run: regrid_interval = %d", sch->regrid_interval); return -1; }
+    const suhmo_level *B = base_of(H);
+    if (sch->regrid_interval > 0) {
+        if (sch->n_tags < 1 || !sch->tags) { suhmo_set_error("suhmo_hier_run: regrid_interval = %d without tag variables", sch->regrid_interval); return -1; }
+        if (sch->max_level < 1 || sch->max_level > 8) { suhmo_set_error("suhmo_hier_run: max_level = %d (1 .. 8)", sch->max_level); return -1; }
+        if (sch->fields ? (sch->n_fields < 0 || sch->n_fields > 16) : false) { suhmo_set_error("suhmo_hier_run: n_fields = %d (at most 16)", sch->n_fields); return -1; }
+        {   // the grid parameters, as suhmo_grids_generate judges them (a map without tags: nothing is generated)
+            const DV &v = B->d[0].v;
+            std::vector<unsigned char> none((size_t)v.nxg * v.nyg, 0);
+            const unsigned char *ptr = none.data();
+            int nl = 0, nb[2] = {};
+            if ((rc = suhmo_grids_generate(v.nxg, v.nyg, H->bc.periodic, &sch->grid, 1, &ptr, &nl, nb, nullptr, 0))) return rc;
+        }
+        const int g = sch->grid.block_factor / 2;
+        for (int m = 0; m < sch->n_tags; m++) {
+            const suhmo_tag_spec_t &t = sch->tags[m];
+            if (t.field < 0 || t.field >= SUHMO_F_COUNT || t.grow < 0 || t.grow_x < 0 || t.grow_y < 0) { suhmo_set_error("suhmo_hier_run: tag variable %d: field %d, grow %d / %d / %d", m, t.field, t.grow, t.grow_x, t.grow_y); return -1; }
+        }
+        if ((sch->subset_nbox == nullptr) != (sch->subset_boxes == nullptr)) { suhmo_set_error("suhmo_hier_run: tag subsets need subset_nbox and subset_boxes"); return -1; }
+        if (sch->subset_nbox) {
+            const int *q = sch->subset_boxes;
+            for (int l = 0; l < sch->max_level; l++) {
+                if (sch->subset_nbox[l] < 0) { suhmo_set_error("suhmo_hier_run: subset_nbox[%d] = %d", l, sch->subset_nbox[l]); return -1; }
+                for (int k = 0; k < sch->subset_nbox[l]; k++, q += 4)
+                    if (q[0] > q[2] || q[1] > q[3] || q[0] % g || q[1] % g || (q[2] + 1) % g || (q[3] + 1) % g) {
+                        suhmo_set_error("suhmo_hier_run: subset box %d of level %d (%d, %d, %d, %d) is empty or not aligned to block_factor / 2 = %d", k, l, q[0], q[1], q[2], q[3], g);
+                        return -1;
+                    }
+            }
+        }
+    }
+    if (recharge && (rc = suhmo_hier_recharge_check_(H, "suhmo_hier_run"))) return rc;
+    if (mp->use_moulin_source && !recharge && !moulins)
+        for (int l = 0; l < H->nlev; l++)
+            for (size_t k = 0; k < H->lev[l].box.size(); k++)
+                if (!H->lev[l].box[k]->d[0].fp.f[SUHMO_F_MSRC]) {
+                    suhmo_set_error("suhmo_hier_run: use_moulin_source without a source term (level %d, box %d) or a schedule that writes one", l, (int)k); return -1;
+                }
+    if ((rc = suhmo_step_check_args_(mp, sch->dt, sch->first_cur_step))) return rc;
+    const int total_rows = sch->diag_every ? sch->n_steps / sch->diag_every : 0;
+    if (total_rows > 0 && !res->rows) { suhmo_set_error("suhmo_hier_run: %d rows and no array for them", total_rows); return -1; }
+    if (total_rows > 0 && (rc = suhmo_level_postproc_row_check_(base_of(H), mp, recharge || moulins))) return rc;
+    if ((rc = suhmo_hier_check_(H))) return rc;
+    HIPCHK(hipSetDevice(H->device));
+    // ---- the series [rows][6] and the column sums of one row, on the device for the length of the run
+    const size_t ncol = 8 * (size_t)B->d[0].v.nx;
+    double *series = nullptr;
+    if (total_rows > 0) HIPCHK(hipMalloc(&series, (6 * (size_t)total_rows + ncol) * sizeof(double)));
+    double *cols = series ? series + 6 * (size_t)total_rows : nullptr;
+    int rows = 0;
+    rc = 0;
+    for (int k = 0; k < sch->n_steps; k++) {
+        const int c = sch->first_cur_step + k;
+        bool changed = false;
+        // 1. regrid
+        if (regrid_due(sch, k)) {
+            rc = run_regrid(Hp, sch, c, res, &changed, s);
+            H = *Hp;
+            if (rc) break;
+        }
+        // 2. forcing
+        if (recharge && (rc = suhmo_hier_recharge_launch_(H, sch->T_K[k], sch->background[k], st))) break;
+        const double factor = sch->moulin_factor ? sch->moulin_factor[k] : 1.0;
+        const bool form = moulins && (k == 0 || changed || !same_bits(factor, sch->moulin_factor ? sch->moulin_factor[k - 1] : 1.0));
+        if (res->moulin_steps) res->moulin_steps[k] = form;
+        if (form && (rc = suhmo_hier_moulin_source(H, sch->n_moulins, sch->positions, sch->sigma, sch->flux, factor, nullptr, s))) break;
+        // 3. time step
+        suhmo_model_params_t mpk = *mp;
+        if (sch->ramp) mpk.ramp = sch->ramp[k];
+        int pi = 0, nv = 0;
+        if ((rc = suhmo_hier_timestep(H, &mpk, sch->dt, c, &pi, &nv, s))) break;
+        if (res->picard_iters) res->picard_iters[k] = pi;
+        if (res->vcycles) res->vcycles[k] = nv;
+        res->steps_done = k + 1;
+        // 4. diagnostic row
+        if (sch->diag_every && (k + 1) % sch->diag_every == 0) {
+            if ((rc = suhmo_level_postproc_row_launch_(base_of(H), &mpk, cols, series + 6 * (size_t)rows, st))) break;
+            rows++;
+        }
+    }
+    res->n_rows = rows;
+    int rc2 = 0;
+    if (rows > 0) {
+        const std::string msg = rc ? suhmo_last_error() : "";
+        hipError_t e = hipMemcpyAsync(res->rows, series, 6 * (size_t)rows * sizeof(double), hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess) e = hipStreamSynchronize(st);
+        H->n_run_readbacks++;
+        if (e != hipSuccess) { suhmo_set_error("suhmo_hier_run: copy of the series: %s", hipGetErrorString(e)); rc2 = -2; }
+        else if (rc) suhmo_set_error("%s", msg.c_str());
+    } else if (series) (void)hipStreamSynchronize(st);
+    if (series) (void)hipFree(series);
+    return rc ? rc : rc2;
+}

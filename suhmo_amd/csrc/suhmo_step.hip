@@ -447,6 +447,7 @@ static int check_step_args(const suhmo_model_params_t *mp, double dt, int cur_st
     if (mp->use_impl_diff && mp->diffFactor == 0.0) { suhmo_set_error("use_ImplDiff with diffFactor = 0"); return -1; }
     return 0;
 }
+int suhmo_step_check_args_(const suhmo_model_params_t *mp, double dt, int cur_step) { return check_step_args(mp, dt, cur_step); }
 // the Picard test after iteration ite_idx (:3169-3195), given max h and max |h_lagged - h| over the cells no finer level covers
 static int picard_test(double maxHead, double maxd, int ite_idx, int cur_step, const suhmo_model_params_t *mp, bool &converged)
 {
@@ -1321,6 +1322,7 @@ extern "C" int suhmo_hier_moulin_source(suhmo_hier_t *H, int n, const double *po
         ARG(sigma[m] > 0.0);
         h[3 * m] = positions[2 * m]; h[3 * m + 1] = positions[2 * m + 1]; h[3 * m + 2] = sigma[m]; h[3 * (size_t)n + m] = flux[m];
     }
+    H->n_moulin_calls++;
     // owner computes (levels >= 1 dealt to the ranks): a rank integrates and fills the boxes it owns; the per-box integrals of all ranks are
     // gathered and added up in the single-process order (finest level first, box after box), so every rank gets the same bits
     const bool parted = H->part;
@@ -1439,6 +1441,40 @@ extern "C" int suhmo_level_time_varying_recharge(suhmo_level_t *L, double T_K, d
     double *out = suhmo_field(L, 0, SUHMO_F_MSRC);
     if (!out) { suhmo_set_error("field allocation failed"); return -2; }
     return launch_time_varying_recharge_(on_level(L, 0), T_K, background_input, (hipStream_t)s);
+}
+// the same on every box of a hierarchy of box unions (timeStepFAS evaluates it level by level, :2846-2863, with no averaging down and no
+// coarse-fine fill): level 0 as a level, every refined level as ONE launch over its boxes.  Everything is checked before the first launch
+int suhmo_hier_recharge_check_(suhmo_hier *H, const char *who)
+{
+    if (H->world > 1 || H->part) { suhmo_set_error("%s: a hierarchy on rank strips (or with levels dealt to the ranks) is not built", who); return -5; }
+    for (int l = 0; l < H->nlev; l++)
+        for (size_t k = 0; k < H->lev[l].box.size(); k++)
+            if (!H->lev[l].box[k]->d[0].fp.f[SUHMO_F_ZS]) {
+                suhmo_set_error("%s: time-varying recharge: load the ice surface height (SUHMO_F_ZS) of level %d, box %d first", who, l, (int)k);
+                return -1;
+            }
+    return 0;
+}
+int suhmo_hier_recharge_launch_(suhmo_hier *H, double T_K, double background_input, hipStream_t st)
+{
+    int rc;
+    for (int l = 0; l < H->nlev; l++) if ((rc = ensure_field(H, l, SUHMO_F_MSRC))) return rc;
+    if ((rc = launch_time_varying_recharge_(on_level(base_of(H), 0), T_K, background_input, st))) return rc;
+    H->n_recharge_launches++;
+    for (int l = 1; l < H->nlev; l++) {
+        suhmo_multi m;
+        if ((rc = multi_of(H, l, st, m)) || (rc = launch_time_varying_recharge_(m.on(), T_K, background_input, st))) return rc;
+        H->n_recharge_launches++;
+    }
+    return 0;
+}
+extern "C" int suhmo_hier_time_varying_recharge(suhmo_hier_t *H, double T_K, double background_input, suhmo_stream_t s)
+{
+    ARG(H);
+    int rc = suhmo_hier_recharge_check_(H, "suhmo_hier_time_varying_recharge"); if (rc) return rc;
+    if ((rc = suhmo_hier_check_(H))) return rc;
+    HIPCHK(hipSetDevice(H->device));
+    return suhmo_hier_recharge_launch_(H, T_K, background_input, (hipStream_t)s);
 }
 
 // ------------------------------------------------------------------ SHMIP cross-section table
@@ -1597,6 +1633,34 @@ extern "C" int suhmo_level_postproc_temporal_device(suhmo_level_t *L, const suhm
     if (rc) return rc;
     if (e != hipSuccess) { suhmo_set_error("postproc temporal: %s", hipGetErrorString(e)); return -2; }
     return 0;
+}
+// what the two calls above check, and their two launches into device memory the caller owns (cols: 8 nx doubles, out6: 6): a run of a
+// hierarchy (suhmo_run.hip) writes the rows of its series with them, no copy and no synchronisation per row
+int suhmo_level_postproc_row_check_(suhmo_level *L, const suhmo_model_params_t *mp, bool forcing_writes_source)
+{
+    Depth &D = L->d[0];
+    if (L->desc.nx_global > 0) { suhmo_set_error("post-processing table on an AMR patch is not built"); return -5; }
+    if (D.v.ext[0] || D.v.ext[1]) { suhmo_set_error("rank strip: add the strips' suhmo_level_postproc_partial sums, then suhmo_postproc_temporal"); return -5; }
+    if (D.v.nx < 2) { suhmo_set_error("temporal post-processing needs at least two columns"); return -1; }
+    if (mp->use_moulin_source && !forcing_writes_source && !D.fp.f[SUHMO_F_MSRC]) { suhmo_set_error("use_moulin_source without suhmo_level_moulin_source"); return -1; }
+    return 0;
+}
+int suhmo_level_postproc_row_launch_(suhmo_level *L, const suhmo_model_params_t *mp, double *cols, double *out6, hipStream_t st)
+{
+    Depth &D = L->d[0];
+    for (int f : {SUHMO_F_QWX, SUHMO_F_CD, SUHMO_F_MR, SUHMO_F_PW}) if (!D.fp.f[f]) { suhmo_set_error("no time step has run on this level"); return -1; }
+    if (mp->use_moulin_source && !D.fp.f[SUHMO_F_MSRC]) { suhmo_set_error("use_moulin_source without suhmo_level_moulin_source"); return -1; }
+    int rc = launch_postproc_columns_(stepping(on_level(L, 0), *mp), cols, st);
+    if (!rc) rc = launch_postproc_temporal_row_(on_level(L, 0), cols, out6, st);
+    return rc;
+}
+// the daily row of a hierarchy: the reference evaluates it on level 0 ("POST PROC -- 1 LEVEL", src/AmrHydro.cpp:3643-3700); the finer
+// levels enter through what the time step averaged down
+extern "C" int suhmo_hier_postproc_temporal(suhmo_hier_t *H, const suhmo_model_params_t *mp, double *out, suhmo_stream_t s)
+{
+    ARG(H && mp && out);
+    if (H->world > 1) { suhmo_set_error("suhmo_hier_postproc_temporal: a hierarchy on rank strips: add the strips' suhmo_level_postproc_partial sums"); return -5; }
+    return suhmo_level_postproc_temporal_device(base_of(H), mp, out, s);
 }
 extern "C" int suhmo_level_postproc_table(suhmo_level_t *L, const suhmo_model_params_t *mp, double *table, suhmo_stream_t s)
 {

@@ -13,11 +13,13 @@ struct suhmo_tagmap {
     unsigned char *d = nullptr;      // device, [nby][nbx]
     int nbx = 0, nby = 0, g = 0;     // g = 0: empty (allocated or not), takes the granularity of the next call
     size_t cap = 0;
+    int *sub = nullptr; int sub_cap = 0;   // device, the box list of the last suhmo_hier_restrict_tags (4 ints per box)
 };
 void suhmo_tagmap_release(suhmo_tagmap *m)
 {
     if (!m) return;
     if (m->d) (void)hipFree(m->d);
+    if (m->sub) (void)hipFree(m->sub);
     delete m;
 }
 
@@ -37,6 +39,18 @@ __global__ __launch_bounds__(256) void k_tag_cells(T t, int field, double vmin, 
     const int b0 = max(J - gy, 0) / g, b1 = min(J + gy, nyd - 1) / g;
     for (int b = b0; b <= b1; b++)
         for (int a = a0; a <= a1; a++) map[(size_t)b * nbx + a] = 1;
+}
+
+// levelTags &= tagSubset (src/AmrHydro.cpp:4530-4533): one thread per entry of the map; an entry whose first cell lies in none of the boxes
+// (lo0, lo1, hi0, hi1, aligned to g: the entry then lies wholly outside all of them) is cleared with a plain byte store
+__global__ __launch_bounds__(256) void k_restrict_tags(unsigned char *__restrict__ map, int nbx, int nby, int g, const int *__restrict__ boxes, int nboxes)
+{
+    const size_t e = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (e >= (size_t)nbx * nby) return;
+    const int I = (int)(e % nbx) * g, J = (int)(e / nbx) * g;
+    for (int k = 0; k < nboxes; k++)
+        if (I >= boxes[4 * k] && I <= boxes[4 * k + 2] && J >= boxes[4 * k + 1] && J <= boxes[4 * k + 3]) return;
+    map[e] = 0;
 }
 
 int tag_args(int field, int grow, int grow_x, int grow_y, int granularity)
@@ -273,6 +287,75 @@ extern "C" int suhmo_hier_get_tags(suhmo_hier_t *H, int level, unsigned char *ho
 {
     ARG(H && level >= 0 && level < H->nlev);
     return tagmap_get(H->tags[level], H->device, host, nbx, nby);
+}
+
+extern "C" int suhmo_hier_restrict_tags(suhmo_hier_t *H, int level, int nboxes, const int *boxes, suhmo_stream_t s)
+{
+    ARG(H && level >= 0 && level < H->nlev && nboxes >= 0 && (boxes || nboxes == 0));
+    if (H->world > 1) { suhmo_set_error("tags: a hierarchy on rank strips is not built"); return -5; }
+    if (nboxes == 0) return 0;                                   // the reference skips an empty subset
+    suhmo_tagmap *m = H->tags[level];
+    if (!m || !m->g) return 0;                                   // no map: nothing to restrict
+    for (int k = 0; k < nboxes; k++) {
+        const int *b = boxes + 4 * (size_t)k;
+        if (b[0] > b[2] || b[1] > b[3]) { suhmo_set_error("tags: subset box %d of level %d is empty (%d, %d, %d, %d)", k, level, b[0], b[1], b[2], b[3]); return -1; }
+        if (b[0] % m->g || b[1] % m->g || (b[2] + 1) % m->g || (b[3] + 1) % m->g) {
+            suhmo_set_error("tags: subset box %d of level %d (%d, %d, %d, %d) is not aligned to the map's granularity %d: an entry must lie wholly inside or outside",
+                            k, level, b[0], b[1], b[2], b[3], m->g);
+            return -1;
+        }
+    }
+    HIPCHK(hipSetDevice(H->device));
+    if (nboxes > m->sub_cap) {
+        if (m->sub) (void)hipFree(m->sub);                        // (hipFree waits for the launches that read the old list)
+        m->sub = nullptr; m->sub_cap = 0;
+        HIPCHK(hipMalloc(&m->sub, 4 * (size_t)nboxes * sizeof(int)));
+        m->sub_cap = nboxes;
+    }
+    HIPCHK(hipMemcpyAsync(m->sub, boxes, 4 * (size_t)nboxes * sizeof(int), hipMemcpyHostToDevice, HST(s)));
+    HIPCHK(hipStreamSynchronize(HST(s)));                        // the caller's list is pageable memory and may be written again on return; once per
+                                                                 // tag variable and level of a regrid, not on the path of a step
+    const size_t n = (size_t)m->nbx * m->nby;
+    hipLaunchKernelGGL(k_restrict_tags, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, HST(s), m->d, m->nbx, m->nby, m->g, m->sub, nboxes);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+// the per-level subsets as the reference nests them when it reads tagSubsetBoxesFile (src/AmrHydro.cpp:1097-1108), host only: for l >= 1 the
+// NESTED subset of level l - 1 refined by 2, when it is not empty, replaces an empty subset of level l and is intersected with a non-empty one
+extern "C" int suhmo_tag_subsets_nest(int nlev, const int *nbox, const int *boxes, int *nbox_out, int *boxes_out, int boxes_cap)
+{
+    ARG(nlev >= 1 && nlev <= 8 && nbox && nbox_out && boxes_cap >= 0 && (boxes_out || boxes_cap == 0));
+    std::vector<std::vector<int>> sub(nlev);
+    const int *q = boxes;
+    for (int l = 0; l < nlev; l++) {
+        ARG(nbox[l] >= 0 && (boxes || nbox[l] == 0));
+        for (int k = 0; k < nbox[l]; k++, q += 4) {
+            ARG(q[0] <= q[2] && q[1] <= q[3]);
+            sub[l].insert(sub[l].end(), q, q + 4);
+        }
+        if (l == 0 || sub[l - 1].empty()) continue;
+        std::vector<int> crse;
+        for (size_t k = 0; k < sub[l - 1].size(); k += 4) {
+            const int *c = &sub[l - 1][k];
+            crse.insert(crse.end(), {2 * c[0], 2 * c[1], 2 * c[2] + 1, 2 * c[3] + 1});
+        }
+        if (sub[l].empty()) { sub[l] = crse; continue; }
+        std::vector<int> both;
+        for (size_t a = 0; a < sub[l].size(); a += 4)
+            for (size_t c = 0; c < crse.size(); c += 4) {
+                const int lo0 = std::max(sub[l][a], crse[c]), lo1 = std::max(sub[l][a + 1], crse[c + 1]);
+                const int hi0 = std::min(sub[l][a + 2], crse[c + 2]), hi1 = std::min(sub[l][a + 3], crse[c + 3]);
+                if (lo0 <= hi0 && lo1 <= hi1) both.insert(both.end(), {lo0, lo1, hi0, hi1});
+            }
+        sub[l] = both;
+    }
+    long total = 0;
+    for (int l = 0; l < nlev; l++) { nbox_out[l] = (int)(sub[l].size() / 4); total += nbox_out[l]; }
+    if (total > boxes_cap) { suhmo_set_error("tag subsets: %ld boxes after nesting, boxes_cap is %d: call again with room for %ld", total, boxes_cap, total); return -4; }
+    int *o = boxes_out;
+    for (int l = 0; l < nlev; l++) o = std::copy(sub[l].begin(), sub[l].end(), o);
+    return 0;
 }
 
 extern "C" int suhmo_hier_generate_grids(suhmo_hier_t *H, const suhmo_grid_params_t *p, int *nlev_out, int *nbox, int *boxes, int boxes_cap, int *same)

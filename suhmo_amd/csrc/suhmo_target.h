@@ -96,6 +96,7 @@ template <class M> __device__ __forceinline__ const M &row_of(const OnMembers &t
 // copy and no synchronisation maintains it)
 struct PerMember { double x[SUHMO_BATCH_MAX]; };
 __device__ __forceinline__ double value_of(const OnLevel &, double x) { return x; }
+__device__ __forceinline__ double value_of(const OnBoxes &, double x) { return x; }       // (one value for every box of the level)
 __device__ __forceinline__ double value_of(const OnMembers &t, const PerMember &p) { return p.x[t.member()]; }
 
 // ---- the grid of a launch: what the threads of a target's x-y plane stand for

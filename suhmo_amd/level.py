@@ -437,6 +437,36 @@ class HipHier:
         self.boxes, self.nlev = boxes, nlev
         self._bind(h)
 
+    def _adopt(self, h):
+        """h: the handle a grid-changing regrid inside suhmo_hier_run left (the old one is consumed): its box lists are read from it and this
+        object is bound to it, as regrid does"""
+        h = C.c_void_p(h if isinstance(h, int) else h.value)
+        nlev = int(capi.lib().suhmo_hier_num_levels(h))
+        boxes = []
+        for l in range(1, nlev):
+            n = int(capi.lib().suhmo_hier_num_boxes(h, l))
+            flat = (C.c_int * (4 * max(n, 1)))()
+            check(capi.lib().suhmo_hier_get_boxes(h, l, flat))
+            boxes.append([tuple(int(v) for v in flat[4 * k:4 * k + 4]) for k in range(n)])
+        for bl in self.level:
+            for v in bl:
+                v.close()
+        self.boxes, self.nlev = boxes, nlev
+        self._bind(h)
+        self._adopts = getattr(self, "_adopts", 0) + 1
+
+    def run(self, mp, sch, res):
+        """suhmo_hier_run with the structures of capi (mp: ModelParams, sch: HierSchedule, res: HierRunResult with its arrays) -> rc.  After a
+        run that moved the hierarchy onto other boxes (res.n_moved regrids did) this object wraps the new handle (new views, self.boxes,
+        self.nlev), as after regrid.  A `reload` callback of the schedule that works through this object calls _adopt(the handle it is
+        given) first; the run is called after every such regrid, so then nothing is left to do here."""
+        hp = C.c_void_p(self.h.value)
+        before = self._adopts = getattr(self, "_adopts", 0)
+        rc = capi.lib().suhmo_hier_run(C.byref(hp), C.byref(mp), C.byref(sch), C.byref(res), self.stream)
+        if res.n_moved > self._adopts - before:            # the last handle was not adopted by a callback
+            self._adopt(hp)
+        return rc
+
     def owns(self, l, k):
         """this rank computes box k of level l (every box of a replicated level; on a level dealt to the ranks: its own boxes)"""
         return self.owner[l][k] in (-1, self.rank)

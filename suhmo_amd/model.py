@@ -83,6 +83,51 @@ def generate_grids(nx0, ny0, periodic, tags, fill_ratio, block_factor, max_box_s
                      len(maps))
 
 
+def regrid_steps(first_cur_step, n_steps, interval, skip_first=False):
+    """the cur_step values before whose step a run regrids (suhmo_hier_run, rule 1; src/AmrHydro.cpp:1317): c = first_cur_step + k with
+    c - 1 != 0 and (c - 1) % interval == 0 -- c - 1 is the reference's m_cur_step before its increment -- except the run's first step when
+    skip_first is set (m_cur_step != m_restart_step).  interval 0: never."""
+    out = []
+    for k in range(int(n_steps)):
+        c = int(first_cur_step) + k
+        if interval > 0 and c - 1 != 0 and (c - 1) % interval == 0 and not (k == 0 and skip_first):
+            out.append(c)
+    return out
+
+
+def _flat_boxes(levels):
+    """[[(lo0, lo1, hi0, hi1), ...] per level] -> (counts, ints) as the C-ABI takes box lists"""
+    nbox = (C.c_int * max(len(levels), 1))(*[len(bl) for bl in levels])
+    flat = [int(v) for bl in levels for b in bl for v in b]
+    return nbox, (C.c_int * max(len(flat), 1))(*flat)
+
+
+def nest_tag_subsets(subsets):
+    """suhmo_tag_subsets_nest (host only): the per-level tagSubset box lists, level 0 first, nested the way the reference does when it
+    reads tagSubsetBoxesFile (src/AmrHydro.cpp:1097-1108): a level whose list is empty inherits the refined subset of the level below, a
+    level with boxes is intersected with it, and an empty subset below constrains nothing.  -> the nested lists, as restrict_tags /
+    tag_and_regrid / run take them"""
+    subsets = [[tuple(int(v) for v in b) for b in bl] for bl in subsets]
+    nbox, flat = _flat_boxes(subsets)
+    out_n, cap = (C.c_int * max(len(subsets), 1))(), 64
+    while True:
+        out = (C.c_int * (4 * cap))()
+        rc = capi.lib().suhmo_tag_subsets_nest(len(subsets), nbox, flat, out_n, out, cap)
+        if rc == -4 and sum(out_n) > cap:
+            cap = sum(out_n)
+            continue
+        check(rc)
+        break
+    res, q = [], 0
+    for l in range(len(subsets)):
+        res.append([tuple(int(v) for v in out[q + 4 * k:q + 4 * k + 4]) for k in range(out_n[l])])
+        q += 4 * out_n[l]
+    return res
+
+
+ALL_LEVELS = 8          # max_level of a run or a tag_and_regrid that is given none: a hierarchy has at most 8 levels
+
+
 def initial_grids(make_model, tag_specs, params, max_level):
     """The loop of AmrHydro::initGrids (src/AmrHydro.cpp:4835-4955): make_model(boxes) creates a model on the boxes so far and loads its
     initial state -- boxes = [] first: level 0 alone, a HipModel or a HipHierModel without boxes -- every level is tagged with tag_specs
@@ -576,24 +621,167 @@ class HipHierModel:
         L = self.level[l][k]
         if "head" in f:
             L.set(lv.F_PHI, f["head"][1:-1, 1:-1])
-        for key, fid in (("B", lv.F_B), ("Pi", lv.F_PI), ("zb", lv.F_ZB), ("mask", lv.F_MASK)):
+        for key, fid in (("B", lv.F_B), ("Pi", lv.F_PI), ("zb", lv.F_ZB), ("mask", lv.F_MASK), ("zs", lv.F_ZS)):
             if key in f:
                 L.set(fid, f[key], ghosted=True)
 
-    def tag_and_regrid(self, tag_specs, params, reload=None):
-        """The body of AmrHydro::regrid (src/AmrHydro.cpp:4227-4511): the tag maps are emptied, every level is tagged with tag_specs (dicts of
-        tag_cells' arguments without the level: name, vmin, vmax, grow, grow_dir), grids are generated with params (generate_grids' keywords)
-        and, when they are not the hierarchy's own (gridsSame), the fields move onto them (regrid).  Returns (boxes, same); with same = True
-        the handle is not touched."""
+    def tag_and_regrid(self, tag_specs, params, reload=None, subsets=None, max_level=None, fields=None):
+        """The body of AmrHydro::regrid (src/AmrHydro.cpp:4227-4511): the tag maps are emptied, every tag variable of tag_specs (dicts of
+        tag_cells' arguments without the level: name, vmin, vmax, grow, grow_dir; and min_level, cap_level: the levels it tags, default all)
+        tags the levels max(min_level, 0) .. min(cap_level, max_level - 1, finest level) (tagCells, :4514-4536), each followed by
+        restrict_tags with subsets[l] where that list is not empty (subsets: per level, level 0 first, nested: nest_tag_subsets); grids are
+        generated with params (generate_grids' keywords) and, when they are not the hierarchy's own (gridsSame), the fields move onto them
+        (regrid).  Returns (boxes, same); with same = True the handle is not touched."""
         g = int(params["block_factor"]) // 2
         self.clear_tags()
-        for l in range(self.hier.nlev):
-            for sp in tag_specs:
+        for sp in tag_specs:
+            sp = dict(sp)
+            lo, cap = max(int(sp.pop("min_level", 0)), 0), sp.pop("cap_level", None)
+            top = min(self.hier.nlev - 1, (ALL_LEVELS if max_level is None else int(max_level)) - 1)
+            top = top if cap is None else min(top, int(cap))
+            for l in range(lo, top + 1):
                 self.tag_cells(l, granularity=g, **sp)
+                if subsets is not None and l < len(subsets) and subsets[l]:
+                    self.restrict_tags(l, subsets[l])
         boxes, same = self.generate_grids(**params)
         if not same:
-            self.regrid(boxes, reload=reload)
+            self.regrid(boxes, reload=reload, fields=fields)
         return boxes, same
+
+    def restrict_tags(self, level, boxes):
+        """levelTags &= tagSubset (suhmo_hier_restrict_tags): every entry of the tag map of `level` that lies in none of `boxes`
+        ((lo0, lo1, hi0, hi1) in cells of that level, aligned to the map's granularity) is cleared; an empty list is a no-op"""
+        boxes = [tuple(int(v) for v in b) for b in boxes]
+        _, flat = _flat_boxes([boxes])
+        check(capi.lib().suhmo_hier_restrict_tags(self.hier.h, int(level), len(boxes), flat, self.hier.stream))
+
+    def set_surface(self, l, k, zs):
+        """the ghosted ice surface height of box k of level l (F_ZS): loaded once, it stays on the device for time_varying_recharge"""
+        self.level[l][k].set(lv.F_ZS, zs, ghosted=True)
+
+    def time_varying_recharge(self, T_K, background):
+        """F_MSRC of every box from its surface height (suhmo_hier_time_varying_recharge): one launch per level"""
+        check(capi.lib().suhmo_hier_time_varying_recharge(self.hier.h, float(T_K), float(background), self.hier.stream))
+
+    def postproc_temporal(self):
+        """the daily row (6 values) of the run: level 0's, as the reference evaluates it (suhmo_hier_postproc_temporal)"""
+        out = np.zeros(6)
+        check(capi.lib().suhmo_hier_postproc_temporal(self.hier.h, C.byref(self._mp), out.ctypes.data_as(C.POINTER(C.c_double)), self.hier.stream))
+        return out
+
+    def run(self, n_steps, dt, T_K=None, background=None, moulins=None, moulin_factor=None, ramp=None, diag_every=0, regrid_interval=0,
+            tag_specs=None, params=None, subsets=None, max_level=None, reload=None, skip_first_regrid=False, fields=None):
+        """AmrHydro::run in ONE call (suhmo_hier_run): per step the regrid the reference does before it (every regrid_interval steps:
+        regrid_steps(self.cur_step + 1, n_steps, regrid_interval, skip_first_regrid) lists them; tag_and_regrid's arguments tag_specs, params,
+        subsets, max_level, fields), the forcing, the time step and, after every diag_every-th step, the daily row finished on the device; the
+        rows come back in one copy.  Bit for bit what tag_and_regrid, time_varying_recharge / moulin_source, timestep and postproc_temporal
+        give step by step.
+        T_K, background: (n_steps,) or scalars, VALUES: the seasonal recharge of every step.  moulins: dict or tuple of positions, sigma, flux,
+        given once; moulin_factor (n_steps,) or None (1.0): the moulin source is formed at the first step, after a regrid that moved boxes
+        and where the factor's bits differ from the step before.  ramp: (n_steps,).
+        reload(l, k, box) -> dict as regrid's reload (and "zs": the ghosted surface height): called for every box of the new hierarchy after a
+        regrid that moved boxes; an exception it raises ends the run and is raised again after the bookkeeping.
+        With T_K the surface height (set_surface) must reach the new boxes of every such regrid: fields = None or a list with "zs" transfers
+        it, or reload returns "zs" for EVERY box.  Otherwise the run ends at that regrid with SuhmoError rc -1 naming the box, before anything
+        is launched on the new hierarchy; the steps before it are done, the model wraps the new hierarchy and goes on once the surface is loaded.
+        Returns (picard iterations (n_steps,), V-cycles (n_steps,), rows (n_steps // diag_every, 6), log) with log = one dict per regrid:
+        cur_step, same, boxes_per_level.  self.last_run: steps_done, n_rows, moulin_steps (n_steps,).  cur_step advances by the steps done;
+        after a regrid that moved boxes self.hier wraps the new handle and self.level holds the new boxes' views."""
+        n_steps, diag_every = int(n_steps), int(diag_every)
+        ns = max(n_steps, 0)
+        dp = lambda a: a.ctypes.data_as(C.POINTER(C.c_double))
+        ip = lambda a: a.ctypes.data_as(C.POINTER(C.c_int))
+        keep = []
+
+        def per_step(x, what):
+            a = np.asarray(x, dtype=np.float64)
+            if a.ndim == 1 and a.shape != (ns,):
+                raise ValueError("%s has shape %s, the run needs (n_steps,) = (%d,)" % (what, a.shape, ns))
+            a = np.ascontiguousarray(np.broadcast_to(a, (ns,)))
+            keep.append(a)
+            return dp(a)
+
+        sch = capi.HierSchedule(n_steps=n_steps, dt=float(dt), first_cur_step=self.cur_step + 1, diag_every=diag_every,
+                                regrid_interval=int(regrid_interval), skip_first_regrid=int(bool(skip_first_regrid)),
+                                max_level=ALL_LEVELS if max_level is None else int(max_level))
+        if (T_K is None) != (background is None):
+            raise ValueError("the seasonal recharge needs T_K and background")
+        if T_K is not None:
+            sch.T_K, sch.background = per_step(T_K, "T_K"), per_step(background, "background")
+        if moulins is None and moulin_factor is not None:
+            raise ValueError("moulin_factor without moulins")
+        if moulins is not None:
+            pos, sg, fl = (moulins[q] for q in ("positions", "sigma", "flux")) if isinstance(moulins, dict) else moulins
+            pos = np.ascontiguousarray(pos, dtype=np.float64).reshape(-1)
+            sg, fl = np.ascontiguousarray(sg, dtype=np.float64).reshape(-1), np.ascontiguousarray(fl, dtype=np.float64).reshape(-1)
+            assert pos.size == 2 * sg.size and fl.size == sg.size
+            keep += [pos, sg, fl]
+            sch.n_moulins, sch.positions, sch.sigma, sch.flux = sg.size, dp(pos), dp(sg), dp(fl)
+            if moulin_factor is not None:
+                sch.moulin_factor = per_step(moulin_factor, "moulin_factor")
+        if ramp is not None:
+            r = np.ascontiguousarray(ramp, dtype=np.float64)
+            if r.shape != (ns,):
+                raise ValueError("ramp has shape %s, the run needs (n_steps,) = (%d,)" % (r.shape, ns))
+            keep.append(r)
+            sch.ramp = dp(r)
+        if tag_specs:
+            tg = (capi.TagSpec * len(tag_specs))()
+            for q, sp in enumerate(tag_specs):
+                cap = sp.get("cap_level")
+                tg[q] = capi.TagSpec(_tag_field(self.FIELDS, sp["name"]), float(sp["vmin"]), float(sp["vmax"]),
+                                     *_tag_reach(sp.get("grow", 0), sp.get("grow_dir", (0, 0))), int(sp.get("min_level", 0)),
+                                     2 ** 30 if cap is None else int(cap))
+            keep.append(tg)
+            sch.n_tags, sch.tags = len(tag_specs), tg
+        if params is not None:
+            sch.grid = capi.GridParams(float(params["fill_ratio"]), int(params["block_factor"]), int(params["max_box_size"]),
+                                       int(params.get("nesting_radius", 2)))
+        if subsets is not None:
+            per = [list(subsets[l]) if l < len(subsets) else [] for l in range(max(sch.max_level, 1))]
+            nb, flat = _flat_boxes(per)
+            keep += [nb, flat]
+            sch.subset_nbox, sch.subset_boxes = nb, flat
+        if fields is not None:
+            ids = (C.c_int * max(len(fields), 1))(*[f if isinstance(f, int) else (lv.F_ZS if f == "zs" else self.FIELDS[f]) for f in fields])
+            keep.append(ids)
+            sch.n_fields, sch.fields = len(fields), ids
+        raised = []
+
+        def on_regrid(user, hnew, index, cur_step):
+            try:
+                self.hier._adopt(hnew)
+                self.level = self.hier.level
+                if reload is not None:
+                    for l, bl in enumerate(self.hier.boxes, start=1):
+                        for k, b in enumerate(bl):
+                            f = reload(l, k, b)
+                            if f:
+                                self._load(l, k, f)
+                return 0
+            except BaseException as e:           # (an exception must not travel through the C frames)
+                raised.append(e)
+                return 1
+
+        cb = capi.RELOAD_FN(on_regrid)
+        sch.reload = cb
+        n_rows = n_steps // diag_every if diag_every > 0 and n_steps > 0 else 0
+        rows = np.zeros((n_rows, 6))
+        pi, nv, ms = np.zeros(ns, dtype=np.intc), np.zeros(ns, dtype=np.intc), np.zeros(ns, dtype=np.intc)
+        log = (capi.HierRegridLog * max(ns, 1))()
+        res = capi.HierRunResult(picard_iters=ip(pi), vcycles=ip(nv), rows=dp(rows) if n_rows else None, moulin_steps=ip(ms), regrids_cap=max(ns, 1),
+                                 regrids=log)
+        rc = self.hier.run(self._mp, sch, res)
+        self.level = self.hier.level
+        self.cur_step += res.steps_done
+        if ramp is not None and res.steps_done > 0:            # the model's ramp is the last step's, as a loop that sets it leaves it
+            self._mp.ramp = float(r[res.steps_done - 1])
+        self.last_run = dict(steps_done=int(res.steps_done), n_rows=int(res.n_rows), moulin_steps=ms, n_moved=int(res.n_moved))
+        if raised:
+            raise raised[0]
+        check(rc)
+        return pi, nv, rows[:res.n_rows], [dict(cur_step=int(e.cur_step), same=bool(e.same), boxes_per_level=[int(e.nbox[l]) for l in range(1, e.nlev)])
+                                            for e in log[:res.n_regrids]]
 
     def get(self, l, k, name, ghosted=False):
         """a field of box k of level l; None where another rank owns the box (levels dealt to the ranks: hier.owns(l, k))"""

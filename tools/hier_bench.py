@@ -1,11 +1,18 @@
 #!/usr/bin/env python3
 """cfg5 (exec/AMR_multiMoulins physics) time step on base + 3 AMR levels of box unions: ms per step.
-    python tools/hier_bench.py [--generated-grids] [--regrid-interval N] [base cells per side] [steps]
+    python tools/hier_bench.py [--generated-grids] [--regrid-interval N [--one-call]] [--recharge] [base cells per side] [steps]
+--one-call (with --regrid-interval N): the same regridding time loop twice in one process, on two models set up alike -- the per-call loop
+(HipHierModel.tag_and_regrid, moulin_source, timestep) and HipHierModel.run (suhmo_hier_run: one call per stretch of steps that begins with a
+regrid, so that the thresholds can alternate as below) -- in alternating rounds of [steps] steps; prints ms per step and ms per regrid interval of
+either for every round and the spread over the rounds, and compares the two models' fields bit for bit at the end.
 --regrid-interval N: the time loop regrids every N steps as AmrHydro::regrid does (HipHierModel.tag_and_regrid's body, with the per-level tag
 thresholds of --generated-grids; the thresholds alternate between two sets, so that every regrid moves boxes) and prints, per regrid, the times of
 tagging, clustering, hierarchy creation, the transfer's plans and launches, the moulin source term on the new boxes and the steps around it --
 and, for the first regrid, what the same move costs through the host (all fields read back, the interpolation in numpy, a new model created and
 loaded: what a caller can do without suhmo_hier_regrid), its valid cells compared with the device's bit for bit.
+--recharge: instead of stepping, the seasonal recharge on the hierarchy's boxes: HipHierModel.time_varying_recharge (suhmo_hier_time_varying_recharge,
+one launch per level) against suhmo_level_time_varying_recharge on every box handle, 50 evaluations between two synchronisations, three alternating
+repetitions (with --generated-grids 256: run_C_3lev's 42 + 56 + 59 boxes).
 --generated-grids: the hierarchy is made the reference's way instead of synthetic.boxes_around -- a level per pass of the initGrids loop, by tagging
 the moulin source term on the device (suhmo_hier_tag_cells) and clustering the tags (suhmo_grids_generate) with run_C_3lev's fill_ratio,
 block_factor, max_box_size, nestingRadius and tags_grow; the time of tagging, copy-out and generation is reported per level."""
@@ -13,7 +20,9 @@ import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from suhmo_amd import model, synthetic as sy
 generated = "--generated-grids" in sys.argv
-argv = [a for a in sys.argv[1:] if a != "--generated-grids"]
+one_call = "--one-call" in sys.argv
+recharge = "--recharge" in sys.argv
+argv = [a for a in sys.argv[1:] if a not in ("--generated-grids", "--one-call", "--recharge")]
 regrid_interval = 0
 if "--regrid-interval" in argv:
     q = argv.index("--regrid-interval")
@@ -185,6 +194,96 @@ def timed_regrid(H, n, first):
 
 boxes = generated_boxes() if generated else sy.boxes_around(mo["positions"], nb, nb, 4, 1.0e5, 1.0e5)
 sts = sy.mountain_amrm_states(nb, nb, boxes)
+
+
+def one_call_rounds(rounds=3):
+    """the regridding loop through the per-call methods and through HipHierModel.run, alternating"""
+    import numpy as np
+    def setup():
+        M = model.HipHierModel(nb, nb, sts[0][0]["dx"], sts[0][0]["dy"], bc, ph, mm, boxes, max_box=64)
+        M.set_states(sts)
+        M.moulin_source(**mo)
+        for _ in range(3):
+            M.timestep(mm["dt"])
+        M.level[0][0].synchronize()
+        return M
+    P, R = setup(), setup()
+    peak = float(P.get(0, 0, "msrc").max())
+    # a tag variable per level (min_level = cap_level = l) with that level's threshold; the two sets alternate from regrid to regrid
+    specs = lambda n: [dict(name="msrc", vmin=(1.0, 0.6)[n % 2] * f * peak, vmax=1.0e300, grow=4, min_level=l, cap_level=l) for l, f in enumerate((0.01, 0.1, 0.5))]
+    def stretches(M):
+        due = model.regrid_steps(M.cur_step + 1, nstep, regrid_interval)
+        cuts = [M.cur_step + 1] + [c for c in due if c != M.cur_step + 1] + [M.cur_step + 1 + nstep]
+        return due, [(a, b - a) for a, b in zip(cuts[:-1], cuts[1:])]
+    def per_call(M):
+        due, _ = stretches(M)
+        moved = 0
+        for k in range(nstep):
+            c = M.cur_step + 1
+            if c in due:
+                moved += not M.tag_and_regrid(specs((c - 1) // regrid_interval), GRID_PARAMS, max_level=3)[1]
+            if k == 0 or c in due:                 # where the calls of run() below form it: their first step
+                M.moulin_source(**mo)
+            M.timestep(mm["dt"])
+        return len(due), moved
+    def run(M):
+        due, parts = stretches(M)
+        moved = 0
+        for c, n in parts:
+            log = M.run(n, mm["dt"], moulins=mo, regrid_interval=regrid_interval, tag_specs=specs((c - 1) // regrid_interval), params=GRID_PARAMS, max_level=3)[3]
+            moved += sum(not e["same"] for e in log)
+        return len(due), moved
+    ms = {"per-call loop": [], "one call": []}
+    for r in range(rounds):
+        for name, fn, M in (("per-call loop", per_call, P), ("one call", run, R)) if r % 2 == 0 else (("one call", run, R), ("per-call loop", per_call, P)):
+            M.level[0][0].synchronize()
+            t0 = time.perf_counter()
+            nreg, moved = fn(M)
+            M.level[0][0].synchronize()
+            t = time.perf_counter() - t0
+            ms[name].append(1e3 * t / nstep)
+            print("round %d, %-13s: %.2f ms per step, %.2f ms per interval of %d steps (regrids included: %d, %d moved boxes), boxes per level %s"
+                  % (r, name, 1e3 * t / nstep, 1e3 * t / nstep * regrid_interval, regrid_interval, nreg, moved, [len(b) for b in M.hier.boxes]), flush=True)
+    for name, v in ms.items():
+        print("%-13s: ms per step over the rounds: min %.2f, median %.2f, max %.2f (spread %.2f)" % (name, min(v), sorted(v)[len(v) // 2], max(v), max(v) - min(v)))
+    eq = P.hier.boxes == R.hier.boxes and all(np.array_equal(P.get(l, k, nm, ghosted=True), R.get(l, k, nm, ghosted=True), equal_nan=True)
+                                              for l, bl in enumerate(P.level) for k in range(len(bl)) for nm in ("head", "B", "mR", "Pw", "msrc"))
+    print("the two models after %d steps each: boxes and fields (head, B, mR, Pw, msrc; ghosted) bitwise equal: %s" % (rounds * nstep, eq))
+    P.close(); R.close()
+
+
+def recharge_bench(evals=50, reps=3):
+    """the hierarchy's recharge call against the per-box level calls"""
+    import numpy as np
+    from suhmo_amd import capi
+    M = model.HipHierModel(nb, nb, sts[0][0]["dx"], sts[0][0]["dy"], bc, ph, mm, boxes, max_box=64)
+    for l, bl in enumerate(M.level):
+        for k, L in enumerate(bl):
+            M.set_surface(l, k, np.random.default_rng([l, k]).uniform(0.0, 2000.0, size=(L.ny + 2, L.nx + 2)))
+    sync, lib = M.level[0][0].synchronize, capi.lib()
+    def per_box():
+        for bl in M.level:
+            for L in bl:
+                capi.check(lib.suhmo_level_time_varying_recharge(L.h, 7.5, 1.0e-9, L.stream))
+    nbx = sum(len(bl) for bl in M.level)
+    print("recharge: boxes per level %s, %d handles with level 0" % ([len(b) for b in boxes], nbx), flush=True)
+    for name, fn in (("hierarchy call", lambda: M.time_varying_recharge(7.5, 1.0e-9)), ("per-box calls", per_box)) * reps:
+        fn(); sync()
+        t0 = time.perf_counter()
+        for _ in range(evals):
+            fn()
+        sync()
+        print("%-15s %.3f ms per evaluation of all %d boxes" % (name, 1e3 * (time.perf_counter() - t0) / evals, nbx), flush=True)
+    M.close()
+
+
+if recharge:
+    recharge_bench()
+    sys.exit(0)
+if one_call:
+    assert regrid_interval > 0, "--one-call needs --regrid-interval"
+    one_call_rounds()
+    sys.exit(0)
 t0 = time.perf_counter()
 H = model.HipHierModel(nb, nb, sts[0][0]["dx"], sts[0][0]["dy"], bc, ph, mm, boxes, max_box=64)
 H.set_states(sts)
