@@ -723,6 +723,70 @@ int suhmo_hier_postproc_temporal(suhmo_hier_t *H, const suhmo_model_params_t *mp
 int suhmo_hier_run(suhmo_hier_t **H, const suhmo_model_params_t *mp, const suhmo_hier_schedule_t *sch, suhmo_hier_run_result_t *res,
                    suhmo_stream_t s);
 
+/* ---- SNAPSHOT (suhmo_amd/csrc/suhmo_snap.hip; DESIGN.md section 5, "Output of a run"; tests/snapshot_ref.py is the numpy twin of this text): a list of
+ * fields of a whole hierarchy gathered on the device into the order Chombo writes a LevelData to disk -- what AmrHydro::writePlotFile and
+ * writeCheckpointFile (src/AmrHydro.cpp:5474-5667, 5670-5842) hand to HDF5 -- with ONE launch and ONE copy per level, whatever the number of boxes.
+ * LAYOUT.  Per level the boxes come in the hierarchy's order; level 0 is the single box (0, 0, nx0 - 1, ny0 - 1).  Box k grown by `ghost` (0 or 1)
+ * is ncomp x (ny_k + 2 ghost) x (nx_k + 2 ghost) doubles ordered [comp][j][i], i fastest; boxes follow one another and levels follow one another.
+ * A level's slice is exactly the "data:datatype=0" dataset of a Chombo LevelData with ncomp components.  box_offset holds, per level, the nbox + 1
+ * prefix sums in doubles (the "data:offsets=0" dataset; total boxes + nlev entries in all, level 0's two first); level_offset[l] is where level l
+ * starts in host_dst and level_offset[nlev] the doubles in all.  host_dst == NULL fills the offsets only: nothing is launched and the device is
+ * not touched.
+ * COMPONENTS (at most SUHMO_SNAP_MAX_COMPS), each {kind, field, value}:
+ *   SUHMO_SNAP_FIELD         a cell-centred SUHMO_F_*: bit for bit what suhmo_level_get_field with ghosted = 1 returns for that box, ghost ring included
+ *                            (its interior for ghost = 0) -- the head wherever the relaxation left it, on either of its two canvases.  A field the box does
+ *                            not hold is written as 0.0; nothing is allocated: a snapshot does not change what a box holds.
+ *   SUHMO_SNAP_FACE_TO_CELL  a face field (QWX, QWY, BX, BY, DCX, DCY) averaged to cells as EdgeToCell does, 0.5 * (lo + hi), in VALID cells; ghost cells are
+ *                            0.0.  This is m_qw of src/AmrHydro.cpp:3281-3287 before its ghost fills.  DEVIATION: the reference fills the ghost cells of
+ *                            Qw_x / Qw_y before it plots them (:3290-3300); here they stay 0.0.
+ *   SUHMO_SNAP_CONST         `value` everywhere.
+ * One body and one kernel template over the launch target: level 0 (and suhmo_level_snapshot: a single level handle, whole, as the one box) as a
+ * level, every refined level as one launch over its boxes, blockIdx.z = box.  The component list travels by value; the per-box offsets are a device
+ * table the hierarchy owns.  Thread (i, j) loops over the components: loads and stores are contiguous in i.  Plain vector stores.  Each level goes
+ * into a device staging buffer and from there in one hipMemcpyAsync into host_dst; one stream synchronisation ends the call.  Read-only options
+ * snapshot_launches and snapshot_copies count them (nlev each per snapshot); a run carries them over its regrids.
+ * MEMORY.  The staging is the largest level's packed size over the snapshots so far, allocated on first use, owned by the hierarchy and freed with
+ * it.  13 components with ghost 1 cost 6.9 MB for a 256 x 256 base and 1.75 GB for the 4096 x 4096 base (level 0's packed size; a refined level
+ * whose boxes hold more cells than level 0 costs what they hold).  A caller who cannot afford that snapshots fewer components per call.  suhmo_level_snapshot allocates its
+ * staging for the call.  The per-box offset tables: 8 B per box and ghost width.
+ * REFUSED before anything is launched, host_dst untouched.  rc -1: ncomp outside 1 .. 16, ghost other than 0 or 1, an unknown kind, a field id out
+ * of range, a face field as SUHMO_SNAP_FIELD or a cell field as SUHMO_SNAP_FACE_TO_CELL, SUHMO_F_COVER / SUHMO_F_PHI2 named directly.  rc -5: a rank
+ * strip, levels dealt to the ranks, a hierarchy created with shadow = 1. */
+enum { SUHMO_SNAP_FIELD = 0, SUHMO_SNAP_FACE_TO_CELL = 1, SUHMO_SNAP_CONST = 2 };
+#define SUHMO_SNAP_MAX_COMPS 16
+typedef struct suhmo_snap_comp { int kind, field; double value; } suhmo_snap_comp_t;
+int suhmo_hier_snapshot(suhmo_hier_t *H, int ncomp, const suhmo_snap_comp_t *comps, int ghost, long *level_offset /* [nlev + 1] */,
+                        long *box_offset /* [total boxes + nlev] */, double *host_dst, suhmo_stream_t s);
+int suhmo_level_snapshot(suhmo_level_t *L, int ncomp, const suhmo_snap_comp_t *comps, int ghost, long *ndoubles, double *host_dst, suhmo_stream_t s);
+
+/* ---- OUTPUT INSIDE THE RUN (suhmo_amd/csrc/suhmo_run.hip): suhmo_hier_run_out is suhmo_hier_run with the plot files and checkpoints AmrHydro::run
+ * writes (src/AmrHydro.cpp:1311-1336, 1343-1358); suhmo_hier_run is the same call with out = NULL.  With b = c - 1, the reference's m_cur_step before
+ * step c:
+ *   1. PLOT when plot_interval > 0 and b % plot_interval == 0 (:1311) -- b = 0 included: the initial state;
+ *   2. the REGRID of suhmo_hier_run's rule 1 (:1317);
+ *   3. CHECKPOINT when check_interval > 0, b % check_interval == 0 and b != restart_step (:1327; m_restart_step is 0 in a fresh run, :806);
+ *   4. the forcing, the step and the row, as suhmo_hier_run does them.
+ * After the last step (:1343-1358), unless no_final is set (a run that another run continues): a plot with cur_step = the last c when plot_interval
+ * >= 0 and a checkpoint when check_interval >= 0, each once.  So at a b where all three fall together the plot shows the OLD boxes and the
+ * checkpoint the NEW ones.  An interval of -1 switches that kind of output off altogether, 0 leaves only the final file.
+ * Each event is one snapshot (ghost 1) of the component list of its kind into a pinned host buffer the run owns, then
+ * write(user, *H, kind, cur_step, ncomp, level_offset, box_offset, data) with the current handle (its boxes: suhmo_hier_get_boxes); cur_step is the
+ * reference's m_cur_step in the file name, b before a step and the last c after the run.  The pointers are valid during the call only.  The library
+ * links no HDF5: writing is the callback's business (suhmo_amd.plotfile, suhmo_amd.checkpoint).  A callback that returns non-zero ends the run with
+ * rc -1, its value in the message: steps_done is exact, the rows so far are copied out and *H is usable.  Checked before the first launch, rc -1: an
+ * interval below -1; an interval >= 0 without a component list or without a callback; a list the snapshot would refuse (its rc).
+ * The plots and checkpoints the last run handed to its callback: read-only options run_plots and run_checkpoints. */
+typedef int (*suhmo_hier_output_fn)(void *user, suhmo_hier_t *H, int kind /* 0 plot, 1 checkpoint */, int cur_step /* m_cur_step of the file name */,
+                                    int ncomp, const long *level_offset, const long *box_offset, const double *data);
+typedef struct suhmo_hier_output {
+    int plot_interval, check_interval, restart_step, no_final;
+    int n_plot; const suhmo_snap_comp_t *plot;
+    int n_check; const suhmo_snap_comp_t *check;
+    suhmo_hier_output_fn write; void *user;
+} suhmo_hier_output_t;
+int suhmo_hier_run_out(suhmo_hier_t **H, const suhmo_model_params_t *mp, const suhmo_hier_schedule_t *sch, const suhmo_hier_output_t *out,
+                       suhmo_hier_run_result_t *res, suhmo_stream_t s);
+
 /* ---- an ENSEMBLE of N independent models on the same grid, stepped together (suhmo_amd/csrc/suhmo_batch.hip): the
  * reference's SHMIP suites are parameter sweeps on one 320 x 64 level (exec/A_SHMIP ... exec/F_SHMIP), far too small to occupy the device.  Every
  * kernel launch of a batch call serves all members that still have work and ONE read-back per V-cycle carries all their residual norms; each

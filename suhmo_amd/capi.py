@@ -101,6 +101,32 @@ class HierRunResult(C.Structure):
                 ("regrids", C.POINTER(HierRegridLog)), ("n_moved", C.c_int)]
 
 
+class SnapComp(C.Structure):
+    """suhmo_snap_comp_t: one component of a snapshot"""
+    _fields_ = [("kind", C.c_int), ("field", C.c_int), ("value", C.c_double)]
+
+
+SNAP_FIELD, SNAP_FACE_TO_CELL, SNAP_CONST = 0, 1, 2
+SNAP_MAX_COMPS = 16
+# user, the hierarchy, kind (0 plot, 1 checkpoint), cur_step, ncomp, level_offset, box_offset, data
+OUTPUT_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_long), C.POINTER(C.c_long), C.POINTER(C.c_double))
+
+
+class HierOutput(C.Structure):
+    """suhmo_hier_output_t: the plot files and checkpoints of a run (suhmo_hier_run_out)"""
+    _fields_ = [("plot_interval", C.c_int), ("check_interval", C.c_int), ("restart_step", C.c_int), ("no_final", C.c_int),
+                ("n_plot", C.c_int), ("plot", C.POINTER(SnapComp)), ("n_check", C.c_int), ("check", C.POINTER(SnapComp)),
+                ("write", OUTPUT_FN), ("user", C.c_void_p)]
+
+
+def snap_comps(comps):
+    """[(kind, field, value) or (kind, field) or SnapComp] -> a C array of suhmo_snap_comp_t"""
+    arr = (SnapComp * max(len(comps), 1))()
+    for q, c in enumerate(comps):
+        arr[q] = c if isinstance(c, SnapComp) else SnapComp(int(c[0]), int(c[1]), float(c[2]) if len(c) > 2 else 0.0)
+    return arr
+
+
 EXCHANGE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int), C.c_int, C.c_void_p)
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(C.c_double))
 REDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(C.c_double), C.c_int, C.c_int)      # values, n, op (0 MAX, 1 SUM)
@@ -139,6 +165,7 @@ SYMBOLS = [
     "suhmo_grids_generate", "suhmo_hier_generate_grids", "suhmo_hier_regrid",
     "suhmo_hier_restrict_tags", "suhmo_tag_subsets_nest", "suhmo_hier_get_boxes",
     "suhmo_hier_time_varying_recharge", "suhmo_hier_postproc_temporal", "suhmo_hier_run",
+    "suhmo_hier_snapshot", "suhmo_level_snapshot", "suhmo_hier_run_out",
 ]
 
 
@@ -305,6 +332,10 @@ def lib():
     L.suhmo_hier_time_varying_recharge.argtypes = [vp, C.c_double, C.c_double, vp]
     L.suhmo_hier_postproc_temporal.argtypes = [vp, C.POINTER(ModelParams), dp, vp]
     L.suhmo_hier_run.argtypes = [C.POINTER(vp), C.POINTER(ModelParams), C.POINTER(HierSchedule), C.POINTER(HierRunResult), vp]
+    lp = C.POINTER(C.c_long)
+    L.suhmo_hier_snapshot.argtypes = [vp, ci, C.POINTER(SnapComp), ci, lp, lp, dp, vp]
+    L.suhmo_level_snapshot.argtypes = [vp, ci, C.POINTER(SnapComp), ci, lp, dp, vp]
+    L.suhmo_hier_run_out.argtypes = [C.POINTER(vp), C.POINTER(ModelParams), C.POINTER(HierSchedule), C.POINTER(HierOutput), C.POINTER(HierRunResult), vp]
     _LIB = L
     return L
 

@@ -46,7 +46,9 @@ def hdf5_prefix():
 
 def build(force=False):
     """g++ against an HDF5 C library; raises RuntimeError when there is none (the checkpoint file is optional: the caller decides)"""
-    src = [os.path.join(CSRC, "suhmo_chk.cpp"), os.path.join(os.path.dirname(_HERE), "include", "suhmo_chk.h")]
+    inc = os.path.join(os.path.dirname(_HERE), "include")
+    src = [os.path.join(CSRC, "suhmo_chk.cpp"), os.path.join(inc, "suhmo_chk.h"),                      # (the plot files live in the same library)
+           os.path.join(CSRC, "suhmo_plt.cpp"), os.path.join(inc, "suhmo_plt.h"), os.path.join(CSRC, "suhmo_h5.h")]
     if force or not os.path.exists(LIB_PATH) or any(os.path.getmtime(s) > os.path.getmtime(LIB_PATH) for s in src):
         prefix = hdf5_prefix()
         if prefix is None:
@@ -157,18 +159,59 @@ def _boxes_of(model):
     return [[(model.level, (0, 0, model.nx - 1, model.ny - 1))]]
 
 
-def write(path, model, time, dt, periodic=(0, 0), extra=None):
-    """AmrHydro::writeCheckpointFile of a device-resident model.  extra: dataset -> constant or list (per level) of lists (per
-    box) of ghosted arrays for velMagData / iceHeightData / bumpHeightData / bumpSpacingData (defaults: |ub|, 0, br, lr)."""
-    from . import model as md
-    m = model.model
+def constants(model_dict, extra=None):
+    """the datasets that are no device fields -> constant or per-box arrays (defaults: |ub|, 0, br, lr; extra overrides)"""
+    m = model_dict
     ub = m.get("ub", (0.0, 0.0))
     const = {"velMagData": float(np.hypot(ub[0], ub[1])), "iceHeightData": 0.0, "bumpHeightData": float(m["br"]), "bumpSpacingData": float(m["lr"])}
     const.update(extra or {})
+    return const
+
+
+def snapshot_components(const):
+    """the component list of the snapshot a packed checkpoint is written from (one ghost cell): the device datasets of FIELDS as fields, the
+    constant ones as constants -> (comps as capi.snap_comps takes them, {dataset: component}); a dataset given as arrays is in neither"""
+    from . import capi, model as md
+    comps, where = [], {}
+    for name, fld in FIELDS:
+        if fld is not None:
+            where[name] = len(comps)
+            comps.append((capi.SNAP_FIELD, md.HipModel.FIELDS[fld]))
+        elif isinstance(const[name], (int, float)):
+            where[name] = len(comps)
+            comps.append((capi.SNAP_CONST, 0, float(const[name])))
+    return comps, where
+
+
+def _packed_fabs(model, const, snapshot=None):
+    """the datasets of snapshot_components from ONE snapshot (suhmo_hier_snapshot: a launch and a copy per level instead of a copy per box and
+    field; snapshot = (level_offset, box_offset, flat) when the caller holds one already) -> fab(name, l, k, box): the ghosted array of a
+    dataset, a view into the packed buffer; None for a dataset the caller gave as arrays"""
+    from . import level as lv, model as md
+    comps, where = snapshot_components(const)
+    if isinstance(model, md.HipHierModel):
+        lo, bo, flat = model.hier.snapshot(comps, 1) if snapshot is None else snapshot
+        return lambda name, l, k, b: lv.snapshot_box(lo, bo, flat, len(comps), 1, l, k, b)[where[name]] if name in where else None
+    if isinstance(model, md.HipModel) and snapshot is None:
+        a = model.level.snapshot(comps, 1)
+        return lambda name, l, k, b: a[where[name]] if name in where else None
+    raise TypeError("checkpoint.write(packed=True) takes a HipModel or a HipHierModel, not %s" % type(model).__name__)
+
+
+def write(path, model, time, dt, periodic=(0, 0), extra=None, packed=False, snapshot=None, step=None):
+    """AmrHydro::writeCheckpointFile of a device-resident model.  extra: dataset -> constant or list (per level) of lists (per
+    box) of ghosted arrays for velMagData / iceHeightData / bumpHeightData / bumpSpacingData (defaults: |ub|, 0, br, lr).
+    packed=True (HipModel, HipHierModel): every device dataset comes from ONE snapshot instead of a copy per box and field; the file is the
+    same.  snapshot = (level_offset, box_offset, flat): the snapshot of snapshot_components(constants(model.model, extra)) with one ghost
+    cell the caller holds already (the callback of a run); step: current_step of the header (default: the model's cur_step)."""
+    from . import model as md
+    const = constants(model.model, extra)
+    packed = packed or snapshot is not None
     tree = _boxes_of(model)
     nx0 = tree[0][0][1][2] + 1
     ny0 = tree[0][0][1][3] + 1
     levels = []
+    fab = _packed_fabs(model, const, snapshot) if packed else None
     for l, bl in enumerate(tree):
         L0 = bl[0][0]
         data = {}
@@ -176,7 +219,9 @@ def write(path, model, time, dt, periodic=(0, 0), extra=None):
             arrs = []
             for k, (L, b) in enumerate(bl):
                 shape = (b[3] - b[1] + 3, b[2] - b[0] + 3)
-                if fld is not None:
+                if packed and fab(name, l, k, b) is not None:
+                    arrs.append(fab(name, l, k, b))
+                elif fld is not None:
                     arrs.append(L.get(md.HipModel.FIELDS[fld], ghosted=True))
                 elif isinstance(const[name], (int, float)):
                     arrs.append(np.full(shape, float(const[name])))
@@ -184,7 +229,7 @@ def write(path, model, time, dt, periodic=(0, 0), extra=None):
                     arrs.append(np.asarray(const[name][l][k], dtype=np.float64))
             data[name] = arrs
         levels.append(dict(dx=L0.dx, dy=L0.dy, domain=(0, 0, (nx0 << l) - 1, (ny0 << l) - 1), boxes=[b for _, b in bl], data=data))
-    write_levels(path, levels, model.cur_step, time, dt, periodic)
+    write_levels(path, levels, model.cur_step if step is None else step, time, dt, periodic)
 
 
 def restart(path, model):

@@ -1,11 +1,6 @@
 // suhmo_chk.cpp -- Chombo-HDF5 checkpoint files of the hydrology state (include/suhmo_chk.h).  Host code, HDF5 C library.
 #include "../../include/suhmo_chk.h"
-#include <hdf5.h>
-#include <cstdarg>
-#include <cstdio>
-#include <cstring>
-#include <string>
-#include <vector>
+#include "suhmo_h5.h"
 
 extern "C" const char *const suhmo_chk_field_names[SUHMO_CHK_NFIELDS] = {
     "headData", "gapHeightData", "overburdenPressData", "velMagData", "bedelevationData", "ReData",
@@ -14,13 +9,7 @@ extern "C" const char *const suhmo_chk_field_names[SUHMO_CHK_NFIELDS] = {
 static const char *const k_comp_names[SUHMO_CHK_NFIELDS] = {
     "head", "gapHeight", "overburdenPress", "magVel", "bedelevation", "Re", "iceHeight", "bumpHeight", "bumpSpacing", "meltRate", "iceMask"};
 
-static thread_local char g_err[512] = "";
-static int fail(const char *fmt, ...)
-{
-    va_list ap; va_start(ap, fmt); vsnprintf(g_err, sizeof(g_err), fmt, ap); va_end(ap);
-    return -1;
-}
-extern "C" const char *suhmo_chk_last_error(void) { return g_err; }
+extern "C" const char *suhmo_chk_last_error(void) { return h5::err; }
 
 struct LevelInfo { int nbox = 0; std::vector<int> boxes; };
 struct suhmo_chk {
@@ -30,50 +19,7 @@ struct suhmo_chk {
     std::vector<LevelInfo> lev;
 };
 
-namespace {
-struct Box2 { int lo_i, lo_j, hi_i, hi_j; };
-struct IV2 { int intvecti, intvectj; };
-hid_t make_box_type()
-{
-    hid_t t = H5Tcreate(H5T_COMPOUND, sizeof(Box2));
-    H5Tinsert(t, "lo_i", HOFFSET(Box2, lo_i), H5T_NATIVE_INT); H5Tinsert(t, "lo_j", HOFFSET(Box2, lo_j), H5T_NATIVE_INT);
-    H5Tinsert(t, "hi_i", HOFFSET(Box2, hi_i), H5T_NATIVE_INT); H5Tinsert(t, "hi_j", HOFFSET(Box2, hi_j), H5T_NATIVE_INT);
-    return t;
-}
-hid_t make_iv_type()
-{
-    hid_t t = H5Tcreate(H5T_COMPOUND, sizeof(IV2));
-    H5Tinsert(t, "intvecti", HOFFSET(IV2, intvecti), H5T_NATIVE_INT); H5Tinsert(t, "intvectj", HOFFSET(IV2, intvectj), H5T_NATIVE_INT);
-    return t;
-}
-int put_attr(hid_t loc, const char *name, hid_t type, const void *val)
-{
-    hid_t sp = H5Screate(H5S_SCALAR);
-    hid_t a = H5Acreate2(loc, name, type, sp, H5P_DEFAULT, H5P_DEFAULT);
-    herr_t e = a >= 0 ? H5Awrite(a, type, val) : -1;
-    if (a >= 0) H5Aclose(a);
-    H5Sclose(sp);
-    return e < 0 ? fail("cannot write attribute %s", name) : 0;
-}
-int put_str(hid_t loc, const char *name, const char *val)
-{
-    hid_t t = H5Tcopy(H5T_C_S1);
-    H5Tset_size(t, strlen(val) > 0 ? strlen(val) : 1);
-    int rc = put_attr(loc, name, t, val);
-    H5Tclose(t);
-    return rc;
-}
-int get_attr(hid_t loc, const char *name, hid_t type, void *val)
-{
-    if (H5Aexists(loc, name) <= 0) return fail("attribute %s missing", name);
-    hid_t a = H5Aopen(loc, name, H5P_DEFAULT);
-    herr_t e = a >= 0 ? H5Aread(a, type, val) : -1;
-    if (a >= 0) H5Aclose(a);
-    return e < 0 ? fail("cannot read attribute %s", name) : 0;
-}
-std::string level_name(int l) { char b[32]; snprintf(b, sizeof(b), "level_%d", l); return b; }
-long box_pts(const int *b, int g) { return (long)(b[2] - b[0] + 1 + 2 * g) * (long)(b[3] - b[1] + 1 + 2 * g); }
-}  // namespace
+using namespace h5;
 
 extern "C" int suhmo_chk_create(suhmo_chk_t **out, const char *path, const suhmo_chk_header_t *hdr)
 {

@@ -315,8 +315,10 @@ extern "C" int suhmo_hier_destroy(suhmo_hier_t *H)
     if (H->red_all) (void)hipFree(H->red_all);
     if (H->xs) (void)hipFree(H->xs);
     if (H->xr) (void)hipFree(H->xr);
+    if (H->snap_buf) (void)hipFree(H->snap_buf);
     for (int l = 0; l < 8; l++) {
         HLev &V = H->lev[l];
+        V.snap_cells[0].release(); V.snap_cells[1].release();
         for (suhmo_level *L : V.box) if (!(l == 0 && H->base_borrowed)) (void)suhmo_level_destroy(L);
         V.ff_side.release(); V.ff_all.release(); V.push.release(); V.pbase.release(); V.cf.release(); V.pwl.release(); V.avg.release(); V.wing.release();
             V.wstart.release(); V.halo.release(); V.hbase.release();
@@ -588,6 +590,10 @@ extern "C" int suhmo_hier_get_option(const suhmo_hier_t *H, const char *key, lon
     if (!strcmp(key, "recharge_launches")) { *value = H->n_recharge_launches; return 0; }
     if (!strcmp(key, "moulin_source_calls")) { *value = H->n_moulin_calls; return 0; }
     if (!strcmp(key, "run_readbacks")) { *value = H->n_run_readbacks; return 0; }
+    if (!strcmp(key, "snapshot_launches")) { *value = H->n_snap_launches; return 0; }
+    if (!strcmp(key, "snapshot_copies")) { *value = H->n_snap_copies; return 0; }
+    if (!strcmp(key, "run_plots")) { *value = H->n_run_plots; return 0; }
+    if (!strcmp(key, "run_checkpoints")) { *value = H->n_run_checkpoints; return 0; }
     if (!strcmp(key, "incremental_residual_passes")) { *value = H->n_incr_residual; return 0; }
     if (!strcmp(key, "residuals_left_by_relax")) { *value = H->n_fused_residual; return 0; }
     if (!strcmp(key, "sparse_gradient_passes")) { *value = H->n_sparse_grad; return 0; }

@@ -127,6 +127,7 @@ struct HLev {
     DevVec<RectEnt> avg_cov; int cov_w = 0, cov_h = 0;       // covered rectangles by the owner of the COARSE cells (zeroing / marking them)
     DevVec<RectEnt> avg_put; DevVec<PutEnt> avg_get; long put_stride = 0, put_mine = 0; int put_w = 0, put_h = 0, get_w = 0, get_h = 0;
     long owned_cells = 0, held_boxes = 0;
+    DevVec<long> snap_cells[2];                      // suhmo_snap.hip: per box the cells of the boxes before it, each grown by 0 / 1 ghost cells (built on first use)
 };
 }  // namespace hier
 
@@ -187,6 +188,10 @@ struct suhmo_hier {
     // launches of suhmo_hier_time_varying_recharge (one per level), calls of suhmo_hier_moulin_source, copies of a run's series to the host
     // (read-only options recharge_launches, moulin_source_calls, run_readbacks; a run carries them across its regrids)
     long n_recharge_launches = 0, n_moulin_calls = 0, n_run_readbacks = 0;
+    // suhmo_snap.hip: device staging of a snapshot (the largest level's packed size so far; allocated on first use), its launches and copies
+    // (read-only options snapshot_launches, snapshot_copies); plots and checkpoints the last run handed to its callback (run_plots, run_checkpoints)
+    double *snap_buf = nullptr; size_t snap_cap = 0;
+    long n_snap_launches = 0, n_snap_copies = 0, n_run_plots = 0, n_run_checkpoints = 0;
     double *red_all = nullptr;                             // partial maxima of a norm over all levels of boxes (64 per box + 16)
     struct suhmo_tagmap *tags[8] = {};                     // tag maps of suhmo_hier_tag_cells, one per level (suhmo_tags.hip), owned
     hier::DevVec<hier::RectEnt> cover_full;                            // coarsen(boxes of level 1) in the shadow: COVER of the whole level 0
@@ -291,3 +296,6 @@ int suhmo_hier_recharge_launch_(suhmo_hier *H, double T_K, double background_inp
 int suhmo_level_postproc_row_check_(suhmo_level *L, const suhmo_model_params_t *mp, bool forcing_writes_source);
 int suhmo_level_postproc_row_launch_(suhmo_level *L, const suhmo_model_params_t *mp, double *cols, double *out6, hipStream_t st);
 int suhmo_step_check_args_(const suhmo_model_params_t *mp, double dt, int cur_step);
+// ---- suhmo_snap.hip: what the run needs of the snapshot -- its refusals, and the offsets (level_offset [nlev + 1], box_offset, either may be NULL) -> doubles in all
+int suhmo_hier_snapshot_check_(const suhmo_hier *H, const char *who, int ncomp, const suhmo_snap_comp_t *comps, int ghost);
+long suhmo_hier_snapshot_sizes_(const suhmo_hier *H, int ncomp, int ghost, long *level_offset, long *box_offset);

@@ -3,7 +3,8 @@
 // recharge :2846-2863, or the moulin source when m_regrid asks for it, :2802), suhmo_hier_timestep, and the daily row of level 0 finished on the
 // device into a series that comes back in one copy.  The C-ABI and the order: include/suhmo_hip.h, "THE RUN OF A HIERARCHY".  Nothing here
 // computes: every step is one of the public calls (or the launches of one), so the results are the per-call loop's bit for bit.  Eager
-// launches, no graph capture, as suhmo_batch_run.
+// launches, no graph capture, as suhmo_batch_run.  suhmo_hier_run_out adds the plot files and checkpoints AmrHydro::run writes (:1311-1336, :1343-1358):
+// a snapshot (suhmo_snap.hip) handed to the caller's callback, include/suhmo_hip.h, "OUTPUT INSIDE THE RUN".
 #include "suhmo_hier_int.h"
 #include <cstring>
 #include <vector>
@@ -63,10 +64,11 @@ int run_regrid(suhmo_hier **Hp, const suhmo_hier_schedule_t *sch, int c, suhmo_h
         res->n_regrids = idx + 1;
     };
     if (same) { log(); return 0; }
-    const long carried[3] = {H->n_recharge_launches, H->n_moulin_calls, H->n_run_readbacks};
+    const long carried[5] = {H->n_recharge_launches, H->n_moulin_calls, H->n_run_readbacks, H->n_snap_launches, H->n_snap_copies};
     suhmo_hier *N = nullptr;
     if ((rc = suhmo_hier_regrid(H, nlev, nbox, boxes.data(), sch->n_fields, sch->fields, &N, s))) return rc;      // (H is untouched and usable)
     N->n_recharge_launches = carried[0]; N->n_moulin_calls = carried[1]; N->n_run_readbacks = carried[2];
+    N->n_snap_launches = carried[3]; N->n_snap_copies = carried[4];
     *Hp = N;
     *changed = true;
     log();
@@ -79,10 +81,51 @@ int run_regrid(suhmo_hier **Hp, const suhmo_hier_schedule_t *sch, int c, suhmo_h
     if ((sch->T_K || sch->background) && (rc = suhmo_hier_recharge_check_(N, "suhmo_hier_run: after a regrid"))) return rc;
     return 0;
 }
+// the plot files and checkpoints of a run: one snapshot per event into a pinned buffer the run owns, then the caller's callback
+struct Output {
+    const suhmo_hier_output_t *o;
+    double *pinned = nullptr; size_t cap = 0;
+    std::vector<long> lo, bo;
+    long n[2] = {0, 0};
+    explicit Output(const suhmo_hier_output_t *out) : o(out) {}
+    ~Output() { if (pinned) (void)hipHostFree(pinned); }
+    bool plot_before(int b) const { return o && o->plot_interval > 0 && b % o->plot_interval == 0; }                                        // :1311
+    bool check_before(int b) const { return o && o->check_interval > 0 && b % o->check_interval == 0 && b != o->restart_step; }             // :1327
+    // kind 0 plot, 1 checkpoint; cur_step: m_cur_step of the file name
+    int emit(suhmo_hier *H, int kind, int cur_step, suhmo_stream_t s)
+    {
+        const int ncomp = kind ? o->n_check : o->n_plot;
+        const suhmo_snap_comp_t *comps = kind ? o->check : o->plot;
+        size_t nbox = 0;
+        for (int l = 0; l < H->nlev; l++) nbox += H->lev[l].box.size();
+        lo.assign(H->nlev + 1, 0); bo.assign(nbox + H->nlev, 0);
+        const size_t need = (size_t)suhmo_hier_snapshot_sizes_(H, ncomp, 1, nullptr, nullptr);
+        if (need > cap) {
+            if (pinned) { HIPCHK(hipHostFree(pinned)); pinned = nullptr; cap = 0; }
+            HIPCHK(hipHostMalloc(&pinned, need * sizeof(double), hipHostMallocDefault));
+            cap = need;
+        }
+        int rc = suhmo_hier_snapshot(H, ncomp, comps, 1, lo.data(), bo.data(), pinned, s);
+        if (rc) return rc;
+        const int r = o->write(o->user, H, kind, cur_step, ncomp, lo.data(), bo.data(), pinned);
+        if (r) {
+            suhmo_set_error("suhmo_hier_run: write returned %d for the %s with cur_step %d", r, kind ? "checkpoint" : "plot", cur_step);
+            return -1;
+        }
+        n[kind]++;
+        return 0;
+    }
+};
 }  // namespace
 
 extern "C" int suhmo_hier_run(suhmo_hier_t **Hp, const suhmo_model_params_t *mp, const suhmo_hier_schedule_t *sch, suhmo_hier_run_result_t *res,
                               suhmo_stream_t s)
+{
+    return suhmo_hier_run_out(Hp, mp, sch, nullptr, res, s);
+}
+
+extern "C" int suhmo_hier_run_out(suhmo_hier_t **Hp, const suhmo_model_params_t *mp, const suhmo_hier_schedule_t *sch, const suhmo_hier_output_t *out,
+                                  suhmo_hier_run_result_t *res, suhmo_stream_t s)
 {
     SUHMO_TIME("AmrHydro::run");
     ARG(Hp && *Hp && mp && sch && res);
@@ -133,6 +176,14 @@ extern "C" int suhmo_hier_run(suhmo_hier_t **Hp, const suhmo_model_params_t *mp,
             }
         }
     }
+    if (out) {
+        if (out->plot_interval < -1 || out->check_interval < -1) { suhmo_set_error("suhmo_hier_run: plot_interval = %d, check_interval = %d (-1: off)", out->plot_interval, out->check_interval); return -1; }
+        const bool plots = out->plot_interval >= 0, checks = out->check_interval >= 0;
+        if ((plots || checks) && !out->write) { suhmo_set_error("suhmo_hier_run: output without a callback to write it"); return -1; }
+        if ((plots && (out->n_plot < 1 || !out->plot)) || (checks && (out->n_check < 1 || !out->check))) { suhmo_set_error("suhmo_hier_run: output without a component list"); return -1; }
+        if (plots && (rc = suhmo_hier_snapshot_check_(H, "suhmo_hier_run: plot components", out->n_plot, out->plot, 1))) return rc;
+        if (checks && (rc = suhmo_hier_snapshot_check_(H, "suhmo_hier_run: checkpoint components", out->n_check, out->check, 1))) return rc;
+    }
     if (recharge && (rc = suhmo_hier_recharge_check_(H, "suhmo_hier_run"))) return rc;
     if (mp->use_moulin_source && !recharge && !moulins)
         for (int l = 0; l < H->nlev; l++)
@@ -153,15 +204,20 @@ extern "C" int suhmo_hier_run(suhmo_hier_t **Hp, const suhmo_model_params_t *mp,
     double *cols = series ? series + 6 * (size_t)total_rows : nullptr;
     int rows = 0;
     rc = 0;
+    Output output(out && (out->plot_interval >= 0 || out->check_interval >= 0) ? out : nullptr);
     for (int k = 0; k < sch->n_steps; k++) {
         const int c = sch->first_cur_step + k;
         bool changed = false;
+        // 0. plot file: the state before the regrid
+        if (output.plot_before(c - 1) && (rc = output.emit(H, 0, c - 1, s))) break;
         // 1. regrid
         if (regrid_due(sch, k)) {
             rc = run_regrid(Hp, sch, c, res, &changed, s);
             H = *Hp;
             if (rc) break;
         }
+        // 1b. checkpoint: on the boxes the regrid left
+        if (output.check_before(c - 1) && (rc = output.emit(H, 1, c - 1, s))) break;
         // 2. forcing
         if (recharge && (rc = suhmo_hier_recharge_launch_(H, sch->T_K[k], sch->background[k], st))) break;
         const double factor = sch->moulin_factor ? sch->moulin_factor[k] : 1.0;
@@ -182,6 +238,13 @@ extern "C" int suhmo_hier_run(suhmo_hier_t **Hp, const suhmo_model_params_t *mp,
             rows++;
         }
     }
+    // the files after the last step (:1343-1358)
+    if (!rc && output.o && !out->no_final) {
+        const int last = sch->first_cur_step + sch->n_steps - 1;
+        if (out->plot_interval >= 0) rc = output.emit(H, 0, last, s);
+        if (!rc && out->check_interval >= 0) rc = output.emit(H, 1, last, s);
+    }
+    H->n_run_plots = output.n[0]; H->n_run_checkpoints = output.n[1];
     res->n_rows = rows;
     int rc2 = 0;
     if (rows > 0) {

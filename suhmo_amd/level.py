@@ -94,6 +94,16 @@ class HipLevel:
         check(capi.lib().suhmo_level_get_field(self.h, depth, field, out.ctypes.data, int(ghosted), 0, self.stream))
         return out
 
+    def snapshot(self, comps, ghost=1):
+        """suhmo_level_snapshot: the components (capi.snap_comps takes them) of the whole level as the one box (0, 0, nx - 1, ny - 1) grown by
+        `ghost`, in Chombo's fab order -> (ncomp, ny + 2 ghost, nx + 2 ghost); one launch, one copy"""
+        n = C.c_long()
+        arr = capi.snap_comps(comps)
+        check(capi.lib().suhmo_level_snapshot(self.h, len(comps), arr, int(ghost), C.byref(n), None, self.stream))
+        out = np.zeros(n.value)
+        check(capi.lib().suhmo_level_snapshot(self.h, len(comps), arr, int(ghost), C.byref(n), out.ctypes.data_as(C.POINTER(C.c_double)), self.stream))
+        return out.reshape(len(comps), self.ny + 2 * ghost, self.nx + 2 * ghost)
+
     def set_device(self, field, dev_ptr, depth=0, ghosted=False):
         check(capi.lib().suhmo_level_set_field(self.h, depth, field, C.c_void_p(dev_ptr), int(ghosted), 1, self.stream))
 
@@ -369,6 +379,21 @@ class HipBatch:
         return v.value
 
 
+def split_box_offsets(box_offset, nbox):
+    """the box_offset array of a snapshot (per level nbox + 1 prefix sums, one level after the other) -> a list of int64 arrays"""
+    out, q = [], 0
+    for n in nbox:
+        out.append(np.array(box_offset[q:q + n + 1], dtype=np.int64))
+        q += n + 1
+    return out
+
+
+def snapshot_box(level_offset, box_offset, flat, ncomp, ghost, l, k, box):
+    """box k of level l (box = (lo0, lo1, hi0, hi1)) of a snapshot as an (ncomp, ny + 2 ghost, nx + 2 ghost) view of flat"""
+    a, b = level_offset[l] + box_offset[l][k], level_offset[l] + box_offset[l][k + 1]
+    return flat[a:b].reshape(ncomp, box[3] - box[1] + 1 + 2 * ghost, box[2] - box[0] + 1 + 2 * ghost)
+
+
 class HipHier:
     """Base level + levels that are unions of boxes (boxes[l-1] = list of (lo0, lo1, hi0, hi1) in the index space of
     level l), the reference's DisjointBoxLayout per AMR level: suhmo_hier_* (suhmo_amd/csrc/suhmo_hier*.hip)."""
@@ -455,17 +480,41 @@ class HipHier:
         self._bind(h)
         self._adopts = getattr(self, "_adopts", 0) + 1
 
-    def run(self, mp, sch, res):
-        """suhmo_hier_run with the structures of capi (mp: ModelParams, sch: HierSchedule, res: HierRunResult with its arrays) -> rc.  After a
+    def _adopt_if_new(self, h):
+        """bind this object to the handle h of a callback of a run unless it is bound to it already"""
+        h = h if isinstance(h, int) else h.value
+        if h != self.h.value:
+            self._adopt(h)
+
+    def run(self, mp, sch, res, out=None):
+        """suhmo_hier_run with the structures of capi (mp: ModelParams, sch: HierSchedule, res: HierRunResult with its arrays) -> rc; with
+        out (capi.HierOutput): suhmo_hier_run_out, whose callback receives the handle the event is about -- after a regrid that moved boxes and
+        no `reload` that adopted it, call _adopt_if_new(handle) there before reading self.boxes.  After a
         run that moved the hierarchy onto other boxes (res.n_moved regrids did) this object wraps the new handle (new views, self.boxes,
         self.nlev), as after regrid.  A `reload` callback of the schedule that works through this object calls _adopt(the handle it is
         given) first; the run is called after every such regrid, so then nothing is left to do here."""
         hp = C.c_void_p(self.h.value)
         before = self._adopts = getattr(self, "_adopts", 0)
-        rc = capi.lib().suhmo_hier_run(C.byref(hp), C.byref(mp), C.byref(sch), C.byref(res), self.stream)
+        if out is None:
+            rc = capi.lib().suhmo_hier_run(C.byref(hp), C.byref(mp), C.byref(sch), C.byref(res), self.stream)
+        else:
+            rc = capi.lib().suhmo_hier_run_out(C.byref(hp), C.byref(mp), C.byref(sch), C.byref(out), C.byref(res), self.stream)
         if res.n_moved > self._adopts - before:            # the last handle was not adopted by a callback
             self._adopt(hp)
         return rc
+
+    def snapshot(self, comps, ghost=1, out=None):
+        """suhmo_hier_snapshot: the components (capi.snap_comps takes them) of every box of every level in Chombo's on-disk order, one
+        launch and one copy per level -> (level_offset (nlev + 1,), box_offset [per level (nbox + 1,)], flat).  Box k of level l grown by
+        `ghost` is flat[level_offset[l] + box_offset[l][k] : ... [k + 1]] viewed as (ncomp, ny + 2 ghost, nx + 2 ghost): snapshot_box"""
+        nbox = [len(bl) for bl in self.level]
+        lo, bo = (C.c_long * (self.nlev + 1))(), (C.c_long * (sum(nbox) + self.nlev))()
+        arr = capi.snap_comps(comps)
+        check(capi.lib().suhmo_hier_snapshot(self.h, len(comps), arr, int(ghost), lo, bo, None, self.stream))
+        flat = np.zeros(lo[self.nlev]) if out is None else out
+        assert flat.shape == (lo[self.nlev],) and flat.dtype == np.float64 and flat.flags.c_contiguous
+        check(capi.lib().suhmo_hier_snapshot(self.h, len(comps), arr, int(ghost), lo, bo, flat.ctypes.data_as(C.POINTER(C.c_double)), self.stream))
+        return np.array(lo[:], dtype=np.int64), split_box_offsets(bo, nbox), flat
 
     def owns(self, l, k):
         """this rank computes box k of level l (every box of a replicated level; on a level dealt to the ranks: its own boxes)"""

@@ -95,6 +95,33 @@ def regrid_steps(first_cur_step, n_steps, interval, skip_first=False):
     return out
 
 
+PLOT, CHECKPOINT = 0, 1            # the `kind` of an output event (suhmo_hier_output_fn)
+
+
+def output_steps(first_cur_step, n_steps, plot_interval, check_interval, restart_step=0, final=True):
+    """the plot files and checkpoints a run writes (suhmo_hier_run_out; src/AmrHydro.cpp:1311, :1327, :1343-1358), in order:
+    [(kind, cur_step, where)] with kind PLOT / CHECKPOINT, cur_step the reference's m_cur_step in the file name and where "before_regrid"
+    (the plot before step c = cur_step + 1, taken before that step's regrid), "after_regrid" (the checkpoint before step c, taken after it) or
+    "final" (after the last step; cur_step = the last c).  With b = c - 1: a plot when plot_interval > 0 and b % plot_interval == 0, b = 0
+    included; a checkpoint when check_interval > 0, b % check_interval == 0 and b != restart_step; after the last step a plot when
+    plot_interval >= 0 and a checkpoint when check_interval >= 0, unless final is False (a run that another run continues).  An interval
+    of -1 switches that kind off."""
+    out = []
+    for k in range(int(n_steps)):
+        b = int(first_cur_step) + k - 1
+        if plot_interval > 0 and b % plot_interval == 0:
+            out.append((PLOT, b, "before_regrid"))
+        if check_interval > 0 and b % check_interval == 0 and b != restart_step:
+            out.append((CHECKPOINT, b, "after_regrid"))
+    if final and n_steps > 0:
+        last = int(first_cur_step) + int(n_steps) - 1
+        if plot_interval >= 0:
+            out.append((PLOT, last, "final"))
+        if check_interval >= 0:
+            out.append((CHECKPOINT, last, "final"))
+    return out
+
+
 def _flat_boxes(levels):
     """[[(lo0, lo1, hi0, hi1), ...] per level] -> (counts, ints) as the C-ABI takes box lists"""
     nbox = (C.c_int * max(len(levels), 1))(*[len(bl) for bl in levels])
@@ -670,7 +697,9 @@ class HipHierModel:
         return out
 
     def run(self, n_steps, dt, T_K=None, background=None, moulins=None, moulin_factor=None, ramp=None, diag_every=0, regrid_interval=0,
-            tag_specs=None, params=None, subsets=None, max_level=None, reload=None, skip_first_regrid=False, fields=None):
+            tag_specs=None, params=None, subsets=None, max_level=None, reload=None, skip_first_regrid=False, fields=None,
+            plot_interval=-1, check_interval=-1, plot_prefix="plot", check_prefix="chk", check_overwrite=True, restart_step=0,
+            final_output=True, time0=0.0, periodic=(0, 0)):
         """AmrHydro::run in ONE call (suhmo_hier_run): per step the regrid the reference does before it (every regrid_interval steps:
         regrid_steps(self.cur_step + 1, n_steps, regrid_interval, skip_first_regrid) lists them; tag_and_regrid's arguments tag_specs, params,
         subsets, max_level, fields), the forcing, the time step and, after every diag_every-th step, the daily row finished on the device; the
@@ -684,8 +713,15 @@ class HipHierModel:
         With T_K the surface height (set_surface) must reach the new boxes of every such regrid: fields = None or a list with "zs" transfers
         it, or reload returns "zs" for EVERY box.  Otherwise the run ends at that regrid with SuhmoError rc -1 naming the box, before anything
         is launched on the new hierarchy; the steps before it are done, the model wraps the new hierarchy and goes on once the surface is loaded.
+        OUTPUT (suhmo_hier_run_out; output_steps lists the events): plot_interval / check_interval as the reference's (-1: none of that kind, 0:
+        only the file after the last step), restart_step, final_output=False for a run that another run continues.  Every event is one
+        snapshot on the device and one file: plotfile's thirteen components into plot_prefix + "%06d.2d.hdf5" % cur_step, the checkpoint's
+        datasets into check_prefix + ".2d.hdf5" (check_overwrite) or check_prefix + "%06d.2d.hdf5" (:5634, :5680-5691); the file's time is
+        time0 + steps done x dt, `periodic` goes into the checkpoint's header.  An exception raised while writing ends the run and is raised
+        again after the bookkeeping, as for reload.
         Returns (picard iterations (n_steps,), V-cycles (n_steps,), rows (n_steps // diag_every, 6), log) with log = one dict per regrid:
-        cur_step, same, boxes_per_level.  self.last_run: steps_done, n_rows, moulin_steps (n_steps,).  cur_step advances by the steps done;
+        cur_step, same, boxes_per_level.  self.last_run: steps_done, n_rows, moulin_steps (n_steps,), plots and checkpoints (the paths
+        written, in order).  cur_step advances by the steps done;
         after a regrid that moved boxes self.hier wraps the new handle and self.level holds the new boxes' views."""
         n_steps, diag_every = int(n_steps), int(diag_every)
         ns = max(n_steps, 0)
@@ -765,18 +801,52 @@ class HipHierModel:
 
         cb = capi.RELOAD_FN(on_regrid)
         sch.reload = cb
+        out, written = None, ([], [])
+        if plot_interval != -1 or check_interval != -1:
+            from . import checkpoint, plotfile
+            const = checkpoint.constants(self.model)
+            chk_comps = checkpoint.snapshot_components(const)[0]
+            first = self.cur_step
+
+            def on_output(user, h, kind, cur_step, ncomp, level_offset, box_offset, data):
+                try:
+                    self.hier._adopt_if_new(h)
+                    self.level = self.hier.level
+                    nbox = [len(bl) for bl in self.level]
+                    lo = np.array(level_offset[:self.hier.nlev + 1], dtype=np.int64)
+                    bo = lv.split_box_offsets(box_offset, nbox)
+                    flat = np.ctypeslib.as_array(data, shape=(int(lo[-1]),))           # the run's pinned buffer: valid during this call
+                    time = float(time0) + (cur_step - first) * float(dt)
+                    if kind == PLOT:
+                        path = "%s%06d.2d.hdf5" % (plot_prefix, cur_step)
+                        plotfile.write_levels(path, plotfile.NAMES, plotfile.levels_of_snapshot(self, lo, bo, flat), time)
+                    else:
+                        path = "%s.2d.hdf5" % check_prefix if check_overwrite else "%s%06d.2d.hdf5" % (check_prefix, cur_step)
+                        checkpoint.write(path, self, time, float(dt), periodic, snapshot=(lo, bo, flat), step=cur_step)
+                    written[kind].append(path)
+                    return 0
+                except BaseException as e:
+                    raised.append(e)
+                    return 1
+
+            pc, cc = capi.snap_comps(plotfile.SNAP), capi.snap_comps(chk_comps)
+            ocb = capi.OUTPUT_FN(on_output)
+            keep += [pc, cc, ocb]
+            out = capi.HierOutput(int(plot_interval), int(check_interval), int(restart_step), int(not final_output), len(plotfile.SNAP), pc,
+                                  len(chk_comps), cc, ocb, None)
         n_rows = n_steps // diag_every if diag_every > 0 and n_steps > 0 else 0
         rows = np.zeros((n_rows, 6))
         pi, nv, ms = np.zeros(ns, dtype=np.intc), np.zeros(ns, dtype=np.intc), np.zeros(ns, dtype=np.intc)
         log = (capi.HierRegridLog * max(ns, 1))()
         res = capi.HierRunResult(picard_iters=ip(pi), vcycles=ip(nv), rows=dp(rows) if n_rows else None, moulin_steps=ip(ms), regrids_cap=max(ns, 1),
                                  regrids=log)
-        rc = self.hier.run(self._mp, sch, res)
+        rc = self.hier.run(self._mp, sch, res, out)
         self.level = self.hier.level
         self.cur_step += res.steps_done
         if ramp is not None and res.steps_done > 0:            # the model's ramp is the last step's, as a loop that sets it leaves it
             self._mp.ramp = float(r[res.steps_done - 1])
-        self.last_run = dict(steps_done=int(res.steps_done), n_rows=int(res.n_rows), moulin_steps=ms, n_moved=int(res.n_moved))
+        self.last_run = dict(steps_done=int(res.steps_done), n_rows=int(res.n_rows), moulin_steps=ms, n_moved=int(res.n_moved),
+                             plots=written[0], checkpoints=written[1])
         if raised:
             raise raised[0]
         check(rc)

@@ -1,6 +1,10 @@
 #!/usr/bin/env python3
 """cfg5 (exec/AMR_multiMoulins physics) time step on base + 3 AMR levels of box unions: ms per step.
-    python tools/hier_bench.py [--generated-grids] [--regrid-interval N [--one-call]] [--recharge] [base cells per side] [steps]
+    python tools/hier_bench.py [--generated-grids] [--regrid-interval N [--one-call [--plot-interval P]]] [--recharge] [--snapshot] [base cells per side] [steps]
+--plot-interval P (with --one-call): the runs of HipHierModel.run also write a plot file before every step c with (c - 1) % P == 0 (suhmo_hier_run_out:
+one snapshot and one file per event, into a temporary directory); the per-call loop beside it writes none, so the difference is what the output costs.
+--snapshot: one 13-component snapshot of the hierarchy (suhmo_hier_snapshot: a launch and a copy per level) against the per-box get loop for the same
+data (a copy per box and field), three alternating rounds, with the launch and copy counts of both.
 --one-call (with --regrid-interval N): the same regridding time loop twice in one process, on two models set up alike -- the per-call loop
 (HipHierModel.tag_and_regrid, moulin_source, timestep) and HipHierModel.run (suhmo_hier_run: one call per stretch of steps that begins with a
 regrid, so that the thresholds can alternate as below) -- in alternating rounds of [steps] steps; prints ms per step and ms per regrid interval of
@@ -22,7 +26,13 @@ from suhmo_amd import model, synthetic as sy
 generated = "--generated-grids" in sys.argv
 one_call = "--one-call" in sys.argv
 recharge = "--recharge" in sys.argv
-argv = [a for a in sys.argv[1:] if a not in ("--generated-grids", "--one-call", "--recharge")]
+snapshot = "--snapshot" in sys.argv
+argv = [a for a in sys.argv[1:] if a not in ("--generated-grids", "--one-call", "--recharge", "--snapshot")]
+plot_interval = -1
+if "--plot-interval" in argv:
+    q = argv.index("--plot-interval")
+    plot_interval = int(argv[q + 1])
+    del argv[q:q + 2]
 regrid_interval = 0
 if "--regrid-interval" in argv:
     q = argv.index("--regrid-interval")
@@ -226,12 +236,18 @@ def one_call_rounds(rounds=3):
                 M.moulin_source(**mo)
             M.timestep(mm["dt"])
         return len(due), moved
+    import tempfile
+    plots = tempfile.TemporaryDirectory() if plot_interval > 0 else None
+    out = dict(plot_interval=plot_interval, final_output=False, plot_prefix=os.path.join(plots.name, "plot")) if plots else {}
+    written = []
     def run(M):
         due, parts = stretches(M)
         moved = 0
         for c, n in parts:
-            log = M.run(n, mm["dt"], moulins=mo, regrid_interval=regrid_interval, tag_specs=specs((c - 1) // regrid_interval), params=GRID_PARAMS, max_level=3)[3]
+            log = M.run(n, mm["dt"], moulins=mo, regrid_interval=regrid_interval, tag_specs=specs((c - 1) // regrid_interval), params=GRID_PARAMS, max_level=3,
+                        **out)[3]
             moved += sum(not e["same"] for e in log)
+            written.extend(M.last_run.get("plots", []))
         return len(due), moved
     ms = {"per-call loop": [], "one call": []}
     for r in range(rounds):
@@ -249,7 +265,47 @@ def one_call_rounds(rounds=3):
     eq = P.hier.boxes == R.hier.boxes and all(np.array_equal(P.get(l, k, nm, ghosted=True), R.get(l, k, nm, ghosted=True), equal_nan=True)
                                               for l, bl in enumerate(P.level) for k in range(len(bl)) for nm in ("head", "B", "mR", "Pw", "msrc"))
     print("the two models after %d steps each: boxes and fields (head, B, mR, Pw, msrc; ghosted) bitwise equal: %s" % (rounds * nstep, eq))
+    if plots:
+        print("one call: %d plot files written (every %d steps), %.1f MB each, %d snapshot launches, %d snapshot copies"
+              % (len(written), plot_interval, os.path.getsize(written[-1]) / 1e6, R.hier.get_option("snapshot_launches"), R.hier.get_option("snapshot_copies")))
+        plots.cleanup()
     P.close(); R.close()
+
+
+def snapshot_bench(rounds=3):
+    """one snapshot of the plot file's thirteen components against the per-box get loop for the same data"""
+    import numpy as np
+    from suhmo_amd import level as lv, plotfile
+    M = model.HipHierModel(nb, nb, sts[0][0]["dx"], sts[0][0]["dy"], bc, ph, mm, boxes, max_box=64)
+    M.set_states(sts)
+    M.moulin_source(**mo)
+    for _ in range(3):
+        M.timestep(mm["dt"])
+    for bl in M.level:                                       # the loop below must not be the one that allocates a field nobody holds yet
+        for L in bl:
+            for _, _, f in plotfile.COMPONENTS:
+                L.get(f, ghosted=f not in (lv.F_QWX, lv.F_QWY))
+    sync = M.level[0][0].synchronize
+    nbx = sum(len(bl) for bl in M.level)
+    flat = np.zeros(M.hier.snapshot(plotfile.SNAP, 1)[2].size)
+    print("snapshot: boxes per level %s, %d handles with level 0, 13 components with one ghost cell: %.2f MB" % ([len(b) for b in boxes], nbx, flat.nbytes / 1e6), flush=True)
+    def packed():
+        M.hier.snapshot(plotfile.SNAP, 1, out=flat)
+        return None
+    def per_box():
+        return [[L.get(f, ghosted=f not in (lv.F_QWX, lv.F_QWY)) for _, _, f in plotfile.COMPONENTS] for bl in M.level for L in bl]
+    for r in range(rounds):
+        for name, fn in (("one snapshot", packed), ("per-box get loop", per_box)) if r % 2 == 0 else (("per-box get loop", per_box), ("one snapshot", packed)):
+            sync()
+            n_l, n_c = M.hier.get_option("snapshot_launches"), M.hier.get_option("snapshot_copies")
+            t0 = time.perf_counter()
+            fn()
+            sync()
+            t = time.perf_counter() - t0
+            counts = ("%d launches, %d copies" % (M.hier.get_option("snapshot_launches") - n_l, M.hier.get_option("snapshot_copies") - n_c) if fn is packed
+                      else "no launch, %d copies (one per box and field)" % (13 * nbx))
+            print("round %d, %-16s: %.3f ms, %s" % (r, name, 1e3 * t, counts), flush=True)
+    M.close()
 
 
 def recharge_bench(evals=50, reps=3):
@@ -279,6 +335,9 @@ def recharge_bench(evals=50, reps=3):
 
 if recharge:
     recharge_bench()
+    sys.exit(0)
+if snapshot:
+    snapshot_bench()
     sys.exit(0)
 if one_call:
     assert regrid_interval > 0, "--one-call needs --regrid-interval"
