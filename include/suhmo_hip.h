@@ -648,7 +648,7 @@ int suhmo_tag_subsets_nest(int nlev, const int *nbox, const int *boxes, int *nbo
 int suhmo_hier_regrid(suhmo_hier_t *H, int nlev, const int *nbox, const int *boxes, int nfields, const int *fields, suhmo_hier_t **out,
                       suhmo_stream_t s);
 
-/* ---- THE RUN OF A HIERARCHY (suhmo_amd/csrc/suhmo_run.hip, suhmo_step.hip): what AmrHydro::run (src/AmrHydro.cpp:1283-1365)
+/* ---- THE RUN OF A HIERARCHY (suhmo_amd/csrc/suhmo_run.hip, suhmo_forcing.hip, suhmo_postproc.hip): what AmrHydro::run (src/AmrHydro.cpp:1283-1365)
  * does around timeStepFAS, for a hierarchy of box unions.
  * suhmo_hier_time_varying_recharge   suhmo_level_time_varying_recharge on every box (timeStepFAS evaluates COMPUTE_TIMEVARYINGRECHARGE level by
  *     level, :2846-2863): SUHMO_F_MSRC of every box, ghost ring included, bit for bit what the level call on that box's handle writes.  ONE launch

@@ -52,7 +52,8 @@ int suhmo_batch_gap_store(const OnMembers &h, const OnMembers &g, size_t elems, 
 int suhmo_batch_timestep_run(suhmo_batch *B, const suhmo_model_params_t *mp, double dt, int cur_step, int *picard_iters, int *vcycles, hipStream_t st,
                              const int *active = nullptr);
 
-// ---- forcing and diagnostics of the members in one launch each (suhmo_step.hip: the device bodies of the per-level calls over OnMembers)
+// ---- forcing and diagnostics of the members in one launch each: the device bodies of the per-level calls over OnMembers
+// suhmo_forcing.hip
 // COMPUTE_TIMEVARYINGRECHARGE of the members `t` serves: SUHMO_F_MSRC from the resident SUHMO_F_ZS, temperature and background input per member
 int launch_time_varying_recharge(const OnMembers &t, const PerMember &TK, const PerMember &background, hipStream_t st);
 // one moulin list on one view, what the three moulin kernels work on: a level, box or patch passes it by value, an ensemble keeps a device row per member
@@ -65,6 +66,7 @@ struct MoulinJob {
 // the lists of the members in `sel` (rows[k]: member k's, on the device; nmax: the longest of them): three launches.  tf != NULL: the time
 // factors of this launch, by value, instead of the rows' (a run writes the rows once and changes the factor every step)
 int suhmo_batch_moulin_launch(const MoulinJob *rows, const BatchSel &sel, int nx, int ny, int nmax, hipStream_t st, const PerMember *tf = nullptr);
+// suhmo_postproc.hip
 // column sums of the SHMIP tables (suhmo_level_postproc_partial), out[k][8][nx] for every member k `t` serves; t.mp: the members' device rows
 int launch_postproc_columns(const OnMembers &t, double *out, hipStream_t st);
 // suhmo_postproc_temporal of those column sums on the device: out[k][6] for every member k `t` serves (one row of a run's series)

@@ -264,6 +264,14 @@ inline int multi_of(suhmo_hier *H, int l, hipStream_t st, suhmo_multi &m)
     if (V.part) { m.dv += V.b0; m.fp += V.b0; m.nbox = V.nown; m.push = nullptr; m.pbase = nullptr; }   // owner computes: the tables from this rank's first box
     return 0;
 }
+// level l as the target of one launcher: f(on_level(base, 0)) for level 0, f(all boxes of level l) for l >= 1 (f: a generic lambda)
+template <class F> inline int on_hier_level(suhmo_hier *H, int l, hipStream_t st, F &&f)
+{
+    if (l == 0) return f(on_level(base_of(H), 0));
+    suhmo_multi m;
+    int rc = multi_of(H, l, st, m);
+    return rc ? rc : f(m.on());
+}
 // the launchers of the plans (what each does: at its definition)
 int hier_ff(suhmo_hier *H, int l, int f0, int f1, bool corners, hipStream_t st, int colour = -1);
 int hier_cf(suhmo_hier *H, int l, int ff, int fc, hipStream_t st, int ff1 = -1, int fc1 = -1);
@@ -290,12 +298,18 @@ int suhmo_hier_gap_(suhmo_hier *H, const suhmo_model_params_t *mp, double dt, su
 int suhmo_hier_create_on_(suhmo_hier **out, const suhmo_level_desc_t *base, suhmo_level *adopt, int nlev, const int *nbox, const int *boxes, const char *options);
 std::string suhmo_hier_options_(const suhmo_hier *H);                               // the options as they are now, "key=value,..."
 int suhmo_hier_check_(suhmo_hier *H);                                               // what every C-ABI entry of a hierarchy does first
-// ---- suhmo_step.hip: what the run of a hierarchy (suhmo_run.hip) needs of the forcing and the diagnostics
+// ---- what the run of a hierarchy (suhmo_run.hip) needs of the time step, the forcing and the diagnostics
+int suhmo_step_check_args_(const suhmo_model_params_t *mp, double dt, int cur_step);   // suhmo_step.hip
+// suhmo_forcing.hip
 int suhmo_hier_recharge_check_(suhmo_hier *H, const char *who);                      // rank strips: -5; a box without SUHMO_F_ZS: -1, naming it
 int suhmo_hier_recharge_launch_(suhmo_hier *H, double T_K, double background_input, hipStream_t st);      // one launch per level
+// suhmo_postproc.hip
 int suhmo_level_postproc_row_check_(suhmo_level *L, const suhmo_model_params_t *mp, bool forcing_writes_source);
 int suhmo_level_postproc_row_launch_(suhmo_level *L, const suhmo_model_params_t *mp, double *cols, double *out6, hipStream_t st);
-int suhmo_step_check_args_(const suhmo_model_params_t *mp, double dt, int cur_step);
+// ---- what suhmo_step.hip and suhmo_forcing.hip share: the cells of a region that do not count (a finer level covers them), and the check
+// of nested levels (suhmo_amr.hip)
+struct Excl { int i0, j0, i1, j1; };       // local cells [i0, i1) x [j0, j1)
+int suhmo_amr_check_hierarchy(suhmo_level_t **lv, int nlev);
 // ---- suhmo_snap.hip: what the run needs of the snapshot -- its refusals, and the offsets (level_offset [nlev + 1], box_offset, either may be NULL) -> doubles in all
 int suhmo_hier_snapshot_check_(const suhmo_hier *H, const char *who, int ncomp, const suhmo_snap_comp_t *comps, int ghost);
 long suhmo_hier_snapshot_sizes_(const suhmo_hier *H, int ncomp, int ghost, long *level_offset, long *box_offset);

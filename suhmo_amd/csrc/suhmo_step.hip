@@ -201,7 +201,6 @@ int suhmo_batch_gap_store(const OnMembers &h, const OnMembers &g, size_t elems, 
 static int keep_icefree(suhmo_level *L, suhmo_level *G, hipStream_t st) { return launch_keep_icefree(on_level(L, 0), on_level(G, 0), st); }
 
 // Picard convergence test, :3169-3185
-struct Excl { int i0, j0, i1, j1; };       // local cells [i0, i1) x [j0, j1) do not count (covered by a finer level)
 static int exchange1(suhmo_level *L, int f, hipStream_t st) { return suhmo_exchange_list(L, 0, &f, 1, st); }
 // Both numbers of the Picard test in one pass and one read-back: max h and max |h_lagged - h|.  The reference's
 // max |(h_lagged - h) / maxHead| is the second divided by |maxHead| afterwards: a correctly rounded division by a fixed
@@ -376,6 +375,19 @@ static int level_melt(suhmo_level *L, const suhmo_model_params_t *mp, double dt,
 // linear operator (alpha = 1, aCoef = 1, beta = dt diffFactor, bCoef = D, no nonlinear term), FixedNeumBCFill = Neumann 0.
 // [Chombo] VCAMRPoissonOp2 / AMRMultiGrid are not in the reference's tree: the cycle is the FAS cycle of suhmo_fas.hip,
 // which for a linear operator converges to the same solution (oracle/time_loop.c:solve_gap_implicit does the same).
+// this step's data of a level handle -> its gap handle G (canvases of one size), and the halo rows of G on a rank strip
+static int gap_load(suhmo_level *L, suhmo_level *G, hipStream_t st)
+{
+    Depth &D = L->d[0], &GD = G->d[0];
+    const size_t bytes = D.elems * sizeof(double);
+    HIPCHK(hipMemcpyAsync(GD.fp.f[SUHMO_F_PHI], D.fp.f[SUHMO_F_B], bytes, hipMemcpyDeviceToDevice, st));      // initial guess = b :3382-3385
+    HIPCHK(hipMemcpyAsync(GD.fp.f[SUHMO_F_RHS], D.fp.f[SUHMO_F_RES], bytes, hipMemcpyDeviceToDevice, st));
+    HIPCHK(hipMemcpyAsync(GD.fp.f[SUHMO_F_BX], D.fp.f[SUHMO_F_DCX], bytes, hipMemcpyDeviceToDevice, st));
+    HIPCHK(hipMemcpyAsync(GD.fp.f[SUHMO_F_BY], D.fp.f[SUHMO_F_DCY], bytes, hipMemcpyDeviceToDevice, st));
+    GD.phi_fresh = 0;
+    static const int halo_fields[] = {SUHMO_F_RHS, SUHMO_F_ACOEF, SUHMO_F_BX, SUHMO_F_BY};
+    return suhmo_exchange_list(G, 0, halo_fields, 4, st);
+}
 // the second handle of a level (created on first use / when dt changes) loaded with this step's data
 static int gap_level_prepare(suhmo_level *L, const suhmo_model_params_t *mp, double dt, hipStream_t st)
 {
@@ -402,16 +414,8 @@ static int gap_level_prepare(suhmo_level *L, const suhmo_model_params_t *mp, dou
         G->ag = L->ag; G->ag_user = L->ag_user; G->agg_min_cells = L->agg_min_cells;
         int rca = suhmo_agg_setup(G); if (rca) return rca;
     }       // same strip, same neighbours
-    Depth &GD = G->d[0];
-    if (GD.elems != D.elems) { suhmo_set_error("internal: gap level geometry"); return -4; }
-    const size_t bytes = D.elems * sizeof(double);
-    HIPCHK(hipMemcpyAsync(GD.fp.f[SUHMO_F_PHI], D.fp.f[SUHMO_F_B], bytes, hipMemcpyDeviceToDevice, st));      // initial guess = b :3382-3385
-    HIPCHK(hipMemcpyAsync(GD.fp.f[SUHMO_F_RHS], D.fp.f[SUHMO_F_RES], bytes, hipMemcpyDeviceToDevice, st));
-    HIPCHK(hipMemcpyAsync(GD.fp.f[SUHMO_F_BX], D.fp.f[SUHMO_F_DCX], bytes, hipMemcpyDeviceToDevice, st));
-    HIPCHK(hipMemcpyAsync(GD.fp.f[SUHMO_F_BY], D.fp.f[SUHMO_F_DCY], bytes, hipMemcpyDeviceToDevice, st));
-    GD.phi_fresh = 0;
-    static const int halo_fields[] = {SUHMO_F_RHS, SUHMO_F_ACOEF, SUHMO_F_BX, SUHMO_F_BY};
-    return suhmo_exchange_list(G, 0, halo_fields, 4, st);
+    if (G->d[0].elems != D.elems) { suhmo_set_error("internal: gap level geometry"); return -4; }
+    return gap_load(L, G, st);
 }
 static void gap_solver_params(suhmo_solver_params_t &sp, int cur_step)
 {
@@ -425,6 +429,25 @@ static void head_solver_params(suhmo_solver_params_t &sp, int cur_step)
     sp.eps = 1.0e-7; sp.hang = 0.01; sp.norm_thresh = 1.0e-7; sp.bcoeff_otf = 1; sp.max_depth = -1;
     if (cur_step < 50) { sp.num_bottom = 10; sp.eps = 1.0e-10; sp.hang = 0.0001; sp.imin = 20; }
 }
+// ghosts of b of level l of nested levels (one level: lv = &L, l = 0): PiecewiseLinearFillPatch on coarse-fine sides (from the coarser
+// level's current b, whose halo rows were exchanged just before), copies on domain sides (:3419-3420 / :3451-3452), halo rows on rank boundaries
+static int amr_gap_ghosts(suhmo_level_t **lv, int l, hipStream_t st)
+{
+    int rc;
+    if (!lv[l]) return 0;
+    if (l > 0 && (rc = suhmo_amr2_pwl_fill(lv[l - 1], lv[l], SUHMO_F_B, SUHMO_F_B, (suhmo_stream_t)st))) return rc;
+    if ((rc = suhmo_copy_ghosts(lv[l], 0, SUHMO_F_B, st))) return rc;
+    return exchange1(lv[l], SUHMO_F_B, st);
+}
+// the solution back into level l: cells without ice keep their b if asked, PHI of the gap handle G -> b, the ghosts of b
+static int gap_store(suhmo_level_t **lv, int l, suhmo_level *G, const suhmo_model_params_t *mp, hipStream_t st)
+{
+    int rc;
+    Depth &D = lv[l]->d[0];
+    if (mp->freeze_icefree_gap && (rc = keep_icefree(lv[l], G, st))) return rc;
+    HIPCHK(hipMemcpyAsync(D.fp.f[SUHMO_F_B], G->d[0].fp.f[SUHMO_F_PHI], D.elems * sizeof(double), hipMemcpyDeviceToDevice, st));
+    return amr_gap_ghosts(lv, l, st);
+}
 static int solve_gap_implicit(suhmo_level *L, const suhmo_model_params_t *mp, double dt, int cur_step, hipStream_t st)
 {
     int rc = gap_level_prepare(L, mp, dt, st); if (rc) return rc;
@@ -433,14 +456,20 @@ static int solve_gap_implicit(suhmo_level *L, const suhmo_model_params_t *mp, do
     suhmo_solver_params_t sp;
     gap_solver_params(sp, cur_step);
     if ((rc = suhmo_level_solve(G, &sp, nullptr, nullptr, (suhmo_stream_t)st))) return rc;
-    if (mp->freeze_icefree_gap && (rc = keep_icefree(L, G, st))) return rc;
-    HIPCHK(hipMemcpyAsync(L->d[0].fp.f[SUHMO_F_B], G->d[0].fp.f[SUHMO_F_PHI], L->d[0].elems * sizeof(double), hipMemcpyDeviceToDevice, st));
-    return 0;
+    return gap_store(&L, 0, G, mp, st);
 }
 
 // ------------------------------------------------------------------ AmrHydro::timeStepFAS, once for every level layout
 // the checks every time step starts with, and the fields of every level its phases write
 static const int step_fields[] = {SUHMO_F_MR, SUHMO_F_PW, SUHMO_F_QWX, SUHMO_F_QWY, SUHMO_F_HLAG, SUHMO_F_CD, SUHMO_F_GRADX, SUHMO_F_GRADY, SUHMO_F_RE};
+static int alloc_step_fields(suhmo_level *L)
+{
+    for (int f : step_fields) if (!suhmo_field(L, 0, f)) { suhmo_set_error("field allocation failed"); return -2; }
+    return 0;
+}
+static bool lacks_source(const suhmo_level *L, const suhmo_model_params_t *mp) { return mp->use_moulin_source && !L->d[0].fp.f[SUHMO_F_MSRC]; }
+// a rank strip (of a whole level: rk = ext) exchanges halo rows and reduces the Picard test through the hooks
+static bool strip_without_hooks(const suhmo_level *L) { const DV &v = L->d[0].v; return (v.rk[0] || v.rk[1]) && !(L->ex && L->ar); }
 static int check_step_args(const suhmo_model_params_t *mp, double dt, int cur_step)
 {
     ARG(mp); ARG(dt > 0 && cur_step >= 1);
@@ -517,7 +546,7 @@ struct OneLevel {
     int nlev = 1;
     int nmem = 1;
     bool select(const char *still) { return still[0] != 0; }
-    int gap_ghosts(int) { int rc = suhmo_copy_ghosts(base, 0, SUHMO_F_B, st); return rc ? rc : exchange1(base, SUHMO_F_B, st); }   // :3419-3420 / :3451-3452
+    int gap_ghosts(int) { return amr_gap_ghosts(&base, 0, st); }
     int lag_head()
     {
         Depth &D = base->d[0];
@@ -538,11 +567,7 @@ struct OneLevel {
         return ::picard_maxima(base, maxh, maxd, st, Excl{0, 0, 0, 0}, false, true);
     }
     int melt_final(int, const suhmo_model_params_t *mp, double dt) { return level_melt(base, mp, dt, 1, false, st); }
-    int solve_gap(const suhmo_model_params_t *mp, double dt, int cur_step)
-    {
-        int rc = solve_gap_implicit(base, mp, dt, cur_step, st);
-        return rc ? rc : gap_ghosts(0);
-    }
+    int solve_gap(const suhmo_model_params_t *mp, double dt, int cur_step) { return solve_gap_implicit(base, mp, dt, cur_step, st); }
 };
 
 extern "C" int suhmo_level_timestep(suhmo_level_t *L, const suhmo_model_params_t *mp, double dt, int cur_step,
@@ -553,10 +578,10 @@ extern "C" int suhmo_level_timestep(suhmo_level_t *L, const suhmo_model_params_t
     int rc = check_step_args(mp, dt, cur_step); if (rc) return rc;
     Depth &D = L->d[0];
     if (L->desc.nx_global > 0 || (D.v.ext[0] && !D.v.rk[0]) || (D.v.ext[1] && !D.v.rk[1])) { suhmo_set_error("timestep on an AMR patch is not built yet"); return -5; }
-    if ((D.v.ext[0] || D.v.ext[1]) && !(L->ex && L->ar)) { suhmo_set_error("timestep on a rank strip needs the exchange hooks (suhmo_level_attach_rccl / suhmo_level_set_hooks)"); return -1; }
+    if (strip_without_hooks(L)) { suhmo_set_error("timestep on a rank strip needs the exchange hooks (suhmo_level_attach_rccl / suhmo_level_set_hooks)"); return -1; }
     HIPCHK(hipSetDevice(L->device));
-    if (mp->use_moulin_source && !L->d[0].fp.f[SUHMO_F_MSRC]) { suhmo_set_error("use_moulin_source without suhmo_level_moulin_source"); return -1; }
-    for (int f : step_fields) if (!suhmo_field(L, 0, f)) { suhmo_set_error("field allocation failed"); return -2; }
+    if (lacks_source(L, mp)) { suhmo_set_error("use_moulin_source without suhmo_level_moulin_source"); return -1; }
+    if ((rc = alloc_step_fields(L))) return rc;
     OneLevel y{L, (hipStream_t)s};
     return timestep_fas(y, mp, dt, cur_step, picard_iters, vcycles);
 }
@@ -659,8 +684,8 @@ int suhmo_batch_timestep_run(suhmo_batch *B, const suhmo_model_params_t *mp, dou
     for (int k = 0; k < suhmo_batch_size_(B); k++) {
         if (!serve[k]) continue;
         suhmo_level *L = suhmo_batch_member(B, k);
-        if (mp[k].use_moulin_source && !L->d[0].fp.f[SUHMO_F_MSRC]) { suhmo_set_error("use_moulin_source without suhmo_level_moulin_source (member %d)", k); return -1; }
-        for (int f : step_fields) if (!suhmo_field(L, 0, f)) { suhmo_set_error("field allocation failed"); return -2; }
+        if (lacks_source(L, &mp[k])) { suhmo_set_error("use_moulin_source without suhmo_level_moulin_source (member %d)", k); return -1; }
+        if ((rc = alloc_step_fields(L))) return rc;
         if (mp[k].diffFactor != 0.0) for (int f : {SUHMO_F_DCX, SUHMO_F_DCY, SUHMO_F_DTERM}) if (!suhmo_field(L, 0, f)) { suhmo_set_error("field allocation failed"); return -2; }
     }
     if ((rc = suhmo_batch_step_begin(B, mp, st, active ? serve : nullptr))) return rc;
@@ -700,17 +725,6 @@ static Excl covered_by(suhmo_level_t **lv, int nlev, int l)
     const DV &vf = lv[l + 1]->d[0].v, &v = lv[l]->d[0].v;
     return Excl{vf.i0 / 2 - v.i0, vf.j0 / 2 - v.j0, (vf.i0 + vf.nx) / 2 - v.i0, (vf.j0 + vf.ny) / 2 - v.j0};
 }
-// ghosts of b of every level: PiecewiseLinearFillPatch on coarse-fine sides (from the coarser level's current b, whose halo
-// rows were exchanged just before), copies on domain sides, halo rows on rank boundaries
-static int amr_gap_ghosts(suhmo_level_t **lv, int nlev, int l, hipStream_t st)
-{
-    int rc;
-    if (!lv[l]) return 0;
-    if (l > 0 && (rc = suhmo_amr2_pwl_fill(lv[l - 1], lv[l], SUHMO_F_B, SUHMO_F_B, (suhmo_stream_t)st))) return rc;
-    if ((rc = suhmo_copy_ghosts(lv[l], 0, SUHMO_F_B, st))) return rc;
-    return exchange1(lv[l], SUHMO_F_B, st);
-}
-int suhmo_amr_check_hierarchy(suhmo_level_t **lv, int nlev);      // suhmo_amr.hip
 
 struct Nested {
     suhmo_level_t **lv;
@@ -720,7 +734,7 @@ struct Nested {
     hipStream_t st;
     int nmem = 1;
     bool select(const char *still) { return still[0] != 0; }
-    int gap_ghosts(int l) { return amr_gap_ghosts(lv, nlev, l, st); }
+    int gap_ghosts(int l) { return amr_gap_ghosts(lv, l, st); }
     int lag_head()
     {
         int rc;
@@ -729,7 +743,7 @@ struct Nested {
             Depth &D = lv[l]->d[0];
             if ((rc = exchange1(lv[l], SUHMO_F_MR, st))) return rc;                    // levelmR.exchange() :2513 (and the stencil of the fill below)
             if (l > 0 && (rc = suhmo_amr2_pwl_fill(lv[l - 1], lv[l], SUHMO_F_MR, SUHMO_F_MR, (suhmo_stream_t)st))) return rc;
-            if ((rc = amr_gap_ghosts(lv, nlev, l, st))) return rc;
+            if ((rc = amr_gap_ghosts(lv, l, st))) return rc;
             HIPCHK(hipMemcpyAsync(D.fp.f[SUHMO_F_HLAG], D.fp.f[SUHMO_F_PHI], D.elems * sizeof(double), hipMemcpyDeviceToDevice, st));
         }
         return 0;
@@ -793,13 +807,7 @@ struct Nested {
         if (nlev == 1) rc = suhmo_level_solve(gaps[0], &spg, nullptr, nullptr, s);
         else rc = suhmo_amr_solve(gaps, nlev, &spg, nullptr, nullptr, s);
         if (rc) return rc;
-        for (int l = 0; l < nlev; l++) {
-            if (!lv[l]) continue;
-            Depth &D = lv[l]->d[0];
-            if (mp->freeze_icefree_gap && (rc = keep_icefree(lv[l], gaps[l], st))) return rc;
-            HIPCHK(hipMemcpyAsync(D.fp.f[SUHMO_F_B], gaps[l]->d[0].fp.f[SUHMO_F_PHI], D.elems * sizeof(double), hipMemcpyDeviceToDevice, st));
-            if ((rc = amr_gap_ghosts(lv, nlev, l, st))) return rc;
-        }
+        for (int l = 0; l < nlev; l++) if (lv[l] && (rc = gap_store(lv, l, gaps[l], mp, st))) return rc;
         return 0;
     }
 };
@@ -815,14 +823,12 @@ extern "C" int suhmo_amr_timestep(suhmo_level_t **lv, int nlev, const suhmo_mode
     for (int l = 0; l < nlev; l++) {
         if (!lv[l]) { strips = true; continue; }
         const DV &v = lv[l]->d[0].v;
-        if (v.rk[0] || v.rk[1]) {
-            strips = true;
-            if (!(lv[l]->ex && lv[l]->ar)) { suhmo_set_error("time step on rank strips needs the exchange hooks on every level"); return -1; }
-        }
-        if (mp->use_moulin_source && !lv[l]->d[0].fp.f[SUHMO_F_MSRC]) { suhmo_set_error("use_moulin_source without a moulin source term (SUHMO_F_MSRC)"); return -1; }
+        if (v.rk[0] || v.rk[1]) strips = true;
+        if (strip_without_hooks(lv[l])) { suhmo_set_error("time step on rank strips needs the exchange hooks on every level"); return -1; }
+        if (lacks_source(lv[l], mp)) { suhmo_set_error("use_moulin_source without a moulin source term (SUHMO_F_MSRC)"); return -1; }
     }
     HIPCHK(hipSetDevice(lv[0]->device));
-    for (int l = 0; l < nlev; l++) if (lv[l]) for (int f : step_fields) if (!suhmo_field(lv[l], 0, f)) { suhmo_set_error("field allocation failed"); return -2; }
+    for (int l = 0; l < nlev; l++) if (lv[l] && (rc = alloc_step_fields(lv[l]))) return rc;
     Nested y{lv, nlev, strips, lv[0], (hipStream_t)s};
     return timestep_fas(y, mp, dt, cur_step, picard_iters, vcycles);
 }
@@ -831,68 +837,55 @@ extern "C" int suhmo_amr_timestep(suhmo_level_t **lv, int nlev, const suhmo_mode
 // oracle/amr_step_m.c: suhmo_amr_timestep with every level's rectangle replaced by its boxes; after every fill of data ghosts
 // the reference's exchange() is the fine-fine copy between the boxes of the level (suhmo_hier.hip).  Every phase of a level
 // >= 1 is ONE launch over all its boxes (blockIdx.z = box, device tables of views and field pointers).
+// One launcher on a whole level goes through on_hier_level (suhmo_hier_int.h); where level 0 does something different in kind (an exchange
+// with the neighbouring strips, a whole-canvas copy), the branch on l == 0 is written out.
 namespace {
-// a level of the hierarchy as a launch target: level 0 = the base handle, level l >= 1 = all its boxes at once
-struct LevT { suhmo_level *base; suhmo_multi m; };
-int lev_target(suhmo_hier *H, int l, hipStream_t st, LevT &t)
-{
-    t.base = nullptr;
-    if (l == 0) { t.base = H->lev[0].box[0]; return 0; }
-    return multi_of(H, l, st, t.m);
-}
 int hier_chain(suhmo_hier *H, int l, hipStream_t st)
 {
     int rc;
-    LevT t;
-    if ((rc = lev_target(H, l, st, t))) return rc;
+    suhmo_multi m;
     if ((rc = hier_cf(H, l, SUHMO_F_PHI, SUHMO_F_PHI, st))) return rc;                  // inside compGradientMAC
     if ((rc = hier_ff(H, l, SUHMO_F_PHI, -1, false, st))) return rc;
-    if (t.base) rc = suhmo_grad_cc(t.base, 0, st); else rc = suhmo_multi_grad_cc(t.m, st);
+    if (l == 0) rc = suhmo_grad_cc(base_of(H), 0, st);                                  // (rank strips: with the halo rows of h)
+    else if (!(rc = multi_of(H, l, st, m))) rc = suhmo_multi_grad_cc(m, st);
     if (rc) return rc;
     if ((rc = hier_cf(H, l, SUHMO_F_GRADX, SUHMO_F_GRADX, st, SUHMO_F_GRADY, SUHMO_F_GRADY))) return rc;   // :1650-1659
     if ((rc = hier_ff(H, l, SUHMO_F_GRADX, SUHMO_F_GRADY, true, st))) return rc;
-    rc = t.base ? launch_re(on_level(t.base, 0), st) : launch_re(t.m.on(), st);
-    if (rc) return rc;
+    if ((rc = on_hier_level(H, l, st, [&](const auto &t) { return launch_re(t, st); }))) return rc;
     if ((rc = hier_pwl(H, l, SUHMO_F_RE, SUHMO_F_RE, st))) return rc;                   // :2711-2721
     if ((rc = hier_ff(H, l, SUHMO_F_RE, -1, true, st))) return rc;
-    return t.base ? launch_qw_faces(on_level(t.base, 0), st) : launch_qw_faces(t.m.on(), st);
+    return on_hier_level(H, l, st, [&](const auto &t) { return launch_qw_faces(t, st); });
 }
 // ghosts of b of level l: PiecewiseLinearFillPatch on coarse-fine cells, exchange between the boxes, copies on domain sides
 int hier_gap_ghosts(suhmo_hier *H, int l, hipStream_t st)
 {
     int rc;
-    LevT t;
-    if ((rc = lev_target(H, l, st, t))) return rc;
+    if (l == 0) { suhmo_level *base = base_of(H); return amr_gap_ghosts(&base, 0, st); }      // (rank strips: with the halo rows)
     if ((rc = hier_pwl(H, l, SUHMO_F_B, SUHMO_F_B, st))) return rc;
     if ((rc = hier_ff(H, l, SUHMO_F_B, -1, true, st))) return rc;
-    if (t.base) { if ((rc = suhmo_copy_ghosts(t.base, 0, SUHMO_F_B, st))) return rc; return exchange1(t.base, SUHMO_F_B, st); }   // rank strips: halo rows
-    return launch_coef_ghosts(t.m.on(), SUHMO_F_B, st);
+    suhmo_multi m;
+    if ((rc = multi_of(H, l, st, m))) return rc;
+    return launch_coef_ghosts(m.on(), SUHMO_F_B, st);
 }
 // lagged diffusion terms (diffusion_terms of one level) and RHS_h / the gap-height right-hand side of a whole level
 int hier_melt(suhmo_hier *H, int l, const suhmo_model_params_t *mp, double dt, int final_, bool diffusion, hipStream_t st)
 {
     int rc;
-    LevT t;
-    if ((rc = lev_target(H, l, st, t))) return rc;
-    if (t.base) return level_melt(t.base, mp, dt, final_, diffusion, st);
-    const suhmo_multi &m = t.m;
+    if (l == 0) return level_melt(base_of(H), mp, dt, final_, diffusion, st);       // (rank strips: with the halo rows of mR)
     if (diffusion) for (int f : {SUHMO_F_DCX, SUHMO_F_DCY, SUHMO_F_DTERM}) if ((rc = ensure_field(H, l, f))) return rc;
+    suhmo_multi m;
+    if ((rc = multi_of(H, l, st, m))) return rc;                             // the tables after the allocation
     if (m.nbox <= 0) return 0;                                               // owner computes: none of this level's boxes is this rank's
-    if (diffusion) {
-        if ((rc = lev_target(H, l, st, t))) return rc;                       // the tables after the allocation
-        if ((rc = launch_diffusion_terms(stepping(m.on(), *mp), st))) return rc;
-    }
+    if (diffusion && (rc = launch_diffusion_terms(stepping(m.on(), *mp), st))) return rc;
     return launch_melt(stepping(m.on(), *mp), final_, dt, st);
 }
 // max h and max |h_lagged - h| over the cells of level l no finer level covers
 int hier_picard_maxima(suhmo_hier *H, int l, bool covered, double *maxh, double *maxd, hipStream_t st)
 {
     int rc;
-    LevT t;
-    if ((rc = lev_target(H, l, st, t))) return rc;
-    suhmo_level *slot = H->lev[0].box[0];
-    if (t.base) {
-        suhmo_level *L = t.base;
+    suhmo_level *slot = base_of(H);
+    if (l == 0) {
+        suhmo_level *L = slot;
         if ((rc = picard_maxima(L, maxh, maxd, st, Excl{0, 0, 0, 0}, covered))) return rc;
         if (L->ar && (L->d[0].v.rk[0] || L->d[0].v.rk[1])) {                     // computeMax over the ranks of level 0
             if ((rc = L->ar(L->user, maxh))) return rc;
@@ -900,7 +893,8 @@ int hier_picard_maxima(suhmo_hier *H, int l, bool covered, double *maxh, double 
         }
         return 0;
     }
-    const suhmo_multi &m = t.m;
+    suhmo_multi m;
+    if ((rc = multi_of(H, l, st, m))) return rc;
     *maxh = -1.0e300; *maxd = 0.0;
     if (m.nbox > 0) {
         int np;
@@ -940,12 +934,8 @@ struct BoxUnions {
     int head_rhs(const suhmo_model_params_t *mp, double dt)
     {
         int rc;
-        for (int l = 0; l < nlev; l++) {                                                        // aCoeff_bCoeff :3087-3102
-            LevT t;
-            if ((rc = lev_target(H, l, st, t))) return rc;
-            rc = t.base ? launch_bcoef_faces(on_level(t.base, 0), st) : launch_bcoef_faces(t.m.on(), st);
-            if (rc) return rc;
-        }
+        for (int l = 0; l < nlev; l++)                                                          // aCoeff_bCoeff :3087-3102
+            if ((rc = on_hier_level(H, l, st, [&](const auto &t) { return launch_bcoef_faces(t, st); }))) return rc;
         for (int l = 0; l < nlev; l++) if ((rc = hier_melt(H, l, mp, dt, 0, mp->diffFactor != 0.0, st))) return rc;
         return exchange1(base, SUHMO_F_RHS, st);                                                // rank strips: halo rows relaxed redundantly
     }
@@ -978,48 +968,29 @@ struct BoxUnions {
         int rc;
         suhmo_hier *G = nullptr;
         if ((rc = suhmo_hier_gap_(H, mp, dt, &G))) return rc;
-        for (int l = 0; l < nlev; l++) {
-            const auto &hb = H->lev[l].box, &gb = G->lev[l].box;
-            if (l > 0) {                                               // all boxes of a level: one launch
-                static const int fd[4] = {SUHMO_F_PHI, SUHMO_F_RHS, SUHMO_F_BX, SUHMO_F_BY}, fs[4] = {SUHMO_F_B, SUHMO_F_RES, SUHMO_F_DCX, SUHMO_F_DCY};
-                for (int f : fs) if ((rc = ensure_field(H, l, f))) return rc;
-                for (int f : fd) if ((rc = ensure_field(G, l, f))) return rc;
-                suhmo_multi mh, mg;
-                if ((rc = multi_of(H, l, st, mh)) || (rc = multi_of(G, l, st, mg))) return rc;
-                if ((rc = launch_copy_between(mg.on(), mh.on(), fd, fs, 4, st))) return rc;                                     // initial guess = b :3382-3385
-                for (suhmo_level *L : gb) L->d[0].phi_fresh = 0;
-                continue;
-            }
-            for (size_t k = 0; k < hb.size(); k++) {
-                Depth &D = hb[k]->d[0], &GD = gb[k]->d[0];
-                if (GD.elems != D.elems) { suhmo_set_error("internal: gap hierarchy geometry"); return -4; }
-                const size_t bytes = D.elems * sizeof(double);
-                HIPCHK(hipMemcpyAsync(GD.fp.f[SUHMO_F_PHI], D.fp.f[SUHMO_F_B], bytes, hipMemcpyDeviceToDevice, st));      // initial guess = b :3382-3385
-                HIPCHK(hipMemcpyAsync(GD.fp.f[SUHMO_F_RHS], D.fp.f[SUHMO_F_RES], bytes, hipMemcpyDeviceToDevice, st));
-                HIPCHK(hipMemcpyAsync(GD.fp.f[SUHMO_F_BX], D.fp.f[SUHMO_F_DCX], bytes, hipMemcpyDeviceToDevice, st));
-                HIPCHK(hipMemcpyAsync(GD.fp.f[SUHMO_F_BY], D.fp.f[SUHMO_F_DCY], bytes, hipMemcpyDeviceToDevice, st));
-                GD.phi_fresh = 0;
-            }
+        suhmo_level *gbase = base_of(G);
+        if (gbase->d[0].elems != base->d[0].elems) { suhmo_set_error("internal: gap hierarchy geometry"); return -4; }
+        if ((rc = gap_load(base, gbase, st))) return rc;               // level 0: one handle, as gap_level_prepare loads it
+        for (int l = 1; l < nlev; l++) {                               // all boxes of a level: one launch
+            static const int fd[4] = {SUHMO_F_PHI, SUHMO_F_RHS, SUHMO_F_BX, SUHMO_F_BY}, fs[4] = {SUHMO_F_B, SUHMO_F_RES, SUHMO_F_DCX, SUHMO_F_DCY};
+            for (int f : fs) if ((rc = ensure_field(H, l, f))) return rc;
+            for (int f : fd) if ((rc = ensure_field(G, l, f))) return rc;
+            suhmo_multi mh, mg;
+            if ((rc = multi_of(H, l, st, mh)) || (rc = multi_of(G, l, st, mg))) return rc;
+            if ((rc = launch_copy_between(mg.on(), mh.on(), fd, fs, 4, st))) return rc;                                         // initial guess = b :3382-3385
+            for (suhmo_level *L : G->lev[l].box) L->d[0].phi_fresh = 0;
         }
-        {   static const int halo_fields[] = {SUHMO_F_RHS, SUHMO_F_ACOEF, SUHMO_F_BX, SUHMO_F_BY};          // rank strips
-            if ((rc = suhmo_exchange_list(G->lev[0].box[0], 0, halo_fields, 4, st))) return rc; }
-        if ((rc = suhmo_level_build_mg_coefficients(G->lev[0].box[0], (suhmo_stream_t)st))) return rc;
+        if ((rc = suhmo_level_build_mg_coefficients(gbase, (suhmo_stream_t)st))) return rc;
         suhmo_solver_params_t spg;
         gap_solver_params(spg, cur_step);
         if ((rc = suhmo_hier_solve(G, &spg, nullptr, nullptr, (suhmo_stream_t)st))) return rc;
-        for (int l = 0; l < nlev; l++) {
-            const auto &hb = H->lev[l].box, &gb = G->lev[l].box;
-            if (l > 0) {
-                static const int fd[1] = {SUHMO_F_B}, fs[1] = {SUHMO_F_PHI};
-                suhmo_multi mh, mg;
-                if ((rc = multi_of(H, l, st, mh)) || (rc = multi_of(G, l, st, mg))) return rc;
-                if (mp->freeze_icefree_gap && (rc = launch_keep_icefree(mh.on(), mg.on(), st))) return rc;
-                if ((rc = launch_copy_between(mh.on(), mg.on(), fd, fs, 1, st))) return rc;
-            } else
-                for (size_t k = 0; k < hb.size(); k++) {
-                    if (mp->freeze_icefree_gap && (rc = keep_icefree(hb[k], gb[k], st))) return rc;
-                    HIPCHK(hipMemcpyAsync(hb[k]->d[0].fp.f[SUHMO_F_B], gb[k]->d[0].fp.f[SUHMO_F_PHI], hb[k]->d[0].elems * sizeof(double), hipMemcpyDeviceToDevice, st));
-                }
+        if ((rc = gap_store(&base, 0, gbase, mp, st))) return rc;
+        for (int l = 1; l < nlev; l++) {
+            static const int fd[1] = {SUHMO_F_B}, fs[1] = {SUHMO_F_PHI};
+            suhmo_multi mh, mg;
+            if ((rc = multi_of(H, l, st, mh)) || (rc = multi_of(G, l, st, mg))) return rc;
+            if (mp->freeze_icefree_gap && (rc = launch_keep_icefree(mh.on(), mg.on(), st))) return rc;
+            if ((rc = launch_copy_between(mh.on(), mg.on(), fd, fs, 1, st))) return rc;
             if ((rc = hier_gap_ghosts(H, l, st))) return rc;
         }
         return 0;
@@ -1041,633 +1012,11 @@ extern "C" int suhmo_hier_timestep(suhmo_hier_t *H, const suhmo_model_params_t *
         if (mp->use_moulin_source) {
             const int k0 = H->lev[l].first_owned(), nk = H->lev[l].n_owned();
             for (int k = k0; k < k0 + nk; k++)
-                if (!H->lev[l].box[k]->d[0].fp.f[SUHMO_F_MSRC]) { suhmo_set_error("use_moulin_source without a moulin source term (suhmo_hier_moulin_source)"); return -1; }
+                if (lacks_source(H->lev[l].box[k], mp)) { suhmo_set_error("use_moulin_source without a moulin source term (suhmo_hier_moulin_source)"); return -1; }
         }
     }
-    suhmo_level *base = H->lev[0].box[0];
-    if ((base->d[0].v.rk[0] || base->d[0].v.rk[1]) && !(base->ex && base->ar)) { suhmo_set_error("time step on rank strips needs the exchange hooks on level 0"); return -1; }
+    suhmo_level *base = base_of(H);
+    if (strip_without_hooks(base)) { suhmo_set_error("time step on rank strips needs the exchange hooks on level 0"); return -1; }
     BoxUnions y{H, nlev, base, (hipStream_t)s};
     return timestep_fas(y, mp, dt, cur_step, picard_iters, vcycles);
-}
-
-// ------------------------------------------------------------------ moulin source term
-// Calc_moulin_integral / Calc_moulin_source_term_distributed (src/AmrHydro.cpp:1866-2066).  The n x N array of the
-// reference (one component per moulin) is never stored: pass 1 integrates every Gaussian (per-tile partial sums in a
-// fixed order, then one block per moulin), pass 2 re-evaluates and normalises.  A Gaussian whose argument exceeds
-// 760 underflows to exactly 0 in the reference too, so tiles / cells that far away are skipped without changing a bit.
-namespace {
-__device__ __forceinline__ double moulin_cell(double xc, double yc, double dx, double dy, double mx, double my, double sg, bool &zero)
-{
-    const double l[3] = {-0.77459666924 / 2.0, 0.0, 0.77459666924 / 2.0};
-    const double v[3] = {0.5555555555, 0.8888888888, 0.5555555555};
-    const double k = -1.0 / (2.0 * sg * sg), prefac = 1.0 / (sg * sqrt(2.0 * 3.14));
-    double ex[3], ey[3];
-    for (int q = 0; q < 3; q++) { ex[q] = (xc + l[q]) * dx - mx; ey[q] = (yc + l[q]) * dy - my; }
-    double ax = fmin(fabs(ex[0]), fabs(ex[2])), ay = fmin(fabs(ey[0]), fabs(ey[2]));
-    if (ex[0] * ex[2] < 0.0) ax = 0.0;
-    if (ey[0] * ey[2] < 0.0) ay = 0.0;
-    zero = -k * (ax * ax + ay * ay) > 760.0;
-    if (zero) return 0.0;
-    double MS[9];
-    for (int b = 0; b < 3; b++)
-        for (int a = 0; a < 3; a++) { double rad = ex[a] * ex[a] + ey[b] * ey[b]; MS[3 * b + a] = prefac * exp(k * rad); }
-    return v[0] * v[0] * MS[0] + v[1] * v[0] * MS[1] + v[2] * v[0] * MS[2]
-         + v[0] * v[1] * MS[3] + v[1] * v[1] * MS[4] + v[2] * v[1] * MS[5]
-         + v[0] * v[2] * MS[6] + v[1] * v[2] * MS[7] + v[2] * v[2] * MS[8];
-}
-// the three device bodies work on one MoulinJob (suhmo_batch.h): one moulin list on one view.  They are launched over a level, a box or a patch
-// (OneMoulinList: the job by value) or over the members of an ensemble (MemberMoulinLists: a device row per member, blockIdx.z -> member)
-struct OneMoulinList {
-    MoulinJob j;
-    __device__ __forceinline__ const MoulinJob &job() const { return j; }
-    __device__ __forceinline__ double time_factor() const { return j.tf; }
-};
-struct MemberMoulinLists {
-    const MoulinJob *rows; BatchSel sel;
-    __device__ __forceinline__ const MoulinJob &job() const { return rows[batch_member(sel)]; }
-    __device__ __forceinline__ double time_factor() const { return job().tf; }
-};
-// the same rows under the time factors of one step of a run (suhmo_batch_run): by value with the launch, the rows are written once
-struct StepMoulinLists : MemberMoulinLists {
-    PerMember tf;
-    __device__ __forceinline__ double time_factor() const { return tf.x[batch_member(sel)]; }
-};
-__device__ __forceinline__ void d_moulin_partial(const DV &v, int n, const double *__restrict__ mo, double *__restrict__ partial, const Excl &ex,
-                                                 const double *__restrict__ cover)
-{
-    __shared__ double sm[256];
-    const int tid = threadIdx.y * 16 + threadIdx.x;
-    const int i = blockIdx.x * 16 + threadIdx.x, j = blockIdx.y * 16 + threadIdx.y;
-    bool in = i < v.nx && j < v.ny && !(i >= ex.i0 && i < ex.i1 && j >= ex.j0 && j < ex.j1);   // covered by a finer level: 0
-    if (in && cover && cover[cidx(v, i, j)] != 0.0) in = false;
-    const int blk = blockIdx.y * gridDim.x + blockIdx.x;
-    const double tx0 = (v.i0 + blockIdx.x * 16) * v.dx, tx1 = (v.i0 + blockIdx.x * 16 + 16) * v.dx;      // the tile in physical coordinates (a patch / box
-    const double ty0 = (v.j0 + blockIdx.y * 16) * v.dy, ty1 = (v.j0 + blockIdx.y * 16 + 16) * v.dy;      // starts at (i0, j0) of its level)
-    for (int m = 0; m < n; m++) {
-        const double mx = mo[3 * m], my = mo[3 * m + 1], sg = mo[3 * m + 2];
-        double ddx = mx < tx0 ? tx0 - mx : (mx > tx1 ? mx - tx1 : 0.0), ddy = my < ty0 ? ty0 - my : (my > ty1 ? my - ty1 : 0.0);
-        if ((ddx * ddx + ddy * ddy) / (2.0 * sg * sg) > 760.0) { if (tid == 0) partial[(size_t)blk * n + m] = 0.0; continue; }   // uniform
-        bool z;
-        double val = in ? moulin_cell(i + 0.5 + v.i0, j + 0.5 + v.j0, v.dx, v.dy, mx, my, sg, z) * v.dx * v.dy : 0.0;
-        sm[tid] = val;
-        __syncthreads();
-        for (int s = 128; s > 0; s >>= 1) { if (tid < s) sm[tid] = sm[tid] + sm[tid + s]; __syncthreads(); }
-        if (tid == 0) partial[(size_t)blk * n + m] = sm[0];
-        __syncthreads();
-    }
-}
-// one workgroup per moulin (blockIdx.x; the lists of an ensemble differ in length: a workgroup past the end of its member's list has nothing to do)
-__device__ __forceinline__ void d_moulin_final(const double *__restrict__ partial, int nblk, int n, double *__restrict__ integ)
-{
-    __shared__ double sm[256];
-    const int m = blockIdx.x, tid = threadIdx.x;
-    if (m >= n) return;                                                                                  // uniform
-    double acc = 0.0;
-    for (int b = tid; b < nblk; b += 256) acc = acc + partial[(size_t)b * n + m];
-    sm[tid] = acc;
-    __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) { if (tid < s) sm[tid] = sm[tid] + sm[tid + s]; __syncthreads(); }
-    if (tid == 0) integ[m] = sm[0];
-}
-__device__ __forceinline__ void d_moulin_src(const DV &v, int n, const double *__restrict__ mo, const double *__restrict__ flux,
-                                             const double *__restrict__ integ, double tf, double *__restrict__ out, const Excl &ex,
-                                             const double *__restrict__ cover)
-{
-    const int i = blockIdx.x * 16 + threadIdx.x, j = blockIdx.y * 16 + threadIdx.y;
-    if (i >= v.nx || j >= v.ny) return;
-    if ((i >= ex.i0 && i < ex.i1 && j >= ex.j0 && j < ex.j1) || (cover && cover[cidx(v, i, j)] != 0.0)) { out[cidx(v, i, j)] = 0.0; return; }   // filled by the average of the finer level
-    double sum = 0.0;
-    for (int m = 0; m < n; m++) {
-        bool z;
-        double val = moulin_cell(i + 0.5 + v.i0, j + 0.5 + v.j0, v.dx, v.dy, mo[3 * m], mo[3 * m + 1], mo[3 * m + 2], z);
-        if (!z) sum += val * tf / integ[m] * flux[m];
-    }
-    out[cidx(v, i, j)] = sum;
-}
-template <class J> __global__ __launch_bounds__(256) void k_moulin_partial(J t, Excl ex, const double *__restrict__ cover)
-{
-    const MoulinJob &j = t.job();
-    d_moulin_partial(j.v, j.n, j.mo, j.partial, ex, cover);
-}
-template <class J> __global__ void k_moulin_final(J t)
-{
-    const MoulinJob &j = t.job();
-    d_moulin_final(j.partial, j.nblk, j.n, j.integ);
-}
-template <class J> __global__ __launch_bounds__(256) void k_moulin_src(J t, Excl ex, const double *__restrict__ cover)
-{
-    const MoulinJob &j = t.job();
-    d_moulin_src(j.v, j.n, j.mo, j.flux, j.integ, t.time_factor(), j.out, ex, cover);
-}
-// the launchers: 16 x 16 tiles of the job's view (grd), one workgroup per moulin for the integrals; gz = 1, or the active members
-template <class J> void launch_moulin_partial(const J &t, dim3 grd, hipStream_t st, Excl ex, const double *cover = nullptr)
-{
-    hipLaunchKernelGGL(k_moulin_partial<J>, grd, dim3(16, 16), 0, st, t, ex, cover);
-}
-template <class J> void launch_moulin_final(const J &t, int nmax, int gz, hipStream_t st) { hipLaunchKernelGGL(k_moulin_final<J>, dim3(nmax, 1, gz), dim3(256), 0, st, t); }
-template <class J> void launch_moulin_src(const J &t, dim3 grd, hipStream_t st, Excl ex, const double *cover = nullptr)
-{
-    hipLaunchKernelGGL(k_moulin_src<J>, grd, dim3(16, 16), 0, st, t, ex, cover);
-}
-// one list on one view: the integration passes read v, n, mo, partial (nblk tiles), integ; the source pass v, n, mo, flux, integ, tf, out
-OneMoulinList moulin_integrals_on(const DV &v, int n, const double *mo, double *partial, size_t nblk, double *integ)
-{
-    return OneMoulinList{MoulinJob{v, n, (int)nblk, mo, nullptr, integ, partial, 0.0, nullptr}};
-}
-OneMoulinList moulin_source_on(const DV &v, int n, const double *mo, const double *flux, double *integ, double tf, double *out)
-{
-    return OneMoulinList{MoulinJob{v, n, 0, mo, flux, integ, nullptr, tf, out}};
-}
-}  // namespace
-// the lists of the active members of an ensemble (rows[k]: member k's, on the device; nmax: the longest list): three launches whatever their number
-// (tf != NULL: the time factors of this launch instead of the rows')
-int suhmo_batch_moulin_launch(const MoulinJob *rows, const BatchSel &sel, int nx, int ny, int nmax, hipStream_t st, const PerMember *tf)
-{
-    if (sel.n <= 0) return 0;
-    const MemberMoulinLists t{rows, sel};
-    const dim3 grd((nx + 15) / 16, (ny + 15) / 16, sel.n);
-    launch_moulin_partial(t, grd, st, Excl{0, 0, 0, 0});
-    launch_moulin_final(t, nmax, sel.n, st);
-    if (tf) launch_moulin_src(StepMoulinLists{{rows, sel}, *tf}, grd, st, Excl{0, 0, 0, 0});
-    else launch_moulin_src(t, grd, st, Excl{0, 0, 0, 0});
-    HIPCHK(hipGetLastError());
-    return 0;
-}
-
-extern "C" int suhmo_level_moulin_source(suhmo_level_t *L, int n, const double *positions, const double *sigma,
-                                         const double *flux, double time_factor, double *integrals, suhmo_stream_t s)
-{
-    SUHMO_TIME("AmrHydro::Calc_moulin_source_term_distributed");
-    ARG(L && n >= 1 && positions && sigma && flux);
-    HIPCHK(hipSetDevice(L->device));
-    hipStream_t st = (hipStream_t)s;
-    Depth &D = L->d[0];
-    if (L->desc.nx_global > 0) { suhmo_set_error("moulin source on an AMR patch is not built yet (the integral spans all levels)"); return -5; }
-    double *out = suhmo_field(L, 0, SUHMO_F_MSRC);
-    if (!out) { suhmo_set_error("field allocation failed"); return -2; }
-    std::vector<double> h(4 * (size_t)n);
-    for (int m = 0; m < n; m++) {
-        ARG(sigma[m] > 0.0);
-        h[3 * m] = positions[2 * m]; h[3 * m + 1] = positions[2 * m + 1]; h[3 * m + 2] = sigma[m]; h[3 * (size_t)n + m] = flux[m];
-    }
-    // rank strip: the integrals run over the whole level on every rank (geometry only), in the single-level order
-    DV vg = D.v;
-    vg.ny = D.v.nyg; vg.j0 = 0;
-    dim3 grd((D.v.nx + 15) / 16, (D.v.ny + 15) / 16), grdg((vg.nx + 15) / 16, (vg.ny + 15) / 16);
-    const size_t nblk = (size_t)grdg.x * grdg.y;
-    double *dev = nullptr;
-    HIPCHK(hipMalloc(&dev, (5 * (size_t)n + nblk * n) * sizeof(double)));
-    double *mo = dev, *fl = dev + 3 * (size_t)n, *integ = dev + 4 * (size_t)n, *partial = dev + 5 * (size_t)n;
-    hipError_t e = hipMemcpyAsync(dev, h.data(), 4 * (size_t)n * sizeof(double), hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) {
-        const OneMoulinList whole = moulin_integrals_on(vg, n, mo, partial, nblk, integ);
-        launch_moulin_partial(whole, grdg, st, Excl{0, 0, 0, 0});
-        launch_moulin_final(whole, n, 1, st);
-        launch_moulin_src(moulin_source_on(D.v, n, mo, fl, integ, time_factor, out), grd, st, Excl{0, 0, 0, 0});
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess && integrals) e = hipMemcpyAsync(integrals, integ, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    (void)hipFree(dev);
-    if (e != hipSuccess) { suhmo_set_error("moulin source: %s", hipGetErrorString(e)); return -2; }
-    return 0;
-}
-
-// Calc_moulin_integral + Calc_moulin_source_term_distributed on the hierarchy (:1866-2066, :2797-2837): every level samples
-// the Gaussians at its own resolution, cells under a finer level do not count in the integrals (finest level first, :1891)
-// and receive the average of the finer level's source term afterwards (CoarseAverage :2819-2826).
-extern "C" int suhmo_amr_moulin_source(suhmo_level_t **lv, int nlev, const int *patch_boxes, int n, const double *positions,
-                                       const double *sigma, const double *flux, double time_factor, double *integrals, suhmo_stream_t s)
-{
-    ARG(lv && nlev >= 1 && nlev <= 8 && lv[0] && n >= 1 && positions && sigma && flux);
-    int rc = suhmo_amr_check_hierarchy(lv, nlev); if (rc) return rc;
-    // geometry of every level's WHOLE rectangle: from the boxes (rank strips: a rank may hold a part of a level or none of
-    // it, and integrates all of them itself -- analytic integrand, single-process order, no communication) or the handles
-    struct Geo { int nx, ny, i0, j0; double dx, dy; } geo[8];
-    const DV &b = lv[0]->d[0].v;
-    geo[0] = Geo{b.nx, b.nyg, 0, 0, b.dx, b.dy};
-    for (int l = 1; l < nlev; l++) {
-        if (patch_boxes) {
-            const int *q = patch_boxes + 4 * (l - 1);
-            ARG(q[2] >= q[0] && q[3] >= q[1]);
-            geo[l] = Geo{2 * (q[2] - q[0] + 1), 2 * (q[3] - q[1] + 1), 2 * q[0], 2 * q[1], geo[l - 1].dx / 2.0, geo[l - 1].dy / 2.0};
-            if (lv[l]) { const DV &v = lv[l]->d[0].v; const bool part = v.rk[0] || v.rk[1];            // a rank strip holds some of the rows, a whole patch all of them
-                if (v.nx != geo[l].nx || v.i0 != geo[l].i0 || v.j0 < geo[l].j0 || v.j0 + v.ny > geo[l].j0 + geo[l].ny
-                    || (!part && (v.j0 != geo[l].j0 || v.ny != geo[l].ny))) { suhmo_set_error("moulin source: level %d does not match patch_boxes", l); return -1; } }
-        } else {
-            if (!lv[l] || lv[l]->d[0].v.rk[0] || lv[l]->d[0].v.rk[1]) { suhmo_set_error("moulin source on rank strips needs patch_boxes"); return -1; }
-            const DV &v = lv[l]->d[0].v;
-            geo[l] = Geo{v.nx, v.ny, v.i0, v.j0, v.dx, v.dy};
-        }
-    }
-    auto excl_of = [&](int l, int i0, int j0) {                       // the box of level l+1 in cells of level l, relative to (i0, j0)
-        if (l >= nlev - 1) return Excl{0, 0, 0, 0};
-        return Excl{geo[l + 1].i0 / 2 - i0, geo[l + 1].j0 / 2 - j0, (geo[l + 1].i0 + geo[l + 1].nx) / 2 - i0, (geo[l + 1].j0 + geo[l + 1].ny) / 2 - j0};
-    };
-    for (int l = 0; l < nlev; l++) if (lv[l] && !suhmo_field(lv[l], 0, SUHMO_F_MSRC)) { suhmo_set_error("field allocation failed"); return -2; }
-    HIPCHK(hipSetDevice(lv[0]->device));
-    hipStream_t st = (hipStream_t)s;
-    std::vector<double> h(4 * (size_t)n), total((size_t)n, 0.0), part((size_t)n);
-    for (int m = 0; m < n; m++) {
-        ARG(sigma[m] > 0.0);
-        h[3 * m] = positions[2 * m]; h[3 * m + 1] = positions[2 * m + 1]; h[3 * m + 2] = sigma[m]; h[3 * (size_t)n + m] = flux[m];
-    }
-    size_t maxblk = 0;
-    for (int l = 0; l < nlev; l++) maxblk = std::max(maxblk, (size_t)((geo[l].nx + 15) / 16) * ((geo[l].ny + 15) / 16));
-    double *dev = nullptr;
-    HIPCHK(hipMalloc(&dev, (5 * (size_t)n + maxblk * n) * sizeof(double)));
-    double *mo = dev, *fl = dev + 3 * (size_t)n, *integ = dev + 4 * (size_t)n, *partial = dev + 5 * (size_t)n;
-    hipError_t e = hipMemcpyAsync(dev, h.data(), 4 * (size_t)n * sizeof(double), hipMemcpyHostToDevice, st);
-    for (int l = nlev - 1; l >= 0 && e == hipSuccess; l--) {          // finest first (:1891)
-        DV vg = b;                                                     // only the geometry below is read by the kernel
-        vg.nx = geo[l].nx; vg.ny = geo[l].ny; vg.i0 = geo[l].i0; vg.j0 = geo[l].j0; vg.dx = geo[l].dx; vg.dy = geo[l].dy;
-        dim3 grd((vg.nx + 15) / 16, (vg.ny + 15) / 16);
-        const OneMoulinList lev = moulin_integrals_on(vg, n, mo, partial, (size_t)grd.x * grd.y, integ);
-        launch_moulin_partial(lev, grd, st, excl_of(l, vg.i0, vg.j0));
-        launch_moulin_final(lev, n, 1, st);
-        e = hipGetLastError();
-        if (e == hipSuccess) e = hipMemcpyAsync(part.data(), integ, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, st);
-        if (e == hipSuccess) e = hipStreamSynchronize(st);
-        for (int m = 0; m < n; m++) total[m] += part[m];
-    }
-    if (e == hipSuccess) e = hipMemcpyAsync(integ, total.data(), (size_t)n * sizeof(double), hipMemcpyHostToDevice, st);
-    for (int l = 0; l < nlev && e == hipSuccess; l++) {
-        if (!lv[l]) continue;
-        const DV &v = lv[l]->d[0].v;
-        dim3 grd((v.nx + 15) / 16, (v.ny + 15) / 16);
-        launch_moulin_src(moulin_source_on(v, n, mo, fl, integ, time_factor, lv[l]->d[0].fp.f[SUHMO_F_MSRC]), grd, st, excl_of(l, v.i0, v.j0));
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    (void)hipFree(dev);
-    if (e != hipSuccess) { suhmo_set_error("moulin source: %s", hipGetErrorString(e)); return -2; }
-    for (int l = nlev - 1; l > 0; l--) if (lv[l] && (rc = suhmo_amr2_average(lv[l - 1], lv[l], SUHMO_F_MSRC, SUHMO_F_MSRC, s))) return rc;
-    if (integrals) for (int m = 0; m < n; m++) integrals[m] = total[m];
-    return 0;
-}
-
-
-// suhmo_amr_moulin_source on a hierarchy of box unions (oracle/amr_step_m.c:or_amrm_model_moulin_source): finest level first,
-// box after box; cells under a finer level (SUHMO_F_COVER) do not count and get the finer level's average afterwards
-extern "C" int suhmo_hier_moulin_source(suhmo_hier_t *H, int n, const double *positions, const double *sigma, const double *flux,
-                                        double time_factor, double *integrals, suhmo_stream_t s)
-{
-    ARG(H && n >= 1 && positions && sigma && flux);
-    const int nlev = H->nlev;
-    HIPCHK(hipSetDevice(H->device));
-    hipStream_t st = (hipStream_t)s;
-    int rc;
-    std::vector<double> h(4 * (size_t)n), total((size_t)n, 0.0), part((size_t)n);
-    for (int m = 0; m < n; m++) {
-        ARG(sigma[m] > 0.0);
-        h[3 * m] = positions[2 * m]; h[3 * m + 1] = positions[2 * m + 1]; h[3 * m + 2] = sigma[m]; h[3 * (size_t)n + m] = flux[m];
-    }
-    H->n_moulin_calls++;
-    // owner computes (levels >= 1 dealt to the ranks): a rank integrates and fills the boxes it owns; the per-box integrals of all ranks are
-    // gathered and added up in the single-process order (finest level first, box after box), so every rank gets the same bits
-    const bool parted = H->part;
-    size_t maxblk = 0, nbt = 0;
-    std::vector<size_t> first(nlev + 1, 0);
-    for (int l = 0; l < nlev; l++) {
-        const auto &bx = H->lev[l].box;
-        first[l] = nbt; nbt += bx.size();
-        const int k0 = H->lev[l].first_owned(), nk = H->lev[l].n_owned();
-        for (int k = 0; k < (int)bx.size(); k++) {
-            suhmo_level *L = bx[k];
-            if (k >= k0 && k < k0 + nk && !suhmo_field(L, 0, SUHMO_F_MSRC)) { suhmo_set_error("field allocation failed"); return -2; }
-            maxblk = std::max(maxblk, (size_t)((L->d[0].v.nx + 15) / 16) * (((l == 0 ? L->d[0].v.nyg : L->d[0].v.ny) + 15) / 16));
-        }
-    }
-    first[nlev] = nbt;
-    double *dev = nullptr;
-    HIPCHK(hipMalloc(&dev, (5 * (size_t)n + maxblk * n) * sizeof(double)));
-    double *mo = dev, *fl = dev + 3 * (size_t)n, *integ = dev + 4 * (size_t)n, *partial = dev + 5 * (size_t)n;
-    hipError_t e = hipMemcpyAsync(dev, h.data(), 4 * (size_t)n * sizeof(double), hipMemcpyHostToDevice, st);
-    const double *whole_cover = dist_base(H) ? H->cover_whole : nullptr;   // level 0 cut into rank strips: every rank integrates all of it (geometry only)
-    std::vector<double> perbox(nbt * (size_t)n, 0.0);                  // the integrals over every box (this rank's; the others' after the gather)
-    for (int l = nlev - 1; l >= 0 && e == hipSuccess; l--) {
-        const auto &bx = H->lev[l].box;
-        const int k0 = H->lev[l].first_owned(), nk = H->lev[l].n_owned();
-        for (int k = k0; k < k0 + nk; k++) {
-            suhmo_level *L = bx[k];
-            const bool cutbase = l == 0 && (L->d[0].v.rk[0] || L->d[0].v.rk[1]);
-            DV v = L->d[0].v;
-            if (cutbase) { v.ny = v.nyg; v.j0 = 0; }
-            dim3 grd((v.nx + 15) / 16, (v.ny + 15) / 16);
-            const double *cover = l < nlev - 1 ? (cutbase ? whole_cover : L->d[0].fp.f[SUHMO_F_COVER]) : nullptr;
-            const OneMoulinList box = moulin_integrals_on(v, n, mo, partial, (size_t)grd.x * grd.y, integ);
-            launch_moulin_partial(box, grd, st, Excl{0, 0, 0, 0}, cover);
-            launch_moulin_final(box, n, 1, st);
-            e = hipGetLastError();
-            if (e == hipSuccess) e = hipMemcpyAsync(part.data(), integ, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, st);
-            if (e == hipSuccess) e = hipStreamSynchronize(st);
-            if (e != hipSuccess) break;
-            for (int m = 0; m < n; m++) perbox[(first[l] + k) * (size_t)n + m] = part[m];
-        }
-    }
-    if (e == hipSuccess && parted) {                                   // every rank's integrals over its boxes -> every rank
-        const int world = H->world;
-        const size_t cnt = nbt * (size_t)n;
-        double *gs = nullptr, *gr = nullptr;
-        std::vector<double> all(cnt * world);
-        e = hipMalloc(&gs, cnt * sizeof(double));
-        if (e == hipSuccess) e = hipMalloc(&gr, cnt * world * sizeof(double));
-        if (e == hipSuccess) e = hipMemcpyAsync(gs, perbox.data(), cnt * sizeof(double), hipMemcpyHostToDevice, st);
-        if (e == hipSuccess && (rc = suhmo_hier_allgather_(H, gs, (long)cnt, gr, st))) { (void)hipFree(gs); (void)hipFree(gr); (void)hipFree(dev); return rc; }
-        if (e == hipSuccess) e = hipMemcpyAsync(all.data(), gr, cnt * world * sizeof(double), hipMemcpyDeviceToHost, st);
-        if (e == hipSuccess) e = hipStreamSynchronize(st);
-        if (gs) (void)hipFree(gs);
-        if (gr) (void)hipFree(gr);
-        if (e == hipSuccess)
-            for (int l = 1; l < nlev; l++)
-                for (size_t k = 0; k < first[l + 1] - first[l]; k++) {
-                    const int o = suhmo_hier_box_owner(H, l, (int)k, nullptr);
-                    if (o >= 0) for (int m = 0; m < n; m++) perbox[(first[l] + k) * (size_t)n + m] = all[(size_t)o * cnt + (first[l] + k) * (size_t)n + m];
-                }
-    }
-    for (int l = nlev - 1; l >= 0; l--)                                // finest first (:1891), box after box
-        for (size_t k = first[l]; k < first[l + 1]; k++)
-            for (int m = 0; m < n; m++) total[m] += perbox[k * (size_t)n + m];
-    if (e == hipSuccess) e = hipMemcpyAsync(integ, total.data(), (size_t)n * sizeof(double), hipMemcpyHostToDevice, st);
-    for (int l = 0; l < nlev && e == hipSuccess; l++) {
-        const auto &bx = H->lev[l].box;
-        const int k0 = H->lev[l].first_owned(), nk = H->lev[l].n_owned();
-        for (int k = k0; k < k0 + nk; k++) {
-            suhmo_level *L = bx[k];
-            const DV &v = L->d[0].v;
-            dim3 grd((v.nx + 15) / 16, (v.ny + 15) / 16);
-            const double *cover = l < nlev - 1 ? L->d[0].fp.f[SUHMO_F_COVER] : nullptr;
-            launch_moulin_src(moulin_source_on(v, n, mo, fl, integ, time_factor, L->d[0].fp.f[SUHMO_F_MSRC]), grd, st, Excl{0, 0, 0, 0}, cover);
-            e = hipGetLastError();
-            if (e != hipSuccess) break;
-        }
-    }
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    (void)hipFree(dev);
-    if (e != hipSuccess) { suhmo_set_error("moulin source: %s", hipGetErrorString(e)); return -2; }
-    for (int l = nlev - 1; l > 0; l--) if ((rc = hier_avg(H, l, SUHMO_F_MSRC, SUHMO_F_MSRC, 0, 0.0, st))) return rc;
-    if (integrals) for (int m = 0; m < n; m++) integrals[m] = total[m];
-    return 0;
-}
-
-// COMPUTE_TIMEVARYINGRECHARGE (src/AmrHydroF.ChF:346-373) on the ghosted box of the source term
-__device__ __forceinline__ void d_time_varying_recharge(const DV &v, const double *__restrict__ zs, double *__restrict__ out, double TK, double background)
-{
-    int i = blockIdx.x * blockDim.x + threadIdx.x - 1, j = blockIdx.y * blockDim.y + threadIdx.y - 1;
-    if (i > v.nx || j > v.ny) return;
-    const double ddf = 0.01 / 86400., dT_dZ = -0.0075;
-    int idx = cidx(v, i, j);
-    out[idx] = fmax(ddf * (TK + zs[idx] * dT_dZ), 0.0) + background;
-}
-// V: the temperature and the background input -- a double each for a level, PerMember for an ensemble
-template <class T, class V> __global__ void k_time_varying_recharge(T t, V TK, V background)
-{
-    d_time_varying_recharge(t.view(), t.field(SUHMO_F_ZS), t.field(SUHMO_F_MSRC), value_of(t, TK), value_of(t, background));
-}
-template <class T, class V> static int launch_time_varying_recharge_(const T &t, const V &TK, const V &background, hipStream_t st)
-{
-    return launch_over(k_time_varying_recharge<T, V>, t, GHOSTED, st, TK, background);
-}
-int launch_time_varying_recharge(const OnMembers &t, const PerMember &TK, const PerMember &background, hipStream_t st)
-{
-    return launch_time_varying_recharge_(t, TK, background, st);
-}
-extern "C" int suhmo_level_time_varying_recharge(suhmo_level_t *L, double T_K, double background_input, suhmo_stream_t s)
-{
-    ARG(L);
-    HIPCHK(hipSetDevice(L->device));
-    Depth &D = L->d[0];
-    if (!D.fp.f[SUHMO_F_ZS]) { suhmo_set_error("time-varying recharge: load the ice surface height (SUHMO_F_ZS) first"); return -1; }
-    double *out = suhmo_field(L, 0, SUHMO_F_MSRC);
-    if (!out) { suhmo_set_error("field allocation failed"); return -2; }
-    return launch_time_varying_recharge_(on_level(L, 0), T_K, background_input, (hipStream_t)s);
-}
-// the same on every box of a hierarchy of box unions (timeStepFAS evaluates it level by level, :2846-2863, with no averaging down and no
-// coarse-fine fill): level 0 as a level, every refined level as ONE launch over its boxes.  Everything is checked before the first launch
-int suhmo_hier_recharge_check_(suhmo_hier *H, const char *who)
-{
-    if (H->world > 1 || H->part) { suhmo_set_error("%s: a hierarchy on rank strips (or with levels dealt to the ranks) is not built", who); return -5; }
-    for (int l = 0; l < H->nlev; l++)
-        for (size_t k = 0; k < H->lev[l].box.size(); k++)
-            if (!H->lev[l].box[k]->d[0].fp.f[SUHMO_F_ZS]) {
-                suhmo_set_error("%s: time-varying recharge: load the ice surface height (SUHMO_F_ZS) of level %d, box %d first", who, l, (int)k);
-                return -1;
-            }
-    return 0;
-}
-int suhmo_hier_recharge_launch_(suhmo_hier *H, double T_K, double background_input, hipStream_t st)
-{
-    int rc;
-    for (int l = 0; l < H->nlev; l++) if ((rc = ensure_field(H, l, SUHMO_F_MSRC))) return rc;
-    if ((rc = launch_time_varying_recharge_(on_level(base_of(H), 0), T_K, background_input, st))) return rc;
-    H->n_recharge_launches++;
-    for (int l = 1; l < H->nlev; l++) {
-        suhmo_multi m;
-        if ((rc = multi_of(H, l, st, m)) || (rc = launch_time_varying_recharge_(m.on(), T_K, background_input, st))) return rc;
-        H->n_recharge_launches++;
-    }
-    return 0;
-}
-extern "C" int suhmo_hier_time_varying_recharge(suhmo_hier_t *H, double T_K, double background_input, suhmo_stream_t s)
-{
-    ARG(H);
-    int rc = suhmo_hier_recharge_check_(H, "suhmo_hier_time_varying_recharge"); if (rc) return rc;
-    if ((rc = suhmo_hier_check_(H))) return rc;
-    HIPCHK(hipSetDevice(H->device));
-    return suhmo_hier_recharge_launch_(H, T_K, background_input, (hipStream_t)s);
-}
-
-// ------------------------------------------------------------------ SHMIP cross-section table
-// one thread per cell column, rows summed in ascending j (the order of the reference's BoxIterator per column)
-__device__ __forceinline__ void d_postproc_columns(const DV &v, const FP &fp, const suhmo_model_params_t &mp, double *__restrict__ out /* 8 x nx */)
-{
-    int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= v.nx) return;
-    const double *__restrict__ qx = fp.f[SUHMO_F_QWX], *__restrict__ cd = fp.f[SUHMO_F_CD], *__restrict__ mR = fp.f[SUHMO_F_MR];
-    const double *__restrict__ Pw = fp.f[SUHMO_F_PW], *__restrict__ Pi = fp.f[SUHMO_F_PI], *__restrict__ mk = fp.f[SUHMO_F_MASK];
-    const double *__restrict__ ms = mp.use_moulin_source ? fp.f[SUHMO_F_MSRC] : nullptr;
-    double qt = 0.0, qc = 0.0, qd = 0.0, ext = 0.0, mr = 0.0, yl = 0.0, avp = 0.0, cnt = 0.0;
-    for (int j = 0; j < v.ny; j++) {
-        int idx = cidx(v, i, j);
-        double cdec = 0.5 * (cd[idx] + cd[idx - 1]);                     // CellToEdge(chanDegree), :3696-3697
-        double q = qx[idx] * v.dy;
-        qt += q; qc += q * cdec; qd += q * (1.0 - cdec);                 // :3734-3738
-        bool ice = mk[idx] > 0.0;
-        double src = ms ? ms[idx] * mp.ramp + mp.distributed_input : (ice ? mp.distributed_input : 0.0);
-        if (ice) { ext += src * v.dy * v.dx; mr += (mR[idx] / mp.rho_w) * v.dy * v.dx; yl += v.dy; }    // :3766-3775
-        if (ice && Pi[idx] > 0.0) { avp += Pi[idx] - Pw[idx]; cnt += 1.0; }                             // :3778-3783
-    }
-    out[0 * v.nx + i] = yl; out[1 * v.nx + i] = qt; out[2 * v.nx + i] = qc; out[3 * v.nx + i] = qd;
-    out[4 * v.nx + i] = ext; out[5 * v.nx + i] = mr; out[6 * v.nx + i] = avp; out[7 * v.nx + i] = cnt;
-}
-// out: 8 x nx of a level; of an ensemble [n][8][nx], the rows of the members the launch serves
-template <class T> __global__ void k_postproc_columns(T t, double *__restrict__ out)
-{
-    d_postproc_columns(t.view(), t.fields(), t.model(), out + t.slot(8 * (size_t)t.view().nx));
-}
-template <class T> static int launch_postproc_columns_(const T &t, double *out, hipStream_t st)
-{
-    return launch_grid(k_postproc_columns<T>, t, dim3((t.nx() + 63) / 64), dim3(64), st, out);
-}
-int launch_postproc_columns(const OnMembers &t, double *out, hipStream_t st) { return launch_postproc_columns_(t, out, st); }
-// column sums over the rows of this level / strip: 8 x nx = width, Q, Q channelised, Q distributed, external recharge,
-// melt recharge, sum of (Pi - Pw), count of its terms
-extern "C" int suhmo_level_postproc_partial(suhmo_level_t *L, const suhmo_model_params_t *mp, double *sums, suhmo_stream_t s)
-{
-    ARG(L && mp && sums);
-    HIPCHK(hipSetDevice(L->device));
-    hipStream_t st = (hipStream_t)s;
-    Depth &D = L->d[0];
-    if (L->desc.nx_global > 0) { suhmo_set_error("post-processing table on an AMR patch is not built"); return -5; }
-    for (int f : {SUHMO_F_QWX, SUHMO_F_CD, SUHMO_F_MR, SUHMO_F_PW}) if (!D.fp.f[f]) { suhmo_set_error("no time step has run on this level"); return -1; }
-    if (mp->use_moulin_source && !D.fp.f[SUHMO_F_MSRC]) { suhmo_set_error("use_moulin_source without suhmo_level_moulin_source"); return -1; }
-    const int nx = D.v.nx;
-    double *dev = nullptr;
-    HIPCHK(hipMalloc(&dev, 8 * (size_t)nx * sizeof(double)));
-    const int rc = launch_postproc_columns_(stepping(on_level(L, 0), *mp), dev, st);
-    hipError_t e = rc ? hipSuccess : hipMemcpyAsync(sums, dev, 8 * (size_t)nx * sizeof(double), hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    (void)hipFree(dev);
-    if (rc) return rc;
-    if (e != hipSuccess) { suhmo_set_error("postproc table: %s", hipGetErrorString(e)); return -2; }
-    return 0;
-}
-// the table from column sums (of the whole level: on rank strips the host adds the strips' sums first)
-extern "C" int suhmo_postproc_finish(const double *sums, int nx, double dx, double *table)
-{
-    ARG(sums && table && nx > 0);
-    const double *h = sums;
-    double cext = 0.0, cmr = 0.0;
-    for (int i = nx - 1; i >= 0; i--) {                    // recharge upstream of the column: cumulative from the upper end
-        cext += h[4 * (size_t)nx + i]; cmr += h[5 * (size_t)nx + i];
-        double *row = table + 8 * (size_t)i;
-        row[0] = (i + 0.5) * dx / 1.0e3; row[1] = h[0 * (size_t)nx + i];
-        row[2] = -h[1 * (size_t)nx + i]; row[3] = -h[2 * (size_t)nx + i]; row[4] = -h[3 * (size_t)nx + i];
-        row[5] = cext; row[6] = cmr; row[7] = h[6 * (size_t)nx + i] / fmax(h[7 * (size_t)nx + i], 1.0) / 1.0e6;
-    }
-    return 0;
-}
-// the "Time(h - d)" lines of the temporal post-processing (src/AmrHydro.cpp:3778-3810, 4040-4053) from the column sums
-extern "C" int suhmo_postproc_temporal(const double *sums, int nx, double dx, double *out)
-{
-    ARG(sums && out && nx > 1);
-    const double *h = sums;
-    const double lo[3] = {600.0, 3000.0, 5100.0}, hi[3] = {900.0, 3300.0, 5400.0};
-    double tot = 0.0, cnt = 0.0, bs[3] = {0.0, 0.0, 0.0}, bc[3] = {0.0, 0.0, 0.0}, rech = 0.0;
-    for (int i = 0; i < nx; i++) {
-        const double x = (i + 0.5) * dx;
-        tot += h[6 * (size_t)nx + i]; cnt += h[7 * (size_t)nx + i];
-        for (int b = 0; b < 3; b++) if (x > lo[b] && x < hi[b]) { bs[b] += h[6 * (size_t)nx + i]; bc[b] += h[7 * (size_t)nx + i]; }
-        if (i >= 1) rech += h[4 * (size_t)nx + i] + h[5 * (size_t)nx + i];
-    }
-    out[0] = tot / cnt;
-    for (int b = 0; b < 3; b++) out[1 + b] = bs[b] / bc[b];
-    out[4] = rech;
-    out[5] = -h[1 * (size_t)nx + 1];
-    return 0;
-}
-extern "C" int suhmo_level_postproc_temporal(suhmo_level_t *L, const suhmo_model_params_t *mp, double *out, suhmo_stream_t s)
-{
-    ARG(L && mp && out);
-    Depth &D = L->d[0];
-    if (D.v.ext[0] || D.v.ext[1]) { suhmo_set_error("rank strip: add the strips' suhmo_level_postproc_partial sums, then suhmo_postproc_temporal"); return -5; }
-    std::vector<double> h(8 * (size_t)D.v.nx);
-    int rc = suhmo_level_postproc_partial(L, mp, h.data(), s); if (rc) return rc;
-    return suhmo_postproc_temporal(h.data(), D.v.nx, D.v.dx, out);
-}
-// suhmo_postproc_temporal on the device: the six values from column sums that never leave it (a run keeps finished rows, 6 doubles per member,
-// instead of 8 nx).  One thread per value, each the host function's loop over the columns in ascending order with its operations -- no tree, so
-// the bits are the host's (0 / 0 of an empty band: NaN on both sides)
-__device__ __forceinline__ void d_postproc_temporal_row(const DV &v, const double *__restrict__ h /* 8 x nx */, double *__restrict__ out /* 6 */)
-{
-    const int q = threadIdx.x;
-    if (q >= 6) return;
-    const size_t nx = v.nx;
-    if (q == 0) {
-        double tot = 0.0, cnt = 0.0;
-        for (size_t i = 0; i < nx; i++) { tot += h[6 * nx + i]; cnt += h[7 * nx + i]; }
-        out[0] = tot / cnt;
-    } else if (q <= 3) {
-        const double lo = q == 1 ? 600.0 : q == 2 ? 3000.0 : 5100.0, hi = q == 1 ? 900.0 : q == 2 ? 3300.0 : 5400.0;
-        double bs = 0.0, bc = 0.0;
-        for (size_t i = 0; i < nx; i++) {
-            const double x = ((int)i + 0.5) * v.dx;
-            if (x > lo && x < hi) { bs += h[6 * nx + i]; bc += h[7 * nx + i]; }
-        }
-        out[q] = bs / bc;
-    } else if (q == 4) {
-        double rech = 0.0;
-        for (size_t i = 1; i < nx; i++) rech += h[4 * nx + i] + h[5 * nx + i];
-        out[4] = rech;
-    } else out[5] = -h[1 * nx + 1];
-}
-// cols: 8 x nx of a level, [n][8][nx] of an ensemble; out: 6 values, of an ensemble [n][6] (one row of a series): the entries of the members served
-template <class T> __global__ void k_postproc_temporal_row(T t, const double *__restrict__ cols, double *__restrict__ out)
-{
-    d_postproc_temporal_row(t.view(), cols + t.slot(8 * (size_t)t.view().nx), out + t.slot(6));
-}
-template <class T> static int launch_postproc_temporal_row_(const T &t, const double *cols, double *out, hipStream_t st)
-{
-    return launch_grid(k_postproc_temporal_row<T>, t, dim3(1), dim3(64), st, cols, out);
-}
-int launch_postproc_temporal_row(const OnMembers &t, const double *cols, double *out, hipStream_t st) { return launch_postproc_temporal_row_(t, cols, out, st); }
-extern "C" int suhmo_level_postproc_temporal_device(suhmo_level_t *L, const suhmo_model_params_t *mp, double *out, suhmo_stream_t s)
-{
-    ARG(L && mp && out);
-    HIPCHK(hipSetDevice(L->device));
-    hipStream_t st = (hipStream_t)s;
-    Depth &D = L->d[0];
-    if (L->desc.nx_global > 0) { suhmo_set_error("post-processing table on an AMR patch is not built"); return -5; }
-    if (D.v.ext[0] || D.v.ext[1]) { suhmo_set_error("rank strip: add the strips' suhmo_level_postproc_partial sums, then suhmo_postproc_temporal"); return -5; }
-    if (D.v.nx < 2) { suhmo_set_error("temporal post-processing needs at least two columns"); return -1; }
-    for (int f : {SUHMO_F_QWX, SUHMO_F_CD, SUHMO_F_MR, SUHMO_F_PW}) if (!D.fp.f[f]) { suhmo_set_error("no time step has run on this level"); return -1; }
-    if (mp->use_moulin_source && !D.fp.f[SUHMO_F_MSRC]) { suhmo_set_error("use_moulin_source without suhmo_level_moulin_source"); return -1; }
-    const size_t ncol = 8 * (size_t)D.v.nx;
-    double *dev = nullptr;
-    HIPCHK(hipMalloc(&dev, (ncol + 6) * sizeof(double)));
-    int rc = launch_postproc_columns_(stepping(on_level(L, 0), *mp), dev, st);
-    if (!rc) rc = launch_postproc_temporal_row_(on_level(L, 0), dev, dev + ncol, st);
-    hipError_t e = rc ? hipSuccess : hipMemcpyAsync(out, dev + ncol, 6 * sizeof(double), hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    (void)hipFree(dev);
-    if (rc) return rc;
-    if (e != hipSuccess) { suhmo_set_error("postproc temporal: %s", hipGetErrorString(e)); return -2; }
-    return 0;
-}
-// what the two calls above check, and their two launches into device memory the caller owns (cols: 8 nx doubles, out6: 6): a run of a
-// hierarchy (suhmo_run.hip) writes the rows of its series with them, no copy and no synchronisation per row
-int suhmo_level_postproc_row_check_(suhmo_level *L, const suhmo_model_params_t *mp, bool forcing_writes_source)
-{
-    Depth &D = L->d[0];
-    if (L->desc.nx_global > 0) { suhmo_set_error("post-processing table on an AMR patch is not built"); return -5; }
-    if (D.v.ext[0] || D.v.ext[1]) { suhmo_set_error("rank strip: add the strips' suhmo_level_postproc_partial sums, then suhmo_postproc_temporal"); return -5; }
-    if (D.v.nx < 2) { suhmo_set_error("temporal post-processing needs at least two columns"); return -1; }
-    if (mp->use_moulin_source && !forcing_writes_source && !D.fp.f[SUHMO_F_MSRC]) { suhmo_set_error("use_moulin_source without suhmo_level_moulin_source"); return -1; }
-    return 0;
-}
-int suhmo_level_postproc_row_launch_(suhmo_level *L, const suhmo_model_params_t *mp, double *cols, double *out6, hipStream_t st)
-{
-    Depth &D = L->d[0];
-    for (int f : {SUHMO_F_QWX, SUHMO_F_CD, SUHMO_F_MR, SUHMO_F_PW}) if (!D.fp.f[f]) { suhmo_set_error("no time step has run on this level"); return -1; }
-    if (mp->use_moulin_source && !D.fp.f[SUHMO_F_MSRC]) { suhmo_set_error("use_moulin_source without suhmo_level_moulin_source"); return -1; }
-    int rc = launch_postproc_columns_(stepping(on_level(L, 0), *mp), cols, st);
-    if (!rc) rc = launch_postproc_temporal_row_(on_level(L, 0), cols, out6, st);
-    return rc;
-}
-// the daily row of a hierarchy: the reference evaluates it on level 0 ("POST PROC -- 1 LEVEL", src/AmrHydro.cpp:3643-3700); the finer
-// levels enter through what the time step averaged down
-extern "C" int suhmo_hier_postproc_temporal(suhmo_hier_t *H, const suhmo_model_params_t *mp, double *out, suhmo_stream_t s)
-{
-    ARG(H && mp && out);
-    if (H->world > 1) { suhmo_set_error("suhmo_hier_postproc_temporal: a hierarchy on rank strips: add the strips' suhmo_level_postproc_partial sums"); return -5; }
-    return suhmo_level_postproc_temporal_device(base_of(H), mp, out, s);
-}
-extern "C" int suhmo_level_postproc_table(suhmo_level_t *L, const suhmo_model_params_t *mp, double *table, suhmo_stream_t s)
-{
-    ARG(L && mp && table);
-    Depth &D = L->d[0];
-    if (D.v.ext[0] || D.v.ext[1]) { suhmo_set_error("rank strip: add the strips' suhmo_level_postproc_partial sums, then suhmo_postproc_finish"); return -5; }
-    std::vector<double> h(8 * (size_t)D.v.nx);
-    int rc = suhmo_level_postproc_partial(L, mp, h.data(), s); if (rc) return rc;
-    return suhmo_postproc_finish(h.data(), D.v.nx, D.v.dx, table);
 }

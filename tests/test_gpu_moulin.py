@@ -146,3 +146,34 @@ def test_amr_moulin_source_against_the_2_and_3_level_convergence_tables():
             assert abs(e - ref[nx0]) <= 6e-5 * ref[nx0], (name, nx0, e, ref[nx0])
             checked += 1
     assert checked == 5
+
+
+def test_moulin_entry_points_are_one_computation():
+    """suhmo_level_moulin_source, suhmo_amr_moulin_source and suhmo_hier_moulin_source are one pass over their regions
+    (suhmo_forcing.hip): the same nested hierarchy given as patches and as one box per level gets the same integrals and the same
+    source term on every level, bit for bit; with no patch at all the single level agrees with both.  One moulin lies inside the
+    finest patch, one on a coarse-fine boundary (x = 40), one at x = 10, so that the tiles of the base level beyond x = 50 take the
+    underflow skip for it"""
+    from suhmo_amd import model
+    nx0, ny0 = 128, 16
+    nested = ((8, 2, 39, 13), (24, 8, 55, 19))                   # in the coarser level's cells: x 8..40, y 2..14 and x 12..28, y 4..10
+    pos, sg, fl = np.array([[20.3, 7.1], [40.0, 8.0], [10.2, 5.5]]), np.ones(3), np.array([30.0, 40.0, 20.0])
+    for patches in (nested, ()):
+        boxes = [[[2 * p[0], 2 * p[1], 2 * p[2] + 1, 2 * p[3] + 1]] for p in patches]
+        A = model.HipAmrModel(nx0, ny0, 1.0, 1.0, sy.A3_BC, sy.A3_PHYS, sy.A3_MODEL, patches, max_box=16)
+        H = model.HipHierModel(nx0, ny0, 1.0, 1.0, sy.A3_BC, sy.A3_PHYS, sy.A3_MODEL, boxes, max_box=16)
+        ia, ih = A.moulin_source(pos, sg, fl, 0.75), H.moulin_source(pos, sg, fl, 0.75)
+        assert np.all(np.isfinite(ia)) and np.all(ia > 0.0)
+        assert np.array_equal(ia, ih), (ia, ih)
+        for l in range(len(patches) + 1):
+            a, h = A.get(l, "msrc"), H.get(l, 0, "msrc")
+            assert a.max() > 0.0 and np.array_equal(a, h), (l, float(np.max(np.abs(a - h))))
+        base = A.get(0, "msrc")
+        assert np.all(base[:, 96:] == 0.0)                       # beyond the reach of every Gaussian: exactly zero
+        if not patches:
+            G = model.HipModel(nx0, ny0, 1.0, 1.0, sy.A3_BC, sy.A3_PHYS, sy.A3_MODEL, max_box=16)
+            ig = G.moulin_source(pos, sg, fl, 0.75)
+            assert np.array_equal(ig, ia), (ig, ia)
+            assert np.array_equal(G.get("msrc"), base)
+            G.close()
+        A.close(); H.close()
