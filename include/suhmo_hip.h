@@ -759,6 +759,51 @@ int suhmo_hier_snapshot(suhmo_hier_t *H, int ncomp, const suhmo_snap_comp_t *com
                         long *box_offset /* [total boxes + nlev] */, double *host_dst, suhmo_stream_t s);
 int suhmo_level_snapshot(suhmo_level_t *L, int ncomp, const suhmo_snap_comp_t *comps, int ghost, long *ndoubles, double *host_dst, suhmo_stream_t s);
 
+/* ---- FLATTEN (suhmo_amd/csrc/suhmo_flatten.hip; DESIGN.md section 5, "Comparison of runs"; tests/flatten_ref.py is the numpy twin of this text): a
+ * hierarchy interpolated onto ONE uniform grid at the resolution of level max_level -- AmrHydro::interpFinest (src/AmrHydro.cpp:4623-4829, called
+ * at :3648-3650 with post_proc_comparisons), the composite writePltPP (:5298-5389) writes so that an AMR run is compared cell by cell with the
+ * uniform run and with other AMR depths.
+ * COMPONENTS (at most SUHMO_FLAT_MAX_COMPS), each {kind, field, field2}:
+ *   SUHMO_FLAT_FIELD   a cell-centred SUHMO_F_* (the head wherever the relaxation left it, on either of its two canvases).
+ *   SUHMO_FLAT_DIFF    field - field2, formed in the cells of each level BEFORE the interpolation: the reference interpolates N = Pi - Pw, not Pi
+ *                      and Pw, and the limiter is not linear.  The reference's two plotted components are {FIELD, B} and {DIFF, PI, PW}.
+ *   A field a box does not hold counts as 0.0 there; nothing is allocated for it (the snapshot's rule).
+ * OUTPUT.  ncomp x nyF x nxF doubles ordered [comp][j][i], nxF = nx0 << max_level, nyF = ny0 << max_level: exactly one box with ghost 0 in the
+ * layout suhmo_plt_write_level takes for a level.  dims = {nxF, nyF}; host_dst == NULL fills dims only: nothing is launched and the device is not
+ * touched.  All offsets are long (32768 x 32768 cells times 16 components is beyond an int).
+ * ARITHMETIC.  Levels l = 0 .. finest level in ASCENDING order, a finer level overwriting what a coarser one wrote (copyTo, :4769-4771).  With
+ * r = 2^(max_level - l), every valid cell (I, J) of level l with value c0 gives its r x r children (r I + p, r J + q), p, q = 0 .. r - 1:
+ *       v = c0; v = v + s0 * dx_p; v = v + s1 * dy_q        with dx_p = -0.5 + (p + 0.5) / r, dy_q = -0.5 + (q + 0.5) / r
+ * -- this order, separate statements, multiply and add NOT contracted (for r >= 4 the offsets are no longer powers of two).  This is
+ * FineInterp::interpToFine with the whole ratio in ONE shot (:4692-4697, :4761-4765), not an iteration of ratio 2.  s0, s1 and the limiter are
+ * rule (a) of "REGRID: FIELD TRANSFER" above statement by statement: central or one-sided slopes, smax / smin over the existing cells of the
+ * 3 x 3 block, eta, and limitTangentialOnly next to a non-periodic domain side.  r = 1 is a copy.
+ * NEIGHBOURS of a cell of level l: across a non-periodic domain side the neighbour does not exist; in another box of the level, or across a
+ * periodic side, it is that box's VALID value; inside the domain but held by no box of the level (l >= 1: the EDGE CLAUSE) it is the
+ * PiecewiseLinearFillPatch value of the same component from level l - 1 -- rule (b) of the regrid (tests/regrid_ref.py: pwl_cell), computed from
+ * the component as evaluated on level l - 1, not from the flattened array.  DEVIATION, [Chombo], UNPINNED: by our reading of upstream Chombo 3.2
+ * the reference reads there ghost cells of FineInterp's coarsened copy that nothing has set.
+ * READ-ONLY.  The components are evaluated into private scratch canvases (one per component and box, with the box's canvas geometry; allocated on
+ * first use, owned by the hierarchy, freed with it; canvas_bytes_level_<l> counts them); the scratch rings are filled by the plans of the regrid's
+ * steps (b) and (d) over those canvases.  No field and no ghost ring a time step, a snapshot or a checkpoint reads is written, and the fields' own
+ * ghost rings are not inputs.  The finest array lives on the device (ncomp x nyF x nxF doubles, the largest so far, owned by the hierarchy).
+ * MEMORY.  Scratch and finest array stay until the hierarchy is destroyed (a regrid makes a new one) or until suhmo_hier_set_option(H,
+ * "flatten_release", 1) gives both back at once; the next flatten allocates again.  Read-only option flatten_device_bytes: what they hold now, level
+ * 0's scratch included.  A scratch allocation that fails part way gives back what the call took of that level, so that every level's device table
+ * lists exactly the slots that exist; option flatten_fail_slot (tests; -1 = off) makes the allocation of that slot on the finest level fail.
+ * LAUNCHES per call, on one stream, with nlev levels: nlev (evaluation) + per level l >= 1 [ncomp if the level has coarse-fine ghost cells] +
+ * [ceil(ncomp / 2) if it has fine-fine ghost cells, periodic images included] + nlev (interpolation); then ONE hipMemcpyAsync into host_dst and one
+ * synchronisation.  Read-only options flatten_launches and flatten_copies count them (they belong to the handle: a regrid starts them at 0).
+ * REFUSED before anything is launched, host_dst untouched.  rc -1: ncomp outside 1 .. 16, an unknown kind, a field id out of range, a face field,
+ * SUHMO_F_COVER / SUHMO_F_PHI2, max_level below the finest level, max_level so large that nxF or nyF leaves int.  rc -2: the finest array (or the
+ * scratch) cannot be allocated; the hierarchy stays usable.  rc -5: a rank strip, levels dealt to the ranks, a hierarchy created with shadow = 1.
+ * Not built: the reference's third quantity tau (:4678; std::pow, whose bits on the device are not the host's), flattening inside suhmo_hier_run_out. */
+enum { SUHMO_FLAT_FIELD = 0, SUHMO_FLAT_DIFF = 1 };
+#define SUHMO_FLAT_MAX_COMPS 16
+typedef struct suhmo_flat_comp { int kind, field, field2; } suhmo_flat_comp_t;
+int suhmo_hier_flatten(suhmo_hier_t *H, int max_level, int ncomp, const suhmo_flat_comp_t *comps, long dims[2] /* nxF, nyF */, double *host_dst,
+                       suhmo_stream_t s);
+
 /* ---- OUTPUT INSIDE THE RUN (suhmo_amd/csrc/suhmo_run.hip): suhmo_hier_run_out is suhmo_hier_run with the plot files and checkpoints AmrHydro::run
  * writes (src/AmrHydro.cpp:1311-1336, 1343-1358); suhmo_hier_run is the same call with out = NULL.  With b = c - 1, the reference's m_cur_step before
  * step c:

@@ -127,6 +127,23 @@ def snap_comps(comps):
     return arr
 
 
+class FlatComp(C.Structure):
+    """suhmo_flat_comp_t: one component of a flatten (FLAT_FIELD: field; FLAT_DIFF: field - field2, formed before the interpolation)"""
+    _fields_ = [("kind", C.c_int), ("field", C.c_int), ("field2", C.c_int)]
+
+
+FLAT_FIELD, FLAT_DIFF = 0, 1
+FLAT_MAX_COMPS = 16
+
+
+def flat_comps(comps):
+    """[(kind, field) or (kind, field, field2) or FlatComp] -> a C array of suhmo_flat_comp_t"""
+    arr = (FlatComp * max(len(comps), 1))()
+    for q, c in enumerate(comps):
+        arr[q] = c if isinstance(c, FlatComp) else FlatComp(int(c[0]), int(c[1]), int(c[2]) if len(c) > 2 else 0)
+    return arr
+
+
 EXCHANGE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int), C.c_int, C.c_void_p)
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(C.c_double))
 REDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(C.c_double), C.c_int, C.c_int)      # values, n, op (0 MAX, 1 SUM)
@@ -165,7 +182,7 @@ SYMBOLS = [
     "suhmo_grids_generate", "suhmo_hier_generate_grids", "suhmo_hier_regrid",
     "suhmo_hier_restrict_tags", "suhmo_tag_subsets_nest", "suhmo_hier_get_boxes",
     "suhmo_hier_time_varying_recharge", "suhmo_hier_postproc_temporal", "suhmo_hier_run",
-    "suhmo_hier_snapshot", "suhmo_level_snapshot", "suhmo_hier_run_out",
+    "suhmo_hier_snapshot", "suhmo_level_snapshot", "suhmo_hier_run_out", "suhmo_hier_flatten",
 ]
 
 
@@ -336,6 +353,7 @@ def lib():
     L.suhmo_hier_snapshot.argtypes = [vp, ci, C.POINTER(SnapComp), ci, lp, lp, dp, vp]
     L.suhmo_level_snapshot.argtypes = [vp, ci, C.POINTER(SnapComp), ci, lp, dp, vp]
     L.suhmo_hier_run_out.argtypes = [C.POINTER(vp), C.POINTER(ModelParams), C.POINTER(HierSchedule), C.POINTER(HierOutput), C.POINTER(HierRunResult), vp]
+    L.suhmo_hier_flatten.argtypes = [vp, ci, ci, C.POINTER(FlatComp), lp, dp, vp]
     _LIB = L
     return L
 

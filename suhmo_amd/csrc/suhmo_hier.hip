@@ -316,6 +316,7 @@ extern "C" int suhmo_hier_destroy(suhmo_hier_t *H)
     if (H->xs) (void)hipFree(H->xs);
     if (H->xr) (void)hipFree(H->xr);
     if (H->snap_buf) (void)hipFree(H->snap_buf);
+    suhmo_hier_flatten_release_(H);
     for (int l = 0; l < 8; l++) {
         HLev &V = H->lev[l];
         V.snap_cells[0].release(); V.snap_cells[1].release();
@@ -563,6 +564,10 @@ extern "C" int suhmo_hier_set_option(suhmo_hier_t *H, const char *key, long valu
         if (rc == 0 && H->gap) rc = suhmo_hier_set_option(H->gap, key, value);
         return rc;
     }
+    // suhmo_flatten.hip.  flatten_release (any value): the finest array and the scratch of suhmo_hier_flatten go back to the device now instead of
+    // with the hierarchy; the next flatten allocates again.  flatten_fail_slot (tests; -1: off): see scratch() there.  Neither is inherited
+    if (!strcmp(key, "flatten_release")) { HIPCHK(hipSetDevice(H->device)); HIPCHK(hipDeviceSynchronize()); suhmo_hier_flatten_release_(H); return 0; }
+    if (!strcmp(key, "flatten_fail_slot")) { H->flat_fail_slot = value; return 0; }
     const HierOpt *o = find_opt(key, strlen(key));
     if (!o) { suhmo_set_error("unknown hierarchy option '%s'", key); return -1; }
     if (o->creation_only) { suhmo_set_error("hierarchy option '%s' is set when the hierarchy is created (suhmo_hier_create_opts)", key); return -1; }
@@ -592,6 +597,14 @@ extern "C" int suhmo_hier_get_option(const suhmo_hier_t *H, const char *key, lon
     if (!strcmp(key, "run_readbacks")) { *value = H->n_run_readbacks; return 0; }
     if (!strcmp(key, "snapshot_launches")) { *value = H->n_snap_launches; return 0; }
     if (!strcmp(key, "snapshot_copies")) { *value = H->n_snap_copies; return 0; }
+    if (!strcmp(key, "flatten_launches")) { *value = H->n_flat_launches; return 0; }
+    if (!strcmp(key, "flatten_copies")) { *value = H->n_flat_copies; return 0; }
+    if (!strcmp(key, "flatten_fail_slot")) { *value = H->flat_fail_slot; return 0; }
+    if (!strcmp(key, "flatten_device_bytes")) {           // the finest array and the scratch of every level, level 0's included
+        long c = (long)H->flat_cap * 8;
+        for (int l = 0; l < H->nlev; l++) c += (long)H->lev[l].flat_slab.size() * (long)H->lev[l].flat_elems * 8;
+        *value = c; return 0;
+    }
     if (!strcmp(key, "run_plots")) { *value = H->n_run_plots; return 0; }
     if (!strcmp(key, "run_checkpoints")) { *value = H->n_run_checkpoints; return 0; }
     if (!strcmp(key, "incremental_residual_passes")) { *value = H->n_incr_residual; return 0; }
@@ -619,7 +632,8 @@ extern "C" int suhmo_hier_get_option(const suhmo_hier_t *H, const char *key, lon
             else if (q == 1) *value = V.part ? V.held_boxes : (long)V.box.size();
             else if (q == 2) { long c = 0; if (V.part) c = V.owned_cells; else for (size_t k = 0; k < V.box.size(); k++) { const int *b = &V.b4[4 * k];
                 c += (long)(b[2] - b[0] + 1) * (b[3] - b[1] + 1); } *value = c; }
-            else if (q == 3) { long c = 0; for (suhmo_level *L : V.box) for (int f = 0; f < SUHMO_F_COUNT; f++) if (L->d[0].fp.f[f]) c += (long)L->d[0].elems * 8; *value = c; }
+            else if (q == 3) { long c = 0; for (suhmo_level *L : V.box) for (int f = 0; f < SUHMO_F_COUNT; f++) if (L->d[0].fp.f[f]) c += (long)L->d[0].elems * 8;
+                               c += (long)V.flat_slab.size() * (long)V.flat_elems * 8; *value = c; }     // (with the scratch of suhmo_hier_flatten)
             // 4 sides x 8 B of the owned boxes
             else { long c = 0; for (int k = V.part ? V.b0 : 0; k < (V.part ? V.b0 + V.nown : 0); k++) { const int *b = &V.b4[4 * k];
                 c += 8L * 2 * ((b[2] - b[0] + 1) + (b[3] - b[1] + 1)); } *value = c; }

@@ -555,8 +555,22 @@ int hier_ff(suhmo_hier *H, int l, int f0, int f1, bool corners, hipStream_t st, 
         if ((rc = sync_run(H, l, S, fl, f1 >= 0 ? 2 : 1, st))) return rc;
     }
     // (a corner ghost's source is a valid cell, never a ghost: sides and corners do not depend on each other)
+    return hier_ff_on(H, l, V.d_fp, f0, f1, corners, st);
+}
+// the launch of hier_ff / hier_pwl over tables the caller holds: canvases with the geometry of the boxes' own, numbered as the caller likes
+// (suhmo_flatten.hip: its private scratch).  Levels held whole by this process
+int hier_ff_on(suhmo_hier *H, int l, const FP *tab, int f0, int f1, bool corners, hipStream_t st)
+{
+    HLev &V = H->lev[l];
     const DevVec<CopyEnt> &list = corners ? V.ff_all : V.ff_side;
-    if (list.n) hipLaunchKernelGGL(k_ff, g1(list.n), dim3(256), 0, st, list.d, (int)list.n, V.d_fp, f0, f1);
+    if (list.n) hipLaunchKernelGGL(k_ff, g1(list.n), dim3(256), 0, st, list.d, (int)list.n, tab, f0, f1);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+int hier_pwl_on(suhmo_hier *H, int l, const FP *ftab, int ff, const FP *ctab, const FP &cbase, int use_base, int fc, hipStream_t st)
+{
+    HLev &V = H->lev[l];
+    if (V.pwl.n) hipLaunchKernelGGL(k_pwl, g1(V.pwl.n), dim3(256), 0, st, V.pwl.d, (int)V.pwl.n, ftab, ff, ctab, cbase, use_base, fc);
     HIPCHK(hipGetLastError());
     return 0;
 }
@@ -607,9 +621,7 @@ int hier_pwl(suhmo_hier *H, int l, int ff, int fc, hipStream_t st)
     if (l == 1 && (rc = refresh_base1(H, fc, st))) return rc;
     if (l > 1 && V.part && (rc = sync1(H, l - 1, V.sy_cread, fc, st))) return rc;
     if ((rc = coarse_args(H, l - 1, st, ca))) return rc;
-    if (V.pwl.n) hipLaunchKernelGGL(k_pwl, g1(V.pwl.n), dim3(256), 0, st, V.pwl.d, (int)V.pwl.n, V.d_fp, ff, ca.tab, ca.base, ca.use_base, fc);
-    HIPCHK(hipGetLastError());
-    return 0;
+    return hier_pwl_on(H, l, V.d_fp, ff, ca.tab, ca.base, ca.use_base, fc, st);
 }
 // FORT_AVERAGE of field ff of level l into the covered cells of field fc of level l-1 (mode 0) / covered cells <- val (mode 1)
 int hier_avg(suhmo_hier *H, int l, int ff, int fc, int mode, double val, hipStream_t st)

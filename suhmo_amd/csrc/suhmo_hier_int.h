@@ -128,6 +128,9 @@ struct HLev {
     DevVec<RectEnt> avg_put; DevVec<PutEnt> avg_get; long put_stride = 0, put_mine = 0; int put_w = 0, put_h = 0, get_w = 0, get_h = 0;
     long owned_cells = 0, held_boxes = 0;
     DevVec<long> snap_cells[2];                      // suhmo_snap.hip: per box the cells of the boxes before it, each grown by 0 / 1 ghost cells (built on first use)
+    // suhmo_flatten.hip: the level's private scratch -- per component slot ONE allocation that holds a canvas of every box (flat_elems doubles),
+    // and the boxes' pointers into them as a table, slot q in f[q] (on the host; for the levels >= 1 on the device too).  Allocated on first use
+    std::vector<double *> flat_slab; size_t flat_elems = 0; std::vector<FP> flat_h; FP *flat_fp = nullptr;
 };
 }  // namespace hier
 
@@ -192,6 +195,11 @@ struct suhmo_hier {
     // (read-only options snapshot_launches, snapshot_copies); plots and checkpoints the last run handed to its callback (run_plots, run_checkpoints)
     double *snap_buf = nullptr; size_t snap_cap = 0;
     long n_snap_launches = 0, n_snap_copies = 0, n_run_plots = 0, n_run_checkpoints = 0;
+    // suhmo_flatten.hip: the finest array on the device (the largest so far; allocated on first use), the launches and copies of the flattens
+    // (read-only options flatten_launches, flatten_copies)
+    double *flat_buf = nullptr; size_t flat_cap = 0;
+    long n_flat_launches = 0, n_flat_copies = 0;
+    long flat_fail_slot = -1;                              // option flatten_fail_slot (tests): the allocation of this scratch slot on the finest level fails
     double *red_all = nullptr;                             // partial maxima of a norm over all levels of boxes (64 per box + 16)
     struct suhmo_tagmap *tags[8] = {};                     // tag maps of suhmo_hier_tag_cells, one per level (suhmo_tags.hip), owned
     hier::DevVec<hier::RectEnt> cover_full;                            // coarsen(boxes of level 1) in the shadow: COVER of the whole level 0
@@ -277,6 +285,8 @@ int hier_ff(suhmo_hier *H, int l, int f0, int f1, bool corners, hipStream_t st, 
 int hier_cf(suhmo_hier *H, int l, int ff, int fc, hipStream_t st, int ff1 = -1, int fc1 = -1);
 int hier_cf_ff(suhmo_hier *H, int l, int ff, int fc, int ff1, int fc1, bool corners, hipStream_t st);
 int hier_pwl(suhmo_hier *H, int l, int ff, int fc, hipStream_t st);
+int hier_ff_on(suhmo_hier *H, int l, const FP *tab, int f0, int f1, bool corners, hipStream_t st);
+int hier_pwl_on(suhmo_hier *H, int l, const FP *ftab, int ff, const FP *ctab, const FP &cbase, int use_base, int fc, hipStream_t st);
 int hier_avg(suhmo_hier *H, int l, int ff, int fc, int mode, double val, hipStream_t st);
 int hier_window_save(suhmo_hier *H, int l, int field_c, hipStream_t st);
 int hier_prolong2(suhmo_hier *H, int l, int field_c, hipStream_t st, bool minus_saved = false, bool leave_below = false);
@@ -313,3 +323,5 @@ int suhmo_amr_check_hierarchy(suhmo_level_t **lv, int nlev);
 // ---- suhmo_snap.hip: what the run needs of the snapshot -- its refusals, and the offsets (level_offset [nlev + 1], box_offset, either may be NULL) -> doubles in all
 int suhmo_hier_snapshot_check_(const suhmo_hier *H, const char *who, int ncomp, const suhmo_snap_comp_t *comps, int ghost);
 long suhmo_hier_snapshot_sizes_(const suhmo_hier *H, int ncomp, int ghost, long *level_offset, long *box_offset);
+// ---- suhmo_flatten.hip: its scratch and finest array go with the hierarchy
+void suhmo_hier_flatten_release_(suhmo_hier *H);

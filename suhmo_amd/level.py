@@ -516,6 +516,19 @@ class HipHier:
         check(capi.lib().suhmo_hier_snapshot(self.h, len(comps), arr, int(ghost), lo, bo, flat.ctypes.data_as(C.POINTER(C.c_double)), self.stream))
         return np.array(lo[:], dtype=np.int64), split_box_offsets(bo, nbox), flat
 
+    def flatten(self, comps, max_level=None, out=None):
+        """suhmo_hier_flatten (AmrHydro::interpFinest): the components (capi.flat_comps takes them: (FLAT_FIELD, field) or (FLAT_DIFF, field,
+        field2)) of the whole hierarchy interpolated onto the uniform grid of level max_level (None: the finest level) -> an
+        (ncomp, ny0 << max_level, nx0 << max_level) array.  Read-only; one copy off the device"""
+        ml = self.nlev - 1 if max_level is None else int(max_level)
+        arr, dims = capi.flat_comps(comps), (C.c_long * 2)()
+        check(capi.lib().suhmo_hier_flatten(self.h, ml, len(comps), arr, dims, None, self.stream))
+        shape = (len(comps), int(dims[1]), int(dims[0]))
+        a = np.zeros(shape) if out is None else out
+        assert a.shape == shape and a.dtype == np.float64 and a.flags.c_contiguous
+        check(capi.lib().suhmo_hier_flatten(self.h, ml, len(comps), arr, dims, a.ctypes.data_as(C.POINTER(C.c_double)), self.stream))
+        return a
+
     def owns(self, l, k):
         """this rank computes box k of level l (every box of a replicated level; on a level dealt to the ranks: its own boxes)"""
         return self.owner[l][k] in (-1, self.rank)

@@ -675,6 +675,16 @@ class HipHierModel:
             self.regrid(boxes, reload=reload, fields=fields)
         return boxes, same
 
+    # the reference's two plotted components (src/AmrHydro.cpp:4672-4677): the gap height, and N = Pi - Pw formed BEFORE the interpolation
+    PP_COMPONENTS = [("gapHeight", (capi.FLAT_FIELD, lv.F_B)), ("N", (capi.FLAT_DIFF, lv.F_PI, lv.F_PW))]
+
+    def interp_finest(self, max_level=None):
+        """AmrHydro::interpFinest (src/AmrHydro.cpp:4623-4829) on the device, suhmo_hier_flatten: gap height and effective pressure of the whole
+        hierarchy on the uniform grid of level max_level (None: the finest level) -> dict(gapHeight=, N=), each (ny0 << max_level,
+        nx0 << max_level).  Read-only."""
+        a = self.hier.flatten([c for _, c in self.PP_COMPONENTS], max_level)
+        return {nm: a[q] for q, (nm, _) in enumerate(self.PP_COMPONENTS)}
+
     def restrict_tags(self, level, boxes):
         """levelTags &= tagSubset (suhmo_hier_restrict_tags): every entry of the tag map of `level` that lies in none of `boxes`
         ((lo0, lo1, hi0, hi1) in cells of that level, aligned to the map's granularity) is cleared; an empty list is a no-op"""

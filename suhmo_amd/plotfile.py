@@ -120,3 +120,25 @@ def write(path, model, time, dt=1.0):
     else:
         raise TypeError("plotfile.write takes a HipModel or a HipHierModel, not %s" % type(model).__name__)
     write_levels(path, NAMES, levels, time, dt)
+
+
+def pp_name(prefix, step):
+    """the name AmrHydro::writePltPP gives its file (src/AmrHydro.cpp:5349-5361, namePlot = ".2d" at :4823)"""
+    return "%sCustom%06d.2d.hdf5" % (prefix, int(step))
+
+
+def write_pp(path, model, time, max_level=None):
+    """AmrHydro::writePltPP (src/AmrHydro.cpp:5298-5389) of a HipHierModel: gap height and N = Pi - Pw of the whole hierarchy on the uniform grid
+    of level max_level (HipHierModel.interp_finest: one flatten on the device, one copy), written as ONE level with ghost 0 and dx = level 0's
+    dx / 2^max_level.  Deviations from the reference's file: the finest domain is one box (the reference cuts it with domainSplit); the
+    ratio attribute is what write_levels writes for a finest level; the reference's third quantity tau (:4678) is not built.
+    -> the (2, nyF, nxF) array that went into the file"""
+    H = model.hier
+    ml = H.nlev - 1 if max_level is None else int(max_level)
+    a = H.flatten([c for _, c in model.PP_COMPONENTS], ml)
+    nyF, nxF = a.shape[1:]
+    L0 = model.level[0][0]
+    lev = dict(dx=L0.dx / 2 ** ml, dy=L0.dy / 2 ** ml, domain=(0, 0, nxF - 1, nyF - 1), boxes=[(0, 0, nxF - 1, nyF - 1)], offsets=np.array([0, a.size]),
+               data=a.reshape(-1))
+    write_levels(path, [nm for nm, _ in model.PP_COMPONENTS], [lev], time, 1.0, ghost=0)
+    return a

@@ -1,6 +1,10 @@
 #!/usr/bin/env python3
 """cfg5 (exec/AMR_multiMoulins physics) time step on base + 3 AMR levels of box unions: ms per step.
-    python tools/hier_bench.py [--generated-grids] [--regrid-interval N [--one-call [--plot-interval P]]] [--recharge] [--snapshot] [base cells per side] [steps]
+    python tools/hier_bench.py [--generated-grids] [--regrid-interval N [--one-call [--plot-interval P]]] [--recharge] [--snapshot] [--flatten] [base cells per side] [steps]
+--flatten: gap height and N = Pi - Pw of the hierarchy on the uniform grid of level 4 (HipHierModel.interp_finest's call, suhmo_hier_flatten), three
+repetitions: the time of the kernels and of the copy to the host separately (the library's named timers with the device synchronised around either
+part), the launch and copy counts -- and, alternating with it, the per-box get calls that bring the same fields to the host (their count and time
+only: the host arithmetic that would follow is no baseline).
 --plot-interval P (with --one-call): the runs of HipHierModel.run also write a plot file before every step c with (c - 1) % P == 0 (suhmo_hier_run_out:
 one snapshot and one file per event, into a temporary directory); the per-call loop beside it writes none, so the difference is what the output costs.
 --snapshot: one 13-component snapshot of the hierarchy (suhmo_hier_snapshot: a launch and a copy per level) against the per-box get loop for the same
@@ -27,7 +31,8 @@ generated = "--generated-grids" in sys.argv
 one_call = "--one-call" in sys.argv
 recharge = "--recharge" in sys.argv
 snapshot = "--snapshot" in sys.argv
-argv = [a for a in sys.argv[1:] if a not in ("--generated-grids", "--one-call", "--recharge", "--snapshot")]
+flatten = "--flatten" in sys.argv
+argv = [a for a in sys.argv[1:] if a not in ("--generated-grids", "--one-call", "--recharge", "--snapshot", "--flatten")]
 plot_interval = -1
 if "--plot-interval" in argv:
     q = argv.index("--plot-interval")
@@ -308,6 +313,55 @@ def snapshot_bench(rounds=3):
     M.close()
 
 
+def flatten_bench(rounds=3, max_level=4):
+    """one flatten of the reference's two components against the per-box get calls for the fields it reads"""
+    import numpy as np
+    from suhmo_amd import capi, level as lv
+    M = model.HipHierModel(nb, nb, sts[0][0]["dx"], sts[0][0]["dy"], bc, ph, mm, boxes, max_box=64)
+    M.set_states(sts)
+    M.moulin_source(**mo)
+    for _ in range(3):
+        M.timestep(mm["dt"])
+    comps = [c for _, c in M.PP_COMPONENTS]
+    fields = (lv.F_B, lv.F_PI, lv.F_PW)
+    for bl in M.level:                                       # (neither side is the one that allocates a field)
+        for L in bl:
+            for f in fields:
+                L.get(f)
+    sync = M.level[0][0].synchronize
+    nbx = sum(len(bl) for bl in M.level)
+    out = M.hier.flatten(comps, max_level)                   # (the first call allocates the scratch and the finest array)
+    print("flatten: boxes per level %s, %d handles with level 0, %d components on %d x %d cells: %.1f MB"
+          % ([len(b) for b in boxes], nbx, len(comps), out.shape[2], out.shape[1], out.nbytes / 1e6), flush=True)
+    def flat():
+        n_l, n_c = M.hier.get_option("flatten_launches"), M.hier.get_option("flatten_copies")
+        capi.lib().suhmo_timers_enable(2); capi.lib().suhmo_timers_reset()
+        M.hier.flatten(comps, max_level, out=out)
+        rep = capi.timers_report(); capi.lib().suhmo_timers_enable(0)
+        t = {}
+        for line in rep.splitlines():
+            q = line.rsplit(None, 3)
+            if len(q) == 4 and q[0].startswith("interpFinest:"):
+                t[q[0]] = 1e3 * float(q[2])
+        return "kernels %.3f ms, copy to the host %.3f ms, %d launches, %d copy" % (
+            t.get("interpFinest: evaluation, ghost fills, interpolation", -1.0), t.get("interpFinest: copy to the host", -1.0),
+            M.hier.get_option("flatten_launches") - n_l, M.hier.get_option("flatten_copies") - n_c)
+    def per_box():
+        for bl in M.level:
+            for L in bl:
+                for f in fields:
+                    L.get(f)
+        return "no launch, %d copies (one per box and field)" % (len(fields) * nbx)
+    for r in range(rounds):
+        for name, fn in (("one flatten", flat), ("per-box get calls", per_box)) if r % 2 == 0 else (("per-box get calls", per_box), ("one flatten", flat)):
+            sync()
+            t0 = time.perf_counter()
+            what = fn()
+            sync()
+            print("round %d, %-17s: %.3f ms in all, %s" % (r, name, 1e3 * (time.perf_counter() - t0), what), flush=True)
+    M.close()
+
+
 def recharge_bench(evals=50, reps=3):
     """the hierarchy's recharge call against the per-box level calls"""
     import numpy as np
@@ -338,6 +392,9 @@ if recharge:
     sys.exit(0)
 if snapshot:
     snapshot_bench()
+    sys.exit(0)
+if flatten:
+    flatten_bench()
     sys.exit(0)
 if one_call:
     assert regrid_interval > 0, "--one-call needs --regrid-interval"
