@@ -604,7 +604,7 @@ int suhmo_tag_subsets_nest(int nlev, const int *nbox, const int *boxes, int *nbo
  *     (I + a, J + b), c0 = c(0, 0):
  *       neighbours  (I + a, J + b) EXISTS if it lies in the coarse domain after the wrap through a periodic side; proper nesting makes every
  *                   existing neighbour a valid cell of level l - 1.
- *       slopes      s[d] as oracle/amr_step.c:or_pwl_fill and k_pwl compute them: central 0.5 * (c(+1) - c(-1)) when both neighbours in
+ *       slopes      s[d] as oracle/amr_step_m.c:or_pwl_fill and k_pwl compute them: central 0.5 * (c(+1) - c(-1)) when both neighbours in
  *                   direction d exist, c(+1) - c0 when the low one does not, c0 - c(-1) when the high one does not (neither: 0).
  *       limiter     FORT_INTERPLIMIT, or_pwl_fill's arithmetic: smax, smin over the existing cells of the 3 x 3 block (c0 included);
  *                   deltasum = 0.5 * (|s0| + |s1|); where deltasum > 0: etamax = (smax - c0) / deltasum, etamin = (c0 - smin) / deltasum,

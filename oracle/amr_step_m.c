@@ -1,33 +1,29 @@
 /*
- * amr_step_m.c -- TEST INFRASTRUCTURE ONLY.  One AmrHydro::timeStepFAS (src/AmrHydro.cpp:2254-3460) on a hierarchy whose
- * levels >= 1 are UNIONS OF BOXES (oracle/amrm.c): amr_step.c with every level's rectangle replaced by its list of boxes.
- * Every box is an OrModel of its own (time_loop.c) whose four sides inside the domain carry data ghosts; after every fill
- * of such ghosts the reference's exchange() follows here as the fine-fine copy between the boxes of the level:
- *   PiecewiseLinearFillPatch of b, mR (:2373-2380, :2499-2507), Re (:2711-2719) + exchange (:2385, :2513, :2721)
- *   QuadCFInterp of h (inside compGradientMAC, coverage-aware stencils of amrm.c) and of the cell-centred gradient
- *     (:1650-1656) + exchange (:1659)
- *   SolveForHead_nl over the hierarchy = or_amrm_solve, CoarseAverage of h (:3138-3141)
+ * amr_step_m.c -- TEST INFRASTRUCTURE ONLY.  One AmrHydro::timeStepFAS (src/AmrHydro.cpp:2254-3460) on a hierarchy: level 0 =
+ * the domain, levels >= 1 = UNIONS OF BOXES refined by 2 (oracle/amrm.c).  The one restatement of the AMR time step: nested
+ * single patches are the one-box-per-level case (OracleAmrModel of pyoracle.py is a view of this file).
+ * Every box is an OrModel of its own (time_loop.c) that runs the phases of time_loop.c on its rectangle; its four sides
+ * inside the domain carry data ghosts, filled by the inter-level steps of the reference, each followed by the reference's
+ * exchange() as the fine-fine copy between the boxes of the level:
+ *   PiecewiseLinearFillPatch of b, mR (:2373-2380, :2499-2507), Re (:2711-2719, :3265-3273) + exchange (:2385, :2513,
+ *     :2721) [the fills of h and qw are never read: h's ghosts are re-interpolated by compGradientMAC before any use, qw
+ *     is a debug variable]
+ *   QuadCFInterp of h inside Gradient::compGradientMAC (util/Gradient.cpp; coverage-aware stencils of amrm.c) and of the
+ *     cell-centred gradient (:1650-1656) + exchange (:1659)
+ *   SolveForHead_nl over all levels (AMRFASMultiGrid) = or_amrm_solve, CoarseAverage of h (:3138-3141)
  *   computeMax over the cells no finer level covers (:3169, :3185)
- * With one box per level this file IS amr_step.c bit for bit (tests/test_oracle_amr_step_m.py).  [Chombo] pieces as there:
- * unpinned.
+ * then the explicit gap-height update or the implicit one (SolveForGap_nl over the hierarchy :593-662, :3425-3455: a second
+ * set of levels with alpha = 1, beta = dt diffFactor, bCoef = D, no nonlinear term, Neumann-0 sides, the stand-in operator
+ * and cycle of time_loop.c:solve_gap_implicit).
+ * [Chombo] PiecewiseLinearFillPatch is restated from upstream Chombo 3.2's documented algorithm (fillConstantInterp +
+ * computeMultiDimSlopes: central differences, one-sided next to the domain boundary, FORT_INTERPLIMIT's multi-dimensional
+ * limiter over the 3 x 3 neighbourhood + FORT_INTERPLINEAR) -- the fork is not vendored: UNPINNED, like CoarseAverage and
+ * the rest of the Chombo-side AMR pieces (amrm.c).
  */
 #include "time_loop.h"
 #include <math.h>
 #include <stdlib.h>
 #include <string.h>
-
-/* oracle/amrm.c */
-typedef struct OrAmrM OrAmrM;
-OrAmrM *or_amrm_create(OrLevel *base, int nx0, int ny0, double dx0, double dy0, const OrBC *bc, const OrPhys *ph,
-                       double alpha, double beta, int nlev, const int *nbox, const int *boxes);
-void or_amrm_destroy(OrAmrM *A);
-void or_amrm_box_io(OrAmrM *A, int l, int k, int field, double *g, int ghosted, int set);
-int or_amrm_solve(OrAmrM *A, const OrSolverParams *sp, double *hist);
-int or_amrm_owner(const OrAmrM *A, int l, int i, int j);
-void or_amrm_exchange_fabs(OrAmrM *A, int l, OrFab **fabs, int corners);
-void or_amrm_cf_interp_fabs(OrAmrM *A, int l, OrFab **fabs, int comp, const double *coarse);
-/* oracle/amr_step.c */
-void or_pwl_fill(const OrModel *F, const OrModel *C, double *f, const double *c);
 
 #define AMAXLEV 8
 typedef struct OrAmrMModel {
@@ -88,6 +84,44 @@ void or_amrm_model_destroy(OrAmrMModel *S)
 OrModel *or_amrm_model_box(OrAmrMModel *S, int l, int k) { return S->M[l][k]; }
 double *or_amrm_model_field(OrAmrMModel *S, int l, int k, int id) { return or_model_field(S->M[l][k], id); }
 void or_amrm_model_gap_solver_layout(OrAmrMModel *S, int max_box, int nthreads) { S->max_box = max_box; S->nthreads = nthreads; }
+
+/* ---- [Chombo] PiecewiseLinearFillPatch, ratio 2, one layer of ghost cells (corners included) of the rectangle F from
+ * the rectangle C of the level below; cells outside the domain are left alone */
+void or_pwl_fill(const OrModel *F, const OrModel *C, double *f, const double *c)
+{
+    for (int j = -1; j <= F->ny; j++)
+        for (int i = -1; i <= F->nx; i++) {
+            if (i >= 0 && i < F->nx && j >= 0 && j < F->ny) continue;
+            int gi = i + F->i0, gj = j + F->j0;
+            if (gi < 0 || gi >= F->nxg || gj < 0 || gj >= F->nyg) continue;
+            int I = gi >> 1, J = gj >> 1, Ic = I - C->i0, Jc = J - C->j0;
+            double c0 = G(C, c, Ic, Jc), s[2];
+            for (int d = 0; d < 2; d++) {
+                int K = d == 0 ? I : J, nd = d == 0 ? C->nxg : C->nyg, ii = d == 0, jj = d == 1;
+                if (K - 1 >= 0 && K + 1 <= nd - 1) s[d] = 0.5 * (G(C, c, Ic + ii, Jc + jj) - G(C, c, Ic - ii, Jc - jj));   /* INTERPCENTRALSLOPE */
+                else if (K - 1 < 0) s[d] = G(C, c, Ic + ii, Jc + jj) - c0;                                               /* INTERPHISIDESLOPE */
+                else s[d] = c0 - G(C, c, Ic - ii, Jc - jj);                                                               /* INTERPLOSIDESLOPE */
+            }
+            double smax = c0, smin = c0;                                                                                 /* INTERPLIMIT */
+            for (int jj = -1; jj <= 1; jj++)
+                for (int ii = -1; ii <= 1; ii++) {
+                    int In = I + ii, Jn = J + jj;
+                    if (In < 0 || In > C->nxg - 1 || Jn < 0 || Jn > C->nyg - 1) continue;
+                    double v = G(C, c, Ic + ii, Jc + jj);
+                    smax = fmax(smax, v); smin = fmin(smin, v);
+                }
+            double deltasum = 0.5 * (fabs(s[0]) + fabs(s[1]));
+            if (deltasum > 0.0) {
+                double etamax = (smax - c0) / deltasum, etamin = (c0 - smin) / deltasum;
+                double eta = fmax(fmin(fmin(etamin, etamax), 1.0), 0.0);
+                s[0] = eta * s[0]; s[1] = eta * s[1];
+            }
+            double v = c0;                                                                                               /* fillConstantInterp */
+            v = v + s[0] * ((gi & 1) ? 0.25 : -0.25);                                                                    /* INTERPLINEAR, dir 0 */
+            v = v + s[1] * ((gj & 1) ? 0.25 : -0.25);
+            G(F, f, i, j) = v;
+        }
+}
 
 /* ---- level-wide helpers ---- */
 /* valid cells of a field of level l over its DOMAIN (zero where the level has no box) */
@@ -161,9 +195,10 @@ static void mm_pwl(OrAmrMModel *S, int l, int fid)
     free(c);
     mm_ff(S, l, fid, 1);
 }
-/* the same for tests of the device's suhmo_hier_pwl_fill on its own (tests/test_gpu_hier_layouts.py) */
+/* the two fills on their own, for tests (the device's suhmo_hier_pwl_fill: tests/test_gpu_hier_layouts.py) */
 void or_amrm_model_pwl_fill(OrAmrMModel *S, int l, int fid) { mm_pwl(S, l, fid); }
-/* [Chombo] CoarseAverage: covered cells of level l-1 <- average of the 4 fine cells */
+void or_amrm_model_quadcf_fill(OrAmrMModel *S, int l, int fid) { mm_quadcf(S, l, fid, 0); }
+/* [Chombo] CoarseAverage / FORT_AVERAGE: covered cell of level l-1 = (sum of its 4 fine cells, i fastest) / 4 */
 static void mm_average_down(OrAmrMModel *S, int l, int fid)
 {
     for (int k = 0; k < S->nbox[l]; k++) {
@@ -197,7 +232,9 @@ static void chain(OrAmrMModel *S, int l)
     for (int k = 0; k < S->nbox[l]; k++) or_model_qw(S->M[l][k]);
 }
 
-/* Calc_moulin_integral + Calc_moulin_source_term_distributed on the hierarchy (:1866-2066, :2797-2837), as amr_step.c */
+/* Calc_moulin_integral + Calc_moulin_source_term_distributed on the hierarchy (:1866-2066, :2797-2837): the Gaussians
+ * are sampled on every level, cells under a finer level do not count in the integral and get the average of the finer
+ * level's source term afterwards.  Result in OM_MSRC of every box (valid cells); integ: nm integrals. */
 void or_amrm_model_moulin_source(OrAmrMModel *S, int nm, const double *pos, const double *sigma, const double *flux,
                                  double time_factor, double *integ)
 {

@@ -15,19 +15,43 @@
  * At a re-entrant corner of the union the same index is the x-ghost of one box and the y-ghost of another, with
  * different interpolated values: per-box storage keeps both, as the reference does.
  *
- * Same provenance as amrn.c, which is the one-box-per-level special case and must agree with this file BIT FOR BIT
- * (tests/test_oracle_amrm.py): operator methods follow src/AMRNonLinearPoissonOp.cpp:690-704, 889-1264,
- * src/VCAMRNonLinearPoissonOp.cpp:34-64, 555-652, 792-841, src/AmrHydro.cpp:1415-1539.  [Chombo] = restated from upstream
- * Chombo 3.2 semantics because the fork is not vendored (UNPINNED):
- *   QuadCFInterp / QuadCFStencil   tangential derivatives on the coarse level use only "good" coarse cells = inside the
- *                                  domain (or periodic images) and NOT covered by the fine level: centred when both
- *                                  neighbours are good, second-order one-sided when two good cells lie on one side,
- *                                  "dropped order" (first-order difference, no second derivative) when only one does,
- *                                  zero derivatives when none does; then the normal quadratic 8/15, 2/3, -1/5.
- *                                  With one rectangular box per level the covered test never fires.
- *   LevelFluxRegister              a coarse cell next to several coarse-fine faces takes their increments one after
- *                                  the other in the order (fine box, direction, side).
- *   FORT_AVERAGE, the ghosted coarse copy of AMRProlongS_2, the AMR FAS cycle order.
+ * The one restatement of the AMR solve: a hierarchy of nested single patches is the one-box-per-level case (the classes
+ * OracleAmr2 / OracleAmr of pyoracle.py are views of this file), cfg3 of BASELINE.json (exec/0_convergence_channelized/
+ * 2lev_base, a fixed refined box around the moulin) is base + one box, cfg4 / cfg5 are 3-level hierarchies.
+ *
+ * Restated from the reference's own source:
+ *   relaxNF / AMRResidualNF / AMROperator / AMRRestrictS / AMRProlongS_2 / AMRNorm
+ *                                              src/AMRNonLinearPoissonOp.cpp:690-704, 889-1069, 1143-1264
+ *   reflux + getFlux                           src/VCAMRNonLinearPoissonOp.cpp:555-652, 792-841
+ *   UpdateOperator / WFlx_level with a coarser level   src/VCAMRNonLinearPoissonOp.cpp:34-64,
+ *                                              src/AmrHydro.cpp:1415-1539 (coarse branch :1455-1488)
+ *   mixBCValues on the box sides on the domain boundary   src/AmrHydro.cpp:248-309
+ *   ExtrapGhostCells on those sides            util/ExtrapGhostCells.cpp:94-180
+ * [Chombo] = NOT in the reference's tree, restated from upstream Chombo 3.2's documented semantics because the fork is
+ * not vendored ("parity unpinned"):
+ *   QuadCFInterp / QuadCFStencil   for every fine ghost cell outside a box side that is neither on the domain boundary
+ *                                  nor held by another box: (1) the coarse field is interpolated along the interface to
+ *                                  the ghost cell's tangential position (+-1/4 coarse cell) with a quadratic through the
+ *                                  coarse cell containing it and its tangential neighbours; (2) a quadratic in the normal
+ *                                  direction through that value (1.5 fine cells beyond the first interior fine cell) and
+ *                                  the two fine cells inside gives ghost = 8/15 phistar + 2/3 near - 1/5 far.  Corner
+ *                                  ghost cells are not filled (the 5-point operator never reads them).  The tangential
+ *                                  derivatives use only "good" coarse cells = inside the domain (or periodic images) and
+ *                                  NOT covered by the fine level: centred when both neighbours are good, second-order
+ *                                  one-sided when two good cells lie on one side, "dropped order" (first-order
+ *                                  difference, no second derivative) when only one does, zero derivatives when none
+ *                                  does.  With one rectangular box per level the covered test never fires.
+ *   LevelFluxRegister              on every coarse-fine face the coarse flux is replaced by the average of the two fine
+ *                                  fluxes: reg = -(dt Fc) + (dt Ff0)/2 + (dt Ff1)/2 (dt = transverse coarse cell size),
+ *                                  then L(phi) of the coarse cell OUTSIDE the box += sign reg / (dx dy), sign = +1 when
+ *                                  the face is the cell's high face.  A coarse cell next to several coarse-fine faces
+ *                                  takes their increments one after the other in the order (fine box, direction, side).
+ *   FORT_AVERAGE                   coarse = (sum of the 4 fine cells, i fastest) * 1/4
+ *   AMRProlongS_2                  the coarse correction with its BC ghosts (inhomogeneous in FAS mode :1163-1165) and,
+ *                                  inside the domain, the neighbouring coarse cells (copyTo + CornerCopier)
+ *   the AMR FAS cycle order        SURVEY.md Appendix D, VCycleAMR
+ * Data of a level is handed between levels as arrays over that level's whole DOMAIN (zero where it has no box), which
+ * keeps the inter-level stencils identical for a base level and for a union of boxes.
  */
 #include "level_shim.h"
 #include <math.h>
@@ -50,11 +74,11 @@ typedef struct LvM {
     int nbox; Bx *b;                  /* l >= 1 */
     int *owner;                       /* l >= 1: nyd x nxd, index of the box holding the cell, -1 = none */
 } LvM;
-typedef struct OrAmrM {
+struct OrAmrM {
     int nlev;
     LvM lv[MAXLEV];
     OrBC bc; OrPhys ph; double alpha, beta;
-} OrAmrM;
+};
 
 static OrFab fab_alloc(OrBox b, int g, int ncomp)
 {
@@ -78,9 +102,7 @@ static int owner_of(const OrAmrM *A, const LvM *V, int i, int j)
     return V->owner[(size_t)j * V->nxd + i];
 }
 
-/* nbox[l], l = 1 .. nlev-1 (nbox[0] is ignored); boxes: all levels' boxes one after the other, 4 ints each
- * (lo0, lo1, hi0, hi1) in the index space of THEIR OWN level.  Returns NULL if a box is misaligned, boxes overlap
- * or the nesting fails. */
+/* (level_shim.h) */
 OrAmrM *or_amrm_create(OrLevel *base, int nx0, int ny0, double dx0, double dy0, const OrBC *bc, const OrPhys *ph,
                        double alpha, double beta, int nlev, const int *nbox, const int *boxes)
 {
@@ -125,7 +147,7 @@ OrAmrM *or_amrm_create(OrLevel *base, int nx0, int ny0, double dx0, double dy0, 
                     if (l - 1 > 0 && C->owner[(size_t)j * C->nxd + i] < 0) { bad = 1; break; }
                 }
         }
-        if (bad) { A->nlev = l + 1; void or_amrm_destroy(OrAmrM *); or_amrm_destroy(A); return NULL; }
+        if (bad) { A->nlev = l + 1; or_amrm_destroy(A); return NULL; }
     }
     return A;
 }
@@ -252,7 +274,8 @@ static void exchange(OrAmrM *A, int l, int field, int corners)
     free(fabs);
 }
 
-/* ---------------- box operator methods, as amrn.c ---------------- */
+/* ---------------- box operator methods ---------------- */
+/* mixBCValues on the sides of the box that lie on the domain boundary (src/AmrHydro.cpp:248-309) */
 static void box_bc(const OrAmrM *A, OrFab *state, int homogeneous, const double dx[2], int ndx, int ndy, OrBox valid)
 {
     for (int dir = 0; dir < 2; dir++) {
@@ -718,6 +741,7 @@ int or_amrm_solve(OrAmrM *A, const OrSolverParams *sp, double *hist)
 void or_amrm_cf_interp_phi(OrAmrM *A, int l) { cf_interp_phi(A, l); }
 void or_amrm_exchange(OrAmrM *A, int l, int field, int corners) { exchange(A, l, field, corners); }
 void or_amrm_gsrb(OrAmrM *A, int l, int sweeps) { lv_gsrb(A, l, sweeps); }
+void or_amrm_apply_op(OrAmrM *A, int l) { lv_apply_op(A, l); }
 void or_amrm_level_residual(OrAmrM *A, int l) { lv_residual(A, l); }
 void or_amrm_update_operator(OrAmrM *A, int l) { level_update_operator(A, l); }
 void or_amrm_average_down(OrAmrM *A, int l, int field) { average_down(A, l, field); }

@@ -104,6 +104,31 @@ void or_difterm_global(const double *phi_ghosted, const double *dx_face, const d
 void or_getflux_global(const double *phi_ghosted, const double *bface, double *flux,
                        int nx, int ny, int dir, double beta, double dx_dir, int ref);
 
+/* --- amrm.c: the AMR head solve on a base level + levels that are unions of boxes --- */
+typedef struct OrAmrM OrAmrM;
+/* nbox[l], l = 1 .. nlev-1 (nbox[0] is ignored); boxes: 4 ints each (lo0, lo1, hi0, hi1) in the index space of their
+ * own level, all levels one after the other.  NULL if a box is misaligned, boxes overlap or the nesting fails. */
+OrAmrM *or_amrm_create(OrLevel *base, int nx0, int ny0, double dx0, double dy0, const OrBC *bc, const OrPhys *ph,
+                       double alpha, double beta, int nlev, const int *nbox, const int *boxes);
+void or_amrm_destroy(OrAmrM *A);
+int  or_amrm_owner(const OrAmrM *A, int l, int i, int j);   /* box holding the cell after the periodic wrap, -1 = none */
+/* box-sized arrays <-> fields of box k of level l >= 1, conventions of or_level_set / or_level_get */
+void or_amrm_box_io(OrAmrM *A, int l, int k, int field, double *g, int ghosted, int set);
+double or_amrm_residual(OrAmrM *A);                          /* composite residual (RES of every level), its max norm */
+void or_amrm_vcycle(OrAmrM *A, const OrSolverParams *sp);
+int  or_amrm_solve(OrAmrM *A, const OrSolverParams *sp, double *hist);
+/* pieces, for kernel-level parity of the device library */
+void or_amrm_cf_interp_phi(OrAmrM *A, int l);
+void or_amrm_exchange(OrAmrM *A, int l, int field, int corners);
+void or_amrm_gsrb(OrAmrM *A, int l, int sweeps);
+void or_amrm_apply_op(OrAmrM *A, int l);
+void or_amrm_level_residual(OrAmrM *A, int l);
+void or_amrm_update_operator(OrAmrM *A, int l);
+void or_amrm_average_down(OrAmrM *A, int l, int field);
+/* the exchange and QuadCFInterp on fabs of the caller's (one per box of level l, 1 ghost layer): the time step's fields */
+void or_amrm_exchange_fabs(OrAmrM *A, int l, OrFab **fabs, int corners);
+void or_amrm_cf_interp_fabs(OrAmrM *A, int l, OrFab **fabs, int comp, const double *coarse);
+
 #ifdef __cplusplus
 }
 #endif

@@ -99,44 +99,7 @@ def lib():
         L.or_model_step_index.argtypes = [C.c_void_p]
         L.or_model_set_ramp.argtypes = [C.c_void_p, C.c_double]
         L.or_time_varying_recharge.argtypes = [C.c_int, dp, C.c_double, C.c_double, dp]
-        L.or_amr_model_create.restype = C.c_void_p
-        L.or_amr_model_create.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_double, C.POINTER(OrBC), C.POINTER(OrPhys),
-                                          C.POINTER(OrModelParams), C.c_int, C.POINTER(C.c_int)]
-        L.or_amr_model_destroy.argtypes = [C.c_void_p]
-        L.or_amr_model_gap_solver_layout.argtypes = [C.c_void_p, C.c_int, C.c_int]
-        L.or_amr_model_level.restype = C.c_void_p
-        L.or_amr_model_level.argtypes = [C.c_void_p, C.c_int]
-        L.or_pwl_fill.argtypes = [C.c_void_p, C.c_void_p, dp, dp]
-        L.or_quadcf_fill.argtypes = [C.c_void_p, C.c_void_p, dp, dp]
-        L.or_amr_model_field.restype = dp
-        L.or_amr_model_field.argtypes = [C.c_void_p, C.c_int, C.c_int]
-        L.or_amr_model_timestep.argtypes = [C.c_void_p, C.c_double, C.POINTER(C.c_int), C.POINTER(C.c_int)]
-        L.or_amr_model_moulin_source.argtypes = [C.c_void_p, C.c_int, dp, dp, dp, C.c_double, dp]
         L.or_moulin_source.argtypes = [C.c_int, C.c_int, C.c_double, C.c_double, C.c_int, dp, dp, dp, C.c_double, dp, dp]
-        L.or_amr2_create.restype = C.c_void_p
-        L.or_amr2_create.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_double, C.POINTER(OrBC), C.POINTER(OrPhys),
-                                     C.c_double, C.c_double, C.c_int, C.c_int, C.c_int, C.c_int]
-        L.or_amr2_destroy.argtypes = [C.c_void_p]
-        L.or_amr2_fine_io.argtypes = [C.c_void_p, C.c_int, dp, C.c_int, C.c_int]
-        for name in ("or_amr2_cf_interp_phi", "or_amr2_fine_residual", "or_amr2_fine_update_operator"):
-            getattr(L, name).argtypes = [C.c_void_p]
-        L.or_amr2_fine_gsrb.argtypes = [C.c_void_p, C.c_int]
-        L.or_amr2_fine_apply_op.argtypes = [C.c_void_p, C.c_int]
-        L.or_amr2_residual.restype = C.c_double
-        L.or_amr2_residual.argtypes = [C.c_void_p]
-        L.or_amr2_vcycle.argtypes = [C.c_void_p, C.POINTER(OrSolverParams)]
-        L.or_amr2_solve.restype = C.c_int
-        L.or_amr2_solve.argtypes = [C.c_void_p, C.POINTER(OrSolverParams), dp]
-        L.or_amr_create.restype = C.c_void_p
-        L.or_amr_create.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_double, C.POINTER(OrBC), C.POINTER(OrPhys),
-                                    C.c_double, C.c_double, C.c_int, C.POINTER(C.c_int)]
-        L.or_amr_destroy.argtypes = [C.c_void_p]
-        L.or_amr_patch_io.argtypes = [C.c_void_p, C.c_int, C.c_int, dp, C.c_int, C.c_int]
-        L.or_amr_residual.restype = C.c_double
-        L.or_amr_residual.argtypes = [C.c_void_p]
-        L.or_amr_vcycle.argtypes = [C.c_void_p, C.POINTER(OrSolverParams)]
-        L.or_amr_solve.restype = C.c_int
-        L.or_amr_solve.argtypes = [C.c_void_p, C.POINTER(OrSolverParams), dp]
         L.or_model_set_cutoffb.argtypes = [C.c_void_p, C.c_int]
         L.or_amrm_model_create.restype = C.c_void_p
         L.or_amrm_model_create.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_double, C.POINTER(OrBC), C.POINTER(OrPhys),
@@ -145,7 +108,11 @@ def lib():
         L.or_amrm_model_gap_solver_layout.argtypes = [C.c_void_p, C.c_int, C.c_int]
         L.or_amrm_model_field.restype = dp
         L.or_amrm_model_field.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int]
-        L.or_amrm_model_pwl_fill.argtypes = [C.c_void_p, C.c_int, C.c_int]
+        L.or_amrm_model_box.restype = C.c_void_p
+        L.or_amrm_model_box.argtypes = [C.c_void_p, C.c_int, C.c_int]
+        L.or_pwl_fill.argtypes = [C.c_void_p, C.c_void_p, dp, dp]
+        for name in ("or_amrm_model_pwl_fill", "or_amrm_model_quadcf_fill"):
+            getattr(L, name).argtypes = [C.c_void_p, C.c_int, C.c_int]
         L.or_amrm_model_timestep.argtypes = [C.c_void_p, C.c_double, C.POINTER(C.c_int), C.POINTER(C.c_int)]
         L.or_amrm_model_moulin_source.argtypes = [C.c_void_p, C.c_int, dp, dp, dp, C.c_double, dp]
         ip = C.POINTER(C.c_int)
@@ -372,118 +339,6 @@ def time_varying_recharge(zs, T_K, background):
     return out
 
 
-class OracleAmrModel:
-    """Hydrology time loop on a hierarchy (base level + nested patches, patches[k] = box of level k+1 in level-k cells):
-    oracle/amr_step.c"""
-
-    def __init__(self, nx0, ny0, dx0, dy0, bc, phys, model, patches, max_box=64, nthreads=1):
-        self.level = OracleLevel(nx0, ny0, dx0, dy0, bc, phys, 0.0, -1.0, max_box, nthreads)
-        self.patches = [tuple(int(v) for v in p) for p in patches]
-        self.nlev = 1 + len(self.patches)
-        self.dims = [(nx0, ny0)] + [(2 * (p[2] - p[0] + 1), 2 * (p[3] - p[1] + 1)) for p in self.patches]
-        self._mp = make_model_params(model)
-        flat = (C.c_int * max(4 * len(self.patches), 1))(*[v for p in self.patches for v in p])
-        self.h = lib().or_amr_model_create(self.level.h, nx0, ny0, dx0, dy0, C.byref(self.level._bc), C.byref(self.level._ph),
-                                           C.byref(self._mp), self.nlev, flat)
-        self.level.set(F_ACOEF, np.zeros((ny0, nx0)))
-        lib().or_amr_model_gap_solver_layout(self.h, max_box, nthreads)
-
-    def field(self, l, fid):
-        nx, ny = self.dims[l]
-        p = lib().or_amr_model_field(self.h, l, fid)
-        shape = {OM_QWX: (ny, nx + 1), OM_QWY: (ny + 1, nx)}.get(fid, (ny + 2, nx + 2))
-        return np.ctypeslib.as_array(p, shape=shape)
-
-    def set_state(self, l, f):
-        for k, fid in (("head", OM_H), ("B", OM_B), ("Pi", OM_PI), ("zb", OM_ZB), ("mask", OM_MASK)):
-            self.field(l, fid)[:] = f[k]
-
-    def fill_ghosts(self, l, fid, kind="pwl"):
-        """coarse-fine ghost cells of field fid of level l from level l-1: PiecewiseLinearFillPatch or QuadCFInterp"""
-        f = lib().or_pwl_fill if kind == "pwl" else lib().or_quadcf_fill
-        f(lib().or_amr_model_level(self.h, l), lib().or_amr_model_level(self.h, l - 1), lib().or_amr_model_field(self.h, l, fid),
-          lib().or_amr_model_field(self.h, l - 1, fid))
-
-    def moulin_source(self, positions, sigma, flux, time_factor=1.0):
-        pos = np.ascontiguousarray(positions, dtype=np.float64).reshape(-1)
-        sg, fl = np.ascontiguousarray(sigma, dtype=np.float64), np.ascontiguousarray(flux, dtype=np.float64)
-        integ = np.zeros(sg.size)
-        lib().or_amr_model_moulin_source(self.h, sg.size, _dp(pos), _dp(sg), _dp(fl), float(time_factor), _dp(integ))
-        return integ
-
-    def timestep(self, dt):
-        pi, nv = C.c_int(), C.c_int()
-        rc = lib().or_amr_model_timestep(self.h, dt, C.byref(pi), C.byref(nv))
-        if rc:
-            raise RuntimeError("AMR time step failed (rc %d)" % rc)
-        return pi.value, nv.value
-
-    def close(self):
-        if self.h:
-            lib().or_amr_model_destroy(self.h)
-            self.h = None
-            self.level.close()
-
-
-class OracleAmr2:
-    """Base level + one fine patch (coarse index box ci0..ci1 x cj0..cj1, refined by 2): oracle/amr2.c"""
-
-    def __init__(self, nxc, nyc, dxc, dyc, bc, phys, patch, alpha=0.0, beta=-1.0, max_box=64, nthreads=1):
-        self.coarse = OracleLevel(nxc, nyc, dxc, dyc, bc, phys, alpha, beta, max_box, nthreads)
-        self.patch = tuple(int(v) for v in patch)
-        ci0, cj0, ci1, cj1 = self.patch
-        self.nxp, self.nyp = 2 * (ci1 - ci0 + 1), 2 * (cj1 - cj0 + 1)
-        self.h = lib().or_amr2_create(self.coarse.h, nxc, nyc, dxc, dyc, C.byref(self.coarse._bc), C.byref(self.coarse._ph),
-                                      alpha, beta, ci0, cj0, ci1, cj1)
-
-    def fine_shape(self, field, ghosted=False):
-        if field == F_BX:
-            return (self.nyp, self.nxp + 1)
-        if field == F_BY:
-            return (self.nyp + 1, self.nxp)
-        return (self.nyp + 2, self.nxp + 2) if ghosted else (self.nyp, self.nxp)
-
-    def fine_set(self, field, arr, ghosted=False):
-        a = np.ascontiguousarray(arr, dtype=np.float64)
-        assert a.shape == self.fine_shape(field, ghosted), (a.shape, self.fine_shape(field, ghosted))
-        lib().or_amr2_fine_io(self.h, field, _dp(a), int(ghosted), 1)
-
-    def fine_get(self, field, ghosted=False):
-        out = np.zeros(self.fine_shape(field, ghosted))
-        lib().or_amr2_fine_io(self.h, field, _dp(out), int(ghosted), 0)
-        return out
-
-    def set_fine_inputs(self, f):
-        self.fine_set(F_PHI, f["phi"])
-        self.fine_set(F_RHS, f["rhs"])
-        self.fine_set(F_ACOEF, f["aCoef"])
-        for k, fid in (("B", F_B), ("Pi", F_PI), ("zb", F_ZB), ("mask", F_MASK)):
-            self.fine_set(fid, f[k], ghosted=True)
-
-    def cf_interp(self): lib().or_amr2_cf_interp_phi(self.h)
-    def fine_gsrb(self, sweeps): lib().or_amr2_fine_gsrb(self.h, sweeps)
-    def fine_residual(self): lib().or_amr2_fine_residual(self.h)
-    def fine_apply_op(self, homogeneous=False): lib().or_amr2_fine_apply_op(self.h, int(homogeneous))
-    def fine_update_operator(self): lib().or_amr2_fine_update_operator(self.h)
-    def residual(self): return lib().or_amr2_residual(self.h)
-
-    def vcycle(self, sp):
-        s = make_solver_params(sp)
-        lib().or_amr2_vcycle(self.h, C.byref(s))
-
-    def solve(self, sp):
-        s = make_solver_params(sp)
-        hist = np.zeros(s.max_iter + 2)
-        n = lib().or_amr2_solve(self.h, C.byref(s), _dp(hist))
-        return n, hist[: n + 1]
-
-    def close(self):
-        if self.h:
-            lib().or_amr2_destroy(self.h)
-            self.h = None
-            self.coarse.close()
-
-
 def moulin_source(nx, ny, dx, dy, positions, sigma, flux, time_factor=1.0):
     """(src (ny, nx), integrals (n,)): oracle/time_loop.c:or_moulin_source"""
     pos = np.ascontiguousarray(positions, dtype=np.float64).reshape(-1)
@@ -492,60 +347,6 @@ def moulin_source(nx, ny, dx, dy, positions, sigma, flux, time_factor=1.0):
     integ, src = np.zeros(nm), np.zeros((ny, nx))
     lib().or_moulin_source(nx, ny, dx, dy, nm, _dp(pos), _dp(sg), _dp(fl), float(time_factor), _dp(integ), _dp(src))
     return src, integ
-
-
-class OracleAmr:
-    """Base level + nested patches (patches[k] = box of level k+1 in the index space of level k): oracle/amrn.c"""
-
-    def __init__(self, nx0, ny0, dx0, dy0, bc, phys, patches, alpha=0.0, beta=-1.0, max_box=64, nthreads=1):
-        self.coarse = OracleLevel(nx0, ny0, dx0, dy0, bc, phys, alpha, beta, max_box, nthreads)
-        self.patches = [tuple(int(v) for v in p) for p in patches]
-        self.nlev = 1 + len(self.patches)
-        flat = (C.c_int * (4 * len(self.patches)))(*[v for p in self.patches for v in p])
-        self.h = lib().or_amr_create(self.coarse.h, nx0, ny0, dx0, dy0, C.byref(self.coarse._bc), C.byref(self.coarse._ph),
-                                     alpha, beta, self.nlev, flat)
-
-    def patch_shape(self, l, field, ghosted=False):
-        ci0, cj0, ci1, cj1 = self.patches[l - 1]
-        nxp, nyp = 2 * (ci1 - ci0 + 1), 2 * (cj1 - cj0 + 1)
-        if field == F_BX:
-            return (nyp, nxp + 1)
-        if field == F_BY:
-            return (nyp + 1, nxp)
-        return (nyp + 2, nxp + 2) if ghosted else (nyp, nxp)
-
-    def patch_set(self, l, field, arr, ghosted=False):
-        a = np.ascontiguousarray(arr, dtype=np.float64)
-        assert a.shape == self.patch_shape(l, field, ghosted), (a.shape, self.patch_shape(l, field, ghosted))
-        lib().or_amr_patch_io(self.h, l, field, _dp(a), int(ghosted), 1)
-
-    def patch_get(self, l, field, ghosted=False):
-        out = np.zeros(self.patch_shape(l, field, ghosted))
-        lib().or_amr_patch_io(self.h, l, field, _dp(out), int(ghosted), 0)
-        return out
-
-    def set_patch_inputs(self, l, f):
-        self.patch_set(l, F_PHI, f["phi"]); self.patch_set(l, F_RHS, f["rhs"]); self.patch_set(l, F_ACOEF, f["aCoef"])
-        for k, fid in (("B", F_B), ("Pi", F_PI), ("zb", F_ZB), ("mask", F_MASK)):
-            self.patch_set(l, fid, f[k], ghosted=True)
-
-    def residual(self): return lib().or_amr_residual(self.h)
-
-    def vcycle(self, sp):
-        s = make_solver_params(sp)
-        lib().or_amr_vcycle(self.h, C.byref(s))
-
-    def solve(self, sp):
-        s = make_solver_params(sp)
-        hist = np.zeros(s.max_iter + 2)
-        n = lib().or_amr_solve(self.h, C.byref(s), _dp(hist))
-        return n, hist[: n + 1]
-
-    def close(self):
-        if self.h:
-            lib().or_amr_destroy(self.h)
-            self.h = None
-            self.coarse.close()
 
 
 class OracleAmrM:
@@ -671,6 +472,10 @@ class OracleAmrMModel:
         """ghost cells of field fid of every box of level l <- PiecewiseLinearFillPatch from level l-1, then the exchange between the boxes"""
         lib().or_amrm_model_pwl_fill(self.h, l, fid)
 
+    def quadcf_fill(self, l, fid):
+        """coarse-fine ghost cells (sides, no corners) of field fid of every box of level l <- QuadCFInterp from level l-1, then the exchange"""
+        lib().or_amrm_model_quadcf_fill(self.h, l, fid)
+
     def moulin_source(self, positions, sigma, flux, time_factor=1.0):
         pos = np.ascontiguousarray(positions, dtype=np.float64).reshape(-1)
         sg, fl = np.ascontiguousarray(sigma, dtype=np.float64), np.ascontiguousarray(flux, dtype=np.float64)
@@ -690,3 +495,64 @@ class OracleAmrMModel:
             lib().or_amrm_model_destroy(self.h)
             self.h = None
             self.level.close()
+
+
+# ---- hierarchies of nested single patches: views of the box-union classes with one box per level
+def patch_boxes(patches):
+    """patches[k] = (ci0, cj0, ci1, cj1), the patch of level k+1 in the cells of level k -> its box in the cells of level k+1"""
+    return [[(2 * ci0, 2 * cj0, 2 * ci1 + 1, 2 * cj1 + 1)] for (ci0, cj0, ci1, cj1) in patches]
+
+
+class OracleAmr(OracleAmrM):
+    """Base level + nested patches (patches[k] = box of level k+1 in the index space of level k): OracleAmrM with one box per level"""
+
+    def __init__(self, nx0, ny0, dx0, dy0, bc, phys, patches, alpha=0.0, beta=-1.0, max_box=64, nthreads=1):
+        self.patches = [tuple(int(v) for v in p) for p in patches]
+        OracleAmrM.__init__(self, nx0, ny0, dx0, dy0, bc, phys, patch_boxes(self.patches), alpha, beta, max_box, nthreads)
+
+    def patch_shape(self, l, field, ghosted=False): return self.box_shape(l, 0, field, ghosted)
+    def patch_set(self, l, field, arr, ghosted=False): self.box_set(l, 0, field, arr, ghosted)
+    def patch_get(self, l, field, ghosted=False): return self.box_get(l, 0, field, ghosted)
+    def set_patch_inputs(self, l, f): self.set_box_inputs(l, 0, f)
+
+
+class OracleAmr2(OracleAmrM):
+    """Base level + one fine patch (coarse index box ci0..ci1 x cj0..cj1, refined by 2): OracleAmrM with one box on level 1"""
+
+    def __init__(self, nxc, nyc, dxc, dyc, bc, phys, patch, alpha=0.0, beta=-1.0, max_box=64, nthreads=1):
+        self.patch = tuple(int(v) for v in patch)
+        OracleAmrM.__init__(self, nxc, nyc, dxc, dyc, bc, phys, patch_boxes([self.patch]), alpha, beta, max_box, nthreads)
+        self.nyp, self.nxp = self.fine_shape(F_PHI)
+
+    def fine_shape(self, field, ghosted=False): return self.box_shape(1, 0, field, ghosted)
+    def fine_set(self, field, arr, ghosted=False): self.box_set(1, 0, field, arr, ghosted)
+    def fine_get(self, field, ghosted=False): return self.box_get(1, 0, field, ghosted)
+    def set_fine_inputs(self, f): self.set_box_inputs(1, 0, f)
+    def cf_interp(self): self.cf_interp_phi(1)
+    def fine_gsrb(self, sweeps): self.gsrb(1, sweeps)
+    def fine_update_operator(self): self.update_operator(1)
+
+
+class OracleAmrModel:
+    """Hydrology time loop on a base level + nested patches (patches[k] = box of level k+1 in level-k cells): OracleAmrMModel with one
+    box per level, addressed by the level alone"""
+
+    def __init__(self, nx0, ny0, dx0, dy0, bc, phys, model, patches, max_box=64, nthreads=1):
+        self.patches = [tuple(int(v) for v in p) for p in patches]
+        self.m = OracleAmrMModel(nx0, ny0, dx0, dy0, bc, phys, model, patch_boxes(self.patches), max_box, nthreads)
+        self.level, self.nlev = self.m.level, self.m.nlev
+        self.dims = [(hi0 - lo0 + 1, hi1 - lo1 + 1) for ((lo0, lo1, hi0, hi1),) in self.m.boxes]
+
+    def field(self, l, fid): return self.m.field(l, 0, fid)
+    def set_state(self, l, f): self.m.set_state(l, 0, f)
+    def moulin_source(self, positions, sigma, flux, time_factor=1.0): return self.m.moulin_source(positions, sigma, flux, time_factor)
+    def timestep(self, dt): return self.m.timestep(dt)
+    def close(self): self.m.close()
+
+    def fill_ghosts(self, l, fid, kind="pwl"):
+        """coarse-fine ghost cells of field fid of level l from level l-1: PiecewiseLinearFillPatch from the rectangle below with its own
+        ghost ring (or_pwl_fill) or QuadCFInterp"""
+        if kind != "pwl":
+            return self.m.quadcf_fill(l, fid)
+        box = lambda k: lib().or_amrm_model_box(self.m.h, k, 0)
+        lib().or_pwl_fill(box(l), box(l - 1), lib().or_amrm_model_field(self.m.h, l, 0, fid), lib().or_amrm_model_field(self.m.h, l - 1, 0, fid))

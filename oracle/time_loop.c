@@ -1,7 +1,7 @@
 /*
  * time_loop.c -- TEST INFRASTRUCTURE ONLY ("next rows" of SURVEY.md 8f: the caller of the
  * head solve).  CPU restatement of one AmrHydro::timeStepFAS (src/AmrHydro.cpp:2254-3460) for a
- * single AMR level (a hierarchy: amr_step.c strings the phases below together per level): distributed or moulin input,
+ * single AMR level (a hierarchy: amr_step_m.c strings the phases below together per level): distributed or moulin input,
  * with or without the diffusive term, explicit or implicit gap-height update:
  *   [I]   ghosts of h and b, copy into old                         :2360-2445
  *   [II]  Picard loop: lagged quantities -> RHS_h -> SolveForHead_nl -> convergence test
@@ -329,7 +329,7 @@ static double max_valid(OrModel *M, const double *a)
     return m;
 }
 
-/* ---- phases of one step; or_model_timestep strings them together for one level, amr_step.c for a hierarchy ---- */
+/* ---- phases of one step; or_model_timestep strings them together for one level, amr_step_m.c for a hierarchy ---- */
 void or_model_begin_step(OrModel *M)                                         /* [I] :2360-2445 */
 {
     size_t nc = (size_t)(M->nx + 2) * (M->ny + 2);

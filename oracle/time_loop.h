@@ -1,5 +1,5 @@
 /* time_loop.h -- TEST INFRASTRUCTURE ONLY: the model state of oracle/time_loop.c and its phases, shared with the AMR
- * time step (oracle/amr_step.c) */
+ * time step (oracle/amr_step_m.c) */
 #ifndef OR_TIME_LOOP_H
 #define OR_TIME_LOOP_H
 #include "level_shim.h"
@@ -44,7 +44,7 @@ typedef struct OrModel {
     double G_dt; int G_max_box, G_nthreads;
     int cur_step;
     double time;
-    /* AMR patch (amr_step.c): place of this level in its refined domain; cf[dir][side] = that side of the rectangle lies
+    /* AMR box (amr_step_m.c): place of this rectangle in its level's domain; cf[dir][side] = that side of the rectangle lies
      * inside the domain: a coarse-fine side whose ghost cells are data (interpolated by the caller), not BC values */
     int i0, j0, nxg, nyg, cf[2][2];
 } OrModel;

@@ -10,7 +10,7 @@
 //   UpdateOperator / WFlx_level with a coarser level   src/VCAMRNonLinearPoissonOp.cpp:34-64, src/AmrHydro.cpp:1455-1488
 // Restated from upstream Chombo's documented semantics because the fork is not vendored (UNPINNED, SURVEY.md
 // Appendix E): QuadCFInterp, LevelFluxRegister, FORT_AVERAGE, the ghosted coarse copy of AMRProlongS_2 and the AMR
-// FAS cycle order.  The oracle's amr2.c and amrn.c state the same arithmetic; parity is bitwise.
+// FAS cycle order.  The oracle's amrm.c states the same arithmetic; parity is bitwise.
 //
 // A fine level is an ordinary suhmo_level created with desc.i0/nx_global/j0/ny_global: sides of its rectangle
 // inside the domain are coarse-fine sides whose ghost cells are STORED (DV::cfx / DV::ext) and filled here.
@@ -54,7 +54,7 @@ __device__ __forceinline__ double cval(const DV &vc, const double *__restrict__ 
     return c[cidx(vc, I - vc.i0, J - vc.j0)];
 }
 
-// [Chombo] QuadCFInterp::coarseFineInterp, ratio 2 (oracle/amr2.c:cf_interp): tangential quadratic on the coarse
+// [Chombo] QuadCFInterp::coarseFineInterp, ratio 2 (oracle/amrm.c:or_amrm_cf_interp_fabs): tangential quadratic on the coarse
 // level (one-sided next to a non-periodic domain boundary), then a normal quadratic through that value and the two
 // fine cells inside: ghost = 8/15 phistar + 2/3 near - 1/5 far.  One thread per coarse-fine ghost cell.
 __global__ void k_cf_interp(DV vf, double *__restrict__ f, DV vc, const double *__restrict__ c)
@@ -101,7 +101,7 @@ __global__ void k_amr_set_covered(DV vf, DV vc, double *__restrict__ c, double v
     c[cidx(vc, I + vf.i0 / 2 - vc.i0, J + vf.j0 / 2 - vc.j0)] = val;
 }
 
-// [Chombo] LevelFluxRegister (oracle/amr2.c:reflux): on every coarse-fine face the coarse flux is replaced by the
+// [Chombo] LevelFluxRegister (oracle/amrm.c:reflux): on every coarse-fine face the coarse flux is replaced by the
 // average of the two fine fluxes; L(phi) of the coarse cell outside the patch += sign * reg / (dx dy).
 // Fluxes as VCAMRNonLinearPoissonOp::getFlux (:792-841).  One thread per coarse face of the patch boundary.
 // residual != 0: lofphi is the composite residual, already rhs - L(phi) everywhere; the cell gets rhs - (L(phi) + register), what
@@ -162,7 +162,7 @@ __global__ void k_amr_prolong2(DV vf, double *__restrict__ phi, DV vc, const dou
     p = p + fx1 * (c[cc + o1] + c[cc + o2 * vc.P]);
     phi[idx] = p;
 }
-// [Chombo] PiecewiseLinearFillPatch, ratio 2, one ghost layer incl. corners (oracle/amr_step.c:or_pwl_fill): coarse value
+// [Chombo] PiecewiseLinearFillPatch, ratio 2, one ghost layer incl. corners (oracle/amr_step_m.c:or_pwl_fill): coarse value
 // + limited slopes (central, one-sided next to the domain boundary, FORT_INTERPLIMIT over the 3 x 3 neighbourhood) times
 // the offset of the fine cell centre (+-1/4).  One thread per ghost cell of the ring; cells outside the domain stay.
 __global__ void k_pwl_fill(DV vf, double *__restrict__ f, DV vc, const double *__restrict__ c)
@@ -373,7 +373,7 @@ extern "C" int suhmo_amr2_set_covered(suhmo_level_t *C, suhmo_level_t *F, int fi
 }
 
 // ================================================================ N nested levels
-// levels[0] = base level, levels[l] = patch of level l (properly nested in level l-1): oracle/amrn.c states the same
+// levels[0] = base level, levels[l] = patch of level l (properly nested in level l-1): oracle/amrm.c states the same
 // cycle.  The residual, V-cycle and solve of a pair (suhmo_amr2_*) are the nlev = 2 case.
 // Rank strips: a rank holds of every level the rows of its own physical slab, so levels[l] may be NULL on a rank the
 // patch of level l does not reach.  Such a rank still runs the coarse half of every pair it has a coarse strip of (the
@@ -525,7 +525,7 @@ extern "C" int suhmo_amr_solve(suhmo_level_t **lv, int nlev, const suhmo_solver_
     return amr_solve(lv, nlev, sp, iters, hist, s);
 }
 
-// the two-level entry points: any pair check_pair accepts, as the nlev = 2 case (oracle/amr2.c states the same arithmetic as amrn.c)
+// the two-level entry points: any pair check_pair accepts, as the nlev = 2 case (oracle/amrm.c with one box on level 1 states the same arithmetic)
 extern "C" int suhmo_amr2_residual(suhmo_level_t *C, suhmo_level_t *F, double *norm, suhmo_stream_t s)
 {
     int rc = check_pair(C, F); if (rc) return rc;

@@ -86,7 +86,7 @@ __global__ void k_cf_ff_lv(LvGhosts lv, FP cbase, int field)
         if (t < nff) d_ff(fe[t], ftab, field, -1);
     }
 }
-// [Chombo] PiecewiseLinearFillPatch (oracle/amr_step.c:or_pwl_fill)
+// [Chombo] PiecewiseLinearFillPatch (oracle/amr_step_m.c:or_pwl_fill)
 __global__ void k_pwl(const PwlEnt *__restrict__ e, int n, const FP *__restrict__ ftab, int ff, const FP *__restrict__ ctab, FP cbase,
                       int use_base, int fc)
 {

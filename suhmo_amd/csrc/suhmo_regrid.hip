@@ -23,7 +23,7 @@ struct RgInterp { int fb, cb, foff, coff, w, h, I0, J0; };
 struct RgCopy { int db, sb, doff, soff, w, h; };
 
 // [Chombo] FineInterp::interpToFine, ratio 2, m_boundary_limit_type = limitTangentialOnly.  One thread = one coarse cell and its four children.
-// Away from the domain sides this is oracle/amr_step.c:or_pwl_fill / k_pwl statement by statement.
+// Away from the domain sides this is oracle/amr_step_m.c:or_pwl_fill / k_pwl statement by statement.
 __global__ __launch_bounds__(256) void k_regrid_interp(const RgInterp *__restrict__ e, const FP *__restrict__ ftab, const DV *__restrict__ fdv,
                                                        const FP *__restrict__ ctab, const DV *__restrict__ cdv, FP cbase, DV cbdv, int use_base,
                                                        int nxd, int nyd, int perx, int pery, RgFields fl)

@@ -695,7 +695,7 @@ int suhmo_batch_timestep_run(suhmo_batch *B, const suhmo_model_params_t *mp, dou
 
 
 // ------------------------------------------------------------------ the time step on an AMR hierarchy
-// oracle/amr_step.c: every level runs the phases above on its own rectangle; in between PiecewiseLinearFillPatch of the
+// oracle/amr_step_m.c: every level runs the phases above on its own rectangle; in between PiecewiseLinearFillPatch of the
 // coarse-fine ghosts of b, mR, Re (:2373-2380, :2499-2507, :2711-2719), QuadCFInterp of h (inside compGradientMAC) and of
 // the cell-centred gradient (:1650-1656), SolveForHead_nl over all levels, CoarseAverage of h (:3138-3141) and the
 // Picard test over the cells no finer level covers (:3169-3185); the gap height by forward Euler level by level, or by

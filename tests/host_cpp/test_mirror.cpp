@@ -13,33 +13,7 @@
 
 using namespace suhmo_host;
 
-// oracle/amr2.c (test infrastructure; no public header)
-extern "C" {
-typedef struct OrAmr2 OrAmr2;
-OrAmr2 *or_amr2_create(OrLevel *coarse, int nxc, int nyc, double dxc, double dyc, const OrBC *bc, const OrPhys *ph,
-                       double alpha, double beta, int ci0, int cj0, int ci1, int cj1);
-void or_amr2_destroy(OrAmr2 *A);
-void or_amr2_fine_io(OrAmr2 *A, int field, double *g, int ghosted, int set);
-int or_amr2_solve(OrAmr2 *A, const OrSolverParams *sp, double *hist);
-void or_amr2_cf_interp_phi(OrAmr2 *A);
-void or_amr2_fine_gsrb(OrAmr2 *A, int sweeps);
-void or_amr2_fine_update_operator(OrAmr2 *A);
-void or_amr2_fine_apply_op(OrAmr2 *A, int homogeneous);
-double or_amr2_residual(OrAmr2 *A);
-const double *or_amr2_coarse_residual(const OrAmr2 *A);
-}
-
 static int g_fail = 0;
-// oracle/amrm.c (test infrastructure; no public header): hierarchies whose levels are unions of boxes
-struct OrAmrM;
-extern "C" {
-OrAmrM *or_amrm_create(OrLevel *base, int nx0, int ny0, double dx0, double dy0, const OrBC *bc, const OrPhys *ph,
-                       double alpha, double beta, int nlev, const int *nbox, const int *boxes);
-void or_amrm_destroy(OrAmrM *A);
-void or_amrm_box_io(OrAmrM *A, int l, int k, int field, double *g, int ghosted, int set);
-int or_amrm_solve(OrAmrM *A, const OrSolverParams *sp, double *hist);
-}
-
 #define CHECK(cond, msg) do { if (!(cond)) { printf("FAIL: %s\n", msg); g_fail++; } else printf("ok:   %s\n", msg); } while (0)
 
 static double hashv(int k, double a, double b) { return a + (b - a) * (double)(((unsigned)k * 2654435761u) % 1000003u) / 1000003.0; }
@@ -290,14 +264,15 @@ int main()
             }
             return a;
         };
-        OrAmr2 *A = or_amr2_create(O, nx, ny, dxv, dyv, &obc, &oph, 0.0, -1.0, ci0, cj0, ci1, cj1);
-        { auto g = patch(fphi, 0); or_amr2_fine_io(A, OR_F_PHI, g.data(), 0, 1); }
-        { auto g = patch(frhs, 0); or_amr2_fine_io(A, OR_F_RHS, g.data(), 0, 1); }
-        { auto g = patch(faCoef, 0); or_amr2_fine_io(A, OR_F_ACOEF, g.data(), 0, 1); }
-        { auto g = patch(fB, 1); or_amr2_fine_io(A, OR_F_B, g.data(), 1, 1); }
-        { auto g = patch(fPi, 1); or_amr2_fine_io(A, OR_F_PI, g.data(), 1, 1); }
-        { auto g = patch(fzb, 1); or_amr2_fine_io(A, OR_F_ZB, g.data(), 1, 1); }
-        { auto g = patch(fmask, 1); or_amr2_fine_io(A, OR_F_MASK, g.data(), 1, 1); }
+        const int nb1[2] = {0, 1}, box1[4] = {2 * ci0, 2 * cj0, 2 * ci1 + 1, 2 * cj1 + 1};           // oracle/amrm.c with one box on level 1
+        OrAmrM *A = or_amrm_create(O, nx, ny, dxv, dyv, &obc, &oph, 0.0, -1.0, 2, nb1, box1);
+        { auto g = patch(fphi, 0); or_amrm_box_io(A, 1, 0, OR_F_PHI, g.data(), 0, 1); }
+        { auto g = patch(frhs, 0); or_amrm_box_io(A, 1, 0, OR_F_RHS, g.data(), 0, 1); }
+        { auto g = patch(faCoef, 0); or_amrm_box_io(A, 1, 0, OR_F_ACOEF, g.data(), 0, 1); }
+        { auto g = patch(fB, 1); or_amrm_box_io(A, 1, 0, OR_F_B, g.data(), 1, 1); }
+        { auto g = patch(fPi, 1); or_amrm_box_io(A, 1, 0, OR_F_PI, g.data(), 1, 1); }
+        { auto g = patch(fzb, 1); or_amrm_box_io(A, 1, 0, OR_F_ZB, g.data(), 1, 1); }
+        { auto g = patch(fmask, 1); or_amrm_box_io(A, 1, 0, OR_F_MASK, g.data(), 1, 1); }
         fac.defineFineLevel(fdom, fgrids, faCoef, fbCoef, fB, fPi, fzb, fmask);
         VCAMRNonLinearPoissonOpHIP *fop = fac.AMRnewOp(fdom);
         CHECK(fop != op && fop != nullptr, "AMRnewOp(fine domain) returns the fine-level operator");
@@ -315,11 +290,11 @@ int main()
         // coarse-fine ghosts of the head (relaxNF with 0 sweeps), UpdateOperator with the coarser level, then
         // relaxNF: coarse-fine interpolation from the current base-level head + 2 sweeps
         fop->relaxNF(fphi, &phi, frhs, 0, 0, 0);
-        or_amr2_cf_interp_phi(A);
+        or_amrm_cf_interp_phi(A, 1);
         fop->UpdateOperator(fphi, &phi, 0, 0, false);
-        or_amr2_fine_update_operator(A);
+        or_amrm_update_operator(A, 1);
         fop->relaxNF(fphi, &phi, frhs, 2, 0, 0);
-        or_amr2_cf_interp_phi(A); or_amr2_fine_gsrb(A, 2); or_amr2_fine_io(A, OR_F_PHI, fg.data(), 0, 0);
+        or_amrm_cf_interp_phi(A, 1); or_amrm_gsrb(A, 1, 2); or_amrm_box_io(A, 1, 0, OR_F_PHI, fg.data(), 0, 0);
         CHECK(same_patch(fphi, fg), "relaxNF (coarseFineInterp + levelGSRB x2 on the patch) == oracle");
         // the two-level solve
         HeadSolverParameters sp2(100, true); sp2.max_iter = 5;
@@ -328,8 +303,8 @@ int main()
         std::vector<LevelData<FArrayBox> *> vrhs = {&rhs, &frhs};
         std::vector<double> h2, oh2(sp2.max_iter + 2);
         int n2 = fac.solveAMR(vphi, vrhs, sp2, &h2);
-        int on2 = or_amr2_solve(A, &osp2, oh2.data());
-        or_level_get(O, 0, OR_F_PHI, og.data(), 0); or_amr2_fine_io(A, OR_F_PHI, fg.data(), 0, 0);
+        int on2 = or_amrm_solve(A, &osp2, oh2.data());
+        or_level_get(O, 0, OR_F_PHI, og.data(), 0); or_amrm_box_io(A, 1, 0, OR_F_PHI, fg.data(), 0, 0);
         CHECK(n2 == on2 && h2.back() == oh2[on2], "solveAMR: V-cycle count and composite residual == oracle");
         CHECK(same_valid(phi, og, nx), "solveAMR: base-level head == oracle (bitwise)");
         CHECK(same_patch(fphi, fg), "solveAMR: fine-level head == oracle (bitwise)");
@@ -340,12 +315,12 @@ int main()
             LevelData<FArrayBox> fL(fgrids, 1, 0), cL(grids, 1, 0), cR(grids, 1, 0);
             // AMROperatorNF: coarseFineInterp + applyOpI on the patch
             fop->AMROperatorNF(fL, fphi, phi, false);
-            or_amr2_cf_interp_phi(A); or_amr2_fine_apply_op(A, 0); or_amr2_fine_io(A, OR_F_LPHI, fg.data(), 0, 0);
+            or_amrm_cf_interp_phi(A, 1); or_amrm_apply_op(A, 1); or_amrm_box_io(A, 1, 0, OR_F_LPHI, fg.data(), 0, 0);
             CHECK(same_patch(fL, fg), "AMROperatorNF == oracle (coarseFineInterp + applyOpI on the patch)");
             // AMROperatorNC = applyOpI + reflux; rhs - that == the oracle's composite residual outside the patch
             op->AMROperatorNC(cL, fphi, phi, false, fop);
             op->AMRResidualNC(cR, fphi, phi, rhs, false, fop);
-            or_amr2_residual(A); memcpy(og.data(), or_amr2_coarse_residual(A), sizeof(double) * (size_t)nx * ny);
+            or_amrm_residual(A); or_level_get(O, 0, OR_F_RES, og.data(), 0);
             bool okc = true, okr = true, changed = false;
             LevelData<FArrayBox> cPlain(grids, 1, 0);
             op->applyOp(cPlain, phi, false);
@@ -423,7 +398,7 @@ int main()
             CHECK(okb, "finerOperatorChanged(fine operator, 2): coarse x-face bCoef under the patch = mean of the two fine faces");
             CHECK(fac.refToFiner(dom) == 2 && fac.refToFiner(fdom) == 1 && fop->refToCoarser() == 2, "refToFiner / refToCoarser");
         }
-        or_amr2_destroy(A);
+        or_amrm_destroy(A);
     }
 
 

@@ -1,4 +1,4 @@
-"""Two AMR levels on the GPU (suhmo_amd/csrc/suhmo_amr.hip) against the oracle's amr2.c on the same inputs:
+"""Two AMR levels on the GPU (suhmo_amd/csrc/suhmo_amr.hip) against the oracle's amrm.c on the same inputs:
 BITWISE for the coarse-fine interpolation, the fine-level operator update with a coarser level, the composite
 residual (reflux), one AMR FAS V-cycle and the solve history.  Config: cfg3 of BASELINE.json
 (exec/0_convergence_channelized/2lev_base/input.hydro: 64 x 16 base, y periodic, refined box around the moulin)."""
@@ -61,7 +61,7 @@ def test_amr2_pieces_bitwise(oracle, case):
     ro, rg = O.residual(), G.residual()
     eq(O.fine_get(oracle.F_RES), G.fine.get(F_RES), "fine residual")
     co, cg = O.coarse.get(oracle.F_RES), G.coarse.get(F_RES)
-    # oracle/amr2.c keeps the composite coarse residual in its own array: compare through the norm and the cycle below
+    # (the base level's part of the composite residual is not compared: through the norm and the cycle below)
     assert ro == rg, (ro, rg)
     # fine relaxation with stored coarse-fine ghosts
     O.fine_gsrb(2); G.fine.gsrb(2)

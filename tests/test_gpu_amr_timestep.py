@@ -1,5 +1,5 @@
 """The time step on an AMR hierarchy (suhmo_amr_timestep: per-level phases + PiecewiseLinearFillPatch / QuadCFInterp
-ghosts, AMR solve, average down, Picard test over the uncovered cells) against oracle/amr_step.c on the same inputs:
+ghosts, AMR solve, average down, Picard test over the uncovered cells) against oracle/amr_step_m.c on the same inputs:
 BITWISE on every level over several steps; a one-level hierarchy equals suhmo_level_timestep."""
 import numpy as np
 import pytest

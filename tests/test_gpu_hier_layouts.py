@@ -98,7 +98,7 @@ def test_layout_pwl_fill_of_B_bitwise(oracle, case):
     """suhmo_hier_pwl_fill of B, level by level, against the oracle's PiecewiseLinearFillPatch on box unions (oracle/amr_step_m.c:mm_pwl =
     or_pwl_fill per box from the level below): every coarse-fine ghost cell of every box, CORNERS INCLUDED (the fill writes them; ghostring
     leaves them out, so the cells are walked here), inside the domain.  Coarse-fine ghost cells ACROSS a periodic side are counted and not
-    compared: or_pwl_fill leaves cells outside the domain box alone (oracle/amr_step.c:91), the device fills them from the wrapped coarse cell
+    compared: or_pwl_fill leaves cells outside the domain box alone (oracle/amr_step_m.c:96), the device fills them from the wrapped coarse cell
     (suhmo_hier_plan.hip: wrap_cell before the classification) -- the oracle defines nothing there to compare with.  Nothing else of the ring
     may change on the device (fine-fine and domain cells keep the caller's data)."""
     from suhmo_amd.level import F_B

@@ -1,4 +1,4 @@
-"""CPU checks of the two-level AMR restatement (oracle/amr2.c): coarse-fine interpolation is exact for
+"""CPU checks of the AMR restatement (oracle/amrm.c) on nested patches: coarse-fine interpolation is exact for
 quadratics, the composite operator conserves (reflux), and the 2-level FAS solve converges to a solution that is
 closer to the uniformly fine one than the coarse solve is."""
 import numpy as np

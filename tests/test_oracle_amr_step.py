@@ -1,4 +1,4 @@
-"""oracle/amr_step.c (test infrastructure): the AMR time step's own pieces have no reference fixture (Chombo-side,
+"""oracle/amr_step_m.c on nested patches (test infrastructure): the AMR time step's own pieces have no reference fixture (Chombo-side,
 unpinned), so they are held to what they must satisfy: a one-level hierarchy IS the pinned single-level loop, the
 ghost-cell interpolations are exact for the polynomials they are built for and bounded where they limit, moulins deliver
 their flux over the composite grid, and the refined run stays closer to the uniformly fine one than the coarse run."""

@@ -1,7 +1,12 @@
 """oracle/amr_step_m.c (test infrastructure): the time step on hierarchies whose levels are unions of boxes.  With one box
-per level it IS oracle/amr_step.c bit for bit; a level cut into more boxes gives the same bits (fine-fine exchange after
+per level, through the box-union class and through the nested-patch view of it, it gives what the nested-patch step it replaced
+gave, bit for bit (recorded results); a level cut into more boxes gives the same bits (fine-fine exchange after
 every ghost fill); on unions with a re-entrant corner, a disjoint box and a box on the domain side the step runs with
 moulins, diffusion and the implicit gap-height solve and conserves what the single-level loop conserves."""
+import hashlib
+import json
+import os
+
 import numpy as np
 import pytest
 
@@ -25,8 +30,20 @@ def make(boxes, m=None, rough=0.5, nx0=64, ny0=32):
     return A, sts, m
 
 
+def digest(a):
+    """sha256 of the little-endian float64 bytes of a + 0.0 (-0.0 == 0.0, as np.array_equal has it): equal digests <=> equal bits"""
+    a = np.ascontiguousarray(np.asarray(a, dtype="<f8")) + 0.0
+    assert np.all(np.isfinite(a))
+    return dict(shape=list(a.shape), sha256=hashlib.sha256(a.tobytes()).hexdigest(), absmax=float(np.abs(a).max()).hex())
+
+
 @pytest.mark.parametrize("variant", ["explicit", "moulins-diffusion-implicit"])
 def test_one_box_per_level_is_the_nested_patch_step(variant):
+    """against the nested-patch step this file replaced (through OracleAmrModel), recorded once on the commit the fixture names:
+    per step the Picard and V-cycle counts and digest() of the whole ghosted OM_H, OM_B, OM_MR, OM_QWX, OM_RE of every level, the moulin
+    integrals as float.hex().  (Digests, not values: 2 variants x 2 steps x 3 levels x 5 fields are 1.3 MB of doubles.)"""
+    with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "oracle_nested_step_parent.json")) as fh:
+        want = json.load(fh)[variant]
     m = dict(sy.A3_MODEL)
     if variant != "explicit":
         m.update(diffFactor=1.0, use_impl_diff=1, use_moulin_source=1, distributed_input=7.93e-11)
@@ -35,13 +52,16 @@ def test_one_box_per_level_is_the_nested_patch_step(variant):
     for l in range(3):
         B.set_state(l, sts[l][0])
     if variant != "explicit":
-        ia, ib = A.moulin_source(**MOULINS), B.moulin_source(**MOULINS)
-        assert np.array_equal(ia, ib)
+        integ = np.array([float.fromhex(v) for v in want["moulin_integrals"]])
+        assert np.array_equal(A.moulin_source(**MOULINS), integ) and np.array_equal(B.moulin_source(**MOULINS), integ)
     for step in range(2):
-        assert A.timestep(m["dt"]) == B.timestep(m["dt"])
+        w = want["steps"][step]
+        assert A.timestep(m["dt"]) == B.timestep(m["dt"]) == (w["picard"], w["vcycles"])
         for l in range(3):
-            for fid in (po.OM_H, po.OM_B, po.OM_MR, po.OM_QWX, po.OM_RE):
-                assert np.array_equal(A.field(l, 0, fid), B.field(l, fid)), (step, l, fid)
+            for nm in ("OM_H", "OM_B", "OM_MR", "OM_QWX", "OM_RE"):
+                fid = getattr(po, nm)
+                assert digest(A.field(l, 0, fid)) == w["fields"][l][nm], ("box-union class", step, l, nm)
+                assert digest(B.field(l, fid)) == w["fields"][l][nm], ("nested-patch view", step, l, nm)
     A.close(); B.close()
 
 

@@ -1,11 +1,15 @@
-"""CPU checks of the multi-box AMR restatement (oracle/amrm.c): with one box per level it IS oracle/amrn.c bit for bit;
-a level cut into more (abutting) boxes gives the same bits (fine-fine exchange = the neighbour's cell); on unions with
+"""CPU checks of the AMR restatement (oracle/amrm.c): with one box per level, through the box-union class and through the
+nested-patch views of it, it gives what the nested-patch code it replaced gave, bit for bit (recorded results); a level cut into more (abutting) boxes gives the same bits (fine-fine exchange = the neighbour's cell); on unions with
 re-entrant corners, disjoint boxes and boxes on the domain boundary the coarse-fine interpolation is exact for quadratics
 (centred and one-sided second-order stencils), and the 4-level FAS solve converges."""
+import json
+import os
+
 import numpy as np
 import pytest
 
 from suhmo_amd import synthetic as sy
+from tests import ghostring as gr
 
 BC = dict(type=[[0, 0], [1, 0]], value=[[0.0, 0.0], [0.0, 0.0]], periodic=[0, 1])     # 2lev_base/input.hydro:8-13,76
 BC_NP = dict(type=[[0, 1], [1, 0]], value=[[0.0, 0.0], [0.0, 0.0]], periodic=[0, 0])  # run_C_3lev/input.hydro: no periodic side
@@ -29,22 +33,81 @@ def make(oracle, boxes, bc=BC, nx0=64, ny0=16, ph=sy.CFG3_PHYS, **kw):
     return A, fs
 
 
+def recorded():
+    """results of the nested-patch code this file replaced (through OracleAmr and OracleAmr2), recorded once on the
+    commit the fixture names: residual norm, cycle count and history as float.hex(), arrays as {shape, hex (row-major)}; written by
+    json.dump(dict(residual=float(r).hex(), cycles=n, history=[v.hex() for v in hist], phi={l: dict(shape=a.shape, hex=[v.hex() for v in a.flat])}, ...))"""
+    with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "oracle_nested_solve_parent.json")) as fh:
+        return json.load(fh)
+
+
+def unhex(rec):
+    return np.array([float.fromhex(v) for v in rec["hex"]]).reshape(rec["shape"])
+
+
 def test_one_box_per_level_is_the_nested_patch_code(oracle):
     sp = dict(sy.SOLVER_DEFAULT, eps=1e-9, norm_thresh=1e-14, max_iter=4, imin=30)
+    want = recorded()["nested_three_levels"]
     AM, fs = make(oracle, ONE)
     patches = ((8, 4, 23, 11), (22, 11, 37, 20))
     AN = oracle.OracleAmr(64, 16, fs[0]["dx"], fs[0]["dy"], BC, sy.CFG3_PHYS, patches, max_box=32, nthreads=2)
     AN.coarse.set_inputs(fs[0]); AN.coarse.build_mg_coefficients()
     for l in (1, 2):
         AN.set_patch_inputs(l, fs[l][0])
-    assert AM.residual() == AN.residual()
+    assert AM.residual() == AN.residual() == float.fromhex(want["residual"])
     nm, hm = AM.solve(sp)
     nn, hn = AN.solve(sp)
-    assert nm == nn and np.array_equal(hm, hn)
+    hist = np.array([float.fromhex(v) for v in want["history"]])
+    assert nm == nn == want["cycles"] and np.array_equal(hm, hist) and np.array_equal(hn, hist)
     for l in (1, 2):
-        assert np.array_equal(AM.box_get(l, 0, oracle.F_PHI), AN.patch_get(l, oracle.F_PHI))
-        assert np.array_equal(AM.box_get(l, 0, oracle.F_BX), AN.patch_get(l, oracle.F_BX))
-    assert np.array_equal(AM.coarse.get(oracle.F_PHI), AN.coarse.get(oracle.F_PHI))
+        for got in (AM.box_get(l, 0, oracle.F_PHI), AN.patch_get(l, oracle.F_PHI)):
+            assert np.array_equal(got, unhex(want["phi"][str(l)])), l
+        for got in (AM.box_get(l, 0, oracle.F_BX), AN.patch_get(l, oracle.F_BX)):
+            assert np.array_equal(got, unhex(want["bx"][str(l)])), l
+    for A in (AM, AN):
+        assert np.array_equal(A.coarse.get(oracle.F_PHI), unhex(want["base_phi"]))
+    AM.close(); AN.close()
+
+
+def test_one_box_on_one_level_is_the_two_level_code(oracle):
+    """cfg3 as tests/test_oracle_amr.py builds it, through OracleAmr2 and through OracleAmrM"""
+    sp = dict(sy.SOLVER_DEFAULT, eps=1e-9, norm_thresh=1e-14, max_iter=4, imin=30)
+    want = recorded()["two_levels_cfg3"]
+    c, f = sy.amr2_fields(64, 16, sy.CFG3_PATCH)
+    A2 = oracle.OracleAmr2(64, 16, c["dx"], c["dy"], BC, sy.CFG3_PHYS, sy.CFG3_PATCH, max_box=32, nthreads=2)
+    A2.coarse.set_inputs(c); A2.coarse.build_mg_coefficients(); A2.set_fine_inputs(f)
+    AM = oracle.OracleAmrM(64, 16, c["dx"], c["dy"], BC, sy.CFG3_PHYS, oracle.patch_boxes([sy.CFG3_PATCH]), max_box=32, nthreads=2)
+    AM.set_inputs([c, [f]])
+    hist = np.array([float.fromhex(v) for v in want["history"]])
+    for A in (A2, AM):
+        assert A.residual() == float.fromhex(want["residual"])
+        n, h = A.solve(sp)
+        assert n == want["cycles"] and np.array_equal(h, hist)
+        assert np.array_equal(A.box_get(1, 0, oracle.F_PHI), unhex(want["fine_phi"]))
+        assert np.array_equal(A.coarse.get(oracle.F_PHI), unhex(want["base_phi"]))
+    assert np.array_equal(A2.fine_get(oracle.F_PHI), unhex(want["fine_phi"]))
+    A2.close(); AM.close()
+
+
+def test_nested_patch_that_spans_the_periodic_direction(oracle):
+    """a patch that is its own periodic neighbour: through the nested-patch view it is the box-union hierarchy, whose y sides are
+    periodic ghost cells (the exchange's wrapped copies), not coarse-fine ones as the nested-patch code this file replaced had them"""
+    sp = dict(sy.SOLVER_DEFAULT, eps=1e-9, norm_thresh=1e-14, max_iter=4, imin=30)
+    patch, box, dom = (0, 0, 23, 15), (0, 0, 47, 31), (128, 32)
+    fs = sy.amrm_fields(64, 16, ([box],))
+    AM = oracle.OracleAmrM(64, 16, fs[0]["dx"], fs[0]["dy"], BC, sy.CFG3_PHYS, ([box],), max_box=32, nthreads=2)
+    AM.set_inputs(fs)
+    AN = oracle.OracleAmr(64, 16, fs[0]["dx"], fs[0]["dy"], BC, sy.CFG3_PHYS, (patch,), max_box=32, nthreads=2)
+    AN.coarse.set_inputs(fs[0]); AN.coarse.build_mg_coefficients(); AN.set_patch_inputs(1, fs[1][0])
+    assert AN.boxes == AM.boxes
+    AM.vcycle(sp); AN.vcycle(sp)
+    g = AN.patch_get(1, oracle.F_PHI, ghosted=True)
+    assert np.array_equal(g, AM.box_get(1, 0, oracle.F_PHI, ghosted=True))
+    assert np.array_equal(AN.coarse.get(oracle.F_PHI), AM.coarse.get(oracle.F_PHI))
+    kinds = gr.ring_kinds(box, dom, BC["periodic"])
+    assert {k: set(v) for k, v in kinds.items()} == {"x-lo": {"domain"}, "x-hi": {"coarse-fine"}, "y-lo": {"periodic"}, "y-hi": {"periodic"}}
+    assert np.array_equal(g[0, 1:-1], g[-2, 1:-1]) and np.array_equal(g[-1, 1:-1], g[1, 1:-1])       # the wrapped valid rows
+    assert gr.domain_bc_holds(g, BC, fs[1][0]["dx"], fs[1][0]["dy"], box, dom, "x-lo") == 32
     AM.close(); AN.close()
 
 
