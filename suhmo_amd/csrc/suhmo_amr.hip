@@ -15,6 +15,7 @@
 // A fine level is an ordinary suhmo_level created with desc.i0/nx_global/j0/ny_global: sides of its rectangle
 // inside the domain are coarse-fine sides whose ghost cells are STORED (DV::cfx / DV::ext) and filled here.
 #include "suhmo_common.h"
+#include "suhmo_transfer.h"
 
 namespace {
 struct Pair { suhmo_level *C, *F; };
@@ -54,16 +55,13 @@ __device__ __forceinline__ double cval(const DV &vc, const double *__restrict__ 
     return c[cidx(vc, I - vc.i0, J - vc.j0)];
 }
 
-// [Chombo] QuadCFInterp::coarseFineInterp, ratio 2 (oracle/amrm.c:or_amrm_cf_interp_fabs): tangential quadratic on the coarse
-// level (one-sided next to a non-periodic domain boundary), then a normal quadratic through that value and the two
-// fine cells inside: ghost = 8/15 phistar + 2/3 near - 1/5 far.  One thread per coarse-fine ghost cell.
+// QuadCFInterp (suhmo_transfer.h: cf_tangential, cf_ghost; oracle/amrm.c:or_amrm_cf_interp_fabs).  One thread per coarse-fine ghost cell.
 __global__ void k_cf_interp(DV vf, double *__restrict__ f, DV vc, const double *__restrict__ c)
 {
     int t = blockIdx.x * blockDim.x + threadIdx.x;
     int dir, side, tt;
     if (t < 2 * vf.ny) { dir = 0; side = t / vf.ny; tt = t % vf.ny; if (!vf.cfx[side]) return; }
     else { t -= 2 * vf.ny; if (t >= 2 * vf.nx) return; dir = 1; side = t / vf.nx; tt = t % vf.nx; if (!vf.ext[side] || vf.rk[side]) return; }
-    const double c_s = 8.0 / 15.0, c_b = 2.0 / 3.0, c_a = -0.2;
     const int tdir = 1 - dir;
     int gl = dir == 0 ? (side ? vf.nx : -1) : (side ? vf.ny : -1);            // local normal index of the ghost cell
     int inward = side ? -1 : 1;
@@ -73,26 +71,25 @@ __global__ void k_cf_interp(DV vf, double *__restrict__ f, DV vc, const double *
     int per = vc.per[tdir], nct = tdir == 0 ? vc.nxg : vc.nyg;
     bool have_lo = per || ict - 1 >= 0, have_hi = per || ict + 1 <= nct - 1;
 #define CV(o) (dir == 0 ? cval(vc, c, icn, ict + (o)) : cval(vc, c, ict + (o), icn))
-    double c0 = CV(0), d1 = 0.0, d2 = 0.0;
-    if (have_lo && have_hi) { double cm = CV(-1), cp = CV(1); d1 = 0.5 * (cp - cm); d2 = cp - 2.0 * c0 + cm; }
-    else if (have_hi) { double cp = CV(1), cpp = CV(2); d1 = 0.5 * (-3.0 * c0 + 4.0 * cp - cpp); d2 = c0 - 2.0 * cp + cpp; }
-    else if (have_lo) { double cm = CV(-1), cmm = CV(-2); d1 = 0.5 * (3.0 * c0 - 4.0 * cm + cmm); d2 = c0 - 2.0 * cm + cmm; }
+    const double c0 = CV(0);
+    double d1, d2;                                                    // the stencil's cells in cf_tangential's order
+    if (have_lo && have_hi) cf_tangential(CF_CENTRED, CV(-1), c0, CV(1), d1, d2);
+    else if (have_hi) cf_tangential(CF_HI2, c0, CV(1), CV(2), d1, d2);
+    else if (have_lo) cf_tangential(CF_LO2, c0, CV(-1), CV(-2), d1, d2);
+    else cf_tangential(CF_NONE, c0, 0.0, 0.0, d1, d2);
 #undef CV
-    double phistar = c0 + xt * d1 + (0.5 * xt * xt) * d2;
     int ig = dir == 0 ? gl : tt, jg = dir == 0 ? tt : gl;
     int idx = cidx(vf, ig, jg), step = dir == 0 ? inward : inward * vf.P;
-    f[idx] = c_s * phistar + c_b * f[idx + step] + c_a * f[idx + 2 * step];
+    f[idx] = cf_ghost(c0, d1, d2, xt, f[idx + step], f[idx + 2 * step]);
 }
 
-// [Chombo] FORT_AVERAGE: covered coarse cell = (sum of its 4 fine cells, i fastest) * 1/4
+// FORT_AVERAGE (suhmo_transfer.h: avg4)
 __global__ void k_amr_average(DV vf, const double *__restrict__ f, DV vc, double *__restrict__ c)
 {
     int I = blockIdx.x * blockDim.x + threadIdx.x, J = blockIdx.y * blockDim.y + threadIdx.y;
     if (I >= vf.nx / 2 || J >= vf.ny / 2) return;
     int b = cidx(vf, 2 * I, 2 * J);
-    double s = 0.0;
-    s = s + f[b]; s = s + f[b + 1]; s = s + f[b + vf.P]; s = s + f[b + vf.P + 1];
-    c[cidx(vc, I + vf.i0 / 2 - vc.i0, J + vf.j0 / 2 - vc.j0)] = s * 0.25;
+    c[cidx(vc, I + vf.i0 / 2 - vc.i0, J + vf.j0 / 2 - vc.j0)] = avg4(f[b], f[b + 1], f[b + vf.P], f[b + vf.P + 1]);
 }
 __global__ void k_amr_set_covered(DV vf, DV vc, double *__restrict__ c, double val)
 {
@@ -101,11 +98,8 @@ __global__ void k_amr_set_covered(DV vf, DV vc, double *__restrict__ c, double v
     c[cidx(vc, I + vf.i0 / 2 - vc.i0, J + vf.j0 / 2 - vc.j0)] = val;
 }
 
-// [Chombo] LevelFluxRegister (oracle/amrm.c:reflux): on every coarse-fine face the coarse flux is replaced by the
-// average of the two fine fluxes; L(phi) of the coarse cell outside the patch += sign * reg / (dx dy).
-// Fluxes as VCAMRNonLinearPoissonOp::getFlux (:792-841).  One thread per coarse face of the patch boundary.
-// residual != 0: lofphi is the composite residual, already rhs - L(phi) everywhere; the cell gets rhs - (L(phi) + register), what
-// copy -> reflux -> axby(-1, 1) leaves there
+// LevelFluxRegister (suhmo_transfer.h: reflux_*; oracle/amrm.c:reflux).  One thread per coarse face of the patch boundary.
+// residual != 0: lofphi is the composite residual, already rhs - L(phi) everywhere; the cell gets rhs - (L(phi) + register)
 __global__ void k_amr_reflux(DV vf, FP ff, DV vc, FP fc, double *__restrict__ lofphi, int residual = 0)
 {
     int t = blockIdx.x * blockDim.x + threadIdx.x;
@@ -124,28 +118,25 @@ __global__ void k_amr_reflux(DV vf, FP ff, DV vc, FP fc, double *__restrict__ lo
     double phihi, philo, bc_;
     if (dir == 0) { int idx = cidx(vc, F - vc.i0, T - vc.j0); phihi = phic[idx]; philo = phic[idx - 1]; bc_ = fc.f[SUHMO_F_BX][idx]; }
     else { int idx = cidx(vc, T - vc.i0, F - vc.j0); phihi = phic[idx]; philo = phic[idx - vc.P]; bc_ = fc.f[SUHMO_F_BY][idx]; }
-    double Fc = -bc_ * ((phihi - philo) * cs);
-    double reg = -(tsize * Fc);
+    double reg = reflux_coarse(tsize, bc_, phihi, philo, cs);
     for (int k = 0; k < 2; k++) {
         int fi = (dir == 0 ? 2 * F : 2 * T + k) - vf.i0, fj = (dir == 0 ? 2 * T + k : 2 * F) - vf.j0;   // local fine face
         int idx = cidx(vf, fi, fj);
         double ph_hi = phif[idx], ph_lo = dir == 0 ? phif[idx - 1] : phif[idx - vf.P];
         double bf = dir == 0 ? ff.f[SUHMO_F_BX][idx] : ff.f[SUHMO_F_BY][idx];
-        double Ff = -bf * ((ph_hi - ph_lo) * fs);
-        reg = reg + (tsize * Ff) * 0.5;
+        reg = reflux_add_fine(reg, tsize, bf, ph_hi, ph_lo, fs);
     }
     int oidx = dir == 0 ? cidx(vc, outside - vc.i0, T - vc.j0) : cidx(vc, T - vc.i0, outside - vc.j0);
-    if (residual) lofphi[oidx] = -1.0 * (fc.f[SUHMO_F_LPHI][oidx] + sign * rscale * reg) + 1.0 * fc.f[SUHMO_F_RHS][oidx];
-    else lofphi[oidx] = lofphi[oidx] + sign * rscale * reg;
+    if (residual) lofphi[oidx] = reflux_residual(reflux_apply(fc.f[SUHMO_F_LPHI][oidx], sign, rscale, reg), fc.f[SUHMO_F_RHS][oidx]);
+    else lofphi[oidx] = reflux_apply(lofphi[oidx], sign, rscale, reg);
 }
 
-// PROLONG_2_NL (src/AMRNonLinearPoissonOpF.ChF:660-705) from the coarse LEVEL's correction canvas (its ghost ring
-// holds the BC values, AMRProlongS_2 :1160-1166)
+// PROLONG_2_NL (suhmo_transfer.h: prolong2_nl) from the coarse LEVEL's correction canvas (its ghost ring holds the BC values,
+// AMRProlongS_2 :1160-1166)
 __global__ void k_amr_prolong2(DV vf, double *__restrict__ phi, DV vc, const double *__restrict__ c)
 {
     int i = blockIdx.x * blockDim.x + threadIdx.x, j = blockIdx.y * blockDim.y + threadIdx.y;
     if (i >= vf.nx || j >= vf.ny) return;
-    const double den = 1.0 / 16.0, fx1 = 3.0 * den, fx2 = 9.0 * den, f0 = 1.0 * den;
     int gi = i + vf.i0, gj = j + vf.j0;
     int ic = gi / 2, jc = gj / 2, o1 = 2 * (gi % 2) - 1, o2 = 2 * (gj % 2) - 1;
     int idx = cidx(vf, i, j), cc = cidx(vc, ic - vc.i0, jc - vc.j0);
@@ -157,14 +148,10 @@ __global__ void k_amr_prolong2(DV vf, double *__restrict__ phi, DV vc, const dou
         const bool xout = !vc.per[0] && (I < 0 || I >= vc.nxg), yout = !vc.per[1] && (J < 0 || J >= vc.nyg);
         if ((xout && (J < cj0 || J > cj1)) || (yout && (I < ci0 || I > ci1))) cd = 0.0;
     }
-    double p = phi[idx];
-    p = p + fx2 * c[cc] + f0 * cd;
-    p = p + fx1 * (c[cc + o1] + c[cc + o2 * vc.P]);
-    phi[idx] = p;
+    phi[idx] = prolong2_nl(phi[idx], c[cc], c[cc + o1], c[cc + o2 * vc.P], cd);
 }
-// [Chombo] PiecewiseLinearFillPatch, ratio 2, one ghost layer incl. corners (oracle/amr_step_m.c:or_pwl_fill): coarse value
-// + limited slopes (central, one-sided next to the domain boundary, FORT_INTERPLIMIT over the 3 x 3 neighbourhood) times
-// the offset of the fine cell centre (+-1/4).  One thread per ghost cell of the ring; cells outside the domain stay.
+// PiecewiseLinearFillPatch, one ghost layer incl. corners (suhmo_transfer.h: limited_slopes, child_value; oracle/amr_step_m.c:or_pwl_fill).
+// One thread per ghost cell of the ring; cells outside the domain stay.
 __global__ void k_pwl_fill(DV vf, double *__restrict__ f, DV vc, const double *__restrict__ c)
 {
     int t = blockIdx.x * blockDim.x + threadIdx.x;
@@ -175,32 +162,14 @@ __global__ void k_pwl_fill(DV vf, double *__restrict__ f, DV vc, const double *_
     if (gi < 0 || gi >= vf.nxg || gj < 0 || gj >= vf.nyg) return;
     if ((j < 0 && vf.rk[0]) || (j >= vf.ny && vf.rk[1])) return;         // rank boundary: exchanged, not interpolated
     const int I = gi >> 1, J = gj >> 1, cc = cidx(vc, I - vc.i0, J - vc.j0);
-    const double c0 = c[cc];
-    double s0, s1;
-    if (I - 1 >= 0 && I + 1 <= vc.nxg - 1) s0 = 0.5 * (c[cc + 1] - c[cc - 1]);
-    else if (I - 1 < 0) s0 = c[cc + 1] - c0;
-    else s0 = c0 - c[cc - 1];
-    if (J - 1 >= 0 && J + 1 <= vc.nyg - 1) s1 = 0.5 * (c[cc + vc.P] - c[cc - vc.P]);
-    else if (J - 1 < 0) s1 = c[cc + vc.P] - c0;
-    else s1 = c0 - c[cc - vc.P];
-    double smax = c0, smin = c0;
-    for (int jj = -1; jj <= 1; jj++)
-        for (int ii = -1; ii <= 1; ii++) {
-            int In = I + ii, Jn = J + jj;
-            if (In < 0 || In > vc.nxg - 1 || Jn < 0 || Jn > vc.nyg - 1) continue;
-            double v = c[cc + ii + jj * vc.P];
-            smax = fmax(smax, v); smin = fmin(smin, v);
-        }
-    const double deltasum = 0.5 * (fabs(s0) + fabs(s1));
-    if (deltasum > 0.0) {
-        double etamax = (smax - c0) / deltasum, etamin = (c0 - smin) / deltasum;
-        double eta = fmax(fmin(fmin(etamin, etamax), 1.0), 0.0);
-        s0 = eta * s0; s1 = eta * s1;
-    }
-    double v = c0;
-    v = v + s0 * ((gi & 1) ? 0.25 : -0.25);
-    v = v + s1 * ((gj & 1) ? 0.25 : -0.25);
-    f[cidx(vf, i, j)] = v;
+    const bool ex[3] = {I - 1 >= 0, true, I + 1 <= vc.nxg - 1}, ey[3] = {J - 1 >= 0, true, J + 1 <= vc.nyg - 1};   // no periodic images
+    double nb[3][3], s0, s1;
+#pragma unroll
+    for (int jj = 0; jj < 3; jj++)
+#pragma unroll
+        for (int ii = 0; ii < 3; ii++) nb[jj][ii] = (ex[ii] && ey[jj]) ? c[cc + (ii - 1) + (jj - 1) * vc.P] : 0.0;
+    limited_slopes(nb, ex[0], ex[2], ey[0], ey[2], false, s0, s1);
+    f[cidx(vf, i, j)] = child_value(nb[1][1], s0, s1, (gi & 1) ? 0.25 : -0.25, (gj & 1) ? 0.25 : -0.25);
 }
 // PROLONGNL with the AMR refinement ratio (AMRProlong / AMRProlongS, src/AMRNonLinearPoissonOp.cpp:1073-1140)
 __global__ void k_amr_prolong_pc(DV vf, double *__restrict__ phi, DV vc, const double *__restrict__ c)
@@ -210,8 +179,7 @@ __global__ void k_amr_prolong_pc(DV vf, double *__restrict__ phi, DV vc, const d
     int idx = cidx(vf, i, j);
     phi[idx] = phi[idx] + c[cidx(vc, (i + vf.i0) / 2 - vc.i0, (j + vf.j0) / 2 - vc.j0)];
 }
-// [Chombo] CoarseAverageFace with the AMR ratio: coarse face under the patch = (sum of its 2 fine faces) / 2
-// (VCAMRNonLinearPoissonOp::finerOperatorChanged :1356-1439; same summation as AverageOperator's k_average_faces)
+// CoarseAverageFace with the AMR ratio (suhmo_transfer.h: avg2): the coarse faces under the patch
 __global__ void k_amr_average_faces(DV vf, const double *__restrict__ bxf, const double *__restrict__ byf, DV vc,
                                     double *__restrict__ bxc, double *__restrict__ byc)
 {
@@ -219,8 +187,8 @@ __global__ void k_amr_average_faces(DV vf, const double *__restrict__ bxf, const
     const int ncx = vf.nx / 2, ncy = vf.ny / 2;
     if (I > ncx || J > ncy) return;
     const int co = cidx(vc, I + vf.i0 / 2 - vc.i0, J + vf.j0 / 2 - vc.j0), fo = cidx(vf, 2 * I, 2 * J);
-    if (J < ncy) { double sm = 0.0; sm = sm + bxf[fo]; sm = sm + bxf[fo + vf.P]; bxc[co] = sm / 2.0; }
-    if (I < ncx) { double sm = 0.0; sm = sm + byf[fo]; sm = sm + byf[fo + 1]; byc[co] = sm / 2.0; }
+    if (J < ncy) bxc[co] = avg2(bxf[fo], bxf[fo + vf.P]);
+    if (I < ncx) byc[co] = avg2(byf[fo], byf[fo + 1]);
 }
 }  // namespace
 

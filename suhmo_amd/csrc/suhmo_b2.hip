@@ -11,6 +11,7 @@
 #include <cmath>
 #include <vector>
 #include "../../include/suhmo_chf.h"
+#include "suhmo_transfer.h"
 
 namespace {
 
@@ -146,17 +147,12 @@ __global__ void kb_prolong(DF phi, DF c, BX r, int m)
     CELL(r);
     for (int n = 0; n < phi.nc; n++) A(phi, i, j, n) = A(phi, i, j, n) + A(c, i / m, j / m, n);
 }
-__global__ void kb_prolong2(DF phi, DF c, BX r, int m)
+__global__ void kb_prolong2(DF phi, DF c, BX r, int m)      // suhmo_transfer.h: prolong2_nl
 {
     CELL(r);
-    const double den = 1.0 / 16.0, fx1 = 3.0 * den, fx2 = 9.0 * den, f0 = 1.0 * den;
     int ic = i / m, jc = j / m, o1 = 2 * (i % 2) - 1, o2 = 2 * (j % 2) - 1;
-    for (int n = 0; n < phi.nc; n++) {
-        double p = A(phi, i, j, n);
-        p = p + fx2 * A(c, ic, jc, n) + f0 * A(c, ic + o1, jc + o2, n);
-        p = p + fx1 * (A(c, ic + o1, jc, n) + A(c, ic, jc + o2, n));
-        A(phi, i, j, n) = p;
-    }
+    for (int n = 0; n < phi.nc; n++)
+        A(phi, i, j, n) = prolong2_nl(A(phi, i, j, n), A(c, ic, jc, n), A(c, ic + o1, jc, n), A(c, ic, jc + o2, n), A(c, ic + o1, jc + o2, n));
 }
 __global__ void kb_getflux(DF flux, DF phi, BX r, double beta_dx, int idir)
 {

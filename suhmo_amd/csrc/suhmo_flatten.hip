@@ -12,6 +12,7 @@
 //   (iv)  one hipMemcpyAsync into host_dst, one synchronisation
 #include "suhmo_hier_int.h"
 #include "suhmo_level_int.h"
+#include "suhmo_transfer.h"
 #include <climits>
 
 using namespace hier;
@@ -42,8 +43,8 @@ template <class T> __global__ void k_flat_eval(T t, FlatComps c, FP sbase, const
     }
 }
 
-// (iii) [Chombo] FineInterp::interpToFine with the whole ratio r = 2^sh in one shot, m_boundary_limit_type = limitTangentialOnly: rule (a) of the
-// regrid (k_regrid_interp) statement by statement, with the child offsets -0.5 + (p + 0.5) / r.  OUTPUT-centric: a thread owns two neighbouring
+// (iii) FineInterp::interpToFine with the whole ratio r = 2^sh in one shot: rule (a) of the regrid (suhmo_transfer.h: limited_slopes with
+// tangential_only, child_value), with the child offsets -0.5 + (p + 0.5) / r.  OUTPUT-centric: a thread owns two neighbouring
 // cells of a finest row (they share their coarse cell, r being even) and stores them as one double2, consecutive lanes consecutive addresses; it
 // recomputes the slopes and eta from the 3 x 3 coarse block, which r / 2 lanes of the row and r rows share through the caches.  COPY: r = 1, one
 // cell per thread.  Rows beyond the grid are taken in further passes (gridDim.y is capped).
@@ -86,31 +87,14 @@ template <bool COPY> __global__ __launch_bounds__(256) void k_flat_interp(const 
         const double dy = -0.5 + ((double)q + 0.5) / rr;
         for (int t = 0; t < ncomp; t++) {
             const double *__restrict__ C = sp.f[t];
-            const double c0 = C[c];
-            double s0 = 0.0, s1 = 0.0;
-            if (xl && xh) s0 = 0.5 * (C[c + ox[2]] - C[c + ox[0]]); else if (xh) s0 = C[c + ox[2]] - c0; else if (xl) s0 = c0 - C[c + ox[0]];
-            if (yl && yh) s1 = 0.5 * (C[c + oy[2]] - C[c + oy[0]]); else if (yh) s1 = C[c + oy[2]] - c0; else if (yl) s1 = c0 - C[c + oy[0]];
-            double smax = c0, smin = c0;
+            double nb[3][3], s0, s1;
 #pragma unroll
             for (int b = 0; b < 3; b++)
 #pragma unroll
-                for (int a = 0; a < 3; a++) {
-                    if (!(ex[a] && ey[b])) continue;
-                    const double w = C[c + oy[b] + ox[a]];
-                    smax = fmax(smax, w); smin = fmin(smin, w);
-                }
-            const double deltasum = 0.5 * (fabs(s0) + fabs(s1));
-            if (deltasum > 0.0) {
-                const double etamax = (smax - c0) / deltasum, etamin = (c0 - smin) / deltasum;
-                const double eta = fmax(fmin(fmin(etamin, etamax), 1.0), 0.0);
-                if (xl && xh) s0 = eta * s0;                   // a one-sided slope normal to a domain side stays as computed
-                if (yl && yh) s1 = eta * s1;
-            }
-            double v0 = c0, v1 = c0;
-            v0 = v0 + s0 * dx0; v1 = v1 + s0 * dx1;
-            v0 = v0 + s1 * dy; v1 = v1 + s1 * dy;
+                for (int a = 0; a < 3; a++) nb[b][a] = (ex[a] && ey[b]) ? C[c + oy[b] + ox[a]] : 0.0;
+            limited_slopes(nb, xl, xh, yl, yh, true, s0, s1);
             // (the finest column of an even fi is even and so are nxF and the plane: 16-byte aligned)
-            *reinterpret_cast<double2 *>(out + t * plane + o) = make_double2(v0, v1);
+            *reinterpret_cast<double2 *>(out + t * plane + o) = make_double2(child_value(nb[1][1], s0, s1, dx0, dy), child_value(nb[1][1], s0, s1, dx1, dy));
         }
     }
 }

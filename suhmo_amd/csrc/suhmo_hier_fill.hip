@@ -1,6 +1,7 @@
 // suhmo_hier_fill.hip -- the plans of a hierarchy of box unions executed (suhmo_hier_int.h): their kernels and launchers, the device tables,
 // the shadow of a level 0 cut into rank strips, the exchange of packed cells between the owners of a partitioned level's boxes
 #include "suhmo_hier_int.h"
+#include "suhmo_transfer.h"
 
 using namespace hier;
 namespace {
@@ -20,26 +21,21 @@ __global__ void k_ff(const CopyEnt *__restrict__ e, int n, const FP *__restrict_
     if (t >= n) return;
     d_ff(e[t], tab, f0, f1);
 }
-// [Chombo] QuadCFInterp (oracle/amrm.c:cf_interp)
+// QuadCFInterp (suhmo_transfer.h: cf_tangential, cf_ghost): q.kind is cf_tangential's, q.c[] its stencil cells in its order
 __device__ __forceinline__ void d_cf(const CfEnt &q, const FP *__restrict__ ftab, int ff0, const FP *__restrict__ ctab, const FP &cbase,
                                      int use_base, int fc0, int ff1, int fc1)
 {
-    const double c_s = 8.0 / 15.0, c_b = 2.0 / 3.0, c_a = -0.2;
     const double xt = q.xsign ? 0.25 : -0.25;
+    const bool two = q.kind != CF_NONE, three = q.kind == CF_CENTRED || q.kind == CF_HI2 || q.kind == CF_LO2;   // cells the stencil has
   for (int pass = 0; pass < (ff1 >= 0 ? 2 : 1); pass++) {          // one or two fields over the same stencils (the two gradient components)
     const int ff = pass ? ff1 : ff0, fc = pass ? fc1 : fc0;
 #define CVAL(m) fptr(ctab, cbase, use_base, q.c[m].b, fc)[q.c[m].off]
-    double c0, d1 = 0.0, d2 = 0.0;
-    if (q.kind == 0) { double cm = CVAL(0), cp = CVAL(2); c0 = CVAL(1); d1 = 0.5 * (cp - cm); d2 = cp - 2.0 * c0 + cm; }
-    else if (q.kind == 1) { c0 = CVAL(0); double cp = CVAL(1), cpp = CVAL(2); d1 = 0.5 * (-3.0 * c0 + 4.0 * cp - cpp); d2 = c0 - 2.0 * cp + cpp; }
-    else if (q.kind == 2) { c0 = CVAL(0); double cp = CVAL(1); d1 = cp - c0; }
-    else if (q.kind == 3) { c0 = CVAL(0); double cm = CVAL(1), cmm = CVAL(2); d1 = 0.5 * (3.0 * c0 - 4.0 * cm + cmm); d2 = c0 - 2.0 * cm + cmm; }
-    else if (q.kind == 4) { c0 = CVAL(0); double cm = CVAL(1); d1 = c0 - cm; }
-    else c0 = CVAL(0);
+    const double a = CVAL(0), b = two ? CVAL(1) : 0.0, c = three ? CVAL(2) : 0.0;
 #undef CVAL
-    double phistar = c0 + xt * d1 + (0.5 * xt * xt) * d2;
+    double d1, d2;
+    const double c0 = cf_tangential(q.kind, a, b, c, d1, d2);
     double *f = ftab[q.f.b].f[ff];
-    f[q.f.off] = c_s * phistar + c_b * f[q.f.off + q.step] + c_a * f[q.f.off + 2 * q.step];
+    f[q.f.off] = cf_ghost(c0, d1, d2, xt, f[q.f.off + q.step], f[q.f.off + 2 * q.step]);
   }
 }
 __global__ void k_cf(const CfEnt *__restrict__ e, int n, const FP *__restrict__ ftab, int ff0, const FP *__restrict__ ctab, FP cbase,
@@ -86,7 +82,8 @@ __global__ void k_cf_ff_lv(LvGhosts lv, FP cbase, int field)
         if (t < nff) d_ff(fe[t], ftab, field, -1);
     }
 }
-// [Chombo] PiecewiseLinearFillPatch (oracle/amr_step_m.c:or_pwl_fill)
+// PiecewiseLinearFillPatch (suhmo_transfer.h: limited_slopes, child_value).  A neighbour the plan marks b < 0 lies outside the domain; q.sx / q.sy
+// say the same of the middle row and column (0: both neighbours, 1: none below, 2: none above)
 __global__ void k_pwl(const PwlEnt *__restrict__ e, int n, const FP *__restrict__ ftab, int ff, const FP *__restrict__ ctab, FP cbase,
                       int use_base, int fc)
 {
@@ -94,29 +91,14 @@ __global__ void k_pwl(const PwlEnt *__restrict__ e, int n, const FP *__restrict_
     if (t >= n) return;
     PwlEnt q = e[t];
 #define CVAL(m) fptr(ctab, cbase, use_base, q.c[m].b, fc)[q.c[m].off]
-    const double c0 = CVAL(4);
-    double s0, s1;
-    if (q.sx == 0) s0 = 0.5 * (CVAL(5) - CVAL(3)); else if (q.sx == 1) s0 = CVAL(5) - c0; else s0 = c0 - CVAL(3);
-    if (q.sy == 0) s1 = 0.5 * (CVAL(7) - CVAL(1)); else if (q.sy == 1) s1 = CVAL(7) - c0; else s1 = c0 - CVAL(1);
-    double smax = c0, smin = c0;
-    for (int m = 0; m < 9; m++) {
-        if (q.c[m].b < 0) continue;
-        double v = CVAL(m);
-        smax = fmax(smax, v); smin = fmin(smin, v);
-    }
+    double nb[3][3], s0, s1;
+#pragma unroll
+    for (int m = 0; m < 9; m++) nb[m / 3][m % 3] = q.c[m].b < 0 ? 0.0 : CVAL(m);
 #undef CVAL
-    const double deltasum = 0.5 * (fabs(s0) + fabs(s1));
-    if (deltasum > 0.0) {
-        double etamax = (smax - c0) / deltasum, etamin = (c0 - smin) / deltasum;
-        double eta = fmax(fmin(fmin(etamin, etamax), 1.0), 0.0);
-        s0 = eta * s0; s1 = eta * s1;
-    }
-    double v = c0;
-    v = v + s0 * ((q.par & 1) ? 0.25 : -0.25);
-    v = v + s1 * ((q.par & 2) ? 0.25 : -0.25);
-    ftab[q.f.b].f[ff][q.f.off] = v;
+    limited_slopes(nb, q.sx != 1, q.sx != 2, q.sy != 1, q.sy != 2, false, s0, s1);
+    ftab[q.f.b].f[ff][q.f.off] = child_value(nb[1][1], s0, s1, (q.par & 1) ? 0.25 : -0.25, (q.par & 2) ? 0.25 : -0.25);
 }
-// [Chombo] FORT_AVERAGE (mode 0) / covered cells <- val (mode 1)
+// FORT_AVERAGE (mode 0; suhmo_transfer.h: avg4) / covered cells <- val (mode 1)
 __device__ __forceinline__ void d_avg(const RectEnt &q, int I, int J, const FP *__restrict__ ftab, const DV *__restrict__ fdv, int ff,
                                       const FP *__restrict__ ctab, const DV *__restrict__ cdv, const FP &cbase, const DV &cbdv, int use_base, int fc, int mode, double val)
 {
@@ -127,9 +109,7 @@ __device__ __forceinline__ void d_avg(const RectEnt &q, int I, int J, const FP *
     const int Pf = fdv[q.fb].P;
     const double *f = ftab[q.fb].f[ff];
     int b = q.foff + 2 * J * Pf + 2 * I;
-    double s = 0.0;
-    s = s + f[b]; s = s + f[b + 1]; s = s + f[b + Pf]; s = s + f[b + Pf + 1];
-    c[q.coff + J * Pc + I] = s * 0.25;
+    c[q.coff + J * Pc + I] = avg4(f[b], f[b + 1], f[b + Pf], f[b + Pf + 1]);
 }
 __global__ void k_avg(const RectEnt *__restrict__ e, const FP *__restrict__ ftab, const DV *__restrict__ fdv, int ff,
                       const FP *__restrict__ ctab, const DV *__restrict__ cdv, FP cbase, DV cbdv, int use_base, int fc, int mode, double val)
@@ -145,9 +125,7 @@ __global__ void k_avg_put(const RectEnt *__restrict__ e, const FP *__restrict__ 
     const int Pf = fdv[q.fb].P;
     const double *f = ftab[q.fb].f[ff];
     int b = q.foff + 2 * J * Pf + 2 * I;
-    double s = 0.0;
-    s = s + f[b]; s = s + f[b + 1]; s = s + f[b + Pf]; s = s + f[b + Pf + 1];
-    buf[q.coff + (long)J * q.w + I] = s * 0.25;
+    buf[q.coff + (long)J * q.w + I] = avg4(f[b], f[b + 1], f[b + Pf], f[b + Pf + 1]);
 }
 // ... and the holder of the coarse cells takes its rectangles out of the writers' segments
 __global__ void k_put_unpack(const PutEnt *__restrict__ e, const FP *__restrict__ ctab, const DV *__restrict__ cdv, FP cbase, DV cbdv, int use_base, int fc,
@@ -176,7 +154,7 @@ __global__ void k_win_gather(const WinEnt *__restrict__ e, double *__restrict__ 
     const double cv = c[q.coff + J * Pc + I];
     wbuf[o] = old ? 1.0 * cv + -1.0 * old[o] : cv;
 }
-// physical BC of the coarse level on the window of every fine box (m_bc on a_temp, AMRProlongS_2 :1160-1166), along the
+// physical BC of the coarse level on the window of every fine box (suhmo_transfer.h: bc_ghost), along the
 // coarsened box's own extent only: the corner cells beyond it are never written (value 0)
 __global__ void k_win_bc(const Win *__restrict__ wins, int nwin, double *__restrict__ wbuf, DV cv /* a view of level l-1: BC data, domain size */)
 {
@@ -195,12 +173,9 @@ __global__ void k_win_bc(const Win *__restrict__ wins, int nwin, double *__restr
     if (g >= 0 && g <= ndom - 1) return;
     const int il = dir == 0 ? (side ? w.nx - 1 : 0) : tt + 1, jl = dir == 0 ? tt + 1 : (side ? w.ny - 1 : 0);
     const int in_ = dir == 0 ? (side ? w.nx - 2 : 1) : il, jn_ = dir == 0 ? jl : (side ? w.ny - 2 : 1);
-    const double nearv = p[(size_t)jn_ * w.nx + in_];
-    double gv;
-    if (cv.bct[dir][side] == 0) gv = cv.two_v[dir][side] - nearv; else gv = nearv + cv.neu[dir][side];
-    p[(size_t)jl * w.nx + il] = gv;
+    p[(size_t)jl * w.nx + il] = bc_ghost(cv.bct[dir][side], cv.two_v[dir][side], cv.neu[dir][side], p[(size_t)jn_ * w.nx + in_]);
 }
-// PROLONG_2_NL (src/AMRNonLinearPoissonOpF.ChF:660-705) of every box of a level from its window
+// PROLONG_2_NL (suhmo_transfer.h: prolong2_nl) of every box of a level from its window
 __global__ void k_prolong2_win(const Win *__restrict__ wins, const double *__restrict__ wbuf, const FP *__restrict__ ftab, const DV *__restrict__ fdv)
 {
     const int k = blockIdx.z;
@@ -209,16 +184,12 @@ __global__ void k_prolong2_win(const Win *__restrict__ wins, const double *__res
     if (i >= v.nx || j >= v.ny) return;
     const Win w = wins[k];
     const double *c = wbuf + w.base;
-    const double den = 1.0 / 16.0, fx1 = 3.0 * den, fx2 = 9.0 * den, f0 = 1.0 * den;
     int gi = i + v.i0, gj = j + v.j0;
     int ic = gi / 2, jc = gj / 2, o1 = 2 * (gi % 2) - 1, o2 = 2 * (gj % 2) - 1;
     int cc = (jc - w.j0) * w.nx + (ic - w.i0);
     double *phi = ftab[k].f[SUHMO_F_PHI];
     int idx = cidx(v, i, j);
-    double p = phi[idx];
-    p = p + fx2 * c[cc] + f0 * c[cc + o1 + o2 * w.nx];
-    p = p + fx1 * (c[cc + o1] + c[cc + o2 * w.nx]);
-    phi[idx] = p;
+    phi[idx] = prolong2_nl(phi[idx], c[cc], c[cc + o1], c[cc + o2 * w.nx], c[cc + o1 + o2 * w.nx]);
 }
 // AMRProlongS_2 of one box per workgroup: the three steps above (gather of the coarse correction into the box's window, physical BC on the
 // window, PROLONG_2_NL) with the window in LDS instead of three launches over a buffer in HBM; the same expressions on the same operands.
@@ -274,16 +245,12 @@ __global__ __launch_bounds__(256) void k_prolong2_fused(const WinEnt *__restrict
             if (g >= 0 && g <= ndom - 1) continue;
             const int il = dir == 0 ? (side ? w.nx - 1 : 0) : tt + 1, jl = dir == 0 ? tt + 1 : (side ? w.ny - 1 : 0);
             const int in_ = dir == 0 ? (side ? w.nx - 2 : 1) : il, jn_ = dir == 0 ? jl : (side ? w.ny - 2 : 1);
-            const double nearv = win[jn_ * w.nx + in_];
-            double gv;
-            if (cbdv.bct[dir][side] == 0) gv = cbdv.two_v[dir][side] - nearv; else gv = nearv + cbdv.neu[dir][side];
-            win[jl * w.nx + il] = gv;
+            win[jl * w.nx + il] = bc_ghost(cbdv.bct[dir][side], cbdv.two_v[dir][side], cbdv.neu[dir][side], win[jn_ * w.nx + in_]);
         }
     }
     __syncthreads();
     {   // k_prolong2_win
         const DV v = fdv[k];
-        const double den = 1.0 / 16.0, fx1 = 3.0 * den, fx2 = 9.0 * den, f0 = 1.0 * den;
         double *phi = ftab[k].f[SUHMO_F_PHI];
         for (int t = tid; t < v.nx * v.ny; t += 256) {
             const int j = t / v.nx, i = t - j * v.nx;
@@ -291,14 +258,11 @@ __global__ __launch_bounds__(256) void k_prolong2_fused(const WinEnt *__restrict
             const int ic = gi / 2, jc = gj / 2, o1 = 2 * (gi % 2) - 1, o2 = 2 * (gj % 2) - 1;
             const int cc = (jc - w.j0) * w.nx + (ic - w.i0);
             const int idx = cidx(v, i, j);
-            double p = phi[idx];
-            p = p + fx2 * win[cc] + f0 * win[cc + o1 + o2 * w.nx];
-            p = p + fx1 * (win[cc + o1] + win[cc + o2 * w.nx]);
-            phi[idx] = p;
+            phi[idx] = prolong2_nl(phi[idx], win[cc], win[cc + o1], win[cc + o2 * w.nx], win[cc + o1 + o2 * w.nx]);
         }
     }
 }
-// [Chombo] LevelFluxRegister (oracle/amrm.c:reflux): one thread per coarse cell next to coarse-fine faces
+// LevelFluxRegister (suhmo_transfer.h: reflux_*): one thread per coarse cell next to coarse-fine faces
 __device__ __forceinline__ void d_reflux(const Target &T, const Face *__restrict__ faces, const FP *__restrict__ ftab, const DV *__restrict__ fdv,
                                          const FP *__restrict__ ctab, const FP &cbase, const FP &cdst, int use_base, int field_c, double dxc, double dyc, double beta, int residual)
 {
@@ -314,19 +278,17 @@ __device__ __forceinline__ void d_reflux(const Target &T, const Face *__restrict
         const double sign = f.side == 0 ? 1.0 : -1.0;
         double phihi = fptr(ctab, cbase, use_base, f.hi.b, SUHMO_F_PHI)[f.hi.off], philo = fptr(ctab, cbase, use_base, f.lo.b, SUHMO_F_PHI)[f.lo.off];
         double bc_ = fptr(ctab, cbase, use_base, f.bq.b, f.dir == 0 ? SUHMO_F_BX : SUHMO_F_BY)[f.bq.off];
-        double Fc = -bc_ * ((phihi - philo) * cs);
-        double reg = -(tsize * Fc);
+        double reg = reflux_coarse(tsize, bc_, phihi, philo, cs);
         const double *phif = ftab[f.fb].f[SUHMO_F_PHI], *bf = ftab[f.fb].f[f.dir == 0 ? SUHMO_F_BX : SUHMO_F_BY];
         const int Pf = fdv[f.fb].P;
         for (int k = 0; k < 2; k++) {
             int idx = f.foff + (f.dir == 0 ? k * Pf : k);
             double ph_hi = phif[idx], ph_lo = f.dir == 0 ? phif[idx - 1] : phif[idx - Pf];
-            double Ff = -bf[idx] * ((ph_hi - ph_lo) * fs);
-            reg = reg + (tsize * Ff) * 0.5;
+            reg = reflux_add_fine(reg, tsize, bf[idx], ph_hi, ph_lo, fs);
         }
-        acc = acc + sign * rscale * reg;
+        acc = reflux_apply(acc, sign, rscale, reg);
     }
-    lof[T.t.off] = residual ? -1.0 * acc + 1.0 * fptr(ctab, cdst, use_base, T.t.b, SUHMO_F_RHS)[T.t.off] : acc;
+    lof[T.t.off] = residual ? reflux_residual(acc, fptr(ctab, cdst, use_base, T.t.b, SUHMO_F_RHS)[T.t.off]) : acc;
 }
 __global__ void k_reflux(const Target *__restrict__ tg, int n, const Face *__restrict__ faces, const FP *__restrict__ ftab, const DV *__restrict__ fdv,
                          const FP *__restrict__ ctab, FP cbase, FP cdst, int use_base, int field_c, double dxc, double dyc, double beta, int residual)

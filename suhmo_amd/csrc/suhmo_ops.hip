@@ -3,6 +3,7 @@
 #include "suhmo_hier.h"
 #include "suhmo_level_int.h"
 #include "suhmo_batch.h"
+#include "suhmo_transfer.h"
 #include <algorithm>
 #include <cmath>
 #include <initializer_list>
@@ -485,18 +486,14 @@ int suhmo_prolong_with_halo(suhmo_level *L, int depth, hipStream_t st)
     return 0;
 }
 
-// PROLONG_2_NL (src/AMRNonLinearPoissonOpF.ChF:660-705), coarse data read with its stored ghosts
+// PROLONG_2_NL (suhmo_transfer.h: prolong2_nl), coarse data read with its stored ghosts
 __global__ void k_prolong2(DV v, double *__restrict__ phi, DV vc, const double *__restrict__ c)
 {
     int i = blockIdx.x * blockDim.x + threadIdx.x, j = blockIdx.y * blockDim.y + threadIdx.y;
     if (i >= v.nx || j >= v.ny) return;
-    const double den = 1.0 / 16.0, fx1 = 3.0 * den, fx2 = 9.0 * den, f0 = 1.0 * den;
     int ic = i / 2, jc = j / 2, o1 = 2 * (i % 2) - 1, o2 = 2 * (j % 2) - 1;
     int idx = cidx(v, i, j), cc = cidx(vc, ic, jc);
-    double p = phi[idx];
-    p = p + fx2 * c[cc] + f0 * c[cc + o1 + o2 * vc.P];
-    p = p + fx1 * (c[cc + o1] + c[cc + o2 * vc.P]);
-    phi[idx] = p;
+    phi[idx] = prolong2_nl(phi[idx], c[cc], c[cc + o1], c[cc + o2 * vc.P], c[cc + o1 + o2 * vc.P]);
 }
 extern "C" int suhmo_level_prolong_bilinear(suhmo_level_t *L, int depth, suhmo_stream_t s)
 {

@@ -12,6 +12,7 @@
 // once and freed.  A coarse neighbour that sits in another box of level l-1 or across a periodic side is read from the coarse box's own ghost
 // ring, which step (d) of level l-1 has just made current with corners; level 0 is one canvas, where the wrapped neighbour is addressed directly.
 #include "suhmo_hier_int.h"
+#include "suhmo_transfer.h"
 
 using namespace hier;
 namespace {
@@ -22,8 +23,8 @@ struct RgInterp { int fb, cb, foff, coff, w, h, I0, J0; };
 // w x h fine cells of old box sb at soff -> new box db at doff
 struct RgCopy { int db, sb, doff, soff, w, h; };
 
-// [Chombo] FineInterp::interpToFine, ratio 2, m_boundary_limit_type = limitTangentialOnly.  One thread = one coarse cell and its four children.
-// Away from the domain sides this is oracle/amr_step_m.c:or_pwl_fill / k_pwl statement by statement.
+// FineInterp::interpToFine, ratio 2 (suhmo_transfer.h: limited_slopes with tangential_only, child_value).  One thread = one coarse cell and its
+// four children.
 __global__ __launch_bounds__(256) void k_regrid_interp(const RgInterp *__restrict__ e, const FP *__restrict__ ftab, const DV *__restrict__ fdv,
                                                        const FP *__restrict__ ctab, const DV *__restrict__ cdv, FP cbase, DV cbdv, int use_base,
                                                        int nxd, int nyd, int perx, int pery, RgFields fl)
@@ -48,32 +49,17 @@ __global__ __launch_bounds__(256) void k_regrid_interp(const RgInterp *__restric
     const int c = q.coff + J * Pc + I, f0 = q.foff + 2 * J * Pf + 2 * I;
     for (int t = 0; t < fl.n; t++) {
         const double *__restrict__ C = use_base ? cbase.f[fl.f[t]] : ctab[q.cb].f[fl.f[t]];
-        const double c0 = C[c];
-        double s0 = 0.0, s1 = 0.0;
-        if (xl && xh) s0 = 0.5 * (C[c + ox[2]] - C[c + ox[0]]); else if (xh) s0 = C[c + ox[2]] - c0; else if (xl) s0 = c0 - C[c + ox[0]];
-        if (yl && yh) s1 = 0.5 * (C[c + oy[2]] - C[c + oy[0]]); else if (yh) s1 = C[c + oy[2]] - c0; else if (yl) s1 = c0 - C[c + oy[0]];
-        double smax = c0, smin = c0;
+        double nb[3][3], s0, s1;
 #pragma unroll
         for (int b = 0; b < 3; b++)
 #pragma unroll
-            for (int a = 0; a < 3; a++) {
-                if (!(ex[a] && ey[b])) continue;
-                const double v = C[c + oy[b] + ox[a]];
-                smax = fmax(smax, v); smin = fmin(smin, v);
-            }
-        const double deltasum = 0.5 * (fabs(s0) + fabs(s1));
-        if (deltasum > 0.0) {
-            const double etamax = (smax - c0) / deltasum, etamin = (c0 - smin) / deltasum;
-            const double eta = fmax(fmin(fmin(etamin, etamax), 1.0), 0.0);
-            if (xl && xh) s0 = eta * s0;                   // a one-sided slope normal to a domain side stays as computed
-            if (yl && yh) s1 = eta * s1;
-        }
-        double v00 = c0, v10 = c0, v01 = c0, v11 = c0;     // v[p][q]: fine cell (2I + p, 2J + q)
-        v00 = v00 + s0 * -0.25; v10 = v10 + s0 * 0.25; v01 = v01 + s0 * -0.25; v11 = v11 + s0 * 0.25;
-        v00 = v00 + s1 * -0.25; v10 = v10 + s1 * -0.25; v01 = v01 + s1 * 0.25; v11 = v11 + s1 * 0.25;
+            for (int a = 0; a < 3; a++) nb[b][a] = (ex[a] && ey[b]) ? C[c + oy[b] + ox[a]] : 0.0;
+        limited_slopes(nb, xl, xh, yl, yh, true, s0, s1);
+        const double c0 = nb[1][1];
         double *__restrict__ F = ftab[q.fb].f[fl.f[t]];
-        *reinterpret_cast<double2 *>(F + f0) = make_double2(v00, v10);          // (canvas offsets of even fine columns are even: 16-byte aligned)
-        *reinterpret_cast<double2 *>(F + f0 + Pf) = make_double2(v01, v11);
+        // fine cells (2I + p, 2J + q), a row per store (canvas offsets of even fine columns are even: 16-byte aligned)
+        *reinterpret_cast<double2 *>(F + f0) = make_double2(child_value(c0, s0, s1, -0.25, -0.25), child_value(c0, s0, s1, 0.25, -0.25));
+        *reinterpret_cast<double2 *>(F + f0 + Pf) = make_double2(child_value(c0, s0, s1, -0.25, 0.25), child_value(c0, s0, s1, 0.25, 0.25));
     }
 }
 // a_oldData->copyTo(*newData): valid cells only

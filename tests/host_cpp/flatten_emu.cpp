@@ -19,6 +19,9 @@ struct double2 { double x, y; };
 static inline double2 make_double2(double a, double b) { return double2{a, b}; }
 #define __global__
 #define __launch_bounds__(x)
+#define __device__
+#define __forceinline__ inline
+#include "../../suhmo_amd/csrc/suhmo_transfer.h"         // the rule the kernel calls: limited_slopes, child_value
 #include FLATTEN_KERNEL_INC
 // input file: ints: nxd0 nyd0 perx pery nlev max_level ncomp; per level: nbox; per box: nx ny i0 j0 P gy elems then ncomp canvases
 int main(int argc, char **argv)
