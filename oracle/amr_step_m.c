@@ -406,7 +406,9 @@ int or_amrm_model_timestep(OrAmrMModel *S, double dt, int *picard_iters, int *vc
         for (int l = 0; l < n; l++) {
             EACH(l, k, M) {
                 from_solver(S, S->GA, S->Gbase, l, k, OR_F_PHI, tmp);
-                for (int j = 0; j < M->ny; j++) for (int i = 0; i < M->nx; i++) G(M, M->c[OM_B], i, j) = tmp[(size_t)j * M->nx + i];
+                /* run-state setting freeze_icefree_gap, as time_loop.c:solve_gap_implicit: cells without ice keep their gap height */
+                for (int j = 0; j < M->ny; j++) for (int i = 0; i < M->nx; i++)
+                    if (!(p->freeze_icefree_gap && G(M, M->c[OM_MASK], i, j) < 0.0)) G(M, M->c[OM_B], i, j) = tmp[(size_t)j * M->nx + i];
                 free(rhs_b[l][k]);
             }
             mm_pwl(S, l, OM_B);

@@ -281,6 +281,7 @@ def getflux(phi_ghosted, bface, direction, beta, dx_dir, ref=1):
 # ---- time loop ("next rows"): one AmrHydro::timeStepFAS per call
 OM_H, OM_B, OM_BOLD, OM_PI, OM_ZB, OM_MASK, OM_MR, OM_PW, OM_SRC, OM_RHSH, OM_CD, OM_GRADX, OM_GRADY, OM_RE, OM_HLAG, OM_MSRC = range(16)
 OM_QWX, OM_QWY = 100, 101
+OM_DCX, OM_DCY, OM_DTERM = 102, 103, 104          # diffusion coefficient on x / y faces, div(D grad b) on valid cells (unghosted)
 
 
 def make_model_params(m):
@@ -305,7 +306,8 @@ class OracleModel:
     def field(self, fid):
         """numpy VIEW of a model array (ghosted cells (ny+2, nx+2); QWX (ny, nx+1); QWY (ny+1, nx))"""
         p = lib().or_model_field(self.h, fid)
-        shape = {OM_QWX: (self.ny, self.nx + 1), OM_QWY: (self.ny + 1, self.nx)}.get(fid, (self.ny + 2, self.nx + 2))
+        shape = {OM_QWX: (self.ny, self.nx + 1), OM_QWY: (self.ny + 1, self.nx), OM_DCX: (self.ny, self.nx + 1), OM_DCY: (self.ny + 1, self.nx),
+                 OM_DTERM: (self.ny, self.nx)}.get(fid, (self.ny + 2, self.nx + 2))
         return np.ctypeslib.as_array(p, shape=shape)
 
     def set_state(self, f):
@@ -455,7 +457,7 @@ class OracleAmrMModel:
         lo0, lo1, hi0, hi1 = self.boxes[l][k]
         nx, ny = hi0 - lo0 + 1, hi1 - lo1 + 1
         p = lib().or_amrm_model_field(self.h, l, k, fid)
-        shape = {OM_QWX: (ny, nx + 1), OM_QWY: (ny + 1, nx)}.get(fid, (ny + 2, nx + 2))
+        shape = {OM_QWX: (ny, nx + 1), OM_QWY: (ny + 1, nx), OM_DCX: (ny, nx + 1), OM_DCY: (ny + 1, nx), OM_DTERM: (ny, nx)}.get(fid, (ny + 2, nx + 2))
         return np.ctypeslib.as_array(p, shape=shape)
 
     def set_state(self, l, k, f):

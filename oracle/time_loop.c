@@ -57,6 +57,9 @@ double *or_model_field(OrModel *M, int id)
 {
     if (id == OM_QWX) return M->qx;
     if (id == OM_QWY) return M->qy;
+    if (id == OM_DCX) return M->dxf;                        /* read-only names of the diffusion pass: D on x / y faces, div(D grad b) on valid cells */
+    if (id == OM_DCY) return M->dyf;
+    if (id == OM_DTERM) return M->dterm;
     return (id >= 0 && id < OM_NCELL) ? M->c[id] : NULL;
 }
 int or_model_step_index(const OrModel *M) { return M->cur_step; }

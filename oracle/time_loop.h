@@ -24,7 +24,7 @@ typedef struct OrModelParams {
 } OrModelParams;
 
 enum { OM_H = 0, OM_B, OM_BOLD, OM_PI, OM_ZB, OM_MASK, OM_MR, OM_PW, OM_SRC, OM_RHSH, OM_CD,
-       OM_GRADX, OM_GRADY, OM_RE, OM_HLAG, OM_MSRC, OM_NCELL, OM_QWX = 100, OM_QWY = 101 };
+       OM_GRADX, OM_GRADY, OM_RE, OM_HLAG, OM_MSRC, OM_NCELL, OM_QWX = 100, OM_QWY = 101, OM_DCX = 102, OM_DCY = 103, OM_DTERM = 104 };
 
 typedef struct OrModel {
     OrLevel *L;

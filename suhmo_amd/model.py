@@ -184,7 +184,8 @@ def initial_grids(make_model, tag_specs, params, max_level):
 
 class HipModel:
     FIELDS = dict(head=lv.F_PHI, B=lv.F_B, Pi=lv.F_PI, zb=lv.F_ZB, mask=lv.F_MASK, mR=lv.F_MR, Pw=lv.F_PW,
-                  qwx=lv.F_QWX, qwy=lv.F_QWY, cd=lv.F_CD, rhs_h=lv.F_RHS, Re=lv.F_RE, msrc=lv.F_MSRC)
+                  qwx=lv.F_QWX, qwy=lv.F_QWY, cd=lv.F_CD, rhs_h=lv.F_RHS, Re=lv.F_RE, msrc=lv.F_MSRC,
+                  dcx=lv.F_DCX, dcy=lv.F_DCY, dterm=lv.F_DTERM)
 
     def __init__(self, nx, ny, dx, dy, bc, phys, model, max_box=64, device=0, j0=0, ny_global=None, halo_rows=1):
         """j0 / ny_global: this process holds rows j0 .. j0 + ny - 1 of a level of ny_global rows (one strip per GPU;

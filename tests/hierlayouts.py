@@ -248,6 +248,23 @@ def unfilled_corners(nx0, ny0, periodic, boxes):
     return out
 
 
+def cf_ghosts_across_periodic(nx0, ny0, periodic, boxes):
+    """the ghost cells (sides of the ring, as tests/ghostring.py walks them) of the boxes of levels >= 1 that lie outside the domain across a periodic
+    side and that ghostring.cell_kind calls coarse-fine: no box of the level holds the wrapped cell.  PiecewiseLinearFillPatch of the oracle
+    (or_pwl_fill) leaves them alone, the device fills them from the wrapped coarse cell, and which of the two the reference's Chombo does is
+    unpinned -- a time step reads them (CellToEdge of B), so tests/stepsweep.py keeps the layouts where this is 0"""
+    from tests import ghostring as gr
+    n = 0
+    for l, bl in enumerate(boxes, start=1):
+        dom = (nx0 << l, ny0 << l)
+        for b in bl:
+            for _, d, s in gr.SIDES:
+                for i, j in gr.side_cells(b, d, s):
+                    if not (0 <= i < dom[0] and 0 <= j < dom[1]) and gr.cell_kind(i, j, dom, periodic, bl) == "coarse-fine":
+                        n += 1
+    return n
+
+
 def analytic_fields(nx0, ny0, boxes, bc):
     """synthetic.amrm_fields on the nx0 x ny0 base, with the ghost cells of B, Pi, zb and the mask across a periodic side replaced by the periodic
     image (synthetic.wrap_ghosts on every level's whole domain, then cut per box).  The library takes these ghost cells from the caller and asks

@@ -8,6 +8,7 @@ import pytest
 
 from suhmo_amd import synthetic as sy
 from tests import ghostring as gr
+from tests.stepsweep import perturbed_state
 
 pytestmark = pytest.mark.gpu
 GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
@@ -18,17 +19,6 @@ def hipmodel():
     from suhmo_amd import capi, model
     assert capi.lib().suhmo_device_count() > 0, "no GPU visible: the product path has no fallback"
     return model
-
-
-def perturbed_state(nx, ny, seed, mask_holes=False, ly=2.0e4):
-    st = sy.shmip_initial_state(nx, ny, ly=ly)
-    rng = np.random.default_rng(seed)
-    st["B"] = st["B"] * rng.uniform(0.5, 12.0, size=st["B"].shape)     # both sides of br = 0.1
-    st["head"] = st["head"] + rng.uniform(0.0, 30.0, size=st["head"].shape)
-    st["zb"] = st["zb"] + rng.uniform(0.0, 2.0, size=st["zb"].shape)
-    if mask_holes:
-        st["mask"][rng.uniform(size=st["mask"].shape) < 0.05] = -1.0
-    return st
 
 
 CASES = [
