@@ -212,9 +212,10 @@ __device__ __forceinline__ void bcoef_tile(const DV &v, const FP &fp, const suhm
     const double *__restrict__ phi = fp.f[SUHMO_F_PHI], *__restrict__ Bf = fp.f[SUHMO_F_B], *__restrict__ mk = fp.f[SUHMO_F_MASK];
     double *__restrict__ bxo = fp.f[SUHMO_F_BX], *__restrict__ byo = fp.f[SUHMO_F_BY];
     const bool halo_lo = v.ext[0], halo_hi = v.ext[1], selfper_y = v.per[1] && !halo_lo && !halo_hi;
-    // a cell "exists" (has its own phi) inside the domain, as a periodic image, or in an exchanged halo row
-    auto xin = [&](int i) { return INTERIOR || (i >= 0 && i < v.nx) || v.per[0]; };
-    auto yin = [&](int j) { return INTERIOR || (j >= 0 && j < v.ny) || selfper_y || (j < 0 && halo_lo && j >= -v.gy) || (j >= v.ny && halo_hi && j < v.ny + v.gy); };
+    // a cell "exists" (has its own phi) inside the domain, as a periodic image, or in an exchanged halo row.  Images: one period to either side
+    // (wrapx / wrapy wrap once); on a level narrower than the tile the positions further out are never used and must not be loaded
+    auto xin = [&](int i) { return INTERIOR || (i >= 0 && i < v.nx) || (v.per[0] && i >= -v.nx && i < 2 * v.nx); };
+    auto yin = [&](int j) { return INTERIOR || (j >= 0 && j < v.ny) || (selfper_y && j >= -v.ny && j < 2 * v.ny) || (j < 0 && halo_lo && j >= -v.gy) || (j >= v.ny && halo_hi && j < v.ny + v.gy); };
     auto wrapx = [&](int i) { return (!INTERIOR && v.per[0]) ? (i < 0 ? i + v.nx : (i >= v.nx ? i - v.nx : i)) : i; };
     auto wrapy = [&](int j) { return (!INTERIOR && selfper_y) ? (j < 0 ? j + v.ny : (j >= v.ny ? j - v.ny : j)) : j; };
 
