@@ -423,11 +423,14 @@ def iteration_problems(p, v, what):
     return out
 
 
-def run_single(oracle, case, on_start=None, on_step=None):
+def run_single(oracle, case, on_start=None, on_step=None, dt=None):
     """two steps of a single-level case on the oracle -> dict(iters=[(picard, vcycles)], census=[per step], problems=[messages]).
-    on_start(O, st, bc, model, src) and on_step(k, dt, O, census, (picard, vcycles)) let the device test run its model in lockstep"""
+    on_start(O, st, bc, model, src) and on_step(k, dt, O, census, (picard, vcycles)) let the device test run its model in lockstep;
+    dt: a first step size other than the row's own (a batch steps all its members with one: tests/batchsweep.py)"""
     cid, nx, ny, b, r = case
     bc, m = BCS[b], model_of(r)
+    if dt is not None:
+        m = dict(m, dt=dt)
     st = single_state(nx, ny, b, r)
     O = oracle.OracleModel(nx, ny, st["dx"], st["dy"], bc, PHYS, m, max_box=16, nthreads=1)
     rec = dict(iters=[], census=[], problems=[])
