@@ -112,7 +112,9 @@ int suhmo_level_num_depths(const suhmo_level_t *L);
  * agg_min_cells, fas_rhs_fused, resid_in_relax (1: the residual the solve loops evaluate after every V-cycle is left behind by the cycle's
  * last launch where the streaming kernel runs depth 0; 0: always a pass of its own).  Read-only counters: overlapped_launches, agg_gathers,
  * rhs_in_streaming_launches, rhs_in_tile_launches, residual_in_relax_launches, vcycle_graph_replays (V-cycles that ran
- * as a launch of a captured graph).
+ * as a launch of a captured graph); on rank strips, what the relaxation scheduler did: strip_tile_launches, strip_tile_restricting_launches,
+ * strip_tile_shallow_halo_fallbacks (the halo held fewer current rows than a tile launch needs: colour passes), strip_colour_passes,
+ * strip_streaming_launches, strip_streaming_restricting_launches, strip_unfused_prolongations.
  * mask_known (default 1): what UpdateOperator finds out about the ice mask is kept until the mask is written again.  Contract: the mask
  * of a level changes only through this library -- every entry point that writes a field the caller names (set_field, put_box, axby,
  * set_value, divergence, fill_ghosts, unpack_rows, the exchanges (suhmo_hier_exchange included), suhmo_amr2_average / _set_covered / _reflux / _finer_operator_changed, suhmo_hier_average
@@ -341,6 +343,9 @@ int suhmo_level_exchange(suhmo_level_t *L, int depth, int field, suhmo_stream_t 
 /* rows of ghost data kept per y side / 1 if the side is a rank boundary */
 int suhmo_level_halo_info(const suhmo_level_t *L, int depth, int *halo_rows, int *ext_lo, int *ext_hi,
                           int *nx, int *ny);
+/* rank strips, read-only: the halo rows of phi (counted from the strip's edge, each rank-boundary side) that hold the neighbour's
+ * current values according to the scheduler's bookkeeping; 0 .. min(halo_rows, ny); -1 on bad arguments */
+int suhmo_level_phi_halo_fresh(const suhmo_level_t *L, int depth);
 
 /* Native transport for those hooks: RCCL send/recv + 1-element MAX all-reduce enqueued on the caller's
  * stream (suhmo_amd/csrc/suhmo_rccl.hip); stands where the reference has MPI under LevelData::exchange

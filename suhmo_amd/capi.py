@@ -160,7 +160,7 @@ SYMBOLS = [
     "suhmo_level_nonlinear", "suhmo_level_compute_lambda", "suhmo_level_fill_ghosts",
     "suhmo_level_divergence", "suhmo_level_get_flux", "suhmo_level_norm", "suhmo_level_axby",
     "suhmo_level_set_value", "suhmo_level_vcycle", "suhmo_level_solve", "suhmo_level_pack_rows",
-    "suhmo_level_unpack_rows", "suhmo_level_set_hooks", "suhmo_level_exchange", "suhmo_level_halo_info", "suhmo_level_profile_reset",
+    "suhmo_level_unpack_rows", "suhmo_level_set_hooks", "suhmo_level_exchange", "suhmo_level_halo_info", "suhmo_level_phi_halo_fresh", "suhmo_level_profile_reset",
     "suhmo_level_profile_enable", "suhmo_level_profile_read", "suhmo_level_profile_read_restricting", "suhmo_level_timestep",
     "suhmo_rccl_load", "suhmo_rccl_unique_id", "suhmo_level_attach_rccl", "suhmo_level_detach_rccl",
     "suhmo_level_rccl_exchanges", "suhmo_level_rccl_comm_count", "suhmo_level_ipc_export", "suhmo_level_attach_ipc", "suhmo_level_ipc_exchanges", "suhmo_level_detach_ipc",
@@ -242,6 +242,7 @@ def lib():
     L.suhmo_level_dot.argtypes = [vp, ci, ci, ci, dp, vp]
     L.suhmo_level_exchange.argtypes = [vp, ci, ci, vp]
     L.suhmo_level_halo_info.argtypes = [vp, ci] + [C.POINTER(ci)] * 5
+    L.suhmo_level_phi_halo_fresh.argtypes = [vp, ci]
     L.suhmo_level_timestep.argtypes = [vp, C.POINTER(ModelParams), C.c_double, ci, C.POINTER(ci), C.POINTER(ci), vp]
     L.suhmo_rccl_load.argtypes = [C.c_char_p]
     L.suhmo_rccl_unique_id.argtypes = [vp]

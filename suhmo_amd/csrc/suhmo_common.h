@@ -223,6 +223,8 @@ struct suhmo_level {
     // bcoef_nd: the depths AverageOperator refreshes right behind that launch; read-only option bcoef_in_relax_launches counts them
     int bcoef_in_relax, bcoef_nd; long bcoef_in_relax_count;
     long frhs_stream, frhs_tile;   // launches that formed a coarse depth's FAS right-hand side themselves (streaming / tile kernel); read-only options
+    // what the relaxation scheduler did on a rank strip (suhmo_launch_gsrb, suhmo_prolong_with_halo); read-only options strip_*
+    long strip_tile, strip_tile_rst, strip_tile_shallow, strip_colour, strip_stream, strip_stream_rst, strip_prolong_unfused;
     int prof_on;
     std::vector<ProfEv> prof;
     int gsrb_variant;           // kernel selection (see suhmo_gsrb.hip); env SUHMO_GSRB_VARIANT

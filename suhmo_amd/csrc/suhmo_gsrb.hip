@@ -1537,11 +1537,12 @@ int suhmo_launch_gsrb(suhmo_level *L, int depth, int sweeps, int tail, hipStream
             if (F < need) {
                 if (D.prolong_pending) { suhmo_set_error("internal: fused prolongation with a shallow halo"); return -4; }
                 TS = 0;                                        // halo shallower than the tile needs: colour passes
+                L->strip_tile_shallow++;
             } else {
                 // as many more halo rows as the work still to come can use are advanced too (one exchange feeds several launches)
                 const int want = 2 * (sweeps - it - TS) + tail;
                 tE = F - need < want ? F - need : want;
-                if (tE > D.v.gy - need - 1) tE = D.v.gy - need - 1;
+                if (tE > D.v.gy - need) tE = D.v.gy - need;        // (the canvas ends at gy; F <= gy says so already)
                 tE = tE < 0 ? 0 : tE & ~1;
             }
         }
@@ -1559,7 +1560,7 @@ int suhmo_launch_gsrb(suhmo_level *L, int depth, int sweeps, int tail, hipStream
             const bool rst = trst && it + TS * tchunks == sweeps;
             int rc = launch_tile_any(L, depth, TS, tchunks, rst, tE, st); if (rc) return rc;
             if (rst) *restricted = 1;
-            if (ext) { F = tE; D.phi_fresh = tE; }
+            if (ext) { F = tE; D.phi_fresh = tE; L->strip_tile++; if (rst) L->strip_tile_rst++; }
         } else if (K == 0) {
             for (int pass = 0; pass < 2; pass++) {
                 if (ext && F < 1) {
@@ -1571,7 +1572,7 @@ int suhmo_launch_gsrb(suhmo_level *L, int depth, int sweeps, int tail, hipStream
                 if (L->desc.nx_global > 0) E = 0;                          // AMR patch strips: the coarse-fine ghost columns of halo
                                                                            // rows are not exchanged -> no redundant advance
                 { int rc2 = launch_simple(L, depth, pass, E, st); if (rc2) return rc2; }
-                if (ext) { F = E; D.phi_fresh = F; }
+                if (ext) { F = E; D.phi_fresh = F; L->strip_colour++; }
             }
         } else {
             const int nt = L->fused_nt ? L->fused_nt : ((long)D.v.nx * D.v.ny >= 8000000L ? 256 : 64);   // 0 = by size
@@ -1580,11 +1581,16 @@ int suhmo_launch_gsrb(suhmo_level *L, int depth, int sweeps, int tail, hipStream
             // behind (same needs as the restricting launch: one more final row and column around a chunk)
             bool rout = L->resout_armed && depth == 0 && !restricted && nt == 64 && K == 2 && it + K == sweeps && D.v.alpha == 0.0
                         && (!(D.v.ext[0] || D.v.ext[1]) || ext) && L->desc.nx_global == 0 && !D.rhs_pending;
+            // rank strip, the correction is added while loading: only the F halo rows that are current on BOTH depths may be read, and no exchange
+            // can deepen them (the neighbour's phi lacks the correction as well).  A launch that would need one row more leaves no residual
+            // behind; the solve loop then evaluates it in its own pass
+            if (ext && D.prolong_pending && F < 2 * K + 1) rout = false;
             // rank strip: 2K current halo rows, one more when the launch also restricts / evaluates the residual (one exchange instead of
             // the one the separate pass would ask for)
             const int need = 2 * K + ((rst || rout) && ext ? 1 : 0);
             bool flying = false;                                           // the exchange is in flight on the second stream
             if (ext && F < need) {
+                if (D.prolong_pending) { suhmo_set_error("internal: fused prolongation with a shallow halo"); return -4; }
                 // only the native transport is stream-ordered (its pack / send / recv / unpack are enqueued on the stream the hook is
                 // given); a host transport (torch.distributed, gloo, threads) orders against other streams or the whole device:
                 // overlap_halo = 1 overlaps with the native transport only, 2 = the caller vouches for its hook
@@ -1629,7 +1635,7 @@ int suhmo_launch_gsrb(suhmo_level *L, int depth, int sweeps, int tail, hipStream
             if (rc) return rc;
             if (rst) *restricted = 1;
             if (rout) { L->resout_done = 1; L->resout_count++; }
-            if (ext) { F = E; D.phi_fresh = F; }
+            if (ext) { F = E; D.phi_fresh = F; L->strip_stream++; if (rst) L->strip_stream_rst++; }
         }
         int done = TS ? TS * tchunks : K == 0 ? 1 : K;
         if (prof) {

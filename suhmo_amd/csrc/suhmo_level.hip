@@ -174,6 +174,7 @@ int suhmo_level_create_(suhmo_level_t **out, const suhmo_level_desc_t *desc, boo
     L->agg_min_cells = 100000; L->agg_depth = 0; L->agg_world = 1; L->agg_rank = 0; L->agg = nullptr; L->ag = nullptr; L->ag_user = nullptr;
     L->agg_send = L->agg_recv = nullptr; L->agg_cap = 0; L->agg_gathers = 0; L->agg_static_stale = 0;
     L->frhs_stream = L->frhs_tile = 0;
+    L->strip_tile = L->strip_tile_rst = L->strip_tile_shallow = L->strip_colour = L->strip_stream = L->strip_stream_rst = L->strip_prolong_unfused = 0;
     L->bcoef_in_relax = 1; L->bcoef_nd = 0; L->bcoef_in_relax_count = 0;
     L->resout_np = 0;
     L->resout_req = L->resout_armed = L->resout_done = 0; L->resout_rhs = nullptr; L->resout_count = 0; L->resid_in_relax = 1;
@@ -393,6 +394,14 @@ extern "C" int suhmo_level_get_option(const suhmo_level_t *L, const char *key, l
     if (!strcmp(key, "agg_gathers")) { *value = L->agg_gathers; return 0; }              // read-only counter (agglomeration)
     if (!strcmp(key, "rhs_in_streaming_launches")) { *value = L->frhs_stream; return 0; }   // read-only counters (fas_rhs_in_relax)
     if (!strcmp(key, "rhs_in_tile_launches")) { *value = L->frhs_tile; return 0; }
+    {   // read-only counters: what the relaxation scheduler did on a rank strip
+        static const struct { const char *k; long suhmo_level::*m; } strip[] = {
+            {"strip_tile_launches", &suhmo_level::strip_tile}, {"strip_tile_restricting_launches", &suhmo_level::strip_tile_rst},
+            {"strip_tile_shallow_halo_fallbacks", &suhmo_level::strip_tile_shallow}, {"strip_colour_passes", &suhmo_level::strip_colour},
+            {"strip_streaming_launches", &suhmo_level::strip_stream}, {"strip_streaming_restricting_launches", &suhmo_level::strip_stream_rst},
+            {"strip_unfused_prolongations", &suhmo_level::strip_prolong_unfused}};
+        for (const auto &e : strip) if (!strcmp(key, e.k)) { *value = L->*(e.m); return 0; }
+    }
     if (!strcmp(key, "residual_in_relax_launches")) { *value = L->resout_count; return 0; }
     if (!strcmp(key, "bcoef_in_relax_launches")) { *value = L->bcoef_in_relax_count; return 0; }   // read-only counter (bcoef_in_relax)
     if (!strcmp(key, "mask_scans")) { *value = L->mask_scans; return 0; }                 // read-only counters (mask_known)
@@ -465,6 +474,12 @@ extern "C" int suhmo_level_halo_info(const suhmo_level_t *L, int depth, int *hal
     if (nx) *nx = v.nx;
     if (ny) *ny = v.ny;
     return 0;
+}
+// rank strips: how many halo rows of phi (each rank-boundary side) hold the neighbour's current values, as the scheduler believes
+extern "C" int suhmo_level_phi_halo_fresh(const suhmo_level_t *L, int depth)
+{
+    if (!L || depth < 0 || depth >= L->ndepth) return -1;
+    return L->d[depth].phi_fresh;
 }
 
 // ------------------------------------------------------------------ LevelData traffic

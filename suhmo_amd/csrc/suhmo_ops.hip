@@ -483,6 +483,7 @@ int suhmo_prolong_with_halo(suhmo_level *L, int depth, hipStream_t st)
     int rc = launch_prolong(on_level(L, depth), on_level(L, depth + 1), -jlo, jhi - (D.v.ny - 1), -cjlo, cjhi - (C.v.ny - 1), st);
     if (rc) return rc;
     D.phi_fresh = R;
+    if (ext) L->strip_prolong_unfused++;
     return 0;
 }
 

@@ -1,0 +1,395 @@
+"""The rank-strip solve (suhmo_launch_gsrb's halo bookkeeping, suhmo_ensure_phi_halo, the prolongation over halo rows, the FAS cycle on strips)
+swept over strip shapes, halo depths, rank counts and launch options: the table of cases, their seeded inputs, the oracle's answers and a census of
+the thresholds the scheduler branches on, for tests/test_strip_sweep_cpu.py (the oracle alone) and tests/test_gpu_strip_sweep.py (thread ranks on one
+device against the oracle's whole level, bitwise).  A plain helper module like tests/bcoefsweep.py; numpy only, nothing here touches the device library.
+
+A case = one value of each of nine axes (strip height with its box size, nx, number of ranks, halo rows, periodicity, alpha, option row, sweep row
+of the piecewise part, solver row of the cycle part).  The full product is not run: the ANCHORS come first -- cases written out by hand, one per
+counter an option row exists for, whose shape satisfies that branch's conditions in suhmo_gsrb.hip -- and after them a deterministic greedy
+fill adds cases until every pair of values of any two axes occurs (tests/test_strip_sweep_cpu.py asserts the pairs).
+
+Constraints of the layout, asserted in cases(): strips are equal (ny_total = height x world: the exchanger moves min(gy, ny) rows per rank, unequal
+strips are not a supported layout); the strip height is a multiple of max_box, so that the strip's boxes and its number of multigrid depths are the
+whole level's; nx is even."""
+import itertools
+import math
+
+import numpy as np
+
+from suhmo_amd import synthetic as sy
+
+# ---- the axes
+HEIGHTS = ((8, 8), (12, 12), (16, 16), (24, 24), (40, 8), (48, 16), (72, 24), (96, 32))      # (rows per rank at depth 0, max_box)
+# 18, 30, 34: edges of the 16- and 32-wide tiles; 62, 64, 66: around fused_ok's nx >= 64; 120 / 122 and 124 / 126: the last column of one one-wave
+# streaming strip and the first of a second at K = 2 and at K = 1; 130; 128: the width whose coarse depths still stream (64 at depth 1)
+NX = (18, 30, 34, 62, 64, 66, 120, 122, 124, 126, 128, 130)
+WORLD = (2, 3, 4)
+HALO = (1, 2, 3, 4, 5, 8, 9, 10, 11, 16, 24)
+BCS = dict([(name, dict(sy.RANDOM_BC, periodic=[px, py])) for name, px, py in (("walls", 0, 0), ("y-periodic", 0, 1), ("x-periodic", 1, 0), ("xy-periodic", 1, 1))])
+ALPHA = (0.0, 0.5)
+SWEEPS = ((1,), (2,), (3,), (4,), (5,), (7,), (2, 3, 4))            # gsrb calls of the piecewise part, back to back
+SOLVER = tuple((ns, nb) for ns in (1, 2, 3, 4, 5) for nb in (1, 16))  # (num_smooth, num_bottom)
+BETA = -1.0
+PHYS = sy.RANDOM_PHYS
+
+_V1 = dict(GSRB_VARIANT=1, FUSED_MIN_CELLS=1, GSRB_TILE=0)
+_V2 = dict(GSRB_VARIANT=2, FUSED_MIN_CELLS=1, GSRB_TILE=0)
+# option row -> (environment knobs SUHMO_<KEY> read when a level is created (suhmo_level.hip, "ONE place where the environment may override them"),
+#                counters the row exists for: non-zero on some rank in at least one of the row's cases,
+#                counters that must stay zero in every case of the row).
+# The expectations are the scheduler's own conditions, satisfied by the row's anchor below:
+#   strip_tile_launches            suhmo_gsrb.hip tile_ok (gy >= 10, ny >= 10, tile_strips, gsrb_tile) and pick_variant -> 0 below fused_min_cells
+#   strip_tile_restricting_..      suhmo_launch_gsrb `trst`: tile_restrict == 1, fused_restrict, a coarser depth, ny and j0 even, the smoothing's last launch
+#   strip_colour_passes            K == 0 and no tile launch: tile_ok false (gy < 10 or ny < 10 or tile_strips = 0 or gsrb_tile = 0)
+#   strip_streaming_launches       fused_ok: nx even and >= 64, ny >= 4K + 4, gy >= 2K, ny >= 2K
+#   strip_streaming_restricting_.. `may_restrict`: gy >= 5, alpha == 0, K == 2 ends an even smoothing, a coarser depth
+#   rhs_in_streaming_launches      suhmo_gsrb_can_fuse_rhs: K == 2, sweeps >= 4, alpha == 0, rhs_local, phi_fresh >= gy >= 5, ny >= gy on the coarse depth
+#   residual_in_relax_launches     `rout`: resid_in_relax, K == 2 ends the cycle's last relaxation of depth 0, alpha == 0 (the solve arms it)
+#   overlapped_launches            overlap_halo == 2, F < need, ny >= 6 * need, an inner chunk exists (fused_hc small)
+#   strip_unfused_prolongations    suhmo_gsrb_can_fuse_prolong false on a strip: prolong_halo_rows < 2 TS / 2 K (halo of one row)
+#   agg_gathers                    suhmo_agg_setup: a depth >= 1 whose strip holds fewer cells than agg_min_cells
+OPTIONS = dict([
+    ("default", ({}, ("strip_tile_launches", "strip_colour_passes"), ())),
+    ("variant-0", (dict(GSRB_VARIANT=0), ("strip_colour_passes", "strip_unfused_prolongations"), ("strip_streaming_launches",))),
+    ("stream-k1", (_V1, ("strip_streaming_launches",), ("strip_tile_launches", "strip_streaming_restricting_launches"))),
+    ("stream-k2", (_V2, ("strip_streaming_launches", "strip_streaming_restricting_launches", "rhs_in_streaming_launches", "residual_in_relax_launches"),
+                   ("strip_tile_launches",))),
+    ("stream-k2-overlap", (dict(_V2, FUSED_HC=4, OVERLAP_HALO=2), ("overlapped_launches", "strip_streaming_launches"), ())),
+    ("stream-k2-no-overlap", (dict(_V2, FUSED_HC=4, OVERLAP_HALO=0), ("strip_streaming_launches",), ("overlapped_launches",))),
+    ("no-tile-on-strips", (dict(TILE_STRIPS=0), ("strip_colour_passes",), ("strip_tile_launches",))),
+    ("tile-restricts", (dict(TILE_RESTRICT=1), ("strip_tile_restricting_launches",), ())),
+    ("tile-s2", (dict(TILE_S=2), ("strip_tile_launches",), ())),
+    ("tile-s1", (dict(TILE_S=1), ("strip_tile_launches",), ())),
+    ("tile-t32", (dict(TILE_T=32), ("strip_tile_launches",), ())),
+    ("rhs-exchanged", (dict(STRIPS_RHS_LOCAL=0), (), ("rhs_in_streaming_launches",))),
+    ("no-rhs-in-relax", (dict(FAS_RHS_IN_RELAX=0), (), ("rhs_in_streaming_launches", "rhs_in_tile_launches"))),
+    ("no-fused-restrict", (dict(FUSED_RESTRICT=0), (), ("strip_tile_restricting_launches", "strip_streaming_restricting_launches"))),
+    ("no-resid-in-relax", (dict(RESID_IN_RELAX=0), (), ("residual_in_relax_launches",))),
+    ("mask-always-read", (dict(SKIP_MASK=0), (), ())),
+    # the three switches above do nothing unless the streaming kernel runs the strips: once more on top of it
+    ("stream-k2-no-rhs-in-relax", (dict(_V2, FAS_RHS_IN_RELAX=0), ("strip_streaming_launches",), ("rhs_in_streaming_launches",))),
+    ("stream-k2-no-fused-restrict", (dict(_V2, FUSED_RESTRICT=0), ("strip_streaming_launches",), ("strip_streaming_restricting_launches",))),
+    ("stream-k2-no-resid-in-relax", (dict(_V2, RESID_IN_RELAX=0), ("strip_streaming_launches",), ("residual_in_relax_launches",))),
+    # AGG_MIN_CELLS by the case's shape (agg_min_cells()): every depth >= 1 agglomerated / the bottom depth alone
+    ("agglomerate-from-depth-1", (dict(AGG_MIN_CELLS="from-depth-1"), ("agg_gathers",), ())),
+    ("agglomerate-bottom-only", (dict(AGG_MIN_CELLS="bottom-only"), ("agg_gathers",), ())),
+])
+COUNTERS = ("strip_tile_launches", "strip_tile_restricting_launches", "strip_tile_shallow_halo_fallbacks", "strip_colour_passes",
+            "strip_streaming_launches", "strip_streaming_restricting_launches", "strip_unfused_prolongations", "overlapped_launches",
+            "rhs_in_streaming_launches", "rhs_in_tile_launches", "residual_in_relax_launches", "agg_gathers")
+# no case can take it: a tile launch on a strip asks for at most 2 * 4 + 1 = 9 current halo rows, tile_ok admits strips with gy >= 10 and ny >= 10
+# only, and an exchange leaves min(gy, ny) >= 10 current rows -- the fallback of suhmo_launch_gsrb (`TS = 0`) is a guard, asserted to stay unused
+NEVER = ("strip_tile_shallow_halo_fallbacks", "rhs_in_tile_launches")      # (rhs_in_tile: suhmo_gsrb_can_fuse_rhs answers `!strip && ...` for K <= 0)
+
+AXES = ("height", "nx", "world", "halo", "bc", "alpha", "option", "sweeps", "solver")
+_VALUES = (HEIGHTS, NX, WORLD, HALO, tuple(BCS), ALPHA, tuple(OPTIONS), SWEEPS, SOLVER)
+
+
+def _anchor(option, height=(48, 16), nx=64, world=2, halo=16, bc="walls", alpha=0.0, sweeps=(4,), solver=(4, 16)):
+    return tuple(v.index(x) for v, x in zip(_VALUES, (height, nx, world, halo, bc, alpha, option, sweeps, solver)))
+
+
+# one case per counter a row exists for, its shape chosen from the conditions quoted above OPTIONS (48 x 64 strips of boxes of 16: depths of
+# 48, 24, 12 and 6 rows; 96 x 128 strips of boxes of 32: 96, 48, 24, 12, 6 rows with 128, 64, ... columns: the streaming kernel on depths 0 and 1)
+ANCHORS = (
+    _anchor("default"), _anchor("variant-0", halo=1), _anchor("stream-k1", nx=128), _anchor("stream-k2", height=(96, 32), nx=128),
+    _anchor("stream-k2-overlap", height=(96, 32), nx=128, halo=4), _anchor("stream-k2-no-overlap", height=(96, 32), nx=128, halo=4),
+    _anchor("no-tile-on-strips"), _anchor("tile-restricts"), _anchor("tile-restricts", world=3, bc="y-periodic", halo=10), _anchor("tile-s2"), _anchor("tile-s1"),
+    _anchor("tile-t32"), _anchor("stream-k2-no-rhs-in-relax", height=(96, 32), nx=128), _anchor("stream-k2-no-fused-restrict", height=(96, 32), nx=128),
+    _anchor("stream-k2-no-resid-in-relax", height=(96, 32), nx=128), _anchor("agglomerate-from-depth-1"), _anchor("agglomerate-bottom-only"),
+    # five pre-smoothing sweeps on 11 halo rows: the four-sweep tile launch keeps min(11 - 8, ..., gy - 8) & ~1 = 2 rows, the one-sweep launch
+    # that restricts needs 2 + 1: the one place where the `+ 1` of its `need` decides whether an exchange happens
+    _anchor("tile-restricts", halo=11, solver=(5, 16)), _anchor("tile-restricts", height=(96, 32), nx=128, world=3, bc="y-periodic", halo=11, solver=(5, 1)),
+    # an ODD number of current halo rows when the correction is added inside the first post-smoothing launch of the streaming kernel (alpha != 0:
+    # the restriction is its own kernel and leaves the 9 - 4 = 5, 11 - 4 - 2 = 5 rows the pre-smoothing kept): prolong_halo_rows' `& ~1`
+    _anchor("stream-k2", height=(96, 32), nx=128, halo=9, alpha=0.5, solver=(2, 16)),
+    _anchor("stream-k2", height=(96, 32), nx=128, world=3, bc="y-periodic", halo=11, alpha=0.5, solver=(3, 16)),
+    # two smoothing sweeps: the ONE streaming launch of depth 0's post-smoothing adds the correction while loading and, in a solve, is also asked
+    # for the residual -- 2K + 1 rows where the prolongation vouches for 2K (the defect of DESIGN.md's findings: RES next to a rank boundary)
+    _anchor("stream-k2", height=(96, 32), nx=128, halo=16, solver=(2, 16)), _anchor("stream-k2", nx=64, halo=24, solver=(2, 1)),
+    _anchor("stream-k2", height=(96, 32), nx=128, world=4, bc="xy-periodic", halo=24, solver=(2, 16)),
+)
+
+
+def _pairwise(sizes, first):
+    """rows of axis indices: `first`, then greedily one row at a time until every pair of values of any two axes occurs; deterministic"""
+    n = len(sizes)
+    open_ = {(a, b): set(itertools.product(range(sizes[a]), range(sizes[b]))) for a in range(n) for b in range(a + 1, n)}
+    used = [[0] * s for s in sizes]
+    rows = []
+
+    def is_open(a, va, b, vb):
+        return (va, vb) in open_[(a, b)] if a < b else (vb, va) in open_[(b, a)]
+
+    def take(row):
+        rows.append(tuple(row))
+        for a in range(n):
+            used[a][row[a]] += 1
+            for b in range(a + 1, n):
+                open_[(a, b)].discard((row[a], row[b]))
+
+    for r in first:
+        take(r)
+    while True:
+        (a, b), left = max(open_.items(), key=lambda kv: (len(kv[1]), -kv[0][0], -kv[0][1]))
+        if not left:
+            return rows
+        va, vb = min(left)
+        row = {a: va, b: vb}
+        for x in sorted(set(range(n)) - {a, b}, key=lambda x: (-sizes[x], x)):
+            row[x] = max(range(sizes[x]), key=lambda v: (sum(is_open(x, v, y, vy) for y, vy in row.items()), -used[x][v], -v))
+        take([row[x] for x in range(n)])
+
+
+_CASES = None
+
+
+def cases():
+    """[(id, nx, ny_total, world, max_box, halo, bc name, alpha, option name, sweep row, solver row, seed)]"""
+    global _CASES
+    if _CASES is None:
+        out = []
+        for k, row in enumerate(_pairwise([len(v) for v in _VALUES], ANCHORS)):
+            (h, mb), nx, world, halo, bc, alpha, opt, sweeps, solver = (v[i] for v, i in zip(_VALUES, row))
+            assert h % mb == 0 and nx % 2 == 0 and nx * h * world <= 130 * 384
+            cid = "%03d-%dx%dx%d-box%d-halo%d-%s-a%g-%s-s%s-n%db%d" % (k, nx, h, world, mb, halo, bc, alpha, opt, "+".join(map(str, sweeps)), solver[0], solver[1])
+            out.append((cid, nx, h * world, world, mb, halo, bc, alpha, opt, sweeps, solver, [nx, h, world, k]))
+        _CASES = out
+    return list(_CASES)
+
+
+def axis_values(case):
+    """the case's value on every axis, in the order of AXES"""
+    cid, nx, nyt, world, mb, halo, bc, alpha, opt, sweeps, solver, seed = case
+    return ((nyt // world, mb), nx, world, halo, bc, alpha, opt, sweeps, solver)
+
+
+# cases the sweep leaves out, with the reason: {case id: reason}.  Nothing else is filtered anywhere.
+EXCLUDED = {}
+
+
+def fields(case):
+    """the whole level's inputs, deterministic in the case: synthetic.random_fields with mask holes, the ghost ring a periodic image where periodic"""
+    cid, nx, nyt, world, mb, halo, bc, alpha, opt, sweeps, solver, seed = case
+    return sy.wrap_ghosts(sy.random_fields(nx, nyt, seed=seed), BCS[bc])
+
+
+def solver_params(case):
+    ns, nb = case[10]
+    return dict(sy.SOLVER_DEFAULT, num_smooth=ns, num_bottom=nb, max_iter=3, eps=1e-10, norm_thresh=1e-13)
+
+
+def coarsenable(n, mb, c):
+    """every box of a row of boxes of mb cells over n cells is a multiple of c cells (boxes_coarsenable of suhmo_level.hip in one direction)"""
+    return all((min(lo + mb, n) - lo) % c == 0 for lo in range(0, n, mb))
+
+
+def strip_ndepth(nx, ny, mb, j0, nyt):
+    """MGnewOp's depth rule as suhmo_level.hip:236-242 states it for the strip of ny rows from row j0 of nyt"""
+    nd = 1
+    for dep in range(1, 16):
+        c = (1 << dep) * 2
+        if not (coarsenable(nx, mb, c) and coarsenable(ny, mb, c)) or j0 % (1 << dep) or nyt % (1 << dep) or nx % (1 << dep):
+            break
+        nd = dep + 1
+    return nd
+
+
+def agg_min_cells(case, kind):
+    """AGG_MIN_CELLS of the two agglomeration rows: above every coarse depth's strip / between the bottom depth's strip and the one above it"""
+    cid, nx, nyt, world, mb = case[:5]
+    h = nyt // world
+    nd = strip_ndepth(nx, h, mb, 0, nyt)
+    if kind == "from-depth-1":
+        return nx * h
+    return ((nx >> (nd - 1)) * (h >> (nd - 1))) + 1
+
+
+def environment(case):
+    """{SUHMO_<KEY>: str} of the case's option row"""
+    env = {}
+    for k, v in OPTIONS[case[8]][0].items():
+        env["SUHMO_" + k] = str(agg_min_cells(case, v) if k == "AGG_MIN_CELLS" else v)
+    return env
+
+
+# ---- the thresholds the scheduler branches on, per depth: {threshold: side}
+def sides(nx, ny, gy):
+    """the strip of nx x ny cells with gy halo rows of one depth: which side of every threshold of suhmo_gsrb.hip / suhmo_ops.hip it sits on"""
+    s = {}
+    for K in (1, 2):
+        s["gy < 2K, K=%d" % K] = gy < 2 * K                          # fused_ok
+        s["gy < 2K + 1, K=%d" % K] = gy < 2 * K + 1                  # the restricting / residual-leaving launch, suhmo_gsrb_can_fuse_rhs
+        s["ny < 4K + 4, K=%d" % K] = ny < 4 * K + 4                  # fused_ok
+        s["ny >= 6 * need, need=2K, K=%d" % K] = ny >= 12 * K        # the overlapped exchange
+        s["ny >= 6 * need, need=2K+1, K=%d" % K] = ny >= 12 * K + 6
+    s["gy < 10"] = gy < 10                                           # tile_ok
+    s["ny < 10"] = ny < 10
+    s["gy >= 5"] = gy >= 5                                           # may_restrict
+    s["ny < gy"] = ny < gy                                           # rows exchanged = ny
+    s["ny == 2"] = ny == 2
+    s["ny == 4"] = ny == 4
+    s["nx < 64"] = nx < 64                                           # fused_ok
+    s["nx <= 16"] = nx <= 16                                         # one tile column
+    s["nx <= 32"] = nx <= 32
+    s["nx <= 120"] = nx <= 120                                       # one one-wave streaming strip at K = 2
+    s["nx <= 124"] = nx <= 124                                       # ... at K = 1
+    s["min(gy, ny) odd"] = bool(min(gy, ny) & 1)                     # the `& ~1` of prolong_halo_rows bites after an exchange
+    for name, need in (("", 8), (" restricting", 9)):                # tE's cap gy - need of a four-sweep tile launch, then `& ~1`
+        cap = gy - need
+        s["tile S=4%s: cap gy - need" % name] = "no tile" if gy < 10 else "odd" if cap & 1 else "even"
+    return s
+
+
+def depth_records(case):
+    """[(depth, nx, ny, rows exchanged, sides)] of the strips of a case"""
+    cid, nx, nyt, world, mb, halo = case[:6]
+    h = nyt // world
+    return [(d, nx >> d, h >> d, min(halo, h >> d), sides(nx >> d, h >> d, halo)) for d in range(strip_ndepth(nx, h, mb, 0, nyt))]
+
+
+# sides no case takes at depth 0 / at a coarse depth, with the reason; every other side must be taken (tests/test_strip_sweep_cpu.py)
+NOT_AT_DEPTH0 = {
+    ("ny < 4K + 4, K=1", True): "the lowest strip of the table has 8 rows", ("ny == 2", True): "the lowest strip of the table has 8 rows",
+    ("ny == 4", True): "the lowest strip of the table has 8 rows", ("nx <= 16", True): "the narrowest level is 18 cells wide",
+}
+NOT_AT_COARSE = {("nx <= 120", False): "the widest level is 130 cells wide", ("nx <= 124", False): "the widest level is 130 cells wide"}
+
+
+def depth_problems(oracle):
+    """the oracle's number of depths of every case's whole level against the strip rule for every rank's j0: [messages]"""
+    out = []
+    for case in cases():
+        cid, nx, nyt, world, mb = case[:5]
+        O = oracle.OracleLevel(nx, nyt, 3.0, 2.0, BCS[case[6]], PHYS, case[7], BETA, mb, 1)
+        mine = {strip_ndepth(nx, nyt // world, mb, r * (nyt // world), nyt) for r in range(world)}
+        if mine != {O.ndepth}:
+            out.append("%s: the oracle's level has %d depths, the strips %s" % (cid, O.ndepth, sorted(mine)))
+        O.close()
+    return out
+
+
+def census():
+    """dict(lines=[per case and depth], arms={(threshold, side, 'depth 0' | 'coarse'): [cases, set of shapes, set of worlds]})"""
+    out = dict(lines=[], arms={})
+    for case in cases():
+        cid, nx, nyt, world = case[:4]
+        for d, nxd, nyd, rows, sd in depth_records(case):
+            out["lines"].append("%-80s depth %d  %3d x %-3d rows exchanged %2d  %s" % (
+                cid, d, nxd, nyd, rows, " ".join("1" if v is True else "0" if v is False else v.replace(" ", "-") for v in sd.values())))
+            for t, v in sd.items():
+                a = out["arms"].setdefault((t, v, "depth 0" if d == 0 else "coarse"), [set(), set(), set()])
+                a[0].add(cid); a[1].add((nxd, nyd)); a[2].add(world)
+    return out
+
+
+def census_table(c):
+    """the census as text: tests/golden/STRIP_SWEEP_CENSUS.txt (tools/strip_sweep_census.py writes it)"""
+    names = list(sides(2, 2, 1))
+    lines = ["# census of the rank-strip sweep: tests/stripsweep.py, regenerated by tools/strip_sweep_census.py",
+             "# %d cases; per case and depth: the strip, the halo rows an exchange moves, and the side of every threshold, in this order:" % len(cases())]
+    lines += ["#   %2d  %s" % (k, t) for k, t in enumerate(names)]
+    lines += c["lines"]
+    lines += ["", "%-44s %-8s %-8s %6s %6s %6s" % ("threshold", "side", "where", "cases", "shapes", "worlds")]
+    for (t, v, where), (cs, shp, ws) in sorted(c["arms"].items(), key=lambda kv: (names.index(kv[0][0]), str(kv[0][1]), kv[0][2] != "depth 0")):
+        lines.append("%-44s %-8s %-8s %6d %6d %6d" % (t, v, where, len(cs), len(shp), len(ws)))
+    return "\n".join(lines) + "\n"
+
+
+# ---- exact sums for norm(., 2) and dot
+def two_prod(x, y):
+    """(p, e) with p + e == x * y exactly (Veltkamp / Dekker; no overflow at these magnitudes)"""
+    p = x * y
+    def split(a):
+        c = 134217729.0 * a
+        hi = c - (c - a)
+        return hi, a - hi
+    xh, xl = split(x)
+    yh, yl = split(y)
+    e = ((xh * yh - p) + xh * yl + xl * yh) + xl * yl
+    return p, e
+
+
+def exact_dot(x, y):
+    """(the correctly rounded sum of x_i y_i, the bound (n - 1) 2^-53 sum |x_i y_i| on what any order of summation can lose)"""
+    x, y = np.ravel(x), np.ravel(y)
+    p, e = two_prod(x, y)
+    s = math.fsum(np.concatenate([p, e]).tolist())
+    return s, (x.size - 1) * 2.0 ** -53 * math.fsum(np.abs(p).tolist())
+
+
+def norm2_bound(s, b):
+    """the bound on |sqrt(computed sum) - sqrt(s)| when the computed sum is within b of s, plus one rounding of the square root on either side"""
+    r = math.sqrt(s)
+    return b / (r + math.sqrt(max(s - b, 0.0))) * (1.0 + 2.0 ** -52) + 2.0 ** -52 * r if r > 0.0 else math.sqrt(b)
+
+
+# ---- the oracle's answers
+def oracle_pieces(oracle, case, f=None):
+    """the piecewise part on the oracle's whole level: [(step name, {field name: array or number})]"""
+    cid, nx, nyt, world, mb, halo, bc, alpha, opt, sweeps, solver, seed = case
+    f = fields(case) if f is None else f
+    O = oracle.OracleLevel(nx, nyt, f["dx"], f["dy"], BCS[bc], PHYS, alpha, BETA, mb, 1)
+    try:
+        O.set_inputs(f)
+        out = []
+        for s in sweeps:
+            O.gsrb(s)
+        out.append(("gsrb", dict(PHI=O.get(oracle.F_PHI))))
+        O.residual()
+        res = O.get(oracle.F_RES)
+        out.append(("residual", dict(PHI=O.get(oracle.F_PHI), RES=res, norm0=O.norm(oracle.F_RES, 0))))
+        O.apply_op()
+        out.append(("apply_op", dict(PHI=O.get(oracle.F_PHI), LPHI=O.get(oracle.F_LPHI))))
+        O.update_operator()
+        out.append(("update_operator", dict(PHI=O.get(oracle.F_PHI), BX=O.get(oracle.F_BX), BY=O.get(oracle.F_BY))))
+        for s in sweeps:
+            O.gsrb(s)
+        out.append(("gsrb again", dict(PHI=O.get(oracle.F_PHI))))
+        return out, O.ndepth
+    finally:
+        O.close()
+
+
+def oracle_cycle(oracle, case, f=None):
+    """the cycle part on the oracle's whole level: dict(ndepth, v1, v2 = {depth: (PHI, RES)} after each V-cycle, phi, res, n, hist of the solve)"""
+    cid, nx, nyt, world, mb, halo, bc, alpha, opt, sweeps, solver, seed = case
+    f = fields(case) if f is None else f
+    sp = solver_params(case)
+    O = oracle.OracleLevel(nx, nyt, f["dx"], f["dy"], BCS[bc], PHYS, alpha, BETA, mb, 1)
+    try:
+        O.set_inputs(f)
+        O.build_mg_coefficients()
+        out = dict(ndepth=O.ndepth)
+        for key in ("v1", "v2"):
+            O.vcycle(sp)
+            out[key] = {d: (O.get(oracle.F_PHI, depth=d), O.get(oracle.F_RES, depth=d)) for d in range(O.ndepth)}
+        n, hist = O.solve(sp)
+        out.update(n=n, hist=hist, phi=O.get(oracle.F_PHI), res=O.get(oracle.F_RES))
+        return out
+    finally:
+        O.close()
+
+
+def rank_boundary_rows(nyt, world, halo, periodic_y, depth=0):
+    """bool per row of the whole level at `depth`: within `halo` rows of a boundary between two ranks"""
+    ny = (nyt // world) >> depth
+    near = np.zeros(ny * world, dtype=bool)
+    for r in range(world):
+        for side, nb in ((0, r - 1), (1, r + 1)):
+            if 0 <= nb < world or periodic_y:
+                lo = r * ny if side == 0 else (r + 1) * ny - min(halo, ny)
+                near[lo:lo + min(halo, ny)] = True
+    return near
+
+
+def first_difference(a, b):
+    """None when a and b hold the same values (NaN equal to NaN), else (row, column) of the first cell that differs"""
+    a, b = np.asarray(a), np.asarray(b)
+    if a.shape != b.shape:
+        return ("shape", a.shape, b.shape)
+    bad = ~((a == b) | (np.isnan(a) & np.isnan(b)))
+    if not bad.any():
+        return None
+    j, i = np.argwhere(bad.reshape(a.shape[0], -1))[0]
+    return int(j), int(i)
