@@ -2,6 +2,7 @@
 // nested patches, of a hierarchy of box unions and of the members of an ensemble, and the time-varying (seasonal) recharge.
 #include "suhmo_hier_int.h"
 #include "suhmo_batch.h"
+#include "suhmo_reduce.h"
 #include <cmath>
 
 using namespace hier;
@@ -51,7 +52,6 @@ struct StepMoulinLists : MemberMoulinLists {
 __device__ __forceinline__ void d_moulin_partial(const DV &v, int n, const double *__restrict__ mo, double *__restrict__ partial, const Excl &ex,
                                                  const double *__restrict__ cover)
 {
-    __shared__ double sm[256];
     const int tid = threadIdx.y * 16 + threadIdx.x;
     const int i = blockIdx.x * 16 + threadIdx.x, j = blockIdx.y * 16 + threadIdx.y;
     bool in = i < v.nx && j < v.ny && !(i >= ex.i0 && i < ex.i1 && j >= ex.j0 && j < ex.j1);   // covered by a finer level: 0
@@ -64,26 +64,21 @@ __device__ __forceinline__ void d_moulin_partial(const DV &v, int n, const doubl
         double ddx = mx < tx0 ? tx0 - mx : (mx > tx1 ? mx - tx1 : 0.0), ddy = my < ty0 ? ty0 - my : (my > ty1 ? my - ty1 : 0.0);
         if ((ddx * ddx + ddy * ddy) / (2.0 * sg * sg) > 760.0) { if (tid == 0) partial[(size_t)blk * n + m] = 0.0; continue; }   // uniform
         bool z;
-        double val = in ? moulin_cell(i + 0.5 + v.i0, j + 0.5 + v.j0, v.dx, v.dy, mx, my, sg, z) * v.dx * v.dy : 0.0;
-        sm[tid] = val;
-        __syncthreads();
-        for (int s = 128; s > 0; s >>= 1) { if (tid < s) sm[tid] = sm[tid] + sm[tid + s]; __syncthreads(); }
-        if (tid == 0) partial[(size_t)blk * n + m] = sm[0];
+        double val[1] = {in ? moulin_cell(i + 0.5 + v.i0, j + 0.5 + v.j0, v.dx, v.dy, mx, my, sg, z) * v.dx * v.dy : 0.0};
+        block_tree<RedSum>(tid, val);                     // one term per thread: the tree alone
+        if (tid == 0) partial[(size_t)blk * n + m] = val[0];
         __syncthreads();
     }
 }
 // one workgroup per moulin (blockIdx.x; the lists of an ensemble differ in length: a workgroup past the end of its member's list has nothing to do)
 __device__ __forceinline__ void d_moulin_final(const double *__restrict__ partial, int nblk, int n, double *__restrict__ integ)
 {
-    __shared__ double sm[256];
     const int m = blockIdx.x, tid = threadIdx.x;
     if (m >= n) return;                                                                                  // uniform
-    double acc = 0.0;
-    for (int b = tid; b < nblk; b += 256) acc = acc + partial[(size_t)b * n + m];
-    sm[tid] = acc;
-    __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) { if (tid < s) sm[tid] = sm[tid] + sm[tid + s]; __syncthreads(); }
-    if (tid == 0) integ[m] = sm[0];
+    double acc[1] = {0.0};
+    for (int b = tid; b < nblk; b += 256) acc[0] = acc[0] + partial[(size_t)b * n + m];      // (the second stage's stride over a list laid out per tile)
+    block_tree<RedSum>(tid, acc);
+    if (tid == 0) integ[m] = acc[0];
 }
 __device__ __forceinline__ void d_moulin_src(const DV &v, int n, const double *__restrict__ mo, const double *__restrict__ flux,
                                              const double *__restrict__ integ, double tf, double *__restrict__ out, const Excl &ex,

@@ -34,9 +34,9 @@ template <class T> int launch_coef_ghosts(const T &t, int field, hipStream_t st)
 template <class T> int launch_bcoef_fused(const T &t, bool wide, unsigned *flag, unsigned epoch, hipStream_t st, unsigned *small = nullptr, bool unmasked = false);   // UpdateOperator, the fused WFlx_level kernel
 int suhmo_multi_grad_cc(const suhmo_multi &m, hipStream_t st);      // launch_grad_cc, or one launch when m.merged
 int suhmo_multi_re_bcoef(const suhmo_multi &m, hipStream_t st);     // launch_re + launch_bcoef_faces, or one launch when m.merged
-int suhmo_multi_norm_max(const suhmo_multi &m, suhmo_level *slot, int field, double *out, hipStream_t st);                // max |x| over the valid cells of all boxes
-// the same in pieces, for one read-back over a whole hierarchy: first stages (partial maxima of level 0 / of a level of boxes), then one launch over all lists
-int suhmo_level_norm_max_partials(suhmo_level *L, int field, const double **partials, int *np, hipStream_t st);
+// max |field| over valid cells in pieces, for one read-back over a whole hierarchy: first stages (the partial maxima of level 0 -- cover: field <- 0
+// where SUHMO_F_COVER is set, on the way -- and of a level of boxes, where they always lie), then one second stage over all lists (suhmo_reduce.h)
+int suhmo_level_norm_max_partials(suhmo_level *L, int field, bool cover, const double **partials, int *np, hipStream_t st);
 int suhmo_multi_norm_max_partials(const suhmo_multi &m, int field, const double **partials, int *np, hipStream_t st);
 int suhmo_norm_max_of_lists(suhmo_level *slot, const double *const *partials, const int *np, int cnt, double *out, hipStream_t st);
 // SEVERAL levels of boxes in one launch (blockIdx.z runs over the boxes of the listed levels, one after the other): by value, indexed with
@@ -44,7 +44,6 @@ int suhmo_norm_max_of_lists(suhmo_level *slot, const double *const *partials, co
 constexpr int SUHMO_LVMAX = 7;
 struct suhmo_lvboxes { const DV *dv[SUHMO_LVMAX]; const FP *fp[SUHMO_LVMAX]; int nbox[SUHMO_LVMAX], mode[SUHMO_LVMAX]; int n, maxnx, maxny; };
 int suhmo_levels_apply(const suhmo_lvboxes &lv, const suhmo_phys_t &ph, bool has_alpha, hipStream_t st);   // mode[q]: 1 RES = rhs - L(phi), 3: LPHI as well (launch_apply_boxes)
-// field <- 0 where SUHMO_F_COVER is set, and the first stage of max |field| over the rest, of the listed levels / of a whole level; one partial per workgroup
+// field <- 0 where SUHMO_F_COVER is set (mode[q] != 0), and the first stage of max |field| over the rest, of the listed levels; one partial per workgroup
 int suhmo_levels_norm_max_cover_partials(const suhmo_lvboxes &lv, int field, double *partial, int *np, hipStream_t st);
-int suhmo_level_norm_max_cover_partials(suhmo_level *L, int field, const double **partials, int *np, hipStream_t st);
 int suhmo_levels_grad_cc(const suhmo_lvboxes &lv, int hasMask, hipStream_t st);                              // suhmo_multi_grad_cc (merged form) of several levels

@@ -746,9 +746,9 @@ static int hier_residual_(suhmo_hier *H, double *norm, suhmo_stream_t s)
         suhmo_lvboxes lv;
         // level 0: a large one is not read a second time for its cover -- its covered rectangles are zeroed by their list (one small launch), then the
         // plain first stage; a small one zeroes as it reduces, like the levels of boxes
-        if (base_of(H)->d[0].elems > (1 << 20)) {
-            if ((rc = hier_avg(H, 1, SUHMO_F_RES, SUHMO_F_RES, 1, 0.0, HST(s))) || (rc = suhmo_level_norm_max_partials(base_of(H), SUHMO_F_RES, &lists[0], &np[0], HST(s)))) return rc;
-        } else if ((rc = suhmo_level_norm_max_cover_partials(base_of(H), SUHMO_F_RES, &lists[0], &np[0], HST(s)))) return rc;
+        const bool large = base_of(H)->d[0].elems > (1 << 20);
+        if (large && (rc = hier_avg(H, 1, SUHMO_F_RES, SUHMO_F_RES, 1, 0.0, HST(s)))) return rc;
+        if ((rc = suhmo_level_norm_max_partials(base_of(H), SUHMO_F_RES, !large, &lists[0], &np[0], HST(s)))) return rc;
         if ((rc = levels_boxes(H, 1, top, 0, 1, s, lv)) || (rc = suhmo_levels_norm_max_cover_partials(lv, SUHMO_F_RES, H->red_all, &np[1], HST(s)))) return rc;
         lists[1] = H->red_all;
         return norm ? suhmo_norm_max_of_lists(base_of(H), lists, np, 2, norm, HST(s)) : 0;
@@ -762,7 +762,7 @@ static int hier_residual_(suhmo_hier *H, double *norm, suhmo_stream_t s)
         // (a maximum is the same in any order) instead of a reduction and a read-back per level
         const double *lists[8];
         int np[8];
-        if ((rc = suhmo_level_norm_max_partials(base_of(H), SUHMO_F_RES, &lists[0], &np[0], HST(s)))) return rc;
+        if ((rc = suhmo_level_norm_max_partials(base_of(H), SUHMO_F_RES, false, &lists[0], &np[0], HST(s)))) return rc;
         for (int l = 1; l <= top; l++) {
             suhmo_multi mv;
             if ((rc = multi_of(H, l, HST(s), mv)) || (rc = suhmo_multi_norm_max_partials(mv, SUHMO_F_RES, &lists[l], &np[l], HST(s)))) return rc;
@@ -775,8 +775,12 @@ static int hier_residual_(suhmo_hier *H, double *norm, suhmo_stream_t s)
         double mp = 0.0;
         for (int l = 1; l <= top; l++) {
             double a = 0.0;
+            const double *list;
+            int n;
             suhmo_multi mv;
-            if ((rc = multi_of(H, l, HST(s), mv)) || (rc = suhmo_multi_norm_max(mv, base_of(H), SUHMO_F_RES, &a, HST(s)))) return rc;
+            if ((rc = multi_of(H, l, HST(s), mv))) return rc;
+            if (mv.nbox <= 0) continue;                                 // a rank that owns no box of the level
+            if ((rc = suhmo_multi_norm_max_partials(mv, SUHMO_F_RES, &list, &n, HST(s))) || (rc = suhmo_norm_max_of_lists(base_of(H), &list, &n, 1, &a, HST(s)))) return rc;
             if (a > mp) mp = a;
         }
         if (H->part && (rc = suhmo_hier_allreduce_max_(H, &mp))) return rc;     // owner computes: every rank saw its own boxes only

@@ -4,6 +4,7 @@
 #include "suhmo_level_int.h"
 #include "suhmo_batch.h"
 #include "suhmo_transfer.h"
+#include "suhmo_reduce.h"
 #include <algorithm>
 #include <cmath>
 #include <initializer_list>
@@ -109,9 +110,7 @@ __device__ __forceinline__ void d_residual_norm(const DV &v, const FP &fp, const
 {
     __shared__ double sm[4];
     const int i = blockIdx.x * blockDim.x + threadIdx.x, j = blockIdx.y * blockDim.y + threadIdx.y;
-    double r = fabs(d_apply_at<HAS_ALPHA, 1>(v, fp, ph, 0, 0, 0, i, j));
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) r = fmax(r, __shfl_xor(r, o));
+    const double r = wave_max(fabs(d_apply_at<HAS_ALPHA, 1>(v, fp, ph, 0, 0, 0, i, j)));
     if (threadIdx.x == 0) sm[threadIdx.y] = r;
     __syncthreads();
     if (threadIdx.x == 0 && threadIdx.y == 0) partial[blockIdx.y * gridDim.x + blockIdx.x] = fmax(fmax(sm[0], sm[1]), fmax(sm[2], sm[3]));
@@ -602,40 +601,32 @@ extern "C" int suhmo_level_set_value(suhmo_level_t *L, int depth, int field, dou
     return 0;
 }
 
-// norms over valid cells.  ord 0: max |x| (exact, order independent).  ord 2: sqrt(sum x^2),
-// two-stage deterministic reduction (fixed partial order; differs from the serial CPU sum
-// by rounding only).
-__global__ __launch_bounds__(256) void k_norm_partial(DV v, const double *__restrict__ x, int ord, double *__restrict__ partial)
+// norms and the dot product over valid cells: the first stages of suhmo_reduce.h (the order of a sum: there), one partial per workgroup.
+// max |x| of a field, the composite norm's covered cells zeroed on the way where `cover` is given (AMRNorm zeroes them,
+// src/AMRNonLinearPoissonOp.cpp:1241-1258)
+__device__ __forceinline__ void d_norm_max(const DV &v, double *__restrict__ x, const double *__restrict__ cover, double *__restrict__ out)
 {
-    __shared__ double sm[256];
-    int tid = threadIdx.y * blockDim.x + threadIdx.x;
-    double acc = 0.0;
-    for (int j = blockIdx.y * blockDim.y + threadIdx.y; j < v.ny; j += gridDim.y * blockDim.y)
-        for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < v.nx; i += gridDim.x * blockDim.x) {
-            double val = x[cidx(v, i, j)];
-            if (ord == 0) acc = fmax(acc, fabs(val)); else acc += val * val;
-        }
-    sm[tid] = acc;
-    __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) {
-        if (tid < s) sm[tid] = ord == 0 ? fmax(sm[tid], sm[tid + s]) : sm[tid] + sm[tid + s];
-        __syncthreads();
-    }
-    if (tid == 0) partial[blockIdx.y * gridDim.x + blockIdx.x] = sm[0];
+    reduce_cells<RedMax>(v, out, [&](int i, int j, double (&a)[1]) {
+        const int idx = cidx(v, i, j);
+        if (cover && cover[idx] != 0.0) x[idx] = 0.0; else a[0] = fmax(a[0], fabs(x[idx]));
+    });
 }
-__global__ void k_norm_final(const double *__restrict__ partial, int n, int ord, double *__restrict__ out, HostSlot hs)
+// (a level, the boxes of a level: a level's own workgroups per box, its partial maxima one after the other)
+template <class T, bool COVER> __global__ __launch_bounds__(256) void k_norm_partial(T t, double *__restrict__ partial, int field)
 {
-    __shared__ double sm[256];
-    int tid = threadIdx.x;
-    double acc = 0.0;
-    for (int k = tid; k < n; k += 256) acc = ord == 0 ? fmax(acc, partial[k]) : acc + partial[k];
-    sm[tid] = acc;
-    __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) {
-        if (tid < s) sm[tid] = ord == 0 ? fmax(sm[tid], sm[tid + s]) : sm[tid] + sm[tid + s];
-        __syncthreads();
-    }
-    if (tid == 0) { out[0] = sm[0]; suhmo_publish(hs, sm[0]); }
+    d_norm_max(t.view(), t.field(field), COVER ? t.field(SUHMO_F_COVER) : nullptr, partial + t.slot((size_t)gridDim.x * gridDim.y) + plane_block());
+}
+__global__ __launch_bounds__(256) void k_norm2_partial(OnLevel t, double *__restrict__ partial, int field)
+{
+    const DV &v = t.view();
+    const double *__restrict__ x = t.field(field);
+    reduce_cells<RedSum>(v, partial + plane_block(), [&](int i, int j, double (&a)[1]) { const double val = x[cidx(v, i, j)]; a[0] += val * val; });
+}
+__global__ __launch_bounds__(256) void k_dot_partial(OnLevel t, double *__restrict__ partial, int fx, int fy)
+{
+    const DV &v = t.view();
+    const double *__restrict__ x = t.field(fx), *__restrict__ y = t.field(fy);
+    reduce_cells<RedSum>(v, partial + plane_block(), [&](int i, int j, double (&a)[1]) { const int idx = cidx(v, i, j); a[0] += x[idx] * y[idx]; });
 }
 // The 8-byte result of a reduction.  Synchronising the stream costs ~17 us of idle GPU per read-back on this platform (the copy
 // kernel, the interrupt, the wake-up); instead the reduction's last kernel stores the value and then, with a system-scope release,
@@ -700,31 +691,15 @@ int suhmo_reduce_finish(suhmo_level *L, hipStream_t st, int n, int op, double *o
     if (out2) *out2 = v[1];
     return 0;
 }
-__global__ __launch_bounds__(256) void k_dot_partial(DV v, const double *__restrict__ x, const double *__restrict__ y, double *__restrict__ partial)
-{
-    __shared__ double sm[256];
-    int tid = threadIdx.y * blockDim.x + threadIdx.x;
-    double acc = 0.0;
-    for (int j = blockIdx.y * blockDim.y + threadIdx.y; j < v.ny; j += gridDim.y * blockDim.y)
-        for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < v.nx; i += gridDim.x * blockDim.x) { int idx = cidx(v, i, j); acc += x[idx] * y[idx]; }
-    sm[tid] = acc;
-    __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) { if (tid < s) sm[tid] = sm[tid] + sm[tid + s]; __syncthreads(); }
-    if (tid == 0) partial[blockIdx.y * gridDim.x + blockIdx.x] = sm[0];
-}
 extern "C" int suhmo_level_dot(suhmo_level_t *L, int depth, int x, int y, double *out, suhmo_stream_t s)
 {
     SUHMO_TIME("AMRNonLinearPoissonOp::dotProduct");
     CHECK_DF(L, depth, x); CHECK_DF(L, depth, y); ARG(out);
     HIPCHK(hipSetDevice(L->device));
     hipStream_t st = (hipStream_t)s;
-    Depth &D = L->d[depth];
-    const double *px = suhmo_field(L, depth, x), *py = suhmo_field(L, depth, y);
-    if (!px || !py) { suhmo_set_error("field allocation failed"); return -2; }
-    dim3 grd(std::min((D.v.nx + 63) / 64, 32), std::min((D.v.ny + 3) / 4, 128));
-    hipLaunchKernelGGL(k_dot_partial, grd, BLK2D, 0, st, D.v, px, py, L->scratch + 2);
-    hipLaunchKernelGGL(k_norm_final, dim3(1), dim3(256), 0, st, L->scratch + 2, (int)(grd.x * grd.y), 2, L->scratch, suhmo_reduce_slot(L));
-    return suhmo_reduce_finish(L, st, 1, 1, out);
+    if (!suhmo_field(L, depth, x) || !suhmo_field(L, depth, y)) { suhmo_set_error("field allocation failed"); return -2; }
+    int rc = launch_reduction<RedSum>(k_dot_partial, on_level(L, depth), CAP_LEVEL, L->scratch + 2, L->scratch, suhmo_reduce_slot(L), st, x, y);
+    return rc ? rc : suhmo_reduce_finish(L, st, 1, 1, out);
 }
 extern "C" int suhmo_level_norm(suhmo_level_t *L, int depth, int field, int ord, double *out, suhmo_stream_t s)
 {
@@ -732,14 +707,14 @@ extern "C" int suhmo_level_norm(suhmo_level_t *L, int depth, int field, int ord,
     CHECK_DF(L, depth, field); ARG(out); ARG(ord == 0 || ord == 2);
     HIPCHK(hipSetDevice(L->device));
     hipStream_t st = (hipStream_t)s;
-    Depth &D = L->d[depth];
-    dim3 grd(std::min((D.v.nx + 63) / 64, 32), std::min((D.v.ny + 3) / 4, 128));
-    int np = grd.x * grd.y;
-    hipLaunchKernelGGL(k_norm_partial, grd, BLK2D, 0, st, D.v, suhmo_field(L, depth, field), ord, L->scratch + 2);
-    hipLaunchKernelGGL(k_norm_final, dim3(1), dim3(256), 0, st, L->scratch + 2, np, ord, L->scratch, suhmo_reduce_slot(L));
+    if (!suhmo_field(L, depth, field)) { suhmo_set_error("field allocation failed"); return -2; }
+    const OnLevel t = on_level(L, depth);
+    int rc = ord == 0 ? launch_reduction<RedMax>(k_norm_partial<OnLevel, false>, t, CAP_LEVEL, L->scratch + 2, L->scratch, suhmo_reduce_slot(L), st, field)
+                      : launch_reduction<RedSum>(k_norm2_partial, t, CAP_LEVEL, L->scratch + 2, L->scratch, suhmo_reduce_slot(L), st, field);
+    if (rc) return rc;
     double r = 0.0;
     // the reference's norm() reduces over the ranks (src/AMRNonLinearPoissonOp.cpp:1222-1264): MAX for the max norm, SUM of the squares for l2
-    { int rc = suhmo_reduce_finish(L, st, 1, ord == 0 ? 0 : 1, &r); if (rc) return rc; }
+    if ((rc = suhmo_reduce_finish(L, st, 1, ord == 0 ? 0 : 1, &r))) return rc;
     if (ord == 2) r = sqrt(r);
     *out = r;
     return 0;
@@ -764,9 +739,9 @@ int suhmo_level_residual_and_norm(suhmo_level *L, double *out, hipStream_t st)
 // stage of suhmo_level_norm alone
 int suhmo_level_norm_from_partials(suhmo_level *L, int np, double *out, hipStream_t st)
 {
-    hipLaunchKernelGGL(k_norm_final, dim3(1), dim3(256), 0, st, L->scratch + 2, np, 0, L->scratch, suhmo_reduce_slot(L));
     double r = 0.0;
-    int rc = suhmo_reduce_finish(L, st, 1, 0, &r); if (rc) return rc;
+    int rc = launch_final<RedMax>(one_list(L->scratch + 2, np), L->scratch, suhmo_reduce_slot(L), st);
+    if (rc || (rc = suhmo_reduce_finish(L, st, 1, 0, &r))) return rc;
     *out = r;
     return 0;
 }
@@ -816,20 +791,6 @@ __global__ void k_copy_between(OnBoxes src, OnBoxes dst, CopyPairs cp)
     int idx = cidx(v, i, j);
     for (int q = 0; q < cp.n; q++) fd.f[cp.fd[q]][idx] = fs.f[cp.fs[q]][idx];
 }
-__global__ __launch_bounds__(256) void k_norm_max_partial(OnBoxes t, int field, double *__restrict__ partial)
-{
-    __shared__ double sm[256];
-    const DV &v = t.view();
-    const double *__restrict__ x = t.fields().f[field];
-    int tid = threadIdx.y * blockDim.x + threadIdx.x;
-    double acc = 0.0;
-    for (int j = blockIdx.y * blockDim.y + threadIdx.y; j < v.ny; j += gridDim.y * blockDim.y)
-        for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < v.nx; i += gridDim.x * blockDim.x) acc = fmax(acc, fabs(x[cidx(v, i, j)]));
-    sm[tid] = acc;
-    __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) { if (tid < s) sm[tid] = fmax(sm[tid], sm[tid + s]); __syncthreads(); }
-    if (tid == 0) partial[t.slot((size_t)gridDim.x * gridDim.y) + blockIdx.y * gridDim.x + blockIdx.x] = sm[0];
-}
 // mode 0: LPHI, 1: RES, 3: both
 int launch_apply_boxes(const OnBoxes &t, bool has_alpha, int mode, hipStream_t st)
 {
@@ -846,69 +807,33 @@ int launch_copy_between(const OnBoxes &dst, const OnBoxes &src, const int *fd, c
     for (int q = 0; q < n; q++) { cp.fd[q] = fd[q]; cp.fs[q] = fs[q]; }
     return launch_over(k_copy_between, src, GHOSTED, st, dst, cp);
 }
-// AMRNorm over a hierarchy in ONE read-back: the first stages of level 0 (suhmo_level_norm_partials) and of every level of boxes
-// (suhmo_multi_norm_max_partials) leave their partial maxima where they always do; one launch takes the maximum of all the lists
+// AMRNorm over a hierarchy in ONE read-back: the first stages of level 0 (suhmo_level_norm_max_partials) and of every level of boxes
+// (suhmo_multi_norm_max_partials) leave their partial maxima where they always do; one second stage takes the maximum of all the lists
 // (a maximum does not care about the order) and publishes it
-constexpr int NORM_LISTS = 8;                        // levels of a hierarchy at most (suhmo_hier_create)
-struct NormLists { const double *p[NORM_LISTS]; int n[NORM_LISTS]; int cnt; };
-__global__ void k_norm_max_final_lists(NormLists nl, double *__restrict__ out, HostSlot hs)
+// (cover: the covered cells of the level are zeroed on the way, SUHMO_F_COVER)
+int suhmo_level_norm_max_partials(suhmo_level *L, int field, bool cover, const double **partials, int *np, hipStream_t st)
 {
-    __shared__ double sm[256];
-    int tid = threadIdx.x;
-    double acc = 0.0;
-    for (int q = 0; q < nl.cnt; q++)
-        for (int k = tid; k < nl.n[q]; k += 256) acc = fmax(acc, nl.p[q][k]);
-    sm[tid] = acc;
-    __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) { if (tid < s) sm[tid] = fmax(sm[tid], sm[tid + s]); __syncthreads(); }
-    if (tid == 0) { out[0] = sm[0]; suhmo_publish(hs, sm[0]); }
-}
-int suhmo_level_norm_max_partials(suhmo_level *L, int field, const double **partials, int *np, hipStream_t st)
-{
-    Depth &D = L->d[0];
-    dim3 grd(std::min((D.v.nx + 63) / 64, 32), std::min((D.v.ny + 3) / 4, 128));
-    hipLaunchKernelGGL(k_norm_partial, grd, BLK2D, 0, st, D.v, suhmo_field(L, 0, field), 0, L->scratch + 2);
-    HIPCHK(hipGetLastError());
-    *partials = L->scratch + 2; *np = grd.x * grd.y;
-    return 0;
+    if (!suhmo_field(L, 0, field) || (cover && !suhmo_field(L, 0, SUHMO_F_COVER))) { suhmo_set_error("field allocation failed"); return -2; }
+    *partials = L->scratch + 2;
+    return launch_partials(cover ? k_norm_partial<OnLevel, true> : k_norm_partial<OnLevel, false>, on_level(L, 0), CAP_LEVEL, L->scratch + 2, np, st, field);
 }
 int suhmo_multi_norm_max_partials(const suhmo_multi &m, int field, const double **partials, int *np, hipStream_t st)
 {
-    *partials = m.red; *np = 0;
-    const dim3 grd(std::min((m.maxnx + 63) / 64, 4), std::min((m.maxny + 3) / 4, 16));
-    *np = (int)(grd.x * grd.y) * std::max(m.nbox, 0);
-    return launch_grid(k_norm_max_partial, m.on(), grd, BLK2D, st, field, m.red);
+    *partials = m.red;
+    int rc = launch_partials(k_norm_partial<OnBoxes, false>, m.on(), CAP_BOX, m.red, np, st, field);
+    *np *= std::max(m.nbox, 0);
+    return rc;
 }
 int suhmo_norm_max_of_lists(suhmo_level *slot, const double *const *partials, const int *np, int cnt, double *out, hipStream_t st)
 {
-    if (cnt > NORM_LISTS) { suhmo_set_error("internal: norm over more lists than levels"); return -4; }
-    NormLists nl;
-    nl.cnt = cnt;
-    for (int q = 0; q < cnt; q++) { nl.p[q] = partials[q]; nl.n[q] = np[q]; }
-    hipLaunchKernelGGL(k_norm_max_final_lists, dim3(1), dim3(256), 0, st, nl, slot->scratch, suhmo_host_slot(slot));
-    HIPCHK(hipGetLastError());
-    return suhmo_readback(slot, st, out);
+    if (cnt > RED_LISTS) { suhmo_set_error("internal: norm over more lists than levels"); return -4; }
+    PartialLists pl;
+    pl.cnt = cnt;
+    for (int q = 0; q < cnt; q++) { pl.p[q] = partials[q]; pl.n[q] = np[q]; }
+    int rc = launch_final<RedMax>(pl, slot->scratch, suhmo_host_slot(slot), st);
+    return rc ? rc : suhmo_readback(slot, st, out);
 }
-// the composite norm's covered cells (AMRNorm zeroes them, src/AMRNonLinearPoissonOp.cpp:1241-1258) and its first stage in one pass
-__device__ __forceinline__ void d_norm_max_cover(const DV &v, double *__restrict__ x, const double *__restrict__ cover, double *__restrict__ partial, int slot)
-{
-    __shared__ double sm[256];
-    int tid = threadIdx.y * blockDim.x + threadIdx.x;
-    double acc = 0.0;
-    for (int j = blockIdx.y * blockDim.y + threadIdx.y; j < v.ny; j += gridDim.y * blockDim.y)
-        for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < v.nx; i += gridDim.x * blockDim.x) {
-            const int idx = cidx(v, i, j);
-            if (cover && cover[idx] != 0.0) x[idx] = 0.0; else acc = fmax(acc, fabs(x[idx]));
-        }
-    sm[tid] = acc;
-    __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) { if (tid < s) sm[tid] = fmax(sm[tid], sm[tid + s]); __syncthreads(); }
-    if (tid == 0) partial[slot] = sm[0];
-}
-__global__ __launch_bounds__(256) void k_norm_max_cover(DV v, double *__restrict__ x, const double *__restrict__ cover, double *__restrict__ partial)
-{
-    d_norm_max_cover(v, x, cover, partial, blockIdx.y * gridDim.x + blockIdx.x);
-}
+// several levels of boxes: lv.mode[q] != 0: the level has cells under a finer one (every level but the finest), they are zeroed on the way
 __global__ __launch_bounds__(256) void k_norm_max_cover_lv(suhmo_lvboxes lv, int field, double *__restrict__ partial)
 {
     int q, k;
@@ -916,69 +841,31 @@ __global__ __launch_bounds__(256) void k_norm_max_cover_lv(suhmo_lvboxes lv, int
     if (!lv_find(lv, q, k)) { if (threadIdx.x == 0 && threadIdx.y == 0) partial[slot] = 0.0; return; }
     const DV *dv = nullptr; const FP *fp = nullptr; int covered = 0;
     LV_PICK(lv, q, dv, dv); LV_PICK(lv, q, fp, fp); LV_PICK(lv, q, mode, covered);
-    d_norm_max_cover(dv[k], fp[k].f[field], covered ? fp[k].f[SUHMO_F_COVER] : nullptr, partial, slot);
+    d_norm_max(dv[k], fp[k].f[field], covered ? fp[k].f[SUHMO_F_COVER] : nullptr, partial + slot);
 }
-// lv.mode[q] != 0: the level has cells under a finer one (every level but the finest)
 int suhmo_levels_norm_max_cover_partials(const suhmo_lvboxes &lv, int field, double *partial, int *np, hipStream_t st)
 {
     int nz = 0;
     for (int q = 0; q < lv.n; q++) nz += lv.nbox[q];
     *np = 0;
     if (nz <= 0) return 0;
-    dim3 grd(std::min((lv.maxnx + 63) / 64, 4), std::min((lv.maxny + 3) / 4, 16), nz);
+    dim3 grd = reduce_grid(lv.maxnx, lv.maxny, CAP_BOX);
+    grd.z = nz;
     hipLaunchKernelGGL(k_norm_max_cover_lv, grd, BLK2D, 0, st, lv, field, partial);
     HIPCHK(hipGetLastError());
     *np = (int)(grd.x * grd.y * grd.z);
     return 0;
 }
-int suhmo_level_norm_max_cover_partials(suhmo_level *L, int field, const double **partials, int *np, hipStream_t st)
-{
-    Depth &D = L->d[0];
-    double *x = suhmo_field(L, 0, field), *cover = suhmo_field(L, 0, SUHMO_F_COVER);
-    if (!x || !cover) { suhmo_set_error("field allocation failed"); return -2; }
-    dim3 grd(std::min((D.v.nx + 63) / 64, 32), std::min((D.v.ny + 3) / 4, 128));
-    hipLaunchKernelGGL(k_norm_max_cover, grd, BLK2D, 0, st, D.v, x, cover, L->scratch + 2);
-    HIPCHK(hipGetLastError());
-    *partials = L->scratch + 2; *np = grd.x * grd.y;
-    return 0;
-}
-int suhmo_multi_norm_max(const suhmo_multi &m, suhmo_level *slot, int field, double *out, hipStream_t st)
-{
-    const double *partials; int np;
-    if (m.nbox <= 0) { *out = 0.0; return 0; }
-    int rc = suhmo_multi_norm_max_partials(m, field, &partials, &np, st); if (rc) return rc;
-    hipLaunchKernelGGL(k_norm_final, dim3(1), dim3(256), 0, st, partials, np, 0, slot->scratch, suhmo_host_slot(slot));
-    HIPCHK(hipGetLastError());
-    return suhmo_readback(slot, st, out);
-}
 
 
 // ------------------------------------------------------------------ every active member of a batch of whole levels in one launch (suhmo_batch.hip)
 int launch_fas_coarse_rhs(const OnMembers &t, bool has_alpha, hipStream_t st) { return launch_apply<2>(t, has_alpha, 0, st); }
-// second stage of the members' max norms: a wave per member (the maximum is exact whatever the order), every value stored into the pinned
-// slot of its member, then ONE sequence number for all of them
-__global__ __launch_bounds__(256) void k_norm_final_members(BatchSel sel, const double *__restrict__ partial, int np, double *__restrict__ slot,
-                                                      unsigned long long *flag, unsigned long long seq)
-{
-    const int lane = threadIdx.x & 63;
-    for (int z = threadIdx.x >> 6; z < sel.n; z += 4) {
-        const int k = sel.m[z];
-        double acc = 0.0;
-        for (int q = lane; q < np; q += 64) acc = fmax(acc, partial[(size_t)k * np + q]);
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) acc = fmax(acc, __shfl_xor(acc, o));
-        if (lane == 0) slot[k] = acc;
-    }
-    __threadfence_system();
-    __syncthreads();
-    if (threadIdx.x == 0) __hip_atomic_store(flag, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-}
 size_t suhmo_batch_residual_partials(const OnMembers &t) { const dim3 g = grid2d(t.nx(), t.ny()); return (size_t)g.x * g.y; }
 int launch_residual_norm_members(const OnMembers &t, bool has_alpha, double *partial, double *slot, unsigned long long *flag, unsigned long long seq, hipStream_t st)
 {
     if (t.count() <= 0) return 0;
     int rc = launch_residual_norm(t, has_alpha, partial, st); if (rc) return rc;
-    hipLaunchKernelGGL(k_norm_final_members, dim3(1), dim3(256), 0, st, t.sel, partial, (int)suhmo_batch_residual_partials(t), slot, flag, seq);
+    hipLaunchKernelGGL(k_norm_final_members<RedMax>, dim3(1), dim3(256), 0, st, t.sel, partial, (int)suhmo_batch_residual_partials(t), slot, flag, seq);
     HIPCHK(hipGetLastError());
     return 0;
 }

@@ -16,6 +16,7 @@
 // integrand, no data), so the result does not depend on the partition bit for bit.
 #include "suhmo_hier_int.h"
 #include "suhmo_batch.h"
+#include "suhmo_reduce.h"
 #include <cmath>
 
 using namespace hier;
@@ -205,79 +206,29 @@ static int exchange1(suhmo_level *L, int f, hipStream_t st) { return suhmo_excha
 // Both numbers of the Picard test in one pass and one read-back: max h and max |h_lagged - h|.  The reference's
 // max |(h_lagged - h) / maxHead| is the second divided by |maxHead| afterwards: a correctly rounded division by a fixed
 // divisor is monotone and sign-symmetric, so the maximum of the quotients is the quotient of the maximum, bit for bit.
-__device__ __forceinline__ void d_picard2_partial(const DV &v, const double *__restrict__ h, const double *__restrict__ hl,
-                                                  double *__restrict__ partial, const Excl &ex, const double *__restrict__ cover)
-{
-    __shared__ double sm0[256], sm1[256];
-    int tid = threadIdx.y * blockDim.x + threadIdx.x;
-    double a0 = -1.0e300, a1 = 0.0;
-    for (int j = blockIdx.y * blockDim.y + threadIdx.y; j < v.ny; j += gridDim.y * blockDim.y)
-        for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < v.nx; i += gridDim.x * blockDim.x) {
-            if (i >= ex.i0 && i < ex.i1 && j >= ex.j0 && j < ex.j1) continue;
-            int idx = cidx(v, i, j);
-            if (cover && cover[idx] != 0.0) continue;          // hierarchy of box unions: SUHMO_F_COVER
-            a0 = fmax(a0, h[idx]);
-            a1 = fmax(a1, fabs(hl[idx] - h[idx]));
-        }
-    sm0[tid] = a0; sm1[tid] = a1;
-    __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) {
-        if (tid < s) { sm0[tid] = fmax(sm0[tid], sm0[tid + s]); sm1[tid] = fmax(sm1[tid], sm1[tid + s]); }
-        __syncthreads();
-    }
-    if (tid == 0) { int b = blockIdx.y * gridDim.x + blockIdx.x; partial[2 * b] = sm0[0]; partial[2 * b + 1] = sm1[0]; }
-}
+// First stage (RedMax2 of suhmo_reduce.h): pairs of partial maxima, one per workgroup.
 // (the boxes of a level, the members of an ensemble: a level's own workgroups per box / member, its partial maxima one after the other)
 template <class T> __global__ __launch_bounds__(256) void k_picard2_partial(T t, double *__restrict__ partial, Excl ex, int use_cover)
 {
+    const DV &v = t.view();
     const FP &fp = t.fields();
-    d_picard2_partial(t.view(), fp.f[SUHMO_F_PHI], fp.f[SUHMO_F_HLAG], partial + 2 * t.slot((size_t)gridDim.x * gridDim.y), ex, use_cover ? fp.f[SUHMO_F_COVER] : nullptr);
-}
-// first stage over the cells of a target with at most gx x gy workgroups each; *np: the pairs of partial maxima it leaves
-template <class T> static int launch_picard2_partial(const T &t, int gx, int gy, double *partial, Excl ex, bool covered, int *np, hipStream_t st)
-{
-    const dim3 grd(std::min((t.nx() + 63) / 64, gx), std::min((t.ny() + 3) / 4, gy));
-    *np = (int)(grd.x * grd.y);
-    return launch_grid(k_picard2_partial<T>, t, grd, BLK2D, st, partial, ex, (int)covered);
-}
-// second stage for all of them: a wave per member (maxima: exact in any order), both values into the member's pinned slots, then ONE sequence number
-__global__ __launch_bounds__(256) void k_max2_final_members(BatchSel sel, const double *__restrict__ partial, int np, double *__restrict__ slot,
-                                                      unsigned long long *flag, unsigned long long seq)
-{
-    const int lane = threadIdx.x & 63;
-    for (int z = threadIdx.x >> 6; z < sel.n; z += 4) {
-        const int k = sel.m[z];
-        double a0 = -1.0e300, a1 = 0.0;
-        for (int q = lane; q < np; q += 64) { a0 = fmax(a0, partial[((size_t)k * np + q) * 2]); a1 = fmax(a1, partial[((size_t)k * np + q) * 2 + 1]); }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) { a0 = fmax(a0, __shfl_xor(a0, o)); a1 = fmax(a1, __shfl_xor(a1, o)); }
-        if (lane == 0) { slot[2 * k] = a0; slot[2 * k + 1] = a1; }
-    }
-    __threadfence_system();
-    __syncthreads();
-    if (threadIdx.x == 0) __hip_atomic_store(flag, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-}
-__global__ void k_max2_final(const double *__restrict__ partial, int n, double *__restrict__ out, HostSlot hs)
-{
-    __shared__ double sm0[256], sm1[256];
-    int tid = threadIdx.x;
-    double a0 = -1.0e300, a1 = 0.0;
-    for (int k = tid; k < n; k += 256) { a0 = fmax(a0, partial[2 * k]); a1 = fmax(a1, partial[2 * k + 1]); }
-    sm0[tid] = a0; sm1[tid] = a1;
-    __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) {
-        if (tid < s) { sm0[tid] = fmax(sm0[tid], sm0[tid + s]); sm1[tid] = fmax(sm1[tid], sm1[tid + s]); }
-        __syncthreads();
-    }
-    if (tid == 0) { out[0] = sm0[0]; out[1] = sm1[0]; if (hs.val) hs.val[1] = sm1[0]; suhmo_publish(hs, sm0[0]); }
+    const double *__restrict__ h = fp.f[SUHMO_F_PHI], *__restrict__ hl = fp.f[SUHMO_F_HLAG];
+    const double *__restrict__ cover = use_cover ? fp.f[SUHMO_F_COVER] : nullptr;     // hierarchy of box unions
+    reduce_cells<RedMax2>(v, partial + 2 * (t.slot((size_t)gridDim.x * gridDim.y) + plane_block()), [&](int i, int j, double (&a)[2]) {
+        if (i >= ex.i0 && i < ex.i1 && j >= ex.j0 && j < ex.j1) return;
+        const int idx = cidx(v, i, j);
+        if (cover && cover[idx] != 0.0) return;
+        a[0] = fmax(a[0], h[idx]);
+        a[1] = fmax(a[1], fabs(hl[idx] - h[idx]));
+    });
 }
 // max h and max |hl - h| over the level's cells (local to the rank)
 // over_ranks: the maxima over all ranks of the level's strip partition (computeMax; one MAX all-reduce of both values)
 static int picard_maxima(suhmo_level *L, double *maxh, double *maxd, hipStream_t st, Excl ex = Excl{0, 0, 0, 0}, bool covered = false, bool over_ranks = false)
 {
-    int np, rc = launch_picard2_partial(on_level(L, 0), 32, 128, L->scratch + 2, ex, covered, &np, st);
+    int rc = launch_reduction<RedMax2>(k_picard2_partial<OnLevel>, on_level(L, 0), CAP_LEVEL, L->scratch + 2, L->scratch,
+                                       over_ranks ? suhmo_reduce_slot(L) : suhmo_host_slot(L), st, ex, (int)covered);
     if (rc) return rc;
-    hipLaunchKernelGGL(k_max2_final, dim3(1), dim3(256), 0, st, L->scratch + 2, np, L->scratch, over_ranks ? suhmo_reduce_slot(L) : suhmo_host_slot(L));
     if (over_ranks) return suhmo_reduce_finish(L, st, 2, 0, maxh, maxd);
     return suhmo_readback(L, st, maxh, maxd);
 }
@@ -647,9 +598,9 @@ struct Batch {
     int picard_maxima(double *maxh, double *maxd)
     {
         const BatchStep p = suhmo_batch_step(B, true);
-        int np, rc = launch_picard2_partial(on_members(p.t, p.sel, *p.v), 32, 128, p.partial, Excl{0, 0, 0, 0}, false, &np, st);   // (the workgroups of picard_maxima, per member)
+        int np, rc = launch_partials(k_picard2_partial<OnMembers>, on_members(p.t, p.sel, *p.v), CAP_LEVEL, p.partial, &np, st, Excl{0, 0, 0, 0}, 0);   // (the workgroups of picard_maxima, per member)
         if (rc) return rc;
-        hipLaunchKernelGGL(k_max2_final_members, dim3(1), dim3(256), 0, st, p.sel, p.partial, np, p.slot, p.flag, p.seq);
+        hipLaunchKernelGGL(k_norm_final_members<RedMax2>, dim3(1), dim3(256), 0, st, p.sel, p.partial, np, p.slot, p.flag, p.seq);
         HIPCHK(hipGetLastError());
         suhmo_batch_count(B, 2);
         return suhmo_batch_step_read(B, st, maxh, maxd);
@@ -897,10 +848,7 @@ int hier_picard_maxima(suhmo_hier *H, int l, bool covered, double *maxh, double 
     if ((rc = multi_of(H, l, st, m))) return rc;
     *maxh = -1.0e300; *maxd = 0.0;
     if (m.nbox > 0) {
-        int np;
-        if ((rc = launch_picard2_partial(m.on(), 4, 8, m.red, Excl{0, 0, 0, 0}, covered, &np, st))) return rc;     // 2 values per block: 64 nbox doubles
-        hipLaunchKernelGGL(k_max2_final, dim3(1), dim3(256), 0, st, m.red, np * m.nbox, slot->scratch, suhmo_host_slot(slot));
-        HIPCHK(hipGetLastError());
+        if ((rc = launch_reduction<RedMax2>(k_picard2_partial<OnBoxes>, m.on(), CAP_BOX_PAIRS, m.red, slot->scratch, suhmo_host_slot(slot), st, Excl{0, 0, 0, 0}, (int)covered))) return rc;
         if ((rc = suhmo_readback(slot, st, maxh, maxd))) return rc;
     }
     if (H->part) {                                            // owner computes: computeMax over the ranks
