@@ -130,6 +130,10 @@ int suhmo_level_num_depths(const suhmo_level_t *L);
  * pre-smoothing launch of depth 0 forms the face coefficients from the head as it loads it and stores them (same bits), AverageOperator
  * follows that launch.  0, or any of the conditions not met: the fused WFlx_level kernel as before.  Read-only: bcoef_in_relax_launches
  * (graph replays included; such a launch also counts as a bcoef_unmasked_launch and a relax_unmasked_launch).
+ * avg_overlap (default 1, env SUHMO_AVG_OVERLAP): in such a cycle, when it runs as plain launches (not as a captured graph or the eager first
+ * use of a level whose cycles are captured, not while profiling), AverageOperator runs on a side stream of the level beside the next depth-0
+ * launch, which reads none of the coarse faces; the cycle's stream waits for it before its first read of a coarse face and before the call
+ * returns, so the caller sees one stream as before.  0: on the cycle's stream.  Same bits either way.  Read-only: avg_overlap_launches.
  * Not a kernel-selection knob (it changes the bits): bottom_solver (default 0: the cycle's bottom is its numBottom relaxes; 1: followed by
  * Chombo's RelaxSolver as the reference configures it, src/AmrHydro.cpp:623,628,726,733-735 -- up to 40 rounds of relax(2), ended by an l2
  * residual below 1e-6 x its first value or reduced by less than 10 %).  It reaches the level's agglomerated copy and its gap-height operator;

@@ -568,7 +568,10 @@ template <class T> __global__ void k_average_faces(T c, T f, int r)      // (fac
 // r = 2^d collinear fine faces divided by r; the running sum of the first r/2 faces of a group IS
 // the (unscaled) depth d-1 sum, so one walk over 2^(nd-1) faces yields every depth bit for bit.
 struct AvgOut { double *bx[SUHMO_MAXDEPTH], *by[SUHMO_MAXDEPTH]; int P[SUHMO_MAXDEPTH]; int gy[SUHMO_MAXDEPTH]; };
-// x-faces: thread = (even fine column i, block of R = 2^(nd-1) rows); walks the rows
+#define AVG_ALL_MAXDEPTH 7     // depths one pass serves (avg_faces_one_pass): a block of 2^(nd-1) rows per thread of the x-face walker
+// x-faces: thread = (even fine column i, block of R = 2^(nd-1) rows); walks the rows.  U: loads a thread keeps in flight (8; 4 on a level,
+// whose launch has to fit beside another kernel's waves: suhmo_average_operator_all) -- the sums and their order do not depend on it
+template <int U>
 __device__ __forceinline__ void d_average_faces_x_all(const DV &vf, const double *__restrict__ bxf, const AvgOut &o, int nd, int bix, int biy, int tx, int ty)
 {
     const int R = 1 << (nd - 1);
@@ -576,11 +579,11 @@ __device__ __forceinline__ void d_average_faces_x_all(const DV &vf, const double
     int jb = biy * 4 + ty;
     int i = 2 * ih;
     if (i > vf.nx || jb * R >= vf.ny) return;
-    double sum[SUHMO_MAXDEPTH];
+    double sum[AVG_ALL_MAXDEPTH];
     const int base = cidx(vf, i, jb * R);
     auto take = [&](int k, double f) {
 #pragma unroll
-        for (int d = 1; d < SUHMO_MAXDEPTH; d++) {
+        for (int d = 1; d < AVG_ALL_MAXDEPTH; d++) {     // (unrolled: one running sum per depth the pass can have, not per depth a level can)
             if (d >= nd) break;
             const int r = 1 << d;
             if ((i & (r - 1)) != 0) break;               // column not on depth d's face grid (nor deeper)
@@ -590,35 +593,35 @@ __device__ __forceinline__ void d_average_faces_x_all(const DV &vf, const double
         }
     };
     if (R >= 8) {
-        for (int k0 = 0; k0 < R; k0 += 8) {              // 8 independent loads in flight, then the (sequential) sums
-            double f8[8];
+        for (int k0 = 0; k0 < R; k0 += U) {              // U independent loads in flight, then the (sequential) sums
+            double fu[U];
 #pragma unroll
-            for (int u = 0; u < 8; u++) f8[u] = bxf[base + (k0 + u) * vf.P];
+            for (int u = 0; u < U; u++) fu[u] = bxf[base + (k0 + u) * vf.P];
 #pragma unroll
-            for (int u = 0; u < 8; u++) take(k0 + u, f8[u]);
+            for (int u = 0; u < U; u++) take(k0 + u, fu[u]);
         }
     } else {
         for (int k = 0; k < R; k++) take(k, bxf[base + k * vf.P]);
     }
 }
 // y-faces: one wave walks 64 consecutive columns of YR even fine rows (their loads in flight together); lane l = column
-#define AVG_YR 8
+template <int YR>
 __device__ __forceinline__ void d_average_faces_y_all(const DV &vf, const double *__restrict__ byf, const AvgOut &o, int nd, int bix, int biy, int tid)
 {
     const int lane = tid & 63;
     const int i = bix * 64 + lane;
-    const int jb = 2 * AVG_YR * (biy * 4 + (tid >> 6));
+    const int jb = 2 * YR * (biy * 4 + (tid >> 6));
     if (jb > vf.ny) return;                               // whole wave leaves together
-    double fr[AVG_YR];
+    double fr[YR];
 #pragma unroll
-    for (int q = 0; q < AVG_YR; q++) {
+    for (int q = 0; q < YR; q++) {
         const int j = jb + 2 * q;
         fr[q] = (i < vf.nx && j <= vf.ny) ? byf[cidx(vf, i, j)] : 0.0;
     }
 #pragma unroll
-    for (int q = 0; q < AVG_YR; q++) {
+    for (int q = 0; q < YR; q++) {
         const int j = jb + 2 * q;
-        if (j > vf.ny) break;                             // uniform
+        if (j > vf.ny) break;                            // uniform
         const double f = fr[q];
         double run = 0.0 + f;                             // depth-0 "sum" of a single face
         for (int d = 1; d < nd; d++) {
@@ -636,11 +639,12 @@ __device__ __forceinline__ void d_average_faces_y_all(const DV &vf, const double
 
 // both directions in ONE launch of 256-thread workgroups: the first gxx * gxy of them are the x-face walkers (64 x 4 threads), the rest the
 // y-face walkers (four waves): nothing of one reads what the other writes
+template <int U>
 __device__ __forceinline__ void d_average_faces_all(const DV &vf, const double *__restrict__ bxf, const double *__restrict__ byf, const AvgOut &o, int nd, int gxx, int gxy, int gyx)
 {
     const int b = blockIdx.x, nbx = gxx * gxy;
-    if (b < nbx) d_average_faces_x_all(vf, bxf, o, nd, b % gxx, b / gxx, threadIdx.x & 63, threadIdx.x >> 6);
-    else d_average_faces_y_all(vf, byf, o, nd, (b - nbx) % gyx, (b - nbx) / gyx, threadIdx.x);
+    if (b < nbx) d_average_faces_x_all<U>(vf, bxf, o, nd, b % gxx, b / gxx, threadIdx.x & 63, threadIdx.x >> 6);
+    else d_average_faces_y_all<U>(vf, byf, o, nd, (b - nbx) % gyx, (b - nbx) / gyx, threadIdx.x);
 }
 // the pointers of all depths beside the target (`A`): by value for a level, a device row per member of an ensemble (row_of)
 struct AvgAll;
@@ -649,11 +653,11 @@ __device__ __forceinline__ const AvgOut &avg_out(const AvgOut &o) { return o; }
 __device__ __forceinline__ const AvgOut &avg_out(const BatchAvg &b);
 __device__ __forceinline__ const AvgAll &avg_all(const AvgAll &a) { return a; }
 __device__ __forceinline__ const AvgAll &avg_all(const BatchAvg &b);
-template <class T, class A>
+template <class T, class A, int U>
 __global__ __launch_bounds__(256) void k_average_faces_all(T t, A av, int nd, int gxx, int gxy, int gyx)
 {
     const FP &fp = t.fields();
-    d_average_faces_all(t.view(), fp.f[SUHMO_F_BX], fp.f[SUHMO_F_BY], avg_out(row_of(t, av)), nd, gxx, gxy, gyx);
+    d_average_faces_all<U>(t.view(), fp.f[SUHMO_F_BX], fp.f[SUHMO_F_BY], avg_out(row_of(t, av)), nd, gxx, gxy, gyx);
 }
 
 template <class T> int launch_average_faces(const T &f, const T &c, int r, hipStream_t st) { return launch_over(k_average_faces<T>, c, FACES, st, f, r); }
@@ -671,13 +675,15 @@ static void fill_avg_out(const suhmo_level *L, int nd, AvgOut &o)
 {
     for (int d = 0; d < nd; d++) { o.bx[d] = L->d[d].fp.f[SUHMO_F_BX]; o.by[d] = L->d[d].fp.f[SUHMO_F_BY]; o.P[d] = L->d[d].v.P; o.gy[d] = L->d[d].v.gy; }
 }
-static void avg_faces_grids(const DV &v, int nd, dim3 &gx, dim3 &gy)      // workgroups of the x-face and of the y-face walkers
+#define AVG_U_BATCH 8     // loads in flight per thread of k_average_faces_all: an ensemble's launch ...
+#define AVG_U_LEVEL 4     // ... and a level's, which at 36 VGPRs fits the 48 that two waves of the restricting relaxation leave on a SIMD
+static void avg_faces_grids(const DV &v, int nd, int U, dim3 &gx, dim3 &gy)      // workgroups of the x-face and of the y-face walkers
 {
     const int R = 1 << (nd - 1);
     gx = dim3((v.nx / 2 + 1 + 63) / 64, (v.ny / R + 3) / 4);
-    gy = dim3((v.nx + 63) / 64, ((v.ny / 2 + 1 + AVG_YR - 1) / AVG_YR + 3) / 4);
+    gy = dim3((v.nx + 63) / 64, ((v.ny / 2 + 1 + U - 1) / U + 3) / 4);
 }
-static bool avg_faces_one_pass(const DV &v, int nd) { return !(nd > 7 || v.nx % (1 << (nd - 1)) || v.ny % (1 << (nd - 1))); }
+static bool avg_faces_one_pass(const DV &v, int nd) { return !(nd > AVG_ALL_MAXDEPTH || v.nx % (1 << (nd - 1)) || v.ny % (1 << (nd - 1))); }
 int suhmo_average_operator_all(suhmo_level *L, int nd, hipStream_t st)
 {
     Depth &F = L->d[0];
@@ -692,8 +698,8 @@ int suhmo_average_operator_all(suhmo_level *L, int nd, hipStream_t st)
     AvgOut o;
     fill_avg_out(L, nd, o);
     dim3 gx, gy;
-    avg_faces_grids(F.v, nd, gx, gy);
-    { int rc = launch_grid(k_average_faces_all<OnLevel, AvgOut>, on_level(L, 0), dim3(gx.x * gx.y + gy.x * gy.y), dim3(256), st, o, nd, (int)gx.x, (int)gx.y, (int)gy.x); if (rc) return rc; }
+    avg_faces_grids(F.v, nd, AVG_U_LEVEL, gx, gy);
+    { int rc = launch_grid(k_average_faces_all<OnLevel, AvgOut, AVG_U_LEVEL>, on_level(L, 0), dim3(gx.x * gx.y + gy.x * gy.y), dim3(256), st, o, nd, (int)gx.x, (int)gx.y, (int)gy.x); if (rc) return rc; }
     // strips: the coarse face coefficients of all depths travel as one message group when the transport can batch
     if (L->ipc) { int rc = suhmo_ipc_batch(L, 1, st); if (rc) return rc; }
     else if (L->ex_begin && L->ex) { int rc = L->ex_begin(L->user); if (rc) return rc; }
@@ -910,9 +916,9 @@ int suhmo_batch_average_operator_all(const OnMembers *t, const void *avg, int nd
         return 0;
     }
     dim3 gx, gy;
-    avg_faces_grids(v, nd, gx, gy);
+    avg_faces_grids(v, nd, AVG_U_BATCH, gx, gy);
     *launches = 1;
-    return launch_grid(k_average_faces_all<OnMembers, BatchAvgRows>, t[0], dim3(gx.x * gx.y + gy.x * gy.y), dim3(256), st, (const BatchAvg *)avg, nd, (int)gx.x, (int)gx.y, (int)gy.x);
+    return launch_grid(k_average_faces_all<OnMembers, BatchAvgRows, AVG_U_BATCH>, t[0], dim3(gx.x * gx.y + gy.x * gy.y), dim3(256), st, (const BatchAvg *)avg, nd, (int)gx.x, (int)gx.y, (int)gy.x);
 }
 // MGnewOp's coefficient averages of every depth > 0 and their ghosts (suhmo_build_mg_coefficients without the faces): two launches
 int suhmo_batch_build_mg_coefficients(const OnMembers &t0, const void *avg, const suhmo_level *L0, hipStream_t st, int *launches)

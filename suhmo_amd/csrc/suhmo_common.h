@@ -222,6 +222,11 @@ struct suhmo_level {
     // UpdateOperator of the V-cycle inside the first pre-smoothing launch of depth 0 (suhmo_gsrb.hip, BCF; option bcoef_in_relax, default 1);
     // bcoef_nd: the depths AverageOperator refreshes right behind that launch; read-only option bcoef_in_relax_launches counts them
     int bcoef_in_relax, bcoef_nd; long bcoef_in_relax_count;
+    // AverageOperator behind that launch on a side stream, beside the next launch of depth 0, which reads none of its output (option avg_overlap,
+    // default 1; suhmo_gsrb_can_overlap_avg); avg_fork: this cycle may fork (vcycle_body); avg_flying: the coarse faces are in flight on
+    // astream -- suhmo_avg_join makes a stream wait for them; read-only option avg_overlap_launches counts the forks
+    int avg_overlap, avg_fork, avg_flying; long avg_overlap_count;
+    hipStream_t astream; hipEvent_t aev[2];
     long frhs_stream, frhs_tile;   // launches that formed a coarse depth's FAS right-hand side themselves (streaming / tile kernel); read-only options
     // what the relaxation scheduler did on a rank strip (suhmo_launch_gsrb, suhmo_prolong_with_halo); read-only options strip_*
     long strip_tile, strip_tile_rst, strip_tile_shallow, strip_colour, strip_stream, strip_stream_rst, strip_prolong_unfused;
@@ -344,6 +349,9 @@ int suhmo_level_residual_and_norm(suhmo_level *L, double *out, hipStream_t st); 
 int suhmo_level_norm_from_partials(suhmo_level *L, int np, double *out, hipStream_t st);   // suhmo_ops.hip
 bool suhmo_gsrb_can_fuse_rhs(suhmo_level *L, int depth, int sweeps, bool rhs_local = false);               // suhmo_gsrb.hip
 bool suhmo_gsrb_can_fuse_bcoef(suhmo_level *L, int sweeps);   // suhmo_gsrb.hip: the first of `sweeps` pre-smoothing sweeps of depth 0 can form the faces
+bool suhmo_gsrb_can_overlap_avg(const suhmo_level *L);        // suhmo_gsrb.hip: ... and AverageOperator behind it may run on the level's side stream
+int suhmo_avg_join(suhmo_level *L, hipStream_t st);           // suhmo_gsrb.hip: st waits for the coarse faces if they are in flight there (else nothing)
+void suhmo_avg_release(suhmo_level *L);                       // suhmo_gsrb.hip: the side stream and its events
 int suhmo_launch_gsrb(suhmo_level *L, int depth, int sweeps, int tail, hipStream_t st, int *restricted = nullptr);   // suhmo_gsrb.hip; tail = halo
                                                     // rows worth keeping valid at exit; restricted: see there
 void suhmo_level_drop_graphs(suhmo_level *L);                                     // suhmo_fas.hip

@@ -67,6 +67,8 @@ static int fas_cycle(suhmo_level *L, int dep, const suhmo_solver_params_t *sp, i
                                                                                   //  row, the prolongation below the rest)
     if (!restricted && (rc = suhmo_restrict_both(L, dep, (hipStream_t)s))) return rc;   // RES[dep+1] and PHI[dep+1] = R(phi); the fused
                                                                                   //  relaxation may have written them already
+    // from here on the cycle reads the coarse depths' faces (the right-hand side of depth dep + 1 is the first to): they have arrived
+    if ((rc = suhmo_avg_join(L, (hipStream_t)s))) return rc;
     if (L->agg && dep + 1 == L->agg_depth) {
         // rank strips, agglomerated depths (suhmo_agg.hip): R phi and RES of every rank's rows -> the whole-level copy A every rank
         // holds; A forms its right-hand side and runs the rest of the cycle without a message; this rank's rows and halo rows of
@@ -115,15 +117,20 @@ static int fas_cycle(suhmo_level *L, int dep, const suhmo_solver_params_t *sp, i
     return relax(L, dep, S, tail_post, s, dep == 0);                              // post-smooth
 }
 
-static int vcycle_body(suhmo_level *L, const suhmo_solver_params_t *sp, int nd, suhmo_stream_t s)
+// eager: the cycle runs as launches on the caller's stream and is not one that a graph will replay (neither a capture nor the eager first
+// use of a level whose cycles are captured): its AverageOperator may run beside the restricting launch of depth 0 (suhmo_gsrb_can_overlap_avg)
+static int vcycle_body(suhmo_level *L, const suhmo_solver_params_t *sp, int nd, suhmo_stream_t s, bool eager)
 {
     int rc;
+    L->avg_fork = 0;
     if (sp->bcoeff_otf && nd > 1 && suhmo_gsrb_can_fuse_bcoef(L, sp->num_smooth)) {
         // UpdateOperator rides on the first pre-smoothing launch of depth 0 (suhmo_gsrb.hip, BCF), AverageOperator follows that launch.  The
         // mask is known clean here: no report, no scan (what suhmo_level_update_operator leaves behind in that state)
         L->d[0].bcoef_pending = 1; L->bcoef_nd = nd;
         L->maskflag_epoch = 0; L->mask_reported = 0;
+        L->avg_fork = eager && suhmo_gsrb_can_overlap_avg(L);
     } else if (sp->bcoeff_otf) {
+        if ((rc = suhmo_avg_join(L, (hipStream_t)s))) return rc;                   // (nothing is in flight between cycles: the faces are rewritten here)
         L->faces_deferred = 1;              // rank strips: the halo rows of the depth-0 faces travel with those of the coarse depths, one message
         rc = suhmo_level_update_operator(L, 0, s);
         if (rc) { L->faces_deferred = 0; return rc; }
@@ -131,6 +138,8 @@ static int vcycle_body(suhmo_level *L, const suhmo_solver_params_t *sp, int nd, 
         if ((rc = suhmo_average_operator_all(L, nd, (hipStream_t)s))) return rc;   // AverageOperator on every depth > 0
     } else L->maskflag_epoch = 0;
     rc = fas_cycle(L, 0, sp, nd, s);
+    L->avg_fork = 0;
+    { int rj = suhmo_avg_join(L, (hipStream_t)s); if (!rc) rc = rj; }              // no cycle returns with the fork open, whichever way it ends
     if (L->d[0].bcoef_pending) {            // (no launch took it up: the predicate and the launcher disagree)
         L->d[0].bcoef_pending = 0;
         if (!rc) { suhmo_set_error("internal: no relaxation launch formed the face coefficients"); rc = -4; }
@@ -152,6 +161,7 @@ void suhmo_level_drop_graphs(suhmo_level *L)
     for (VGraph &g : L->vgraphs) if (g.exec) (void)hipGraphExecDestroy(g.exec);
     L->vgraphs.clear();
     if (L->gstream) { (void)hipStreamDestroy(L->gstream); L->gstream = nullptr; }
+    suhmo_avg_release(L);                   // (the side stream of the eager cycles' AverageOperator goes with it; both come back on first use)
 }
 static int vcycle_graph(suhmo_level *L, const suhmo_solver_params_t *sp, int nd, suhmo_stream_t s, bool &done)
 {
@@ -208,7 +218,7 @@ static int vcycle_graph(suhmo_level *L, const suhmo_solver_params_t *sp, int nd,
     int rc = 0;
     if (e == hipSuccess) {
         L->mask_capturing = 1; L->mask_scan_captured = 0;
-        rc = vcycle_body(L, sp, nd, (suhmo_stream_t)L->gstream);
+        rc = vcycle_body(L, sp, nd, (suhmo_stream_t)L->gstream, false);
         L->mask_capturing = 0; g.has_scan = L->mask_scan_captured;
         e = hipStreamEndCapture(L->gstream, &graph);
     }
@@ -249,12 +259,13 @@ extern "C" int suhmo_level_vcycle(suhmo_level_t *L, const suhmo_solver_params_t 
     // (a bottom solved by the host loop decides on the host after every iteration: not capturable)
     const bool host_bottom = L->bottom_solver && !suhmo_bottom_one_launch(L, nd - 1);
     suhmo_mask_poll(L);                     // (before a graph is chosen: the answer of a scan of the ice mask, if it is there)
-    if (L->graph_max_cells > 0 && !L->ex && !ext && !L->prof_on && !host_bottom && (long)D.v.nx * D.v.ny <= L->graph_max_cells) {
+    const bool graphs = L->graph_max_cells > 0 && !L->ex && !ext && !L->prof_on && !host_bottom && (long)D.v.nx * D.v.ny <= L->graph_max_cells;
+    if (graphs) {
         bool done = false;
         int rc = vcycle_graph(L, sp, nd, s, done);
         if (rc || done) return rc;
     }
-    return vcycle_body(L, sp, nd, s);
+    return vcycle_body(L, sp, nd, s, !graphs);
 }
 
 extern "C" int suhmo_level_solve(suhmo_level_t *L, const suhmo_solver_params_t *sp, int *iters, double *hist, suhmo_stream_t s)

@@ -1484,6 +1484,43 @@ bool suhmo_gsrb_can_fuse_bcoef(suhmo_level *L, int sweeps)
     const int nt = L->fused_nt ? L->fused_nt : ((long)D.v.nx * D.v.ny >= 8000000L ? 256 : 64);
     return sweeps >= 3 && nt == 64 && pick_K(L, D, pick_variant(L, D), sweeps) == 2;
 }
+// AverageOperator behind that launch may leave the cycle's stream: the next launch of depth 0 (two sweeps and the restriction) reads none of the
+// coarse faces, so the two can share the GPU -- k_average_faces_all<OnLevel, ..> fits beside two resident waves of that launch per SIMD.
+// suhmo_gsrb_can_fuse_bcoef has excluded rank strips, agglomerated levels and exchange hooks; not inside a capture (a captured graph keeps
+// one branch) and not while profiling (the event pairs keep timing one launch each)
+bool suhmo_gsrb_can_overlap_avg(const suhmo_level *L)
+{
+    return L->avg_overlap && !L->mask_capturing && !L->prof_on && !L->ex && !L->agg && !L->ex_begin && !L->ex_end && !L->ipc;
+}
+// the fork: an event behind the launch that stored depth 0's faces, the averages behind it on the level's side stream, an event behind them
+// (enqueued before the launch they run beside: enqueued after it the cycle takes the same time, profiles/r21_avg_overlap_bench_parent_new_alternation.txt)
+static int avg_fork(suhmo_level *L, hipStream_t st)
+{
+    if (!L->astream) {
+        HIPCHK(hipStreamCreateWithFlags(&L->astream, hipStreamNonBlocking));
+        HIPCHK(hipEventCreateWithFlags(&L->aev[0], hipEventDisableTiming)); HIPCHK(hipEventCreateWithFlags(&L->aev[1], hipEventDisableTiming));
+    }
+    HIPCHK(hipEventRecord(L->aev[0], st));
+    HIPCHK(hipStreamWaitEvent(L->astream, L->aev[0], 0));
+    int rc = suhmo_average_operator_all(L, L->bcoef_nd, L->astream); if (rc) return rc;
+    HIPCHK(hipEventRecord(L->aev[1], L->astream));
+    L->avg_flying = 1; L->avg_overlap_count++;
+    return 0;
+}
+// ... and the join, before anything on st that reads a coarse face or hands the level back to the caller
+int suhmo_avg_join(suhmo_level *L, hipStream_t st)
+{
+    if (!L->avg_flying) return 0;
+    L->avg_flying = 0;
+    HIPCHK(hipStreamWaitEvent(st, L->aev[1], 0));
+    return 0;
+}
+void suhmo_avg_release(suhmo_level *L)
+{
+    if (!L->astream) return;
+    (void)hipStreamDestroy(L->astream); (void)hipEventDestroy(L->aev[0]); (void)hipEventDestroy(L->aev[1]);
+    L->astream = nullptr; L->aev[0] = L->aev[1] = nullptr; L->avg_flying = 0;
+}
 bool suhmo_gsrb_can_fuse_prolong(suhmo_level *L, int depth, int sweeps)
 {
     Depth &D = L->d[depth];
@@ -1520,6 +1557,7 @@ int suhmo_launch_gsrb(suhmo_level *L, int depth, int sweeps, int tail, hipStream
     int F = ext ? D.phi_fresh : 0;
     if (ext && D.prolong_pending) F = prolong_halo_rows(L, depth);   // the first launch adds the correction while loading
     int it = 0;
+    if (depth > 0) { int rc = suhmo_avg_join(L, st); if (rc) return rc; }   // the coarse faces, should they still be in flight on the side stream
     while (it < sweeps) {
         int K = pick_K(L, D, variant, sweeps - it);   // sweeps done by the next launch (0 = simple path, 1 sweep)
         int TS = (K == 0 && tile_ok(L, D)) ? (sweeps - it >= 4 && L->tile_s >= 4 ? 4 : sweeps - it >= 2 && L->tile_s >= 2 ? 2 : 1) : 0;   // sweeps of a tile launch
@@ -1644,8 +1682,8 @@ int suhmo_launch_gsrb(suhmo_level *L, int depth, int sweeps, int tail, hipStream
             pe.restricts = bcf ? 2 : (restricted && *restricted && it + done == sweeps) ? 1 : 0;
             L->prof.push_back(pe);
         }
-        // AverageOperator reads the faces that launch has just stored: right behind it
-        if (bcf) { int rc = suhmo_average_operator_all(L, L->bcoef_nd, st); if (rc) return rc; }
+        // AverageOperator reads the faces that launch has just stored: right behind it, on the side stream where the cycle allows (avg_fork)
+        if (bcf) { int rc = L->avg_fork ? avg_fork(L, st) : suhmo_average_operator_all(L, L->bcoef_nd, st); if (rc) return rc; }
         it += done;
     }
     HIPCHK(hipGetLastError());

@@ -176,6 +176,7 @@ int suhmo_level_create_(suhmo_level_t **out, const suhmo_level_desc_t *desc, boo
     L->frhs_stream = L->frhs_tile = 0;
     L->strip_tile = L->strip_tile_rst = L->strip_tile_shallow = L->strip_colour = L->strip_stream = L->strip_stream_rst = L->strip_prolong_unfused = 0;
     L->bcoef_in_relax = 1; L->bcoef_nd = 0; L->bcoef_in_relax_count = 0;
+    L->avg_overlap = 1; L->avg_fork = L->avg_flying = 0; L->avg_overlap_count = 0; L->astream = nullptr; L->aev[0] = L->aev[1] = nullptr;
     L->resout_np = 0;
     L->resout_req = L->resout_armed = L->resout_done = 0; L->resout_rhs = nullptr; L->resout_count = 0; L->resid_in_relax = 1;
     L->graph_max_cells = 1500000; L->gstream = nullptr; L->vgraph_replays = 0; memset(L->vgraph_seen, 0, sizeof(L->vgraph_seen));
@@ -196,7 +197,7 @@ int suhmo_level_create_(suhmo_level_t **out, const suhmo_level_desc_t *desc, boo
             {"SUHMO_TILE_RESTRICT", &suhmo_level::tile_restrict}, {"SUHMO_TILE_ORDER", &suhmo_level::tile_order}, {"SUHMO_FAS_RHS_IN_RELAX", &suhmo_level::fas_rhs_in_relax},
             {"SUHMO_TILE_S", &suhmo_level::tile_s}, {"SUHMO_GSRB_TILE", &suhmo_level::gsrb_tile}, {"SUHMO_TILE_T", &suhmo_level::tile_t},
             {"SUHMO_FUSED_RESTRICT", &suhmo_level::fused_restrict}, {"SUHMO_SKIP_MASK", &suhmo_level::skip_mask}, {"SUHMO_MASK_KNOWN", &suhmo_level::mask_known},
-            {"SUHMO_POLL_READBACK", &suhmo_level::poll_readback}};
+            {"SUHMO_POLL_READBACK", &suhmo_level::poll_readback}, {"SUHMO_AVG_OVERLAP", &suhmo_level::avg_overlap}};
         static const LongKnob longs[] = {
             {"SUHMO_AGG_MIN_CELLS", &suhmo_level::agg_min_cells}, {"SUHMO_TILE_MAX_CELLS", &suhmo_level::tile_max_cells},
             {"SUHMO_GRAPH_MAX_CELLS", &suhmo_level::graph_max_cells}, {"SUHMO_FUSED_MIN_CELLS", &suhmo_level::fused_min_cells},
@@ -355,7 +356,7 @@ static int *option_slot_int(suhmo_level *L, const char *key)
         {"tile_strips", &suhmo_level::tile_strips}, {"overlap_halo", &suhmo_level::overlap_halo}, {"skip_mask", &suhmo_level::skip_mask}, {"mask_known", &suhmo_level::mask_known}, {"tile_chunks",
             &suhmo_level::tile_chunks}, {"tile_order", &suhmo_level::tile_order}, {"tile_restrict", &suhmo_level::tile_restrict}, {"fas_rhs_in_relax",
             &suhmo_level::fas_rhs_in_relax}, {"resid_in_relax", &suhmo_level::resid_in_relax}, {"bcoef_in_relax", &suhmo_level::bcoef_in_relax}, {"fas_rhs_fused", &suhmo_level::fas_rhs_fused},
-        {"tile_s", &suhmo_level::tile_s}, {"gsrb_tile", &suhmo_level::gsrb_tile}, {"tile_t", &suhmo_level::tile_t}, {"poll_readback", &suhmo_level::poll_readback}};
+        {"avg_overlap", &suhmo_level::avg_overlap}, {"tile_s", &suhmo_level::tile_s}, {"gsrb_tile", &suhmo_level::gsrb_tile}, {"tile_t", &suhmo_level::tile_t}, {"poll_readback", &suhmo_level::poll_readback}};
     for (const auto &e : tab) if (!strcmp(key, e.k)) return &(L->*(e.m));
     return nullptr;
 }
@@ -404,7 +405,8 @@ extern "C" int suhmo_level_get_option(const suhmo_level_t *L, const char *key, l
     }
     if (!strcmp(key, "residual_in_relax_launches")) { *value = L->resout_count; return 0; }
     if (!strcmp(key, "bcoef_in_relax_launches")) { *value = L->bcoef_in_relax_count; return 0; }   // read-only counter (bcoef_in_relax)
-    if (!strcmp(key, "mask_scans")) { *value = L->mask_scans; return 0; }                 // read-only counters (mask_known)
+    if (!strcmp(key, "avg_overlap_launches")) { *value = L->avg_overlap_count; return 0; }         // read-only counter (avg_overlap)
+    if (!strcmp(key, "mask_scans")) { *value = L->mask_scans; return 0; }                // read-only counters (mask_known)
     if (!strcmp(key, "mask_state")) { *value = L->mask_state; return 0; }                 // 0 unknown, 1 clean, 2 dirty, as of the last V-cycle
     if (!strcmp(key, "bcoef_unmasked_launches")) { *value = L->bcoef_unmasked; return 0; }
     if (!strcmp(key, "relax_unmasked_launches")) { *value = L->relax_unmasked; return 0; }
