@@ -813,6 +813,45 @@ typedef struct suhmo_flat_comp { int kind, field, field2; } suhmo_flat_comp_t;
 int suhmo_hier_flatten(suhmo_hier_t *H, int max_level, int ncomp, const suhmo_flat_comp_t *comps, long dims[2] /* nxF, nyF */, double *host_dst,
                        suhmo_stream_t s);
 
+/* ---- COMPARE (suhmo_amd/csrc/suhmo_compare.hip; DESIGN.md section 5, "Comparison of runs"; tests/compare_ref.py is the numpy twin of this text, of
+ * suhmo_compare.h and of suhmo_reduce.h): the composite error of a hierarchy against a finer SINGLE-LEVEL run, reduced on the device to three doubles
+ * per component -- L1, L2 and max.  It is the number the reference's convergence tables hold, which CONV_ANA/scripts/launch_comparaison*.py produce
+ * with ChomboCompare in two ways: on the levels of the plot file, the exact solution averaged down to each level and covered cells left out
+ * (SUHMO_CMP_COMPOSITE), and on the plotCustom composites, cell by cell on the same finest grid (SUHMO_CMP_FINEST).
+ * INPUTS.  `exact` is a plain whole level on the hierarchy's device whose valid cells are exactly (nx0 << exact_level) x (ny0 << exact_level),
+ * exact_level >= the finest level of H.  comps is the list suhmo_hier_flatten takes: FIELD or DIFF is evaluated on BOTH sides from the same field
+ * ids, a DIFF per cell on each side before anything else.  A field a box of H does not hold counts as 0.0 (the flatten's rule); a field `exact`
+ * does not hold is refused.
+ * COMPOSITE.  For level l, r = 2^(exact_level - l) and w_l = dx_l * dy_l (formed on the host).  For every valid cell of every box whose
+ * SUHMO_F_COVER is 0 (a covered cell contributes nothing and the exact cells under it are not read), with c its component:
+ *       avg   the exact component over the r x r block under the cell: within a row of the block the r values are added as a PAIRWISE TREE OF
+ *             NEIGHBOURS, (x0 + x1) + (x2 + x3), ...; the r row sums are added in ascending row order, starting from the first row's sum; the
+ *             result times 1.0 / (r r), which is exact.  r = 1: the value as it is.
+ *       e = c - avg;   terms  |e| * w_l,  (e * e) * w_l,  |e|          -- products rounded before the sums, nothing contracted
+ * The order of the block is layout-independent and lets a group of r lanes form a row sum with __shfl_xor butterflies from coalesced loads.
+ * The three terms are reduced as sum, sum, max in the order of suhmo_reduce.h and nothing else: a first stage per level -- level 0 under CAP_LEVEL;
+ * a level of boxes under CAP_BOX with ONE grid for all its boxes, that of the level's largest box extents (max nx, max ny over the boxes), every
+ * box leaving that many partials (a workgroup without cells leaves 0.0, 0.0, 0.0) -- the partials one list per level, boxes ascending; the second
+ * stage over the lists in ascending level order.  norms[q] = {sum1, sqrt(sum2), max}; the max is exact.  level_terms[l][q] = {sum1, sum2, max}
+ * of level l's own second stage (the same rule over that list alone), without the square root.
+ * FINEST.  The device part of suhmo_hier_flatten at max_level = exact_level -- its steps (i) to (iii), the same scratch, the same finest array,
+ * the same launches (flatten_launches counts them) -- then ONE first stage under CAP_LEVEL over the nyF x nxF array: e = flat - x, the terms as
+ * above with w = dx * dy of the exact level.  Nothing but the result is copied: flatten_copies does not move.  level_terms must be NULL.
+ * READ-ONLY, like the flatten.  LAUNCHES: COMPOSITE nlev first stages (every component in the one launch of its level) + one final stage; FINEST
+ * one first stage + one final stage beside the flatten's.  ONE copy of 3 ncomp doubles (with level_terms: 3 ncomp (1 + nlev)) and ONE
+ * synchronisation.  Read-only options compare_launches and compare_copies count them.  The partial buffer belongs to the hierarchy: allocated on
+ * first use (compare_device_bytes: what it holds), freed with it; a regrid makes a new handle, which allocates its own.
+ * REFUSED before anything is launched, norms untouched.  rc -1: the component checks of the flatten; an unknown mode; level_terms in FINEST;
+ * exact NULL; exact_level below the finest level, or so large that the finest grid leaves int; exact's extents other than those above;
+ * COMPOSITE with r > 64 on level 0 (exact_level > 6); a field exact does not hold.  rc -2: an allocation fails (the partial buffer; in FINEST
+ * the flatten's finest array or scratch); the hierarchy stays usable.  rc -5: H on rank strips, with levels dealt to the ranks or created with
+ * shadow = 1; exact a rank strip; exact on another device.
+ * Not built: a hierarchy as the exact side, tau, rank strips, comparing inside suhmo_hier_run_out. */
+enum { SUHMO_CMP_COMPOSITE = 0, SUHMO_CMP_FINEST = 1 };
+int suhmo_hier_compare(suhmo_hier_t *H, suhmo_level_t *exact, int exact_level, int mode, int ncomp, const suhmo_flat_comp_t *comps,
+                       double *norms /* [ncomp][3]: L1, L2, max */, double *level_terms /* NULL or [nlev][ncomp][3]: sum1, sum2, max */,
+                       suhmo_stream_t s);
+
 /* ---- OUTPUT INSIDE THE RUN (suhmo_amd/csrc/suhmo_run.hip): suhmo_hier_run_out is suhmo_hier_run with the plot files and checkpoints AmrHydro::run
  * writes (src/AmrHydro.cpp:1311-1336, 1343-1358); suhmo_hier_run is the same call with out = NULL.  With b = c - 1, the reference's m_cur_step before
  * step c:

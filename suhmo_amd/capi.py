@@ -134,6 +134,7 @@ class FlatComp(C.Structure):
 
 FLAT_FIELD, FLAT_DIFF = 0, 1
 FLAT_MAX_COMPS = 16
+CMP_COMPOSITE, CMP_FINEST = 0, 1             # the modes of suhmo_hier_compare
 
 
 def flat_comps(comps):
@@ -183,6 +184,7 @@ SYMBOLS = [
     "suhmo_hier_restrict_tags", "suhmo_tag_subsets_nest", "suhmo_hier_get_boxes",
     "suhmo_hier_time_varying_recharge", "suhmo_hier_postproc_temporal", "suhmo_hier_run",
     "suhmo_hier_snapshot", "suhmo_level_snapshot", "suhmo_hier_run_out", "suhmo_hier_flatten",
+    "suhmo_hier_compare",
 ]
 
 
@@ -355,6 +357,7 @@ def lib():
     L.suhmo_level_snapshot.argtypes = [vp, ci, C.POINTER(SnapComp), ci, lp, dp, vp]
     L.suhmo_hier_run_out.argtypes = [C.POINTER(vp), C.POINTER(ModelParams), C.POINTER(HierSchedule), C.POINTER(HierOutput), C.POINTER(HierRunResult), vp]
     L.suhmo_hier_flatten.argtypes = [vp, ci, ci, C.POINTER(FlatComp), lp, dp, vp]
+    L.suhmo_hier_compare.argtypes = [vp, vp, ci, ci, ci, C.POINTER(FlatComp), dp, dp, vp]
     _LIB = L
     return L
 

@@ -10,6 +10,8 @@
 //   (iii) k_flat_interp   one launch per level, ascending (a finer level overwrites): the level's valid cells times 2^(max_level - l) in each
 //                         direction into the finest array on the device
 //   (iv)  one hipMemcpyAsync into host_dst, one synchronisation
+// (i) to (iii) are suhmo_hier_flatten_device_, which suhmo_compare.hip calls too (its FINEST mode reduces the finest array where it lies); (iv) is
+// suhmo_hier_flatten's own
 #include "suhmo_hier_int.h"
 #include "suhmo_level_int.h"
 #include "suhmo_transfer.h"
@@ -18,8 +20,6 @@
 using namespace hier;
 
 namespace {
-struct FlatComps { int n; int kind[SUHMO_FLAT_MAX_COMPS], f1[SUHMO_FLAT_MAX_COMPS], f2[SUHMO_FLAT_MAX_COMPS]; };
-
 __device__ __forceinline__ const FP &scratch_of(const OnLevel &, const FP &base, const FP *) { return base; }
 __device__ __forceinline__ const FP &scratch_of(const OnBoxes &, const FP &, const FP *tab) { return tab[blockIdx.z]; }
 
@@ -99,9 +99,8 @@ template <bool COPY> __global__ __launch_bounds__(256) void k_flat_interp(const 
     }
 }
 
-int flat_comps(int ncomp, const suhmo_flat_comp_t *comps, FlatComps &c)
+int flat_comps(int ncomp, const suhmo_flat_comp_t *comps, FlatComps &c, const char *who)
 {
-    const char *who = "suhmo_hier_flatten";
     if (ncomp < 1 || ncomp > SUHMO_FLAT_MAX_COMPS || !comps) { suhmo_set_error("%s: %d components (1 .. %d)", who, ncomp, SUHMO_FLAT_MAX_COMPS); return -1; }
     memset(&c, 0, sizeof(c));
     c.n = ncomp;
@@ -177,14 +176,11 @@ void suhmo_hier_flatten_release_(suhmo_hier *H)
     }
 }
 
-extern "C" int suhmo_hier_flatten(suhmo_hier_t *H, int max_level, int ncomp, const suhmo_flat_comp_t *comps, long dims[2], double *host_dst,
-                                  suhmo_stream_t s)
+int suhmo_flat_comps_(const char *who, int ncomp, const suhmo_flat_comp_t *comps, FlatComps &c) { return flat_comps(ncomp, comps, c, who); }
+
+// the refusals that depend on max_level and on how the hierarchy is laid out, in the order of the header
+int suhmo_hier_flatten_check_(const suhmo_hier *H, int max_level)
 {
-    SUHMO_TIME("AmrHydro::interpFinest");
-    ARG(H && H->nlev >= 1 && dims);
-    FlatComps c;
-    int rc;
-    if ((rc = flat_comps(ncomp, comps, c))) return rc;
     const int top = H->nlev - 1;
     const int nx0 = H->lev[0].nxd, ny0 = H->lev[0].nyd;
     if (max_level < top) { suhmo_set_error("suhmo_hier_flatten: max_level = %d is below the finest level %d", max_level, top); return -1; }
@@ -194,11 +190,17 @@ extern "C" int suhmo_hier_flatten(suhmo_hier_t *H, int max_level, int ncomp, con
     if (H->world > 1 || H->part || H->shadowed) {
         suhmo_set_error("suhmo_hier_flatten: a hierarchy on rank strips, with levels dealt to the ranks or created with shadow = 1 is not built"); return -5;
     }
+    return 0;
+}
+
+// the device part of a flatten, steps (i) to (iii): the components of `c` on the uniform grid of max_level in H->flat_buf, [comp][j][i].  The
+// caller has checked (suhmo_flat_comps_, suhmo_hier_flatten_check_) and set the device; nothing is copied and nothing synchronised at the end
+int suhmo_hier_flatten_device_(suhmo_hier *H, int max_level, const FlatComps &c, hipStream_t st)
+{
+    int rc;
+    const int ncomp = c.n, top = H->nlev - 1;
+    const int nx0 = H->lev[0].nxd, ny0 = H->lev[0].nyd;
     const long nxF = (long)nx0 << max_level, nyF = (long)ny0 << max_level, plane = nxF * nyF;
-    dims[0] = nxF; dims[1] = nyF;
-    if (!host_dst) return 0;
-    hipStream_t st = HST(s);
-    HIPCHK(hipSetDevice(H->device));
     const size_t need = (size_t)ncomp * (size_t)plane;       // (< 2^4 x 2^62: no overflow; bytes may overflow, hence the first test)
     if (H->flat_cap < need) {
         if (H->flat_buf) { HIPCHK(hipDeviceSynchronize()); (void)hipFree(H->flat_buf); H->flat_buf = nullptr; H->flat_cap = 0; }
@@ -255,6 +257,24 @@ extern "C" int suhmo_hier_flatten(suhmo_hier_t *H, int max_level, int ncomp, con
         H->n_flat_launches++;
     }
   }
+    return 0;
+}
+
+extern "C" int suhmo_hier_flatten(suhmo_hier_t *H, int max_level, int ncomp, const suhmo_flat_comp_t *comps, long dims[2], double *host_dst,
+                                  suhmo_stream_t s)
+{
+    SUHMO_TIME("AmrHydro::interpFinest");
+    ARG(H && H->nlev >= 1 && dims);
+    FlatComps c;
+    int rc;
+    if ((rc = flat_comps(ncomp, comps, c, "suhmo_hier_flatten")) || (rc = suhmo_hier_flatten_check_(H, max_level))) return rc;
+    const long nxF = (long)H->lev[0].nxd << max_level, nyF = (long)H->lev[0].nyd << max_level;
+    dims[0] = nxF; dims[1] = nyF;
+    if (!host_dst) return 0;
+    hipStream_t st = HST(s);
+    HIPCHK(hipSetDevice(H->device));
+    if ((rc = suhmo_hier_flatten_device_(H, max_level, c, st))) return rc;
+    const size_t need = (size_t)ncomp * (size_t)(nxF * nyF);
   { SUHMO_TIME("interpFinest: copy to the host");
     // (iv)
     HIPCHK(hipMemcpyAsync(host_dst, H->flat_buf, need * sizeof(double), hipMemcpyDeviceToHost, st));

@@ -317,6 +317,7 @@ extern "C" int suhmo_hier_destroy(suhmo_hier_t *H)
     if (H->xr) (void)hipFree(H->xr);
     if (H->snap_buf) (void)hipFree(H->snap_buf);
     suhmo_hier_flatten_release_(H);
+    suhmo_hier_compare_release_(H);
     for (int l = 0; l < 8; l++) {
         HLev &V = H->lev[l];
         V.snap_cells[0].release(); V.snap_cells[1].release();
@@ -605,6 +606,9 @@ extern "C" int suhmo_hier_get_option(const suhmo_hier_t *H, const char *key, lon
         for (int l = 0; l < H->nlev; l++) c += (long)H->lev[l].flat_slab.size() * (long)H->lev[l].flat_elems * 8;
         *value = c; return 0;
     }
+    if (!strcmp(key, "compare_launches")) { *value = H->n_cmp_launches; return 0; }
+    if (!strcmp(key, "compare_copies")) { *value = H->n_cmp_copies; return 0; }
+    if (!strcmp(key, "compare_device_bytes")) { *value = (long)H->cmp_cap * 8; return 0; }
     if (!strcmp(key, "run_plots")) { *value = H->n_run_plots; return 0; }
     if (!strcmp(key, "run_checkpoints")) { *value = H->n_run_checkpoints; return 0; }
     if (!strcmp(key, "incremental_residual_passes")) { *value = H->n_incr_residual; return 0; }

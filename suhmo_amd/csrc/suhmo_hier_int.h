@@ -199,6 +199,10 @@ struct suhmo_hier {
     // (read-only options flatten_launches, flatten_copies)
     double *flat_buf = nullptr; size_t flat_cap = 0;
     long n_flat_launches = 0, n_flat_copies = 0;
+    // suhmo_compare.hip: the partials of every first stage of a comparison and, behind them, what its final stage leaves (allocated on first use;
+    // cmp_cap doubles), its launches and copies (read-only options compare_launches, compare_copies, compare_device_bytes)
+    double *cmp_buf = nullptr; size_t cmp_cap = 0;
+    long n_cmp_launches = 0, n_cmp_copies = 0;
     long flat_fail_slot = -1;                              // option flatten_fail_slot (tests): the allocation of this scratch slot on the finest level fails
     double *red_all = nullptr;                             // partial maxima of a norm over all levels of boxes (64 per box + 16)
     struct suhmo_tagmap *tags[8] = {};                     // tag maps of suhmo_hier_tag_cells, one per level (suhmo_tags.hip), owned
@@ -325,3 +329,11 @@ int suhmo_hier_snapshot_check_(const suhmo_hier *H, const char *who, int ncomp, 
 long suhmo_hier_snapshot_sizes_(const suhmo_hier *H, int ncomp, int ghost, long *level_offset, long *box_offset);
 // ---- suhmo_flatten.hip: its scratch and finest array go with the hierarchy
 void suhmo_hier_flatten_release_(suhmo_hier *H);
+// ... and what suhmo_compare.hip needs of it: the component list checked (who: the entry point the message names), the refusals that depend on
+// max_level, and the device part of a flatten -- steps (i) to (iii), the finest array left in H->flat_buf, nothing copied
+struct FlatComps { int n; int kind[SUHMO_FLAT_MAX_COMPS], f1[SUHMO_FLAT_MAX_COMPS], f2[SUHMO_FLAT_MAX_COMPS]; };
+int suhmo_flat_comps_(const char *who, int ncomp, const suhmo_flat_comp_t *comps, FlatComps &c);
+int suhmo_hier_flatten_check_(const suhmo_hier *H, int max_level);
+int suhmo_hier_flatten_device_(suhmo_hier *H, int max_level, const FlatComps &c, hipStream_t st);
+// ---- suhmo_compare.hip: its partial buffer goes with the hierarchy
+void suhmo_hier_compare_release_(suhmo_hier *H);

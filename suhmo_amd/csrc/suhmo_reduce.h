@@ -9,11 +9,13 @@
 //   block tree    sm[tid] = acc, tid = ty * blockDim.x + tx; for s = 128, 64, ..., 1: sm[tid] = op(sm[tid], sm[tid + s]) for tid < s
 //   second stage  256 threads; thread t takes the partials t, t + 256, ... of each list in turn, starting from init; then the block tree
 //
+// op is the reduction's own; one whose values combine differently (RedSumSumMax: sum, sum, max) is asked with the value's number (red_op).
 // A sum differs from the serial CPU sum by rounding only; a maximum is exact in any order.  tests/reduce_ref.py restates this order in
 // numpy (two_stage_sum, block_tree) and tests/test_gpu_reductions.py holds the device to it bit for bit: change one, change the other.
 #pragma once
 #include "suhmo_target.h"
 #include <algorithm>
+#include <type_traits>
 
 // ---- a reduction: NV values per cell that travel together, where they start and how two of them combine
 struct RedMax { static constexpr int NV = 1;            // max |x|: the terms are >= 0
@@ -25,6 +27,19 @@ struct RedSum { static constexpr int NV = 1;
 struct RedMax2 { static constexpr int NV = 2;           // the Picard test's pair: max h (any sign) and max |h_lagged - h|
     static __device__ __forceinline__ double init(int q) { return q == 0 ? -1.0e300 : 0.0; }
     static __device__ __forceinline__ double op(double a, double b) { return fmax(a, b); } };
+// a reduction whose values do not all combine the same way says so (PER_VALUE) and takes the value's number: sum |e| w, sum e e w, max |e| of
+// suhmo_compare.hip.  red_op is what the tree and the second stage call: q is a constant after unrolling, so a reduction with ONE op compiles to
+// the code it always had
+struct RedSumSumMax { static constexpr int NV = 3; static constexpr bool PER_VALUE = true;      // the terms are >= 0
+    static __device__ __forceinline__ double init(int) { return 0.0; }
+    static __device__ __forceinline__ double op(int q, double a, double b) { return q == 2 ? fmax(a, b) : a + b; } };
+template <class R, class = void> struct red_per_value : std::false_type {};
+template <class R> struct red_per_value<R, std::void_t<decltype(R::PER_VALUE)>> : std::true_type {};
+template <class R> __device__ __forceinline__ double red_op(int q, double a, double b)
+{
+    if constexpr (red_per_value<R>::value) return R::op(q, a, b);
+    else return R::op(a, b);
+}
 
 // ---- the walk: f(i, j) for the valid cells of `v` this thread takes, j outer, i inner (what else a body skips -- an exclusion rectangle,
 // covered cells -- is the body's business)
@@ -44,7 +59,7 @@ template <class R> __device__ __forceinline__ void block_tree(int tid, double (&
     for (int s = 128; s > 0; s >>= 1) {
         if (tid < s) {
 #pragma unroll
-            for (int q = 0; q < R::NV; q++) sm[q][tid] = R::op(sm[q][tid], sm[q][tid + s]);
+            for (int q = 0; q < R::NV; q++) sm[q][tid] = red_op<R>(q, sm[q][tid], sm[q][tid + s]);
         }
         __syncthreads();
     }
@@ -82,7 +97,7 @@ template <class R> __global__ __launch_bounds__(256) void k_norm_final(PartialLi
     for (int l = 0; l < pl.cnt; l++)
         for (int k = tid; k < pl.n[l]; k += 256) {
 #pragma unroll
-            for (int q = 0; q < R::NV; q++) a[q] = R::op(a[q], pl.p[l][R::NV * k + q]);
+            for (int q = 0; q < R::NV; q++) a[q] = red_op<R>(q, a[q], pl.p[l][R::NV * k + q]);
         }
     block_tree<R>(tid, a);
     if (tid == 0) {

@@ -529,6 +529,22 @@ class HipHier:
         check(capi.lib().suhmo_hier_flatten(self.h, ml, len(comps), arr, dims, a.ctypes.data_as(C.POINTER(C.c_double)), self.stream))
         return a
 
+    def compare(self, exact, comps, exact_level=None, mode="composite", level_terms=False):
+        """suhmo_hier_compare: the L1, L2 and max norms of the hierarchy's error against `exact`, a HipLevel (or its handle) that holds the same
+        fields on the uniform grid of level exact_level (None: the finest level), reduced on the device -> an (ncomp, 3) array.  comps as
+        flatten takes them, evaluated on both sides.  mode "composite": level by level, the exact solution averaged down to each level,
+        covered cells left out (ChomboCompare on a plot file); "finest": cell by cell against the flattened hierarchy (on the plotCustom
+        composite).  level_terms=True (composite only): -> (norms, (nlev, ncomp, 3) array of each level's own sum |e| w, sum e e w, max |e|).
+        Read-only; three doubles per component leave the device"""
+        el = self.nlev - 1 if exact_level is None else int(exact_level)
+        md = {"composite": capi.CMP_COMPOSITE, "finest": capi.CMP_FINEST}[mode] if isinstance(mode, str) else int(mode)
+        norms = np.zeros((len(comps), 3))
+        terms = np.zeros((self.nlev, len(comps), 3)) if level_terms else None
+        dp = lambda a: a.ctypes.data_as(C.POINTER(C.c_double))
+        check(capi.lib().suhmo_hier_compare(self.h, getattr(exact, "h", exact), el, md, len(comps), capi.flat_comps(comps), dp(norms),
+                                            dp(terms) if level_terms else None, self.stream))
+        return (norms, terms) if level_terms else norms
+
     def owns(self, l, k):
         """this rank computes box k of level l (every box of a replicated level; on a level dealt to the ranks: its own boxes)"""
         return self.owner[l][k] in (-1, self.rank)

@@ -686,6 +686,18 @@ class HipHierModel:
         a = self.hier.flatten([c for _, c in self.PP_COMPONENTS], max_level)
         return {nm: a[q] for q, (nm, _) in enumerate(self.PP_COMPONENTS)}
 
+    # the fields of the reference's convergence tables (CONV_ANA/scripts/launch_comparaison*.py: head, gapHeight, Pw, Re, N)
+    CMP_COMPONENTS = [("head", (capi.FLAT_FIELD, lv.F_PHI)), ("gapHeight", (capi.FLAT_FIELD, lv.F_B)), ("Pw", (capi.FLAT_FIELD, lv.F_PW)),
+                      ("Re", (capi.FLAT_FIELD, lv.F_RE)), ("N", (capi.FLAT_DIFF, lv.F_PI, lv.F_PW))]
+
+    def compare(self, exact_model, exact_level=None, mode="composite"):
+        """suhmo_hier_compare against a single-level model (HipModel) on the uniform grid of level exact_level (None: the one its width gives):
+        -> dict(head=, gapHeight=, Pw=, Re=, N=) of (L1, L2, max) arrays.  Read-only; nothing but the norms leaves the device"""
+        if exact_level is None:
+            exact_level = (exact_model.nx // self.level[0][0].nx).bit_length() - 1
+        a = self.hier.compare(exact_model.level, [c for _, c in self.CMP_COMPONENTS], exact_level, mode)
+        return {nm: a[q] for q, (nm, _) in enumerate(self.CMP_COMPONENTS)}
+
     def restrict_tags(self, level, boxes):
         """levelTags &= tagSubset (suhmo_hier_restrict_tags): every entry of the tag map of `level` that lies in none of `boxes`
         ((lo0, lo1, hi0, hi1) in cells of that level, aligned to the map's granularity) is cleared; an empty list is a no-op"""

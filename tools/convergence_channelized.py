@@ -7,7 +7,10 @@ L2 self-convergence errors between successive resolutions as ChomboCompare compu
 exec/0_convergence_channelized/CONV_ANA/results/convergence_data_singleLevel.dat.
 usage: convergence_channelized.py [max_level 2..7]
        convergence_channelized.py --generated-grids [--oracle] [--steps n] [base cells ...]: the grids of the {k}lev_base / {k}lev_base2levs runs made by
-       tagging the melt rate with the run's own settings (suhmo_grids_generate), next to the rectangles inferred from the reference's tables"""
+       tagging the melt rate with the run's own settings (suhmo_grids_generate), next to the rectangles inferred from the reference's tables
+       convergence_channelized.py --device-compare amr ...: the composite errors of the amr mode (amr_errors) and the hip leg of amr_moulin_error
+       come from suhmo_hier_compare -- the exact solution on a level of the device, three doubles per field copied back -- instead of the
+       per-box get calls and the numpy loop over the boxes (the default, unchanged)"""
 import os
 import sys
 import time
@@ -126,7 +129,10 @@ def amr_boxes(nx0, rects):
     return out
 
 
-def amr_moulin_error(nx0, rects, which="oracle"):
+DEVICE_COMPARE = False       # --device-compare
+
+
+def amr_moulin_error(nx0, rects, which="oracle", device_compare=None):
     """RHS_moulin entry of CONV_ANA/results/convergence_data_{2,3}Levels.dat: composite L2 difference (ChomboCompare: cells under a
     finer level do not count, the exact solution averaged to each level) between the moulin source term of the hierarchy
     (base nx0 x nx0/4 + len(rects) AMR levels) and the single level len(rects) + 1 refinements finer"""
@@ -146,6 +152,11 @@ def amr_moulin_error(nx0, rects, which="oracle"):
         get = lambda l, k: A.get(l, k, "msrc")
         E = model.HipModel(nxe, nxe // 4, LX / nxe, LY / (nxe // 4), BC, PHYS, MODEL, max_box=min(64, nxe // 4))
         E.moulin_source(*MOULIN, 1.0)
+        if DEVICE_COMPARE if device_compare is None else device_compare:
+            from suhmo_amd import capi
+            l2 = float(A.hier.compare(E.level, [(capi.FLAT_FIELD, model.lv.F_MSRC)], nlev)[0][1])
+            E.close(); A.close()
+            return l2
         ex = E.get("msrc")
         E.close()
     allb = [[(0, 0, nx0 - 1, nx0 // 4 - 1)]] + boxes
@@ -249,7 +260,7 @@ def union_metres(nx0, boxes):
     return out
 
 
-def amr_run(nx0, rects, main_steps=3000, total_steps=7200):
+def amr_run(nx0, rects, main_steps=3000, total_steps=7200, keep=False):
     """{k}lev_base / {k}lev_base2levs on the device with the inferred (fixed) grids: the reference restarts the AMR run from the
     single-level checkpoint after the ramp (3000 steps) and regrids every 250 steps; here the hierarchy exists from the start --
     both end in the same steady channel.  Returns per level and box the fields ChomboCompare reads."""
@@ -270,13 +281,32 @@ def amr_run(nx0, rects, main_steps=3000, total_steps=7200):
     for k in range(total_steps):
         H._mp.ramp = float(ramp(k * m["dt"])) if k < main_steps else 1.0
         H.timestep(m["dt"])
+    if keep:                                                # the model itself, for a comparison on the device; the caller closes it
+        return H, allb
     out = [[{nm: H.get(l, k, nm) for nm in ("head", "B", "Pw", "Re")} for k in range(len(bl))] for l, bl in enumerate(allb)]
     H.close()
     return out, allb
 
 
-def amr_errors(nx0, rects, exact):
+def amr_errors_device(nx0, rects, exact):
+    """amr_errors through suhmo_hier_compare: `exact` goes onto a level of the device, the hierarchy stays there, the norms come back"""
+    from suhmo_amd import capi, level as lv
+    H, allb = amr_run(nx0, rects, keep=True)
+    ny, nx = exact["head"].shape
+    el = int(np.log2(nx // nx0))
+    E = lv.HipLevel(nx, ny, LX / nx, LY / ny, BC, PHYS, max_box=min(64, ny))
+    fields = dict(head=lv.F_PHI, B=lv.F_B, Pw=lv.F_PW, Re=lv.F_RE)
+    for nm, f in fields.items():
+        E.set(f, exact[nm])
+    norms = H.hier.compare(E, [(capi.FLAT_FIELD, f) for f in fields.values()], el)
+    E.close(); H.close()
+    return {nm: float(norms[q][1]) for q, nm in enumerate(fields)}
+
+
+def amr_errors(nx0, rects, exact, device_compare=None):
     """composite L2 errors (head, gapHeight, Pw, Re) of the AMR run against the single-level solution `exact` (dict of arrays)"""
+    if DEVICE_COMPARE if device_compare is None else device_compare:
+        return amr_errors_device(nx0, rects, exact)
     sol, allb = amr_run(nx0, rects)
     nxe = exact["head"].shape[1]
     res = {}
@@ -322,6 +352,9 @@ def table(max_level=7, log=None, which="hip", phys=None):
 
 if __name__ == "__main__":
     args = sys.argv[1:]
+    if "--device-compare" in args:
+        args.remove("--device-compare")
+        DEVICE_COMPARE = True
     if "--generated-grids" in args:                     # convergence_channelized.py --generated-grids [--oracle] [--steps n] [base cells ...]
         args.remove("--generated-grids")
         which = "hip"

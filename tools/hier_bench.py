@@ -1,6 +1,10 @@
 #!/usr/bin/env python3
 """cfg5 (exec/AMR_multiMoulins physics) time step on base + 3 AMR levels of box unions: ms per step.
-    python tools/hier_bench.py [--generated-grids] [--regrid-interval N [--one-call [--plot-interval P]]] [--recharge] [--snapshot] [--flatten] [base cells per side] [steps]
+    python tools/hier_bench.py [--generated-grids] [--regrid-interval N [--one-call [--plot-interval P]]] [--recharge] [--snapshot] [--flatten] [--compare] [base cells per side] [steps]
+--compare: the L1, L2 and max norms of the reference's two components against a single level on the uniform grid of level 4 (random fields), on the
+hierarchy --flatten uses: suhmo_hier_compare in both modes (HipHier.compare: composite, finest), in alternating rounds with the two routes that
+existed before it -- one flatten to the host and the norms in numpy; the per-box get calls and, box by box, the block means and norms in numpy
+(either with the time of its copies and of its host arithmetic apart) -- with the launch and copy counts.
 --flatten: gap height and N = Pi - Pw of the hierarchy on the uniform grid of level 4 (HipHierModel.interp_finest's call, suhmo_hier_flatten), three
 repetitions: the time of the kernels and of the copy to the host separately (the library's named timers with the device synchronised around either
 part), the launch and copy counts -- and, alternating with it, the per-box get calls that bring the same fields to the host (their count and time
@@ -32,7 +36,8 @@ one_call = "--one-call" in sys.argv
 recharge = "--recharge" in sys.argv
 snapshot = "--snapshot" in sys.argv
 flatten = "--flatten" in sys.argv
-argv = [a for a in sys.argv[1:] if a not in ("--generated-grids", "--one-call", "--recharge", "--snapshot", "--flatten")]
+compare = "--compare" in sys.argv
+argv = [a for a in sys.argv[1:] if a not in ("--generated-grids", "--one-call", "--recharge", "--snapshot", "--flatten", "--compare")]
 plot_interval = -1
 if "--plot-interval" in argv:
     q = argv.index("--plot-interval")
@@ -362,6 +367,82 @@ def flatten_bench(rounds=3, max_level=4):
     M.close()
 
 
+def compare_bench(rounds=4, exact_level=4):
+    """suhmo_hier_compare, both modes, against flatten + numpy and against the per-box get loop + numpy"""
+    import numpy as np
+    from suhmo_amd import capi, level as lv
+    M = model.HipHierModel(nb, nb, sts[0][0]["dx"], sts[0][0]["dy"], bc, ph, mm, boxes, max_box=64)
+    M.set_states(sts)
+    M.moulin_source(**mo)
+    for _ in range(3):
+        M.timestep(mm["dt"])
+    comps = [c for _, c in M.PP_COMPONENTS]
+    fields = (lv.F_B, lv.F_PI, lv.F_PW)
+    nF = nb << exact_level
+    dxF = sts[0][0]["dx"] / 2 ** exact_level
+    X = lv.HipLevel(nF, nF, dxF, dxF, bc, ph, max_box=64)
+    rng = np.random.default_rng(1)
+    xh = {}
+    for f in fields:                                         # the hierarchy's own range of values, so that no term overflows or vanishes
+        a = M.level[0][0].get(f)
+        xh[f] = rng.uniform(a.min(), a.max() + 1.0e-12, size=(nF, nF))
+        X.set(f, xh[f])
+    xc = [xh[lv.F_B], xh[lv.F_PI] - xh[lv.F_PW]]
+    sync = M.level[0][0].synchronize
+    H = M.hier
+    nbx = sum(len(bl) for bl in M.level)
+    out = H.flatten(comps, exact_level)                      # (the first calls allocate: scratch, finest array, partial buffer)
+    H.compare(X, comps, exact_level, "composite"); H.compare(X, comps, exact_level, "finest")
+    allb = [[(0, 0, nb - 1, nb - 1)]] + [list(bl) for bl in H.boxes]
+    print("compare: boxes per level %s, %d handles with level 0, %d components against %d x %d exact cells (%.1f MB per field)"
+          % ([len(b) for b in boxes], nbx, len(comps), nF, nF, xh[lv.F_B].nbytes / 1e6), flush=True)
+    def counted(fn):
+        keys = ("compare_launches", "compare_copies", "flatten_launches", "flatten_copies")
+        n = [H.get_option(k) for k in keys]
+        r = fn()
+        return r, "%d + %d launches (compare + flatten), %d + %d copies" % tuple(H.get_option(k) - a for k, a in zip((keys[0], keys[2], keys[1], keys[3]), (n[0], n[2], n[1], n[3])))
+    def composite():
+        r, c = counted(lambda: H.compare(X, comps, exact_level, "composite"))
+        return "%s; gapHeight %s" % (c, r[0])
+    def finest():
+        r, c = counted(lambda: H.compare(X, comps, exact_level, "finest"))
+        return "%s; gapHeight %s" % (c, r[0])
+    def norms_of(e, w):
+        ae = np.abs(e)
+        return np.array([(ae * w).sum(), np.sqrt(((e * e) * w).sum()), ae.max()])
+    def flatten_host():
+        t0 = time.perf_counter()
+        H.flatten(comps, exact_level, out=out)
+        t1 = time.perf_counter()
+        r = [norms_of(out[q] - xc[q], dxF * dxF) for q in range(len(comps))]
+        return "flatten %.3f ms, numpy norms %.3f ms; gapHeight %s" % (1e3 * (t1 - t0), 1e3 * (time.perf_counter() - t1), r[0])
+    def per_box():
+        t0 = time.perf_counter()
+        got = [[[L.get(f) for f in fields + (lv.F_COVER,)] for L in bl] for bl in M.level]
+        t1 = time.perf_counter()
+        acc = np.zeros((len(comps), 3))
+        for l, bl in enumerate(allb):
+            r = 1 << (exact_level - l)
+            w = (dxF * r) * (dxF * r)
+            for (lo0, lo1, hi0, hi1), (b, pi, pw, cov) in zip(bl, got[l]):
+                for q, c in enumerate((b, pi - pw)):
+                    x = xc[q][lo1 * r:(hi1 + 1) * r, lo0 * r:(hi0 + 1) * r].reshape(hi1 - lo1 + 1, r, hi0 - lo0 + 1, r).mean(axis=(1, 3))
+                    e = np.where(cov != 0, 0.0, c - x)
+                    acc[q] += (np.abs(e).sum() * w, (e * e).sum() * w, 0.0)
+                    acc[q, 2] = max(acc[q, 2], np.abs(e).max())
+        acc[:, 1] = np.sqrt(acc[:, 1])
+        return "%d get calls %.3f ms, numpy block means and norms %.3f ms; gapHeight %s" % (4 * nbx, 1e3 * (t1 - t0), 1e3 * (time.perf_counter() - t1), acc[0])
+    routes = [("compare, composite", composite), ("compare, finest", finest), ("flatten + numpy", flatten_host), ("per-box get + numpy", per_box)]
+    for r in range(rounds):
+        for name, fn in routes if r % 2 == 0 else routes[::-1]:
+            sync()
+            t0 = time.perf_counter()
+            what = fn()
+            sync()
+            print("round %d, %-19s: %.3f ms in all, %s" % (r, name, 1e3 * (time.perf_counter() - t0), what), flush=True)
+    X.close(); M.close()
+
+
 def recharge_bench(evals=50, reps=3):
     """the hierarchy's recharge call against the per-box level calls"""
     import numpy as np
@@ -395,6 +476,9 @@ if snapshot:
     sys.exit(0)
 if flatten:
     flatten_bench()
+    sys.exit(0)
+if compare:
+    compare_bench()
     sys.exit(0)
 if one_call:
     assert regrid_interval > 0, "--one-call needs --regrid-interval"
