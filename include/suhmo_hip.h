@@ -992,6 +992,49 @@ int suhmo_batch_run(suhmo_batch_t *B, const suhmo_model_params_t *mp, const suhm
 int suhmo_batch_set_option(suhmo_batch_t *B, const char *key, long value);
 int suhmo_batch_get_option(const suhmo_batch_t *B, const char *key, long *value);
 
+/* ---- MASS BALANCE (suhmo_amd/csrc/suhmo_balance.hip; DESIGN.md section 5, "Mass balance"; tests/massbalance_ref.py is the numpy twin of this text,
+ * of suhmo_balance.h and of suhmo_reduce.h): AmrHydro::check_fluxes (src/AmrHydro.cpp:440-590), the third part of the post_proc block that ends
+ * every timeStepFAS (:3643-3652), reduced on the device to seven doubles per level: the discharge through the four domain sides, the discharge
+ * through the ice margin (the "fake EB" faces) and the ice-bearing domain sides, the water volume.
+ * A FACE.  The x-face between cell lo = (i - 1, j) and cell hi = (i, j) of a box, I = i0 + i its global face column, nxg the columns of the
+ * level's domain; the arithmetic is the reference's, statement by statement, nothing contracted:
+ *       area = dy;   gradphi = (phihi - philo) * (-1.0) / dx   (a division, as the reference has it);   flux = -K * gradphi
+ *       K            SUHMO_F_BX at that face; the high domain face I = nxg lies in the canvas column right of the last cell
+ *       phihi/philo  the head beside the face as phiE / phiW return it with homog = false: the neighbour inside the box, the STORED ghost on a
+ *                    box or coarse-fine side, the wrap on a periodic side, the mixBCValues ghost on a physical side -- what the reference's
+ *                    m_head holds in its ghost cells after the last solve of the Picard loop (:3157-3164)
+ *       mhi/mlo      SUHMO_F_MASK of the two cells, read from the canvas as stored, ghost cells included
+ *       mec          as bcoef_face forms it: +-1 where |mhi - mlo| < 1e-10, otherwise 0, and 0 on both domain faces (HydroIBC.cpp:139-184)
+ *   where fabs(mec) < 1e-10, with d = mhi - mlo:   d > 0: DIR_X += flux*area;   d < 0: DIR_X -= flux*area;   d == 0 and mhi > 0: += at I == 0,
+ *   -= at I == nxg.  Independently: LO_X += flux*area at I == 0, HI_X += flux*area at I == nxg.  The y direction is the same rule with j0, nyg,
+ *   area = dx, SUHMO_F_BY and phiN / phiS.  The reference asks no question about periodicity here: a periodic side counts like any other.
+ * A CELL.  Where mask > 0: VOLUME += B * dx * dy, multiplied left to right.  m_old_gapheight is not kept on the device: the call reports the volume
+ * of the state it is given; the reference's Bold is the same call before the step (tools/mass_balance.py does that).
+ * BOXES.  The reference walks all faces of every box, so a face on a side two boxes share is counted by BOTH -- its LO / HI never (such a face is
+ * no domain face), its DIR where it is a margin face.  Restated as it is.  Every level is summed whole, covered cells included.
+ * ORDER.  That of suhmo_reduce.h and nothing else.  First stage: the walk over the valid cells; the thread of cell (i, j) folds, in this order,
+ * its low x-face, its high x-face if i == nx - 1, its low y-face, its high y-face if j == ny - 1, its volume term; each of the seven values has its
+ * own accumulator, started at 0.0; the block tree; seven doubles per workgroup.  The grid: CAP_LEVEL for a level or a member of an ensemble; for a
+ * level of boxes CAP_BOX on the level's largest box extents, ONE grid for all its boxes, boxes ascending.  Second stage per level / member: thread
+ * t takes the partials t, t + 256, ..., then the tree -- so a member's bits are those of the same model run alone, and level 0 of a hierarchy's
+ * those of the same level alone.
+ * LAUNCHES AND COPIES.  suhmo_level_mass_balance: two launches, one copy of 7 doubles, one synchronisation.  suhmo_hier_mass_balance: nlev first
+ * stages + ONE final launch (a workgroup per level), one copy of 7 nlev doubles, one synchronisation; read-only options balance_launches and
+ * balance_copies count them, balance_device_bytes is what the partial buffer holds (the hierarchy's: allocated on first use, freed with it; a
+ * regrid makes a new handle, which allocates its own).  suhmo_batch_mass_balance: one first stage over the flagged members, ONE final launch (a
+ * workgroup per flagged member), one read-back (batch_launches += 2, batch_readbacks += 1); entries of members without a flag keep the caller's.
+ * READ-ONLY: nothing a step, a snapshot or a checkpoint reads is written.
+ * REFUSED before anything is launched, out untouched, a step afterwards unaffected.  rc -1: a NULL argument; a level (a box, a member) whose face
+ * coefficients have never been formed or loaded (no solve, no step, no UpdateOperator has run on it -- after a regrid: on its new boxes).  rc -5: a
+ * rank strip; a hierarchy on rank strips, with levels dealt to the ranks or created with shadow = 1; a nested-patch handle (nx_global > 0) passed
+ * to the level call.
+ * Not built: Bold kept on the device, a balance series inside suhmo_hier_run / suhmo_batch_run, rank strips, nested patches (suhmo_amr_*), a
+ * composite balance with covered cells left out. */
+enum { SUHMO_MB_LO_X = 0, SUHMO_MB_HI_X, SUHMO_MB_LO_Y, SUHMO_MB_HI_Y, SUHMO_MB_DIR_X, SUHMO_MB_DIR_Y, SUHMO_MB_VOLUME, SUHMO_MB_COUNT };
+int suhmo_level_mass_balance(suhmo_level_t *L, double out[SUHMO_MB_COUNT], suhmo_stream_t s);
+int suhmo_hier_mass_balance(suhmo_hier_t *H, double *out /* [nlev][SUHMO_MB_COUNT] */, suhmo_stream_t s);
+int suhmo_batch_mass_balance(suhmo_batch_t *B, double *out /* [n][SUHMO_MB_COUNT] */, const int *active, suhmo_stream_t s);
+
 /* Named timers with the reference's CH_TIME labels (src/VCAMRNonLinearPoissonOp.cpp:40,69,103,277,390,660; CH_TIMER_REPORT at
  * exec/A_SHMIP/Suhmo.cpp:136).  mode 0 off (default; env SUHMO_TIMERS), 1 host wall time per scope, 2 with the device synchronised at
  * both ends of a scope (the time of the kernels it launched; serialises, for profiling only).  suhmo_timers_report writes

@@ -185,7 +185,10 @@ SYMBOLS = [
     "suhmo_hier_time_varying_recharge", "suhmo_hier_postproc_temporal", "suhmo_hier_run",
     "suhmo_hier_snapshot", "suhmo_level_snapshot", "suhmo_hier_run_out", "suhmo_hier_flatten",
     "suhmo_hier_compare",
+    "suhmo_level_mass_balance", "suhmo_hier_mass_balance", "suhmo_batch_mass_balance",
 ]
+# the seven values of a mass balance in the order of the enum SUHMO_MB_* (include/suhmo_hip.h, "MASS BALANCE")
+MB_NAMES = ("lo_x", "hi_x", "lo_y", "hi_y", "dir_x", "dir_y", "volume")
 
 
 def build(force=False):
@@ -358,6 +361,9 @@ def lib():
     L.suhmo_hier_run_out.argtypes = [C.POINTER(vp), C.POINTER(ModelParams), C.POINTER(HierSchedule), C.POINTER(HierOutput), C.POINTER(HierRunResult), vp]
     L.suhmo_hier_flatten.argtypes = [vp, ci, ci, C.POINTER(FlatComp), lp, dp, vp]
     L.suhmo_hier_compare.argtypes = [vp, vp, ci, ci, ci, C.POINTER(FlatComp), dp, dp, vp]
+    L.suhmo_level_mass_balance.argtypes = [vp, dp, vp]
+    L.suhmo_hier_mass_balance.argtypes = [vp, dp, vp]
+    L.suhmo_batch_mass_balance.argtypes = [vp, dp, ip, vp]
     _LIB = L
     return L
 

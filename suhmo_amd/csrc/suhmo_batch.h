@@ -37,6 +37,7 @@ bool suhmo_batch_step_select(suhmo_batch *B, const char *still);             // 
 BatchStep suhmo_batch_step(suhmo_batch *B, bool reduction = false);         // (reduction: a new sequence number)
 BatchSel suhmo_batch_step_subset(const suhmo_batch *B, const suhmo_model_params_t *mp_host, bool (*pick)(const suhmo_model_params_t &));
 void suhmo_batch_count(suhmo_batch *B, int launches);
+void suhmo_batch_step_faces_made(suhmo_batch *B);                           // the phase's members are about to have their face coefficients formed (suhmo_faces_made)
 int suhmo_batch_step_mg_coefficients(suhmo_batch *B, hipStream_t st);
 int suhmo_batch_step_solve(suhmo_batch *B, const suhmo_solver_params_t *sp, int *iters, hipStream_t st);   // SolveForHead_nl of the phase's members; iters[n]
 int suhmo_batch_step_read(suhmo_batch *B, hipStream_t st, double *a, double *b);                          // the pinned slots of the phase's members -> a[k], b[k]
@@ -71,3 +72,9 @@ int suhmo_batch_moulin_launch(const MoulinJob *rows, const BatchSel &sel, int nx
 int launch_postproc_columns(const OnMembers &t, double *out, hipStream_t st);
 // suhmo_postproc_temporal of those column sums on the device: out[k][6] for every member k `t` serves (one row of a run's series)
 int launch_postproc_temporal_row(const OnMembers &t, const double *cols, double *out, hipStream_t st);
+// suhmo_balance.hip
+// the mass balance of the members `t` serves: one first stage into partial (suhmo_balance_member_doubles() per member of the batch), one final launch
+// into out[k][SUHMO_MB_COUNT] for every member k served; suhmo_balance_check_member_: what member k must hold (rc -1, nothing launched)
+size_t suhmo_balance_member_doubles();
+int suhmo_balance_check_member_(const suhmo_level *L, int k);
+int launch_mass_balance(const OnMembers &t, double *partial, double *out, hipStream_t st);

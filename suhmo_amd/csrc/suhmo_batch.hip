@@ -53,6 +53,7 @@ struct suhmo_batch {
     std::vector<double> h_moulin, h_integ;                  // what is sent to / read from it
     double *d_cols, *h_cols; size_t cols_cap;               // column sums [n][8][nx] on the device and in pinned host memory
     double *d_series, *h_series; size_t series_cap;         // the finished rows of a run [rows][n][6] (suhmo_batch_run), the same way
+    double *d_bal, *h_bal;                                  // suhmo_batch_mass_balance: the members' partials and, behind them, their seven sums [n][7]; the sums in pinned memory
 };
 constexpr int SLOT_FLAG = 2 * SUHMO_BATCH_MAX;             // pinned slot: two values per member, then the sequence number
 
@@ -217,6 +218,7 @@ static int batch_vcycle(suhmo_batch *B, const suhmo_solver_params_t *sp, const B
     if (B->bottom_solver && (rc = batch_bottom_fits(B, nd - 1))) return rc;                             // (max_depth moves the bottom)
     if (sp->bcoeff_otf) {                                                                               // UpdateOperator, AverageOperator on every depth > 0
         if ((rc = launch_bcoef_fused(on(B, 0, sel), false, nullptr, 0u, st))) return rc;
+        for (int z = 0; z < sel.n; z++) suhmo_faces_made(B->mem[sel.m[z]]);
         B->launches++;
         OnMembers tabs[SUHMO_MAXDEPTH];
         for (int dep = 0; dep < nd; dep++) tabs[dep] = on(B, dep, sel);
@@ -271,6 +273,8 @@ extern "C" int suhmo_batch_destroy(suhmo_batch_t *B)
     if (B->h_cols) (void)hipHostFree(B->h_cols);
     if (B->d_series) (void)hipFree(B->d_series);
     if (B->h_series) (void)hipHostFree(B->h_series);
+    if (B->d_bal) (void)hipFree(B->d_bal);
+    if (B->h_bal) (void)hipHostFree(B->h_bal);
     if (B->hslot) (void)hipHostFree(B->hslot);
     if (B->gap) (void)suhmo_batch_destroy(B->gap);
     delete B;
@@ -425,6 +429,7 @@ extern "C" int suhmo_batch_solve(suhmo_batch_t *B, const suhmo_solver_params_t *
 
 // ---- the time step: timestep_fas over the layout Batch (suhmo_step.hip), whose hooks reach the batch through these
 int suhmo_batch_size_(const suhmo_batch *B) { return B->n; }
+void suhmo_batch_step_faces_made(suhmo_batch *B) { for (int z = 0; z < B->phase.n; z++) suhmo_faces_made(B->mem[B->phase.m[z]]); }
 void suhmo_batch_count(suhmo_batch *B, int launches) { B->launches += launches; }
 bool suhmo_batch_step_select(suhmo_batch *B, const char *still)
 {
@@ -723,6 +728,36 @@ extern "C" int suhmo_batch_postproc_table(suhmo_batch_t *B, const suhmo_model_pa
 {
     ARG(B && mp && table);
     return batch_postproc(B, mp, table, active, s, 2);
+}
+
+// ---- the mass balance of the flagged members (include/suhmo_hip.h, "MASS BALANCE"; suhmo_balance.hip): one first stage, one final launch, one
+// read-back; the rows of members without a flag stay the caller's.  Read-only
+extern "C" int suhmo_batch_mass_balance(suhmo_batch_t *B, double *out, const int *active, suhmo_stream_t s)
+{
+    ARG(B && out);
+    const BatchSel sel = flagged_members(B, active);
+    if (!sel.n) return 0;
+    int rc;
+    for (int z = 0; z < sel.n; z++) if ((rc = suhmo_balance_check_member_(B->mem[sel.m[z]], sel.m[z]))) return rc;
+    hipStream_t st = (hipStream_t)s;
+    if ((rc = batch_enter(B, st))) return rc;
+    const size_t per = suhmo_balance_member_doubles(), nres = (size_t)SUHMO_MB_COUNT * B->n;
+    if (!B->d_bal) {
+        if (hipMalloc(&B->d_bal, (B->n * per + nres) * sizeof(double)) != hipSuccess) { (void)hipGetLastError(); B->d_bal = nullptr; suhmo_set_error("batch: the partial buffer of the mass balance cannot be allocated"); return -2; }
+        if (hipHostMalloc(&B->h_bal, nres * sizeof(double), hipHostMallocDefault) != hipSuccess) {
+            (void)hipGetLastError(); (void)hipFree(B->d_bal); B->d_bal = B->h_bal = nullptr;
+            suhmo_set_error("batch: the pinned rows of the mass balance cannot be allocated"); return -2;
+        }
+    }
+    double *res = B->d_bal + B->n * per;
+    if ((rc = launch_mass_balance(on(B, 0, sel), B->d_bal, res, st))) return rc;
+    B->launches += 2;
+    const int k0 = sel.m[0], k1 = sel.m[sel.n - 1];           // (the list ascends: the rows from the first to the last flagged member)
+    HIPCHK(hipMemcpyAsync(B->h_bal + SUHMO_MB_COUNT * k0, res + SUHMO_MB_COUNT * k0, (size_t)(k1 - k0 + 1) * SUHMO_MB_COUNT * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    B->readbacks++;
+    for (int z = 0; z < sel.n; z++) memcpy(out + SUHMO_MB_COUNT * (size_t)sel.m[z], B->h_bal + SUHMO_MB_COUNT * (size_t)sel.m[z], SUHMO_MB_COUNT * sizeof(double));
+    return 0;
 }
 
 // ---- the run: AmrHydro::run (src/AmrHydro.cpp:1283-1365) of the flagged members in one call.  Per step the forcing launches from the

@@ -498,6 +498,7 @@ extern "C" int suhmo_level_update_operator(suhmo_level_t *L, int depth, suhmo_st
         if ((rc = launch_over(k_grad_ghosts<OnLevel>, t, PERIMETER, st)) || (rc = launch_re(t, st)) || (rc = launch_bcoef_faces(t, st))) return rc;
     }
     HIPCHK(hipGetLastError());
+    if (depth == 0) suhmo_faces_made(L);
     // strips: the fused relaxation recomputes halo rows, so it needs the coefficients there too (faces_deferred: the V-cycle sends them
     // with the coarse depths' faces, one message for all depths: suhmo_average_operator_all)
     if (depth == 0 && L->faces_deferred) return 0;
@@ -528,6 +529,7 @@ int suhmo_grad_cc_list(suhmo_level *L, int depth, const int2 *d_cells, int n, hi
 int suhmo_re_bcoef_unfused(suhmo_level *L, int depth, hipStream_t st)
 {
     int rc = launch_re(on_level(L, depth), st);
+    if (depth == 0) suhmo_faces_made(L);
     return rc ? rc : launch_bcoef_faces(on_level(L, depth), st);
 }
 // grad h (cell centred, extrapolated ghosts) and Re on the ghosted level, for the time step

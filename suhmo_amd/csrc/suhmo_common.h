@@ -285,7 +285,11 @@ struct suhmo_level {
     int gsrb_tile, tile_t, tile_s;      // cache-resident depths: S sweeps per launch on LDS tiles (env SUHMO_GSRB_TILE, default 1); tile edge 16 / 32
                                 // (env SUHMO_TILE_T, 0 = by size)
     struct suhmo_tagmap *tags;  // tag map of suhmo_level_tag_cells (suhmo_tags.hip), owned; NULL until the first call
+    int faces_made;             // depth 0's face coefficients have been formed (UpdateOperator in any of its forms, the time step) or loaded by the
+                                // caller at least once: what the mass balance (suhmo_balance.hip) asks before it reads them (suhmo_faces_made)
+    double *bal_buf;            // suhmo_level_mass_balance: the partials of its first stage and, behind them, its seven sums; allocated on first use
 };
+static inline void suhmo_faces_made(suhmo_level *L) { L->faces_made = 1; }
 
 enum { SUHMO_MASK_UNKNOWN = 0, SUHMO_MASK_CLEAN = 1, SUHMO_MASK_DIRTY = 2 };
 // a write to the ice mask of the level's cells or ghost ring: the coarse masks are no longer its averages, no report about it holds

@@ -885,7 +885,7 @@ static int launch_fused(suhmo_level *L, int depth, int ext_rows, hipStream_t st,
         //  workgroups, more sweeps to follow)
         if constexpr (K == 2 && NT == 64 && !RR) {
             if (part || depth != 0 || !unmasked || D.rhs_pending || g.pc || v.ext[0] || v.ext[1]) { suhmo_set_error("internal: bcoef_pending on a launch that cannot form the faces"); return -4; }
-            D.bcoef_pending = 0; L->bcoef_in_relax_count++;
+            D.bcoef_pending = 0; L->bcoef_in_relax_count++; suhmo_faces_made(L);
             hipLaunchKernelGGL((k_gsrb_fused<2, false, 64, 0, false, false, true>), dim3(g.ntiles), dim3(NT), 0, st, v, D.fp, pin, D.phi_alt, L->ph, g);
             L->relax_unmasked++; L->bcoef_unmasked++;         // (it is the cycle's unmasked UpdateOperator too)
             { std::swap(D.fp.f[SUHMO_F_PHI], D.phi_alt); suhmo_fp_changed(); }

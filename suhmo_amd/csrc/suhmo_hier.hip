@@ -181,6 +181,7 @@ int hier_update_operator(suhmo_hier *H, int l, suhmo_stream_t s)
         if ((rc = hier_cf_ff(H, l, SUHMO_F_GRADX, SUHMO_F_GRADX, SUHMO_F_GRADY, SUHMO_F_GRADY, true, HST(s)))) return rc;
         suhmo_multi m;
         if ((rc = multi_of(H, l, HST(s), m))) return rc;
+        faces_made(H, l);
         return suhmo_multi_re_bcoef(m, HST(s));
     }
     if ((rc = cf_phi(H, l - 1, s))) return rc;                    // the coarser level's own coarse-fine ghosts (its gradient reads them)
@@ -198,6 +199,7 @@ int hier_update_operator(suhmo_hier *H, int l, suhmo_stream_t s)
     }
     suhmo_multi m;
     if ((rc = multi_of(H, l, HST(s), m))) return rc;
+    faces_made(H, l);
     return suhmo_multi_re_bcoef(m, HST(s));
 }
 // RES of level l-1 = rhs - [applyOpI(phi) + reflux from level l]; LPHI of level l-1 keeps the plain L(phi)
@@ -318,6 +320,7 @@ extern "C" int suhmo_hier_destroy(suhmo_hier_t *H)
     if (H->snap_buf) (void)hipFree(H->snap_buf);
     suhmo_hier_flatten_release_(H);
     suhmo_hier_compare_release_(H);
+    suhmo_hier_balance_release_(H);
     for (int l = 0; l < 8; l++) {
         HLev &V = H->lev[l];
         V.snap_cells[0].release(); V.snap_cells[1].release();
@@ -609,6 +612,9 @@ extern "C" int suhmo_hier_get_option(const suhmo_hier_t *H, const char *key, lon
     if (!strcmp(key, "compare_launches")) { *value = H->n_cmp_launches; return 0; }
     if (!strcmp(key, "compare_copies")) { *value = H->n_cmp_copies; return 0; }
     if (!strcmp(key, "compare_device_bytes")) { *value = (long)H->cmp_cap * 8; return 0; }
+    if (!strcmp(key, "balance_launches")) { *value = H->n_bal_launches; return 0; }
+    if (!strcmp(key, "balance_copies")) { *value = H->n_bal_copies; return 0; }
+    if (!strcmp(key, "balance_device_bytes")) { *value = (long)H->bal_cap * 8; return 0; }
     if (!strcmp(key, "run_plots")) { *value = H->n_run_plots; return 0; }
     if (!strcmp(key, "run_checkpoints")) { *value = H->n_run_checkpoints; return 0; }
     if (!strcmp(key, "incremental_residual_passes")) { *value = H->n_incr_residual; return 0; }

@@ -203,6 +203,10 @@ struct suhmo_hier {
     // cmp_cap doubles), its launches and copies (read-only options compare_launches, compare_copies, compare_device_bytes)
     double *cmp_buf = nullptr; size_t cmp_cap = 0;
     long n_cmp_launches = 0, n_cmp_copies = 0;
+    // suhmo_balance.hip: the partials of every first stage of a mass balance and, behind them, the seven sums per level (allocated on first use;
+    // bal_cap doubles), its launches and copies (read-only options balance_launches, balance_copies, balance_device_bytes)
+    double *bal_buf = nullptr; size_t bal_cap = 0;
+    long n_bal_launches = 0, n_bal_copies = 0;
     long flat_fail_slot = -1;                              // option flatten_fail_slot (tests): the allocation of this scratch slot on the finest level fails
     double *red_all = nullptr;                             // partial maxima of a norm over all levels of boxes (64 per box + 16)
     struct suhmo_tagmap *tags[8] = {};                     // tag maps of suhmo_hier_tag_cells, one per level (suhmo_tags.hip), owned
@@ -235,6 +239,7 @@ inline Ref cell_ref(const suhmo_hier *H, const HLev &V, int i, int j)
 }
 inline bool dist_base(const suhmo_hier *H) { return H->shadowed; }
 inline suhmo_level *base_of(suhmo_hier *H) { return H->lev[0].box[0]; }
+inline void faces_made(suhmo_hier *H, int l) { for (suhmo_level *L : H->lev[l].box) suhmo_faces_made(L); }      // the level's face coefficients are about to be formed
 inline Ref local_ref(const HLev &V, int k, int il, int jl) { return Ref{k, cidx(V.box[k]->d[0].v, il, jl)}; }
 
 // ---- suhmo_hier_plan.hip: the plans of level l, compiled once at creation (after part_setup has dealt the boxes to the ranks)
@@ -337,3 +342,5 @@ int suhmo_hier_flatten_check_(const suhmo_hier *H, int max_level);
 int suhmo_hier_flatten_device_(suhmo_hier *H, int max_level, const FlatComps &c, hipStream_t st);
 // ---- suhmo_compare.hip: its partial buffer goes with the hierarchy
 void suhmo_hier_compare_release_(suhmo_hier *H);
+// ---- suhmo_balance.hip: likewise
+void suhmo_hier_balance_release_(suhmo_hier *H);

@@ -302,6 +302,7 @@ extern "C" int suhmo_level_destroy(suhmo_level_t *L)
     for (auto &pe : L->prof) { (void)hipEventDestroy(pe.a); (void)hipEventDestroy(pe.b); }
     if (L->xstream) { (void)hipStreamDestroy(L->xstream); (void)hipEventDestroy(L->xev[0]); (void)hipEventDestroy(L->xev[1]); }
     if (L->scratch) (void)hipFree(L->scratch);
+    if (L->bal_buf) (void)hipFree(L->bal_buf);
     if (L->bottom_ctr) (void)hipFree(L->bottom_ctr);
     suhmo_tagmap_release(L->tags);
     if (L->mask_ev) (void)hipEventDestroy(L->mask_ev);
@@ -493,6 +494,7 @@ extern "C" int suhmo_level_field_view(suhmo_level_t *L, int depth, int field, do
     if (!p) { suhmo_set_error("field allocation failed"); return -2; }
     // a writable pointer to the ice mask: the library no longer sees the writes, so it stops keeping anything about the mask for good
     if (field == SUHMO_F_MASK) { L->mask_view = 1; suhmo_mask_written(L); suhmo_level_drop_graphs(L); }
+    if (depth == 0 && (field == SUHMO_F_BX || field == SUHMO_F_BY)) suhmo_faces_made(L);      // (a writable pointer: the caller may load them)
     if (base) *base = p;
     if (pitch) *pitch = L->d[depth].v.P;
     if (origin) *origin = cidx(L->d[depth].v, 0, 0);
@@ -536,6 +538,7 @@ extern "C" int suhmo_level_set_field(suhmo_level_t *L, int depth, int field, con
     HIPCHK(hipSetDevice(L->device));
     if (field == SUHMO_F_PHI) phi_changed(L, depth);
     if (field == SUHMO_F_MASK) suhmo_mask_written(L);
+    if (depth == 0 && (field == SUHMO_F_BX || field == SUHMO_F_BY)) suhmo_faces_made(L);
     return field_io(L, depth, field, (double *)src, ghosted, on_device, true, (hipStream_t)s);
 }
 extern "C" int suhmo_level_get_field(suhmo_level_t *L, int depth, int field, double *dst, int ghosted,
@@ -566,6 +569,7 @@ extern "C" int suhmo_level_put_box(suhmo_level_t *L, int depth, int field, int i
     const DV &v = L->d[depth].v;
     if (field == SUHMO_F_PHI) phi_changed(L, depth);
     if (field == SUHMO_F_MASK) suhmo_mask_written(L);
+    if (depth == 0 && (field == SUHMO_F_BX || field == SUHMO_F_BY)) suhmo_faces_made(L);
     int r[4]; box_region(L, depth, field, ibox, r);
     int j0 = v.j0;                         // fab indices are global: local j = global j - j0
     flo0 -= v.i0; fhi0 -= v.i0;            // ... and local i = global i - i0 (AMR patch)

@@ -33,6 +33,9 @@ struct RedMax2 { static constexpr int NV = 2;           // the Picard test's pai
 struct RedSumSumMax { static constexpr int NV = 3; static constexpr bool PER_VALUE = true;      // the terms are >= 0
     static __device__ __forceinline__ double init(int) { return 0.0; }
     static __device__ __forceinline__ double op(int q, double a, double b) { return q == 2 ? fmax(a, b) : a + b; } };
+struct RedSum7 { static constexpr int NV = 7;           // the seven sums of the mass balance (suhmo_balance.hip), terms of any sign
+    static __device__ __forceinline__ double init(int) { return 0.0; }
+    static __device__ __forceinline__ double op(double a, double b) { return a + b; } };
 template <class R, class = void> struct red_per_value : std::false_type {};
 template <class R> struct red_per_value<R, std::void_t<decltype(R::PER_VALUE)>> : std::true_type {};
 template <class R> __device__ __forceinline__ double red_op(int q, double a, double b)

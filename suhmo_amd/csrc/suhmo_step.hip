@@ -509,6 +509,7 @@ struct OneLevel {
     {
         int rc;
         if ((rc = launch_bcoef_faces(on_level(base, 0), st))) return rc;                          // aCoeff_bCoeff :3087-3102
+        suhmo_faces_made(base);
         if ((rc = level_melt(base, mp, dt, 0, mp->diffFactor != 0.0, st))) return rc;   // lagged melt rate :2548-2551, :2982-2992
         return exchange1(base, SUHMO_F_RHS, st);                                        // rank strips relax their halo rows redundantly
     }
@@ -591,6 +592,7 @@ struct Batch {
     {
         const BatchStep p = suhmo_batch_step(B);
         int rc = launch_bcoef_faces(on_members(p.t, p.sel, *p.v), st); if (rc) return rc;      // aCoeff_bCoeff :3087-3102
+        suhmo_batch_step_faces_made(B);
         suhmo_batch_count(B, 1);
         return melt(mp, dt, 0, true);                                                    // lagged melt rate :2548-2551, :2982-2992
     }
@@ -706,6 +708,7 @@ struct Nested {
         for (int l = 0; l < nlev; l++) {
             if (!lv[l]) continue;
             if ((rc = launch_bcoef_faces(on_level(lv[l], 0), st))) return rc;                      // aCoeff_bCoeff :3087-3102
+            suhmo_faces_made(lv[l]);
             if ((rc = level_melt(lv[l], mp, dt, 0, mp->diffFactor != 0.0, st))) return rc;
             if ((rc = exchange1(lv[l], SUHMO_F_RHS, st))) return rc;                   // halo rows relaxed redundantly
         }
@@ -884,6 +887,7 @@ struct BoxUnions {
         int rc;
         for (int l = 0; l < nlev; l++)                                                          // aCoeff_bCoeff :3087-3102
             if ((rc = on_hier_level(H, l, st, [&](const auto &t) { return launch_bcoef_faces(t, st); }))) return rc;
+        for (int l = 0; l < nlev; l++) faces_made(H, l);
         for (int l = 0; l < nlev; l++) if ((rc = hier_melt(H, l, mp, dt, 0, mp->diffFactor != 0.0, st))) return rc;
         return exchange1(base, SUHMO_F_RHS, st);                                                // rank strips: halo rows relaxed redundantly
     }

@@ -282,6 +282,14 @@ class HipModel:
         check(capi.lib().suhmo_postproc_temporal(a.ctypes.data_as(C.POINTER(C.c_double)), self.nx, self.dx, out.ctypes.data_as(C.POINTER(C.c_double))))
         return out
 
+    def mass_balance(self):
+        """AmrHydro::check_fluxes reduced on the device (suhmo_level_mass_balance; include/suhmo_hip.h, "MASS BALANCE"): the discharge through
+        the four domain sides (lo_x, hi_x, lo_y, hi_y), through the ice margin and the ice-bearing domain sides (dir_x, dir_y) and the water
+        volume of the state as it is -> a dict of the seven names (capi.MB_NAMES).  Read-only"""
+        out = np.zeros(len(capi.MB_NAMES))
+        check(capi.lib().suhmo_level_mass_balance(self.level.h, out.ctypes.data_as(C.POINTER(C.c_double)), self.level.stream))
+        return dict(zip(capi.MB_NAMES, out.tolist()))
+
     def postproc_table(self):
         """SHMIP cross-section table (src/AmrHydro.cpp:3647-4102) from the device-resident state, reduced on the host"""
         mask = self.get("mask")
@@ -428,6 +436,15 @@ class HipBatchModel:
     def postproc_table_device_all(self, active=None, out=None):
         """the SHMIP cross-section table of every member, (n, nx, 8)"""
         return self._postproc_all(capi.lib().suhmo_batch_postproc_table, (self.nx, 8), active, out)
+
+    def mass_balance_all(self, active=None, out=None):
+        """the mass balance of every member (suhmo_batch_mass_balance), (n, 7) in the order of capi.MB_NAMES: one first stage, one final launch
+        and one read-back for all of them, every member bit for bit HipModel.mass_balance of the same model alone; out: an array whose rows of
+        the members that are not active are kept.  Read-only"""
+        t = np.zeros((self.n, len(capi.MB_NAMES))) if out is None else out
+        assert t.shape == (self.n, len(capi.MB_NAMES)) and t.dtype == np.float64 and t.flags.c_contiguous
+        check(capi.lib().suhmo_batch_mass_balance(self.batch.h, t.ctypes.data_as(C.POINTER(C.c_double)), self._active(active), self.batch.stream))
+        return t
 
     def run(self, n_steps, dt, T_K=None, background=None, moulins=None, moulin_factor=None, ramp=None, diag_every=0, active=None, rows=None):
         """the time loop of the active members in ONE call (suhmo_batch_run): per step the forcing of the schedule, the time step and, after
@@ -697,6 +714,14 @@ class HipHierModel:
             exact_level = (exact_model.nx // self.level[0][0].nx).bit_length() - 1
         a = self.hier.compare(exact_model.level, [c for _, c in self.CMP_COMPONENTS], exact_level, mode)
         return {nm: a[q] for q, (nm, _) in enumerate(self.CMP_COMPONENTS)}
+
+    def mass_balance(self):
+        """AmrHydro::check_fluxes of every level, reduced on the device (suhmo_hier_mass_balance): a list of dicts of the seven names
+        (capi.MB_NAMES), level 0 first; every level is summed whole, as the reference does.  A first stage per level, one final launch, one
+        copy of 7 nlev doubles.  Read-only"""
+        out = np.zeros((self.hier.nlev, len(capi.MB_NAMES)))
+        check(capi.lib().suhmo_hier_mass_balance(self.hier.h, out.ctypes.data_as(C.POINTER(C.c_double)), self.hier.stream))
+        return [dict(zip(capi.MB_NAMES, row.tolist())) for row in out]
 
     def restrict_tags(self, level, boxes):
         """levelTags &= tagSubset (suhmo_hier_restrict_tags): every entry of the tag map of `level` that lies in none of `boxes`
