@@ -1028,12 +1028,76 @@ int suhmo_batch_get_option(const suhmo_batch_t *B, const char *key, long *value)
  * coefficients have never been formed or loaded (no solve, no step, no UpdateOperator has run on it -- after a regrid: on its new boxes).  rc -5: a
  * rank strip; a hierarchy on rank strips, with levels dealt to the ranks or created with shadow = 1; a nested-patch handle (nx_global > 0) passed
  * to the level call.
- * Not built: Bold kept on the device, a balance series inside suhmo_hier_run / suhmo_batch_run, rank strips, nested patches (suhmo_amr_*), a
- * composite balance with covered cells left out. */
+ * Not built: rank strips, nested patches (suhmo_amr_*), a composite balance with covered cells left out.  Bold kept on the device and the series
+ * inside suhmo_hier_run / suhmo_batch_run: "WATER BUDGET" below. */
 enum { SUHMO_MB_LO_X = 0, SUHMO_MB_HI_X, SUHMO_MB_LO_Y, SUHMO_MB_HI_Y, SUHMO_MB_DIR_X, SUHMO_MB_DIR_Y, SUHMO_MB_VOLUME, SUHMO_MB_COUNT };
 int suhmo_level_mass_balance(suhmo_level_t *L, double out[SUHMO_MB_COUNT], suhmo_stream_t s);
 int suhmo_hier_mass_balance(suhmo_hier_t *H, double *out /* [nlev][SUHMO_MB_COUNT] */, suhmo_stream_t s);
 int suhmo_batch_mass_balance(suhmo_batch_t *B, double *out /* [n][SUHMO_MB_COUNT] */, const int *active, suhmo_stream_t s);
+
+/* ---- WATER BUDGET (suhmo_amd/csrc/suhmo_balance.hip, suhmo_run.hip, suhmo_batch.hip; DESIGN.md section 5, "Water budget"; tests/budget_ref.py is
+ * the numpy twin): the conservation record the reference prints after every step of a run with AmrHydro.post_proc = true -- check_fluxes with
+ * B/Bold (src/AmrHydro.cpp:440-590) and the line "Time(months) VOL_waterTot rechargeTOT ramp" (:4036-4038) -- as TEN doubles per level or member:
+ *   0 .. 6        the seven values of "MASS BALANCE": the same rule, the same order, the same bits (mb_fold of suhmo_balance.h is stated once)
+ *   VOLUME_OLD    the reference's BtotOld: sum of B dx dy over the cells with mask > 0 of the gap height the last TRACKED step started from.  The
+ *                 device updates b in place, so the sum is measured at the entry of the step, before anything writes b (after the regrid, reload
+ *                 and forcing of a run's step: the reference copies m_old_gapheight at the top of timeStepFAS).  First stage k_volume (mask and B
+ *                 only, 16 B per cell) on the grid, walk and tree of k_balance; the partials stay on the device, nothing is copied or
+ *                 synchronised; the final stage of a budget finishes them with the second-stage walk.  So the value is bit for bit the VOLUME of
+ *                 the mass-balance call made immediately before that step.  A quiet NaN where no tracked step has run on that level or member:
+ *                 option off, no step yet, a member the tracked steps left out from the start, EVERY level of the new handle after a regrid.
+ *   RECH_EXT      the two parts of rechargeTOT (:3766-3773), per cell with ice = mask > 0 as d_postproc_columns forms them:
+ *   RECH_MELT         src = use_moulin_source ? MSRC * ramp + distributed_input : (ice ? distributed_input : 0.0)
+ *                     ice:  ext += src * dy * dx;   melt += (MR / rho_w) * dy * dx
+ *                 folded AFTER the volume term of the same cell, each with its own accumulator started at 0.0, reduced in the order of
+ *                 suhmo_reduce.h like the other values.  This is NOT the per-column order of the SHMIP table (suhmo_level_postproc_partial sums
+ *                 a column's rows first): the two agree to rounding only.  The reference forms the line on level 0; here every level has its own.
+ * mp supplies ramp, distributed_input, rho_w and use_moulin_source (an ensemble: each member's own row of mp[n]).
+ * OPTION track_old_volume (suhmo_level_set_option, suhmo_hier_set_option, suhmo_batch_set_option; 0 or 1, default 0: every launch sequence and
+ * counter of a step is what it was).  With 1, suhmo_level_timestep, suhmo_hier_timestep and suhmo_batch_timestep begin -- after their refusals --
+ * with the k_volume first stage into a buffer the handle owns (allocated on first use, freed with it): one launch for a level, one per level of a
+ * hierarchy (never one per box), one for the members the step serves; members it does not serve keep what they had.  suhmo_hier_regrid carries
+ * the option to the new handle as it carries the others; the kept volume does not carry over.  Refused with rc -5 on rank strips.
+ * LAUNCHES AND COPIES of the stand-alone calls, as the mass-balance calls: suhmo_level_water_budget: two launches, one copy of 10 doubles, one
+ * synchronisation.  suhmo_hier_water_budget: nlev first stages (k_budget: head, mask, B, BX, BY, MR, MSRC; nine values per workgroup) + ONE final
+ * launch (a workgroup per level: the nine sums, VOLUME_OLD from the kept partials, ten doubles), one copy, one synchronisation.
+ * suhmo_batch_water_budget: one first stage, one final launch (a workgroup per flagged member), one read-back (batch_launches += 2,
+ * batch_readbacks += 1); rows of members without a flag keep the caller's.  Read-only options of a hierarchy: budget_launches (the k_volume
+ * launches of tracked steps, the first stages and final launches of budgets), budget_copies, budget_device_bytes (the partial buffers the handle
+ * holds); a run carries the first two across its regrids.  An ensemble counts in batch_launches and batch_readbacks.  READ-ONLY calls.
+ * REFUSED before anything is launched, out untouched, a step afterwards unaffected: everything the mass-balance calls refuse, with their codes;
+ * rc -1: mp is NULL; SUHMO_F_MR is missing (no time step has run); use_moulin_source without SUHMO_F_MSRC (the message names the level and box,
+ * or the member).
+ * THE SERIES INSIDE THE RUNS.  suhmo_hier_run_bud and suhmo_batch_run_bud with bud = NULL ARE suhmo_hier_run_out and suhmo_batch_run (which
+ * are thin wrappers of them).  With bud: a row after step k when (k + 1) % every == 0.  The run sets track_old_volume = 1 for exactly the steps
+ * that end in a row (the other steps run with the caller's setting) and puts the caller's setting back on every way out.  After such a step --
+ * and after the daily row if both fall together -- the first stages and the final stage, which writes straight into a device series the run
+ * owns: no copy and no synchronisation per row; after the last step the series comes back in ONE copy (budget_copies += 1; an ensemble:
+ * batch_readbacks += 1).  The series belongs to the run and survives a regrid's change of handle; the partial buffers belong to the handle.
+ * Entries of levels the hierarchy does not have at that row, and of members without a flag, keep the caller's values.  A failing step, regrid,
+ * reload or output callback ends the run as it does without a budget; the rows finished so far are copied out and n_rows is exact.
+ * Refused before the first launch, rc -1: every < 1; rows NULL; nlev NULL for a hierarchy; lev_cap too small; what the stand-alone call refuses of
+ * the starting state, except the face coefficients and SUHMO_F_MR, which the first step forms; use_moulin_source with no forcing of the run to
+ * write the source and no source on some box (the run's own rule).  rc -5: rank strips, levels dealt to the ranks, shadow = 1.
+ * Not built: rank strips; nested patches (suhmo_amr_*); a composite budget with covered cells left out (the reference gives no rule for a face
+ * between a covered and an uncovered cell); the band-discharge lines of post_proc_shmip_temporal (:4055-4078; the reference's own dump_PP.py
+ * does not read them). */
+enum { SUHMO_WB_LO_X = 0, SUHMO_WB_HI_X, SUHMO_WB_LO_Y, SUHMO_WB_HI_Y, SUHMO_WB_DIR_X, SUHMO_WB_DIR_Y, SUHMO_WB_VOLUME,
+       SUHMO_WB_VOLUME_OLD, SUHMO_WB_RECH_EXT, SUHMO_WB_RECH_MELT, SUHMO_WB_COUNT };
+int suhmo_level_water_budget(suhmo_level_t *L, const suhmo_model_params_t *mp, double out[SUHMO_WB_COUNT], suhmo_stream_t s);
+int suhmo_hier_water_budget(suhmo_hier_t *H, const suhmo_model_params_t *mp, double *out /* [nlev][SUHMO_WB_COUNT] */, suhmo_stream_t s);
+int suhmo_batch_water_budget(suhmo_batch_t *B, const suhmo_model_params_t *mp, double *out /* [n][SUHMO_WB_COUNT] */, const int *active, suhmo_stream_t s);
+typedef struct suhmo_run_budget {
+    int every;        /* a row after step k when (k + 1) % every == 0; > 0 */
+    int lev_cap;      /* hierarchy: levels a row has room for (>= min(max_level + 1, 8) when the run regrids, >= nlev otherwise); ensemble: ignored */
+    double *rows;     /* hierarchy [n_steps / every][lev_cap][SUHMO_WB_COUNT]; ensemble [n_steps / every][n][SUHMO_WB_COUNT] */
+    int *nlev;        /* hierarchy [n_steps / every]: levels the hierarchy had at that row; ensemble: may be NULL */
+    int n_rows;       /* out */
+} suhmo_run_budget_t;
+int suhmo_hier_run_bud(suhmo_hier_t **H, const suhmo_model_params_t *mp, const suhmo_hier_schedule_t *sch, const suhmo_hier_output_t *out,
+                       suhmo_run_budget_t *bud, suhmo_hier_run_result_t *res, suhmo_stream_t s);
+int suhmo_batch_run_bud(suhmo_batch_t *B, const suhmo_model_params_t *mp, const suhmo_batch_schedule_t *sch, const int *active,
+                        suhmo_run_budget_t *bud, suhmo_batch_run_result_t *res, suhmo_stream_t s);
 
 /* Named timers with the reference's CH_TIME labels (src/VCAMRNonLinearPoissonOp.cpp:40,69,103,277,390,660; CH_TIMER_REPORT at
  * exec/A_SHMIP/Suhmo.cpp:136).  mode 0 off (default; env SUHMO_TIMERS), 1 host wall time per scope, 2 with the device synchronised at

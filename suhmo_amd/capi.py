@@ -65,6 +65,11 @@ class BatchRunResult(C.Structure):
                 ("rows", C.POINTER(C.c_double))]
 
 
+class RunBudget(C.Structure):
+    """suhmo_run_budget_t: the water budget series of suhmo_hier_run_bud / suhmo_batch_run_bud (include/suhmo_hip.h, "WATER BUDGET")"""
+    _fields_ = [("every", C.c_int), ("lev_cap", C.c_int), ("rows", C.POINTER(C.c_double)), ("nlev", C.POINTER(C.c_int)), ("n_rows", C.c_int)]
+
+
 class GridParams(C.Structure):
     """suhmo_grid_params_t: what the reference hands to BRMeshRefine"""
     _fields_ = [("fill_ratio", C.c_double), ("block_factor", C.c_int), ("max_box_size", C.c_int), ("nesting_radius", C.c_int)]
@@ -186,9 +191,13 @@ SYMBOLS = [
     "suhmo_hier_snapshot", "suhmo_level_snapshot", "suhmo_hier_run_out", "suhmo_hier_flatten",
     "suhmo_hier_compare",
     "suhmo_level_mass_balance", "suhmo_hier_mass_balance", "suhmo_batch_mass_balance",
+    "suhmo_level_water_budget", "suhmo_hier_water_budget", "suhmo_batch_water_budget", "suhmo_hier_run_bud", "suhmo_batch_run_bud",
 ]
 # the seven values of a mass balance in the order of the enum SUHMO_MB_* (include/suhmo_hip.h, "MASS BALANCE")
 MB_NAMES = ("lo_x", "hi_x", "lo_y", "hi_y", "dir_x", "dir_y", "volume")
+# the ten values of a water budget in the order of the enum SUHMO_WB_* ("WATER BUDGET"): those seven, the volume the last tracked step started
+# from (NaN: none), the two parts of rechargeTOT
+WB_NAMES = MB_NAMES + ("volume_old", "recharge_ext", "recharge_melt")
 
 
 def build(force=False):
@@ -364,6 +373,12 @@ def lib():
     L.suhmo_level_mass_balance.argtypes = [vp, dp, vp]
     L.suhmo_hier_mass_balance.argtypes = [vp, dp, vp]
     L.suhmo_batch_mass_balance.argtypes = [vp, dp, ip, vp]
+    L.suhmo_level_water_budget.argtypes = [vp, C.POINTER(ModelParams), dp, vp]
+    L.suhmo_hier_water_budget.argtypes = [vp, C.POINTER(ModelParams), dp, vp]
+    L.suhmo_batch_water_budget.argtypes = [vp, C.POINTER(ModelParams), dp, ip, vp]
+    L.suhmo_hier_run_bud.argtypes = [C.POINTER(vp), C.POINTER(ModelParams), C.POINTER(HierSchedule), C.POINTER(HierOutput), C.POINTER(RunBudget),
+                                     C.POINTER(HierRunResult), vp]
+    L.suhmo_batch_run_bud.argtypes = [vp, C.POINTER(ModelParams), C.POINTER(BatchSchedule), ip, C.POINTER(RunBudget), C.POINTER(BatchRunResult), vp]
     _LIB = L
     return L
 

@@ -42,10 +42,12 @@ __device__ __forceinline__ void mb_cell(double mask, double B, double dx, double
 {
     vol = mask > 0.0 ? vol + B * dx * dy : vol;
 }
-// cell (i, j) of the box with view v: head, mask, B, bx, by its canvases; a[SUHMO_MB_COUNT] the thread's seven values
-__device__ __forceinline__ void mb_fold(const DV &v, const double *__restrict__ head, const double *__restrict__ mask, const double *__restrict__ B,
-                                        const double *__restrict__ bx, const double *__restrict__ by, int i, int j, double (&a)[SUHMO_MB_COUNT])
+// cell (i, j) of the box with view v: head, mask, B, bx, by its canvases; a[0 .. SUHMO_MB_COUNT - 1] the thread's seven values (N > SUHMO_MB_COUNT:
+// the water budget's accumulators, whose first seven are these)
+template <int N> __device__ __forceinline__ void mb_fold(const DV &v, const double *__restrict__ head, const double *__restrict__ mask, const double *__restrict__ B,
+                                                         const double *__restrict__ bx, const double *__restrict__ by, int i, int j, double (&a)[N])
 {
+    static_assert(N >= SUHMO_MB_COUNT, "the seven values of the mass balance come first");
     const int idx = cidx(v, i, j);
     const int I = v.i0 + i, J = v.j0 + j;
     const double c = head[idx], m = mask[idx];
@@ -60,4 +62,26 @@ __device__ __forceinline__ void mb_fold(const DV &v, const double *__restrict__ 
         mb_face(phiN(v, head, idx, j, c, false), c, by[idx + v.P], mask[idx + v.P], m, v.dy, v.dx, J + 1 == 0, J + 1 == v.nyg,
                 a[SUHMO_MB_LO_Y], a[SUHMO_MB_HI_Y], a[SUHMO_MB_DIR_Y]);
     mb_cell(m, B[idx], v.dx, v.dy, a[SUHMO_MB_VOLUME]);
+}
+
+// ---- "WATER BUDGET" (include/suhmo_hip.h): what a first stage of the budget leaves per workgroup -- the seven values above, then the two parts of
+// the reference's rechargeTOT (src/AmrHydro.cpp:3766-3773) as d_postproc_columns (suhmo_postproc.hip) forms them per cell, statement by statement
+enum { WB_P_EXT = SUHMO_MB_COUNT, WB_P_MELT, WB_P_COUNT };
+// ms: SUHMO_F_MSRC where the model has a moulin source (use_moulin_source), else NULL; mr: SUHMO_F_MR
+__device__ __forceinline__ void wb_cell(double mask, const double *__restrict__ ms, const double *__restrict__ mr, int idx, double ramp, double distributed_input,
+                                        double rho_w, double dx, double dy, double &ext, double &melt)
+{
+    const bool ice = mask > 0.0;
+    const double src = ms ? ms[idx] * ramp + distributed_input : (ice ? distributed_input : 0.0);
+    ext = ice ? ext + src * dy * dx : ext;
+    melt = ice ? melt + (mr[idx] / rho_w) * dy * dx : melt;
+}
+// mb_fold of the cell, then its two recharge terms: after the volume term, each into its own accumulator
+__device__ __forceinline__ void wb_fold(const DV &v, const double *__restrict__ head, const double *__restrict__ mask, const double *__restrict__ B,
+                                        const double *__restrict__ bx, const double *__restrict__ by, const double *__restrict__ mr, const double *__restrict__ ms,
+                                        double ramp, double distributed_input, double rho_w, int i, int j, double (&a)[WB_P_COUNT])
+{
+    mb_fold(v, head, mask, B, bx, by, i, j, a);
+    const int idx = cidx(v, i, j);
+    wb_cell(mask[idx], ms, mr, idx, ramp, distributed_input, rho_w, v.dx, v.dy, a[WB_P_EXT], a[WB_P_MELT]);
 }

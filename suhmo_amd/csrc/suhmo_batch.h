@@ -77,3 +77,14 @@ int launch_postproc_temporal_row(const OnMembers &t, const double *cols, double 
 size_t suhmo_balance_member_doubles();
 int suhmo_balance_check_member_(const suhmo_level *L, int k);
 int launch_mass_balance(const OnMembers &t, double *partial, double *out, hipStream_t st);
+// the water budget of the members `t` serves (t.mp: the members' device rows): one first stage into partial (suhmo_budget_member_doubles() per member
+// of the batch), one final launch into out[k][SUHMO_WB_COUNT] -- a DEVICE address -- for every member k served.  vol: the volume partials tracked
+// steps kept (npo per member, launch_member_volumes; NULL: none), have: bit k = member k has some; VOLUME_OLD of the others is a quiet NaN
+size_t suhmo_budget_member_doubles();
+size_t suhmo_volume_member_doubles();
+int suhmo_budget_check_member_(const suhmo_level *L, const suhmo_model_params_t *mp, int k, const char *who, bool faces, bool source);
+int launch_member_volumes(const OnMembers &t, double *vol, int *np, hipStream_t st);
+int launch_water_budget(const OnMembers &t, double *partial, const double *vol, int npo, unsigned long long have, double *out, hipStream_t st);
+// suhmo_batch.hip: option track_old_volume is on, and then the first stage above for the members the step serves (suhmo_step.hip calls it behind
+// suhmo_batch_step_begin)
+int suhmo_batch_step_track_volume(suhmo_batch *B, hipStream_t st);

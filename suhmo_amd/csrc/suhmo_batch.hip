@@ -55,6 +55,12 @@ struct suhmo_batch {
     double *d_cols, *h_cols; size_t cols_cap;               // column sums [n][8][nx] on the device and in pinned host memory
     double *d_series, *h_series; size_t series_cap;         // the finished rows of a run [rows][n][6] (suhmo_batch_run), the same way
     double *d_bal, *h_bal;                                  // suhmo_batch_mass_balance: the members' partials and, behind them, their seven sums [n][7]; the sums in pinned memory
+    // "WATER BUDGET": option track_old_volume; the volume partials the tracked steps kept (vol_np per member; bit k of vol_have: member k has some);
+    // the members' partials of a budget and, behind them, their ten values [n][10], those in pinned memory too; the rows of a run's series
+    int track_old_volume, vol_np;
+    double *d_vol; unsigned long long vol_have;
+    double *d_wb, *h_wb;
+    double *d_wbs, *h_wbs; size_t wbs_cap;
 };
 constexpr int SLOT_FLAG = 2 * SUHMO_BATCH_MAX;             // pinned slot: two values per member, then the sequence number
 
@@ -275,6 +281,11 @@ extern "C" int suhmo_batch_destroy(suhmo_batch_t *B)
     if (B->h_series) (void)hipHostFree(B->h_series);
     if (B->d_bal) (void)hipFree(B->d_bal);
     if (B->h_bal) (void)hipHostFree(B->h_bal);
+    if (B->d_vol) (void)hipFree(B->d_vol);
+    if (B->d_wb) (void)hipFree(B->d_wb);
+    if (B->h_wb) (void)hipHostFree(B->h_wb);
+    if (B->d_wbs) (void)hipFree(B->d_wbs);
+    if (B->h_wbs) (void)hipHostFree(B->h_wbs);
     if (B->hslot) (void)hipHostFree(B->hslot);
     if (B->gap) (void)suhmo_batch_destroy(B->gap);
     delete B;
@@ -538,6 +549,24 @@ int suhmo_batch_step_begin(suhmo_batch *B, const suhmo_model_params_t *mp, hipSt
     B->phase = B->everyone;
     return 0;
 }
+// "WATER BUDGET", option track_old_volume: the volume the step starts from, of the members it serves; the others keep what they had
+int suhmo_batch_step_track_volume(suhmo_batch *B, hipStream_t st)
+{
+    if (!B->track_old_volume || B->everyone.n <= 0) return 0;
+    for (int z = 0; z < B->everyone.n; z++) {
+        const FP &fp = B->mem[B->everyone.m[z]]->d[0].fp;
+        if (!fp.f[SUHMO_F_MASK] || !fp.f[SUHMO_F_B]) { suhmo_set_error("batch: track_old_volume: member %d holds no ice mask or no gap height", (int)B->everyone.m[z]); return -1; }
+    }
+    if (!B->d_vol && hipMalloc(&B->d_vol, B->n * suhmo_volume_member_doubles() * sizeof(double)) != hipSuccess) {
+        (void)hipGetLastError(); B->d_vol = nullptr; suhmo_set_error("batch: the volume partials cannot be allocated"); return -2;
+    }
+    int np = 0, rc = launch_member_volumes(on(B, 0, B->everyone), B->d_vol, &np, st);
+    if (rc) return rc;
+    B->launches++;
+    B->vol_np = np;
+    for (int z = 0; z < B->everyone.n; z++) B->vol_have |= 1ull << B->everyone.m[z];
+    return 0;
+}
 extern "C" int suhmo_batch_timestep(suhmo_batch_t *B, const suhmo_model_params_t *mp, double dt, int cur_step, int *picard_iters, int *vcycles,
                                     suhmo_stream_t s)
 {
@@ -760,6 +789,54 @@ extern "C" int suhmo_batch_mass_balance(suhmo_batch_t *B, double *out, const int
     return 0;
 }
 
+// ---- the water budget of the flagged members (include/suhmo_hip.h, "WATER BUDGET"; suhmo_balance.hip): as the mass balance, with mp[n] on the
+// device for the members' ramp, distributed input, water density and source switch.  Read-only
+static int batch_budget_check(const suhmo_batch *B, const suhmo_model_params_t *mp, const BatchSel &sel, const char *who, bool faces, bool source)
+{
+    int rc;
+    for (int z = 0; z < sel.n; z++) if ((rc = suhmo_budget_check_member_(B->mem[sel.m[z]], &mp[sel.m[z]], sel.m[z], who, faces, source))) return rc;
+    return 0;
+}
+static int batch_budget_buffers(suhmo_batch *B)
+{
+    if (B->d_wb) return 0;
+    const size_t per = suhmo_budget_member_doubles(), nres = (size_t)SUHMO_WB_COUNT * B->n;
+    if (hipMalloc(&B->d_wb, (B->n * per + nres) * sizeof(double)) != hipSuccess) { (void)hipGetLastError(); B->d_wb = nullptr; suhmo_set_error("batch: the partial buffer of the water budget cannot be allocated"); return -2; }
+    if (hipHostMalloc(&B->h_wb, nres * sizeof(double), hipHostMallocDefault) != hipSuccess) {
+        (void)hipGetLastError(); (void)hipFree(B->d_wb); B->d_wb = B->h_wb = nullptr;
+        suhmo_set_error("batch: the pinned rows of the water budget cannot be allocated"); return -2;
+    }
+    return 0;
+}
+// the first stage and the final launch; out: a DEVICE address, [n][SUHMO_WB_COUNT]
+static int batch_budget_launch(suhmo_batch *B, const suhmo_model_params_t *mp, const BatchSel &sel, double *out, hipStream_t st)
+{
+    int rc = batch_enter(B, st); if (rc) return rc;
+    if ((rc = batch_mp_sync(B, mp, st))) return rc;
+    if ((rc = launch_water_budget(on_members(tab(B, 0), sel, view(B, 0), B->d_mp), B->d_wb, B->d_vol, B->vol_np, B->vol_have, out, st))) return rc;
+    B->launches += 2;
+    return 0;
+}
+extern "C" int suhmo_batch_water_budget(suhmo_batch_t *B, const suhmo_model_params_t *mp, double *out, const int *active, suhmo_stream_t s)
+{
+    ARG(B && mp && out);
+    const BatchSel sel = flagged_members(B, active);
+    if (!sel.n) return 0;
+    int rc;
+    if ((rc = batch_budget_check(B, mp, sel, "suhmo_batch_water_budget", true, true))) return rc;
+    hipStream_t st = (hipStream_t)s;
+    HIPCHK(hipSetDevice(B->device));
+    if ((rc = batch_budget_buffers(B))) return rc;
+    double *res = B->d_wb + B->n * suhmo_budget_member_doubles();
+    if ((rc = batch_budget_launch(B, mp, sel, res, st))) return rc;
+    const int k0 = sel.m[0], k1 = sel.m[sel.n - 1];           // (the list ascends: the rows from the first to the last flagged member)
+    HIPCHK(hipMemcpyAsync(B->h_wb + SUHMO_WB_COUNT * k0, res + SUHMO_WB_COUNT * k0, (size_t)(k1 - k0 + 1) * SUHMO_WB_COUNT * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    B->readbacks++;
+    for (int z = 0; z < sel.n; z++) memcpy(out + SUHMO_WB_COUNT * (size_t)sel.m[z], B->h_wb + SUHMO_WB_COUNT * (size_t)sel.m[z], SUHMO_WB_COUNT * sizeof(double));
+    return 0;
+}
+
 // ---- the run: AmrHydro::run (src/AmrHydro.cpp:1283-1365) of the flagged members in one call.  Per step the forcing launches from the
 // schedule's values, suhmo_batch_timestep_run, and on a diagnostic step the column sums and the row finished on the device
 // (d_postproc_temporal_row) into B->d_series[row][n][6]; one copy and one synchronisation after the last step
@@ -774,13 +851,34 @@ static int batch_run_series_out(suhmo_batch *B, const BatchSel &sel, int rows, d
         for (int z = 0; z < sel.n; z++) memcpy(out + r * per + 6 * (size_t)sel.m[z], B->h_series + r * per + 6 * (size_t)sel.m[z], 6 * sizeof(double));
     return 0;
 }
+// the budget rows of a run [rows][n][10] (B->d_wbs): one copy, one synchronisation; the entries of members without a flag stay the caller's
+static int batch_run_budget_out(suhmo_batch *B, const BatchSel &sel, int rows, double *out, hipStream_t st)
+{
+    if (rows <= 0) return 0;
+    const size_t per = (size_t)SUHMO_WB_COUNT * B->n;
+    HIPCHK(hipMemcpyAsync(B->h_wbs, B->d_wbs, rows * per * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    B->readbacks++;
+    for (int r = 0; r < rows; r++)
+        for (int z = 0; z < sel.n; z++)
+            memcpy(out + r * per + SUHMO_WB_COUNT * (size_t)sel.m[z], B->h_wbs + r * per + SUHMO_WB_COUNT * (size_t)sel.m[z], SUHMO_WB_COUNT * sizeof(double));
+    return 0;
+}
 extern "C" int suhmo_batch_run(suhmo_batch_t *B, const suhmo_model_params_t *mp, const suhmo_batch_schedule_t *sch, const int *active,
                                suhmo_batch_run_result_t *res, suhmo_stream_t s)
+{
+    return suhmo_batch_run_bud(B, mp, sch, active, nullptr, res, s);
+}
+// bud != NULL: "WATER BUDGET", the series inside the runs -- a budget row of every flagged member after the steps that end one, finished on the
+// device into B->d_wbs; those steps run with track_old_volume = 1, the others with the caller's setting, which every way out restores
+extern "C" int suhmo_batch_run_bud(suhmo_batch_t *B, const suhmo_model_params_t *mp, const suhmo_batch_schedule_t *sch, const int *active,
+                                   suhmo_run_budget_t *bud, suhmo_batch_run_result_t *res, suhmo_stream_t s)
 {
     SUHMO_TIME("AmrHydro::run");
     ARG(B && mp && sch && res);
     hipStream_t st = (hipStream_t)s;
     res->steps_done = 0; res->n_rows = 0;
+    if (bud) bud->n_rows = 0;
     if (sch->n_steps < 1) { suhmo_set_error("batch: run: n_steps = %d (at least 1)", sch->n_steps); return -1; }
     if (!(sch->dt > 0.0) || sch->first_cur_step < 1 || sch->diag_every < 0) { suhmo_set_error("batch: run: dt > 0, first_cur_step >= 1 and diag_every >= 0"); return -1; }
     if (sch->n_members != B->n) { suhmo_set_error("batch: run: the schedule is laid out for %d members, the batch has %d", sch->n_members, B->n); return -1; }
@@ -792,6 +890,9 @@ extern "C" int suhmo_batch_run(suhmo_batch_t *B, const suhmo_model_params_t *mp,
     if (recharge && moulins) { suhmo_set_error("batch: run: a temperature schedule and a moulin schedule write the same source term (SUHMO_F_MSRC): give one"); return -1; }
     const int n = B->n, total_rows = sch->diag_every ? sch->n_steps / sch->diag_every : 0;
     if (total_rows > 0 && !res->rows) { suhmo_set_error("batch: run: %d rows and no array for them", total_rows); return -1; }
+    if (bud && bud->every < 1) { suhmo_set_error("batch: run: a budget row every %d steps (at least 1)", bud->every); return -1; }
+    if (bud && !bud->rows) { suhmo_set_error("batch: run: a budget series and no array for its rows"); return -1; }
+    const int total_wb = bud ? sch->n_steps / bud->every : 0;
     const BatchSel sel = flagged_members(B, active);
     if (!sel.n) return 0;
     // ---- every flagged member, before anything is launched
@@ -808,6 +909,8 @@ extern "C" int suhmo_batch_run(suhmo_batch_t *B, const suhmo_model_params_t *mp,
         }
     }
     if (moulins && (rc = batch_moulin_check(B, sel, sch->n_moulins, sch->sigma, off, &nmax))) return rc;
+    // (the face coefficients and the melt rate are the first step's to form; the source term is the rule above)
+    if (bud && (rc = batch_budget_check(B, mp, sel, "batch: run: budget", false, false))) return rc;
     HIPCHK(hipSetDevice(B->device));
     if ((rc = (recharge || moulins) ? batch_source_fields(B, sel, st) : batch_enter(B, st))) return rc;      // (bottom_solver of the handles: rc -5)
     // ---- what the run needs on the device: the lists once, the series
@@ -827,8 +930,22 @@ extern "C" int suhmo_batch_run(suhmo_batch_t *B, const suhmo_model_params_t *mp,
         HIPCHK(hipHostMalloc(&B->h_series, total_rows * per * sizeof(double), hipHostMallocDefault));
         B->series_cap = total_rows * per;
     }
+    const size_t wper = (size_t)SUHMO_WB_COUNT * n;
+    if (total_wb > 0) {
+        if ((rc = batch_budget_buffers(B))) return rc;
+        if (total_wb * wper > B->wbs_cap) {
+            HIPCHK(hipStreamSynchronize(st));
+            if (B->d_wbs) (void)hipFree(B->d_wbs);
+            if (B->h_wbs) (void)hipHostFree(B->h_wbs);
+            B->d_wbs = B->h_wbs = nullptr; B->wbs_cap = 0;
+            HIPCHK(hipMalloc(&B->d_wbs, total_wb * wper * sizeof(double)));
+            HIPCHK(hipHostMalloc(&B->h_wbs, total_wb * wper * sizeof(double), hipHostMallocDefault));
+            B->wbs_cap = total_wb * wper;
+        }
+    }
     std::vector<suhmo_model_params_t> mps(mp, mp + n);
-    int rows = 0;
+    const int track = B->track_old_volume;
+    int rows = 0, wrows = 0;
     rc = 0;
     for (int k = 0; k < sch->n_steps && !rc; k++) {
         PerMember a, b;
@@ -845,8 +962,12 @@ extern "C" int suhmo_batch_run(suhmo_batch_t *B, const suhmo_model_params_t *mp,
             B->launches += 3;
         }
         if (sch->ramp) for (int m = 0; m < n; m++) mps[m].ramp = sch->ramp[k];
-        if ((rc = suhmo_batch_timestep_run(B, mps.data(), sch->dt, sch->first_cur_step + k, res->picard_iters ? res->picard_iters + (size_t)k * n : nullptr,
-                                           res->vcycles ? res->vcycles + (size_t)k * n : nullptr, st, active))) break;
+        const bool brow = total_wb > 0 && (k + 1) % bud->every == 0;
+        if (brow) B->track_old_volume = 1;
+        rc = suhmo_batch_timestep_run(B, mps.data(), sch->dt, sch->first_cur_step + k, res->picard_iters ? res->picard_iters + (size_t)k * n : nullptr,
+                                      res->vcycles ? res->vcycles + (size_t)k * n : nullptr, st, active);
+        B->track_old_volume = track;
+        if (rc) break;
         res->steps_done = k + 1;
         if (sch->diag_every && (k + 1) % sch->diag_every == 0) {
             if ((rc = batch_column_launch(B, mps.data(), sel, st))) break;
@@ -854,9 +975,20 @@ extern "C" int suhmo_batch_run(suhmo_batch_t *B, const suhmo_model_params_t *mp,
             B->launches++;
             rows++;
         }
+        if (brow) {
+            if ((rc = batch_budget_launch(B, mps.data(), sel, B->d_wbs + wrows * wper, st))) break;
+            wrows++;
+        }
     }
     res->n_rows = rows;
-    const int rc2 = batch_run_series_out(B, sel, rows, res->rows, st);
+    const std::string msg = rc ? suhmo_last_error() : "";
+    int rc2 = batch_run_series_out(B, sel, rows, res->rows, st);
+    if (bud) {
+        const int rc3 = batch_run_budget_out(B, sel, wrows, bud->rows, st);
+        if (!rc3) bud->n_rows = wrows;
+        rc2 = rc2 ? rc2 : rc3;
+    }
+    if (rc && !rc2) suhmo_set_error("%s", msg.c_str());
     return rc ? rc : rc2;
 }
 
@@ -870,6 +1002,7 @@ extern "C" int suhmo_batch_set_option(suhmo_batch_t *B, const char *key, long va
         return -5;
     }
     if (!strcmp(key, "implicit_gap")) { ARG(value == 0 || value == 1); B->implicit_gap = (int)value; return 0; }
+    if (!strcmp(key, "track_old_volume")) { ARG(value == 0 || value == 1); B->track_old_volume = (int)value; return 0; }
     if (!strcmp(key, "batch_launches") || !strcmp(key, "batch_readbacks") || !strcmp(key, "batch_member_cycles") || !strcmp(key, "batch_gap_member_cycles")
         || !strcmp(key, "bottom_solver_iterations") || !strcmp(key, "bottom_solves_one_launch")) { suhmo_set_error("batch: option %s is read-only", key); return -1; }
     suhmo_set_error("batch: unknown option %s", key);
@@ -887,6 +1020,7 @@ extern "C" int suhmo_batch_get_option(const suhmo_batch_t *B, const char *key, l
             if (b) for (const suhmo_level *L : b->mem) *value += suhmo_bottom_counter(L, which);
     }
     else if (!strcmp(key, "implicit_gap")) *value = B->implicit_gap;
+    else if (!strcmp(key, "track_old_volume")) *value = B->track_old_volume;
     else if (!strcmp(key, "batch_launches")) *value = B->launches + (B->gap ? B->gap->launches : 0);
     else if (!strcmp(key, "batch_readbacks")) *value = B->readbacks + (B->gap ? B->gap->readbacks : 0);
     else if (!strcmp(key, "batch_member_cycles")) *value = B->member_cycles;

@@ -288,6 +288,10 @@ struct suhmo_level {
     int faces_made;             // depth 0's face coefficients have been formed (UpdateOperator in any of its forms, the time step) or loaded by the
                                 // caller at least once: what the mass balance (suhmo_balance.hip) asks before it reads them (suhmo_faces_made)
     double *bal_buf;            // suhmo_level_mass_balance: the partials of its first stage and, behind them, its seven sums; allocated on first use
+    // "WATER BUDGET" (suhmo_balance.hip).  track_old_volume: option, 1 = suhmo_level_timestep begins with k_volume into vol_buf (vol_np partials;
+    // 0: no tracked step has run); wb_buf: the partials of suhmo_level_water_budget and, behind them, its ten values.  Allocated on first use
+    int track_old_volume, vol_np;
+    double *vol_buf, *wb_buf;
 };
 static inline void suhmo_faces_made(suhmo_level *L) { L->faces_made = 1; }
 

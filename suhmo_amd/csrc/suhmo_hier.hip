@@ -370,6 +370,7 @@ static const HierOpt hier_opts[] = {
     {"fused_relax",          &suhmo_hier::fused_relax,     1,      flag,         false, nullptr},
     {"shadow",               &suhmo_hier::shadowed,        0,      flag,         true,  nullptr},
     {"partition_min_cells",  &suhmo_hier::part_min_cells,  350000, at_least_one, true,  nullptr},
+    {"track_old_volume",     &suhmo_hier::track_old_volume, 0,     flag,         false, nullptr},
 };
 static const HierOpt *find_opt(const char *key, size_t n)
 {
@@ -615,6 +616,9 @@ extern "C" int suhmo_hier_get_option(const suhmo_hier_t *H, const char *key, lon
     if (!strcmp(key, "balance_launches")) { *value = H->n_bal_launches; return 0; }
     if (!strcmp(key, "balance_copies")) { *value = H->n_bal_copies; return 0; }
     if (!strcmp(key, "balance_device_bytes")) { *value = (long)H->bal_cap * 8; return 0; }
+    if (!strcmp(key, "budget_launches")) { *value = H->n_wb_launches; return 0; }
+    if (!strcmp(key, "budget_copies")) { *value = H->n_wb_copies; return 0; }
+    if (!strcmp(key, "budget_device_bytes")) { *value = (long)(H->wb_cap + H->vol_cap) * 8; return 0; }
     if (!strcmp(key, "run_plots")) { *value = H->n_run_plots; return 0; }
     if (!strcmp(key, "run_checkpoints")) { *value = H->n_run_checkpoints; return 0; }
     if (!strcmp(key, "incremental_residual_passes")) { *value = H->n_incr_residual; return 0; }

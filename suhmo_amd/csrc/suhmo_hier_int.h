@@ -207,6 +207,14 @@ struct suhmo_hier {
     // bal_cap doubles), its launches and copies (read-only options balance_launches, balance_copies, balance_device_bytes)
     double *bal_buf = nullptr; size_t bal_cap = 0;
     long n_bal_launches = 0, n_bal_copies = 0;
+    // "WATER BUDGET" (suhmo_balance.hip).  track_old_volume: option (hier_opts): suhmo_hier_timestep begins with k_volume of every level into
+    // vol_buf -- level l's partials at vol_off[l], vol_n[l] of them (0: no tracked step has run on this handle); wb_buf: the partials of every
+    // first stage of a budget and, behind them, ten values per level (wb_cap doubles).  Allocated on first use.  Read-only options
+    // budget_launches, budget_copies (a run carries them across its regrids), budget_device_bytes
+    long track_old_volume;
+    double *vol_buf = nullptr, *wb_buf = nullptr; size_t vol_cap = 0, wb_cap = 0;
+    size_t vol_off[8] = {}; int vol_n[8] = {};
+    long n_wb_launches = 0, n_wb_copies = 0;
     long flat_fail_slot = -1;                              // option flatten_fail_slot (tests): the allocation of this scratch slot on the finest level fails
     double *red_all = nullptr;                             // partial maxima of a norm over all levels of boxes (64 per box + 16)
     struct suhmo_tagmap *tags[8] = {};                     // tag maps of suhmo_hier_tag_cells, one per level (suhmo_tags.hip), owned
@@ -342,5 +350,13 @@ int suhmo_hier_flatten_check_(const suhmo_hier *H, int max_level);
 int suhmo_hier_flatten_device_(suhmo_hier *H, int max_level, const FlatComps &c, hipStream_t st);
 // ---- suhmo_compare.hip: its partial buffer goes with the hierarchy
 void suhmo_hier_compare_release_(suhmo_hier *H);
-// ---- suhmo_balance.hip: likewise
+// ---- suhmo_balance.hip: likewise (the buffers of the mass balance and of the water budget)
 void suhmo_hier_balance_release_(suhmo_hier *H);
+// ---- suhmo_balance.hip, "WATER BUDGET": what the time steps (suhmo_step.hip) and the run (suhmo_run.hip) need of it
+int suhmo_level_track_volume_(suhmo_level *L, hipStream_t st);                      // k_volume of a level into L->vol_buf (rank strips: -5)
+int suhmo_hier_track_volume_(suhmo_hier *H, hipStream_t st);                        // ... of every level of H into H->vol_buf: nlev launches
+// what suhmo_hier_water_budget refuses (faces: the face coefficients and SUHMO_F_MR are asked for too -- a run leaves them to its first step;
+// source: use_moulin_source needs SUHMO_F_MSRC on every box now)
+int suhmo_hier_budget_check_(const suhmo_hier *H, const suhmo_model_params_t *mp, const char *who, bool faces, bool source);
+// the nlev first stages and the final launch: ten doubles per level to the DEVICE address out; nothing copied, nothing synchronised
+int suhmo_hier_budget_launch_(suhmo_hier *H, const suhmo_model_params_t *mp, double *out, hipStream_t st);

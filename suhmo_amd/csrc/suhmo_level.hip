@@ -303,6 +303,8 @@ extern "C" int suhmo_level_destroy(suhmo_level_t *L)
     if (L->xstream) { (void)hipStreamDestroy(L->xstream); (void)hipEventDestroy(L->xev[0]); (void)hipEventDestroy(L->xev[1]); }
     if (L->scratch) (void)hipFree(L->scratch);
     if (L->bal_buf) (void)hipFree(L->bal_buf);
+    if (L->vol_buf) (void)hipFree(L->vol_buf);
+    if (L->wb_buf) (void)hipFree(L->wb_buf);
     if (L->bottom_ctr) (void)hipFree(L->bottom_ctr);
     suhmo_tagmap_release(L->tags);
     if (L->mask_ev) (void)hipEventDestroy(L->mask_ev);
@@ -373,6 +375,11 @@ extern "C" int suhmo_level_set_option(suhmo_level_t *L, const char *key, long va
         if (value < 0) { suhmo_set_error("bottom_one_launch_max_cells: >= 0"); return -1; }
         return suhmo_bottom_configure(L, L->bottom_solver, value);
     }
+    // "WATER BUDGET": the time step measures the volume it starts from (no kernel selection: captured V-cycles stay)
+    if (!strcmp(key, "track_old_volume")) {
+        if (value != 0 && value != 1) { suhmo_set_error("track_old_volume: 0 or 1"); return -1; }
+        L->track_old_volume = (int)value; return 0;
+    }
     if (long *p = option_slot_long(L, key)) {
         *p = value; suhmo_level_drop_graphs(L);
         if (!strcmp(key, "agg_min_cells")) return suhmo_agg_setup(L);     // (every rank of the partition must set the same value)
@@ -413,6 +420,7 @@ extern "C" int suhmo_level_get_option(const suhmo_level_t *L, const char *key, l
     if (!strcmp(key, "relax_unmasked_launches")) { *value = L->relax_unmasked; return 0; }
     if (!strcmp(key, "vcycle_graph_replays")) { *value = L->vgraph_replays; return 0; }   // read-only counter (graph_max_cells)
     if (!strcmp(key, "bottom_solver")) { *value = L->bottom_solver; return 0; }
+    if (!strcmp(key, "track_old_volume")) { *value = L->track_old_volume; return 0; }
     if (!strcmp(key, "bottom_one_launch_max_cells")) { *value = L->bottom_one_launch_max_cells; return 0; }
     if (!strcmp(key, "bottom_solver_iterations")) { *value = suhmo_bottom_counter(L, 0); return 0; }    // read-only counters (bottom_solver)
     if (!strcmp(key, "bottom_solves_one_launch")) { *value = suhmo_bottom_counter(L, 1); return 0; }

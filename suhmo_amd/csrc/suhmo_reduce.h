@@ -36,6 +36,9 @@ struct RedSumSumMax { static constexpr int NV = 3; static constexpr bool PER_VAL
 struct RedSum7 { static constexpr int NV = 7;           // the seven sums of the mass balance (suhmo_balance.hip), terms of any sign
     static __device__ __forceinline__ double init(int) { return 0.0; }
     static __device__ __forceinline__ double op(double a, double b) { return a + b; } };
+struct RedSum9 { static constexpr int NV = 9;           // those seven and the two recharge sums of the water budget (suhmo_balance.hip)
+    static __device__ __forceinline__ double init(int) { return 0.0; }
+    static __device__ __forceinline__ double op(double a, double b) { return a + b; } };
 template <class R, class = void> struct red_per_value : std::false_type {};
 template <class R> struct red_per_value<R, std::void_t<decltype(R::PER_VALUE)>> : std::true_type {};
 template <class R> __device__ __forceinline__ double red_op(int q, double a, double b)

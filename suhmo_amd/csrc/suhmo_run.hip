@@ -4,7 +4,8 @@
 // device into a series that comes back in one copy.  The C-ABI and the order: include/suhmo_hip.h, "THE RUN OF A HIERARCHY".  Nothing here
 // computes: every step is one of the public calls (or the launches of one), so the results are the per-call loop's bit for bit.  Eager
 // launches, no graph capture, as suhmo_batch_run.  suhmo_hier_run_out adds the plot files and checkpoints AmrHydro::run writes (:1311-1336, :1343-1358):
-// a snapshot (suhmo_snap.hip) handed to the caller's callback, include/suhmo_hip.h, "OUTPUT INSIDE THE RUN".
+// a snapshot (suhmo_snap.hip) handed to the caller's callback, include/suhmo_hip.h, "OUTPUT INSIDE THE RUN".  suhmo_hier_run_bud adds the water
+// budget series ("WATER BUDGET" there): rows of ten doubles per level finished on the device into a series the run owns, one copy at the end.
 #include "suhmo_hier_int.h"
 #include <cstring>
 #include <vector>
@@ -64,11 +65,12 @@ int run_regrid(suhmo_hier **Hp, const suhmo_hier_schedule_t *sch, int c, suhmo_h
         res->n_regrids = idx + 1;
     };
     if (same) { log(); return 0; }
-    const long carried[5] = {H->n_recharge_launches, H->n_moulin_calls, H->n_run_readbacks, H->n_snap_launches, H->n_snap_copies};
+    const long carried[7] = {H->n_recharge_launches, H->n_moulin_calls, H->n_run_readbacks, H->n_snap_launches, H->n_snap_copies, H->n_wb_launches, H->n_wb_copies};
     suhmo_hier *N = nullptr;
     if ((rc = suhmo_hier_regrid(H, nlev, nbox, boxes.data(), sch->n_fields, sch->fields, &N, s))) return rc;      // (H is untouched and usable)
     N->n_recharge_launches = carried[0]; N->n_moulin_calls = carried[1]; N->n_run_readbacks = carried[2];
     N->n_snap_launches = carried[3]; N->n_snap_copies = carried[4];
+    N->n_wb_launches = carried[5]; N->n_wb_copies = carried[6];
     *Hp = N;
     *changed = true;
     log();
@@ -127,11 +129,21 @@ extern "C" int suhmo_hier_run(suhmo_hier_t **Hp, const suhmo_model_params_t *mp,
 extern "C" int suhmo_hier_run_out(suhmo_hier_t **Hp, const suhmo_model_params_t *mp, const suhmo_hier_schedule_t *sch, const suhmo_hier_output_t *out,
                                   suhmo_hier_run_result_t *res, suhmo_stream_t s)
 {
+    return suhmo_hier_run_bud(Hp, mp, sch, out, nullptr, res, s);
+}
+
+// bud != NULL: a budget row of every level after the steps that end one.  Those steps run with track_old_volume = 1 (the volume is measured
+// inside the step: behind its regrid, reload and forcing), the others with the caller's setting, which is put back right behind the step -- so
+// every way out leaves it.  A regrid hands the setting to the new handle with the other options; the series stays with the run
+extern "C" int suhmo_hier_run_bud(suhmo_hier_t **Hp, const suhmo_model_params_t *mp, const suhmo_hier_schedule_t *sch, const suhmo_hier_output_t *out,
+                                  suhmo_run_budget_t *bud, suhmo_hier_run_result_t *res, suhmo_stream_t s)
+{
     SUHMO_TIME("AmrHydro::run");
     ARG(Hp && *Hp && mp && sch && res);
     suhmo_hier *H = *Hp;
     hipStream_t st = HST(s);
     res->steps_done = 0; res->n_rows = 0; res->n_regrids = 0; res->n_moved = 0;
+    if (bud) bud->n_rows = 0;
     int rc;
     // ---- everything that can be refused, before anything is launched
     if (sch->n_steps < 1) { suhmo_set_error("suhmo_hier_run: n_steps = %d (at least 1)", sch->n_steps); return -1; }
@@ -195,12 +207,31 @@ extern "C" int suhmo_hier_run_out(suhmo_hier_t **Hp, const suhmo_model_params_t 
     const int total_rows = sch->diag_every ? sch->n_steps / sch->diag_every : 0;
     if (total_rows > 0 && !res->rows) { suhmo_set_error("suhmo_hier_run: %d rows and no array for them", total_rows); return -1; }
     if (total_rows > 0 && (rc = suhmo_level_postproc_row_check_(base_of(H), mp, recharge || moulins))) return rc;
+    if (bud) {
+        if (bud->every < 1) { suhmo_set_error("suhmo_hier_run: a budget row every %d steps (at least 1)", bud->every); return -1; }
+        if (!bud->rows || !bud->nlev) { suhmo_set_error("suhmo_hier_run: a budget series needs the arrays rows and nlev"); return -1; }
+        const int need = sch->regrid_interval > 0 ? std::max(std::min(sch->max_level + 1, 8), H->nlev) : H->nlev;     // (at most 8 levels: suhmo_hier_create)
+        if (bud->lev_cap < need) { suhmo_set_error("suhmo_hier_run: budget rows with room for %d levels, the run can have %d", bud->lev_cap, need); return -1; }
+        // (the face coefficients and the melt rate are the first step's to form; the source term is the rule above)
+        if ((rc = suhmo_hier_budget_check_(H, mp, "suhmo_hier_run: budget", false, false))) return rc;
+    }
     if ((rc = suhmo_hier_check_(H))) return rc;
     HIPCHK(hipSetDevice(H->device));
+    // ---- the budget series [rows][lev_cap][10] on the device for the length of the run, and where its one copy lands
+    const int total_wb = bud ? sch->n_steps / bud->every : 0;
+    const size_t wper = bud ? (size_t)SUHMO_WB_COUNT * bud->lev_cap : 0;
+    double *wseries = nullptr;
+    if (total_wb > 0) HIPCHK(hipMalloc(&wseries, total_wb * wper * sizeof(double)));
+    const long track = H->track_old_volume;
+    int wrows = 0;
     // ---- the series [rows][6] and the column sums of one row, on the device for the length of the run
     const size_t ncol = 8 * (size_t)B->d[0].v.nx;
     double *series = nullptr;
-    if (total_rows > 0) HIPCHK(hipMalloc(&series, (6 * (size_t)total_rows + ncol) * sizeof(double)));
+    if (total_rows > 0 && hipMalloc(&series, (6 * (size_t)total_rows + ncol) * sizeof(double)) != hipSuccess) {
+        (void)hipGetLastError();
+        if (wseries) (void)hipFree(wseries);
+        suhmo_set_error("suhmo_hier_run: the series (%zu doubles) cannot be allocated", 6 * (size_t)total_rows + ncol); return -2;
+    }
     double *cols = series ? series + 6 * (size_t)total_rows : nullptr;
     int rows = 0;
     rc = 0;
@@ -228,7 +259,11 @@ extern "C" int suhmo_hier_run_out(suhmo_hier_t **Hp, const suhmo_model_params_t 
         suhmo_model_params_t mpk = *mp;
         if (sch->ramp) mpk.ramp = sch->ramp[k];
         int pi = 0, nv = 0;
-        if ((rc = suhmo_hier_timestep(H, &mpk, sch->dt, c, &pi, &nv, s))) break;
+        const bool brow = total_wb > 0 && (k + 1) % bud->every == 0;
+        if (brow) H->track_old_volume = 1;
+        rc = suhmo_hier_timestep(H, &mpk, sch->dt, c, &pi, &nv, s);
+        H->track_old_volume = track;
+        if (rc) break;
         if (res->picard_iters) res->picard_iters[k] = pi;
         if (res->vcycles) res->vcycles[k] = nv;
         res->steps_done = k + 1;
@@ -236,6 +271,11 @@ extern "C" int suhmo_hier_run_out(suhmo_hier_t **Hp, const suhmo_model_params_t 
         if (sch->diag_every && (k + 1) % sch->diag_every == 0) {
             if ((rc = suhmo_level_postproc_row_launch_(base_of(H), &mpk, cols, series + 6 * (size_t)rows, st))) break;
             rows++;
+        }
+        // 5. budget row: the levels the hierarchy has now
+        if (brow) {
+            if ((rc = suhmo_hier_budget_launch_(H, &mpk, wseries + wrows * wper, st))) break;
+            bud->nlev[wrows++] = H->nlev;
         }
     }
     // the files after the last step (:1343-1358)
@@ -256,5 +296,20 @@ extern "C" int suhmo_hier_run_out(suhmo_hier_t **Hp, const suhmo_model_params_t 
         else if (rc) suhmo_set_error("%s", msg.c_str());
     } else if (series) (void)hipStreamSynchronize(st);
     if (series) (void)hipFree(series);
+    // the budget rows finished so far: one copy, then the levels each row has (the other entries keep the caller's values)
+    if (wrows > 0) {
+        const std::string msg = rc ? suhmo_last_error() : "";
+        std::vector<double> h(wrows * wper);
+        hipError_t e = hipMemcpyAsync(h.data(), wseries, h.size() * sizeof(double), hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess) e = hipStreamSynchronize(st);
+        H->n_wb_copies++;
+        if (e != hipSuccess) { suhmo_set_error("suhmo_hier_run: copy of the budget series: %s", hipGetErrorString(e)); rc2 = rc2 ? rc2 : -2; }
+        else {
+            for (int r = 0; r < wrows; r++) memcpy(bud->rows + r * wper, h.data() + r * wper, (size_t)SUHMO_WB_COUNT * bud->nlev[r] * sizeof(double));
+            bud->n_rows = wrows;
+            if (rc) suhmo_set_error("%s", msg.c_str());
+        }
+    } else if (wseries) (void)hipStreamSynchronize(st);
+    if (wseries) (void)hipFree(wseries);
     return rc ? rc : rc2;
 }

@@ -534,6 +534,7 @@ extern "C" int suhmo_level_timestep(suhmo_level_t *L, const suhmo_model_params_t
     HIPCHK(hipSetDevice(L->device));
     if (lacks_source(L, mp)) { suhmo_set_error("use_moulin_source without suhmo_level_moulin_source"); return -1; }
     if ((rc = alloc_step_fields(L))) return rc;
+    if (L->track_old_volume && (rc = suhmo_level_track_volume_(L, (hipStream_t)s))) return rc;     // "WATER BUDGET": the volume the step starts from
     OneLevel y{L, (hipStream_t)s};
     return timestep_fas(y, mp, dt, cur_step, picard_iters, vcycles);
 }
@@ -642,6 +643,7 @@ int suhmo_batch_timestep_run(suhmo_batch *B, const suhmo_model_params_t *mp, dou
         if (mp[k].diffFactor != 0.0) for (int f : {SUHMO_F_DCX, SUHMO_F_DCY, SUHMO_F_DTERM}) if (!suhmo_field(L, 0, f)) { suhmo_set_error("field allocation failed"); return -2; }
     }
     if ((rc = suhmo_batch_step_begin(B, mp, st, active ? serve : nullptr))) return rc;
+    if ((rc = suhmo_batch_step_track_volume(B, st))) return rc;                                     // "WATER BUDGET": option track_old_volume
     Batch y{B, st, 1, suhmo_batch_size_(B)};
     return timestep_fas(y, mp, dt, cur_step, picard_iters, vcycles, active ? serve : nullptr);
 }
@@ -969,6 +971,7 @@ extern "C" int suhmo_hier_timestep(suhmo_hier_t *H, const suhmo_model_params_t *
     }
     suhmo_level *base = base_of(H);
     if (strip_without_hooks(base)) { suhmo_set_error("time step on rank strips needs the exchange hooks on level 0"); return -1; }
+    if (H->track_old_volume && (rc = suhmo_hier_track_volume_(H, (hipStream_t)s))) return rc;       // "WATER BUDGET": the volume the step starts from
     BoxUnions y{H, nlev, base, (hipStream_t)s};
     return timestep_fas(y, mp, dt, cur_step, picard_iters, vcycles);
 }

@@ -486,8 +486,9 @@ class HipHier:
         if h != self.h.value:
             self._adopt(h)
 
-    def run(self, mp, sch, res, out=None):
+    def run(self, mp, sch, res, out=None, bud=None):
         """suhmo_hier_run with the structures of capi (mp: ModelParams, sch: HierSchedule, res: HierRunResult with its arrays) -> rc; with
+        bud (capi.RunBudget): suhmo_hier_run_bud, the water budget series; with
         out (capi.HierOutput): suhmo_hier_run_out, whose callback receives the handle the event is about -- after a regrid that moved boxes and
         no `reload` that adopted it, call _adopt_if_new(handle) there before reading self.boxes.  After a
         run that moved the hierarchy onto other boxes (res.n_moved regrids did) this object wraps the new handle (new views, self.boxes,
@@ -495,7 +496,10 @@ class HipHier:
         given) first; the run is called after every such regrid, so then nothing is left to do here."""
         hp = C.c_void_p(self.h.value)
         before = self._adopts = getattr(self, "_adopts", 0)
-        if out is None:
+        if bud is not None:
+            rc = capi.lib().suhmo_hier_run_bud(C.byref(hp), C.byref(mp), C.byref(sch), None if out is None else C.byref(out), C.byref(bud), C.byref(res),
+                                               self.stream)
+        elif out is None:
             rc = capi.lib().suhmo_hier_run(C.byref(hp), C.byref(mp), C.byref(sch), C.byref(res), self.stream)
         else:
             rc = capi.lib().suhmo_hier_run_out(C.byref(hp), C.byref(mp), C.byref(sch), C.byref(out), C.byref(res), self.stream)

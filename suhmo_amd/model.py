@@ -290,6 +290,14 @@ class HipModel:
         check(capi.lib().suhmo_level_mass_balance(self.level.h, out.ctypes.data_as(C.POINTER(C.c_double)), self.level.stream))
         return dict(zip(capi.MB_NAMES, out.tolist()))
 
+    def water_budget(self):
+        """the conservation record of a step (suhmo_level_water_budget; include/suhmo_hip.h, "WATER BUDGET"): the seven values of
+        mass_balance, volume_old (the volume the last step with level option track_old_volume = 1 started from; NaN: none) and the two
+        parts of the reference's rechargeTOT -> a dict of the ten names (capi.WB_NAMES).  Read-only"""
+        out = np.zeros(len(capi.WB_NAMES))
+        check(capi.lib().suhmo_level_water_budget(self.level.h, C.byref(self._mp), out.ctypes.data_as(C.POINTER(C.c_double)), self.level.stream))
+        return dict(zip(capi.WB_NAMES, out.tolist()))
+
     def postproc_table(self):
         """SHMIP cross-section table (src/AmrHydro.cpp:3647-4102) from the device-resident state, reduced on the host"""
         mask = self.get("mask")
@@ -446,7 +454,17 @@ class HipBatchModel:
         check(capi.lib().suhmo_batch_mass_balance(self.batch.h, t.ctypes.data_as(C.POINTER(C.c_double)), self._active(active), self.batch.stream))
         return t
 
-    def run(self, n_steps, dt, T_K=None, background=None, moulins=None, moulin_factor=None, ramp=None, diag_every=0, active=None, rows=None):
+    def water_budget_all(self, active=None, out=None):
+        """the water budget of every member (suhmo_batch_water_budget), (n, 10) in the order of capi.WB_NAMES, every member bit for bit
+        HipModel.water_budget of the same model alone; volume_old: what the last step with batch option track_old_volume = 1 that served the
+        member started from (NaN: none); out: an array whose rows of the members that are not active are kept.  Read-only"""
+        t = np.zeros((self.n, len(capi.WB_NAMES))) if out is None else out
+        assert t.shape == (self.n, len(capi.WB_NAMES)) and t.dtype == np.float64 and t.flags.c_contiguous
+        check(capi.lib().suhmo_batch_water_budget(self.batch.h, self._mp, t.ctypes.data_as(C.POINTER(C.c_double)), self._active(active), self.batch.stream))
+        return t
+
+    def run(self, n_steps, dt, T_K=None, background=None, moulins=None, moulin_factor=None, ramp=None, diag_every=0, active=None, rows=None,
+            balance_every=0, budget=None):
         """the time loop of the active members in ONE call (suhmo_batch_run): per step the forcing of the schedule, the time step and, after
         every diag_every-th step, the daily row finished on the device; the rows of the whole run come back in one copy.  Bit for bit what
         time_varying_recharge / moulin_source, timestep and postproc_temporal_all give step by step.
@@ -454,6 +472,9 @@ class HipBatchModel:
         caller evaluates the temperature.  moulins: lists[k] = (positions, sigma, flux) as moulin_source takes them, given once, with
         moulin_factor (n_steps, n).  ramp: (n_steps,), written into every member's ramp for that step.  rows: an (n_rows, n, 6) array whose
         entries of the members that are not active are kept.
+        balance_every > 0 (suhmo_batch_run_bud): the water budget of the active members after every balance_every-th step, finished on the
+        device, one more copy for the run -> self.last_run["budget"], (n_steps // balance_every, n, 10) prefilled with NaN (budget: an array
+        of that shape to fill instead); self.last_run also holds steps_done and budget_rows.
         Returns (picard iterations (n_steps, n), V-cycles (n_steps, n), rows (n_steps // diag_every, n, 6))."""
         n = self.n
         n_steps, diag_every = int(n_steps), int(diag_every)
@@ -505,7 +526,19 @@ class HipBatchModel:
         pi, nv = np.zeros((max(n_steps, 0), n), dtype=np.intc), np.zeros((max(n_steps, 0), n), dtype=np.intc)
         ip = lambda a: a.ctypes.data_as(C.POINTER(C.c_int))
         res = capi.BatchRunResult(picard_iters=ip(pi), vcycles=ip(nv), rows=dp(out))
-        rc = capi.lib().suhmo_batch_run(self.batch.h, self._mp, C.byref(sch), self._active(active), C.byref(res), self.batch.stream)
+        balance_every = int(balance_every)
+        if balance_every < 0:
+            raise ValueError("balance_every = %d" % balance_every)
+        if balance_every:
+            wb_rows = n_steps // balance_every if n_steps > 0 else 0
+            wb = np.full((wb_rows, n, len(capi.WB_NAMES)), np.nan) if budget is None else budget
+            assert wb.shape == (wb_rows, n, len(capi.WB_NAMES)) and wb.dtype == np.float64 and wb.flags.c_contiguous
+            bud = capi.RunBudget(every=balance_every, lev_cap=0, rows=dp(wb), nlev=None)
+            rc = capi.lib().suhmo_batch_run_bud(self.batch.h, self._mp, C.byref(sch), self._active(active), C.byref(bud), C.byref(res), self.batch.stream)
+            self.last_run = dict(steps_done=int(res.steps_done), budget=wb[:bud.n_rows], budget_rows=int(bud.n_rows))
+        else:
+            rc = capi.lib().suhmo_batch_run(self.batch.h, self._mp, C.byref(sch), self._active(active), C.byref(res), self.batch.stream)
+            self.last_run = dict(steps_done=int(res.steps_done))
         self.cur_step += res.steps_done
         for m in self.members:
             m.cur_step = self.cur_step
@@ -723,6 +756,15 @@ class HipHierModel:
         check(capi.lib().suhmo_hier_mass_balance(self.hier.h, out.ctypes.data_as(C.POINTER(C.c_double)), self.hier.stream))
         return [dict(zip(capi.MB_NAMES, row.tolist())) for row in out]
 
+    def water_budget(self):
+        """the conservation record of a step, per level (suhmo_hier_water_budget; include/suhmo_hip.h, "WATER BUDGET"): a list of dicts of the
+        ten names (capi.WB_NAMES), level 0 first -- the seven values of mass_balance, volume_old (the volume the last step with hierarchy
+        option track_old_volume = 1 started from; NaN: none, as on every level after a regrid), the two parts of rechargeTOT.  A first
+        stage per level, one final launch, one copy of 10 nlev doubles.  Read-only"""
+        out = np.zeros((self.hier.nlev, len(capi.WB_NAMES)))
+        check(capi.lib().suhmo_hier_water_budget(self.hier.h, C.byref(self._mp), out.ctypes.data_as(C.POINTER(C.c_double)), self.hier.stream))
+        return [dict(zip(capi.WB_NAMES, row.tolist())) for row in out]
+
     def restrict_tags(self, level, boxes):
         """levelTags &= tagSubset (suhmo_hier_restrict_tags): every entry of the tag map of `level` that lies in none of `boxes`
         ((lo0, lo1, hi0, hi1) in cells of that level, aligned to the map's granularity) is cleared; an empty list is a no-op"""
@@ -747,7 +789,7 @@ class HipHierModel:
     def run(self, n_steps, dt, T_K=None, background=None, moulins=None, moulin_factor=None, ramp=None, diag_every=0, regrid_interval=0,
             tag_specs=None, params=None, subsets=None, max_level=None, reload=None, skip_first_regrid=False, fields=None,
             plot_interval=-1, check_interval=-1, plot_prefix="plot", check_prefix="chk", check_overwrite=True, restart_step=0,
-            final_output=True, time0=0.0, periodic=(0, 0)):
+            final_output=True, time0=0.0, periodic=(0, 0), balance_every=0):
         """AmrHydro::run in ONE call (suhmo_hier_run): per step the regrid the reference does before it (every regrid_interval steps:
         regrid_steps(self.cur_step + 1, n_steps, regrid_interval, skip_first_regrid) lists them; tag_and_regrid's arguments tag_specs, params,
         subsets, max_level, fields), the forcing, the time step and, after every diag_every-th step, the daily row finished on the device; the
@@ -769,7 +811,9 @@ class HipHierModel:
         again after the bookkeeping, as for reload.
         Returns (picard iterations (n_steps,), V-cycles (n_steps,), rows (n_steps // diag_every, 6), log) with log = one dict per regrid:
         cur_step, same, boxes_per_level.  self.last_run: steps_done, n_rows, moulin_steps (n_steps,), plots and checkpoints (the paths
-        written, in order).  cur_step advances by the steps done;
+        written, in order).  balance_every > 0 (suhmo_hier_run_bud): the water budget of every level after every balance_every-th step,
+        finished on the device, one more copy for the run: self.last_run["budget"], (rows, lev_cap, 10) prefilled with NaN (lev_cap:
+        max_level + 1 when the run regrids, else the levels it has), and ["budget_nlev"], the levels at each row.  cur_step advances by the steps done;
         after a regrid that moved boxes self.hier wraps the new handle and self.level holds the new boxes' views."""
         n_steps, diag_every = int(n_steps), int(diag_every)
         ns = max(n_steps, 0)
@@ -888,13 +932,23 @@ class HipHierModel:
         log = (capi.HierRegridLog * max(ns, 1))()
         res = capi.HierRunResult(picard_iters=ip(pi), vcycles=ip(nv), rows=dp(rows) if n_rows else None, moulin_steps=ip(ms), regrids_cap=max(ns, 1),
                                  regrids=log)
-        rc = self.hier.run(self._mp, sch, res, out)
+        balance_every, bud = int(balance_every), None
+        if balance_every < 0:
+            raise ValueError("balance_every = %d" % balance_every)
+        if balance_every:
+            wb_rows = n_steps // balance_every if n_steps > 0 else 0
+            lev_cap = max(self.hier.nlev, min(sch.max_level + 1, 8) if regrid_interval > 0 else 0)      # (a hierarchy has at most 8 levels)
+            wb, wb_nlev = np.full((wb_rows, lev_cap, len(capi.WB_NAMES)), np.nan), np.zeros(max(wb_rows, 1), dtype=np.intc)
+            bud = capi.RunBudget(every=balance_every, lev_cap=lev_cap, rows=dp(wb), nlev=ip(wb_nlev))
+        rc = self.hier.run(self._mp, sch, res, out, bud)
         self.level = self.hier.level
         self.cur_step += res.steps_done
         if ramp is not None and res.steps_done > 0:            # the model's ramp is the last step's, as a loop that sets it leaves it
             self._mp.ramp = float(r[res.steps_done - 1])
         self.last_run = dict(steps_done=int(res.steps_done), n_rows=int(res.n_rows), moulin_steps=ms, n_moved=int(res.n_moved),
                              plots=written[0], checkpoints=written[1])
+        if bud is not None:
+            self.last_run.update(budget=wb[:bud.n_rows], budget_nlev=wb_nlev[:bud.n_rows].astype(int))
         if raised:
             raise raised[0]
         check(rc)

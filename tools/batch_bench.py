@@ -28,7 +28,10 @@ trees too) and (b) through suhmo_batch_time_varying_recharge / suhmo_batch_mouli
 steps of 2 h, a daily row) of `--steps` steps after `--warmup`, timed (a) as the per-call loop (time_varying_recharge + timestep per step,
 postproc_partial_all + the host function per day) and (b) as ONE call of HipBatchModel.run (suhmo_batch_run), the two in alternating runs on the
 same ensemble; wall time per step, median of `--repeat` runs each [min .. max].  A gain smaller than the spread is no gain.
-    python tools/batch_bench.py --run [--only both|loop|run] [--n 1,5,16,32] [--steps 2000] [--warmup 200] [--repeat 3]
+    python tools/batch_bench.py --run [--only both|loop|run] [--n 1,5,16,32] [--steps 2000] [--warmup 200] [--repeat 3] [--balance-every N]
+--balance-every N (with --run): both ways also take the water budget after every N-th step ("WATER BUDGET", include/suhmo_hip.h) -- the one
+call as the series inside the run (balance_every=N: no copy and no synchronisation per row), the loop as a user writes it without the series
+(mass_balance_all before the step for Bold, water_budget_all after it: two synchronising read-backs per row).
 """
 import argparse
 import json
@@ -247,14 +250,19 @@ def run_table(a):
             T_K = temperatures(steps)
             for k in range(steps):
                 B.time_varying_recharge(T_K[k], rf.BACKGROUND)
+                row = a.balance_every > 0 and (k + 1) % a.balance_every == 0
+                if row and B.cur_step > 0:
+                    B.mass_balance_all()
                 B.timestep(dt)
+                if row:
+                    B.water_budget_all()
                 if (k + 1) % per_day == 0:
                     sums = B.postproc_partial_all()
                     for q in range(n):
                         B.members[q].postproc_temporal_host(sums[q])
 
         def one_call(steps):
-            B.run(steps, dt, T_K=temperatures(steps), background=rf.BACKGROUND, diag_every=per_day)
+            B.run(steps, dt, T_K=temperatures(steps), background=rf.BACKGROUND, diag_every=per_day, balance_every=a.balance_every)
 
         ways = [w for w in (("loop", loop), ("run", one_call)) if a.only in ("both", w[0])]
         ways[0][1](a.warmup)
@@ -289,6 +297,7 @@ def main():
     ap.add_argument("--suite", choices=("A", "B"), default="A")
     ap.add_argument("--forcing", action="store_true")
     ap.add_argument("--run", action="store_true")
+    ap.add_argument("--balance-every", type=int, default=0)
     ap.add_argument("--only", choices=("both", "batch", "solo", "handles", "loop", "run"), default="both")
     a = ap.parse_args()
     a.n = a.n or ("1,6,16,32" if a.bottom_solver else "1,5,16,32" if a.forcing or a.run else "1,2,4,6,8,16,32")

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """cfg5 (exec/AMR_multiMoulins physics) time step on base + 3 AMR levels of box unions: ms per step.
-    python tools/hier_bench.py [--generated-grids] [--regrid-interval N [--one-call [--plot-interval P]]] [--recharge] [--snapshot] [--flatten] [--compare] [base cells per side] [steps]
+    python tools/hier_bench.py [--generated-grids] [--regrid-interval N [--one-call [--plot-interval P] [--balance-every B]]] [--recharge] [--snapshot] [--flatten] [--compare] [base cells per side] [steps]
 --compare: the L1, L2 and max norms of the reference's two components against a single level on the uniform grid of level 4 (random fields), on the
 hierarchy --flatten uses: suhmo_hier_compare in both modes (HipHier.compare: composite, finest), in alternating rounds with the two routes that
 existed before it -- one flatten to the host and the norms in numpy; the per-box get calls and, box by box, the block means and norms in numpy
@@ -13,6 +13,9 @@ only: the host arithmetic that would follow is no baseline).
 one snapshot and one file per event, into a temporary directory); the per-call loop beside it writes none, so the difference is what the output costs.
 --snapshot: one 13-component snapshot of the hierarchy (suhmo_hier_snapshot: a launch and a copy per level) against the per-box get loop for the same
 data (a copy per box and field), three alternating rounds, with the launch and copy counts of both.
+--balance-every B (with --one-call): both loops also take the water budget of every level after every B-th step ("WATER BUDGET", include/suhmo_hip.h):
+the one call as the series inside the run (no copy and no synchronisation per row, one copy per run call), the per-call loop with mass_balance
+before the step (Bold) and water_budget after it.
 --one-call (with --regrid-interval N): the same regridding time loop twice in one process, on two models set up alike -- the per-call loop
 (HipHierModel.tag_and_regrid, moulin_source, timestep) and HipHierModel.run (suhmo_hier_run: one call per stretch of steps that begins with a
 regrid, so that the thresholds can alternate as below) -- in alternating rounds of [steps] steps; prints ms per step and ms per regrid interval of
@@ -38,6 +41,11 @@ snapshot = "--snapshot" in sys.argv
 flatten = "--flatten" in sys.argv
 compare = "--compare" in sys.argv
 argv = [a for a in sys.argv[1:] if a not in ("--generated-grids", "--one-call", "--recharge", "--snapshot", "--flatten", "--compare")]
+balance_every = 0
+if "--balance-every" in argv:
+    q = argv.index("--balance-every")
+    balance_every = int(argv[q + 1])
+    del argv[q:q + 2]
 plot_interval = -1
 if "--plot-interval" in argv:
     q = argv.index("--plot-interval")
@@ -244,7 +252,12 @@ def one_call_rounds(rounds=3):
                 moved += not M.tag_and_regrid(specs((c - 1) // regrid_interval), GRID_PARAMS, max_level=3)[1]
             if k == 0 or c in due:                 # where the calls of run() below form it: their first step
                 M.moulin_source(**mo)
+            row = balance_every > 0 and (k + 1) % balance_every == 0
+            if row and c not in due:               # (boxes a regrid has just made hold no face coefficients yet)
+                M.mass_balance()
             M.timestep(mm["dt"])
+            if row:
+                M.water_budget()
         return len(due), moved
     import tempfile
     plots = tempfile.TemporaryDirectory() if plot_interval > 0 else None
@@ -255,7 +268,7 @@ def one_call_rounds(rounds=3):
         moved = 0
         for c, n in parts:
             log = M.run(n, mm["dt"], moulins=mo, regrid_interval=regrid_interval, tag_specs=specs((c - 1) // regrid_interval), params=GRID_PARAMS, max_level=3,
-                        **out)[3]
+                        balance_every=balance_every, **out)[3]
             moved += sum(not e["same"] for e in log)
             written.extend(M.last_run.get("plots", []))
         return len(due), moved

@@ -3,10 +3,15 @@
 (:582-588) -- the discharge through the four domain sides, through the ice margin and the ice-bearing domain sides, the water volume B with Bold
 taken from the same call before the step -- and one closing line: (V - Vold) / dt of the last step against recharge minus outflow, the recharge
 from the column sums of the SHMIP table (external + melt; level 0's, as the reference evaluates it).
-    python tools/mass_balance.py [--hier [--generated-grids]] [--time] [cells per side of the base] [steps]
+    python tools/mass_balance.py [--hier [--generated-grids]] [--one-call] [--time] [cells per side of the base] [steps]
 default     SHMIP A3 on one level (cells: nx, with ny = nx / 5; default 320 x 64)
 --hier      cfg5 (exec/AMR_multiMoulins physics) on base + 3 levels of box unions as tools/hier_bench.py makes them (default base 256^2);
             --generated-grids: the boxes from tagging the moulin source and clustering, the reference's way, instead of synthetic.boxes_around
+--one-call  the same lines from the water budget series of ONE run call (HipHierModel.run / HipBatchModel.run with balance_every=1; include/
+            suhmo_hip.h, "WATER BUDGET"): B/Bold with Bold kept on the device by the tracked step, and per step the reference's line
+            "Time(months) VOL_waterTot rechargeTOT ramp" (:4036-4038; VOL_waterTot here is level 0's whole volume, the reference prints its first
+            column's).  Without --hier the single level runs as an ensemble of one.  With --time: the one call against the per-call loop
+            (balance, step, balance: two synchronising read-backs a step) in three alternating rounds, the counters of both
 --time      instead of the lines: the call against the route that existed before it -- ghosted gets of head, mask and gap height and gets of both
             face coefficients for every box (5 copies per handle) followed by the sums in numpy -- in three alternating rounds, with the launch
             and copy counts, and 20 calls in a row; without --hier on a single level of [cells]^2 (default 4096^2) whose face coefficients are
@@ -107,7 +112,78 @@ def host_route(levels, bc):
     return out, t_copy
 
 
+def one_call():
+    """--one-call: the series of one run, printed as the reference prints its post_proc block; --time: against the per-call loop"""
+    nstep = int(argv[1]) if len(argv) > 1 else 5
+    if hier:
+        nb = int(argv[0]) if argv else 256
+        bc, ph, mm, mo = sy.multimoulins_setup()
+        boxes = generated_boxes(nb, bc, ph, mm, mo) if generated else sy.boxes_around(mo["positions"], nb, nb, 4, 1.0e5, 1.0e5)
+        def make():
+            M = model.HipHierModel(nb, nb, 1.0e5 / nb, 1.0e5 / nb, bc, ph, mm, boxes, max_box=64)
+            M.set_states(sy.mountain_amrm_states(nb, nb, boxes))
+            return M
+        run = lambda M: M.run(nstep, mm["dt"], moulins=mo, balance_every=1)
+        def loop(M):
+            M.moulin_source(**mo)
+            for n in range(nstep):
+                if n > 0:
+                    M.mass_balance()
+                M.timestep(mm["dt"])
+                M.mass_balance()
+        series = lambda M: (M.last_run["budget"], M.last_run["budget_nlev"])
+        counters = lambda M: dict(budget_launches=M.hier.get_option("budget_launches"), budget_copies=M.hier.get_option("budget_copies"),
+                                  balance_copies=M.hier.get_option("balance_copies"), run_readbacks=M.hier.get_option("run_readbacks"))
+        dt, ramp = mm["dt"], mm.get("ramp", 1.0)
+    else:
+        m = sy.A3_MODEL
+        nx = int(argv[0]) if argv else m["nx"]
+        ny = max(nx // 5, 4)
+        st = sy.shmip_initial_state(nx, ny, m["lx"], m["ly"])
+        def make():
+            M = model.HipBatchModel(nx, ny, st["dx"], st["dy"], sy.A3_BC, sy.A3_PHYS, [m], max_box=64)
+            M.set_state(0, st)
+            return M
+        run = lambda M: M.run(nstep, m["dt"], balance_every=1)
+        def loop(M):
+            for n in range(nstep):
+                if n > 0:
+                    M.mass_balance_all()
+                M.timestep(m["dt"])
+                M.mass_balance_all()
+        series = lambda M: (M.last_run["budget"], np.ones(M.last_run["budget_rows"], dtype=int))
+        counters = lambda M: dict(batch_launches=M.get_option("batch_launches"), batch_readbacks=M.get_option("batch_readbacks"))
+        dt, ramp = m["dt"], m.get("ramp", 1.0)
+    if timing:
+        for r in range(3):
+            for name, fn in (("one call with the series", run), ("per-call loop", loop)) if r % 2 == 0 else (("per-call loop", loop), ("one call with the series", run)):
+                M = make()
+                t0 = time.perf_counter()
+                fn(M)
+                print("round %d, %-24s: %d steps in %.3f ms; %s" % (r, name, nstep, 1e3 * (time.perf_counter() - t0), counters(M)), flush=True)
+                M.close()
+        return
+    M = make()
+    run(M)
+    rows, nlev = series(M)
+    for n in range(rows.shape[0]):
+        for l in range(int(nlev[n])):
+            v = dict(zip(capi.WB_NAMES, rows[n, l].tolist()))
+            print("step %d level %d" % (n + 1, l))
+            print("\n".join(lines(v, dict(volume=v["volume_old"]))))
+        v = dict(zip(capi.WB_NAMES, rows[n, 0].tolist()))
+        print("Time(months) VOL_waterTot rechargeTOT ramp = %g %g %g %g" % ((n + 1) * dt / 2635200.0, v["volume"], v["recharge_ext"] + v["recharge_melt"], ramp))
+    v = dict(zip(capi.WB_NAMES, rows[-1, 0].tolist()))
+    inflow = v["lo_x"] + v["lo_y"] - v["hi_x"] - v["hi_y"]
+    r = v["recharge_ext"] + v["recharge_melt"]
+    print("level 0, last step: (V - Vold) / dt = %.6e m^3/s; recharge %.6e + inflow through the domain sides %.6e = %.6e m^3/s"
+          % ((v["volume"] - v["volume_old"]) / dt, r, inflow, r + inflow))
+    M.close()
+
+
 def main():
+    if "--one-call" in sys.argv:
+        return one_call()
     nstep = int(argv[1]) if len(argv) > 1 else (3 if timing else 5)
     M, levels, dt, balance, recharge, bc = setup()
     sync = levels[0][0].synchronize
