@@ -125,6 +125,14 @@ int suhmo_level_num_depths(const suhmo_level_t *L);
  * the fused WFlx_level kernel and of the streaming relaxation that leave the mask out (no load, no register, no test); the results are the
  * same bits.  0: the per-cycle report of skip_mask only.  Ensembles and box unions always read the mask.  Read-only: mask_scans,
  * bcoef_unmasked_launches, relax_unmasked_launches (launches of graph replays included), mask_state (0 unknown, 1 clean, 2 dirty).
+ * zb_known (default 1): what a scan finds out about the bed elevation is kept until SUHMO_F_ZB is written again, under the same contract as
+ * the mask's (the entry points above notice that field too, on any depth; suhmo_level_build_mg_coefficients rewrites the coarse depths';
+ * suhmo_level_field_view of SUHMO_F_ZB ends the bookkeeping of that level for good).  The first V-cycle after a write scans every depth's
+ * cells, bit pattern against bit pattern (-0.0 is not +0.0); the answers come back through an asynchronous copy and an event that later
+ * cycles only query.  While a depth's bed is ONE pattern, the streaming relaxation of a whole level with a clean mask and alpha = 0 takes
+ * it as a scalar and loads no zb (same operand, same bits); a varying bed, rank strips, AMR patches, hierarchies, ensembles: the array is
+ * loaded as before.  0: nothing is scanned.  Read-only: zb_scans, zb_state (depth 0; zb_state_d<depth>: 0 unknown, 1 uniform, 2 varying),
+ * relax_zb_uniform_launches (all depths; relax_zb_uniform_launches_d<depth>; launches of graph replays included).
  * bcoef_in_relax (default 1): while the mask of a whole level (no rank strip, no AMR patch) is known clean, alpha = 0, depth 0 relaxes on the
  * streaming kernel and the pre-smoothing has at least three sweeps, the V-cycle's UpdateOperator is not a pass of its own: the first
  * pre-smoothing launch of depth 0 forms the face coefficients from the head as it loads it and stores them (same bits), AverageOperator

@@ -129,6 +129,7 @@ int suhmo_agg_setup(suhmo_level *L)
         return 0;
     }
     A->graph_max_cells = 0;                                                  // driven depth by depth from the strip's cycle
+    A->zb_off = 1;                                                           // (its coefficients are gathered copies: it keeps loading the bed)
     if ((rc = suhmo_bottom_configure(A, L->bottom_solver, L->bottom_one_launch_max_cells))) { suhmo_level_destroy(A); return rc; }   // its bottom is the strip's
     L->agg = A; L->agg_depth = da; L->agg_world = v0.nyg / v0.ny; L->agg_rank = v0.j0 / v0.ny;
     L->agg_static_stale = 1;                                                 // (nothing of the level's coefficients is in A yet: suhmo_agg_gather_static)

@@ -221,6 +221,7 @@ extern "C" int suhmo_amr2_average(suhmo_level_t *C, suhmo_level_t *F, int field_
     if (!pf || !pc) { suhmo_set_error("field allocation failed"); return -2; }
     if (field_c == SUHMO_F_PHI) C->d[0].phi_fresh = 0;
     if (field_c == SUHMO_F_MASK) suhmo_mask_written(C);
+    if (field_c == SUHMO_F_ZB) suhmo_zb_written(C);
     hipLaunchKernelGGL(k_amr_average, dim3((vf.nx / 2 + 63) / 64, (vf.ny / 2 + 3) / 4), dim3(64, 4), 0, (hipStream_t)s, vf, pf, vc, pc);
     HIPCHK(hipGetLastError());
     return 0;
@@ -253,6 +254,7 @@ extern "C" int suhmo_amr2_reflux(suhmo_level_t *C, suhmo_level_t *F, int field_c
     if (!p) { suhmo_set_error("field allocation failed"); return -2; }
     if ((rc = suhmo_amr2_cf_interp(C, F, SUHMO_F_PHI, SUHMO_F_PHI, s))) return rc;
     if (field_c == SUHMO_F_MASK) suhmo_mask_written(C);
+    if (field_c == SUHMO_F_ZB) suhmo_zb_written(C);
     int n = vf.ny + vf.nx;
     hipLaunchKernelGGL(k_amr_reflux, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)s, vf, F->d[0].fp, vc, C->d[0].fp, p);
     HIPCHK(hipGetLastError());
@@ -302,7 +304,7 @@ extern "C" int suhmo_amr2_finer_operator_changed(suhmo_level_t *C, suhmo_level_t
     hipLaunchKernelGGL(k_amr_average_faces, dim3((vf.nx / 2 + 1 + 63) / 64, (vf.ny / 2 + 1 + 3) / 4), dim3(64, 4), 0, (hipStream_t)s, vf,
                        F->d[0].fp.f[SUHMO_F_BX], F->d[0].fp.f[SUHMO_F_BY], vc, C->d[0].fp.f[SUHMO_F_BX], C->d[0].fp.f[SUHMO_F_BY]);
     HIPCHK(hipGetLastError());
-    suhmo_mask_written(C);
+    suhmo_mask_written(C); suhmo_zb_written(C);
     suhmo_level_drop_graphs(C);
     return 0;
 }
@@ -335,6 +337,7 @@ extern "C" int suhmo_amr2_set_covered(suhmo_level_t *C, suhmo_level_t *F, int fi
     if (!p) { suhmo_set_error("field allocation failed"); return -2; }
     if (field_c == SUHMO_F_PHI) C->d[0].phi_fresh = 0;
     if (field_c == SUHMO_F_MASK) suhmo_mask_written(C);
+    if (field_c == SUHMO_F_ZB) suhmo_zb_written(C);
     hipLaunchKernelGGL(k_amr_set_covered, dim3((vf.nx / 2 + 63) / 64, (vf.ny / 2 + 3) / 4), dim3(64, 4), 0, (hipStream_t)s, vf, vc, p, value);
     HIPCHK(hipGetLastError());
     return 0;

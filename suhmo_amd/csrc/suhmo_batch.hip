@@ -312,7 +312,7 @@ static int batch_create(suhmo_batch **out, const suhmo_level_desc_t *desc, int n
         suhmo_level *L = nullptr;
         int rc = suhmo_level_create(&L, desc);
         if (rc) return fail(rc);                              // (no device: rc -3 with suhmo_level_create's message)
-        L->batch_owned = 1;
+        L->batch_owned = 1; L->zb_off = 1;                    // (an ensemble's launches load every member's bed elevation)
         B->mem.push_back(L);
         if (k == 0) {                                         // (a bottom the one launch cannot take: refused before the other members are allocated)
             B->ndepth = L->ndepth; B->bottom_max_cells = L->bottom_one_launch_max_cells;

@@ -859,6 +859,7 @@ int suhmo_build_mg_coefficients(suhmo_level *L, bool with_faces, hipStream_t st)
     // become so now, it looks again
     if (!L->coarse_mask_ok && (L->d[0].v.ext[0] || L->d[0].v.ext[1])) suhmo_mask_halo_written(L);
     L->coarse_mask_ok = 1;
+    if (nd > 1) suhmo_zb_written(L);        // (the coarse depths' bed elevations are new averages: each is scanned on its own, suhmo_common.h)
     return suhmo_agg_gather_static(L, with_faces, st);
 }
 extern "C" int suhmo_level_build_mg_coefficients(suhmo_level_t *L, suhmo_stream_t s)

@@ -163,6 +163,8 @@ struct Depth {
     int bcoef_pending;   // depth 0: the next streaming relax forms the face coefficients from phi as loaded (UpdateOperator) and stores them
     double *phi_alt;   // second phi canvas: the fused GSRB kernel writes out of place (ping-pong)
     int phi_fresh;     // strips: halo rows of phi (each rank-boundary side) that hold the neighbour's CURRENT values
+    int zb_state;      // what is known about the depth's bed elevation (suhmo_level::zb_known): SUHMO_ZB_UNKNOWN / _UNIFORM / _VARYING
+    double zb_value;   // _UNIFORM: the value of every cell
 };
 
 struct VGraph {                 // a V-cycle captured for one set of solver parameters and one state of the phi ping-pong (suhmo_fas.hip)
@@ -173,6 +175,9 @@ struct VGraph {                 // a V-cycle captured for one set of solver para
     int rout_req, rout_done, rout_np; const double *rout_rhs;     // the residual its last launch was asked to leave behind (resout_req, resout_rhs) and did
     int bcoef_in_relax; long n_bcoef_in_relax;                    // captured with the option (part of the key); its launches that form depth 0's faces
     int mask_clean; long n_bcoef_unmasked, n_relax_unmasked;      // captured with the ice mask known clean (part of the key); its launches that leave the mask out
+    // captured with these depths' bed known uniform (bit d; part of the key, and with any bit set the count of writes to the bed too: the
+    // launches carry the VALUE); its launches per depth that take the bed as a scalar
+    unsigned zb_uniform, zb_version; long n_relax_zb[SUHMO_MAXDEPTH];
     int has_scan;                                                 // its (masked) k_bcoef_fused also writes the scan word: a launch of it can carry a scan of the mask
 };
 struct ProfEv { hipEvent_t a, b; long cells; int restricts; };   // restricts: 1 the launch also did the restriction (RST), 2 it also formed the face coefficients (BCF: neither read counts it)
@@ -265,6 +270,21 @@ struct suhmo_level {
     int mask_scan_errors;                       // event queries that failed for good (not "not ready"): after three the level stops scanning
     unsigned *mask_host; hipEvent_t mask_ev;    // pinned word the scan's answer arrives in (0: nothing below 1e-6), the event behind the copy
     long mask_scans, bcoef_unmasked, relax_unmasked;   // read-only options mask_scans, bcoef_unmasked_launches, relax_unmasked_launches
+    // what is known about the BED ELEVATION across cycles (option zb_known, default 1; 0: nothing is scanned, every launch loads the array).
+    // zb is caller data like the mask: it changes through the entry points that write SUHMO_F_ZB on any depth (suhmo_zb_written) and through
+    // MGnewOp's averages (suhmo_build_mg_coefficients); between two writes what one scan found stays true.  UNIFORM: the level's own cells of
+    // the depth -- all a streaming launch of a whole level reads -- hold ONE bit pattern (compared as 64-bit integers: -0.0 is not +0.0, a NaN
+    // equals itself), kept in Depth::zb_value; VARYING: they do not.  Every depth is scanned on its own (an average (c + c + c + c) / 4 is c
+    // for many values, not for all).  The first V-cycle after a write launches the scan (k_zb_scan, one launch per depth), a copy of the
+    // answers into pinned memory and an event follow on the stream, later cycles ask the event (hipEventQuery: never a wait); until the answer
+    // is there everything runs as without the option.  zb_off: nothing is ever known -- the caller holds a writable pointer
+    // (suhmo_level_field_view), or the level serves a hierarchy, an ensemble or the agglomerated depths of a rank strip.
+    int zb_known, zb_off;
+    unsigned zb_version, zb_scan_version;       // writes so far; the one the scan in flight (zb_scan_pending) looked at
+    int zb_scan_pending, zb_scan_errors;        // (errors: event queries that failed for good; after three the level stops scanning)
+    unsigned long long *zb_dev, *zb_host;       // per depth two words, [2 d] differing cells seen, [2 d + 1] the first cell's bits: on the device, in pinned memory
+    hipEvent_t zb_ev;
+    long zb_scans, relax_zb_uniform[SUHMO_MAXDEPTH];   // read-only options zb_scans, relax_zb_uniform_launches (+ _d<depth>)
     int overlap_halo;           // rank strips, streaming kernel: the halo exchange travels on a second stream while the chunks that do not
                                 // read halo rows relax; the two end chunks follow (env SUHMO_OVERLAP_HALO; 1 = default: with the native, stream-ordered
                                 // RCCL transport only; 2 = with any hook, the caller vouches that it orders against the stream it is given; 0 = off)
@@ -304,11 +324,27 @@ static inline void suhmo_mask_written(suhmo_level *L)
 }
 // a write to the halo rows of a rank strip's mask only (the neighbours' cells): the strip's own averages stand, what a scan found does not
 static inline void suhmo_mask_halo_written(suhmo_level *L) { L->mask_version++; L->mask_state = SUHMO_MASK_UNKNOWN; }
+enum { SUHMO_ZB_UNKNOWN = 0, SUHMO_ZB_UNIFORM = 1, SUHMO_ZB_VARYING = 2 };
+// a write to the bed elevation of any depth (cells, ghost ring or halo rows): nothing about it holds any more
+static inline void suhmo_zb_written(suhmo_level *L)
+{
+    L->zb_version++;
+    for (int d = 0; d < SUHMO_MAXDEPTH; d++) L->d[d].zb_state = SUHMO_ZB_UNKNOWN;
+}
+// the streaming relaxation of `depth` may take the bed as a scalar (whole levels: no rank strip, no AMR patch)
+static inline bool suhmo_zb_uniform(const suhmo_level *L, int depth)
+{
+    return L->zb_known && !L->zb_off && L->d[depth].zb_state == SUHMO_ZB_UNIFORM && !L->ex && L->desc.nx_global == 0;
+}
+void suhmo_zb_poll(suhmo_level *L);                       // suhmo_level.hip: takes the answer of a scan up if it has arrived
+int suhmo_zb_scan_if_due(suhmo_level *L, hipStream_t st); // suhmo_level.hip: launches the scan when nothing is known and none is in flight
+bool suhmo_gsrb_streams(const suhmo_level *L, int depth); // suhmo_gsrb.hip: the depth's relaxation runs on the streaming kernel
 bool suhmo_mask_would_scan(const suhmo_level *L);   // suhmo_bcoef.hip: the next UpdateOperator of depth 0 scans the mask
 // the two device words behind the reductions' scratch (its last double): [0] the per-cycle report "a negative cell" (= the epoch), [1] the scan
 // "a value below 1e-6"; the scan's answer arrives in the pinned scratch at double SUHMO_HSCRATCH_MASK (the reductions use [0, 16))
 #define SUHMO_HSCRATCH_DOUBLES 64
 #define SUHMO_HSCRATCH_MASK 60
+#define SUHMO_HSCRATCH_ZB 16       // 2 x SUHMO_MAXDEPTH words: the answers of a scan of the bed elevation
 static inline unsigned *suhmo_mask_report_word(const suhmo_level *L) { return (unsigned *)(L->scratch + L->scratch_elems - 1); }
 static inline unsigned *suhmo_mask_scan_word(const suhmo_level *L) { return suhmo_mask_report_word(L) + 1; }
 int suhmo_mask_scan_begin(suhmo_level *L, hipStream_t st);   // suhmo_bcoef.hip: clears the scan word on st ...

@@ -175,6 +175,16 @@ static int vcycle_graph(suhmo_level *L, const suhmo_solver_params_t *sp, int nd,
     const int mask_clean = (suhmo_mask_clean(L, 0) ? 1 : 0) | (L->ndepth > 1 && suhmo_mask_clean(L, 1) ? 2 : 0);
     const bool scanning = sp->bcoeff_otf && suhmo_mask_would_scan(L);
     const int bcoef_in_relax = L->bcoef_in_relax != 0;                   // selects depth 0's first pre-smoothing kernel: part of the identity too
+    // ... and so does what is known about the bed elevation, per depth; a graph captured with a depth's bed uniform carries the VALUE in its
+    // launches: it is that bed's alone (zb_version) and goes when the bed has been written since
+    unsigned zb_uniform = 0;
+    for (int d = 0; d < L->ndepth; d++) if (suhmo_zb_uniform(L, d)) zb_uniform |= 1u << d;
+    for (size_t k = L->vgraphs.size(); k-- > 0;) {
+        VGraph &g = L->vgraphs[k];
+        if (!g.zb_uniform || g.zb_version == L->zb_version) continue;
+        if (g.exec) (void)hipGraphExecDestroy(g.exec);
+        L->vgraphs.erase(L->vgraphs.begin() + k);
+    }
     auto launch = [&](const VGraph &g) {
         int rc = 0;
         if (scanning && (rc = suhmo_mask_scan_begin(L, (hipStream_t)s))) return rc;
@@ -184,10 +194,11 @@ static int vcycle_graph(suhmo_level *L, const suhmo_solver_params_t *sp, int nd,
     };
     auto replayed = [&](const VGraph &g) {
         L->bcoef_unmasked += g.n_bcoef_unmasked; L->relax_unmasked += g.n_relax_unmasked; L->bcoef_in_relax_count += g.n_bcoef_in_relax;
+        for (int d = 0; d < L->ndepth; d++) L->relax_zb_uniform[d] += g.n_relax_zb[d];
         if (g.rout_done) { L->resout_done = 1; L->resout_count++; L->resout_np = g.rout_np; }
     };
     auto at_start = [&](const VGraph &g) {
-        if (memcmp(g.key, key, sizeof(key)) || g.mask_clean != mask_clean || g.bcoef_in_relax != bcoef_in_relax) return false;
+        if (memcmp(g.key, key, sizeof(key)) || g.mask_clean != mask_clean || g.bcoef_in_relax != bcoef_in_relax || g.zb_uniform != zb_uniform) return false;
         for (int d = 0; d < L->ndepth; d++) if (L->d[d].fp.f[SUHMO_F_PHI] != g.p0[d] || L->d[d].phi_alt != g.a0[d]) return false;
         if (g.rout_req != (L->resid_in_relax ? L->resout_req : 0) || g.rout_rhs != L->resout_rhs) return false;   // (what the last launch leaves behind)
         return L->d[0].fp.f[SUHMO_F_RHS] == g.rhs;                       // an AMR cycle runs level 0 on a second right-hand-side canvas (suhmo_hier.hip)
@@ -206,6 +217,8 @@ static int vcycle_graph(suhmo_level *L, const suhmo_solver_params_t *sp, int nd,
     if (L->vgraphs.size() >= 16) return 0;                               // (pointer states keep changing: give up capturing)
     if (!L->gstream) HIPCHK(hipStreamCreateWithFlags(&L->gstream, hipStreamNonBlocking));
     VGraph g; memcpy(g.key, key, sizeof(key)); g.exec = nullptr; g.mask_clean = mask_clean; g.has_scan = 0; g.bcoef_in_relax = bcoef_in_relax;
+    g.zb_uniform = zb_uniform; g.zb_version = L->zb_version;
+    long relax_zb[SUHMO_MAXDEPTH]; memcpy(relax_zb, L->relax_zb_uniform, sizeof(relax_zb));
     for (int d = 0; d < SUHMO_MAXDEPTH; d++) { g.p0[d] = g.a0[d] = g.p1[d] = g.a1[d] = nullptr; }
     for (int d = 0; d < L->ndepth; d++) { g.p0[d] = L->d[d].fp.f[SUHMO_F_PHI]; g.a0[d] = L->d[d].phi_alt; }
     g.rhs = L->d[0].fp.f[SUHMO_F_RHS];
@@ -225,6 +238,7 @@ static int vcycle_graph(suhmo_level *L, const suhmo_solver_params_t *sp, int nd,
     g.n_bcoef_unmasked = L->bcoef_unmasked - bcoef_unmasked; g.n_relax_unmasked = L->relax_unmasked - relax_unmasked;
     g.n_bcoef_in_relax = L->bcoef_in_relax_count - bcoef_in_relax_count; L->bcoef_in_relax_count = bcoef_in_relax_count;
     L->bcoef_unmasked = bcoef_unmasked; L->relax_unmasked = relax_unmasked;
+    for (int d = 0; d < SUHMO_MAXDEPTH; d++) { g.n_relax_zb[d] = L->relax_zb_uniform[d] - relax_zb[d]; L->relax_zb_uniform[d] = relax_zb[d]; }
     g.rout_done = L->resout_count != rout_count;                         // (nothing was executed during capture: the flags go back)
     g.rout_np = L->resout_np;
     L->resout_done = rout_before; L->resout_count = rout_count;
@@ -259,6 +273,8 @@ extern "C" int suhmo_level_vcycle(suhmo_level_t *L, const suhmo_solver_params_t 
     // (a bottom solved by the host loop decides on the host after every iteration: not capturable)
     const bool host_bottom = L->bottom_solver && !suhmo_bottom_one_launch(L, nd - 1);
     suhmo_mask_poll(L);                     // (before a graph is chosen: the answer of a scan of the ice mask, if it is there)
+    suhmo_zb_poll(L);                       // ... and of a scan of the bed elevation; where nothing is known and none is in flight, one starts
+    { int rc = suhmo_zb_scan_if_due(L, (hipStream_t)s); if (rc) return rc; }
     const bool graphs = L->graph_max_cells > 0 && !L->ex && !ext && !L->prof_on && !host_bottom && (long)D.v.nx * D.v.ny <= L->graph_max_cells;
     if (graphs) {
         bool done = false;

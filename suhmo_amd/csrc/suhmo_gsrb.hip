@@ -320,6 +320,7 @@ struct FusedGeom {
     // about (inside an AMR cycle the level relaxes against its FAS right-hand side while the true one waits on the second canvas)
     const double *ortrue; double *ores, *olphi;
     double *onorm;      // ... and the chunk's max |RES| (one partial per strip x chunk: k_norm_partial's job, for k_norm_final); NULL: not asked for
+    double zb_uniform;  // ZBU: the bed elevation of every cell of the depth (suhmo_common.h, "what is known about the bed")
 };
 
 // Cold uniform data of k_gsrb_fused<.., BCF>: what only a workgroup at a side of the level reads (the boundary types and values, the level's
@@ -351,20 +352,29 @@ __device__ __forceinline__ double bc_ghost(const SideBC &b, double c) { return (
 // MASKED = false: the level's ice mask is known clean (suhmo_common.h): the ring carries no mask, nothing loads, moves or tests it
 template <bool MASKED> struct RowMask { double mask[2]; };
 template <> struct RowMask<false> {};
-template <bool MASKED>
-struct RowCoef : RowMask<MASKED> {          // per-thread coefficients of its column pair in one row
-    double rhs[2], B[2], Pi[2], zb[2], a[2], byS[2], byN[2];
+// ZBU = true: the depth's bed elevation is known to be one value (suhmo_common.h): the ring carries no zb, nothing loads or moves it, and
+// COMPUTENONLINEARTERMS gets the value itself (FusedGeom::zb_uniform: the same operand, so the same bits)
+template <bool ZBU> struct RowZb { double zb[2]; };
+template <> struct RowZb<true> {};
+template <bool MASKED, bool ZBU = false>
+struct RowCoef : RowMask<MASKED>, RowZb<ZBU> {          // per-thread coefficients of its column pair in one row
+    double rhs[2], B[2], Pi[2], a[2], byS[2], byN[2];
     double bx0, bx1, bx2;
 };
-template <bool MASKED> __device__ __forceinline__ double row_mask(const RowCoef<MASKED> &q, int a)
+template <bool MASKED, bool ZBU> __device__ __forceinline__ double row_mask(const RowCoef<MASKED, ZBU> &q, int a)
 {
     if constexpr (MASKED) return q.mask[a]; else return 1.0;
 }
-#define CP2(d, s, f) d.f[0] = s.f[0]; d.f[1] = s.f[1]
-template <bool HAS_ALPHA, bool MASKED>
-__device__ __forceinline__ void copy_coef(RowCoef<MASKED> &d, const RowCoef<MASKED> &s)
+template <bool MASKED, bool ZBU> __device__ __forceinline__ double row_zb(const RowCoef<MASKED, ZBU> &q, int a, const FusedGeom &g)
 {
-    CP2(d, s, rhs); CP2(d, s, B); CP2(d, s, Pi); CP2(d, s, zb);
+    if constexpr (ZBU) return g.zb_uniform; else return q.zb[a];
+}
+#define CP2(d, s, f) d.f[0] = s.f[0]; d.f[1] = s.f[1]
+template <bool HAS_ALPHA, bool MASKED, bool ZBU>
+__device__ __forceinline__ void copy_coef(RowCoef<MASKED, ZBU> &d, const RowCoef<MASKED, ZBU> &s)
+{
+    CP2(d, s, rhs); CP2(d, s, B); CP2(d, s, Pi);
+    if constexpr (!ZBU) { CP2(d, s, zb); }
     if constexpr (MASKED) { CP2(d, s, mask); }
     if (HAS_ALPHA) { CP2(d, s, a); }
     CP2(d, s, byS); CP2(d, s, byN);
@@ -388,7 +398,7 @@ __device__ __forceinline__ void copy_coef(RowCoef<MASKED> &d, const RowCoef<MASK
 // halo columns per side) and one more row of phi above and below a chunk; rhs, Pi and zb, which only the half-sweeps read, are loaded one
 // step later than B (registers: 247, two waves per SIMD).  Every workgroup forms the faces of its halo cells itself, so no
 // workgroup reads bx or by during the launch; owners store, the domain's last face column / row goes with the last strip / chunk.
-template <int K, bool HAS_ALPHA, int NT, int RM = 0, bool FRHS = false, bool MASKED = true, bool BCF = false>
+template <int K, bool HAS_ALPHA, int NT, int RM = 0, bool FRHS = false, bool MASKED = true, bool BCF = false, bool ZBU = false>
 __global__ __launch_bounds__(NT) void k_gsrb_fused(DV v, FP fp, const double *__restrict__ pin,
                                                    double *__restrict__ pout, suhmo_phys_t ph, FusedGeom g)
 {
@@ -396,6 +406,7 @@ __global__ __launch_bounds__(NT) void k_gsrb_fused(DV v, FP fp, const double *__
     constexpr bool ROUT = RM == 2, RR = RM != 0;
     static_assert(!(FRHS && (RR || HAS_ALPHA)), "the right-hand side is formed in the plain launch of an alpha = 0 operator");
     static_assert(!BCF || (K == 2 && NT == 64 && RM == 0 && !FRHS && !HAS_ALPHA && !MASKED), "the faces are formed in the plain two-sweep launch of a clean-mask alpha = 0 operator");
+    static_assert(!ZBU || (K == 2 && NT == 64 && !HAS_ALPHA && !MASKED), "the bed as a scalar: the two-sweep launches of a clean-mask alpha = 0 operator");
     constexpr bool WIDE = RR || BCF;           // one more ring row and coefficient row, two more halo columns per side
     constexpr int DL = BCF ? 1 : 0;            // steps the half-sweeps (and the output) lag behind
     constexpr int LW = 2 * NT, R = 2 * K + 3 + (WIDE ? 1 : 0);
@@ -440,7 +451,7 @@ __global__ __launch_bounds__(NT) void k_gsrb_fused(DV v, FP fp, const double *__
 
     // coefficient ring as NAMED variables (an indexed array ends up in scratch memory):
     // cf0 = row r (being prefetched), cfM = row r-M
-    RowCoef<MASKED> cf0, cf1, cf2, cf3, cf4, cf5;
+    RowCoef<MASKED, ZBU> cf0, cf1, cf2, cf3, cf4, cf5;
     double racc = 0.0, raccp = 0.0;        // RST: the coarse cell's sums after its first fine row
     double nmax = 0.0;                     // ROUT: max |RES| over this thread's cells of the chunk
     // physical-BC sides this tile can touch (uniform): skip the per-lane boundary tests elsewhere
@@ -478,7 +489,7 @@ __global__ __launch_bounds__(NT) void k_gsrb_fused(DV v, FP fp, const double *__
         if (lcf) {
             int idx = cidx(v, im, wrapj(r));
 #define LD2(dst, p, ix) { double2 t_ = ld2(p, ix); dst[0] = t_.x; dst[1] = t_.y; }
-            if constexpr (!BCF) { LD2(cf0.rhs, (FRHS ? g.fres : f_rhs), idx); LD2(cf0.Pi, f_Pi, idx); LD2(cf0.zb, f_zb, idx); }
+            if constexpr (!BCF) { LD2(cf0.rhs, (FRHS ? g.fres : f_rhs), idx); LD2(cf0.Pi, f_Pi, idx); if constexpr (!ZBU) { LD2(cf0.zb, f_zb, idx); } }
             LD2(cf0.B, f_B, idx);
             if constexpr (MASKED) { if (usemask) { LD2(cf0.mask, f_mask, idx); } else { cf0.mask[0] = 1.0; cf0.mask[1] = 1.0; } }
             if (HAS_ALPHA) LD2(cf0.a, f_a, idx);
@@ -493,7 +504,7 @@ __global__ __launch_bounds__(NT) void k_gsrb_fused(DV v, FP fp, const double *__
             // what only the half-sweeps read comes a step later, with the row that is one step from its first half-sweep (registers)
             if (cval && (r - 1 >= jmin) && (r - 1 <= jmax)) {
                 const int idx = cidx(v, im, wrapj(r - 1));
-                LD2(cf1.rhs, f_rhs, idx); LD2(cf1.Pi, f_Pi, idx); LD2(cf1.zb, f_zb, idx);
+                LD2(cf1.rhs, f_rhs, idx); LD2(cf1.Pi, f_Pi, idx); if constexpr (!ZBU) { LD2(cf1.zb, f_zb, idx); }
             }
         }
         __syncthreads();                   // row r (written at the end of step r-1) is visible
@@ -521,7 +532,7 @@ __global__ __launch_bounds__(NT) void k_gsrb_fused(DV v, FP fp, const double *__
                         if (jf == v.ny - 1 && !v.ext[1]) n = (v.bct[1][1] == 0) ? v.two_v[1][1] - c : c + v.neu[1][1];
                     }
                     double nl, dnl;
-                    nl_terms(ph, c, cf1.B[a], cf1.Pi[a], cf1.zb[a], row_mask(cf1, a), nl, dnl);
+                    nl_terms(ph, c, cf1.B[a], cf1.Pi[a], row_zb(cf1, a, g), row_mask(cf1, a), nl, dnl);
                     const double bxW = a ? cf1.bx1 : cf1.bx0, bxE = a ? cf1.bx2 : cf1.bx1;
                     lo[a] = lofphi_cell(v, v.alpha, c, e, w, n, s, bxE, bxW, cf1.byN[a], cf1.byS[a], nl);
                     cc[a] = c;
@@ -550,7 +561,7 @@ __global__ __launch_bounds__(NT) void k_gsrb_fused(DV v, FP fp, const double *__
         // One half-sweep of row r-m.  The colour offset `a` (which cell of the pair is updated)
         // depends only on the row, so it is WAVE-UNIFORM: branch on it once (scalar branch) and
         // address the pair's coefficients statically instead of selecting per lane.
-        auto advance_a = [&](const int m, const RowCoef<MASKED> &q, auto a_tag) {
+        auto advance_a = [&](const int m, const RowCoef<MASKED, ZBU> &q, auto a_tag) {
             constexpr int a = decltype(a_tag)::value;
             const int j = r - m - DL;
             const int x = xl + a, i = im + a;
@@ -569,7 +580,7 @@ __global__ __launch_bounds__(NT) void k_gsrb_fused(DV v, FP fp, const double *__
                 if (j == v.ny - 1 && (BCF || !v.ext[1])) n = bc_ghost(side_bc<BCF>(v, 1, 1), c);
             }
             double nl, dnl;
-            nl_terms(ph, c, q.B[a], q.Pi[a], q.zb[a], row_mask(q, a), nl, dnl);
+            nl_terms(ph, c, q.B[a], q.Pi[a], row_zb(q, a, g), row_mask(q, a), nl, dnl);
             const double bxW = a ? q.bx1 : q.bx0, bxE = a ? q.bx2 : q.bx1;
             double aterm = HAS_ALPHA ? v.alpha * q.a[a] : v.alpha;
             double lofphi = lofphi_cell(v, aterm, c, e, w, n, s, bxE, bxW, q.byN[a], q.byS[a], nl);
@@ -577,7 +588,7 @@ __global__ __launch_bounds__(NT) void k_gsrb_fused(DV v, FP fp, const double *__
             double denom = 1.0e-16 + lam + dnl;
             lds[s0 * LW + x] = c + (q.rhs[a] - lofphi) / denom;
         };
-        auto advance = [&](const int m, const RowCoef<MASKED> &q) {
+        auto advance = [&](const int m, const RowCoef<MASKED, ZBU> &q) {
             const int j = r - m - DL;
             if (j >= jmin && j <= jmax) {                      // uniform
                 const int a = (j + v.j0 + ((m - 1) & 1)) & 1;  // uniform: colour offset of this row
@@ -699,7 +710,7 @@ __global__ __launch_bounds__(NT) void k_gsrb_fused(DV v, FP fp, const double *__
         if constexpr (RR) {
             const int jr = r - 2 * K - 1;
             if (own && jr >= jA && jr < jB && jr >= 0 && jr < v.ny) {    // (rank strips: halo rows are advanced, not restricted)
-                const RowCoef<MASKED> &q = (K >= 2) ? cf5 : cf3;
+                const RowCoef<MASKED, ZBU> &q = (K >= 2) ? cf5 : cf3;
                 const int s0 = ring(sr - (2 * K + 1)), sN = ring(sr - 2 * K), sS = ring(sr - (2 * K + 2));
                 const double *row = lds + s0 * LW;
                 double acc = (jr & 1) ? racc : 0.0, accp = (jr & 1) ? raccp : 0.0;
@@ -718,7 +729,7 @@ __global__ __launch_bounds__(NT) void k_gsrb_fused(DV v, FP fp, const double *__
                         if (jr == v.ny - 1 && !v.ext[1]) n = (v.bct[1][1] == 0) ? v.two_v[1][1] - c : c + v.neu[1][1];
                     }
                     double nl, dnl;
-                    nl_terms(ph, c, q.B[a], q.Pi[a], q.zb[a], row_mask(q, a), nl, dnl);
+                    nl_terms(ph, c, q.B[a], q.Pi[a], row_zb(q, a, g), row_mask(q, a), nl, dnl);
                     const double bxW = a ? q.bx1 : q.bx0, bxE = a ? q.bx2 : q.bx1;
                     double aterm = HAS_ALPHA ? v.alpha * q.a[a] : v.alpha;
                     double lofphi = lofphi_cell(v, aterm, c, e, w, n, s, bxE, bxW, q.byN[a], q.byS[a], nl);
@@ -753,12 +764,12 @@ __global__ __launch_bounds__(NT) void k_gsrb_fused(DV v, FP fp, const double *__
         // ---- 4. row r+1 enters the ring (its slot held row r-2K-2: no longer read), rotate
         sr = sr + 1 == R ? 0 : sr + 1;
         if (in_row) { lds[sr * LW + xl] = pnext.x; lds[sr * LW + xl + 1] = pnext.y; }
-        if constexpr (WIDE && K >= 2) copy_coef<HAS_ALPHA, MASKED>(cf5, cf4);
-        if constexpr (K >= 2) { copy_coef<HAS_ALPHA, MASKED>(cf4, cf3); copy_coef<HAS_ALPHA, MASKED>(cf3, cf2); }
-        else if constexpr (RR) copy_coef<HAS_ALPHA, MASKED>(cf3, cf2);
-        copy_coef<HAS_ALPHA, MASKED>(cf2, cf1);
+        if constexpr (WIDE && K >= 2) copy_coef<HAS_ALPHA, MASKED, ZBU>(cf5, cf4);
+        if constexpr (K >= 2) { copy_coef<HAS_ALPHA, MASKED, ZBU>(cf4, cf3); copy_coef<HAS_ALPHA, MASKED, ZBU>(cf3, cf2); }
+        else if constexpr (RR) copy_coef<HAS_ALPHA, MASKED, ZBU>(cf3, cf2);
+        copy_coef<HAS_ALPHA, MASKED, ZBU>(cf2, cf1);
         if constexpr (BCF) { CP2(cf1, cf0, B); bw1 = bw0; be1 = be0; }      // (its faces are formed in the next step, the rest is loaded then)
-        else copy_coef<HAS_ALPHA, MASKED>(cf1, cf0);
+        else copy_coef<HAS_ALPHA, MASKED, ZBU>(cf1, cf0);
     }
     if constexpr (ROUT) {
         if (g.onorm) {                         // (uniform) the chunk's max norm: a maximum, so the order of the lanes does not matter
@@ -789,6 +800,7 @@ struct RelaxStep {
     int S, T, chunks;            // tile
     int K, NT;                   // streaming
     bool masked;                 // streaming: the ice mask is not known clean (or alpha != 0): the instantiation that reads it
+    bool zbu;                    // streaming: the depth's bed elevation is known to be one value: the instantiation that takes it as a scalar
     // what the launch absorbs: it restricts; it leaves the residual of the final phi behind; it forms the FAS right-hand side; it forms depth
     // 0's faces; it adds the prolonged correction while loading
     bool rst, rout, frhs, bcf, prolong;
@@ -802,22 +814,26 @@ struct RelaxStep {
 // stands for the launches of their (K, NT, RM, masked) that also take alpha or form the right-hand side or the faces
 typedef void (*FusedFn)(DV, FP, const double *, double *, suhmo_phys_t, FusedGeom);
 struct FusedKernel { int key; FusedFn fn; int slots; };
-constexpr int fused_key(int K, bool alpha, int NT, int RM, bool frhs, bool masked, bool bcf)
+constexpr int fused_key(int K, bool alpha, int NT, int RM, bool frhs, bool masked, bool bcf, bool zbu = false)
 {
-    return K | RM << 4 | alpha << 8 | frhs << 9 | masked << 10 | bcf << 11 | NT << 12;       // (K, RM < 16)
+    return K | RM << 4 | alpha << 8 | frhs << 9 | masked << 10 | bcf << 11 | NT << 12 | zbu << 24;       // (K, RM < 16; NT < 4096)
 }
 #define FK(K, A, NT, RM, F, M, B) {fused_key(K, A, NT, RM, F, M, B), k_gsrb_fused<K, A, NT, RM, F, M, B>, 0}
+// the launches of the clean-mask alpha = 0 cycle at K = 2, NT = 64 with the bed as a scalar (ZBU); the plain ones have their own occupancy
+#define FK_ZBU(RM, F, B) {fused_key(2, false, 64, RM, F, false, B, true), k_gsrb_fused<2, false, 64, RM, F, false, B, true>, 0}
 #define FK_PLAIN(K, NT, RM) FK(K, false, NT, RM, false, true, false), FK(K, false, NT, RM, false, false, false)
 static FusedKernel fused_kernels[] = {
     FK_PLAIN(2, 64, 0), FK_PLAIN(2, 64, 1), FK_PLAIN(2, 64, 2), FK_PLAIN(1, 64, 0), FK_PLAIN(2, 256, 0), FK_PLAIN(1, 256, 0),
     FK(1, true, 64, 0, false, true, false), FK(2, true, 64, 0, false, true, false), FK(1, true, 256, 0, false, true, false), FK(2, true, 256, 0, false, true, false),
     FK(2, false, 64, 0, true, true, false), FK(2, false, 64, 0, true, false, false), FK(2, false, 64, 0, false, false, true),
+    FK_ZBU(0, false, false), FK_ZBU(1, false, false), FK_ZBU(2, false, false), FK_ZBU(0, true, false), FK_ZBU(0, false, true),
 };
+#undef FK_ZBU
 #undef FK_PLAIN
 #undef FK
-static FusedKernel *fused_kernel(int K, bool alpha, int NT, int RM, bool frhs, bool masked, bool bcf)
+static FusedKernel *fused_kernel(int K, bool alpha, int NT, int RM, bool frhs, bool masked, bool bcf, bool zbu)
 {
-    const int key = fused_key(K, alpha, NT, RM, frhs, masked, bcf);
+    const int key = fused_key(K, alpha, NT, RM, frhs, masked, bcf, zbu);
     for (FusedKernel &k : fused_kernels) if (k.key == key) return &k;
     return nullptr;
 }
@@ -831,8 +847,8 @@ static int launch_fused(suhmo_level *L, int depth, const RelaxStep &s, hipStream
     Depth &D = L->d[depth];
     const DV &v = D.v;
     // the one check that relax_step handed over a launch that exists: alpha with no variant, the variants whole (no part) and one at a time
-    FusedKernel *k = fused_kernel(K, v.alpha != 0.0, NT, RM, s.frhs, s.masked, s.bcf);
-    FusedKernel *plain = (v.alpha != 0.0 || s.frhs || s.bcf) ? fused_kernel(K, false, NT, RM, false, s.masked, false) : k;   // (whose occupancy it has)
+    FusedKernel *k = fused_kernel(K, v.alpha != 0.0, NT, RM, s.frhs, s.masked, s.bcf, s.zbu);
+    FusedKernel *plain = (v.alpha != 0.0 || s.frhs || s.bcf) ? fused_kernel(K, false, NT, RM, false, s.masked, false, s.zbu) : k;   // (whose occupancy it has)
     if (!k || !plain || (part && (s.frhs || s.bcf)) || (s.bcf && s.prolong)) { suhmo_set_error("internal: a streaming relaxation step without a kernel"); return -4; }
     if (!D.phi_alt) {
         HIPCHK(hipMalloc(&D.phi_alt, D.elems * sizeof(double)));
@@ -850,7 +866,7 @@ static int launch_fused(suhmo_level *L, int depth, const RelaxStep &s, hipStream
     // a partial second round costs a full one), but never shorter than 16K rows so that the
     // 4K-row pipeline fill stays small; measured on MI355X: profiles/r01_b_hc_sweep.log
     {
-        if (!plain->slots) {                                      // per (K, NT, RM) instantiation, with / without the mask: its own occupancy
+        if (!plain->slots) {                                      // per (K, NT, RM) instantiation, with / without the mask and the bed: its own occupancy
             int nb = 0, ncu = 0, dev = 0;
             HIPCHK(hipGetDevice(&dev));
             HIPCHK(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev));
@@ -911,6 +927,7 @@ static int launch_fused(suhmo_level *L, int depth, const RelaxStep &s, hipStream
         g.rres = C.fp.f[SUHMO_F_RES]; g.rphi = C.fp.f[SUHMO_F_PHI]; g.rP = C.v.P; g.rgy = C.v.gy;
         C.phi_fresh = 0;
     }
+    g.zb_uniform = s.zbu ? D.zb_value : 0.0;
     g.fres = nullptr; g.frhs = g.flphi = g.fphiold = nullptr;
     g.ortrue = nullptr; g.ores = g.olphi = nullptr; g.onorm = nullptr;
     if (RM == 2) {
@@ -928,6 +945,7 @@ static int launch_fused(suhmo_level *L, int depth, const RelaxStep &s, hipStream
     if (s.bcf) { D.bcoef_pending = 0; L->bcoef_in_relax_count++; suhmo_faces_made(L); L->bcoef_unmasked++; }   // (it is the cycle's unmasked UpdateOperator too)
     hipLaunchKernelGGL(k->fn, dim3(g.ntiles), dim3(NT), 0, st, v, D.fp, pin, D.phi_alt, L->ph, g);
     if (unmasked) L->relax_unmasked++;
+    if (s.zbu) L->relax_zb_uniform[depth]++;
     if (part != 1) { std::swap(D.fp.f[SUHMO_F_PHI], D.phi_alt); suhmo_fp_changed(); }
     return 0;
 }
@@ -1490,6 +1508,8 @@ static RelaxStep relax_step(const suhmo_level *L, int depth, int left, int tail,
     // the variants exist for the two-sweep launch of one-wave workgroups with alpha = 0 (with aCoef the extra coefficient row no longer fits
     // 2 waves per SIMD); restricting and the residual belong to the launch that ends the sweeps, not on AMR patches
     const bool variants = K == 2 && s.NT == 64 && v.alpha == 0.0, last = K == left;
+    // the bed is known to be one value (suhmo_common.h): every variant of the clean-mask cycle of a whole level has an instantiation without it
+    s.zbu = variants && !s.masked && !stored && suhmo_zb_uniform(L, depth);
     s.rst = can_restrict && variants && last && (!stored || (ext && L->desc.nx_global == 0 && v.gy >= 5));
     // the launch that ends the cycle (armed by the cycle for its last relax of depth 0) also leaves the residual of the final phi behind (same
     // needs as the restricting launch: one more final row and column around a chunk)
@@ -1504,6 +1524,9 @@ static RelaxStep relax_step(const suhmo_level *L, int depth, int left, int tail,
     s.adv = ext ? plan_halo_advance(F, s.need, (absorb & ABSORB_RHS) ? F : 2 * (left - K) + tail, v.gy - s.need, s.rst) : 0;
     return s;
 }
+
+// a two-sweep relaxation of the depth runs on the streaming kernel (what the scan of the bed elevation asks, suhmo_level.hip)
+bool suhmo_gsrb_streams(const suhmo_level *L, int depth) { return relax_step(L, depth, 2, 0, false, 0, false, 0).path == STEP_STREAM; }
 
 // ---- what suhmo_fas.hip asks before it leaves a pass to the first launch of a relaxation: would that launch absorb it?
 // the first relaxation of a coarse FAS depth can form its right-hand side itself

@@ -86,6 +86,7 @@ int hier_copy(suhmo_hier *H, int l, int dst, int src, suhmo_stream_t s)
     if (dst == SUHMO_F_PHI) { for (suhmo_level *L : H->lev[l].box) L->d[0].phi_fresh = 0; H->phi_ver[l]++; }
     if (dst == SUHMO_F_PHI && l == 0) H->phi_shadow_fresh = false;
     if (dst == SUHMO_F_MASK) for (suhmo_level *L : H->lev[l].box) suhmo_mask_written(L);
+    if (dst == SUHMO_F_ZB) for (suhmo_level *L : H->lev[l].box) suhmo_zb_written(L);
     if (l == 0) H->base_full_ver++;
     if (l == 0) {
         suhmo_level *L = base_of(H);
@@ -418,6 +419,7 @@ int suhmo_hier_create_on_(suhmo_hier **out, const suhmo_level_desc_t *base, suhm
     H->base_borrowed = adopt != nullptr;
     int rc = adopt ? 0 : suhmo_level_create(&B, base);
     if (rc) { delete H; return rc; }
+    B->zb_off = 1;                          // (a hierarchy's base keeps loading its bed elevation: suhmo_common.h)
     H->lev[0].l = 0; H->lev[0].nxd = base->nx; H->lev[0].nyd = base->ny_global; H->lev[0].box.push_back(B);
     H->vglob = B->d[0].v;
     if (H->shadowed) {
@@ -701,6 +703,7 @@ extern "C" int suhmo_hier_exchange(suhmo_hier_t *H, int l, int field, int corner
     ARG(l >= 0 && l < H->nlev && field >= 0 && field < SUHMO_F_COUNT);
     HIPCHK(hipSetDevice(H->device));
     if (field == SUHMO_F_MASK) for (suhmo_level *L : H->lev[l].box) suhmo_mask_written(L);      // (ghost cells of the mask are rewritten)
+    if (field == SUHMO_F_ZB) for (suhmo_level *L : H->lev[l].box) suhmo_zb_written(L);
     return hier_ff(H, l, field, -1, corners != 0, HST(s));
 }
 extern "C" int suhmo_hier_cf_interp(suhmo_hier_t *H, int l, int field_f, int field_c, suhmo_stream_t s)

@@ -594,6 +594,7 @@ int hier_avg(suhmo_hier *H, int l, int ff, int fc, int mode, double val, hipStre
     if ((rc = ensure_field(H, l, ff)) || (rc = ensure_field(H, l - 1, fc)) || (rc = refresh_tables(H, l, st)) || (rc = coarse_args(H, l - 1, st, ca))) return rc;
     if (fc == SUHMO_F_PHI) { for (suhmo_level *L : H->lev[l - 1].box) L->d[0].phi_fresh = 0; H->phi_ver[l - 1]++; }
     if (fc == SUHMO_F_PHI && l == 1) H->phi_shadow_fresh = false;
+    if (fc == SUHMO_F_ZB) for (suhmo_level *L : H->lev[l - 1].box) suhmo_zb_written(L);
     if (fc == SUHMO_F_MASK) for (suhmo_level *L : H->lev[l - 1].box) suhmo_mask_written(L);      // (level 0 is a whole level: it may know its mask clean)
     if (mode == 1) {                                        // geometry only: every holder of coarse cells marks / zeroes its own
         if (V.avg_cov.n) {
@@ -710,6 +711,7 @@ int hier_reflux(suhmo_hier *H, int l, int field_c, hipStream_t st, int residual)
     int rc;
     CoarseArgs ca;
     if ((rc = ensure_field(H, l - 1, field_c)) || (rc = refresh_tables(H, l, st))) return rc;
+    if (field_c == SUHMO_F_ZB) for (suhmo_level *L : H->lev[l - 1].box) suhmo_zb_written(L);
     if (field_c == SUHMO_F_MASK) for (suhmo_level *L : H->lev[l - 1].box) suhmo_mask_written(L);
     { const int fl[3] = {SUHMO_F_PHI, SUHMO_F_BX, SUHMO_F_BY};
       if (l == 1) { if ((rc = refresh_base(H, fl, 3, st))) return rc; }

@@ -4,6 +4,7 @@
 // gfx950 only.  Reference citations: file:line in the SUHMO checkout.
 #include "suhmo_hier.h"
 #include "suhmo_level_int.h"
+#include "suhmo_reduce.h"
 #include <algorithm>
 #include <cstdarg>
 #include <cmath>
@@ -181,7 +182,7 @@ int suhmo_level_create_(suhmo_level_t **out, const suhmo_level_desc_t *desc, boo
     L->resout_req = L->resout_armed = L->resout_done = 0; L->resout_rhs = nullptr; L->resout_count = 0; L->resid_in_relax = 1;
     L->graph_max_cells = 1500000; L->gstream = nullptr; L->vgraph_replays = 0; memset(L->vgraph_seen, 0, sizeof(L->vgraph_seen));
     L->fused_min_cells = 1000000;
-    L->skip_mask = 1; L->mask_known = 1; L->poll_readback = 1;
+    L->skip_mask = 1; L->mask_known = 1; L->poll_readback = 1; L->zb_known = 1;
     L->bottom_solver = 0; L->bottom_one_launch_max_cells = 16384;    // (every bottom the one-launch kernel's LDS holds: up to 128 x 128)
     L->bottom_ctr = nullptr; L->bottom_host_iters = L->bottom_host_solves = 0;
     // ... and ONE place where the environment may override them, read when a level is created: the A/B runs DESIGN.md quotes and the tests that
@@ -196,7 +197,7 @@ int suhmo_level_create_(suhmo_level_t **out, const suhmo_level_desc_t *desc, boo
             {"SUHMO_RESID_IN_RELAX", &suhmo_level::resid_in_relax}, {"SUHMO_BCOEF_IN_RELAX", &suhmo_level::bcoef_in_relax}, {"SUHMO_TILE_STRIPS", &suhmo_level::tile_strips}, {"SUHMO_TILE_CHUNKS", &suhmo_level::tile_chunks},
             {"SUHMO_TILE_RESTRICT", &suhmo_level::tile_restrict}, {"SUHMO_TILE_ORDER", &suhmo_level::tile_order}, {"SUHMO_FAS_RHS_IN_RELAX", &suhmo_level::fas_rhs_in_relax},
             {"SUHMO_TILE_S", &suhmo_level::tile_s}, {"SUHMO_GSRB_TILE", &suhmo_level::gsrb_tile}, {"SUHMO_TILE_T", &suhmo_level::tile_t},
-            {"SUHMO_FUSED_RESTRICT", &suhmo_level::fused_restrict}, {"SUHMO_SKIP_MASK", &suhmo_level::skip_mask}, {"SUHMO_MASK_KNOWN", &suhmo_level::mask_known},
+            {"SUHMO_FUSED_RESTRICT", &suhmo_level::fused_restrict}, {"SUHMO_SKIP_MASK", &suhmo_level::skip_mask}, {"SUHMO_MASK_KNOWN", &suhmo_level::mask_known}, {"SUHMO_ZB_KNOWN", &suhmo_level::zb_known},
             {"SUHMO_POLL_READBACK", &suhmo_level::poll_readback}, {"SUHMO_AVG_OVERLAP", &suhmo_level::avg_overlap}};
         static const LongKnob longs[] = {
             {"SUHMO_AGG_MIN_CELLS", &suhmo_level::agg_min_cells}, {"SUHMO_TILE_MAX_CELLS", &suhmo_level::tile_max_cells},
@@ -249,12 +250,15 @@ int suhmo_level_create_(suhmo_level_t **out, const suhmo_level_desc_t *desc, boo
         D.nbox = L->desc.nbox;
         memset(&D.fp, 0, sizeof(D.fp));
         D.phi_alt = nullptr; D.prolong_pending = 0; D.rhs_pending = 0; D.bcoef_pending = 0; D.phi_fresh = 0;
+        D.zb_state = SUHMO_ZB_UNKNOWN; D.zb_value = 0.0;
     }
     L->scratch = nullptr; L->scratch_elems = 0; L->hscratch = nullptr; L->hscratch_dev = nullptr; L->hseq = 0;
     L->mask_epoch = 0; L->maskflag_epoch = 0; L->mask_reported = 0; L->coarse_mask_ok = 0;
     L->mask_state = SUHMO_MASK_UNKNOWN; L->mask_version = 1; L->mask_scan_version = 0; L->mask_scan_pending = 0; L->mask_capturing = 0;
     L->mask_scan_captured = 0; L->mask_view = 0; L->mask_scan_errors = 0;
     L->mask_host = nullptr; L->mask_ev = nullptr; L->mask_scans = L->bcoef_unmasked = L->relax_unmasked = 0;
+    L->zb_off = 0; L->zb_version = 1; L->zb_scan_version = 0; L->zb_scan_pending = 0; L->zb_scan_errors = 0;
+    L->zb_dev = L->zb_host = nullptr; L->zb_ev = nullptr; L->zb_scans = 0; memset(L->relax_zb_uniform, 0, sizeof(L->relax_zb_uniform));
     L->stub = 1;
     if (!stub) { int rc = level_storage(L); if (rc) { suhmo_level_destroy(L); return rc; } }
     *out = L;
@@ -279,6 +283,8 @@ static int level_storage(suhmo_level *L)
     HIPCHK(hipHostMalloc(&L->hscratch, SUHMO_HSCRATCH_DOUBLES * sizeof(double), hipHostMallocMapped | hipHostMallocCoherent));
     memset(L->hscratch, 0, SUHMO_HSCRATCH_DOUBLES * sizeof(double));
     L->mask_host = (unsigned *)(L->hscratch + SUHMO_HSCRATCH_MASK);
+    L->zb_host = (unsigned long long *)(L->hscratch + SUHMO_HSCRATCH_ZB);
+    HIPCHK(hipMalloc(&L->zb_dev, 2 * SUHMO_MAXDEPTH * sizeof(unsigned long long)));
     if (L->poll_readback && hipHostGetDevicePointer((void **)&L->hscratch_dev, L->hscratch, 0) != hipSuccess) { L->hscratch_dev = nullptr; L->poll_readback = 0; (void)hipGetLastError(); }
     return 0;
 }
@@ -308,8 +314,59 @@ extern "C" int suhmo_level_destroy(suhmo_level_t *L)
     if (L->bottom_ctr) (void)hipFree(L->bottom_ctr);
     suhmo_tagmap_release(L->tags);
     if (L->mask_ev) (void)hipEventDestroy(L->mask_ev);
+    if (L->zb_ev) (void)hipEventDestroy(L->zb_ev);
+    if (L->zb_dev) (void)hipFree(L->zb_dev);
     if (L->hscratch) (void)hipHostFree(L->hscratch);
     delete L;
+    return 0;
+}
+
+// ---- what is known about the bed elevation (suhmo_common.h).  The scan of one depth: the bits of every cell of the level against the first
+// cell's; a workgroup that meets another pattern says so (every writer stores the same word), the first one also leaves the pattern
+__global__ __launch_bounds__(256) void k_zb_scan(DV v, const double *__restrict__ zb, unsigned long long *__restrict__ out)
+{
+    const long long first = __double_as_longlong(zb[cidx(v, 0, 0)]);
+    bool differs = false;
+    for_valid_cells(v, [&](int i, int j) { differs = differs || __double_as_longlong(zb[cidx(v, i, j)]) != first; });
+    if (differs) out[0] = 1ull;
+    if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0 && threadIdx.y == 0) out[1] = (unsigned long long)first;
+}
+// the answer of a scan, if it has arrived (an event query: never a wait); a scan of a bed that has been written since is forgotten
+void suhmo_zb_poll(suhmo_level *L)
+{
+    if (!L->zb_scan_pending) return;
+    const hipError_t e = hipEventQuery(L->zb_ev);
+    if (e == hipErrorNotReady) { (void)hipGetLastError(); return; }
+    L->zb_scan_pending = 0;
+    if (e != hipSuccess) { (void)hipGetLastError(); L->zb_scan_errors++; return; }      // (as the mask's: no answer, a later cycle scans again)
+    if (L->zb_scan_version != L->zb_version) return;
+    const volatile unsigned long long *h = L->zb_host;
+    for (int d = 0; d < L->ndepth; d++) {
+        const unsigned long long bits = h[2 * d + 1];
+        L->d[d].zb_state = h[2 * d] ? SUHMO_ZB_VARYING : SUHMO_ZB_UNIFORM;
+        memcpy(&L->d[d].zb_value, &bits, sizeof(double));
+    }
+}
+// whole levels whose relaxation streams on some depth: every other level keeps loading the array and is not scanned
+int suhmo_zb_scan_if_due(suhmo_level *L, hipStream_t st)
+{
+    const DV &v0 = L->d[0].v;
+    if (!L->zb_known || L->zb_off || L->zb_scan_pending || L->zb_scan_errors >= 3 || !L->zb_host || !L->zb_dev || L->d[0].zb_state != SUHMO_ZB_UNKNOWN) return 0;
+    if (L->ex || L->desc.nx_global != 0 || v0.ext[0] || v0.ext[1] || L->batch_owned) return 0;
+    bool streams = false;
+    for (int d = 0; d < L->ndepth && !streams; d++) streams = suhmo_gsrb_streams(L, d);
+    if (!streams) return 0;
+    if (!L->zb_ev) HIPCHK(hipEventCreateWithFlags(&L->zb_ev, hipEventDisableTiming));
+    const size_t bytes = 2 * (size_t)L->ndepth * sizeof(unsigned long long);
+    HIPCHK(hipMemsetAsync(L->zb_dev, 0, bytes, st));
+    for (int d = 0; d < L->ndepth; d++) {
+        const DV &v = L->d[d].v;
+        hipLaunchKernelGGL(k_zb_scan, reduce_grid(v.nx, v.ny, CAP_LEVEL), BLK2D, 0, st, v, (const double *)L->d[d].fp.f[SUHMO_F_ZB], L->zb_dev + 2 * d);
+    }
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(L->zb_host, L->zb_dev, bytes, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipEventRecord(L->zb_ev, st));
+    L->zb_scan_pending = 1; L->zb_scan_version = L->zb_version; L->zb_scans++;
     return 0;
 }
 
@@ -356,7 +413,7 @@ static int *option_slot_int(suhmo_level *L, const char *key)
     static const struct { const char *k; int suhmo_level::*m; } tab[] = {
         {"gsrb_variant", &suhmo_level::gsrb_variant}, {"fused_hc", &suhmo_level::fused_hc}, {"bcoef_fused", &suhmo_level::bcoef_fused}, {"bcoef_tile_x", &suhmo_level::bcoef_tile_x},
         {"fused_nt", &suhmo_level::fused_nt}, {"fused_restrict", &suhmo_level::fused_restrict}, {"strips_rhs_local", &suhmo_level::strips_rhs_local},
-        {"tile_strips", &suhmo_level::tile_strips}, {"overlap_halo", &suhmo_level::overlap_halo}, {"skip_mask", &suhmo_level::skip_mask}, {"mask_known", &suhmo_level::mask_known}, {"tile_chunks",
+        {"tile_strips", &suhmo_level::tile_strips}, {"overlap_halo", &suhmo_level::overlap_halo}, {"skip_mask", &suhmo_level::skip_mask}, {"mask_known", &suhmo_level::mask_known}, {"zb_known", &suhmo_level::zb_known}, {"tile_chunks",
             &suhmo_level::tile_chunks}, {"tile_order", &suhmo_level::tile_order}, {"tile_restrict", &suhmo_level::tile_restrict}, {"fas_rhs_in_relax",
             &suhmo_level::fas_rhs_in_relax}, {"resid_in_relax", &suhmo_level::resid_in_relax}, {"bcoef_in_relax", &suhmo_level::bcoef_in_relax}, {"fas_rhs_fused", &suhmo_level::fas_rhs_fused},
         {"avg_overlap", &suhmo_level::avg_overlap}, {"tile_s", &suhmo_level::tile_s}, {"gsrb_tile", &suhmo_level::gsrb_tile}, {"tile_t", &suhmo_level::tile_t}, {"poll_readback", &suhmo_level::poll_readback}};
@@ -418,6 +475,23 @@ extern "C" int suhmo_level_get_option(const suhmo_level_t *L, const char *key, l
     if (!strcmp(key, "mask_state")) { *value = L->mask_state; return 0; }                 // 0 unknown, 1 clean, 2 dirty, as of the last V-cycle
     if (!strcmp(key, "bcoef_unmasked_launches")) { *value = L->bcoef_unmasked; return 0; }
     if (!strcmp(key, "relax_unmasked_launches")) { *value = L->relax_unmasked; return 0; }
+    {   // read-only (zb_known): the scans so far; per depth ("..._d<depth>", without the suffix: depth 0's state, all depths' launches) what is
+        // known about the bed -- 0 unknown, 1 uniform, 2 varying, as of the last V-cycle -- and the streaming launches that took it as a scalar
+        if (!strcmp(key, "zb_scans")) { *value = L->zb_scans; return 0; }
+        const bool st = !strncmp(key, "zb_state", 8), nl = !strncmp(key, "relax_zb_uniform_launches", 25);
+        const char *rest = st ? key + 8 : nl ? key + 25 : nullptr;
+        if (rest && !*rest) {
+            *value = st ? L->d[0].zb_state : 0;
+            for (int d = 0; nl && d < L->ndepth; d++) *value += L->relax_zb_uniform[d];
+            return 0;
+        }
+        if (rest && rest[0] == '_' && rest[1] == 'd' && rest[2] >= '0' && rest[2] <= '9') {
+            const int d = atoi(rest + 2);
+            if (d >= L->ndepth) { suhmo_set_error("option '%s': the level has %d depths", key, L->ndepth); return -1; }
+            *value = st ? L->d[d].zb_state : L->relax_zb_uniform[d];
+            return 0;
+        }
+    }
     if (!strcmp(key, "vcycle_graph_replays")) { *value = L->vgraph_replays; return 0; }   // read-only counter (graph_max_cells)
     if (!strcmp(key, "bottom_solver")) { *value = L->bottom_solver; return 0; }
     if (!strcmp(key, "track_old_volume")) { *value = L->track_old_volume; return 0; }
@@ -471,6 +545,7 @@ extern "C" int suhmo_level_exchange(suhmo_level_t *L, int depth, int field, suhm
         int rc = L->ex(L->user, L, depth, &field, 1, s);
         if (!rc && field == SUHMO_F_PHI) L->d[depth].phi_fresh = suhmo_halo_rows(v);
         if (field == SUHMO_F_MASK) suhmo_mask_halo_written(L);
+        if (field == SUHMO_F_ZB) suhmo_zb_written(L);
         return rc;
     }
     return 0;
@@ -502,6 +577,7 @@ extern "C" int suhmo_level_field_view(suhmo_level_t *L, int depth, int field, do
     if (!p) { suhmo_set_error("field allocation failed"); return -2; }
     // a writable pointer to the ice mask: the library no longer sees the writes, so it stops keeping anything about the mask for good
     if (field == SUHMO_F_MASK) { L->mask_view = 1; suhmo_mask_written(L); suhmo_level_drop_graphs(L); }
+    if (field == SUHMO_F_ZB) { L->zb_off = 1; suhmo_zb_written(L); suhmo_level_drop_graphs(L); }      // ... and the same for the bed elevation
     if (depth == 0 && (field == SUHMO_F_BX || field == SUHMO_F_BY)) suhmo_faces_made(L);      // (a writable pointer: the caller may load them)
     if (base) *base = p;
     if (pitch) *pitch = L->d[depth].v.P;
@@ -546,6 +622,7 @@ extern "C" int suhmo_level_set_field(suhmo_level_t *L, int depth, int field, con
     HIPCHK(hipSetDevice(L->device));
     if (field == SUHMO_F_PHI) phi_changed(L, depth);
     if (field == SUHMO_F_MASK) suhmo_mask_written(L);
+    if (field == SUHMO_F_ZB) suhmo_zb_written(L);
     if (depth == 0 && (field == SUHMO_F_BX || field == SUHMO_F_BY)) suhmo_faces_made(L);
     return field_io(L, depth, field, (double *)src, ghosted, on_device, true, (hipStream_t)s);
 }
@@ -577,6 +654,7 @@ extern "C" int suhmo_level_put_box(suhmo_level_t *L, int depth, int field, int i
     const DV &v = L->d[depth].v;
     if (field == SUHMO_F_PHI) phi_changed(L, depth);
     if (field == SUHMO_F_MASK) suhmo_mask_written(L);
+    if (field == SUHMO_F_ZB) suhmo_zb_written(L);
     if (depth == 0 && (field == SUHMO_F_BX || field == SUHMO_F_BY)) suhmo_faces_made(L);
     int r[4]; box_region(L, depth, field, ibox, r);
     int j0 = v.j0;                         // fab indices are global: local j = global j - j0
@@ -663,6 +741,7 @@ extern "C" int suhmo_level_unpack_rows(suhmo_level_t *L, int depth, int field, i
     ARG(rows >= 1 && rows <= v.gy);
     HIPCHK(hipSetDevice(L->device));
     if (field == SUHMO_F_MASK) suhmo_mask_halo_written(L);
+    if (field == SUHMO_F_ZB) suhmo_zb_written(L);
     int jstart = side == 0 ? -rows : v.ny;        // ghost rows of that side, ascending j
     if (field == SUHMO_F_BY && side == 1) jstart = v.ny + 1;   // face row ny is owned (see pack)
     hipLaunchKernelGGL(k_unpack_rows, grid2d(v.nx + 1, rows), BLK2D, 0, (hipStream_t)s, v, suhmo_field(L, depth, field), jstart, rows, dev_buf);

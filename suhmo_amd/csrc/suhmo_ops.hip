@@ -44,6 +44,7 @@ extern "C" int suhmo_level_fill_ghosts(suhmo_level_t *L, int depth, int field, i
     CHECK_DF(L, depth, field); ARG(!is_face(field));
     HIPCHK(hipSetDevice(L->device));
     if (!suhmo_field(L, depth, field)) return -2;
+    if (field == SUHMO_F_ZB) suhmo_zb_written(L);
     if (field == SUHMO_F_MASK) suhmo_mask_written(L);      // (the stored ghost ring is part of what the gradient's mask tests read)
     return launch_fill_ghosts(on_level(L, depth), field, homogeneous, (hipStream_t)s);
 }
@@ -178,6 +179,7 @@ int suhmo_exchange_fields(suhmo_level *L, int depth, std::initializer_list<int> 
     int rc = L->ex(L->user, L, depth, fields.begin(), (int)fields.size(), (suhmo_stream_t)st);
     if (!rc) for (int f : fields) if (f == SUHMO_F_PHI) L->d[depth].phi_fresh = suhmo_halo_rows(v);
     for (int f : fields) if (f == SUHMO_F_MASK) suhmo_mask_halo_written(L);
+    for (int f : fields) if (f == SUHMO_F_ZB) suhmo_zb_written(L);
     return rc;
 }
 int suhmo_exchange_list(suhmo_level *L, int depth, const int *fields, int n, hipStream_t st)    // for suhmo_step.hip
@@ -188,6 +190,7 @@ int suhmo_exchange_list(suhmo_level *L, int depth, const int *fields, int n, hip
     int rc = L->ex(L->user, L, depth, fields, n, (suhmo_stream_t)st);
     if (!rc) for (int k = 0; k < n; k++) if (fields[k] == SUHMO_F_PHI) L->d[depth].phi_fresh = suhmo_halo_rows(v);
     for (int k = 0; k < n; k++) if (fields[k] == SUHMO_F_MASK) suhmo_mask_halo_written(L);
+    for (int k = 0; k < n; k++) if (fields[k] == SUHMO_F_ZB) suhmo_zb_written(L);
     return rc;
 }
 // strips: make sure `need` halo rows of phi hold the neighbours' current values.  Every kernel that
@@ -525,6 +528,7 @@ extern "C" int suhmo_level_divergence(suhmo_level_t *L, int depth, int dst_field
     Depth &D = L->d[depth];
     double *dst = suhmo_field(L, depth, dst_field);
     if (dst_field == SUHMO_F_MASK) suhmo_mask_written(L);
+    if (dst_field == SUHMO_F_ZB) suhmo_zb_written(L);
     hipLaunchKernelGGL(k_divergence, grid2d(D.v.nx, D.v.ny), BLK2D, 0, (hipStream_t)s, D.v, D.fp.f[SUHMO_F_BX], D.fp.f[SUHMO_F_BY], dst);
     HIPCHK(hipGetLastError());
     return 0;
@@ -586,6 +590,7 @@ extern "C" int suhmo_level_axby(suhmo_level_t *L, int depth, int dst, int x, int
     HIPCHK(hipSetDevice(L->device));
     if (!suhmo_field(L, depth, dst) || !suhmo_field(L, depth, x) || !suhmo_field(L, depth, y)) return -2;
     if (dst == SUHMO_F_PHI) phi_changed(L, depth);
+    if (dst == SUHMO_F_ZB) suhmo_zb_written(L);
     if (dst == SUHMO_F_MASK) suhmo_mask_written(L);      // (the reports about the ice mask end with any write to it)
     return launch_axby(on_level(L, depth), dst, x, y, a, b, (hipStream_t)s);
 }
@@ -596,6 +601,7 @@ extern "C" int suhmo_level_set_value(suhmo_level_t *L, int depth, int field, dou
     Depth &D = L->d[depth];
     if (field == SUHMO_F_PHI) phi_changed(L, depth);
     if (field == SUHMO_F_MASK) suhmo_mask_written(L);
+    if (field == SUHMO_F_ZB) suhmo_zb_written(L);
     hipLaunchKernelGGL(k_setval, grid2d(D.v.nx, D.v.ny), BLK2D, 0, (hipStream_t)s, D.v, suhmo_field(L, depth, field), val);
     HIPCHK(hipGetLastError());
     return 0;

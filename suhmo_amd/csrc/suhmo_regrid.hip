@@ -169,6 +169,7 @@ int transfer_level(suhmo_hier *O, suhmo_hier *N, int l, const RgFields &fl, hipS
             else if (f == SUHMO_F_PI || f == SUHMO_F_ZS || f == SUHMO_F_MR || f == SUHMO_F_PW) rc = launch_extrap_ghosts(m.on(), f, st);
             if (rc) return rc;
             if (f == SUHMO_F_MASK) for (suhmo_level *L : F.box) suhmo_mask_written(L);
+            if (f == SUHMO_F_ZB) for (suhmo_level *L : F.box) suhmo_zb_written(L);
         }
         return 0;
     };
@@ -220,7 +221,7 @@ extern "C" int suhmo_hier_regrid(suhmo_hier_t *O, int nlev, const int *nbox, con
     }
     // the base level changes hands: nothing the old hierarchy knew about it survives -- its gap-height hierarchy, tag maps, plans and tables go
     // with it, the base level forgets what it knew about its ice mask and its captured V-cycles
-    suhmo_mask_written(B);
+    suhmo_mask_written(B); suhmo_zb_written(B);
     suhmo_level_drop_graphs(B);
     B->resout_req = 0; B->resout_rhs = nullptr; B->resout_done = 0;
     N->base_borrowed = false;

@@ -13,7 +13,7 @@ for K in $KA $KB; do
   i=0
   for ctrs in "FETCH_SIZE" "WRITE_SIZE" "TCC_EA0_RDREQ_sum TCC_EA0_WRREQ_sum"; do
     i=$((i+1))
-    rocprofv3 --pmc $ctrs --output-format csv -d $OUT/k${K}_p$i -- python3 $R/bench.py --steps $K --warmup 2 --no-cpu --no-side > $OUT/k${K}_p$i.log 2>&1 || exit 1
+    timeout -k 10 ${PMC_TIMEOUT:-300} rocprofv3 --pmc $ctrs --output-format csv -d $OUT/k${K}_p$i -- python3 $R/bench.py --steps $K --warmup 2 --no-cpu --no-side > $OUT/k${K}_p$i.log 2>&1 || exit 1
     echo "pass K=$K $ctrs done"
   done
 done
