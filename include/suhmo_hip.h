@@ -133,6 +133,12 @@ int suhmo_level_num_depths(const suhmo_level_t *L);
  * it as a scalar and loads no zb (same operand, same bits); a varying bed, rank strips, AMR patches, hierarchies, ensembles: the array is
  * loaded as before.  0: nothing is scanned.  Read-only: zb_scans, zb_state (depth 0; zb_state_d<depth>: 0 unknown, 1 uniform, 2 varying),
  * relax_zb_uniform_launches (all depths; relax_zb_uniform_launches_d<depth>; launches of graph replays included).
+ * yface_ring (default 1, env SUHMO_YFACE_RING): of those launches the plain one -- it absorbs nothing but a prolongation -- keeps one ring of
+ * y-faces (the north face of a row is the south face of the next), which leaves it three waves per SIMD, and cuts its chunks for its own
+ * occupancy; not on levels that are periodic in y, where face 0 and face ny are two stored rows.  0: two rings, two waves, the chunks of
+ * those.  Same bits either way.  Read-only: relax_yring_launches (all depths; relax_yring_launches_d<depth>; graph replays included);
+ * stream_wg_per_cu_<plain | yring | rst | rout | frhs | bcf>: the workgroups per CU the occupancy query answers for that launch of the
+ * clean-mask, uniform-bed cycle (12 for yring, 8 for the others on MI355X).
  * bcoef_in_relax (default 1): while the mask of a whole level (no rank strip, no AMR patch) is known clean, alpha = 0, depth 0 relaxes on the
  * streaming kernel and the pre-smoothing has at least three sweeps, the V-cycle's UpdateOperator is not a pass of its own: the first
  * pre-smoothing launch of depth 0 forms the face coefficients from the head as it loads it and stores them (same bits), AverageOperator

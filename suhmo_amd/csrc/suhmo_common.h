@@ -178,6 +178,7 @@ struct VGraph {                 // a V-cycle captured for one set of solver para
     // captured with these depths' bed known uniform (bit d; part of the key, and with any bit set the count of writes to the bed too: the
     // launches carry the VALUE); its launches per depth that take the bed as a scalar
     unsigned zb_uniform, zb_version; long n_relax_zb[SUHMO_MAXDEPTH];
+    int yface_ring; long n_relax_yring[SUHMO_MAXDEPTH];           // captured with this yface_ring (part of the key); its launches per depth with one ring of y-faces
     int has_scan;                                                 // its (masked) k_bcoef_fused also writes the scan word: a launch of it can carry a scan of the mask
 };
 struct ProfEv { hipEvent_t a, b; long cells; int restricts; };   // restricts: 1 the launch also did the restriction (RST), 2 it also formed the face coefficients (BCF: neither read counts it)
@@ -285,6 +286,10 @@ struct suhmo_level {
     unsigned long long *zb_dev, *zb_host;       // per depth two words, [2 d] differing cells seen, [2 d + 1] the first cell's bits: on the device, in pinned memory
     hipEvent_t zb_ev;
     long zb_scans, relax_zb_uniform[SUHMO_MAXDEPTH];   // read-only options zb_scans, relax_zb_uniform_launches (+ _d<depth>)
+    int yface_ring;             // 1 (default): the plain two-sweep streaming launch with the bed as a scalar keeps one ring of y-faces and three waves
+                                // per SIMD (not on y-periodic levels); 0: two rings, two waves, the chunk heights of those (env SUHMO_YFACE_RING;
+                                // same bits)
+    long relax_yring[SUHMO_MAXDEPTH];                  // read-only options relax_yring_launches (+ _d<depth>)
     int overlap_halo;           // rank strips, streaming kernel: the halo exchange travels on a second stream while the chunks that do not
                                 // read halo rows relax; the two end chunks follow (env SUHMO_OVERLAP_HALO; 1 = default: with the native, stream-ordered
                                 // RCCL transport only; 2 = with any hook, the caller vouches that it orders against the stream it is given; 0 = off)
@@ -339,6 +344,7 @@ static inline bool suhmo_zb_uniform(const suhmo_level *L, int depth)
 void suhmo_zb_poll(suhmo_level *L);                       // suhmo_level.hip: takes the answer of a scan up if it has arrived
 int suhmo_zb_scan_if_due(suhmo_level *L, hipStream_t st); // suhmo_level.hip: launches the scan when nothing is known and none is in flight
 bool suhmo_gsrb_streams(const suhmo_level *L, int depth); // suhmo_gsrb.hip: the depth's relaxation runs on the streaming kernel
+int suhmo_gsrb_stream_wg_per_cu(const char *which, long *value);   // suhmo_gsrb.hip: read-only options stream_wg_per_cu_<which>; 1: no such name
 bool suhmo_mask_would_scan(const suhmo_level *L);   // suhmo_bcoef.hip: the next UpdateOperator of depth 0 scans the mask
 // the two device words behind the reductions' scratch (its last double): [0] the per-cycle report "a negative cell" (= the epoch), [1] the scan
 // "a value below 1e-6"; the scan's answer arrives in the pinned scratch at double SUHMO_HSCRATCH_MASK (the reductions use [0, 16))

@@ -177,6 +177,7 @@ static int vcycle_graph(suhmo_level *L, const suhmo_solver_params_t *sp, int nd,
     const int bcoef_in_relax = L->bcoef_in_relax != 0;                   // selects depth 0's first pre-smoothing kernel: part of the identity too
     // ... and so does what is known about the bed elevation, per depth; a graph captured with a depth's bed uniform carries the VALUE in its
     // launches: it is that bed's alone (zb_version) and goes when the bed has been written since
+    const int yface_ring = L->yface_ring != 0;                           // selects the plain launches' kernel and chunks: part of the identity too
     unsigned zb_uniform = 0;
     for (int d = 0; d < L->ndepth; d++) if (suhmo_zb_uniform(L, d)) zb_uniform |= 1u << d;
     for (size_t k = L->vgraphs.size(); k-- > 0;) {
@@ -194,11 +195,11 @@ static int vcycle_graph(suhmo_level *L, const suhmo_solver_params_t *sp, int nd,
     };
     auto replayed = [&](const VGraph &g) {
         L->bcoef_unmasked += g.n_bcoef_unmasked; L->relax_unmasked += g.n_relax_unmasked; L->bcoef_in_relax_count += g.n_bcoef_in_relax;
-        for (int d = 0; d < L->ndepth; d++) L->relax_zb_uniform[d] += g.n_relax_zb[d];
+        for (int d = 0; d < L->ndepth; d++) { L->relax_zb_uniform[d] += g.n_relax_zb[d]; L->relax_yring[d] += g.n_relax_yring[d]; }
         if (g.rout_done) { L->resout_done = 1; L->resout_count++; L->resout_np = g.rout_np; }
     };
     auto at_start = [&](const VGraph &g) {
-        if (memcmp(g.key, key, sizeof(key)) || g.mask_clean != mask_clean || g.bcoef_in_relax != bcoef_in_relax || g.zb_uniform != zb_uniform) return false;
+        if (memcmp(g.key, key, sizeof(key)) || g.mask_clean != mask_clean || g.bcoef_in_relax != bcoef_in_relax || g.zb_uniform != zb_uniform || g.yface_ring != yface_ring) return false;
         for (int d = 0; d < L->ndepth; d++) if (L->d[d].fp.f[SUHMO_F_PHI] != g.p0[d] || L->d[d].phi_alt != g.a0[d]) return false;
         if (g.rout_req != (L->resid_in_relax ? L->resout_req : 0) || g.rout_rhs != L->resout_rhs) return false;   // (what the last launch leaves behind)
         return L->d[0].fp.f[SUHMO_F_RHS] == g.rhs;                       // an AMR cycle runs level 0 on a second right-hand-side canvas (suhmo_hier.hip)
@@ -217,7 +218,8 @@ static int vcycle_graph(suhmo_level *L, const suhmo_solver_params_t *sp, int nd,
     if (L->vgraphs.size() >= 16) return 0;                               // (pointer states keep changing: give up capturing)
     if (!L->gstream) HIPCHK(hipStreamCreateWithFlags(&L->gstream, hipStreamNonBlocking));
     VGraph g; memcpy(g.key, key, sizeof(key)); g.exec = nullptr; g.mask_clean = mask_clean; g.has_scan = 0; g.bcoef_in_relax = bcoef_in_relax;
-    g.zb_uniform = zb_uniform; g.zb_version = L->zb_version;
+    g.zb_uniform = zb_uniform; g.zb_version = L->zb_version; g.yface_ring = yface_ring;
+    long relax_yr[SUHMO_MAXDEPTH]; memcpy(relax_yr, L->relax_yring, sizeof(relax_yr));
     long relax_zb[SUHMO_MAXDEPTH]; memcpy(relax_zb, L->relax_zb_uniform, sizeof(relax_zb));
     for (int d = 0; d < SUHMO_MAXDEPTH; d++) { g.p0[d] = g.a0[d] = g.p1[d] = g.a1[d] = nullptr; }
     for (int d = 0; d < L->ndepth; d++) { g.p0[d] = L->d[d].fp.f[SUHMO_F_PHI]; g.a0[d] = L->d[d].phi_alt; }
@@ -239,6 +241,7 @@ static int vcycle_graph(suhmo_level *L, const suhmo_solver_params_t *sp, int nd,
     g.n_bcoef_in_relax = L->bcoef_in_relax_count - bcoef_in_relax_count; L->bcoef_in_relax_count = bcoef_in_relax_count;
     L->bcoef_unmasked = bcoef_unmasked; L->relax_unmasked = relax_unmasked;
     for (int d = 0; d < SUHMO_MAXDEPTH; d++) { g.n_relax_zb[d] = L->relax_zb_uniform[d] - relax_zb[d]; L->relax_zb_uniform[d] = relax_zb[d]; }
+    for (int d = 0; d < SUHMO_MAXDEPTH; d++) { g.n_relax_yring[d] = L->relax_yring[d] - relax_yr[d]; L->relax_yring[d] = relax_yr[d]; }
     g.rout_done = L->resout_count != rout_count;                         // (nothing was executed during capture: the flags go back)
     g.rout_np = L->resout_np;
     L->resout_done = rout_before; L->resout_count = rout_count;

@@ -356,28 +356,34 @@ template <> struct RowMask<false> {};
 // COMPUTENONLINEARTERMS gets the value itself (FusedGeom::zb_uniform: the same operand, so the same bits)
 template <bool ZBU> struct RowZb { double zb[2]; };
 template <> struct RowZb<true> {};
-template <bool MASKED, bool ZBU = false>
-struct RowCoef : RowMask<MASKED>, RowZb<ZBU> {          // per-thread coefficients of its column pair in one row
-    double rhs[2], B[2], Pi[2], a[2], byS[2], byN[2];
+// YR = true: one ring of y-faces.  byN of row j IS byS of row j+1 (the same canvas row of by) wherever y is not periodic within the launch, so
+// a row carries its north face only and a half-sweep takes the south face from the row below it in the ring: one load and two registers per
+// row less (what the third wave per SIMD of the plain launch needs)
+template <bool YR> struct RowByS { double byS[2]; };
+template <> struct RowByS<true> {};
+template <bool MASKED, bool ZBU = false, bool YR = false>
+struct RowCoef : RowMask<MASKED>, RowZb<ZBU>, RowByS<YR> {          // per-thread coefficients of its column pair in one row
+    double rhs[2], B[2], Pi[2], a[2], byN[2];
     double bx0, bx1, bx2;
 };
-template <bool MASKED, bool ZBU> __device__ __forceinline__ double row_mask(const RowCoef<MASKED, ZBU> &q, int a)
+template <bool MASKED, bool ZBU, bool YR> __device__ __forceinline__ double row_mask(const RowCoef<MASKED, ZBU, YR> &q, int a)
 {
     if constexpr (MASKED) return q.mask[a]; else return 1.0;
 }
-template <bool MASKED, bool ZBU> __device__ __forceinline__ double row_zb(const RowCoef<MASKED, ZBU> &q, int a, const FusedGeom &g)
+template <bool MASKED, bool ZBU, bool YR> __device__ __forceinline__ double row_zb(const RowCoef<MASKED, ZBU, YR> &q, int a, const FusedGeom &g)
 {
     if constexpr (ZBU) return g.zb_uniform; else return q.zb[a];
 }
 #define CP2(d, s, f) d.f[0] = s.f[0]; d.f[1] = s.f[1]
-template <bool HAS_ALPHA, bool MASKED, bool ZBU>
-__device__ __forceinline__ void copy_coef(RowCoef<MASKED, ZBU> &d, const RowCoef<MASKED, ZBU> &s)
+template <bool HAS_ALPHA, bool MASKED, bool ZBU, bool YR>
+__device__ __forceinline__ void copy_coef(RowCoef<MASKED, ZBU, YR> &d, const RowCoef<MASKED, ZBU, YR> &s)
 {
     CP2(d, s, rhs); CP2(d, s, B); CP2(d, s, Pi);
     if constexpr (!ZBU) { CP2(d, s, zb); }
     if constexpr (MASKED) { CP2(d, s, mask); }
     if (HAS_ALPHA) { CP2(d, s, a); }
-    CP2(d, s, byS); CP2(d, s, byN);
+    if constexpr (!YR) { CP2(d, s, byS); }
+    CP2(d, s, byN);
     d.bx0 = s.bx0; d.bx1 = s.bx1; d.bx2 = s.bx2;
 }
 
@@ -398,7 +404,7 @@ __device__ __forceinline__ void copy_coef(RowCoef<MASKED, ZBU> &d, const RowCoef
 // halo columns per side) and one more row of phi above and below a chunk; rhs, Pi and zb, which only the half-sweeps read, are loaded one
 // step later than B (registers: 247, two waves per SIMD).  Every workgroup forms the faces of its halo cells itself, so no
 // workgroup reads bx or by during the launch; owners store, the domain's last face column / row goes with the last strip / chunk.
-template <int K, bool HAS_ALPHA, int NT, int RM = 0, bool FRHS = false, bool MASKED = true, bool BCF = false, bool ZBU = false>
+template <int K, bool HAS_ALPHA, int NT, int RM = 0, bool FRHS = false, bool MASKED = true, bool BCF = false, bool ZBU = false, bool YR = false>
 __global__ __launch_bounds__(NT) void k_gsrb_fused(DV v, FP fp, const double *__restrict__ pin,
                                                    double *__restrict__ pout, suhmo_phys_t ph, FusedGeom g)
 {
@@ -407,6 +413,7 @@ __global__ __launch_bounds__(NT) void k_gsrb_fused(DV v, FP fp, const double *__
     static_assert(!(FRHS && (RR || HAS_ALPHA)), "the right-hand side is formed in the plain launch of an alpha = 0 operator");
     static_assert(!BCF || (K == 2 && NT == 64 && RM == 0 && !FRHS && !HAS_ALPHA && !MASKED), "the faces are formed in the plain two-sweep launch of a clean-mask alpha = 0 operator");
     static_assert(!ZBU || (K == 2 && NT == 64 && !HAS_ALPHA && !MASKED), "the bed as a scalar: the two-sweep launches of a clean-mask alpha = 0 operator");
+    static_assert(!YR || (ZBU && RM == 0 && !FRHS && !BCF), "one ring of y-faces: the plain two-sweep launch with the bed as a scalar");
     constexpr bool WIDE = RR || BCF;           // one more ring row and coefficient row, two more halo columns per side
     constexpr int DL = BCF ? 1 : 0;            // steps the half-sweeps (and the output) lag behind
     constexpr int LW = 2 * NT, R = 2 * K + 3 + (WIDE ? 1 : 0);
@@ -451,7 +458,8 @@ __global__ __launch_bounds__(NT) void k_gsrb_fused(DV v, FP fp, const double *__
 
     // coefficient ring as NAMED variables (an indexed array ends up in scratch memory):
     // cf0 = row r (being prefetched), cfM = row r-M
-    RowCoef<MASKED, ZBU> cf0, cf1, cf2, cf3, cf4, cf5;
+    RowCoef<MASKED, ZBU, YR> cf0, cf1, cf2, cf3, cf4, cf5;
+    double ys5[2] = {0.0, 0.0};            // YR: the north face of row r-5, the south face of the oldest row that is still advanced
     double racc = 0.0, raccp = 0.0;        // RST: the coarse cell's sums after its first fine row
     double nmax = 0.0;                     // ROUT: max |RES| over this thread's cells of the chunk
     // physical-BC sides this tile can touch (uniform): skip the per-lane boundary tests elsewhere
@@ -495,10 +503,16 @@ __global__ __launch_bounds__(NT) void k_gsrb_fused(DV v, FP fp, const double *__
             if (HAS_ALPHA) LD2(cf0.a, f_a, idx);
             if constexpr (BCF) { bw0 = f_B[idx - 1]; be0 = f_B[idx + 2]; }      // (the stored ghost cell at a side of the level)
             else {
-                LD2(cf0.byS, f_by, idx); LD2(cf0.byN, f_by, idx + v.P);
+                if constexpr (!YR) { LD2(cf0.byS, f_by, idx); }
+                LD2(cf0.byN, f_by, idx + v.P);
                 double2 bxp = ld2(f_bx, idx);
                 cf0.bx0 = bxp.x; cf0.bx1 = bxp.y; cf0.bx2 = f_bx[idx + 2];
             }
+        }
+        if constexpr (YR) {
+            // the chunk's first row has no loaded row below it: its south face, as that row's north face, one step early (launch_fused keeps
+            // y-periodic levels off this instantiation: no canvas row is an image of another here, this one is row jmin of by)
+            if (cval && r == jmin - 1) { LD2(cf0.byN, f_by, cidx(v, im, r) + v.P); }
         }
         if constexpr (BCF) {
             // what only the half-sweeps read comes a step later, with the row that is one step from its first half-sweep (registers)
@@ -561,7 +575,7 @@ __global__ __launch_bounds__(NT) void k_gsrb_fused(DV v, FP fp, const double *__
         // One half-sweep of row r-m.  The colour offset `a` (which cell of the pair is updated)
         // depends only on the row, so it is WAVE-UNIFORM: branch on it once (scalar branch) and
         // address the pair's coefficients statically instead of selecting per lane.
-        auto advance_a = [&](const int m, const RowCoef<MASKED, ZBU> &q, auto a_tag) {
+        auto advance_a = [&](const int m, const RowCoef<MASKED, ZBU, YR> &q, const double (&byS)[2], auto a_tag) {
             constexpr int a = decltype(a_tag)::value;
             const int j = r - m - DL;
             const int x = xl + a, i = im + a;
@@ -583,18 +597,22 @@ __global__ __launch_bounds__(NT) void k_gsrb_fused(DV v, FP fp, const double *__
             nl_terms(ph, c, q.B[a], q.Pi[a], row_zb(q, a, g), row_mask(q, a), nl, dnl);
             const double bxW = a ? q.bx1 : q.bx0, bxE = a ? q.bx2 : q.bx1;
             double aterm = HAS_ALPHA ? v.alpha * q.a[a] : v.alpha;
-            double lofphi = lofphi_cell(v, aterm, c, e, w, n, s, bxE, bxW, q.byN[a], q.byS[a], nl);
-            double lam = lambda_cell(v, aterm, bxE, bxW, q.byN[a], q.byS[a]);
+            double lofphi = lofphi_cell(v, aterm, c, e, w, n, s, bxE, bxW, q.byN[a], byS[a], nl);
+            double lam = lambda_cell(v, aterm, bxE, bxW, q.byN[a], byS[a]);
             double denom = 1.0e-16 + lam + dnl;
             lds[s0 * LW + x] = c + (q.rhs[a] - lofphi) / denom;
         };
-        auto advance = [&](const int m, const RowCoef<MASKED, ZBU> &q) {
+        // byS: the row's south faces -- its own, or (YR) the north faces of the row below it in the ring
+        auto advance_s = [&](const int m, const RowCoef<MASKED, ZBU, YR> &q, const double (&byS)[2]) {
             const int j = r - m - DL;
             if (j >= jmin && j <= jmax) {                      // uniform
                 const int a = (j + v.j0 + ((m - 1) & 1)) & 1;  // uniform: colour offset of this row
-                if (a) { if (cval) advance_a(m, q, std::integral_constant<int, 1>()); }
-                else   { if (cval) advance_a(m, q, std::integral_constant<int, 0>()); }
+                if (a) { if (cval) advance_a(m, q, byS, std::integral_constant<int, 1>()); }
+                else   { if (cval) advance_a(m, q, byS, std::integral_constant<int, 0>()); }
             }
+        };
+        auto advance = [&](const int m, const RowCoef<MASKED, ZBU, YR> &q, const RowCoef<MASKED, ZBU, YR> &below) {
+            if constexpr (YR) advance_s(m, q, below.byN); else advance_s(m, q, q.byS);
         };
         if constexpr (BCF) {
             // ---- 1c / 2. the faces of row r-1 (cf1), around the half-sweeps of rows r-2 .. r-5 (cf2 .. cf5)
@@ -671,7 +689,7 @@ __global__ __launch_bounds__(NT) void k_gsrb_fused(DV v, FP fp, const double *__
                 } else { cf1.byS[0] = 0.0; cf1.byS[1] = 0.0; }      // (the chunk's first loaded row: at the level's bottom set one step later, else never valid)
                 gpv[t] = make_double2(gx0, gx1); gpv[NT + t] = make_double2(gy0, gy1);
             }
-            advance(1, cf2);
+            advance(1, cf2, cf3);
             __syncthreads();                   // (also: Re of row r-1 is visible)
             if (faces && cval) {
                 double reW = rre[xl == 0 ? 0 : xl - 1], reE = rre[xl == LW - 2 ? LW - 1 : xl + 2];
@@ -689,20 +707,20 @@ __global__ __launch_bounds__(NT) void k_gsrb_fused(DV v, FP fp, const double *__
                 }
                 rep0 = rn0; rep1 = rn1;
             }
-            advance(2, cf3);
+            advance(2, cf3, cf4);
             __syncthreads();
-            advance(3, cf4);
+            advance(3, cf4, cf5);
             __syncthreads();
-            advance(4, cf5);
+            advance(4, cf5, cf5);              // (never YR: the row's own south faces)
         } else {
-        advance(1, cf1);
+        advance(1, cf1, cf2);
         __syncthreads();
-        advance(2, cf2);
+        advance(2, cf2, cf3);
         if constexpr (K >= 2) {
             __syncthreads();
-            advance(3, cf3);
+            advance(3, cf3, cf4);
             __syncthreads();
-            advance(4, cf4);
+            if constexpr (YR) advance_s(4, cf4, ys5); else advance(4, cf4, cf4);
         }
         }
 
@@ -710,7 +728,7 @@ __global__ __launch_bounds__(NT) void k_gsrb_fused(DV v, FP fp, const double *__
         if constexpr (RR) {
             const int jr = r - 2 * K - 1;
             if (own && jr >= jA && jr < jB && jr >= 0 && jr < v.ny) {    // (rank strips: halo rows are advanced, not restricted)
-                const RowCoef<MASKED, ZBU> &q = (K >= 2) ? cf5 : cf3;
+                const RowCoef<MASKED, ZBU, YR> &q = (K >= 2) ? cf5 : cf3;
                 const int s0 = ring(sr - (2 * K + 1)), sN = ring(sr - 2 * K), sS = ring(sr - (2 * K + 2));
                 const double *row = lds + s0 * LW;
                 double acc = (jr & 1) ? racc : 0.0, accp = (jr & 1) ? raccp : 0.0;
@@ -764,12 +782,13 @@ __global__ __launch_bounds__(NT) void k_gsrb_fused(DV v, FP fp, const double *__
         // ---- 4. row r+1 enters the ring (its slot held row r-2K-2: no longer read), rotate
         sr = sr + 1 == R ? 0 : sr + 1;
         if (in_row) { lds[sr * LW + xl] = pnext.x; lds[sr * LW + xl + 1] = pnext.y; }
-        if constexpr (WIDE && K >= 2) copy_coef<HAS_ALPHA, MASKED, ZBU>(cf5, cf4);
-        if constexpr (K >= 2) { copy_coef<HAS_ALPHA, MASKED, ZBU>(cf4, cf3); copy_coef<HAS_ALPHA, MASKED, ZBU>(cf3, cf2); }
-        else if constexpr (RR) copy_coef<HAS_ALPHA, MASKED, ZBU>(cf3, cf2);
-        copy_coef<HAS_ALPHA, MASKED, ZBU>(cf2, cf1);
+        if constexpr (WIDE && K >= 2) copy_coef<HAS_ALPHA, MASKED, ZBU, YR>(cf5, cf4);
+        if constexpr (YR) { ys5[0] = cf4.byN[0]; ys5[1] = cf4.byN[1]; }
+        if constexpr (K >= 2) { copy_coef<HAS_ALPHA, MASKED, ZBU, YR>(cf4, cf3); copy_coef<HAS_ALPHA, MASKED, ZBU, YR>(cf3, cf2); }
+        else if constexpr (RR) copy_coef<HAS_ALPHA, MASKED, ZBU, YR>(cf3, cf2);
+        copy_coef<HAS_ALPHA, MASKED, ZBU, YR>(cf2, cf1);
         if constexpr (BCF) { CP2(cf1, cf0, B); bw1 = bw0; be1 = be0; }      // (its faces are formed in the next step, the rest is loaded then)
-        else copy_coef<HAS_ALPHA, MASKED, ZBU>(cf1, cf0);
+        else copy_coef<HAS_ALPHA, MASKED, ZBU, YR>(cf1, cf0);
     }
     if constexpr (ROUT) {
         if (g.onorm) {                         // (uniform) the chunk's max norm: a maximum, so the order of the lanes does not matter
@@ -801,6 +820,7 @@ struct RelaxStep {
     int K, NT;                   // streaming
     bool masked;                 // streaming: the ice mask is not known clean (or alpha != 0): the instantiation that reads it
     bool zbu;                    // streaming: the depth's bed elevation is known to be one value: the instantiation that takes it as a scalar
+    bool yring;                  // streaming: the plain launch of those with one ring of y-faces (three waves per SIMD; not where y is periodic)
     // what the launch absorbs: it restricts; it leaves the residual of the final phi behind; it forms the FAS right-hand side; it forms depth
     // 0's faces; it adds the prolonged correction while loading
     bool rst, rout, frhs, bcf, prolong;
@@ -810,32 +830,62 @@ struct RelaxStep {
     int RM() const { return rout ? 2 : rst ? 1 : 0; }
 };
 
-// the instantiations of k_gsrb_fused, by what they do.  slots: workgroups the chip holds at once -- of the plain rows only, whose occupancy
-// stands for the launches of their (K, NT, RM, masked) that also take alpha or form the right-hand side or the faces
+// the instantiations of k_gsrb_fused, by what they do.  wg_per_cu, slots: workgroups a CU / the chip holds at once, each instantiation's own
+// answer of the occupancy query (asked at its first launch): the chunks of a launch are cut for the kernel that runs them
 typedef void (*FusedFn)(DV, FP, const double *, double *, suhmo_phys_t, FusedGeom);
-struct FusedKernel { int key; FusedFn fn; int slots; };
-constexpr int fused_key(int K, bool alpha, int NT, int RM, bool frhs, bool masked, bool bcf, bool zbu = false)
+struct FusedKernel { int key; FusedFn fn; int slots, wg_per_cu; };
+constexpr int fused_key(int K, bool alpha, int NT, int RM, bool frhs, bool masked, bool bcf, bool zbu = false, bool yring = false)
 {
-    return K | RM << 4 | alpha << 8 | frhs << 9 | masked << 10 | bcf << 11 | NT << 12 | zbu << 24;       // (K, RM < 16; NT < 4096)
+    return K | RM << 4 | alpha << 8 | frhs << 9 | masked << 10 | bcf << 11 | NT << 12 | zbu << 24 | yring << 25;       // (K, RM < 16; NT < 4096)
 }
-#define FK(K, A, NT, RM, F, M, B) {fused_key(K, A, NT, RM, F, M, B), k_gsrb_fused<K, A, NT, RM, F, M, B>, 0}
-// the launches of the clean-mask alpha = 0 cycle at K = 2, NT = 64 with the bed as a scalar (ZBU); the plain ones have their own occupancy
-#define FK_ZBU(RM, F, B) {fused_key(2, false, 64, RM, F, false, B, true), k_gsrb_fused<2, false, 64, RM, F, false, B, true>, 0}
+#define FK(K, A, NT, RM, F, M, B) {fused_key(K, A, NT, RM, F, M, B), k_gsrb_fused<K, A, NT, RM, F, M, B>, 0, 0}
+// the launches of the clean-mask alpha = 0 cycle at K = 2, NT = 64 with the bed as a scalar (ZBU); YR: the plain one with one ring of y-faces
+#define FK_ZBU(RM, F, B, YR) {fused_key(2, false, 64, RM, F, false, B, true, YR), k_gsrb_fused<2, false, 64, RM, F, false, B, true, YR>, 0, 0}
 #define FK_PLAIN(K, NT, RM) FK(K, false, NT, RM, false, true, false), FK(K, false, NT, RM, false, false, false)
 static FusedKernel fused_kernels[] = {
     FK_PLAIN(2, 64, 0), FK_PLAIN(2, 64, 1), FK_PLAIN(2, 64, 2), FK_PLAIN(1, 64, 0), FK_PLAIN(2, 256, 0), FK_PLAIN(1, 256, 0),
     FK(1, true, 64, 0, false, true, false), FK(2, true, 64, 0, false, true, false), FK(1, true, 256, 0, false, true, false), FK(2, true, 256, 0, false, true, false),
     FK(2, false, 64, 0, true, true, false), FK(2, false, 64, 0, true, false, false), FK(2, false, 64, 0, false, false, true),
-    FK_ZBU(0, false, false), FK_ZBU(1, false, false), FK_ZBU(2, false, false), FK_ZBU(0, true, false), FK_ZBU(0, false, true),
+    FK_ZBU(0, false, false, false), FK_ZBU(1, false, false, false), FK_ZBU(2, false, false, false), FK_ZBU(0, true, false, false), FK_ZBU(0, false, true, false),
+    FK_ZBU(0, false, false, true),
 };
 #undef FK_ZBU
 #undef FK_PLAIN
 #undef FK
-static FusedKernel *fused_kernel(int K, bool alpha, int NT, int RM, bool frhs, bool masked, bool bcf, bool zbu)
+static FusedKernel *fused_kernel(int K, bool alpha, int NT, int RM, bool frhs, bool masked, bool bcf, bool zbu, bool yring = false)
 {
-    const int key = fused_key(K, alpha, NT, RM, frhs, masked, bcf, zbu);
+    const int key = fused_key(K, alpha, NT, RM, frhs, masked, bcf, zbu, yring);
     for (FusedKernel &k : fused_kernels) if (k.key == key) return &k;
     return nullptr;
+}
+// the occupancy of an instantiation, asked once
+static int fused_occupancy(FusedKernel *k, int NT)
+{
+    if (k->slots) return 0;
+    int nb = 0, ncu = 0, dev = 0;
+    HIPCHK(hipGetDevice(&dev));
+    HIPCHK(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev));
+    HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k->fn, NT, 0));
+    k->wg_per_cu = nb > 0 ? nb : 1;
+    k->slots = k->wg_per_cu * (ncu > 0 ? ncu : 256);
+    return 0;
+}
+// read-only options stream_wg_per_cu_<which> (suhmo_level.hip): workgroups per CU of the two-sweep one-wave launches of the clean-mask
+// alpha = 0 cycle with the bed as a scalar -- plain, yring, rst, rout, frhs, bcf.  1: no such name
+int suhmo_gsrb_stream_wg_per_cu(const char *which, long *value)
+{
+    static const struct { const char *name; int RM; bool frhs, bcf, yring; } tab[] = {
+        {"plain", 0, false, false, false}, {"yring", 0, false, false, true}, {"rst", 1, false, false, false}, {"rout", 2, false, false, false},
+        {"frhs", 0, true, false, false}, {"bcf", 0, false, true, false}};
+    for (const auto &e : tab) {
+        if (strcmp(which, e.name)) continue;
+        FusedKernel *k = fused_kernel(2, false, 64, e.RM, e.frhs, false, e.bcf, true, e.yring);
+        if (!k) { suhmo_set_error("internal: no streaming kernel '%s'", which); return -4; }
+        int rc = fused_occupancy(k, 64); if (rc) return rc;
+        *value = k->wg_per_cu;
+        return 0;
+    }
+    return 1;
 }
 
 // part 0: the whole level.  Rank strips with the exchange in flight: part 1 = the chunks that read no halo row (returns 1 and
@@ -847,9 +897,8 @@ static int launch_fused(suhmo_level *L, int depth, const RelaxStep &s, hipStream
     Depth &D = L->d[depth];
     const DV &v = D.v;
     // the one check that relax_step handed over a launch that exists: alpha with no variant, the variants whole (no part) and one at a time
-    FusedKernel *k = fused_kernel(K, v.alpha != 0.0, NT, RM, s.frhs, s.masked, s.bcf, s.zbu);
-    FusedKernel *plain = (v.alpha != 0.0 || s.frhs || s.bcf) ? fused_kernel(K, false, NT, RM, false, s.masked, false, s.zbu) : k;   // (whose occupancy it has)
-    if (!k || !plain || (part && (s.frhs || s.bcf)) || (s.bcf && s.prolong)) { suhmo_set_error("internal: a streaming relaxation step without a kernel"); return -4; }
+    FusedKernel *k = fused_kernel(K, v.alpha != 0.0, NT, RM, s.frhs, s.masked, s.bcf, s.zbu, s.yring);
+    if (!k || (part && (s.frhs || s.bcf)) || (s.bcf && s.prolong)) { suhmo_set_error("internal: a streaming relaxation step without a kernel"); return -4; }
     if (!D.phi_alt) {
         HIPCHK(hipMalloc(&D.phi_alt, D.elems * sizeof(double)));
         HIPCHK(hipMemsetAsync(D.phi_alt, 0, D.elems * sizeof(double), st));
@@ -866,22 +915,23 @@ static int launch_fused(suhmo_level *L, int depth, const RelaxStep &s, hipStream
     // a partial second round costs a full one), but never shorter than 16K rows so that the
     // 4K-row pipeline fill stays small; measured on MI355X: profiles/r01_b_hc_sweep.log
     {
-        if (!plain->slots) {                                      // per (K, NT, RM) instantiation, with / without the mask and the bed: its own occupancy
-            int nb = 0, ncu = 0, dev = 0;
-            HIPCHK(hipGetDevice(&dev));
-            HIPCHK(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev));
-            HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, plain->fn, NT, 0));
-            plain->slots = (nb > 0 ? nb : 1) * (ncu > 0 ? ncu : 256);
-        }
+        { int rc = fused_occupancy(k, NT); if (rc) return rc; }   // of the kernel that is launched: the plain one with one ring of y-faces holds 12 per CU, the others 8
         g.jbeg = v.ext[0] ? -ext_rows : 0;
         g.jend = v.ny + (v.ext[1] ? ext_rows : 0);
         const int nrows = g.jend - g.jbeg;
-        int nch = plain->slots / g.nstrips;
+        // The launch with one ring of y-faces (12 workgroups per CU) is cut for 15/16 of its slots and may go down to 6K rows: a round filled
+        // to the last slot is slower than one that leaves a few free, and its shorter chunks still pay (MI355X, us per launch, the parent's
+        // launch 266.1 at 71 rows and 80.6 at 19, profiles/r27_yface_ring_hc_sweep.txt):
+        //   4096^2, 35 strips: 47 rows (two rounds) 314.9, 48 (3010 of 3072 slots) 268.7, 49 247.1, 50 252.9, 51 251.7, 52 248.6, 55 254.2, 60 257.4, 71 258.4
+        //   2048^2, 18 strips: 12 rows (two rounds) 94.0, 13 74.4, 15 78.5, 16 82.0, 19 82.9
+        // 15/16 of 3072 slots: 50 rows and 13 rows.
+        const int slots = s.yring ? k->slots - k->slots / 16 : k->slots, floorK = s.yring ? 6 : 8;
+        int nch = slots / g.nstrips;
         if (nch < 1) nch = 1;
         g.Hc = (nrows + nch - 1) / nch;
         // (not shorter than 8K rows: the 4K-row pipeline fill.  The one-round height itself is the optimum where it is allowed: 2048^2,
         //  19 rows: 45.1 us per sweep, 24 rows 51.4, 32 rows -- two rounds, the old lower bound -- 60.3, profiles/r03_stream2048.txt)
-        if (g.Hc < 8 * K) g.Hc = 8 * K;
+        if (g.Hc < floorK * K) g.Hc = floorK * K;
         // cache-resident depths (about 1 M cells) are latency-bound: many short chunks beat few long ones
         // (profiles/r01_k_sweep_small_hc.log: 1024^2, K = 2: 22.3 us per sweep at 6 rows vs 28.1 for the colour passes)
         if ((long)v.nx * v.ny < 2000000L) g.Hc = 6;
@@ -946,6 +996,7 @@ static int launch_fused(suhmo_level *L, int depth, const RelaxStep &s, hipStream
     hipLaunchKernelGGL(k->fn, dim3(g.ntiles), dim3(NT), 0, st, v, D.fp, pin, D.phi_alt, L->ph, g);
     if (unmasked) L->relax_unmasked++;
     if (s.zbu) L->relax_zb_uniform[depth]++;
+    if (s.yring) L->relax_yring[depth]++;
     if (part != 1) { std::swap(D.fp.f[SUHMO_F_PHI], D.phi_alt); suhmo_fp_changed(); }
     return 0;
 }
@@ -1520,6 +1571,9 @@ static RelaxStep relax_step(const suhmo_level *L, int depth, int left, int tail,
     s.frhs = (absorb & ABSORB_RHS) && plain;
     // depth 0 of a whole level -- no rank strip, no AMR patch -- with a mask known clean, and nothing else to absorb
     s.bcf = absorb == ABSORB_BCOEF && plain && depth == 0 && !stored && !s.masked;
+    // the plain launch with the bed as a scalar that absorbs nothing but a prolongation: one ring of y-faces.  Not where y is periodic: face 0
+    // and face ny are two canvas rows of by there, whose bits may differ (a ghost row of B that is not the periodic image)
+    s.yring = L->yface_ring && s.zbu && plain && !s.frhs && !s.bcf && !v.per[1];
     // (the launch that forms the right-hand side loads, and keeps, all halo rows)
     s.adv = ext ? plan_halo_advance(F, s.need, (absorb & ABSORB_RHS) ? F : 2 * (left - K) + tail, v.gy - s.need, s.rst) : 0;
     return s;

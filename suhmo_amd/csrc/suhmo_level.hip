@@ -183,6 +183,7 @@ int suhmo_level_create_(suhmo_level_t **out, const suhmo_level_desc_t *desc, boo
     L->graph_max_cells = 1500000; L->gstream = nullptr; L->vgraph_replays = 0; memset(L->vgraph_seen, 0, sizeof(L->vgraph_seen));
     L->fused_min_cells = 1000000;
     L->skip_mask = 1; L->mask_known = 1; L->poll_readback = 1; L->zb_known = 1;
+    L->yface_ring = 1; memset(L->relax_yring, 0, sizeof(L->relax_yring));
     L->bottom_solver = 0; L->bottom_one_launch_max_cells = 16384;    // (every bottom the one-launch kernel's LDS holds: up to 128 x 128)
     L->bottom_ctr = nullptr; L->bottom_host_iters = L->bottom_host_solves = 0;
     // ... and ONE place where the environment may override them, read when a level is created: the A/B runs DESIGN.md quotes and the tests that
@@ -198,7 +199,7 @@ int suhmo_level_create_(suhmo_level_t **out, const suhmo_level_desc_t *desc, boo
             {"SUHMO_TILE_RESTRICT", &suhmo_level::tile_restrict}, {"SUHMO_TILE_ORDER", &suhmo_level::tile_order}, {"SUHMO_FAS_RHS_IN_RELAX", &suhmo_level::fas_rhs_in_relax},
             {"SUHMO_TILE_S", &suhmo_level::tile_s}, {"SUHMO_GSRB_TILE", &suhmo_level::gsrb_tile}, {"SUHMO_TILE_T", &suhmo_level::tile_t},
             {"SUHMO_FUSED_RESTRICT", &suhmo_level::fused_restrict}, {"SUHMO_SKIP_MASK", &suhmo_level::skip_mask}, {"SUHMO_MASK_KNOWN", &suhmo_level::mask_known}, {"SUHMO_ZB_KNOWN", &suhmo_level::zb_known},
-            {"SUHMO_POLL_READBACK", &suhmo_level::poll_readback}, {"SUHMO_AVG_OVERLAP", &suhmo_level::avg_overlap}};
+            {"SUHMO_POLL_READBACK", &suhmo_level::poll_readback}, {"SUHMO_AVG_OVERLAP", &suhmo_level::avg_overlap}, {"SUHMO_YFACE_RING", &suhmo_level::yface_ring}};
         static const LongKnob longs[] = {
             {"SUHMO_AGG_MIN_CELLS", &suhmo_level::agg_min_cells}, {"SUHMO_TILE_MAX_CELLS", &suhmo_level::tile_max_cells},
             {"SUHMO_GRAPH_MAX_CELLS", &suhmo_level::graph_max_cells}, {"SUHMO_FUSED_MIN_CELLS", &suhmo_level::fused_min_cells},
@@ -416,7 +417,7 @@ static int *option_slot_int(suhmo_level *L, const char *key)
         {"tile_strips", &suhmo_level::tile_strips}, {"overlap_halo", &suhmo_level::overlap_halo}, {"skip_mask", &suhmo_level::skip_mask}, {"mask_known", &suhmo_level::mask_known}, {"zb_known", &suhmo_level::zb_known}, {"tile_chunks",
             &suhmo_level::tile_chunks}, {"tile_order", &suhmo_level::tile_order}, {"tile_restrict", &suhmo_level::tile_restrict}, {"fas_rhs_in_relax",
             &suhmo_level::fas_rhs_in_relax}, {"resid_in_relax", &suhmo_level::resid_in_relax}, {"bcoef_in_relax", &suhmo_level::bcoef_in_relax}, {"fas_rhs_fused", &suhmo_level::fas_rhs_fused},
-        {"avg_overlap", &suhmo_level::avg_overlap}, {"tile_s", &suhmo_level::tile_s}, {"gsrb_tile", &suhmo_level::gsrb_tile}, {"tile_t", &suhmo_level::tile_t}, {"poll_readback", &suhmo_level::poll_readback}};
+        {"avg_overlap", &suhmo_level::avg_overlap}, {"yface_ring", &suhmo_level::yface_ring}, {"tile_s", &suhmo_level::tile_s}, {"gsrb_tile", &suhmo_level::gsrb_tile}, {"tile_t", &suhmo_level::tile_t}, {"poll_readback", &suhmo_level::poll_readback}};
     for (const auto &e : tab) if (!strcmp(key, e.k)) return &(L->*(e.m));
     return nullptr;
 }
@@ -478,19 +479,24 @@ extern "C" int suhmo_level_get_option(const suhmo_level_t *L, const char *key, l
     {   // read-only (zb_known): the scans so far; per depth ("..._d<depth>", without the suffix: depth 0's state, all depths' launches) what is
         // known about the bed -- 0 unknown, 1 uniform, 2 varying, as of the last V-cycle -- and the streaming launches that took it as a scalar
         if (!strcmp(key, "zb_scans")) { *value = L->zb_scans; return 0; }
-        const bool st = !strncmp(key, "zb_state", 8), nl = !strncmp(key, "relax_zb_uniform_launches", 25);
-        const char *rest = st ? key + 8 : nl ? key + 25 : nullptr;
+        // (yface_ring: relax_yring_launches, the plain ones of those that kept one ring of y-faces)
+        const bool st = !strncmp(key, "zb_state", 8), nl = !strncmp(key, "relax_zb_uniform_launches", 25), yr = !strncmp(key, "relax_yring_launches", 20);
+        const char *rest = st ? key + 8 : nl ? key + 25 : yr ? key + 20 : nullptr;
         if (rest && !*rest) {
             *value = st ? L->d[0].zb_state : 0;
-            for (int d = 0; nl && d < L->ndepth; d++) *value += L->relax_zb_uniform[d];
+            for (int d = 0; (nl || yr) && d < L->ndepth; d++) *value += yr ? L->relax_yring[d] : L->relax_zb_uniform[d];
             return 0;
         }
         if (rest && rest[0] == '_' && rest[1] == 'd' && rest[2] >= '0' && rest[2] <= '9') {
             const int d = atoi(rest + 2);
             if (d >= L->ndepth) { suhmo_set_error("option '%s': the level has %d depths", key, L->ndepth); return -1; }
-            *value = st ? L->d[d].zb_state : L->relax_zb_uniform[d];
+            *value = st ? L->d[d].zb_state : yr ? L->relax_yring[d] : L->relax_zb_uniform[d];
             return 0;
         }
+    }
+    if (!strncmp(key, "stream_wg_per_cu_", 17)) {       // read-only: what the occupancy query answers for a streaming instantiation (suhmo_gsrb.hip)
+        const int rc = suhmo_gsrb_stream_wg_per_cu(key + 17, value);
+        if (rc <= 0) return rc;
     }
     if (!strcmp(key, "vcycle_graph_replays")) { *value = L->vgraph_replays; return 0; }   // read-only counter (graph_max_cells)
     if (!strcmp(key, "bottom_solver")) { *value = L->bottom_solver; return 0; }
