@@ -1113,6 +1113,84 @@ int suhmo_hier_run_bud(suhmo_hier_t **H, const suhmo_model_params_t *mp, const s
 int suhmo_batch_run_bud(suhmo_batch_t *B, const suhmo_model_params_t *mp, const suhmo_batch_schedule_t *sch, const int *active,
                         suhmo_run_budget_t *bud, suhmo_batch_run_result_t *res, suhmo_stream_t s);
 
+/* ---- INITIAL CONDITIONS (suhmo_amd/csrc/suhmo_ibc.hip, suhmo_ibc.h; tests/ibc_ref.py is the numpy twin of this text): the
+ * reference's four IBC classes, selected by problem_type in exec/<case>/Suhmo.cpp, evaluated on the device -- the first state of a model
+ * (initializeData + setup_iceMask, AmrHydro::initData :5100-5147) and what AmrHydro::regrid evaluates anew on every new level
+ * (initializeBed, the 10-argument initializePi, setup_iceMask with the ghost fills around them, :4387-4437).
+ *   SUHMO_IBC_BASIC   HydroIBC          SUHMO_IBC_SQRT   SqrtIBC (SHMIP A, B, F)
+ *   SUHMO_IBC_VALLEY  ValleyIBC (E)     SUHMO_IBC_DINO   MountainIBC (AMR_multiMoulins)
+ * suhmo_ibc_t holds the kind, the suhmo_params values the formulas read (slope = m_slope, ice_height = m_H, gap_init = m_gapInit, rho_i, rho_w,
+ * gravity, G, L) and ValleyIBC's gamma.  Fact = 1 / (rho_w * gravity) below.
+ * CELLS.  Every body runs over the box WITH its ghost ring, i = -1 .. nx, j = -1 .. ny, cell (i, j) of a box whose first cell is (i0, j0) of its
+ * level: gi = i0 + i, gj = j0 + j; a (gi, gj) that lies beyond a PERIODIC side of the level's domain is first wrapped into it (so every
+ * written field holds the periodic image there, what Chombo's exchange leaves); x = (gi + 0.5) * dx, y = (gj + 0.5) * dy, and y = (gj + 0.5) * dy
+ * - 750 for the valley.  Every expression is evaluated left to right as written, one rounding per operation, no contraction; max(a, b) and
+ * min(a, b) are std::max / std::min, a < b ? b : a and b < a ? b : a: a NaN in a (sqrt's ghost cells left of x = -ice_height) comes back.
+ * CONSTANTS formed once on the host with the C library and passed by value: P = pow(2.0e10, 0.25); H6 = 100 * pow(6200, 0.25) + 6000 / 60 - P + 1;
+ * cos and sin of a * 3.14159 / 180 for the dino's angles a = 35, 90, 60, 2.  On the device run only sqrt (correctly rounded), the valley's
+ * pow(x + 200, 0.25) and the dino's exp: those two kinds are NOT bit for bit the host's where they enter.
+ * INITIAL STATE (initializeData), per kind -- zb = SUHMO_F_ZB, zs = SUHMO_F_ZS (m_iceheight), Pi = SUHMO_F_PI, b = SUHMO_F_B, Pw = SUHMO_F_PW, h = SUHMO_F_PHI:
+ *   basic   zb = slope * x; b = gap_init; zs = ice_height; Pi = rho_i * gravity * zs; Pw = Pi * 0.5; h = Pw * Fact + zb.
+ *   sqrt    zb = slope * x; zs = max(6 * (sqrt(x + ice_height) - sqrt(ice_height)) + 1, 0); Pi = max(rho_i * gravity * zs, 0);
+ *           b = 1e-16 where Pi < 2, else gap_init; Pw = 101325; h = Pw * Fact + zb.
+ *   valley  S = 100 * pow(x + 200, 0.25) + x / 60 - P + 1; f(g) = (H6 - 6000 * g) * x * x / (6000 * 6000) + g * x; fx = f(gamma), fb = f(0.05);
+ *           gy = 0.5e-6 * |y * y * y|; hx = (-4.5 * x / 6000 + 5) * (S - fx) / (S - fb + 1e-16); zb = fx + gy * hx;
+ *           Pi = rho_i * gravity * max(S - zb, 0); b = 1e-16 where Pi < 1e-10, else gap_init; zs = max(S - zb, 0) (the CORRECTED ice height);
+ *           Pw = Pi * 0.5; h = Pw * Fact + zb, then 0 where h < 0 (resetCovered).
+ *   dino    t = 1.5e-3 * x + -1.5e-3 * y + 100; zs = 2 * (t + 100); finger(a, x0, y0, A, sg, sigma): xb = x - x0, yb = y - y0, xt = xb * cos + yb * sin,
+ *           yt = -xb * sin + yb * cos, Ag = A * exp(-0.5 / (sg * sg) * yt * yt), value Ag * exp(-0.5 / (sigma * sigma) * xt * xt); the four fingers
+ *           (35, 1e5, 0, 250, 5e4, sigma = 12000 - 3000 * min(1 - (50000 - yt) / 50000, 1)), (90, 85000, 0, 250, 3e4, 1e4), (60, 55000, 0, 100, 2e4, 5000),
+ *           (2, 1e5, 2e4, 300, 35000, 6000); zb = max(max(t, 0) + f2 + f3 + f4 + f5, 0) -- WITHOUT the reference's bed noise (an unseeded
+ *           std::default_random_engine drawn in box order, :174, :270: not reproducible); Pi = rho_i * gravity * max(zs, 0); b = 1e-16 where
+ *           Pi == 0, else gap_init; Pw = Pi * 0.5; h = Pw * Fact + zb, then 0 where h < 0.
+ *   all     SUHMO_F_MR = G / L; SUHMO_F_ACOEF = 0; SUHMO_F_MASK = 1 where Pi > 0, else -1 (setup_iceMask).  Re, qw ("dummy stuff -- will be erased
+ *           right away"), the sliding speed and the bump fields (scalars of the model here) are not written; the AGU_test_case branches are not built.
+ * RELOAD BODY (initializeBed + initializePi), what each class writes there and nothing else:
+ *   basic, sqrt   zb = slope * x.        valley   zs = S (UNcorrected), zb, Pi as above.
+ *   dino          zs, Pi as above, b = 1e-16 where Pi == 0 (else b stays); its bed is what the transfer brought.
+ * MASK BODY (setup_iceMask): SUHMO_F_MASK = 1 where the stored Pi > 0, else -1, ghost ring included.
+ * One __global__ template per body over the launch targets (a level, the boxes of a level, the members of an ensemble); 64 x 4 threads over
+ * (nx + 2) x (ny + 2); plain vector stores.
+ *
+ * suhmo_level_ibc_init(L, ibc, s)    the initial state and the mask of one whole level in ONE launch, then CopyGhostCells (ghost = the cell next to it,
+ *     side cells only) of SUHMO_F_ZB and SUHMO_F_MASK across the non-periodic domain sides (initData, :5133-5147).  A whole level is one created with
+ *     j0 = 0, ny = ny_global and nx_global = 0 (or i0 = 0, nx_global = nx, as a hierarchy's base may be written).  A rank strip, a patch of a
+ *     nested hierarchy (suhmo_amr_*) or a box of a hierarchy -- anything else: rc -5.
+ * suhmo_hier_ibc_init(H, ibc, s)     the same on every level: one launch for level 0 and one per refined level (read-only option ibc_launches counts
+ *     the launches of the bodies), CopyGhostCells of ZB and MASK on every level; then for l = 1, 2, ... in order the MASK of level l:
+ *     PiecewiseLinearFillPatch of its coarse-fine ghost cells from level l - 1 (suhmo_hier_pwl_fill), exchange with corners (suhmo_hier_exchange),
+ *     CopyGhostCells.  rc -5: rank strips, levels dealt to the ranks, shadow = 1.
+ * suhmo_batch_ibc_init(B, ibcs, active, s)   suhmo_level_ibc_init on every member whose flag in active[n] is not 0 (NULL: all) in ONE launch + the two
+ *     ghost launches; ibcs[n_members], a device row per member: the kinds of the active members must be equal (rc -1), every other value is the member's.
+ *     The rows are uploaded for the call and freed at its end: the call SYNCHRONISES the stream (an initialisation call; batch_launches grows by the
+ *     launches made, 3).
+ * suhmo_hier_set_ibc(H, ibc)         keeps *ibc on the handle (NULL: none); suhmo_hier_regrid hands it to the new handle with the options.
+ * suhmo_hier_ibc_reload(H, level, s) level >= 1, :4387-4437: (1) the reload body on every box of the level, one launch; (2) for each field it wrote among
+ *     ZB, PI, ZS, in this order: suhmo_hier_pwl_fill from level - 1, suhmo_hier_exchange with corners, then CopyGhostCells (ZB) or
+ *     ExtrapGhostCells (PI, ZS; ghost = 2 x the cell next to it - the one behind); (3) the mask body, one launch; (4) pwl fill, exchange,
+ *     CopyGhostCells of MASK.  A field the body did not write keeps what the transfer left (the dino's b is written inside valid and ghost cells
+ *     alike and gets no fill).  Needs suhmo_hier_set_ibc; ibc_launches grows by 2.
+ * suhmo_hier_regrid with an IBC on H: after steps a - e of the new level l, suhmo_hier_ibc_reload(new handle, l) -- INSIDE the ascending loop, so that
+ *     level l + 1 interpolates from the reloaded level l, as the reference's loop does.  Without an IBC nothing changes.
+ * suhmo_hier_run with an IBC on *H: `reload` may be NULL; one that is given still runs, after the device reload.  For THE SURFACE HEIGHT ACROSS A
+ *     REGRID valley and dino bring SUHMO_F_ZS to every new box, basic and sqrt do not.
+ * Every call counts as a write of the fields it touches, as suhmo_level_set_field does: what the level knows about its ice mask and bed, the halo
+ * state of its head, and the hierarchy's ghost / residual bookkeeping start over.
+ * Checked before anything is launched, rc -1 and a message: a NULL handle or struct, an unknown kind, gap_init <= 0, a level outside
+ * 1 .. nlev - 1 for the reload, a reload without an IBC on the handle.
+ * Not built: the bed noise, AGU_test_case, an IBC that reads files, bump fields as arrays, rank strips. */
+enum { SUHMO_IBC_BASIC = 0, SUHMO_IBC_SQRT = 1, SUHMO_IBC_VALLEY = 2, SUHMO_IBC_DINO = 3 };
+typedef struct suhmo_ibc {
+    int kind;
+    double slope, ice_height, gap_init, rho_i, rho_w, gravity, G, L;
+    double gamma;      /* valley */
+} suhmo_ibc_t;
+int suhmo_level_ibc_init(suhmo_level_t *L, const suhmo_ibc_t *ibc, suhmo_stream_t s);
+int suhmo_hier_ibc_init(suhmo_hier_t *H, const suhmo_ibc_t *ibc, suhmo_stream_t s);
+int suhmo_batch_ibc_init(suhmo_batch_t *B, const suhmo_ibc_t *ibcs, const int *active, suhmo_stream_t s);
+int suhmo_hier_set_ibc(suhmo_hier_t *H, const suhmo_ibc_t *ibc);
+int suhmo_hier_ibc_reload(suhmo_hier_t *H, int level, suhmo_stream_t s);
+
 /* Named timers with the reference's CH_TIME labels (src/VCAMRNonLinearPoissonOp.cpp:40,69,103,277,390,660; CH_TIMER_REPORT at
  * exec/A_SHMIP/Suhmo.cpp:136).  mode 0 off (default; env SUHMO_TIMERS), 1 host wall time per scope, 2 with the device synchronised at
  * both ends of a scope (the time of the kernels it launched; serialises, for profiling only).  suhmo_timers_report writes

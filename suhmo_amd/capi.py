@@ -81,6 +81,16 @@ class TagSpec(C.Structure):
                 ("min_level", C.c_int), ("cap_level", C.c_int)]
 
 
+IBC_BASIC, IBC_SQRT, IBC_VALLEY, IBC_DINO = 0, 1, 2, 3          # SUHMO_IBC_*: the reference's problem_type basic / sqrt / valley / dino
+IBC_KINDS = dict(basic=IBC_BASIC, sqrt=IBC_SQRT, valley=IBC_VALLEY, dino=IBC_DINO)
+
+
+class Ibc(C.Structure):
+    """suhmo_ibc_t: an IBC class of the reference and the values its formulas read (include/suhmo_hip.h, "INITIAL CONDITIONS")"""
+    _fields_ = [("kind", C.c_int), ("slope", C.c_double), ("ice_height", C.c_double), ("gap_init", C.c_double), ("rho_i", C.c_double),
+                ("rho_w", C.c_double), ("gravity", C.c_double), ("G", C.c_double), ("L", C.c_double), ("gamma", C.c_double)]
+
+
 RELOAD_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int)      # user, the new hierarchy, index of the regrid, cur_step
 
 
@@ -192,6 +202,7 @@ SYMBOLS = [
     "suhmo_hier_compare",
     "suhmo_level_mass_balance", "suhmo_hier_mass_balance", "suhmo_batch_mass_balance",
     "suhmo_level_water_budget", "suhmo_hier_water_budget", "suhmo_batch_water_budget", "suhmo_hier_run_bud", "suhmo_batch_run_bud",
+    "suhmo_level_ibc_init", "suhmo_hier_ibc_init", "suhmo_batch_ibc_init", "suhmo_hier_set_ibc", "suhmo_hier_ibc_reload",
 ]
 # the seven values of a mass balance in the order of the enum SUHMO_MB_* (include/suhmo_hip.h, "MASS BALANCE")
 MB_NAMES = ("lo_x", "hi_x", "lo_y", "hi_y", "dir_x", "dir_y", "volume")
@@ -379,6 +390,11 @@ def lib():
     L.suhmo_hier_run_bud.argtypes = [C.POINTER(vp), C.POINTER(ModelParams), C.POINTER(HierSchedule), C.POINTER(HierOutput), C.POINTER(RunBudget),
                                      C.POINTER(HierRunResult), vp]
     L.suhmo_batch_run_bud.argtypes = [vp, C.POINTER(ModelParams), C.POINTER(BatchSchedule), ip, C.POINTER(RunBudget), C.POINTER(BatchRunResult), vp]
+    L.suhmo_level_ibc_init.argtypes = [vp, C.POINTER(Ibc), vp]
+    L.suhmo_hier_ibc_init.argtypes = [vp, C.POINTER(Ibc), vp]
+    L.suhmo_batch_ibc_init.argtypes = [vp, C.POINTER(Ibc), ip, vp]
+    L.suhmo_hier_set_ibc.argtypes = [vp, C.POINTER(Ibc)]
+    L.suhmo_hier_ibc_reload.argtypes = [vp, ci, vp]
     _LIB = L
     return L
 

@@ -17,6 +17,7 @@
 // solve loop.  Its beta = dt x diffFactor is the member's own (the kernels read it from the member's row).
 #include "suhmo_batch.h"
 #include "suhmo_relax_plan.h"
+#include "suhmo_ibc.h"
 #include <algorithm>
 #include <new>
 
@@ -609,6 +610,49 @@ extern "C" int suhmo_batch_time_varying_recharge(suhmo_batch_t *B, const double 
     if ((rc = launch_time_varying_recharge(on(B, 0, sel), tk, bg, st))) return rc;
     B->launches++;
     return 0;
+}
+// suhmo_level_ibc_init of the flagged members in one launch (+ the two CopyGhostCells launches): include/suhmo_hip.h, "INITIAL CONDITIONS".  The
+// members' parameter rows live on the device for the length of the call
+extern "C" int suhmo_batch_ibc_init(suhmo_batch_t *B, const suhmo_ibc_t *ibcs, const int *active, suhmo_stream_t s)
+{
+    if (!B) { suhmo_set_error("suhmo_batch_ibc_init: no batch"); return -1; }
+    if (!ibcs) { suhmo_set_error("suhmo_batch_ibc_init: no suhmo_ibc_t given"); return -1; }
+    hipStream_t st = (hipStream_t)s;
+    const BatchSel sel = flagged_members(B, active);
+    if (!sel.n) return 0;
+    int rc;
+    for (int z = 0; z < sel.n; z++) {
+        if ((rc = suhmo_ibc_check_(&ibcs[sel.m[z]], "suhmo_batch_ibc_init"))) return rc;
+        if (ibcs[sel.m[z]].kind != ibcs[sel.m[0]].kind) {
+            suhmo_set_error("suhmo_batch_ibc_init: member %d has kind %d, member %d kind %d: the members of one call share the kind", sel.m[z], ibcs[sel.m[z]].kind,
+                            sel.m[0], ibcs[sel.m[0]].kind);
+            return -1;
+        }
+    }
+    HIPCHK(hipSetDevice(B->device));
+    static const int fields[] = {SUHMO_F_ZB, SUHMO_F_ZS, SUHMO_F_PI, SUHMO_F_B, SUHMO_F_PW, SUHMO_F_PHI, SUHMO_F_MR, SUHMO_F_ACOEF, SUHMO_F_MASK};
+    for (int z = 0; z < sel.n; z++)
+        for (int f : fields)
+            if (!suhmo_field(B->mem[sel.m[z]], 0, f)) { suhmo_set_error("batch: field allocation failed (member %d)", sel.m[z]); return -2; }
+    if ((rc = batch_enter(B, st))) return rc;
+    std::vector<IbcRow> rows(B->n);
+    for (int z = 0; z < sel.n; z++) rows[sel.m[z]] = ibc_row(ibcs[sel.m[z]]);
+    IbcRow *d_rows = nullptr;
+    HIPCHK(hipMalloc(&d_rows, rows.size() * sizeof(IbcRow)));
+    hipError_t e = hipMemcpy(d_rows, rows.data(), rows.size() * sizeof(IbcRow), hipMemcpyHostToDevice);
+    if (e == hipSuccess) {
+        int launched = 0;
+        rc = launch_ibc_init(on(B, 0, sel), d_rows, st, &launched);
+        B->launches += launched;
+        e = hipStreamSynchronize(st);                        // (the rows are read by the launch in flight)
+    }
+    (void)hipFree(d_rows);
+    if (e != hipSuccess) { suhmo_set_error("suhmo_batch_ibc_init: %s", hipGetErrorString(e)); return -2; }
+    for (int z = 0; z < sel.n && !rc; z++) {
+        suhmo_level *L = B->mem[sel.m[z]];
+        L->d[0].phi_fresh = 0; suhmo_mask_written(L); suhmo_zb_written(L);
+    }
+    return rc;
 }
 // member k's moulins are entries off[k] .. off[k] + n_moulins[k] - 1 of the concatenated arrays, off[k] = the entries of the members before it
 // (a member without a flag may give 0, or a list that is skipped).  The checks of every flagged member; *nmax: the longest list

@@ -593,6 +593,7 @@ extern "C" int suhmo_hier_get_option(const suhmo_hier_t *H, const char *key, lon
             && (rc = suhmo_hier_get_option(H->gap, key, &g)) == 0) *value += g;
         return rc;
     }
+    if (!strcmp(key, "ibc_launches")) { *value = H->n_ibc_launches; return 0; }
     if (!strcmp(key, "fused_relax_launches")) { *value = H->n_fused_relax + (H->gap ? H->gap->n_fused_relax : 0); return 0; }
     if (!strcmp(key, "gap_num_boxes")) {                  // boxes of the levels >= 1 of the gap-height hierarchy of the implicit step; -1: there is none (yet)
         *value = -1;

@@ -215,6 +215,10 @@ struct suhmo_hier {
     double *vol_buf = nullptr, *wb_buf = nullptr; size_t vol_cap = 0, wb_cap = 0;
     size_t vol_off[8] = {}; int vol_n[8] = {};
     long n_wb_launches = 0, n_wb_copies = 0;
+    // suhmo_ibc.hip, "INITIAL CONDITIONS": the IBC suhmo_hier_set_ibc left on the handle (suhmo_hier_regrid reloads every new level with it and hands it
+    // to the new handle) and the launches of the IBC bodies so far (read-only option ibc_launches; a regrid carries it over)
+    bool has_ibc = false; suhmo_ibc_t ibc{};
+    long n_ibc_launches = 0;
     long flat_fail_slot = -1;                              // option flatten_fail_slot (tests): the allocation of this scratch slot on the finest level fails
     double *red_all = nullptr;                             // partial maxima of a norm over all levels of boxes (64 per box + 16)
     struct suhmo_tagmap *tags[8] = {};                     // tag maps of suhmo_hier_tag_cells, one per level (suhmo_tags.hip), owned

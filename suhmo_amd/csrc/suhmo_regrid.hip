@@ -8,11 +8,14 @@
 //   (c) k_regrid_copy     valid cells an old box of level l holds <- the old values, over the plan "old box x new box" (after (a): the copy wins)
 //   (d) hier_ff           exchange between the new boxes, corners included
 //   (e) domain ghost cells across a non-periodic side: CopyGhostCells / ExtrapGhostCells, the launches the time step uses
+// With an IBC on the old handle (suhmo_hier_set_ibc) the level is then reloaded -- initializeBed / initializePi / setup_iceMask and their ghost fills,
+// suhmo_ibc.hip -- before level l + 1 reads it (:4387-4437 sit inside the reference's loop over the levels).
 // The two plans are lists of RECTANGLES (a few dozen bytes per pair of boxes that intersect), built on the host from the two box lists, uploaded, used
 // once and freed.  A coarse neighbour that sits in another box of level l-1 or across a periodic side is read from the coarse box's own ghost
 // ring, which step (d) of level l-1 has just made current with corners; level 0 is one canvas, where the wrapped neighbour is addressed directly.
 #include "suhmo_hier_int.h"
 #include "suhmo_transfer.h"
+#include "suhmo_ibc.h"
 
 using namespace hier;
 namespace {
@@ -208,7 +211,12 @@ extern "C" int suhmo_hier_regrid(suhmo_hier_t *O, int nlev, const int *nbox, con
     if (!rc) {
         SUHMO_TIME("regrid: transfer plans and launches");
         N->ag = O->ag; N->ag_user = O->ag_user;
-        for (int l = 1; l < N->nlev && !rc; l++) if (fl.n) rc = transfer_level(O, N, l, fl, HST(s));
+        N->has_ibc = O->has_ibc; N->ibc = O->ibc; N->n_ibc_launches = O->n_ibc_launches;
+        for (int l = 1; l < N->nlev && !rc; l++) {
+            if (fl.n) rc = transfer_level(O, N, l, fl, HST(s));
+            // initializeBed / initializePi / setup_iceMask of the new level (src/AmrHydro.cpp:4387-4437), before level l + 1 interpolates from it
+            if (!rc && N->has_ibc) rc = suhmo_hier_ibc_reload_(N, l, HST(s));
+        }
     }
     if (rc) {
         // the old hierarchy stays as it was.  The one thing creation writes into the base level is SUHMO_F_COVER (geometry): marked again for the old boxes

@@ -91,6 +91,7 @@ template <class T> struct Stepping : T {
 template <class T> static inline Stepping<T> stepping(const T &t, const suhmo_model_params_t &mp) { return Stepping<T>{t, mp}; }
 // a table a kernel needs beside the target's own: by value for a level, a device row per member of an ensemble
 template <class M> __device__ __forceinline__ const M &row_of(const OnLevel &, const M &m) { return m; }
+template <class M> __device__ __forceinline__ const M &row_of(const OnBoxes &, const M &m) { return m; }           // (one table for every box of the level)
 template <class M> __device__ __forceinline__ const M &row_of(const OnMembers &t, const M *m) { return m[t.member()]; }
 // a number a kernel needs per launch: itself for a level, one per member of an ensemble -- like BatchSel a kernel argument by value (512 B: no
 // copy and no synchronisation maintains it)

@@ -152,6 +152,20 @@ def nest_tag_subsets(subsets):
     return res
 
 
+def ibc(kind, **params):
+    """suhmo_ibc_t for init_ibc / set_ibc: kind "basic", "sqrt", "valley" or "dino" (the reference's problem_type) and the values its formulas
+    read -- slope, ice_height (m_H), gap_init, rho_i, rho_w, gravity, G, L, gamma (valley).  Defaults: synthetic's constants, suite A's G and L,
+    slope 0, ice_height 5000, gap_init 0.01, gamma 0.05"""
+    p = dict(slope=0.0, ice_height=5000.0, gap_init=0.01, rho_i=sy.RHO_I, rho_w=sy.RHO_W, gravity=sy.GRAV, G=sy.A3_MODEL["G"], L=sy.A3_MODEL["L"],
+             gamma=0.05)
+    unknown = set(params) - set(p)
+    if unknown:
+        raise ValueError("ibc: unknown parameter(s) %s" % sorted(unknown))
+    p.update(params)
+    k = capi.IBC_KINDS[kind] if isinstance(kind, str) else int(kind)
+    return capi.Ibc(k, *[float(p[q]) for q in ("slope", "ice_height", "gap_init", "rho_i", "rho_w", "gravity", "G", "L", "gamma")])
+
+
 ALL_LEVELS = 8          # max_level of a run or a tag_and_regrid that is given none: a hierarchy has at most 8 levels
 
 
@@ -204,6 +218,11 @@ class HipModel:
         L.set(lv.F_ACOEF, np.zeros((self.ny, self.nx)))
         for k, fid in (("B", lv.F_B), ("Pi", lv.F_PI), ("zb", lv.F_ZB), ("mask", lv.F_MASK)):
             L.set(fid, f[k], ghosted=True)
+
+    def init_ibc(self, ibc):
+        """the initial state evaluated on the device (suhmo_level_ibc_init): initializeData and setup_iceMask of the reference's IBC class
+        `ibc` (model.ibc(kind, ...)) in one launch -- head, B, Pi, zb, mask, zs, Pw, mR; nothing is loaded from the host"""
+        check(capi.lib().suhmo_level_ibc_init(self.level.h, C.byref(ibc) if ibc is not None else None, self.level.stream))
 
     def moulin_source(self, positions, sigma, flux, time_factor=1.0):
         """Calc_moulin_integral + Calc_moulin_source_term_distributed (src/AmrHydro.cpp:1866-2066) -> F_MSRC; returns the integrals"""
@@ -357,6 +376,15 @@ class HipBatchModel:
 
     def set_state(self, k, f):
         self.members[k].set_state(f)
+
+    def init_ibc_all(self, ibcs, active=None):
+        """the initial state of every (active) member on the device in one launch (suhmo_batch_ibc_init): ibcs = one model.ibc(...) per member
+        -- the same kind, any parameters, e.g. SHMIP E's five gammas -- or one for all"""
+        rows = list(ibcs) if isinstance(ibcs, (list, tuple)) else [ibcs] * self.n
+        if len(rows) != self.n:
+            raise ValueError("init_ibc_all: %d rows for %d members" % (len(rows), self.n))
+        arr = (capi.Ibc * self.n)(*rows)
+        check(capi.lib().suhmo_batch_ibc_init(self.batch.h, arr, self._active(active), self.batch.stream))
 
     def set_model(self, k, **changes):
         """change model parameters of member k between steps (e.g. ramp)"""
@@ -633,6 +661,20 @@ class HipHierModel:
             for k, st in enumerate(bl):
                 self.set_state(l, k, st)
 
+    def init_ibc(self, ibc):
+        """the initial state of every box of every level evaluated on the device (suhmo_hier_ibc_init): one launch per level, then the
+        ghost fills of initData; nothing is loaded from the host"""
+        check(capi.lib().suhmo_hier_ibc_init(self.hier.h, C.byref(ibc) if ibc is not None else None, self.hier.stream))
+
+    def set_ibc(self, ibc):
+        """keep `ibc` on the hierarchy (suhmo_hier_set_ibc; None clears it): regrid, tag_and_regrid and run then evaluate initializeBed /
+        initializePi / setup_iceMask on every new level on the device, inside the regrid, and `reload` may stay None"""
+        check(capi.lib().suhmo_hier_set_ibc(self.hier.h, C.byref(ibc) if ibc is not None else None))
+
+    def ibc_reload(self, level):
+        """suhmo_hier_ibc_reload: the reload of one level >= 1 with the IBC set_ibc left (what regrid does per new level)"""
+        check(capi.lib().suhmo_hier_ibc_reload(self.hier.h, int(level), self.hier.stream))
+
     def timestep(self, dt):
         self.cur_step += 1
         pi, nv = C.c_int(), C.c_int()
@@ -680,7 +722,7 @@ class HipHierModel:
         model parameters and cur_step stay.  self.hier wraps the new handle afterwards and self.level holds the new boxes' views.
         reload(l, k, box) -> dict as set_state takes it, possibly partial (head, B, Pi, zb, mask: ghosted arrays of the box), or None: called
         for every new box after the transfer and loaded over the transferred values -- the place of initializeBed / initializePi /
-        setup_iceMask (:4387-4437); the IBCs stay the caller's.
+        setup_iceMask (:4387-4437).  With an IBC on the hierarchy (set_ibc) that evaluation has already run on the device, inside the regrid; a reload that is given runs after it.
         THE MASK: a transferred ice mask is INTERPOLATED and therefore not +-1 along an ice margin.  The reference does not keep it either:
         it recomputes the mask from Pi after every regrid (setup_iceMask, :4436).  A caller whose domain has a margin must do the same in
         `reload` (return "mask" for every box); where the mask is +1 everywhere the transferred one is exact.

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """cfg5 (exec/AMR_multiMoulins physics) time step on base + 3 AMR levels of box unions: ms per step.
-    python tools/hier_bench.py [--generated-grids] [--regrid-interval N [--one-call [--plot-interval P] [--balance-every B]]] [--recharge] [--snapshot] [--flatten] [--compare] [base cells per side] [steps]
+    python tools/hier_bench.py [--generated-grids] [--regrid-interval N [--device-ibc] [--one-call [--plot-interval P] [--balance-every B]]] [--recharge] [--snapshot] [--flatten] [--compare] [base cells per side] [steps]
 --compare: the L1, L2 and max norms of the reference's two components against a single level on the uniform grid of level 4 (random fields), on the
 hierarchy --flatten uses: suhmo_hier_compare in both modes (HipHier.compare: composite, finest), in alternating rounds with the two routes that
 existed before it -- one flatten to the host and the norms in numpy; the per-box get calls and, box by box, the block means and norms in numpy
@@ -16,6 +16,12 @@ data (a copy per box and field), three alternating rounds, with the launch and c
 --balance-every B (with --one-call): both loops also take the water budget of every level after every B-th step ("WATER BUDGET", include/suhmo_hip.h):
 the one call as the series inside the run (no copy and no synchronisation per row, one copy per run call), the per-call loop with mass_balance
 before the step (Bold) and water_budget after it.
+--device-ibc (with --regrid-interval N): the same regridding time loop on two models set up alike -- one whose regrids call the host `reload` (the
+dino's initializePi and setup_iceMask in numpy on every new box, pushed through the per-box set calls), one with the IBC on the handle
+(HipHierModel.set_ibc: the reload runs on the device inside suhmo_hier_regrid) -- and the time per grid-changing regrid of either, the regrid call
+with its reload between two synchronisations.  The two routes differ in the ghost cells (the host route loads the formula's, the device route
+fills them as the reference does), so the states are not compared.  The callback writes the dino's b = 1e-16 only on boxes where Pi == 0 occurs, which
+is none on this domain; the device body tests every cell.
 --one-call (with --regrid-interval N): the same regridding time loop twice in one process, on two models set up alike -- the per-call loop
 (HipHierModel.tag_and_regrid, moulin_source, timestep) and HipHierModel.run (suhmo_hier_run: one call per stretch of steps that begins with a
 regrid, so that the thresholds can alternate as below) -- in alternating rounds of [steps] steps; prints ms per step and ms per regrid interval of
@@ -36,11 +42,12 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from suhmo_amd import model, synthetic as sy
 generated = "--generated-grids" in sys.argv
 one_call = "--one-call" in sys.argv
+device_ibc = "--device-ibc" in sys.argv
 recharge = "--recharge" in sys.argv
 snapshot = "--snapshot" in sys.argv
 flatten = "--flatten" in sys.argv
 compare = "--compare" in sys.argv
-argv = [a for a in sys.argv[1:] if a not in ("--generated-grids", "--one-call", "--recharge", "--snapshot", "--flatten", "--compare")]
+argv = [a for a in sys.argv[1:] if a not in ("--generated-grids", "--one-call", "--device-ibc", "--recharge", "--snapshot", "--flatten", "--compare")]
 balance_every = 0
 if "--balance-every" in argv:
     q = argv.index("--balance-every")
@@ -222,6 +229,51 @@ def timed_regrid(H, n, first):
 
 boxes = generated_boxes() if generated else sy.boxes_around(mo["positions"], nb, nb, 4, 1.0e5, 1.0e5)
 sts = sy.mountain_amrm_states(nb, nb, boxes)
+
+
+def device_ibc_rounds():
+    """the regridding loop with the host `reload` and with the IBC on the handle: time per grid-changing regrid"""
+    import numpy as np
+
+    def host_reload(l, k, b):
+        # MountainIBC::initializePi + setup_iceMask on the ghosted box (src/MountainSetupIBC.cpp:89-108), as a caller's callback evaluates them
+        d = 1.0e5 / (nb << l)
+        X, Y = np.meshgrid((np.arange(b[0] - 1, b[2] + 2) + 0.5) * d, (np.arange(b[1] - 1, b[3] + 2) + 0.5) * d)
+        zs = 2.0 * (1.5e-3 * X + -1.5e-3 * Y + 100.0 + 100.0)
+        Pi = sy.RHO_I * sy.GRAV * np.maximum(zs, 0.0)
+        f = dict(Pi=np.ascontiguousarray(Pi), zs=np.ascontiguousarray(zs), mask=np.where(Pi > 0.0, 1.0, -1.0))
+        if (Pi == 0.0).any():               # b = 1e-16 where Pi == 0 (:105-107): the transferred gap height read back, changed, loaded again.  On this
+            f["B"] = np.where(Pi == 0.0, 1.0e-16, M.get(l, k, "B", ghosted=True))      # domain the ice never ends, so no box takes this branch
+        return f
+
+    for name in ("host reload", "device IBC"):
+        M = model.HipHierModel(nb, nb, sts[0][0]["dx"], sts[0][0]["dy"], bc, ph, mm, boxes, max_box=64)
+        M.set_states(sts)
+        M.moulin_source(**mo)
+        if name == "device IBC":
+            M.set_ibc(model.ibc("dino"))
+        sync = lambda: M.level[0][0].synchronize()
+        peak = float(M.get(0, 0, "msrc").max())
+        times, nbox = [], []
+        for n in range(nstep):
+            M.timestep(mm["dt"])
+            if (n + 1) % regrid_interval:
+                continue
+            scale = (1.0, 0.6)[((n + 1) // regrid_interval) % 2]
+            M.clear_tags()
+            for l in range(min(M.hier.nlev, 3)):
+                M.tag_cells(l, "msrc", scale * (0.01, 0.1, 0.5)[l] * peak, 1.0e300, grow=4, granularity=GRID_PARAMS["block_factor"] // 2)
+            new, same = M.generate_grids(**GRID_PARAMS)
+            if same:
+                continue
+            sync(); t0 = time.perf_counter()
+            M.regrid(new, reload=host_reload if name == "host reload" else None)
+            sync(); times.append(time.perf_counter() - t0)
+            nbox.append(sum(len(bl) for bl in new))
+            M.moulin_source(**mo)
+        print("%-12s: %d grid-changing regrids of %d steps, %s new boxes: %.2f ms per regrid (min %.2f, max %.2f)"
+              % (name, len(times), nstep, nbox, 1e3 * sum(times) / max(1, len(times)), 1e3 * min(times or [0.0]), 1e3 * max(times or [0.0])), flush=True)
+        M.close()
 
 
 def one_call_rounds(rounds=3):
@@ -492,6 +544,10 @@ if flatten:
     sys.exit(0)
 if compare:
     compare_bench()
+    sys.exit(0)
+if device_ibc:
+    assert regrid_interval > 0, "--device-ibc needs --regrid-interval"
+    device_ibc_rounds()
     sys.exit(0)
 if one_call:
     assert regrid_interval > 0, "--one-call needs --regrid-interval"
